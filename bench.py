@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- committed log slots / second of the fused Phase-2 step on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 Workload (BASELINE.json metric; SURVEY.md section 8d "steady"): a "step" is one fused pass
@@ -271,6 +271,16 @@ def replica_axis_row(fa, dist, backend, dev, rank, world, local_rank, ballot_mod
     }
 
 
+def dump_outputs(out_dir, step, lo, hi):
+    """--dump-outputs: the Chosen records one headline step returns to its caller, the slots [lo, hi) of its batch, as
+    float64 (int32 rounds and values are exact in it): 3 x 8 B x 2^20 slots = 24 MiB.  The inputs are a function of the
+    arguments alone, so two builds run with the same arguments can be compared file for file."""
+    _, _, _, ch, cr, cv = step
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in (("chosen", ch), ("chosen_round", cr), ("chosen_value", cv)):
+        np.save(os.path.join(out_dir, name + ".npy"), t[lo:hi].cpu().numpy().astype(np.float64))
+
+
 def sig(x, digits=5):
     """a float rounded to `digits` significant digits (the line is kept short: the driver keeps 8 KB of it)"""
     if x is None or isinstance(x, (bool, int)):
@@ -465,7 +475,12 @@ def main():
                     help="honour the FPX_BENCH_* test hooks of tests/test_bench_distributed.py (refused without this flag)")
     ap.add_argument("--replica-row-steps", type=int, default=5,
                     help="N > 1, --shard group: steps of the extra replica-axis row (0 = skip it)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="headline only: after the timed steps, write what the last timed step returned to its caller (the "
+                         "Chosen records: chosen flag, round, value per slot; rank 0's slots at N > 1) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.dump_outputs and args.config != "headline":
+        raise SystemExit("bench.py: --dump-outputs covers the headline workload (--config headline)")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` by itself: become N ranks (one per GPU) under torch.distributed.run.
@@ -645,6 +660,8 @@ def main():
         assert bool((cv[lo:hi] == val[lo:hi]).all()), "step %d: chosen value != proposed value" % i
         assert bool((cr[lo:hi] == rnd[lo:hi]).all()), "step %d: chosen round != proposing round" % i
     assert committed == K * (hi - lo), (committed, K * (hi - lo))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, steps[Wm + K - 1], lo, hi)
     if dist is not None:
         t = torch.tensor([committed], dtype=torch.int64, device=dev)
         all_reduce(t, dist.ReduceOp.SUM)

@@ -350,33 +350,38 @@ def test_range_tallies_are_reclaimed(fa, oracle):
 
 
 @pytest.mark.gpu
-def test_slot_major_flag_gives_the_same_state(fa, oracle):
+def test_slot_major_flag_gives_the_same_state(fa, oracle, row_layout, monkeypatch):
     """FPX_F_SLOT_MAJOR_ROWS (include/fpx.h) changes where a slot's row lives, nothing else: commands, noop ranges,
-    garbage collection and recycling on two contexts that differ only in the flag, and on the oracle"""
-    import os
-    if os.environ.get("FPX_SLOT_MAJOR"):
-        pytest.skip("the environment switch overrides the flag")
+    garbage collection and recycling on two contexts that differ only in the flag, and on the oracle.  The context
+    without the flag is created without the FPX_SLOT_MAJOR switch, so that its rows stay leader-group-major; under the
+    slot-major layout a third context, without the flag, takes its slot-major rows from the switch."""
     S, L = 1 << 14, 8
     kw = dict(num_slots=S, num_replicas=3, num_groups=2, num_leader_groups=L, f=1, tally_ways=8)
-    a, b = fa.Context(fa.make_config(**kw)), fa.Context(fa.make_config(flags=fa.FPX_F_SLOT_MAJOR_ROWS, **kw))
+    with monkeypatch.context() as m:
+        m.delenv("FPX_SLOT_MAJOR", raising=False)
+        a = fa.Context(fa.make_config(**kw))
+    ctxs = [a, fa.Context(fa.make_config(flags=fa.FPX_F_SLOT_MAJOR_ROWS, **kw))]
+    if row_layout == "slot-major":
+        ctxs.append(fa.Context(fa.make_config(**kw)))
     ref = oracle.System(oracle.make_config(**kw))
     rng = np.random.default_rng(77)
     for step in range(6):
         slots = np.unique(rng.integers(0, S, 3000)).astype(np.int32)
         rr = np.full(len(slots), step // 3, np.int32)
         tm = W.bits_from_bool(W.random_subsets(rng, len(slots), 3, 1, 3))
-        outs = [W.run_script(x, [("fused", slots, rr, slots * 7 + step, tm)]) for x in (a, b, ref)]
-        W.assert_same_outputs(outs[0], outs[2])
-        W.assert_same_outputs(outs[1], outs[2])
+        script = [("fused", slots, rr, slots * 7 + step, tm)]
+        want = W.run_script(ref, script)
+        for x in ctxs:
+            W.assert_same_outputs(W.run_script(x, script), want)
         start, end, rnd = _random_range_batch(rng, S, L, 60, [step // 3] * L)
-        ra, rb, rc = (x.noop_ranges_fused(start, end, rnd) for x in (a, b, ref))
-        _same_ranges(ra, rc)
-        _same_ranges(rb, rc)
+        want = ref.noop_ranges_fused(start, end, rnd)
+        for x in ctxs:
+            _same_ranges(x.noop_ranges_fused(start, end, rnd), want)
         if step == 3:
-            for x in (a, b, ref):
+            for x in ctxs + [ref]:
                 x.proxy_forget(100, S // 3)
                 x.recycle_slots(S // 2 + 3, 1000)
-    for x in (a, b):
+    for x in ctxs:
         W.assert_same_state(x, ref, tally_slots=range(0, S, 37))
         np.testing.assert_array_equal(x.state_digest(), ref.state_digest())
 
@@ -416,16 +421,15 @@ def test_slot_ordered_batches_are_walked_by_column(fa, oracle, L, A, R):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("L", [2048, 1500])
-def test_row_sweep_fill_with_two_thousand_leader_groups(fa, oracle, L):
+def test_row_sweep_fill_with_two_thousand_leader_groups(fa, oracle, row_layout, L):
     """on slot-ordered rows (FPX_F_SLOT_MAJOR_ROWS) the noop-range fill that sweeps 8 log rows with an LDS
     ownership map (k_ranges_fill_rows) needs 8 x L x 4 B of dynamic LDS + its static words: beyond the default 64 KiB at
-    L close to 2048 -- without the opt-in every fused range call failed with FPX_EHIP instead of working"""
-    import os
-    if os.environ.get("FPX_SLOT_MAJOR"):
-        pytest.skip("the environment switch overrides the flag")
+    L close to 2048 -- without the opt-in every fused range call failed with FPX_EHIP instead of working.  The rows are
+    slot-ordered by the flag, or under the slot-major layout by the FPX_SLOT_MAJOR switch alone."""
     S = L * 16
     kw = dict(num_slots=S, num_replicas=3, num_groups=1, num_leader_groups=L, f=1, tally_ways=4)
-    gpu, ref = fa.Context(fa.make_config(flags=fa.FPX_F_SLOT_MAJOR_ROWS, **kw)), oracle.System(oracle.make_config(**kw))
+    flags = 0 if row_layout == "slot-major" else fa.FPX_F_SLOT_MAJOR_ROWS
+    gpu, ref = fa.Context(fa.make_config(flags=flags, **kw)), oracle.System(oracle.make_config(**kw))
     rng = np.random.default_rng(L)
     for step in range(3):
         start, end, rnd = _random_range_batch(rng, S, L, 300, [step] * L)
