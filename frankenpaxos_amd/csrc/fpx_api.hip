@@ -13,8 +13,10 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <new>
 #include <set>
+#include <type_traits>
 #include <vector>
 
 #include "fpx_kernels.hpp"
@@ -68,6 +70,12 @@ struct HostSlot {
   int n = 0;
 };
 
+// host staging of a range batch (host_ranges): int32 start / end / round / entry / nack_round, u8 is_new / chosen, and
+// num_groups x 4 words of target / vote / nack bits per range
+struct RangeStage {
+  DevBuf start, end, round, entry, nack_round, is_new, chosen, target, votes, nacks;
+};
+
 struct fpx_ctx {
   fpx_config cfg;
   Geom g;
@@ -115,19 +123,19 @@ struct fpx_ctx {
   // the events of the K1 / K3 launch being enqueued: they ride on the kernel's own dispatch packet (hipExtLaunchKernelGGL),
   // so a timed launch puts no marker packets on the stream (two hipEventRecords per launch cost 5 - 15 us of a step)
   hipEvent_t ev_start = nullptr, ev_stop = nullptr;
-  // host-pointer K3 on big batches: upload / K3 / download of consecutive pieces overlap on three streams
-  hipStream_t up_stream = nullptr, down_stream = nullptr;
+  // host-pointer K3 on page-locked arrays: the inputs go up on a stream of their own (host_submit)
+  hipStream_t up_stream = nullptr;
   HostSlot* hslots = nullptr;  // calls in flight on page-locked arrays (host_submit / host_wait)
   int hnext = 0;
-  std::vector<hipEvent_t> pipe_ev;  // [2 * pieces]: uploaded, computed
-  int32_t index_base = 0;           // message index of the piece being launched (error reports are batch-relative)
+  int32_t index_base = 0;  // message index of the run being launched in its host batch (error reports are batch-relative)
   bool lazy_active = false;  // PER_SLOT: lazy Phase1a promises may be outstanding (k_phase2 runs its lazy-aware form)
   bool packed_pass = false;  // the launch being enqueued is the packed walk over runs of acceptors (k_phase2 MODE 3)
   DevBuf d_run_done;         // one byte per chunk: taken by the packed walk
   // K4: the proxy leader's noop-range tallies (two buffers: fpx_proxy_forget rehashes into the other one)
   RangeTable rt[2];
   int rt_cur = 0;
-  DevBuf d_rng;  // staging of range batches
+  DevBuf d_rng;     // scratch of device range batches (fpx_noop_ranges_fused_dev)
+  RangeStage rng;  // staging of host range batches
   // fpx_mencius_band_fused_dev: the ranges' half of an independent step runs here, between a fork and a join event
   hipStream_t band_stream = nullptr;
   int64_t band_merged_steps = 0;
@@ -417,12 +425,17 @@ int launch_check(fpx_ctx* ctx) {
   return FPX_OK;
 }
 
-// While a host entry point drives its own device runs the run contract holds by construction
-// (split_runs), so the device-side validation pass is skipped.
-struct HostRun {
+// The per-context flags that steer the launches of a host batch, set for the batch and cleared on every way out: a flag
+// left set would change every later call on the context.  cut_on_host: the host cut the batch into runs (split_runs), so
+// the run contract holds by construction and the device-side validation pass is skipped; otherwise the batch is validated
+// on the device even under FPX_F_TRUSTED (that flag is a promise about _dev batches only).  index_base is the message
+// index of the run being launched.
+struct HostFlags {
   fpx_ctx* ctx;
-  explicit HostRun(fpx_ctx* c) : ctx(c) { ctx->host_validated = true; }
-  ~HostRun() { ctx->host_validated = false; }
+  HostFlags(fpx_ctx* c, bool cut_on_host) : ctx(c) { (cut_on_host ? ctx->host_validated : ctx->force_validate) = true; }
+  ~HostFlags() { ctx->host_validated = ctx->force_validate = false, ctx->index_base = 0; }
+  HostFlags(const HostFlags&) = delete;
+  HostFlags& operator=(const HostFlags&) = delete;
 };
 
 // validation pass of one device run (skipped with FPX_F_TRUSTED)
@@ -934,16 +947,17 @@ void free_state(fpx_ctx* ctx) {
                 ctx->rt[1].key, ctx->rt[1].bits, ctx->rt[1].owner, ctx->rt[1].count, ctx->d_rng.p, ctx->d_run_done.p};
   for (void* p : ps)
     if (p) (void)hipFree(p);
+  RangeStage& rs = ctx->rng;
   DevBuf* bs[] = {&ctx->d_slot,   &ctx->d_round, &ctx->d_value, &ctx->d_target, &ctx->d_bits_a, &ctx->d_bits_b,
-                  &ctx->d_i32_a,  &ctx->d_i32_b, &ctx->d_i32_c, &ctx->d_u8,     &ctx->d_scratch};
+                  &ctx->d_i32_a,  &ctx->d_i32_b, &ctx->d_i32_c, &ctx->d_u8,     &ctx->d_scratch,
+                  &rs.start,      &rs.end,       &rs.round,     &rs.entry,      &rs.nack_round, &rs.is_new,
+                  &rs.chosen,     &rs.target,    &rs.votes,     &rs.nacks};
   for (DevBuf* b : bs)
     if (b->p) (void)hipFree(b->p);
   for (hipEvent_t e : ctx->ev) (void)hipEventDestroy(e);
   ctx->ev.clear();
   for (hipEvent_t e : ctx->cev) (void)hipEventDestroy(e);
   ctx->cev.clear();
-  for (hipEvent_t e : ctx->pipe_ev) (void)hipEventDestroy(e);
-  ctx->pipe_ev.clear();
   if (ctx->hslots) {
     for (int k = 0; k < HOST_DEPTH; ++k) {
       HostSlot& h = ctx->hslots[k];
@@ -963,7 +977,6 @@ void free_state(fpx_ctx* ctx) {
   if (ctx->band_stream) (void)hipStreamDestroy(ctx->band_stream);
   if (ctx->d_band.p) (void)hipFree(ctx->d_band.p);
   if (ctx->up_stream) (void)hipStreamDestroy(ctx->up_stream);
-  if (ctx->down_stream) (void)hipStreamDestroy(ctx->down_stream);
   if (ctx->d_part.p) (void)hipFree(ctx->d_part.p);
   if (ctx->d_mine.p) (void)hipFree(ctx->d_mine.p);
   if (ctx->own_stream) (void)hipStreamDestroy(ctx->own_stream);
@@ -1080,130 +1093,66 @@ int d2h(fpx_ctx* ctx, T* dst, const DevBuf& b, size_t count) {
 }
 
 
-// ---- host-pointer K3 helpers --------------------------------------------------------------------------------
-// the host-split replay of [from, n) of a staged batch (the slices are still in the staging buffers): cut into
-// runs on the host, launch them back to back, download that part of the outputs
-int host_fused_replay(fpx_ctx* ctx, int n, const int32_t* slot, const int32_t* round, bool has_target, int from,
-                      uint8_t* chosen, int32_t* chosen_round, int32_t* chosen_value, int32_t* nack_round) {
-  int32_t *d_slot = (int32_t*)ctx->d_slot.p, *d_round = (int32_t*)ctx->d_round.p, *d_value = (int32_t*)ctx->d_value.p;
-  uint64_t* d_target = has_target ? (uint64_t*)ctx->d_target.p : nullptr;
-  uint8_t* d_ch = (uint8_t*)ctx->d_u8.p;
-  int32_t *d_cr = (int32_t*)ctx->d_i32_a.p, *d_cv = (int32_t*)ctx->d_i32_b.p, *d_nr = (int32_t*)ctx->d_i32_c.p;
-  const int len_all = n - from;
+// ---- host batches: stage, cut into runs, run, copy back ----------------------------------------------------------
+// The arrays of a host batch: `bytes` per message in the caller's array and in its staging buffer.  An input whose
+// array is NULL is neither uploaded nor staged; every output is staged, and downloaded when its array is not NULL.
+struct HostIn {
+  DevBuf* buf;
+  const void* src;
+  size_t bytes;
+};
+struct HostOut {
+  DevBuf* buf;
+  void* dst;
+  size_t bytes;
+};
+
+// message i of a staging buffer of T
+template <typename T>
+T* staged(const DevBuf& b, size_t i) {
+  return (T*)b.p + i;
+}
+
+// The driver of the host-pointer entry points.  Uploads the inputs and grows the outputs; then cut(&cuts) checks the
+// batch on the host -- behind the uploads, so with page-locked arrays the CPU pass overlaps the DMA; nothing is launched
+// on a bad batch -- and cuts it into runs that satisfy the run contract; run(lo, len) launches messages [lo, lo + len)
+// with ctx->index_base = lo, the runs back to back (= message-at-a-time delivery in array order); then the outputs come
+// down and the device's status is returned.  cut == nullptr: the whole batch is ONE run, validated on the device.
+template <typename Cut, typename Run>
+int host_batch(fpx_ctx* ctx, int n, std::initializer_list<HostIn> in, std::initializer_list<HostOut> out, Cut cut,
+               Run run) {
+  constexpr bool cut_on_host = !std::is_null_pointer<Cut>::value;
   int rc;
-  if ((rc = check_inputs(ctx, len_all, slot + from, round + from))) {
-    ctx->err_index += from;
-    return rc;
+  for (const HostIn& a : in)
+    if (a.src && (rc = h2d(ctx, a.buf, (const char*)a.src, (size_t)n * a.bytes))) return rc;
+  for (const HostOut& a : out)
+    if ((rc = grow(ctx, a.buf, (size_t)n * a.bytes))) return rc;
+  std::vector<int> cuts{0, n};
+  if constexpr (cut_on_host) {
+    if ((rc = cut(&cuts))) return rc;
   }
-  HostRun host_run(ctx);
-  std::vector<int> cuts;
-  split_runs(ctx, len_all, slot + from, round + from, true, &cuts);
-  for (size_t k = 0; k + 1 < cuts.size(); ++k) {
-    const int lo = from + cuts[k], len = cuts[k + 1] - cuts[k];
-    ctx->index_base = lo;
-    rc = fpx_phase2_fused_dev(ctx, len, d_slot + lo, d_round + lo, d_value + lo,
-                              d_target ? d_target + (size_t)lo * 4 : nullptr, d_ch + lo, d_cr + lo, d_cv + lo, d_nr + lo);
-    ctx->index_base = 0;
-    if (rc) {
-      (void)hipStreamSynchronize(ctx->stream);
-      return rc;
+  {
+    HostFlags flags(ctx, cut_on_host);
+    for (size_t k = 0; k + 1 < cuts.size(); ++k) {
+      ctx->index_base = cuts[k];
+      if ((rc = run(cuts[k], cuts[k + 1] - cuts[k]))) {
+        (void)hipStreamSynchronize(ctx->stream);
+        return rc;
+      }
     }
   }
-  const size_t cnt = (size_t)len_all;
-  if (chosen) HIPCHK(ctx, hipMemcpyAsync(chosen + from, d_ch + from, cnt, hipMemcpyDeviceToHost, ctx->stream));
-  if (chosen_round) HIPCHK(ctx, hipMemcpyAsync(chosen_round + from, d_cr + from, cnt * 4, hipMemcpyDeviceToHost, ctx->stream));
-  if (chosen_value) HIPCHK(ctx, hipMemcpyAsync(chosen_value + from, d_cv + from, cnt * 4, hipMemcpyDeviceToHost, ctx->stream));
-  if (nack_round) HIPCHK(ctx, hipMemcpyAsync(nack_round + from, d_nr + from, cnt * 4, hipMemcpyDeviceToHost, ctx->stream));
+  for (const HostOut& a : out)
+    if ((rc = d2h(ctx, (char*)a.dst, *a.buf, (size_t)n * a.bytes))) return rc;
   return fetch_status(ctx);
 }
 
-// piece size of the pipelined host path.  OFF unless FPX_HOST_PIECE is set: measured on two boxes
-// (profiles/r02_host_path.txt) the three-stream pipeline buys nothing over upload -> K3 -> download in sequence --
-// 1.90-2.07 ms against 1.96 ms per 2^20 messages on the slow-PCIe box -- as in round 1: the host copies do not
-// overlap a kernel that saturates HBM on this stack.  At most 64 pieces.
-int host_piece(const fpx_ctx* ctx, int n) {
-  (void)ctx;
-  const char* e = getenv("FPX_HOST_PIECE");
-  if (!e || !*e) return n > 0 ? n : 1;
-  int piece = std::max(1024, atoi(e));
-  while ((long long)piece * 64 < n) piece <<= 1;
-  return piece;
-}
-
-// Big host batches: the three stages of the host-pointer K3 -- upload (12 B per message), the fused step, download
-// (13 B per message) -- run as a pipeline over pieces on three streams (opt-in, see host_piece).  Pieces are
-// separate device runs, launched in order on the context's stream: sequential semantics across pieces for free.
-// Range errors are found on the host BEFORE anything is launched (FPX_EINVAL => nothing applied, as ever); a run
-// -contract violation inside a piece aborts that piece and everything after it on the device, and the host-split
-// replay takes over from that piece's first message.
-int host_fused_pipelined(fpx_ctx* ctx, int n, const int32_t* slot, const int32_t* round, const int32_t* value_id,
-                         const uint64_t* target_mask, uint8_t* chosen, int32_t* chosen_round, int32_t* chosen_value,
-                         int32_t* nack_round) {
-  int rc;
-  if ((rc = check_inputs(ctx, n, slot, round))) return rc;
-  ctx->batch_increasing = ctx->batch_one_round = false;
-  if ((rc = grow(ctx, &ctx->d_slot, (size_t)n * 4))) return rc;
-  if ((rc = grow(ctx, &ctx->d_round, (size_t)n * 4))) return rc;
-  if ((rc = grow(ctx, &ctx->d_value, (size_t)n * 4))) return rc;
-  if (target_mask && (rc = grow(ctx, &ctx->d_target, (size_t)n * 32))) return rc;
-  const int piece = host_piece(ctx, n), pieces = (n + piece - 1) / piece;
-  if (!ctx->up_stream) HIPCHK(ctx, hipStreamCreateWithFlags(&ctx->up_stream, hipStreamNonBlocking));
-  if (!ctx->down_stream) HIPCHK(ctx, hipStreamCreateWithFlags(&ctx->down_stream, hipStreamNonBlocking));
-  while (ctx->pipe_ev.size() < (size_t)2 * pieces) {
-    hipEvent_t e;
-    HIPCHK(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    ctx->pipe_ev.push_back(e);
-  }
-  int32_t *d_slot = (int32_t*)ctx->d_slot.p, *d_round = (int32_t*)ctx->d_round.p, *d_value = (int32_t*)ctx->d_value.p;
-  uint64_t* d_target = target_mask ? (uint64_t*)ctx->d_target.p : nullptr;
-  uint8_t* d_ch = (uint8_t*)ctx->d_u8.p;
-  int32_t *d_cr = (int32_t*)ctx->d_i32_a.p, *d_cv = (int32_t*)ctx->d_i32_b.p, *d_nr = (int32_t*)ctx->d_i32_c.p;
-  // every early return below (HIPCHK) must leave the context as it found it: a FPX_F_TRUSTED context that kept
-  // force_validate / index_base would silently validate and report shifted indices ever after
-  struct PieceGuard {
-    fpx_ctx* c;
-    ~PieceGuard() { c->force_validate = false, c->index_base = 0; }
-  } _pg{ctx};
-  ctx->force_validate = true;
-  for (int k = 0; k < pieces && rc == FPX_OK; ++k) {
-    const int lo = k * piece, len = std::min(piece, n - lo);
-    const size_t c = (size_t)len;
-    hipEvent_t up = ctx->pipe_ev[2 * k], done = ctx->pipe_ev[2 * k + 1];
-    HIPCHK(ctx, hipMemcpyAsync(d_slot + lo, slot + lo, c * 4, hipMemcpyHostToDevice, ctx->up_stream));
-    HIPCHK(ctx, hipMemcpyAsync(d_round + lo, round + lo, c * 4, hipMemcpyHostToDevice, ctx->up_stream));
-    HIPCHK(ctx, hipMemcpyAsync(d_value + lo, value_id + lo, c * 4, hipMemcpyHostToDevice, ctx->up_stream));
-    if (target_mask)
-      HIPCHK(ctx, hipMemcpyAsync(d_target + (size_t)lo * 4, target_mask + (size_t)lo * 4, c * 32, hipMemcpyHostToDevice, ctx->up_stream));
-    HIPCHK(ctx, hipEventRecord(up, ctx->up_stream));
-    HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, up, 0));
-    ctx->index_base = lo;
-    rc = fpx_phase2_fused_dev(ctx, len, d_slot + lo, d_round + lo, d_value + lo, d_target ? d_target + (size_t)lo * 4 : nullptr,
-                              d_ch + lo, d_cr + lo, d_cv + lo, d_nr + lo);
-    ctx->index_base = 0;
-    if (rc) break;
-    HIPCHK(ctx, hipEventRecord(done, ctx->stream));
-    HIPCHK(ctx, hipStreamWaitEvent(ctx->down_stream, done, 0));
-    if (chosen) HIPCHK(ctx, hipMemcpyAsync(chosen + lo, d_ch + lo, c, hipMemcpyDeviceToHost, ctx->down_stream));
-    if (chosen_round) HIPCHK(ctx, hipMemcpyAsync(chosen_round + lo, d_cr + lo, c * 4, hipMemcpyDeviceToHost, ctx->down_stream));
-    if (chosen_value) HIPCHK(ctx, hipMemcpyAsync(chosen_value + lo, d_cv + lo, c * 4, hipMemcpyDeviceToHost, ctx->down_stream));
-    if (nack_round) HIPCHK(ctx, hipMemcpyAsync(nack_round + lo, d_nr + lo, c * 4, hipMemcpyDeviceToHost, ctx->down_stream));
-  }
-  ctx->force_validate = false;
-  (void)hipStreamSynchronize(ctx->up_stream);
-  const hipError_t dsync = hipStreamSynchronize(ctx->down_stream);
-  if (rc) {
-    (void)hipStreamSynchronize(ctx->stream);
+// the cuts of a host batch of messages: the range check (the first offender for fpx_error_detail), then split_runs
+auto message_runs(fpx_ctx* ctx, int n, const int32_t* slot, const int32_t* round, bool check_round) {
+  return [=](std::vector<int>* cuts) {
+    const int rc = check_inputs(ctx, n, slot, round);
+    if (rc == FPX_OK) split_runs(ctx, n, slot, round, check_round, cuts);
     return rc;
-  }
-  rc = fetch_status(ctx);
-  if (dsync != hipSuccess) {
-    ctx->last_hip = (int)dsync;
-    return FPX_EHIP;
-  }
-  if (rc != FPX_EORDER) return rc;
-  // the piece that holds the first offender and everything after it applied nothing: replay from its first message
-  const int from = (ctx->err_index / piece) * piece;
-  return host_fused_replay(ctx, n, slot, round, target_mask != nullptr, from, chosen, chosen_round, chosen_value, nack_round);
+  };
 }
 
 // ---- page-locked host batches (fpx_phase2_fused_submit / _wait) ------------------------------------------------------
@@ -1275,11 +1224,7 @@ int host_submit(fpx_ctx* ctx, int n, const int32_t* slot, const int32_t* round, 
   HIPCHK(ctx, hipEventRecord(h.up, ctx->up_stream));
   HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, h.up, 0));
   {
-    struct Guard {
-      fpx_ctx* c;
-      ~Guard() { c->force_validate = false; }
-    } _g{ctx};
-    ctx->force_validate = true;  // also under FPX_F_TRUSTED: that flag is a promise about _dev batches only
+    HostFlags flags(ctx, false);  // one run, validated on the device
     rc = fpx_phase2_fused_dev(ctx, n, (int32_t*)h.in[0].p, (int32_t*)h.in[1].p, (int32_t*)h.in[2].p,
                               target_mask ? (uint64_t*)h.in[3].p : nullptr, (uint8_t*)dout[0], (int32_t*)dout[1],
                               (int32_t*)dout[2], (int32_t*)dout[3]);
@@ -1812,31 +1757,19 @@ int32_t fpx_acceptor_phase2a(fpx_ctx* ctx, int32_t n, const int32_t* slot, const
   if (rc) return rc;
   if (n == 0) return FPX_OK;
   if (!value_id) return FPX_EINVAL;
-  if ((rc = h2d(ctx, &ctx->d_slot, slot, n))) return rc;
-  if ((rc = h2d(ctx, &ctx->d_round, round, n))) return rc;
-  if ((rc = h2d(ctx, &ctx->d_value, value_id, n))) return rc;
-  if (target_mask && (rc = h2d(ctx, &ctx->d_target, target_mask, (size_t)n * 4))) return rc;
-  if ((rc = grow(ctx, &ctx->d_bits_a, (size_t)n * 32))) return rc;
-  if ((rc = grow(ctx, &ctx->d_bits_b, (size_t)n * 32))) return rc;
-  if ((rc = grow(ctx, &ctx->d_i32_a, (size_t)n * 4))) return rc;
-  if ((rc = check_inputs(ctx, n, slot, round))) return rc;
-  HostRun host_run(ctx);
-  std::vector<int> cuts;
-  split_runs(ctx, n, slot, round, true, &cuts);
-  for (size_t k = 0; k + 1 < cuts.size(); ++k) {
-    const int lo = cuts[k], len = cuts[k + 1] - cuts[k];
-    rc = fpx_acceptor_phase2a_dev(ctx, len, (int32_t*)ctx->d_slot.p + lo, (int32_t*)ctx->d_round.p + lo,
-                                  (int32_t*)ctx->d_value.p + lo,
-                                  target_mask ? (uint64_t*)ctx->d_target.p + (size_t)lo * 4 : nullptr,
-                                  (uint64_t*)ctx->d_bits_a.p + (size_t)lo * 4,
-                                  nack_bits ? (uint64_t*)ctx->d_bits_b.p + (size_t)lo * 4 : nullptr,
-                                  (int32_t*)ctx->d_i32_a.p + lo);
-    if (rc) return rc;
-  }
-  if ((rc = d2h(ctx, vote_bits, ctx->d_bits_a, (size_t)n * 4))) return rc;
-  if ((rc = d2h(ctx, nack_bits, ctx->d_bits_b, (size_t)n * 4))) return rc;
-  if ((rc = d2h(ctx, nack_round, ctx->d_i32_a, (size_t)n))) return rc;
-  return fetch_status(ctx);
+  return host_batch(ctx, n,
+                    {{&ctx->d_slot, slot, 4}, {&ctx->d_round, round, 4}, {&ctx->d_value, value_id, 4},
+                     {&ctx->d_target, target_mask, 32}},
+                    {{&ctx->d_bits_a, vote_bits, 32}, {&ctx->d_bits_b, nack_bits, 32}, {&ctx->d_i32_a, nack_round, 4}},
+                    message_runs(ctx, n, slot, round, true), [&](int lo, int len) {
+                      return fpx_acceptor_phase2a_dev(
+                          ctx, len, staged<int32_t>(ctx->d_slot, lo), staged<int32_t>(ctx->d_round, lo),
+                          staged<int32_t>(ctx->d_value, lo),
+                          target_mask ? staged<uint64_t>(ctx->d_target, (size_t)lo * 4) : nullptr,
+                          staged<uint64_t>(ctx->d_bits_a, (size_t)lo * 4),
+                          nack_bits ? staged<uint64_t>(ctx->d_bits_b, (size_t)lo * 4) : nullptr,
+                          staged<int32_t>(ctx->d_i32_a, lo));
+                    });
 }
 
 // Host-pointer K3.  Optimistic: the uploads are followed at once by the whole batch as ONE validated
@@ -1851,48 +1784,28 @@ int32_t fpx_phase2_fused(fpx_ctx* ctx, int32_t n, const int32_t* slot, const int
   if (rc) return rc;
   if (n == 0) return FPX_OK;
   if (!value_id) return FPX_EINVAL;
-  if ((rc = grow(ctx, &ctx->d_u8, (size_t)n))) return rc;
-  if ((rc = grow(ctx, &ctx->d_i32_a, (size_t)n * 4))) return rc;
-  if ((rc = grow(ctx, &ctx->d_i32_b, (size_t)n * 4))) return rc;
-  if ((rc = grow(ctx, &ctx->d_i32_c, (size_t)n * 4))) return rc;
-  if (n >= 4096) {  // page-locked arrays: staged by kernels, pipelined with the fused step
+  if (n >= 4096) {  // page-locked arrays: submit + wait
     bool used = false;
     rc = host_fused_staged(ctx, n, slot, round, value_id, target_mask, chosen, chosen_round, chosen_value, nack_round, &used);
     if (used) return rc;
   }
-  if (n >= 2 * host_piece(ctx, n))
-    return host_fused_pipelined(ctx, n, slot, round, value_id, target_mask, chosen, chosen_round, chosen_value, nack_round);
-  if ((rc = h2d(ctx, &ctx->d_slot, slot, n))) return rc;
-  if ((rc = h2d(ctx, &ctx->d_round, round, n))) return rc;
-  if ((rc = h2d(ctx, &ctx->d_value, value_id, n))) return rc;
-  if (target_mask && (rc = h2d(ctx, &ctx->d_target, target_mask, (size_t)n * 4))) return rc;
-  int32_t *d_slot = (int32_t*)ctx->d_slot.p, *d_round = (int32_t*)ctx->d_round.p, *d_value = (int32_t*)ctx->d_value.p;
-  uint64_t* d_target = target_mask ? (uint64_t*)ctx->d_target.p : nullptr;
-  uint8_t* d_ch = (uint8_t*)ctx->d_u8.p;
-  int32_t *d_cr = (int32_t*)ctx->d_i32_a.p, *d_cv = (int32_t*)ctx->d_i32_b.p, *d_nr = (int32_t*)ctx->d_i32_c.p;
-  auto download = [&]() -> int {
-    int r2;
-    if ((r2 = d2h(ctx, chosen, ctx->d_u8, (size_t)n))) return r2;
-    if ((r2 = d2h(ctx, chosen_round, ctx->d_i32_a, (size_t)n))) return r2;
-    if ((r2 = d2h(ctx, chosen_value, ctx->d_i32_b, (size_t)n))) return r2;
-    return d2h(ctx, nack_round, ctx->d_i32_c, (size_t)n);
+  const std::initializer_list<HostOut> out = {
+      {&ctx->d_u8, chosen, 1}, {&ctx->d_i32_a, chosen_round, 4}, {&ctx->d_i32_b, chosen_value, 4}, {&ctx->d_i32_c, nack_round, 4}};
+  auto run = [&](int lo, int len) {
+    return fpx_phase2_fused_dev(ctx, len, staged<int32_t>(ctx->d_slot, lo), staged<int32_t>(ctx->d_round, lo),
+                                staged<int32_t>(ctx->d_value, lo),
+                                target_mask ? staged<uint64_t>(ctx->d_target, (size_t)lo * 4) : nullptr,
+                                staged<uint8_t>(ctx->d_u8, lo), staged<int32_t>(ctx->d_i32_a, lo),
+                                staged<int32_t>(ctx->d_i32_b, lo), staged<int32_t>(ctx->d_i32_c, lo));
   };
-  int replay_from = 0;  // the host-split replay below covers [replay_from, n)
-  {
-    ctx->force_validate = true;  // also under FPX_F_TRUSTED: that flag is a promise about _dev batches only
-    rc = fpx_phase2_fused_dev(ctx, n, d_slot, d_round, d_value, d_target, d_ch, d_cr, d_cv, d_nr);
-    ctx->force_validate = false;
-    if (rc == FPX_OK) rc = download();
-    if (rc) {
-      (void)hipStreamSynchronize(ctx->stream);
-      return rc;
-    }
-    rc = fetch_status(ctx);
-    if (rc == FPX_EINVAL) return check_inputs(ctx, n, slot, round);  // the FIRST offender, for fpx_error_detail
-    if (rc != FPX_EORDER) return rc;
-  }
-  return host_fused_replay(ctx, n, slot, round, target_mask != nullptr, replay_from, chosen, chosen_round, chosen_value,
-                           nack_round);
+  rc = host_batch(ctx, n,
+                  {{&ctx->d_slot, slot, 4}, {&ctx->d_round, round, 4}, {&ctx->d_value, value_id, 4},
+                   {&ctx->d_target, target_mask, 32}},
+                  out, nullptr, run);
+  if (rc == FPX_EINVAL) return check_inputs(ctx, n, slot, round);  // the FIRST offender, for fpx_error_detail
+  if (rc != FPX_EORDER) return rc;
+  // the host-split replay: the inputs are still in the staging buffers
+  return host_batch(ctx, n, {}, out, message_runs(ctx, n, slot, round, true), run);
 }
 
 int32_t fpx_phase2_fused_submit(fpx_ctx* ctx, int32_t n, const int32_t* slot, const int32_t* round, const int32_t* value_id,
@@ -1922,22 +1835,11 @@ int32_t fpx_proxy_open(fpx_ctx* ctx, int32_t n, const int32_t* slot, const int32
   if (rc) return rc;
   if (n == 0) return FPX_OK;
   if (!value_id) return FPX_EINVAL;
-  if ((rc = h2d(ctx, &ctx->d_slot, slot, n))) return rc;
-  if ((rc = h2d(ctx, &ctx->d_round, round, n))) return rc;
-  if ((rc = h2d(ctx, &ctx->d_value, value_id, n))) return rc;
-  if ((rc = grow(ctx, &ctx->d_u8, (size_t)n))) return rc;
-  if ((rc = check_inputs(ctx, n, slot, round))) return rc;
-  HostRun host_run(ctx);
-  std::vector<int> cuts;
-  split_runs(ctx, n, slot, round, false, &cuts);
-  for (size_t k = 0; k + 1 < cuts.size(); ++k) {
-    const int lo = cuts[k], len = cuts[k + 1] - cuts[k];
-    rc = fpx_proxy_open_dev(ctx, len, (int32_t*)ctx->d_slot.p + lo, (int32_t*)ctx->d_round.p + lo,
-                            (int32_t*)ctx->d_value.p + lo, (uint8_t*)ctx->d_u8.p + lo);
-    if (rc) return rc;
-  }
-  if ((rc = d2h(ctx, is_new, ctx->d_u8, (size_t)n))) return rc;
-  return fetch_status(ctx);
+  return host_batch(ctx, n, {{&ctx->d_slot, slot, 4}, {&ctx->d_round, round, 4}, {&ctx->d_value, value_id, 4}},
+                    {{&ctx->d_u8, is_new, 1}}, message_runs(ctx, n, slot, round, false), [&](int lo, int len) {
+                      return fpx_proxy_open_dev(ctx, len, staged<int32_t>(ctx->d_slot, lo), staged<int32_t>(ctx->d_round, lo),
+                                                staged<int32_t>(ctx->d_value, lo), staged<uint8_t>(ctx->d_u8, lo));
+                    });
 }
 
 int32_t fpx_proxy_phase2b(fpx_ctx* ctx, int32_t n, const int32_t* slot, const int32_t* round, const uint64_t* vote_bits,
@@ -1947,27 +1849,13 @@ int32_t fpx_proxy_phase2b(fpx_ctx* ctx, int32_t n, const int32_t* slot, const in
   if (rc) return rc;
   if (n == 0) return FPX_OK;
   if (!vote_bits) return FPX_EINVAL;
-  if ((rc = h2d(ctx, &ctx->d_slot, slot, n))) return rc;
-  if ((rc = h2d(ctx, &ctx->d_round, round, n))) return rc;
-  if ((rc = h2d(ctx, &ctx->d_bits_a, vote_bits, (size_t)n * 4))) return rc;
-  if ((rc = grow(ctx, &ctx->d_u8, (size_t)n))) return rc;
-  if ((rc = grow(ctx, &ctx->d_i32_a, (size_t)n * 4))) return rc;
-  if ((rc = grow(ctx, &ctx->d_i32_b, (size_t)n * 4))) return rc;
-  if ((rc = check_inputs(ctx, n, slot, round))) return rc;
-  HostRun host_run(ctx);
-  std::vector<int> cuts;
-  split_runs(ctx, n, slot, round, false, &cuts);
-  for (size_t k = 0; k + 1 < cuts.size(); ++k) {
-    const int lo = cuts[k], len = cuts[k + 1] - cuts[k];
-    rc = fpx_proxy_phase2b_dev(ctx, len, (int32_t*)ctx->d_slot.p + lo, (int32_t*)ctx->d_round.p + lo,
-                               (uint64_t*)ctx->d_bits_a.p + (size_t)lo * 4, (uint8_t*)ctx->d_u8.p + lo,
-                               (int32_t*)ctx->d_i32_a.p + lo, (int32_t*)ctx->d_i32_b.p + lo);
-    if (rc) return rc;
-  }
-  if ((rc = d2h(ctx, newly_chosen, ctx->d_u8, (size_t)n))) return rc;
-  if ((rc = d2h(ctx, chosen_round, ctx->d_i32_a, (size_t)n))) return rc;
-  if ((rc = d2h(ctx, chosen_value, ctx->d_i32_b, (size_t)n))) return rc;
-  return fetch_status(ctx);
+  return host_batch(ctx, n, {{&ctx->d_slot, slot, 4}, {&ctx->d_round, round, 4}, {&ctx->d_bits_a, vote_bits, 32}},
+                    {{&ctx->d_u8, newly_chosen, 1}, {&ctx->d_i32_a, chosen_round, 4}, {&ctx->d_i32_b, chosen_value, 4}},
+                    message_runs(ctx, n, slot, round, false), [&](int lo, int len) {
+                      return fpx_proxy_phase2b_dev(ctx, len, staged<int32_t>(ctx->d_slot, lo), staged<int32_t>(ctx->d_round, lo),
+                                                   staged<uint64_t>(ctx->d_bits_a, (size_t)lo * 4), staged<uint8_t>(ctx->d_u8, lo),
+                                                   staged<int32_t>(ctx->d_i32_a, lo), staged<int32_t>(ctx->d_i32_b, lo));
+                    });
 }
 
 // Phase1a on device-resident arguments, asynchronous: d_target_mask 4 words or NULL, d_outp / d_outn 4 words each = promised
@@ -2320,27 +2208,6 @@ struct RangeKey {
   bool operator<(const RangeKey& o) const { return s != o.s ? s < o.s : (e != o.e ? e < o.e : r < o.r); }
 };
 
-// host staging of a range batch: [start | end | round | entry | nack_round] int32, [is_new | chosen] u8, then the
-// bitmaps [target | votes | nacks] u64
-struct RangeStage {
-  int32_t *start, *end, *round, *entry, *nack_round;
-  uint8_t *is_new, *chosen;
-  uint64_t *target, *votes, *nacks;
-};
-
-int stage_ranges(fpx_ctx* ctx, int n, RangeStage* st) {
-  const size_t words = (size_t)n * ctx->g.num_groups * 4;
-  const size_t ints = ((size_t)n * 5 * 4 + 63) & ~(size_t)63, bytes = ((size_t)n * 2 + 63) & ~(size_t)63;
-  int rc = grow(ctx, &ctx->d_rng, ints + bytes + 3 * words * 8);
-  if (rc) return rc;
-  char* p = (char*)ctx->d_rng.p;
-  st->start = (int32_t*)p, st->end = st->start + n, st->round = st->end + n, st->entry = st->round + n;
-  st->nack_round = st->entry + n;
-  st->is_new = (uint8_t*)(p + ints), st->chosen = st->is_new + n;
-  st->target = (uint64_t*)(p + ints + bytes), st->votes = st->target + words, st->nacks = st->votes + words;
-  return FPX_OK;
-}
-
 // host batches: argument check (the first offender for fpx_error_detail) and the cuts that make every piece a run
 int check_ranges(fpx_ctx* ctx, int n, const int32_t* start, const int32_t* end, const int32_t* round) {
   for (int i = 0; i < n; ++i)
@@ -2385,39 +2252,35 @@ static int32_t host_ranges(fpx_ctx* ctx, int mode, int32_t n, const int32_t* sta
   int rc = ranges_ctx_ok(ctx, n);
   if (rc) return rc;
   if (n == 0) return FPX_OK;
-  if (!start || !end || !round || (mode == RANGES_TALLY && !votes_in)) return FPX_EINVAL;
+  const bool tally = mode == RANGES_TALLY;
+  if (!start || !end || !round || (tally && !votes_in)) return FPX_EINVAL;
   if ((rc = check_ranges(ctx, n, start, end, round))) return rc;
-  const size_t words = (size_t)n * ctx->g.num_groups * 4, per = (size_t)ctx->g.num_groups * 4;
-  RangeStage sg;
-  if ((rc = stage_ranges(ctx, n, &sg))) return rc;
-  HIPCHK(ctx, hipMemcpyAsync(sg.start, start, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
-  HIPCHK(ctx, hipMemcpyAsync(sg.end, end, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
-  HIPCHK(ctx, hipMemcpyAsync(sg.round, round, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
-  if (target_masks) HIPCHK(ctx, hipMemcpyAsync(sg.target, target_masks, words * 8, hipMemcpyHostToDevice, ctx->stream));
-  if (mode == RANGES_TALLY) HIPCHK(ctx, hipMemcpyAsync(sg.votes, votes_in, words * 8, hipMemcpyHostToDevice, ctx->stream));
-  HostRun host_run(ctx);
-  std::vector<int> cuts;
-  // one round per leader group in every run: the acceptors' scalar needs it, and the table insert relies on
-  // "same (start, end) in one launch => same key"
-  split_range_runs(ctx, n, start, end, round, true, mode == RANGES_TALLY, &cuts);
-  for (size_t k = 0; k + 1 < cuts.size(); ++k) {
-    const int lo = cuts[k], len = cuts[k + 1] - cuts[k];
-    RangeBatch b;
-    memset(&b, 0, sizeof(b));
-    b.n = len, b.start = sg.start + lo, b.end = sg.end + lo, b.round = sg.round + lo;
-    b.target = target_masks ? sg.target + (size_t)lo * per : nullptr;
-    b.entry = sg.entry + lo, b.nack_round = sg.nack_round + lo;
-    b.vote_bits = sg.votes + (size_t)lo * per, b.nack_bits = sg.nacks + (size_t)lo * per;
-    b.is_new = sg.is_new + lo, b.chosen = sg.chosen + lo;
-    if (mode == RANGES_TALLY) b.votes_in = sg.votes + (size_t)lo * per;
-    if ((rc = enqueue_ranges(ctx, b, mode))) return rc;
-  }
-  if (vote_bits) HIPCHK(ctx, hipMemcpyAsync(vote_bits, sg.votes, words * 8, hipMemcpyDeviceToHost, ctx->stream));
-  if (nack_bits) HIPCHK(ctx, hipMemcpyAsync(nack_bits, sg.nacks, words * 8, hipMemcpyDeviceToHost, ctx->stream));
-  if (nack_round) HIPCHK(ctx, hipMemcpyAsync(nack_round, sg.nack_round, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
-  if (is_new) HIPCHK(ctx, hipMemcpyAsync(is_new, sg.is_new, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-  if (chosen) HIPCHK(ctx, hipMemcpyAsync(chosen, sg.chosen, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-  return fetch_status(ctx);
+  const size_t per = (size_t)ctx->g.num_groups * 4;
+  RangeStage& rs = ctx->rng;
+  return host_batch(
+      ctx, n,
+      {{&rs.start, start, 4}, {&rs.end, end, 4}, {&rs.round, round, 4}, {&rs.target, target_masks, per * 8},
+       {&rs.votes, votes_in, per * 8}},
+      {{&rs.votes, vote_bits, per * 8}, {&rs.nacks, nack_bits, per * 8}, {&rs.nack_round, nack_round, 4},
+       {&rs.is_new, is_new, 1}, {&rs.chosen, chosen, 1}, {&rs.entry, nullptr, 4}},
+      [&](std::vector<int>* cuts) {
+        // one round per leader group in every run: the acceptors' scalar needs it, and the table insert relies on
+        // "same (start, end) in one launch => same key"
+        split_range_runs(ctx, n, start, end, round, true, tally, cuts);
+        return FPX_OK;
+      },
+      [&](int lo, int len) {
+        RangeBatch b;
+        memset(&b, 0, sizeof(b));
+        b.n = len, b.start = staged<int32_t>(rs.start, lo), b.end = staged<int32_t>(rs.end, lo);
+        b.round = staged<int32_t>(rs.round, lo);
+        b.target = target_masks ? staged<uint64_t>(rs.target, lo * per) : nullptr;
+        b.entry = staged<int32_t>(rs.entry, lo), b.nack_round = staged<int32_t>(rs.nack_round, lo);
+        b.vote_bits = staged<uint64_t>(rs.votes, lo * per), b.nack_bits = staged<uint64_t>(rs.nacks, lo * per);
+        b.is_new = staged<uint8_t>(rs.is_new, lo), b.chosen = staged<uint8_t>(rs.chosen, lo);
+        if (tally) b.votes_in = b.vote_bits;
+        return enqueue_ranges(ctx, b, mode);
+      });
 }
 
 int32_t fpx_noop_ranges_fused(fpx_ctx* ctx, int32_t n, const int32_t* slot_start, const int32_t* slot_end,
@@ -2526,28 +2389,24 @@ int32_t fpx_replica_chosen(fpx_ctx* ctx, int32_t n, const int32_t* slot, const i
       return FPX_EINVAL;
     }
   }
-  int rc;
-  if (n > 0) {
-    // masked-out messages must not trip the slot checks on the device: compact them away
-    std::vector<int32_t> s, v;
-    s.reserve(n), v.reserve(n);
-    for (int i = 0; i < n; ++i)
-      if (!mask || mask[i]) s.push_back(slot[i]), v.push_back(value_id[i]);
-    const int m = (int)s.size();
-    if (m > 0) {
-      if ((rc = h2d(ctx, &ctx->d_slot, s.data(), m))) return rc;
-      if ((rc = h2d(ctx, &ctx->d_value, v.data(), m))) return rc;
-      std::vector<int> cuts;
-      split_runs(ctx, m, s.data(), nullptr, false, &cuts);
-      for (size_t k = 0; k + 1 < cuts.size(); ++k) {
-        const int lo = cuts[k], len = cuts[k + 1] - cuts[k];
-        rc = fpx_replica_chosen_dev(ctx, len, (int32_t*)ctx->d_slot.p + lo, (int32_t*)ctx->d_value.p + lo, nullptr);
-        if (rc) return rc;
-      }
-    }
-  }
-  if ((rc = fpx_replica_state(ctx, executed_watermark, num_chosen))) return rc;
-  return fetch_status(ctx);
+  // masked-out messages must not trip the slot checks on the device: compact them away
+  std::vector<int32_t> s, v;
+  s.reserve(n), v.reserve(n);
+  for (int i = 0; i < n; ++i)
+    if (!mask || mask[i]) s.push_back(slot[i]), v.push_back(value_id[i]);
+  const int m = (int)s.size();
+  const int rc = host_batch(
+      ctx, m, {{&ctx->d_slot, s.data(), 4}, {&ctx->d_value, v.data(), 4}}, {},
+      [&](std::vector<int>* cuts) {
+        split_runs(ctx, m, s.data(), nullptr, false, cuts);
+        return FPX_OK;
+      },
+      [&](int lo, int len) {
+        return fpx_replica_chosen_dev(ctx, len, staged<int32_t>(ctx->d_slot, lo), staged<int32_t>(ctx->d_value, lo), nullptr);
+      });
+  if (rc == FPX_EHIP || rc == FPX_ENOMEM) return rc;  // (a HIP failure: no scalars to report)
+  const int st = fpx_replica_state(ctx, executed_watermark, num_chosen);
+  return st ? st : rc;
 }
 
 int32_t fpx_replica_chosen_noop_range(fpx_ctx* ctx, int32_t slot_start, int32_t slot_end, int32_t* executed_watermark,
@@ -2905,7 +2764,7 @@ int32_t fpx_phase2_replica_sharded_dev(fpx_ctx* ctx, int32_t n, const int32_t* d
   }
   // ProxyLeader.handlePhase2a bookkeeping + handlePhase2b for my slice of the slots; K1's validation pass
   // covered the whole batch (slots distinct), so the slice needs none
-  HostRun trusted(ctx);
+  HostFlags trusted(ctx, true);
   Batch o;
   memset(&o, 0, sizeof(o));
   o.n = per, o.slot = d_slot + lo, o.round = d_round + lo, o.value = d_value_id + lo;

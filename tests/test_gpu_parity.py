@@ -725,12 +725,11 @@ def test_phase1a_dev_is_asynchronous_and_equal(fa, oracle, monkeypatch, split):
 
 
 @pytest.mark.parametrize("ballot_mode", [0, 1])
-def test_pipelined_host_batches(fa, oracle, ballot_mode, monkeypatch):
-    """big host batches run as a 3-stream pipeline over pieces (upload / K3 / download overlap).  Forced here at a
-    small piece size: a well-formed batch, a batch with range errors (FPX_EINVAL: nothing applied), and batches
-    that break the run contract in a LATER piece (duplicate slots, a round change) -- the pieces before it stay
-    applied, the host-split replay takes over from the offending piece, results equal message-at-a-time delivery"""
-    monkeypatch.setenv("FPX_HOST_PIECE", "1024")
+def test_host_batch_late_errors_and_replay(fa, oracle, ballot_mode):
+    """host-pointer K3 on a batch of pageable arrays: a well-formed batch, a batch with a range error late in it
+    (FPX_EINVAL with the offender's index, nothing applied), and batches that break the run contract part-way
+    (duplicate slots, a round change) -- the optimistic whole-batch run applies nothing, the host-split replay runs
+    the batch as runs back to back, results equal message-at-a-time delivery"""
     S, R = 1 << 15, 256
     gpu, ref = both(fa, oracle, num_slots=S, num_replicas=R, f=127, ballot_mode=ballot_mode, tally_ways=8)
     rng = np.random.default_rng(17 + ballot_mode)
@@ -747,22 +746,22 @@ def test_pipelined_host_batches(fa, oracle, ballot_mode, monkeypatch):
     assert a[0] == b[0] == fa.FPX_EINVAL and gpu.error_detail() == ref.error_detail() == (7000, S + 5, 1)
     np.testing.assert_array_equal(gpu.state_digest(), before)
     dup = slot.copy()
-    dup[5000:5050] = dup[4000:4050]                      # duplicates inside piece 4, and of piece-3 slots
+    dup[5000:5050] = dup[4000:4050]                      # duplicates of earlier slots in the middle of the batch
     r2 = rnd + 1
     r2[8000:] = 2                                         # and a round change further on
     check(gpu, ref, [("fused", dup, r2, val, None), ("fused", slot[::-1].copy(), rnd + 3, val, tgt)],
           tally_slots=range(0, S, 997))
-    monkeypatch.delenv("FPX_HOST_PIECE")
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("n,shape", [(5000, "steady"), (300000, "steady"), (1 << 20, "steady"), (300000, "repeats"),
                                       (700001, "rounds")])
 def test_page_locked_batches_are_staged_by_kernels(fa, oracle, n, shape):
-    """fpx_phase2_fused with EVERY array in page-locked memory (fpx_host_alloc): the batch is staged by k_stage on its own
-    streams in pieces, pipelined with the fused step, the outputs are written back to host memory by kernels too.  Same
-    results as the oracle for batches that are one device run (steady), that repeat slots (split into runs by the
-    replay), and that change rounds in the middle; a slot out of range is FPX_EINVAL with its index, nothing applied."""
+    """fpx_phase2_fused with EVERY array in page-locked memory (fpx_host_alloc): submit + wait -- the inputs go up by the
+    copy engine on a stream of their own, the batch is validated and run on the device as one run, and the vote kernel
+    writes the outputs straight into the caller's page-locked arrays.  Same results as the oracle for batches that are
+    one device run (steady), that repeat slots (split into runs by the replay), and that change rounds in the middle; a
+    slot out of range is FPX_EINVAL with its index, nothing applied."""
     import ctypes as C
 
     S, R = 1 << 21, 5
