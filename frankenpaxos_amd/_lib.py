@@ -139,6 +139,12 @@ SIGNATURES = {
     "fpx_epx_read_cmdlog_deps": (C.c_int32, [VP, C.c_int32, C.c_int32, C.c_int32, VP, VP]),
     "fpx_epx_handle_preaccept": (C.c_int32, [VP, C.c_int32] + [VP] * 18),
     "fpx_epx_read_index": (C.c_int32, [VP, C.c_int32, C.c_int32, VP, VP]),
+    "fpx_epx_preaccept_mk": (C.c_int32, [VP, C.c_int32] + [VP] * 13),
+    "fpx_epx_preaccept_mk_dev": (C.c_int32, [VP, C.c_int32] + [VP] * 13),
+    "fpx_epx_preaccept_mk_packed_dev": (C.c_int32, [VP, C.c_int32] + [VP] * 10),
+    "fpx_epx_handle_preaccept_mk": (C.c_int32, [VP, C.c_int32] + [VP] * 19),
+    "fpx_epx_accept_mk": (C.c_int32, [VP, C.c_int32] + [VP] * 14),
+    "fpx_epx_handle_commit_mk": (C.c_int32, [VP, C.c_int32] + [VP] * 9),
     "fpx_replica_chosen": (C.c_int32, [VP, C.c_int32, VP, VP, VP, I32P, I32P]),
     "fpx_replica_chosen_dev": (C.c_int32, [VP, C.c_int32, VP, VP, VP]),
     "fpx_replica_state": (C.c_int32, [VP, I32P, I32P]),

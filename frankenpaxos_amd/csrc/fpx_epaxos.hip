@@ -919,6 +919,8 @@ struct ClBatch {
   const int32_t* triple;   // Accept
   const int32_t* key;      // Accept: the command's key, -1 = Noop
   const uint8_t* is_set;   // Accept
+  const int32_t* key_off;  // Accept, multi-key form (else null): message i's keys are keys[key_off[i] .. key_off[i + 1])
+  const int32_t* keys;
   const uint8_t* target;
   uint8_t* ok_bits;
   uint8_t* nack_bits;
@@ -944,6 +946,16 @@ __device__ __forceinline__ void index_put(const EpxState& st, int r, int key, in
   int32_t* a = is_set ? st.sets : st.gets;
   atomicMax(&a[((size_t)r * st.num_keys + key) * st.n + L], x + 1);
 }
+// the same for message i's command: its single key (key_off null) or every key of its list (KeyValueStore.scala:236-254:
+// put records the instance under each key of the command; a repeated key is the same maximum twice, no keys = nothing)
+__device__ __forceinline__ void index_put_cmd(const EpxState& st, int r, const int32_t* key, const int32_t* key_off,
+                                              const int32_t* keys, int i, int is_set, int L, int x) {
+  if (!key_off) {
+    index_put(st, r, key[i], is_set, L, x);
+    return;
+  }
+  for (int j = key_off[i]; j < key_off[i + 1]; ++j) index_put(st, r, keys[j], is_set, L, x);
+}
 
 // an Accept names its triple by the caller's id alone: the stored dependencies are marked unknown
 __device__ __forceinline__ void deps_by_id(const EpxState& st, size_t cell) {
@@ -958,7 +970,7 @@ __global__ void __launch_bounds__(256) k_cl_validate(const EpxState st, const Cl
   bool ok = L >= 0 && L < n && x >= 0 && x < st.num_instances && bo >= 0 && bo < (1 << 27) && br >= 0 && br < n &&
             (b.target[i] >> n) == 0;
   if (ok && b.accept) ok = !((b.target[i] >> br) & 1u);  // thriftyOtherReplicas: never the proposer itself (:774)
-  if (ok && b.accept) ok = b.key[i] >= -1 && b.key[i] < st.num_keys;
+  if (ok && b.accept && !b.key_off) ok = b.key[i] >= -1 && b.key[i] < st.num_keys;  // (key lists: checked on the host)
   if (ok) ok = atomicExch(&st.cl_stamp[(size_t)L * st.num_instances + x], b.run_id) != b.run_id;
   if (!ok) epx_report(st.status, FPX_EINVAL, i);
 }
@@ -981,7 +993,7 @@ __global__ void __launch_bounds__(256) k_cl_propose(const EpxState st, const ClB
   }
   st.cl_status[c] = CL_ACCEPTED, st.cl_ballot[c] = ballot, st.cl_vote[c] = ballot, st.cl_triple[c] = b.triple[i];  // :759-762
   deps_by_id(st, c);
-  index_put(st, P, b.key[i], b.is_set[i], b.leader[i], b.number[i]);  // :763
+  index_put_cmd(st, P, b.key, b.key_off, b.keys, i, b.is_set[i], b.leader[i], b.number[i]);  // :763
 }
 
 // handlePrepare (:1632-1757) / handleAccept (:1421-1511) at replica r for message i: one thread per (i, r)
@@ -1018,7 +1030,7 @@ __global__ void __launch_bounds__(256) k_cl_handle(const EpxState st, const ClBa
         contrib = ballot;  // :1487
         st.cl_status[c] = CL_ACCEPTED, st.cl_ballot[c] = ballot, st.cl_vote[c] = ballot, st.cl_triple[c] = b.triple[i];
         deps_by_id(st, c);
-        index_put(st, r, b.key[i], b.is_set[i], b.leader[i], b.number[i]);  // :1503
+        index_put_cmd(st, r, b.key, b.key_off, b.keys, i, b.is_set[i], b.leader[i], b.number[i]);  // :1503
       }
     }
   }
@@ -1104,7 +1116,7 @@ __global__ void __launch_bounds__(256) k_cl_commit(const EpxState st, const ClBa
         const size_t c = ((size_t)r * n + b.leader[i]) * st.num_instances + b.number[i];
         st.cl_status[c] = CL_COMMITTED, st.cl_ballot[c] = -1, st.cl_vote[c] = -1, st.cl_triple[c] = b.triple[i];
         deps_by_id(st, c);
-        index_put(st, r, b.key[i], b.is_set[i], b.leader[i], b.number[i]);  // commit :828, at every replica (Commit)
+        index_put_cmd(st, r, b.key, b.key_off, b.keys, i, b.is_set[i], b.leader[i], b.number[i]);  // commit :828, at every replica (Commit)
       }
     }
   }
@@ -1121,6 +1133,8 @@ struct LcBatch {
   const int32_t* triple;
   const int32_t* key;
   const uint8_t* is_set;
+  const int32_t* key_off;   // multi-key form (else null): message i's keys are keys[key_off[i] .. key_off[i + 1])
+  const int32_t* keys;
   const int32_t* deps;      // [m][n] or null: the triple is known by its id alone
   const int32_t* deps_end;  // [m] or null
   const uint8_t* target;
@@ -1146,7 +1160,7 @@ __global__ void __launch_bounds__(256) k_cl_learn_commit(const EpxState st, cons
       deps_by_id(st, c);
     }
   }
-  index_put(st, r, b.key[i], b.is_set[i], b.leader[i], b.number[i]);  // (a maximum: every message's put, in any order)
+  index_put_cmd(st, r, b.key, b.key_off, b.keys, i, b.is_set[i], b.leader[i], b.number[i]);  // (a maximum: every message's put, in any order)
 }
 
 // ---- K8: Replica.handlePrepareOk (Replica.scala:1759-1884), the recovering replica's decision -- one thread per instance
@@ -1235,7 +1249,11 @@ struct HpBatch {
   const int32_t* number;
   const int32_t* b_ord;
   const int32_t* b_rep;
-  const int32_t* key;       // -1 = Noop
+  const int32_t* key;       // -1 = Noop; null in the multi-key form
+  const int32_t* key_off;   // multi-key form (else null): message i's keys are keys[key_off[i] .. key_off[i + 1]), the pair
+  const int32_t* keys;      // sequences are P long (pair j at position j: array order) and uniq[j] = 0 drops a repeated key
+  const uint8_t* uniq;
+  int P;
   const uint8_t* is_set;
   const int32_t* triple;    // may be null
   const int32_t* deps_in;   // [m][n]
@@ -1260,7 +1278,8 @@ struct HpBatch {
 __global__ void __launch_bounds__(256) k_hp_validate(const EpxState st, const HpBatch b) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= b.m) return;
-  const int n = st.n, L = b.leader[i], x = b.number[i], bo = b.b_ord[i], br = b.b_rep[i], k = b.key[i];
+  const int n = st.n, L = b.leader[i], x = b.number[i], bo = b.b_ord[i], br = b.b_rep[i];
+  const int k = b.key_off ? 0 : b.key[i];  // (key lists: checked on the host)
   bool ok = L >= 0 && L < n && x >= 0 && x < st.num_instances && bo >= 0 && bo < (1 << 27) && br >= 0 && br < n &&
             (b.target[i] >> n) == 0 && k >= -1 && k < st.num_keys;
   if (ok) {
@@ -1280,7 +1299,7 @@ __global__ void __launch_bounds__(256) k_hp_gate(const EpxState st, const HpBatc
   if (t >= (long long)b.m * n) return;
   const int r = (int)(t / b.m), i = (int)(t % b.m);
   int act = HP_NONE;
-  const int L = b.leader[i], ballot = b.b_ord[i] * 8 + b.b_rep[i], k = b.key[i];
+  const int L = b.leader[i], ballot = b.b_ord[i] * 8 + b.b_rep[i], k = b.key_off ? 0 : b.key[i];
   // (a malformed message is reported by k_hp_validate; here it only must not index out of bounds)
   if (((b.target[i] >> r) & 1u) && L >= 0 && L < n && b.number[i] >= 0 && b.number[i] < st.num_instances) {
     const size_t c = ((size_t)r * n + L) * st.num_instances + b.number[i];
@@ -1298,6 +1317,11 @@ __global__ void __launch_bounds__(256) k_hp_gate(const EpxState st, const HpBatc
   // only what the replica processes takes part in its conflict scan; the rest (and Noops, :592-593) sorts last
   const bool scanned = act == HP_PROCESS && k >= 0 && k < st.num_keys;
   const uint32_t flags = ((uint32_t)(b.is_set[i] ? 1 : 0) << EPX_SET_SHIFT) | ((uint32_t)(L & 7) << EPX_LEADER_SHIFT);
+  if (b.key_off) {  // one pair per (message, distinct key), in array order; the payload is the pair index
+    for (int j = b.key_off[i]; j < b.key_off[i + 1]; ++j)
+      b.kv[(size_t)r * b.P + j] = make_uint2((scanned && b.uniq[j] ? (uint32_t)b.keys[j] : (uint32_t)st.num_keys) | flags, (uint32_t)j);
+    return;
+  }
   b.kv[o] = make_uint2((scanned ? (uint32_t)k : (uint32_t)st.num_keys) | flags, (uint32_t)i);
 }
 
@@ -1321,7 +1345,8 @@ __global__ void __launch_bounds__(256) k_hp_reply(const EpxState st, const HpBat
     int row[N];
 #pragma unroll
     for (int l = 0; l < N; ++l) row[l] = 0;
-    if (b.key[i] >= 0) {  // computeSequenceNumberAndDependencies :569-600: the conflicts the scan found
+    if (b.key_off || b.key[i] >= 0) {  // computeSequenceNumberAndDependencies :569-600: the conflicts the scan found
+      // (key lists: the row k_mk_merge formed from the command's pairs, zeros for a command without keys)
       const int32_t* cr = b.conf + ((size_t)i * N + r) * NP;
 #pragma unroll
       for (int l = 0; l < N; ++l) row[l] = cr[l];
@@ -1377,6 +1402,8 @@ __global__ void __launch_bounds__(256) k_hp_commit(const EpxState st, const HpBa
   if (seen[st.n + l] > *s2) *s2 = seen[st.n + l];
 }
 
+#include "fpx_epaxos_mk.hpp"
+
 struct Buf {
   void* p = nullptr;
   size_t cap = 0;
@@ -1390,6 +1417,8 @@ struct fpx_epx {
   hipStream_t stream = nullptr, own_stream = nullptr;
   int last_hip = 0;
   Buf kv, kv2, seg, conf, tmp, tick, h_leader, h_number, h_key, h_set, h_mask, h_seen, h_rank, h_triple, o_fast, o_deps, o_ldeps, o_own, cl, hp, fusedb, metab;
+  Buf mk_misc, mk_rec, mk_pair, mk_pconf, h_off, h_keys;  // multi-key commands (fpx_epaxos_mk.hpp)
+  int32_t* mk_host = nullptr;                              // page-locked: k_mk_total's line
   Buf p_fast, p_deps, p_ldeps, p_own;      // the four output arrays when a packed tick goes the first form's way
   Buf kp_hist, kp_recs, kp_misc;          // K5 second form (fpx_epaxos_kp.hpp)
   Buf dg_msg, dg_direct, dg_clo, dg_pre, dg_tmax, dg_pairs, dg_pairs2, dg_ctl, dg_key;  // device dependency-graph execution
@@ -1456,9 +1485,11 @@ void launch_scan_decide(fpx_epx* e, const EpxBatch& b) {
 }
 
 template <int N>
-void launch_hp(fpx_epx* e, const EpxBatch& sb, const HpBatch& hb) {
+void launch_hp(fpx_epx* e, const EpxBatch& sb, const HpBatch& hb, const MkMerge* mm = nullptr, bool scan = true) {
   const int segs = N * e->st.num_keys;
-  hipLaunchKernelGGL((k_epx_scan<N>), dim3((segs + 3) / 4), dim3(256), 0, e->stream, e->st, sb);
+  if (scan) hipLaunchKernelGGL((k_epx_scan<N>), dim3((segs + 3) / 4), dim3(256), 0, e->stream, e->st, sb);
+  // key lists: the command's row at a replica = the max of its pairs' rows (k_hp_reply reads the command's row)
+  if (mm) hipLaunchKernelGGL((k_mk_merge<N>), dim3((mm->m + 255) / 256), dim3(256), 0, e->stream, e->st, *mm);
   hipLaunchKernelGGL((k_hp_reply<N>), dim3((unsigned)(((long long)hb.m * N + 255) / 256)), dim3(256), 0, e->stream, e->st, hb);
 }
 
@@ -1927,9 +1958,11 @@ int32_t fpx_epx_destroy(fpx_epx* e) {
     if (p) (void)hipFree(p);
   Buf* bs[] = {&e->kv, &e->kv2, &e->seg, &e->conf, &e->tmp, &e->tick, &e->h_leader, &e->h_number,
                &e->h_key, &e->h_set, &e->h_mask, &e->h_seen, &e->h_rank, &e->h_triple, &e->o_fast, &e->o_deps, &e->o_ldeps,
-               &e->o_own, &e->cl, &e->hp, &e->fusedb, &e->metab};
+               &e->o_own, &e->cl, &e->hp, &e->fusedb, &e->metab, &e->mk_misc, &e->mk_rec, &e->mk_pair, &e->mk_pconf,
+               &e->h_off, &e->h_keys};
   for (Buf* b : bs)
     if (b->p) (void)hipFree(b->p);
+  if (e->mk_host) (void)hipHostFree(e->mk_host);
   for (Buf* b : {&e->kp_hist, &e->kp_recs, &e->kp_misc, &e->p_fast, &e->p_deps, &e->p_ldeps, &e->p_own, &e->dg_msg, &e->dg_direct,
                  &e->dg_clo, &e->dg_pre, &e->dg_tmax, &e->dg_pairs, &e->dg_pairs2, &e->dg_ctl, &e->dg_key, &e->dgh_in, &e->dgh_out})
     if (b->p) (void)hipFree(b->p);
@@ -1958,6 +1991,29 @@ int32_t fpx_epx_sync(fpx_epx* e) {
     EHIP(e, hipStreamSynchronize(e->stream));
   }
   return h[0];
+}
+
+// key lists (the _mk entry points): key_off[0] = 0, non-decreasing, at most FPX_EPX_MK_MAX_PAIRS keys, each in [0, num_keys)
+static int check_key_lists(int32_t m, const int32_t* key_off, const int32_t* keys, int num_keys, int64_t* P) {
+  if (!key_off || key_off[0] != 0) return FPX_EINVAL;
+  for (int32_t i = 0; i < m; ++i)
+    if (key_off[i + 1] < key_off[i]) return FPX_EINVAL;
+  *P = key_off[m];
+  if (*P > FPX_EPX_MK_MAX_PAIRS || (*P > 0 && !keys)) return FPX_EINVAL;
+  for (int64_t j = 0; j < *P; ++j)
+    if (keys[j] < 0 || keys[j] >= num_keys) return FPX_EINVAL;
+  return FPX_OK;
+}
+
+static int upload_key_lists(fpx_epx* e, int32_t m, const int32_t* key_off, const int32_t* keys, int64_t P, const int32_t** d_off,
+                            const int32_t** d_keys) {
+  int rc;
+  if ((rc = grow(e, &e->h_off, ((size_t)m + 1) * 4))) return rc;
+  if ((rc = grow(e, &e->h_keys, (size_t)std::max<int64_t>(P, 1) * 4))) return rc;
+  EHIP(e, hipMemcpyAsync(e->h_off.p, key_off, ((size_t)m + 1) * 4, hipMemcpyHostToDevice, e->stream));
+  if (P > 0) EHIP(e, hipMemcpyAsync(e->h_keys.p, keys, (size_t)P * 4, hipMemcpyHostToDevice, e->stream));
+  *d_off = (const int32_t*)e->h_off.p, *d_keys = (const int32_t*)e->h_keys.p;
+  return FPX_OK;
 }
 
 static int32_t preaccept_dev_impl(fpx_epx* e, int32_t m, const int32_t* d_leader, const int32_t* d_number,
@@ -2182,18 +2238,199 @@ int32_t fpx_epx_preaccept(fpx_epx* e, int32_t m, const int32_t* leader, const in
   return fpx_epx_sync(e);
 }
 
+// K5 with key lists: every command one key -> the single-key tick as it is (keys as key); otherwise the pair form
+// (fpx_epaxos_mk.hpp).  One host wait: k_mk_prep's totals (pair count, distinct pairs, commands without exactly one key)
+// decide the route and size the pair buffers; a bad list is caught there, before anything is applied.
+static int32_t preaccept_mk_impl(fpx_epx* e, int32_t m, const int32_t* d_leader, const int32_t* d_number, const int32_t* d_off,
+                                 const int32_t* d_keys, const uint8_t* d_is_set, const uint8_t* d_resp_mask,
+                                 const uint8_t* d_seen_mask, const int32_t* d_rank, const int32_t* d_triple_id, uint8_t* d_fast,
+                                 int32_t* d_deps, int32_t* d_leader_deps, int32_t* d_own_values_end, int32_t* d_packed) {
+  if (!e || m < 0) return FPX_EINVAL;
+  EpxDeviceGuard _dg(e->cfg.device);
+  if (m == 0) return FPX_OK;
+  if (!d_off) return FPX_EINVAL;
+  const int n = e->st.n;
+  const int tiles = (m + MK_TILE - 1) / MK_TILE;
+  int rc;
+  const int blocks = (m + 255) / 256;
+  if ((rc = grow(e, &e->mk_misc, 64 + (size_t)m * 4 + (size_t)n * tiles * 4 + (size_t)blocks * 8 + 16))) return rc;
+  if (!e->mk_host && hipHostMalloc((void**)&e->mk_host, 64, hipHostMallocDefault) != hipSuccess) {
+    e->mk_host = nullptr;
+    return FPX_ENOMEM;
+  }
+  MkBatch mb;
+  memset(&mb, 0, sizeof(mb));
+  mb.m = m, mb.tiles = tiles, mb.off = d_off, mb.keys = d_keys, mb.leader = d_leader, mb.number = d_number;
+  mb.is_set = d_is_set, mb.resp_mask = d_resp_mask, mb.seen_mask = d_seen_mask, mb.rank = d_rank;
+  mb.info = (int32_t*)e->mk_misc.p, mb.ucnt = mb.info + 16, mb.tsum = (uint32_t*)(mb.ucnt + m);
+  mb.part = (int2*)(((uintptr_t)(mb.tsum + (size_t)n * tiles) + 15) & ~(uintptr_t)15);
+  const dim3 gm(blocks), blk(256);
+  hipLaunchKernelGGL(k_mk_prep, gm, blk, 0, e->stream, e->st, mb);
+  hipLaunchKernelGGL(k_mk_total, dim3(1), blk, 0, e->stream, e->st, mb, blocks);
+  int32_t* h = e->mk_host;  // page-locked
+  EHIP(e, hipMemcpyAsync(h, mb.info, 16, hipMemcpyDeviceToHost, e->stream));
+  EHIP(e, hipStreamSynchronize(e->stream));
+  if (h[3] != 0) return fpx_epx_sync(e);  // (returns the status and clears it)
+  const int U = h[0], P = h[2];
+  if (P > FPX_EPX_MK_MAX_PAIRS) return FPX_EINVAL;
+  if (h[1] == 0)  // key_off[i] = i: today's tick, on chip where it fits
+    return preaccept_dev_impl(e, m, d_leader, d_number, d_keys, d_is_set, d_resp_mask, d_seen_mask, d_rank, d_triple_id, d_fast,
+                              d_deps, d_leader_deps, d_own_values_end, d_packed);
+  if (d_packed) {
+    if ((rc = grow(e, &e->p_fast, (size_t)m))) return rc;
+    if ((rc = grow(e, &e->p_deps, (size_t)m * n * 4))) return rc;
+    if ((rc = grow(e, &e->p_ldeps, (size_t)m * n * 4))) return rc;
+    if ((rc = grow(e, &e->p_own, (size_t)m * 8))) return rc;
+    d_fast = (uint8_t*)e->p_fast.p, d_deps = (int32_t*)e->p_deps.p, d_leader_deps = (int32_t*)e->p_ldeps.p;
+    d_own_values_end = (int32_t*)e->p_own.p;
+  }
+  const int NP = n <= 4 ? 4 : 8, Ux = std::max(U, 1);
+  if ((rc = grow(e, &e->mk_rec, (size_t)n * m * 16))) return rc;
+  if ((rc = grow(e, &e->mk_pair, (size_t)std::max(P, 1) * 5 + 64))) return rc;
+  if ((rc = grow(e, &e->mk_pconf, (size_t)std::max(P, 1) * n * NP * 4))) return rc;
+  if ((rc = grow(e, &e->kv, (size_t)n * Ux * 8))) return rc;
+  if ((rc = grow(e, &e->kv2, (size_t)n * Ux * 8))) return rc;
+  if ((rc = grow(e, &e->tick, (size_t)n * e->st.num_keys * 2 * n * 4))) return rc;
+  if ((rc = grow(e, &e->seg, (size_t)n * e->st.num_keys * 8))) return rc;
+  if ((rc = grow(e, &e->conf, (size_t)m * n * NP * 4))) return rc;
+  mb.P = P, mb.U = U, mb.rec = (int4*)e->mk_rec.p, mb.kv = (uint2*)e->kv.p;
+  mb.pnum = (int32_t*)e->mk_pair.p, mb.uniq = (uint8_t*)e->mk_pair.p + (size_t)std::max(P, 1) * 4;
+  hipLaunchKernelGGL(k_mk_pairs, gm, blk, 0, e->stream, mb);
+  hipLaunchKernelGGL(k_mk_place, gm, blk, 0, e->stream, e->st, mb);
+  hipLaunchKernelGGL(k_mk_tilesum, dim3(tiles, n), blk, 0, e->stream, mb);
+  hipLaunchKernelGGL(k_mk_tilescan, dim3(n), blk, 0, e->stream, mb);
+  hipLaunchKernelGGL(k_mk_scatter, dim3(tiles, n), blk, 0, e->stream, e->st, mb);
+  // the pairs through K5's first form: sort by key (stable: delivery order within a key), segments, scan -> pair rows
+  EpxBatch sb;
+  memset(&sb, 0, sizeof(sb));
+  sb.m = U, sb.number = mb.pnum, sb.kv = mb.kv, sb.kv_sorted = (uint2*)e->kv2.p;
+  sb.tick = (int32_t*)e->tick.p, sb.seg = (int32_t*)e->seg.p, sb.conf = (int32_t*)e->mk_pconf.p;
+  if (U > 0) {
+    const uint32_t* key_totals = nullptr;
+    int key_buckets = 0;
+    sb.kv_sorted = sort_by_key(e, U, sb.kv, sb.kv_sorted, nullptr, &rc, &key_totals, &key_buckets);
+    if (rc) return rc;
+    launch_segments(e, sb, key_totals, key_buckets);
+  }
+  // ... and the commands: merged rows -> k_epx_decide as in the first form
+  EpxBatch db;
+  memset(&db, 0, sizeof(db));
+  db.m = m, db.leader = d_leader, db.number = d_number, db.is_set = d_is_set, db.resp_mask = d_resp_mask;
+  db.seen_mask = d_seen_mask, db.rank = d_rank, db.triple = d_triple_id, db.conf = (int32_t*)e->conf.p;
+  db.fast = d_fast, db.deps = d_deps, db.leader_deps = d_leader_deps, db.own_values_end = d_own_values_end;
+  MkMerge mm;
+  memset(&mm, 0, sizeof(mm));
+  mm.m = m, mm.off = d_off, mm.uniq = mb.uniq, mm.pconf = sb.conf, mm.conf = db.conf, mm.leader = d_leader;
+  mm.resp_mask = d_resp_mask, mm.seen_mask = d_seen_mask;
+  const int segs = n * e->st.num_keys;
+  switch (n) {
+    case 3:
+      if (U > 0) hipLaunchKernelGGL((k_epx_scan<3>), dim3((segs + 3) / 4), blk, 0, e->stream, e->st, sb);
+      hipLaunchKernelGGL((k_mk_merge<3>), gm, blk, 0, e->stream, e->st, mm);
+      hipLaunchKernelGGL((k_epx_decide<3>), gm, blk, 0, e->stream, e->st, db);
+      break;
+    case 5:
+      if (U > 0) hipLaunchKernelGGL((k_epx_scan<5>), dim3((segs + 3) / 4), blk, 0, e->stream, e->st, sb);
+      hipLaunchKernelGGL((k_mk_merge<5>), gm, blk, 0, e->stream, e->st, mm);
+      hipLaunchKernelGGL((k_epx_decide<5>), gm, blk, 0, e->stream, e->st, db);
+      break;
+    default:
+      if (U > 0) hipLaunchKernelGGL((k_epx_scan<7>), dim3((segs + 3) / 4), blk, 0, e->stream, e->st, sb);
+      hipLaunchKernelGGL((k_mk_merge<7>), gm, blk, 0, e->stream, e->st, mm);
+      hipLaunchKernelGGL((k_epx_decide<7>), gm, blk, 0, e->stream, e->st, db);
+      break;
+  }
+  const long long tot = (long long)e->st.num_keys * n * n;
+  if (U > 0) hipLaunchKernelGGL(k_epx_commit, dim3((unsigned)((tot + 255) / 256)), blk, 0, e->stream, e->st, sb);
+  if (d_packed)
+    hipLaunchKernelGGL(k_epx_pack, gm, blk, 0, e->stream, e->st, m, d_fast, d_deps, d_leader_deps, d_own_values_end, d_packed,
+                       fpx_epx_packed_stride(n));
+  hipError_t le = hipGetLastError();
+  if (le != hipSuccess) {
+    e->last_hip = (int)le;
+    return FPX_EHIP;
+  }
+  return FPX_OK;
+}
+
+int32_t fpx_epx_preaccept_mk_dev(fpx_epx* e, int32_t m, const int32_t* d_leader, const int32_t* d_number, const int32_t* d_key_offsets,
+                                 const int32_t* d_keys, const uint8_t* d_is_set, const uint8_t* d_resp_mask,
+                                 const uint8_t* d_seen_mask, const int32_t* d_rank, const int32_t* d_triple_id, uint8_t* d_fast,
+                                 int32_t* d_deps, int32_t* d_leader_deps, int32_t* d_own_values_end) {
+  return preaccept_mk_impl(e, m, d_leader, d_number, d_key_offsets, d_keys, d_is_set, d_resp_mask, d_seen_mask, d_rank,
+                           d_triple_id, d_fast, d_deps, d_leader_deps, d_own_values_end, nullptr);
+}
+
+int32_t fpx_epx_preaccept_mk_packed_dev(fpx_epx* e, int32_t m, const int32_t* d_leader, const int32_t* d_number,
+                                        const int32_t* d_key_offsets, const int32_t* d_keys, const uint8_t* d_is_set,
+                                        const uint8_t* d_resp_mask, const uint8_t* d_seen_mask, const int32_t* d_rank,
+                                        const int32_t* d_triple_id, int32_t* d_packed) {
+  if (!d_packed && m > 0) return FPX_EINVAL;
+  return preaccept_mk_impl(e, m, d_leader, d_number, d_key_offsets, d_keys, d_is_set, d_resp_mask, d_seen_mask, d_rank,
+                           d_triple_id, nullptr, nullptr, nullptr, nullptr, d_packed);
+}
+
+int32_t fpx_epx_preaccept_mk(fpx_epx* e, int32_t m, const int32_t* leader, const int32_t* number, const int32_t* key_offsets,
+                             const int32_t* keys, const uint8_t* is_set, const uint8_t* resp_mask, const uint8_t* seen_mask,
+                             const int32_t* rank, const int32_t* triple_id, uint8_t* fast, int32_t* deps, int32_t* leader_deps,
+                             int32_t* own_values_end) {
+  if (!e || m < 0 || (m > 0 && (!leader || !number || !key_offsets || !is_set || !resp_mask || !rank))) return FPX_EINVAL;
+  EpxDeviceGuard _dg(e->cfg.device);
+  if (m == 0) return FPX_OK;
+  const int n = e->st.n;
+  int64_t P = 0;
+  int rc;
+  if ((rc = check_key_lists(m, key_offsets, keys, e->st.num_keys, &P))) return rc;
+  auto up = [&](Buf* b, const void* src, size_t bytes) -> int {
+    int r2 = grow(e, b, bytes);
+    if (r2) return r2;
+    EHIP(e, hipMemcpyAsync(b->p, src, bytes, hipMemcpyHostToDevice, e->stream));
+    return FPX_OK;
+  };
+  const int32_t *d_off = nullptr, *d_keys = nullptr;
+  if ((rc = upload_key_lists(e, m, key_offsets, keys, P, &d_off, &d_keys))) return rc;
+  if ((rc = up(&e->h_leader, leader, (size_t)m * 4))) return rc;
+  if ((rc = up(&e->h_number, number, (size_t)m * 4))) return rc;
+  if ((rc = up(&e->h_set, is_set, (size_t)m))) return rc;
+  if ((rc = up(&e->h_mask, resp_mask, (size_t)m))) return rc;
+  if (seen_mask && (rc = up(&e->h_seen, seen_mask, (size_t)m))) return rc;
+  if ((rc = up(&e->h_rank, rank, (size_t)n * m * 4))) return rc;
+  if (triple_id && (rc = up(&e->h_triple, triple_id, (size_t)m * 4))) return rc;
+  if ((rc = grow(e, &e->o_fast, (size_t)m))) return rc;
+  if ((rc = grow(e, &e->o_deps, (size_t)m * n * 4))) return rc;
+  if ((rc = grow(e, &e->o_ldeps, (size_t)m * n * 4))) return rc;
+  if ((rc = grow(e, &e->o_own, (size_t)m * 8))) return rc;
+  rc = fpx_epx_preaccept_mk_dev(e, m, (int32_t*)e->h_leader.p, (int32_t*)e->h_number.p, d_off, d_keys, (uint8_t*)e->h_set.p,
+                                (uint8_t*)e->h_mask.p, seen_mask ? (uint8_t*)e->h_seen.p : nullptr, (int32_t*)e->h_rank.p,
+                                triple_id ? (int32_t*)e->h_triple.p : nullptr, (uint8_t*)e->o_fast.p, (int32_t*)e->o_deps.p,
+                                (int32_t*)e->o_ldeps.p, (int32_t*)e->o_own.p);
+  if (rc) return rc;
+  if (fast) EHIP(e, hipMemcpyAsync(fast, e->o_fast.p, (size_t)m, hipMemcpyDeviceToHost, e->stream));
+  if (deps) EHIP(e, hipMemcpyAsync(deps, e->o_deps.p, (size_t)m * n * 4, hipMemcpyDeviceToHost, e->stream));
+  if (leader_deps) EHIP(e, hipMemcpyAsync(leader_deps, e->o_ldeps.p, (size_t)m * n * 4, hipMemcpyDeviceToHost, e->stream));
+  if (own_values_end) EHIP(e, hipMemcpyAsync(own_values_end, e->o_own.p, (size_t)m * 8, hipMemcpyDeviceToHost, e->stream));
+  return fpx_epx_sync(e);
+}
+
 // Prepare / Accept on the command log: stage, validate, handle, scan the largestBallot's, (Accept) tally + commit
 static int32_t cl_run(fpx_epx* e, int accept, int32_t m, const int32_t* leader, const int32_t* number,
                       const int32_t* b_ord, const int32_t* b_rep, const int32_t* triple, const int32_t* key,
                       const uint8_t* is_set, const uint8_t* target, uint8_t* ok_bits, uint8_t* nack_bits,
                       uint8_t* commit_bits, int32_t* nack_ballot, uint8_t* committed, int32_t* reply_status,
-                      int32_t* reply_vote, int32_t* reply_triple) {
+                      int32_t* reply_vote, int32_t* reply_triple, const int32_t* key_off = nullptr,
+                      const int32_t* keys = nullptr) {
   if (!e || m < 0) return FPX_EINVAL;
   EpxDeviceGuard _dg(e->cfg.device);
   if (e->st.num_instances <= 0) return FPX_EINVAL;
   if (m == 0) return FPX_OK;
-  if (!leader || !number || !b_ord || !b_rep || !target || (accept && (!triple || !key || !is_set))) return FPX_EINVAL;
+  if (!leader || !number || !b_ord || !b_rep || !target || (accept && (!triple || !(key || key_off) || !is_set))) return FPX_EINVAL;
   const int n = e->st.n;
+  const int32_t *d_off = nullptr, *d_keys = nullptr;
+  if (key_off) {
+    int64_t P = 0;
+    int rc0 = check_key_lists(m, key_off, keys, e->st.num_keys, &P);
+    if (rc0 || (rc0 = upload_key_lists(e, m, key_off, keys, P, &d_off, &d_keys))) return rc0;
+  }
   const int tiles = (m + CL_TILE - 1) / CL_TILE;
   const size_t mp = ((size_t)m + 63) & ~(size_t)63;
   // staging: 6 int32 inputs, is_set, target, 3 reply bit arrays, skip, committed, nack_ballot, 3 reply int arrays
@@ -2219,7 +2456,7 @@ static int32_t cl_run(fpx_epx* e, int accept, int32_t m, const int32_t* leader, 
   EHIP(e, hipMemcpyAsync(d_bo, b_ord, (size_t)m * 4, hipMemcpyHostToDevice, e->stream));
   EHIP(e, hipMemcpyAsync(d_br, b_rep, (size_t)m * 4, hipMemcpyHostToDevice, e->stream));
   if (accept) EHIP(e, hipMemcpyAsync(d_tr, triple, (size_t)m * 4, hipMemcpyHostToDevice, e->stream));
-  if (accept) EHIP(e, hipMemcpyAsync(d_key, key, (size_t)m * 4, hipMemcpyHostToDevice, e->stream));
+  if (accept && key) EHIP(e, hipMemcpyAsync(d_key, key, (size_t)m * 4, hipMemcpyHostToDevice, e->stream));
   if (accept) EHIP(e, hipMemcpyAsync(d_set, is_set, (size_t)m, hipMemcpyHostToDevice, e->stream));
   EHIP(e, hipMemcpyAsync(d_tgt, target, (size_t)m, hipMemcpyHostToDevice, e->stream));
   EHIP(e, hipMemsetAsync(d_ok, 0, mp * 5, e->stream));  // ok, nack, commit, skip, committed are contiguous
@@ -2227,7 +2464,7 @@ static int32_t cl_run(fpx_epx* e, int accept, int32_t m, const int32_t* leader, 
   ClBatch b;
   memset(&b, 0, sizeof(b));
   b.m = m, b.accept = accept, b.leader = d_leader, b.number = d_number, b.b_ord = d_bo, b.b_rep = d_br, b.triple = d_tr;
-  b.key = d_key, b.is_set = d_set;
+  b.key = d_key, b.is_set = d_set, b.key_off = d_off, b.keys = d_keys;
   b.target = d_tgt, b.ok_bits = d_ok, b.nack_bits = d_nack, b.commit_bits = d_com, b.nack_ballot = d_nb;
   b.committed = d_done, b.reply_status = d_rs, b.reply_vote = d_rv, b.reply_triple = d_rt;
   b.contrib = d_contrib, b.nackflag = d_flag, b.tilemax = d_tm, b.skip = d_skip;
@@ -2268,18 +2505,20 @@ int32_t fpx_epx_prepare(fpx_epx* e, int32_t m, const int32_t* leader, const int3
                 nack_bits, commit_bits, nack_ballot, nullptr, reply_status, reply_vote_ballot, reply_triple);
 }
 
-int32_t fpx_epx_handle_commit(fpx_epx* e, int32_t m, const int32_t* leader, const int32_t* number, const int32_t* triple_id,
-                              const int32_t* key, const uint8_t* is_set, const int32_t* deps, const int32_t* deps_values_end,
-                              const uint8_t* target_mask) {
+static int32_t handle_commit_impl(fpx_epx* e, int32_t m, const int32_t* leader, const int32_t* number, const int32_t* triple_id,
+                                  const int32_t* key, const int32_t* key_off, const int32_t* keys, const uint8_t* is_set,
+                                  const int32_t* deps, const int32_t* deps_values_end, const uint8_t* target_mask) {
   if (!e || m < 0) return FPX_EINVAL;
   EpxDeviceGuard _dg(e->cfg.device);
   if (e->st.num_instances <= 0) return FPX_EINVAL;
   if (m == 0) return FPX_OK;
-  if (!leader || !number || !triple_id || !key || !is_set || !target_mask) return FPX_EINVAL;
+  if (!leader || !number || !triple_id || !(key || key_off) || !is_set || !target_mask) return FPX_EINVAL;
   const int n = e->st.n;
+  int64_t P = 0;
+  if (key_off && check_key_lists(m, key_off, keys, e->st.num_keys, &P)) return FPX_EINVAL;
   for (int i = 0; i < m; ++i) {  // host arrays: checked here, nothing is applied on a bad one
-    if (leader[i] < 0 || leader[i] >= n || number[i] < 0 || number[i] >= e->st.num_instances || key[i] < -1 || key[i] >= e->st.num_keys ||
-        (target_mask[i] >> n) != 0)
+    if (leader[i] < 0 || leader[i] >= n || number[i] < 0 || number[i] >= e->st.num_instances ||
+        (!key_off && (key[i] < -1 || key[i] >= e->st.num_keys)) || (target_mask[i] >> n) != 0)
       return FPX_EINVAL;
     if (deps) {
       for (int l = 0; l < n; ++l)
@@ -2325,13 +2564,16 @@ int32_t fpx_epx_handle_commit(fpx_epx* e, int32_t m, const int32_t* leader, cons
   EHIP(e, hipMemcpyAsync(d_leader, leader, (size_t)m * 4, hipMemcpyHostToDevice, e->stream));
   EHIP(e, hipMemcpyAsync(d_number, number, (size_t)m * 4, hipMemcpyHostToDevice, e->stream));
   EHIP(e, hipMemcpyAsync(d_tr, triple_id, (size_t)m * 4, hipMemcpyHostToDevice, e->stream));
-  EHIP(e, hipMemcpyAsync(d_key, key, (size_t)m * 4, hipMemcpyHostToDevice, e->stream));
+  if (key) EHIP(e, hipMemcpyAsync(d_key, key, (size_t)m * 4, hipMemcpyHostToDevice, e->stream));
   EHIP(e, hipMemcpyAsync(d_set, is_set, (size_t)m, hipMemcpyHostToDevice, e->stream));
   EHIP(e, hipMemcpyAsync(d_tgt, target_mask, (size_t)m, hipMemcpyHostToDevice, e->stream));
+  const int32_t *d_off = nullptr, *d_keys = nullptr;
+  if (key_off && (rc = upload_key_lists(e, m, key_off, keys, P, &d_off, &d_keys))) return rc;
   if (deps) EHIP(e, hipMemcpyAsync(d_deps, deps, (size_t)m * n * 4, hipMemcpyHostToDevice, e->stream));
   if (deps && deps_values_end) EHIP(e, hipMemcpyAsync(d_end, deps_values_end, (size_t)m * 4, hipMemcpyHostToDevice, e->stream));
   LcBatch b;
   b.m = m, b.leader = d_leader, b.number = d_number, b.triple = d_tr, b.key = d_key, b.is_set = d_set;
+  b.key_off = d_off, b.keys = d_keys;
   b.deps = deps ? d_deps : nullptr, b.deps_end = (deps && deps_values_end) ? d_end : nullptr, b.target = d_tgt, b.writer = d_wr;
   hipLaunchKernelGGL(k_cl_learn_commit, dim3((unsigned)(((long long)m * n + 255) / 256)), dim3(256), 0, e->stream, e->st, b);
   hipError_t le = hipGetLastError();
@@ -2394,24 +2636,29 @@ int32_t fpx_epx_accept(fpx_epx* e, int32_t m, const int32_t* leader, const int32
                 nack_bits, commit_bits, nack_ballot, committed, nullptr, nullptr, nullptr);
 }
 
-int32_t fpx_epx_handle_preaccept(fpx_epx* e, int32_t m, const int32_t* leader, const int32_t* number,
-                                 const int32_t* ballot_ordering, const int32_t* ballot_replica, const int32_t* key,
-                                 const uint8_t* is_set, const int32_t* triple_id, const int32_t* deps_in,
-                                 const int32_t* deps_in_values_end, const uint8_t* target_mask, uint8_t* ok_bits,
-                                 uint8_t* resend_bits, uint8_t* nack_bits, uint8_t* commit_bits, int32_t* nack_ballot,
-                                 int32_t* reply_deps, int32_t* reply_values_end, int32_t* reply_triple) {
+static int32_t handle_preaccept_impl(fpx_epx* e, int32_t m, const int32_t* leader, const int32_t* number,
+                                     const int32_t* ballot_ordering, const int32_t* ballot_replica, const int32_t* key,
+                                     const int32_t* key_off, const int32_t* keys,
+                                     const uint8_t* is_set, const int32_t* triple_id, const int32_t* deps_in,
+                                     const int32_t* deps_in_values_end, const uint8_t* target_mask, uint8_t* ok_bits,
+                                     uint8_t* resend_bits, uint8_t* nack_bits, uint8_t* commit_bits, int32_t* nack_ballot,
+                                     int32_t* reply_deps, int32_t* reply_values_end, int32_t* reply_triple) {
   if (!e || m < 0) return FPX_EINVAL;
   EpxDeviceGuard _dg(e->cfg.device);
   if (e->st.num_instances <= 0) return FPX_EINVAL;
   if (m == 0) return FPX_OK;
-  if (!leader || !number || !ballot_ordering || !ballot_replica || !key || !is_set || !deps_in || !target_mask)
+  if (!leader || !number || !ballot_ordering || !ballot_replica || !(key || key_off) || !is_set || !deps_in || !target_mask)
     return FPX_EINVAL;
   const int n = e->st.n;
+  // key lists: P pairs in array order instead of m messages in the scan (pair j of the CSR at position j)
+  int64_t P64 = 0;
+  if (key_off && check_key_lists(m, key_off, keys, e->st.num_keys, &P64)) return FPX_EINVAL;
+  const int P = key_off ? (int)P64 : m;
   const int tiles = (m + CL_TILE - 1) / CL_TILE;
   const size_t mp = ((size_t)m + 63) & ~(size_t)63;
   int rc;
-  if ((rc = grow(e, &e->kv, (size_t)n * m * 8))) return rc;
-  if ((rc = grow(e, &e->kv2, (size_t)n * m * 8))) return rc;
+  if ((rc = grow(e, &e->kv, (size_t)n * std::max(P, 1) * 8))) return rc;
+  if ((rc = grow(e, &e->kv2, (size_t)n * std::max(P, 1) * 8))) return rc;
   if ((rc = grow(e, &e->tick, (size_t)n * e->st.num_keys * 2 * n * 4))) return rc;
   if ((rc = grow(e, &e->seg, (size_t)n * e->st.num_keys * 8))) return rc;
   if ((rc = grow(e, &e->conf, (size_t)m * n * (n <= 4 ? 4 : 8) * 4))) return rc;
@@ -2439,7 +2686,19 @@ int32_t fpx_epx_handle_preaccept(fpx_epx* e, int32_t m, const int32_t* leader, c
   EHIP(e, up(d_number, number, (size_t)m * 4));
   EHIP(e, up(d_bo, ballot_ordering, (size_t)m * 4));
   EHIP(e, up(d_br, ballot_replica, (size_t)m * 4));
-  EHIP(e, up(d_key, key, (size_t)m * 4));
+  if (key) EHIP(e, up(d_key, key, (size_t)m * 4));
+  const int32_t *d_off = nullptr, *d_keys = nullptr;
+  int32_t* d_pconf = nullptr;
+  MkBatch mb;
+  memset(&mb, 0, sizeof(mb));
+  if (key_off) {
+    if ((rc = upload_key_lists(e, m, key_off, keys, P, &d_off, &d_keys))) return rc;
+    if ((rc = grow(e, &e->mk_pair, (size_t)std::max(P, 1) * 5 + 64))) return rc;
+    if ((rc = grow(e, &e->mk_pconf, (size_t)std::max(P, 1) * n * (n <= 4 ? 4 : 8) * 4))) return rc;
+    d_pconf = (int32_t*)e->mk_pconf.p;
+    mb.m = m, mb.P = P, mb.off = d_off, mb.keys = d_keys, mb.number = d_number;
+    mb.pnum = (int32_t*)e->mk_pair.p, mb.uniq = (uint8_t*)e->mk_pair.p + (size_t)std::max(P, 1) * 4;
+  }
   if (triple_id) EHIP(e, up(d_tr, triple_id, (size_t)m * 4));
   if (deps_in_values_end) EHIP(e, up(d_dend, deps_in_values_end, (size_t)m * 4));
   EHIP(e, up(d_din, deps_in, (size_t)m * n * 4));
@@ -2450,6 +2709,7 @@ int32_t fpx_epx_handle_preaccept(fpx_epx* e, int32_t m, const int32_t* leader, c
   HpBatch hb;
   memset(&hb, 0, sizeof(hb));
   hb.m = m, hb.leader = d_leader, hb.number = d_number, hb.b_ord = d_bo, hb.b_rep = d_br, hb.key = d_key, hb.is_set = d_set;
+  if (key_off) hb.key = nullptr, hb.key_off = d_off, hb.keys = d_keys, hb.uniq = mb.uniq, hb.P = P;
   hb.triple = triple_id ? d_tr : nullptr, hb.deps_in = d_din, hb.dend_in = deps_in_values_end ? d_dend : nullptr;
   hb.target = d_tgt, hb.ok_bits = d_ok, hb.resend_bits = d_resend, hb.nack_bits = d_nack, hb.commit_bits = d_com;
   hb.reply_deps = d_rd, hb.reply_end = d_re, hb.reply_triple = d_rt;
@@ -2462,17 +2722,20 @@ int32_t fpx_epx_handle_preaccept(fpx_epx* e, int32_t m, const int32_t* leader, c
   hb.run_id = e->cl_run;
   const dim3 gm((m + 255) / 256), gmn((unsigned)(((long long)m * n + 255) / 256)), blk(256);
   hipLaunchKernelGGL(k_hp_validate, gm, blk, 0, e->stream, e->st, hb);
+  if (key_off) hipLaunchKernelGGL(k_mk_pairs, gm, blk, 0, e->stream, mb);
   hipLaunchKernelGGL(k_hp_gate, gmn, blk, 0, e->stream, e->st, hb);
   // the conflict scan of what each replica processes, in array order: K5's sort / segments / scan
   EpxBatch sb;
   memset(&sb, 0, sizeof(sb));
-  sb.m = m, sb.number = d_number, sb.kv = hb.kv;
+  sb.m = P, sb.number = key_off ? mb.pnum : d_number, sb.kv = hb.kv;
   const uint32_t* key_totals = nullptr;
   int key_buckets = 0;
-  sb.kv_sorted = sort_by_key(e, m, hb.kv, (uint2*)e->kv2.p, nullptr, &rc, &key_totals, &key_buckets);
-  if (rc) return rc;
-  sb.tick = (int32_t*)e->tick.p, sb.seg = (int32_t*)e->seg.p, sb.conf = (int32_t*)e->conf.p;
-  launch_segments(e, sb, key_totals, key_buckets);
+  if (P > 0) {  // (key lists that are all empty: nothing to scan, nothing for the index to learn)
+    sb.kv_sorted = sort_by_key(e, P, hb.kv, (uint2*)e->kv2.p, nullptr, &rc, &key_totals, &key_buckets);
+    if (rc) return rc;
+  }
+  sb.tick = (int32_t*)e->tick.p, sb.seg = (int32_t*)e->seg.p, sb.conf = key_off ? d_pconf : (int32_t*)e->conf.p;
+  if (P > 0) launch_segments(e, sb, key_totals, key_buckets);
   // the largestBallot every Nack carries: prefix max per replica over the ballots it took in (as for Prepare / Accept)
   ClBatch cb;
   memset(&cb, 0, sizeof(cb));
@@ -2480,13 +2743,16 @@ int32_t fpx_epx_handle_preaccept(fpx_epx* e, int32_t m, const int32_t* leader, c
   hipLaunchKernelGGL(k_cl_tilemax, dim3(tiles, n), blk, 0, e->stream, cb, tiles);
   hipLaunchKernelGGL(k_cl_tilescan, dim3(n), blk, 0, e->stream, e->st, cb, tiles);
   hipLaunchKernelGGL(k_cl_nacks, dim3(tiles, n), blk, 0, e->stream, cb, tiles);
+  MkMerge mm;
+  memset(&mm, 0, sizeof(mm));
+  mm.m = m, mm.off = d_off, mm.uniq = mb.uniq, mm.pconf = d_pconf, mm.conf = (int32_t*)e->conf.p, mm.act = d_act;
   switch (n) {
-    case 3: launch_hp<3>(e, sb, hb); break;
-    case 5: launch_hp<5>(e, sb, hb); break;
-    default: launch_hp<7>(e, sb, hb); break;
+    case 3: launch_hp<3>(e, sb, hb, key_off ? &mm : nullptr, P > 0); break;
+    case 5: launch_hp<5>(e, sb, hb, key_off ? &mm : nullptr, P > 0); break;
+    default: launch_hp<7>(e, sb, hb, key_off ? &mm : nullptr, P > 0); break;
   }
   const long long tot = (long long)e->st.num_keys * n * n;
-  hipLaunchKernelGGL(k_hp_commit, dim3((unsigned)((tot + 255) / 256)), blk, 0, e->stream, e->st, hb);
+  if (P > 0) hipLaunchKernelGGL(k_hp_commit, dim3((unsigned)((tot + 255) / 256)), blk, 0, e->stream, e->st, hb);
   hipError_t le = hipGetLastError();
   if (le != hipSuccess) {
     e->last_hip = (int)le;
@@ -2550,6 +2816,51 @@ int32_t fpx_epx_read_index(fpx_epx* e, int32_t replica, int32_t key, int32_t* ge
   if (gets) EHIP(e, hipMemcpy(gets, e->st.gets + off, (size_t)e->st.n * 4, hipMemcpyDeviceToHost));
   if (sets) EHIP(e, hipMemcpy(sets, e->st.sets + off, (size_t)e->st.n * 4, hipMemcpyDeviceToHost));
   return FPX_OK;
+}
+
+int32_t fpx_epx_accept_mk(fpx_epx* e, int32_t m, const int32_t* leader, const int32_t* number, const int32_t* ballot_ordering,
+                          const int32_t* ballot_replica, const int32_t* triple_id, const int32_t* key_offsets, const int32_t* keys,
+                          const uint8_t* is_set, const uint8_t* target_mask, uint8_t* ok_bits, uint8_t* nack_bits,
+                          uint8_t* commit_bits, int32_t* nack_ballot, uint8_t* committed) {
+  if (m > 0 && !key_offsets) return FPX_EINVAL;
+  return cl_run(e, 1, m, leader, number, ballot_ordering, ballot_replica, triple_id, nullptr, is_set, target_mask, ok_bits,
+                nack_bits, commit_bits, nack_ballot, committed, nullptr, nullptr, nullptr, key_offsets, keys);
+}
+
+int32_t fpx_epx_handle_commit(fpx_epx* e, int32_t m, const int32_t* leader, const int32_t* number, const int32_t* triple_id,
+                              const int32_t* key, const uint8_t* is_set, const int32_t* deps, const int32_t* deps_values_end,
+                              const uint8_t* target_mask) {
+  return handle_commit_impl(e, m, leader, number, triple_id, key, nullptr, nullptr, is_set, deps, deps_values_end, target_mask);
+}
+
+int32_t fpx_epx_handle_commit_mk(fpx_epx* e, int32_t m, const int32_t* leader, const int32_t* number, const int32_t* triple_id,
+                                 const int32_t* key_offsets, const int32_t* keys, const uint8_t* is_set, const int32_t* deps,
+                                 const int32_t* deps_values_end, const uint8_t* target_mask) {
+  if (m > 0 && !key_offsets) return FPX_EINVAL;
+  return handle_commit_impl(e, m, leader, number, triple_id, nullptr, key_offsets, keys, is_set, deps, deps_values_end, target_mask);
+}
+
+int32_t fpx_epx_handle_preaccept(fpx_epx* e, int32_t m, const int32_t* leader, const int32_t* number,
+                                 const int32_t* ballot_ordering, const int32_t* ballot_replica, const int32_t* key,
+                                 const uint8_t* is_set, const int32_t* triple_id, const int32_t* deps_in,
+                                 const int32_t* deps_in_values_end, const uint8_t* target_mask, uint8_t* ok_bits,
+                                 uint8_t* resend_bits, uint8_t* nack_bits, uint8_t* commit_bits, int32_t* nack_ballot,
+                                 int32_t* reply_deps, int32_t* reply_values_end, int32_t* reply_triple) {
+  return handle_preaccept_impl(e, m, leader, number, ballot_ordering, ballot_replica, key, nullptr, nullptr, is_set, triple_id,
+                               deps_in, deps_in_values_end, target_mask, ok_bits, resend_bits, nack_bits, commit_bits, nack_ballot,
+                               reply_deps, reply_values_end, reply_triple);
+}
+
+int32_t fpx_epx_handle_preaccept_mk(fpx_epx* e, int32_t m, const int32_t* leader, const int32_t* number,
+                                    const int32_t* ballot_ordering, const int32_t* ballot_replica, const int32_t* key_offsets,
+                                    const int32_t* keys, const uint8_t* is_set, const int32_t* triple_id, const int32_t* deps_in,
+                                    const int32_t* deps_in_values_end, const uint8_t* target_mask, uint8_t* ok_bits,
+                                    uint8_t* resend_bits, uint8_t* nack_bits, uint8_t* commit_bits, int32_t* nack_ballot,
+                                    int32_t* reply_deps, int32_t* reply_values_end, int32_t* reply_triple) {
+  if (m > 0 && !key_offsets) return FPX_EINVAL;
+  return handle_preaccept_impl(e, m, leader, number, ballot_ordering, ballot_replica, nullptr, key_offsets, keys, is_set, triple_id,
+                               deps_in, deps_in_values_end, target_mask, ok_bits, resend_bits, nack_bits, commit_bits, nack_ballot,
+                               reply_deps, reply_values_end, reply_triple);
 }
 
 }  // extern "C"

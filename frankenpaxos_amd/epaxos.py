@@ -160,6 +160,101 @@ class EPaxos:
                                              p(re), p(rt))
         return st, ok, resend, nack, com, nb, rd, re, rt
 
+    # ---- multi-key commands (the _mk entry points): key_lists = one list of keys per command, or (key_offsets, keys) ----
+    @staticmethod
+    def key_lists(key_lists):
+        """[[k, ...], ...] or (key_offsets[m + 1], keys) -> the CSR pair of int32 arrays"""
+        if isinstance(key_lists, tuple) and len(key_lists) == 2 and all(isinstance(a, np.ndarray) for a in key_lists):
+            return np.ascontiguousarray(key_lists[0], np.int32), np.ascontiguousarray(key_lists[1], np.int32)
+        off = np.zeros(len(key_lists) + 1, np.int32)
+        off[1:] = np.cumsum([len(k) for k in key_lists])
+        keys = np.ascontiguousarray([k for ks in key_lists for k in ks], np.int32)
+        return off, keys
+
+    def preaccept_mk(self, leader, number, key_lists, is_set, resp_mask, rank, seen_mask=None, triple_id=None):
+        """preaccept() with any number of keys per command: (status, fast, deps, leader_deps, own_values_end)"""
+        a32 = lambda x: np.ascontiguousarray(x, dtype=np.int32)
+        a8 = lambda x: np.ascontiguousarray(x, dtype=np.uint8)
+        off, keys = self.key_lists(key_lists)
+        leader, number, rank = a32(leader), a32(number), a32(rank)
+        is_set, resp_mask = a8(is_set), a8(resp_mask)
+        seen_mask = None if seen_mask is None else a8(seen_mask)
+        triple_id = None if triple_id is None else a32(triple_id)
+        m = len(leader)
+        fast = np.zeros(m, np.uint8)
+        deps, ldeps = np.zeros((m, self.n), np.int32), np.zeros((m, self.n), np.int32)
+        own = np.zeros((m, 2), np.int32)
+        p = lambda a: None if a is None else a.ctypes.data
+        st = self.L.fpx_epx_preaccept_mk(self._h, m, p(leader), p(number), p(off), p(keys), p(is_set), p(resp_mask),
+                                         p(seen_mask), p(rank), p(triple_id), p(fast), p(deps), p(ldeps), p(own))
+        return st, fast, deps, ldeps, own
+
+    def preaccept_mk_dev(self, leader, number, key_offsets, keys, is_set, resp_mask, rank, fast=None, deps=None,
+                         leader_deps=None, seen_mask=None, own_values_end=None, triple_id=None):
+        d = lambda t: None if t is None else t.data_ptr()
+        st = self.L.fpx_epx_preaccept_mk_dev(self._h, leader.numel(), d(leader), d(number), d(key_offsets), d(keys),
+                                             d(is_set), d(resp_mask), d(seen_mask), d(rank), d(triple_id), d(fast), d(deps),
+                                             d(leader_deps), d(own_values_end))
+        if st:
+            raise FpxError(st, "fpx_epx_preaccept_mk_dev")
+
+    def preaccept_mk_packed_dev(self, leader, number, key_offsets, keys, is_set, resp_mask, rank, packed, seen_mask=None,
+                                triple_id=None):
+        d = lambda t: None if t is None else t.data_ptr()
+        st = self.L.fpx_epx_preaccept_mk_packed_dev(self._h, leader.numel(), d(leader), d(number), d(key_offsets), d(keys),
+                                                    d(is_set), d(resp_mask), d(seen_mask), d(rank), d(triple_id), d(packed))
+        if st:
+            raise FpxError(st, "fpx_epx_preaccept_mk_packed_dev")
+
+    def handle_preaccept_mk(self, leader, number, ballot_ordering, ballot_replica, key_lists, is_set, triple_id, deps_in,
+                            deps_in_values_end, target_mask):
+        """handle_preaccept() with a key list per command (an empty list: no conflicts, no put)"""
+        a32 = lambda x: None if x is None else np.ascontiguousarray(x, dtype=np.int32)
+        off, keys = self.key_lists(key_lists)
+        leader, number, bo, br = a32(leader), a32(number), a32(ballot_ordering), a32(ballot_replica)
+        is_set = np.ascontiguousarray(is_set, dtype=np.uint8)
+        tr, din, dend = a32(triple_id), a32(deps_in), a32(deps_in_values_end)
+        tgt = np.ascontiguousarray(target_mask, dtype=np.uint8)
+        m = len(leader)
+        ok, resend, nack, com = (np.zeros(m, np.uint8) for _ in range(4))
+        nb = np.full(m, -1, np.int32)
+        rd = np.zeros((m, self.n, self.n), np.int32)
+        re = np.zeros((m, self.n), np.int32)
+        rt = np.full((m, self.n), -1, np.int32)
+        p = lambda a: None if a is None else a.ctypes.data
+        st = self.L.fpx_epx_handle_preaccept_mk(self._h, m, p(leader), p(number), p(bo), p(br), p(off), p(keys), p(is_set),
+                                                p(tr), p(din), p(dend), p(tgt), p(ok), p(resend), p(nack), p(com), p(nb),
+                                                p(rd), p(re), p(rt))
+        return st, ok, resend, nack, com, nb, rd, re, rt
+
+    def accept_mk(self, leader, number, ballot_ordering, ballot_replica, triple_id, target_mask, key_lists, is_set):
+        """accept() with a key list per triple: (status, ok_bits, nack_bits, commit_bits, nack_ballot, committed)"""
+        a32 = lambda x: np.ascontiguousarray(x, dtype=np.int32)
+        off, keys = self.key_lists(key_lists)
+        leader, number, bo, br, tr = a32(leader), a32(number), a32(ballot_ordering), a32(ballot_replica), a32(triple_id)
+        tgt = np.ascontiguousarray(target_mask, dtype=np.uint8)
+        is_set = np.ascontiguousarray(is_set, dtype=np.uint8)
+        m = len(leader)
+        ok, nack, com, done = (np.zeros(m, np.uint8) for _ in range(4))
+        nb = np.full(m, -1, np.int32)
+        p = lambda a: a.ctypes.data
+        st = self.L.fpx_epx_accept_mk(self._h, m, p(leader), p(number), p(bo), p(br), p(tr), p(off), p(keys), p(is_set),
+                                      p(tgt), p(ok), p(nack), p(com), p(nb), p(done))
+        return st, ok, nack, com, nb, done
+
+    def handle_commit_mk(self, leader, number, triple_id, target_mask, key_lists, is_set, deps=None, deps_values_end=None):
+        """handle_commit() with a key list per triple -> status"""
+        a32 = lambda x: None if x is None else np.ascontiguousarray(x, dtype=np.int32)
+        off, keys = self.key_lists(key_lists)
+        leader, number, tr = a32(leader), a32(number), a32(triple_id)
+        m = len(leader)
+        tgt = np.ascontiguousarray(target_mask, dtype=np.uint8)
+        is_set = np.ascontiguousarray(is_set, dtype=np.uint8)
+        d, de = a32(deps), a32(deps_values_end)
+        p = lambda a: None if a is None else a.ctypes.data
+        return self.L.fpx_epx_handle_commit_mk(self._h, m, p(leader), p(number), p(tr), p(off), p(keys), p(is_set), p(d), p(de),
+                                               p(tgt))
+
     def read_cmdlog_deps(self, replica, leader, number):
         """the dependencies kept with a command-log entry: (watermarks[n], values_end)"""
         deps, end = np.zeros(self.n, np.int32), np.zeros(1, np.int32)

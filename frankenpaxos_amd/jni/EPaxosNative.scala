@@ -25,8 +25,9 @@
 // (:1121-1147).  A Commit from a replica outside is recorded in the device's command log and conflict index
 // (Native.epxHandleCommit: Replica.handleCommit :1567-1575) and executed like the others.
 //
-// Scope (DESIGN.md section 8): single-key get / set commands of the key-value store (statemachine/KeyValueStore.scala),
-// top-one dependencies, sequence number 0; the leader-side recovery timers (Replica.scala:1021-1078) stay with a
+// Scope (DESIGN.md section 8): get / set commands of the key-value store with any number of keys
+// (statemachine/KeyValueStore.scala:221-302; a burst whose commands all have one key takes the single-key natives, any
+// other burst their multi-key forms Native.epx*Mk; only KeyValueStoreInput.Request.Empty is fatal), top-one dependencies, sequence number 0; the leader-side recovery timers (Replica.scala:1021-1078) stay with a
 // reference Replica if one is wanted -- Prepare / PrepareOk are answered here, not originated; the answers carry what
 // the reference's handlePrepareOk reads (:1819-1843: sequenceNumber and dependencies of a PreAccepted / Accepted entry,
 // the Commit for a committed one, Replica.nullBallot for an instance never seen).  `leaderStates` (the
@@ -67,13 +68,25 @@ class GpuEPaxosEngine[Transport <: frankenpaxos.Transport[Transport]](
   private val keyIds = mutable.Map[String, Int]()
   def keyOf(k: String): Int = keyIds.getOrElseUpdate(k, { logger.check(keyIds.size < numKeys); keyIds.size })
 
-  // (key id, is set) of a key-value-store command; anything else is outside the device's conflict model
-  def classify(c: Command): (Int, Boolean) =
+  // (key ids, is set) of a key-value-store command, any number of keys (KeyValueStore.scala:221-302 merges and puts over
+  // all of them); only a request that is neither a get nor a set is outside the device's conflict model
+  def classify(c: Command): (Array[Int], Boolean) =
     KeyValueStoreInput.parseFrom(c.command.toByteArray).request match {
-      case KeyValueStoreInput.Request.GetRequest(GetRequest(Seq(k)))             => (keyOf(k), false)
-      case KeyValueStoreInput.Request.SetRequest(SetRequest(Seq(kv)))            => (keyOf(kv.key), true)
-      case _ => logger.fatal("GpuEPaxosEngine: single-key get / set commands only (DESIGN.md section 8).")
+      case KeyValueStoreInput.Request.GetRequest(GetRequest(keys))               => (keys.map(keyOf).toArray, false)
+      case KeyValueStoreInput.Request.SetRequest(SetRequest(kvs))                => (kvs.map(kv => keyOf(kv.key)).toArray, true)
+      case _ => logger.fatal("GpuEPaxosEngine: get / set commands of the key-value store only (Request.Empty).")
     }
+  // the same for a triple's commandOrNoop: a Noop has no keys to put (None)
+  def classify(c: CommandOrNoop): (Option[Array[Int]], Boolean) =
+    if (c.value.isNoop) (None, false) else { val (k, s) = classify(c.getCommand); (Some(k), s) }
+
+  // A burst goes to the natives it has always gone to when every command has exactly one key (key -1 = Noop); any other
+  // burst takes the multi-key natives (Native.epx*Mk), which take the keys as keyOffsets (m + 1) + keys -- a Noop is an
+  // empty list there, which the device treats exactly like a Noop (no dependencies, nothing put).
+  def singleKeys(ks: Seq[Option[Array[Int]]]): Boolean = ks.forall(_.forall(_.length == 1))
+  def singleKey(ks: Seq[Option[Array[Int]]]): Array[Int] = ks.map(_.map(_(0)).getOrElse(-1)).toArray
+  def keyOffsets(ks: Seq[Option[Array[Int]]]): Array[Int] = ks.scanLeft(0)(_ + _.map(_.length).getOrElse(0)).toArray
+  def keyList(ks: Seq[Option[Array[Int]]]): Array[Int] = ks.flatMap(_.getOrElse(Array.empty[Int])).toArray
 
   def close(): Unit = Native.check(Native.epxDestroy(handle), logger)
 }
@@ -260,7 +273,7 @@ class GpuEPaxosReplica[Transport <: frankenpaxos.Transport[Transport]](
     val m = requests.size
     if (m > 0) {
       val leader = Array.fill(m)(index); val number = new Array[Int](m)
-      val key = new Array[Int](m); val isSet = new Array[Byte](m)
+      val keys = new Array[Option[Array[Int]]](m); val isSet = new Array[Byte](m)
       val resp = new Array[Byte](m); val seen = new Array[Byte](m)
       val rank = Array.tabulate(n * m)(i => i % m)
       val others = (0 until n).filter(_ != index)
@@ -268,20 +281,31 @@ class GpuEPaxosReplica[Transport <: frankenpaxos.Transport[Transport]](
       val first = engine.triples.size
       for (((_, r), i) <- requests.zipWithIndex) {
         number(i) = engine.nextNumber(index); engine.nextNumber(index) += 1
-        val (k, set) = engine.classify(r.command); key(i) = k; isSet(i) = if (set) 1 else 0
+        val (k, set) = engine.classify(r.command); keys(i) = Some(k); isSet(i) = if (set) 1 else 0
         resp(i) = counted; seen(i) = all
         engine.triples += CommandOrNoop().withCommand(r.command)
       }
       val fast = new Array[Byte](m); val deps = new Array[Int](m * n); val ldeps = new Array[Int](m * n); val ends = new Array[Int](2 * m)
-      Native.check(Native.epxPreaccept(engine.handle, m, n, leader, number, key, isSet, resp, seen, rank, fast, deps, ldeps, ends), logger)
+      Native.check(if (engine.singleKeys(keys))
+                     Native.epxPreaccept(engine.handle, m, n, leader, number, engine.singleKey(keys), isSet, resp, seen, rank, fast,
+                                         deps, ldeps, ends)
+                   else
+                     Native.epxPreacceptMk(engine.handle, m, n, leader, number, engine.keyOffsets(keys), engine.keyList(keys), isSet,
+                                           resp, seen, rank, fast, deps, ldeps, ends), logger)
       // the slow path: Accept with the union of the answers (preAcceptingSlowPath :796-813), f other replicas + the proposer
       val slow = (0 until m).filter(fast(_) == 0).toArray
       if (slow.nonEmpty) {
         val k = slow.length
         val tgt = Array.fill(k)(others.take(config.f).map(1 << _).sum.toByte)
         val replies = new Array[Byte](4 * k); val nb = new Array[Int](k)
-        Native.check(Native.epxAccept(engine.handle, k, slow.map(leader), slow.map(number), Array.fill(k)(0), Array.fill(k)(index),
-                                      slow.map(first + _), slow.map(key), slow.map(isSet), tgt, replies, nb), logger)
+        val sk = slow.map(keys).toSeq
+        Native.check(if (engine.singleKeys(sk))
+                       Native.epxAccept(engine.handle, k, slow.map(leader), slow.map(number), Array.fill(k)(0), Array.fill(k)(index),
+                                        slow.map(first + _), engine.singleKey(sk), slow.map(isSet), tgt, replies, nb)
+                     else
+                       Native.epxAcceptMk(engine.handle, k, slow.map(leader), slow.map(number), Array.fill(k)(0), Array.fill(k)(index),
+                                          slow.map(first + _), engine.keyOffsets(sk), engine.keyList(sk), slow.map(isSet), tgt, replies,
+                                          nb), logger)
         for ((i, j) <- slow.zipWithIndex) logger.check(replies(3 * k + j) != 0)   // f + 1 votes: committed (no competing ballot exists)
       }
       // commit (:815-860): every replica outside this process learns it; the hosted ones already hold the CommittedEntry
@@ -316,15 +340,17 @@ class GpuEPaxosReplica[Transport <: frankenpaxos.Transport[Transport]](
       val endsOf = mutable.Map[Commit, Int]()
       if (forDevice.nonEmpty) {
         val k = forDevice.size
-        val keyset = forDevice.map(c => if (c.commandOrNoop.value.isNoop) (-1, false) else engine.classify(c.commandOrNoop.getCommand))
+        val keyset = forDevice.map(c => engine.classify(c.commandOrNoop)); val ks = keyset.map(_._1)
         val first = engine.triples.size; forDevice.foreach(c => engine.triples += c.commandOrNoop)
         val own = forDevice.map(c => c.dependencies.intPrefixSet(c.instance.replicaIndex).value)
         val endsIn = own.map(v => if (v.isEmpty) 0 else v.max + 1).toArray
-        Native.check(Native.epxHandleCommit(engine.handle, k, n, forDevice.map(_.instance.replicaIndex).toArray,
-                                            forDevice.map(_.instance.instanceNumber).toArray, Array.tabulate(k)(first + _),
-                                            keyset.map(_._1).toArray, keyset.map(x => (if (x._2) 1 else 0).toByte).toArray,
-                                            forDevice.flatMap(c => watermarks(c.dependencies)).toArray, endsIn,
-                                            Array.fill(k)(bit(index))), logger)
+        val (ls, ns, ts) = (forDevice.map(_.instance.replicaIndex).toArray, forDevice.map(_.instance.instanceNumber).toArray,
+                            Array.tabulate(k)(first + _))
+        val (sets, ws, tg) = (keyset.map(x => (if (x._2) 1 else 0).toByte).toArray,
+                              forDevice.flatMap(c => watermarks(c.dependencies)).toArray, Array.fill(k)(bit(index)))
+        Native.check(if (engine.singleKeys(ks)) Native.epxHandleCommit(engine.handle, k, n, ls, ns, ts, engine.singleKey(ks), sets, ws, endsIn, tg)
+                     else Native.epxHandleCommitMk(engine.handle, k, n, ls, ns, ts, engine.keyOffsets(ks), engine.keyList(ks), sets, ws,
+                                                   endsIn, tg), logger)
         for ((c, i) <- forDevice.zipWithIndex) endsOf(c) = endsIn(i)
       }
       for (c <- commits) {
@@ -339,15 +365,21 @@ class GpuEPaxosReplica[Transport <: frankenpaxos.Transport[Transport]](
     if (preAccepts.nonEmpty) {
       val k = preAccepts.size
       val ps = preAccepts.map(_._2)
-      val keyset = ps.map(p => if (p.commandOrNoop.value.isNoop) (-1, false) else engine.classify(p.commandOrNoop.getCommand))
+      val keyset = ps.map(p => engine.classify(p.commandOrNoop)); val ks = keyset.map(_._1)
       val first = engine.triples.size; ps.foreach(p => engine.triples += p.commandOrNoop)
       val depsIn = ps.flatMap(p => watermarks(p.dependencies)).toArray
       val endsIn = ps.map(p => { val v = p.dependencies.intPrefixSet(p.instance.replicaIndex).value; if (v.isEmpty) 0 else v.max + 1 }).toArray
       val replies = new Array[Byte](4 * k); val nb = new Array[Int](k); val rd = new Array[Int](k * n * n); val ret = new Array[Int](2 * k * n)
-      Native.check(Native.epxHandlePreaccept(engine.handle, k, n, ps.map(_.instance.replicaIndex).toArray, ps.map(_.instance.instanceNumber).toArray,
-                                             ps.map(_.ballot.ordering).toArray, ps.map(_.ballot.replicaIndex).toArray, keyset.map(_._1).toArray,
-                                             keyset.map(x => (if (x._2) 1 else 0).toByte).toArray, Array.tabulate(k)(first + _), depsIn, endsIn,
-                                             Array.fill(k)(bit(index)), replies, nb, rd, ret), logger)
+      val (ls, ns, bo, br) = (ps.map(_.instance.replicaIndex).toArray, ps.map(_.instance.instanceNumber).toArray,
+                              ps.map(_.ballot.ordering).toArray, ps.map(_.ballot.replicaIndex).toArray)
+      val sets = keyset.map(x => (if (x._2) 1 else 0).toByte).toArray
+      Native.check(if (engine.singleKeys(ks))
+                     Native.epxHandlePreaccept(engine.handle, k, n, ls, ns, bo, br, engine.singleKey(ks), sets, Array.tabulate(k)(first + _),
+                                               depsIn, endsIn, Array.fill(k)(bit(index)), replies, nb, rd, ret)
+                   else
+                     Native.epxHandlePreacceptMk(engine.handle, k, n, ls, ns, bo, br, engine.keyOffsets(ks), engine.keyList(ks), sets,
+                                                 Array.tabulate(k)(first + _), depsIn, endsIn, Array.fill(k)(bit(index)), replies, nb,
+                                                 rd, ret), logger)
       for (((src, p), i) <- preAccepts.zipWithIndex) {
         val back = chan[Replica[Transport]](src, Replica.serializer)
         val mine = (replies(i) & bit(index)) != 0 || (replies(k + i) & bit(index)) != 0        // processed, or answered again
@@ -368,17 +400,21 @@ class GpuEPaxosReplica[Transport <: frankenpaxos.Transport[Transport]](
     // ---- Accepts (:1421-1511) and Prepares (:1632-1757) from replicas outside, at THIS replica
     if (accepts.nonEmpty) {
       val k = accepts.size; val as = accepts.map(_._2)
-      val keyset = as.map(a => if (a.commandOrNoop.value.isNoop) (-1, false) else engine.classify(a.commandOrNoop.getCommand))
+      val keyset = as.map(a => engine.classify(a.commandOrNoop)); val ks = keyset.map(_._1)
       val first = engine.triples.size; as.foreach(a => engine.triples += a.commandOrNoop)
       for ((a, i) <- as.zipWithIndex) {   // the device keeps an accepted triple by its id: its dependencies stay here
         val v = a.dependencies.intPrefixSet(a.instance.replicaIndex).value
         engine.tripleDeps(first + i) = (watermarks(a.dependencies), if (v.isEmpty) 0 else v.max + 1)
       }
       val replies = new Array[Byte](4 * k); val nb = new Array[Int](k)
-      Native.check(Native.epxAccept(engine.handle, k, as.map(_.instance.replicaIndex).toArray, as.map(_.instance.instanceNumber).toArray,
-                                    as.map(_.ballot.ordering).toArray, as.map(_.ballot.replicaIndex).toArray, Array.tabulate(k)(first + _),
-                                    keyset.map(_._1).toArray, keyset.map(x => (if (x._2) 1 else 0).toByte).toArray,
-                                    Array.fill(k)(bit(index)), replies, nb), logger)
+      val (ls, ns, bo, br, ts) = (as.map(_.instance.replicaIndex).toArray, as.map(_.instance.instanceNumber).toArray,
+                                  as.map(_.ballot.ordering).toArray, as.map(_.ballot.replicaIndex).toArray, Array.tabulate(k)(first + _))
+      val sets = keyset.map(x => (if (x._2) 1 else 0).toByte).toArray
+      Native.check(if (engine.singleKeys(ks))
+                     Native.epxAccept(engine.handle, k, ls, ns, bo, br, ts, engine.singleKey(ks), sets, Array.fill(k)(bit(index)), replies, nb)
+                   else
+                     Native.epxAcceptMk(engine.handle, k, ls, ns, bo, br, ts, engine.keyOffsets(ks), engine.keyList(ks), sets,
+                                        Array.fill(k)(bit(index)), replies, nb), logger)
       for (((src, a), i) <- accepts.zipWithIndex) {
         val back = chan[Replica[Transport]](src, Replica.serializer)
         if ((replies(i) & bit(index)) != 0) back.send(ReplicaInbound().withAcceptOk(AcceptOk(a.instance, a.ballot, index)))

@@ -126,6 +126,26 @@ object Native {
                                  tripleId: Array[Int], depsIn: Array[Int], depsInValuesEnd: Array[Int],
                                  targetMask: Array[Byte], replies: Array[Byte], nackBallot: Array[Int],
                                  replyDeps: Array[Int], replyEndTriple: Array[Int]): Int
+  // the multi-key forms of epxPreaccept / epxAccept / epxHandleCommit / epxHandlePreaccept: command i's keys are
+  // keys(keyOffsets(i) until keyOffsets(i + 1)) (keyOffsets: m + 1 entries from 0), everything else as above
+  @native def epxPreacceptMk(handle: Long, m: Int, numReplicas: Int, leader: Array[Int],
+                             number: Array[Int], keyOffsets: Array[Int], keys: Array[Int], isSet: Array[Byte],
+                             respMask: Array[Byte], seenMask: Array[Byte], rank: Array[Int],
+                             fast: Array[Byte], deps: Array[Int], leaderDeps: Array[Int],
+                             ownValuesEnd: Array[Int]): Int
+  @native def epxAcceptMk(handle: Long, m: Int, leader: Array[Int], number: Array[Int],
+                          ballotOrdering: Array[Int], ballotReplica: Array[Int], tripleId: Array[Int],
+                          keyOffsets: Array[Int], keys: Array[Int], isSet: Array[Byte],
+                          targetMask: Array[Byte], replies: Array[Byte], nackBallot: Array[Int]): Int
+  @native def epxHandleCommitMk(handle: Long, m: Int, numReplicas: Int, leader: Array[Int], number: Array[Int],
+                                tripleId: Array[Int], keyOffsets: Array[Int], keys: Array[Int], isSet: Array[Byte],
+                                deps: Array[Int], depsValuesEnd: Array[Int], targetMask: Array[Byte]): Int
+  @native def epxHandlePreacceptMk(handle: Long, m: Int, numReplicas: Int, leader: Array[Int],
+                                   number: Array[Int], ballotOrdering: Array[Int],
+                                   ballotReplica: Array[Int], keyOffsets: Array[Int], keys: Array[Int],
+                                   isSet: Array[Byte], tripleId: Array[Int], depsIn: Array[Int],
+                                   depsInValuesEnd: Array[Int], targetMask: Array[Byte], replies: Array[Byte],
+                                   nackBallot: Array[Int], replyDeps: Array[Int], replyEndTriple: Array[Int]): Int
   @native def epxReadCmdlog(handle: Long, numReplicas: Int, replica: Int, leader: Int, number: Int,
                             entry: Array[Int]): Int
   // multi-GPU: one context per GPU, one RCCL communicator over them (fpx_comm_*); the 128-byte id of

@@ -556,6 +556,138 @@ JNIEXPORT jint JNICALL Java_frankenpaxos_gpu_Native_epxHandlePreaccept(
   return st;
 }
 
+/* ---- multi-key get / set commands (the _mk entry points): keyOffsets m + 1, keys keyOffsets[m] (fpx.h) -------------- */
+/* copies the key lists: 0 = a list the library may look at (it checks the rest), else FPX_EINVAL / FPX_ENOMEM */
+static int32_t in_key_lists(JNIEnv* env, jint m, jintArray keyOffsets, jintArray keys, jint** off, jint** k) {
+  *off = NULL, *k = NULL;
+  if (!has(env, keyOffsets, (jlong)m + 1)) return FPX_EINVAL;
+  if (!(*off = in_ints(env, keyOffsets, (jlong)m + 1))) return FPX_ENOMEM;
+  const jint P = (*off)[m];
+  if (P < 0 || P > FPX_EPX_MK_MAX_PAIRS || (P > 0 && !has(env, keys, P))) return FPX_EINVAL;
+  if (P > 0 && !(*k = in_ints(env, keys, P))) return FPX_ENOMEM;
+  return FPX_OK;
+}
+
+JNIEXPORT jint JNICALL Java_frankenpaxos_gpu_Native_epxPreacceptMk(
+    JNIEnv* env, jclass cls, jlong h, jint m, jint numReplicas, jintArray leader, jintArray number, jintArray keyOffsets,
+    jintArray keys, jbyteArray isSet, jbyteArray respMask, jbyteArray seenMask, jintArray rank, jbyteArray fast,
+    jintArray deps, jintArray leaderDeps, jintArray ownValuesEnd) {
+  if (m < 0 || numReplicas < 3 || !epx_n_is(h, numReplicas)) return FPX_EINVAL;
+  if (m == 0) return FPX_OK;
+  const jlong mn = (jlong)m * numReplicas;
+  if (!has(env, leader, m) || !has(env, number, m) || !has(env, isSet, m) || !has(env, respMask, m) ||
+      !opt(env, seenMask, m) || !has(env, rank, mn) || !opt(env, fast, m) || !opt(env, deps, mn) ||
+      !opt(env, leaderDeps, mn) || !opt(env, ownValuesEnd, 2 * (jlong)m))
+    return FPX_EINVAL;
+  jint *off, *k;
+  int32_t st = in_key_lists(env, m, keyOffsets, keys, &off, &k);
+  jint *l = in_ints(env, leader, m), *nu = in_ints(env, number, m), *rk = in_ints(env, rank, mn);
+  jbyte *is = in_bytes(env, isSet, m), *rm = in_bytes(env, respMask, m), *sm = in_bytes(env, seenMask, m);
+  jbyte* f = out_buf(fast, m, 1);
+  jint *d = out_buf(deps, mn, 4), *ld = out_buf(leaderDeps, mn, 4), *ov = out_buf(ownValuesEnd, 2 * (jlong)m, 4);
+  if (st == FPX_OK)
+    st = (!l || !nu || !rk || !is || !rm || (seenMask && !sm) || (fast && !f) || (deps && !d) || (leaderDeps && !ld) ||
+          (ownValuesEnd && !ov))
+             ? FPX_ENOMEM
+             : fpx_epx_preaccept_mk((fpx_epx*)(intptr_t)h, m, l, nu, off, k, (const uint8_t*)is, (const uint8_t*)rm,
+                                    (const uint8_t*)sm, rk, NULL, (uint8_t*)f, d, ld, ov);
+  put_bytes(env, fast, m, f); put_ints(env, deps, mn, d); put_ints(env, leaderDeps, mn, ld);
+  put_ints(env, ownValuesEnd, 2 * (jlong)m, ov);
+  free(off); free(k); free(l); free(nu); free(rk); free(is); free(rm); free(sm); free(f); free(d); free(ld); free(ov);
+  return st;
+}
+
+JNIEXPORT jint JNICALL Java_frankenpaxos_gpu_Native_epxAcceptMk(JNIEnv* env, jclass cls, jlong h, jint m, jintArray leader,
+                                                                jintArray number, jintArray ballotOrdering,
+                                                                jintArray ballotReplica, jintArray tripleId,
+                                                                jintArray keyOffsets, jintArray keys, jbyteArray isSet,
+                                                                jbyteArray targetMask, jbyteArray replies,
+                                                                jintArray nackBallot) {
+  if (m < 0) return FPX_EINVAL;
+  if (m == 0) return FPX_OK;
+  if (!has(env, leader, m) || !has(env, number, m) || !has(env, ballotOrdering, m) || !has(env, ballotReplica, m) ||
+      !has(env, tripleId, m) || !has(env, isSet, m) || !has(env, targetMask, m) || !opt(env, replies, 4 * (jlong)m) ||
+      !opt(env, nackBallot, m))
+    return FPX_EINVAL;
+  jint *off, *k;
+  int32_t st = in_key_lists(env, m, keyOffsets, keys, &off, &k);
+  jint *l = in_ints(env, leader, m), *nu = in_ints(env, number, m), *bo = in_ints(env, ballotOrdering, m),
+       *br = in_ints(env, ballotReplica, m), *tr = in_ints(env, tripleId, m);
+  jbyte *tg = in_bytes(env, targetMask, m), *is = in_bytes(env, isSet, m);
+  jbyte* rp = out_buf(replies, 4 * (jlong)m, 1);
+  jint* nb = out_buf(nackBallot, m, 4);
+  uint8_t* r8 = (uint8_t*)rp;
+  if (st == FPX_OK)
+    st = (!l || !nu || !bo || !br || !tr || !tg || !is || (replies && !rp) || (nackBallot && !nb))
+             ? FPX_ENOMEM
+             : fpx_epx_accept_mk((fpx_epx*)(intptr_t)h, m, l, nu, bo, br, tr, off, k, (const uint8_t*)is, (const uint8_t*)tg,
+                                 r8, r8 ? r8 + m : NULL, r8 ? r8 + 2 * (size_t)m : NULL, nb, r8 ? r8 + 3 * (size_t)m : NULL);
+  put_bytes(env, replies, 4 * (jlong)m, rp); put_ints(env, nackBallot, m, nb);
+  free(off); free(k); free(l); free(nu); free(bo); free(br); free(tr); free(is); free(tg); free(rp); free(nb);
+  return st;
+}
+
+JNIEXPORT jint JNICALL Java_frankenpaxos_gpu_Native_epxHandleCommitMk(JNIEnv* env, jclass cls, jlong h, jint m, jint numReplicas,
+                                                                      jintArray leader, jintArray number, jintArray tripleId,
+                                                                      jintArray keyOffsets, jintArray keys, jbyteArray isSet,
+                                                                      jintArray deps, jintArray depsValuesEnd,
+                                                                      jbyteArray targetMask) {
+  if (m < 0 || numReplicas < 3 || !epx_n_is(h, numReplicas)) return FPX_EINVAL;
+  if (m == 0) return FPX_OK;
+  const jlong mn = (jlong)m * numReplicas;
+  if (!has(env, leader, m) || !has(env, number, m) || !has(env, tripleId, m) || !has(env, isSet, m) ||
+      !opt(env, deps, mn) || !opt(env, depsValuesEnd, m) || !has(env, targetMask, m) || (depsValuesEnd && !deps))
+    return FPX_EINVAL;
+  jint *off, *k;
+  int32_t st = in_key_lists(env, m, keyOffsets, keys, &off, &k);
+  jint *l = in_ints(env, leader, m), *nu = in_ints(env, number, m), *tr = in_ints(env, tripleId, m);
+  jint* d = deps ? in_ints(env, deps, mn) : NULL;
+  jint* de = depsValuesEnd ? in_ints(env, depsValuesEnd, m) : NULL;
+  jbyte *is = in_bytes(env, isSet, m), *tg = in_bytes(env, targetMask, m);
+  if (st == FPX_OK)
+    st = (!l || !nu || !tr || !is || !tg || (deps && !d) || (depsValuesEnd && !de))
+             ? FPX_ENOMEM
+             : fpx_epx_handle_commit_mk((fpx_epx*)(intptr_t)h, m, l, nu, tr, off, k, (const uint8_t*)is, d, de, (const uint8_t*)tg);
+  free(off); free(k); free(l); free(nu); free(tr); free(d); free(de); free(is); free(tg);
+  return st;
+}
+
+JNIEXPORT jint JNICALL Java_frankenpaxos_gpu_Native_epxHandlePreacceptMk(
+    JNIEnv* env, jclass cls, jlong h, jint m, jint numReplicas, jintArray leader, jintArray number,
+    jintArray ballotOrdering, jintArray ballotReplica, jintArray keyOffsets, jintArray keys, jbyteArray isSet,
+    jintArray tripleId, jintArray depsIn, jintArray depsInValuesEnd, jbyteArray targetMask, jbyteArray replies,
+    jintArray nackBallot, jintArray replyDeps, jintArray replyEndTriple) {
+  if (m < 0 || numReplicas < 3 || !epx_n_is(h, numReplicas)) return FPX_EINVAL;
+  if (m == 0) return FPX_OK;
+  const jlong mn = (jlong)m * numReplicas;
+  if (!has(env, leader, m) || !has(env, number, m) || !has(env, ballotOrdering, m) || !has(env, ballotReplica, m) ||
+      !has(env, isSet, m) || !opt(env, tripleId, m) || !has(env, depsIn, mn) || !opt(env, depsInValuesEnd, m) ||
+      !has(env, targetMask, m) || !opt(env, replies, 4 * (jlong)m) || !opt(env, nackBallot, m) ||
+      !opt(env, replyDeps, mn * numReplicas) || !opt(env, replyEndTriple, 2 * mn))
+    return FPX_EINVAL;
+  jint *off, *k;
+  int32_t st = in_key_lists(env, m, keyOffsets, keys, &off, &k);
+  jint *l = in_ints(env, leader, m), *nu = in_ints(env, number, m), *bo = in_ints(env, ballotOrdering, m),
+       *br = in_ints(env, ballotReplica, m), *tr = in_ints(env, tripleId, m), *di = in_ints(env, depsIn, mn),
+       *de = in_ints(env, depsInValuesEnd, m);
+  jbyte *is = in_bytes(env, isSet, m), *tg = in_bytes(env, targetMask, m);
+  jbyte* rp = out_buf(replies, 4 * (jlong)m, 1);
+  jint *nb = out_buf(nackBallot, m, 4), *rd = out_buf(replyDeps, mn * numReplicas, 4), *re = out_buf(replyEndTriple, 2 * mn, 4);
+  uint8_t* r8 = (uint8_t*)rp;
+  if (st == FPX_OK)
+    st = (!l || !nu || !bo || !br || !di || !is || !tg || (tripleId && !tr) || (depsInValuesEnd && !de) ||
+          (replies && !rp) || (nackBallot && !nb) || (replyDeps && !rd) || (replyEndTriple && !re))
+             ? FPX_ENOMEM
+             : fpx_epx_handle_preaccept_mk((fpx_epx*)(intptr_t)h, m, l, nu, bo, br, off, k, (const uint8_t*)is, tr, di, de,
+                                           (const uint8_t*)tg, r8, r8 ? r8 + m : NULL, r8 ? r8 + 2 * (size_t)m : NULL,
+                                           r8 ? r8 + 3 * (size_t)m : NULL, nb, rd, re, re ? re + mn : NULL);
+  put_bytes(env, replies, 4 * (jlong)m, rp); put_ints(env, nackBallot, m, nb);
+  put_ints(env, replyDeps, mn * numReplicas, rd); put_ints(env, replyEndTriple, 2 * mn, re);
+  free(off); free(k); free(l); free(nu); free(bo); free(br); free(tr); free(di); free(de); free(is); free(tg); free(rp);
+  free(nb); free(rd); free(re);
+  return st;
+}
+
 /* entry = kind, ballot, voteBallot, triple id, the replica's largestBallot, then the n stored dependency watermarks
  * and the own column's values end (5 + n + 1 ints) */
 JNIEXPORT jint JNICALL Java_frankenpaxos_gpu_Native_epxReadCmdlog(JNIEnv* env, jclass cls, jlong h, jint numReplicas,

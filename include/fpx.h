@@ -653,6 +653,63 @@ int32_t fpx_epx_handle_preaccept(fpx_epx* epx, int32_t m, const int32_t* leader,
 int32_t fpx_epx_handle_commit(fpx_epx* epx, int32_t m, const int32_t* leader, const int32_t* number,
                               const int32_t* triple_id, const int32_t* key, const uint8_t* is_set, const int32_t* deps,
                               const int32_t* deps_values_end, const uint8_t* target_mask);
+/* ---- multi-key get / set commands: one _mk form per entry point above that takes a command ----------------------
+ * The reference's key-value store takes GetRequest / SetRequest with any number of keys (statemachine/KeyValueStore.scala
+ * :221-302, typedTopKConflictIndex with k = 1): a command's top-one conflicts are the element-wise max, over its keys, of
+ * each key's TopOne (a get merges the sets of its keys, a set their gets and sets), and put records the instance under
+ * every key of the command.  The _mk forms take, in place of key[m], a CSR key list:
+ *   key_offsets[m + 1]  key_offsets[0] = 0, non-decreasing; command i's keys are keys[key_offsets[i] .. key_offsets[i + 1])
+ *   keys[key_offsets[m]]  each in [0, num_keys); is_set[m] per command (the reference's command is a GetRequest or a
+ *                         SetRequest, not a mix)
+ * A key repeated inside one command counts once (the reference's merge and put are idempotent); the library drops the
+ * repeats itself.  A command with NO keys gets the empty set as its conflicts (snapshots, which EPaxos never fills: it
+ * never calls putSnapshot) and put adds nothing -- on the device it behaves exactly like a Noop (no dependencies, the
+ * index untouched), while it stays a command for the caller's triple.  Offsets that are not monotone, a key out of
+ * range or more than FPX_EPX_MK_MAX_PAIRS keys in one call: FPX_EINVAL, nothing applied.  Everything else is the
+ * single-key form's contract, word for word.
+ *
+ * fpx_epx_preaccept_mk / _mk_dev / _mk_packed_dev: K5's tick.  When every command has exactly one key (key_offsets[i] = i)
+ * the tick IS the single-key tick with keys as key (same kernels, same results, same device state).  Otherwise it runs
+ * on (command, distinct key) pairs: each replica's pair sequence in its delivery order (an exclusive scan of the key
+ * counts per replica), K5's sort / scan over the pairs, one max per command over its pairs' conflict rows, and K5's
+ * decision on those rows (the output encoding is unchanged, so fpx_epx_execute_dev orders the commits as it does
+ * single-key ones).  The device forms read key_offsets / keys on the device and wait once on the host for the pair count
+ * (before anything is applied): not capturable into a HIP graph.  The multi-key tick never takes the on-chip
+ * key-partitioned form (which decides per key).
+ * fpx_epx_handle_preaccept_mk: K7 (fpx_epx_handle_preaccept) with the same pair expansion in array order.
+ * fpx_epx_accept_mk / fpx_epx_handle_commit_mk: updateConflictIndex (Replica.scala:602-614) puts the instance under
+ * every key of the command; no keys = nothing, as a Noop. */
+#define FPX_EPX_MK_MAX_PAIRS (1 << 23)
+int32_t fpx_epx_preaccept_mk(fpx_epx* epx, int32_t m, const int32_t* leader, const int32_t* number,
+                             const int32_t* key_offsets, const int32_t* keys, const uint8_t* is_set,
+                             const uint8_t* resp_mask, const uint8_t* seen_mask, const int32_t* rank,
+                             const int32_t* triple_id, uint8_t* fast, int32_t* deps, int32_t* leader_deps,
+                             int32_t* own_values_end);
+int32_t fpx_epx_preaccept_mk_dev(fpx_epx* epx, int32_t m, const int32_t* d_leader, const int32_t* d_number,
+                                 const int32_t* d_key_offsets, const int32_t* d_keys, const uint8_t* d_is_set,
+                                 const uint8_t* d_resp_mask, const uint8_t* d_seen_mask, const int32_t* d_rank,
+                                 const int32_t* d_triple_id, uint8_t* d_fast, int32_t* d_deps, int32_t* d_leader_deps,
+                                 int32_t* d_own_values_end);
+int32_t fpx_epx_preaccept_mk_packed_dev(fpx_epx* epx, int32_t m, const int32_t* d_leader, const int32_t* d_number,
+                                        const int32_t* d_key_offsets, const int32_t* d_keys, const uint8_t* d_is_set,
+                                        const uint8_t* d_resp_mask, const uint8_t* d_seen_mask, const int32_t* d_rank,
+                                        const int32_t* d_triple_id, int32_t* d_packed);
+int32_t fpx_epx_handle_preaccept_mk(fpx_epx* epx, int32_t m, const int32_t* leader, const int32_t* number,
+                                    const int32_t* ballot_ordering, const int32_t* ballot_replica,
+                                    const int32_t* key_offsets, const int32_t* keys, const uint8_t* is_set,
+                                    const int32_t* triple_id, const int32_t* deps_in, const int32_t* deps_in_values_end,
+                                    const uint8_t* target_mask, uint8_t* ok_bits, uint8_t* resend_bits,
+                                    uint8_t* nack_bits, uint8_t* commit_bits, int32_t* nack_ballot, int32_t* reply_deps,
+                                    int32_t* reply_values_end, int32_t* reply_triple);
+int32_t fpx_epx_accept_mk(fpx_epx* epx, int32_t m, const int32_t* leader, const int32_t* number,
+                          const int32_t* ballot_ordering, const int32_t* ballot_replica, const int32_t* triple_id,
+                          const int32_t* key_offsets, const int32_t* keys, const uint8_t* is_set,
+                          const uint8_t* target_mask, uint8_t* ok_bits, uint8_t* nack_bits, uint8_t* commit_bits,
+                          int32_t* nack_ballot, uint8_t* committed);
+int32_t fpx_epx_handle_commit_mk(fpx_epx* epx, int32_t m, const int32_t* leader, const int32_t* number,
+                                 const int32_t* triple_id, const int32_t* key_offsets, const int32_t* keys,
+                                 const uint8_t* is_set, const int32_t* deps, const int32_t* deps_values_end,
+                                 const uint8_t* target_mask);
 /* one command-log entry: out[0..4] = kind, ballot, voteBallot, triple id, the replica's largestBallot */
 int32_t fpx_epx_read_cmdlog(fpx_epx* epx, int32_t replica, int32_t leader, int32_t number, int32_t out[5]);
 /* the dependencies kept with that entry: deps[n] watermarks (deps[0] = -1: known by triple id only), *values_end */
