@@ -501,6 +501,15 @@ class Context:
             raise FpxError(st, "fpx_state_digest")
         return out
 
+    def ballot_summary_audit(self):
+        """FPX_BALLOT_PER_SLOT: (uniform rows, mixed rows, violations) of the per-row ballot summaries
+        (fpx_ballot_summary_audit); violations -- uniform rows with a cell that differs from the summary -- must be 0"""
+        out = np.zeros(3, np.int64)
+        st = self.L.fpx_ballot_summary_audit(self._h, _hp(out))
+        if st:
+            raise FpxError(st, "fpx_ballot_summary_audit")
+        return int(out[0]), int(out[1]), int(out[2])
+
     def read_tally(self, slot):
         n = C.c_int32()
         rounds = np.zeros(8, np.int32)

@@ -614,6 +614,7 @@ int init_state(fpx_ctx* ctx) {
     HIPCHK(ctx, hipMemsetAsync(st.vote_value, 0xFF, ncell * 4, ctx->stream));
   }
   if (st.ballot) HIPCHK(ctx, hipMemsetAsync(st.ballot, 0xFF, ncell * 4, ctx->stream));
+  if (st.ballot_sum) HIPCHK(ctx, hipMemsetAsync(st.ballot_sum, 0xFF, (size_t)g.S * 4, ctx->stream));  // every row -1
   HIPCHK(ctx, hipMemsetAsync(st.pl_key, 0, (size_t)g.S * g.wp * 4, ctx->stream));
   HIPCHK(ctx, hipMemsetAsync(st.pl_value, 0xFF, (size_t)g.S * g.wp * 4, ctx->stream));
   HIPCHK(ctx, hipMemsetAsync(st.pl_bits, 0, (size_t)g.S * g.wp * 32, ctx->stream));
@@ -942,7 +943,7 @@ void free_state(fpx_ctx* ctx) {
   void* ps[] = {st.promised, st.max_voted, ctx->slab, st.pl_key, st.pl_value,
                 st.pl_bits,  st.stamp,     st.run_round,  st.status,     st.part,
                 st.log_value, st.log_present, st.log_scalars, st.part_stamp, st.part_all,
-                st.row_voted, st.lz_round, st.lz_from, st.max_ballot, st.p1,
+                st.row_voted, st.ballot_sum, st.lz_round, st.lz_from, st.max_ballot, st.p1,
                 ctx->rt[0].key, ctx->rt[0].bits, ctx->rt[0].owner, ctx->rt[0].count,
                 ctx->rt[1].key, ctx->rt[1].bits, ctx->rt[1].owner, ctx->rt[1].count, ctx->d_rng.p, ctx->d_run_done.p};
   for (void* p : ps)
@@ -1465,6 +1466,7 @@ int32_t fpx_create(const fpx_config* cfg, fpx_ctx** out) {
   if ((rc = dalloc(ctx, &st.pl_bits, (size_t)g.S * g.wp * 4))) return fail(rc);
   if ((rc = dalloc(ctx, &st.stamp, (size_t)g.S))) return fail(rc);
   if ((rc = dalloc(ctx, &st.row_voted, (size_t)g.S))) return fail(rc);
+  if (g.per_slot && sums_kept(g) && (rc = dalloc(ctx, &st.ballot_sum, (size_t)g.S))) return fail(rc);  // (outside the placed slab)
   if ((rc = dalloc(ctx, &st.lz_round, nsc + 4))) return fail(rc);
   if ((rc = dalloc(ctx, &st.lz_from, nsc + 4))) return fail(rc);
   if ((rc = dalloc(ctx, &st.max_ballot, nsc + 4))) return fail(rc);
@@ -1926,7 +1928,15 @@ int32_t fpx_acceptor_phase1a(fpx_ctx* ctx, int32_t group, int32_t round, int32_t
 // and forgotten; k_phase2 goes back to its lean form.  Readback and digests do this implicitly.
 static int flush_promises(fpx_ctx* ctx) {
   if (!ctx->g.per_slot || !ctx->lazy_active) return FPX_OK;
-  hipLaunchKernelGGL(k_lazy_flush, dim3(ctx->num_cus * 8), dim3(256), 0, ctx->stream, ctx->g, ctx->st);
+  const Geom& g = ctx->g;
+  const dim3 grid(ctx->num_cus * 8);
+  if (g.R > 32) hipLaunchKernelGGL(k_lazy_flush<64>, grid, dim3(256), 0, ctx->stream, g, ctx->st);
+  else if (g.R > 16) hipLaunchKernelGGL(k_lazy_flush<32>, grid, dim3(256), 0, ctx->stream, g, ctx->st);
+  else if (g.R > 8) hipLaunchKernelGGL(k_lazy_flush<16>, grid, dim3(256), 0, ctx->stream, g, ctx->st);
+  else if (g.R > 4) hipLaunchKernelGGL(k_lazy_flush<8>, grid, dim3(256), 0, ctx->stream, g, ctx->st);
+  else if (g.R > 2) hipLaunchKernelGGL(k_lazy_flush<4>, grid, dim3(256), 0, ctx->stream, g, ctx->st);
+  else if (g.R > 1) hipLaunchKernelGGL(k_lazy_flush<2>, grid, dim3(256), 0, ctx->stream, g, ctx->st);
+  else hipLaunchKernelGGL(k_lazy_flush<1>, grid, dim3(256), 0, ctx->stream, g, ctx->st);
   const int nsc = ctx->g.ngroups * ctx->g.R;
   hipLaunchKernelGGL(k_lazy_clear, dim3((nsc + 255) / 256), dim3(256), 0, ctx->stream, ctx->g, ctx->st);
   int rc = launch_check(ctx);
@@ -2840,6 +2850,28 @@ int32_t fpx_state_digest(fpx_ctx* ctx, uint64_t out[8]) {
   }
   if ((rc = launch_check(ctx))) return rc;
   HIPCHK(ctx, hipMemcpyAsync(out, d, 64, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  return FPX_OK;
+}
+
+int32_t fpx_ballot_summary_audit(fpx_ctx* ctx, int64_t out[3]) {
+  DeviceGuard _dg(ctx);
+  if (!ctx || !out || !ctx->g.per_slot) return FPX_EINVAL;
+  if (!ctx->st.ballot_sum) {  // rows of at most 128 cells: no summaries, every row counts as mixed
+    out[0] = 0, out[1] = ctx->g.S, out[2] = 0;
+    return FPX_OK;
+  }
+  int rc;
+  if ((rc = grow(ctx, &ctx->d_scratch, 128))) return rc;
+  unsigned long long* d = (unsigned long long*)ctx->d_scratch.p;
+  HIPCHK(ctx, hipMemsetAsync(d, 0, 3 * sizeof(unsigned long long), ctx->stream));
+  const Geom& g = ctx->g;
+  const dim3 grid(ctx->num_cus * 8);
+  if (g.R > 32) hipLaunchKernelGGL(k_ballot_audit<64>, grid, dim3(256), 0, ctx->stream, g, ctx->st, d);
+  else if (g.R > 4) hipLaunchKernelGGL(k_ballot_audit<8>, grid, dim3(256), 0, ctx->stream, g, ctx->st, d);
+  else hipLaunchKernelGGL(k_ballot_audit<1>, grid, dim3(256), 0, ctx->stream, g, ctx->st, d);
+  if ((rc = launch_check(ctx))) return rc;
+  HIPCHK(ctx, hipMemcpyAsync(out, d, 3 * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
   return FPX_OK;
 }

@@ -62,6 +62,7 @@ typedef unsigned int uint4v __attribute__((ext_vector_type(4)));
 // single-slot key, mencius/ProxyLeader.scala:86-90).
 enum : uint32_t { KEY_DONE = 0x80000000u, KEY_RANGE = 0x40000000u, KEY_ROUND_MASK = 0x3fffffffu };
 constexpr int MAX_ROUND = 0x3ffffffe;
+constexpr int SUM_MIXED = INT32_MIN;  // State::ballot_sum: the row's cells differ (never a legal round)
 constexpr int PART_ALL_STRIDE = 32;  // ints: one 128-byte line per shard of the whole-group maxima
 
 // status word layout in HBM (int32[8])
@@ -135,7 +136,15 @@ struct State {
   int32_t* log_value;   // [S]  the replica's log (BufferMap), -1 where absent
   uint8_t* log_present; // [S]
   int32_t* log_scalars; // [8]  LG_*: executedWatermark, numChosen, largestKey, scan result
+  // FPX_BALLOT_PER_SLOT: one word per ballot row (indexed like the rows): != SUM_MIXED => every stored cell of the row holds
+  // that round.  It describes the STORED cells, not the effective ballot (lazy promises still apply on top of it); a
+  // vote kernel that finds a row uniform takes its cells from this word instead of reading the row.  Kept only where the
+  // vote kernel reads it, rows of more than 128 cells (sums_kept): elsewhere null, as if every row were SUM_MIXED
+  int32_t* ballot_sum;  // [S] or null
 };
+
+// the ballot-row summaries are kept (and read by the vote kernel) for rows of more than 128 cells: 1 KiB rows, G = 64
+__host__ __device__ __forceinline__ bool sums_kept(const Geom& g) { return g.R > 128; }
 
 struct Batch {
   int32_t n;
@@ -759,6 +768,11 @@ __device__ __forceinline__ void p1a_decide_body(const Geom& g, const State& st, 
   if (r < 4) outp[r] = bits[r], outn[r] = 0ull;
 }
 
+// a ballot cell of the row moved outside the vote kernel: its summary (where there are summaries) says nothing any more
+__device__ __forceinline__ void mark_mixed(const State& st, size_t row) {
+  if (st.ballot_sum) st.ballot_sum[row] = SUM_MIXED;
+}
+
 // workgroup `bid` of `nblk` (256 threads each) of the sweep
 __device__ __forceinline__ void p1a_sweep_body(const Geom& g, const State& st, int group, int round, int watermark, uint64_t* outp,
                                                uint64_t* outn, int bid, int nblk) {
@@ -775,7 +789,8 @@ __device__ __forceinline__ void p1a_sweep_body(const Geom& g, const State& st, i
     const int cur = st.ballot[c];
     if (m == 1) {
       if (s >= st.p1[P1_A * g.R + r] && s < st.p1[P1_B * g.R + r] && st.p1[P1_C * g.R + r] > cur)
-        st.ballot[c] = st.p1[P1_C * g.R + r];
+        // (rare: the row is read again until a whole-group vote rewrites it)
+        st.ballot[c] = st.p1[P1_C * g.R + r], mark_mixed(st, c / g.RS);
     } else if (s >= wm) {
       const size_t e = (size_t)group * g.R + r;
       const int lz = s >= st.lz_from[e] ? st.lz_round[e] : -1;
@@ -788,7 +803,7 @@ __device__ __forceinline__ void p1a_sweep_body(const Geom& g, const State& st, i
         if (!((__hip_atomic_load(word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >> (bit & 63)) & 1ull))
           atomicOr(word, 1ull << (bit & 63));
       } else if (cur != round) {
-        st.ballot[c] = round;
+        st.ballot[c] = round, mark_mixed(st, c / g.RS);
       }
     }
   }
@@ -889,7 +904,7 @@ __global__ void __launch_bounds__(256) k_p1a_fast(const Geom g, const State st, 
       if (!((__hip_atomic_load(&nacks[b2 >> 6], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >> (b2 & 63)) & 1ull))
         atomicOr(&nacks[b2 >> 6], 1ull << (b2 & 63));
     } else if (cur != round) {
-      st.ballot[c] = round;
+      st.ballot[c] = round, mark_mixed(st, c / g.RS);
     }
   }
   __threadfence();
@@ -907,17 +922,59 @@ __global__ void __launch_bounds__(256) k_p1a_fast(const Geom g, const State st, 
 }
 
 // every outstanding lazy promise written into the cells it covers, the records cleared (readback / digests /
-// fpx_acceptor_flush_promises)
+// fpx_acceptor_flush_promises).  Row by row, LW lanes to a row (LW = R rounded up to a power of two, at most 64), so
+// that the row's summary comes out exact: a uniform row (Phase 1 promised the same round to every cell from the
+// watermark on: the steady stream's setup) is not even read -- its cells are its summary
+template <int LW>
 __global__ void __launch_bounds__(256) k_lazy_flush(const Geom g, const State st) {
-  const size_t ncell = (size_t)g.S * g.RS;
-  for (size_t c = (size_t)blockIdx.x * blockDim.x + threadIdx.x; c < ncell; c += (size_t)gridDim.x * blockDim.x) {
-    const int s = slot_of_row(g, (int)(c / g.RS)), r = (int)(c % g.RS);
-    if (r >= g.R) continue;
-    const size_t e = (size_t)group_of_slot(g, s) * g.R + r;
-    const int lr = st.lz_round[e];
-    if (lr >= 0 && s >= st.lz_from[e] && lr > st.ballot[c]) st.ballot[c] = lr;
+  const int sub = threadIdx.x & (LW - 1);
+  const int rows_per_pass = (int)(gridDim.x * blockDim.x / LW);
+  // (the LW lanes of a row run the same iterations: the reductions below only ever read lanes of their own row)
+  for (int row = (int)((blockIdx.x * blockDim.x + threadIdx.x) / LW); row < g.S; row += rows_per_pass) {
+    const int s = slot_of_row(g, row), grp = group_of_slot(g, s);
+    const int bs = st.ballot_sum ? st.ballot_sum[row] : SUM_MIXED;
+    int32_t* cells = st.ballot + (size_t)row * g.RS;
+    int lo = 0x7fffffff, hi = INT32_MIN;
+    for (int r = sub; r < g.R; r += LW) {
+      const size_t e = (size_t)grp * g.R + r;
+      const int lr = st.lz_round[e];
+      const int cur = bs != SUM_MIXED ? bs : cells[r];
+      const int nv = (lr >= 0 && s >= st.lz_from[e] && lr > cur) ? lr : cur;
+      if (nv != cur) cells[r] = nv;
+      lo = nv < lo ? nv : lo, hi = nv > hi ? nv : hi;
+    }
+#pragma unroll
+    for (int m = 1; m < LW; m <<= 1) {
+      const int a = __shfl_xor(lo, m), b = __shfl_xor(hi, m);
+      lo = a < lo ? a : lo, hi = b > hi ? b : hi;
+    }
+    const int ns = lo == hi ? lo : SUM_MIXED;
+    if (st.ballot_sum && sub == 0 && ns != bs) st.ballot_sum[row] = ns;
   }
 }
+// fpx_ballot_summary_audit: the ballot-row summaries against the cells they describe.  LW lanes to a row (as k_lazy_flush),
+// counts per workgroup in LDS, three atomics per workgroup into out[0..2] (uniform rows, mixed rows, uniform rows with a
+// cell that differs)
+template <int LW>
+__global__ void __launch_bounds__(256) k_ballot_audit(const Geom g, const State st, unsigned long long* out) {
+  __shared__ unsigned long long cnt[3];
+  if (threadIdx.x < 3) cnt[threadIdx.x] = 0ull;
+  __syncthreads();
+  const int sub = threadIdx.x & (LW - 1);
+  const int rows_per_pass = (int)(gridDim.x * blockDim.x / LW);
+  for (int row = (int)((blockIdx.x * blockDim.x + threadIdx.x) / LW); row < g.S; row += rows_per_pass) {
+    const int bs = st.ballot_sum[row];
+    bool bad = false;
+    if (bs != SUM_MIXED)
+      for (int r = sub; r < g.R; r += LW) bad = bad || st.ballot[(size_t)row * g.RS + r] != bs;
+#pragma unroll
+    for (int m = 1; m < LW; m <<= 1) bad = (__shfl_xor((int)bad, m) != 0) || bad;
+    if (sub == 0) atomicAdd(&cnt[bs == SUM_MIXED ? 1 : bad ? 2 : 0], 1ull);
+  }
+  __syncthreads();
+  if (threadIdx.x < 3 && cnt[threadIdx.x]) atomicAdd(&out[threadIdx.x], cnt[threadIdx.x]);
+}
+
 __global__ void k_lazy_clear(const Geom g, const State st) {
   const int e = blockIdx.x * blockDim.x + threadIdx.x;
   if (e < g.ngroups * g.R) st.lz_round[e] = -1, st.lz_from[e] = 0;

@@ -22,6 +22,11 @@ __global__ void __launch_bounds__(256)
   constexpr bool RMW = MODE == 2;  // (3: target masks that are all runs of neighbouring acceptors, see PACK below)
   constexpr bool VEC = true;  // 16-byte row accesses
   constexpr int Q = 64 / G;           // slots per step
+  // the ballot-row summary (State::ballot_sum): a row it calls uniform is not read.  Read and kept exact at G = 64 only
+  // (sums_kept), where a row is 1 KiB and the whole wavefront's: at G <= 4 a row is 16 - 64 bytes, no more traffic than
+  // the 4-byte gather of its summary, and at G = 8 .. 32 the bookkeeping cost these kernels a wave per SIMD
+  // (kernel-resource-usage) for a gain nothing measures.  Below G = 64 there are no summaries (State::ballot_sum null)
+  constexpr bool SUMREAD = PERSLOT && G == 64;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   FPX_P2_PROLOGUE
 
@@ -169,11 +174,19 @@ __global__ void __launch_bounds__(256)
     }
     bool myfresh = false;
     if constexpr (TGT) myfresh = mv && st.row_voted[myphys] == 0;
+    int mysum = SUM_MIXED;  // the summary of my message's row (SUM_MIXED: read the row)
+    if constexpr (SUMREAD) mysum = mv ? st.ballot_sum[myphys] : SUM_MIXED;  // (G = 64: R > 128, allocated: sums_kept)
     // ---- walk the chunk, Q slots per step; the ballot row of the next step is already in flight ----
     // message src of the chunk as seen from this lane (at G = 1 a lane walks its own message: nothing to fetch)
     auto pick = [&](int v, int src) -> int {
       if constexpr (G == 1) return v;
       else return __shfl(v, src);
+    };
+    // the summary of message src's row (at G = 64 src is the same in every lane: a scalar, and a scalar branch below)
+    auto row_sum = [&](int src) -> int {
+      if constexpr (!SUMREAD) return SUM_MIXED;
+      else if constexpr (G == 64) return __builtin_amdgcn_readlane(mysum, src);
+      else return __shfl(mysum, src);
     };
     auto load_thr = [&](int step, int& s_out, int& grp_out, int& phys_out) -> int4v {
       const int src = step * Q + q;
@@ -183,6 +196,7 @@ __global__ void __launch_bounds__(256)
       phys_out = s;
       // (fetched by every lane, outside the branch below: a lane that sits the branch out could not be read from)
       if constexpr (G <= 8) phys_out = pick(myphys, src), grp_out = pick(mygrp, src);
+      const int bs = row_sum(src);
       int4v thr = init_thr;
       if (s >= 0) {
         const size_t row = (size_t)phys_out * (size_t)g.RS + (size_t)r0;
@@ -190,12 +204,17 @@ __global__ void __launch_bounds__(256)
           if (!one_group) grp_out = group_of_slot(g, s);
         }
         if (PERSLOT) {
-          if (VEC) {
+          if (bs != SUM_MIXED) {
+            thr = int4v{bs, bs, bs, bs};  // a uniform row: nothing to read
+          } else if (VEC) {
 #if FPX_NT_LOAD
             if (own) thr = __builtin_nontemporal_load(reinterpret_cast<const int4v*>(st.ballot + row));
 #else
             if (own) thr = *reinterpret_cast<const int4v*>(st.ballot + row);
 #endif
+            // waited for HERE, on the path that loaded: left to the compiler, the wait sits behind the branch, where
+            // every uniform row would wait for the stores of the step before it (vmcnt counts stores on gfx9)
+            if constexpr (SUMREAD && !FPX_PREFETCH) __builtin_amdgcn_s_waitcnt(0x0F70);
           } else {
 #pragma unroll
             for (int k = 0; k < 4; ++k)
@@ -326,7 +345,8 @@ __global__ void __launch_bounds__(256)
         const uint32_t tn = own_c & (uint32_t)((tw >> (bp & 63)) & 0xFull);
         const size_t row = (size_t)s * (size_t)g.RS + (size_t)bp, vrow = (size_t)s * (size_t)g.VS + (size_t)bp;
         int4v thr = hi ? th_hi : th_lo;
-        if (PERSLOT && active) thr = *reinterpret_cast<const int4v*>(st.ballot + row);
+        const int bs = __shfl(mysum, src);  // (every lane: `active` ones read it from lanes that may not be)
+        if (PERSLOT && active) thr = bs != SUM_MIXED ? int4v{bs, bs, bs, bs} : *reinterpret_cast<const int4v*>(st.ballot + row);
         uint32_t acc = 0, nck = 0;
         int nr = -1;
 #pragma unroll
@@ -347,7 +367,11 @@ __global__ void __launch_bounds__(256)
           }
           row_store(rr, reinterpret_cast<int4v*>(st.vote_round + vrow));
           row_store(vv, reinterpret_cast<int4v*>(st.vote_value + vrow));
-          if (PERSLOT && ballot_moves) row_store(nb, reinterpret_cast<int4v*>(st.ballot + row));
+          if (PERSLOT && ballot_moves) {
+            row_store(nb, reinterpret_cast<int4v*>(st.ballot + row));
+            // a run of at most 128 cells moved: the row is not uniform (its other cells kept the summary's round)
+            if (bs != SUM_MIXED) st.ballot_sum[s] = SUM_MIXED;
+          }
         }
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
@@ -436,6 +460,19 @@ __global__ void __launch_bounds__(256)
           nr = thr[k] > nr ? thr[k] : nr;
         }
       }
+      // For the row's summary.  Whatever the path below, a cell that votes with thr != rnd is stored as rnd (`moved`), and
+      // no other cell changes whether it equals rnd: a cell that votes with thr == rnd, or does not vote, holds thr -- or,
+      // with lazy promises, possibly an older round that a promise raised thr over (known to be rnd only when the row
+      // was uniform in rnd).  No cell of the row moved: nothing was stored
+      uint32_t neq = 0, moved = 0;
+      int bs = SUM_MIXED;
+      bool lane_all = false;
+      if constexpr (SUMREAD) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) neq |= thr[k] != rnd ? (1u << k) : 0u;
+        moved = acc & neq, bs = row_sum(src);
+        lane_all = LAZY ? (bs == rnd || (own & ~moved) == 0u) : (own & ~acc & neq) == 0u;
+      }
       // Acceptor.scala:204-208: round = phase2a.round; states(slot) = State(round, value)
       const bool full_cell = (acc | (~own & 0xFu)) == 0xFu;
       // does any acceptor of my 64-byte sector (4 lanes x 16 B) vote?  A fresh sector nobody votes in stays as it is
@@ -506,6 +543,12 @@ __global__ void __launch_bounds__(256)
             }
           }
         }
+      }
+      // the row's new summary (the wavefront's row): rnd if every cell now holds it; as it was if no cell was stored; else mixed
+      if constexpr (SUMREAD) {
+        const bool row_all = __all(lane_all), row_w = __any(moved != 0u);
+        const int ns = row_all ? rnd : (row_w ? SUM_MIXED : bs);
+        if (gi == 0 && s >= 0 && ns != bs) st.ballot_sum[phys_cur] = ns;
       }
       // maxVotedSlot (Acceptor.scala:209) and the acceptor's new round.  When the WHOLE group voted
       // (the steady state) the maxima are the same for every acceptor: two wave-uniform scalars.

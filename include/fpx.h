@@ -844,6 +844,14 @@ int32_t fpx_profile_read_collective(fpx_ctx* ctx, int32_t* launches, double* tot
  * equal digests <=> equal state up to 2^-64.  Waits for the stream. */
 int32_t fpx_state_digest(fpx_ctx* ctx, uint64_t out[8]);
 
+/* FPX_BALLOT_PER_SLOT: audit of the per-row ballot summaries (one round per row that every stored ballot cell of
+ * the row holds, or "mixed"), a test hook.  out[0] = rows summarised as uniform, out[1] = rows marked mixed,
+ * out[2] = violations: uniform rows with a stored cell that differs from the summary (must be 0).  Outstanding
+ * lazy Phase1a promises are left as they are (the summaries describe the stored cells).  Groups of at most 128
+ * acceptors keep no summaries: every row counts as mixed.  FPX_EINVAL in FPX_BALLOT_ACCEPTOR mode.  Waits for the
+ * stream. */
+int32_t fpx_ballot_summary_audit(fpx_ctx* ctx, int64_t out[3]);
+
 #ifdef __cplusplus
 }
 #endif
