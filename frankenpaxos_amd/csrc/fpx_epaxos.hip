@@ -31,7 +31,9 @@
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <new>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/fpx.h"
@@ -1416,13 +1418,13 @@ struct fpx_epx {
   EpxState st;
   hipStream_t stream = nullptr, own_stream = nullptr;
   int last_hip = 0;
-  Buf kv, kv2, seg, conf, tmp, tick, h_leader, h_number, h_key, h_set, h_mask, h_seen, h_rank, h_triple, o_fast, o_deps, o_ldeps, o_own, cl, hp, fusedb, metab;
-  Buf mk_misc, mk_rec, mk_pair, mk_pconf, h_off, h_keys;  // multi-key commands (fpx_epaxos_mk.hpp)
+  Buf kv, kv2, seg, conf, tmp, tick, fusedb, metab;
+  Buf stage;                                               // the arrays of a host-pointer call (host_call)
+  Buf mk_misc, mk_rec, mk_pair, mk_pconf;                  // multi-key commands (fpx_epaxos_mk.hpp)
   int32_t* mk_host = nullptr;                              // page-locked: k_mk_total's line
   Buf p_fast, p_deps, p_ldeps, p_own;      // the four output arrays when a packed tick goes the first form's way
   Buf kp_hist, kp_recs, kp_misc;          // K5 second form (fpx_epaxos_kp.hpp)
   Buf dg_msg, dg_direct, dg_clo, dg_pre, dg_tmax, dg_pairs, dg_pairs2, dg_ctl, dg_key;  // device dependency-graph execution
-  Buf dgh_in, dgh_out;                    // fpx_epx_execute: the host arrays' stay on the device
   int32_t dg_seq = 0;
   int dg_rounds_hint = 8;                 // closure rounds the first chunk of the next fpx_epx_execute_dev enqueues (DG_ROUNDS at first)
   uint32_t* kp_flag = nullptr;            // page-locked: [0] sequence number of the tick whose count [1] is valid
@@ -1465,6 +1467,118 @@ int grow(fpx_epx* e, Buf* b, size_t bytes) {
   EHIP(e, hipMalloc(&b->p, std::max<size_t>(bytes, 256)));
   b->cap = std::max<size_t>(bytes, 256);
   return FPX_OK;
+}
+
+int launch_check(fpx_epx* e) {
+  hipError_t le = hipGetLastError();
+  if (le != hipSuccess) {
+    e->last_hip = (int)le;
+    return FPX_EHIP;
+  }
+  return FPX_OK;
+}
+
+// f(std::integral_constant<int, n>) for the replica counts a context can have (3, 5, 7)
+template <typename F>
+auto by_n(int n, F&& f) {
+  switch (n) {
+    case 3: return f(std::integral_constant<int, 3>());
+    case 5: return f(std::integral_constant<int, 5>());
+    default: return f(std::integral_constant<int, 7>());
+  }
+}
+
+// the run id of a Prepare / Accept / handlePreAccept batch: the validation kernels stamp every instance with it, so the
+// instances of one batch must be distinct
+int next_run_id(fpx_epx* e, uint32_t* id) {
+  if (++e->cl_run == 0) {  // stamp space exhausted: start over
+    EHIP(e, hipMemsetAsync(e->st.cl_stamp, 0, (size_t)e->st.n * e->st.num_instances * 4, e->stream));
+    e->cl_run = 1;
+  }
+  *id = e->cl_run;
+  return FPX_OK;
+}
+
+// a packed tick that goes the first form's way writes the four output arrays into the context's own, packed at the end
+int packed_fallback(fpx_epx* e, int m, uint8_t** fast, int32_t** deps, int32_t** leader_deps, int32_t** own_values_end) {
+  const int n = e->st.n;
+  int rc;
+  if ((rc = grow(e, &e->p_fast, (size_t)m))) return rc;
+  if ((rc = grow(e, &e->p_deps, (size_t)m * n * 4))) return rc;
+  if ((rc = grow(e, &e->p_ldeps, (size_t)m * n * 4))) return rc;
+  if ((rc = grow(e, &e->p_own, (size_t)m * 8))) return rc;
+  *fast = (uint8_t*)e->p_fast.p, *deps = (int32_t*)e->p_deps.p, *leader_deps = (int32_t*)e->p_ldeps.p;
+  *own_values_end = (int32_t*)e->p_own.p;
+  return FPX_OK;
+}
+
+// ---- host-pointer calls: stage, launch, copy back ------------------------------------------------------------------
+// An array of a host call, carved out of the context's staging buffer: uploaded from `src` when that is not NULL,
+// downloaded to `dst` when that is not NULL, and starting as `fill` bytes (0 or 0xFF; NO_FILL: whatever the buffer held).
+// It is staged either way: an input or output the caller leaves out is device scratch.
+constexpr int NO_FILL = -1;
+constexpr size_t STAGE_ALIGN = 256;  // (what hipMalloc guarantees)
+struct Staged {
+  void* slot;                   // the caller's T*, pointed at the array
+  void (*place)(void*, char*);
+  const void* src;
+  void* dst;
+  size_t bytes;
+  int fill;
+  size_t span() const { return (bytes + STAGE_ALIGN - 1) & ~(STAGE_ALIGN - 1); }
+};
+template <typename T>
+Staged arr(T*& d, const void* src, void* dst, size_t count, int fill) {
+  return {&d, [](void* s, char* p) { *static_cast<T**>(s) = reinterpret_cast<T*>(p); }, src, dst, count * sizeof(T), fill};
+}
+template <typename T>
+Staged in(T*& d, const void* src, size_t count) {
+  return arr(d, src, nullptr, count, NO_FILL);
+}
+template <typename T>
+Staged out(T*& d, void* dst, size_t count, int fill = NO_FILL) {
+  return arr(d, nullptr, dst, count, fill);
+}
+template <typename T>
+Staged scratch(T*& d, size_t count, int fill = NO_FILL) {
+  return arr(d, nullptr, nullptr, count, fill);
+}
+
+// The driver of the host-pointer entry points: grows the staging buffer once to hold every array, carves them in order,
+// uploads the inputs, fills (neighbours with one fill value are one memset), runs launch(), checks the launches, downloads
+// the outputs and returns the device's status.  The host checks of the call come before it: nothing is staged on a bad
+// batch.
+template <typename Launch>
+int host_call(fpx_epx* e, std::initializer_list<Staged> arrays, Launch launch) {
+  size_t total = 0;
+  for (const Staged& a : arrays) total += a.span();
+  int rc;
+  if ((rc = grow(e, &e->stage, total))) return rc;
+  char* const base = (char*)e->stage.p;
+  char* p = base;
+  for (const Staged& a : arrays) {
+    a.place(a.slot, p);
+    if (a.src && a.bytes) EHIP(e, hipMemcpyAsync(p, a.src, a.bytes, hipMemcpyHostToDevice, e->stream));
+    p += a.span();
+  }
+  char* run = nullptr;  // [run, p) is filled with the byte `value`
+  int value = NO_FILL;
+  p = base;
+  for (const Staged& a : arrays) {
+    if (a.fill != value) {
+      if (value != NO_FILL) EHIP(e, hipMemsetAsync(run, value, p - run, e->stream));
+      run = p, value = a.fill;
+    }
+    p += a.span();
+  }
+  if (value != NO_FILL) EHIP(e, hipMemsetAsync(run, value, p - run, e->stream));
+  if ((rc = launch()) || (rc = launch_check(e))) return rc;
+  p = base;
+  for (const Staged& a : arrays) {
+    if (a.dst && a.bytes) EHIP(e, hipMemcpyAsync(a.dst, p, a.bytes, hipMemcpyDeviceToHost, e->stream));
+    p += a.span();
+  }
+  return fpx_epx_sync(e);
 }
 
 template <int N>
@@ -1741,12 +1855,7 @@ int dg_execute_packed(fpx_epx* e, int m, const int32_t* d_leader, const int32_t*
   if (nexec) *nexec = executables;
   if (ncomp) *ncomp = executables > 0 ? host[4] : 0;
   if (needs_host) *needs_host = host[2];
-  hipError_t le = hipGetLastError();
-  if (le != hipSuccess) {
-    e->last_hip = (int)le;
-    return FPX_EHIP;
-  }
-  return FPX_OK;
+  return launch_check(e);
 }
 
 // device dependency-graph execution of one tick's commits (fpx_depgraph_dev.hpp)
@@ -1859,12 +1968,7 @@ int dg_execute(fpx_epx* e, int m, const int32_t* d_leader, const int32_t* d_numb
   if (nexec) *nexec = executables;
   if (ncomp) *ncomp = executables > 0 ? host[4] : 0;
   if (needs_host) *needs_host = host[2];
-  hipError_t le = hipGetLastError();
-  if (le != hipSuccess) {
-    e->last_hip = (int)le;
-    return FPX_EHIP;
-  }
-  return FPX_OK;
+  return launch_check(e);
 }
 
 }  // namespace
@@ -1956,15 +2060,13 @@ int32_t fpx_epx_destroy(fpx_epx* e) {
                 e->st.largest, e->st.cl_stamp, e->st.cl_deps, e->st.cl_dend};
   for (void* p : ps)
     if (p) (void)hipFree(p);
-  Buf* bs[] = {&e->kv, &e->kv2, &e->seg, &e->conf, &e->tmp, &e->tick, &e->h_leader, &e->h_number,
-               &e->h_key, &e->h_set, &e->h_mask, &e->h_seen, &e->h_rank, &e->h_triple, &e->o_fast, &e->o_deps, &e->o_ldeps,
-               &e->o_own, &e->cl, &e->hp, &e->fusedb, &e->metab, &e->mk_misc, &e->mk_rec, &e->mk_pair, &e->mk_pconf,
-               &e->h_off, &e->h_keys};
+  Buf* bs[] = {&e->kv, &e->kv2, &e->seg, &e->conf, &e->tmp, &e->tick, &e->fusedb, &e->metab, &e->stage, &e->mk_misc, &e->mk_rec,
+               &e->mk_pair, &e->mk_pconf};
   for (Buf* b : bs)
     if (b->p) (void)hipFree(b->p);
   if (e->mk_host) (void)hipHostFree(e->mk_host);
   for (Buf* b : {&e->kp_hist, &e->kp_recs, &e->kp_misc, &e->p_fast, &e->p_deps, &e->p_ldeps, &e->p_own, &e->dg_msg, &e->dg_direct,
-                 &e->dg_clo, &e->dg_pre, &e->dg_tmax, &e->dg_pairs, &e->dg_pairs2, &e->dg_ctl, &e->dg_key, &e->dgh_in, &e->dgh_out})
+                 &e->dg_clo, &e->dg_pre, &e->dg_tmax, &e->dg_pairs, &e->dg_pairs2, &e->dg_ctl, &e->dg_key})
     if (b->p) (void)hipFree(b->p);
   if (e->kp_flag) (void)hipHostFree(e->kp_flag);
   if (e->own_stream) (void)hipStreamDestroy(e->own_stream);
@@ -2005,17 +2107,6 @@ static int check_key_lists(int32_t m, const int32_t* key_off, const int32_t* key
   return FPX_OK;
 }
 
-static int upload_key_lists(fpx_epx* e, int32_t m, const int32_t* key_off, const int32_t* keys, int64_t P, const int32_t** d_off,
-                            const int32_t** d_keys) {
-  int rc;
-  if ((rc = grow(e, &e->h_off, ((size_t)m + 1) * 4))) return rc;
-  if ((rc = grow(e, &e->h_keys, (size_t)std::max<int64_t>(P, 1) * 4))) return rc;
-  EHIP(e, hipMemcpyAsync(e->h_off.p, key_off, ((size_t)m + 1) * 4, hipMemcpyHostToDevice, e->stream));
-  if (P > 0) EHIP(e, hipMemcpyAsync(e->h_keys.p, keys, (size_t)P * 4, hipMemcpyHostToDevice, e->stream));
-  *d_off = (const int32_t*)e->h_off.p, *d_keys = (const int32_t*)e->h_keys.p;
-  return FPX_OK;
-}
-
 static int32_t preaccept_dev_impl(fpx_epx* e, int32_t m, const int32_t* d_leader, const int32_t* d_number,
                                   const int32_t* d_key, const uint8_t* d_is_set, const uint8_t* d_resp_mask,
                                   const uint8_t* d_seen_mask, const int32_t* d_rank, const int32_t* d_triple_id,
@@ -2028,7 +2119,7 @@ static int32_t preaccept_dev_impl(fpx_epx* e, int32_t m, const int32_t* d_leader
   int rc;
   // the second form (fpx_epaxos_kp.hpp): one partition pass by key, everything else on chip -- when the keys are
   // one LDS counter each and ranks and slots share a 32-bit sort word
-  const int kp_tc = n == 3 ? KpTile<3>::TC : n == 5 ? KpTile<5>::TC : KpTile<7>::TC;
+  const int kp_tc = by_n(n, [](auto N) { return KpTile<N>::TC; });
   if (!e->kp_off && e->kp_flag_dev && e->st.num_keys <= KP_MAXB && m < (1 << 21) &&
       (long long)m <= (long long)e->st.num_keys * kp_tc &&  // (else some key must overflow the on-chip tables)
       ((e->st.num_instances == 0 && !d_triple_id) || n >= 5)) {  // (n = 3 with a command log: the first form)
@@ -2038,29 +2129,10 @@ static int32_t preaccept_dev_impl(fpx_epx* e, int32_t m, const int32_t* d_leader
     kb.seen_mask = d_seen_mask, kb.rank = d_rank, kb.triple = d_triple_id;
     kb.fast = d_fast, kb.deps = d_deps, kb.leader_deps = d_leader_deps, kb.own_values_end = d_own_values_end;
     bool done = false;
-    switch (n) {
-      case 3: rc = launch_kp<3>(e, kb, d_packed, &done); break;
-      case 5: rc = launch_kp<5>(e, kb, d_packed, &done); break;
-      default: rc = launch_kp<7>(e, kb, d_packed, &done); break;
-    }
-    if (rc) return rc;
-    if (done) {
-      hipError_t le = hipGetLastError();
-      if (le != hipSuccess) {
-        e->last_hip = (int)le;
-        return FPX_EHIP;
-      }
-      return FPX_OK;
-    }
+    if ((rc = by_n(n, [&](auto N) { return launch_kp<N>(e, kb, d_packed, &done); }))) return rc;
+    if (done) return launch_check(e);
   }
-  if (d_packed) {  // the first form writes the four arrays: into the context's own, packed at the end
-    if ((rc = grow(e, &e->p_fast, (size_t)m))) return rc;
-    if ((rc = grow(e, &e->p_deps, (size_t)m * n * 4))) return rc;
-    if ((rc = grow(e, &e->p_ldeps, (size_t)m * n * 4))) return rc;
-    if ((rc = grow(e, &e->p_own, (size_t)m * 8))) return rc;
-    d_fast = (uint8_t*)e->p_fast.p, d_deps = (int32_t*)e->p_deps.p, d_leader_deps = (int32_t*)e->p_ldeps.p;
-    d_own_values_end = (int32_t*)e->p_own.p;
-  }
+  if (d_packed && (rc = packed_fallback(e, m, &d_fast, &d_deps, &d_leader_deps, &d_own_values_end))) return rc;
   if ((rc = grow(e, &e->kv, (size_t)n * m * 8))) return rc;
   if ((rc = grow(e, &e->kv2, (size_t)n * m * 8))) return rc;
   if ((rc = grow(e, &e->tick, (size_t)n * e->st.num_keys * 2 * n * 4))) return rc;
@@ -2093,22 +2165,13 @@ static int32_t preaccept_dev_impl(fpx_epx* e, int32_t m, const int32_t* d_leader
   b.kv_sorted = sort_by_key(e, m, b.kv, b.kv_sorted, d_rank, &rc, &key_totals, &key_buckets);
   if (rc) return rc;
   launch_segments(e, b, key_totals, key_buckets);
-  switch (n) {
-    case 3: launch_scan_decide<3>(e, b); break;
-    case 5: launch_scan_decide<5>(e, b); break;
-    default: launch_scan_decide<7>(e, b); break;
-  }
+  by_n(n, [&](auto N) { launch_scan_decide<N>(e, b); });
   const long long tot = (long long)e->st.num_keys * n * n;
   hipLaunchKernelGGL(k_epx_commit, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, e->stream, e->st, b);
   if (d_packed)
     hipLaunchKernelGGL(k_epx_pack, dim3((m + 255) / 256), dim3(256), 0, e->stream, e->st, m, d_fast, d_deps, d_leader_deps,
                        d_own_values_end, d_packed, fpx_epx_packed_stride(n));
-  hipError_t le = hipGetLastError();
-  if (le != hipSuccess) {
-    e->last_hip = (int)le;
-    return FPX_EHIP;
-  }
-  return FPX_OK;
+  return launch_check(e);
 }
 
 int32_t fpx_epx_packed_stride(int32_t num_replicas) { return (2 * num_replicas + 3 + 3) / 4 * 4; }
@@ -2123,11 +2186,10 @@ int32_t fpx_epx_execute_dev(fpx_epx* e, int32_t m, const int32_t* d_leader, cons
   if (needs_host_path) *needs_host_path = 0;
   if (m == 0) return FPX_OK;
   if (m >= (1 << 21)) return FPX_EINVAL;
-  switch (e->st.n) {
-    case 3: return dg_execute<3>(e, m, d_leader, d_number, d_packed, d_committed, first, count, d_order, d_component, num_executed, num_components, needs_host_path);
-    case 5: return dg_execute<5>(e, m, d_leader, d_number, d_packed, d_committed, first, count, d_order, d_component, num_executed, num_components, needs_host_path);
-    default: return dg_execute<7>(e, m, d_leader, d_number, d_packed, d_committed, first, count, d_order, d_component, num_executed, num_components, needs_host_path);
-  }
+  return by_n(e->st.n, [&](auto N) {
+    return dg_execute<N>(e, m, d_leader, d_number, d_packed, d_committed, first, count, d_order, d_component, num_executed,
+                         num_components, needs_host_path);
+  });
 }
 
 int32_t fpx_epx_execute(fpx_epx* e, int32_t m, const int32_t* leader, const int32_t* number, const int32_t* deps,
@@ -2154,32 +2216,29 @@ int32_t fpx_epx_execute(fpx_epx* e, int32_t m, const int32_t* leader, const int3
     for (int l = 0; l < n; ++l) line[l] = deps[(size_t)i * n + l];
     line[2 * n] = deps_values_end ? deps_values_end[i] : 0;
   }
-  const size_t mp = ((size_t)m + 63) & ~(size_t)63;
-  int rc;
-  if ((rc = grow(e, &e->dgh_in, mp * 4 * 2 + mp + lines.size() * 4 + 256))) return rc;
-  if ((rc = grow(e, &e->dgh_out, mp * 4 * 2))) return rc;
-  char* p = (char*)e->dgh_in.p;
-  int32_t *d_leader = (int32_t*)p, *d_number = (int32_t*)(p + mp * 4), *d_packed = (int32_t*)(p + mp * 8);
-  uint8_t* d_mask = (uint8_t*)(p + mp * 8 + lines.size() * 4);
-  int32_t *d_order = (int32_t*)e->dgh_out.p, *d_comp = d_order + mp;
-  EHIP(e, hipMemcpyAsync(d_leader, leader, (size_t)m * 4, hipMemcpyHostToDevice, e->stream));
-  EHIP(e, hipMemcpyAsync(d_number, number, (size_t)m * 4, hipMemcpyHostToDevice, e->stream));
-  EHIP(e, hipMemcpyAsync(d_packed, lines.data(), lines.size() * 4, hipMemcpyHostToDevice, e->stream));
-  if (committed) EHIP(e, hipMemcpyAsync(d_mask, committed, (size_t)m, hipMemcpyHostToDevice, e->stream));
-  EHIP(e, hipStreamSynchronize(e->stream));  // (the host arrays and `lines` may be pageable)
-  int64_t ne = 0, nc = 0;
-  int32_t nh = 0;
-  rc = fpx_epx_execute_dev(e, m, d_leader, d_number, d_packed, committed ? d_mask : nullptr, first, count, d_order, d_comp, &ne, &nc, &nh);
-  if (rc) return rc;
-  if (ne > 0 && !nh) {
-    EHIP(e, hipMemcpyAsync(order, d_order, (size_t)ne * 4, hipMemcpyDeviceToHost, e->stream));
-    EHIP(e, hipMemcpyAsync(component, d_comp, (size_t)ne * 4, hipMemcpyDeviceToHost, e->stream));
-    EHIP(e, hipStreamSynchronize(e->stream));
-  }
-  if (num_executed) *num_executed = ne;
-  if (num_components) *num_components = nc;
-  if (needs_host_path) *needs_host_path = nh;
-  return FPX_OK;
+  const int32_t *d_leader, *d_number, *d_packed;
+  const uint8_t* d_mask;
+  int32_t *d_order, *d_comp;
+  auto launch = [&]() -> int {
+    EHIP(e, hipStreamSynchronize(e->stream));  // (the host arrays and `lines` may be pageable)
+    int64_t ne = 0, nc = 0;
+    int32_t nh = 0;
+    const int rc = fpx_epx_execute_dev(e, m, d_leader, d_number, d_packed, committed ? d_mask : nullptr, first, count, d_order,
+                                       d_comp, &ne, &nc, &nh);
+    if (rc) return rc;
+    if (ne > 0 && !nh) {  // (the executed entries only)
+      EHIP(e, hipMemcpyAsync(order, d_order, (size_t)ne * 4, hipMemcpyDeviceToHost, e->stream));
+      EHIP(e, hipMemcpyAsync(component, d_comp, (size_t)ne * 4, hipMemcpyDeviceToHost, e->stream));
+      EHIP(e, hipStreamSynchronize(e->stream));
+    }
+    if (num_executed) *num_executed = ne;
+    if (num_components) *num_components = nc;
+    if (needs_host_path) *needs_host_path = nh;
+    return FPX_OK;
+  };
+  return host_call(e, {in(d_leader, leader, m), in(d_number, number, m), in(d_packed, lines.data(), lines.size()),
+                       in(d_mask, committed, m), scratch(d_order, m), scratch(d_comp, m)},
+                   launch);
 }
 
 int32_t fpx_epx_preaccept_dev(fpx_epx* e, int32_t m, const int32_t* d_leader, const int32_t* d_number,
@@ -2197,45 +2256,6 @@ int32_t fpx_epx_preaccept_packed_dev(fpx_epx* e, int32_t m, const int32_t* d_lea
   if (!d_packed && m > 0) return FPX_EINVAL;
   return preaccept_dev_impl(e, m, d_leader, d_number, d_key, d_is_set, d_resp_mask, d_seen_mask, d_rank, d_triple_id, nullptr,
                             nullptr, nullptr, nullptr, d_packed);
-}
-
-int32_t fpx_epx_preaccept(fpx_epx* e, int32_t m, const int32_t* leader, const int32_t* number, const int32_t* key,
-                          const uint8_t* is_set, const uint8_t* resp_mask, const uint8_t* seen_mask,
-                          const int32_t* rank, const int32_t* triple_id, uint8_t* fast, int32_t* deps,
-                          int32_t* leader_deps, int32_t* own_values_end) {
-  if (!e || m < 0 || (m > 0 && (!leader || !number || !key || !is_set || !resp_mask || !rank))) return FPX_EINVAL;
-  EpxDeviceGuard _dg(e->cfg.device);
-  if (m == 0) return FPX_OK;
-  const int n = e->st.n;
-  int rc;
-  auto up = [&](Buf* b, const void* src, size_t bytes) -> int {
-    int r2 = grow(e, b, bytes);
-    if (r2) return r2;
-    EHIP(e, hipMemcpyAsync(b->p, src, bytes, hipMemcpyHostToDevice, e->stream));
-    return FPX_OK;
-  };
-  if ((rc = up(&e->h_leader, leader, (size_t)m * 4))) return rc;
-  if ((rc = up(&e->h_number, number, (size_t)m * 4))) return rc;
-  if ((rc = up(&e->h_key, key, (size_t)m * 4))) return rc;
-  if ((rc = up(&e->h_set, is_set, (size_t)m))) return rc;
-  if ((rc = up(&e->h_mask, resp_mask, (size_t)m))) return rc;
-  if (seen_mask && (rc = up(&e->h_seen, seen_mask, (size_t)m))) return rc;
-  if ((rc = up(&e->h_rank, rank, (size_t)n * m * 4))) return rc;
-  if (triple_id && (rc = up(&e->h_triple, triple_id, (size_t)m * 4))) return rc;
-  if ((rc = grow(e, &e->o_fast, (size_t)m))) return rc;
-  if ((rc = grow(e, &e->o_deps, (size_t)m * n * 4))) return rc;
-  if ((rc = grow(e, &e->o_ldeps, (size_t)m * n * 4))) return rc;
-  if ((rc = grow(e, &e->o_own, (size_t)m * 8))) return rc;
-  rc = fpx_epx_preaccept_dev(e, m, (int32_t*)e->h_leader.p, (int32_t*)e->h_number.p, (int32_t*)e->h_key.p,
-                             (uint8_t*)e->h_set.p, (uint8_t*)e->h_mask.p, seen_mask ? (uint8_t*)e->h_seen.p : nullptr,
-                             (int32_t*)e->h_rank.p, triple_id ? (int32_t*)e->h_triple.p : nullptr, (uint8_t*)e->o_fast.p,
-                             (int32_t*)e->o_deps.p, (int32_t*)e->o_ldeps.p, (int32_t*)e->o_own.p);
-  if (rc) return rc;
-  if (fast) EHIP(e, hipMemcpyAsync(fast, e->o_fast.p, (size_t)m, hipMemcpyDeviceToHost, e->stream));
-  if (deps) EHIP(e, hipMemcpyAsync(deps, e->o_deps.p, (size_t)m * n * 4, hipMemcpyDeviceToHost, e->stream));
-  if (leader_deps) EHIP(e, hipMemcpyAsync(leader_deps, e->o_ldeps.p, (size_t)m * n * 4, hipMemcpyDeviceToHost, e->stream));
-  if (own_values_end) EHIP(e, hipMemcpyAsync(own_values_end, e->o_own.p, (size_t)m * 8, hipMemcpyDeviceToHost, e->stream));
-  return fpx_epx_sync(e);
 }
 
 // K5 with key lists: every command one key -> the single-key tick as it is (keys as key); otherwise the pair form
@@ -2276,14 +2296,7 @@ static int32_t preaccept_mk_impl(fpx_epx* e, int32_t m, const int32_t* d_leader,
   if (h[1] == 0)  // key_off[i] = i: today's tick, on chip where it fits
     return preaccept_dev_impl(e, m, d_leader, d_number, d_keys, d_is_set, d_resp_mask, d_seen_mask, d_rank, d_triple_id, d_fast,
                               d_deps, d_leader_deps, d_own_values_end, d_packed);
-  if (d_packed) {
-    if ((rc = grow(e, &e->p_fast, (size_t)m))) return rc;
-    if ((rc = grow(e, &e->p_deps, (size_t)m * n * 4))) return rc;
-    if ((rc = grow(e, &e->p_ldeps, (size_t)m * n * 4))) return rc;
-    if ((rc = grow(e, &e->p_own, (size_t)m * 8))) return rc;
-    d_fast = (uint8_t*)e->p_fast.p, d_deps = (int32_t*)e->p_deps.p, d_leader_deps = (int32_t*)e->p_ldeps.p;
-    d_own_values_end = (int32_t*)e->p_own.p;
-  }
+  if (d_packed && (rc = packed_fallback(e, m, &d_fast, &d_deps, &d_leader_deps, &d_own_values_end))) return rc;
   const int NP = n <= 4 ? 4 : 8, Ux = std::max(U, 1);
   if ((rc = grow(e, &e->mk_rec, (size_t)n * m * 16))) return rc;
   if ((rc = grow(e, &e->mk_pair, (size_t)std::max(P, 1) * 5 + 64))) return rc;
@@ -2323,34 +2336,17 @@ static int32_t preaccept_mk_impl(fpx_epx* e, int32_t m, const int32_t* d_leader,
   mm.m = m, mm.off = d_off, mm.uniq = mb.uniq, mm.pconf = sb.conf, mm.conf = db.conf, mm.leader = d_leader;
   mm.resp_mask = d_resp_mask, mm.seen_mask = d_seen_mask;
   const int segs = n * e->st.num_keys;
-  switch (n) {
-    case 3:
-      if (U > 0) hipLaunchKernelGGL((k_epx_scan<3>), dim3((segs + 3) / 4), blk, 0, e->stream, e->st, sb);
-      hipLaunchKernelGGL((k_mk_merge<3>), gm, blk, 0, e->stream, e->st, mm);
-      hipLaunchKernelGGL((k_epx_decide<3>), gm, blk, 0, e->stream, e->st, db);
-      break;
-    case 5:
-      if (U > 0) hipLaunchKernelGGL((k_epx_scan<5>), dim3((segs + 3) / 4), blk, 0, e->stream, e->st, sb);
-      hipLaunchKernelGGL((k_mk_merge<5>), gm, blk, 0, e->stream, e->st, mm);
-      hipLaunchKernelGGL((k_epx_decide<5>), gm, blk, 0, e->stream, e->st, db);
-      break;
-    default:
-      if (U > 0) hipLaunchKernelGGL((k_epx_scan<7>), dim3((segs + 3) / 4), blk, 0, e->stream, e->st, sb);
-      hipLaunchKernelGGL((k_mk_merge<7>), gm, blk, 0, e->stream, e->st, mm);
-      hipLaunchKernelGGL((k_epx_decide<7>), gm, blk, 0, e->stream, e->st, db);
-      break;
-  }
+  by_n(n, [&](auto N) {
+    if (U > 0) hipLaunchKernelGGL((k_epx_scan<N>), dim3((segs + 3) / 4), blk, 0, e->stream, e->st, sb);
+    hipLaunchKernelGGL((k_mk_merge<N>), gm, blk, 0, e->stream, e->st, mm);
+    hipLaunchKernelGGL((k_epx_decide<N>), gm, blk, 0, e->stream, e->st, db);
+  });
   const long long tot = (long long)e->st.num_keys * n * n;
   if (U > 0) hipLaunchKernelGGL(k_epx_commit, dim3((unsigned)((tot + 255) / 256)), blk, 0, e->stream, e->st, sb);
   if (d_packed)
     hipLaunchKernelGGL(k_epx_pack, gm, blk, 0, e->stream, e->st, m, d_fast, d_deps, d_leader_deps, d_own_values_end, d_packed,
                        fpx_epx_packed_stride(n));
-  hipError_t le = hipGetLastError();
-  if (le != hipSuccess) {
-    e->last_hip = (int)le;
-    return FPX_EHIP;
-  }
-  return FPX_OK;
+  return launch_check(e);
 }
 
 int32_t fpx_epx_preaccept_mk_dev(fpx_epx* e, int32_t m, const int32_t* d_leader, const int32_t* d_number, const int32_t* d_key_offsets,
@@ -2370,46 +2366,52 @@ int32_t fpx_epx_preaccept_mk_packed_dev(fpx_epx* e, int32_t m, const int32_t* d_
                            d_triple_id, nullptr, nullptr, nullptr, nullptr, d_packed);
 }
 
-int32_t fpx_epx_preaccept_mk(fpx_epx* e, int32_t m, const int32_t* leader, const int32_t* number, const int32_t* key_offsets,
-                             const int32_t* keys, const uint8_t* is_set, const uint8_t* resp_mask, const uint8_t* seen_mask,
-                             const int32_t* rank, const int32_t* triple_id, uint8_t* fast, int32_t* deps, int32_t* leader_deps,
-                             int32_t* own_values_end) {
-  if (!e || m < 0 || (m > 0 && (!leader || !number || !key_offsets || !is_set || !resp_mask || !rank))) return FPX_EINVAL;
+// fpx_epx_preaccept and fpx_epx_preaccept_mk: one key per command (key) or key lists (key_off / keys)
+static int32_t preaccept_host(fpx_epx* e, int32_t m, const int32_t* leader, const int32_t* number, const int32_t* key,
+                              const int32_t* key_off, const int32_t* keys, const uint8_t* is_set, const uint8_t* resp_mask,
+                              const uint8_t* seen_mask, const int32_t* rank, const int32_t* triple_id, uint8_t* fast,
+                              int32_t* deps, int32_t* leader_deps, int32_t* own_values_end) {
+  if (!e || m < 0 || (m > 0 && (!leader || !number || !(key || key_off) || !is_set || !resp_mask || !rank))) return FPX_EINVAL;
   EpxDeviceGuard _dg(e->cfg.device);
   if (m == 0) return FPX_OK;
   const int n = e->st.n;
   int64_t P = 0;
   int rc;
-  if ((rc = check_key_lists(m, key_offsets, keys, e->st.num_keys, &P))) return rc;
-  auto up = [&](Buf* b, const void* src, size_t bytes) -> int {
-    int r2 = grow(e, b, bytes);
-    if (r2) return r2;
-    EHIP(e, hipMemcpyAsync(b->p, src, bytes, hipMemcpyHostToDevice, e->stream));
-    return FPX_OK;
+  if (key_off && (rc = check_key_lists(m, key_off, keys, e->st.num_keys, &P))) return rc;
+  const int32_t *d_leader, *d_number, *d_key, *d_off, *d_keys, *d_rank, *d_triple;
+  const uint8_t *d_set, *d_mask, *d_seen;
+  uint8_t* d_fast;
+  int32_t *d_deps, *d_ldeps, *d_own;
+  auto launch = [&]() -> int {
+    const uint8_t* seen = seen_mask ? d_seen : nullptr;
+    const int32_t* triple = triple_id ? d_triple : nullptr;
+    if (key_off)
+      return preaccept_mk_impl(e, m, d_leader, d_number, d_off, d_keys, d_set, d_mask, seen, d_rank, triple, d_fast, d_deps, d_ldeps,
+                               d_own, nullptr);
+    return preaccept_dev_impl(e, m, d_leader, d_number, d_key, d_set, d_mask, seen, d_rank, triple, d_fast, d_deps, d_ldeps, d_own,
+                              nullptr);
   };
-  const int32_t *d_off = nullptr, *d_keys = nullptr;
-  if ((rc = upload_key_lists(e, m, key_offsets, keys, P, &d_off, &d_keys))) return rc;
-  if ((rc = up(&e->h_leader, leader, (size_t)m * 4))) return rc;
-  if ((rc = up(&e->h_number, number, (size_t)m * 4))) return rc;
-  if ((rc = up(&e->h_set, is_set, (size_t)m))) return rc;
-  if ((rc = up(&e->h_mask, resp_mask, (size_t)m))) return rc;
-  if (seen_mask && (rc = up(&e->h_seen, seen_mask, (size_t)m))) return rc;
-  if ((rc = up(&e->h_rank, rank, (size_t)n * m * 4))) return rc;
-  if (triple_id && (rc = up(&e->h_triple, triple_id, (size_t)m * 4))) return rc;
-  if ((rc = grow(e, &e->o_fast, (size_t)m))) return rc;
-  if ((rc = grow(e, &e->o_deps, (size_t)m * n * 4))) return rc;
-  if ((rc = grow(e, &e->o_ldeps, (size_t)m * n * 4))) return rc;
-  if ((rc = grow(e, &e->o_own, (size_t)m * 8))) return rc;
-  rc = fpx_epx_preaccept_mk_dev(e, m, (int32_t*)e->h_leader.p, (int32_t*)e->h_number.p, d_off, d_keys, (uint8_t*)e->h_set.p,
-                                (uint8_t*)e->h_mask.p, seen_mask ? (uint8_t*)e->h_seen.p : nullptr, (int32_t*)e->h_rank.p,
-                                triple_id ? (int32_t*)e->h_triple.p : nullptr, (uint8_t*)e->o_fast.p, (int32_t*)e->o_deps.p,
-                                (int32_t*)e->o_ldeps.p, (int32_t*)e->o_own.p);
-  if (rc) return rc;
-  if (fast) EHIP(e, hipMemcpyAsync(fast, e->o_fast.p, (size_t)m, hipMemcpyDeviceToHost, e->stream));
-  if (deps) EHIP(e, hipMemcpyAsync(deps, e->o_deps.p, (size_t)m * n * 4, hipMemcpyDeviceToHost, e->stream));
-  if (leader_deps) EHIP(e, hipMemcpyAsync(leader_deps, e->o_ldeps.p, (size_t)m * n * 4, hipMemcpyDeviceToHost, e->stream));
-  if (own_values_end) EHIP(e, hipMemcpyAsync(own_values_end, e->o_own.p, (size_t)m * 8, hipMemcpyDeviceToHost, e->stream));
-  return fpx_epx_sync(e);
+  return host_call(e, {in(d_leader, leader, m), in(d_number, number, m), in(d_key, key, key_off ? 0 : m),
+                       in(d_off, key_off, key_off ? m + 1 : 0), in(d_keys, keys, P), in(d_set, is_set, m), in(d_mask, resp_mask, m),
+                       in(d_seen, seen_mask, m), in(d_rank, rank, (size_t)n * m), in(d_triple, triple_id, m), out(d_fast, fast, m),
+                       out(d_deps, deps, (size_t)m * n), out(d_ldeps, leader_deps, (size_t)m * n), out(d_own, own_values_end, (size_t)m * 2)},
+                   launch);
+}
+
+int32_t fpx_epx_preaccept(fpx_epx* e, int32_t m, const int32_t* leader, const int32_t* number, const int32_t* key,
+                          const uint8_t* is_set, const uint8_t* resp_mask, const uint8_t* seen_mask,
+                          const int32_t* rank, const int32_t* triple_id, uint8_t* fast, int32_t* deps,
+                          int32_t* leader_deps, int32_t* own_values_end) {
+  return preaccept_host(e, m, leader, number, key, nullptr, nullptr, is_set, resp_mask, seen_mask, rank, triple_id, fast, deps,
+                        leader_deps, own_values_end);
+}
+
+int32_t fpx_epx_preaccept_mk(fpx_epx* e, int32_t m, const int32_t* leader, const int32_t* number, const int32_t* key_offsets,
+                             const int32_t* keys, const uint8_t* is_set, const uint8_t* resp_mask, const uint8_t* seen_mask,
+                             const int32_t* rank, const int32_t* triple_id, uint8_t* fast, int32_t* deps, int32_t* leader_deps,
+                             int32_t* own_values_end) {
+  return preaccept_host(e, m, leader, number, nullptr, key_offsets, keys, is_set, resp_mask, seen_mask, rank, triple_id, fast, deps,
+                        leader_deps, own_values_end);
 }
 
 // Prepare / Accept on the command log: stage, validate, handle, scan the largestBallot's, (Accept) tally + commit
@@ -2425,76 +2427,44 @@ static int32_t cl_run(fpx_epx* e, int accept, int32_t m, const int32_t* leader, 
   if (m == 0) return FPX_OK;
   if (!leader || !number || !b_ord || !b_rep || !target || (accept && (!triple || !(key || key_off) || !is_set))) return FPX_EINVAL;
   const int n = e->st.n;
-  const int32_t *d_off = nullptr, *d_keys = nullptr;
-  if (key_off) {
-    int64_t P = 0;
-    int rc0 = check_key_lists(m, key_off, keys, e->st.num_keys, &P);
-    if (rc0 || (rc0 = upload_key_lists(e, m, key_off, keys, P, &d_off, &d_keys))) return rc0;
-  }
-  const int tiles = (m + CL_TILE - 1) / CL_TILE;
-  const size_t mp = ((size_t)m + 63) & ~(size_t)63;
-  // staging: 6 int32 inputs, is_set, target, 3 reply bit arrays, skip, committed, nack_ballot, 3 reply int arrays
-  // [m][n], contrib [n][m], nackflag [n][m], tilemax [n][tiles]
-  const size_t bytes = mp * 4 * 6 + mp * 7 + mp * 4 + (size_t)m * n * 4 * 3 + (size_t)n * mp * 4 + (size_t)n * mp +
-                       (size_t)n * tiles * 4 + 2048;
+  int64_t P = 0;
   int rc;
-  if ((rc = grow(e, &e->cl, bytes))) return rc;
-  char* p = (char*)e->cl.p;
-  auto take = [&](size_t sz) { char* q = p; p += (sz + 63) & ~(size_t)63; return q; };
-  int32_t* d_leader = (int32_t*)take(mp * 4); int32_t* d_number = (int32_t*)take(mp * 4);
-  int32_t* d_bo = (int32_t*)take(mp * 4); int32_t* d_br = (int32_t*)take(mp * 4); int32_t* d_tr = (int32_t*)take(mp * 4);
-  int32_t* d_key = (int32_t*)take(mp * 4); uint8_t* d_set = (uint8_t*)take(mp);
-  uint8_t* d_tgt = (uint8_t*)take(mp); uint8_t* d_ok = (uint8_t*)take(mp); uint8_t* d_nack = (uint8_t*)take(mp);
-  uint8_t* d_com = (uint8_t*)take(mp); uint8_t* d_skip = (uint8_t*)take(mp); uint8_t* d_done = (uint8_t*)take(mp);
-  int32_t* d_nb = (int32_t*)take(mp * 4);
-  int32_t* d_rs = (int32_t*)take((size_t)m * n * 4); int32_t* d_rv = (int32_t*)take((size_t)m * n * 4);
-  int32_t* d_rt = (int32_t*)take((size_t)m * n * 4);
-  int32_t* d_contrib = (int32_t*)take((size_t)n * m * 4); uint8_t* d_flag = (uint8_t*)take((size_t)n * m);
-  int32_t* d_tm = (int32_t*)take((size_t)n * tiles * 4);
-  EHIP(e, hipMemcpyAsync(d_leader, leader, (size_t)m * 4, hipMemcpyHostToDevice, e->stream));
-  EHIP(e, hipMemcpyAsync(d_number, number, (size_t)m * 4, hipMemcpyHostToDevice, e->stream));
-  EHIP(e, hipMemcpyAsync(d_bo, b_ord, (size_t)m * 4, hipMemcpyHostToDevice, e->stream));
-  EHIP(e, hipMemcpyAsync(d_br, b_rep, (size_t)m * 4, hipMemcpyHostToDevice, e->stream));
-  if (accept) EHIP(e, hipMemcpyAsync(d_tr, triple, (size_t)m * 4, hipMemcpyHostToDevice, e->stream));
-  if (accept && key) EHIP(e, hipMemcpyAsync(d_key, key, (size_t)m * 4, hipMemcpyHostToDevice, e->stream));
-  if (accept) EHIP(e, hipMemcpyAsync(d_set, is_set, (size_t)m, hipMemcpyHostToDevice, e->stream));
-  EHIP(e, hipMemcpyAsync(d_tgt, target, (size_t)m, hipMemcpyHostToDevice, e->stream));
-  EHIP(e, hipMemsetAsync(d_ok, 0, mp * 5, e->stream));  // ok, nack, commit, skip, committed are contiguous
-  EHIP(e, hipMemsetAsync(d_nb, 0xFF, mp * 4, e->stream));
-  ClBatch b;
-  memset(&b, 0, sizeof(b));
-  b.m = m, b.accept = accept, b.leader = d_leader, b.number = d_number, b.b_ord = d_bo, b.b_rep = d_br, b.triple = d_tr;
-  b.key = d_key, b.is_set = d_set, b.key_off = d_off, b.keys = d_keys;
-  b.target = d_tgt, b.ok_bits = d_ok, b.nack_bits = d_nack, b.commit_bits = d_com, b.nack_ballot = d_nb;
-  b.committed = d_done, b.reply_status = d_rs, b.reply_vote = d_rv, b.reply_triple = d_rt;
-  b.contrib = d_contrib, b.nackflag = d_flag, b.tilemax = d_tm, b.skip = d_skip;
-  if (++e->cl_run == 0) {  // stamp space exhausted: start over
-    EHIP(e, hipMemsetAsync(e->st.cl_stamp, 0, (size_t)n * e->st.num_instances * 4, e->stream));
-    e->cl_run = 1;
-  }
-  b.run_id = e->cl_run;
-  const dim3 gm((m + 255) / 256), blk(256);
-  hipLaunchKernelGGL(k_cl_validate, gm, blk, 0, e->stream, e->st, b);
-  if (accept) hipLaunchKernelGGL(k_cl_propose, gm, blk, 0, e->stream, e->st, b);
-  hipLaunchKernelGGL(k_cl_handle, dim3((unsigned)(((long long)m * n + 255) / 256)), blk, 0, e->stream, e->st, b);
-  hipLaunchKernelGGL(k_cl_tilemax, dim3(tiles, n), blk, 0, e->stream, b, tiles);
-  hipLaunchKernelGGL(k_cl_tilescan, dim3(n), blk, 0, e->stream, e->st, b, tiles);
-  hipLaunchKernelGGL(k_cl_nacks, dim3(tiles, n), blk, 0, e->stream, b, tiles);
-  if (accept) hipLaunchKernelGGL(k_cl_commit, gm, blk, 0, e->stream, e->st, b);
-  hipError_t le = hipGetLastError();
-  if (le != hipSuccess) {
-    e->last_hip = (int)le;
-    return FPX_EHIP;
-  }
-  if (ok_bits) EHIP(e, hipMemcpyAsync(ok_bits, d_ok, (size_t)m, hipMemcpyDeviceToHost, e->stream));
-  if (nack_bits) EHIP(e, hipMemcpyAsync(nack_bits, d_nack, (size_t)m, hipMemcpyDeviceToHost, e->stream));
-  if (commit_bits) EHIP(e, hipMemcpyAsync(commit_bits, d_com, (size_t)m, hipMemcpyDeviceToHost, e->stream));
-  if (nack_ballot) EHIP(e, hipMemcpyAsync(nack_ballot, d_nb, (size_t)m * 4, hipMemcpyDeviceToHost, e->stream));
-  if (committed) EHIP(e, hipMemcpyAsync(committed, d_done, (size_t)m, hipMemcpyDeviceToHost, e->stream));
-  if (reply_status) EHIP(e, hipMemcpyAsync(reply_status, d_rs, (size_t)m * n * 4, hipMemcpyDeviceToHost, e->stream));
-  if (reply_vote) EHIP(e, hipMemcpyAsync(reply_vote, d_rv, (size_t)m * n * 4, hipMemcpyDeviceToHost, e->stream));
-  if (reply_triple) EHIP(e, hipMemcpyAsync(reply_triple, d_rt, (size_t)m * n * 4, hipMemcpyDeviceToHost, e->stream));
-  return fpx_epx_sync(e);
+  if (key_off && (rc = check_key_lists(m, key_off, keys, e->st.num_keys, &P))) return rc;
+  const int tiles = (m + CL_TILE - 1) / CL_TILE;
+  const size_t mn = (size_t)m * n;
+  const int32_t *d_leader, *d_number, *d_bo, *d_br, *d_tr, *d_key, *d_off, *d_keys;
+  const uint8_t *d_set, *d_tgt;
+  uint8_t *d_ok, *d_nack, *d_com, *d_skip, *d_done, *d_flag;
+  int32_t *d_nb, *d_rs, *d_rv, *d_rt, *d_contrib, *d_tm;
+  auto launch = [&]() -> int {
+    ClBatch b;
+    memset(&b, 0, sizeof(b));
+    b.m = m, b.accept = accept, b.leader = d_leader, b.number = d_number, b.b_ord = d_bo, b.b_rep = d_br, b.triple = d_tr;
+    b.key = d_key, b.is_set = d_set;
+    if (key_off) b.key_off = d_off, b.keys = d_keys;
+    b.target = d_tgt, b.ok_bits = d_ok, b.nack_bits = d_nack, b.commit_bits = d_com, b.nack_ballot = d_nb;
+    b.committed = d_done, b.reply_status = d_rs, b.reply_vote = d_rv, b.reply_triple = d_rt;
+    b.contrib = d_contrib, b.nackflag = d_flag, b.tilemax = d_tm, b.skip = d_skip;
+    int rc2;
+    if ((rc2 = next_run_id(e, &b.run_id))) return rc2;
+    const dim3 gm((m + 255) / 256), blk(256);
+    hipLaunchKernelGGL(k_cl_validate, gm, blk, 0, e->stream, e->st, b);
+    if (accept) hipLaunchKernelGGL(k_cl_propose, gm, blk, 0, e->stream, e->st, b);
+    hipLaunchKernelGGL(k_cl_handle, dim3((unsigned)(((long long)m * n + 255) / 256)), blk, 0, e->stream, e->st, b);
+    hipLaunchKernelGGL(k_cl_tilemax, dim3(tiles, n), blk, 0, e->stream, b, tiles);
+    hipLaunchKernelGGL(k_cl_tilescan, dim3(n), blk, 0, e->stream, e->st, b, tiles);
+    hipLaunchKernelGGL(k_cl_nacks, dim3(tiles, n), blk, 0, e->stream, b, tiles);
+    if (accept) hipLaunchKernelGGL(k_cl_commit, gm, blk, 0, e->stream, e->st, b);
+    return FPX_OK;
+  };
+  // ok, nack, commit, skip and committed start at 0 (one memset), nack_ballot at -1
+  return host_call(e, {in(d_leader, leader, m), in(d_number, number, m), in(d_bo, b_ord, m), in(d_br, b_rep, m), in(d_tr, triple, m),
+                       in(d_key, key, m), in(d_off, key_off, key_off ? m + 1 : 0), in(d_keys, keys, P), in(d_set, is_set, m),
+                       in(d_tgt, target, m), out(d_ok, ok_bits, m, 0), out(d_nack, nack_bits, m, 0), out(d_com, commit_bits, m, 0),
+                       scratch(d_skip, m, 0), out(d_done, committed, m, 0), out(d_nb, nack_ballot, m, 0xFF),
+                       out(d_rs, reply_status, mn), out(d_rv, reply_vote, mn), out(d_rt, reply_triple, mn), scratch(d_contrib, mn),
+                       scratch(d_flag, mn), scratch(d_tm, (size_t)n * tiles)},
+                   launch);
 }
 
 int32_t fpx_epx_prepare(fpx_epx* e, int32_t m, const int32_t* leader, const int32_t* number, const int32_t* ballot_ordering,
@@ -2527,8 +2497,6 @@ static int32_t handle_commit_impl(fpx_epx* e, int32_t m, const int32_t* leader, 
       if (end != 0 && (end <= number[i] + 1 || deps[(size_t)i * n + leader[i]] > number[i])) return FPX_EINVAL;
     }
   }
-  const size_t mp = ((size_t)m + 63) & ~(size_t)63;
-  int rc;
   // who writes the entry: walking the batch from its end, a message leaves to the later messages of its instance the
   // replicas they go to
   std::vector<uint8_t> writer;
@@ -2553,35 +2521,21 @@ static int32_t handle_commit_impl(fpx_epx* e, int32_t m, const int32_t* leader, 
       a = z;
     }
   }
-  if ((rc = grow(e, &e->cl, mp * 4 * 5 + mp * 3 + (size_t)m * n * 4 + 1024))) return rc;
-  char* p = (char*)e->cl.p;
-  auto take = [&](size_t sz) { char* q = p; p += (sz + 63) & ~(size_t)63; return q; };
-  int32_t *d_leader = (int32_t*)take(mp * 4), *d_number = (int32_t*)take(mp * 4), *d_tr = (int32_t*)take(mp * 4);
-  int32_t *d_key = (int32_t*)take(mp * 4), *d_end = (int32_t*)take(mp * 4);
-  uint8_t *d_set = (uint8_t*)take(mp), *d_tgt = (uint8_t*)take(mp), *d_wr = (uint8_t*)take(mp);
-  EHIP(e, hipMemcpyAsync(d_wr, writer.data(), (size_t)m, hipMemcpyHostToDevice, e->stream));
-  int32_t* d_deps = (int32_t*)take((size_t)m * n * 4);
-  EHIP(e, hipMemcpyAsync(d_leader, leader, (size_t)m * 4, hipMemcpyHostToDevice, e->stream));
-  EHIP(e, hipMemcpyAsync(d_number, number, (size_t)m * 4, hipMemcpyHostToDevice, e->stream));
-  EHIP(e, hipMemcpyAsync(d_tr, triple_id, (size_t)m * 4, hipMemcpyHostToDevice, e->stream));
-  if (key) EHIP(e, hipMemcpyAsync(d_key, key, (size_t)m * 4, hipMemcpyHostToDevice, e->stream));
-  EHIP(e, hipMemcpyAsync(d_set, is_set, (size_t)m, hipMemcpyHostToDevice, e->stream));
-  EHIP(e, hipMemcpyAsync(d_tgt, target_mask, (size_t)m, hipMemcpyHostToDevice, e->stream));
-  const int32_t *d_off = nullptr, *d_keys = nullptr;
-  if (key_off && (rc = upload_key_lists(e, m, key_off, keys, P, &d_off, &d_keys))) return rc;
-  if (deps) EHIP(e, hipMemcpyAsync(d_deps, deps, (size_t)m * n * 4, hipMemcpyHostToDevice, e->stream));
-  if (deps && deps_values_end) EHIP(e, hipMemcpyAsync(d_end, deps_values_end, (size_t)m * 4, hipMemcpyHostToDevice, e->stream));
-  LcBatch b;
-  b.m = m, b.leader = d_leader, b.number = d_number, b.triple = d_tr, b.key = d_key, b.is_set = d_set;
-  b.key_off = d_off, b.keys = d_keys;
-  b.deps = deps ? d_deps : nullptr, b.deps_end = (deps && deps_values_end) ? d_end : nullptr, b.target = d_tgt, b.writer = d_wr;
-  hipLaunchKernelGGL(k_cl_learn_commit, dim3((unsigned)(((long long)m * n + 255) / 256)), dim3(256), 0, e->stream, e->st, b);
-  hipError_t le = hipGetLastError();
-  if (le != hipSuccess) {
-    e->last_hip = (int)le;
-    return FPX_EHIP;
-  }
-  return fpx_epx_sync(e);
+  const int32_t *d_leader, *d_number, *d_tr, *d_key, *d_off, *d_keys, *d_end, *d_deps;
+  const uint8_t *d_set, *d_tgt, *d_wr;
+  auto launch = [&]() -> int {
+    LcBatch b;
+    b.m = m, b.leader = d_leader, b.number = d_number, b.triple = d_tr, b.key = d_key, b.is_set = d_set;
+    b.key_off = key_off ? d_off : nullptr, b.keys = key_off ? d_keys : nullptr;
+    b.deps = deps ? d_deps : nullptr, b.deps_end = (deps && deps_values_end) ? d_end : nullptr, b.target = d_tgt, b.writer = d_wr;
+    hipLaunchKernelGGL(k_cl_learn_commit, dim3((unsigned)(((long long)m * n + 255) / 256)), dim3(256), 0, e->stream, e->st, b);
+    return FPX_OK;
+  };
+  return host_call(e, {in(d_leader, leader, m), in(d_number, number, m), in(d_tr, triple_id, m), in(d_key, key, m),
+                       in(d_end, deps ? deps_values_end : nullptr, m), in(d_set, is_set, m), in(d_tgt, target_mask, m),
+                       in(d_wr, writer.data(), m), in(d_deps, deps, (size_t)m * n), in(d_off, key_off, key_off ? m + 1 : 0),
+                       in(d_keys, keys, P)},
+                   launch);
 }
 
 int32_t fpx_epx_handle_prepare_oks(fpx_epx* e, int32_t m, const int32_t* leader, const int32_t* number,
@@ -2595,37 +2549,22 @@ int32_t fpx_epx_handle_prepare_oks(fpx_epx* e, int32_t m, const int32_t* leader,
   if (!leader || !number || !ballot_ordering || !ballot_replica || !resp_mask || !reply_status || !reply_vote_ballot || !reply_triple)
     return FPX_EINVAL;
   const int n = e->st.n;
-  const size_t mp = ((size_t)m + 63) & ~(size_t)63;
-  int rc;
-  if ((rc = grow(e, &e->cl, mp * 4 * 7 + mp + (size_t)m * n * 4 * 3 + 2048))) return rc;
-  char* p = (char*)e->cl.p;
-  auto take = [&](size_t sz) { char* q = p; p += (sz + 63) & ~(size_t)63; return q; };
-  int32_t *d_leader = (int32_t*)take(mp * 4), *d_number = (int32_t*)take(mp * 4), *d_bo = (int32_t*)take(mp * 4);
-  int32_t *d_br = (int32_t*)take(mp * 4), *d_act = (int32_t*)take(mp * 4), *d_src = (int32_t*)take(mp * 4), *d_tr = (int32_t*)take(mp * 4);
-  uint8_t* d_mask = (uint8_t*)take(mp);
-  int32_t *d_rs = (int32_t*)take((size_t)m * n * 4), *d_rv = (int32_t*)take((size_t)m * n * 4), *d_rt = (int32_t*)take((size_t)m * n * 4);
-  EHIP(e, hipMemcpyAsync(d_leader, leader, (size_t)m * 4, hipMemcpyHostToDevice, e->stream));
-  EHIP(e, hipMemcpyAsync(d_number, number, (size_t)m * 4, hipMemcpyHostToDevice, e->stream));
-  EHIP(e, hipMemcpyAsync(d_bo, ballot_ordering, (size_t)m * 4, hipMemcpyHostToDevice, e->stream));
-  EHIP(e, hipMemcpyAsync(d_br, ballot_replica, (size_t)m * 4, hipMemcpyHostToDevice, e->stream));
-  EHIP(e, hipMemcpyAsync(d_mask, resp_mask, (size_t)m, hipMemcpyHostToDevice, e->stream));
-  EHIP(e, hipMemcpyAsync(d_rs, reply_status, (size_t)m * n * 4, hipMemcpyHostToDevice, e->stream));
-  EHIP(e, hipMemcpyAsync(d_rv, reply_vote_ballot, (size_t)m * n * 4, hipMemcpyHostToDevice, e->stream));
-  EHIP(e, hipMemcpyAsync(d_rt, reply_triple, (size_t)m * n * 4, hipMemcpyHostToDevice, e->stream));
-  RcBatch b;
-  memset(&b, 0, sizeof(b));
-  b.m = m, b.as_intended = as_intended ? 1 : 0, b.leader = d_leader, b.number = d_number, b.b_ord = d_bo, b.b_rep = d_br;
-  b.resp_mask = d_mask, b.rs = d_rs, b.rv = d_rv, b.rt = d_rt, b.action = d_act, b.source = d_src, b.triple = d_tr;
-  hipLaunchKernelGGL(k_cl_recover, dim3((m + 255) / 256), dim3(256), 0, e->stream, e->st, b);
-  hipError_t le = hipGetLastError();
-  if (le != hipSuccess) {
-    e->last_hip = (int)le;
-    return FPX_EHIP;
-  }
-  if (action) EHIP(e, hipMemcpyAsync(action, d_act, (size_t)m * 4, hipMemcpyDeviceToHost, e->stream));
-  if (source) EHIP(e, hipMemcpyAsync(source, d_src, (size_t)m * 4, hipMemcpyDeviceToHost, e->stream));
-  if (triple) EHIP(e, hipMemcpyAsync(triple, d_tr, (size_t)m * 4, hipMemcpyDeviceToHost, e->stream));
-  return fpx_epx_sync(e);
+  const size_t mn = (size_t)m * n;
+  const int32_t *d_leader, *d_number, *d_bo, *d_br, *d_rs, *d_rv, *d_rt;
+  const uint8_t* d_mask;
+  int32_t *d_act, *d_src, *d_tr;
+  auto launch = [&]() -> int {
+    RcBatch b;
+    memset(&b, 0, sizeof(b));
+    b.m = m, b.as_intended = as_intended ? 1 : 0, b.leader = d_leader, b.number = d_number, b.b_ord = d_bo, b.b_rep = d_br;
+    b.resp_mask = d_mask, b.rs = d_rs, b.rv = d_rv, b.rt = d_rt, b.action = d_act, b.source = d_src, b.triple = d_tr;
+    hipLaunchKernelGGL(k_cl_recover, dim3((m + 255) / 256), dim3(256), 0, e->stream, e->st, b);
+    return FPX_OK;
+  };
+  return host_call(e, {in(d_leader, leader, m), in(d_number, number, m), in(d_bo, ballot_ordering, m), in(d_br, ballot_replica, m),
+                       out(d_act, action, m), out(d_src, source, m), out(d_tr, triple, m), in(d_mask, resp_mask, m),
+                       in(d_rs, reply_status, mn), in(d_rv, reply_vote_ballot, mn), in(d_rt, reply_triple, mn)},
+                   launch);
 }
 
 int32_t fpx_epx_accept(fpx_epx* e, int32_t m, const int32_t* leader, const int32_t* number, const int32_t* ballot_ordering,
@@ -2655,119 +2594,82 @@ static int32_t handle_preaccept_impl(fpx_epx* e, int32_t m, const int32_t* leade
   if (key_off && check_key_lists(m, key_off, keys, e->st.num_keys, &P64)) return FPX_EINVAL;
   const int P = key_off ? (int)P64 : m;
   const int tiles = (m + CL_TILE - 1) / CL_TILE;
-  const size_t mp = ((size_t)m + 63) & ~(size_t)63;
+  const size_t mn = (size_t)m * n;
+  const int NP = n <= 4 ? 4 : 8;
   int rc;
   if ((rc = grow(e, &e->kv, (size_t)n * std::max(P, 1) * 8))) return rc;
   if ((rc = grow(e, &e->kv2, (size_t)n * std::max(P, 1) * 8))) return rc;
   if ((rc = grow(e, &e->tick, (size_t)n * e->st.num_keys * 2 * n * 4))) return rc;
   if ((rc = grow(e, &e->seg, (size_t)n * e->st.num_keys * 8))) return rc;
-  if ((rc = grow(e, &e->conf, (size_t)m * n * (n <= 4 ? 4 : 8) * 4))) return rc;
-  // staging: 7 int32 inputs + deps_in [m][n], is_set, target, 4 reply bit arrays, nack_ballot, reply_deps [m][n][n],
-  // reply_end / reply_triple [m][n], act / nackflag [n][m], contrib [n][m], tilemax [n][tiles]
-  const size_t bytes = mp * 4 * 7 + (size_t)m * n * 4 + mp * 6 + mp * 4 + (size_t)m * n * n * 4 + (size_t)m * n * 4 * 2 +
-                       (size_t)n * mp * 2 + (size_t)n * mp * 4 + (size_t)n * tiles * 4 + 2048;
-  if ((rc = grow(e, &e->hp, bytes))) return rc;
-  char* p = (char*)e->hp.p;
-  auto take = [&](size_t sz) { char* q = p; p += (sz + 63) & ~(size_t)63; return q; };
-  int32_t* d_leader = (int32_t*)take(mp * 4); int32_t* d_number = (int32_t*)take(mp * 4);
-  int32_t* d_bo = (int32_t*)take(mp * 4); int32_t* d_br = (int32_t*)take(mp * 4); int32_t* d_key = (int32_t*)take(mp * 4);
-  int32_t* d_tr = (int32_t*)take(mp * 4); int32_t* d_dend = (int32_t*)take(mp * 4);
-  int32_t* d_din = (int32_t*)take((size_t)m * n * 4);
-  uint8_t* d_set = (uint8_t*)take(mp); uint8_t* d_tgt = (uint8_t*)take(mp);
-  uint8_t* d_ok = (uint8_t*)take(mp); uint8_t* d_resend = (uint8_t*)take(mp); uint8_t* d_nack = (uint8_t*)take(mp);
-  uint8_t* d_com = (uint8_t*)take(mp);
-  int32_t* d_nb = (int32_t*)take(mp * 4);
-  int32_t* d_rd = (int32_t*)take((size_t)m * n * n * 4); int32_t* d_re = (int32_t*)take((size_t)m * n * 4);
-  int32_t* d_rt = (int32_t*)take((size_t)m * n * 4);
-  uint8_t* d_act = (uint8_t*)take((size_t)n * m); uint8_t* d_flag = (uint8_t*)take((size_t)n * m);
-  int32_t* d_contrib = (int32_t*)take((size_t)n * m * 4); int32_t* d_tm = (int32_t*)take((size_t)n * tiles * 4);
-  auto up = [&](void* dst, const void* src, size_t sz) { return hipMemcpyAsync(dst, src, sz, hipMemcpyHostToDevice, e->stream); };
-  EHIP(e, up(d_leader, leader, (size_t)m * 4));
-  EHIP(e, up(d_number, number, (size_t)m * 4));
-  EHIP(e, up(d_bo, ballot_ordering, (size_t)m * 4));
-  EHIP(e, up(d_br, ballot_replica, (size_t)m * 4));
-  if (key) EHIP(e, up(d_key, key, (size_t)m * 4));
-  const int32_t *d_off = nullptr, *d_keys = nullptr;
-  int32_t* d_pconf = nullptr;
-  MkBatch mb;
-  memset(&mb, 0, sizeof(mb));
+  if ((rc = grow(e, &e->conf, (size_t)m * n * NP * 4))) return rc;
   if (key_off) {
-    if ((rc = upload_key_lists(e, m, key_off, keys, P, &d_off, &d_keys))) return rc;
     if ((rc = grow(e, &e->mk_pair, (size_t)std::max(P, 1) * 5 + 64))) return rc;
-    if ((rc = grow(e, &e->mk_pconf, (size_t)std::max(P, 1) * n * (n <= 4 ? 4 : 8) * 4))) return rc;
-    d_pconf = (int32_t*)e->mk_pconf.p;
-    mb.m = m, mb.P = P, mb.off = d_off, mb.keys = d_keys, mb.number = d_number;
-    mb.pnum = (int32_t*)e->mk_pair.p, mb.uniq = (uint8_t*)e->mk_pair.p + (size_t)std::max(P, 1) * 4;
+    if ((rc = grow(e, &e->mk_pconf, (size_t)std::max(P, 1) * n * NP * 4))) return rc;
   }
-  if (triple_id) EHIP(e, up(d_tr, triple_id, (size_t)m * 4));
-  if (deps_in_values_end) EHIP(e, up(d_dend, deps_in_values_end, (size_t)m * 4));
-  EHIP(e, up(d_din, deps_in, (size_t)m * n * 4));
-  EHIP(e, up(d_set, is_set, (size_t)m));
-  EHIP(e, up(d_tgt, target_mask, (size_t)m));
-  EHIP(e, hipMemsetAsync(d_ok, 0, mp * 4, e->stream));  // ok, resend, nack, commit are contiguous
-  EHIP(e, hipMemsetAsync(d_nb, 0xFF, mp * 4, e->stream));
-  HpBatch hb;
-  memset(&hb, 0, sizeof(hb));
-  hb.m = m, hb.leader = d_leader, hb.number = d_number, hb.b_ord = d_bo, hb.b_rep = d_br, hb.key = d_key, hb.is_set = d_set;
-  if (key_off) hb.key = nullptr, hb.key_off = d_off, hb.keys = d_keys, hb.uniq = mb.uniq, hb.P = P;
-  hb.triple = triple_id ? d_tr : nullptr, hb.deps_in = d_din, hb.dend_in = deps_in_values_end ? d_dend : nullptr;
-  hb.target = d_tgt, hb.ok_bits = d_ok, hb.resend_bits = d_resend, hb.nack_bits = d_nack, hb.commit_bits = d_com;
-  hb.reply_deps = d_rd, hb.reply_end = d_re, hb.reply_triple = d_rt;
-  hb.act = d_act, hb.contrib = d_contrib, hb.nackflag = d_flag, hb.kv = (uint2*)e->kv.p;
-  hb.conf = (int32_t*)e->conf.p, hb.tick = (int32_t*)e->tick.p;
-  if (++e->cl_run == 0) {  // stamp space exhausted: start over
-    EHIP(e, hipMemsetAsync(e->st.cl_stamp, 0, (size_t)n * e->st.num_instances * 4, e->stream));
-    e->cl_run = 1;
-  }
-  hb.run_id = e->cl_run;
-  const dim3 gm((m + 255) / 256), gmn((unsigned)(((long long)m * n + 255) / 256)), blk(256);
-  hipLaunchKernelGGL(k_hp_validate, gm, blk, 0, e->stream, e->st, hb);
-  if (key_off) hipLaunchKernelGGL(k_mk_pairs, gm, blk, 0, e->stream, mb);
-  hipLaunchKernelGGL(k_hp_gate, gmn, blk, 0, e->stream, e->st, hb);
-  // the conflict scan of what each replica processes, in array order: K5's sort / segments / scan
-  EpxBatch sb;
-  memset(&sb, 0, sizeof(sb));
-  sb.m = P, sb.number = key_off ? mb.pnum : d_number, sb.kv = hb.kv;
-  const uint32_t* key_totals = nullptr;
-  int key_buckets = 0;
-  if (P > 0) {  // (key lists that are all empty: nothing to scan, nothing for the index to learn)
-    sb.kv_sorted = sort_by_key(e, P, hb.kv, (uint2*)e->kv2.p, nullptr, &rc, &key_totals, &key_buckets);
-    if (rc) return rc;
-  }
-  sb.tick = (int32_t*)e->tick.p, sb.seg = (int32_t*)e->seg.p, sb.conf = key_off ? d_pconf : (int32_t*)e->conf.p;
-  if (P > 0) launch_segments(e, sb, key_totals, key_buckets);
-  // the largestBallot every Nack carries: prefix max per replica over the ballots it took in (as for Prepare / Accept)
-  ClBatch cb;
-  memset(&cb, 0, sizeof(cb));
-  cb.m = m, cb.contrib = d_contrib, cb.nackflag = d_flag, cb.tilemax = d_tm, cb.nack_ballot = d_nb;
-  hipLaunchKernelGGL(k_cl_tilemax, dim3(tiles, n), blk, 0, e->stream, cb, tiles);
-  hipLaunchKernelGGL(k_cl_tilescan, dim3(n), blk, 0, e->stream, e->st, cb, tiles);
-  hipLaunchKernelGGL(k_cl_nacks, dim3(tiles, n), blk, 0, e->stream, cb, tiles);
-  MkMerge mm;
-  memset(&mm, 0, sizeof(mm));
-  mm.m = m, mm.off = d_off, mm.uniq = mb.uniq, mm.pconf = d_pconf, mm.conf = (int32_t*)e->conf.p, mm.act = d_act;
-  switch (n) {
-    case 3: launch_hp<3>(e, sb, hb, key_off ? &mm : nullptr, P > 0); break;
-    case 5: launch_hp<5>(e, sb, hb, key_off ? &mm : nullptr, P > 0); break;
-    default: launch_hp<7>(e, sb, hb, key_off ? &mm : nullptr, P > 0); break;
-  }
-  const long long tot = (long long)e->st.num_keys * n * n;
-  if (P > 0) hipLaunchKernelGGL(k_hp_commit, dim3((unsigned)((tot + 255) / 256)), blk, 0, e->stream, e->st, hb);
-  hipError_t le = hipGetLastError();
-  if (le != hipSuccess) {
-    e->last_hip = (int)le;
-    return FPX_EHIP;
-  }
-  auto down = [&](void* dst, const void* src, size_t sz) { return hipMemcpyAsync(dst, src, sz, hipMemcpyDeviceToHost, e->stream); };
-  if (ok_bits) EHIP(e, down(ok_bits, d_ok, (size_t)m));
-  if (resend_bits) EHIP(e, down(resend_bits, d_resend, (size_t)m));
-  if (nack_bits) EHIP(e, down(nack_bits, d_nack, (size_t)m));
-  if (commit_bits) EHIP(e, down(commit_bits, d_com, (size_t)m));
-  if (nack_ballot) EHIP(e, down(nack_ballot, d_nb, (size_t)m * 4));
-  if (reply_deps) EHIP(e, down(reply_deps, d_rd, (size_t)m * n * n * 4));
-  if (reply_values_end) EHIP(e, down(reply_values_end, d_re, (size_t)m * n * 4));
-  if (reply_triple) EHIP(e, down(reply_triple, d_rt, (size_t)m * n * 4));
-  return fpx_epx_sync(e);
+  const int32_t *d_leader, *d_number, *d_bo, *d_br, *d_key, *d_tr, *d_dend, *d_din, *d_off, *d_keys;
+  const uint8_t *d_set, *d_tgt;
+  uint8_t *d_ok, *d_resend, *d_nack, *d_com, *d_act, *d_flag;
+  int32_t *d_nb, *d_rd, *d_re, *d_rt, *d_contrib, *d_tm;
+  auto launch = [&]() -> int {
+    int32_t* d_pconf = nullptr;
+    MkBatch mb;
+    memset(&mb, 0, sizeof(mb));
+    if (key_off) {
+      d_pconf = (int32_t*)e->mk_pconf.p;
+      mb.m = m, mb.P = P, mb.off = d_off, mb.keys = d_keys, mb.number = d_number;
+      mb.pnum = (int32_t*)e->mk_pair.p, mb.uniq = (uint8_t*)e->mk_pair.p + (size_t)std::max(P, 1) * 4;
+    }
+    HpBatch hb;
+    memset(&hb, 0, sizeof(hb));
+    hb.m = m, hb.leader = d_leader, hb.number = d_number, hb.b_ord = d_bo, hb.b_rep = d_br, hb.key = d_key, hb.is_set = d_set;
+    if (key_off) hb.key = nullptr, hb.key_off = d_off, hb.keys = d_keys, hb.uniq = mb.uniq, hb.P = P;
+    hb.triple = triple_id ? d_tr : nullptr, hb.deps_in = d_din, hb.dend_in = deps_in_values_end ? d_dend : nullptr;
+    hb.target = d_tgt, hb.ok_bits = d_ok, hb.resend_bits = d_resend, hb.nack_bits = d_nack, hb.commit_bits = d_com;
+    hb.reply_deps = d_rd, hb.reply_end = d_re, hb.reply_triple = d_rt;
+    hb.act = d_act, hb.contrib = d_contrib, hb.nackflag = d_flag, hb.kv = (uint2*)e->kv.p;
+    hb.conf = (int32_t*)e->conf.p, hb.tick = (int32_t*)e->tick.p;
+    int rc2;
+    if ((rc2 = next_run_id(e, &hb.run_id))) return rc2;
+    const dim3 gm((m + 255) / 256), gmn((unsigned)(((long long)m * n + 255) / 256)), blk(256);
+    hipLaunchKernelGGL(k_hp_validate, gm, blk, 0, e->stream, e->st, hb);
+    if (key_off) hipLaunchKernelGGL(k_mk_pairs, gm, blk, 0, e->stream, mb);
+    hipLaunchKernelGGL(k_hp_gate, gmn, blk, 0, e->stream, e->st, hb);
+    // the conflict scan of what each replica processes, in array order: K5's sort / segments / scan
+    EpxBatch sb;
+    memset(&sb, 0, sizeof(sb));
+    sb.m = P, sb.number = key_off ? mb.pnum : d_number, sb.kv = hb.kv;
+    const uint32_t* key_totals = nullptr;
+    int key_buckets = 0;
+    if (P > 0) {  // (key lists that are all empty: nothing to scan, nothing for the index to learn)
+      sb.kv_sorted = sort_by_key(e, P, hb.kv, (uint2*)e->kv2.p, nullptr, &rc2, &key_totals, &key_buckets);
+      if (rc2) return rc2;
+    }
+    sb.tick = (int32_t*)e->tick.p, sb.seg = (int32_t*)e->seg.p, sb.conf = key_off ? d_pconf : (int32_t*)e->conf.p;
+    if (P > 0) launch_segments(e, sb, key_totals, key_buckets);
+    // the largestBallot every Nack carries: prefix max per replica over the ballots it took in (as for Prepare / Accept)
+    ClBatch cb;
+    memset(&cb, 0, sizeof(cb));
+    cb.m = m, cb.contrib = d_contrib, cb.nackflag = d_flag, cb.tilemax = d_tm, cb.nack_ballot = d_nb;
+    hipLaunchKernelGGL(k_cl_tilemax, dim3(tiles, n), blk, 0, e->stream, cb, tiles);
+    hipLaunchKernelGGL(k_cl_tilescan, dim3(n), blk, 0, e->stream, e->st, cb, tiles);
+    hipLaunchKernelGGL(k_cl_nacks, dim3(tiles, n), blk, 0, e->stream, cb, tiles);
+    MkMerge mm;
+    memset(&mm, 0, sizeof(mm));
+    mm.m = m, mm.off = key_off ? d_off : nullptr, mm.uniq = mb.uniq, mm.pconf = d_pconf, mm.conf = (int32_t*)e->conf.p, mm.act = d_act;
+    by_n(n, [&](auto N) { launch_hp<N>(e, sb, hb, key_off ? &mm : nullptr, P > 0); });
+    const long long tot = (long long)e->st.num_keys * n * n;
+    if (P > 0) hipLaunchKernelGGL(k_hp_commit, dim3((unsigned)((tot + 255) / 256)), blk, 0, e->stream, e->st, hb);
+    return FPX_OK;
+  };
+  // ok, resend, nack and commit start at 0 (one memset), nack_ballot at -1
+  return host_call(e, {in(d_leader, leader, m), in(d_number, number, m), in(d_bo, ballot_ordering, m), in(d_br, ballot_replica, m),
+                       in(d_key, key, m), in(d_tr, triple_id, m), in(d_dend, deps_in_values_end, m), in(d_din, deps_in, mn),
+                       in(d_set, is_set, m), in(d_tgt, target_mask, m), in(d_off, key_off, key_off ? m + 1 : 0),
+                       in(d_keys, keys, key_off ? P : 0), out(d_ok, ok_bits, m, 0), out(d_resend, resend_bits, m, 0), out(d_nack, nack_bits, m, 0),
+                       out(d_com, commit_bits, m, 0), out(d_nb, nack_ballot, m, 0xFF), out(d_rd, reply_deps, mn * n),
+                       out(d_re, reply_values_end, mn), out(d_rt, reply_triple, mn), scratch(d_act, mn), scratch(d_flag, mn),
+                       scratch(d_contrib, mn), scratch(d_tm, (size_t)n * tiles)},
+                   launch);
 }
 
 int32_t fpx_epx_read_cmdlog_deps(fpx_epx* e, int32_t replica, int32_t leader, int32_t number, int32_t* deps,
