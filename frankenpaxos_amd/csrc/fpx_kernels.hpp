@@ -46,6 +46,9 @@
 #ifndef FPX_EARLY_THR
 #define FPX_EARLY_THR 1  // the first step's ballot row is requested with the chunk's other loads (fpx_phase2_body.inc)
 #endif
+#ifndef FPX_STEADY_WALK
+#define FPX_STEADY_WALK 1  // G = 64, dense, PER_SLOT: a chunk whose rows all make the same choice walks them as scalars
+#endif                     // (fpx_phase2_body.inc)
 #ifndef FPX_NT
 #define FPX_NT 1  // vote rows are written once and not re-read soon: nontemporal stores
 #endif

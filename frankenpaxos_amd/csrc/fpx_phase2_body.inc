@@ -95,6 +95,20 @@ __global__ void __launch_bounds__(256)
   int pk_pr[8] = {-1, -1, -1, -1, -1, -1, -1, -1}, pk_mv[8] = {-1, -1, -1, -1, -1, -1, -1, -1};
   bool pk_used = false;
 
+  // the steady walk (below) of the dense G = 64 kernels without lazy promises: may a chunk take it at all?  One acceptor
+  // group, and (fused) the whole group's votes -- what every row of a steady chunk collects -- make a write quorum
+  constexpr bool STEADY = FPX_STEADY_WALK && G == 64 && MODE == 0 && PS == 1;
+  bool steady_ok = false;
+  if constexpr (STEADY) {
+    if (one_group) {
+      uint64_t x[4];
+      assemble_bits<G>(own, lane, g.base, x);
+#pragma unroll
+      for (int w = 0; w < 4; ++w) x[w] &= g.member[w];
+      steady_ok = !FUSED || is_write_quorum(g, x);
+    }
+  }
+
   int lzr[4] = {-1, -1, -1, -1}, lzf[4] = {0, 0, 0, 0};
   if (LAZY && one_group) {
 #pragma unroll
@@ -180,6 +194,9 @@ __global__ void __launch_bounds__(256)
     // message src of the chunk as seen from this lane (at G = 1 a lane walks its own message: nothing to fetch)
     auto pick = [&](int v, int src) -> int {
       if constexpr (G == 1) return v;
+      // (at G = 64 src is the same in every lane: a scalar, no LDS permute.  Not in the acceptor model, whose kernels
+      // then spilled SGPRs to scratch)
+      else if constexpr (G == 64 && PERSLOT) return __builtin_amdgcn_readlane(v, src);
       else return __shfl(v, src);
     };
     // the summary of message src's row (at G = 64 src is the same in every lane: a scalar, and a scalar branch below)
@@ -426,6 +443,49 @@ __global__ void __launch_bounds__(256)
     // body, where -- vmcnt counts stores on gfx9 -- it makes every step wait for the rows the step before it wrote.
     // In the FPX_BALLOT_ACCEPTOR model the walk then has no vector-memory wait at all: rows stream out back to back.
     __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0), expcnt and lgkmcnt untouched
+    // The steady walk.  A chunk every valid message of which is delivered (a new (slot, round) with a free way) to a
+    // uniform row whose round it is not below makes the same choice in every row: the whole group votes (a quorum, checked
+    // once above), nobody Nacks, the slot is chosen.  Its rows then cost only their stores, taken from the lanes as
+    // scalars -- the general walk's decision, bitmap and reductions (~650 instructions per row) are what paced the
+    // headline once the uniform rows were no longer read (profiles/r08_steady_walk.md).  What it writes is what the
+    // general walk writes for such a chunk, store for store: both rows, the ballot row and its summary where the round
+    // moves, the whole-group maxima, and (below the walk) the chosen records.  A slot met twice in the chunk sees the
+    // summary gathered with the chunk on both paths.
+    bool steady = false;
+    if constexpr (STEADY)
+      steady = steady_ok && __all(!mv || (mydeliver && myslot >= 0 && mysum != SUM_MIXED && myround >= mysum));
+    if (STEADY && steady) {
+      const int nv = b.n - v0 < CH ? b.n - v0 : CH;  // the valid messages are the first nv lanes
+      for (int t = 0; t < nv; ++t) {
+        const int s = __builtin_amdgcn_readlane(myslot, t);
+        const int rnd = __builtin_amdgcn_readlane(myround, t);
+        const int val = __builtin_amdgcn_readlane(myvalue, t);
+        const int bs = __builtin_amdgcn_readlane(mysum, t);
+        if (own) {
+          const int4v rr = {rnd, rnd, rnd, rnd};
+          const int4v vv = {val, val, val, val};
+          const size_t vrow = (size_t)s * (size_t)g.VS + (size_t)r0;
+          row_store(rr, reinterpret_cast<int4v*>(st.vote_round + vrow));
+          row_store(vv, reinterpret_cast<int4v*>(st.vote_value + vrow));
+          if (rnd != bs) row_store(rr, reinterpret_cast<int4v*>(st.ballot + (size_t)s * (size_t)g.RS + (size_t)r0));
+        }
+        if (rnd != bs && lane == 0) st.ballot_sum[s] = rnd;
+        w_slot = s > w_slot ? s : w_slot;
+        w_round = rnd > w_round ? rnd : w_round;
+      }
+      if constexpr (FUSED) {
+        if (mv) wo->chosen[lane] = 1, wo->nack_round[lane] = -1;
+      } else {
+        uint64_t vb[4];
+        assemble_bits<G>(own, lane, g.base, vb);
+        if (mv) {
+#pragma unroll
+          for (int w = 0; w < 4; ++w) wo->votes[lane][w] = vb[w], wo->nacks[lane][w] = 0ull;
+          wo->nack_round[lane] = -1;
+        }
+      }
+    }
+    if (!STEADY || !steady) {  // (without the steady walk: no branch at all, the code of the kernels before it)
     if constexpr (!EARLY) thr_cur = load_thr(0, s_cur, grp_cur, phys_cur);
     for (int t = 0; t < G * CH / 64; ++t) {
 #if FPX_PREFETCH
@@ -653,6 +713,7 @@ __global__ void __launch_bounds__(256)
       if (t + 1 < G) thr_cur = load_thr(t + 1, s_cur, grp_cur, phys_cur);
 #endif
     }
+    }  // (the general walk)
     }  // (the walk, one row per step)
 
     // ---- outputs of the 64 messages leave as coalesced lines ------------------------------------
