@@ -1,8 +1,13 @@
 #!/usr/bin/env python3
 """bench.py -- committed log slots / second of the fused Phase-2 step on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run does what the headline figure needs and no more: set up, warm up, time the K steps, check them, write the
+outputs (--dump-outputs) and print the line.  `--full` adds what the line carried beside the headline before: the CPU
+baselines, the `configs` block of BASELINE.json's other configs (N = 1), the replica-axis row and the RCCL probe (N > 1)
+and the roofline's measured traffic from profiles/traffic.json.  None of it runs before the timed steps.
 
 Workload (BASELINE.json metric; SURVEY.md section 8d "steady"): a "step" is one fused pass
 (ProxyLeader.handlePhase2a -> Acceptor.handlePhase2a x 256 -> ProxyLeader.handlePhase2b) over one
@@ -456,13 +461,16 @@ def main():
     ap.add_argument("--shard", choices=["group", "replica"], default="group")
     ap.add_argument("--validate", action="store_true",
                     help="keep the run-contract validation kernel in the timed region")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="headline: also run what the headline figure does not need -- the CPU baselines, the `configs` "
+                         "block (N = 1), the replica-axis row and the RCCL probe (N > 1), the traffic of profiles/traffic.json")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="leave the CPU baselines out of a --full or a --config line")
     ap.add_argument("--config", choices=["headline", "2", "3", "4", "5", "thrifty", "thrifty_random", "acceptor_model", "host_path", "adversarial", "4_execute"], default="headline",
                     help="headline = BASELINE.json's metric grid (2^20 slots x 256 acceptors); 2..5 = the other "
                          "BASELINE.json configs as bench lines of the same schema (bench_configs.py)")
     ap.add_argument("--configs-block-steps", type=int, default=20,
-                    help="N = 1 headline run: steps of each of BASELINE.json's other configs (2..5) timed after the "
-                         "headline and reported in the line's `configs` block (0 = leave the block out)")
+                    help="N = 1 headline run with --full: steps of each of BASELINE.json's other configs (2..5) timed after "
+                         "the headline and reported in the line's `configs` block (0 = leave the block out)")
     ap.add_argument("--replica-row-deadline", type=int, default=120,
                     help="seconds the extra replica-axis row may take before the line is printed without it")
     ap.add_argument("--preflight", action="store_true",
@@ -474,7 +482,7 @@ def main():
     ap.add_argument("--test-hooks", action="store_true",
                     help="honour the FPX_BENCH_* test hooks of tests/test_bench_distributed.py (refused without this flag)")
     ap.add_argument("--replica-row-steps", type=int, default=5,
-                    help="N > 1, --shard group: steps of the extra replica-axis row (0 = skip it)")
+                    help="N > 1, --shard group, --full: steps of the extra replica-axis row (0 = skip it)")
     ap.add_argument("--dump-outputs", metavar="DIR",
                     help="headline only: after the timed steps, write what the last timed step returned to its caller (the "
                          "Chosen records: chosen flag, round, value per slot; rank 0's slots at N > 1) as DIR/<name>.npy")
@@ -667,11 +675,11 @@ def main():
         all_reduce(t, dist.ReduceOp.SUM)
         committed = int(t.item())
 
-    # SURVEY.md 8e asks for both sharding rows: with N > 1 the default (group-sharded) run appends the
+    # SURVEY.md 8e asks for both sharding rows: with N > 1 a --full (group-sharded) run appends the
     # replica-axis row -- one 2^20 x 256 grid split over the N GPUs' acceptor columns, RCCL reduce-scatter of
     # the vote bitmaps behind the C ABI, collective time broken out
     replica_row, hung, replica_row_tried = None, False, False
-    if world > 1 and not replica_shard and args.replica_row_steps > 0:
+    if args.full and world > 1 and not replica_shard and args.replica_row_steps > 0:
         replica_row_tried = True
         # the headline line must not be lost to the extra row: an exception becomes an "error" field, and a
         # collective that never returns (RCCL between real GPUs runs for the first time in the driver's own
@@ -684,11 +692,11 @@ def main():
         if rank != 0 and not hung:
             replica_row = None
 
-    # N > 1: does RCCL carry bytes between these GPUs at all?  Asked on its own (a communicator behind the C ABI on a
+    # N > 1, --full: does RCCL carry bytes between these GPUs at all?  Asked on its own (a communicator behind the C ABI on a
     # small context + one all-gather of Chosen records), so that `rccl` in the line does not depend on the extra
     # row having finished; deadline-guarded like the row.
     rccl_info = None
-    if world > 1 and (backend == "nccl" or hook("FPX_BENCH_FPX_COMM") == "1") and not hung:
+    if args.full and world > 1 and (backend == "nccl" or hook("FPX_BENCH_FPX_COMM") == "1") and not hung:
         def rccl_probe():
             pctx = fa.Context(fa.make_config(num_slots=4096, num_replicas=4, f=1, device=local_rank))
             pctx.set_stream(torch.cuda.current_stream().cuda_stream)
@@ -706,9 +714,9 @@ def main():
         rccl_info, hung2 = run_with_deadline(rccl_probe, 90, dev)
         hung = hung or hung2
 
-    # N = 1: BASELINE.json's other configs, a few steps each, so that the driver's own run times them too
+    # N = 1, --full: BASELINE.json's other configs, a few steps each, timed in the same run as the headline
     configs_block = None
-    if world == 1 and args.configs_block_steps > 0 and not replica_shard:
+    if args.full and world == 1 and args.configs_block_steps > 0 and not replica_shard:
         import types
         import bench_configs
         ctx.close()
@@ -760,7 +768,7 @@ def main():
         achieved = bps * slots_per_launch / avg_kernel_s / 1e9 if launches else None
         traffic, traffic_round = None, None
         tfile = os.path.join(ROOT, "profiles", "traffic.json")
-        if os.path.exists(tfile):
+        if args.full and os.path.exists(tfile):
             try:
                 te = json.load(open(tfile)).get(args.ballot) or {}
                 traffic, traffic_round = te.get("bytes"), te.get("round")
@@ -844,7 +852,7 @@ def main():
             }
         if replica_row is not None:
             line["replica_axis"] = replica_row
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(ballot_mode, light=world > 1)
         print(json.dumps(round_floats(line)), flush=True)
     if hung:  # a collective of the extra row never returned: no barrier, no teardown that could wait for it

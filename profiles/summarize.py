@@ -61,7 +61,7 @@ with open(os.path.join(out, tag + "_pmc_summary.md"), "w") as f:
     f.write("# %s rocprofv3 summary\n\n" % tag)
     f.write("Collected by `bash profiles/collect.sh %s` on the MI355X box, summarised by "
             "`python profiles/summarize.py %s`.\n\n" % (tag, tag))
-    f.write("## Kernel trace (`rocprofv3 --kernel-trace --stats -- python bench.py --no-cpu-baseline`)\n\n")
+    f.write("## Kernel trace (`rocprofv3 --kernel-trace --stats -- python bench.py --full --no-cpu-baseline`)\n\n")
     f.write("`%s`: %s calls, average **%.1f us** (min %.1f, max %.1f). HIP-event average measured live by "
             "bench.py in the same run: **%.1f us** (%d timed launches).\nFull table: `%s_kernel_stats.csv`.\n\n"
             % (k2["Name"].split("(")[0], k2["Calls"], float(k2["AverageNs"]) / 1e3, float(k2["MinNs"]) / 1e3,

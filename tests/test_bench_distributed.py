@@ -45,7 +45,7 @@ def test_bench_spawns_its_own_ranks():
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(k, None)
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--test-hooks", "--gpus", "2", "--steps", "2",
-                          "--warmup", "1", "--replica-row-steps", "2"],
+                          "--warmup", "1", "--full", "--replica-row-steps", "2"],
                          capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -60,7 +60,7 @@ def test_bench_spawns_its_own_ranks():
 
 
 def test_group_sharded_bench_two_ranks():
-    d = _run(["--replica-row-steps", "0"])
+    d = _run(["--full", "--replica-row-steps", "0"])
     assert "replica_axis" not in d
     assert d["n_gpus"] == 2 and d["scaling"] == "weak" and d["steps"] == 3
     # every rank commits its own 2^20 slots per step: whole-job value counts both
@@ -81,8 +81,8 @@ def test_replica_sharded_bench_two_ranks():
 
 
 def test_single_gpu_bench_contract():
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1",
-                          "--no-cpu-baseline"], capture_output=True, text=True, timeout=600, cwd=ROOT)
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1"],
+                         capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-3000:]
     d = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][0])
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better",
@@ -91,6 +91,21 @@ def test_single_gpu_bench_contract():
     assert d["n_gpus"] == 1 and d["vs_baseline"] is None and d["dtype"] == "int32"
     assert d["roofline"]["bound"] == "hbm" and d["roofline"]["peak"] == 8000.0
     assert "workload" in d["config"]
+    # a plain run carries the headline alone: the rest of the line is --full's
+    assert "configs" not in d and "cpu_baseline" not in d and d["roofline"]["traffic"] is None
+
+
+def test_single_gpu_full_line():
+    """--full at N = 1: the headline, then the `configs` block of the other configs and the CPU baselines, in one line"""
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--full",
+                          "--configs-block-steps", "2"], capture_output=True, text=True, timeout=900, cwd=ROOT)
+    assert out.returncode == 0, out.stderr[-3000:]
+    d = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][0])
+    assert d["n_gpus"] == 1 and d["steps"] == 3 and d["value"] > 0 and d["roofline"]["launches_timed"] == 3
+    for c in ("1", "2", "3", "4", "5"):
+        assert "error" not in d["configs"][c] and d["configs"][c]["verified"], (c, d["configs"][c])
+    b = d["cpu_baseline"]
+    assert b["kind"] == "port" and b["value"] > 0 and b["all_cores_value"] > 0 and b["fifo_pump_value"] > 0
 
 
 @pytest.mark.parametrize("config", ["2", "3", "4", "5"])
@@ -110,7 +125,7 @@ def test_headline_line_survives_an_extra_row_that_never_finishes():
     """the replica-axis row runs RCCL between real GPUs for the first time in the driver's own multi-GPU job: if a
     collective in it never returns, the headline line is still printed (with the row marked) and every rank leaves
     with status 0.  A deadline of 0 s makes the row 'never finish' here."""
-    d = _run(["--replica-row-steps", "2", "--replica-row-deadline", "0"])
+    d = _run(["--full", "--replica-row-steps", "2", "--replica-row-deadline", "0"])
     assert d["n_gpus"] == 2 and d["value"] > 0
     assert "no answer" in d["replica_axis"]["error"]
 
@@ -132,7 +147,7 @@ def test_bench_spawns_four_ranks():
         env.pop(k, None)
     N = SHARED_RANKS
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--test-hooks", "--gpus", str(N), "--steps", "2", "--warmup", "1",
-                          "--replica-row-steps", "0"], capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
+                          "--full", "--replica-row-steps", "0"], capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, out.stdout
@@ -159,7 +174,7 @@ def test_four_rank_lines_through_the_library_communicator(shard):
                FPX_BENCH_SLOTS_LOG2="16")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(k, None)
-    extra = ["--replica-row-steps", "2"] if shard == "group" else ["--shard", "replica"]
+    extra = ["--full", "--replica-row-steps", "2"] if shard == "group" else ["--shard", "replica"]
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--test-hooks", "--gpus", str(N), "--steps", "2", "--warmup", "1"] + extra,
                          capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
