@@ -283,17 +283,16 @@ size_t lds_bytes(const fpx_ctx* ctx, bool fused, bool targets) {
   return tab + 4 * (fused ? sizeof(WaveOut<true>) : sizeof(WaveOut<false>)) + (targets ? 4 * (256 + 16) * sizeof(uint64_t) : 0);
 }
 
-// messages per wavefront at G = 64: FPX_CHUNK for batches that fill the chip anyway, fewer (down to 4) for small
+// messages per wavefront at G = 64: CHUNK for batches that fill the chip anyway, fewer (down to 4) for small
 // ones -- a wave walks its chunk one row at a time, so a 20 k-message epoch in 32-message chunks is 670 waves
 // walking 32 dependent steps each on a machine with room for 6000
 int chunk_for(const fpx_ctx* ctx, int n) {
   if (ctx->lanes_per_slot != 64) return 64;
-  // (FPX_MIN_CHUNK: the sweep of profiles/r06_raw/adversarial_chunk_sweep.txt -- 8 / 4 / 2 / 1 messages per wavefront at ~21 500
+  // (the floor: the sweep of profiles/r06_raw/adversarial_chunk_sweep.txt -- 8 / 4 / 2 / 1 messages per wavefront at ~21 500
   // messages per launch: 6.12 / 6.50 / 6.55 / 6.53e8 proposals/s; 4 stays)
-  static const int min_chunk = [] { const char* e = getenv("FPX_MIN_CHUNK"); return e ? std::max(1, atoi(e)) : 4; }();
   const long long want_waves = (long long)ctx->num_cus * 16;
-  int ch = FPX_CHUNK;
-  while (ch > min_chunk && (long long)(n + ch - 1) / ch < want_waves) ch >>= 1;
+  int ch = CHUNK;
+  while (ch > 4 && (long long)(n + ch - 1) / ch < want_waves) ch >>= 1;
   return ch;
 }
 
@@ -317,7 +316,7 @@ size_t phase2_lds(fpx_ctx* ctx, Batch& b, bool fused, bool targets, bool accepto
   // every array they move as 16 bytes is aligned for it
   auto al = [](const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; };
   if (ctx->g.lg_rows && al(b.slot, 16) && al(b.round, 16) && al(b.value, 16) && al(b.chosen, 4) && al(b.chosen_round, 16) &&
-      al(b.chosen_value, 16) && al(b.nack_round, 16) && !getenv("FPX_NO_QUADS")) {
+      al(b.chosen_value, 16) && al(b.nack_round, 16)) {
     lds = (lds + 15) & ~(size_t)15;
     b.sc_lds = (int32_t)lds;
     lds += 4 * 3 * 4 * 64 * sizeof(int32_t);
@@ -499,7 +498,7 @@ int enqueue_phase2(fpx_ctx* ctx, Batch& b, bool fused) {
   b.index_base = ctx->index_base;
   // at most two chunks per wavefront of one workgroup: that workgroup finalises itself (k_phase2, `solo`); the parity
   // of the partial-maxima buffers is not consumed
-  b.solo = ((b.n + b.chunk - 1) / b.chunk <= 8 && !getenv("FPX_NO_SOLO")) ? 1 : 0;
+  b.solo = (b.n + b.chunk - 1) / b.chunk <= 8 ? 1 : 0;
   if (b.solo) grid = 1;
   // Target masks on 256-cell rows of one group: thrifty delivery to RUNS of neighbouring acceptors (what GpuProxyLeader
   // sends by default; any f + 1 will do: ProxyLeader.scala:190-191) takes two rows per wavefront step.  Two launches: the
@@ -720,7 +719,6 @@ bool place_chunks(fpx_ctx* ctx, int narr, size_t array_bytes, int q4, char** sla
   if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) return false;
   // spare chunks give the search somewhere to go when the pool's mix is lopsided; they are released afterwards
   int spare = std::min(need / 2 + 4, 24);
-  if (const char* e = getenv("FPX_PLACEMENT_SPARE")) spare = std::max(0, std::min(64, atoi(e)));
   while (spare > 0 && free_b < (size_t)(need + spare) * PLACE_CHUNK + ((size_t)8 << 30)) --spare;
   if (free_b < (size_t)need * PLACE_CHUNK + ((size_t)4 << 30)) return false;
   int pool = need + spare;
@@ -859,10 +857,9 @@ bool place_chunks(fpx_ctx* ctx, int narr, size_t array_bytes, int q4, char** sla
   }
   freec.insert(freec.end(), aside.begin(), aside.end());
   // the ballots' chunk: the first candidate (spread over what is left, as above) within 1 % of the fastest triple stream
-  // seen, else the best of 12 (FPX_PLACEMENT_A_TRIES).  The read stream's region matters as much as the pair's: with three
-  // candidates 3 of 25 windows ended 10 % slow, with eight none (profiles/r05_placement.md)
-  int a_tries = 12;
-  if (const char* e = getenv("FPX_PLACEMENT_A_TRIES")) a_tries = std::max(1, atoi(e));
+  // seen, else the best of 12.  The read stream's region matters as much as the pair's: with three candidates 3 of 25
+  // windows ended 10 % slow, with eight none (profiles/r05_placement.md)
+  const int a_tries = 12;
   std::vector<float> win_ms(per, 0.f);
   for (int w = 0; w < per && !bad; ++w) {
     if (narr < 3) {
@@ -1264,12 +1261,11 @@ int host_wait(fpx_ctx* ctx, int ticket) {
 }
 
 // the synchronous call on page-locked arrays = submit + wait; *used = false: not every array is mapped host memory (or
-// the knob is off, or calls are in flight) -- the caller takes the copy-engine path
+// calls are in flight) -- the caller takes the copy-engine path
 int host_fused_staged(fpx_ctx* ctx, int n, const int32_t* slot, const int32_t* round, const int32_t* value_id,
                       const uint64_t* target_mask, uint8_t* chosen, int32_t* chosen_round, int32_t* chosen_value,
                       int32_t* nack_round, bool* used) {
   *used = false;
-  if (getenv("FPX_HOST_NO_STAGE")) return FPX_OK;
   int ticket = -1;
   int rc = host_submit(ctx, n, slot, round, value_id, target_mask, chosen, chosen_round, chosen_value, nack_round, &ticket);
   if (rc == FPX_EINVAL || rc == FPX_ECAPACITY) return FPX_OK;  // not page-locked / ring busy: the other path
@@ -1356,7 +1352,7 @@ int32_t fpx_create(const fpx_config* cfg, fpx_ctx** out) {
   }
   hipDeviceProp_t prop;
   if (hipGetDeviceProperties(&prop, cfg->device) == hipSuccess) ctx->num_cus = prop.multiProcessorCount;
-  // 32 workgroups per CU: at 2^20 messages every wavefront gets exactly one FPX_CHUNK-message chunk and
+  // 32 workgroups per CU: at 2^20 messages every wavefront gets exactly one CHUNK-message chunk and
   // the hardware dispatcher load-balances them (measured r01: +10 % over a 2048-workgroup persistent
   // grid, a further +8 % going from 64- to 32-message chunks)
   int G = 1;
@@ -1368,7 +1364,6 @@ int32_t fpx_create(const fpx_config* cfg, fpx_ctx** out) {
   // LDS (23.5 KB with the column-quad staging) lets be resident at once: 3 - 4 % faster than four on BASELINE.json configs[4],
   // 5 - 15 % on configs[2]; seven and more (a second round of workgroups) are 8 % slower (profiles/r05_cfg5.md)
   ctx->max_grid = ctx->num_cus * (G <= 4 ? 6 : 32);
-  if (const char* e = getenv("FPX_MAX_GRID")) ctx->max_grid = std::max(1, atoi(e));  // tuning aid
   ctx->vec = true;  // rows are padded to a multiple of 4 cells (Geom::RS)
   // big tables: fewer resident blocks so that the partial table stays small
   const int ntab = ctx->g.ngroups * ctx->g.R;
@@ -1387,24 +1382,20 @@ int32_t fpx_create(const fpx_config* cfg, fpx_ctx** out) {
   if ((rc = dalloc(ctx, &st.promised, nsc))) return fail(rc);
   if ((rc = dalloc(ctx, &st.max_voted, nsc))) return fail(rc);
   {
-    // the 2-3 cell arrays are streamed in lockstep (row s of each at the same time): one slab, the
-    // arrays staggered by FPX_STAGGER bytes so that their rows do not all start in the same DRAM
-    // channel / bank (tuning aid; measured in profiles/r01_stagger.txt)
-    size_t stagger = 0;
-    if (const char* e = getenv("FPX_STAGGER")) stagger = (size_t)atoll(e) & ~(size_t)15;
+    // the 2-3 cell arrays are streamed in lockstep (row s of each at the same time): one slab (offsets of 1 KiB to 8 MiB
+    // between the arrays measured no gain, profiles/r01_stagger_box{A,B}.txt)
     const int narr = g.per_slot ? 3 : 2;
-    size_t stride = ncell * 4 + stagger;
+    size_t stride = ncell * 4;
     // Placement: the very same kernel streams a slab at one of two speeds ~7 % apart depending on where the
     // allocation landed (deterministic per allocation, profiles/r02_placement.txt).  A big context therefore
-    // allocates up to FPX_PLACEMENT_TRIES slabs (default 4, while free HBM allows), times the hot access pattern
-    // on each (k_probe, 3 x 0.5 ms) and keeps the fastest; the others are freed before anything else is allocated.
+    // allocates up to 4 slabs (while free HBM allows), times the hot access pattern on each (k_probe, 3 x 0.5 ms)
+    // and keeps the fastest; the others are freed before anything else is allocated.
     int tries = stride * narr >= ((size_t)2 << 30) && g.RS >= 64 ? 4 : 1;
-    if (const char* e = getenv("FPX_PLACEMENT_TRIES")) tries = std::max(1, std::min(8, atoi(e)));
     char* slab = nullptr;
     // round 5: chunk placement first (place_chunks above) -- a big slab of separate arrays is built from 1 GiB physical
     // chunks paired by measurement; one hipMalloc with candidate probing (rounds 2 - 4) stays the fallback
     bool chunked = false;
-    if (tries > 1 && g.VS == g.RS && stagger == 0 && !(getenv("FPX_PLACEMENT_CHUNKS") && atoi(getenv("FPX_PLACEMENT_CHUNKS")) == 0)) {
+    if (tries > 1 && g.VS == g.RS && !(getenv("FPX_PLACEMENT_CHUNKS") && atoi(getenv("FPX_PLACEMENT_CHUNKS")) == 0)) {
       size_t cstride = 0;
       if (place_chunks(ctx, narr, ncell * 4, g.RS / 4, &slab, &cstride)) chunked = true, stride = cstride, tries = 0;
     }
@@ -2020,7 +2011,7 @@ static int enqueue_ranges(fpx_ctx* ctx, RangeBatch& b, int mode) {
   // a few ranges: one workgroup walks clear -> open -> resolve -> acceptors -> tally (fpx_ranges.hpp: k_ranges_chain)
   const long long chain_words = ranges_chain_words(b.n, g.num_groups);
   const bool chain = mode == RANGES_FUSED && b.n <= RANGES_CHAIN_MAX && chain_words <= RANGES_CHAIN_LDS_WORDS &&
-                     (long long)b.n * g.num_groups * g.R <= 8 * 1024 && !getenv("FPX_RANGES_NO_CHAIN");
+                     (long long)b.n * g.num_groups * g.R <= 8 * 1024;
   if (chain) {
     allow_lds(k_ranges_chain, (size_t)chain_words * 4 + 64);
     hipLaunchKernelGGL(k_ranges_chain, dim3(1), dim3(1024), (size_t)chain_words * 4, ctx->stream, g, ctx->st, rt, b);
@@ -2042,7 +2033,7 @@ static int enqueue_ranges(fpx_ctx* ctx, RangeBatch& b, int mode) {
       const int gy = std::min(b.n, 4096);
       const int gx = std::max(1, std::min(ctx->num_cus * 16 / gy, 64));
       hipLaunchKernelGGL(k_ranges_fill_lg, dim3(gx, gy), dim3(256), 0, ctx->stream, g, ctx->st, b);
-    } else if (b.n <= RF_MAXN && g.num_leader_groups <= RF_MAXL && !getenv("FPX_RANGES_FILL_V1")) {
+    } else if (b.n <= RF_MAXN && g.num_leader_groups <= RF_MAXL) {
       // (RF_JB rows of L ownership words + the kernel's own 12 static bytes: beyond the default 64 KiB of dynamic LDS
       // the kernel needs the opt-in -- ADVICE r03: L close to 2048 failed every launch with FPX_EHIP)
       allow_lds(k_ranges_fill_rows, (size_t)RF_JB * g.num_leader_groups * 4 + 64);
@@ -2091,8 +2082,7 @@ static int enqueue_band_merged(fpx_ctx* ctx, Batch& b, RangeBatch& rb, bool* don
   const int G = ctx->lanes_per_slot;
   if (G > 8 || b.target || !g.lg_rows || g.per_slot || getenv("FPX_BAND_SERIAL")) return FPX_OK;
   const long long chain_words = ranges_chain_words(rb.n, g.num_groups);
-  if (rb.n > RANGES_CHAIN_MAX || chain_words > RANGES_CHAIN_LDS_WORDS || (long long)rb.n * g.num_groups * g.R > 8 * 1024 ||
-      getenv("FPX_RANGES_NO_CHAIN"))
+  if (rb.n > RANGES_CHAIN_MAX || chain_words > RANGES_CHAIN_LDS_WORDS || (long long)rb.n * g.num_groups * g.R > 8 * 1024)
     return FPX_OK;
   b.chunk = chunk_for(ctx, b.n);
   if ((b.n + b.chunk - 1) / b.chunk <= 8) return FPX_OK;  // one workgroup of commands: it finalises itself (`solo`)

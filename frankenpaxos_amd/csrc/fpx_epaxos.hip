@@ -62,11 +62,6 @@ struct EpxState {
   uint32_t* cl_stamp;   // [n * num_instances]  run id: instances of one batch must be distinct
 };
 
-#ifndef FPX_RS_ITEMS
-#define FPX_RS_ITEMS 16  // 64-element steps per wavefront (tile = 4 x that); 8 / 16 / 32 measured 0.317 / 0.302 / 0.322 ms per tick
-#endif
-#define FPX_RS_ITEMS_V FPX_RS_ITEMS
-
 struct EpxBatch {
   int m;
   const int32_t* leader;
@@ -174,14 +169,12 @@ __global__ void __launch_bounds__(256) k_epx_keys(const EpxState st, const EpxBa
 // step, lane) is the input order, so the sort is stable.  The tile is first sorted into LDS and leaves as runs of
 // consecutive elements per digit (a scatter straight from the ranking loop wrote 8 bytes per lane and instruction
 // to 64 different places: two such passes were 66 us for 5 M pairs, profiles/r02_epaxos_kernel_stats.csv).
-constexpr int RS_ITEMS = FPX_RS_ITEMS;      // 64-element steps per wavefront
+constexpr int RS_ITEMS = 16;                // 64-element steps per wavefront (tile = 4 x that); 8 / 16 / 32 measured
+                                            // 0.317 / 0.302 / 0.322 ms per tick
 constexpr int RS_TILE = 256 * RS_ITEMS;     // elements per workgroup tile
 constexpr int RS_MAXW = 11;                 // widest digit
 constexpr int RS_MAXB = 1 << RS_MAXW;
-#ifndef FPX_RS_SW
-#define FPX_RS_SW 8
-#endif
-constexpr int RS_SW = FPX_RS_SW;               // wavefronts of a scatter workgroup: 4 / 8 / 16 measured 0.259 / 0.240 / 0.255 ms per tick
+constexpr int RS_SW = 8;                    // wavefronts of a scatter workgroup: 4 / 8 / 16 measured 0.259 / 0.240 / 0.255 ms per tick
 constexpr size_t RS_SCATTER_LDS = (size_t)RS_TILE * 8 + (size_t)RS_SW * (RS_MAXB / 2) * 4 + (size_t)RS_MAXB * 4 + 64;
 
 struct RsArgs {

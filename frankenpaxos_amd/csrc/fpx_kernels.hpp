@@ -28,31 +28,6 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-// tuning knobs (compile time)
-// One slot row in flight per wavefront: batching 2 / 4 rows per wave cost occupancy and measured
-// slower (profiles/r01_tuning_sweep.txt); requesting the next row's ballots one step ahead measured
-// no better than not doing it (profiles/r01_tuning_sweep2.txt) -- the other 5-6 waves of the SIMD
-// already cover the latency.
-#ifndef FPX_CHUNK
-#define FPX_CHUNK 32   // messages per wavefront chunk at R in (128, 256]: 64 / 32 / 16 / 8 measured,
-                       // 32 and 16 are best (profiles/r01_tuning_sweep4.txt): finer units balance the XCDs
-#endif
-#ifndef FPX_NT_LOAD
-#define FPX_NT_LOAD 0  // ballot rows are read once: nontemporal loads
-#endif
-#ifndef FPX_PREFETCH
-#define FPX_PREFETCH 0
-#endif
-#ifndef FPX_EARLY_THR
-#define FPX_EARLY_THR 1  // the first step's ballot row is requested with the chunk's other loads (fpx_phase2_body.inc)
-#endif
-#ifndef FPX_STEADY_WALK
-#define FPX_STEADY_WALK 1  // G = 64, dense, PER_SLOT: a chunk whose rows all make the same choice walks them as scalars
-#endif                     // (fpx_phase2_body.inc)
-#ifndef FPX_NT
-#define FPX_NT 1  // vote rows are written once and not re-read soon: nontemporal stores
-#endif
-
 #include "fpx_fastdiv.hpp"
 
 namespace fpx {
@@ -67,6 +42,13 @@ enum : uint32_t { KEY_DONE = 0x80000000u, KEY_RANGE = 0x40000000u, KEY_ROUND_MAS
 constexpr int MAX_ROUND = 0x3ffffffe;
 constexpr int SUM_MIXED = INT32_MIN;  // State::ballot_sum: the row's cells differ (never a legal round)
 constexpr int PART_ALL_STRIDE = 32;  // ints: one 128-byte line per shard of the whole-group maxima
+
+// One slot row in flight per wavefront: batching 2 / 4 rows per wave cost occupancy and measured
+// slower (profiles/r01_tuning_sweep.txt); requesting the next row's ballots one step ahead measured
+// no better than not doing it (profiles/r01_tuning_sweep2.txt) -- the other 5-6 waves of the SIMD
+// already cover the latency.
+constexpr int CHUNK = 32;  // messages per wavefront chunk at R in (128, 256]: 64 / 32 / 16 / 8 measured,
+                           // 32 and 16 are best (profiles/r01_tuning_sweep4.txt): finer units balance the XCDs
 
 // status word layout in HBM (int32[8])
 // ST_ABORT: set by k_validate only (FPX_EINVAL / FPX_EORDER on a _dev batch): every later kernel up to the next
@@ -167,7 +149,7 @@ struct Batch {
   int32_t parity;          // K1 / K3 launch counter mod 3: which third of part_all this launch uses
   uint32_t launch_seq;     // K1 / K3 launch counter (never 0): stamps the rows of `part` this launch writes
   int32_t check_round;     // validate: enforce one round per group (ACCEPTOR ballot mode)
-  int32_t chunk;           // K1 / K3 at G = 64: messages per wavefront (4 .. FPX_CHUNK)
+  int32_t chunk;           // K1 / K3 at G = 64: messages per wavefront (4 .. CHUNK)
   int32_t index_base;      // added to the message index an error reports (host batches launched in pieces)
   int32_t solo;            // K1 / K3: the launch is ONE workgroup, which applies its maxima itself (no k_finalize follows)
   int32_t sc_lds;          // K1 / K3 on leader-group-major rows: byte offset of 4 x 3 KiB of LDS for the column quads (0 = none)
@@ -218,11 +200,7 @@ __device__ __forceinline__ void report(const State& st, int code, int index, int
 }
 
 __device__ __forceinline__ void row_store(int4v v, int4v* p) {
-#if FPX_NT
-  __builtin_nontemporal_store(v, p);
-#else
-  *p = v;
-#endif
+  __builtin_nontemporal_store(v, p);  // vote rows are written once and not re-read soon
 }
 
 __device__ __forceinline__ void report_abort(const State& st, int code, int index, int slot, int round) {
@@ -473,7 +451,7 @@ __global__ void __launch_bounds__(256) k_validate(const Geom g, const State st, 
 //           padded to a multiple of 4 cells)
 //   PERSLOT ballot[S][R] in HBM instead of the per-acceptor scalar
 //   FUSED   K3 (open + vote + tally) instead of K1 (vote, bitmaps out)
-// A wavefront owns a chunk of consecutive messages (FPX_CHUNK = 32 at G = 64, else 64): it stages
+// A wavefront owns a chunk of consecutive messages (CHUNK = 32 at G = 64, else 64): it stages
 // their (slot, round, value) in registers with one coalesced load each, runs the proxy leader's open
 // step for all of them at once (K3), then walks them Q = 64/G at a time.
 // LDS: the workgroup's maxima (whole-group scalars, or [2][ntab] tables after a partial vote), then

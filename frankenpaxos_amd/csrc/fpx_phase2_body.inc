@@ -97,7 +97,7 @@ __global__ void __launch_bounds__(256)
 
   // the steady walk (below) of the dense G = 64 kernels without lazy promises: may a chunk take it at all?  One acceptor
   // group, and (fused) the whole group's votes -- what every row of a steady chunk collects -- make a write quorum
-  constexpr bool STEADY = FPX_STEADY_WALK && G == 64 && MODE == 0 && PS == 1;
+  constexpr bool STEADY = G == 64 && MODE == 0 && PS == 1;
   bool steady_ok = false;
   if constexpr (STEADY) {
     if (one_group) {
@@ -224,14 +224,10 @@ __global__ void __launch_bounds__(256)
           if (bs != SUM_MIXED) {
             thr = int4v{bs, bs, bs, bs};  // a uniform row: nothing to read
           } else if (VEC) {
-#if FPX_NT_LOAD
-            if (own) thr = __builtin_nontemporal_load(reinterpret_cast<const int4v*>(st.ballot + row));
-#else
             if (own) thr = *reinterpret_cast<const int4v*>(st.ballot + row);
-#endif
             // waited for HERE, on the path that loaded: left to the compiler, the wait sits behind the branch, where
             // every uniform row would wait for the stores of the step before it (vmcnt counts stores on gfx9)
-            if constexpr (SUMREAD && !FPX_PREFETCH) __builtin_amdgcn_s_waitcnt(0x0F70);
+            if constexpr (SUMREAD) __builtin_amdgcn_s_waitcnt(0x0F70);
           } else {
 #pragma unroll
             for (int k = 0; k < 4; ++k)
@@ -269,7 +265,7 @@ __global__ void __launch_bounds__(256)
     // HERE, beside the tally keys and the row_voted bytes, instead of behind the wait for those -- one memory round trip
     // less per chunk: BASELINE.json configs[1] 0.0093 -> 0.0088 ms per step.  The wide-row kernels keep the order they had
     // (measured the same or up to 1 % slower with it: profiles/r06_raw/early_thr_ab.txt).
-    constexpr bool EARLY = FPX_EARLY_THR && G == 1 && PERSLOT && !PACK;
+    constexpr bool EARLY = G == 1 && PERSLOT && !PACK;
     int s_cur = -1, grp_cur = 0, phys_cur = 0;
     int4v thr_cur = init_thr;
     if constexpr (EARLY) thr_cur = load_thr(0, s_cur, grp_cur, phys_cur);
@@ -488,11 +484,6 @@ __global__ void __launch_bounds__(256)
     if (!STEADY || !steady) {  // (without the steady walk: no branch at all, the code of the kernels before it)
     if constexpr (!EARLY) thr_cur = load_thr(0, s_cur, grp_cur, phys_cur);
     for (int t = 0; t < G * CH / 64; ++t) {
-#if FPX_PREFETCH
-      int s_nxt = -1, grp_nxt = 0, phys_nxt = 0;
-      int4v thr_nxt = init_thr;
-      if (t + 1 < G) thr_nxt = load_thr(t + 1, s_nxt, grp_nxt, phys_nxt);
-#endif
       const int src = t * Q + q;
       const int s = s_cur;
       const int rnd = pick(myround, src);
@@ -707,11 +698,7 @@ __global__ void __launch_bounds__(256)
           wo->nack_round[src] = nrm;
         }
       }
-#if FPX_PREFETCH
-      s_cur = s_nxt, grp_cur = grp_nxt, phys_cur = phys_nxt, thr_cur = thr_nxt;
-#else
       if (t + 1 < G) thr_cur = load_thr(t + 1, s_cur, grp_cur, phys_cur);
-#endif
     }
     }  // (the general walk)
     }  // (the walk, one row per step)
