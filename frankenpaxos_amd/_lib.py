@@ -37,6 +37,11 @@ FPX_F_SLOT_MAJOR_ROWS = 4
 
 FPX_NOOP = -1
 
+# fpx_vote_launch_census (include/fpx.h): the forms of a vote launch, then the fates of its fold
+CENSUS_FORMS = ("solo", "grid", "fin", "band", "fold_now", "fold_behind", "fold_carried", "fold_flushed")
+CENSUS_CELLS = 7 * 4 * 3 * 2
+CENSUS_WORDS = CENSUS_CELLS * len(CENSUS_FORMS) + 3
+
 
 class FpxConfig(C.Structure):
     """fpx_config (include/fpx.h)."""
@@ -83,6 +88,7 @@ SIGNATURES = {
     "fpx_placement_search": (C.c_int32, [VP, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_float)]),
     "fpx_band_merged_steps": (C.c_int64, [VP]),
     "fpx_deferred_folds": (C.c_int64, [VP]),
+    "fpx_vote_launch_census": (C.c_int32, [VP, C.c_int32, C.POINTER(C.c_int64), I32P]),
     "fpx_acceptor_max_voted_in": (C.c_int32, [VP, C.c_int32, C.c_int32, C.c_int32, C.c_int32, I32P]),
     "fpx_profile_read_launches": (C.c_int32, [VP, C.c_int32, C.POINTER(C.c_float), C.POINTER(C.c_int32)]),
     "fpx_get_config": (C.c_int32, [VP, CFGP]),

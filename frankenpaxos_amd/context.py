@@ -146,6 +146,28 @@ class Context:
         """diagnostic: the mencius_band_fused_dev steps that ran in the two-launch form"""
         return int(self.L.fpx_band_merged_steps(self._h))
 
+    def vote_launch_census(self):
+        """diagnostic: the vote launches since the context was created (include/fpx.h, fpx_vote_launch_census) --
+        {"cells": {(G, mode, ps, fused, form): count} with the non-zero cells only, "capped": n, "sc_lds": n, "th_lds": n};
+        form is one of _lib.CENSUS_FORMS"""
+        out = (C.c_int64 * _lib.CENSUS_WORDS)()
+        n = C.c_int32(0)
+        st = self.L.fpx_vote_launch_census(self._h, _lib.CENSUS_WORDS, out, C.byref(n))
+        if st:
+            raise FpxError(st, "fpx_vote_launch_census")
+        assert n.value == _lib.CENSUS_WORDS, "include/fpx.h and _lib.CENSUS_WORDS disagree"
+        nf = len(_lib.CENSUS_FORMS)
+        cells = {}
+        for k in range(_lib.CENSUS_CELLS * nf):
+            if out[k]:
+                cell, form = divmod(k, nf)
+                rest, fused = divmod(cell, 2)
+                rest, ps = divmod(rest, 3)
+                g_log2, mode = divmod(rest, 4)
+                cells[(1 << g_log2, mode, ps, fused, _lib.CENSUS_FORMS[form])] = int(out[k])
+        base = _lib.CENSUS_CELLS * nf
+        return {"cells": cells, "capped": int(out[base]), "sc_lds": int(out[base + 1]), "th_lds": int(out[base + 2])}
+
     # ---- host-pointer entry points (numpy) ---------------------------------------------------
     def acceptor_phase2a(self, slot, round_, value, target_mask=None):
         slot, round_, value, target_mask = _i32(slot), _i32(round_), _i32(value), _u64(target_mask)

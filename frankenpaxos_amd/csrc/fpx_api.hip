@@ -140,6 +140,10 @@ struct fpx_ctx {
   hipStream_t band_stream = nullptr;
   int64_t band_merged_steps = 0;
   hipEvent_t band_fork = nullptr, band_join = nullptr;
+  // fpx_vote_launch_census (include/fpx.h): host counters of the vote launches and of their folds
+  int64_t census[FPX_CENSUS_WORDS] = {};
+  int census_cell = 0;                       // the cell of the vote launch just enqueued
+  int census_pending = 0, census_carry = 0;  // the cells of the launches whose folds are pending_fin / carry_fin
   DevBuf d_band;  // [num_leader_groups] marks: the leader groups with a range in the step being checked
   // multi-GPU (fpx_comm_*): one communicator per context, rank = this context's GPU
   RcclComm comm = nullptr;
@@ -329,6 +333,16 @@ size_t phase2_lds(fpx_ctx* ctx, Batch& b, bool fused, bool targets, bool accepto
   return lds;
 }
 
+// one vote launch in its census cell (fpx_vote_launch_census); returns the cell
+int census_launch(fpx_ctx* ctx, int G, int mode, int ps, bool fused, int form, const Batch& b) {
+  const int cell = FPX_CENSUS_CELL(__builtin_ctz((unsigned)G), mode, ps, fused ? 1 : 0);
+  ++ctx->census[cell * FPX_CENSUS_FORMS + form];
+  if (b.sc_lds) ++ctx->census[FPX_CENSUS_SC_LDS];
+  if (b.th_lds) ++ctx->census[FPX_CENSUS_TH_LDS];
+  return ctx->census_cell = cell;
+}
+void census_fold(fpx_ctx* ctx, int cell, int fate) { ++ctx->census[cell * FPX_CENSUS_FORMS + fate]; }
+
 template <int G, int MODE, int PS>
 void launch_phase2_3(fpx_ctx* ctx, const Batch& b0, bool fused, int grid) {
   Batch b = b0;
@@ -344,9 +358,12 @@ void launch_phase2_3(fpx_ctx* ctx, const Batch& b0, bool fused, int grid) {
                             ctx->ev_start, ctx->ev_stop, 0, ctx->g, ctx->launch_st, b, ctx->carry_fin);
       ctx->carry_fin.nblk = 0;
       ++ctx->fins_carried;
+      census_launch(ctx, G, MODE, PS, fused, FPX_CENSUS_FIN, b);
+      census_fold(ctx, ctx->census_carry, FPX_CENSUS_FOLD_CARRIED);
       return;
     }
   }
+  census_launch(ctx, G, MODE, PS, fused, b.solo ? FPX_CENSUS_SOLO : FPX_CENSUS_GRID, b);
   if (fused)
     hipExtLaunchKernelGGL((k_phase2<G, MODE, PS, true>), dim3(grid), dim3(256), (uint32_t)lds, ctx->stream, ctx->ev_start,
                           ctx->ev_stop, 0, ctx->g, ctx->launch_st, b);
@@ -396,6 +413,7 @@ void launch_phase2(fpx_ctx* ctx, const Batch& b, bool fused, int grid) {
 template <int G>
 void launch_band_g(fpx_ctx* ctx, const Batch& b, size_t lds, int grid, const RangeTable& rt, const RangeBatch& rb) {
   allow_lds(k_phase2_band<G, 0, 0, true>, lds);
+  census_launch(ctx, G, 0, 0, true, FPX_CENSUS_BAND, b);
   hipExtLaunchKernelGGL((k_phase2_band<G, 0, 0, true>), dim3(grid + 1), dim3(256), (uint32_t)lds, ctx->stream, ctx->ev_start,
                         ctx->ev_stop, 0, ctx->g, ctx->launch_st, b, rt, rb);
 }
@@ -484,6 +502,7 @@ void flush_pending_fin(fpx_ctx* ctx) {
   if (!ctx->pending_fin.nblk) return;
   launch_fin_alone(ctx, ctx->pending_fin);
   ctx->pending_fin.nblk = 0;
+  census_fold(ctx, ctx->census_pending, FPX_CENSUS_FOLD_FLUSHED);
   (void)launch_check(ctx);
 }
 
@@ -500,6 +519,7 @@ int enqueue_phase2(fpx_ctx* ctx, Batch& b, bool fused) {
   // of the partial-maxima buffers is not consumed
   b.solo = (b.n + b.chunk - 1) / b.chunk <= 8 ? 1 : 0;
   if (b.solo) grid = 1;
+  else if ((b.n + 4 * b.chunk - 1) / (4 * b.chunk) > grid) ++ctx->census[FPX_CENSUS_CAPPED];
   // Target masks on 256-cell rows of one group: thrifty delivery to RUNS of neighbouring acceptors (what GpuProxyLeader
   // sends by default; any f + 1 will do: ProxyLeader.scala:190-191) takes two rows per wavefront step.  Two launches: the
   // packed walk takes the chunks all of whose messages go to such runs of rows nobody voted in yet and marks them, the
@@ -532,6 +552,7 @@ int enqueue_phase2(fpx_ctx* ctx, Batch& b, bool fused) {
     // the fold of the launch before, if it is still pending: offered to this launch (launch_phase2_3 takes it into its
     // grid when the kernel has that form), else launched by itself behind it -- before the launch after this one either way
     ctx->carry_fin = ctx->pending_fin;
+    ctx->census_carry = ctx->census_pending;
     ctx->pending_fin.nblk = 0;
     launch_phase2(ctx, b, fused, grid);
     ctx->packed_pass = false;
@@ -539,6 +560,7 @@ int enqueue_phase2(fpx_ctx* ctx, Batch& b, bool fused) {
     if (ctx->carry_fin.nblk) {
       launch_fin_alone(ctx, ctx->carry_fin);
       ctx->carry_fin.nblk = 0;
+      census_fold(ctx, ctx->census_carry, FPX_CENSUS_FOLD_BEHIND);
     }
     rc = launch_check(ctx);
     if (rc) return rc;
@@ -550,7 +572,9 @@ int enqueue_phase2(fpx_ctx* ctx, Batch& b, bool fused) {
     const bool no_defer = getenv("FPX_NO_DEFER_FINALIZE") != nullptr;  // (read per launch: a test switches it between contexts)
     if (fused && ctx->g.per_slot && !no_defer) {
       ctx->pending_fin = fj;
+      ctx->census_pending = ctx->census_cell;
     } else {
+      census_fold(ctx, ctx->census_cell, FPX_CENSUS_FOLD_NOW);
       launch_fin_alone(ctx, fj);
       rc = launch_check(ctx);
       if (rc) return rc;
@@ -2094,6 +2118,7 @@ static int enqueue_band_merged(fpx_ctx* ctx, Batch& b, RangeBatch& rb, bool* don
   int rc = enqueue_validate(ctx, b, true);
   if (rc) return rc;
   const int grid = grid_for(ctx, b.n);
+  if ((b.n + 4 * b.chunk - 1) / (4 * b.chunk) > grid) ++ctx->census[FPX_CENSUS_CAPPED];
   b.solo = 0;
   begin_phase2_launch(ctx, b);
   if (++ctx->launch_seq == 0) ctx->launch_seq = 1;
@@ -2201,6 +2226,14 @@ int32_t fpx_mencius_band_fused_dev(fpx_ctx* ctx, int32_t n, const int32_t* d_slo
 }
 
 int64_t fpx_band_merged_steps(fpx_ctx* ctx) { return ctx ? ctx->band_merged_steps : 0; }
+
+// (no DeviceGuard: reading the census must not launch the pending fold it would then count)
+int32_t fpx_vote_launch_census(fpx_ctx* ctx, int32_t cap, int64_t* out, int32_t* n) {
+  if (!ctx || cap < 0) return FPX_EINVAL;
+  if (out) memcpy(out, ctx->census, sizeof(int64_t) * (size_t)std::min<int32_t>(cap, FPX_CENSUS_WORDS));
+  if (n) *n = FPX_CENSUS_WORDS;
+  return FPX_OK;
+}
 
 namespace {
 struct RangeKey {

@@ -420,6 +420,54 @@ int32_t fpx_mencius_band_fused_dev(fpx_ctx* ctx, int32_t n, const int32_t* d_slo
 int64_t fpx_deferred_folds(fpx_ctx* ctx);
 /* diagnostic: the steps of fpx_mencius_band_fused_dev that ran in the two-launch form since fpx_create */
 int64_t fpx_band_merged_steps(fpx_ctx* ctx);
+/* diagnostic: a census of the vote launches (K1 / K3, the kernel k_phase2 and its forms) since fpx_create -- plain host
+ * counters, bumped where the host chooses a launch; nothing runs on the device and reading them launches nothing (not even a
+ * pending fold).  fpx_reset does NOT clear them (nor fpx_deferred_folds / fpx_band_merged_steps): they count the life of
+ * the context.  Writes min(cap, FPX_CENSUS_WORDS) int64 words to out and FPX_CENSUS_WORDS to *n (either may be NULL).
+ *
+ * Words [0, FPX_CENSUS_CELLS * FPX_CENSUS_FORMS): counts[cell * FPX_CENSUS_FORMS + form], cell = FPX_CENSUS_CELL(...):
+ *   G       lanes per slot (1, 2, 4, ... 64: the smallest power of two with 4 G >= num_replicas)
+ *   mode    0 dense delivery, 1 target masks, 2 target masks + FPX_F_SCATTERED_TARGETS, 3 the packed walk (G = 64)
+ *   ps      0 a round per acceptor (FPX_BALLOT_ACCEPTOR), 1 a ballot per cell, 2 a ballot per cell with lazy Phase1a
+ *           promises outstanding
+ *   fused   0 K1 (fpx_acceptor_phase2a*), 1 K3 (fpx_phase2_fused*, fpx_mencius_band_fused_dev)
+ * Every vote launch counts once under one of the first four forms, in its own cell:
+ *   FPX_CENSUS_SOLO   one workgroup that applies its maxima itself (no fold follows)
+ *   FPX_CENSUS_GRID   several workgroups, k_phase2: a fold of their per-workgroup maxima rows follows (below)
+ *   FPX_CENSUS_FIN    several workgroups, k_phase2_fin: the grid also carries the fold of the launch before
+ *   FPX_CENSUS_BAND   k_phase2_band: a Mencius band's vote kernel with the range chain as its first workgroup
+ *                     (its fold rides in the fill behind it)
+ * and the fold of every FPX_CENSUS_GRID / FPX_CENSUS_FIN launch counts once under one of the other four, in the cell of
+ * the launch whose maxima it folds:
+ *   FPX_CENSUS_FOLD_NOW      launched by itself (k_finalize) right behind its vote launch
+ *   FPX_CENSUS_FOLD_BEHIND   left pending, then launched by itself right behind the NEXT vote launch (the widths
+ *                            without k_phase2_fin: the two launches use the two halves of the maxima rows)
+ *   FPX_CENSUS_FOLD_CARRIED  left pending, then carried in the next vote launch's grid (FPX_CENSUS_FIN there)
+ *   FPX_CENSUS_FOLD_FLUSHED  left pending, then launched by itself by an entry point or ahead of a solo launch
+ *   (a fold still pending when the census is read is not counted yet)
+ * Then three words: FPX_CENSUS_CAPPED  the vote launches whose grid was capped below what the batch needed (every
+ * wavefront walks several chunks); FPX_CENSUS_SC_LDS  those that had LDS for the column quads of a slot-ordered batch
+ * (leader-group-major rows and every array 16-byte aligned); FPX_CENSUS_TH_LDS  those that staged the acceptors'
+ * rounds of every group per workgroup. */
+enum {
+  FPX_CENSUS_SOLO = 0,
+  FPX_CENSUS_GRID = 1,
+  FPX_CENSUS_FIN = 2,
+  FPX_CENSUS_BAND = 3,
+  FPX_CENSUS_FOLD_NOW = 4,
+  FPX_CENSUS_FOLD_BEHIND = 5,
+  FPX_CENSUS_FOLD_CARRIED = 6,
+  FPX_CENSUS_FOLD_FLUSHED = 7,
+  FPX_CENSUS_FORMS = 8,
+  FPX_CENSUS_CELLS = 7 * 4 * 3 * 2,
+  FPX_CENSUS_CAPPED = FPX_CENSUS_CELLS * FPX_CENSUS_FORMS,
+  FPX_CENSUS_SC_LDS = FPX_CENSUS_CAPPED + 1,
+  FPX_CENSUS_TH_LDS = FPX_CENSUS_CAPPED + 2,
+  FPX_CENSUS_WORDS = FPX_CENSUS_CAPPED + 3
+};
+/* the census cell of (G, mode, ps, fused) as above: G_log2 = log2(G) */
+#define FPX_CENSUS_CELL(G_log2, mode, ps, fused) ((((G_log2) * 4 + (mode)) * 3 + (ps)) * 2 + (fused))
+int32_t fpx_vote_launch_census(fpx_ctx* ctx, int32_t cap, int64_t* out, int32_t* n);
 /* batches of one (bitmaps num_groups x 4 words) */
 int32_t fpx_acceptor_phase2a_noop_range(fpx_ctx* ctx, int32_t slot_start, int32_t slot_end,
                                         int32_t round, const uint64_t* target_masks,

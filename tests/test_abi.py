@@ -58,6 +58,22 @@ def test_header_compiles_as_c_and_cxx(tmp_path):
     assert os.system("g++ -std=c++17 -Wall -Werror -I%s -x c++ -c %s -o %s" % (inc, src, tmp_path / "t2.o")) == 0
 
 
+def test_vote_launch_census_layout_matches_the_binding(fa, tmp_path):
+    """the census words of include/fpx.h (fpx_vote_launch_census) as Context.vote_launch_census decodes them"""
+    src = tmp_path / "c.c"
+    src.write_text('#include <stdio.h>\n#include "fpx.h"\nint main(void){printf("%d %d %d %d %d %d %d\\n", '
+                   'FPX_CENSUS_WORDS, FPX_CENSUS_CELLS, FPX_CENSUS_FORMS, FPX_CENSUS_FOLD_FLUSHED, FPX_CENSUS_CAPPED, '
+                   'FPX_CENSUS_TH_LDS, FPX_CENSUS_CELL(5, 2, 1, 1)); return 0;}\n')
+    exe = tmp_path / "c"
+    assert os.system("gcc -std=c99 -Wall -Werror -I%s %s -o %s" % (os.path.join(ROOT, "include"), src, exe)) == 0
+    words, ncells, forms, flushed, capped, th, cell = map(int, os.popen(str(exe)).read().split())
+    L = fa._lib
+    assert (words, ncells, forms) == (L.CENSUS_WORDS, L.CENSUS_CELLS, len(L.CENSUS_FORMS))
+    assert L.CENSUS_FORMS[flushed] == "fold_flushed" and capped == ncells * forms and th == capped + 2
+    assert cell == ((5 * 4 + 2) * 3 + 1) * 2 + 1      # (G = 32, mode 2, ps 1, fused): Context decodes cells this way
+    assert fa._lib.SIGNATURES["fpx_vote_launch_census"][0] is C.c_int32
+
+
 def test_config_struct_layout_matches_the_oracle(fa, oracle):
     a, b = fa.FpxConfig, oracle.Config
     assert [(n, t) for n, t in a._fields_] == [(n, t) for n, t in b._fields_]

@@ -80,7 +80,9 @@ def test_adversarial_256_replicas(fa, oracle, seed, ballot_mode, fused):
 
 
 # ---------------------------------------------------------------------------------------------------
-# every lanes-per-slot instantiation: R from 1 to 256, odd sizes included
+# every lanes-per-slot width: R from 1 to 256, odd sizes included.  Batches here stay below 512 messages, so below
+# G = 64 every launch is solo (one workgroup that finalises itself); the multi-workgroup forms of every width are
+# tests/test_gpu_vote_matrix.py's
 # ---------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("R", [1, 2, 3, 4, 5, 7, 8, 12, 16, 17, 31, 32, 33, 64, 65, 100, 128, 129, 255])
 @pytest.mark.parametrize("ballot_mode", [0, 1])
