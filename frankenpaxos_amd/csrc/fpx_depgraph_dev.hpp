@@ -37,22 +37,19 @@ constexpr int DG_SUB = DG_TILE / 256;  // workgroups of k_dg_relax per tile: eac
 
 template <int N> struct DgRow { static constexpr int NP = N <= 4 ? 4 : 8; };
 
-struct DgArgs {
+// What both forms of the closure rounds share (the wide rows below, the packed ones of fpx_depgraph_pk.hpp): the inputs and
+// everything behind the rounds -- keys, sorts, component starts, the handshake with the host.  A form's own argument
+// struct adds its rows.
+struct DgCommon {
   int m, n, stride;                 // messages, replicas, ints per packed line
-  int32_t first[8], count[8], base[8], tiles[8], tile_base[8];  // per column: first id, instances, first vertex, scan tiles
-  int ntiles;
+  int32_t first[8], count[8], base[8];  // per column: first id, instances, first vertex
   const int32_t* leader;            // [m]
   const int32_t* number;            // [m]
   const int32_t* packed;            // [m][stride]: deps | leader_deps | own_values_end[2] | fast
   const uint8_t* mask;              // [m] or null: 0 = not committed (blocks what depends on it)
   int32_t* msg_of;                  // [m] vertex -> message (-1: no such instance was handed in)
-  int32_t* direct;                  // [m][NP] direct dependency covers (own column: max(watermark, values end))
-  int32_t* clo;                     // [m][NP] closure
-  int32_t* pre;                     // [m][NP] prefix max of clo within the column
-  int32_t* tmax;                    // [ntiles][DG_SUB][NP]: what the next round's scan carries in from the tiles before it (one row
-                                    // per workgroup of k_dg_relax; k_dg_tilemax fills row 0 of a tile for the first round)
   int32_t* tstarts;                 // [out tiles] component starts per tile of the sorted order
-  int32_t* belig;                   // [ceil(m / 256)] executable vertices per workgroup of k_dg_keys (summed by k_dg_rekey)
+  int32_t* belig;                   // [ceil(m / 256)] executable vertices per workgroup of the keys kernel (summed by k_dg_rekey)
   uint2* pairs;                     // [m] (sort key, vertex)
   uint2* pairs2;
   uint32_t* key32;                  // [m] the main sort key of a vertex (pairs carry the closure's hash first)
@@ -65,6 +62,17 @@ struct DgArgs {
                                     // FPX_DG_HASH_BITS, which tests use to force the collisions ctl[2] reports)
   int32_t* order;                   // [m] message indices in execution order
   int32_t* comp;                    // [m] component number of position p (0, 1, ..)
+};
+
+// the wide form: rows of NP ints, a prefix kernel and a gather kernel per round
+struct DgArgs : DgCommon {
+  int32_t tiles[8], tile_base[8];   // per column: scan tiles, the first one's index
+  int ntiles;
+  int32_t* direct;                  // [m][NP] direct dependency covers (own column: max(watermark, values end))
+  int32_t* clo;                     // [m][NP] closure
+  int32_t* pre;                     // [m][NP] prefix max of clo within the column
+  int32_t* tmax;                    // [ntiles][DG_SUB][NP]: what the next round's scan carries in from the tiles before it (one row
+                                    // per workgroup of k_dg_relax; k_dg_tilemax fills row 0 of a tile for the first round)
 };
 
 // vertex of (L, x), or -1
@@ -140,14 +148,13 @@ __global__ void __launch_bounds__(256) k_dg_tilemax(const DgArgs a) {
 }
 
 // pre[v] = max of the closures of the column's vertices up to and including v
-// r = the round (absolute: the tile maxima's half), k = its number within the chunk enqueued at once
+// k = the round's number within the chunk enqueued at once
 template <int N>
-__global__ void __launch_bounds__(256) k_dg_prefix(const DgArgs a, int r, int k) {
+__global__ void __launch_bounds__(256) k_dg_prefix(const DgArgs a, int k) {
   constexpr int NP = DgRow<N>::NP;
   __shared__ int carry[NP];
   __shared__ int wtot[4][NP];
   if (k > 1 && a.ctl[8 + k - 1] == 0) return;  // the round before moved nothing: pre[] is final
-  (void)r;
   int col = 0;
   while (col + 1 < N && (int)blockIdx.x >= a.tile_base[col + 1]) ++col;
   const int t = blockIdx.x - a.tile_base[col];
@@ -218,9 +225,8 @@ __global__ void __launch_bounds__(256) k_dg_prefix(const DgArgs a, int r, int k)
 // tmax written with plain stores.  (A first version folded them with atomicMax from vertex-order workgroups: 160 atomics
 // on each tile's 32-byte line cost 55 us per launch, profiles/r05_depgraph_dev.md.)
 template <int N>
-__global__ void __launch_bounds__(256) k_dg_relax(const DgArgs a, int r, int k) {
+__global__ void __launch_bounds__(256) k_dg_relax(const DgArgs a, int k) {
   constexpr int NP = DgRow<N>::NP;
-  (void)r;
   __shared__ int sh[4][NP];
   if (k > 1 && a.ctl[8 + k - 1] == 0) return;
   const int tile = blockIdx.x / DG_SUB, sub = blockIdx.x % DG_SUB;
@@ -279,12 +285,21 @@ __global__ void __launch_bounds__(256) k_dg_relax(const DgArgs a, int r, int k) 
     a.tmax[(size_t)blockIdx.x * NP + threadIdx.x] = imax(imax(sh[0][threadIdx.x], sh[1][threadIdx.x]), imax(sh[2][threadIdx.x], sh[3][threadIdx.x]));
 }
 
-// publishes the control words of the round to the host (one workgroup, after the round's kernels)
-__global__ void k_dg_publish(const DgArgs a, int round) {
-  (void)round;
-  if (threadIdx.x < 7) a.host[threadIdx.x] = threadIdx.x == 5 ? a.ctl[8 + DG_ROUNDS] : a.ctl[threadIdx.x];  // [5]: the chunk's last round still moved
+// publishes the control words of a chunk of rounds to the host (one workgroup, after the chunk's kernels).  last_k: the
+// rounds of the chunk that were enqueued.  [5] = the last of them still moved (another chunk is needed), [6] = how many of
+// them moved something (the next call enqueues one more than that: see dg_run)
+__global__ void k_dg_publish(const DgCommon a, int last_k) {
+  if (threadIdx.x < 7) {
+    int v = a.ctl[threadIdx.x];
+    if (threadIdx.x == 5) v = a.ctl[8 + last_k];
+    if (threadIdx.x == 6) {
+      v = 0;
+      for (int k = 1; k <= last_k; ++k) v += a.ctl[8 + k] != 0 ? 1 : 0;
+    }
+    a.host[threadIdx.x] = v;
+  }
   __threadfence_system();
-  if (threadIdx.x == 0) a.host[7] = a.seq;  // (call, round): what the host waits for
+  if (threadIdx.x == 0) a.host[7] = a.seq;  // (call, chunk): what the host waits for
 }
 
 // the sort key of every vertex: 3 x (sum of the closure beyond the columns' executed prefixes) + kind (the sum is at most m,
@@ -298,11 +313,11 @@ __device__ __forceinline__ uint32_t dg_hash(const int* c, int bits) {
   for (int l = 0; l < N; ++l) h = kp_mix32(h ^ (uint32_t)c[l]) + 0x7F4A7C15u;
   return h >> (32 - bits);
 }
-__global__ void __launch_bounds__(256) k_dg_rekey(const DgArgs a) {  // after the sort on the hash: the main key, by vertex
+__global__ void __launch_bounds__(256) k_dg_rekey(const DgCommon a) {  // after the sort on the hash: the main key, by vertex
   __shared__ uint32_t sh[8];
   const int p = blockIdx.x * blockDim.x + threadIdx.x;
   if (p < a.m) a.pairs[p].x = a.key32[a.pairs[p].y];
-  if (blockIdx.x == 0) {  // the number of executables (ctl[3]) from the workgroups' counts of k_dg_keys
+  if (blockIdx.x == 0) {  // the number of executables (ctl[3]) from the workgroups' counts of the keys kernel
     const int vblocks = (a.m + 255) >> 8;
     uint32_t s = 0;
     for (int b = (int)threadIdx.x; b < vblocks; b += 256) s += (uint32_t)a.belig[b];
@@ -372,53 +387,67 @@ __global__ void __launch_bounds__(256) k_dg_keys(const DgArgs a) {
   if (threadIdx.x == 0) a.belig[blockIdx.x] = block_eligible;
 }
 
+// What the kernels behind the sorts ask of a form's closures: are those of two vertices equal, and the hash one was sorted
+// by.  (The hash stays the form's own: the order inside one key follows it.)
 template <int N>
-__device__ __forceinline__ int dg_cmp_clo(const DgArgs& a, uint32_t u, uint32_t v) {  // closure vectors, lexicographically
-  constexpr int NP = DgRow<N>::NP;
-  for (int l = 0; l < N; ++l) {
-    const int x = a.clo[(size_t)u * NP + l], y = a.clo[(size_t)v * NP + l];
-    if (x != y) return x < y ? -1 : 1;
+struct DgClosures {
+  static constexpr int NP = DgRow<N>::NP;
+  const int32_t* clo;
+  __device__ __forceinline__ bool equal(uint32_t u, uint32_t v) const {
+    for (int l = 0; l < N; ++l)
+      if (clo[(size_t)u * NP + l] != clo[(size_t)v * NP + l]) return false;
+    return true;
   }
-  return 0;
-}
+  __device__ __forceinline__ uint32_t hash(uint32_t u, int bits) const { return dg_hash<N>(clo + (size_t)u * NP, bits); }
+};
 
-// component starts -> component numbers (inclusive scan of the start flags, one workgroup per DG_TILE positions, the
-// tiles' totals through tmax as three kernels would: here the flags of a tile are counted by every later tile again --
-// 512 tiles x 8 KB at most), and the message indices in execution order
 // does a component start at position p of the sorted order?  Vertices that lie on no cycle are components of their own;
 // cyclic neighbours with one key belong together iff their closures are equal.  Two DIFFERENT closures with one key and
 // one hash would leave their members interleaved: that is seen here and sends the tick the host's way.
-template <int N>
-__device__ __forceinline__ uint32_t dg_starts(const DgArgs& a, int p, int executables) {  // executables = ctl[3], read by the caller
-  constexpr int NP = DgRow<N>::NP;
+template <class Clo>
+__device__ __forceinline__ uint32_t dg_starts(const DgCommon& a, const Clo& c, int p, int executables) {  // executables = ctl[3], read by the caller
   if (p >= executables) return 0u;
   const uint2 e = a.pairs[p];
   if (e.x % 3u != 0u || p == 0) return 1u;
   const uint2 f = a.pairs[p - 1];
   if (f.x != e.x) return 1u;
-  if (dg_cmp_clo<N>(a, f.y, e.y) == 0) return 0u;
-  if (dg_hash<N>(a.clo + (size_t)f.y * NP, a.hash_bits) == dg_hash<N>(a.clo + (size_t)e.y * NP, a.hash_bits)) a.ctl[2] = 1;
+  if (c.equal(f.y, e.y)) return 0u;
+  if (c.hash(f.y, a.hash_bits) == c.hash(e.y, a.hash_bits)) a.ctl[2] = 1;
   return 1u;
 }
 
-template <int N>
-__global__ void __launch_bounds__(256) k_dg_emit(const DgArgs a) {
+// component starts -> component numbers (inclusive scan of the start flags, one workgroup per DG_TILE positions; the
+// tiles' totals go through tstarts: k_dg_count_starts leaves them, k_dg_emit computes its tile's flags again), and the
+// message indices in execution order
+template <class Clo>
+__global__ void __launch_bounds__(256) k_dg_count_starts(const DgCommon a, const Clo c) {
+  __shared__ uint32_t sh[8];
+  const int executables = a.ctl[3];
+  const int t0 = blockIdx.x * DG_TILE;
+  uint32_t total = 0;
+  for (int j = 0; j < DG_TILE / 256; ++j) total += dg_starts(a, c, t0 + j * 256 + threadIdx.x, executables);
+  const uint32_t ex = block_excl_sum(total, sh);
+  if (threadIdx.x == 255) a.tstarts[blockIdx.x] = (int32_t)(ex + total);
+}
+
+template <class Clo>
+__global__ void __launch_bounds__(256) k_dg_emit(const DgCommon a, const Clo c) {
   __shared__ uint32_t sh[8];
   __shared__ uint32_t before_tile;
   const int executables = a.ctl[3];
-  auto starts = [&](int p) -> uint32_t { return dg_starts<N>(a, p, executables); };
   const int t0 = blockIdx.x * DG_TILE;
-  // flags of my tile
-  uint32_t mine[DG_TILE / 256], total = 0;
+  uint32_t mine[DG_TILE / 256];
 #pragma unroll
-  for (int j = 0; j < DG_TILE / 256; ++j) mine[j] = starts(t0 + j * 256 + threadIdx.x), total += mine[j];
-  // the components that start before my tile were counted into tstarts[tile] by k_dg_count_starts
-  if (threadIdx.x == 0) {
+  for (int j = 0; j < DG_TILE / 256; ++j) mine[j] = dg_starts(a, c, t0 + j * 256 + threadIdx.x, executables);
+  {
+    // the components that start in the tiles before this one: 256 threads add up the tiles' counts (one thread walking up to
+    // 512 of them was ~10 us of the kernel)
     uint32_t s = 0;
-    for (int t = 0; t < (int)blockIdx.x; ++t) s += (uint32_t)a.tstarts[t];
-    before_tile = s;
+    for (int t = (int)threadIdx.x; t < (int)blockIdx.x; t += 256) s += (uint32_t)a.tstarts[t];
+    const uint32_t ex = block_excl_sum(s, sh);
+    if (threadIdx.x == 255) before_tile = ex + s;
+    __syncthreads();
   }
-  __syncthreads();
   uint32_t run = before_tile;
 #pragma unroll
   for (int j = 0; j < DG_TILE / 256; ++j) {
@@ -435,18 +464,4 @@ __global__ void __launch_bounds__(256) k_dg_emit(const DgArgs a) {
     __syncthreads();
   }
   if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) a.ctl[4] = (int32_t)run;
-}
-
-template <int N>
-__global__ void __launch_bounds__(256) k_dg_count_starts(const DgArgs a) {
-  __shared__ uint32_t sh[8];
-  const int executables = a.ctl[3];
-  const int t0 = blockIdx.x * DG_TILE;
-  uint32_t total = 0;
-  for (int j = 0; j < DG_TILE / 256; ++j) {
-    const int p = t0 + j * 256 + threadIdx.x;
-    total += dg_starts<N>(a, p, executables);
-  }
-  const uint32_t ex = block_excl_sum(total, sh);
-  if (threadIdx.x == 255) a.tstarts[blockIdx.x] = (int32_t)(ex + total);
 }

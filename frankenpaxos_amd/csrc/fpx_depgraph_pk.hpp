@@ -1,5 +1,6 @@
-// fpx_depgraph_pk.hpp -- the device dependency graph's PACKED path (round 5): the algorithm of fpx_depgraph_dev.hpp with
-// half the bytes per vertex and one kernel less per closure round.  Included by fpx_epaxos.hip behind fpx_depgraph_dev.hpp.
+// fpx_depgraph_pk.hpp -- the device dependency graph's PACKED form (round 5): the closure rounds and the keys of
+// fpx_depgraph_dev.hpp with half the bytes per vertex and one kernel less per closure round.  Included by fpx_epaxos.hip
+// behind fpx_depgraph_dev.hpp.
 //
 // What bounds the closure rounds is HBM traffic: every round every vertex reads its closure, gathers n prefix rows and
 // writes a row or two (fpx_depgraph_dev.hpp: 8 ints = 32 bytes per row, a prefix kernel and a gather kernel per round:
@@ -11,7 +12,9 @@
 //     it): the gather kernel itself scans its workgroup's new closures for the next round (`lp`, `bt`), a one-workgroup-
 //     per-column kernel turns the workgroup totals into carries (`cy`: 4096 rows, L2-resident), and a gather reads
 //     lp[j] and cy[j / 256].  No separate prefix pass over the vertices: 128 B per vertex and round.
-// Everything else -- cycle test, keys, the two sorts, component starts -- is the wide path's, on packed rows.
+// The cycle test and the keys are the wide form's rule on packed rows (k_dp_keys).  Everything behind them -- the two
+// sorts, k_dg_rekey, component starts, k_dg_emit, k_dg_publish -- and the host driver are the SAME code for both forms
+// (fpx_depgraph_dev.hpp, dg_run in fpx_epaxos.hip): they read the closures through DpClosures below.
 #pragma once
 
 constexpr int PK_BITS = 21;
@@ -37,33 +40,24 @@ __device__ __forceinline__ uint32_t pk_hash(const ulonglong2 r, int bits) {
   return h >> (32 - bits);
 }
 
-struct DpArgs {
-  int m, n, stride;
-  int32_t first[8], count[8], base[8];   // per column: first id, instances, first vertex
+struct DpArgs : DgCommon {
   int32_t nblk[8], blk_base[8];          // per column: workgroups of 256 vertices, the first one's index
   int nblocks;
-  const int32_t* leader;
-  const int32_t* number;
-  const int32_t* packed;
-  const uint8_t* mask;
-  int32_t* msg_of;                       // [m]
   ulonglong2* direct;                    // [m] direct covers
   ulonglong2* clo;                       // [m] closures
   ulonglong2* lp[2];                     // [m] inclusive prefix max of the closures INSIDE the vertex's workgroup
   ulonglong2* bt[2];                     // [nblocks] the workgroups' maxima
   ulonglong2* cy[2];                     // [nblocks] max over the workgroups of the column BEFORE this one
-  uint2* pairs;
-  uint2* pairs2;
-  uint32_t* key32;
-  int32_t* tstarts;
-  int32_t* belig;                        // [ceil(m / 256)] executable vertices per workgroup of k_dp_keys (summed by k_dp_rekey)
-  int32_t* ctl;                          // as DgArgs::ctl
-  volatile int32_t* host;
-  int32_t seq;
-  int32_t count_moved;
-  int32_t hash_bits;                     // as DgArgs::hash_bits
-  int32_t* order;
-  int32_t* comp;
+};
+
+// the packed closures as the shared kernels behind the sorts read them (DgClosures of fpx_depgraph_dev.hpp)
+struct DpClosures {
+  const ulonglong2* clo;
+  __device__ __forceinline__ bool equal(uint32_t u, uint32_t v) const {
+    const ulonglong2 cu = clo[u], cv = clo[v];
+    return cu.x == cv.x && cu.y == cv.y;
+  }
+  __device__ __forceinline__ uint32_t hash(uint32_t u, int bits) const { return pk_hash(clo[u], bits); }
 };
 
 // The gathers of a closure round (and of the cycle test) read rows of OTHER vertices: the prefix row just below each of a
@@ -348,93 +342,6 @@ __global__ void __launch_bounds__(256) k_dp_keys(const DpArgs a) {
     a.pairs[u] = make_uint2(kind == 0u ? pk_hash(cr, a.hash_bits) : 0u, (uint32_t)u);
   }
   // (4096 workgroups adding to ONE word serialise in its L2 channel: ~35 of this kernel's 54 us were that atomic, the same
-  // effect k_validate's round word showed in round 2; each workgroup leaves its count, k_dp_rekey's first workgroup adds them up)
+  // effect k_validate's round word showed in round 2; each workgroup leaves its count, k_dg_rekey's first workgroup adds them up)
   if (threadIdx.x == 0) a.belig[lb] = block_eligible;
-}
-
-__global__ void __launch_bounds__(256) k_dp_rekey(const DpArgs a) {
-  __shared__ uint32_t sh[8];
-  const int p = blockIdx.x * blockDim.x + threadIdx.x;
-  if (p < a.m) a.pairs[p].x = a.key32[a.pairs[p].y];
-  if (blockIdx.x == 0) {  // the number of executables (what k_dp_count_starts / k_dp_emit / k_dp_publish read from ctl[3])
-    const int vblocks = (a.m + 255) >> 8;
-    uint32_t s = 0;
-    for (int b = (int)threadIdx.x; b < vblocks; b += 256) s += (uint32_t)a.belig[b];
-    const uint32_t ex = block_excl_sum(s, sh);
-    if (threadIdx.x == 255) a.ctl[3] = (int32_t)(ex + s);
-  }
-}
-
-// does a component start at position p of the sorted order?  (dg_starts on packed rows)
-__device__ __forceinline__ uint32_t dp_starts(const DpArgs& a, int p, int executables) {
-  if (p >= executables) return 0u;
-  const uint2 e = a.pairs[p];
-  if (e.x % 3u != 0u || p == 0) return 1u;
-  const uint2 f = a.pairs[p - 1];
-  if (f.x != e.x) return 1u;
-  const ulonglong2 ce = a.clo[e.y], cf = a.clo[f.y];
-  if (ce.x == cf.x && ce.y == cf.y) return 0u;
-  if (pk_hash(ce, a.hash_bits) == pk_hash(cf, a.hash_bits)) a.ctl[2] = 1;  // two different closures with one key and one hash: their members may interleave
-  return 1u;
-}
-
-__global__ void __launch_bounds__(256) k_dp_count_starts(const DpArgs a) {
-  __shared__ uint32_t sh[8];
-  const int executables = a.ctl[3];
-  const int t0 = blockIdx.x * DG_TILE;
-  uint32_t total = 0;
-  for (int j = 0; j < DG_TILE / 256; ++j) total += dp_starts(a, t0 + j * 256 + threadIdx.x, executables);
-  const uint32_t ex = block_excl_sum(total, sh);
-  if (threadIdx.x == 255) a.tstarts[blockIdx.x] = (int32_t)(ex + total);
-}
-
-__global__ void __launch_bounds__(256) k_dp_emit(const DpArgs a) {
-  __shared__ uint32_t sh[8];
-  __shared__ uint32_t before_tile;
-  const int executables = a.ctl[3];
-  const int t0 = blockIdx.x * DG_TILE;
-  uint32_t mine[DG_TILE / 256];
-#pragma unroll
-  for (int j = 0; j < DG_TILE / 256; ++j) mine[j] = dp_starts(a, t0 + j * 256 + threadIdx.x, executables);
-  {
-    // the components that start in the tiles before this one: 256 threads add up the tiles' counts (one thread walking up to
-    // 512 of them was ~10 us of the kernel)
-    uint32_t s = 0;
-    for (int t = (int)threadIdx.x; t < (int)blockIdx.x; t += 256) s += (uint32_t)a.tstarts[t];
-    const uint32_t ex = block_excl_sum(s, sh);
-    if (threadIdx.x == 255) before_tile = ex + s;
-    __syncthreads();
-  }
-  uint32_t run = before_tile;
-#pragma unroll
-  for (int j = 0; j < DG_TILE / 256; ++j) {
-    const uint32_t ex = block_excl_sum(mine[j], sh);
-    const int p = t0 + j * 256 + threadIdx.x;
-    if (p < executables) {
-      a.comp[p] = (int32_t)(run + ex + mine[j]) - 1;
-      a.order[p] = a.msg_of[a.pairs[p].y];
-    }
-    __syncthreads();
-    if (threadIdx.x == 255) sh[7] = ex + mine[j];
-    __syncthreads();
-    run += sh[7];
-    __syncthreads();
-  }
-  if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) a.ctl[4] = (int32_t)run;
-}
-
-// last_k: the rounds of the chunk that were enqueued.  [5] = the last of them still moved (another chunk is needed),
-// [6] = how many of them moved something (the next call enqueues one more than that: see dg_execute_packed)
-__global__ void k_dp_publish(const DpArgs a, int last_k) {
-  if (threadIdx.x < 7) {
-    int v = a.ctl[threadIdx.x];
-    if (threadIdx.x == 5) v = a.ctl[8 + last_k];
-    if (threadIdx.x == 6) {
-      v = 0;
-      for (int k = 1; k <= last_k; ++k) v += a.ctl[8 + k] != 0 ? 1 : 0;
-    }
-    a.host[threadIdx.x] = v;
-  }
-  __threadfence_system();
-  if (threadIdx.x == 0) a.host[7] = a.seq;
 }

@@ -1738,158 +1738,105 @@ int dg_hash_bits() {
   return b < 2 ? 2 : b > DG_HASH_BITS ? DG_HASH_BITS : b;
 }
 
-// the packed path of the device dependency graph (fpx_depgraph_pk.hpp): n <= 5, columns of fewer than 2^21 - 2 instances
-template <int N>
-int dg_execute_packed(fpx_epx* e, int m, const int32_t* d_leader, const int32_t* d_number, const int32_t* d_packed, const uint8_t* d_mask,
-                      const int32_t* first, const int32_t* count, int32_t* d_order, int32_t* d_comp, int64_t* nexec, int64_t* ncomp,
-                      int32_t* needs_host) {
-  static_assert(N <= 5, "five 21-bit watermarks per 16-byte row");
-  DpArgs a;
-  memset(&a, 0, sizeof(a));
-  a.m = m, a.n = N, a.stride = fpx_epx_packed_stride(N);
-  long long total = 0;
-  for (int l = 0; l < N; ++l) {
-    a.first[l] = first[l], a.count[l] = count[l], a.base[l] = (int32_t)total;
-    a.nblk[l] = (count[l] + 255) / 256, a.blk_base[l] = a.nblocks;
-    a.nblocks += a.nblk[l], total += count[l];
-  }
-  for (int l = N; l < 8; ++l) a.base[l] = (int32_t)total, a.blk_base[l] = a.nblocks;
-  int rc;
-  const int out_tiles = (m + DG_TILE - 1) / DG_TILE;
-  const size_t nb = (size_t)std::max(a.nblocks, 1);
-  if ((rc = grow(e, &e->dg_msg, (size_t)m * 4))) return rc;
-  if ((rc = grow(e, &e->dg_direct, (size_t)m * 16))) return rc;
-  if ((rc = grow(e, &e->dg_clo, (size_t)m * 16))) return rc;
-  if ((rc = grow(e, &e->dg_pre, (size_t)m * 32))) return rc;
-  if ((rc = grow(e, &e->dg_tmax, nb * 16 * 4 + (size_t)out_tiles * 4 + (size_t)((m + 255) / 256) * 4 + 64))) return rc;
-  if ((rc = grow(e, &e->dg_pairs, (size_t)m * 8))) return rc;
-  if ((rc = grow(e, &e->dg_pairs2, (size_t)m * 8))) return rc;
-  if ((rc = grow(e, &e->dg_key, (size_t)m * 4))) return rc;
-  if ((rc = grow(e, &e->dg_ctl, 256))) return rc;
-  if (!e->kp_flag_dev) return FPX_EHIP;
-  a.leader = d_leader, a.number = d_number, a.packed = d_packed, a.mask = d_mask;
-  a.msg_of = (int32_t*)e->dg_msg.p, a.direct = (ulonglong2*)e->dg_direct.p, a.clo = (ulonglong2*)e->dg_clo.p;
-  a.lp[0] = (ulonglong2*)e->dg_pre.p, a.lp[1] = a.lp[0] + m;
-  a.bt[0] = (ulonglong2*)e->dg_tmax.p, a.bt[1] = a.bt[0] + nb, a.cy[0] = a.bt[1] + nb, a.cy[1] = a.cy[0] + nb;
-  a.tstarts = (int32_t*)(a.cy[1] + nb);
-  a.belig = a.tstarts + out_tiles;
-  a.pairs = (uint2*)e->dg_pairs.p, a.pairs2 = (uint2*)e->dg_pairs2.p, a.ctl = (int32_t*)e->dg_ctl.p;
-  a.key32 = (uint32_t*)e->dg_key.p;
-  a.host = reinterpret_cast<volatile int32_t*>(e->kp_flag_dev + 8);
-  a.order = d_order, a.comp = d_comp;
-  volatile int32_t* host = reinterpret_cast<volatile int32_t*>(e->kp_flag + 8);
-  const int call = (++e->dg_seq) & 0xffff;
-  a.count_moved = getenv("FPX_DG_DEBUG") ? 1 : 0;
-  a.hash_bits = dg_hash_bits();
-  auto wait_for = [&](int round) -> int {
-    const int32_t want = call * 64 + round;
-    for (long spin = 0; spin < 400000000L; ++spin) {
-      if (host[7] == want) return FPX_OK;
-      if ((spin & 0xfffff) == 0xfffff) {
-        const hipError_t q = hipStreamQuery(e->stream);
-        (void)hipGetLastError();
-        if (q != hipErrorNotReady) break;
-      }
-    }
-    EHIP(e, hipStreamSynchronize(e->stream));
-    return host[7] == want ? FPX_OK : FPX_EHIP;
-  };
-  EHIP(e, hipMemsetAsync(a.msg_of, 0xFF, (size_t)m * 4, e->stream));
-  EHIP(e, hipMemsetAsync(a.ctl, 0, 256, e->stream));
-  const int grid = (m + 255) / 256;
-  hipLaunchKernelGGL((k_dp_scatter<N>), dim3(grid), dim3(256), 0, e->stream, a);
-  hipLaunchKernelGGL((k_dp_scan0<N>), dim3(dp_grid(a.nblocks)), dim3(256), 0, e->stream, a);
-  hipLaunchKernelGGL((k_dp_carry<N>), dim3(N), dim3(1024), 0, e->stream, a, 0, 1);
-  int cur = 0, executables = 0;
-  for (int chunk = 0;; ++chunk) {
-    if (chunk > 0) EHIP(e, hipMemsetAsync(a.ctl + 8, 0, (DG_ROUNDS + 1) * 4, e->stream));
-    // How many rounds to enqueue: a round that finds "the one before moved nothing" leaves at its first instruction, but it
-    // is still a launch (and its carry kernel another): ~8 us per skipped round, four of them per FIFO tick.  The first
-    // chunk enqueues one round more than moved something in the context's previous call (ticks of one deployment need the
-    // same depth, 4 with FIFO channels, 7 - 8 with reordering ones); a tick that needs more gets full chunks as before.
-    const int rounds = chunk == 0 ? std::max(2, std::min(DG_ROUNDS, e->dg_rounds_hint)) : DG_ROUNDS;
-    for (int k = 1; k <= rounds; ++k) {
-      // round k gathers from half `cur` and leaves its scan in the other half.  (A skipped round does not flip anything on
-      // the device, but after the round that moved nothing both halves hold the same, final values.)
-      hipLaunchKernelGGL((k_dp_relax<N>), dim3(dp_grid(a.nblocks)), dim3(256), 0, e->stream, a, cur, k);
-      hipLaunchKernelGGL((k_dp_carry<N>), dim3(N), dim3(1024), 0, e->stream, a, cur ^ 1, k);
-      cur ^= 1;
-    }
-    // (ctl[3], the executables, is WRITTEN by the rekey kernel's first workgroup since round 6 and ctl[4], the components,
-    // by the emit kernel's last: nothing accumulates in them any more, so nothing has to be cleared in front of the keys)
-    hipLaunchKernelGGL((k_dp_keys<N>), dim3(dp_grid(grid)), dim3(256), 0, e->stream, a);
-    uint2* sorted = radix_sort_pairs(e, 1, m, (unsigned)a.hash_bits, a.pairs, a.pairs2, nullptr, &rc, nullptr, nullptr);
-    if (rc) return rc;
-    if (sorted != a.pairs) std::swap(a.pairs, a.pairs2);
-    hipLaunchKernelGGL(k_dp_rekey, dim3(grid), dim3(256), 0, e->stream, a);
-    unsigned key_bits = 2;
-    while (((1ull << key_bits) - 1) <= 3ull * (unsigned long long)m + 2) ++key_bits;
-    sorted = radix_sort_pairs(e, 1, m, key_bits, a.pairs, a.pairs2, nullptr, &rc, nullptr, nullptr);
-    if (rc) return rc;
-    if (sorted != a.pairs) std::swap(a.pairs, a.pairs2);
-    hipLaunchKernelGGL(k_dp_count_starts, dim3(out_tiles), dim3(256), 0, e->stream, a);
-    hipLaunchKernelGGL(k_dp_emit, dim3(out_tiles), dim3(256), 0, e->stream, a);
-    a.seq = call * 64 + (chunk & 31) + 1;
-    hipLaunchKernelGGL(k_dp_publish, dim3(1), dim3(64), 0, e->stream, a, rounds);
-    if ((rc = wait_for((chunk & 31) + 1))) return rc;
-    if (host[1] != 0) return FPX_EINVAL;
-    e->dg_rounds_hint = host[5] != 0 ? DG_ROUNDS : host[6] + 1;
-    if (a.count_moved) {
-      int32_t dbg[64];
-      EHIP(e, hipMemcpy(dbg, a.ctl, sizeof(dbg), hipMemcpyDeviceToHost));
-      fprintf(stderr, "libfpx: depgraph (packed) chunk %d, vertices moved per round:", chunk);
-      for (int k = 1; k <= DG_ROUNDS; ++k) fprintf(stderr, " %d", dbg[24 + k]);
-      fprintf(stderr, "\n");
-    }
-    executables = host[3];
-    if (host[5] == 0) break;
-    if (chunk >= 6) return FPX_EHIP;
-  }
-  if (nexec) *nexec = executables;
-  if (ncomp) *ncomp = executables > 0 ? host[4] : 0;
-  if (needs_host) *needs_host = host[2];
-  return launch_check(e);
-}
+// What a form of the closure rounds brings to dg_run: its argument struct `a` (dg_run fills the DgCommon part), its row
+// buffers, the launches in front of the first round and those of round k, its keys kernel, and its closures as the
+// kernels behind the sorts read them.
 
-// device dependency-graph execution of one tick's commits (fpx_depgraph_dev.hpp)
+// the wide form (fpx_depgraph_dev.hpp): 32-byte rows, every n and every column length
 template <int N>
-int dg_execute(fpx_epx* e, int m, const int32_t* d_leader, const int32_t* d_number, const int32_t* d_packed, const uint8_t* d_mask,
-               const int32_t* first, const int32_t* count, int32_t* d_order, int32_t* d_comp, int64_t* nexec, int64_t* ncomp,
-               int32_t* needs_host) {
-  constexpr int NP = DgRow<N>::NP;
-  DgArgs a;
-  memset(&a, 0, sizeof(a));
-  a.m = m, a.n = N, a.stride = fpx_epx_packed_stride(N);
-  long long total = 0;
-  for (int l = 0; l < N; ++l) {
-    if (first[l] < 0 || count[l] < 0) return FPX_EINVAL;
-    a.first[l] = first[l], a.count[l] = count[l], a.base[l] = (int32_t)total;
-    a.tiles[l] = (count[l] + DG_TILE - 1) / DG_TILE, a.tile_base[l] = a.ntiles;
-    a.ntiles += a.tiles[l], total += count[l];
+struct DgWide {
+  static constexpr int NP = DgRow<N>::NP;
+  static constexpr const char* name = "wide";
+  DgArgs a{};
+  // sizes and carves the rows; *behind = the `extra` bytes of dg_tmax behind the form's own
+  int rows(fpx_epx* e, size_t extra, int32_t** behind) {
+    for (int l = 0; l < N; ++l) a.tiles[l] = (a.count[l] + DG_TILE - 1) / DG_TILE, a.tile_base[l] = a.ntiles, a.ntiles += a.tiles[l];
+    for (int l = N; l < 8; ++l) a.tile_base[l] = a.ntiles;
+    int rc;
+    if ((rc = grow(e, &e->dg_direct, (size_t)a.m * NP * 4))) return rc;
+    if ((rc = grow(e, &e->dg_clo, (size_t)a.m * NP * 4))) return rc;
+    if ((rc = grow(e, &e->dg_pre, (size_t)a.m * NP * 4))) return rc;
+    if ((rc = grow(e, &e->dg_tmax, (size_t)DG_SUB * a.ntiles * NP * 4 + extra))) return rc;
+    a.direct = (int32_t*)e->dg_direct.p, a.clo = (int32_t*)e->dg_clo.p, a.pre = (int32_t*)e->dg_pre.p;
+    a.tmax = (int32_t*)e->dg_tmax.p, *behind = a.tmax + (size_t)DG_SUB * a.ntiles * NP;
+    return FPX_OK;
   }
-  for (int l = N; l < 8; ++l) a.base[l] = (int32_t)total, a.tile_base[l] = a.ntiles;
-  if (total != m) return FPX_EINVAL;  // the columns are dense: every instance first[l] .. first[l] + count[l] - 1, once
-  if constexpr (N <= 5) {
-    bool fits = !getenv("FPX_DG_WIDE");
-    for (int l = 0; l < N; ++l) fits = fits && count[l] <= PK_MAX_COUNT;
-    if (fits) return dg_execute_packed<N>(e, m, d_leader, d_number, d_packed, d_mask, first, count, d_order, d_comp, nexec, ncomp, needs_host);
+  void before_rounds(hipStream_t st, int grid) {
+    hipLaunchKernelGGL((k_dg_scatter<N>), dim3(grid), dim3(256), 0, st, a);
+    // round 1 scans from the direct covers' tile maxima; every later round from what the gather before it folded
+    hipLaunchKernelGGL((k_dg_tilemax<N>), dim3(a.ntiles), dim3(256), 0, st, a);
+  }
+  void round(hipStream_t st, int k) {
+    hipLaunchKernelGGL((k_dg_prefix<N>), dim3(a.ntiles), dim3(256), 0, st, a, k);
+    hipLaunchKernelGGL((k_dg_relax<N>), dim3(a.ntiles * DG_SUB), dim3(256), 0, st, a, k);
+  }
+  void keys(hipStream_t st, int grid) { hipLaunchKernelGGL((k_dg_keys<N>), dim3(grid), dim3(256), 0, st, a); }
+  DgClosures<N> closures() const { return {a.clo}; }
+};
+
+// the packed form (fpx_depgraph_pk.hpp): 16-byte rows, n <= 5 and columns of at most PK_MAX_COUNT instances
+template <int N>
+struct DgPacked {
+  static_assert(N <= 5, "five 21-bit watermarks per 16-byte row");
+  static constexpr const char* name = "packed";
+  DpArgs a{};
+  int cur = 0;  // the half of lp / bt / cy the next round gathers from
+  int rows(fpx_epx* e, size_t extra, int32_t** behind) {
+    for (int l = 0; l < N; ++l) a.nblk[l] = (a.count[l] + 255) / 256, a.blk_base[l] = a.nblocks, a.nblocks += a.nblk[l];
+    for (int l = N; l < 8; ++l) a.blk_base[l] = a.nblocks;
+    const size_t nb = (size_t)std::max(a.nblocks, 1);
+    int rc;
+    if ((rc = grow(e, &e->dg_direct, (size_t)a.m * 16))) return rc;
+    if ((rc = grow(e, &e->dg_clo, (size_t)a.m * 16))) return rc;
+    if ((rc = grow(e, &e->dg_pre, (size_t)a.m * 32))) return rc;
+    if ((rc = grow(e, &e->dg_tmax, nb * 16 * 4 + extra))) return rc;
+    a.direct = (ulonglong2*)e->dg_direct.p, a.clo = (ulonglong2*)e->dg_clo.p;
+    a.lp[0] = (ulonglong2*)e->dg_pre.p, a.lp[1] = a.lp[0] + a.m;
+    a.bt[0] = (ulonglong2*)e->dg_tmax.p, a.bt[1] = a.bt[0] + nb, a.cy[0] = a.bt[1] + nb, a.cy[1] = a.cy[0] + nb;
+    *behind = (int32_t*)(a.cy[1] + nb);
+    return FPX_OK;
+  }
+  void before_rounds(hipStream_t st, int grid) {
+    hipLaunchKernelGGL((k_dp_scatter<N>), dim3(grid), dim3(256), 0, st, a);
+    hipLaunchKernelGGL((k_dp_scan0<N>), dim3(dp_grid(a.nblocks)), dim3(256), 0, st, a);
+    hipLaunchKernelGGL((k_dp_carry<N>), dim3(N), dim3(1024), 0, st, a, 0, 1);
+  }
+  void round(hipStream_t st, int k) {
+    // round k gathers from half `cur` and leaves its scan in the other half.  (A skipped round does not flip anything on
+    // the device, but after the round that moved nothing both halves hold the same, final values.)
+    hipLaunchKernelGGL((k_dp_relax<N>), dim3(dp_grid(a.nblocks)), dim3(256), 0, st, a, cur, k);
+    hipLaunchKernelGGL((k_dp_carry<N>), dim3(N), dim3(1024), 0, st, a, cur ^ 1, k);
+    cur ^= 1;
+  }
+  void keys(hipStream_t st, int grid) { hipLaunchKernelGGL((k_dp_keys<N>), dim3(dp_grid(grid)), dim3(256), 0, st, a); }
+  DpClosures closures() const { return {a.clo}; }
+};
+
+// one tick through one form: the closure rounds in chunks until nothing moves, keys, the two sorts, component starts
+template <int N, class Form>
+int dg_run(fpx_epx* e, Form& form, int m, const int32_t* d_leader, const int32_t* d_number, const int32_t* d_packed, const uint8_t* d_mask,
+           const int32_t* first, const int32_t* count, int32_t* d_order, int32_t* d_comp, int64_t* nexec, int64_t* ncomp,
+           int32_t* needs_host) {
+  using Clo = decltype(form.closures());
+  DgCommon& a = form.a;
+  a.m = m, a.n = N, a.stride = fpx_epx_packed_stride(N);
+  for (int l = 0, base = 0; l < 8; base += a.count[l], ++l) {  // (the columns behind N are empty: their base is m)
+    if (l < N) a.first[l] = first[l], a.count[l] = count[l];
+    a.base[l] = base;
   }
   int rc;
   const int out_tiles = (m + DG_TILE - 1) / DG_TILE;
+  const int grid = (m + 255) / 256;
+  if ((rc = form.rows(e, ((size_t)out_tiles + (size_t)grid) * 4 + 64, &a.tstarts))) return rc;
+  a.belig = a.tstarts + out_tiles;
   if ((rc = grow(e, &e->dg_msg, (size_t)m * 4))) return rc;
-  if ((rc = grow(e, &e->dg_direct, (size_t)m * NP * 4))) return rc;
-  if ((rc = grow(e, &e->dg_clo, (size_t)m * NP * 4))) return rc;
-  if ((rc = grow(e, &e->dg_pre, (size_t)m * NP * 4))) return rc;
-  if ((rc = grow(e, &e->dg_tmax, ((size_t)DG_SUB * a.ntiles * NP + out_tiles + (size_t)((m + 255) / 256)) * 4 + 64))) return rc;
   if ((rc = grow(e, &e->dg_pairs, (size_t)m * 8))) return rc;
   if ((rc = grow(e, &e->dg_pairs2, (size_t)m * 8))) return rc;
   if ((rc = grow(e, &e->dg_key, (size_t)m * 4))) return rc;
   if ((rc = grow(e, &e->dg_ctl, 256))) return rc;
   if (!e->kp_flag_dev) return FPX_EHIP;
   a.leader = d_leader, a.number = d_number, a.packed = d_packed, a.mask = d_mask;
-  a.msg_of = (int32_t*)e->dg_msg.p, a.direct = (int32_t*)e->dg_direct.p, a.clo = (int32_t*)e->dg_clo.p, a.pre = (int32_t*)e->dg_pre.p;
-  a.tmax = (int32_t*)e->dg_tmax.p, a.tstarts = a.tmax + (size_t)DG_SUB * a.ntiles * NP;
-  a.belig = a.tstarts + out_tiles;
+  a.msg_of = (int32_t*)e->dg_msg.p;
   a.pairs = (uint2*)e->dg_pairs.p, a.pairs2 = (uint2*)e->dg_pairs2.p, a.ctl = (int32_t*)e->dg_ctl.p;
   a.key32 = (uint32_t*)e->dg_key.p;
   a.host = reinterpret_cast<volatile int32_t*>(e->kp_flag_dev + 8);  // the second half of the page-locked line
@@ -1898,8 +1845,8 @@ int dg_execute(fpx_epx* e, int m, const int32_t* d_leader, const int32_t* d_numb
   const int call = (++e->dg_seq) & 0xffff;
   a.count_moved = getenv("FPX_DG_DEBUG") ? 1 : 0;
   a.hash_bits = dg_hash_bits();
-  auto wait_for = [&](int round) -> int {
-    const int32_t want = call * 64 + round;
+  auto wait_for = [&](int chunk) -> int {
+    const int32_t want = call * 64 + chunk;
     for (long spin = 0; spin < 400000000L; ++spin) {
       if (host[7] == want) return FPX_OK;
       if ((spin & 0xfffff) == 0xfffff) {  // now and then: did the stream die?  (hipErrorNotReady is what a live one answers;
@@ -1913,23 +1860,23 @@ int dg_execute(fpx_epx* e, int m, const int32_t* d_leader, const int32_t* d_numb
   };
   EHIP(e, hipMemsetAsync(a.msg_of, 0xFF, (size_t)m * 4, e->stream));
   EHIP(e, hipMemsetAsync(a.ctl, 0, 256, e->stream));
-  const int grid = (m + 255) / 256;
-  hipLaunchKernelGGL((k_dg_scatter<N>), dim3(grid), dim3(256), 0, e->stream, a);
-  // round 1 scans from the direct covers' tile maxima; every later round from what the gather before it folded
-  hipLaunchKernelGGL((k_dg_tilemax<N>), dim3(a.ntiles), dim3(256), 0, e->stream, a);
-  int round = 0, executables = 0;
+  form.before_rounds(e->stream, grid);
+  const Clo clo = form.closures();
+  int enqueued = 0, executables = 0;
   for (int chunk = 0;; ++chunk) {
-    // DG_ROUNDS closure rounds at once: a round returns at its first instruction when the one before it moved nothing,
-    // and everything behind them is enqueued right away -- one host read per chunk, and one chunk covers 2^8 hops
+    // A chunk of closure rounds at once: a round returns at its first instruction when the one before it moved nothing,
+    // and everything behind them is enqueued right away -- one host read per chunk, and a full chunk covers 2^8 hops
     if (chunk > 0) EHIP(e, hipMemsetAsync(a.ctl + 8, 0, (DG_ROUNDS + 1) * 4, e->stream));
-    for (int k = 1; k <= DG_ROUNDS; ++k) {
-      ++round;
-      hipLaunchKernelGGL((k_dg_prefix<N>), dim3(a.ntiles), dim3(256), 0, e->stream, a, round, k);
-      hipLaunchKernelGGL((k_dg_relax<N>), dim3(a.ntiles * DG_SUB), dim3(256), 0, e->stream, a, round, k);
-    }
+    // How many rounds to enqueue: a round that finds "the one before moved nothing" leaves at its first instruction, but it
+    // is still a launch (and its second kernel another): ~8 us per skipped round, four of them per FIFO tick.  The first
+    // chunk enqueues one round more than moved something in the context's previous call (ticks of one deployment need the
+    // same depth, 4 with FIFO channels, 7 - 8 with reordering ones); a tick that needs more gets full chunks as before.
+    const int rounds = chunk == 0 ? std::max(2, std::min(DG_ROUNDS, e->dg_rounds_hint)) : DG_ROUNDS;
+    for (int k = 1; k <= rounds; ++k) form.round(e->stream, k);
+    enqueued += rounds;
     // (ctl[3], the executables, is WRITTEN by the rekey kernel's first workgroup since round 6 and ctl[4], the components,
     // by the emit kernel's last: nothing accumulates in them any more, so nothing has to be cleared in front of the keys)
-    hipLaunchKernelGGL((k_dg_keys<N>), dim3(grid), dim3(256), 0, e->stream, a);
+    form.keys(e->stream, grid);
     // least significant first: the closures' hashes, then (stable) the closure sums and kinds
     uint2* sorted = radix_sort_pairs(e, 1, m, (unsigned)a.hash_bits, a.pairs, a.pairs2, nullptr, &rc, nullptr, nullptr);
     if (rc) return rc;
@@ -1941,27 +1888,51 @@ int dg_execute(fpx_epx* e, int m, const int32_t* d_leader, const int32_t* d_numb
     if (rc) return rc;
     if (sorted != a.pairs) std::swap(a.pairs, a.pairs2);
     // (the number of executables stays on the device: both kernels cover all m positions and leave at once beyond it)
-    hipLaunchKernelGGL((k_dg_count_starts<N>), dim3(out_tiles), dim3(256), 0, e->stream, a);
-    hipLaunchKernelGGL((k_dg_emit<N>), dim3(out_tiles), dim3(256), 0, e->stream, a);
+    hipLaunchKernelGGL((k_dg_count_starts<Clo>), dim3(out_tiles), dim3(256), 0, e->stream, a, clo);
+    hipLaunchKernelGGL((k_dg_emit<Clo>), dim3(out_tiles), dim3(256), 0, e->stream, a, clo);
     a.seq = call * 64 + (chunk & 31) + 1;
-    hipLaunchKernelGGL(k_dg_publish, dim3(1), dim3(64), 0, e->stream, a, chunk);
+    hipLaunchKernelGGL(k_dg_publish, dim3(1), dim3(64), 0, e->stream, a, rounds);
     if ((rc = wait_for((chunk & 31) + 1))) return rc;
     if (host[1] != 0) return FPX_EINVAL;        // an instance outside its column, twice, or missing
+    e->dg_rounds_hint = host[5] != 0 ? DG_ROUNDS : host[6] + 1;
     if (a.count_moved) {
       int32_t dbg[64];
       EHIP(e, hipMemcpy(dbg, a.ctl, sizeof(dbg), hipMemcpyDeviceToHost));
-      fprintf(stderr, "libfpx: depgraph chunk %d, vertices moved per round:", chunk);
+      fprintf(stderr, "libfpx: depgraph (%s) chunk %d, vertices moved per round:", Form::name, chunk);
       for (int k = 1; k <= DG_ROUNDS; ++k) fprintf(stderr, " %d", dbg[24 + k]);
       fprintf(stderr, "\n");
     }
     executables = host[3];
-    if (host[5] == 0) break;                    // the chunk's last round moved nothing (or never ran): converged
-    if (round >= 48) return FPX_EHIP;           // (a round doubles the hops covered: 2^48 hops do not exist)
+    if (host[5] == 0) break;                    // the chunk's last round moved nothing: converged
+    if (enqueued >= 48) return FPX_EHIP;        // (a round doubles the hops covered: 2^48 hops do not exist)
   }
   if (nexec) *nexec = executables;
   if (ncomp) *ncomp = executables > 0 ? host[4] : 0;
   if (needs_host) *needs_host = host[2];
   return launch_check(e);
+}
+
+// device dependency-graph execution of one tick's commits (fpx_depgraph_dev.hpp): checks the columns, chooses the form
+template <int N>
+int dg_execute(fpx_epx* e, int m, const int32_t* d_leader, const int32_t* d_number, const int32_t* d_packed, const uint8_t* d_mask,
+               const int32_t* first, const int32_t* count, int32_t* d_order, int32_t* d_comp, int64_t* nexec, int64_t* ncomp,
+               int32_t* needs_host) {
+  long long total = 0;
+  for (int l = 0; l < N; ++l) {
+    if (first[l] < 0 || count[l] < 0) return FPX_EINVAL;
+    total += count[l];
+  }
+  if (total != m) return FPX_EINVAL;  // the columns are dense: every instance first[l] .. first[l] + count[l] - 1, once
+  if constexpr (N <= 5) {
+    bool fits = !getenv("FPX_DG_WIDE");
+    for (int l = 0; l < N; ++l) fits = fits && count[l] <= PK_MAX_COUNT;
+    if (fits) {
+      DgPacked<N> form;
+      return dg_run<N>(e, form, m, d_leader, d_number, d_packed, d_mask, first, count, d_order, d_comp, nexec, ncomp, needs_host);
+    }
+  }
+  DgWide<N> form;
+  return dg_run<N>(e, form, m, d_leader, d_number, d_packed, d_mask, first, count, d_order, d_comp, nexec, ncomp, needs_host);
 }
 
 }  // namespace

@@ -136,8 +136,10 @@ def run_both(n, leader, number, first, count, deps, own, committed=None, kind="t
 @pytest.fixture(params=["packed", "wide"])
 def dg_path(request, monkeypatch):
     """fpx_epx_execute_dev has two forms of its closure rounds: 16-byte rows with the prefix kept per workgroup
-    (csrc/fpx_depgraph_pk.hpp; n <= 5) and 32-byte rows with a prefix pass per round (fpx_depgraph_dev.hpp; every n).
-    FPX_DG_WIDE=1 sends everything the second way: results must not depend on it"""
+    (csrc/fpx_depgraph_pk.hpp: k_dp_*; n <= 5) and 32-byte rows with a prefix pass per round (fpx_depgraph_dev.hpp:
+    k_dg_scatter .. k_dg_keys; every n).  One host driver (dg_run in fpx_epaxos.hip) runs either, and what follows the keys
+    -- the sorts, k_dg_rekey, k_dg_count_starts, k_dg_emit, k_dg_publish -- is one set of kernels that reads the closures
+    of either.  FPX_DG_WIDE=1 sends everything the second way: results must not depend on it"""
     if request.param == "wide":
         monkeypatch.setenv("FPX_DG_WIDE", "1")
     else:
