@@ -278,6 +278,79 @@ class Context:
             raise FpxError(st, "fpx_wire_decode_%s_dev" % which)
         return out
 
+    def _wire_encode_out(self, device, cap, max_msgs, out, out_offsets, totals):
+        import torch
+        if out is None:
+            out = torch.empty(max(int(cap), 1), dtype=torch.uint8, device=device)
+        if out_offsets is None:
+            out_offsets = torch.empty(int(max_msgs) + 1, dtype=torch.int64, device=device)
+        if totals is None:
+            totals = torch.empty(2, dtype=torch.int64, device=device)
+        return out, out_offsets, totals
+
+    def wire_encode_chosen_dev(self, slot, value_off, value_len, values, emit=None, is_noop=None, cap=None, out=None,
+                               out_offsets=None, totals=None, values_len=None):
+        """ReplicaInbound{Chosen} of every record with emit[i] != 0 (None: all), back to back: slot / value_len int32,
+        value_off int64, is_noop int32, emit uint8 CUDA tensors as wire_decode_dev and phase2_fused_dev leave them; values =
+        the tick's bytes (uint8 CUDA tensor).  Returns CUDA tensors (out, out_offsets[n + 1], totals[2] = count, bytes
+        needed), enqueued on the context's stream; FPX_ECAPACITY / FPX_EINVAL surface at sync() and abort nothing.
+        cap: capacity in bytes (default: out.numel(), or values.numel() + 24 n when out is None)."""
+        n = slot.numel()
+        nv = values.numel() if values_len is None else values_len
+        if cap is None:
+            cap = out.numel() if out is not None else nv + 24 * n
+        out, out_offsets, totals = self._wire_encode_out(slot.device, cap, n, out, out_offsets, totals)
+        from . import wire
+        st = wire._L().fpx_wire_encode_replica_chosen_dev(self._h, n, _dp(emit), _dp(slot), _dp(is_noop), _dp(values), nv,
+                                                          _dp(value_off), _dp(value_len), _dp(out), cap, _dp(out_offsets),
+                                                          _dp(totals))
+        if st:
+            raise FpxError(st, "fpx_wire_encode_replica_chosen_dev")
+        return out, out_offsets, totals
+
+    def wire_encode_phase2b_batch_dev(self, slot, round_, vote_bits, group_of_slot=None, grid_cols=0, dialect=0, cap=None,
+                                      max_msgs=None, out=None, out_offsets=None, totals=None):
+        """ProxyLeaderInbound{Phase2b} per set bit of vote_bits (n x 4 words; int64 or uint64 CUDA tensor), as
+        wire.encode_phase2b_batch on the host.  Defaults: max_msgs = 256 n, cap = 46 max_msgs (no Phase2b is longer)."""
+        n = slot.numel()
+        if max_msgs is None:
+            max_msgs = out_offsets.numel() - 1 if out_offsets is not None else 256 * n
+        if cap is None:
+            cap = out.numel() if out is not None else 46 * max_msgs
+        out, out_offsets, totals = self._wire_encode_out(slot.device, cap, max_msgs, out, out_offsets, totals)
+        from . import wire
+        st = wire._L().fpx_wire_encode_phase2b_batch_dev(self._h, dialect, n, _dp(slot), _dp(round_), _dp(vote_bits),
+                                                         _dp(group_of_slot), grid_cols, _dp(out), cap, _dp(out_offsets),
+                                                         max_msgs, _dp(totals))
+        if st:
+            raise FpxError(st, "fpx_wire_encode_phase2b_batch_dev")
+        return out, out_offsets, totals
+
+    def wire_encode_leader_nack_dev(self, nack_round, dialect=0, cap=None, max_msgs=None, out=None, out_offsets=None,
+                                    totals=None):
+        """LeaderInbound{Nack} of every record with nack_round[i] >= 0 (int32 CUDA tensor, as K1 / K3 report them)."""
+        n = nack_round.numel()
+        if max_msgs is None:
+            max_msgs = out_offsets.numel() - 1 if out_offsets is not None else n
+        if cap is None:
+            cap = out.numel() if out is not None else 13 * max_msgs
+        out, out_offsets, totals = self._wire_encode_out(nack_round.device, cap, max_msgs, out, out_offsets, totals)
+        from . import wire
+        st = wire._L().fpx_wire_encode_leader_nack_dev(self._h, dialect, n, _dp(nack_round), _dp(out), cap,
+                                                       _dp(out_offsets), max_msgs, _dp(totals))
+        if st:
+            raise FpxError(st, "fpx_wire_encode_leader_nack_dev")
+        return out, out_offsets, totals
+
+    def wire_phase2_tick(self, in_ptr, in_len, in_offsets_ptr, n, out_ptr, out_cap, out_offsets_ptr, nack_round_ptr=None):
+        """fpx_wire_phase2_tick on raw addresses of page-locked buffers (host_alloc): returns (status, count,
+        bytes_needed, bad_index); the status is returned, not raised -- FPX_ECAPACITY is an answer here."""
+        from . import wire
+        count, need, bad = C.c_int64(0), C.c_int64(0), C.c_int32(-1)
+        st = wire._L().fpx_wire_phase2_tick(self._h, in_ptr, in_len, in_offsets_ptr, n, out_ptr, out_cap, out_offsets_ptr,
+                                            C.byref(count), nack_round_ptr, C.byref(need), C.byref(bad))
+        return st, count.value, need.value, bad.value
+
     # ---- multi-GPU: RCCL communicator behind the C ABI (fpx_comm_*) ----------------------------------
     def comm_create(self, unique_id, rank, world):
         """collective over the `world` contexts (one per GPU): unique_id = comm_unique_id() of one rank"""

@@ -22,6 +22,7 @@
 #include "fpx_kernels.hpp"
 #include "fpx_ranges.hpp"
 #include "fpx_wire_dev.hpp"
+#include "fpx_wire_enc_dev.hpp"
 #include "../../include/fpx_wire.h"
 
 using namespace fpx;
@@ -144,6 +145,10 @@ struct fpx_ctx {
   int64_t census[FPX_CENSUS_WORDS] = {};
   int census_cell = 0;                       // the cell of the vote launch just enqueued
   int census_pending = 0, census_carry = 0;  // the cells of the launches whose folds are pending_fin / carry_fin
+  DevBuf d_enc;   // the device encoders' workgroup sums (fpx_wire_encode_*_dev)
+  // fpx_wire_phase2_tick: the tick's bytes and offsets, its decoded records (kind, slot, round, is_noop, value_len, value_id,
+  // value_off), the reply's bytes, offsets and totals
+  DevBuf w_buf, w_off, w_rec[7], w_out, w_ooff, w_tot;
   DevBuf d_band;  // [num_leader_groups] marks: the leader groups with a range in the step being checked
   // multi-GPU (fpx_comm_*): one communicator per context, rank = this context's GPU
   RcclComm comm = nullptr;
@@ -973,7 +978,10 @@ void free_state(fpx_ctx* ctx) {
   DevBuf* bs[] = {&ctx->d_slot,   &ctx->d_round, &ctx->d_value, &ctx->d_target, &ctx->d_bits_a, &ctx->d_bits_b,
                   &ctx->d_i32_a,  &ctx->d_i32_b, &ctx->d_i32_c, &ctx->d_u8,     &ctx->d_scratch,
                   &rs.start,      &rs.end,       &rs.round,     &rs.entry,      &rs.nack_round, &rs.is_new,
-                  &rs.chosen,     &rs.target,    &rs.votes,     &rs.nacks};
+                  &rs.chosen,     &rs.target,    &rs.votes,     &rs.nacks,
+                  &ctx->d_enc,    &ctx->w_buf,   &ctx->w_off,   &ctx->w_out,    &ctx->w_ooff,   &ctx->w_tot,
+                  &ctx->w_rec[0], &ctx->w_rec[1], &ctx->w_rec[2], &ctx->w_rec[3], &ctx->w_rec[4], &ctx->w_rec[5],
+                  &ctx->w_rec[6]};
   for (DevBuf* b : bs)
     if (b->p) (void)hipFree(b->p);
   for (hipEvent_t e : ctx->ev) (void)hipEventDestroy(e);
@@ -1118,15 +1126,18 @@ int d2h(fpx_ctx* ctx, T* dst, const DevBuf& b, size_t count) {
 // ---- host batches: stage, cut into runs, run, copy back ----------------------------------------------------------
 // The arrays of a host batch: `bytes` per message in the caller's array and in its staging buffer.  An input whose
 // array is NULL is neither uploaded nor staged; every output is staged, and downloaded when its array is not NULL.
+// `extra`: bytes on top of n * bytes (a tick's byte buffer is not per message; its offsets are n + 1).
 struct HostIn {
   DevBuf* buf;
   const void* src;
   size_t bytes;
+  size_t extra = 0;
 };
 struct HostOut {
   DevBuf* buf;
   void* dst;
   size_t bytes;
+  size_t extra = 0;
 };
 
 // message i of a staging buffer of T
@@ -1146,9 +1157,9 @@ int host_batch(fpx_ctx* ctx, int n, std::initializer_list<HostIn> in, std::initi
   constexpr bool cut_on_host = !std::is_null_pointer<Cut>::value;
   int rc;
   for (const HostIn& a : in)
-    if (a.src && (rc = h2d(ctx, a.buf, (const char*)a.src, (size_t)n * a.bytes))) return rc;
+    if (a.src && (rc = h2d(ctx, a.buf, (const char*)a.src, (size_t)n * a.bytes + a.extra))) return rc;
   for (const HostOut& a : out)
-    if ((rc = grow(ctx, a.buf, (size_t)n * a.bytes))) return rc;
+    if ((rc = grow(ctx, a.buf, (size_t)n * a.bytes + a.extra))) return rc;
   std::vector<int> cuts{0, n};
   if constexpr (cut_on_host) {
     if ((rc = cut(&cuts))) return rc;
@@ -1164,7 +1175,7 @@ int host_batch(fpx_ctx* ctx, int n, std::initializer_list<HostIn> in, std::initi
     }
   }
   for (const HostOut& a : out)
-    if ((rc = d2h(ctx, (char*)a.dst, *a.buf, (size_t)n * a.bytes))) return rc;
+    if ((rc = d2h(ctx, (char*)a.dst, *a.buf, (size_t)n * a.bytes + a.extra))) return rc;
   return fetch_status(ctx);
 }
 
@@ -1321,6 +1332,31 @@ static int32_t wire_decode_dev(fpx_ctx* ctx, const uint8_t* d_buf, int64_t buf_l
   hipLaunchKernelGGL(k_wire_tail, dim3(1), dim3(1), 0, ctx->stream, ctx->st);
   HIPCHK(ctx, hipGetLastError());
   return FPX_OK;
+}
+
+
+// ---- the device encoders (fpx_wire_enc_dev.hpp) -----------------------------------------------------------------
+template <int KIND>
+static int32_t wire_encode_dev(fpx_ctx* ctx, EncArgs a) {
+  a.nblk = (a.n + ENC_BLOCK - 1) / ENC_BLOCK;
+  int rc = grow(ctx, &ctx->d_enc, (size_t)(ENC_W_SUMS + 2 * (size_t)a.nblk) * 8);
+  if (rc) return rc;
+  a.scratch = (int64_t*)ctx->d_enc.p;
+  if (a.nblk) {
+    HIPCHK(ctx, hipMemsetAsync(a.scratch, 0x7f, 8, ctx->stream));  // ENC_NO_BAD
+    hipLaunchKernelGGL(k_enc_len<KIND>, dim3(a.nblk), dim3(ENC_BLOCK), 0, ctx->stream, a);
+  }
+  hipLaunchKernelGGL(k_enc_scan, dim3(1), dim3(1024), 0, ctx->stream, ctx->st, a);
+  if (a.nblk) {
+    if (KIND == ENC_PHASE2B) hipLaunchKernelGGL(k_enc_emit_p2b, dim3(a.nblk), dim3(ENC_BLOCK), 0, ctx->stream, a);
+    else hipLaunchKernelGGL(k_enc_emit_hv<KIND>, dim3(a.nblk), dim3(ENC_BLOCK), 0, ctx->stream, a);
+  }
+  return launch_check(ctx);
+}
+
+static bool enc_common_ok(const fpx_ctx* ctx, int32_t n, const uint8_t* d_out, int64_t cap, const int64_t* d_out_offsets,
+                          int64_t max_msgs, const int64_t* d_totals) {
+  return ctx && n >= 0 && n < (1 << 30) && cap >= 0 && max_msgs >= 0 && d_out_offsets && d_totals && (d_out || cap == 0);
 }
 
 extern "C" {
@@ -1729,6 +1765,106 @@ int32_t fpx_wire_decode_acceptor_inbound_dev(fpx_ctx* ctx, const uint8_t* d_buf,
   WireOut o{d_kind, d_slot, d_round, d_is_noop, d_value_len, d_chosen_watermark, nullptr, d_value_id, d_value_off,
             value_id_base};
   return wire_decode_dev<1>(ctx, d_buf, buf_len, d_offsets, n, o);
+}
+
+int32_t fpx_phase2_fused_dev(fpx_ctx* ctx, int32_t n, const int32_t* d_slot, const int32_t* d_round,
+                             const int32_t* d_value_id, const uint64_t* d_target_mask, uint8_t* d_chosen,
+                             int32_t* d_chosen_round, int32_t* d_chosen_value, int32_t* d_nack_round);
+
+int32_t fpx_wire_encode_replica_chosen_dev(fpx_ctx* ctx, int32_t n, const uint8_t* d_emit, const int32_t* d_slot,
+                                           const int32_t* d_is_noop, const uint8_t* d_values, int64_t values_len,
+                                           const int64_t* d_value_off, const int32_t* d_value_len, uint8_t* d_out,
+                                           int64_t cap, int64_t* d_out_offsets, int64_t* d_totals) {
+  if (!enc_common_ok(ctx, n, d_out, cap, d_out_offsets, n, d_totals) || values_len < 0) return FPX_EINVAL;
+  if (n > 0 && (!d_slot || !d_value_off || !d_value_len || (!d_values && values_len > 0))) return FPX_EINVAL;
+  DeviceGuard _dg(ctx);
+  EncArgs a = {};
+  a.n = n, a.emit = d_emit, a.slot = d_slot, a.is_noop = d_is_noop, a.values = d_values, a.values_len = values_len;
+  a.value_off = d_value_off, a.value_len = d_value_len;
+  a.out = d_out, a.cap = cap, a.max_msgs = n, a.out_offsets = d_out_offsets, a.totals = d_totals;
+  return wire_encode_dev<ENC_CHOSEN>(ctx, a);
+}
+
+int32_t fpx_wire_encode_phase2b_batch_dev(fpx_ctx* ctx, int32_t dialect, int32_t n, const int32_t* d_slot,
+                                          const int32_t* d_round, const uint64_t* d_vote_bits,
+                                          const int32_t* d_group_of_slot, int32_t grid_cols, uint8_t* d_out, int64_t cap,
+                                          int64_t* d_out_offsets, int64_t max_msgs, int64_t* d_totals) {
+  if (!enc_common_ok(ctx, n, d_out, cap, d_out_offsets, max_msgs, d_totals)) return FPX_EINVAL;
+  if ((dialect != FPX_WIRE_MULTIPAXOS && dialect != FPX_WIRE_MENCIUS) || (n > 0 && (!d_slot || !d_round || !d_vote_bits)))
+    return FPX_EINVAL;
+  DeviceGuard _dg(ctx);
+  EncArgs a = {};
+  a.n = n, a.dialect = dialect, a.grid_cols = grid_cols, a.slot = d_slot, a.round = d_round, a.vote_bits = d_vote_bits;
+  a.group_of_slot = d_group_of_slot;
+  a.out = d_out, a.cap = cap, a.max_msgs = max_msgs, a.out_offsets = d_out_offsets, a.totals = d_totals;
+  return wire_encode_dev<ENC_PHASE2B>(ctx, a);
+}
+
+int32_t fpx_wire_encode_leader_nack_dev(fpx_ctx* ctx, int32_t dialect, int32_t n, const int32_t* d_nack_round,
+                                        uint8_t* d_out, int64_t cap, int64_t* d_out_offsets, int64_t max_msgs,
+                                        int64_t* d_totals) {
+  if (!enc_common_ok(ctx, n, d_out, cap, d_out_offsets, max_msgs, d_totals)) return FPX_EINVAL;
+  if ((dialect != FPX_WIRE_MULTIPAXOS && dialect != FPX_WIRE_MENCIUS) || (n > 0 && !d_nack_round)) return FPX_EINVAL;
+  DeviceGuard _dg(ctx);
+  EncArgs a = {};
+  a.n = n, a.dialect = dialect, a.round = d_nack_round;
+  a.out = d_out, a.cap = cap, a.max_msgs = max_msgs, a.out_offsets = d_out_offsets, a.totals = d_totals;
+  return wire_encode_dev<ENC_NACK>(ctx, a);
+}
+
+// One proxy-leader tick, bytes to bytes, through the staging driver of the host-pointer entry points (host_batch): the
+// tick's bytes and offsets go up, ONE device run decodes, requires Phase2a's, votes and tallies, and encodes the Chosen
+// messages, and the reply's bytes, offsets, totals and Nack rounds come down.
+int32_t fpx_wire_phase2_tick(fpx_ctx* ctx, const uint8_t* in, int64_t in_len, const int64_t* in_offsets, int32_t n,
+                             uint8_t* out, int64_t out_cap, int64_t* out_offsets, int64_t* out_count,
+                             int32_t* nack_round, int64_t* bytes_needed, int32_t* bad_index) {
+  if (!ctx || n < 0 || n >= (1 << 30) || in_len < 0 || out_cap < 0 || !out_offsets || !out_count) return FPX_EINVAL;
+  if (n > 0 && (!in || !in_offsets || (!out && out_cap > 0))) return FPX_EINVAL;
+  DeviceGuard _dg(ctx);
+  *out_count = 0, out_offsets[0] = 0;
+  if (bytes_needed) *bytes_needed = 0;
+  if (bad_index) *bad_index = -1;
+  if (n == 0) return FPX_OK;
+  if (!mapped_host(in) || !mapped_host(in_offsets) || (out && !mapped_host(out)) || !mapped_host(out_offsets) ||
+      (nack_round && !mapped_host(nack_round)))
+    return FPX_EINVAL;
+  int rc;
+  const size_t rec_bytes[7] = {4, 4, 4, 4, 4, 4, 8};
+  for (int k = 0; k < 7; ++k)
+    if ((rc = grow(ctx, &ctx->w_rec[k], (size_t)n * rec_bytes[k]))) return rc;
+  for (DevBuf* b : {&ctx->d_u8, &ctx->d_i32_a, &ctx->d_i32_b})
+    if ((rc = grow(ctx, b, (size_t)n * 4))) return rc;
+  int64_t totals[2] = {0, 0};
+  rc = host_batch(
+      ctx, n, {{&ctx->w_buf, in, 0, (size_t)in_len}, {&ctx->w_off, in_offsets, 8, 8}},
+      {{&ctx->w_out, out, 0, (size_t)out_cap}, {&ctx->w_ooff, out_offsets, 8, 8}, {&ctx->d_i32_c, nack_round, 4},
+       {&ctx->w_tot, totals, 0, 16}},
+      nullptr, [&](int, int) {
+        int32_t* rec[6];
+        for (int k = 0; k < 6; ++k) rec[k] = (int32_t*)ctx->w_rec[k].p;
+        int64_t* value_off = (int64_t*)ctx->w_rec[6].p;
+        const uint8_t* buf = (const uint8_t*)ctx->w_buf.p;
+        int r = fpx_wire_decode_proxy_leader_inbound_dev(ctx, buf, in_len, (const int64_t*)ctx->w_off.p, n, rec[0], rec[1],
+                                                         rec[2], rec[3], value_off, rec[4], nullptr, nullptr, 0, rec[5]);
+        if (r) return r;
+        hipLaunchKernelGGL(k_wire_require_kind, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, ctx->st, rec[0], n,
+                           (int32_t)FPX_WIRE_PHASE2A);
+        hipLaunchKernelGGL(k_wire_tail, dim3(1), dim3(1), 0, ctx->stream, ctx->st);
+        if ((r = launch_check(ctx))) return r;
+        uint8_t* chosen = (uint8_t*)ctx->d_u8.p;
+        r = fpx_phase2_fused_dev(ctx, n, rec[1], rec[2], rec[5], nullptr, chosen, (int32_t*)ctx->d_i32_a.p,
+                                 (int32_t*)ctx->d_i32_b.p, (int32_t*)ctx->d_i32_c.p);
+        if (r) return r;
+        return fpx_wire_encode_replica_chosen_dev(ctx, n, chosen, rec[1], rec[3], buf, in_len, value_off, rec[4],
+                                                  (uint8_t*)ctx->w_out.p, out_cap, (int64_t*)ctx->w_ooff.p,
+                                                  (int64_t*)ctx->w_tot.p);
+      });
+  if (bad_index && (rc == FPX_EINVAL || rc == FPX_EORDER)) *bad_index = ctx->err_index;
+  if (rc != FPX_OK && rc != FPX_ECAPACITY) return rc;
+  if (bytes_needed) *bytes_needed = totals[1];
+  if (rc == FPX_OK) *out_count = totals[0];
+  else out_offsets[0] = 0;
+  return rc;
 }
 
 int32_t fpx_phase2_fused_dev(fpx_ctx* ctx, int32_t n, const int32_t* d_slot, const int32_t* d_round,

@@ -8,79 +8,30 @@
 #include <vector>
 
 #include "../../include/fpx.h"
+#include "fpx_wire_emit.hpp"
 #include "fpx_wire_parse.hpp"
 
 namespace {
 
 using namespace fpxw;
 
-// ---- writing ---------------------------------------------------------------------------------------------
-struct Writer {
-  uint8_t* p;        // null: only count
-  int64_t n = 0;
-  void byte(uint8_t b) {
-    if (p) p[n] = b;
-    ++n;
-  }
-  void varint(uint64_t v) {
-    while (v >= 0x80) {
-      byte((uint8_t)(v | 0x80));
-      v >>= 7;
-    }
-    byte((uint8_t)v);
-  }
-  void tag(uint32_t field, uint32_t wt) { varint(((uint64_t)field << 3) | wt); }
-  void i32(uint32_t field, int32_t v) {
-    tag(field, 0);
-    varint((uint64_t)(int64_t)v);  // negative: sign-extended, 10 bytes (protobuf int32)
-  }
-  void bytes(const uint8_t* src, int64_t len) {
-    if (p && len) memcpy(p + n, src, (size_t)len);
-    n += len;
-  }
-};
-
-int64_t varint_len(uint64_t v) {
-  int64_t k = 1;
-  while (v >= 0x80) v >>= 7, ++k;
-  return k;
-}
-int64_t i32_len(int32_t v) { return 1 + varint_len((uint64_t)(int64_t)v); }  // fields 1..15: one tag byte
-
-// the CommandBatchOrNoop body to embed: the caller's bytes, or {noop = 2: empty Noop} = 12 00
-static const uint8_t NOOP_VALUE[2] = {0x12, 0x00};
-inline void pick_value(const uint8_t*& value, int32_t& len, int32_t is_noop) {
-  if (is_noop) value = NOOP_VALUE, len = 2;
-  if (len < 0) len = 0;
-}
-
-// wraps `inner_len` bytes produced by `emit` as field `wrapper_field` (length-delimited) of an ...Inbound message
+// the host encoders' return convention around a layout of fpx_wire_emit.hpp: the length written, or the negated
+// length needed when cap is too small (nothing written)
 template <typename F>
-int64_t wrapped(uint8_t* out, int64_t cap, uint32_t wrapper_field, int64_t inner_len, F emit) {
-  const int64_t total = 1 + varint_len((uint64_t)inner_len) + inner_len;
+int64_t fits(uint8_t* out, int64_t cap, int64_t total, F emit) {
   if (total > cap || !out) return -total;
-  Writer w{out};
-  w.tag(wrapper_field, 2);
-  w.varint((uint64_t)inner_len);
-  emit(w);
-  return w.n;
+  return emit();
 }
 
 int64_t encode_phase2a(uint8_t* out, int64_t cap, uint32_t wrapper_field, int32_t slot, int32_t round,
                        const uint8_t* value, int32_t value_len, int32_t is_noop) {
   pick_value(value, value_len, is_noop);
-  const int64_t inner = i32_len(slot) + i32_len(round) + 1 + varint_len((uint64_t)value_len) + value_len;
-  return wrapped(out, cap, wrapper_field, inner, [&](Writer& w) {
-    w.i32(1, slot);
-    w.i32(2, round);
-    w.tag(3, 2);
-    w.varint((uint64_t)value_len);
-    w.bytes(value, value_len);
-  });
+  return fits(out, cap, phase2a_len(slot, round, value_len),
+              [&] { return phase2a_emit(out, wrapper_field, slot, round, value, value_len); });
 }
 
-int64_t phase2b_len(int32_t g, int32_t a, int32_t slot, int32_t round) {
-  return i32_len(g) + i32_len(a) + i32_len(slot) + i32_len(round);
+int64_t encode_ints(uint8_t* out, int64_t cap, uint32_t wrapper_field, int k, const int32_t* v) {
+  return fits(out, cap, ints_len(k, v), [&] { return ints_emit(out, wrapper_field, k, v); });
 }
 
 template <typename Emit>
@@ -243,36 +194,25 @@ int64_t fpx_wire_encode_acceptor_phase2a(uint8_t* out, int64_t cap, int32_t slot
 }
 
 int64_t fpx_wire_encode_acceptor_phase1a(uint8_t* out, int64_t cap, int32_t round, int32_t chosen_watermark) {
-  return wrapped(out, cap, 1, i32_len(round) + i32_len(chosen_watermark), [&](Writer& w) {
-    w.i32(1, round);
-    w.i32(2, chosen_watermark);
-  });
+  const int32_t v[2] = {round, chosen_watermark};
+  return encode_ints(out, cap, 1, 2, v);
 }
 
 int64_t fpx_wire_encode_proxy_leader_phase2b(uint8_t* out, int64_t cap, int32_t group_index, int32_t acceptor_index,
                                              int32_t slot, int32_t round) {
-  return wrapped(out, cap, 2, phase2b_len(group_index, acceptor_index, slot, round), [&](Writer& w) {
-    w.i32(1, group_index);
-    w.i32(2, acceptor_index);
-    w.i32(3, slot);
-    w.i32(4, round);
-  });
+  return fits(out, cap, phase2b_len(FPX_WIRE_MULTIPAXOS, group_index, acceptor_index, slot, round),
+              [&] { return phase2b_emit(out, FPX_WIRE_MULTIPAXOS, group_index, acceptor_index, slot, round); });
 }
 
 int64_t fpx_wire_encode_replica_chosen(uint8_t* out, int64_t cap, int32_t slot, const uint8_t* value,
                                        int32_t value_len, int32_t is_noop) {
   pick_value(value, value_len, is_noop);
-  const int64_t inner = i32_len(slot) + 1 + varint_len((uint64_t)value_len) + value_len;
-  return wrapped(out, cap, 1, inner, [&](Writer& w) {
-    w.i32(1, slot);
-    w.tag(2, 2);
-    w.varint((uint64_t)value_len);
-    w.bytes(value, value_len);
-  });
+  if (!value) value = NOOP_VALUE;  // (value_len is 0 here or the caller's bug: chosen_emit's nullptr means "head only")
+  return fits(out, cap, chosen_len(slot, value_len), [&] { return chosen_emit(out, slot, value, value_len); });
 }
 
 int64_t fpx_wire_encode_leader_nack(uint8_t* out, int64_t cap, int32_t round) {
-  return wrapped(out, cap, 6, i32_len(round), [&](Writer& w) { w.i32(1, round); });
+  return fits(out, cap, nack_len(round), [&] { return nack_emit(out, FPX_WIRE_MULTIPAXOS, round); });
 }
 
 int64_t fpx_wire_encode_client_max_slot_reply(uint8_t* out, int64_t cap, const uint8_t* command_id, int32_t command_id_len,
@@ -291,13 +231,8 @@ int64_t fpx_wire_encode_client_max_slot_reply(uint8_t* out, int64_t cap, const u
 
 int64_t fpx_wire_encode_read_batcher_batch_max_slot_reply(uint8_t* out, int64_t cap, int32_t read_batcher_index,
                                                           int32_t read_batcher_id, int32_t acceptor_index, int32_t slot) {
-  const int64_t inner = i32_len(read_batcher_index) + i32_len(read_batcher_id) + i32_len(acceptor_index) + i32_len(slot);
-  return wrapped(out, cap, 4, inner, [&](Writer& w) {
-    w.i32(1, read_batcher_index);
-    w.i32(2, read_batcher_id);
-    w.i32(3, acceptor_index);
-    w.i32(4, slot);
-  });
+  const int32_t v[4] = {read_batcher_index, read_batcher_id, acceptor_index, slot};
+  return encode_ints(out, cap, 4, 4, v);
 }
 
 int64_t fpx_wire_encode_leader_phase1b(uint8_t* out, int64_t cap, int32_t group_index, int32_t acceptor_index,
@@ -572,13 +507,6 @@ int64_t fpx_wire_mencius_encode_acceptor_phase2a(uint8_t* out, int64_t cap, int3
                                                  const uint8_t* value, int32_t value_len, int32_t is_noop) {
   return encode_phase2a(out, cap, 2, slot, round, value, value_len, is_noop);
 }
-static int64_t encode_ints(uint8_t* out, int64_t cap, uint32_t wrapper_field, int k, const int32_t* v) {
-  int64_t inner = 0;
-  for (int j = 0; j < k; ++j) inner += i32_len(v[j]);
-  return wrapped(out, cap, wrapper_field, inner, [&](Writer& w) {
-    for (int j = 0; j < k; ++j) w.i32((uint32_t)j + 1, v[j]);
-  });
-}
 int64_t fpx_wire_mencius_encode_proxy_leader_phase2a_noop_range(uint8_t* out, int64_t cap, int32_t slot_start,
                                                                 int32_t slot_end, int32_t round) {
   const int32_t v[3] = {slot_start, slot_end, round};
@@ -595,8 +523,8 @@ int64_t fpx_wire_mencius_encode_acceptor_phase1a(uint8_t* out, int64_t cap, int3
 }
 int64_t fpx_wire_mencius_encode_proxy_leader_phase2b(uint8_t* out, int64_t cap, int32_t acceptor_index, int32_t slot,
                                                      int32_t round) {
-  const int32_t v[3] = {acceptor_index, slot, round};
-  return encode_ints(out, cap, 4, 3, v);
+  return fits(out, cap, phase2b_len(FPX_WIRE_MENCIUS, 0, acceptor_index, slot, round),
+              [&] { return phase2b_emit(out, FPX_WIRE_MENCIUS, 0, acceptor_index, slot, round); });
 }
 int64_t fpx_wire_mencius_encode_proxy_leader_phase2b_noop_range(uint8_t* out, int64_t cap, int32_t acceptor_group_index,
                                                                 int32_t acceptor_index, int32_t slot_start,
@@ -614,7 +542,7 @@ int64_t fpx_wire_mencius_encode_replica_chosen_noop_range(uint8_t* out, int64_t 
   return encode_ints(out, cap, 2, 2, v);
 }
 int64_t fpx_wire_mencius_encode_leader_nack(uint8_t* out, int64_t cap, int32_t round) {
-  return encode_ints(out, cap, 7, 1, &round);
+  return fits(out, cap, nack_len(round), [&] { return nack_emit(out, FPX_WIRE_MENCIUS, round); });
 }
 
 // ---- EPaxos (epaxos/EPaxos.proto) ------------------------------------------------------------------------------

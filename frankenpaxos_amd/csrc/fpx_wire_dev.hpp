@@ -52,6 +52,13 @@ __global__ void __launch_bounds__(256) k_wire_decode(const State st, const uint8
   if (o.value_id) o.value_id[i] = m.kind == 1 ? o.value_id_base + i : -1;
 }
 
+// a tick that may hold one kind of message only (fpx_wire_phase2_tick): anything else is refused like a malformed message
+__global__ void __launch_bounds__(256) k_wire_require_kind(const State st, const int32_t* __restrict__ kind, int32_t n,
+                                                           int32_t want) {
+  const int32_t i = blockIdx.x * 256 + threadIdx.x;
+  if (i < n && kind[i] != want) wire_bad(st, true, i);
+}
+
 // one thread: a bad message becomes the context's sticky FPX_EINVAL, and every later _dev call of the run applies nothing
 __global__ void k_wire_tail(const State st) {
   const int32_t w = st.status[ST_WIRE];

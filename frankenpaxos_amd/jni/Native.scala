@@ -64,6 +64,14 @@ object Native {
                                       nackRound: java.nio.ByteBuffer): Int
   @native def phase2FusedWait(handle: Long, ticket: Int): Int
 
+  // one proxy-leader tick bytes to bytes (fpx_wire_phase2_tick): n serialised ProxyLeaderInbound{Phase2a} in `in`
+  // (inLen bytes, inOffsets: n + 1 longs) -> the tick's ReplicaInbound{Chosen} messages in `out` (out.capacity >= inLen
+  // always suffices; outOffsets: n + 1 longs) and the Nack rounds (n ints, may be null); every buffer a direct buffer
+  // over hostAlloc memory in native byte order.  counts(0) = messages written, (1) = bytes needed, (2) = bad index
+  @native def wirePhase2Tick(handle: Long, in: java.nio.ByteBuffer, inLen: Long, inOffsets: java.nio.ByteBuffer,
+                             n: Int, out: java.nio.ByteBuffer, outOffsets: java.nio.ByteBuffer,
+                             nackRound: java.nio.ByteBuffer, counts: Array[Long]): Int
+
   // the rows around the fused step
   @native def roundLeader(numLeaders: Int, round: Int): Int // < 0: -status (numLeaders < 1)
   @native def acceptorPhase1a(handle: Long, group: Int, round: Int, chosenWatermark: Int,

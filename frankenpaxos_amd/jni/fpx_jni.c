@@ -889,6 +889,30 @@ JNIEXPORT jint JNICALL Java_frankenpaxos_gpu_Native_phase2FusedWait(JNIEnv* env,
   return fpx_phase2_fused_wait(CTX(h), ticket);
 }
 
+/* One proxy-leader tick bytes to bytes (fpx_wire_phase2_tick): every buffer a direct ByteBuffer over hostAlloc memory.
+ * in holds inLen bytes, inOffsets n + 1 longs; out takes the Chosen messages (its capacity is the cap; inLen bytes always
+ * suffice), outOffsets n + 1 longs, nackRound (may be null) n ints; counts[3] = messages written, bytes needed, bad index */
+JNIEXPORT jint JNICALL Java_frankenpaxos_gpu_Native_wirePhase2Tick(JNIEnv* env, jclass cls, jlong h, jobject in,
+                                                                   jlong inLen, jobject inOffsets, jint n, jobject out,
+                                                                   jobject outOffsets, jobject nackRound,
+                                                                   jlongArray counts) {
+  if (n < 0 || inLen < 0 || !counts || !opt(env, counts, 3)) return FPX_EINVAL;
+  int bad = 0;
+  const uint8_t* i = direct(env, in, inLen, &bad);
+  const int64_t* io = direct(env, inOffsets, 8 * ((jlong)n + 1), &bad);
+  uint8_t* o = direct(env, out, 0, &bad);
+  int64_t* oo = direct(env, outOffsets, 8 * ((jlong)n + 1), &bad);
+  int32_t* nr = direct(env, nackRound, 4 * (jlong)n, &bad);
+  if (bad || !oo || (n > 0 && (!i || !io || !o))) return FPX_EINVAL;
+  int64_t count = 0, need = 0;
+  int32_t bad_index = -1;
+  const int32_t st = fpx_wire_phase2_tick(CTX(h), i, inLen, io, n, o, o ? (*env)->GetDirectBufferCapacity(env, out) : 0, oo,
+                                          &count, nr, &need, &bad_index);
+  const jlong c[3] = {count, need, bad_index};
+  put_longs(env, counts, 3, c);
+  return st;
+}
+
 /* K8 Replica.handlePrepareOk (epaxos/Replica.scala:1759-1884): prepareOk = epxPrepare's output (status | voteBallot |
  * triple, 3 x m x numReplicas), respMask = its okBits; decision = action | source | triple (3 x m ints) */
 JNIEXPORT jint JNICALL Java_frankenpaxos_gpu_Native_epxHandlePrepareOks(JNIEnv* env, jclass cls, jlong h, jint m,

@@ -1,11 +1,13 @@
 """Wire adapter (include/fpx_wire.h): the reference's protobuf messages of the Phase-2 path <-> SoA batches.
-Thin ctypes binding of the C functions in libfpx.so; host code only (works without a GPU)."""
+Thin ctypes binding of the C functions in libfpx.so.  What this module calls itself is host code (works without a GPU);
+the _dev prototypes bound here are used by Context.wire_decode_dev / wire_encode_*_dev / wire_phase2_tick."""
 import ctypes as C
 
 import numpy as np
 
 from . import _lib
 
+MULTIPAXOS, MENCIUS = 0, 1     # dialect of the device encoders (FPX_WIRE_MULTIPAXOS / FPX_WIRE_MENCIUS)
 OTHER, PHASE2A, PHASE2B, PHASE1A, CHOSEN, NACK, PHASE2A_NOOP_RANGE, PHASE2B_NOOP_RANGE, CHOSEN_NOOP_RANGE = range(9)
 PHASE1B = 9
 MAX_SLOT_REQUEST, BATCH_MAX_SLOT_REQUEST = 10, 11      # the acceptor's read path (multipaxos/Acceptor.scala:222-254)
@@ -37,6 +39,16 @@ def _L():
         # the device decoders (Context.wire_decode_dev): ctx, d_buf, buf_len, d_offsets, n, outputs..., value_id_base, d_value_id
         L.fpx_wire_decode_proxy_leader_inbound_dev.argtypes = [VP, VP, C.c_int64, VP, C.c_int32] + [VP] * 8 + [C.c_int32, VP]
         L.fpx_wire_decode_acceptor_inbound_dev.argtypes = [VP, VP, C.c_int64, VP, C.c_int32] + [VP] * 7 + [C.c_int32, VP]
+        # the device encoders (Context.wire_encode_*_dev) and the bytes-to-bytes tick (Context.wire_phase2_tick)
+        L.fpx_wire_encode_replica_chosen_dev.argtypes = [VP, C.c_int32, VP, VP, VP, VP, C.c_int64, VP, VP, VP, C.c_int64, VP, VP]
+        L.fpx_wire_encode_phase2b_batch_dev.argtypes = [VP, C.c_int32, C.c_int32, VP, VP, VP, VP, C.c_int32, VP, C.c_int64,
+                                                        VP, C.c_int64, VP]
+        L.fpx_wire_encode_leader_nack_dev.argtypes = [VP, C.c_int32, C.c_int32, VP, VP, C.c_int64, VP, C.c_int64, VP]
+        L.fpx_wire_phase2_tick.argtypes = [VP, VP, C.c_int64, VP, C.c_int32, VP, C.c_int64, VP, C.POINTER(C.c_int64), VP,
+                                           C.POINTER(C.c_int64), I32P]
+        for name in ("fpx_wire_encode_replica_chosen_dev", "fpx_wire_encode_phase2b_batch_dev",
+                     "fpx_wire_encode_leader_nack_dev", "fpx_wire_phase2_tick"):
+            getattr(L, name).restype = C.c_int32
         L.fpx_wire_decode_replica_inbound.argtypes = [VP, C.c_int64, VP, C.c_int32] + [VP] * 5 + [I32P]
         L.fpx_wire_mencius_decode_proxy_leader_inbound.argtypes = [VP, C.c_int64, VP, C.c_int32] + [VP] * 9 + [I32P]
         L.fpx_wire_mencius_decode_acceptor_inbound.argtypes = [VP, C.c_int64, VP, C.c_int32] + [VP] * 8 + [I32P]

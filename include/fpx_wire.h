@@ -1,6 +1,8 @@
 /*
  * fpx_wire.h -- wire adapter of libfpx: the reference's protobuf messages of the
- * Phase-2 path <-> the struct-of-arrays batches of include/fpx.h.  Host code only (no GPU involved), plain C ABI.
+ * Phase-2 path <-> the struct-of-arrays batches of include/fpx.h.  Plain C ABI.  The functions that take no context are
+ * host code (no GPU involved); the _dev entry points decode a tick and encode its replies ON THE GPU, and
+ * fpx_wire_phase2_tick runs a whole proxy-leader tick bytes to bytes.
  *
  * The reference's actors exchange ScalaPB messages serialised with `toByteArray` / parsed with `parseFrom`
  * (shared/src/main/scala/frankenpaxos/ProtoSerializer.scala:8-9) and wrapped in one `...Inbound` oneof per actor:
@@ -109,6 +111,76 @@ int32_t fpx_wire_decode_acceptor_inbound_dev(struct fpx_ctx* ctx, const uint8_t*
                                              int32_t* d_round, int32_t* d_is_noop, int64_t* d_value_off,
                                              int32_t* d_value_len, int32_t* d_chosen_watermark, int32_t value_id_base,
                                              int32_t* d_value_id);
+
+/* ---- the encoders ON THE DEVICE ----------------------------------------------------------------------------------
+ * The replies of a tick as wire bytes without the records coming down first: what fpx_phase2_fused_dev /
+ * fpx_acceptor_phase2a_dev left in HBM (Chosen flags, vote bits, Nack rounds) and what the device decoder left there
+ * (slot, is_noop, value_off, value_len, and the tick's bytes themselves) go in, the serialised messages come out back to
+ * back.  _dev convention: device pointers, enqueued on the context's stream, FPX_OK once enqueued, errors at fpx_sync.
+ * Shared contract:
+ *   bytes    d_out is, byte for byte, the concatenation of what the host encoder returns for the same records in the
+ *            same order (one emitter source, csrc/fpx_wire_emit.hpp, compiled for both sides).
+ *   offsets  d_out_offsets[k] = start of message k, d_out_offsets[count] = the total.
+ *   totals   d_totals[0] = count, d_totals[1] = the bytes needed: ALWAYS written, valid after fpx_sync.
+ *   FPX_ECAPACITY  the bytes needed exceed cap, or count exceeds max_msgs: no byte of d_out and no entry of
+ *            d_out_offsets beyond [0] (= 0) is written; d_totals says what to allocate.  A PER-CALL code, not an abort:
+ *            later _dev calls on the context apply as usual (the votes are applied already, the caller only encodes
+ *            again).  Like every device status it is sticky up to the next fpx_sync, which returns and clears it.
+ *   FPX_EINVAL     (Chosen) an emitted, non-Noop record whose value_off / value_len leave [0, values_len]:
+ *            fpx_error_detail's index names the first one, nothing is written beyond d_totals and d_out_offsets[0];
+ *            also a per-call code.  A negative value_len counts as 0, as in the host encoder.
+ *   empty    n == 0 or nothing to emit: count 0, d_out_offsets[0] = 0, FPX_OK.
+ *   aborted run  if the context is in the "apply nothing" state (a malformed tick, a run-contract violation) nothing
+ *            is encoded either: d_totals and d_out_offsets[0] are written, d_out is not.
+ *   graphs   no host wait inside, so a call can be captured into a HIP graph -- once the context's scratch is sized:
+ *            the first call with a larger n than any before allocates (8 bytes per 128 records), so run one call with
+ *            the largest n outside the capture.
+ * NULL context, n < 0 or n >= 2^30, negative cap / max_msgs, a missing required array: FPX_EINVAL at once, nothing is
+ * enqueued.  d_out may be NULL when cap == 0 (a sizing call: FPX_ECAPACITY and d_totals).
+ * Deviations from the issue's proposal: none in the signatures; the scratch note under "graphs" above. */
+enum { FPX_WIRE_MULTIPAXOS = 0, FPX_WIRE_MENCIUS = 1 }; /* dialect: which .proto's layout */
+
+/* ReplicaInbound{Chosen(slot, command_batch_or_noop)} for every record i with d_emit[i] != 0 (NULL = all), in index
+ * order.  Value of record i: d_values[d_value_off[i] .. + d_value_len[i]), or Noop where d_is_noop[i] != 0 (NULL = none):
+ * exactly fpx_wire_encode_replica_chosen's choice.  The two dialects share this message (same shape, same field
+ * numbers).  d_out_offsets has n + 1 entries, d_totals 2. */
+int32_t fpx_wire_encode_replica_chosen_dev(struct fpx_ctx* ctx, int32_t n, const uint8_t* d_emit, const int32_t* d_slot,
+                                           const int32_t* d_is_noop, const uint8_t* d_values, int64_t values_len,
+                                           const int64_t* d_value_off, const int32_t* d_value_len, uint8_t* d_out,
+                                           int64_t cap, int64_t* d_out_offsets, int64_t* d_totals);
+/* fpx_wire_encode_phase2b_batch on the device: one ProxyLeaderInbound{Phase2b} per set bit of d_vote_bits (n x 4
+ * words), message-major, bits ascending; bit -> (group_index, acceptor_index) as the host encoder maps it
+ * (d_group_of_slot may be NULL: group 0).  dialect FPX_WIRE_MENCIUS: Mencius.proto's Phase2b (acceptor_index, slot,
+ * round; wrapper field 4).  d_out_offsets has max_msgs + 1 entries. */
+int32_t fpx_wire_encode_phase2b_batch_dev(struct fpx_ctx* ctx, int32_t dialect, int32_t n, const int32_t* d_slot,
+                                          const int32_t* d_round, const uint64_t* d_vote_bits,
+                                          const int32_t* d_group_of_slot, int32_t grid_cols, uint8_t* d_out, int64_t cap,
+                                          int64_t* d_out_offsets, int64_t max_msgs, int64_t* d_totals);
+/* LeaderInbound{Nack(round)} for every record with d_nack_round[i] >= 0 (what K1 / K3 report), in index order; wrapper
+ * field 6 (MultiPaxos) / 7 (Mencius). */
+int32_t fpx_wire_encode_leader_nack_dev(struct fpx_ctx* ctx, int32_t dialect, int32_t n, const int32_t* d_nack_round,
+                                        uint8_t* d_out, int64_t cap, int64_t* d_out_offsets, int64_t max_msgs,
+                                        int64_t* d_totals);
+
+/* One proxy-leader tick, bytes to bytes, on PAGE-LOCKED buffers (fpx_host_alloc; FPX_EINVAL for anything else): n
+ * serialised ProxyLeaderInbound{Phase2a} messages (in, in_len, in_offsets[n + 1]) -> copy up ->
+ * fpx_wire_decode_proxy_leader_inbound_dev -> fpx_phase2_fused_dev (target_mask NULL, value_id = the message's index) ->
+ * fpx_wire_encode_replica_chosen_dev -> copy down: the ReplicaInbound{Chosen} messages of the tick in message order
+ * (out, out_offsets[count + 1], *out_count), each carrying the value bytes of the Phase2a it answers, and the Nack
+ * rounds (nack_round[n], may be NULL; -1 = none).  Synchronous.
+ * Every message must be a Phase2a: anything else, a malformed message or a bad offset is FPX_EINVAL with *bad_index
+ * (may be NULL), and the tick must be one device run (FPX_EORDER, *bad_index: as fpx_phase2_fused_submit); in both
+ * cases NOTHING is applied.
+ * Sizing out: a Chosen is never longer than the Phase2a it answers -- it drops the round field (at least two bytes),
+ * its slot is the same non-negative int32 in its shortest form, its value is the same bytes (or the two bytes of a Noop
+ * where the Phase2a's value was at least those two), and the two length prefixes can only shrink -- so out_cap >= in_len
+ * (with out_offsets of n + 1 entries) makes FPX_ECAPACITY unreachable.  A caller who passes less may get FPX_ECAPACITY:
+ * the tick WAS applied, out holds nothing, *bytes_needed (may be NULL; set on FPX_OK too) is what it would have taken.
+ * The copy down moves out_cap bytes (what lies in out behind the messages, up to out_cap, is unspecified): do not pass
+ * much more than in_len. */
+int32_t fpx_wire_phase2_tick(struct fpx_ctx* ctx, const uint8_t* in, int64_t in_len, const int64_t* in_offsets, int32_t n,
+                             uint8_t* out, int64_t out_cap, int64_t* out_offsets, int64_t* out_count,
+                             int32_t* nack_round, int64_t* bytes_needed, int32_t* bad_index);
 
 /* Folds decoded Phase2b messages into the rows fpx_proxy_phase2b takes: one row per distinct (slot, round), in
  * order of first appearance, with the acceptors that answered as a 256-bit set.  Bit of a message =
