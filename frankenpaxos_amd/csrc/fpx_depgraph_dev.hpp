@@ -34,6 +34,11 @@
 constexpr int DG_TILE = 2048;  // vertices per scan tile
 constexpr int DG_ROUNDS = 8;   // closure rounds enqueued per chunk (a round doubles the hops covered)
 constexpr int DG_SUB = DG_TILE / 256;  // workgroups of k_dg_relax per tile: each leaves its own row of maxima (no atomics)
+// The cover of an instance that is not committed: beyond every column.  A column ends at first[l] + count[l] <= DG_ID_END,
+// which dg_execute checks (fpx.h states it), so the cover is above every watermark that can still execute and
+// first[l] + count[l] does not overflow.
+constexpr int32_t DG_BEYOND = 0x7fffffff;
+constexpr int32_t DG_ID_END = DG_BEYOND - 1;
 
 template <int N> struct DgRow { static constexpr int NP = N <= 4 ? 4 : 8; };
 
@@ -101,7 +106,7 @@ __global__ void __launch_bounds__(256) k_dg_scatter(const DgArgs a) {
   for (int l = 0; l < N; ++l) {
     // an instance that is not committed can be waited for only: its cover is beyond every column, so is the closure of
     // whatever reaches it
-    d[l] = committed ? line[l] : 0x3fffffff;
+    d[l] = committed ? line[l] : DG_BEYOND;
     if (d[l] < 0) a.ctl[1] = 1;
   }
   const int end = line[2 * N];  // explicit ids x + 1 .. end - 1 of the own column (dependencies.subtractOne, Replica.scala:582)
@@ -357,7 +362,7 @@ __global__ void __launch_bounds__(256) k_dg_keys(const DgArgs a) {
     sum += (uint32_t)max(0, c[l] - a.first[l]);
   }
   // on a cycle iff the closure of a direct dependency covers x in column L.  Only a vertex that can execute is asked: one
-  // that is not committed has 0x3fffffff in every column of d[] and would walk the rest of its column, load by load
+  // that is not committed has DG_BEYOND in every column of d[] and would walk the rest of its column, load by load
   // (O(m^2) per tick with a few percent of the tick uncommitted)
   int back = 0;
   if (eligible) {

@@ -1900,7 +1900,7 @@ int dg_run(fpx_epx* e, Form& form, int m, const int32_t* d_leader, const int32_t
       EHIP(e, hipMemcpy(dbg, a.ctl, sizeof(dbg), hipMemcpyDeviceToHost));
       fprintf(stderr, "libfpx: depgraph (%s) chunk %d, vertices moved per round:", Form::name, chunk);
       for (int k = 1; k <= DG_ROUNDS; ++k) fprintf(stderr, " %d", dbg[24 + k]);
-      fprintf(stderr, "\n");
+      fprintf(stderr, " (%d rounds enqueued)\n", rounds);
     }
     executables = host[3];
     if (host[5] == 0) break;                    // the chunk's last round moved nothing: converged
@@ -1920,6 +1920,8 @@ int dg_execute(fpx_epx* e, int m, const int32_t* d_leader, const int32_t* d_numb
   long long total = 0;
   for (int l = 0; l < N; ++l) {
     if (first[l] < 0 || count[l] < 0) return FPX_EINVAL;
+    // ids are int32 and "beyond the column" has to be expressible: the column ends at DG_ID_END at the latest
+    if ((long long)first[l] + count[l] > DG_ID_END) return FPX_EINVAL;
     total += count[l];
   }
   if (total != m) return FPX_EINVAL;  // the columns are dense: every instance first[l] .. first[l] + count[l] - 1, once

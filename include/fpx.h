@@ -568,6 +568,11 @@ int32_t fpx_epx_sync(fpx_epx* epx);
  * output: deps watermarks + the explicit ids of the own column); d_committed (may be NULL = all) 0 = not committed yet:
  * it and whatever reaches it wait.  The columns must be DENSE: leader l's instances first[l] .. first[l] + count[l] - 1
  * each exactly once (sum of count = m), everything below first[l] executed earlier (FPX_EINVAL otherwise).
+ * Ids: 0 <= first[l] and first[l] + count[l] <= 2^31 - 2 for every column (FPX_EINVAL otherwise, nothing is run), so that
+ * every instance id is at most 2^31 - 3 and a watermark can still name an instance beyond the column's end; watermarks are
+ * any int32 >= 0 (negative: FPX_EINVAL), one above first[l] + count[l] makes the instance wait.  m < 2^21.  (With int32
+ * first and count and m < 2^21, the one end this refuses that int32 ids could still hold is 2^31 - 1: there no watermark
+ * could lie beyond the column; larger sums do not fit an id at all.)
  * Outputs: d_order[p] = the message executed p-th, d_component[p] = its component's number (consecutive from 0; equal
  * numbers = one strongly connected component), for p < *num_executed; *num_components.  Where the reference leaves the
  * order open (components that do not depend on each other) this path takes its own; the SET of components and the

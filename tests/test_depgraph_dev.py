@@ -12,7 +12,7 @@ pytestmark = pytest.mark.gpu
 
 def labels(n, leader, number, order_leader, order_id, comp_of_pos):
     """canonical component label (the smallest member's key) of every executed vertex, as {key: label}"""
-    key = order_leader.astype(np.int64) * (1 << 22) + order_id
+    key = (order_leader.astype(np.int64) << 32) | order_id.astype(np.int64)   # (distinct for every leader and every int32 id)
     starts = np.nonzero(np.diff(np.concatenate([[-1], comp_of_pos])))[0]
     lab = np.minimum.reduceat(key, starts) if len(key) else key
     return dict(zip(key.tolist(), np.repeat(lab, np.diff(np.concatenate([starts, [len(key)]]))).tolist()))
@@ -147,9 +147,23 @@ def dg_path(request, monkeypatch):
     return request.param
 
 
+# what an independent reference (tests/depgraph_ref.py) finds in each of these graphs, (n, m, jitter) -> (components, the largest
+# one's size): a random prefix graph with jitter is ONE giant component and at most a few singletons.  Graphs with many
+# components are in tests/test_depgraph_dev_components.py
+COMPONENTS = {(3, 300, 0): (300, 1),          # acyclic
+              (5, 2000, 3): (2, 1999),        # one component and 1 singleton
+              (5, 3000, 12): (1, 3000),       # one component
+              (7, 2500, 40): (1, 2500),       # one component
+              (3, 5000, 200): (19, 4982),     # one component and 18 singletons
+              (5, 1, 0): (1, 1),
+              (5, 40000, 6): (2, 39999)}      # one component and 1 singleton
+
+
 @pytest.mark.parametrize("n,m,jitter,holes", [(3, 300, 0, False), (5, 2000, 3, False), (5, 3000, 12, True), (7, 2500, 40, True),
                                               (3, 5000, 200, True), (5, 1, 0, False), (5, 40000, 6, True)])
 def test_device_components_equal_the_host_graphs(n, m, jitter, holes, dg_path):
+    from tests import depgraph_ref as R
+
     rng = np.random.default_rng(n * 1000 + m + jitter)
     big = m > 10000
     leader, number, first, count, deps, own = random_prefix_graph(rng, n, m, jitter, holes, from_zero=big)
@@ -162,6 +176,11 @@ def test_device_components_equal_the_host_graphs(n, m, jitter, holes, dg_path):
     check_valid_order(n, first, leader, number, deps, own[:, 0], order, comp)
     if jitter >= 3:
         assert nc < m                                       # there were cycles
+    lab, ex = R.scc_reference(n, leader, number, first, count, deps, own[:, 0])
+    sizes = R.component_sizes(lab, ex)
+    assert ex.all() and (nc, np.bincount(comp).max()) == COMPONENTS[(n, m, jitter)] == (len(sizes), sizes.max())
+    key = R.instance_key(leader, number)
+    assert np.array_equal(R.canonical_of_order(key, order, comp), R.canonical_of_labels(key, lab, ex))
 
 
 @pytest.mark.parametrize("n,m,dg_path", [(5, 3000, "packed"), (5, 3000, "wide"), (3, 800, "packed"), (3, 800, "wide")], indirect=["dg_path"])
