@@ -801,7 +801,10 @@ int32_t fpx_replica_read_log(fpx_ctx* ctx, int32_t first, int32_t count, int32_t
  *     which any of them voted (-1 if none).  For slot = chosen_watermark .. maxSlot (at most cap
  *     entries are written): safe_round = the highest voteRound among the quorum's acceptors of the
  *     slot's group that voted in the slot (-1 if none voted), safe_value = the value voted in that
- *     round (FPX_NOOP if none: "everything is safe, we return Noop"). */
+ *     round (FPX_NOOP if none: "everything is safe, we return Noop"; when several of them voted in
+ *     that round, the value of the one with the lowest index).  Only the bits [replica_base,
+ *     replica_base + num_replicas) of a set are read: a bit outside them names no acceptor of this
+ *     context and is ignored, it is not an error. */
 int32_t fpx_leader_phase1b_scan(fpx_ctx* ctx, int32_t chosen_watermark, const uint64_t* quorum_masks,
                                 int32_t cap, int32_t* max_slot, int32_t* safe_round,
                                 int32_t* safe_value);
