@@ -217,6 +217,19 @@ class Context:
                                       _hp(cr), _hp(cv))
         return st, ch, cr, cv
 
+    def proxy_phase2b_msgs(self, acceptor_index, slot, round_, kind=None, group_index=None, grid_cols=0):
+        """one Phase2b per (acceptor, slot), any order, duplicates allowed: = wire.phase2b_rows + proxy_phase2b, each
+        row's outcome at the index of its first message (kind None: all are Phase2bs; group_index None: 0)"""
+        acceptor_index, slot, round_ = _i32(acceptor_index), _i32(slot), _i32(round_)
+        kind, group_index = _i32(kind), _i32(group_index)
+        n = len(slot)
+        ch = np.zeros(n, np.uint8)
+        cr = np.zeros(n, np.int32)
+        cv = np.zeros(n, np.int32)
+        st = self.L.fpx_proxy_phase2b_msgs(self._h, n, _hp(kind), _hp(group_index), _hp(acceptor_index), _hp(slot),
+                                           _hp(round_), grid_cols, _hp(ch), _hp(cr), _hp(cv))
+        return st, ch, cr, cv
+
     def phase2_fused(self, slot, round_, value, target_mask=None):
         slot, round_, value, target_mask = _i32(slot), _i32(round_), _i32(value), _u64(target_mask)
         n = len(slot)
@@ -250,6 +263,14 @@ class Context:
                                           _dp(chosen_value))
         if st:
             raise FpxError(st, "fpx_proxy_phase2b_dev")
+
+    def proxy_phase2b_msgs_dev(self, acceptor_index, slot, round_, kind=None, group_index=None, grid_cols=0,
+                               newly_chosen=None, chosen_round=None, chosen_value=None):
+        st = self.L.fpx_proxy_phase2b_msgs_dev(self._h, slot.numel(), _dp(kind), _dp(group_index), _dp(acceptor_index),
+                                               _dp(slot), _dp(round_), grid_cols, _dp(newly_chosen), _dp(chosen_round),
+                                               _dp(chosen_value))
+        if st:
+            raise FpxError(st, "fpx_proxy_phase2b_msgs_dev")
 
     def phase2_fused_dev(self, slot, round_, value, target_mask=None, chosen=None, chosen_round=None,
                          chosen_value=None, nack_round=None):
@@ -350,6 +371,16 @@ class Context:
         st = wire._L().fpx_wire_phase2_tick(self._h, in_ptr, in_len, in_offsets_ptr, n, out_ptr, out_cap, out_offsets_ptr,
                                             C.byref(count), nack_round_ptr, C.byref(need), C.byref(bad))
         return st, count.value, need.value, bad.value
+
+    def wire_phase2b_tick(self, in_ptr, in_len, in_offsets_ptr, n, out_slot_ptr, out_round_ptr, out_value_ptr, out_cap,
+                          grid_cols=0):
+        """fpx_wire_phase2b_tick on raw addresses of page-locked buffers (host_alloc): returns (status, count, bad_index);
+        the status is returned, not raised -- FPX_ECAPACITY (count = the capacity needed) is an answer here."""
+        from . import wire
+        count, bad = C.c_int32(0), C.c_int32(-1)
+        st = wire._L().fpx_wire_phase2b_tick(self._h, in_ptr, in_len, in_offsets_ptr, n, grid_cols, out_slot_ptr,
+                                             out_round_ptr, out_value_ptr, out_cap, C.byref(count), C.byref(bad))
+        return st, count.value, bad.value
 
     # ---- multi-GPU: RCCL communicator behind the C ABI (fpx_comm_*) ----------------------------------
     def comm_create(self, unique_id, rank, world):

@@ -21,6 +21,7 @@
 
 #include "fpx_kernels.hpp"
 #include "fpx_ranges.hpp"
+#include "fpx_tally_msgs.hpp"
 #include "fpx_wire_dev.hpp"
 #include "fpx_wire_enc_dev.hpp"
 #include "../../include/fpx_wire.h"
@@ -149,6 +150,9 @@ struct fpx_ctx {
   // fpx_wire_phase2_tick: the tick's bytes and offsets, its decoded records (kind, slot, round, is_noop, value_len, value_id,
   // value_off), the reply's bytes, offsets and totals
   DevBuf w_buf, w_off, w_rec[7], w_out, w_ooff, w_tot;
+  // fpx_proxy_phase2b_msgs_dev (fpx_tally_msgs.hpp): the owner word of every tally entry ([S][wp], INT_MAX between calls;
+  // allocated by the first call), and per call the messages' entries, the gathered rows and the compaction's workgroup sums
+  DevBuf m_owner, m_entry, m_rows, m_blk;
   DevBuf d_band;  // [num_leader_groups] marks: the leader groups with a range in the step being checked
   // multi-GPU (fpx_comm_*): one communicator per context, rank = this context's GPU
   RcclComm comm = nullptr;
@@ -604,6 +608,29 @@ int enqueue_tally(fpx_ctx* ctx, Batch& b) {
   return launch_check(ctx);
 }
 
+// ProxyLeader.handlePhase2b for per-acceptor messages: claim, gather, tally, tail (fpx_tally_msgs.hpp)
+int enqueue_tally_msgs(fpx_ctx* ctx, MsgBatch& b) {
+  if (b.n == 0) return FPX_OK;
+  int rc;
+  if (!ctx->m_owner.p) {
+    const size_t words = (size_t)ctx->g.S * ctx->g.wp;
+    if ((rc = grow(ctx, &ctx->m_owner, words * 4))) return rc;
+    ctx->bytes += (int64_t)ctx->m_owner.cap;
+    fill32(ctx, ctx->m_owner.p, INT_MAX, ctx->m_owner.cap / 4);
+  }
+  if ((rc = grow(ctx, &ctx->m_entry, (size_t)b.n * 4))) return rc;
+  if ((rc = grow(ctx, &ctx->m_rows, (size_t)b.n * 32))) return rc;
+  b.owner = (int32_t*)ctx->m_owner.p, b.entry = (int32_t*)ctx->m_entry.p, b.row_bits = (unsigned long long*)ctx->m_rows.p;
+  b.phase2b = FPX_WIRE_PHASE2B;
+  HIPCHK(ctx, hipMemsetAsync(b.row_bits, 0, (size_t)b.n * 32, ctx->stream));
+  const dim3 grid((b.n + 255) / 256), blk(256);
+  hipLaunchKernelGGL(k_msgs_claim, grid, blk, 0, ctx->stream, ctx->g, ctx->st, b);
+  hipLaunchKernelGGL(k_msgs_gather, grid, blk, 0, ctx->stream, ctx->g, ctx->st, b);
+  hipLaunchKernelGGL(k_msgs_tally, grid, blk, 0, ctx->stream, ctx->g, ctx->st, b);
+  hipLaunchKernelGGL(k_msgs_tail, dim3(1), dim3(1), 0, ctx->stream, ctx->st, b);
+  return launch_check(ctx);
+}
+
 // fetch + clear the sticky device status (synchronises the stream)
 int fetch_status(fpx_ctx* ctx) {
   int32_t h[4] = {0, 0, 0, 0};
@@ -981,7 +1008,7 @@ void free_state(fpx_ctx* ctx) {
                   &rs.chosen,     &rs.target,    &rs.votes,     &rs.nacks,
                   &ctx->d_enc,    &ctx->w_buf,   &ctx->w_off,   &ctx->w_out,    &ctx->w_ooff,   &ctx->w_tot,
                   &ctx->w_rec[0], &ctx->w_rec[1], &ctx->w_rec[2], &ctx->w_rec[3], &ctx->w_rec[4], &ctx->w_rec[5],
-                  &ctx->w_rec[6]};
+                  &ctx->w_rec[6], &ctx->m_owner, &ctx->m_entry,  &ctx->m_rows,   &ctx->m_blk};
   for (DevBuf* b : bs)
     if (b->p) (void)hipFree(b->p);
   for (hipEvent_t e : ctx->ev) (void)hipEventDestroy(e);
@@ -1899,6 +1926,98 @@ int32_t fpx_proxy_phase2b_dev(fpx_ctx* ctx, int32_t n, const int32_t* d_slot, co
   b.n = n, b.slot = d_slot, b.round = d_round, b.vote_bits = const_cast<uint64_t*>(d_vote_bits);
   b.chosen = d_newly_chosen, b.chosen_round = d_chosen_round, b.chosen_value = d_chosen_value;
   return enqueue_tally(ctx, b);
+}
+
+int32_t fpx_proxy_phase2b_msgs_dev(fpx_ctx* ctx, int32_t n, const int32_t* d_kind, const int32_t* d_group_index,
+                                   const int32_t* d_acceptor_index, const int32_t* d_slot, const int32_t* d_round,
+                                   int32_t grid_cols, uint8_t* d_newly_chosen, int32_t* d_chosen_round,
+                                   int32_t* d_chosen_value) {
+  DeviceGuard _dg(ctx);
+  if (!ctx || n < 0 || n >= (1 << 30) || grid_cols < 0) return FPX_EINVAL;
+  if (n == 0) return FPX_OK;
+  if (!d_acceptor_index || !d_slot || !d_round) return FPX_EINVAL;
+  MsgBatch b;
+  memset(&b, 0, sizeof(b));
+  b.n = n, b.kind = d_kind, b.group = d_group_index, b.acceptor = d_acceptor_index, b.slot = d_slot, b.round = d_round;
+  b.grid_cols = grid_cols;
+  b.chosen = d_newly_chosen, b.chosen_round = d_chosen_round, b.chosen_value = d_chosen_value;
+  return enqueue_tally_msgs(ctx, b);
+}
+
+// the host form: ONE run through the staging driver (no run contract applies, so there is nothing to cut)
+int32_t fpx_proxy_phase2b_msgs(fpx_ctx* ctx, int32_t n, const int32_t* kind, const int32_t* group_index,
+                               const int32_t* acceptor_index, const int32_t* slot, const int32_t* round, int32_t grid_cols,
+                               uint8_t* newly_chosen, int32_t* chosen_round, int32_t* chosen_value) {
+  DeviceGuard _dg(ctx);
+  if (!ctx || n < 0 || n >= (1 << 30) || grid_cols < 0) return FPX_EINVAL;
+  if (n == 0) return FPX_OK;
+  if (!acceptor_index || !slot || !round) return FPX_EINVAL;
+  return host_batch(ctx, n,
+                    {{&ctx->d_value, kind, 4}, {&ctx->d_target, group_index, 4}, {&ctx->d_i32_c, acceptor_index, 4},
+                     {&ctx->d_slot, slot, 4}, {&ctx->d_round, round, 4}},
+                    {{&ctx->d_u8, newly_chosen, 1}, {&ctx->d_i32_a, chosen_round, 4}, {&ctx->d_i32_b, chosen_value, 4}},
+                    nullptr, [&](int, int) {
+                      return fpx_proxy_phase2b_msgs_dev(
+                          ctx, n, kind ? (const int32_t*)ctx->d_value.p : nullptr,
+                          group_index ? (const int32_t*)ctx->d_target.p : nullptr, (const int32_t*)ctx->d_i32_c.p,
+                          (const int32_t*)ctx->d_slot.p, (const int32_t*)ctx->d_round.p, grid_cols, (uint8_t*)ctx->d_u8.p,
+                          (int32_t*)ctx->d_i32_a.p, (int32_t*)ctx->d_i32_b.p);
+                    });
+}
+
+// One tick of a proxy leader among remote acceptors, bytes to records, through the staging driver as ONE run: the tick's
+// bytes and offsets go up, the device decodes, tallies the Phase2b's (claim / gather / tally) and compacts the newly
+// chosen records in message order; the count and the records come down.
+int32_t fpx_wire_phase2b_tick(fpx_ctx* ctx, const uint8_t* in, int64_t in_len, const int64_t* in_offsets, int32_t n,
+                              int32_t grid_cols, int32_t* out_slot, int32_t* out_round, int32_t* out_value_id,
+                              int32_t out_cap, int32_t* out_count, int32_t* bad_index) {
+  if (!ctx || n < 0 || n >= (1 << 30) || in_len < 0 || out_cap < 0 || grid_cols < 0 || !out_count) return FPX_EINVAL;
+  if (out_cap > 0 && (!out_slot || !out_round || !out_value_id)) return FPX_EINVAL;
+  if (n > 0 && (!in || !in_offsets)) return FPX_EINVAL;
+  DeviceGuard _dg(ctx);
+  *out_count = 0;
+  if (bad_index) *bad_index = -1;
+  if (n == 0) return FPX_OK;
+  if (!mapped_host(in) || !mapped_host(in_offsets) ||
+      (out_cap > 0 && (!mapped_host(out_slot) || !mapped_host(out_round) || !mapped_host(out_value_id))))
+    return FPX_EINVAL;
+  int rc;
+  for (int k = 0; k < 5; ++k)
+    if ((rc = grow(ctx, &ctx->w_rec[k], (size_t)n * 4))) return rc;
+  for (DevBuf* b : {&ctx->d_u8, &ctx->d_i32_a, &ctx->d_i32_b})
+    if ((rc = grow(ctx, b, (size_t)n * 4))) return rc;
+  MsgCompact c;
+  memset(&c, 0, sizeof(c));
+  c.n = n, c.nblk = (n + 255) / 256, c.cap = out_cap;
+  if ((rc = grow(ctx, &ctx->m_blk, (size_t)c.nblk * 4))) return rc;
+  int64_t totals[2] = {0, 0};
+  const size_t rec = (size_t)out_cap * 4;
+  rc = host_batch(
+      ctx, n, {{&ctx->w_buf, in, 0, (size_t)in_len}, {&ctx->w_off, in_offsets, 8, 8}},
+      {{&ctx->w_out, out_slot, 0, rec}, {&ctx->w_ooff, out_round, 0, rec}, {&ctx->d_i32_c, out_value_id, 0, rec},
+       {&ctx->w_tot, totals, 0, 16}},
+      nullptr, [&](int, int) {
+        int32_t* r5[5];
+        for (int k = 0; k < 5; ++k) r5[k] = (int32_t*)ctx->w_rec[k].p;  // kind, slot, round, group_index, acceptor_index
+        int r = fpx_wire_decode_proxy_leader_inbound_dev(ctx, (const uint8_t*)ctx->w_buf.p, in_len,
+                                                         (const int64_t*)ctx->w_off.p, n, r5[0], r5[1], r5[2], nullptr,
+                                                         nullptr, nullptr, r5[3], r5[4], 0, nullptr);
+        if (r) return r;
+        r = fpx_proxy_phase2b_msgs_dev(ctx, n, r5[0], r5[3], r5[4], r5[1], r5[2], grid_cols, (uint8_t*)ctx->d_u8.p,
+                                       (int32_t*)ctx->d_i32_a.p, (int32_t*)ctx->d_i32_b.p);
+        if (r) return r;
+        c.chosen = (const uint8_t*)ctx->d_u8.p, c.slot = r5[1], c.chosen_round = (const int32_t*)ctx->d_i32_a.p;
+        c.chosen_value = (const int32_t*)ctx->d_i32_b.p, c.blk = (int32_t*)ctx->m_blk.p;
+        c.out_slot = (int32_t*)ctx->w_out.p, c.out_round = (int32_t*)ctx->w_ooff.p, c.out_value = (int32_t*)ctx->d_i32_c.p;
+        c.totals = (int64_t*)ctx->w_tot.p;
+        hipLaunchKernelGGL(k_msgs_count, dim3(c.nblk), dim3(256), 0, ctx->stream, ctx->st, c);
+        hipLaunchKernelGGL(k_msgs_scan, dim3(1), dim3(1024), 0, ctx->stream, ctx->st, c);
+        hipLaunchKernelGGL(k_msgs_emit, dim3(c.nblk), dim3(256), 0, ctx->stream, ctx->st, c);
+        return launch_check(ctx);
+      });
+  if (bad_index && rc == FPX_EINVAL) *bad_index = ctx->err_index;
+  if (rc == FPX_OK || rc == FPX_ECAPACITY || rc == FPX_EFATAL_UNKNOWN_SLOTROUND) *out_count = (int32_t)totals[0];
+  return rc;
 }
 
 // ---- host-pointer entry points: stage, split into runs, run, copy back ----------------------------

@@ -630,46 +630,52 @@ __global__ void __launch_bounds__(256) k_open(const Geom g, const State st, cons
 // k_tally (K2): ProxyLeader.handlePhase2b (ProxyLeader.scala:217-258). Thread / message; the slots
 // of a run are distinct so a tally entry has exactly one writer.
 // ------------------------------------------------------------------------------------------------
+// One row of votes -- the acceptors `bits` answered Phase2b for (s, rnd) -- against its tally entry: k_tally's work per
+// message, and what the owner of an entry does with the row gathered from a tick's per-acceptor messages
+// (fpx_tally_msgs.hpp).  `index` is what an unknown (slot, round) reports.
+__device__ __forceinline__ void tally_row(const Geom& g, const State& st, int index, int s, int rnd, const uint64_t bits[4],
+                                          uint8_t* ch, int* cr, int* cv) {
+  uint64_t in[4];
+#pragma unroll
+  for (int w = 0; w < 4; ++w) in[w] = bits[w] & g.member[w];
+  *ch = 0, *cr = -1, *cv = -1;
+  if ((in[0] | in[1] | in[2] | in[3]) == 0) return;
+  const size_t ps = (size_t)phys_slot(g, s);
+  const uint32_t* kr = st.pl_key + ps * g.wp;
+  const uint32_t want = (uint32_t)rnd + 1u;
+  int way = -1;
+  uint32_t key = 0;
+  for (int w = 0; w < g.ways; ++w) {
+    const uint32_t k = kr[w];
+    if ((k & KEY_ROUND_MASK) == want) way = w, key = k;
+  }
+  if (way < 0) {
+    report(st, 2 /*FPX_EFATAL_UNKNOWN_SLOTROUND*/, index, s, rnd);  // :220-225
+  } else if (!(key & (KEY_DONE | KEY_RANGE))) {  // Done -> ignored, :227-232; a pending noop range
+                                                 // under the same key -> ignored, mencius :327-333
+    const size_t e = ps * g.wp + way;
+    uint64_t x[4];
+#pragma unroll
+    for (int w = 0; w < 4; ++w) x[w] = st.pl_bits[e * 4 + w] | in[w];  // :237
+    if (is_write_quorum(g, x)) {                                        // :238-243
+      *ch = 1;
+      *cr = rnd;
+      *cv = st.pl_value[e];  // :246-253  Chosen(slot, pending.phase2a.value)
+      st.pl_key[e] = key | KEY_DONE;  // :256
+    } else {
+#pragma unroll
+      for (int w = 0; w < 4; ++w) st.pl_bits[e * 4 + w] = x[w];
+    }
+  }
+}
+
 __global__ void __launch_bounds__(256) k_tally(const Geom g, const State st, const Batch b) {
   if (st.status[ST_ABORT] != 0) return;
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= b.n) return;
-  const int s = b.slot[i], rnd = b.round[i];
-  uint64_t in[4];
-  const uint64_t* vin = b.vote_bits + (size_t)i * 4;
-#pragma unroll
-  for (int w = 0; w < 4; ++w) in[w] = vin[w] & g.member[w];
-  uint8_t ch = 0;
-  int cr = -1, cv = -1;
-  if ((in[0] | in[1] | in[2] | in[3]) != 0) {
-    const size_t ps = (size_t)phys_slot(g, s);
-    const uint32_t* kr = st.pl_key + ps * g.wp;
-    const uint32_t want = (uint32_t)rnd + 1u;
-    int way = -1;
-    uint32_t key = 0;
-    for (int w = 0; w < g.ways; ++w) {
-      const uint32_t k = kr[w];
-      if ((k & KEY_ROUND_MASK) == want) way = w, key = k;
-    }
-    if (way < 0) {
-      report(st, 2 /*FPX_EFATAL_UNKNOWN_SLOTROUND*/, i, s, rnd);  // :220-225
-    } else if (!(key & (KEY_DONE | KEY_RANGE))) {  // Done -> ignored, :227-232; a pending noop range
-                                                   // under the same key -> ignored, mencius :327-333
-      const size_t e = ps * g.wp + way;
-      uint64_t x[4];
-#pragma unroll
-      for (int w = 0; w < 4; ++w) x[w] = st.pl_bits[e * 4 + w] | in[w];  // :237
-      if (is_write_quorum(g, x)) {                                        // :238-243
-        ch = 1;
-        cr = rnd;
-        cv = st.pl_value[e];  // :246-253  Chosen(slot, pending.phase2a.value)
-        st.pl_key[e] = key | KEY_DONE;  // :256
-      } else {
-#pragma unroll
-        for (int w = 0; w < 4; ++w) st.pl_bits[e * 4 + w] = x[w];
-      }
-    }
-  }
+  uint8_t ch;
+  int cr, cv;
+  tally_row(g, st, i, b.slot[i], b.round[i], b.vote_bits + (size_t)i * 4, &ch, &cr, &cv);
   if (b.chosen) b.chosen[i] = ch;
   if (b.chosen_round) b.chosen_round[i] = cr;
   if (b.chosen_value) b.chosen_value[i] = cv;

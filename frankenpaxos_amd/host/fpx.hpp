@@ -292,6 +292,24 @@ class Phase2Engine {
     return out;
   }
 
+  // The same with the fold of the messages into rows done on the device (fpx_proxy_phase2b_msgs): one Phase2b per
+  // (acceptor, slot) as remote acceptors send them, any order, duplicates allowed.  Chosen in message order.
+  std::vector<Chosen> proxyLeaderHandlePhase2bMsgs(const std::vector<Phase2b>& msgs) {
+    const int n = (int)msgs.size();
+    std::vector<int32_t> group(n), acceptor(n), slot(n), round(n);
+    for (int i = 0; i < n; ++i)
+      group[i] = msgs[i].groupIndex, acceptor[i] = msgs[i].acceptorIndex, slot[i] = msgs[i].slot, round[i] = msgs[i].round;
+    std::vector<uint8_t> ch(n);
+    std::vector<int32_t> cr(n), cv(n);
+    check(fpx_proxy_phase2b_msgs(ctx_, n, nullptr, group.data(), acceptor.data(), slot.data(), round.data(),
+                                 config_.flexible ? config_.acceptorsPerGroup : 0, ch.data(), cr.data(), cv.data()),
+          "ProxyLeader.handlePhase2b");
+    std::vector<Chosen> out;
+    for (int i = 0; i < n; ++i)
+      if (ch[i]) out.push_back(Chosen{slot[i], cv[i]});
+    return out;
+  }
+
   // ---- the fused tick: ProxyLeader.handlePhase2a -> Acceptor.handlePhase2a -> ProxyLeader.handlePhase2b
   std::vector<Chosen> handlePhase2(const std::vector<Phase2a>& msgs,
                                    const std::vector<std::vector<std::pair<int, int>>>& targets = {}) {

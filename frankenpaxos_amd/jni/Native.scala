@@ -4,7 +4,9 @@
 // `Native` is the JNI surface of frankenpaxos_amd/jni/fpx_jni.c.  `GpuPhase2Engine` owns one libfpx context --
 // the acceptors of every group plus the proxy leader's tallies -- and maps the unbounded log onto the
 // context's window of rows.  Two thin actors put it behind the unchanged Actor/Transport trait surface:
-//   * `GpuProxyLeader` stands at a proxy leader's address: its `receive` only ENQUEUES Phase2a messages, a
+//   * `GpuProxyLeader` stands at a proxy leader's address (with `remoteAcceptors = true` among the reference's own
+//     Acceptor actors: Phase2as are opened and forwarded, the acceptors' Phase2bs tallied on the device once per
+//     tick); with every acceptor in the engine its `receive` only ENQUEUES Phase2a messages, a
 //     zero-delay Transport timer (the "tick") flushes the queue through ONE native call and then `send`s the
 //     Nack / Chosen messages the Scala handlers would have sent (multipaxos/Acceptor.scala:192-219,
 //     multipaxos/ProxyLeader.scala:246-253);
@@ -39,6 +41,12 @@ object Native {
   @native def proxyPhase2b(handle: Long, n: Int, slot: Array[Int], round: Array[Int],
                            voteBits: Array[Long], newlyChosen: Array[Byte],
                            chosenRound: Array[Int], chosenValue: Array[Int]): Int
+  // the same for ONE Phase2b per (acceptor, slot) as remote acceptors send them, any order, duplicates allowed
+  // (fpx_proxy_phase2b_msgs): the fold into rows runs on the device; a row's outcome is at its first message.  kind
+  // (FPX_WIRE_*; null = all Phase2b) and groupIndex (null = 0) may be null; gridCols = 0 unless the quorums are a grid
+  @native def proxyPhase2bMsgs(handle: Long, n: Int, kind: Array[Int], groupIndex: Array[Int],
+                               acceptorIndex: Array[Int], slot: Array[Int], round: Array[Int], gridCols: Int,
+                               newlyChosen: Array[Byte], chosenRound: Array[Int], chosenValue: Array[Int]): Int
   @native def phase2Fused(handle: Long, n: Int, slot: Array[Int], round: Array[Int],
                           value: Array[Int], targetMask: Array[Long], chosen: Array[Byte],
                           chosenRound: Array[Int], chosenValue: Array[Int], nackRound: Array[Int]): Int
@@ -420,6 +428,52 @@ class GpuPhase2Engine[Transport <: frankenpaxos.Transport[Transport]](
     TickResult(chosenOut, nackOut)
   }
 
+  // ---- Phase 2 among REMOTE (reference) acceptors: the engine keeps the proxy leader's tallies only.
+  // ProxyLeader.handlePhase2a's bookkeeping for one tick (ProxyLeader.scala:175-184, 213): opens the tallies and returns
+  // the Phase2as that were new, in message order -- the caller forwards exactly those to the acceptors (:186-211); a
+  // duplicate is not forwarded.  The window is kept as in phase2Tick: what lies beyond it waits, what lies below it
+  // was chosen long ago.
+  def openPhase2as(incoming: Seq[Phase2a]): Seq[Phase2a] = {
+    val fresh = mutable.Buffer[Phase2a]()
+    val batch: Seq[Phase2a] = deferred.dequeueAll(_ => true) ++ incoming
+    val (now, later) = batch.filter(_.slot >= base).partition(_.slot < base + numSlots)
+    deferred ++= later
+    val n = now.size
+    val slot = new Array[Int](n); val round = new Array[Int](n); val value = new Array[Int](n)
+    for ((p, i) <- now.zipWithIndex) {
+      slot(i) = row(p.slot); round(i) = p.round; value(i) = intern(row(p.slot), p.commandBatchOrNoop)
+    }
+    val isNew = new Array[Byte](n)
+    if (n > 0) Native.check(Native.proxyOpen(handle, n, slot, round, value, isNew), logger)
+    for (i <- 0 until n if isNew(i) != 0) fresh += now(i)
+    fresh
+  }
+
+  // ProxyLeader.handlePhase2b for one tick of Phase2bs from remote acceptors (ProxyLeader.scala:217-258), tallied on the
+  // device in ONE native call (fpx_proxy_phase2b_msgs).  Returns the Chosen to broadcast, in message order; the window,
+  // row and markChosen bookkeeping is phase2Tick's.  A Phase2b below the window answers a slot chosen and recycled
+  // long ago (the reference's `Done`: ignored); one beyond it was never opened here.
+  def tallyPhase2bs(msgs: Seq[Phase2b]): Seq[Chosen] = {
+    val chosenOut = mutable.Buffer[Chosen]()
+    val now = msgs.filter(m => m.slot >= base && m.slot < base + numSlots)
+    val n = now.size
+    if (n == 0) return chosenOut
+    val group = new Array[Int](n); val acc = new Array[Int](n); val slot = new Array[Int](n); val round = new Array[Int](n)
+    for ((m, i) <- now.zipWithIndex) {
+      group(i) = m.groupIndex; acc(i) = m.acceptorIndex; slot(i) = row(m.slot); round(i) = m.round
+    }
+    val chosen = new Array[Byte](n); val cr = new Array[Int](n); val cv = new Array[Int](n)
+    // a grid's bit is groupIndex * perGroup + acceptorIndex (ctxReplica); otherwise the group follows from the slot
+    val gridCols = if (config.flexible) perGroup else 0
+    Native.check(Native.proxyPhase2bMsgs(handle, n, null, group, acc, slot, round, gridCols, chosen, cr, cv), logger)
+    for (i <- 0 until n if chosen(i) != 0) {
+      chosenOut += Chosen(slot = now(i).slot, commandBatchOrNoop = valueOf(cv(i))) // ProxyLeader.scala:246-253
+      markChosen(now(i).slot)
+    }
+    advanceWindow()                                      // what it admits is opened by the next openPhase2as
+    chosenOut
+  }
+
   // ---- Phase 1, acceptor side (Acceptor.handlePhase1a, multipaxos/Acceptor.scala:148-182)
   def handlePhase1a(groupIndex: Int, index: Int, phase1a: Phase1a): Either[Nack, Phase1b] = {
     val g = ctxGroup(groupIndex); val a = ctxReplica(groupIndex, index)
@@ -477,7 +531,11 @@ class GpuProxyLeader[Transport <: frankenpaxos.Transport[Transport]](
     transport: Transport,
     logger: Logger,
     config: Config[Transport],
-    engine: GpuPhase2Engine[Transport]
+    engine: GpuPhase2Engine[Transport],
+    // true: the acceptors are the reference's own Acceptor actors somewhere else.  A Phase2a is opened on the device and
+    // forwarded to f + 1 acceptors of its slot's group (or a grid column), their Phase2bs are buffered and tallied on
+    // the device once per tick.  false: every acceptor lives in `engine` (the fused step) and no Phase2b ever arrives
+    remoteAcceptors: Boolean = false
 ) extends Actor(address, transport, logger) {
   override type InboundMessage = ProxyLeaderInbound
   override val serializer = ProxyLeaderInboundSerializer
@@ -486,6 +544,9 @@ class GpuProxyLeader[Transport <: frankenpaxos.Transport[Transport]](
   private val leaders = for (a <- config.leaderAddresses) yield chan[Leader[Transport]](a, Leader.serializer)
   private val replicas = for (a <- config.replicaAddresses) yield chan[Replica[Transport]](a, Replica.serializer)
   private val pending = mutable.Buffer[Phase2a]()
+  private val pendingPhase2bs = mutable.Buffer[Phase2b]()
+  private val acceptors =
+    for (group <- config.acceptorAddresses) yield for (a <- group) yield chan[Acceptor[Transport]](a, Acceptor.serializer)
 
   // one tick: a zero-delay timer, i.e. "after the messages already queued on the event loop"
   private val tick = timer("gpuPhase2Tick", java.time.Duration.ZERO, () => flushTick())
@@ -493,21 +554,48 @@ class GpuProxyLeader[Transport <: frankenpaxos.Transport[Transport]](
   override def receive(src: Transport#Address, inbound: ProxyLeaderInbound): Unit = {
     inbound.request match {
       case ProxyLeaderInbound.Request.Phase2A(p) =>
-        if (pending.isEmpty) tick.start()
+        if (pending.isEmpty && pendingPhase2bs.isEmpty) tick.start()
         pending += p
-      case ProxyLeaderInbound.Request.Phase2B(_) =>
-        logger.fatal("GpuProxyLeader tallies on the device; it never receives Phase2b messages.")
+      case ProxyLeaderInbound.Request.Phase2B(b) =>
+        if (!remoteAcceptors)
+          logger.fatal("GpuProxyLeader tallies on the device; it never receives Phase2b messages.")
+        if (pending.isEmpty && pendingPhase2bs.isEmpty) tick.start()
+        pendingPhase2bs += b
       case ProxyLeaderInbound.Request.Empty =>
         logger.fatal("Empty ProxyLeaderInbound encountered.")
     }
   }
 
   private def flushTick(): Unit = {
+    if (remoteAcceptors) {
+      flushRemoteTick()
+      return
+    }
     val result = engine.phase2Tick(pending.toList)
     pending.clear()
     for (c <- result.chosen) replicas.foreach(_.send(ReplicaInbound().withChosen(c)))
     for ((round, nack) <- result.nacks)
       leaders(roundSystem.leader(round)).send(LeaderInbound().withNack(nack))
+  }
+
+  // the tick among remote acceptors: the Phase2as first (a Phase2b of this tick may answer a Phase2a of this tick only
+  // if an acceptor was faster than the event loop; opening first keeps it known either way), then the Phase2bs
+  private def flushRemoteTick(): Unit = {
+    val fresh = engine.openPhase2as(pending.toList)
+    pending.clear()
+    for (p <- fresh) {
+      // ProxyLeader.scala:186-211: f + 1 acceptors of the slot's group, or a random write quorum of the grid (a column)
+      val quorum =
+        if (!config.flexible) scala.util.Random.shuffle(acceptors(p.slot % config.numAcceptorGroups)).take(config.f + 1)
+        else {
+          val col = scala.util.Random.nextInt(engine.perGroup)
+          acceptors.map(_(col))
+        }
+      quorum.foreach(_.send(AcceptorInbound().withPhase2A(p)))
+    }
+    val chosen = engine.tallyPhase2bs(pendingPhase2bs.toList)
+    pendingPhase2bs.clear()
+    for (c <- chosen) replicas.foreach(_.send(ReplicaInbound().withChosen(c)))          // ProxyLeader.scala:246-253
   }
 }
 

@@ -162,6 +162,28 @@ JNIEXPORT jint JNICALL Java_frankenpaxos_gpu_Native_proxyPhase2b(JNIEnv* env, jc
   return st;
 }
 
+/* ProxyLeader.handlePhase2b for one Phase2b per (acceptor, slot): fpx_proxy_phase2b_msgs; kind and groupIndex may be null */
+JNIEXPORT jint JNICALL Java_frankenpaxos_gpu_Native_proxyPhase2bMsgs(JNIEnv* env, jclass cls, jlong h, jint n,
+                                                                     jintArray kind, jintArray groupIndex,
+                                                                     jintArray acceptorIndex, jintArray slot,
+                                                                     jintArray round, jint gridCols,
+                                                                     jbyteArray newlyChosen, jintArray chosenRound,
+                                                                     jintArray chosenValue) {
+  if (n < 0) return FPX_EINVAL;
+  if (n == 0) return FPX_OK;
+  if (!opt(env, kind, n) || !opt(env, groupIndex, n) || !has(env, acceptorIndex, n) || !has(env, slot, n) ||
+      !has(env, round, n) || !opt(env, newlyChosen, n) || !opt(env, chosenRound, n) || !opt(env, chosenValue, n))
+    return FPX_EINVAL;
+  jint *k = in_ints(env, kind, n), *g = in_ints(env, groupIndex, n), *a = in_ints(env, acceptorIndex, n);
+  jint *s = in_ints(env, slot, n), *r = in_ints(env, round, n);
+  jbyte* ch = out_buf(newlyChosen, n, 1);
+  jint *cr = out_buf(chosenRound, n, 4), *cv = out_buf(chosenValue, n, 4);
+  int32_t st = fpx_proxy_phase2b_msgs(CTX(h), n, k, g, a, s, r, gridCols, (uint8_t*)ch, cr, cv);
+  put_bytes(env, newlyChosen, n, ch); put_ints(env, chosenRound, n, cr); put_ints(env, chosenValue, n, cv);
+  free(k); free(g); free(a); free(s); free(r); free(ch); free(cr); free(cv);
+  return st;
+}
+
 /* the fused tick (open + Phase2a to the targeted acceptors + tally) */
 JNIEXPORT jint JNICALL Java_frankenpaxos_gpu_Native_phase2Fused(
     JNIEnv* env, jclass cls, jlong h, jint n, jintArray slot, jintArray round, jintArray value,

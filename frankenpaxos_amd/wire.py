@@ -46,8 +46,10 @@ def _L():
         L.fpx_wire_encode_leader_nack_dev.argtypes = [VP, C.c_int32, C.c_int32, VP, VP, C.c_int64, VP, C.c_int64, VP]
         L.fpx_wire_phase2_tick.argtypes = [VP, VP, C.c_int64, VP, C.c_int32, VP, C.c_int64, VP, C.POINTER(C.c_int64), VP,
                                            C.POINTER(C.c_int64), I32P]
+        # the Phase2b tick of a proxy leader among remote acceptors (Context.wire_phase2b_tick)
+        L.fpx_wire_phase2b_tick.argtypes = [VP, VP, C.c_int64, VP, C.c_int32, C.c_int32, VP, VP, VP, C.c_int32, I32P, I32P]
         for name in ("fpx_wire_encode_replica_chosen_dev", "fpx_wire_encode_phase2b_batch_dev",
-                     "fpx_wire_encode_leader_nack_dev", "fpx_wire_phase2_tick"):
+                     "fpx_wire_encode_leader_nack_dev", "fpx_wire_phase2_tick", "fpx_wire_phase2b_tick"):
             getattr(L, name).restype = C.c_int32
         L.fpx_wire_decode_replica_inbound.argtypes = [VP, C.c_int64, VP, C.c_int32] + [VP] * 5 + [I32P]
         L.fpx_wire_mencius_decode_proxy_leader_inbound.argtypes = [VP, C.c_int64, VP, C.c_int32] + [VP] * 9 + [I32P]

@@ -296,6 +296,33 @@ int32_t fpx_proxy_phase2b_dev(fpx_ctx* ctx, int32_t n, const int32_t* d_slot, co
                               const uint64_t* d_vote_bits, uint8_t* d_newly_chosen,
                               int32_t* d_chosen_round, int32_t* d_chosen_value);
 
+/* The same for PER-ACCEPTOR messages, as reference acceptors send them (Acceptor.scala:211-219): message i is ONE
+ * Phase2b(group_index[i], acceptor_index[i], slot[i], round[i]).  NO run contract applies: any number of messages per
+ * (slot, round) in any order, several rounds of one slot, and duplicates are all allowed.  These are the outputs of
+ * fpx_wire_decode_proxy_leader_inbound(_dev): kind (NULL = every message is a Phase2b; messages whose kind is not
+ * FPX_WIRE_PHASE2B are skipped), group_index (NULL = 0).  The bit of a message is acceptor_index when grid_cols == 0 and
+ * group_index * grid_cols + acceptor_index for a grid, as in fpx_wire_phase2b_rows.
+ * Contract: the result equals fpx_wire_phase2b_rows followed by fpx_proxy_phase2b on those rows, with each row's outcome
+ * reported at the index of the row's FIRST message (every other message reports newly_chosen = 0, chosen_round =
+ * chosen_value = -1), and the tally state afterwards is identical -- Done entries keep their stored bits untouched.  The
+ * fold runs on the device (csrc/fpx_tally_msgs.hpp: claim / gather / tally launches and an owner word per tally entry,
+ * allocated by the first call: 4 bytes x num_slots x 4 or 8), with integer atomics only: results are reproducible.
+ * A message whose bit lies outside the context's member set [0, replicas_total) contributes nothing: it is not looked
+ * up, never reports an unknown (slot, round), and never is the "first message" of its row -- the row's outcome is at its
+ * first message whose bit is a member.
+ * Errors: FPX_EINVAL with NOTHING applied (the validation convention of the _dev calls: the context applies nothing up to
+ * the next fpx_sync) for a bit outside 0..255, acceptor_index < 0, acceptor_index >= grid_cols for a grid, a slot
+ * outside the window or a round outside 0 .. 2^30 - 2; FPX_EFATAL_UNKNOWN_SLOTROUND per message for an unknown (slot,
+ * round): that message is dropped, the others are applied.  fpx_error_detail names the LOWEST offending index in both
+ * cases.  n == 0 is FPX_OK.  The host form is synchronous and goes through the staging driver as a single run. */
+int32_t fpx_proxy_phase2b_msgs(fpx_ctx* ctx, int32_t n, const int32_t* kind, const int32_t* group_index,
+                               const int32_t* acceptor_index, const int32_t* slot, const int32_t* round,
+                               int32_t grid_cols, uint8_t* newly_chosen, int32_t* chosen_round, int32_t* chosen_value);
+int32_t fpx_proxy_phase2b_msgs_dev(fpx_ctx* ctx, int32_t n, const int32_t* d_kind, const int32_t* d_group_index,
+                                   const int32_t* d_acceptor_index, const int32_t* d_slot, const int32_t* d_round,
+                                   int32_t grid_cols, uint8_t* d_newly_chosen, int32_t* d_chosen_round,
+                                   int32_t* d_chosen_value);
+
 /* Garbage collection of the proxy leader (NOT in the reference, whose ProxyLeader.states grows forever,
  * ProxyLeader.scala:135): forgets every tally -- Pending or Done -- of the slots
  * [first_slot, first_slot + count) and every noop-range tally whose range lies inside that window, so that a long-running simulation can re-propose a chosen-and-executed

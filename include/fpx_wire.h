@@ -182,6 +182,24 @@ int32_t fpx_wire_phase2_tick(struct fpx_ctx* ctx, const uint8_t* in, int64_t in_
                              uint8_t* out, int64_t out_cap, int64_t* out_offsets, int64_t* out_count,
                              int32_t* nack_round, int64_t* bytes_needed, int32_t* bad_index);
 
+/* One tick of a proxy leader among REMOTE acceptors, bytes to records, on PAGE-LOCKED buffers (fpx_host_alloc;
+ * FPX_EINVAL for anything else): n serialised ProxyLeaderInbound messages (in, in_len, in_offsets[n + 1]) -> copy up ->
+ * fpx_wire_decode_proxy_leader_inbound_dev -> fpx_proxy_phase2b_msgs_dev (include/fpx.h) -> the newly chosen records
+ * compacted on the device in message order -> copy down of the count and the records only.  Synchronous.
+ * Record k = (out_slot[k], out_round[k], out_value_id[k]): the k-th (slot, round) that reached its quorum in this tick
+ * and the value id given to fpx_proxy_open.  The outputs are records, not Chosen bytes: the value bytes belong to the
+ * Phase2a of an earlier tick and stay with the caller under their value id.  Phase2a messages (and any other kind) in
+ * the tick are skipped: the caller opens and forwards them.
+ * A malformed message or a bad offset is FPX_EINVAL with *bad_index (may be NULL) and NOTHING is applied, as is a Phase2b
+ * that fpx_proxy_phase2b_msgs refuses.  out_cap (records) too small is FPX_ECAPACITY: the tick WAS applied, *out_count
+ * holds the count needed and the first out_cap records are written.  FPX_EFATAL_UNKNOWN_SLOTROUND: per message, the
+ * others were applied and their records are out (compare *out_count with out_cap: this status outranks FPX_ECAPACITY).
+ * The copy down moves out_cap records (what lies in the arrays behind the *out_count records, up to out_cap, is
+ * unspecified): size out_cap by the slots that can complete in a tick, not by n. */
+int32_t fpx_wire_phase2b_tick(struct fpx_ctx* ctx, const uint8_t* in, int64_t in_len, const int64_t* in_offsets, int32_t n,
+                              int32_t grid_cols, int32_t* out_slot, int32_t* out_round, int32_t* out_value_id,
+                              int32_t out_cap, int32_t* out_count, int32_t* bad_index);
+
 /* Folds decoded Phase2b messages into the rows fpx_proxy_phase2b takes: one row per distinct (slot, round), in
  * order of first appearance, with the acceptors that answered as a 256-bit set.  Bit of a message =
  * acceptor_index when grid_cols == 0 (non-flexible: the acceptor group follows from the slot,
