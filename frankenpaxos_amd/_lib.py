@@ -41,6 +41,9 @@ FPX_NOOP = -1
 CENSUS_FORMS = ("solo", "grid", "fin", "band", "fold_now", "fold_behind", "fold_carried", "fold_flushed")
 CENSUS_CELLS = 7 * 4 * 3 * 2
 CENSUS_WORDS = CENSUS_CELLS * len(CENSUS_FORMS) + 3
+# fpx_range_launch_census (include/fpx.h): its words in order
+RANGE_CENSUS_FORMS = ("chain", "steps", "band", "fill_lg", "fill_sweep", "fill_range", "tally_only", "open_only",
+                      "acceptors_only", "rehash")
 
 
 class FpxConfig(C.Structure):
@@ -89,6 +92,7 @@ SIGNATURES = {
     "fpx_band_merged_steps": (C.c_int64, [VP]),
     "fpx_deferred_folds": (C.c_int64, [VP]),
     "fpx_vote_launch_census": (C.c_int32, [VP, C.c_int32, C.POINTER(C.c_int64), I32P]),
+    "fpx_range_launch_census": (C.c_int32, [VP, C.POINTER(C.c_int64), C.c_int32, I32P]),
     "fpx_acceptor_max_voted_in": (C.c_int32, [VP, C.c_int32, C.c_int32, C.c_int32, C.c_int32, I32P]),
     "fpx_profile_read_launches": (C.c_int32, [VP, C.c_int32, C.POINTER(C.c_float), C.POINTER(C.c_int32)]),
     "fpx_get_config": (C.c_int32, [VP, CFGP]),
@@ -126,6 +130,7 @@ SIGNATURES = {
     "fpx_noop_ranges_fused_dev": (C.c_int32, [VP, C.c_int32] + [VP] * 9),
     "fpx_mencius_band_fused_dev": (C.c_int32, [VP, C.c_int32] + [VP] * 8 + [C.c_int32] + [VP] * 9 + [C.c_int32]),
     "fpx_read_range_tally": (C.c_int32, [VP, C.c_int32, C.c_int32, C.c_int32, I32P, VP]),
+    "fpx_read_range_position": (C.c_int32, [VP, C.c_int32, C.c_int32, C.c_int32, I32P, I32P, I32P]),
     "fpx_recycle_slots": (C.c_int32, [VP, C.c_int32, C.c_int32]),
     "fpx_proxy_forget": (C.c_int32, [VP, C.c_int32, C.c_int32]),
     "fpx_epx_create": (C.c_int32, [VP, C.POINTER(VP)]),

@@ -168,6 +168,18 @@ class Context:
         base = _lib.CENSUS_CELLS * nf
         return {"cells": cells, "capped": int(out[base]), "sc_lds": int(out[base + 1]), "th_lds": int(out[base + 2])}
 
+    def range_launch_census(self):
+        """diagnostic: the noop-range launches since the context was created (include/fpx.h, fpx_range_launch_census) --
+        {form: count} over every form of _lib.RANGE_CENSUS_FORMS, zeros included"""
+        nw = len(_lib.RANGE_CENSUS_FORMS)
+        out = (C.c_int64 * nw)()
+        n = C.c_int32(0)
+        st = self.L.fpx_range_launch_census(self._h, out, nw, C.byref(n))
+        if st:
+            raise FpxError(st, "fpx_range_launch_census")
+        assert n.value == nw, "include/fpx.h and _lib.RANGE_CENSUS_FORMS disagree"
+        return {name: int(out[k]) for k, name in enumerate(_lib.RANGE_CENSUS_FORMS)}
+
     # ---- host-pointer entry points (numpy) ---------------------------------------------------
     def acceptor_phase2a(self, slot, round_, value, target_mask=None):
         slot, round_, value, target_mask = _i32(slot), _i32(round_), _i32(value), _u64(target_mask)
@@ -530,6 +542,15 @@ class Context:
         if st:
             raise FpxError(st, "fpx_read_range_tally")
         return state.value, bits
+
+    def read_range_position(self, slot_start, slot_end, round_):
+        """where the tally of (slot_start, slot_end, round_) lives in the range table: (capacity, home bucket, bucket);
+        bucket is -1 for an unknown key"""
+        cap, home, at = C.c_int32(), C.c_int32(), C.c_int32()
+        st = self.L.fpx_read_range_position(self._h, slot_start, slot_end, round_, C.byref(cap), C.byref(home), C.byref(at))
+        if st:
+            raise FpxError(st, "fpx_read_range_position")
+        return cap.value, home.value, at.value
 
     # ---- f1: replica log / f2: Phase-1 recovery scan ----------------------------------------------
     def replica_chosen(self, slot, value, mask=None):

@@ -146,6 +146,7 @@ struct fpx_ctx {
   int64_t census[FPX_CENSUS_WORDS] = {};
   int census_cell = 0;                       // the cell of the vote launch just enqueued
   int census_pending = 0, census_carry = 0;  // the cells of the launches whose folds are pending_fin / carry_fin
+  int64_t range_census[FPX_RANGE_CENSUS_WORDS] = {};  // fpx_range_launch_census: host counters of the K4 launches
   DevBuf d_enc;   // the device encoders' workgroup sums (fpx_wire_encode_*_dev)
   // fpx_wire_phase2_tick: the tick's bytes and offsets, its decoded records (kind, slot, round, is_noop, value_len, value_id,
   // value_off), the reply's bytes, offsets and totals
@@ -2240,6 +2241,7 @@ int32_t fpx_proxy_forget(fpx_ctx* ctx, int32_t first_slot, int32_t count) {
     if (rc) return rc;
     hipLaunchKernelGGL(k_ranges_rehash, dim3((from.cap + 255) / 256), dim3(256), 0, ctx->stream, from, to,
                        ctx->g.num_groups * 4, first_slot, count);
+    ++ctx->range_census[FPX_RANGE_CENSUS_REHASH];
     if ((rc = launch_check(ctx))) return rc;
     ctx->rt_cur ^= 1;
   }
@@ -2291,6 +2293,8 @@ static int enqueue_ranges(fpx_ctx* ctx, RangeBatch& b, int mode) {
   const long long chain_words = ranges_chain_words(b.n, g.num_groups);
   const bool chain = mode == RANGES_FUSED && b.n <= RANGES_CHAIN_MAX && chain_words <= RANGES_CHAIN_LDS_WORDS &&
                      (long long)b.n * g.num_groups * g.R <= 8 * 1024;
+  static const int only[4] = {-1, FPX_RANGE_CENSUS_ACCEPTORS_ONLY, FPX_RANGE_CENSUS_OPEN_ONLY, FPX_RANGE_CENSUS_TALLY_ONLY};
+  ++ctx->range_census[mode != RANGES_FUSED ? only[mode] : chain ? FPX_RANGE_CENSUS_CHAIN : FPX_RANGE_CENSUS_STEPS];
   if (chain) {
     allow_lds(k_ranges_chain, (size_t)chain_words * 4 + 64);
     hipLaunchKernelGGL(k_ranges_chain, dim3(1), dim3(1024), (size_t)chain_words * 4, ctx->stream, g, ctx->st, rt, b);
@@ -2312,6 +2316,7 @@ static int enqueue_ranges(fpx_ctx* ctx, RangeBatch& b, int mode) {
       const int gy = std::min(b.n, 4096);
       const int gx = std::max(1, std::min(ctx->num_cus * 16 / gy, 64));
       hipLaunchKernelGGL(k_ranges_fill_lg, dim3(gx, gy), dim3(256), 0, ctx->stream, g, ctx->st, b);
+      ++ctx->range_census[FPX_RANGE_CENSUS_FILL_LG];
     } else if (b.n <= RF_MAXN && g.num_leader_groups <= RF_MAXL) {
       // (RF_JB rows of L ownership words + the kernel's own 12 static bytes: beyond the default 64 KiB of dynamic LDS
       // the kernel needs the opt-in -- ADVICE r03: L close to 2048 failed every launch with FPX_EHIP)
@@ -2319,10 +2324,12 @@ static int enqueue_ranges(fpx_ctx* ctx, RangeBatch& b, int mode) {
       // sweep the log rows the ranges touch in memory order (fpx_ranges.hpp)
       hipLaunchKernelGGL(k_ranges_fill_rows, dim3(ctx->num_cus * 8), dim3(256), (size_t)RF_JB * g.num_leader_groups * 4,
                          ctx->stream, g, ctx->st, b);
+      ++ctx->range_census[FPX_RANGE_CENSUS_FILL_SWEEP];
     } else {
       const int gy = std::min(b.n, 4096);
       const int gx = std::max(1, std::min(ctx->num_cus * 16 / gy, 64));
       hipLaunchKernelGGL(k_ranges_fill, dim3(gx, gy), dim3(256), 0, ctx->stream, g, ctx->st, b);
+      ++ctx->range_census[FPX_RANGE_CENSUS_FILL_RANGE];
     }
   }
   if (mode == RANGES_TALLY) hipLaunchKernelGGL(k_ranges_open, dim3(gn), dim3(256), 0, ctx->stream, g, ctx->st, rt, b, 1);
@@ -2398,6 +2405,7 @@ static int enqueue_band_merged(fpx_ctx* ctx, Batch& b, RangeBatch& rb, bool* don
                      (int)b.parity, grid, b.launch_seq, fgx, slices);
   *done = true;
   ++ctx->band_merged_steps;
+  ++ctx->range_census[FPX_RANGE_CENSUS_BAND];
   return launch_check(ctx);
 }
 
@@ -2487,6 +2495,13 @@ int32_t fpx_vote_launch_census(fpx_ctx* ctx, int32_t cap, int64_t* out, int32_t*
   if (!ctx || cap < 0) return FPX_EINVAL;
   if (out) memcpy(out, ctx->census, sizeof(int64_t) * (size_t)std::min<int32_t>(cap, FPX_CENSUS_WORDS));
   if (n) *n = FPX_CENSUS_WORDS;
+  return FPX_OK;
+}
+
+int32_t fpx_range_launch_census(fpx_ctx* ctx, int64_t* out, int32_t cap, int32_t* n) {
+  if (!ctx || cap < 0) return FPX_EINVAL;
+  if (out) memcpy(out, ctx->range_census, sizeof(int64_t) * (size_t)std::min<int32_t>(cap, FPX_RANGE_CENSUS_WORDS));
+  if (n) *n = FPX_RANGE_CENSUS_WORDS;
   return FPX_OK;
 }
 
@@ -2618,22 +2633,44 @@ int32_t fpx_proxy_phase2b_noop_range(fpx_ctx* ctx, int32_t slot_start, int32_t s
   return fpx_proxy_phase2b_noop_ranges(ctx, 1, &slot_start, &slot_end, &round, vote_bits, newly_chosen);
 }
 
-// the proxy leader's tally of one range (parity): state 0 = unknown, 1 = Pending, 2 = Done; votes num_groups x 4 words
-int32_t fpx_read_range_tally(fpx_ctx* ctx, int32_t slot_start, int32_t slot_end, int32_t round, int32_t* state,
-                             uint64_t* vote_bits) {
-  DeviceGuard _dg(ctx);
+// the proxy leader's tally of one range (parity), as k_ranges_read leaves it: state, num_groups x 4 words of votes,
+// capacity, home bucket, bucket
+static int32_t read_range_entry(fpx_ctx* ctx, int32_t slot_start, int32_t slot_end, int32_t round, std::vector<uint64_t>* h) {
   int rc = ranges_ctx_ok(ctx, 0);
   if (rc) return rc;
   const size_t words = (size_t)ctx->g.num_groups * 4;
-  if ((rc = grow(ctx, &ctx->d_scratch, (words + 1) * 8))) return rc;
+  if ((rc = grow(ctx, &ctx->d_scratch, (words + 4) * 8))) return rc;
   hipLaunchKernelGGL(k_ranges_read, dim3(1), dim3(64), 0, ctx->stream, ctx->g, ctx->rt[ctx->rt_cur], slot_start, slot_end,
                      round, (uint64_t*)ctx->d_scratch.p);
   if ((rc = launch_check(ctx))) return rc;
-  std::vector<uint64_t> h(words + 1);
-  HIPCHK(ctx, hipMemcpyAsync(h.data(), ctx->d_scratch.p, h.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
+  h->resize(words + 4);
+  HIPCHK(ctx, hipMemcpyAsync(h->data(), ctx->d_scratch.p, h->size() * 8, hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  return FPX_OK;
+}
+
+// state 0 = unknown, 1 = Pending, 2 = Done; votes num_groups x 4 words
+int32_t fpx_read_range_tally(fpx_ctx* ctx, int32_t slot_start, int32_t slot_end, int32_t round, int32_t* state,
+                             uint64_t* vote_bits) {
+  DeviceGuard _dg(ctx);
+  std::vector<uint64_t> h;
+  int rc = read_range_entry(ctx, slot_start, slot_end, round, &h);
+  if (rc) return rc;
   if (state) *state = (int32_t)h[0];
-  if (vote_bits) memcpy(vote_bits, h.data() + 1, words * 8);
+  if (vote_bits) memcpy(vote_bits, h.data() + 1, (h.size() - 4) * 8);
+  return FPX_OK;
+}
+
+int32_t fpx_read_range_position(fpx_ctx* ctx, int32_t slot_start, int32_t slot_end, int32_t round, int32_t* capacity,
+                                int32_t* home_bucket, int32_t* bucket) {
+  DeviceGuard _dg(ctx);
+  std::vector<uint64_t> h;
+  int rc = read_range_entry(ctx, slot_start, slot_end, round, &h);
+  if (rc) return rc;
+  const size_t at = h.size() - 3;
+  if (capacity) *capacity = (int32_t)h[at];
+  if (home_bucket) *home_bucket = (int32_t)h[at + 1];
+  if (bucket) *bucket = h[at + 2] == ~0ull ? -1 : (int32_t)h[at + 2];
   return FPX_OK;
 }
 

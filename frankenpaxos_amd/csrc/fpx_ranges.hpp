@@ -705,7 +705,8 @@ __global__ void __launch_bounds__(256) k_ranges_rehash(const RangeTable from, co
   }
 }
 
-// readback of one range tally (parity): out[0] = state (0 unknown, 1 Pending, 2 Done), then A * 4 words of votes
+// readback of one range tally (parity): out[0] = state (0 unknown, 1 Pending, 2 Done), then A * 4 words of votes, then
+// where it lives: the table's capacity, the key's home bucket, the bucket of the entry (all ones: unknown key)
 __global__ void k_ranges_read(const Geom g, const RangeTable rt, int start, int end, int round, uint64_t* out) {
   if (blockIdx.x != 0 || threadIdx.x != 0) return;
   const int words = g.num_groups * 4;
@@ -714,12 +715,14 @@ __global__ void k_ranges_read(const Geom g, const RangeTable rt, int start, int 
   const uint64_t k0 = range_k0(start, end);
   const uint32_t mask = (uint32_t)rt.cap - 1u;
   uint32_t p = range_hash(k0) & mask;
+  out[1 + words] = (uint64_t)rt.cap, out[2 + words] = p, out[3 + words] = ~0ull;
   for (int probes = 0; probes < rt.cap; ++probes, p = (p + 1) & mask) {
     const uint64_t cur = rt.key[(size_t)p * 2];
     if (cur == 0) return;
     const uint64_t k1 = rt.key[(size_t)p * 2 + 1];
     if (cur == k0 && (uint32_t)((k1 >> 2) & 0x3fffffffu) == (uint32_t)round) {
       out[0] = k1 & 3u;
+      out[3 + words] = p;
       if ((k1 & 3u) == RT_PENDING)
         for (int w = 0; w < words; ++w) out[1 + w] = rt.bits[(size_t)p * words + w];
       return;

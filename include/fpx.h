@@ -495,6 +495,39 @@ enum {
 /* the census cell of (G, mode, ps, fused) as above: G_log2 = log2(G) */
 #define FPX_CENSUS_CELL(G_log2, mode, ps, fused) ((((G_log2) * 4 + (mode)) * 3 + (ps)) * 2 + (fused))
 int32_t fpx_vote_launch_census(fpx_ctx* ctx, int32_t cap, int64_t* out, int32_t* n);
+/* diagnostic: a census of the noop-range launches (K4, fpx_ranges.hpp) since fpx_create -- plain host counters like those
+ * of fpx_vote_launch_census, bumped where the host chooses a launch, once per device run (the host entry points cut a
+ * batch into runs of one round per leader group); reading them launches nothing and fpx_reset treats them as it treats the
+ * vote census (they count the life of the context).  Writes min(cap, FPX_RANGE_CENSUS_WORDS) int64 words to out and
+ * FPX_RANGE_CENSUS_WORDS to *n (either may be NULL).  A fused run (fpx_noop_ranges_fused*, the ranges of
+ * fpx_mencius_band_fused_dev) counts once under one of
+ *   FPX_RANGE_CENSUS_CHAIN   k_ranges_chain: one workgroup walks open -> resolve -> acceptors -> tally
+ *   FPX_RANGE_CENSUS_STEPS   the same steps as launches of their own (k_ranges_open, _resolve, _acceptors, _tally): more
+ *                            than 2048 ranges, more LDS than the chain may take, or more than 8192 acceptor threads
+ *   FPX_RANGE_CENSUS_BAND    the chain as the first workgroup of a band's vote kernel (k_phase2_band), its fill in
+ *                            k_ranges_fill_lg_fin (counted under no fill word)
+ * the unfused entry points once under FPX_RANGE_CENSUS_OPEN_ONLY (fpx_proxy_open_noop_range*),
+ * FPX_RANGE_CENSUS_ACCEPTORS_ONLY (fpx_acceptor_phase2a_noop_range*) or FPX_RANGE_CENSUS_TALLY_ONLY
+ * (fpx_proxy_phase2b_noop_range*), and every run with an acceptor step outside a band once under its fill:
+ *   FPX_RANGE_CENSUS_FILL_LG     k_ranges_fill_lg (leader-group-major rows)
+ *   FPX_RANGE_CENSUS_FILL_SWEEP  k_ranges_fill_rows (slot-ordered rows, at most 1024 ranges and 2048 leader groups)
+ *   FPX_RANGE_CENSUS_FILL_RANGE  k_ranges_fill (slot-ordered rows otherwise)
+ * FPX_RANGE_CENSUS_REHASH counts the moves of the range tallies to their other buffer (fpx_proxy_forget,
+ * fpx_recycle_slots with a window of at least one slot). */
+enum {
+  FPX_RANGE_CENSUS_CHAIN = 0,
+  FPX_RANGE_CENSUS_STEPS = 1,
+  FPX_RANGE_CENSUS_BAND = 2,
+  FPX_RANGE_CENSUS_FILL_LG = 3,
+  FPX_RANGE_CENSUS_FILL_SWEEP = 4,
+  FPX_RANGE_CENSUS_FILL_RANGE = 5,
+  FPX_RANGE_CENSUS_TALLY_ONLY = 6,
+  FPX_RANGE_CENSUS_OPEN_ONLY = 7,
+  FPX_RANGE_CENSUS_ACCEPTORS_ONLY = 8,
+  FPX_RANGE_CENSUS_REHASH = 9,
+  FPX_RANGE_CENSUS_WORDS = 10
+};
+int32_t fpx_range_launch_census(fpx_ctx* ctx, int64_t* out, int32_t cap, int32_t* n);
 /* batches of one (bitmaps num_groups x 4 words) */
 int32_t fpx_acceptor_phase2a_noop_range(fpx_ctx* ctx, int32_t slot_start, int32_t slot_end,
                                         int32_t round, const uint64_t* target_masks,
@@ -507,6 +540,12 @@ int32_t fpx_proxy_phase2b_noop_range(fpx_ctx* ctx, int32_t slot_start, int32_t s
  * unless Pending) */
 int32_t fpx_read_range_tally(fpx_ctx* ctx, int32_t slot_start, int32_t slot_end, int32_t round, int32_t* state,
                              uint64_t* vote_bits);
+/* readback (parity) of where that tally lives in the context's open-addressing table: capacity = the table's buckets (a
+ * power of two; at most capacity / 2 entries are live), home_bucket = the bucket the key's hash selects, computed on the
+ * device, bucket = the one the entry was found in by linear probing from there (wrapping from the last bucket to bucket
+ * 0), or -1 for an unknown key.  Any output may be NULL. */
+int32_t fpx_read_range_position(fpx_ctx* ctx, int32_t slot_start, int32_t slot_end, int32_t round, int32_t* capacity,
+                                int32_t* home_bucket, int32_t* bucket);
 
 /* ---- a9 (K5): EPaxos pre-accept fast path -------------------------------------------------------------
  * One tick of FRESH instances through the pre-accept phase of n = 2f+1 EPaxos replicas with the

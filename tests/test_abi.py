@@ -74,6 +74,22 @@ def test_vote_launch_census_layout_matches_the_binding(fa, tmp_path):
     assert fa._lib.SIGNATURES["fpx_vote_launch_census"][0] is C.c_int32
 
 
+def test_range_launch_census_layout_matches_the_binding(fa, tmp_path):
+    """the words of fpx_range_launch_census (include/fpx.h) in the order Context.range_launch_census names them"""
+    names = ("CHAIN", "STEPS", "BAND", "FILL_LG", "FILL_SWEEP", "FILL_RANGE", "TALLY_ONLY", "OPEN_ONLY", "ACCEPTORS_ONLY",
+             "REHASH", "WORDS")
+    src = tmp_path / "r.c"
+    src.write_text('#include <stdio.h>\n#include "fpx.h"\nint main(void){printf("%s\\n", %s); return 0;}\n'
+                   % (" ".join(["%d"] * len(names)), ", ".join("FPX_RANGE_CENSUS_" + x for x in names)))
+    exe = tmp_path / "r"
+    assert os.system("gcc -std=c99 -Wall -Werror -I%s %s -o %s" % (os.path.join(ROOT, "include"), src, exe)) == 0
+    got = list(map(int, os.popen(str(exe)).read().split()))
+    forms = fa._lib.RANGE_CENSUS_FORMS
+    assert got == list(range(len(forms) + 1)) and tuple(x.lower() for x in names[:-1]) == forms
+    assert fa._lib.SIGNATURES["fpx_range_launch_census"] == (C.c_int32, [C.c_void_p, C.POINTER(C.c_int64), C.c_int32,
+                                                                         C.POINTER(C.c_int32)])
+
+
 def test_config_struct_layout_matches_the_oracle(fa, oracle):
     a, b = fa.FpxConfig, oracle.Config
     assert [(n, t) for n, t in a._fields_] == [(n, t) for n, t in b._fields_]
