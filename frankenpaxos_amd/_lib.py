@@ -165,6 +165,9 @@ SIGNATURES = {
     "fpx_replica_read_log": (C.c_int32, [VP, C.c_int32, C.c_int32, VP, VP]),
     "fpx_leader_phase1b_scan": (C.c_int32, [VP, C.c_int32, VP, C.c_int32, I32P, VP, VP]),
     "fpx_acceptor_phase1b_info": (C.c_int32, [VP, C.c_int32, C.c_int32, C.c_int32, C.c_int32, I32P, VP, VP, VP]),
+    "fpx_acceptor_phase1b_info_all_dev": (C.c_int32, [VP, C.c_int32, VP, C.c_int64, VP, VP, VP, VP, VP]),
+    "fpx_acceptor_phase1b_info_all": (C.c_int32, [VP, C.c_int32, VP, C.c_int64, VP, VP, VP, VP, C.POINTER(C.c_int64)]),
+    "fpx_acceptor_phase1": (C.c_int32, [VP, C.c_int32, C.c_int32, VP, VP, VP, C.c_int64, VP, VP, VP, VP, C.POINTER(C.c_int64)]),
     "fpx_read_acceptor": (C.c_int32, [VP, C.c_int32, C.c_int32, I32P, I32P, VP, VP, VP]),
     "fpx_read_state": (C.c_int32, [VP, VP, VP, VP]),
     "fpx_read_scalars": (C.c_int32, [VP, VP, VP]),

@@ -610,6 +610,55 @@ class Context:
                 raise FpxError(st, "fpx_acceptor_phase1b_info")
         return sl, vr, vv
 
+    def _p1_masks(self, masks):
+        return None if masks is None else np.ascontiguousarray(masks, dtype=np.uint64).reshape(self.ngroups, 4)
+
+    def acceptor_phase1b_info_all(self, watermark=0, masks=None):
+        """Phase1b.info of every selected acceptor in one device pass: (offsets, slot, vote_round, vote_value); entry
+        e = group * R + replica owns offsets[e]:offsets[e + 1].  masks: ngroups x 4 uint64 (acceptor_phase1a's target
+        bits) or None = all.  Sizes with one cap = 0 call."""
+        masks = self._p1_masks(masks)
+        off = np.zeros(self.ngroups * self.R + 1, np.int64)
+        k = C.c_int64()
+        st = self.L.fpx_acceptor_phase1b_info_all(self._h, watermark, _hp(masks), 0, _hp(off), None, None, None, C.byref(k))
+        if st not in (0, _lib.FPX_ECAPACITY):
+            raise FpxError(st, "fpx_acceptor_phase1b_info_all")
+        return (off,) + self._p1_fill(watermark, masks, k.value, off)
+
+    def _p1_fill(self, watermark, masks, n, off):
+        """the records of a pass whose sizing call counted n: one call with cap = n"""
+        sl, vr, vv = (np.zeros(n, np.int32) for _ in range(3))
+        if n:
+            k = C.c_int64()
+            st = self.L.fpx_acceptor_phase1b_info_all(self._h, watermark, _hp(masks), n, _hp(off), _hp(sl), _hp(vr), _hp(vv),
+                                                      C.byref(k))
+            if st:
+                raise FpxError(st, "fpx_acceptor_phase1b_info_all")
+        return sl, vr, vv
+
+    def acceptor_phase1b_info_all_dev(self, watermark, masks, cap, offsets, slot, vote_round, vote_value, totals):
+        """asynchronous form on torch CUDA tensors: masks ngroups x 4 int64 words or None, offsets E + 1 int64, the
+        record arrays int32 of at least cap elements (None with cap = 0), totals 2 int64 (needed, written)"""
+        st = self.L.fpx_acceptor_phase1b_info_all_dev(self._h, watermark, _dp(masks), cap, _dp(offsets), _dp(slot),
+                                                      _dp(vote_round), _dp(vote_value), _dp(totals))
+        if st:
+            raise FpxError(st, "fpx_acceptor_phase1b_info_all_dev")
+
+    def acceptor_phase1(self, round_, watermark=0, masks=None):
+        """A Leader's Phase1a at every acceptor it addresses: (promised_bits, nack_bits, offsets, slot, vote_round,
+        vote_value), the bits ngroups x 4, the info of exactly the acceptors that promised.  The round moves once, in a
+        sizing call; the records are fetched behind it by one fpx_acceptor_phase1b_info_all on the promised bits."""
+        masks = self._p1_masks(masks)
+        pb = np.zeros((self.ngroups, 4), np.uint64)
+        nb = np.zeros((self.ngroups, 4), np.uint64)
+        off = np.zeros(self.ngroups * self.R + 1, np.int64)
+        k = C.c_int64()
+        st = self.L.fpx_acceptor_phase1(self._h, round_, watermark, _hp(masks), _hp(pb), _hp(nb), 0, _hp(off), None, None,
+                                        None, C.byref(k))
+        if st not in (0, _lib.FPX_ECAPACITY):
+            raise FpxError(st, "fpx_acceptor_phase1")
+        return (pb, nb, off) + self._p1_fill(watermark, pb, k.value, off)
+
     # ---- readback ------------------------------------------------------------------------------
     def read_acceptor(self, group, replica):
         p, m = C.c_int32(), C.c_int32()

@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "fpx_kernels.hpp"
+#include "fpx_phase1_info.hpp"
 #include "fpx_ranges.hpp"
 #include "fpx_tally_msgs.hpp"
 #include "fpx_wire_dev.hpp"
@@ -154,6 +155,9 @@ struct fpx_ctx {
   // fpx_proxy_phase2b_msgs_dev (fpx_tally_msgs.hpp): the owner word of every tally entry ([S][wp], INT_MAX between calls;
   // allocated by the first call), and per call the messages' entries, the gathered rows and the compaction's workgroup sums
   DevBuf m_owner, m_entry, m_rows, m_blk;
+  // fpx_acceptor_phase1b_info_all[_dev] (fpx_phase1_info.hpp): the chunk counts, column totals and the go word; the host
+  // form's offsets and totals
+  DevBuf p1i, p1i_off, p1i_tot;
   DevBuf d_band;  // [num_leader_groups] marks: the leader groups with a range in the step being checked
   // multi-GPU (fpx_comm_*): one communicator per context, rank = this context's GPU
   RcclComm comm = nullptr;
@@ -1009,7 +1013,8 @@ void free_state(fpx_ctx* ctx) {
                   &rs.chosen,     &rs.target,    &rs.votes,     &rs.nacks,
                   &ctx->d_enc,    &ctx->w_buf,   &ctx->w_off,   &ctx->w_out,    &ctx->w_ooff,   &ctx->w_tot,
                   &ctx->w_rec[0], &ctx->w_rec[1], &ctx->w_rec[2], &ctx->w_rec[3], &ctx->w_rec[4], &ctx->w_rec[5],
-                  &ctx->w_rec[6], &ctx->m_owner, &ctx->m_entry,  &ctx->m_rows,   &ctx->m_blk};
+                  &ctx->w_rec[6], &ctx->m_owner, &ctx->m_entry,  &ctx->m_rows,   &ctx->m_blk,
+                  &ctx->p1i,      &ctx->p1i_off, &ctx->p1i_tot};
   for (DevBuf* b : bs)
     if (b->p) (void)hipFree(b->p);
   for (hipEvent_t e : ctx->ev) (void)hipEventDestroy(e);
@@ -1340,6 +1345,76 @@ int host_fused_staged(fpx_ctx* ctx, int n, const int32_t* slot, const int32_t* r
   // not one device run: cut into runs on the host and replayed (from the copy-engine path's staging buffers)
   *used = false;
   return FPX_OK;
+}
+
+// ---- Phase1b.info of every selected acceptor in one pass (fpx_phase1_info.hpp) ------------------------------------
+template <int G>
+void launch_p1i(fpx_ctx* ctx, const P1iArgs& a, int grid) {
+  hipLaunchKernelGGL((k_p1i_count<G>), dim3(grid), dim3(256), 0, ctx->stream, ctx->g, ctx->st, a);
+  hipLaunchKernelGGL(k_p1i_colscan, dim3((a.ES + P1I_COLS - 1) / P1I_COLS), dim3(P1I_COLS * P1I_SEGS), 0, ctx->stream, ctx->st, a);
+  hipLaunchKernelGGL(k_p1i_offsets, dim3(1), dim3(1024), 0, ctx->stream, ctx->g, ctx->st, a);
+  // the scatter: one wavefront per workgroup and (chunk, group, block of 64 acceptors), three workgroups' LDS to a CU
+  const int64_t units = (int64_t)a.nchunks * ctx->g.ngroups * (G < 16 ? 1 : G / 16);
+  const int sgrid = (int)std::max<int64_t>(1, std::min<int64_t>(units, (int64_t)ctx->num_cus * 12));
+  hipLaunchKernelGGL((k_p1i_scatter<G>), dim3(sgrid), dim3(64), 0, ctx->stream, ctx->g, ctx->st, a);
+}
+
+bool p1i_args_ok(const fpx_ctx* ctx, int64_t cap, const int64_t* offsets, const int32_t* slot, const int32_t* vote_round,
+                        const int32_t* vote_value, const int64_t* totals) {
+  return ctx && cap >= 0 && offsets && totals && (cap == 0 || (slot && vote_round && vote_value));
+}
+
+int enqueue_p1i(fpx_ctx* ctx, int32_t chosen_watermark, const uint64_t* d_masks, int64_t cap, int64_t* d_offsets,
+                       int32_t* d_slot, int32_t* d_vote_round, int32_t* d_vote_value, int64_t* d_totals) {
+  const Geom& g = ctx->g;
+  P1iArgs a;
+  memset(&a, 0, sizeof(a));
+  a.masks = d_masks;
+  a.lo = chosen_watermark < 0 ? 0 : chosen_watermark;
+  a.vec = ctx->vec ? 1 : 0;
+  const int64_t span = (int64_t)P1I_TILE * g.ngroups;
+  a.ntiles = (int32_t)((g.S + span - 1) / span);
+  a.nchunks = (a.ntiles + P1I_CHUNK - 1) / P1I_CHUNK;
+  a.ES = g.ngroups * g.RS;
+  int rc;
+  if ((rc = grow(ctx, &ctx->p1i, ((size_t)a.nchunks * a.ES + a.ES + 4) * 4))) return rc;
+  a.csum = (int32_t*)ctx->p1i.p;
+  a.ctot = a.csum + (size_t)a.nchunks * a.ES;
+  a.go = a.ctot + a.ES;
+  a.cap = cap;
+  a.offsets = d_offsets, a.slot = d_slot, a.vote_round = d_vote_round, a.vote_value = d_vote_value, a.totals = d_totals;
+  // one wavefront per (chunk, group), four to a workgroup, grid-stride beyond num_cus * 8 workgroups
+  const int64_t units = (int64_t)a.nchunks * g.ngroups;
+  const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((units + 3) / 4, (int64_t)ctx->num_cus * 8));
+  switch (ctx->lanes_per_slot) {
+    case 1: launch_p1i<1>(ctx, a, grid); break;
+    case 2: launch_p1i<2>(ctx, a, grid); break;
+    case 4: launch_p1i<4>(ctx, a, grid); break;
+    case 8: launch_p1i<8>(ctx, a, grid); break;
+    case 16: launch_p1i<16>(ctx, a, grid); break;
+    case 32: launch_p1i<32>(ctx, a, grid); break;
+    default: launch_p1i<64>(ctx, a, grid); break;
+  }
+  return launch_check(ctx);
+}
+
+// the host form's staging: the masks up (d_bits_a), offsets / records / totals down -- ONE run of the staging driver
+int host_p1i(fpx_ctx* ctx, int32_t chosen_watermark, const uint64_t* masks, bool masks_staged, int64_t cap, int64_t* offsets,
+                    int32_t* slot, int32_t* vote_round, int32_t* vote_value, int64_t* count) {
+  const size_t E = (size_t)ctx->g.ngroups * ctx->g.R, mbytes = (size_t)ctx->g.ngroups * 32, rec = (size_t)cap * 4;
+  int64_t totals[2] = {0, 0};
+  const bool up = masks && !masks_staged;
+  const int rc = host_batch(
+      ctx, 1, {{&ctx->d_bits_a, up ? masks : nullptr, 0, mbytes}},
+      {{&ctx->p1i_off, offsets, 0, (E + 1) * 8}, {&ctx->d_i32_a, slot, 0, rec}, {&ctx->d_i32_b, vote_round, 0, rec},
+       {&ctx->d_i32_c, vote_value, 0, rec}, {&ctx->p1i_tot, totals, 0, 16}},
+      nullptr, [&](int, int) {
+        return enqueue_p1i(ctx, chosen_watermark, masks ? (const uint64_t*)ctx->d_bits_a.p : nullptr, cap,
+                           (int64_t*)ctx->p1i_off.p, (int32_t*)ctx->d_i32_a.p, (int32_t*)ctx->d_i32_b.p, (int32_t*)ctx->d_i32_c.p,
+                           (int64_t*)ctx->p1i_tot.p);
+      });
+  if (count) *count = totals[0];
+  return rc;
 }
 
 }  // namespace
@@ -2940,6 +3015,58 @@ int32_t fpx_acceptor_phase1b_info(fpx_ctx* ctx, int32_t group, int32_t replica, 
   }
   *count = k;
   return FPX_OK;
+}
+
+int32_t fpx_acceptor_phase1b_info_all_dev(fpx_ctx* ctx, int32_t chosen_watermark, const uint64_t* d_acceptor_masks, int64_t cap,
+                                          int64_t* d_offsets, int32_t* d_slot, int32_t* d_vote_round, int32_t* d_vote_value,
+                                          int64_t* d_totals) {
+  if (!p1i_args_ok(ctx, cap, d_offsets, d_slot, d_vote_round, d_vote_value, d_totals)) return FPX_EINVAL;
+  DeviceGuard _dg(ctx->cfg.device);  // (the scan is [watermark, S), never bounded by max_voted: a pending fold stays pending)
+  return enqueue_p1i(ctx, chosen_watermark, d_acceptor_masks, cap, d_offsets, d_slot, d_vote_round, d_vote_value, d_totals);
+}
+
+int32_t fpx_acceptor_phase1b_info_all(fpx_ctx* ctx, int32_t chosen_watermark, const uint64_t* acceptor_masks, int64_t cap,
+                                      int64_t* offsets, int32_t* slot, int32_t* vote_round, int32_t* vote_value, int64_t* count) {
+  if (!p1i_args_ok(ctx, cap, offsets, slot, vote_round, vote_value, count)) return FPX_EINVAL;
+  DeviceGuard _dg(ctx->cfg.device);
+  int rc;
+  if ((rc = grow(ctx, &ctx->d_bits_a, (size_t)ctx->g.ngroups * 32))) return rc;  // (host_batch stages only what it uploads)
+  return host_p1i(ctx, chosen_watermark, acceptor_masks, false, cap, offsets, slot, vote_round, vote_value, count);
+}
+
+int32_t fpx_acceptor_phase1(fpx_ctx* ctx, int32_t round, int32_t chosen_watermark, const uint64_t* target_masks,
+                            uint64_t* promised_bits, uint64_t* nack_bits, int64_t cap, int64_t* offsets, int32_t* slot,
+                            int32_t* vote_round, int32_t* vote_value, int64_t* count) {
+  if (!p1i_args_ok(ctx, cap, offsets, slot, vote_round, vote_value, count) || round < 0 || round > MAX_ROUND) return FPX_EINVAL;
+  DeviceGuard _dg(ctx->cfg.device);  // (enqueue_phase1a deals with a pending fold)
+  const int ng = ctx->g.ngroups;
+  const size_t words = (size_t)ng * 4;
+  int rc;
+  // d_bits_a: the promised bits (the info pass's masks); d_bits_b: the nack bits, then the targets
+  if ((rc = grow(ctx, &ctx->d_bits_a, words * 8))) return rc;
+  if ((rc = grow(ctx, &ctx->d_bits_b, 2 * words * 8))) return rc;
+  uint64_t *d_prom = (uint64_t*)ctx->d_bits_a.p, *d_nack = (uint64_t*)ctx->d_bits_b.p, *d_tgt = d_nack + words;
+  if (target_masks) HIPCHK(ctx, hipMemcpyAsync(d_tgt, target_masks, words * 8, hipMemcpyHostToDevice, ctx->stream));
+  // the reply bits of the groups nobody addressed (the Phase1a kernels write an addressed group's in full)
+  HIPCHK(ctx, hipMemsetAsync(d_prom, 0, words * 8, ctx->stream));
+  HIPCHK(ctx, hipMemsetAsync(d_nack, 0, words * 8, ctx->stream));
+  for (int grp = 0; grp < ng; ++grp) {
+    if (target_masks) {
+      const uint64_t* t = target_masks + (size_t)grp * 4;
+      bool any = false;
+      for (int w = 0; w < 4; ++w) any = any || (t[w] & ctx->g.member[w]) != 0;
+      if (!any) continue;  // nobody of the group is addressed
+    }
+    if ((rc = enqueue_phase1a(ctx, grp, round, chosen_watermark, target_masks ? d_tgt + (size_t)grp * 4 : nullptr,
+                              d_prom + (size_t)grp * 4, d_nack + (size_t)grp * 4)))
+      return rc;
+  }
+  rc = host_p1i(ctx, chosen_watermark, d_prom, true, cap, offsets, slot, vote_round, vote_value, count);  // (synchronises)
+  // the reply bits last, straight into the caller's arrays (host_p1i leaves d_bits_a / d_bits_b alone)
+  if (promised_bits) HIPCHK(ctx, hipMemcpyAsync(promised_bits, d_prom, words * 8, hipMemcpyDeviceToHost, ctx->stream));
+  if (nack_bits) HIPCHK(ctx, hipMemcpyAsync(nack_bits, d_nack, words * 8, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  return rc;
 }
 
 // ---- multi-GPU: RCCL behind the C ABI ------------------------------------------------------------------

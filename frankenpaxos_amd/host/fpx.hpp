@@ -346,6 +346,49 @@ class Phase2Engine {
     return out;
   }
 
+  // ---- a Leader's Phase1a at EVERY acceptor it addresses, one call (fpx_acceptor_phase1): acceptors[g] = the acceptor
+  // indices of group g the Phase1a goes to (an empty outer vector => everybody).  Returns per entry
+  // g * numReplicas + acceptor the Phase1b.info of the acceptors that promised (votes in slots >= chosenWatermark,
+  // ascending); the others -- Nackers and acceptors nobody addressed -- have promised[e] == false and no info.
+  struct Phase1bSlotInfo { int32_t slot, voteRound, voteValue; };
+  struct Phase1Result {
+    std::vector<bool> promised, nacked;               // per entry
+    std::vector<std::vector<Phase1bSlotInfo>> info;   // per entry
+  };
+  Phase1Result acceptorsHandlePhase1aAll(int round, int chosenWatermark, const std::vector<std::vector<int>>& acceptors = {}) {
+    const int ng = fcfg_.num_groups * fcfg_.num_leader_groups, R = fcfg_.num_replicas;
+    if (!acceptors.empty() && (int)acceptors.size() != ng) throw std::invalid_argument("one acceptor list per group");
+    std::vector<uint64_t> tgt((size_t)ng * 4, 0), promised((size_t)ng * 4), nack((size_t)ng * 4);
+    for (size_t g = 0; g < acceptors.size(); ++g)
+      for (int a : acceptors[g]) {
+        if (a < 0 || a >= R) throw std::invalid_argument("acceptor index out of range");
+        tgt[g * 4 + (a >> 6)] |= 1ull << (a & 63);
+      }
+    std::vector<int64_t> off((size_t)ng * R + 1);
+    std::vector<int32_t> slot, vr, vv;
+    int64_t count = 0;
+    const uint64_t* masks = acceptors.empty() ? nullptr : tgt.data();
+    int32_t st = fpx_acceptor_phase1(ctx_, round, chosenWatermark, masks, promised.data(), nack.data(), 0, off.data(), nullptr,
+                                     nullptr, nullptr, &count);
+    if (st != FPX_OK && st != FPX_ECAPACITY) check(st, "Acceptor.handlePhase1a (all)");
+    if (count > 0) {  // the promises hold: the records of exactly the promisers
+      slot.resize((size_t)count), vr.resize((size_t)count), vv.resize((size_t)count);
+      check(fpx_acceptor_phase1b_info_all(ctx_, chosenWatermark, promised.data(), count, off.data(), slot.data(), vr.data(),
+                                          vv.data(), &count),
+            "Acceptor.handlePhase1a (info)");
+    }
+    Phase1Result out;
+    out.promised.resize((size_t)ng * R), out.nacked.resize((size_t)ng * R), out.info.resize((size_t)ng * R);
+    for (int g = 0; g < ng; ++g)
+      for (int a = 0; a < R; ++a) {
+        const size_t e = (size_t)g * R + a;
+        out.promised[e] = (promised[(size_t)g * 4 + (a >> 6)] >> (a & 63)) & 1;
+        out.nacked[e] = (nack[(size_t)g * 4 + (a >> 6)] >> (a & 63)) & 1;
+        for (int64_t j = off[e]; j < off[e + 1]; ++j) out.info[e].push_back(Phase1bSlotInfo{slot[j], vr[j], vv[j]});
+      }
+    return out;
+  }
+
   // ---- Acceptor.handleMaxSlotRequest / handleBatchMaxSlotRequest (Acceptor.scala:222-254): what the reply's `slot` is --
   // the acceptor's maxVotedSlot, over the whole log or over the slots [firstSlot, firstSlot + count) of it
   int acceptorMaxVotedSlot(int groupIndex, int acceptorIndex, int firstSlot = 0, int count = -1) {

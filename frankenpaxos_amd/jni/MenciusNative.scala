@@ -208,6 +208,66 @@ class GpuMenciusEngine[Transport <: frankenpaxos.Transport[Transport]](
     Right(Phase1b(groupIndex = acceptorGroup, acceptorIndex = index, round = phase1a.round, info = info))
   }
 
+  // ---- Phase 1 for a burst of Phase1as, as GpuPhase2Engine's: a new leader of a leader group sends one to every
+  // acceptor address of that group (mencius/Leader.scala:486-491), and they arrive together.  The GpuMenciusAcceptors
+  // enqueue them here; the zero-delay timer of the first one flushes the burst: maximal runs of equal
+  // (round, chosenWatermark), ONE native call per run (fpx_acceptor_phase1 over the L * A context groups, only the
+  // addressed ones with a non-empty mask), each acceptor answered from its slice.  As in handlePhase1a the call runs with
+  // watermark row 0; the per-slot filter and slotOfRow stay here.
+  private val pendingPhase1as = mutable.Buffer[(Int, Int, Int, Phase1a, Either[Nack, Phase1b] => Unit)]()
+
+  // true: the queue was empty -- the caller starts its tick
+  def enqueuePhase1a(leaderGroup: Int, acceptorGroup: Int, index: Int, phase1a: Phase1a,
+                     reply: Either[Nack, Phase1b] => Unit): Boolean = {
+    val first = pendingPhase1as.isEmpty
+    pendingPhase1as += ((leaderGroup, acceptorGroup, index, phase1a, reply))
+    first
+  }
+
+  def flushPhase1as(): Unit = {
+    var rest = pendingPhase1as.toList
+    pendingPhase1as.clear()
+    while (rest.nonEmpty) {
+      val key = (rest.head._4.round, rest.head._4.chosenWatermark)
+      val (run, later) = rest.span(m => (m._4.round, m._4.chosenWatermark) == key)
+      rest = later
+      if (run.size == 1) run.head._5(handlePhase1a(run.head._1, run.head._2, run.head._3, run.head._4))   // a lone message
+      else phase1Run(run)
+    }
+  }
+
+  private def phase1Run(run: List[(Int, Int, Int, Phase1a, Either[Nack, Phase1b] => Unit)]): Unit = {
+    val phase1a = run.head._4
+    val ctxGroups = L * A
+    val words = 4 * ctxGroups
+    val target = new Array[Long](words)
+    for ((l, a, i, _, _) <- run) target(4 * ctxGroup(l, a) + (i >> 6)) |= 1L << (i & 63)
+    val bits = new Array[Long](2 * words)
+    val offsets = new Array[Long](ctxGroups * R + 1)
+    var cap = 1024 * run.size
+    var slots = new Array[Int](cap); var vr = new Array[Int](cap); var vv = new Array[Int](cap)
+    var k = Native.acceptorPhase1All(handle, phase1a.round, 0, ctxGroups, target, bits, cap, offsets, slots, vr, vv)
+    if (k > cap) {
+      // the promises hold; the same call again answers the same (a promiser promises its own round again)
+      cap = k.toInt; slots = new Array[Int](cap); vr = new Array[Int](cap); vv = new Array[Int](cap)
+      k = Native.acceptorPhase1All(handle, phase1a.round, 0, ctxGroups, target, bits, cap, offsets, slots, vr, vv)
+    }
+    if (k < 0) Native.check((-k).toInt, logger)
+    for ((l, a, i, p, reply) <- run) {
+      val g = ctxGroup(l, a)
+      if ((bits(words + 4 * g + (i >> 6)) & (1L << (i & 63))) != 0) {
+        reply(Left(Nack(round = Native.acceptorRound(handle, g, i))))                    // mencius/Acceptor.scala:173-180
+      } else {
+        val e = g * R + i
+        val info = (offsets(e).toInt until offsets(e + 1).toInt)                         // :184-199
+          .map(j => Phase1bSlotInfo(slot = slotOfRow(slots(j)), voteRound = vr(j), voteValue = valueOf(vv(j))))
+          .filter(_.slot >= p.chosenWatermark)
+          .sortBy(_.slot)
+        reply(Right(Phase1b(groupIndex = a, acceptorIndex = i, round = p.round, info = info)))
+      }
+    }
+  }
+
   def close(): Unit = Native.check(Native.destroy(handle), logger)
 }
 
@@ -291,14 +351,19 @@ class GpuMenciusAcceptor[Transport <: frankenpaxos.Transport[Transport]](
     if addr == address
   } yield (l, a, i)).head
 
+  // one tick, as GpuMenciusProxyLeader's: "after the messages already queued on the event loop" -- the Phase1as of a burst
+  private val phase1Tick = timer("gpuMenciusPhase1Tick", java.time.Duration.ZERO, () => engine.flushPhase1as())
+
   override def receive(src: Transport#Address, inbound: AcceptorInbound): Unit = {
     inbound.request match {
       case AcceptorInbound.Request.Phase1A(phase1a) =>
+        // enqueued, not answered: the burst a new leader sends is flushed by one tick (engine.flushPhase1as)
         val leader = chan[Leader[Transport]](src, Leader.serializer)
-        engine.handlePhase1a(leaderGroup, acceptorGroup, index, phase1a) match {
+        val reply: Either[Nack, Phase1b] => Unit = {
           case Left(nack)     => leader.send(LeaderInbound().withNack(nack))        // mencius/Acceptor.scala:173-180
           case Right(phase1b) => leader.send(LeaderInbound().withPhase1B(phase1b))  // :184-199
         }
+        if (engine.enqueuePhase1a(leaderGroup, acceptorGroup, index, phase1a, reply)) phase1Tick.start()
       case AcceptorInbound.Request.Phase2A(_) | AcceptorInbound.Request.Phase2ANoopRange(_) =>
         // the reference's leaders send these to PROXY LEADERS (mencius/Leader.scala:342-345, 455); a deployment that
         // points them at GpuMenciusProxyLeader never delivers one here

@@ -178,6 +178,12 @@ object Native {
   // fpx_recycle_slots, fpx_proxy_forget)
   @native def acceptorPhase1bInfo(handle: Long, group: Int, replica: Int, chosenWatermark: Int, cap: Int,
                                   slot: Array[Int], voteRound: Array[Int], voteValue: Array[Int]): Int // count, < 0: -status
+  // a Leader's Phase1a at every acceptor it addresses in ONE call (fpx_acceptor_phase1): targetMasks 4 x numGroups words
+  // (null: everybody), bits = promised | nack (4 x numGroups words each), entry group * perGroup + replica owns
+  // offsets(e) until offsets(e + 1) of the record arrays (empty unless it promised); count, < 0: -status
+  @native def acceptorPhase1All(handle: Long, round: Int, chosenWatermark: Int, numGroups: Int, targetMasks: Array[Long],
+                                bits: Array[Long], cap: Int, offsets: Array[Long], slot: Array[Int],
+                                voteRound: Array[Int], voteValue: Array[Int]): Long
   @native def acceptorRound(handle: Long, group: Int, replica: Int): Int // Acceptor.round, < -1: -status - 1
   // the largest row of [firstRow, firstRow + count) in which the acceptor holds a vote, -1: none, < -1: -status - 1
   @native def acceptorMaxVotedIn(handle: Long, group: Int, replica: Int, firstRow: Int, count: Int): Int
@@ -503,6 +509,66 @@ class GpuPhase2Engine[Transport <: frankenpaxos.Transport[Transport]](
     Right(Phase1b(groupIndex = groupIndex, acceptorIndex = index, round = phase1a.round, info = info))
   }
 
+  // ---- Phase 1 for a burst of Phase1as: a new leader sends one to every acceptor address, and they arrive together.
+  // The GpuAcceptors enqueue them here; the zero-delay timer of the first one flushes the burst: maximal runs of equal
+  // (round, chosenWatermark), ONE native call per run (fpx_acceptor_phase1: the round movement of every addressed group,
+  // then the Phase1b.info of exactly the promisers, compacted on the device), each acceptor answered from its slice.
+  // As in handlePhase1a the call runs with watermark row 0; the per-slot filter and slotOfRow stay here.
+  private val pendingPhase1as = mutable.Buffer[(Int, Int, Phase1a, Either[Nack, Phase1b] => Unit)]()
+
+  // true: the queue was empty -- the caller starts its tick
+  def enqueuePhase1a(groupIndex: Int, index: Int, phase1a: Phase1a, reply: Either[Nack, Phase1b] => Unit): Boolean = {
+    val first = pendingPhase1as.isEmpty
+    pendingPhase1as += ((groupIndex, index, phase1a, reply))
+    first
+  }
+
+  def flushPhase1as(): Unit = {
+    var rest = pendingPhase1as.toList
+    pendingPhase1as.clear()
+    while (rest.nonEmpty) {
+      val key = (rest.head._3.round, rest.head._3.chosenWatermark)
+      val (run, later) = rest.span(m => (m._3.round, m._3.chosenWatermark) == key)
+      rest = later
+      if (run.size == 1) run.head._4(handlePhase1a(run.head._1, run.head._2, run.head._3))   // a lone message
+      else phase1Run(run)
+    }
+  }
+
+  private def phase1Run(run: List[(Int, Int, Phase1a, Either[Nack, Phase1b] => Unit)]): Unit = {
+    val phase1a = run.head._3
+    val words = 4 * ctxGroups
+    val target = new Array[Long](words)
+    for ((g, i, _, _) <- run) {
+      val a = ctxReplica(g, i)
+      target(4 * ctxGroup(g) + (a >> 6)) |= 1L << (a & 63)
+    }
+    val bits = new Array[Long](2 * words)
+    val offsets = new Array[Long](ctxGroups * ctxReplicas + 1)
+    var cap = 1024 * run.size
+    var slots = new Array[Int](cap); var vr = new Array[Int](cap); var vv = new Array[Int](cap)
+    var k = Native.acceptorPhase1All(handle, phase1a.round, 0, ctxGroups, target, bits, cap, offsets, slots, vr, vv)
+    if (k > cap) {
+      // the promises hold; the same call again answers the same (a promiser promises its own round again)
+      cap = k.toInt; slots = new Array[Int](cap); vr = new Array[Int](cap); vv = new Array[Int](cap)
+      k = Native.acceptorPhase1All(handle, phase1a.round, 0, ctxGroups, target, bits, cap, offsets, slots, vr, vv)
+    }
+    if (k < 0) Native.check((-k).toInt, logger)
+    for ((g, i, p, reply) <- run) {
+      val cg = ctxGroup(g); val a = ctxReplica(g, i)
+      if ((bits(words + 4 * cg + (a >> 6)) & (1L << (a & 63))) != 0) {
+        reply(Left(Nack(round = Native.acceptorRound(handle, cg, a))))                  // Acceptor.scala:155-162
+      } else {
+        val e = cg * ctxReplicas + a
+        val info = (offsets(e).toInt until offsets(e + 1).toInt)                        // Acceptor.scala:163-181
+          .map(j => Phase1bSlotInfo(slot = slotOfRow(slots(j)), voteRound = vr(j), voteValue = valueOf(vv(j))))
+          .filter(_.slot >= p.chosenWatermark)
+          .sortBy(_.slot)
+        reply(Right(Phase1b(groupIndex = g, acceptorIndex = i, round = p.round, info = info)))
+      }
+    }
+  }
+
   // a Phase2a sent straight to one acceptor (not how the reference's Leader sends them, but part of
   // AcceptorInbound): Acceptor.handlePhase2a, multipaxos/Acceptor.scala:184-220
   def handlePhase2a(groupIndex: Int, index: Int, p: Phase2a): Either[Nack, Phase2b] = {
@@ -616,15 +682,19 @@ class GpuAcceptor[Transport <: frankenpaxos.Transport[Transport]](
   private val groupIndex = config.acceptorAddresses.indexWhere(_.contains(address))
   private val index = config.acceptorAddresses(groupIndex).indexOf(address)
   private val roundSystem = new RoundSystem.ClassicRoundRobin(config.numLeaders)
+  // one tick, as GpuProxyLeader's: "after the messages already queued on the event loop" -- the Phase1as of a burst
+  private val phase1Tick = timer("gpuPhase1Tick", java.time.Duration.ZERO, () => engine.flushPhase1as())
 
   override def receive(src: Transport#Address, inbound: AcceptorInbound): Unit = {
     inbound.request match {
       case AcceptorInbound.Request.Phase1A(phase1a) =>
+        // enqueued, not answered: the burst a new leader sends is flushed by one tick (engine.flushPhase1as)
         val leader = chan[Leader[Transport]](src, Leader.serializer)
-        engine.handlePhase1a(groupIndex, index, phase1a) match {
+        val reply: Either[Nack, Phase1b] => Unit = {
           case Left(nack)     => leader.send(LeaderInbound().withNack(nack))        // Acceptor.scala:155-162
           case Right(phase1b) => leader.send(LeaderInbound().withPhase1B(phase1b))  // Acceptor.scala:163-181
         }
+        if (engine.enqueuePhase1a(groupIndex, index, phase1a, reply)) phase1Tick.start()
       case AcceptorInbound.Request.Phase2A(phase2a) =>
         engine.handlePhase2a(groupIndex, index, phase2a) match {
           case Left(nack) =>                                                          // Acceptor.scala:192-199

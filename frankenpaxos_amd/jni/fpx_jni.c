@@ -795,6 +795,40 @@ JNIEXPORT jint JNICALL Java_frankenpaxos_gpu_Native_acceptorPhase1bInfo(JNIEnv* 
   return st == FPX_OK ? count : -st;
 }
 
+/* A Leader's Phase1a at every acceptor it addresses, ONE call (fpx_acceptor_phase1): targetMasks 4 x numGroups words or
+ * null (everybody), bits = promised[4 x numGroups] then nack[4 x numGroups], offsets numGroups x numReplicas + 1; entry
+ * group * numReplicas + replica owns offsets[e] .. offsets[e + 1] of the record arrays (empty unless it promised).
+ * Returns the number of records (>= 0; the first min(count, cap) are written: with more than cap the promises hold and
+ * a second call with larger arrays answers the same), or -status */
+JNIEXPORT jlong JNICALL Java_frankenpaxos_gpu_Native_acceptorPhase1All(JNIEnv* env, jclass cls, jlong h, jint round,
+                                                                       jint chosenWatermark, jint numGroups,
+                                                                       jlongArray targetMasks, jlongArray bits, jint cap,
+                                                                       jlongArray offsets, jintArray slot,
+                                                                       jintArray voteRound, jintArray voteValue) {
+  fpx_config c;
+  if (cap < 0 || numGroups < 1 || !ctx_all_groups_is(h, numGroups) || fpx_get_config(CTX(h), &c) != FPX_OK) return -FPX_EINVAL;
+  const jlong words = 4 * (jlong)numGroups, entries = (jlong)numGroups * c.num_replicas;
+  if (!opt(env, targetMasks, words) || !has(env, bits, 2 * words) || !has(env, offsets, entries + 1) ||
+      (cap > 0 && (!has(env, slot, cap) || !has(env, voteRound, cap) || !has(env, voteValue, cap))))
+    return -FPX_EINVAL;
+  jlong* t = in_longs(env, targetMasks, words);
+  jlong *b = out_buf(bits, 2 * words, 8), *off = out_buf(offsets, entries + 1, 8);
+  jint *s = out_buf(slot, cap, 4), *r = out_buf(voteRound, cap, 4), *v = out_buf(voteValue, cap, 4);
+  int64_t count = 0;
+  int32_t st = (!b || !off || (targetMasks && !t) || (cap > 0 && (!s || !r || !v)))
+                   ? FPX_ENOMEM
+                   : fpx_acceptor_phase1(CTX(h), round, chosenWatermark, (const uint64_t*)t, (uint64_t*)b, (uint64_t*)b + words,
+                                         cap, (int64_t*)off, s, r, v, &count);
+  if (st == FPX_OK || st == FPX_ECAPACITY) {
+    const jlong k = count < cap ? count : cap;
+    put_longs(env, bits, 2 * words, b); put_longs(env, offsets, entries + 1, off);
+    put_ints(env, slot, k, s); put_ints(env, voteRound, k, r); put_ints(env, voteValue, k, v);
+    st = FPX_OK;
+  }
+  free(t); free(b); free(off); free(s); free(r); free(v);
+  return st == FPX_OK ? (jlong)count : -(jlong)st;
+}
+
 JNIEXPORT jint JNICALL Java_frankenpaxos_gpu_Native_recycleSlots(JNIEnv* env, jclass cls, jlong h, jint firstSlot, jint count) {
   return fpx_recycle_slots(CTX(h), firstSlot, count);
 }

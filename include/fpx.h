@@ -892,6 +892,35 @@ int32_t fpx_acceptor_max_voted_in(fpx_ctx* ctx, int32_t group, int32_t replica, 
 int32_t fpx_acceptor_phase1b_info(fpx_ctx* ctx, int32_t group, int32_t replica, int32_t chosen_watermark,
                                   int32_t cap, int32_t* count, int32_t* slot, int32_t* vote_round,
                                   int32_t* vote_value);
+/* Phase1b.info of EVERY selected acceptor in one pass; _dev convention (device pointers, enqueued on the
+ * context's stream, FPX_OK once enqueued, errors at fpx_sync).  An entry is e = group * num_replicas + replica,
+ * E = groups * num_replicas entries; entry e's records -- what fpx_acceptor_phase1b_info returns for it, slots
+ * ascending -- are d_offsets[e] .. d_offsets[e + 1] of the three record arrays, the entries back to back in entry
+ * order, d_offsets[E] the total.  An acceptor whose mask bit is clear gets an empty run (bits outside the members
+ * are ignored, as fpx_acceptor_phase1a ignores them).  The vote rows are read once, coalesced, from the watermark
+ * on (count, scan, scatter: csrc/fpx_phase1_info.hpp); nothing is read by the host between the passes and the
+ * result is deterministic.
+ * Capacity, as the device encoders of fpx_wire.h: d_totals and all E + 1 offsets are always written; with more
+ * records than cap, the records at global index < cap are written and the status is FPX_ECAPACITY -- a per-call
+ * code that aborts nothing.  cap = 0 with NULL record arrays is the sizing call.  FPX_EINVAL at once, nothing
+ * enqueued: NULL context, negative cap, missing offsets or totals, missing record arrays with cap > 0.  A context
+ * in the "apply nothing" state writes d_totals = {0, 0} and d_offsets[0] = 0 only. */
+int32_t fpx_acceptor_phase1b_info_all_dev(fpx_ctx* ctx, int32_t chosen_watermark,
+        const uint64_t* d_acceptor_masks /* ngroups x 4, bit convention of fpx_acceptor_phase1a's target_mask; NULL = all */,
+        int64_t cap, int64_t* d_offsets /* E + 1 */, int32_t* d_slot, int32_t* d_vote_round, int32_t* d_vote_value,
+        int64_t* d_totals /* [0] = records needed, [1] = records written */);
+/* host arrays, synchronous, through the staging driver the other host-pointer entry points use; *count = records
+ * needed.  The records are staged in three device buffers of cap x 4 bytes each, which the context keeps (like every
+ * staging buffer) until fpx_destroy: 3 x 512 MiB after one leader change of 2^20 slots x 256 acceptors. */
+int32_t fpx_acceptor_phase1b_info_all(fpx_ctx* ctx, int32_t chosen_watermark, const uint64_t* acceptor_masks,
+        int64_t cap, int64_t* offsets, int32_t* slot, int32_t* vote_round, int32_t* vote_value, int64_t* count);
+/* A Leader's Phase1a broadcast at every acceptor it addresses, one call: fpx_acceptor_phase1a for each group with
+ * a non-empty mask (in group order; target_masks NULL = every acceptor of every group), then the info of exactly
+ * the acceptors that promised.  With FPX_ECAPACITY the promises were applied.  The round a Nack carries stays
+ * with fpx_read_acceptor / the per-acceptor call. */
+int32_t fpx_acceptor_phase1(fpx_ctx* ctx, int32_t round, int32_t chosen_watermark, const uint64_t* target_masks,
+        uint64_t* promised_bits /* ngroups x 4 */, uint64_t* nack_bits /* ngroups x 4 */,
+        int64_t cap, int64_t* offsets, int32_t* slot, int32_t* vote_round, int32_t* vote_value, int64_t* count);
 
 /* ---- state readback (parity) ------------------------------------------------------------------- */
 /* acceptor `replica` of `group`: its round (FPX_BALLOT_ACCEPTOR; -1 in PER_SLOT mode),
