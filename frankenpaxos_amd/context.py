@@ -571,6 +571,24 @@ class Context:
         if st:
             raise FpxError(st, "fpx_replica_chosen_dev")
 
+    def replica_chosen_msgs(self, kind, slot, slot_end, value, mask=None):
+        """a burst of Chosen / ChosenNoopRange messages in delivery order (kinds of frankenpaxos_amd.wire), exactly as a
+        Mencius replica handles them one by one: (status, executed_watermark, num_chosen)"""
+        kind, slot, slot_end, value = _i32(kind), _i32(slot), _i32(slot_end), _i32(value)
+        assert len(kind) == len(slot) == len(slot_end) == len(value)
+        mask = None if mask is None else np.ascontiguousarray(mask, dtype=np.uint8)
+        wm, nc = C.c_int32(), C.c_int32()
+        st = self.L.fpx_replica_chosen_msgs(self._h, len(kind), _hp(kind), _hp(slot), _hp(slot_end), _hp(value),
+                                            _hp(mask), C.byref(wm), C.byref(nc))
+        return st, wm.value, nc.value
+
+    def replica_chosen_msgs_dev(self, kind, slot, slot_end, value, mask=None, n=None):
+        """the same on device tensors (n: the number of messages, default kind.numel()); errors surface at sync()"""
+        st = self.L.fpx_replica_chosen_msgs_dev(self._h, kind.numel() if n is None else n, _dp(kind), _dp(slot),
+                                                _dp(slot_end), _dp(value), _dp(mask))
+        if st:
+            raise FpxError(st, "fpx_replica_chosen_msgs_dev")
+
     def replica_state(self):
         wm, nc = C.c_int32(), C.c_int32()
         st = self.L.fpx_replica_state(self._h, C.byref(wm), C.byref(nc))

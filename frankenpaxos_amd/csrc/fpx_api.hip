@@ -23,6 +23,7 @@
 #include "fpx_phase1_info.hpp"
 #include "fpx_ranges.hpp"
 #include "fpx_tally_msgs.hpp"
+#include "fpx_replica_msgs.hpp"
 #include "fpx_wire_dev.hpp"
 #include "fpx_wire_enc_dev.hpp"
 #include "../../include/fpx_wire.h"
@@ -155,6 +156,9 @@ struct fpx_ctx {
   // fpx_proxy_phase2b_msgs_dev (fpx_tally_msgs.hpp): the owner word of every tally entry ([S][wp], INT_MAX between calls;
   // allocated by the first call), and per call the messages' entries, the gathered rows and the compaction's workgroup sums
   DevBuf m_owner, m_entry, m_rows, m_blk;
+  // fpx_replica_chosen_msgs_dev (fpx_replica_msgs.hpp): the claim word of every slot ([S], INT_MAX between calls; allocated
+  // by the first call), and per call the header words, the workgroups' folds, and the list of the burst's ranges
+  DevBuf rm_claim, rm_buf;
   // fpx_acceptor_phase1b_info_all[_dev] (fpx_phase1_info.hpp): the chunk counts, column totals and the go word; the host
   // form's offsets and totals
   DevBuf p1i, p1i_off, p1i_tot;
@@ -1014,6 +1018,7 @@ void free_state(fpx_ctx* ctx) {
                   &ctx->d_enc,    &ctx->w_buf,   &ctx->w_off,   &ctx->w_out,    &ctx->w_ooff,   &ctx->w_tot,
                   &ctx->w_rec[0], &ctx->w_rec[1], &ctx->w_rec[2], &ctx->w_rec[3], &ctx->w_rec[4], &ctx->w_rec[5],
                   &ctx->w_rec[6], &ctx->m_owner, &ctx->m_entry,  &ctx->m_rows,   &ctx->m_blk,
+                  &ctx->rm_claim, &ctx->rm_buf,
                   &ctx->p1i,      &ctx->p1i_off, &ctx->p1i_tot};
   for (DevBuf* b : bs)
     if (b->p) (void)hipFree(b->p);
@@ -2836,6 +2841,65 @@ int32_t fpx_replica_chosen_noop_range(fpx_ctx* ctx, int32_t slot_start, int32_t 
   int rc = fpx_replica_state(ctx, executed_watermark, num_chosen);
   if (rc) return rc;
   return fetch_status(ctx);
+}
+
+// mencius.Replica.handleChosen + handleChosenNoopRange for a burst in delivery order (fpx_replica_msgs.hpp): eight launches,
+// nothing read by the host in between
+int32_t fpx_replica_chosen_msgs_dev(fpx_ctx* ctx, int32_t n, const int32_t* d_kind, const int32_t* d_slot,
+                                    const int32_t* d_slot_end, const int32_t* d_value_id, const uint8_t* d_mask) {
+  DeviceGuard _dg(ctx);
+  if (!ctx || n < 0 || n >= (1 << 30)) return FPX_EINVAL;
+  if (n == 0) return FPX_OK;
+  if (!d_kind || !d_slot || !d_slot_end || !d_value_id) return FPX_EINVAL;
+  int rc;
+  if (!ctx->rm_claim.p) {
+    if ((rc = grow(ctx, &ctx->rm_claim, (size_t)ctx->g.S * 4))) return rc;
+    ctx->bytes += (int64_t)ctx->rm_claim.cap;
+    fill32(ctx, ctx->rm_claim.p, INT_MAX, ctx->rm_claim.cap / 4);
+  }
+  ReplicaMsgs b;
+  memset(&b, 0, sizeof(b));
+  b.n = n, b.nblk = (n + 255) / 256;
+  b.nparts = std::max(1, std::min({b.nblk, ctx->num_cus * 8, LG_MAX_PARTS}));
+  const size_t words = (size_t)RM_HDR_WORDS + 3 * (size_t)LG_MAX_PARTS + (size_t)b.nblk + 2 * (size_t)n;
+  if ((rc = grow(ctx, &ctx->rm_buf, words * 4))) return rc;
+  b.chosen_kind = FPX_WIRE_CHOSEN, b.range_kind = FPX_WIRE_CHOSEN_NOOP_RANGE;
+  b.kind = d_kind, b.slot = d_slot, b.slot_end = d_slot_end, b.value = d_value_id, b.mask = d_mask;
+  b.claim = (int32_t*)ctx->rm_claim.p;
+  b.hdr = (int32_t*)ctx->rm_buf.p;
+  b.parts = b.hdr + RM_HDR_WORDS, b.blk = b.parts + 3 * LG_MAX_PARTS, b.list = b.blk + b.nblk, b.res = b.list + n;
+  const dim3 per_msg(b.nblk), blk(256);
+  const int sweep = std::min(std::max(b.nblk, ctx->num_cus), ctx->num_cus * 8);
+  hipLaunchKernelGGL(k_rm_claim, per_msg, blk, 0, ctx->stream, ctx->g, ctx->st, b);
+  hipLaunchKernelGGL(k_rm_offsets, dim3(1), dim3(1024), 0, ctx->stream, b);
+  hipLaunchKernelGGL(k_rm_list, per_msg, blk, 0, ctx->stream, b);
+  hipLaunchKernelGGL(k_rm_walk, dim3(ctx->g.num_leader_groups), dim3(RM_WALK_THREADS), 0, ctx->stream, ctx->g, ctx->st, b);
+  hipLaunchKernelGGL(k_rm_apply, dim3(b.nparts), blk, 0, ctx->stream, ctx->g, ctx->st, b);
+  hipLaunchKernelGGL(k_rm_prep, dim3(1), blk, 0, ctx->stream, ctx->g, ctx->st, b);
+  hipLaunchKernelGGL(k_rm_scan, dim3(ctx->num_cus * 4), blk, 0, ctx->stream, ctx->g, ctx->st, b);
+  hipLaunchKernelGGL(k_rm_finish, dim3(sweep), blk, 0, ctx->stream, ctx->g, ctx->st, b);
+  return launch_check(ctx);
+}
+
+// the host form: ONE run through the staging driver, validated on the device like the _dev form
+int32_t fpx_replica_chosen_msgs(fpx_ctx* ctx, int32_t n, const int32_t* kind, const int32_t* slot, const int32_t* slot_end,
+                                const int32_t* value_id, const uint8_t* mask, int32_t* executed_watermark,
+                                int32_t* num_chosen) {
+  DeviceGuard _dg(ctx);
+  if (!ctx || n < 0 || n >= (1 << 30) || (n > 0 && (!kind || !slot || !slot_end || !value_id))) return FPX_EINVAL;
+  int rc = FPX_OK;
+  if (n > 0)
+    rc = host_batch(ctx, n,
+                    {{&ctx->d_i32_a, kind, 4}, {&ctx->d_slot, slot, 4}, {&ctx->d_i32_b, slot_end, 4},
+                     {&ctx->d_value, value_id, 4}, {&ctx->d_u8, mask, 1}},
+                    {}, nullptr, [&](int, int) {
+                      return fpx_replica_chosen_msgs_dev(ctx, n, (const int32_t*)ctx->d_i32_a.p, (const int32_t*)ctx->d_slot.p,
+                                                         (const int32_t*)ctx->d_i32_b.p, (const int32_t*)ctx->d_value.p,
+                                                         mask ? (const uint8_t*)ctx->d_u8.p : nullptr);
+                    });
+  if (rc == FPX_EHIP || rc == FPX_ENOMEM) return rc;  // (a HIP failure: no scalars to report)
+  const int st = fpx_replica_state(ctx, executed_watermark, num_chosen);
+  return st ? st : rc;
 }
 
 int32_t fpx_replica_read_log(fpx_ctx* ctx, int32_t first, int32_t count, int32_t* values, uint8_t* present) {

@@ -34,6 +34,7 @@
 
 #include "../../include/fpx.h"
 #include "../../include/fpx_depgraph.h"
+#include "../../include/fpx_wire.h"
 
 namespace frankenpaxos {
 
@@ -590,6 +591,24 @@ class NoopRangeEngine {
     int32_t wm = 0, nc = 0;
     check(fpx_replica_chosen_noop_range(ctx_, m.slotStartInclusive, m.slotEndExclusive, &wm, &nc),
           "Replica.handleChosenNoopRange");
+    numChosen_ = nc;
+    return wm;
+  }
+  // One message of a replica's inbox (mencius/Replica.scala:380-400): a Chosen (range == false: slot, value) or a
+  // ChosenNoopRange (range == true: slot = slotStartInclusive, slotEnd = slotEndExclusive).
+  struct ReplicaInbound { bool range; int32_t slot, slotEnd, value; };
+  // mencius.Replica.handleChosen + handleChosenNoopRange (Replica.scala:402-485) for a burst of the inbox in delivery
+  // order, in one device call and exactly as if handled one by one: returns executedWatermark.
+  int replicaHandleChosenMsgs(const std::vector<ReplicaInbound>& msgs) {
+    std::vector<int32_t> kind, slot, end, value;
+    for (const ReplicaInbound& m : msgs) {
+      kind.push_back(m.range ? FPX_WIRE_CHOSEN_NOOP_RANGE : FPX_WIRE_CHOSEN);
+      slot.push_back(m.slot), end.push_back(m.slotEnd), value.push_back(m.value);
+    }
+    int32_t wm = 0, nc = 0;
+    check(fpx_replica_chosen_msgs(ctx_, (int32_t)msgs.size(), kind.data(), slot.data(), end.data(), value.data(), nullptr,
+                                  &wm, &nc),
+          "Replica.handleChosen / handleChosenNoopRange");
     numChosen_ = nc;
     return wm;
   }

@@ -91,6 +91,10 @@ object Native {
                             mask: Array[Byte], state: Array[Int]): Int
   @native def replicaChosenNoopRange(handle: Long, slotStart: Int, slotEnd: Int,
                                      state: Array[Int]): Int
+  // a burst of Chosen / ChosenNoopRange messages in delivery order (kind as fpx_wire.h numbers it)
+  @native def replicaChosenMsgs(handle: Long, n: Int, kind: Array[Int], slot: Array[Int],
+                                slotEnd: Array[Int], value: Array[Int], mask: Array[Byte],
+                                state: Array[Int]): Int
   // Mencius noop ranges: n per call (the fused step), and the unfused pieces for one range
   @native def noopRangesFused(handle: Long, n: Int, numGroups: Int, slotStart: Array[Int],
                               slotEnd: Array[Int], round: Array[Int], targetMasks: Array[Long],

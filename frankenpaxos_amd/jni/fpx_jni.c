@@ -316,6 +316,24 @@ JNIEXPORT jint JNICALL Java_frankenpaxos_gpu_Native_replicaChosenNoopRange(JNIEn
   return st;
 }
 
+/* mencius.Replica.handleChosen + handleChosenNoopRange for a burst in delivery order: mencius/Replica.scala:402-485.
+ * kind as fpx_wire.h numbers it; slotEnd is read for the ranges, value for the Chosens.  state = {executedWatermark,
+ * numChosen} */
+JNIEXPORT jint JNICALL Java_frankenpaxos_gpu_Native_replicaChosenMsgs(JNIEnv* env, jclass cls, jlong h, jint n,
+                                                                      jintArray kind, jintArray slot, jintArray slotEnd,
+                                                                      jintArray value, jbyteArray mask, jintArray state) {
+  if (n < 0 || (n > 0 && (!has(env, kind, n) || !has(env, slot, n) || !has(env, slotEnd, n) || !has(env, value, n))) ||
+      !opt(env, mask, n) || !opt(env, state, 2))
+    return FPX_EINVAL;
+  jint *k = in_ints(env, kind, n), *s = in_ints(env, slot, n), *e = in_ints(env, slotEnd, n), *v = in_ints(env, value, n);
+  jint o[2] = {0, 0};
+  jbyte* m = in_bytes(env, mask, n);
+  int32_t st = fpx_replica_chosen_msgs(CTX(h), n, k, s, e, v, (const uint8_t*)m, &o[0], &o[1]);
+  put_ints(env, state, 2, o);
+  free(k); free(s); free(e); free(v); free(m);
+  return st;
+}
+
 /* Mencius noop ranges, n per call (mencius/Acceptor.scala:237-291, mencius/ProxyLeader.scala:255-303, 355-411): the
  * fused step = open + acceptors + tally.  Bitmaps are n x numGroups x 4 longs. */
 JNIEXPORT jint JNICALL Java_frankenpaxos_gpu_Native_noopRangesFused(

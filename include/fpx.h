@@ -857,6 +857,36 @@ int32_t fpx_replica_state(fpx_ctx* ctx, int32_t* executed_watermark, int32_t* nu
  * executeLog does not run (kept as is).  Otherwise the contiguous prefix executes.  Synchronous. */
 int32_t fpx_replica_chosen_noop_range(fpx_ctx* ctx, int32_t slot_start, int32_t slot_end,
                                       int32_t* executed_watermark, int32_t* num_chosen);
+/* mencius.Replica.handleChosen + handleChosenNoopRange (mencius/Replica.scala:402-420, 464-485; executeLog :331-371) for
+ * a BURST of n messages in delivery order, the two kinds interleaved as a Mencius replica's inbox has them (:380-400).
+ * kind[i] (fpx_wire.h): FPX_WIRE_CHOSEN = Chosen(slot[i], value_id[i]); FPX_WIRE_CHOSEN_NOOP_RANGE =
+ * ChosenNoopRange(slot[i], slot_end[i]) (value_id[i] is ignored); any other kind, and any message with mask[i] == 0
+ * (mask may be NULL), is skipped -- the arrays are what fpx_wire_mencius_decode_replica_inbound produces.  The result is
+ * EXACTLY the state after handling the messages one by one:
+ *   Chosen: slot in the log -> ignored and executeLog does NOT run (here fpx_replica_chosen[_dev], which always scans,
+ *     differs); else put, numChosen += 1, executeLog.
+ *   ChosenNoopRange: slot, slot + num_leader_groups, ... below slot_end in order: the first one that is in the log ends the
+ *     handler (the rest is dropped, executeLog does not run); the others get Noop (-1), numChosen += 1.  A range that runs
+ *     to its end (an empty one included) runs executeLog.
+ * So the lower index puts a slot; a range is cut by what an earlier message of the same burst put, not by a later one; and
+ * executedWatermark is the contiguous prefix of the log as it stood after the last message that reached executeLog (it
+ * does not move when none did), while numChosen counts every put.
+ * _dev: device pointers, enqueued on the context's stream, nothing is read by the host between its passes; read the
+ * result with fpx_replica_state / fpx_replica_read_log.  A Chosen with a slot outside [0, num_slots), or a range with
+ * slot < 0 or slot_end > num_slots, is found on the device before anything is applied: FPX_EINVAL at fpx_sync, the lowest
+ * offending index in fpx_error_detail, log and scalars untouched.  NULL context, n < 0 or n >= 2^30, or a NULL d_kind /
+ * d_slot / d_slot_end / d_value_id with n > 0: FPX_EINVAL at once, nothing enqueued.  The first call allocates one int32
+ * per slot (4 B x num_slots, kept until fpx_destroy, counted by fpx_device_bytes).
+ * One array per field, the two kinds in the same arrays, so that a band feeds the call without a copy: a caller that lays
+ * out d_slot | d_slot_start in one buffer, d_chosen | d_range_chosen in one buffer, and gives d_chosen_value n_ranges
+ * spare words passes fpx_mencius_band_fused_dev's outputs straight in as d_slot, d_mask and d_value_id, with constant
+ * d_kind / d_slot_end arrays.
+ * The host form takes host arrays, any n, and is synchronous (outputs may be NULL). */
+int32_t fpx_replica_chosen_msgs_dev(fpx_ctx* ctx, int32_t n, const int32_t* d_kind, const int32_t* d_slot,
+                                    const int32_t* d_slot_end, const int32_t* d_value_id, const uint8_t* d_mask);
+int32_t fpx_replica_chosen_msgs(fpx_ctx* ctx, int32_t n, const int32_t* kind, const int32_t* slot,
+                                const int32_t* slot_end, const int32_t* value_id, const uint8_t* mask,
+                                int32_t* executed_watermark, int32_t* num_chosen);
 /* log entries [first, first + count): value (-1 where absent) and present flag */
 int32_t fpx_replica_read_log(fpx_ctx* ctx, int32_t first, int32_t count, int32_t* values,
                              uint8_t* present);
