@@ -37,6 +37,11 @@ FPX_F_SLOT_MAJOR_ROWS = 4
 
 FPX_NOOP = -1
 
+# fpx_leader_phase1b_msgs (include/fpx.h): its flag and the words of its result
+FPX_P1B_GRID_ALL_ROWS = 1
+FPX_P1B_COMPLETE, FPX_P1B_DECIDED_AT, FPX_P1B_COUNT, FPX_P1B_MAX_SLOT, FPX_P1B_NEXT_SLOT, FPX_P1B_WRITTEN = range(6)
+FPX_P1B_RESULT_WORDS = 8
+
 # fpx_vote_launch_census (include/fpx.h): the forms of a vote launch, then the fates of its fold
 CENSUS_FORMS = ("solo", "grid", "fin", "band", "fold_now", "fold_behind", "fold_carried", "fold_flushed")
 CENSUS_CELLS = 7 * 4 * 3 * 2
@@ -166,6 +171,8 @@ SIGNATURES = {
     "fpx_replica_chosen_noop_range": (C.c_int32, [VP, C.c_int32, C.c_int32, I32P, I32P]),
     "fpx_replica_read_log": (C.c_int32, [VP, C.c_int32, C.c_int32, VP, VP]),
     "fpx_leader_phase1b_scan": (C.c_int32, [VP, C.c_int32, VP, C.c_int32, I32P, VP, VP]),
+    "fpx_leader_phase1b_msgs": (C.c_int32, [VP] + [C.c_int32] * 4 + [C.c_uint32, C.c_int32] + [VP] * 8 + [C.c_int32, C.c_int32] + [VP] * 5),
+    "fpx_leader_phase1b_msgs_dev": (C.c_int32, [VP] + [C.c_int32] * 4 + [C.c_uint32, C.c_int32] + [VP] * 8 + [C.c_int32, C.c_int32] + [VP] * 5),
     "fpx_acceptor_phase1b_info": (C.c_int32, [VP, C.c_int32, C.c_int32, C.c_int32, C.c_int32, I32P, VP, VP, VP]),
     "fpx_acceptor_phase1b_info_all_dev": (C.c_int32, [VP, C.c_int32, VP, C.c_int64, VP, VP, VP, VP, VP]),
     "fpx_acceptor_phase1b_info_all": (C.c_int32, [VP, C.c_int32, VP, C.c_int64, VP, VP, VP, VP, C.POINTER(C.c_int64)]),

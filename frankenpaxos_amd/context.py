@@ -614,6 +614,67 @@ class Context:
         k = max(0, min(cap, mx.value - watermark + 1))
         return st, mx.value, sr[:k], sv[:k]
 
+    def leader_phase1b_msgs(self, round_, watermark, msg_round, acceptor_index, offsets, info_slot, info_vote_round,
+                            info_value_id, kind=None, group_index=None, leader_group=0, recover_slot=-1, flags=0,
+                            grid_cols=0, cap=None):
+        """Leader.handlePhase1b for a burst of Phase1b messages in delivery order (host arrays, synchronous).  Message i
+        owns the records offsets[i]:offsets[i + 1] (offsets: n + 1 entries; or pass the decoder's info_first, n entries,
+        and it is completed from the record count).  cap None: a sizing call first.  Returns (status, result) with
+        result a dict: complete, decided_at, and -- when complete -- count, max_slot, next_slot, out_slot, safe_round,
+        safe_value (the first min(count, cap) entries), held_bits (ngroups x 4)."""
+        msg_round, acceptor_index = _i32(msg_round), _i32(acceptor_index)
+        kind, group_index = _i32(kind), _i32(group_index)
+        info_slot, info_vote_round, info_value_id = _i32(info_slot), _i32(info_vote_round), _i32(info_value_id)
+        n = len(msg_round)
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        if len(offsets) == n:  # a prefix sum without its total (wire.decode_leader_inbound's info_first)
+            offsets = np.concatenate([offsets, np.array([len(info_slot)], np.int64)])
+        assert len(offsets) == n + 1, "offsets has n + 1 entries"
+
+        def call(c, sl, sr, sv, held):
+            res = np.full(_lib.FPX_P1B_RESULT_WORDS, -1, np.int64)
+            st = self.L.fpx_leader_phase1b_msgs(self._h, round_, watermark, leader_group, recover_slot, flags, n, _hp(kind),
+                                                _hp(msg_round), _hp(group_index), _hp(acceptor_index), _hp(offsets),
+                                                _hp(info_slot), _hp(info_vote_round), _hp(info_value_id), grid_cols, c,
+                                                _hp(sl), _hp(sr), _hp(sv), _hp(res), _hp(held))
+            return st, res
+
+        if cap is None:
+            st, res = call(0, None, None, None, None)
+            if res[0] != 1:  # refused, or no quorum yet (a complete result comes with FPX_ECAPACITY or FPX_EFATAL_PROTOCOL too)
+                return st, self._p1b_result(res, None, None, None, None)
+            cap = int(res[_lib.FPX_P1B_COUNT])
+        sl, sr, sv = (np.full(cap, -7, np.int32) for _ in range(3))
+        held = np.zeros((self.ngroups, 4), np.uint64)
+        st, res = call(cap, sl, sr, sv, held)
+        return st, self._p1b_result(res, sl, sr, sv, held)
+
+    @staticmethod
+    def _p1b_result(res, sl, sr, sv, held):
+        out = {"complete": int(res[0]), "decided_at": int(res[1])}
+        if res[0] == 1:
+            w = int(res[_lib.FPX_P1B_WRITTEN])
+            out.update(count=int(res[_lib.FPX_P1B_COUNT]), max_slot=int(res[_lib.FPX_P1B_MAX_SLOT]),
+                       next_slot=int(res[_lib.FPX_P1B_NEXT_SLOT]), written=w, held_bits=held,
+                       out_slot=None if sl is None else sl[:w], safe_round=None if sr is None else sr[:w],
+                       safe_value=None if sv is None else sv[:w])
+        return out
+
+    def leader_phase1b_msgs_dev(self, round_, watermark, msg_round, acceptor_index, offsets, info_slot, info_vote_round,
+                                info_value_id, result, kind=None, group_index=None, leader_group=0, recover_slot=-1,
+                                flags=0, grid_cols=0, cap=0, out_slot=None, safe_round=None, safe_value=None,
+                                held_bits=None):
+        """asynchronous form on torch CUDA tensors: the headers int32 [n], offsets int64 [n + 1], the records int32,
+        result int64 [FPX_P1B_RESULT_WORDS], the outputs int32 of at least cap elements (None with cap = 0), held_bits
+        int64 [ngroups x 4] or None.  Errors surface at sync()."""
+        st = self.L.fpx_leader_phase1b_msgs_dev(self._h, round_, watermark, leader_group, recover_slot, flags,
+                                                msg_round.numel(), _dp(kind), _dp(msg_round), _dp(group_index),
+                                                _dp(acceptor_index), _dp(offsets), _dp(info_slot), _dp(info_vote_round),
+                                                _dp(info_value_id), grid_cols, cap, _dp(out_slot), _dp(safe_round),
+                                                _dp(safe_value), _dp(result), _dp(held_bits))
+        if st:
+            raise FpxError(st, "fpx_leader_phase1b_msgs_dev")
+
     def acceptor_phase1b_info(self, group, replica, watermark=0):
         """Phase1b.info of one acceptor: (slot, vote_round, vote_value) of its votes in slots >= watermark, ascending"""
         k = C.c_int32()

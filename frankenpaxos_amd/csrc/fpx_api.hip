@@ -21,6 +21,7 @@
 
 #include "fpx_kernels.hpp"
 #include "fpx_phase1_info.hpp"
+#include "fpx_phase1b_msgs.hpp"
 #include "fpx_ranges.hpp"
 #include "fpx_tally_msgs.hpp"
 #include "fpx_replica_msgs.hpp"
@@ -162,6 +163,9 @@ struct fpx_ctx {
   // fpx_acceptor_phase1b_info_all[_dev] (fpx_phase1_info.hpp): the chunk counts, column totals and the go word; the host
   // form's offsets and totals
   DevBuf p1i, p1i_off, p1i_tot;
+  // fpx_leader_phase1b_msgs[_dev] (fpx_phase1b_msgs.hpp): the per-call scratch (control block, first / last tables, the
+  // winners' work list), the bid table (cap x 8 bytes), and the host form's staging (8 inputs, 5 outputs)
+  DevBuf p1m_buf, p1m_tab, p1m_stage[13];
   DevBuf d_band;  // [num_leader_groups] marks: the leader groups with a range in the step being checked
   // multi-GPU (fpx_comm_*): one communicator per context, rank = this context's GPU
   RcclComm comm = nullptr;
@@ -1019,9 +1023,11 @@ void free_state(fpx_ctx* ctx) {
                   &ctx->w_rec[0], &ctx->w_rec[1], &ctx->w_rec[2], &ctx->w_rec[3], &ctx->w_rec[4], &ctx->w_rec[5],
                   &ctx->w_rec[6], &ctx->m_owner, &ctx->m_entry,  &ctx->m_rows,   &ctx->m_blk,
                   &ctx->rm_claim, &ctx->rm_buf,
-                  &ctx->p1i,      &ctx->p1i_off, &ctx->p1i_tot};
+                  &ctx->p1i,      &ctx->p1i_off, &ctx->p1i_tot, &ctx->p1m_buf, &ctx->p1m_tab};
   for (DevBuf* b : bs)
     if (b->p) (void)hipFree(b->p);
+  for (DevBuf& b : ctx->p1m_stage)
+    if (b.p) (void)hipFree(b.p);
   for (hipEvent_t e : ctx->ev) (void)hipEventDestroy(e);
   ctx->ev.clear();
   for (hipEvent_t e : ctx->cev) (void)hipEventDestroy(e);
@@ -2952,6 +2958,109 @@ int32_t fpx_leader_phase1b_scan(fpx_ctx* ctx, int32_t chosen_watermark, const ui
   if ((rc = d2h(ctx, safe_value, ctx->d_i32_b, (size_t)count))) return rc;
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
   return FPX_OK;
+}
+
+// ---- Leader.handlePhase1b for a burst of Phase1b messages (fpx_phase1b_msgs.hpp) -----------------------------------
+int32_t fpx_leader_phase1b_msgs_dev(fpx_ctx* ctx, int32_t round, int32_t chosen_watermark, int32_t leader_group,
+                                    int32_t recover_slot, uint32_t flags, int32_t n, const int32_t* d_kind,
+                                    const int32_t* d_msg_round, const int32_t* d_group_index, const int32_t* d_acceptor_index,
+                                    const int64_t* d_offsets, const int32_t* d_info_slot, const int32_t* d_info_vote_round,
+                                    const int32_t* d_info_value_id, int32_t grid_cols, int32_t cap, int32_t* d_out_slot,
+                                    int32_t* d_safe_round, int32_t* d_safe_value, int64_t* d_result, uint64_t* d_held_bits) {
+  if (!ctx || !d_result ||
+      !p1m_scalars_ok(ctx->g.num_groups, ctx->g.num_leader_groups, round, MAX_ROUND, chosen_watermark, leader_group,
+                      recover_slot, flags, FPX_P1B_GRID_ALL_ROWS, n, grid_cols, cap) ||
+      (n > 0 && (!d_msg_round || !d_acceptor_index || !d_offsets)) || (cap > 0 && (!d_out_slot || !d_safe_round || !d_safe_value)))
+    return FPX_EINVAL;
+  DeviceGuard _dg(ctx->cfg.device);  // (no acceptor, tally or replica state is read: a pending fold stays pending)
+  const Geom& g = ctx->g;
+  const P1mLayout l = p1m_layout(n, g.num_groups, g.ngroups, grid_cols);
+  int rc;
+  if ((rc = grow(ctx, &ctx->p1m_buf, l.bytes))) return rc;
+  if ((rc = grow(ctx, &ctx->p1m_tab, (size_t)cap * 8))) return rc;
+  char* base = (char*)ctx->p1m_buf.p;
+  P1mArgs a;
+  memset(&a, 0, sizeof(a));
+  a.n = n, a.round = round, a.leader_group = leader_group, a.recover_slot = recover_slot, a.watermark = chosen_watermark;
+  a.all_rows = (flags & FPX_P1B_GRID_ALL_ROWS) ? 1 : 0, a.grid_cols = grid_cols, a.need = ctx->cfg.f + 1;
+  a.phase1b = FPX_WIRE_PHASE1B, a.cap = cap;
+  a.kind = d_kind, a.msg_round = d_msg_round, a.group = d_group_index, a.acceptor = d_acceptor_index, a.offsets = d_offsets;
+  a.info_slot = d_info_slot, a.info_round = d_info_vote_round, a.info_value = d_info_value_id;
+  a.keys = l.keys;
+  a.ctl = (unsigned long long*)(base + l.ctl), a.held = (unsigned long long*)(base + l.held);
+  a.unit0 = (int64_t*)(base + l.unit0), a.first = (int32_t*)(base + l.first), a.last = (int32_t*)(base + l.last);
+  a.win = (int32_t*)(base + l.win), a.table = (unsigned long long*)ctx->p1m_tab.p;
+  a.out_slot = d_out_slot, a.safe_round = d_safe_round, a.safe_value = d_safe_value, a.result = d_result, a.held_out = d_held_bits;
+  HIPCHK(ctx, hipMemsetAsync(base, 0, l.zero_bytes, ctx->stream));
+  HIPCHK(ctx, hipMemsetAsync(a.first, 0x7f, (size_t)l.keys * 4, ctx->stream));  // 0x7f7f7f7f: above any message index
+  HIPCHK(ctx, hipMemsetAsync(a.last, 0xFF, (size_t)l.keys * 4, ctx->stream));
+  const dim3 blk(256), sweep(ctx->num_cus * 8);
+  if (n > 0) hipLaunchKernelGGL(k_p1m_headers, dim3((n + 255) / 256), blk, 0, ctx->stream, g, ctx->st, a);
+  hipLaunchKernelGGL(k_p1m_decide, dim3(1), dim3(1024), 0, ctx->stream, g, ctx->st, a);
+  hipLaunchKernelGGL(k_p1m_plan, dim3(1), dim3(1024), 0, ctx->stream, g, a);
+  hipLaunchKernelGGL(k_p1m_clear, sweep, blk, 0, ctx->stream, a);
+  hipLaunchKernelGGL(k_p1m_walk<false>, sweep, blk, 0, ctx->stream, g, a);
+  hipLaunchKernelGGL(k_p1m_walk<true>, sweep, blk, 0, ctx->stream, g, a);
+  hipLaunchKernelGGL(k_p1m_fill, sweep, blk, 0, ctx->stream, g, ctx->st, a);
+  return launch_check(ctx);
+}
+
+// the host form: ONE run through the staging driver; the offsets are checked here first, because they size the uploads
+int32_t fpx_leader_phase1b_msgs(fpx_ctx* ctx, int32_t round, int32_t chosen_watermark, int32_t leader_group,
+                                int32_t recover_slot, uint32_t flags, int32_t n, const int32_t* kind, const int32_t* msg_round,
+                                const int32_t* group_index, const int32_t* acceptor_index, const int64_t* offsets,
+                                const int32_t* info_slot, const int32_t* info_vote_round, const int32_t* info_value_id,
+                                int32_t grid_cols, int32_t cap, int32_t* out_slot, int32_t* safe_round, int32_t* safe_value,
+                                int64_t* result, uint64_t* held_bits) {
+  if (!ctx || !result ||
+      !p1m_scalars_ok(ctx->g.num_groups, ctx->g.num_leader_groups, round, MAX_ROUND, chosen_watermark, leader_group,
+                      recover_slot, flags, FPX_P1B_GRID_ALL_ROWS, n, grid_cols, cap) ||
+      (n > 0 && (!msg_round || !acceptor_index || !offsets)) || (cap > 0 && (!out_slot || !safe_round || !safe_value)))
+    return FPX_EINVAL;
+  int32_t bad = -1;
+  const int64_t total = p1m_check_offsets(n, offsets, &bad);
+  if (total < 0) {
+    ctx->err_index = bad, ctx->err_slot = -1, ctx->err_round = msg_round[bad];
+    return FPX_EINVAL;
+  }
+  if (total > 0 && (!info_slot || !info_vote_round || !info_value_id)) return FPX_EINVAL;
+  DeviceGuard _dg(ctx->cfg.device);
+  DevBuf* s = ctx->p1m_stage;
+  const size_t rec = (size_t)total * 4, outb = (size_t)cap * 4, heldb = (size_t)ctx->g.ngroups * 32;
+  const int64_t zero = 0;
+  int64_t res[8];
+  const int rc = host_batch(
+      ctx, n,
+      {{&s[0], kind, 4}, {&s[1], msg_round, 4}, {&s[2], group_index, 4}, {&s[3], acceptor_index, 4},
+       {&s[4], n > 0 ? offsets : &zero, 8, 8}, {&s[5], info_slot, 0, rec}, {&s[6], info_vote_round, 0, rec},
+       {&s[7], info_value_id, 0, rec}},
+      {{&s[8], nullptr, 0, outb}, {&s[9], nullptr, 0, outb}, {&s[10], nullptr, 0, outb}, {&s[11], res, 0, sizeof(res)},
+       {&s[12], nullptr, 0, heldb}},
+      nullptr, [&](int, int) -> int {
+        // -1 in every result word: "not written" (a refused call writes none, an incomplete one two)
+        HIPCHK(ctx, hipMemsetAsync(s[11].p, 0xFF, sizeof(res), ctx->stream));
+        return fpx_leader_phase1b_msgs_dev(ctx, round, chosen_watermark, leader_group, recover_slot, flags, n,
+                                           kind ? (const int32_t*)s[0].p : nullptr, (const int32_t*)s[1].p,
+                                           group_index ? (const int32_t*)s[2].p : nullptr, (const int32_t*)s[3].p,
+                                           (const int64_t*)s[4].p, (const int32_t*)s[5].p, (const int32_t*)s[6].p,
+                                           (const int32_t*)s[7].p, grid_cols, cap, (int32_t*)s[8].p, (int32_t*)s[9].p,
+                                           (int32_t*)s[10].p, (int64_t*)s[11].p, (uint64_t*)s[12].p);
+      });
+  if (rc == FPX_EHIP || rc == FPX_ENOMEM || rc == FPX_EINVAL) return rc;
+  // what the device wrote, and no more, reaches the caller's arrays
+  if (res[0] == 0) {
+    result[0] = 0;
+    if (res[1] == -1) result[1] = -1;
+  } else if (res[0] == 1) {
+    for (int w = 0; w < 6; ++w) result[w] = res[w];
+    const size_t wr = (size_t)res[5];
+    int rc2;
+    if ((rc2 = d2h(ctx, out_slot, s[8], wr)) || (rc2 = d2h(ctx, safe_round, s[9], wr)) || (rc2 = d2h(ctx, safe_value, s[10], wr)))
+      return rc2;
+    if ((rc2 = d2h(ctx, held_bits, s[12], (size_t)ctx->g.ngroups * 4))) return rc2;
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  }
+  return rc;
 }
 
 // ---- readback ----------------------------------------------------------------------------------------

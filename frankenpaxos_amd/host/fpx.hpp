@@ -421,6 +421,47 @@ class Phase2Engine {
     return out;
   }
 
+  // ---- Leader.handlePhase1b for a burst of Phase1b MESSAGES in delivery order (Leader.scala:504-577; the acceptors need
+  // not live in this context): nullopt-like `complete == false` while a quorum is missing
+  struct Phase1bMsg {
+    int round, groupIndex, acceptorIndex;
+    std::vector<Phase1bSlotInfo> info;
+  };
+  struct Phase1Recovery {
+    bool complete = false;
+    int decidedAt = -1, maxSlot = -1, nextSlot = 0;
+    std::vector<SafeValue> safe;
+  };
+  Phase1Recovery leaderHandlePhase1bMsgs(int round, int chosenWatermark, const std::vector<Phase1bMsg>& msgs, int gridCols = 0,
+                                         int leaderGroup = 0, int recoverSlot = -1, uint32_t flags = 0) {
+    const int32_t n = (int32_t)msgs.size();
+    std::vector<int32_t> mr, g, a, sl, vr, vv;
+    std::vector<int64_t> off{0};
+    for (const Phase1bMsg& m : msgs) {
+      mr.push_back(m.round), g.push_back(m.groupIndex), a.push_back(m.acceptorIndex);
+      for (const Phase1bSlotInfo& i : m.info) sl.push_back(i.slot), vr.push_back(i.voteRound), vv.push_back(i.voteValue);
+      off.push_back((int64_t)sl.size());
+    }
+    int64_t res[FPX_P1B_RESULT_WORDS];
+    auto call = [&](int32_t cap, int32_t* os, int32_t* sr, int32_t* sv) {
+      for (int64_t& w : res) w = -1;
+      const int32_t st = fpx_leader_phase1b_msgs(ctx_, round, chosenWatermark, leaderGroup, recoverSlot, flags, n, nullptr,
+                                                 mr.data(), g.data(), a.data(), off.data(), sl.data(), vr.data(), vv.data(),
+                                                 gridCols, cap, os, sr, sv, res, nullptr);
+      if (st != FPX_OK && st != FPX_ECAPACITY) check(st, "Leader.handlePhase1b (messages)");
+    };
+    call(0, nullptr, nullptr, nullptr);
+    Phase1Recovery out;
+    if (res[FPX_P1B_COMPLETE] != 1) return out;
+    const int32_t count = (int32_t)res[FPX_P1B_COUNT];
+    std::vector<int32_t> os(count), sr(count), sv(count);
+    if (count > 0) call(count, os.data(), sr.data(), sv.data());
+    out.complete = true, out.decidedAt = (int)res[FPX_P1B_DECIDED_AT], out.maxSlot = (int)res[FPX_P1B_MAX_SLOT];
+    out.nextSlot = (int)res[FPX_P1B_NEXT_SLOT];
+    for (int32_t k = 0; k < count; ++k) out.safe.push_back(SafeValue{os[k], sr[k], sv[k]});
+    return out;
+  }
+
   // ---- Replica.handleChosen + executeLog (Replica.scala:572-590, 394-447): returns executedWatermark
   int replicaHandleChosen(const std::vector<Chosen>& msgs) {
     std::vector<int32_t> slot(msgs.size()), value(msgs.size());

@@ -271,6 +271,26 @@ class GpuMenciusEngine[Transport <: frankenpaxos.Transport[Transport]](
   def close(): Unit = Native.check(Native.destroy(handle), logger)
 }
 
+// mencius.Leader's Phase 1 among acceptors outside the leader's context (GpuLeaderRecoveryCore, Native.scala): the
+// leader group's index and phase1.recoverSlot go in, and the slots that come out are the leader group's own
+// (mencius/Leader.scala:582-659)
+class GpuMenciusLeaderRecovery(logger: Logger, handle: Long, round: Int, chosenWatermark: Int, leaderGroup: Int,
+                               recoverSlot: Int) {
+  private val core = new GpuLeaderRecoveryCore(logger, handle, round, chosenWatermark, leaderGroup, recoverSlot, 0, 0)
+  private val values = mutable.ArrayBuffer[CommandBatchOrNoop]()
+  private def intern(v: CommandBatchOrNoop): Int = if (v.value.isNoop) -1 else { values += v; values.size - 1 }
+
+  def handlePhase1b(p: Phase1b): Option[(Seq[Phase2a], Int)] = {
+    core.append(p.round, p.groupIndex, p.acceptorIndex, p.info.map(i => (i.slot, i.voteRound, intern(i.voteValue))))
+    core.tryRecover().map { r =>
+      val phase2as = for (j <- r.slots.indices) yield Phase2a(
+        slot = r.slots(j), round = round,
+        commandBatchOrNoop = if (r.valueIds(j) < 0) CommandBatchOrNoop().withNoop(Noop()) else values(r.valueIds(j)))
+      (phase2as, r.nextSlot)                                                          // Leader.scala:629-647
+    }
+  }
+}
+
 class GpuMenciusProxyLeader[Transport <: frankenpaxos.Transport[Transport]](
     address: Transport#Address,
     transport: Transport,

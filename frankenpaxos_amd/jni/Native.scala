@@ -188,6 +188,14 @@ object Native {
   @native def acceptorPhase1All(handle: Long, round: Int, chosenWatermark: Int, numGroups: Int, targetMasks: Array[Long],
                                 bits: Array[Long], cap: Int, offsets: Array[Long], slot: Array[Int],
                                 voteRound: Array[Int], voteValue: Array[Int]): Long
+  // Leader.handlePhase1b for a burst of Phase1bs in delivery order (fpx_leader_phase1b_msgs): scalars = (round,
+  // chosenWatermark, leaderGroup, recoverSlot, flags, gridCols); message i owns the records offsets(i) until
+  // offsets(i + 1); result = 8 longs (complete, decidedAt, count, maxSlot, nextSlot, written), -1 where nothing was written
+  @native def leaderPhase1bMsgs(handle: Long, scalars: Array[Int], n: Int, kind: Array[Int], msgRound: Array[Int],
+                                groupIndex: Array[Int], acceptorIndex: Array[Int], offsets: Array[Long],
+                                infoSlot: Array[Int], infoVoteRound: Array[Int], infoValue: Array[Int], cap: Int,
+                                outSlot: Array[Int], safeRound: Array[Int], safeValue: Array[Int], result: Array[Long],
+                                heldBits: Array[Long]): Int
   @native def acceptorRound(handle: Long, group: Int, replica: Int): Int // Acceptor.round, < -1: -status - 1
   // the largest row of [firstRow, firstRow + count) in which the acceptor holds a vote, -1: none, < -1: -status - 1
   @native def acceptorMaxVotedIn(handle: Long, group: Int, replica: Int, firstRow: Int, count: Int): Int
@@ -592,6 +600,63 @@ class GpuPhase2Engine[Transport <: frankenpaxos.Transport[Transport]](
   }
 
   def close(): Unit = Native.check(Native.destroy(handle), logger)
+}
+
+// ---- Phase 1, leader side: a leader among acceptors that are NOT in its context (reference Acceptor actors, the
+// shards of a replica-sharded group).  The Phase1bs are appended as they arrive and the whole burst is handed to
+// fpx_leader_phase1b_msgs, which is stateless and decides exactly where Leader.handlePhase1b would have
+// (multipaxos/Leader.scala:504-577): call again with the longer burst until it is complete.  `handle` is any context
+// with the deployment's geometry (groups, f, the grid); value ids are positions in `values`, -1 = Noop.
+class GpuLeaderRecoveryCore(logger: Logger, handle: Long, round: Int, chosenWatermark: Int, leaderGroup: Int,
+                            recoverSlot: Int, gridCols: Int, flags: Int) {
+  private val msgRound = mutable.ArrayBuffer[Int](); private val group = mutable.ArrayBuffer[Int]()
+  private val acc = mutable.ArrayBuffer[Int](); private val offsets = mutable.ArrayBuffer[Long](0L)
+  private val slot = mutable.ArrayBuffer[Int](); private val voteRound = mutable.ArrayBuffer[Int]()
+  private val valueId = mutable.ArrayBuffer[Int]()
+  // (outSlot, safeValueId) per re-proposed slot, nextSlot
+  case class Recovered(slots: Array[Int], valueIds: Array[Int], nextSlot: Int)
+
+  def append(r: Int, groupIndex: Int, acceptorIndex: Int, info: Seq[(Int, Int, Int)]): Unit = {
+    msgRound += r; group += groupIndex; acc += acceptorIndex
+    for ((s, vr, id) <- info) { slot += s; voteRound += vr; valueId += id }
+    offsets += slot.size.toLong
+  }
+
+  // None: still waiting for a quorum
+  def tryRecover(): Option[Recovered] = {
+    val scalars = Array(round, chosenWatermark, leaderGroup, recoverSlot, flags, gridCols)
+    val n = msgRound.size
+    val (mr, g, a, off) = (msgRound.toArray, group.toArray, acc.toArray, offsets.toArray)
+    val (s, vr, id) = (slot.toArray, voteRound.toArray, valueId.toArray)
+    val result = new Array[Long](8)
+    def call(cap: Int, os: Array[Int], sr: Array[Int], sv: Array[Int]): Unit = {
+      val st = Native.leaderPhase1bMsgs(handle, scalars, n, null, mr, g, a, off, s, vr, id, cap, os, sr, sv, result, null)
+      if (st != 0 && st != 5 /*FPX_ECAPACITY: the sizing call*/ ) Native.check(st, logger) // checkLt / check fire here
+    }
+    call(0, null, null, null)
+    if (result(0) != 1) return None
+    val count = result(2).toInt
+    val os = new Array[Int](count); val sr = new Array[Int](count); val sv = new Array[Int](count)
+    if (count > 0) call(count, os, sr, sv)
+    Some(Recovered(os, sv, result(4).toInt))
+  }
+}
+
+// multipaxos.Leader's Phase 1: feed it every Phase1b; Some(phase2as, nextSlot) is what the handler sends and sets
+class GpuLeaderRecovery(logger: Logger, handle: Long, round: Int, chosenWatermark: Int, gridCols: Int = 0, flags: Int = 0) {
+  private val core = new GpuLeaderRecoveryCore(logger, handle, round, chosenWatermark, 0, -1, gridCols, flags)
+  private val values = mutable.ArrayBuffer[CommandBatchOrNoop]()
+  private def intern(v: CommandBatchOrNoop): Int = if (v.value.isNoop) -1 else { values += v; values.size - 1 }
+
+  def handlePhase1b(p: Phase1b): Option[(Seq[Phase2a], Int)] = {
+    core.append(p.round, p.groupIndex, p.acceptorIndex, p.info.map(i => (i.slot, i.voteRound, intern(i.voteValue))))
+    core.tryRecover().map { r =>
+      val phase2as = for (j <- r.slots.indices) yield Phase2a(
+        slot = r.slots(j), round = round,
+        commandBatchOrNoop = if (r.valueIds(j) < 0) CommandBatchOrNoop().withNoop(Noop()) else values(r.valueIds(j)))
+      (phase2as, r.nextSlot)                                                          // Leader.scala:553-569
+    }
+  }
 }
 
 // Stands where a ProxyLeader stands (ProxyLeaderMain): Leaders keep sending Phase2a to it exactly as they send

@@ -847,6 +847,51 @@ JNIEXPORT jlong JNICALL Java_frankenpaxos_gpu_Native_acceptorPhase1All(JNIEnv* e
   return st == FPX_OK ? (jlong)count : -(jlong)st;
 }
 
+/* Leader.handlePhase1b for a burst of decoded Phase1bs in delivery order (multipaxos/Leader.scala:504-577,
+ * mencius/Leader.scala:582-659).  scalars = {round, chosenWatermark, leaderGroup, recoverSlot, flags, gridCols}; message
+ * i owns the records offsets(i) until offsets(i + 1) (n + 1 longs); result = FPX_P1B_RESULT_WORDS longs, -1 where the
+ * call wrote nothing; heldBits 4 x groups longs or null.  The status: FPX_ECAPACITY and FPX_EFATAL_PROTOCOL come with a
+ * result all the same (include/fpx.h). */
+JNIEXPORT jint JNICALL Java_frankenpaxos_gpu_Native_leaderPhase1bMsgs(
+    JNIEnv* env, jclass cls, jlong h, jintArray scalars, jint n, jintArray kind, jintArray msgRound, jintArray groupIndex,
+    jintArray acceptorIndex, jlongArray offsets, jintArray infoSlot, jintArray infoVoteRound, jintArray infoValue, jint cap,
+    jintArray outSlot, jintArray safeRound, jintArray safeValue, jlongArray result, jlongArray heldBits) {
+  fpx_config c;
+  if (n < 0 || cap < 0 || !has(env, scalars, 6) || !has(env, result, FPX_P1B_RESULT_WORDS) || !opt(env, kind, n) ||
+      !has(env, msgRound, n) || !opt(env, groupIndex, n) || !has(env, acceptorIndex, n) || !has(env, offsets, (jlong)n + 1) ||
+      (cap > 0 && (!has(env, outSlot, cap) || !has(env, safeRound, cap) || !has(env, safeValue, cap))) ||
+      fpx_get_config(CTX(h), &c) != FPX_OK)
+    return FPX_EINVAL;
+  const jlong words = 4 * (jlong)c.num_groups * c.num_leader_groups;
+  if (!opt(env, heldBits, words)) return FPX_EINVAL;
+  jlong* off = in_longs(env, offsets, (jlong)n + 1);
+  if (!off) return FPX_ENOMEM;
+  const jlong total = off[n] > 0 ? off[n] : 0;  /* (offsets that do not ascend are refused before a record is read) */
+  if (total > 0 && (!has(env, infoSlot, total) || !has(env, infoVoteRound, total) || !has(env, infoValue, total))) {
+    free(off);
+    return FPX_EINVAL;
+  }
+  jint* sc = in_ints(env, scalars, 6);
+  jint *k = in_ints(env, kind, n), *mr = in_ints(env, msgRound, n), *g = in_ints(env, groupIndex, n), *a = in_ints(env, acceptorIndex, n);
+  jint *is = in_ints(env, infoSlot, total), *ir = in_ints(env, infoVoteRound, total), *iv = in_ints(env, infoValue, total);
+  jint *os = out_buf(outSlot, cap, 4), *sr = out_buf(safeRound, cap, 4), *sv = out_buf(safeValue, cap, 4);
+  jlong* hb = out_buf(heldBits, words, 8);
+  jlong res[FPX_P1B_RESULT_WORDS];
+  for (int w = 0; w < FPX_P1B_RESULT_WORDS; ++w) res[w] = -1;
+  int32_t st = (!sc || (cap > 0 && (!os || !sr || !sv)) || (heldBits && !hb))
+                   ? FPX_ENOMEM
+                   : fpx_leader_phase1b_msgs(CTX(h), sc[0], sc[1], sc[2], sc[3], (uint32_t)sc[4], n, k, mr, g, a, (const int64_t*)off,
+                                             is, ir, iv, sc[5], cap, os, sr, sv, (int64_t*)res, (uint64_t*)hb);
+  put_longs(env, result, FPX_P1B_RESULT_WORDS, res);
+  if (res[FPX_P1B_COMPLETE] == 1) {
+    const jlong wr = res[FPX_P1B_WRITTEN];
+    put_ints(env, outSlot, wr, os); put_ints(env, safeRound, wr, sr); put_ints(env, safeValue, wr, sv);
+    if (heldBits) put_longs(env, heldBits, words, hb);
+  }
+  free(off); free(sc); free(k); free(mr); free(g); free(a); free(is); free(ir); free(iv); free(os); free(sr); free(sv); free(hb);
+  return st;
+}
+
 JNIEXPORT jint JNICALL Java_frankenpaxos_gpu_Native_recycleSlots(JNIEnv* env, jclass cls, jlong h, jint firstSlot, jint count) {
   return fpx_recycle_slots(CTX(h), firstSlot, count);
 }

@@ -905,6 +905,78 @@ int32_t fpx_leader_phase1b_scan(fpx_ctx* ctx, int32_t chosen_watermark, const ui
                                 int32_t cap, int32_t* max_slot, int32_t* safe_round,
                                 int32_t* safe_value);
 
+/* Leader.handlePhase1b (multipaxos/Leader.scala:306-329, 504-577; mencius/Leader.scala:359-385, 582-659) for a BURST of
+ * n Phase1b MESSAGES in delivery order -- the acceptors anywhere: reference processes (the outputs of
+ * fpx_wire_decode_leader_inbound), other contexts or GPUs of a replica-sharded group (the outputs of
+ * fpx_acceptor_phase1b_info_all_dev, as they stand).  Stateless with respect to Phase 1: the context gives the geometry
+ * (num_groups, num_leader_groups, f, replicas_total, the read-quorum predicate) and keeps the scratch; no acceptor, tally
+ * or replica state is read or written.  A caller still waiting for a quorum calls again with the longer burst.
+ * Message i: kind[i] (NULL = every message is a Phase1b; kinds other than FPX_WIRE_PHASE1B are skipped), msg_round[i],
+ * group_index[i] (NULL = 0; the acceptor group's index inside the leader's leader group), acceptor_index[i], and the
+ * records offsets[i] .. offsets[i + 1] of info_slot / info_vote_round / info_value_id (offsets: n + 1 int64, FPX_NOOP the
+ * value id of a Noop).  grid_cols as in fpx_proxy_phase2b_msgs: 0 = acceptor acceptor_index (0 .. replicas_total - 1) of
+ * group group_index; > 0 = the bit group_index * grid_cols + acceptor_index of the single grid group (a context with one
+ * group), whose rows are the grid_cols-wide runs of bits.
+ * The result is exactly the handler's, message by message:
+ *   1. msg_round != round: ignored, does not count (:517-526).  msg_round > round is logger.checkLt firing: the message
+ *      is skipped all the same, the status is FPX_EFATAL_PROTOCOL with the lowest such index, the others still decide.
+ *   2. phase1bs(group)(acceptor) = message: a later message of an acceptor replaces the earlier one whole.
+ *   3. The call decides at the first index k after which the quorum condition holds: without a grid every acceptor group
+ *      holds f + 1 distinct acceptors (the context's f); with a grid the context's read-quorum predicate
+ *      (fpx_read_quorum_eval) holds over the bits held.  Only messages at indices <= k are used, the last per acceptor;
+ *      what follows k finds the leader in Phase 2 and is ignored.  No such k: result[FPX_P1B_COMPLETE] = 0,
+ *      result[FPX_P1B_DECIDED_AT] = -1, nothing else is written and no record is read.
+ *   4. max_slot = the largest info_slot of the messages used (-1 if they carry none), and at least recover_slot
+ *      (phase1.recoverSlot of Mencius; -1 for MultiPaxos).  Mencius checks max_slot == -1 || max_slot % num_leader_groups
+ *      == leader_group: a violation is FPX_EFATAL_PROTOCOL (fpx_error_detail: index -1, the slot) and nothing is written.
+ *   5. Output slots: nextClassicRound(leader_group, chosen_watermark - 1) .. max_slot in steps of num_leader_groups
+ *      (MultiPaxos, one leader group: chosen_watermark .. max_slot).  Records below the watermark enter max_slot only.
+ *   6. For output slot s the messages used are those of group (s / num_leader_groups) % num_groups; with a grid, those of
+ *      row s % rows -- literally what Leader.scala:552 takes -- or, with FPX_P1B_GRID_ALL_ROWS, every message held.
+ *   7. safe_round[j] = the highest vote_round among their records of s (-1: none), safe_value[j] = that record's value id
+ *      (FPX_NOOP: none); on equal rounds the lowest bit wins (fpx_leader_phase1b_scan's rule).  out_slot[j] = s: with the
+ *      leader's round a Phase2a batch for fpx_proxy_open_dev / fpx_phase2_fused_dev.
+ *   8. result: FPX_P1B_COUNT entries, FPX_P1B_MAX_SLOT, FPX_P1B_NEXT_SLOT = nextClassicRound(leader_group, max_slot)
+ *      (max_slot + 1 for MultiPaxos: 0 for a log without votes, whatever the watermark), FPX_P1B_WRITTEN = min(count,
+ *      cap); held_bits (num_leader_groups * num_groups x 4 words, may be NULL) names the acceptors used.
+ * Checked on the device before anything is written -- FPX_EINVAL, the lowest offending message index in
+ * fpx_error_detail, and (the _dev convention) the context applies nothing up to the next fpx_sync: offsets not
+ * non-decreasing from 0; group_index / acceptor_index outside the geometry or grid_cols; and, in the messages the result
+ * uses, a record with vote_round outside 0 .. 2^30 - 2, a negative slot, or slots not strictly ascending (an acceptor's
+ * states.iteratorFrom yields them so, which is what makes info.find(_.slot == slot) unambiguous).  Messages the handler
+ * ignores are not read.  FPX_EINVAL at once, nothing enqueued: NULL context or result, n < 0 or >= 2^30, cap < 0, round
+ * outside 0 .. 2^30 - 2, chosen_watermark < 0, recover_slot < -1, leader_group outside the leader groups, an unknown flag,
+ * grid_cols outside 0 .. 256 or > 0 on a context with several groups, missing arrays.
+ * Capacity as fpx_acceptor_phase1b_info_all_dev: with count > cap the first cap entries are written and the status is
+ * FPX_ECAPACITY, which aborts nothing; cap = 0 with NULL arrays is the sizing call.  A context in the "apply nothing"
+ * state writes result[FPX_P1B_COMPLETE] = 0 only.
+ * Seven launches, nothing read by the host in between, integer atomics only (csrc/fpx_phase1b_msgs.hpp): the result is
+ * reproducible bit for bit.  The scratch (a bid table of cap x 8 bytes among it) stays with the context.
+ * _dev: device pointers, enqueued on the context's stream, errors at fpx_sync.  The host form is synchronous, goes
+ * through the staging driver, reports bad offsets before anything is uploaded, and writes to the caller's arrays exactly
+ * what the device form would have written. */
+#define FPX_P1B_GRID_ALL_ROWS 1u
+enum {
+  FPX_P1B_COMPLETE = 0,
+  FPX_P1B_DECIDED_AT = 1,
+  FPX_P1B_COUNT = 2,
+  FPX_P1B_MAX_SLOT = 3,
+  FPX_P1B_NEXT_SLOT = 4,
+  FPX_P1B_WRITTEN = 5,
+  FPX_P1B_RESULT_WORDS = 8
+};
+int32_t fpx_leader_phase1b_msgs_dev(fpx_ctx* ctx, int32_t round, int32_t chosen_watermark, int32_t leader_group,
+        int32_t recover_slot, uint32_t flags, int32_t n, const int32_t* d_kind, const int32_t* d_msg_round,
+        const int32_t* d_group_index, const int32_t* d_acceptor_index, const int64_t* d_offsets /* n + 1 */,
+        const int32_t* d_info_slot, const int32_t* d_info_vote_round, const int32_t* d_info_value_id, int32_t grid_cols,
+        int32_t cap, int32_t* d_out_slot, int32_t* d_safe_round, int32_t* d_safe_value,
+        int64_t* d_result /* FPX_P1B_RESULT_WORDS */, uint64_t* d_held_bits /* groups x 4, or NULL */);
+int32_t fpx_leader_phase1b_msgs(fpx_ctx* ctx, int32_t round, int32_t chosen_watermark, int32_t leader_group,
+        int32_t recover_slot, uint32_t flags, int32_t n, const int32_t* kind, const int32_t* msg_round,
+        const int32_t* group_index, const int32_t* acceptor_index, const int64_t* offsets, const int32_t* info_slot,
+        const int32_t* info_vote_round, const int32_t* info_value_id, int32_t grid_cols, int32_t cap, int32_t* out_slot,
+        int32_t* safe_round, int32_t* safe_value, int64_t* result, uint64_t* held_bits);
+
 /* Acceptor.maxVotedSlot (multipaxos/Acceptor.scala:104, 208) as the read path reports it (handleMaxSlotRequest /
  * handleBatchMaxSlotRequest, :222-254), restricted to the slots [first_slot, first_slot + count) of the acceptor's group:
  * the largest of them in which the acceptor holds a vote, -1 if there is none.  With first_slot = 0 and count = num_slots
