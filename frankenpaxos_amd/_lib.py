@@ -121,6 +121,10 @@ SIGNATURES = {
     "fpx_proxy_phase2b_dev": (C.c_int32, [VP, C.c_int32, VP, VP, VP, VP, VP, VP]),
     "fpx_proxy_phase2b_msgs": (C.c_int32, [VP, C.c_int32, VP, VP, VP, VP, VP, C.c_int32, VP, VP, VP]),
     "fpx_proxy_phase2b_msgs_dev": (C.c_int32, [VP, C.c_int32, VP, VP, VP, VP, VP, C.c_int32, VP, VP, VP]),
+    "fpx_mencius_proxy_phase2b_msgs": (C.c_int32, [VP, C.c_int32, VP, VP, VP, VP, VP, VP, VP, VP, VP]),
+    "fpx_mencius_proxy_phase2b_msgs_dev": (C.c_int32, [VP, C.c_int32, VP, VP, VP, VP, VP, VP, VP, VP, VP]),
+    "fpx_mencius_phase2b_tick": (C.c_int32, [VP, C.c_int32, VP, VP, VP, VP, VP, VP, VP, VP, VP, VP, VP, C.c_int32,
+                                             C.POINTER(C.c_int32)]),
     "fpx_phase2_fused": (C.c_int32, [VP, C.c_int32, VP, VP, VP, VP, VP, VP, VP, VP]),
     "fpx_phase2_fused_submit": (C.c_int32, [VP, C.c_int32, VP, VP, VP, VP, VP, VP, VP, VP, I32P]),
     "fpx_phase2_fused_wait": (C.c_int32, [VP, C.c_int32]),

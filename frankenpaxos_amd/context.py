@@ -242,6 +242,35 @@ class Context:
                                            _hp(round_), grid_cols, _hp(ch), _hp(cr), _hp(cv))
         return st, ch, cr, cv
 
+    def mencius_proxy_phase2b_msgs(self, acceptor_index, slot, round_, kind=None, group_index=None, slot_end=None):
+        """one Phase2b / Phase2bNoopRange per (acceptor, key) in delivery order (mencius/ProxyLeader.scala:305-411): = the
+        burst folded into rows + proxy_phase2b / proxy_phase2b_noop_ranges, each row's outcome at the index of its first
+        message (kind None: all are Phase2bs; group_index None: 0; slot_end None: no range message)"""
+        acceptor_index, slot, round_ = _i32(acceptor_index), _i32(slot), _i32(round_)
+        kind, group_index, slot_end = _i32(kind), _i32(group_index), _i32(slot_end)
+        n = len(slot)
+        ch = np.zeros(n, np.uint8)
+        cr = np.zeros(n, np.int32)
+        cv = np.zeros(n, np.int32)
+        st = self.L.fpx_mencius_proxy_phase2b_msgs(self._h, n, _hp(kind), _hp(group_index), _hp(acceptor_index),
+                                                   _hp(slot), _hp(slot_end), _hp(round_), _hp(ch), _hp(cr), _hp(cv))
+        return st, ch, cr, cv
+
+    def mencius_phase2b_tick(self, acceptor_index, slot, round_, kind=None, group_index=None, slot_end=None, out_cap=None):
+        """fpx_mencius_phase2b_tick: (status, count, records) with records = the first min(count, out_cap) newly chosen
+        (kind, slot, slot_end or -1, round, value id or -1) in message order; the status is returned, not raised --
+        FPX_ECAPACITY (count = the capacity needed) is an answer here.  out_cap None: n."""
+        acceptor_index, slot, round_ = _i32(acceptor_index), _i32(slot), _i32(round_)
+        kind, group_index, slot_end = _i32(kind), _i32(group_index), _i32(slot_end)
+        n = len(slot)
+        cap = n if out_cap is None else int(out_cap)
+        outs = [np.full(max(cap, 1), -77, np.int32) for _ in range(5)]
+        count = C.c_int32(0)
+        st = self.L.fpx_mencius_phase2b_tick(self._h, n, _hp(kind), _hp(group_index), _hp(acceptor_index), _hp(slot),
+                                             _hp(slot_end), _hp(round_), *[_hp(o) for o in outs], cap, C.byref(count))
+        k = min(count.value, cap)
+        return st, count.value, list(zip(*[o[:k].tolist() for o in outs]))
+
     def phase2_fused(self, slot, round_, value, target_mask=None):
         slot, round_, value, target_mask = _i32(slot), _i32(round_), _i32(value), _u64(target_mask)
         n = len(slot)
@@ -283,6 +312,14 @@ class Context:
                                                _dp(chosen_value))
         if st:
             raise FpxError(st, "fpx_proxy_phase2b_msgs_dev")
+
+    def mencius_proxy_phase2b_msgs_dev(self, acceptor_index, slot, round_, kind=None, group_index=None, slot_end=None,
+                                       newly_chosen=None, chosen_round=None, chosen_value=None):
+        st = self.L.fpx_mencius_proxy_phase2b_msgs_dev(self._h, slot.numel(), _dp(kind), _dp(group_index),
+                                                       _dp(acceptor_index), _dp(slot), _dp(slot_end), _dp(round_),
+                                                       _dp(newly_chosen), _dp(chosen_round), _dp(chosen_value))
+        if st:
+            raise FpxError(st, "fpx_mencius_proxy_phase2b_msgs_dev")
 
     def phase2_fused_dev(self, slot, round_, value, target_mask=None, chosen=None, chosen_round=None,
                          chosen_value=None, nack_round=None):

@@ -24,6 +24,7 @@
 #include "fpx_phase1b_msgs.hpp"
 #include "fpx_ranges.hpp"
 #include "fpx_tally_msgs.hpp"
+#include "fpx_mencius_msgs.hpp"
 #include "fpx_replica_msgs.hpp"
 #include "fpx_wire_dev.hpp"
 #include "fpx_wire_enc_dev.hpp"
@@ -157,6 +158,9 @@ struct fpx_ctx {
   // fpx_proxy_phase2b_msgs_dev (fpx_tally_msgs.hpp): the owner word of every tally entry ([S][wp], INT_MAX between calls;
   // allocated by the first call), and per call the messages' entries, the gathered rows and the compaction's workgroup sums
   DevBuf m_owner, m_entry, m_rows, m_blk;
+  // fpx_mencius_proxy_phase2b_msgs_dev (fpx_mencius_msgs.hpp): the claim word of every range-table entry ([cap], INT_MAX
+  // between calls; allocated by the first call; one array for both table buffers), and the tick's staged slot_end / records
+  DevBuf mm_claim, mm_end, mm_rec[5];
   // fpx_replica_chosen_msgs_dev (fpx_replica_msgs.hpp): the claim word of every slot ([S], INT_MAX between calls; allocated
   // by the first call), and per call the header words, the workgroups' folds, and the list of the burst's ranges
   DevBuf rm_claim, rm_buf;
@@ -621,9 +625,8 @@ int enqueue_tally(fpx_ctx* ctx, Batch& b) {
   return launch_check(ctx);
 }
 
-// ProxyLeader.handlePhase2b for per-acceptor messages: claim, gather, tally, tail (fpx_tally_msgs.hpp)
-int enqueue_tally_msgs(fpx_ctx* ctx, MsgBatch& b) {
-  if (b.n == 0) return FPX_OK;
+// the owner table, the messages' entries and the gathered rows (zeroed) of a claim / gather / tally call
+int prepare_tally_msgs(fpx_ctx* ctx, MsgBatch& b) {
   int rc;
   if (!ctx->m_owner.p) {
     const size_t words = (size_t)ctx->g.S * ctx->g.wp;
@@ -636,6 +639,14 @@ int enqueue_tally_msgs(fpx_ctx* ctx, MsgBatch& b) {
   b.owner = (int32_t*)ctx->m_owner.p, b.entry = (int32_t*)ctx->m_entry.p, b.row_bits = (unsigned long long*)ctx->m_rows.p;
   b.phase2b = FPX_WIRE_PHASE2B;
   HIPCHK(ctx, hipMemsetAsync(b.row_bits, 0, (size_t)b.n * 32, ctx->stream));
+  return FPX_OK;
+}
+
+// ProxyLeader.handlePhase2b for per-acceptor messages: claim, gather, tally, tail (fpx_tally_msgs.hpp)
+int enqueue_tally_msgs(fpx_ctx* ctx, MsgBatch& b) {
+  if (b.n == 0) return FPX_OK;
+  int rc = prepare_tally_msgs(ctx, b);
+  if (rc) return rc;
   const dim3 grid((b.n + 255) / 256), blk(256);
   hipLaunchKernelGGL(k_msgs_claim, grid, blk, 0, ctx->stream, ctx->g, ctx->st, b);
   hipLaunchKernelGGL(k_msgs_gather, grid, blk, 0, ctx->stream, ctx->g, ctx->st, b);
@@ -1022,7 +1033,8 @@ void free_state(fpx_ctx* ctx) {
                   &ctx->d_enc,    &ctx->w_buf,   &ctx->w_off,   &ctx->w_out,    &ctx->w_ooff,   &ctx->w_tot,
                   &ctx->w_rec[0], &ctx->w_rec[1], &ctx->w_rec[2], &ctx->w_rec[3], &ctx->w_rec[4], &ctx->w_rec[5],
                   &ctx->w_rec[6], &ctx->m_owner, &ctx->m_entry,  &ctx->m_rows,   &ctx->m_blk,
-                  &ctx->rm_claim, &ctx->rm_buf,
+                  &ctx->rm_claim, &ctx->rm_buf,   &ctx->mm_claim, &ctx->mm_end,   &ctx->mm_rec[0], &ctx->mm_rec[1],
+                  &ctx->mm_rec[2], &ctx->mm_rec[3], &ctx->mm_rec[4],
                   &ctx->p1i,      &ctx->p1i_off, &ctx->p1i_tot, &ctx->p1m_buf, &ctx->p1m_tab};
   for (DevBuf* b : bs)
     if (b->p) (void)hipFree(b->p);
@@ -2717,6 +2729,116 @@ int32_t fpx_proxy_open_noop_range(fpx_ctx* ctx, int32_t slot_start, int32_t slot
 int32_t fpx_proxy_phase2b_noop_range(fpx_ctx* ctx, int32_t slot_start, int32_t slot_end, int32_t round,
                                      const uint64_t* vote_bits, uint8_t* newly_chosen) {
   return fpx_proxy_phase2b_noop_ranges(ctx, 1, &slot_start, &slot_end, &round, vote_bits, newly_chosen);
+}
+
+// ---- mencius.ProxyLeader.handlePhase2b + handlePhase2bNoopRange for per-acceptor messages (fpx_mencius_msgs.hpp) ----
+int32_t fpx_mencius_proxy_phase2b_msgs_dev(fpx_ctx* ctx, int32_t n, const int32_t* d_kind, const int32_t* d_group_index,
+                                           const int32_t* d_acceptor_index, const int32_t* d_slot, const int32_t* d_slot_end,
+                                           const int32_t* d_round, uint8_t* d_newly_chosen, int32_t* d_chosen_round,
+                                           int32_t* d_chosen_value) {
+  DeviceGuard _dg(ctx);
+  int rc = ranges_ctx_ok(ctx, n);
+  if (rc) return rc;
+  if (n >= (1 << 30)) return FPX_EINVAL;
+  if (n == 0) return FPX_OK;
+  if (!d_acceptor_index || !d_slot || !d_round) return FPX_EINVAL;
+  const RangeTable& rt = ctx->rt[ctx->rt_cur];
+  if (!ctx->mm_claim.p) {
+    if ((rc = grow(ctx, &ctx->mm_claim, (size_t)rt.cap * 4))) return rc;
+    ctx->bytes += (int64_t)ctx->mm_claim.cap;
+    fill32(ctx, ctx->mm_claim.p, INT_MAX, ctx->mm_claim.cap / 4);
+  }
+  MenciusMsgs b;
+  memset(&b, 0, sizeof(b));
+  b.m.n = n, b.m.kind = d_kind, b.m.acceptor = d_acceptor_index, b.m.slot = d_slot, b.m.round = d_round;
+  b.m.chosen = d_newly_chosen, b.m.chosen_round = d_chosen_round, b.m.chosen_value = d_chosen_value;
+  if ((rc = prepare_tally_msgs(ctx, b.m))) return rc;
+  b.group = d_group_index, b.slot_end = d_slot_end, b.range_kind = FPX_WIRE_PHASE2B_NOOP_RANGE;
+  b.claim = (int32_t*)ctx->mm_claim.p, b.quorum = ctx->cfg.f + 1, b.run_id = ++ctx->run_id;
+  const dim3 grid((n + 255) / 256), blk(256);
+  hipLaunchKernelGGL(k_mm_claim, grid, blk, 0, ctx->stream, ctx->g, ctx->st, rt, b);
+  hipLaunchKernelGGL(k_mm_gather, grid, blk, 0, ctx->stream, ctx->g, ctx->st, rt, b);
+  hipLaunchKernelGGL(k_mm_tally, grid, blk, 0, ctx->stream, ctx->g, ctx->st, rt, b);
+  hipLaunchKernelGGL(k_msgs_tail, dim3(1), dim3(1), 0, ctx->stream, ctx->st, b.m);
+  return launch_check(ctx);
+}
+
+// the host form: ONE run through the staging driver, validated on the device like the _dev form
+int32_t fpx_mencius_proxy_phase2b_msgs(fpx_ctx* ctx, int32_t n, const int32_t* kind, const int32_t* group_index,
+                                       const int32_t* acceptor_index, const int32_t* slot, const int32_t* slot_end,
+                                       const int32_t* round, uint8_t* newly_chosen, int32_t* chosen_round,
+                                       int32_t* chosen_value) {
+  DeviceGuard _dg(ctx);
+  int rc = ranges_ctx_ok(ctx, n);
+  if (rc) return rc;
+  if (n >= (1 << 30)) return FPX_EINVAL;
+  if (n == 0) return FPX_OK;
+  if (!acceptor_index || !slot || !round) return FPX_EINVAL;
+  return host_batch(ctx, n,
+                    {{&ctx->d_value, kind, 4}, {&ctx->d_target, group_index, 4}, {&ctx->d_i32_c, acceptor_index, 4},
+                     {&ctx->d_slot, slot, 4}, {&ctx->mm_end, slot_end, 4}, {&ctx->d_round, round, 4}},
+                    {{&ctx->d_u8, newly_chosen, 1}, {&ctx->d_i32_a, chosen_round, 4}, {&ctx->d_i32_b, chosen_value, 4}},
+                    nullptr, [&](int, int) {
+                      return fpx_mencius_proxy_phase2b_msgs_dev(
+                          ctx, n, kind ? (const int32_t*)ctx->d_value.p : nullptr,
+                          group_index ? (const int32_t*)ctx->d_target.p : nullptr, (const int32_t*)ctx->d_i32_c.p,
+                          (const int32_t*)ctx->d_slot.p, slot_end ? (const int32_t*)ctx->mm_end.p : nullptr,
+                          (const int32_t*)ctx->d_round.p, (uint8_t*)ctx->d_u8.p, (int32_t*)ctx->d_i32_a.p,
+                          (int32_t*)ctx->d_i32_b.p);
+                    });
+}
+
+// One tick of a Mencius proxy leader among remote acceptors, decoded arrays to records, through the staging driver as ONE
+// run: the arrays go up, the device tallies both kinds (claim / gather / tally) and compacts the newly chosen records in
+// message order; the count and the records come down.
+int32_t fpx_mencius_phase2b_tick(fpx_ctx* ctx, int32_t n, const int32_t* kind, const int32_t* group_index,
+                                 const int32_t* acceptor_index, const int32_t* slot, const int32_t* slot_end,
+                                 const int32_t* round, int32_t* out_kind, int32_t* out_slot, int32_t* out_slot_end,
+                                 int32_t* out_round, int32_t* out_value_id, int32_t out_cap, int32_t* out_count) {
+  DeviceGuard _dg(ctx);
+  int rc = ranges_ctx_ok(ctx, n);
+  if (rc) return rc;
+  if (n >= (1 << 30) || out_cap < 0 || !out_count) return FPX_EINVAL;
+  if (out_cap > 0 && (!out_kind || !out_slot || !out_slot_end || !out_round || !out_value_id)) return FPX_EINVAL;
+  *out_count = 0;
+  if (n == 0) return FPX_OK;
+  if (!acceptor_index || !slot || !round) return FPX_EINVAL;
+  for (DevBuf* b : {&ctx->d_u8, &ctx->d_i32_a, &ctx->d_i32_b})
+    if ((rc = grow(ctx, b, (size_t)n * 4))) return rc;
+  MenciusEmit m;
+  memset(&m, 0, sizeof(m));
+  MsgCompact& c = m.c;
+  c.n = n, c.nblk = (n + 255) / 256, c.cap = out_cap;
+  if ((rc = grow(ctx, &ctx->m_blk, (size_t)c.nblk * 4))) return rc;
+  int64_t totals[2] = {0, 0};
+  const size_t rec = (size_t)out_cap * 4;
+  rc = host_batch(
+      ctx, n,
+      {{&ctx->d_value, kind, 4}, {&ctx->d_target, group_index, 4}, {&ctx->d_i32_c, acceptor_index, 4},
+       {&ctx->d_slot, slot, 4}, {&ctx->mm_end, slot_end, 4}, {&ctx->d_round, round, 4}},
+      {{&ctx->mm_rec[0], out_kind, 0, rec}, {&ctx->mm_rec[1], out_slot, 0, rec}, {&ctx->mm_rec[2], out_slot_end, 0, rec},
+       {&ctx->mm_rec[3], out_round, 0, rec}, {&ctx->mm_rec[4], out_value_id, 0, rec}, {&ctx->w_tot, totals, 0, 16}},
+      nullptr, [&](int, int) {
+        const int32_t* d_kind = kind ? (const int32_t*)ctx->d_value.p : nullptr;
+        const int32_t* d_end = slot_end ? (const int32_t*)ctx->mm_end.p : nullptr;
+        int r = fpx_mencius_proxy_phase2b_msgs_dev(ctx, n, d_kind, group_index ? (const int32_t*)ctx->d_target.p : nullptr,
+                                                   (const int32_t*)ctx->d_i32_c.p, (const int32_t*)ctx->d_slot.p, d_end,
+                                                   (const int32_t*)ctx->d_round.p, (uint8_t*)ctx->d_u8.p,
+                                                   (int32_t*)ctx->d_i32_a.p, (int32_t*)ctx->d_i32_b.p);
+        if (r) return r;
+        c.chosen = (const uint8_t*)ctx->d_u8.p, c.slot = (const int32_t*)ctx->d_slot.p;
+        c.chosen_round = (const int32_t*)ctx->d_i32_a.p, c.chosen_value = (const int32_t*)ctx->d_i32_b.p;
+        c.blk = (int32_t*)ctx->m_blk.p, c.totals = (int64_t*)ctx->w_tot.p;
+        c.out_slot = (int32_t*)ctx->mm_rec[1].p, c.out_round = (int32_t*)ctx->mm_rec[3].p, c.out_value = (int32_t*)ctx->mm_rec[4].p;
+        m.kind = d_kind, m.slot_end = d_end, m.phase2b = FPX_WIRE_PHASE2B, m.range_kind = FPX_WIRE_PHASE2B_NOOP_RANGE;
+        m.out_kind = (int32_t*)ctx->mm_rec[0].p, m.out_slot_end = (int32_t*)ctx->mm_rec[2].p;
+        hipLaunchKernelGGL(k_msgs_count, dim3(c.nblk), dim3(256), 0, ctx->stream, ctx->st, c);
+        hipLaunchKernelGGL(k_msgs_scan, dim3(1), dim3(1024), 0, ctx->stream, ctx->st, c);
+        hipLaunchKernelGGL(k_mm_emit, dim3(c.nblk), dim3(256), 0, ctx->stream, ctx->st, m);
+        return launch_check(ctx);
+      });
+  if (rc == FPX_OK || rc == FPX_ECAPACITY || rc == FPX_EFATAL_UNKNOWN_SLOTROUND) *out_count = (int32_t)totals[0];
+  return rc;
 }
 
 // the proxy leader's tally of one range (parity), as k_ranges_read leaves it: state, num_groups x 4 words of votes,

@@ -19,6 +19,9 @@
 // one message whose index the minimum settled on, and that message resets it in k_msgs_tally -- also when the call
 // applies nothing (a bad bit, or the context already in the "apply nothing" state, in which case nothing is claimed).
 //
+// The per-message bodies (msgs_claim_one, msgs_gather_dst + msgs_or_merged, msgs_tally_one) are device functions: the
+// Mencius burst kernels (fpx_mencius_msgs.hpp) run them for the Phase2b's of a mixed burst.
+//
 // Then the compaction of a tick's newly chosen records in message order (fpx_wire_phase2b_tick): count per workgroup,
 // scan of the workgroup counts, emit.
 #pragma once
@@ -52,45 +55,41 @@ struct MsgBatch {
   int32_t* chosen_value;
 };
 
+// the claim of ONE Phase2b message: its tally entry, -1 = contributes nothing (shared with fpx_mencius_msgs.hpp)
+__device__ __forceinline__ int msgs_claim_one(const Geom& g, const State& st, const MsgBatch& b, int i) {
+  int e = -1;
+  const int a = b.acceptor[i], s = b.slot[i], rnd = b.round[i];
+  const long long bit = b.grid_cols > 0 ? (long long)(b.group ? b.group[i] : 0) * b.grid_cols + a : a;
+  if (bit < 0 || bit >= 256 || a < 0 || (b.grid_cols > 0 && a >= b.grid_cols) || s < 0 || s >= g.S || rnd < 0 ||
+      rnd > MAX_ROUND) {
+    atomicMax(&st.status[ST_MSG_BAD], 0x7fffffff - i);
+  } else if ((g.member[bit >> 6] >> (bit & 63)) & 1ull) {  // a bit outside the member set contributes nothing
+    const size_t ps = (size_t)phys_slot(g, s);
+    const uint32_t* kr = st.pl_key + ps * g.wp;
+    const uint32_t want = (uint32_t)rnd + 1u;
+    int way = -1;
+    for (int w = 0; w < g.ways; ++w)
+      if ((kr[w] & KEY_ROUND_MASK) == want) way = w;
+    if (way < 0) {
+      atomicMax(&st.status[ST_MSG_UNKNOWN], 0x7fffffff - i);  // :220-225; the message is dropped
+    } else {
+      e = (int)(ps * g.wp + way);
+      atomicMin(&b.owner[e], i);
+    }
+  }
+  return e;
+}
+
 __global__ void __launch_bounds__(256) k_msgs_claim(const Geom g, const State st, const MsgBatch b) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= b.n) return;
   int e = -1;
-  if (st.status[ST_ABORT] == 0 && (!b.kind || b.kind[i] == b.phase2b)) {
-    const int a = b.acceptor[i], s = b.slot[i], rnd = b.round[i];
-    const long long bit = b.grid_cols > 0 ? (long long)(b.group ? b.group[i] : 0) * b.grid_cols + a : a;
-    if (bit < 0 || bit >= 256 || a < 0 || (b.grid_cols > 0 && a >= b.grid_cols) || s < 0 || s >= g.S || rnd < 0 ||
-        rnd > MAX_ROUND) {
-      atomicMax(&st.status[ST_MSG_BAD], 0x7fffffff - i);
-    } else if ((g.member[bit >> 6] >> (bit & 63)) & 1ull) {  // a bit outside the member set contributes nothing
-      const size_t ps = (size_t)phys_slot(g, s);
-      const uint32_t* kr = st.pl_key + ps * g.wp;
-      const uint32_t want = (uint32_t)rnd + 1u;
-      int way = -1;
-      for (int w = 0; w < g.ways; ++w)
-        if ((kr[w] & KEY_ROUND_MASK) == want) way = w;
-      if (way < 0) {
-        atomicMax(&st.status[ST_MSG_UNKNOWN], 0x7fffffff - i);  // :220-225; the message is dropped
-      } else {
-        e = (int)(ps * g.wp + way);
-        atomicMin(&b.owner[e], i);
-      }
-    }
-  }
+  if (st.status[ST_ABORT] == 0 && (!b.kind || b.kind[i] == b.phase2b)) e = msgs_claim_one(g, st, b, i);
   b.entry[i] = e;
 }
 
-__global__ void __launch_bounds__(256) k_msgs_gather(const Geom g, const State st, const MsgBatch b) {
-  if (st.status[ST_ABORT] != 0 || st.status[ST_MSG_BAD] != 0) return;  // nothing is applied: no row is read
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  const int e = i < b.n ? b.entry[i] : -1;
-  long long dst = -1;  // the word of row_bits this message's bit goes to
-  unsigned long long v = 0;
-  if (e >= 0) {
-    const int bit = b.grid_cols > 0 ? (b.group ? b.group[i] : 0) * b.grid_cols + b.acceptor[i] : b.acceptor[i];
-    dst = (long long)b.owner[e] * 4 + (bit >> 6);
-    v = 1ull << (bit & 63);
-  }
+// atomicOr(&base[dst], v) for every lane with dst >= 0 (every lane of the wavefront calls this)
+__device__ __forceinline__ void msgs_or_merged(unsigned long long* base, long long dst, unsigned long long v) {
 #if FPX_GATHER_MERGE
   // The votes of one slot often sit next to each other in a tick: a run of neighbouring lanes with one destination
   // becomes ONE atomic, sent by the run's first lane (a segmented OR towards lower lanes, 6 steps; every lane of the
@@ -104,28 +103,50 @@ __global__ void __launch_bounds__(256) k_msgs_gather(const Geom g, const State s
     const long long od = __shfl_down(dst, d);
     if (lane + d < 64 && od == dst) v |= ov;  // lanes lane .. lane + d hold dst throughout: runs are contiguous
   }
-  if (dst >= 0 && head) atomicOr(&b.row_bits[dst], v);
+  if (dst >= 0 && head) atomicOr(&base[dst], v);
 #else
-  if (dst >= 0) atomicOr(&b.row_bits[dst], v);
+  if (dst >= 0) atomicOr(&base[dst], v);
 #endif
+}
+
+// where the bit of Phase2b message i goes: the word of row_bits (-1: nowhere) and the bit within it
+__device__ __forceinline__ long long msgs_gather_dst(const MsgBatch& b, int i, int e, unsigned long long* v) {
+  if (e < 0) return -1;
+  const int bit = b.grid_cols > 0 ? (b.group ? b.group[i] : 0) * b.grid_cols + b.acceptor[i] : b.acceptor[i];
+  *v = 1ull << (bit & 63);
+  return (long long)b.owner[e] * 4 + (bit >> 6);
+}
+
+__global__ void __launch_bounds__(256) k_msgs_gather(const Geom g, const State st, const MsgBatch b) {
+  if (st.status[ST_ABORT] != 0 || st.status[ST_MSG_BAD] != 0) return;  // nothing is applied: no row is read
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  const int e = i < b.n ? b.entry[i] : -1;
+  unsigned long long v = 0;
+  const long long dst = msgs_gather_dst(b, i, e, &v);  // the word of row_bits this message's bit goes to
+  msgs_or_merged(b.row_bits, dst, v);
+}
+
+// the tally of ONE Phase2b message (shared with fpx_mencius_msgs.hpp): the owner of entry e tallies the gathered row
+__device__ __forceinline__ void msgs_tally_one(const Geom& g, const State& st, const MsgBatch& b, int i, int e, bool apply,
+                                               uint8_t* ch, int* cr, int* cv) {
+  if (e >= 0 && b.owner[e] == i) {
+    if (apply) {
+      uint64_t row[4];
+#pragma unroll
+      for (int w = 0; w < 4; ++w) row[w] = b.row_bits[(size_t)i * 4 + w];
+      tally_row(g, st, i, b.slot[i], b.round[i], row, ch, cr, cv);
+    }
+    b.owner[e] = INT_MAX;
+  }
 }
 
 __global__ void __launch_bounds__(256) k_msgs_tally(const Geom g, const State st, const MsgBatch b) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= b.n) return;
   const bool apply = st.status[ST_ABORT] == 0 && st.status[ST_MSG_BAD] == 0;
-  const int e = b.entry[i];
   uint8_t ch = 0;
   int cr = -1, cv = -1;
-  if (e >= 0 && b.owner[e] == i) {
-    if (apply) {
-      uint64_t row[4];
-#pragma unroll
-      for (int w = 0; w < 4; ++w) row[w] = b.row_bits[(size_t)i * 4 + w];
-      tally_row(g, st, i, b.slot[i], b.round[i], row, &ch, &cr, &cv);
-    }
-    b.owner[e] = INT_MAX;
-  }
+  msgs_tally_one(g, st, b, i, b.entry[i], apply, &ch, &cr, &cv);
   if (b.chosen) b.chosen[i] = ch;
   if (b.chosen_round) b.chosen_round[i] = cr;
   if (b.chosen_value) b.chosen_value[i] = cv;

@@ -625,6 +625,35 @@ class NoopRangeEngine {
     return ChosenNoopRange{h.slotStartInclusive, h.slotEndExclusive};
   }
 
+  // One message of a proxy leader's inbox from REMOTE acceptors (mencius/ProxyLeader.scala:179-205): a Phase2b (range ==
+  // false: acceptorIndex, slot, round) or a Phase2bNoopRange (range == true: acceptorGroupIndex, acceptorIndex, slot =
+  // slotStartInclusive, slotEnd = slotEndExclusive, round).
+  struct ProxyLeaderInbound { bool range; int32_t acceptorGroupIndex, acceptorIndex, slot, slotEnd, round; };
+  // What the proxy leader sends to every replica: a Chosen (range == false: slot, value id) or a ChosenNoopRange
+  struct ProxyLeaderOutbound { bool range; int32_t slot, slotEnd, value; };
+  // mencius.ProxyLeader.handlePhase2b + handlePhase2bNoopRange (ProxyLeader.scala:305-411) for a tick of the inbox in
+  // delivery order, one message per (acceptor, key), duplicates allowed: the fold into rows and both tallies run on the
+  // device in one call (fpx_mencius_phase2b_tick).  Returns the Chosen / ChosenNoopRange in message order.
+  std::vector<ProxyLeaderOutbound> menciusProxyLeaderHandlePhase2bMsgs(const std::vector<ProxyLeaderInbound>& msgs) {
+    const int32_t n = (int32_t)msgs.size();
+    std::vector<int32_t> kind(n), group(n), acceptor(n), slot(n), end(n), round(n);
+    for (int32_t i = 0; i < n; ++i) {
+      const ProxyLeaderInbound& m = msgs[i];
+      kind[i] = m.range ? FPX_WIRE_PHASE2B_NOOP_RANGE : FPX_WIRE_PHASE2B;
+      group[i] = m.acceptorGroupIndex, acceptor[i] = m.acceptorIndex, slot[i] = m.slot, end[i] = m.range ? m.slotEnd : -1;
+      round[i] = m.round;
+    }
+    std::vector<int32_t> ok(n), os(n), oe(n), orr(n), ov(n);  // at most one record per message
+    int32_t count = 0;
+    check(fpx_mencius_phase2b_tick(ctx_, n, kind.data(), group.data(), acceptor.data(), slot.data(), end.data(), round.data(),
+                                   ok.data(), os.data(), oe.data(), orr.data(), ov.data(), n, &count),
+          "ProxyLeader.handlePhase2b / handlePhase2bNoopRange");
+    std::vector<ProxyLeaderOutbound> out;
+    for (int32_t k = 0; k < count; ++k)
+      out.push_back(ProxyLeaderOutbound{ok[k] == FPX_WIRE_PHASE2B_NOOP_RANGE, os[k], oe[k], ov[k]});
+    return out;
+  }
+
   // mencius.Replica.handleChosenNoopRange (Replica.scala:464-485) at the replica whose log lives in this
   // context: returns executedWatermark.  Like the reference it stops at the first slot of the range that
   // is already chosen -- without filling the rest and without executing the log.

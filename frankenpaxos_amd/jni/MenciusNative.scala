@@ -6,7 +6,10 @@
 //                          the GPU box (one Transport event loop: not thread-safe, like every actor).  Log window, value
 //                          garbage collection and thrifty target windows as in GpuPhase2Engine (Native.scala).
 //   GpuMenciusProxyLeader  stands where a mencius.ProxyLeader stands (mencius/ProxyLeaderMain.scala): leaders of EVERY
-//                          leader group keep sending it Phase2a and Phase2aNoopRange (mencius/Leader.scala:342-345, 455)
+//                          leader group keep sending it Phase2a and Phase2aNoopRange (mencius/Leader.scala:342-345, 455).
+//                          remoteAcceptors = true: the acceptors are the reference's own, elsewhere -- the proxy leader
+//                          forwards to them, and tallies their Phase2b / Phase2bNoopRange messages a tick at a time on the
+//                          device (fpx_mencius_phase2b_tick; mencius/ProxyLeader.scala:216-411)
 //   GpuMenciusAcceptor     stands at ONE acceptor address (mencius/AcceptorMain.scala); every acceptor address gets one,
 //                          all over the same engine.  A Mencius Leader sends Phase1a to ACCEPTOR addresses
 //                          (mencius/Leader.scala:486-491, resend timer :288-297): without an actor there a new leader
@@ -184,6 +187,78 @@ class GpuMenciusEngine[Transport <: frankenpaxos.Transport[Transport]](
     Result(Seq.empty, chosenOut, nackOut)
   }
 
+  // ---- a proxy leader among REMOTE acceptors (GpuMenciusProxyLeader, remoteAcceptors = true): only the proxy leader's
+  // tallies live in the context.  The window must cover the slots in flight: a key that lies outside it, or a range that
+  // wraps around it, is fatal here (the colocated path defers and cuts; a remote acceptor answers with the key it was
+  // sent, so the key cannot be cut).
+  private def remoteRow(slot: Int): Int = {
+    if (!inWindow(slot)) { advanceWindow(); if (!inWindow(slot)) logger.fatal(s"slot $slot lies outside the window at $base") }
+    row(slot)
+  }
+  private def remoteRangeRows(start: Int, end: Int): (Int, Int) = {
+    if (end > start) { remoteRow(start); remoteRow(end - 1) }
+    val a = row(start)
+    if (a + (end - start) > numSlots) logger.fatal(s"range [$start, $end) wraps around the window")
+    (a, a + (end - start))
+  }
+
+  // mencius/ProxyLeader.scala:216-253 without the relay: the Phase2as that are new (to be forwarded), in order
+  def openCommands(incoming: Seq[Phase2a]): Seq[Phase2a] = {
+    val n = incoming.size
+    if (n == 0) return Seq.empty
+    val slot = incoming.map(p => remoteRow(p.slot)).toArray; val round = incoming.map(_.round).toArray
+    val value = incoming.map(p => intern(row(p.slot), p.commandBatchOrNoop)).toArray
+    val isNew = new Array[Byte](n)
+    Native.check(Native.proxyOpen(handle, n, slot, round, value, isNew), logger)
+    incoming.indices.filter(isNew(_) != 0).map(incoming)
+  }
+
+  // mencius/ProxyLeader.scala:255-303 without the relay
+  def openRanges(incoming: Seq[Phase2aNoopRange]): Seq[Phase2aNoopRange] = {
+    val n = incoming.size
+    if (n == 0) return Seq.empty
+    val rows = incoming.map(p => remoteRangeRows(p.slotStartInclusive, p.slotEndExclusive))
+    val isNew = new Array[Byte](n)
+    Native.check(Native.proxyOpenNoopRanges(handle, n, rows.map(_._1).toArray, rows.map(_._2).toArray,
+                                            incoming.map(_.round).toArray, isNew), logger)
+    incoming.indices.filter(isNew(_) != 0).map(incoming)
+  }
+
+  // mencius/ProxyLeader.scala:305-411 for one tick of Phase2b (Left) and Phase2bNoopRange (Right) messages in arrival
+  // order: ONE native call; the Chosen / ChosenNoopRange to send, in message order
+  def tallyPhase2bs(msgs: Seq[Either[Phase2b, Phase2bNoopRange]]): Seq[Either[Chosen, ChosenNoopRange]] = {
+    val n = msgs.size
+    if (n == 0) return Seq.empty
+    val kind = new Array[Int](n); val group = new Array[Int](n); val acceptor = new Array[Int](n)
+    val slot = new Array[Int](n); val slotEnd = new Array[Int](n); val round = new Array[Int](n)
+    for ((m, i) <- msgs.zipWithIndex) m match {
+      case Left(p) =>
+        kind(i) = Native.WIRE_PHASE2B; acceptor(i) = p.acceptorIndex; slot(i) = remoteRow(p.slot); slotEnd(i) = -1
+        round(i) = p.round
+      case Right(p) =>
+        val (a, b) = remoteRangeRows(p.slotStartInclusive, p.slotEndExclusive)
+        kind(i) = Native.WIRE_PHASE2B_NOOP_RANGE; group(i) = p.acceptorGroupIndex; acceptor(i) = p.acceptorIndex
+        slot(i) = a; slotEnd(i) = b; round(i) = p.round
+    }
+    // at most one record per message
+    val oKind = new Array[Int](n); val oSlot = new Array[Int](n); val oEnd = new Array[Int](n)
+    val oRound = new Array[Int](n); val oValue = new Array[Int](n); val count = new Array[Int](1)
+    Native.check(Native.menciusPhase2bTick(handle, n, kind, group, acceptor, slot, slotEnd, round, oKind, oSlot, oEnd, oRound,
+                                           oValue, n, count), logger)
+    for (k <- 0 until count(0)) yield {
+      val s = slotOfRow(oSlot(k))
+      if (oKind(k) == Native.WIRE_PHASE2B) {                  // mencius/ProxyLeader.scala:335-351
+        markChosen(s)
+        Left(Chosen(slot = s, commandBatchOrNoop = valueOf(oValue(k))))
+      } else {                                               // :395-407
+        val e = s + (oEnd(k) - oSlot(k))
+        var t = s
+        while (t < e) { markChosen(t); t += L }               // the leader group's own slots
+        Right(ChosenNoopRange(slotStartInclusive = s, slotEndExclusive = e))
+      }
+    }
+  }
+
   // ---- Phase 1, acceptor side (mencius/Acceptor.scala:166-200)
   def handlePhase1a(leaderGroup: Int, acceptorGroup: Int, index: Int, phase1a: Phase1a): Either[Nack, Phase1b] = {
     val g = ctxGroup(leaderGroup, acceptorGroup)
@@ -296,7 +371,11 @@ class GpuMenciusProxyLeader[Transport <: frankenpaxos.Transport[Transport]](
     transport: Transport,
     logger: Logger,
     config: Config[Transport],
-    engine: GpuMenciusEngine[Transport]
+    engine: GpuMenciusEngine[Transport],
+    // true: the acceptors are remote (the reference's mencius.Acceptor, or anything that speaks its protocol) -- this
+    // actor relays Phase2a / Phase2aNoopRange to them and tallies their Phase2b / Phase2bNoopRange on the device
+    remoteAcceptors: Boolean = false,
+    seed: Long = System.identityHashCode(this)
 ) extends Actor(address, transport, logger) {
   override type InboundMessage = ProxyLeaderInbound
   override val serializer = ProxyLeaderInboundSerializer
@@ -306,22 +385,37 @@ class GpuMenciusProxyLeader[Transport <: frankenpaxos.Transport[Transport]](
   private val leaders = for (group <- config.leaderAddresses)
     yield for (a <- group) yield chan[Leader[Transport]](a, Leader.serializer)
   private val replicas = for (a <- config.replicaAddresses) yield chan[Replica[Transport]](a, Replica.serializer)
+  // config.acceptorAddresses(leaderGroup)(acceptorGroup)(index), mencius/ProxyLeader.scala:121-128
+  private val acceptors =
+    if (!remoteAcceptors) Seq.empty
+    else for (groups <- config.acceptorAddresses) yield for (group <- groups)
+      yield for (a <- group) yield chan[Acceptor[Transport]](a, Acceptor.serializer)
+  private val rand = new scala.util.Random(seed)
 
   // the burst, in arrival order: Left = a command, Right = a noop range
   private val pending = mutable.Buffer[Either[Phase2a, Phase2aNoopRange]]()
+  // remoteAcceptors: the acceptors' answers of the tick, in arrival order
+  private val pendingPhase2bs = mutable.Buffer[Either[Phase2b, Phase2bNoopRange]]()
   private val tick = timer("gpuMenciusTick", java.time.Duration.ZERO, () => flushTick())
+  private def enqueued(): Unit = if (pending.isEmpty && pendingPhase2bs.isEmpty) tick.start()
 
   override def receive(src: Transport#Address, inbound: ProxyLeaderInbound): Unit = {
     import ProxyLeaderInbound.Request
     inbound.request match {
       case Request.Phase2A(p) =>
-        if (pending.isEmpty) tick.start()
+        enqueued()
         pending += Left(p)
       case Request.Phase2ANoopRange(p) =>
-        if (pending.isEmpty) tick.start()
+        enqueued()
         pending += Right(p)
       case Request.HighWatermark(h) =>                       // mencius/ProxyLeader.scala:207-214
         for (group <- leaders; leader <- group) leader.send(LeaderInbound().withHighWatermark(h))
+      case Request.Phase2B(p) if remoteAcceptors =>          // mencius/ProxyLeader.scala:305-353, tallied by the tick
+        enqueued()
+        pendingPhase2bs += Left(p)
+      case Request.Phase2BNoopRange(p) if remoteAcceptors => // :355-411
+        enqueued()
+        pendingPhase2bs += Right(p)
       case Request.Phase2B(_) | Request.Phase2BNoopRange(_) =>
         logger.fatal("GpuMenciusProxyLeader tallies on the device; it never receives Phase2b messages.")
       case Request.Empty =>
@@ -346,10 +440,37 @@ class GpuMenciusProxyLeader[Transport <: frankenpaxos.Transport[Transport]](
       var j = i
       while (j < pending.size && pending(j).isLeft == pending(i).isLeft) j += 1
       val run = pending.slice(i, j)
-      deliver(if (pending(i).isLeft) engine.commands(run.map(_.left.get)) else engine.ranges(run.map(_.right.get)))
+      if (remoteAcceptors) relay(run)
+      else deliver(if (pending(i).isLeft) engine.commands(run.map(_.left.get)) else engine.ranges(run.map(_.right.get)))
       i = j
     }
     pending.clear()
+    if (pendingPhase2bs.nonEmpty) {
+      // the tick's Phase2b and Phase2bNoopRange messages in ONE native call; Chosen / ChosenNoopRange to every replica in
+      // record (= message) order (mencius/ProxyLeader.scala:335-351, 395-407)
+      val out = engine.tallyPhase2bs(pendingPhase2bs)
+      pendingPhase2bs.clear()
+      for (c <- out) c match {
+        case Left(chosen)  => replicas.foreach(_.send(ReplicaInbound().withChosen(chosen)))
+        case Right(chosen) => replicas.foreach(_.send(ReplicaInbound().withChosenNoopRange(chosen)))
+      }
+    }
+  }
+
+  // remoteAcceptors: a run of one kind is opened on the device (a duplicate is not forwarded, :222-229, 262-271) and
+  // relayed -- a command to quorumSize acceptors of its slot's acceptor group (:231-236), a range to quorumSize acceptors
+  // of EVERY acceptor group of its leader group (:274-293)
+  private def relay(run: Seq[Either[Phase2a, Phase2aNoopRange]]): Unit = {
+    if (run.head.isLeft) {
+      for (p <- engine.openCommands(run.map(_.left.get))) {
+        val lg = slotSystem.leader(p.slot)
+        val group = acceptors(lg)((p.slot / config.numLeaderGroups) % acceptors(lg).size)   // :169-176
+        rand.shuffle(group).take(config.quorumSize).foreach(_.send(AcceptorInbound().withPhase2A(p)))
+      }
+    } else {
+      for (p <- engine.openRanges(run.map(_.right.get)); group <- acceptors(slotSystem.leader(p.slotStartInclusive)))
+        rand.shuffle(group).take(config.quorumSize).foreach(_.send(AcceptorInbound().withPhase2ANoopRange(p)))
+    }
   }
 }
 

@@ -30,6 +30,8 @@ object Native {
 
   // status codes of include/fpx.h
   val OK = 0; val EINVAL = 1; val EFATAL_UNKNOWN_SLOTROUND = 2
+  // message kinds of include/fpx_wire.h (the `kind` arrays of proxyPhase2bMsgs / menciusProxyPhase2bMsgs)
+  val WIRE_PHASE2B = 2; val WIRE_PHASE2B_NOOP_RANGE = 7
 
   @native def create(cfg: Array[Int]): Long // < 0: -status
   @native def destroy(handle: Long): Int
@@ -47,6 +49,24 @@ object Native {
   @native def proxyPhase2bMsgs(handle: Long, n: Int, kind: Array[Int], groupIndex: Array[Int],
                                acceptorIndex: Array[Int], slot: Array[Int], round: Array[Int], gridCols: Int,
                                newlyChosen: Array[Byte], chosenRound: Array[Int], chosenValue: Array[Int]): Int
+  // mencius.ProxyLeader.handlePhase2aNoopRange bookkeeping for n ranges in one call (fpx_proxy_open_noop_ranges)
+  @native def proxyOpenNoopRanges(handle: Long, n: Int, slotStart: Array[Int], slotEnd: Array[Int],
+                                  round: Array[Int], isNew: Array[Byte]): Int
+  // Mencius: ONE Phase2b / Phase2bNoopRange per (acceptor, key) as remote Mencius acceptors send them, both kinds
+  // interleaved in delivery order (fpx_mencius_proxy_phase2b_msgs; mencius/ProxyLeader.scala:305-411).  kind (FPX_WIRE_*;
+  // null = all Phase2b), groupIndex (null = 0; a range message's acceptor group) and slotEnd (null = no range message)
+  // may be null; a row's outcome is at its first message, chosenValue = -1 for a ChosenNoopRange
+  @native def menciusProxyPhase2bMsgs(handle: Long, n: Int, kind: Array[Int], groupIndex: Array[Int],
+                                      acceptorIndex: Array[Int], slot: Array[Int], slotEnd: Array[Int],
+                                      round: Array[Int], newlyChosen: Array[Byte], chosenRound: Array[Int],
+                                      chosenValue: Array[Int]): Int
+  // the same as one tick: the newly chosen records (kind, slot, slotEnd or -1, round, value id or -1) compacted on the
+  // device in message order into arrays of outCap records; outCount(0) = how many there are (ECAPACITY = 5: the tick was
+  // applied, the first outCap records are written)
+  @native def menciusPhase2bTick(handle: Long, n: Int, kind: Array[Int], groupIndex: Array[Int],
+                                 acceptorIndex: Array[Int], slot: Array[Int], slotEnd: Array[Int], round: Array[Int],
+                                 outKind: Array[Int], outSlot: Array[Int], outSlotEnd: Array[Int],
+                                 outRound: Array[Int], outValue: Array[Int], outCap: Int, outCount: Array[Int]): Int
   @native def phase2Fused(handle: Long, n: Int, slot: Array[Int], round: Array[Int],
                           value: Array[Int], targetMask: Array[Long], chosen: Array[Byte],
                           chosenRound: Array[Int], chosenValue: Array[Int], nackRound: Array[Int]): Int

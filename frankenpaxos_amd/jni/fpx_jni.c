@@ -184,6 +184,70 @@ JNIEXPORT jint JNICALL Java_frankenpaxos_gpu_Native_proxyPhase2bMsgs(JNIEnv* env
   return st;
 }
 
+/* mencius.ProxyLeader.handlePhase2aNoopRange bookkeeping for n ranges (mencius/ProxyLeader.scala:255-303):
+ * fpx_proxy_open_noop_ranges */
+JNIEXPORT jint JNICALL Java_frankenpaxos_gpu_Native_proxyOpenNoopRanges(JNIEnv* env, jclass cls, jlong h, jint n,
+                                                                        jintArray slotStart, jintArray slotEnd,
+                                                                        jintArray round, jbyteArray isNew) {
+  if (n < 0) return FPX_EINVAL;
+  if (n == 0) return FPX_OK;
+  if (!has(env, slotStart, n) || !has(env, slotEnd, n) || !has(env, round, n) || !opt(env, isNew, n)) return FPX_EINVAL;
+  jint *s = in_ints(env, slotStart, n), *e = in_ints(env, slotEnd, n), *r = in_ints(env, round, n);
+  jbyte* f = out_buf(isNew, n, 1);
+  int32_t st = fpx_proxy_open_noop_ranges(CTX(h), n, s, e, r, (uint8_t*)f);
+  put_bytes(env, isNew, n, f);
+  free(s); free(e); free(r); free(f);
+  return st;
+}
+
+/* mencius.ProxyLeader.handlePhase2b + handlePhase2bNoopRange (mencius/ProxyLeader.scala:305-411) for one message per
+ * (acceptor, key): fpx_mencius_proxy_phase2b_msgs; kind, groupIndex and slotEnd may be null */
+JNIEXPORT jint JNICALL Java_frankenpaxos_gpu_Native_menciusProxyPhase2bMsgs(
+    JNIEnv* env, jclass cls, jlong h, jint n, jintArray kind, jintArray groupIndex, jintArray acceptorIndex, jintArray slot,
+    jintArray slotEnd, jintArray round, jbyteArray newlyChosen, jintArray chosenRound, jintArray chosenValue) {
+  if (n < 0) return FPX_EINVAL;
+  if (n == 0) return FPX_OK;
+  if (!opt(env, kind, n) || !opt(env, groupIndex, n) || !has(env, acceptorIndex, n) || !has(env, slot, n) ||
+      !opt(env, slotEnd, n) || !has(env, round, n) || !opt(env, newlyChosen, n) || !opt(env, chosenRound, n) ||
+      !opt(env, chosenValue, n))
+    return FPX_EINVAL;
+  jint *k = in_ints(env, kind, n), *g = in_ints(env, groupIndex, n), *a = in_ints(env, acceptorIndex, n);
+  jint *s = in_ints(env, slot, n), *e = in_ints(env, slotEnd, n), *r = in_ints(env, round, n);
+  jbyte* ch = out_buf(newlyChosen, n, 1);
+  jint *cr = out_buf(chosenRound, n, 4), *cv = out_buf(chosenValue, n, 4);
+  int32_t st = fpx_mencius_proxy_phase2b_msgs(CTX(h), n, k, g, a, s, e, r, (uint8_t*)ch, cr, cv);
+  put_bytes(env, newlyChosen, n, ch); put_ints(env, chosenRound, n, cr); put_ints(env, chosenValue, n, cv);
+  free(k); free(g); free(a); free(s); free(e); free(r); free(ch); free(cr); free(cv);
+  return st;
+}
+
+/* one tick of a Mencius proxy leader among remote acceptors: fpx_mencius_phase2b_tick; the five record arrays hold outCap
+ * records each, outCount[0] = the number of newly chosen records */
+JNIEXPORT jint JNICALL Java_frankenpaxos_gpu_Native_menciusPhase2bTick(
+    JNIEnv* env, jclass cls, jlong h, jint n, jintArray kind, jintArray groupIndex, jintArray acceptorIndex, jintArray slot,
+    jintArray slotEnd, jintArray round, jintArray outKind, jintArray outSlot, jintArray outSlotEnd, jintArray outRound,
+    jintArray outValue, jint outCap, jintArray outCount) {
+  if (n < 0 || outCap < 0 || !has(env, outCount, 1)) return FPX_EINVAL;
+  if (!opt(env, kind, n) || !opt(env, groupIndex, n) || !opt(env, slotEnd, n)) return FPX_EINVAL;
+  if (n > 0 && (!has(env, acceptorIndex, n) || !has(env, slot, n) || !has(env, round, n))) return FPX_EINVAL;
+  if (outCap > 0 && (!has(env, outKind, outCap) || !has(env, outSlot, outCap) || !has(env, outSlotEnd, outCap) ||
+                     !has(env, outRound, outCap) || !has(env, outValue, outCap)))
+    return FPX_EINVAL;
+  jint *k = in_ints(env, kind, n), *g = in_ints(env, groupIndex, n), *a = in_ints(env, acceptorIndex, n);
+  jint *s = in_ints(env, slot, n), *e = in_ints(env, slotEnd, n), *r = in_ints(env, round, n);
+  jint *ok = out_buf(outKind, outCap, 4), *os = out_buf(outSlot, outCap, 4), *oe = out_buf(outSlotEnd, outCap, 4);
+  jint *orr = out_buf(outRound, outCap, 4), *ov = out_buf(outValue, outCap, 4);
+  int32_t count = 0;
+  int32_t st = fpx_mencius_phase2b_tick(CTX(h), n, k, g, a, s, e, r, ok, os, oe, orr, ov, outCap, &count);
+  const jint written = count < outCap ? count : outCap;
+  put_ints(env, outKind, written, ok); put_ints(env, outSlot, written, os); put_ints(env, outSlotEnd, written, oe);
+  put_ints(env, outRound, written, orr); put_ints(env, outValue, written, ov);
+  jint c = count;
+  put_ints(env, outCount, 1, &c);
+  free(k); free(g); free(a); free(s); free(e); free(r); free(ok); free(os); free(oe); free(orr); free(ov);
+  return st;
+}
+
 /* the fused tick (open + Phase2a to the targeted acceptors + tally) */
 JNIEXPORT jint JNICALL Java_frankenpaxos_gpu_Native_phase2Fused(
     JNIEnv* env, jclass cls, jlong h, jint n, jintArray slot, jintArray round, jintArray value,

@@ -402,6 +402,53 @@ int32_t fpx_proxy_open_noop_ranges(fpx_ctx* ctx, int32_t n, const int32_t* slot_
  * (newly_chosen = 1) once every acceptor group has f+1 votes. */
 int32_t fpx_proxy_phase2b_noop_ranges(fpx_ctx* ctx, int32_t n, const int32_t* slot_start, const int32_t* slot_end,
                                       const int32_t* round, const uint64_t* vote_bits, uint8_t* newly_chosen);
+/* Both tallies of a Mencius proxy leader for PER-ACCEPTOR messages, as reference Mencius acceptors send them
+ * (mencius/ProxyLeader.scala:305-411): message i of the burst, in delivery order, is a Phase2b(group_index[i],
+ * acceptor_index[i], slot[i], round[i]) (kind[i] == FPX_WIRE_PHASE2B, handlePhase2b :305-353) or a
+ * Phase2bNoopRange(group_index[i], acceptor_index[i], slot[i] = slot_start, slot_end[i], round[i]) (kind[i] ==
+ * FPX_WIRE_PHASE2B_NOOP_RANGE, handlePhase2bNoopRange :355-411) -- the outputs of
+ * fpx_wire_mencius_decode_proxy_leader_inbound.  kind == NULL: every message is a Phase2b; a message of any other kind is
+ * skipped.  slot_end may be NULL when the burst has no range message.  group_index (NULL = 0) is the range message's
+ * acceptor group; a Phase2b's is ignored (its group follows from the slot, :231-235).  The bit of a message is
+ * acceptor_index for both kinds.  NO run contract applies: any number of messages per key in any order, several rounds of
+ * one key and duplicates are allowed.
+ * Contract: the tally state afterwards -- the Phase2b tallies and the range table alike -- equals what this gives: the
+ * burst's Phase2b's folded into one row per (slot, round) and handed to fpx_proxy_phase2b, and the burst's range messages
+ * folded into one num_groups x 4 row per distinct (slot_start, slot_end, round) in order of first appearance and handed to
+ * fpx_proxy_phase2b_noop_ranges.  Each row's outcome is reported at the row's FIRST member message: newly_chosen = 1,
+ * chosen_round = round, chosen_value = the value given to fpx_proxy_open, or -1 for a ChosenNoopRange(slot, slot_end)
+ * (:395-407); every other message reports newly_chosen = 0, chosen_round = chosen_value = -1.  What
+ * fpx_proxy_phase2b_noop_ranges ignores is ignored here: a Done range (:370-376) and a length-1 key held by a single-slot
+ * tally (:377-385).  A message whose bit lies outside the member set [0, replicas_total) contributes nothing: it is not
+ * looked up, never reports an unknown key and never is its row's first message.  The fold runs on the device
+ * (csrc/fpx_mencius_msgs.hpp: claim / gather / tally, one launch each for both kinds; a claim word per range-table entry,
+ * allocated by the first call) with integer atomics only: results are reproducible.  Needs FPX_BALLOT_ACCEPTOR and
+ * num_leader_groups >= 1, as the range entry points do (FPX_EINVAL otherwise).
+ * Errors: FPX_EINVAL with NOTHING applied for acceptor_index outside 0..255, a range message's group_index outside
+ * [0, num_groups), a slot outside the window, slot_end < slot or slot_end > num_slots (a range message without a slot_end
+ * array included), a round outside 0 .. 2^30 - 2; FPX_EFATAL_UNKNOWN_SLOTROUND per message for a key that was never
+ * opened (:309-316, :361-368): that message is dropped, the others are applied.  fpx_error_detail names the LOWEST offending
+ * index across both kinds.  n == 0 is FPX_OK.  The host form is synchronous and goes through the staging driver as a
+ * single run; the _dev form takes device pointers and enqueues on the context's stream. */
+int32_t fpx_mencius_proxy_phase2b_msgs(fpx_ctx* ctx, int32_t n, const int32_t* kind, const int32_t* group_index,
+                                       const int32_t* acceptor_index, const int32_t* slot, const int32_t* slot_end,
+                                       const int32_t* round, uint8_t* newly_chosen, int32_t* chosen_round,
+                                       int32_t* chosen_value);
+int32_t fpx_mencius_proxy_phase2b_msgs_dev(fpx_ctx* ctx, int32_t n, const int32_t* d_kind, const int32_t* d_group_index,
+                                           const int32_t* d_acceptor_index, const int32_t* d_slot,
+                                           const int32_t* d_slot_end, const int32_t* d_round, uint8_t* d_newly_chosen,
+                                           int32_t* d_chosen_round, int32_t* d_chosen_value);
+/* One tick of a Mencius proxy leader among remote acceptors: fpx_mencius_proxy_phase2b_msgs on the six decoded arrays
+ * (pageable or page-locked host memory), then the newly chosen records compacted on the device in message order: record k
+ * is (out_kind, out_slot = slot or slot_start, out_slot_end = slot_end or -1 for a Chosen, out_round, out_value_id = the
+ * value id or -1 for a ChosenNoopRange) -- what the proxy leader sends to every replica as Chosen / ChosenNoopRange
+ * (:335-351, :395-407).  *out_count = the number of records.  out_cap (records) too small is FPX_ECAPACITY: the tick WAS
+ * applied, *out_count is the count needed and the first out_cap records are written; an unknown-key status outranks it.
+ * Every other error is fpx_mencius_proxy_phase2b_msgs': a refused tick applies nothing.  n == 0 is FPX_OK. */
+int32_t fpx_mencius_phase2b_tick(fpx_ctx* ctx, int32_t n, const int32_t* kind, const int32_t* group_index,
+                                 const int32_t* acceptor_index, const int32_t* slot, const int32_t* slot_end,
+                                 const int32_t* round, int32_t* out_kind, int32_t* out_slot, int32_t* out_slot_end,
+                                 int32_t* out_round, int32_t* out_value_id, int32_t out_cap, int32_t* out_count);
 /* The fused step for ranges = open + acceptors + tally (the K3 of noop ranges): a range that is already
  * known is neither forwarded nor tallied again.  Outputs may be NULL.  The _dev form takes device pointers,
  * enqueues on the context's stream and needs one round per leader group within the batch (the run contract;
