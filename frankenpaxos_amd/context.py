@@ -626,6 +626,31 @@ class Context:
         if st:
             raise FpxError(st, "fpx_replica_chosen_msgs_dev")
 
+    def replica_inbox(self, kind, slot, value, mask=None, exec_count=None, reply_slot=None, order=None):
+        """a MultiPaxos replica's burst of Chosens and reads in delivery order (kinds of frankenpaxos_amd.wire), exactly as
+        the replica handles them one by one: (status, exec_count, reply_slot, order, counts, executed_watermark,
+        num_chosen); counts = [reads, reads that ran, W0, W1], order's first counts[0] entries are valid.  The output
+        arrays may be passed in (int32, len(kind)): on an error they are left as they were"""
+        kind, slot, value = _i32(kind), _i32(slot), _i32(value)
+        assert len(kind) == len(slot) == len(value)
+        n = len(kind)
+        mask = None if mask is None else np.ascontiguousarray(mask, dtype=np.uint8)
+        outs = [np.full(max(n, 1), -9, np.int32) if a is None else a for a in (exec_count, reply_slot, order)]
+        counts = np.full(4, -9, np.int32)
+        wm, nc = C.c_int32(), C.c_int32()
+        st = self.L.fpx_replica_inbox(self._h, n, _hp(kind), _hp(slot), _hp(value), _hp(mask), _hp(outs[0]), _hp(outs[1]),
+                                      _hp(outs[2]), _hp(counts), C.byref(wm), C.byref(nc))
+        return st, outs[0][:n], outs[1][:n], outs[2][:n], counts, wm.value, nc.value
+
+    def replica_inbox_dev(self, kind, slot, value, mask=None, exec_count=None, reply_slot=None, order=None, counts=None,
+                          n=None):
+        """the same on device tensors (the four outputs all given or all None: then the burst's Chosens are ingested and
+        nothing is scheduled); errors surface at sync()"""
+        st = self.L.fpx_replica_inbox_dev(self._h, kind.numel() if n is None else n, _dp(kind), _dp(slot), _dp(value),
+                                          _dp(mask), _dp(exec_count), _dp(reply_slot), _dp(order), _dp(counts))
+        if st:
+            raise FpxError(st, "fpx_replica_inbox_dev")
+
     def replica_state(self):
         wm, nc = C.c_int32(), C.c_int32()
         st = self.L.fpx_replica_state(self._h, C.byref(wm), C.byref(nc))

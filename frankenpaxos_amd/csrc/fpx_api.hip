@@ -26,6 +26,7 @@
 #include "fpx_tally_msgs.hpp"
 #include "fpx_mencius_msgs.hpp"
 #include "fpx_replica_msgs.hpp"
+#include "fpx_replica_inbox.hpp"
 #include "fpx_wire_dev.hpp"
 #include "fpx_wire_enc_dev.hpp"
 #include "../../include/fpx_wire.h"
@@ -164,6 +165,10 @@ struct fpx_ctx {
   // fpx_replica_chosen_msgs_dev (fpx_replica_msgs.hpp): the claim word of every slot ([S], INT_MAX between calls; allocated
   // by the first call), and per call the header words, the workgroups' folds, and the list of the burst's ranges
   DevBuf rm_claim, rm_buf;
+  // fpx_replica_inbox[_dev] (fpx_replica_inbox.hpp): the per-call scratch (header words, the workgroups' folds, the tiles'
+  // maxima, the sort's counts and its two key / value buffers), and the host form's staged outputs (exec_count, reply_slot,
+  // order, counts).  The claim words are rm_claim's.
+  DevBuf ri_buf, ri_out[4];
   // fpx_acceptor_phase1b_info_all[_dev] (fpx_phase1_info.hpp): the chunk counts, column totals and the go word; the host
   // form's offsets and totals
   DevBuf p1i, p1i_off, p1i_tot;
@@ -1035,7 +1040,8 @@ void free_state(fpx_ctx* ctx) {
                   &ctx->w_rec[6], &ctx->m_owner, &ctx->m_entry,  &ctx->m_rows,   &ctx->m_blk,
                   &ctx->rm_claim, &ctx->rm_buf,   &ctx->mm_claim, &ctx->mm_end,   &ctx->mm_rec[0], &ctx->mm_rec[1],
                   &ctx->mm_rec[2], &ctx->mm_rec[3], &ctx->mm_rec[4],
-                  &ctx->p1i,      &ctx->p1i_off, &ctx->p1i_tot, &ctx->p1m_buf, &ctx->p1m_tab};
+                  &ctx->p1i,      &ctx->p1i_off, &ctx->p1i_tot, &ctx->p1m_buf, &ctx->p1m_tab,
+                  &ctx->ri_buf,   &ctx->ri_out[0], &ctx->ri_out[1], &ctx->ri_out[2], &ctx->ri_out[3]};
   for (DevBuf* b : bs)
     if (b->p) (void)hipFree(b->p);
   for (DevBuf& b : ctx->p1m_stage)
@@ -3027,6 +3033,121 @@ int32_t fpx_replica_chosen_msgs(fpx_ctx* ctx, int32_t n, const int32_t* kind, co
                     });
   if (rc == FPX_EHIP || rc == FPX_ENOMEM) return rc;  // (a HIP failure: no scalars to report)
   const int st = fpx_replica_state(ctx, executed_watermark, num_chosen);
+  return st ? st : rc;
+}
+
+// multipaxos.Replica's inbox for a burst in delivery order: the Chosens as above, and when and with which reply slot
+// every read of the burst runs (fpx_replica_inbox.hpp).  Nothing is read by the host between the launches.
+int32_t fpx_replica_inbox_dev(fpx_ctx* ctx, int32_t n, const int32_t* d_kind, const int32_t* d_slot,
+                              const int32_t* d_value_id, const uint8_t* d_mask, int32_t* d_exec_count,
+                              int32_t* d_reply_slot, int32_t* d_order, int32_t* d_counts) {
+  DeviceGuard _dg(ctx);
+  if (!ctx || n < 0 || n >= (1 << 30)) return FPX_EINVAL;
+  if (ctx->g.num_leader_groups > 1) return FPX_EINVAL;  // mencius.Replica has no read handlers
+  const int nout = (d_exec_count != nullptr) + (d_reply_slot != nullptr) + (d_order != nullptr) + (d_counts != nullptr);
+  if (nout != 0 && nout != 4) return FPX_EINVAL;
+  if (n == 0 && nout == 0) return FPX_OK;
+  if (n > 0 && (!d_kind || !d_slot || !d_value_id)) return FPX_EINVAL;
+  int rc;
+  if (!ctx->rm_claim.p) {
+    if ((rc = grow(ctx, &ctx->rm_claim, (size_t)ctx->g.S * 4))) return rc;
+    ctx->bytes += (int64_t)ctx->rm_claim.cap;
+    fill32(ctx, ctx->rm_claim.p, INT_MAX, ctx->rm_claim.cap / 4);
+  }
+  const int nblk = std::max(1, (n + 255) / 256);
+  const size_t cap_n = (size_t)nblk * 256;  // >= n and >= 1
+  const size_t ntiles_max = ((size_t)ctx->g.S + RI_TILE - 1) / RI_TILE;
+  const size_t words = 3 * (size_t)RM_HDR_WORDS + 3 * (size_t)LG_MAX_PARTS + (size_t)nblk + ntiles_max +
+                       (nout ? (size_t)RI_RADIX * nblk + 4 * cap_n : 0);
+  const size_t had = ctx->ri_buf.cap;
+  if ((rc = grow(ctx, &ctx->ri_buf, words * 4))) return rc;
+  ctx->bytes += (int64_t)ctx->ri_buf.cap - (int64_t)had;
+  // the Chosens: fpx_replica_msgs.hpp's kernels on a burst without ranges
+  ReplicaMsgs m;
+  memset(&m, 0, sizeof(m));
+  m.n = n, m.nblk = nblk;
+  m.nparts = std::max(1, std::min({nblk, ctx->num_cus * 8, LG_MAX_PARTS}));
+  m.chosen_kind = FPX_WIRE_CHOSEN, m.range_kind = FPX_WIRE_CHOSEN_NOOP_RANGE;
+  m.kind = d_kind, m.slot = d_slot, m.slot_end = d_slot, m.value = d_value_id, m.mask = d_mask;
+  m.claim = (int32_t*)ctx->rm_claim.p;
+  m.hdr = (int32_t*)ctx->ri_buf.p;
+  ReplicaInbox b;
+  memset(&b, 0, sizeof(b));
+  b.n = n, b.S = ctx->g.S;
+  b.kind = d_kind, b.slot = d_slot, b.mask = d_mask;
+  b.claim = m.claim, b.mhdr = m.hdr, b.rhdr = b.mhdr + RM_HDR_WORDS, b.hdr = b.rhdr + RM_HDR_WORDS;
+  m.parts = b.hdr + RM_HDR_WORDS;
+  b.blk = m.parts + 3 * LG_MAX_PARTS, b.tmax = b.blk + nblk;
+  if (nout) {
+    b.hist = b.tmax + ntiles_max;
+    b.key[0] = b.hist + (size_t)RI_RADIX * nblk, b.key[1] = b.key[0] + cap_n;
+    b.val[0] = b.key[1] + cap_n, b.val[1] = b.val[0] + cap_n;
+  }
+  b.exec_count = d_exec_count, b.reply_slot = d_reply_slot, b.order = d_order, b.counts = d_counts;
+  ReplicaMsgs r = m;  // the reads' counts through k_rm_offsets: its "number of ranges" is the number of reads
+  r.hdr = b.rhdr, r.blk = b.blk;
+  const dim3 per_msg(nblk), blk(256);
+  const int sweep = std::min(std::max(nblk, ctx->num_cus), ctx->num_cus * 8);
+  hipLaunchKernelGGL(k_ri_claim, per_msg, blk, 0, ctx->stream, ctx->g, ctx->st, b);
+  hipLaunchKernelGGL(k_rm_apply, dim3(m.nparts), blk, 0, ctx->stream, ctx->g, ctx->st, m);
+  hipLaunchKernelGGL(k_rm_prep, dim3(1), blk, 0, ctx->stream, ctx->g, ctx->st, m);
+  hipLaunchKernelGGL(k_rm_scan, dim3(ctx->num_cus * 4), blk, 0, ctx->stream, ctx->g, ctx->st, m);
+  if (!nout) {
+    hipLaunchKernelGGL(k_rm_finish, dim3(sweep), blk, 0, ctx->stream, ctx->g, ctx->st, m);
+    return launch_check(ctx);
+  }
+  const int tiles_grid = (int)std::max<size_t>(1, std::min<size_t>(ntiles_max, (size_t)ctx->num_cus * 8));
+  hipLaunchKernelGGL(k_rm_offsets, dim3(1), dim3(1024), 0, ctx->stream, r);
+  hipLaunchKernelGGL(k_ri_tilemax, dim3(tiles_grid), blk, 0, ctx->stream, ctx->st, b);
+  hipLaunchKernelGGL(k_ri_tilescan, dim3(1), dim3(RI_SCAN_THREADS), 0, ctx->stream, ctx->st, b);
+  hipLaunchKernelGGL(k_ri_execby, dim3(tiles_grid), blk, 0, ctx->stream, b);
+  hipLaunchKernelGGL(k_ri_reads, per_msg, blk, 0, ctx->stream, b);
+  // keys are 0 .. num_slots + 1: the pass count is fixed per context
+  int bits = 0;
+  while (((int64_t)ctx->g.S + 1) >> bits) ++bits;
+  const int passes = (bits + RI_RADIX_BITS - 1) / RI_RADIX_BITS;
+  for (int p = 0; p < passes; ++p) {
+    RiSort a;
+    a.hdr = b.hdr, a.hist = b.hist, a.shift = p * RI_RADIX_BITS;
+    a.key_in = b.key[p & 1], a.val_in = b.val[p & 1];
+    a.key_out = b.key[(p + 1) & 1], a.val_out = p + 1 == passes ? d_order : b.val[(p + 1) & 1];
+    hipLaunchKernelGGL(k_ri_hist, per_msg, blk, 0, ctx->stream, a);
+    hipLaunchKernelGGL(k_ri_hscan, dim3(1), dim3(1024), 0, ctx->stream, a);
+    hipLaunchKernelGGL(k_ri_scatter, per_msg, blk, 0, ctx->stream, a);
+  }
+  hipLaunchKernelGGL(k_ri_finish, dim3(sweep), blk, 0, ctx->stream, ctx->g, ctx->st, b);
+  return launch_check(ctx);
+}
+
+// the host form: ONE run through the staging driver; the outputs come down only when the burst was applied
+int32_t fpx_replica_inbox(fpx_ctx* ctx, int32_t n, const int32_t* kind, const int32_t* slot, const int32_t* value_id,
+                          const uint8_t* mask, int32_t* exec_count, int32_t* reply_slot, int32_t* order, int32_t counts[4],
+                          int32_t* executed_watermark, int32_t* num_chosen) {
+  DeviceGuard _dg(ctx);
+  if (!ctx || n < 0 || n >= (1 << 30) || (n > 0 && (!kind || !slot || !value_id))) return FPX_EINVAL;
+  if (ctx->g.num_leader_groups > 1) return FPX_EINVAL;
+  if (n > 0 && (!exec_count || !reply_slot || !order)) return FPX_EINVAL;
+  if (!counts) return FPX_EINVAL;
+  int rc;
+  const size_t cap = (size_t)std::max(n, 1) * 4;
+  for (int a = 0; a < 3; ++a)
+    if ((rc = grow(ctx, &ctx->ri_out[a], cap))) return rc;
+  if ((rc = grow(ctx, &ctx->ri_out[3], 16))) return rc;
+  rc = host_batch(ctx, n, {{&ctx->d_i32_a, kind, 4}, {&ctx->d_slot, slot, 4}, {&ctx->d_value, value_id, 4}, {&ctx->d_u8, mask, 1}},
+                  {}, nullptr, [&](int, int) {
+                    return fpx_replica_inbox_dev(ctx, n, (const int32_t*)ctx->d_i32_a.p, (const int32_t*)ctx->d_slot.p,
+                                                 (const int32_t*)ctx->d_value.p, mask ? (const uint8_t*)ctx->d_u8.p : nullptr,
+                                                 (int32_t*)ctx->ri_out[0].p, (int32_t*)ctx->ri_out[1].p,
+                                                 (int32_t*)ctx->ri_out[2].p, (int32_t*)ctx->ri_out[3].p);
+                  });
+  if (rc == FPX_EHIP || rc == FPX_ENOMEM) return rc;  // (a HIP failure: no scalars to report)
+  if (rc == FPX_OK) {
+    int32_t* outs[3] = {exec_count, reply_slot, order};
+    for (int a = 0; a < 3; ++a)
+      if (n > 0) HIPCHK(ctx, hipMemcpyAsync(outs[a], ctx->ri_out[a].p, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(counts, ctx->ri_out[3].p, 16, hipMemcpyDeviceToHost, ctx->stream));
+  }
+  const int st = fpx_replica_state(ctx, executed_watermark, num_chosen);  // (synchronises the stream)
   return st ? st : rc;
 }
 

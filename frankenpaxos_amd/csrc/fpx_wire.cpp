@@ -125,6 +125,22 @@ int32_t fpx_wire_decode_replica_inbound(const uint8_t* buf, int64_t buf_len, con
   });
 }
 
+int32_t fpx_wire_decode_replica_inbound_reads(const uint8_t* buf, int64_t buf_len, const int64_t* offsets, int32_t n,
+                                              int32_t* kind, int32_t* slot, int32_t* is_noop, int64_t* value_off,
+                                              int32_t* value_len, int32_t* count, int32_t* bad_index) {
+  if (n > 0 && (!kind || !slot)) return FPX_EINVAL;
+  return decode_loop(buf, buf_len, offsets, n, bad_index, [&](int32_t i, Reader r) {
+    ReplicaMsg o;
+    const bool ok = parse_replica_inbound_reads(buf, r, &o);
+    kind[i] = o.kind, slot[i] = o.slot;
+    if (is_noop) is_noop[i] = o.is_noop;
+    if (value_off) value_off[i] = o.value_off;
+    if (value_len) value_len[i] = o.value_len;
+    if (count) count[i] = o.count;
+    return ok;
+  });
+}
+
 int32_t fpx_wire_phase2b_rows(int32_t n, const int32_t* kind, const int32_t* group_index,
                               const int32_t* acceptor_index, const int32_t* slot, const int32_t* round,
                               int32_t grid_cols, int32_t* num_rows, int32_t* row_slot, int32_t* row_round,

@@ -204,6 +204,100 @@ FPX_HD inline bool parse_acceptor_inbound(const uint8_t* base, Reader r, Msg* o)
   return r.ok;
 }
 
+// ---- the replica's inbox with its read path: ReplicaInbound fields 1 - 7   MultiPaxos.proto:351-396, 566-575 ----------
+struct ReplicaMsg {
+  int32_t kind = 0, slot = -1, is_noop = -1, value_len = -1;
+  int32_t count = -1;      // a read: its number of commands
+  int64_t value_off = -1;  // Chosen: the CommandBatchOrNoop; a read: the Command; a read batch: the whole inner message
+};
+
+// CommandId { bytes client_address = 1; int32 client_pseudonym = 2; int32 client_id = 3 }, all required   :188-196
+FPX_HD inline bool check_command_id(Reader c) {
+  unsigned seen = 0;
+  while (c.more()) {
+    const uint64_t tag = c.varint();
+    const uint32_t field = (uint32_t)(tag >> 3), wt = (uint32_t)(tag & 7);
+    if (field == 1 && wt == 2) (void)c.sub(), seen |= 2u;
+    else if ((field == 2 || field == 3) && wt == 0) (void)c.varint(), seen |= 1u << field;
+    else c.skip(wt);
+  }
+  return c.ok && seen == 0xeu;
+}
+
+// Command { CommandId command_id = 1; bytes command = 2 }, both required   :198-204
+FPX_HD inline bool check_command(Reader c) {
+  unsigned seen = 0;
+  while (c.more()) {
+    const uint64_t tag = c.varint();
+    const uint32_t field = (uint32_t)(tag >> 3), wt = (uint32_t)(tag & 7);
+    if (field == 1 && wt == 2) {
+      Reader id = c.sub();
+      if (!c.ok || !check_command_id(id)) return false;
+      seen |= 2u;
+    } else if (field == 2 && wt == 2) {
+      (void)c.sub(), seen |= 4u;
+    } else {
+      c.skip(wt);
+    }
+  }
+  return c.ok && seen == 6u;
+}
+
+// One read request.  slot_field / command_field: the field numbers inside it (slot_field 0: an eventual read, which has
+// none); batch: `command` is repeated (any number, none included), otherwise required (the last one wins)
+FPX_HD inline bool parse_read(const uint8_t* base, Reader m, int slot_field, int command_field, bool batch, int kind,
+                              ReplicaMsg* o) {
+  *o = ReplicaMsg();
+  const uint8_t* at = m.p;
+  int32_t len = (int32_t)(m.end - m.p), count = 0, slot = -1;
+  bool have_slot = slot_field == 0;
+  while (m.more()) {
+    const uint64_t tag = m.varint();
+    const uint32_t field = (uint32_t)(tag >> 3), wt = (uint32_t)(tag & 7);
+    if (slot_field && (int)field == slot_field && wt == 0) {
+      slot = as_i32(m.varint()), have_slot = true;
+    } else if ((int)field == command_field && wt == 2) {
+      Reader c = m.sub();
+      if (!m.ok) return false;
+      if (!batch) at = c.p, len = (int32_t)(c.end - c.p);
+      if (!check_command(c)) return false;
+      ++count;
+    } else {
+      m.skip(wt);
+    }
+  }
+  if (!m.ok || !have_slot || (!batch && count == 0)) return false;
+  o->kind = kind, o->slot = slot, o->value_off = at - base, o->value_len = len, o->count = batch ? count : 1;
+  return true;
+}
+
+// ReplicaInbound { oneof request { Chosen chosen = 1; ReadRequest read_request = 2; SequentialReadRequest
+//   sequential_read_request = 3; EventualReadRequest eventual_read_request = 4; ReadRequestBatch read_request_batch = 5;
+//   SequentialReadRequestBatch sequential_read_request_batch = 6; EventualReadRequestBatch eventual_read_request_batch = 7 } }
+FPX_HD inline bool parse_replica_inbound_reads(const uint8_t* base, Reader r, ReplicaMsg* o) {
+  while (r.more()) {  // the last member of the oneof that is present wins
+    const uint64_t tag = r.varint();
+    const uint32_t field = (uint32_t)(tag >> 3), wt = (uint32_t)(tag & 7);
+    if (field == 1 && wt == 2) {  // Chosen { slot = 1; command_batch_or_noop = 2 }
+      Fields f;
+      if (!parse_flat(r.sub(), 2, &f) || !r.ok || (f.seen & 0x2) != 0x2 || !f.has_value) return false;
+      *o = ReplicaMsg();
+      o->kind = 4, o->slot = f.i[1];
+      o->is_noop = f.value.is_noop, o->value_off = f.value.at - base, o->value_len = f.value.len;
+    } else if (field >= 2 && field <= 7 && wt == 2) {
+      Reader m = r.sub();
+      if (!r.ok) return false;
+      const bool eventual = field == 4 || field == 7, batch = field >= 5;
+      // kinds: FPX_WIRE_READ_REQUEST 12, SEQUENTIAL 13, EVENTUAL 14, and their batches 24, 25, 26
+      const int kind = batch ? 19 + (int)field : 10 + (int)field;
+      if (!parse_read(base, m, eventual ? 0 : 1, eventual ? 1 : 2, batch, kind, o)) return false;
+    } else {
+      r.skip(wt);
+    }
+  }
+  return r.ok;
+}
+
 // message i of a tick is buf[offsets[i] .. offsets[i + 1]): is offsets[i] a legal boundary?
 FPX_HD inline bool offset_ok(const int64_t* offsets, int32_t i, int64_t buf_len) {
   return offsets[i] >= 0 && offsets[i] <= buf_len && (i == 0 || offsets[i] >= offsets[i - 1]);

@@ -472,6 +472,36 @@ class Phase2Engine {
     numChosen_ = nc;
     return wm;
   }
+  // One message of a replica's inbox (Replica.scala:532-560): kind = FPX_WIRE_CHOSEN (slot, value id) or one of the
+  // read kinds of include/fpx_wire.h (slot = the request's slot, ignored for an eventual read); a batch is one message.
+  struct ReplicaInbound { int32_t kind, slot, value; };
+  // A read of the burst: its index in the burst, the number of log entries executed before it runs, and the slot its
+  // ReadReply carries (executedWatermark - 1 as executeRead evaluates it: r - 1 for a read released under slot r).
+  struct ScheduledRead { int32_t index, execCount, replySlot; };
+  struct InboxSchedule {
+    int executedBefore = 0, executedWatermark = 0;  // the caller executes slots executedBefore .. executedWatermark - 1
+    std::vector<ScheduledRead> ran;                 // in the order the reference runs them
+    std::vector<int32_t> stillDeferred;             // hand these back at the FRONT of the next burst, in this order
+  };
+  // Replica.handleChosen + executeLog + handleDeferrableRead[s] / handleEventualRead[s] / processDeferredReads
+  // (Replica.scala:394-413, 455-529, 572-590, 629-690) for a burst of the inbox in delivery order, in one device call and
+  // exactly as if handled one by one (fpx_replica_inbox).  The state machine, the client table and the replies stay with
+  // the caller.
+  InboxSchedule replicaHandleInbox(const std::vector<ReplicaInbound>& msgs) {
+    const int32_t n = (int32_t)msgs.size();
+    std::vector<int32_t> kind(n), slot(n), value(n), exec(n), reply(n), order(n);
+    for (int32_t i = 0; i < n; ++i) kind[i] = msgs[i].kind, slot[i] = msgs[i].slot, value[i] = msgs[i].value;
+    int32_t counts[4] = {0, 0, 0, 0}, wm = 0, nc = 0;
+    check(fpx_replica_inbox(ctx_, n, kind.data(), slot.data(), value.data(), nullptr, exec.data(), reply.data(), order.data(),
+                            counts, &wm, &nc),
+          "Replica.handleChosen / handleDeferrableRead / handleEventualRead");
+    numChosen_ = nc;
+    InboxSchedule out;
+    out.executedBefore = counts[2], out.executedWatermark = counts[3];
+    for (int32_t k = 0; k < counts[1]; ++k) out.ran.push_back(ScheduledRead{order[k], exec[order[k]], reply[order[k]]});
+    out.stillDeferred.assign(order.begin() + counts[1], order.begin() + counts[0]);
+    return out;
+  }
   int numChosen() const { return numChosen_; }
 
   fpx_ctx* context() { return ctx_; }

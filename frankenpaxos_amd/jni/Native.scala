@@ -115,6 +115,11 @@ object Native {
   @native def replicaChosenMsgs(handle: Long, n: Int, kind: Array[Int], slot: Array[Int],
                                 slotEnd: Array[Int], value: Array[Int], mask: Array[Byte],
                                 state: Array[Int]): Int
+  // a MultiPaxos replica's burst of Chosens and reads in delivery order (fpx_replica_inbox): execCount / replySlot per
+  // message, order = the reads that ran in run order then the still-deferred ones, counts = {reads, ran, W0, W1}
+  @native def replicaInbox(handle: Long, n: Int, kind: Array[Int], slot: Array[Int], value: Array[Int],
+                           mask: Array[Byte], execCount: Array[Int], replySlot: Array[Int], order: Array[Int],
+                           counts: Array[Int], state: Array[Int]): Int
   // Mencius noop ranges: n per call (the fused step), and the unfused pieces for one range
   @native def noopRangesFused(handle: Long, n: Int, numGroups: Int, slotStart: Array[Int],
                               slotEnd: Array[Int], round: Array[Int], targetMasks: Array[Long],
@@ -676,6 +681,89 @@ class GpuLeaderRecovery(logger: Logger, handle: Long, round: Int, chosenWatermar
         commandBatchOrNoop = if (r.valueIds(j) < 0) CommandBatchOrNoop().withNoop(Noop()) else values(r.valueIds(j)))
       (phase2as, r.nextSlot)                                                          // Leader.scala:553-569
     }
+  }
+}
+
+// ---- the replica's log and read path: a helper, not an actor (like GpuLeaderRecovery).  It buffers a tick's decoded
+// ReplicaInbounds, puts the reads that are still deferred in front of them, hands the burst to fpx_replica_inbox and
+// returns the schedule multipaxos.Replica would have followed message by message (Replica.scala:394-413, 455-529,
+// 572-590, 629-690): for every slot executed this tick its value, then the reads released there, and the reads that ran
+// at once in between.  The state machine, the client table, the routing of ClientReply / ReadReply and the recover timer
+// stay with the caller, and so does sending the ChosenWatermarks this helper says are due.  `handle` is a MultiPaxos
+// context (one leader group) that holds this replica's log.
+class GpuReplicaLog(logger: Logger, handle: Long, index: Int, numReplicas: Int, sendChosenWatermarkEveryNEntries: Int) {
+  // one read request as it arrived: a single command or a whole batch (one message, one slot, one fate)
+  case class Read(kind: Int, slot: Int, src: Any, commands: Seq[Command])
+  // a step of the schedule, in the order the reference takes them
+  sealed trait Step
+  case class Execute(slot: Int, value: CommandBatchOrNoop) extends Step
+  // replySlot: what executeRead puts into ReadReply.slot (executedWatermark - 1 as it stands when the read runs: r - 1
+  // for a read released under slot r, because executeLog has not incremented the watermark yet, :405-413, 526)
+  case class RunRead(read: Read, replySlot: Int) extends Step
+  case class Tick(steps: Seq[Step], chosenWatermarks: Seq[Int], executedWatermark: Int, numChosen: Int)
+
+  private val kinds = mutable.ArrayBuffer[Int](); private val slots = mutable.ArrayBuffer[Int]()
+  private val chosen = mutable.ArrayBuffer[CommandBatchOrNoop]()        // value id = position here
+  private val valueIds = mutable.ArrayBuffer[Int]()
+  private val reads = mutable.ArrayBuffer[Read]()                       // by message index (null for a Chosen)
+  private var deferred = Vector[Read]()                                 // still deferred, in hand-back order
+  // the values in the log above the watermark (the device holds their ids only for the burst that put them)
+  private val held = mutable.Map[Int, CommandBatchOrNoop]()
+
+  private def add(kind: Int, slot: Int, valueId: Int, read: Read): Unit = {
+    kinds += kind; slots += slot; valueIds += valueId; reads += read
+  }
+
+  def receive(src: Any, inbound: ReplicaInbound): Unit = {
+    import ReplicaInbound.Request
+    inbound.request match {
+      case Request.Chosen(c) =>
+        chosen += c.commandBatchOrNoop
+        add(4 /*FPX_WIRE_CHOSEN*/, c.slot, chosen.size - 1, null)
+      case Request.ReadRequest(r)                => add(12, r.slot, -1, Read(12, r.slot, src, Seq(r.command)))
+      case Request.SequentialReadRequest(r)      => add(13, r.slot, -1, Read(13, r.slot, src, Seq(r.command)))
+      case Request.EventualReadRequest(r)        => add(14, -1, -1, Read(14, -1, src, Seq(r.command)))
+      case Request.ReadRequestBatch(r)           => add(24, r.slot, -1, Read(24, r.slot, src, r.command))
+      case Request.SequentialReadRequestBatch(r) => add(25, r.slot, -1, Read(25, r.slot, src, r.command))
+      case Request.EventualReadRequestBatch(r)   => add(26, -1, -1, Read(26, -1, src, r.command))
+      case Request.Empty                         => logger.fatal("Empty ReplicaInbound encountered.")
+    }
+  }
+
+  // the tick: everything received since the last one, behind the reads still deferred
+  def flush(): Tick = {
+    val burstReads = deferred ++ reads
+    val k = deferred.map(_.kind).toArray ++ kinds; val s = deferred.map(_.slot).toArray ++ slots
+    val v = Array.fill(deferred.size)(-1) ++ valueIds
+    val n = k.length
+    val (exec, reply, order) = (new Array[Int](n), new Array[Int](n), new Array[Int](n))
+    val (counts, state) = (new Array[Int](4), new Array[Int](2))
+    Native.check(Native.replicaInbox(handle, n, k, s, v, null, exec, reply, order, counts, state), logger)
+    val (numReads, ran, w0, w1) = (counts(0), counts(1), counts(2), counts(3))
+    // the value of every slot executed this tick: put by this burst, or in the log from an earlier one
+    val put = mutable.Map[Int, CommandBatchOrNoop]()
+    // (a Chosen below W0 is a duplicate of an executed slot; the first Chosen of a slot is the one that was put)
+    for (i <- 0 until n if k(i) == 4 && s(i) >= w0 && !put.contains(s(i)) && !held.contains(s(i))) put(s(i)) = chosen(v(i))
+    held ++= put
+    val steps = mutable.ArrayBuffer[Step]()
+    var next = 0                                                        // into order(0 until ran)
+    def runReadsUpTo(executed: Int): Unit =
+      while (next < ran && exec(order(next)) <= executed) {
+        steps += RunRead(burstReads(order(next)), reply(order(next))); next += 1
+      }
+    runReadsUpTo(w0)
+    val watermarks = mutable.ArrayBuffer[Int]()
+    for (slot <- w0 until w1) {
+      steps += Execute(slot, held.remove(slot).get)
+      runReadsUpTo(slot + 1)
+      // Replica.scala:425-427, after executedWatermark += 1
+      val wm = slot + 1
+      if (wm % sendChosenWatermarkEveryNEntries == 0 && (wm / sendChosenWatermarkEveryNEntries) % numReplicas == index)
+        watermarks += wm
+    }
+    deferred = (ran until numReads).map(j => burstReads(order(j))).toVector
+    kinds.clear(); slots.clear(); valueIds.clear(); reads.clear(); chosen.clear()
+    Tick(steps.toSeq, watermarks.toSeq, state(0), state(1))
   }
 }
 

@@ -398,6 +398,35 @@ JNIEXPORT jint JNICALL Java_frankenpaxos_gpu_Native_replicaChosenMsgs(JNIEnv* en
   return st;
 }
 
+/* multipaxos.Replica's inbox for a burst in delivery order, Chosens and reads: multipaxos/Replica.scala:394-413, 455-529,
+ * 572-590, 629-690 (fpx_replica_inbox).  kind as fpx_wire.h numbers it.  execCount, replySlot and order are n long, counts
+ * = {reads, reads that ran, W0, W1}, state = {executedWatermark, numChosen}.  On an error the output arrays are left as
+ * they were. */
+JNIEXPORT jint JNICALL Java_frankenpaxos_gpu_Native_replicaInbox(JNIEnv* env, jclass cls, jlong h, jint n, jintArray kind,
+                                                                 jintArray slot, jintArray value, jbyteArray mask,
+                                                                 jintArray execCount, jintArray replySlot, jintArray order,
+                                                                 jintArray counts, jintArray state) {
+  if (n < 0 || (n > 0 && (!has(env, kind, n) || !has(env, slot, n) || !has(env, value, n) || !has(env, execCount, n) ||
+                          !has(env, replySlot, n) || !has(env, order, n))) ||
+      !opt(env, mask, n) || !has(env, counts, 4) || !opt(env, state, 2))
+    return FPX_EINVAL;
+  jint *k = in_ints(env, kind, n), *s = in_ints(env, slot, n), *v = in_ints(env, value, n);
+  jbyte* m = in_bytes(env, mask, n);
+  jint *ec = out_buf(execCount, n, sizeof(jint)), *rs = out_buf(replySlot, n, sizeof(jint)), *od = out_buf(order, n, sizeof(jint));
+  jint c[4] = {0, 0, 0, 0}, o[2] = {0, 0};
+  int32_t st = FPX_ENOMEM;
+  if (n == 0 || (k && s && v && ec && rs && od && (m || !mask)))
+    st = fpx_replica_inbox(CTX(h), n, k, s, v, (const uint8_t*)m, ec, rs, od, c, &o[0], &o[1]);
+  if (st == FPX_OK) {
+    put_ints(env, execCount, n, ec), put_ints(env, replySlot, n, rs);
+    put_ints(env, order, c[0], od);
+    put_ints(env, counts, 4, c);
+  }
+  if (st != FPX_ENOMEM) put_ints(env, state, 2, o);
+  free(k); free(s); free(v); free(m); free(ec); free(rs); free(od);
+  return st;
+}
+
 /* Mencius noop ranges, n per call (mencius/Acceptor.scala:237-291, mencius/ProxyLeader.scala:255-303, 355-411): the
  * fused step = open + acceptors + tally.  Bitmaps are n x numGroups x 4 longs. */
 JNIEXPORT jint JNICALL Java_frankenpaxos_gpu_Native_noopRangesFused(

@@ -11,6 +11,11 @@ MULTIPAXOS, MENCIUS = 0, 1     # dialect of the device encoders (FPX_WIRE_MULTIP
 OTHER, PHASE2A, PHASE2B, PHASE1A, CHOSEN, NACK, PHASE2A_NOOP_RANGE, PHASE2B_NOOP_RANGE, CHOSEN_NOOP_RANGE = range(9)
 PHASE1B = 9
 MAX_SLOT_REQUEST, BATCH_MAX_SLOT_REQUEST = 10, 11      # the acceptor's read path (multipaxos/Acceptor.scala:222-254)
+# the replica's read path (multipaxos/Replica.scala:455-529, 629-690); a batch is ONE message
+READ_REQUEST, SEQUENTIAL_READ_REQUEST, EVENTUAL_READ_REQUEST = 12, 13, 14
+READ_REQUEST_BATCH, SEQUENTIAL_READ_REQUEST_BATCH, EVENTUAL_READ_REQUEST_BATCH = 24, 25, 26
+DEFERRABLE_READS = (READ_REQUEST, SEQUENTIAL_READ_REQUEST, READ_REQUEST_BATCH, SEQUENTIAL_READ_REQUEST_BATCH)
+EVENTUAL_READS = (EVENTUAL_READ_REQUEST, EVENTUAL_READ_REQUEST_BATCH)
 EPX_PRE_ACCEPT, EPX_PRE_ACCEPT_OK, EPX_ACCEPT, EPX_ACCEPT_OK, EPX_COMMIT, EPX_PREPARE, EPX_PREPARE_OK, EPX_NACK = range(16, 24)
 
 
@@ -52,6 +57,7 @@ def _L():
                      "fpx_wire_encode_leader_nack_dev", "fpx_wire_phase2_tick", "fpx_wire_phase2b_tick"):
             getattr(L, name).restype = C.c_int32
         L.fpx_wire_decode_replica_inbound.argtypes = [VP, C.c_int64, VP, C.c_int32] + [VP] * 5 + [I32P]
+        L.fpx_wire_decode_replica_inbound_reads.argtypes = [VP, C.c_int64, VP, C.c_int32] + [VP] * 6 + [I32P]
         L.fpx_wire_mencius_decode_proxy_leader_inbound.argtypes = [VP, C.c_int64, VP, C.c_int32] + [VP] * 9 + [I32P]
         L.fpx_wire_mencius_decode_acceptor_inbound.argtypes = [VP, C.c_int64, VP, C.c_int32] + [VP] * 8 + [I32P]
         L.fpx_wire_mencius_decode_replica_inbound.argtypes = [VP, C.c_int64, VP, C.c_int32] + [VP] * 6 + [I32P]
@@ -126,6 +132,13 @@ def decode_acceptor_inbound(messages):
 
 def decode_replica_inbound(messages):
     return _decode("fpx_wire_decode_replica_inbound", messages, ["kind", "slot", "is_noop", "value_off", "value_len"])
+
+
+def decode_replica_inbound_reads(messages, offsets=None):
+    """ReplicaInbound with the read path: the arrays Context.replica_inbox takes (kind, slot), where each Chosen's value
+    and each read's Command(s) lie, and a read's number of commands"""
+    return _decode("fpx_wire_decode_replica_inbound_reads", messages,
+                   ["kind", "slot", "is_noop", "value_off", "value_len", "count"], offsets)
 
 
 def phase2b_rows(d, grid_cols=0):

@@ -934,6 +934,50 @@ int32_t fpx_replica_chosen_msgs_dev(fpx_ctx* ctx, int32_t n, const int32_t* d_ki
 int32_t fpx_replica_chosen_msgs(fpx_ctx* ctx, int32_t n, const int32_t* kind, const int32_t* slot,
                                 const int32_t* slot_end, const int32_t* value_id, const uint8_t* mask,
                                 int32_t* executed_watermark, int32_t* num_chosen);
+/* multipaxos.Replica's inbox (multipaxos/Replica.scala): handleChosen + executeLog (:572-590, 394-413) and the read path,
+ * handleDeferrableRead[s] / processDeferredReads / executeRead and the eventual reads (:455-529, 629-690), for a BURST of n
+ * messages in delivery order.  kind[i] (fpx_wire.h): FPX_WIRE_CHOSEN = Chosen(slot[i], value_id[i]); a DEFERRABLE read =
+ * FPX_WIRE_READ_REQUEST / SEQUENTIAL_READ_REQUEST / READ_REQUEST_BATCH / SEQUENTIAL_READ_REQUEST_BATCH with the request's
+ * slot in slot[i] (any int32: -1 is what a read batcher sends, negative means "at once"); an EVENTUAL read =
+ * FPX_WIRE_EVENTUAL_READ_REQUEST[_BATCH] (slot[i] is ignored).  value_id[i] is read for Chosens only.  Any other kind, and
+ * any message with mask[i] == 0 (mask may be NULL), is skipped.  A batch is ONE message: its commands share one slot and
+ * one fate.  With W0 = executedWatermark before the burst, W(i) = the watermark after the messages < i and W1 = the
+ * watermark after the burst, the result is EXACTLY that of handling the messages one by one:
+ *   Chosen: as fpx_replica_chosen_msgs handles a Chosen -- the lower index puts a slot, a slot that is in the log already
+ *     is ignored, numChosen counts the puts; the log, numChosen and executedWatermark end as they do there.
+ *   eventual read at i: runs at once: exec_count[i] = W(i), reply_slot[i] = W(i) - 1.
+ *   deferrable read at i with slot r: r < W(i): at once, as above.  Otherwise it is deferred under r.  r < W1: it is
+ *     released in this burst, inside the executeLog that executes slot r, after that slot's commands and before the next
+ *     slot's: exec_count[i] = r + 1 and reply_slot[i] = r - 1.  That reply slot is the reference's as it evaluates it, kept
+ *     as is: executeRead reads executedWatermark - 1 while executeLog has not yet incremented the watermark past r
+ *     (:405-413, 526), so a released read reports one slot less than the same read would have reported had it arrived
+ *     right after the Chosen.  r >= W1 (r >= num_slots included): still deferred, exec_count[i] = reply_slot[i] = -1.
+ *   anything that is not a read (Chosens, skipped messages): exec_count[i] = reply_slot[i] = -2.
+ * exec_count is the number of log entries executed before the read runs.  order: first the indices of the reads that run in
+ * this burst, in the order the reference runs them = ascending (exec_count, index) (the reads deferred under r all arrived
+ * before the message that executed r, the reads that ran at once with exec_count r + 1 all after it), then the reads still
+ * deferred in index order; only its first counts[0] entries are written.  counts[4] = the number of reads, the number that
+ * ran, W0, W1.  The caller runs its state machine over slots W0 .. W1 - 1, interleaving the reads by exec_count, and hands
+ * the still-deferred reads back at the FRONT of its next burst in the order `order` lists them: the call keeps no read
+ * state between bursts, and because the watermark does not move between calls they defer again, ahead of every newer read
+ * of their slot -- re-submission is exact.
+ * MultiPaxos contexts only: num_leader_groups > 1 is FPX_EINVAL at once (mencius.Replica has no read handlers).
+ * _dev: device pointers (arrays of n; d_counts of 4), enqueued on the context's stream, nothing is read by the host
+ * between its passes.  A Chosen with a slot outside [0, num_slots) is found on the device before anything is applied:
+ * FPX_EINVAL at fpx_sync, the lowest offending index in fpx_error_detail, log and scalars untouched, no output written.
+ * The four outputs may be NULL together (some but not all: FPX_EINVAL): then the call is fpx_replica_chosen_msgs_dev for
+ * a burst without ranges.  NULL context, n < 0 or n >= 2^30, or a NULL d_kind / d_slot / d_value_id with n > 0:
+ * FPX_EINVAL at once, nothing enqueued.  The claim words are fpx_replica_chosen_msgs_dev's (4 B x num_slots); the call's
+ * scratch (4 B per 256 slots and about 17 B per message) lives in the context, is allocated on first use, grows with n and
+ * is counted by fpx_device_bytes.
+ * The host form takes host arrays, any n, and is synchronous; exec_count, reply_slot and order (n > 0) and counts are
+ * required there, executed_watermark and num_chosen may be NULL; on an error the output arrays are left untouched. */
+int32_t fpx_replica_inbox_dev(fpx_ctx* ctx, int32_t n, const int32_t* d_kind, const int32_t* d_slot,
+                              const int32_t* d_value_id, const uint8_t* d_mask, int32_t* d_exec_count,
+                              int32_t* d_reply_slot, int32_t* d_order, int32_t* d_counts);
+int32_t fpx_replica_inbox(fpx_ctx* ctx, int32_t n, const int32_t* kind, const int32_t* slot, const int32_t* value_id,
+                          const uint8_t* mask, int32_t* exec_count, int32_t* reply_slot, int32_t* order,
+                          int32_t counts[4], int32_t* executed_watermark, int32_t* num_chosen);
 /* log entries [first, first + count): value (-1 where absent) and present flag */
 int32_t fpx_replica_read_log(fpx_ctx* ctx, int32_t first, int32_t count, int32_t* values,
                              uint8_t* present);

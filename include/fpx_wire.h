@@ -50,6 +50,14 @@ enum {
   /* the acceptor's read path (multipaxos/Acceptor.scala:222-254) */
   FPX_WIRE_MAX_SLOT_REQUEST = 10,
   FPX_WIRE_BATCH_MAX_SLOT_REQUEST = 11,
+  /* the replica's read path (multipaxos/Replica.scala:455-529, 629-690): ReplicaInbound fields 2 - 7.  A ...BATCH is ONE
+   * message: its commands share one slot and one fate */
+  FPX_WIRE_READ_REQUEST = 12,
+  FPX_WIRE_SEQUENTIAL_READ_REQUEST = 13,
+  FPX_WIRE_EVENTUAL_READ_REQUEST = 14,
+  FPX_WIRE_READ_REQUEST_BATCH = 24,
+  FPX_WIRE_SEQUENTIAL_READ_REQUEST_BATCH = 25,
+  FPX_WIRE_EVENTUAL_READ_REQUEST_BATCH = 26,
   /* mencius/Mencius.proto */
   FPX_WIRE_PHASE2A_NOOP_RANGE = 6,
   FPX_WIRE_PHASE2B_NOOP_RANGE = 7,
@@ -63,6 +71,7 @@ enum {
   FPX_WIRE_EPX_PREPARE = 21,
   FPX_WIRE_EPX_PREPARE_OK = 22,
   FPX_WIRE_EPX_NACK = 23
+  /* 24 - 26: the replica's read batches, above */
 };
 
 /* Decodes n ProxyLeaderInbound messages: message i is buf[offsets[i] .. offsets[i + 1]); buf_len = the bytes buf
@@ -86,6 +95,18 @@ int32_t fpx_wire_decode_acceptor_inbound(const uint8_t* buf, int64_t buf_len, co
 int32_t fpx_wire_decode_replica_inbound(const uint8_t* buf, int64_t buf_len, const int64_t* offsets, int32_t n, int32_t* kind,
                                         int32_t* slot, int32_t* is_noop, int64_t* value_off, int32_t* value_len,
                                         int32_t* bad_index);
+
+/* Decodes n ReplicaInbound messages WITH the replica's read path (fields 1 - 7, MultiPaxos.proto:351-396, 566-575):
+ * kind CHOSEN (slot, is_noop, value_off / value_len as above; count -1) / READ_REQUEST, SEQUENTIAL_READ_REQUEST (slot =
+ * the request's slot; value_off / value_len = where the serialised Command lies; count 1) / EVENTUAL_READ_REQUEST (slot
+ * -1; the Command; count 1) / READ_REQUEST_BATCH, SEQUENTIAL_READ_REQUEST_BATCH, EVENTUAL_READ_REQUEST_BATCH (slot, -1
+ * for the eventual one; value_off / value_len = the whole inner message; count = its number of commands, 0 included) /
+ * OTHER.  Every Command is checked for its required fields (command_id with its three, command).  kind and slot are
+ * required, the other arrays may be NULL; the arrays feed fpx_replica_inbox.  Malformed input as in the other decoders.
+ * Host only. */
+int32_t fpx_wire_decode_replica_inbound_reads(const uint8_t* buf, int64_t buf_len, const int64_t* offsets, int32_t n,
+                                              int32_t* kind, int32_t* slot, int32_t* is_noop, int64_t* value_off,
+                                              int32_t* value_len, int32_t* count, int32_t* bad_index);
 
 /* The two decoders above ON THE DEVICE: the tick's bytes and its n + 1 offsets are device pointers (or page-locked host
  * memory the GPU can read), the outputs are device arrays of n elements, and the work is enqueued on the context's
