@@ -27,6 +27,7 @@
 #include "fpx_mencius_msgs.hpp"
 #include "fpx_replica_msgs.hpp"
 #include "fpx_replica_inbox.hpp"
+#include "fpx_acceptor_inbox.hpp"
 #include "fpx_wire_dev.hpp"
 #include "fpx_wire_enc_dev.hpp"
 #include "../../include/fpx_wire.h"
@@ -169,6 +170,11 @@ struct fpx_ctx {
   // maxima, the sort's counts and its two key / value buffers), and the host form's staged outputs (exec_count, reply_slot,
   // order, counts).  The claim words are rm_claim's.
   DevBuf ri_buf, ri_out[4];
+  // fpx_acceptor_inbox[_dev] (fpx_acceptor_inbox.hpp): the per-call scratch (header words, the tiles' maxima, the sort's
+  // counts and its two key / value buffers, the accepted slots and claim positions, the entries' new scalars), the claim
+  // table sized by the largest burst so far (cell numbers, all ones between calls; bids, -1 between calls), and the host
+  // form's staged replies
+  DevBuf ai_buf, ai_tkey, ai_tval, ai_out[2];
   // fpx_acceptor_phase1b_info_all[_dev] (fpx_phase1_info.hpp): the chunk counts, column totals and the go word; the host
   // form's offsets and totals
   DevBuf p1i, p1i_off, p1i_tot;
@@ -1041,7 +1047,8 @@ void free_state(fpx_ctx* ctx) {
                   &ctx->rm_claim, &ctx->rm_buf,   &ctx->mm_claim, &ctx->mm_end,   &ctx->mm_rec[0], &ctx->mm_rec[1],
                   &ctx->mm_rec[2], &ctx->mm_rec[3], &ctx->mm_rec[4],
                   &ctx->p1i,      &ctx->p1i_off, &ctx->p1i_tot, &ctx->p1m_buf, &ctx->p1m_tab,
-                  &ctx->ri_buf,   &ctx->ri_out[0], &ctx->ri_out[1], &ctx->ri_out[2], &ctx->ri_out[3]};
+                  &ctx->ri_buf,   &ctx->ri_out[0], &ctx->ri_out[1], &ctx->ri_out[2], &ctx->ri_out[3],
+                  &ctx->ai_buf,   &ctx->ai_tkey,  &ctx->ai_tval, &ctx->ai_out[0], &ctx->ai_out[1]};
   for (DevBuf* b : bs)
     if (b->p) (void)hipFree(b->p);
   for (DevBuf& b : ctx->p1m_stage)
@@ -3149,6 +3156,115 @@ int32_t fpx_replica_inbox(fpx_ctx* ctx, int32_t n, const int32_t* kind, const in
   }
   const int st = fpx_replica_state(ctx, executed_watermark, num_chosen);  // (synchronises the stream)
   return st ? st : rc;
+}
+
+// multipaxos.Acceptor's inbox for a burst of per-acceptor messages in delivery order (fpx_acceptor_inbox.hpp).  Nothing is
+// read by the host between the launches.
+static int32_t acceptor_inbox_ctx_ok(fpx_ctx* ctx, int32_t n, int32_t grid_cols) {
+  if (!ctx || n < 0 || n >= (1 << 30) || grid_cols < 0) return FPX_EINVAL;
+  if (ctx->g.per_slot || ctx->g.num_leader_groups != 1) return FPX_EINVAL;  // multipaxos.Acceptor: one round per acceptor
+  if (grid_cols > 0 && ctx->g.ngroups != 1) return FPX_EINVAL;             // a grid is ONE acceptor group
+  return FPX_OK;
+}
+
+int32_t fpx_acceptor_inbox_dev(fpx_ctx* ctx, int32_t n, const int32_t* d_kind, const int32_t* d_group_index,
+                               const int32_t* d_acceptor_index, const int32_t* d_slot, const int32_t* d_round,
+                               const int32_t* d_value_id, int32_t grid_cols, int32_t* d_reply_kind, int32_t* d_reply_value) {
+  // (the guard launches the fold of a fused step that is still pending: the burst reads promised and max_voted)
+  DeviceGuard _dg(ctx);
+  int rc;
+  if ((rc = acceptor_inbox_ctx_ok(ctx, n, grid_cols))) return rc;
+  if (n == 0) return FPX_OK;
+  if (!d_kind || !d_acceptor_index || !d_slot || !d_round || !d_value_id) return FPX_EINVAL;
+  flush_pending_fin(ctx);
+  const Geom& g = ctx->g;
+  const int E = g.ngroups * g.R;
+  const int nblk = (n + AI_TILE - 1) / AI_TILE;
+  const size_t cap_n = (size_t)nblk * AI_TILE;
+  // [hdr | tile (64-bit) | key x 2 | val x 2 | accslot | tpos | hist | fin_round | fin_slot]
+  const size_t words = (size_t)AI_HDR_WORDS + 2 * (size_t)nblk + 6 * cap_n + (size_t)RI_RADIX * nblk + 2 * (size_t)E;
+  size_t had = ctx->ai_buf.cap;
+  if ((rc = grow(ctx, &ctx->ai_buf, words * 4))) return rc;
+  ctx->bytes += (int64_t)ctx->ai_buf.cap - (int64_t)had;
+  size_t tsize = 1024;
+  while (tsize < 2 * (size_t)n) tsize <<= 1;
+  if (tsize * 8 > ctx->ai_tkey.cap) {  // a new table: every word at its between-calls value
+    had = ctx->ai_tkey.cap + ctx->ai_tval.cap;
+    if ((rc = grow(ctx, &ctx->ai_tkey, tsize * 8))) return rc;
+    if ((rc = grow(ctx, &ctx->ai_tval, tsize * 4))) return rc;
+    ctx->bytes += (int64_t)(ctx->ai_tkey.cap + ctx->ai_tval.cap) - (int64_t)had;
+    fill32(ctx, ctx->ai_tkey.p, -1, ctx->ai_tkey.cap / 4);
+    fill32(ctx, ctx->ai_tval.p, -1, ctx->ai_tval.cap / 4);
+  }
+  AcceptorInbox b;
+  memset(&b, 0, sizeof(b));
+  b.n = n, b.E = E, b.grid_cols = grid_cols;
+  b.kind = d_kind, b.group = d_group_index, b.acceptor = d_acceptor_index, b.slot = d_slot, b.round = d_round;
+  b.value = d_value_id;
+  b.hdr = (int32_t*)ctx->ai_buf.p;
+  b.tile = (long long*)(b.hdr + AI_HDR_WORDS);
+  int32_t* key[2];
+  int32_t* val[2];
+  key[0] = (int32_t*)(b.tile + nblk), key[1] = key[0] + cap_n, val[0] = key[1] + cap_n, val[1] = val[0] + cap_n;
+  b.accslot = val[1] + cap_n, b.tpos = b.accslot + cap_n;
+  int32_t* hist = b.tpos + cap_n;
+  b.fin_round = hist + (size_t)RI_RADIX * nblk, b.fin_slot = b.fin_round + E;
+  b.tkey = (unsigned long long*)ctx->ai_tkey.p, b.tval = (int32_t*)ctx->ai_tval.p, b.tmask = (uint32_t)(tsize - 1);
+  b.reply_kind = d_reply_kind, b.reply_value = d_reply_value;
+  const dim3 per_tile(nblk), blk(256);
+  const int sweep = std::max(1, std::min(nblk, ctx->num_cus * 8));
+  hipLaunchKernelGGL(k_ai_keys, per_tile, blk, 0, ctx->stream, g, ctx->st, b, key[0], val[0]);
+  // keys are 0 .. E: the pass count is fixed per context
+  int bits = 0;
+  while (E >> bits) ++bits;
+  const int passes = (bits + RI_RADIX_BITS - 1) / RI_RADIX_BITS;
+  for (int p = 0; p < passes; ++p) {
+    RiSort a;
+    a.hdr = b.hdr, a.hist = hist, a.shift = p * RI_RADIX_BITS;
+    a.key_in = key[p & 1], a.val_in = val[p & 1];
+    a.key_out = key[(p + 1) & 1], a.val_out = val[(p + 1) & 1];
+    hipLaunchKernelGGL(k_ri_hist, per_tile, blk, 0, ctx->stream, a);
+    hipLaunchKernelGGL(k_ai_hscan, dim3(1), dim3(1024), 0, ctx->stream, a);
+    hipLaunchKernelGGL(k_ri_scatter, per_tile, blk, 0, ctx->stream, a);
+  }
+  b.key = key[passes & 1], b.perm = val[passes & 1];
+  hipLaunchKernelGGL(k_ai_tilemax<0>, dim3(sweep), blk, 0, ctx->stream, b);
+  hipLaunchKernelGGL(k_ai_tilescan, dim3(1), dim3(AI_SCAN_THREADS), 0, ctx->stream, ctx->st, b);
+  hipLaunchKernelGGL(k_ai_accept, per_tile, blk, 0, ctx->stream, g, ctx->st, b);
+  hipLaunchKernelGGL(k_ai_tilemax<1>, dim3(sweep), blk, 0, ctx->stream, b);
+  hipLaunchKernelGGL(k_ai_tilescan, dim3(1), dim3(AI_SCAN_THREADS), 0, ctx->stream, ctx->st, b);
+  hipLaunchKernelGGL(k_ai_reads, per_tile, blk, 0, ctx->stream, g, ctx->st, b);
+  hipLaunchKernelGGL(k_ai_finish, per_tile, blk, 0, ctx->stream, ctx->st, b);
+  return launch_check(ctx);
+}
+
+// the host form: ONE run through the staging driver (no run contract applies, so there is nothing to cut); the replies
+// come down only when the burst was applied
+int32_t fpx_acceptor_inbox(fpx_ctx* ctx, int32_t n, const int32_t* kind, const int32_t* group_index,
+                           const int32_t* acceptor_index, const int32_t* slot, const int32_t* round, const int32_t* value_id,
+                           int32_t grid_cols, int32_t* reply_kind, int32_t* reply_value) {
+  DeviceGuard _dg(ctx);
+  int rc;
+  if ((rc = acceptor_inbox_ctx_ok(ctx, n, grid_cols))) return rc;
+  if (n == 0) return FPX_OK;
+  if (!kind || !acceptor_index || !slot || !round || !value_id) return FPX_EINVAL;
+  for (int a = 0; a < 2; ++a)
+    if ((rc = grow(ctx, &ctx->ai_out[a], (size_t)n * 4))) return rc;
+  rc = host_batch(ctx, n,
+                  {{&ctx->d_i32_a, kind, 4}, {&ctx->d_target, group_index, 4}, {&ctx->d_i32_c, acceptor_index, 4},
+                   {&ctx->d_slot, slot, 4}, {&ctx->d_round, round, 4}, {&ctx->d_value, value_id, 4}},
+                  {}, nullptr, [&](int, int) {
+                    return fpx_acceptor_inbox_dev(
+                        ctx, n, (const int32_t*)ctx->d_i32_a.p, group_index ? (const int32_t*)ctx->d_target.p : nullptr,
+                        (const int32_t*)ctx->d_i32_c.p, (const int32_t*)ctx->d_slot.p, (const int32_t*)ctx->d_round.p,
+                        (const int32_t*)ctx->d_value.p, grid_cols, reply_kind ? (int32_t*)ctx->ai_out[0].p : nullptr,
+                        reply_value ? (int32_t*)ctx->ai_out[1].p : nullptr);
+                  });
+  if (rc != FPX_OK) return rc;
+  if (reply_kind) HIPCHK(ctx, hipMemcpyAsync(reply_kind, ctx->ai_out[0].p, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
+  if (reply_value) HIPCHK(ctx, hipMemcpyAsync(reply_value, ctx->ai_out[1].p, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  return FPX_OK;
 }
 
 int32_t fpx_replica_read_log(fpx_ctx* ctx, int32_t first, int32_t count, int32_t* values, uint8_t* present) {

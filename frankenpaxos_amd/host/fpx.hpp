@@ -347,6 +347,31 @@ class Phase2Engine {
     return out;
   }
 
+  // ---- the acceptors' inbox (Acceptor.receive, Acceptor.scala:122-254) for a burst of per-acceptor messages in delivery
+  // order, the kinds interleaved, in one device call and exactly as if every acceptor had handled its messages one by one
+  // (fpx_acceptor_inbox).  kind = FPX_WIRE_PHASE2A (slot, round, value) / FPX_WIRE_PHASE1A (round) /
+  // FPX_WIRE_MAX_SLOT_REQUEST / FPX_WIRE_BATCH_MAX_SLOT_REQUEST; (groupIndex, acceptorIndex) = who received it.
+  struct AcceptorInbound { int32_t kind, groupIndex, acceptorIndex, slot, round, value; };
+  // kind = 0 (skipped) / FPX_WIRE_PHASE2B / FPX_WIRE_NACK / FPX_WIRE_PHASE1B / FPX_WIRE_MAX_SLOT_REQUEST; value = the Nack's
+  // round (it goes to leader roundsystem.leader(message.round), :197), the vote's or promise's round, the read's
+  // maxVotedSlot.  A Phase1b's info is not produced: end the burst at the Phase1a and ask acceptorsHandlePhase1aAll /
+  // fpx_acceptor_phase1b_info_all for the promisers.
+  struct AcceptorReply { int32_t kind, value; };
+  std::vector<AcceptorReply> acceptorsHandleInbox(const std::vector<AcceptorInbound>& msgs) {
+    const int32_t n = (int32_t)msgs.size();
+    std::vector<int32_t> kind(n), group(n), acceptor(n), slot(n), round(n), value(n), rk(n), rv(n);
+    for (int32_t i = 0; i < n; ++i) {
+      kind[i] = msgs[i].kind, group[i] = msgs[i].groupIndex, acceptor[i] = msgs[i].acceptorIndex;
+      slot[i] = msgs[i].slot, round[i] = msgs[i].round, value[i] = msgs[i].value;
+    }
+    check(fpx_acceptor_inbox(ctx_, n, kind.data(), group.data(), acceptor.data(), slot.data(), round.data(), value.data(),
+                             config_.flexible ? config_.acceptorsPerGroup : 0, rk.data(), rv.data()),
+          "Acceptor.receive");
+    std::vector<AcceptorReply> out(n);
+    for (int32_t i = 0; i < n; ++i) out[i] = AcceptorReply{rk[i], rv[i]};
+    return out;
+  }
+
   // ---- a Leader's Phase1a at EVERY acceptor it addresses, one call (fpx_acceptor_phase1): acceptors[g] = the acceptor
   // indices of group g the Phase1a goes to (an empty outer vector => everybody).  Returns per entry
   // g * numReplicas + acceptor the Phase1b.info of the acceptors that promised (votes in slots >= chosenWatermark,

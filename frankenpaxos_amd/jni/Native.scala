@@ -16,6 +16,10 @@
 //     is what the unchanged Leader.handlePhase1b (Leader.scala:504-577) needs to recover and re-propose; and the
 //     read path -- MaxSlotRequest / BatchMaxSlotRequest are answered with Acceptor.maxVotedSlot (Acceptor.scala:
 //     222-254), which the engine follows per acceptor (GpuPhase2Engine.maxVotedSlot).
+//     Among the reference's own ProxyLeader actors -- GPU acceptors, everything else the reference's -- every Phase2a
+//     arrives once per acceptor address (ProxyLeader.scala:190-215): `receive` only ENQUEUES, and one tick hands the
+//     whole burst, Phase2as, Phase1as and reads interleaved, to ONE native call (fpx_acceptor_inbox;
+//     GpuPhase2Engine.flushInbox).
 package frankenpaxos.gpu
 
 import frankenpaxos.Actor
@@ -32,6 +36,9 @@ object Native {
   val OK = 0; val EINVAL = 1; val EFATAL_UNKNOWN_SLOTROUND = 2
   // message kinds of include/fpx_wire.h (the `kind` arrays of proxyPhase2bMsgs / menciusProxyPhase2bMsgs)
   val WIRE_PHASE2B = 2; val WIRE_PHASE2B_NOOP_RANGE = 7
+  // ... and of acceptorInbox's kind / replyKind
+  val WIRE_OTHER = 0; val WIRE_PHASE2A = 1; val WIRE_PHASE1A = 3; val WIRE_NACK = 5; val WIRE_PHASE1B = 9
+  val WIRE_MAX_SLOT_REQUEST = 10; val WIRE_BATCH_MAX_SLOT_REQUEST = 11
 
   @native def create(cfg: Array[Int]): Long // < 0: -status
   @native def destroy(handle: Long): Int
@@ -49,6 +56,15 @@ object Native {
   @native def proxyPhase2bMsgs(handle: Long, n: Int, kind: Array[Int], groupIndex: Array[Int],
                                acceptorIndex: Array[Int], slot: Array[Int], round: Array[Int], gridCols: Int,
                                newlyChosen: Array[Byte], chosenRound: Array[Int], chosenValue: Array[Int]): Int
+  // multipaxos.Acceptor's inbox for a burst of per-acceptor messages in delivery order, the kinds interleaved
+  // (fpx_acceptor_inbox; Acceptor.scala:148-254): kind = WIRE_PHASE2A / WIRE_PHASE1A / WIRE_MAX_SLOT_REQUEST /
+  // WIRE_BATCH_MAX_SLOT_REQUEST / WIRE_OTHER (skipped); (groupIndex, acceptorIndex) = who received message i, local to the
+  // context (groupIndex null = 0; gridCols as in proxyPhase2bMsgs).  replyKind: 0 / WIRE_PHASE2B / WIRE_NACK /
+  // WIRE_PHASE1B / WIRE_MAX_SLOT_REQUEST; replyValue: the Nack's round, the vote's or promise's round, the read's
+  // maxVotedSlot (a ROW of the window here: GpuPhase2Engine keeps slots itself).  Phase1b.info is not produced
+  @native def acceptorInbox(handle: Long, n: Int, kind: Array[Int], groupIndex: Array[Int], acceptorIndex: Array[Int],
+                            slot: Array[Int], round: Array[Int], value: Array[Int], gridCols: Int,
+                            replyKind: Array[Int], replyValue: Array[Int]): Int
   // mencius.ProxyLeader.handlePhase2aNoopRange bookkeeping for n ranges in one call (fpx_proxy_open_noop_ranges)
   @native def proxyOpenNoopRanges(handle: Long, n: Int, slotStart: Array[Int], slotEnd: Array[Int],
                                   round: Array[Int], isNew: Array[Byte]): Int
@@ -531,6 +547,12 @@ class GpuPhase2Engine[Transport <: frankenpaxos.Transport[Transport]](
       return Left(Nack(round = Native.acceptorRound(handle, g, a)))
     }
     // :163-181  Phase1b(info = votes in slots >= chosenWatermark, ascending)
+    Right(Phase1b(groupIndex = groupIndex, acceptorIndex = index, round = phase1a.round,
+                  info = phase1bInfo(g, a, phase1a.chosenWatermark)))
+  }
+
+  // Phase1b.info of one acceptor: its votes in slots >= chosenWatermark, ascending (Acceptor.scala:167-180)
+  private def phase1bInfo(g: Int, a: Int, chosenWatermark: Int): Seq[Phase1bSlotInfo] = {
     var cap = 1024
     var slots = new Array[Int](cap); var vr = new Array[Int](cap); var vv = new Array[Int](cap)
     var k = Native.acceptorPhase1bInfo(handle, g, a, 0, cap, slots, vr, vv)
@@ -539,39 +561,16 @@ class GpuPhase2Engine[Transport <: frankenpaxos.Transport[Transport]](
       k = Native.acceptorPhase1bInfo(handle, g, a, 0, cap, slots, vr, vv)
     }
     if (k < 0) Native.check(-k, logger)
-    val info = (0 until k)
+    (0 until k)
       .map(j => Phase1bSlotInfo(slot = slotOfRow(slots(j)), voteRound = vr(j), voteValue = valueOf(vv(j))))
-      .filter(_.slot >= phase1a.chosenWatermark)
+      .filter(_.slot >= chosenWatermark)
       .sortBy(_.slot)
-    Right(Phase1b(groupIndex = groupIndex, acceptorIndex = index, round = phase1a.round, info = info))
   }
 
-  // ---- Phase 1 for a burst of Phase1as: a new leader sends one to every acceptor address, and they arrive together.
-  // The GpuAcceptors enqueue them here; the zero-delay timer of the first one flushes the burst: maximal runs of equal
-  // (round, chosenWatermark), ONE native call per run (fpx_acceptor_phase1: the round movement of every addressed group,
-  // then the Phase1b.info of exactly the promisers, compacted on the device), each acceptor answered from its slice.
-  // As in handlePhase1a the call runs with watermark row 0; the per-slot filter and slotOfRow stay here.
-  private val pendingPhase1as = mutable.Buffer[(Int, Int, Phase1a, Either[Nack, Phase1b] => Unit)]()
-
-  // true: the queue was empty -- the caller starts its tick
-  def enqueuePhase1a(groupIndex: Int, index: Int, phase1a: Phase1a, reply: Either[Nack, Phase1b] => Unit): Boolean = {
-    val first = pendingPhase1as.isEmpty
-    pendingPhase1as += ((groupIndex, index, phase1a, reply))
-    first
-  }
-
-  def flushPhase1as(): Unit = {
-    var rest = pendingPhase1as.toList
-    pendingPhase1as.clear()
-    while (rest.nonEmpty) {
-      val key = (rest.head._3.round, rest.head._3.chosenWatermark)
-      val (run, later) = rest.span(m => (m._3.round, m._3.chosenWatermark) == key)
-      rest = later
-      if (run.size == 1) run.head._4(handlePhase1a(run.head._1, run.head._2, run.head._3))   // a lone message
-      else phase1Run(run)
-    }
-  }
-
+  // ---- Phase 1 for a run of Phase1as of ONE round: a new leader sends one to every acceptor address, and they arrive
+  // together (inboxBurst below hands them over).  ONE native call per run (fpx_acceptor_phase1: the round movement of every
+  // addressed group, then the Phase1b.info of exactly the promisers, compacted on the device), each acceptor answered from
+  // its slice.  As in handlePhase1a the call runs with watermark row 0; the per-slot filter and slotOfRow stay here.
   private def phase1Run(run: List[(Int, Int, Phase1a, Either[Nack, Phase1b] => Unit)]): Unit = {
     val phase1a = run.head._3
     val words = 4 * ctxGroups
@@ -606,8 +605,106 @@ class GpuPhase2Engine[Transport <: frankenpaxos.Transport[Transport]](
     }
   }
 
-  // a Phase2a sent straight to one acceptor (not how the reference's Leader sends them, but part of
-  // AcceptorInbound): Acceptor.handlePhase2a, multipaxos/Acceptor.scala:184-220
+  // ---- the acceptors' inbox as a burst (fpx_acceptor_inbox).  Among reference proxy leaders every Phase2a arrives once per
+  // acceptor address, f + 1 times per slot (ProxyLeader.scala:190-215), with the clients' and read batchers' reads and now
+  // and then a leader's Phase1as between them.  The GpuAcceptors enqueue whatever they receive here; the zero-delay timer
+  // of the first message flushes the queue: ONE native call per burst, every acceptor answered from its message's reply,
+  // exactly as if each had handled its messages one by one.  The call does not produce Phase1b.info -- a promise's info is
+  // the acceptor's votes as of that message -- so a burst is cut after each maximal run of Phase1as, and the promisers of
+  // that run get their info from acceptorPhase1All's slices (no vote lies between the promise and the end of the burst).
+  sealed trait InboxReply
+  case class Voted(phase2b: Phase2b) extends InboxReply
+  case class Nacked(nack: Nack) extends InboxReply
+  case class Promised(phase1b: Phase1b) extends InboxReply
+  case class MaxVotedSlot(slot: Int) extends InboxReply
+  private case class InboxMsg(groupIndex: Int, index: Int, request: AcceptorInbound.Request, reply: InboxReply => Unit) {
+    def isPhase1a: Boolean = request.isPhase1A
+  }
+  private val pendingInbox = mutable.Buffer[InboxMsg]()
+
+  // true: the queue was empty -- the caller starts its tick
+  def enqueueInbox(groupIndex: Int, index: Int, request: AcceptorInbound.Request, reply: InboxReply => Unit): Boolean = {
+    val first = pendingInbox.isEmpty
+    pendingInbox += InboxMsg(groupIndex, index, request, reply)
+    first
+  }
+
+  def flushInbox(): Unit = {
+    var rest = pendingInbox.toList
+    pendingInbox.clear()
+    while (rest.nonEmpty) {
+      val (head, tail) = rest.span(!_.isPhase1a)
+      val (phase1as, later) = tail.span(_.isPhase1a)
+      rest = later
+      val burst = head ++ phase1as
+      if (burst.size == 1) loneInboxMsg(burst.head) else inboxBurst(burst, head.size)
+    }
+  }
+
+  private def loneInboxMsg(m: InboxMsg): Unit = m.request match {
+    case AcceptorInbound.Request.Phase2A(p) =>
+      m.reply(handlePhase2a(m.groupIndex, m.index, p).fold(Nacked(_), Voted(_)))
+    case AcceptorInbound.Request.Phase1A(p) =>
+      m.reply(handlePhase1a(m.groupIndex, m.index, p).fold(Nacked(_), Promised(_)))
+    case _ => m.reply(MaxVotedSlot(maxVotedSlot(m.groupIndex, m.index)))
+  }
+
+  // burst = any messages but Phase1as, then (from firstPhase1a on) a run of Phase1as
+  private def inboxBurst(burst: List[InboxMsg], firstPhase1a: Int): Unit = {
+    val n = burst.size
+    val kind = new Array[Int](n); val group = new Array[Int](n); val acc = new Array[Int](n)
+    val slot = Array.fill(n)(-1); val round = Array.fill(n)(-1); val value = Array.fill(n)(-1)
+    refreshStaleGroups()                                 // maxVoted is followed from the replies below: exact before the burst
+    for ((m, i) <- burst.zipWithIndex) {
+      // the context's addressing: a grid is ONE group of numGroups x perGroup, bit = groupIndex * perGroup + index
+      group(i) = m.groupIndex; acc(i) = m.index
+      m.request match {
+        case AcceptorInbound.Request.Phase2A(p) =>
+          logger.check(p.slot >= base && p.slot < base + numSlots)
+          kind(i) = Native.WIRE_PHASE2A; slot(i) = row(p.slot); round(i) = p.round
+          value(i) = intern(row(p.slot), p.commandBatchOrNoop)
+        case AcceptorInbound.Request.Phase1A(p) => kind(i) = Native.WIRE_PHASE1A; round(i) = p.round
+        case AcceptorInbound.Request.MaxSlotRequest(_) => kind(i) = Native.WIRE_MAX_SLOT_REQUEST
+        case AcceptorInbound.Request.BatchMaxSlotRequest(_) => kind(i) = Native.WIRE_BATCH_MAX_SLOT_REQUEST
+        case AcceptorInbound.Request.Empty => logger.fatal("Empty AcceptorInbound encountered.")
+      }
+    }
+    val replyKind = new Array[Int](n); val replyValue = new Array[Int](n)
+    val gridCols = if (config.flexible) perGroup else 0
+    Native.check(Native.acceptorInbox(handle, n, kind, group, acc, slot, round, value, gridCols, replyKind, replyValue),
+                 logger)
+    // everything but the promises, in delivery order.  Acceptor.maxVotedSlot in SLOTS is followed here, vote by vote (the
+    // device's scalar is over rows, and the lap query is for votes the engine did not see one by one)
+    for ((m, i) <- burst.zipWithIndex) {
+      val g = ctxGroup(m.groupIndex); val a = ctxReplica(m.groupIndex, m.index)
+      (m.request, replyKind(i)) match {
+        case (_, Native.WIRE_NACK) => m.reply(Nacked(Nack(round = replyValue(i))))          // Acceptor.scala:155-162, 192-199
+        case (AcceptorInbound.Request.Phase2A(p), _) =>                                     // Acceptor.scala:204-219
+          maxVoted(g)(a) = math.max(maxVoted(g)(a), p.slot)
+          m.reply(Voted(Phase2b(groupIndex = m.groupIndex, acceptorIndex = m.index, slot = p.slot, round = p.round)))
+        case (AcceptorInbound.Request.Phase1A(_), _) => ()                                  // below
+        case _ => m.reply(MaxVotedSlot(maxVoted(g)(a)))                                     // Acceptor.scala:222-254
+      }
+    }
+    // the promisers of the run of Phase1as.  An acceptor's round after the run is its last promise's; the promises of
+    // that round are fetched per round by acceptorPhase1All (promising an equal round again changes nothing, :155), an
+    // earlier promise of an acceptor that promised twice in one run by acceptorPhase1bInfo -- the votes are the same
+    val promisers = burst.zipWithIndex.drop(firstPhase1a).filter(mi => replyKind(mi._2) == Native.WIRE_PHASE1B).map(_._1)
+    val lastRound = mutable.Map[(Int, Int), Int]()
+    for (m <- promisers) lastRound((m.groupIndex, m.index)) = m.request.phase1A.get.round
+    val (current, earlier) = promisers.partition(m => lastRound((m.groupIndex, m.index)) == m.request.phase1A.get.round)
+    for ((_, run) <- current.groupBy(_.request.phase1A.get.round).toSeq.sortBy(_._1))
+      phase1Run(run.map(m => (m.groupIndex, m.index, m.request.phase1A.get, (r: Either[Nack, Phase1b]) =>
+        m.reply(r.fold(Nacked(_), Promised(_))))))
+    for (m <- earlier) {
+      val p = m.request.phase1A.get
+      m.reply(Promised(Phase1b(groupIndex = m.groupIndex, acceptorIndex = m.index, round = p.round,
+                               info = phase1bInfo(ctxGroup(m.groupIndex), ctxReplica(m.groupIndex, m.index), p.chosenWatermark))))
+    }
+  }
+
+  // ONE Phase2a at one acceptor, for a message that arrives alone (a burst goes through inboxBurst):
+  // Acceptor.handlePhase2a, multipaxos/Acceptor.scala:184-220
   def handlePhase2a(groupIndex: Int, index: Int, p: Phase2a): Either[Nack, Phase2b] = {
     logger.check(p.slot >= base && p.slot < base + numSlots)
     val a = ctxReplica(groupIndex, index)
@@ -859,41 +956,49 @@ class GpuAcceptor[Transport <: frankenpaxos.Transport[Transport]](
   private val groupIndex = config.acceptorAddresses.indexWhere(_.contains(address))
   private val index = config.acceptorAddresses(groupIndex).indexOf(address)
   private val roundSystem = new RoundSystem.ClassicRoundRobin(config.numLeaders)
-  // one tick, as GpuProxyLeader's: "after the messages already queued on the event loop" -- the Phase1as of a burst
-  private val phase1Tick = timer("gpuPhase1Tick", java.time.Duration.ZERO, () => engine.flushPhase1as())
+  // one tick, as GpuProxyLeader's: "after the messages already queued on the event loop" -- the burst that the proxy
+  // leaders, leaders, clients and read batchers sent to the acceptor addresses of this engine
+  private val inboxTick = timer("gpuAcceptorInboxTick", java.time.Duration.ZERO, () => engine.flushInbox())
 
   override def receive(src: Transport#Address, inbound: AcceptorInbound): Unit = {
-    inbound.request match {
-      case AcceptorInbound.Request.Phase1A(phase1a) =>
-        // enqueued, not answered: the burst a new leader sends is flushed by one tick (engine.flushPhase1as)
+    // enqueued, not answered: one tick flushes the burst through ONE native call (engine.flushInbox)
+    val reply: engine.InboxReply => Unit = inbound.request match {
+      case AcceptorInbound.Request.Phase1A(_) =>
         val leader = chan[Leader[Transport]](src, Leader.serializer)
-        val reply: Either[Nack, Phase1b] => Unit = {
-          case Left(nack)     => leader.send(LeaderInbound().withNack(nack))        // Acceptor.scala:155-162
-          case Right(phase1b) => leader.send(LeaderInbound().withPhase1B(phase1b))  // Acceptor.scala:163-181
-        }
-        if (engine.enqueuePhase1a(groupIndex, index, phase1a, reply)) phase1Tick.start()
+        ({
+          case engine.Nacked(nack)      => leader.send(LeaderInbound().withNack(nack))        // Acceptor.scala:155-162
+          case engine.Promised(phase1b) => leader.send(LeaderInbound().withPhase1B(phase1b))  // Acceptor.scala:163-181
+          case other                    => logger.fatal(s"Phase1a answered with $other")
+        })
       case AcceptorInbound.Request.Phase2A(phase2a) =>
-        engine.handlePhase2a(groupIndex, index, phase2a) match {
-          case Left(nack) =>                                                          // Acceptor.scala:192-199
-            val leader = chan[Leader[Transport]](config.leaderAddresses(roundSystem.leader(phase2a.round)),
-                                                 Leader.serializer)
-            leader.send(LeaderInbound().withNack(nack))
-          case Right(phase2b) =>                                                      // Acceptor.scala:211-219
-            chan[ProxyLeader[Transport]](src, ProxyLeader.serializer)
-              .send(ProxyLeaderInbound().withPhase2B(phase2b))
-        }
-      case AcceptorInbound.Request.MaxSlotRequest(r) =>                               // Acceptor.scala:222-237
-        chan[Client[Transport]](src, Client.serializer).send(
-          ClientInbound().withMaxSlotReply(
-            MaxSlotReply(commandId = r.commandId, groupIndex = groupIndex, acceptorIndex = index,
-                         slot = engine.maxVotedSlot(groupIndex, index))))
-      case AcceptorInbound.Request.BatchMaxSlotRequest(r) =>                          // Acceptor.scala:239-254
-        chan[ReadBatcher[Transport]](src, ReadBatcher.serializer).send(
-          ReadBatcherInbound().withBatchMaxSlotReply(
-            BatchMaxSlotReply(readBatcherIndex = r.readBatcherIndex, readBatcherId = r.readBatcherId,
-                              acceptorIndex = index, slot = engine.maxVotedSlot(groupIndex, index))))
+        ({
+          case engine.Nacked(nack) =>                                                         // Acceptor.scala:192-199
+            chan[Leader[Transport]](config.leaderAddresses(roundSystem.leader(phase2a.round)), Leader.serializer)
+              .send(LeaderInbound().withNack(nack))
+          case engine.Voted(phase2b) =>                                                       // Acceptor.scala:211-219
+            chan[ProxyLeader[Transport]](src, ProxyLeader.serializer).send(ProxyLeaderInbound().withPhase2B(phase2b))
+          case other => logger.fatal(s"Phase2a answered with $other")
+        })
+      case AcceptorInbound.Request.MaxSlotRequest(r) =>                                       // Acceptor.scala:222-237
+        ({
+          case engine.MaxVotedSlot(slot) =>
+            chan[Client[Transport]](src, Client.serializer).send(
+              ClientInbound().withMaxSlotReply(
+                MaxSlotReply(commandId = r.commandId, groupIndex = groupIndex, acceptorIndex = index, slot = slot)))
+          case other => logger.fatal(s"MaxSlotRequest answered with $other")
+        })
+      case AcceptorInbound.Request.BatchMaxSlotRequest(r) =>                                  // Acceptor.scala:239-254
+        ({
+          case engine.MaxVotedSlot(slot) =>
+            chan[ReadBatcher[Transport]](src, ReadBatcher.serializer).send(
+              ReadBatcherInbound().withBatchMaxSlotReply(
+                BatchMaxSlotReply(readBatcherIndex = r.readBatcherIndex, readBatcherId = r.readBatcherId,
+                                  acceptorIndex = index, slot = slot)))
+          case other => logger.fatal(s"BatchMaxSlotRequest answered with $other")
+        })
       case AcceptorInbound.Request.Empty =>
         logger.fatal("Empty AcceptorInbound encountered.")
     }
+    if (engine.enqueueInbox(groupIndex, index, inbound.request, reply)) inboxTick.start()
   }
 }

@@ -184,6 +184,30 @@ JNIEXPORT jint JNICALL Java_frankenpaxos_gpu_Native_proxyPhase2bMsgs(JNIEnv* env
   return st;
 }
 
+/* multipaxos.Acceptor's inbox for a burst of per-acceptor messages in delivery order: multipaxos/Acceptor.scala:148-254
+ * (fpx_acceptor_inbox).  kind as fpx_wire.h numbers it; groupIndex, replyKind and replyValue may be null.  On an error the
+ * output arrays are left as they were. */
+JNIEXPORT jint JNICALL Java_frankenpaxos_gpu_Native_acceptorInbox(JNIEnv* env, jclass cls, jlong h, jint n, jintArray kind,
+                                                                  jintArray groupIndex, jintArray acceptorIndex,
+                                                                  jintArray slot, jintArray round, jintArray value,
+                                                                  jint gridCols, jintArray replyKind,
+                                                                  jintArray replyValue) {
+  if (n < 0) return FPX_EINVAL;
+  if (n == 0) return fpx_acceptor_inbox(CTX(h), 0, NULL, NULL, NULL, NULL, NULL, NULL, gridCols, NULL, NULL);
+  if (!has(env, kind, n) || !opt(env, groupIndex, n) || !has(env, acceptorIndex, n) || !has(env, slot, n) ||
+      !has(env, round, n) || !has(env, value, n) || !opt(env, replyKind, n) || !opt(env, replyValue, n))
+    return FPX_EINVAL;
+  jint *k = in_ints(env, kind, n), *g = in_ints(env, groupIndex, n), *a = in_ints(env, acceptorIndex, n);
+  jint *s = in_ints(env, slot, n), *r = in_ints(env, round, n), *v = in_ints(env, value, n);
+  jint *rk = out_buf(replyKind, n, sizeof(jint)), *rv = out_buf(replyValue, n, sizeof(jint));
+  int32_t st = FPX_ENOMEM;
+  if (k && a && s && r && v && (g || !groupIndex) && (rk || !replyKind) && (rv || !replyValue))
+    st = fpx_acceptor_inbox(CTX(h), n, k, g, a, s, r, v, gridCols, rk, rv);
+  if (st == FPX_OK) put_ints(env, replyKind, n, rk), put_ints(env, replyValue, n, rv);
+  free(k); free(g); free(a); free(s); free(r); free(v); free(rk); free(rv);
+  return st;
+}
+
 /* mencius.ProxyLeader.handlePhase2aNoopRange bookkeeping for n ranges (mencius/ProxyLeader.scala:255-303):
  * fpx_proxy_open_noop_ranges */
 JNIEXPORT jint JNICALL Java_frankenpaxos_gpu_Native_proxyOpenNoopRanges(JNIEnv* env, jclass cls, jlong h, jint n,

@@ -978,6 +978,58 @@ int32_t fpx_replica_inbox_dev(fpx_ctx* ctx, int32_t n, const int32_t* d_kind, co
 int32_t fpx_replica_inbox(fpx_ctx* ctx, int32_t n, const int32_t* kind, const int32_t* slot, const int32_t* value_id,
                           const uint8_t* mask, int32_t* exec_count, int32_t* reply_slot, int32_t* order,
                           int32_t counts[4], int32_t* executed_watermark, int32_t* num_chosen);
+/* multipaxos.Acceptor's inbox (multipaxos/Acceptor.scala:122-254): handlePhase1a (:148-182), handlePhase2a (:184-220),
+ * handleMaxSlotRequest (:222-237) and handleBatchMaxSlotRequest (:239-254) for a BURST of n AcceptorInbound messages in
+ * delivery order, the kinds interleaved and addressed to any of the context's acceptors -- what a reference ProxyLeader
+ * (one Phase2a per acceptor address, to f + 1 of them, multipaxos/ProxyLeader.scala:190-215), Leader, Client and
+ * ReadBatcher send.  The mirror image of fpx_proxy_phase2b_msgs: NO run contract applies -- a slot may come any number of
+ * times, rounds may go up and down.  The arrays are what fpx_wire_decode_acceptor_inbound[_dev] produces, plus who
+ * received each message:
+ *   kind[i] (fpx_wire.h): FPX_WIRE_PHASE2A (slot, round, value_id) / FPX_WIRE_PHASE1A (round) / FPX_WIRE_MAX_SLOT_REQUEST /
+ *     FPX_WIRE_BATCH_MAX_SLOT_REQUEST (slot, round and value_id are not read: the decoder keeps other fields there);
+ *     FPX_WIRE_OTHER is skipped (none of its fields is read).
+ *   group_index[i] (NULL = 0), acceptor_index[i]: the acceptor the message was delivered to, LOCAL to the context:
+ *     grid_cols == 0: acceptor acceptor_index (0 .. num_replicas - 1) of acceptor group group_index (0 .. num_groups - 1);
+ *     grid_cols > 0: acceptor group_index * grid_cols + acceptor_index of the context's one group, as in
+ *     fpx_proxy_phase2b_msgs.
+ * The result is EXACTLY that of every acceptor handling its messages one by one in index order.  For acceptor e:
+ *   Phase2a / Phase1a with round[i] < e.round: Nack(e.round) (:155, :192 -- `<`: an equal round is accepted again).
+ *   otherwise e.round := round[i]; a Phase2a stores (round[i], value_id[i]) in cell (slot[i], e) and raises maxVotedSlot
+ *     (:204-209).  The cell keeps the LAST accepted Phase2a of (e, slot) in the burst, an equal round sent again with
+ *     another value included.
+ *   MaxSlotRequest / BatchMaxSlotRequest: answered with e.maxVotedSlot as it stands at that message (:233, :250).
+ * reply_kind[i]: 0 = no reply (skipped), FPX_WIRE_PHASE2B = voted, FPX_WIRE_NACK, FPX_WIRE_PHASE1B = promised,
+ * FPX_WIRE_MAX_SLOT_REQUEST = answered.  reply_value[i]: a Nack's round (the acceptor's, at that moment); a vote's or a
+ * promise's round (the message's); a read's maxVotedSlot; -1 with no reply.  A Nack goes to
+ * fpx_round_leader(num_leaders, round[i]) (:197), which stays with the caller.  Either output may be NULL.
+ * Afterwards the acceptors' rounds, maxVotedSlots and vote cells (fpx_read_scalars, fpx_read_state, fpx_state_digest) are
+ * what the message-at-a-time route (fpx_acceptor_phase2a / fpx_acceptor_phase1a with single-bit masks) leaves, and so is
+ * what the vote kernels keep about fresh rows.
+ * Phase1b.info is NOT produced: the call moves rounds and reports promise or Nack.  A promise's info is the acceptor's
+ * votes as of that message (:167-180), so a caller that needs it ends its burst at that Phase1a and calls
+ * fpx_acceptor_phase1b_info_all[_dev] for the promisers (jni/Native.scala's GpuAcceptor does).  A Phase1a in the middle
+ * of a burst is still handled correctly for every later message.
+ * FPX_BALLOT_ACCEPTOR contexts with num_leader_groups == 1 only; with grid_cols > 0, num_groups == 1: anything else, a
+ * NULL context, n < 0 or n >= 2^30, grid_cols < 0, or a NULL kind / acceptor_index / slot / round / value_id with n > 0
+ * is FPX_EINVAL at once, nothing enqueued.  n == 0 is FPX_OK.
+ * _dev: device pointers (arrays of n), enqueued on the context's stream behind the fold of an earlier fused step
+ * (fpx_deferred_folds); nothing is read by the host between its passes (csrc/fpx_acceptor_inbox.hpp: a stable radix
+ * sort by acceptor, two device-wide running maxima, a claim table sized by the burst; integer atomics only, results are
+ * reproducible).  A kind other than the five above, an index that names no acceptor of the context, and for a
+ * Phase2a / Phase1a a round outside 0 .. 2^30 - 2, for a Phase2a a slot outside [0, num_slots) or of another acceptor
+ * group than the message's, are found on the device before anything is applied: FPX_EINVAL at fpx_sync, the LOWEST
+ * offending index in fpx_error_detail, state untouched, no output written, and (the _dev convention) the context applies
+ * nothing up to that fpx_sync.  The scratch (about 40 B per message and a claim table of 12 B x the power of two at or
+ * above 2 n) lives in the context, is allocated on first use, grows with n and is counted by fpx_device_bytes.
+ * The host form takes host arrays, goes through the staging driver as a single run and is synchronous; on an error the
+ * output arrays are left untouched. */
+int32_t fpx_acceptor_inbox_dev(fpx_ctx* ctx, int32_t n, const int32_t* d_kind, const int32_t* d_group_index,
+                               const int32_t* d_acceptor_index, const int32_t* d_slot, const int32_t* d_round,
+                               const int32_t* d_value_id, int32_t grid_cols, int32_t* d_reply_kind,
+                               int32_t* d_reply_value);
+int32_t fpx_acceptor_inbox(fpx_ctx* ctx, int32_t n, const int32_t* kind, const int32_t* group_index,
+                           const int32_t* acceptor_index, const int32_t* slot, const int32_t* round,
+                           const int32_t* value_id, int32_t grid_cols, int32_t* reply_kind, int32_t* reply_value);
 /* log entries [first, first + count): value (-1 where absent) and present flag */
 int32_t fpx_replica_read_log(fpx_ctx* ctx, int32_t first, int32_t count, int32_t* values,
                              uint8_t* present);
