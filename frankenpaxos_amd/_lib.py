@@ -175,6 +175,8 @@ SIGNATURES = {
     "fpx_replica_inbox_dev": (C.c_int32, [VP, C.c_int32, VP, VP, VP, VP, VP, VP, VP, VP]),
     "fpx_acceptor_inbox": (C.c_int32, [VP, C.c_int32, VP, VP, VP, VP, VP, VP, C.c_int32, VP, VP]),
     "fpx_acceptor_inbox_dev": (C.c_int32, [VP, C.c_int32, VP, VP, VP, VP, VP, VP, C.c_int32, VP, VP]),
+    "fpx_mencius_acceptor_inbox": (C.c_int32, [VP, C.c_int32, VP, VP, VP, VP, VP, VP, VP, VP, VP]),
+    "fpx_mencius_acceptor_inbox_dev": (C.c_int32, [VP, C.c_int32, VP, VP, VP, VP, VP, VP, VP, VP, VP]),
     "fpx_replica_state": (C.c_int32, [VP, I32P, I32P]),
     "fpx_replica_chosen_noop_range": (C.c_int32, [VP, C.c_int32, C.c_int32, I32P, I32P]),
     "fpx_replica_read_log": (C.c_int32, [VP, C.c_int32, C.c_int32, VP, VP]),

@@ -256,6 +256,30 @@ class Context:
                                        _hp(value), grid_cols, _hp(rk), _hp(rv))
         return st, rk, rv
 
+    def mencius_acceptor_inbox(self, kind, acceptor_index, slot, slot_end, round_, value, group_index=None, replies=True):
+        """a burst of Mencius AcceptorInbound messages in delivery order (Phase2a, Phase2aNoopRange with slot = start and
+        slot_end = end, Phase1a), each delivered to acceptor acceptor_index of row group_index = leader_group * num_groups +
+        acceptor_group, exactly as mencius.Acceptor handles them one by one: (status, reply_kind, reply_value).
+        group_index None: 0; replies False: both outputs NULL (returned as None)"""
+        kind, acceptor_index, slot, slot_end = _i32(kind), _i32(acceptor_index), _i32(slot), _i32(slot_end)
+        round_, value, group_index = _i32(round_), _i32(value), _i32(group_index)
+        n = len(kind)
+        assert len(acceptor_index) == len(slot) == len(slot_end) == len(round_) == len(value) == n
+        rk = np.full(n, -9, np.int32) if replies else None
+        rv = np.full(n, -9, np.int32) if replies else None
+        st = self.L.fpx_mencius_acceptor_inbox(self._h, n, _hp(kind), _hp(group_index), _hp(acceptor_index), _hp(slot),
+                                               _hp(slot_end), _hp(round_), _hp(value), _hp(rk), _hp(rv))
+        return st, rk, rv
+
+    def mencius_acceptor_inbox_dev(self, kind, acceptor_index, slot, slot_end, round_, value, group_index=None,
+                                   reply_kind=None, reply_value=None, n=None):
+        """the same on device tensors (int32; either output may be None); errors surface at sync()"""
+        st = self.L.fpx_mencius_acceptor_inbox_dev(self._h, kind.numel() if n is None else n, _dp(kind), _dp(group_index),
+                                                   _dp(acceptor_index), _dp(slot), _dp(slot_end), _dp(round_), _dp(value),
+                                                   _dp(reply_kind), _dp(reply_value))
+        if st:
+            raise FpxError(st, "fpx_mencius_acceptor_inbox_dev")
+
     def mencius_proxy_phase2b_msgs(self, acceptor_index, slot, round_, kind=None, group_index=None, slot_end=None):
         """one Phase2b / Phase2bNoopRange per (acceptor, key) in delivery order (mencius/ProxyLeader.scala:305-411): = the
         burst folded into rows + proxy_phase2b / proxy_phase2b_noop_ranges, each row's outcome at the index of its first

@@ -156,14 +156,15 @@ __global__ void __launch_bounds__(1024) k_ai_hscan(const RiSort a) {
 }
 
 // what position p contributes to the running maximum: MODE 0 the round of a Phase1a / Phase2a, MODE 1 the slot of an
-// accepted Phase2a, each + 1 under the position's key (0 = nothing)
+// accepted Phase2a, each + 1 under the position's key (0 = nothing); MODE 2 is MODE 0 for a Mencius acceptor, whose
+// Phase2aNoopRanges move the round too (fpx_mencius_acceptor_inbox.hpp)
 template <int MODE>
 __device__ __forceinline__ long long ai_word(const AcceptorInbox& b, int p) {
   if (p >= b.n) return -1;
   int v;
-  if (MODE == 0) {
-    const int i = b.perm[p];
-    v = ai_moves_round(b.kind[i]) ? b.round[i] + 1 : 0;
+  if (MODE == 0 || MODE == 2) {
+    const int i = b.perm[p], k = b.kind[i];
+    v = ai_moves_round(k) || (MODE == 2 && k == FPX_WIRE_PHASE2A_NOOP_RANGE) ? b.round[i] + 1 : 0;
   } else {
     v = b.accslot[p];
   }

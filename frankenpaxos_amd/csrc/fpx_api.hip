@@ -28,6 +28,7 @@
 #include "fpx_replica_msgs.hpp"
 #include "fpx_replica_inbox.hpp"
 #include "fpx_acceptor_inbox.hpp"
+#include "fpx_mencius_acceptor_inbox.hpp"
 #include "fpx_wire_dev.hpp"
 #include "fpx_wire_enc_dev.hpp"
 #include "../../include/fpx_wire.h"
@@ -175,6 +176,9 @@ struct fpx_ctx {
   // table sized by the largest burst so far (cell numbers, all ones between calls; bids, -1 between calls), and the host
   // form's staged replies
   DevBuf ai_buf, ai_tkey, ai_tval, ai_out[2];
+  // fpx_mencius_acceptor_inbox[_dev] (fpx_mencius_acceptor_inbox.hpp): the per-call scratch (ai_buf's parts, the range
+  // flags, the tiles' range counts and the list of accepted ranges).  The claim table and the staged replies are ai_*'s.
+  DevBuf mai_buf;
   // fpx_acceptor_phase1b_info_all[_dev] (fpx_phase1_info.hpp): the chunk counts, column totals and the go word; the host
   // form's offsets and totals
   DevBuf p1i, p1i_off, p1i_tot;
@@ -1048,7 +1052,8 @@ void free_state(fpx_ctx* ctx) {
                   &ctx->mm_rec[2], &ctx->mm_rec[3], &ctx->mm_rec[4],
                   &ctx->p1i,      &ctx->p1i_off, &ctx->p1i_tot, &ctx->p1m_buf, &ctx->p1m_tab,
                   &ctx->ri_buf,   &ctx->ri_out[0], &ctx->ri_out[1], &ctx->ri_out[2], &ctx->ri_out[3],
-                  &ctx->ai_buf,   &ctx->ai_tkey,  &ctx->ai_tval, &ctx->ai_out[0], &ctx->ai_out[1]};
+                  &ctx->ai_buf,   &ctx->ai_tkey,  &ctx->ai_tval, &ctx->ai_out[0], &ctx->ai_out[1],
+                  &ctx->mai_buf};
   for (DevBuf* b : bs)
     if (b->p) (void)hipFree(b->p);
   for (DevBuf& b : ctx->p1m_stage)
@@ -3167,6 +3172,44 @@ static int32_t acceptor_inbox_ctx_ok(fpx_ctx* ctx, int32_t n, int32_t grid_cols)
   return FPX_OK;
 }
 
+// the claim table of the two inbox calls for a burst of n: open-addressed, the next power of two at or above 2 n words,
+// grown (and then every word set to its between-calls value) when the burst needs more than the context has
+static int32_t ai_claim_table(fpx_ctx* ctx, int32_t n, size_t* tsize_out) {
+  int rc;
+  size_t tsize = 1024;
+  while (tsize < 2 * (size_t)n) tsize <<= 1;
+  if (tsize * 8 > ctx->ai_tkey.cap) {  // a new table: every word at its between-calls value
+    const size_t had = ctx->ai_tkey.cap + ctx->ai_tval.cap;
+    if ((rc = grow(ctx, &ctx->ai_tkey, tsize * 8))) return rc;
+    if ((rc = grow(ctx, &ctx->ai_tval, tsize * 4))) return rc;
+    ctx->bytes += (int64_t)(ctx->ai_tkey.cap + ctx->ai_tval.cap) - (int64_t)had;
+    fill32(ctx, ctx->ai_tkey.p, -1, ctx->ai_tkey.cap / 4);
+    fill32(ctx, ctx->ai_tval.p, -1, ctx->ai_tval.cap / 4);
+  }
+  *tsize_out = tsize;
+  return FPX_OK;
+}
+
+// the stable radix sort of (key[0], val[0]) by entry; the result is in key[passes & 1], val[passes & 1]
+static int ai_sort_by_entry(fpx_ctx* ctx, int32_t* hdr, int32_t* hist, int32_t* const key[2], int32_t* const val[2], int E,
+                            int nblk) {
+  // keys are 0 .. E: the pass count is fixed per context
+  int bits = 0;
+  while (E >> bits) ++bits;
+  const int passes = (bits + RI_RADIX_BITS - 1) / RI_RADIX_BITS;
+  const dim3 per_tile(nblk), blk(256);
+  for (int p = 0; p < passes; ++p) {
+    RiSort a;
+    a.hdr = hdr, a.hist = hist, a.shift = p * RI_RADIX_BITS;
+    a.key_in = key[p & 1], a.val_in = val[p & 1];
+    a.key_out = key[(p + 1) & 1], a.val_out = val[(p + 1) & 1];
+    hipLaunchKernelGGL(k_ri_hist, per_tile, blk, 0, ctx->stream, a);
+    hipLaunchKernelGGL(k_ai_hscan, dim3(1), dim3(1024), 0, ctx->stream, a);
+    hipLaunchKernelGGL(k_ri_scatter, per_tile, blk, 0, ctx->stream, a);
+  }
+  return passes;
+}
+
 int32_t fpx_acceptor_inbox_dev(fpx_ctx* ctx, int32_t n, const int32_t* d_kind, const int32_t* d_group_index,
                                const int32_t* d_acceptor_index, const int32_t* d_slot, const int32_t* d_round,
                                const int32_t* d_value_id, int32_t grid_cols, int32_t* d_reply_kind, int32_t* d_reply_value) {
@@ -3186,16 +3229,8 @@ int32_t fpx_acceptor_inbox_dev(fpx_ctx* ctx, int32_t n, const int32_t* d_kind, c
   size_t had = ctx->ai_buf.cap;
   if ((rc = grow(ctx, &ctx->ai_buf, words * 4))) return rc;
   ctx->bytes += (int64_t)ctx->ai_buf.cap - (int64_t)had;
-  size_t tsize = 1024;
-  while (tsize < 2 * (size_t)n) tsize <<= 1;
-  if (tsize * 8 > ctx->ai_tkey.cap) {  // a new table: every word at its between-calls value
-    had = ctx->ai_tkey.cap + ctx->ai_tval.cap;
-    if ((rc = grow(ctx, &ctx->ai_tkey, tsize * 8))) return rc;
-    if ((rc = grow(ctx, &ctx->ai_tval, tsize * 4))) return rc;
-    ctx->bytes += (int64_t)(ctx->ai_tkey.cap + ctx->ai_tval.cap) - (int64_t)had;
-    fill32(ctx, ctx->ai_tkey.p, -1, ctx->ai_tkey.cap / 4);
-    fill32(ctx, ctx->ai_tval.p, -1, ctx->ai_tval.cap / 4);
-  }
+  size_t tsize;
+  if ((rc = ai_claim_table(ctx, n, &tsize))) return rc;
   AcceptorInbox b;
   memset(&b, 0, sizeof(b));
   b.n = n, b.E = E, b.grid_cols = grid_cols;
@@ -3214,19 +3249,7 @@ int32_t fpx_acceptor_inbox_dev(fpx_ctx* ctx, int32_t n, const int32_t* d_kind, c
   const dim3 per_tile(nblk), blk(256);
   const int sweep = std::max(1, std::min(nblk, ctx->num_cus * 8));
   hipLaunchKernelGGL(k_ai_keys, per_tile, blk, 0, ctx->stream, g, ctx->st, b, key[0], val[0]);
-  // keys are 0 .. E: the pass count is fixed per context
-  int bits = 0;
-  while (E >> bits) ++bits;
-  const int passes = (bits + RI_RADIX_BITS - 1) / RI_RADIX_BITS;
-  for (int p = 0; p < passes; ++p) {
-    RiSort a;
-    a.hdr = b.hdr, a.hist = hist, a.shift = p * RI_RADIX_BITS;
-    a.key_in = key[p & 1], a.val_in = val[p & 1];
-    a.key_out = key[(p + 1) & 1], a.val_out = val[(p + 1) & 1];
-    hipLaunchKernelGGL(k_ri_hist, per_tile, blk, 0, ctx->stream, a);
-    hipLaunchKernelGGL(k_ai_hscan, dim3(1), dim3(1024), 0, ctx->stream, a);
-    hipLaunchKernelGGL(k_ri_scatter, per_tile, blk, 0, ctx->stream, a);
-  }
+  const int passes = ai_sort_by_entry(ctx, b.hdr, hist, key, val, E, nblk);
   b.key = key[passes & 1], b.perm = val[passes & 1];
   hipLaunchKernelGGL(k_ai_tilemax<0>, dim3(sweep), blk, 0, ctx->stream, b);
   hipLaunchKernelGGL(k_ai_tilescan, dim3(1), dim3(AI_SCAN_THREADS), 0, ctx->stream, ctx->st, b);
@@ -3259,6 +3282,104 @@ int32_t fpx_acceptor_inbox(fpx_ctx* ctx, int32_t n, const int32_t* kind, const i
                         (const int32_t*)ctx->d_i32_c.p, (const int32_t*)ctx->d_slot.p, (const int32_t*)ctx->d_round.p,
                         (const int32_t*)ctx->d_value.p, grid_cols, reply_kind ? (int32_t*)ctx->ai_out[0].p : nullptr,
                         reply_value ? (int32_t*)ctx->ai_out[1].p : nullptr);
+                  });
+  if (rc != FPX_OK) return rc;
+  if (reply_kind) HIPCHK(ctx, hipMemcpyAsync(reply_kind, ctx->ai_out[0].p, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
+  if (reply_value) HIPCHK(ctx, hipMemcpyAsync(reply_value, ctx->ai_out[1].p, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  return FPX_OK;
+}
+
+// mencius.Acceptor's inbox for a burst of per-acceptor messages in delivery order, Phase2aNoopRanges among them
+// (fpx_mencius_acceptor_inbox.hpp).  Nothing is read by the host between the launches.
+static int32_t mencius_acceptor_inbox_ctx_ok(fpx_ctx* ctx, int32_t n) {
+  if (!ctx || n < 0 || n >= (1 << 30)) return FPX_EINVAL;
+  if (ctx->g.per_slot || ctx->g.qkind == FPX_Q_GRID) return FPX_EINVAL;  // mencius.Acceptor: one round per acceptor, no grids
+  return FPX_OK;
+}
+
+int32_t fpx_mencius_acceptor_inbox_dev(fpx_ctx* ctx, int32_t n, const int32_t* d_kind, const int32_t* d_group_index,
+                                       const int32_t* d_acceptor_index, const int32_t* d_slot, const int32_t* d_slot_end,
+                                       const int32_t* d_round, const int32_t* d_value_id, int32_t* d_reply_kind,
+                                       int32_t* d_reply_value) {
+  // (the guard launches the fold of a fused step that is still pending: the burst reads promised and max_voted)
+  DeviceGuard _dg(ctx);
+  int rc;
+  if ((rc = mencius_acceptor_inbox_ctx_ok(ctx, n))) return rc;
+  if (n == 0) return FPX_OK;
+  if (!d_kind || !d_acceptor_index || !d_slot || !d_slot_end || !d_round || !d_value_id) return FPX_EINVAL;
+  flush_pending_fin(ctx);
+  const Geom& g = ctx->g;
+  const int E = g.ngroups * g.R;
+  const int nblk = (n + AI_TILE - 1) / AI_TILE;
+  const size_t cap_n = (size_t)nblk * AI_TILE;
+  // [hdr | tile (64-bit) | key x 2 | val x 2 | accslot | tpos | rflag | list x 5 | hist | rcnt | fin_round | fin_slot]
+  const size_t words =
+      (size_t)AI_HDR_WORDS + 2 * (size_t)nblk + 12 * cap_n + (size_t)RI_RADIX * nblk + (size_t)nblk + 2 * (size_t)E;
+  size_t had = ctx->mai_buf.cap;
+  if ((rc = grow(ctx, &ctx->mai_buf, words * 4))) return rc;
+  ctx->bytes += (int64_t)ctx->mai_buf.cap - (int64_t)had;
+  size_t tsize;
+  if ((rc = ai_claim_table(ctx, n, &tsize))) return rc;
+  MenciusAcceptorInbox b;
+  memset(&b, 0, sizeof(b));
+  b.a.n = n, b.a.E = E, b.a.grid_cols = 0;
+  b.a.kind = d_kind, b.a.group = d_group_index, b.a.acceptor = d_acceptor_index, b.a.slot = d_slot, b.a.round = d_round;
+  b.a.value = d_value_id, b.slot_end = d_slot_end;
+  b.a.hdr = (int32_t*)ctx->mai_buf.p;
+  b.a.tile = (long long*)(b.a.hdr + AI_HDR_WORDS);
+  int32_t* key[2];
+  int32_t* val[2];
+  key[0] = (int32_t*)(b.a.tile + nblk), key[1] = key[0] + cap_n, val[0] = key[1] + cap_n, val[1] = val[0] + cap_n;
+  b.a.accslot = val[1] + cap_n, b.a.tpos = b.a.accslot + cap_n, b.rflag = b.a.tpos + cap_n;
+  b.lent = b.rflag + cap_n, b.lq0 = b.lent + cap_n, b.lq1 = b.lq0 + cap_n, b.lround = b.lq1 + cap_n;
+  b.lidx = b.lround + cap_n;
+  int32_t* hist = b.lidx + cap_n;
+  b.rcnt = hist + (size_t)RI_RADIX * nblk;
+  b.a.fin_round = b.rcnt + nblk, b.a.fin_slot = b.a.fin_round + E;
+  b.a.tkey = (unsigned long long*)ctx->ai_tkey.p, b.a.tval = (int32_t*)ctx->ai_tval.p, b.a.tmask = (uint32_t)(tsize - 1);
+  b.a.reply_kind = d_reply_kind, b.a.reply_value = d_reply_value;
+  const dim3 per_tile(nblk), blk(256);
+  const int sweep = std::max(1, std::min(nblk, ctx->num_cus * 8));
+  hipLaunchKernelGGL(k_mai_keys, per_tile, blk, 0, ctx->stream, g, ctx->st, b, key[0], val[0]);
+  const int passes = ai_sort_by_entry(ctx, b.a.hdr, hist, key, val, E, nblk);
+  b.a.key = key[passes & 1], b.a.perm = val[passes & 1];
+  hipLaunchKernelGGL(k_ai_tilemax<2>, dim3(sweep), blk, 0, ctx->stream, b.a);
+  hipLaunchKernelGGL(k_ai_tilescan, dim3(1), dim3(AI_SCAN_THREADS), 0, ctx->stream, ctx->st, b.a);
+  hipLaunchKernelGGL(k_mai_accept, per_tile, blk, 0, ctx->stream, g, ctx->st, b);
+  hipLaunchKernelGGL(k_mai_offsets, dim3(1), dim3(AI_SCAN_THREADS), 0, ctx->stream, b);
+  hipLaunchKernelGGL(k_mai_list, per_tile, blk, 0, ctx->stream, g, b);
+  hipLaunchKernelGGL(k_ai_tilemax<1>, dim3(sweep), blk, 0, ctx->stream, b.a);
+  hipLaunchKernelGGL(k_ai_tilescan, dim3(1), dim3(AI_SCAN_THREADS), 0, ctx->stream, ctx->st, b.a);
+  hipLaunchKernelGGL(k_mai_points, per_tile, blk, 0, ctx->stream, g, ctx->st, b);
+  // (the list's length stays on the device: the grid is sized by what the burst could hold)
+  hipLaunchKernelGGL(k_mai_ranges, dim3(4, std::max(1, std::min(n, ctx->num_cus * 4))), blk, 0, ctx->stream, g, ctx->st, b);
+  hipLaunchKernelGGL(k_ai_finish, per_tile, blk, 0, ctx->stream, ctx->st, b.a);
+  return launch_check(ctx);
+}
+
+// the host form: ONE run through the staging driver; the replies come down only when the burst was applied
+int32_t fpx_mencius_acceptor_inbox(fpx_ctx* ctx, int32_t n, const int32_t* kind, const int32_t* group_index,
+                                   const int32_t* acceptor_index, const int32_t* slot, const int32_t* slot_end,
+                                   const int32_t* round, const int32_t* value_id, int32_t* reply_kind,
+                                   int32_t* reply_value) {
+  DeviceGuard _dg(ctx);
+  int rc;
+  if ((rc = mencius_acceptor_inbox_ctx_ok(ctx, n))) return rc;
+  if (n == 0) return FPX_OK;
+  if (!kind || !acceptor_index || !slot || !slot_end || !round || !value_id) return FPX_EINVAL;
+  for (int a = 0; a < 2; ++a)
+    if ((rc = grow(ctx, &ctx->ai_out[a], (size_t)n * 4))) return rc;
+  rc = host_batch(ctx, n,
+                  {{&ctx->d_i32_a, kind, 4}, {&ctx->d_target, group_index, 4}, {&ctx->d_i32_c, acceptor_index, 4},
+                   {&ctx->d_slot, slot, 4}, {&ctx->d_i32_b, slot_end, 4}, {&ctx->d_round, round, 4},
+                   {&ctx->d_value, value_id, 4}},
+                  {}, nullptr, [&](int, int) {
+                    return fpx_mencius_acceptor_inbox_dev(
+                        ctx, n, (const int32_t*)ctx->d_i32_a.p, group_index ? (const int32_t*)ctx->d_target.p : nullptr,
+                        (const int32_t*)ctx->d_i32_c.p, (const int32_t*)ctx->d_slot.p, (const int32_t*)ctx->d_i32_b.p,
+                        (const int32_t*)ctx->d_round.p, (const int32_t*)ctx->d_value.p,
+                        reply_kind ? (int32_t*)ctx->ai_out[0].p : nullptr, reply_value ? (int32_t*)ctx->ai_out[1].p : nullptr);
                   });
   if (rc != FPX_OK) return rc;
   if (reply_kind) HIPCHK(ctx, hipMemcpyAsync(reply_kind, ctx->ai_out[0].p, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));

@@ -659,6 +659,33 @@ class NoopRangeEngine {
     if (nackRound >= 0) nacks->push_back(Nack{nackRound});
   }
 
+  // ---- the acceptors' inbox (mencius.Acceptor.receive, Acceptor.scala:142-291) for a burst of per-acceptor messages in
+  // delivery order, the kinds interleaved, in one device call and exactly as if every acceptor had handled its messages
+  // one by one (fpx_mencius_acceptor_inbox).  kind = FPX_WIRE_PHASE2A (slot, round, value) / FPX_WIRE_PHASE2A_NOOP_RANGE
+  // (slot = slotStartInclusive, slotEnd = slotEndExclusive, round) / FPX_WIRE_PHASE1A (round); (leaderGroupIndex,
+  // acceptorGroupIndex, acceptorIndex) = who received it.
+  struct AcceptorInbound { int32_t kind, leaderGroupIndex, acceptorGroupIndex, acceptorIndex, slot, slotEnd, round, value; };
+  // kind = 0 (skipped) / FPX_WIRE_PHASE2B / FPX_WIRE_PHASE2B_NOOP_RANGE / FPX_WIRE_PHASE1B / FPX_WIRE_NACK; value = the
+  // Nack's round (it goes to leader roundSystem.leader(message.round) of leader group slot % numLeaderGroups, :215-218,
+  // :250-253), the vote's or the promise's round.  A Phase1b's info is not produced: end the burst at the Phase1a and ask
+  // fpx_acceptor_phase1b_info_all for the promisers.
+  struct AcceptorReply { int32_t kind, value; };
+  std::vector<AcceptorReply> acceptorsHandleInbox(const std::vector<AcceptorInbound>& msgs) {
+    const int32_t n = (int32_t)msgs.size();
+    std::vector<int32_t> kind(n), group(n), acceptor(n), slot(n), slotEnd(n), round(n), value(n), rk(n), rv(n);
+    for (int32_t i = 0; i < n; ++i) {
+      kind[i] = msgs[i].kind, acceptor[i] = msgs[i].acceptorIndex;
+      group[i] = msgs[i].leaderGroupIndex * fcfg_.num_groups + msgs[i].acceptorGroupIndex;
+      slot[i] = msgs[i].slot, slotEnd[i] = msgs[i].slotEnd, round[i] = msgs[i].round, value[i] = msgs[i].value;
+    }
+    check(fpx_mencius_acceptor_inbox(ctx_, n, kind.data(), group.data(), acceptor.data(), slot.data(), slotEnd.data(),
+                                     round.data(), value.data(), rk.data(), rv.data()),
+          "Acceptor.receive");
+    std::vector<AcceptorReply> out(n);
+    for (int32_t i = 0; i < n; ++i) out[i] = AcceptorReply{rk[i], rv[i]};
+    return out;
+  }
+
   // mencius.ProxyLeader.handlePhase2bNoopRange (ProxyLeader.scala:355-411): all messages must carry the
   // same (start, end, round); ChosenNoopRange once every acceptor group has f + 1 votes.
   std::optional<ChosenNoopRange> proxyLeaderHandlePhase2bNoopRange(const std::vector<Phase2bNoopRange>& msgs) {

@@ -13,7 +13,10 @@
 //   GpuMenciusAcceptor     stands at ONE acceptor address (mencius/AcceptorMain.scala); every acceptor address gets one,
 //                          all over the same engine.  A Mencius Leader sends Phase1a to ACCEPTOR addresses
 //                          (mencius/Leader.scala:486-491, resend timer :288-297): without an actor there a new leader
-//                          would never finish Phase 1 (mencius/Acceptor.scala:166-200).
+//                          would never finish Phase 1 (mencius/Acceptor.scala:166-200).  hostsPhase2 = true: the
+//                          acceptor stands among the REFERENCE's mencius.ProxyLeaders and answers their per-acceptor
+//                          Phase2a / Phase2aNoopRange too, a tick's burst in one device call
+//                          (fpx_mencius_acceptor_inbox; mencius/Acceptor.scala:142-291)
 //
 // The walk of both on wire bytes -- a leader change in one leader group beside an undisturbed one, commands and noop
 // ranges, Nacks to LeaderInbound field 7 -- is tests/test_jni_shim.py::test_a_mencius_leader_change_on_wire_bytes_...
@@ -343,6 +346,113 @@ class GpuMenciusEngine[Transport <: frankenpaxos.Transport[Transport]](
     }
   }
 
+  // ---- the acceptors' inbox as a burst (fpx_mencius_acceptor_inbox), for acceptors hosted here among the REFERENCE's
+  // mencius.ProxyLeaders.  Those send every Phase2a once per acceptor address to quorumSize acceptors of the slot's group,
+  // and every Phase2aNoopRange once per acceptor address to quorumSize acceptors of every acceptor group of the leader
+  // group (mencius/ProxyLeader.scala:216-303); now and then a leader's Phase1as lie between them.  The GpuMenciusAcceptors
+  // (hostsPhase2 = true) enqueue whatever they receive here; the zero-delay timer of the first message flushes the queue:
+  // ONE native call per burst, every acceptor answered from its message's reply, exactly as if each had handled its
+  // messages one by one.  The call does not produce Phase1b.info -- a promise's info is the acceptor's votes as of that
+  // message -- so a burst is cut after each maximal run of Phase1as, and the promisers of that run get their info from
+  // acceptorPhase1All's slices (no vote lies between the promise and the end of the burst).  As for a proxy leader among
+  // remote acceptors, the window must cover the slots in flight (remoteRow / remoteRangeRows).
+  sealed trait InboxReply
+  case class Voted(phase2b: Phase2b) extends InboxReply
+  case class VotedRange(phase2b: Phase2bNoopRange) extends InboxReply
+  case class Nacked(nack: Nack) extends InboxReply
+  case class Promised(phase1b: Phase1b) extends InboxReply
+  private case class InboxMsg(leaderGroup: Int, acceptorGroup: Int, index: Int, request: AcceptorInbound.Request,
+                              reply: InboxReply => Unit) {
+    def isPhase1a: Boolean = request.isPhase1A
+  }
+  private val pendingInbox = mutable.Buffer[InboxMsg]()
+
+  // true: the queue was empty -- the caller starts its tick
+  def enqueueInbox(leaderGroup: Int, acceptorGroup: Int, index: Int, request: AcceptorInbound.Request,
+                   reply: InboxReply => Unit): Boolean = {
+    val first = pendingInbox.isEmpty
+    pendingInbox += InboxMsg(leaderGroup, acceptorGroup, index, request, reply)
+    first
+  }
+
+  def flushInbox(): Unit = {
+    var rest = pendingInbox.toList
+    pendingInbox.clear()
+    while (rest.nonEmpty) {
+      val (head, tail) = rest.span(!_.isPhase1a)
+      val (phase1as, later) = tail.span(_.isPhase1a)
+      rest = later
+      inboxBurst(head ++ phase1as, head.size)
+    }
+  }
+
+  private def phase1bInfo(g: Int, index: Int, chosenWatermark: Int): Seq[Phase1bSlotInfo] = {
+    var cap = 1024
+    var slots = new Array[Int](cap); var vr = new Array[Int](cap); var vv = new Array[Int](cap)
+    var k = Native.acceptorPhase1bInfo(handle, g, index, 0, cap, slots, vr, vv)
+    if (k > cap) {
+      cap = k; slots = new Array[Int](cap); vr = new Array[Int](cap); vv = new Array[Int](cap)
+      k = Native.acceptorPhase1bInfo(handle, g, index, 0, cap, slots, vr, vv)
+    }
+    if (k < 0) Native.check(-k, logger)
+    (0 until k)                                                                           // :184-199
+      .map(j => Phase1bSlotInfo(slot = slotOfRow(slots(j)), voteRound = vr(j), voteValue = valueOf(vv(j))))
+      .filter(_.slot >= chosenWatermark)
+      .sortBy(_.slot)
+  }
+
+  // burst = any messages but Phase1as, then (from firstPhase1a on) a run of Phase1as
+  private def inboxBurst(burst: List[InboxMsg], firstPhase1a: Int): Unit = {
+    val n = burst.size
+    val kind = new Array[Int](n); val group = new Array[Int](n); val acc = new Array[Int](n)
+    val slot = Array.fill(n)(-1); val slotEnd = Array.fill(n)(-1); val round = Array.fill(n)(-1); val value = Array.fill(n)(-1)
+    for ((m, i) <- burst.zipWithIndex) {
+      group(i) = ctxGroup(m.leaderGroup, m.acceptorGroup); acc(i) = m.index
+      m.request match {
+        case AcceptorInbound.Request.Phase2A(p) =>
+          kind(i) = Native.WIRE_PHASE2A; slot(i) = remoteRow(p.slot); round(i) = p.round
+          value(i) = intern(row(p.slot), p.commandBatchOrNoop)
+        case AcceptorInbound.Request.Phase2ANoopRange(p) =>
+          val (a, b) = remoteRangeRows(p.slotStartInclusive, p.slotEndExclusive)
+          kind(i) = Native.WIRE_PHASE2A_NOOP_RANGE; slot(i) = a; slotEnd(i) = b; round(i) = p.round
+        case AcceptorInbound.Request.Phase1A(p) => kind(i) = Native.WIRE_PHASE1A; round(i) = p.round
+        case AcceptorInbound.Request.Empty => logger.fatal("Empty AcceptorInbound encountered.")
+      }
+    }
+    val replyKind = new Array[Int](n); val replyValue = new Array[Int](n)
+    Native.check(Native.menciusAcceptorInbox(handle, n, kind, group, acc, slot, slotEnd, round, value, replyKind, replyValue),
+                 logger)
+    // everything but the promises, in delivery order
+    for ((m, i) <- burst.zipWithIndex) {
+      (m.request, replyKind(i)) match {
+        case (_, Native.WIRE_NACK) => m.reply(Nacked(Nack(round = replyValue(i))))            // :173-180, :210-218, :245-256
+        case (AcceptorInbound.Request.Phase2A(p), _) =>                                       // :220-234
+          m.reply(Voted(Phase2b(acceptorIndex = m.index, slot = p.slot, round = p.round)))
+        case (AcceptorInbound.Request.Phase2ANoopRange(p), _) =>                              // :279-290
+          m.reply(VotedRange(Phase2bNoopRange(acceptorGroupIndex = m.acceptorGroup, acceptorIndex = m.index,
+                                              slotStartInclusive = p.slotStartInclusive,
+                                              slotEndExclusive = p.slotEndExclusive, round = p.round)))
+        case _ => ()                                                                          // a promise: below
+      }
+    }
+    // the promisers of the run of Phase1as, as GpuPhase2Engine.inboxBurst: the promises of an acceptor's last round per
+    // (round, chosenWatermark) by acceptorPhase1All, an earlier promise of an acceptor that promised twice in one run by
+    // acceptorPhase1bInfo -- the votes are the same
+    val promisers = burst.zipWithIndex.drop(firstPhase1a).filter(mi => replyKind(mi._2) == Native.WIRE_PHASE1B).map(_._1)
+    val lastRound = mutable.Map[(Int, Int, Int), Int]()
+    for (m <- promisers) lastRound((m.leaderGroup, m.acceptorGroup, m.index)) = m.request.phase1A.get.round
+    val (current, earlier) =
+      promisers.partition(m => lastRound((m.leaderGroup, m.acceptorGroup, m.index)) == m.request.phase1A.get.round)
+    for ((_, run) <- current.groupBy(_.request.phase1A.get.round).toSeq.sortBy(_._1))
+      phase1Run(run.map(m => (m.leaderGroup, m.acceptorGroup, m.index, m.request.phase1A.get,
+                              (r: Either[Nack, Phase1b]) => m.reply(r.fold(Nacked(_), Promised(_))))))
+    for (m <- earlier) {
+      val p = m.request.phase1A.get
+      m.reply(Promised(Phase1b(groupIndex = m.acceptorGroup, acceptorIndex = m.index, round = p.round,
+                               info = phase1bInfo(ctxGroup(m.leaderGroup, m.acceptorGroup), m.index, p.chosenWatermark))))
+    }
+  }
+
   def close(): Unit = Native.check(Native.destroy(handle), logger)
 }
 
@@ -479,7 +589,12 @@ class GpuMenciusAcceptor[Transport <: frankenpaxos.Transport[Transport]](
     transport: Transport,
     logger: Logger,
     config: Config[Transport],
-    engine: GpuMenciusEngine[Transport]
+    engine: GpuMenciusEngine[Transport],
+    // true: this acceptor stands among the REFERENCE's mencius.ProxyLeaders, which send Phase2a and Phase2aNoopRange to
+    // acceptor addresses (mencius/ProxyLeader.scala:216-303): everything is enqueued and one tick flushes the burst
+    // through ONE native call (engine.flushInbox).  false: only Phase1as arrive here (GpuMenciusProxyLeader holds the
+    // acceptors), and a Phase2a / Phase2aNoopRange is fatal
+    hostsPhase2: Boolean = false
 ) extends Actor(address, transport, logger) {
   override type InboundMessage = AcceptorInbound
   override val serializer = AcceptorInboundSerializer
@@ -492,10 +607,56 @@ class GpuMenciusAcceptor[Transport <: frankenpaxos.Transport[Transport]](
     if addr == address
   } yield (l, a, i)).head
 
+  private val roundSystem = new RoundSystem.ClassicRoundRobin(config.leaderAddresses(leaderGroup).size)  // mencius/Acceptor.scala:104-106
+  private val slotSystem = new RoundSystem.ClassicRoundRobin(config.numLeaderGroups)                      // :112-113
+  private val leaders: Seq[Seq[Chan[Leader[Transport]]]] =
+    for (group <- config.leaderAddresses) yield for (a <- group) yield chan[Leader[Transport]](a, Leader.serializer)
+
   // one tick, as GpuMenciusProxyLeader's: "after the messages already queued on the event loop" -- the Phase1as of a burst
   private val phase1Tick = timer("gpuMenciusPhase1Tick", java.time.Duration.ZERO, () => engine.flushPhase1as())
+  // ... and with hostsPhase2 the whole burst the proxy leaders and leaders sent to the acceptor addresses of this engine
+  private val inboxTick = timer("gpuMenciusInboxTick", java.time.Duration.ZERO, () => engine.flushInbox())
 
   override def receive(src: Transport#Address, inbound: AcceptorInbound): Unit = {
+    if (hostsPhase2) receiveHosted(src, inbound) else receivePhase1Only(src, inbound)
+  }
+
+  // enqueued, not answered: one tick flushes the burst through ONE native call (engine.flushInbox)
+  private def receiveHosted(src: Transport#Address, inbound: AcceptorInbound): Unit = {
+    // a Nack goes to leaders(slotSystem.leader(slot or start))(roundSystem.leader(round)): mencius/Acceptor.scala:215-218,
+    // :250-253
+    def nackTo(slot: Int, round: Int, nack: Nack): Unit =
+      leaders(slotSystem.leader(slot))(roundSystem.leader(round)).send(LeaderInbound().withNack(nack))
+    val reply: engine.InboxReply => Unit = inbound.request match {
+      case AcceptorInbound.Request.Phase1A(_) =>
+        val leader = chan[Leader[Transport]](src, Leader.serializer)
+        ({
+          case engine.Nacked(nack)      => leader.send(LeaderInbound().withNack(nack))        // :173-180
+          case engine.Promised(phase1b) => leader.send(LeaderInbound().withPhase1B(phase1b))  // :184-199
+          case other                    => logger.fatal(s"Phase1a answered with $other")
+        })
+      case AcceptorInbound.Request.Phase2A(p) =>
+        ({
+          case engine.Nacked(nack) => nackTo(p.slot, p.round, nack)                           // :210-218
+          case engine.Voted(phase2b) =>                                                       // :226-234
+            chan[ProxyLeader[Transport]](src, ProxyLeader.serializer).send(ProxyLeaderInbound().withPhase2B(phase2b))
+          case other => logger.fatal(s"Phase2a answered with $other")
+        })
+      case AcceptorInbound.Request.Phase2ANoopRange(p) =>
+        ({
+          case engine.Nacked(nack) => nackTo(p.slotStartInclusive, p.round, nack)             // :245-256
+          case engine.VotedRange(phase2b) =>                                                  // :279-290
+            chan[ProxyLeader[Transport]](src, ProxyLeader.serializer)
+              .send(ProxyLeaderInbound().withPhase2BNoopRange(phase2b))
+          case other => logger.fatal(s"Phase2aNoopRange answered with $other")
+        })
+      case AcceptorInbound.Request.Empty =>
+        logger.fatal("Empty AcceptorInbound encountered.")
+    }
+    if (engine.enqueueInbox(leaderGroup, acceptorGroup, index, inbound.request, reply)) inboxTick.start()
+  }
+
+  private def receivePhase1Only(src: Transport#Address, inbound: AcceptorInbound): Unit = {
     inbound.request match {
       case AcceptorInbound.Request.Phase1A(phase1a) =>
         // enqueued, not answered: the burst a new leader sends is flushed by one tick (engine.flushPhase1as)

@@ -38,6 +38,7 @@ object Native {
   val WIRE_PHASE2B = 2; val WIRE_PHASE2B_NOOP_RANGE = 7
   // ... and of acceptorInbox's kind / replyKind
   val WIRE_OTHER = 0; val WIRE_PHASE2A = 1; val WIRE_PHASE1A = 3; val WIRE_NACK = 5; val WIRE_PHASE1B = 9
+  val WIRE_PHASE2A_NOOP_RANGE = 6       // menciusAcceptorInbox
   val WIRE_MAX_SLOT_REQUEST = 10; val WIRE_BATCH_MAX_SLOT_REQUEST = 11
 
   @native def create(cfg: Array[Int]): Long // < 0: -status
@@ -65,6 +66,12 @@ object Native {
   @native def acceptorInbox(handle: Long, n: Int, kind: Array[Int], groupIndex: Array[Int], acceptorIndex: Array[Int],
                             slot: Array[Int], round: Array[Int], value: Array[Int], gridCols: Int,
                             replyKind: Array[Int], replyValue: Array[Int]): Int
+  // mencius.Acceptor.receive for a burst of per-acceptor messages in delivery order, Phase2aNoopRanges among them
+  // (fpx_mencius_acceptor_inbox; mencius/Acceptor.scala:142-291): slot = a Phase2a's slot or a range's start, slotEnd = a
+  // range's end; groupIndex = leader group * numGroups + acceptor group; groupIndex, replyKind, replyValue may be null
+  @native def menciusAcceptorInbox(handle: Long, n: Int, kind: Array[Int], groupIndex: Array[Int],
+                                   acceptorIndex: Array[Int], slot: Array[Int], slotEnd: Array[Int], round: Array[Int],
+                                   value: Array[Int], replyKind: Array[Int], replyValue: Array[Int]): Int
   // mencius.ProxyLeader.handlePhase2aNoopRange bookkeeping for n ranges in one call (fpx_proxy_open_noop_ranges)
   @native def proxyOpenNoopRanges(handle: Long, n: Int, slotStart: Array[Int], slotEnd: Array[Int],
                                   round: Array[Int], isNew: Array[Byte]): Int

@@ -208,6 +208,32 @@ JNIEXPORT jint JNICALL Java_frankenpaxos_gpu_Native_acceptorInbox(JNIEnv* env, j
   return st;
 }
 
+/* mencius.Acceptor's inbox for a burst of per-acceptor messages in delivery order, Phase2aNoopRanges among them:
+ * mencius/Acceptor.scala:142-291 (fpx_mencius_acceptor_inbox).  kind as fpx_wire.h numbers it; groupIndex = leader group *
+ * numGroups + acceptor group; groupIndex, replyKind and replyValue may be null.  On an error the output arrays are left
+ * as they were. */
+JNIEXPORT jint JNICALL Java_frankenpaxos_gpu_Native_menciusAcceptorInbox(JNIEnv* env, jclass cls, jlong h, jint n,
+                                                                         jintArray kind, jintArray groupIndex,
+                                                                         jintArray acceptorIndex, jintArray slot,
+                                                                         jintArray slotEnd, jintArray round, jintArray value,
+                                                                         jintArray replyKind, jintArray replyValue) {
+  if (n < 0) return FPX_EINVAL;
+  if (n == 0) return fpx_mencius_acceptor_inbox(CTX(h), 0, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL);
+  if (!has(env, kind, n) || !opt(env, groupIndex, n) || !has(env, acceptorIndex, n) || !has(env, slot, n) ||
+      !has(env, slotEnd, n) || !has(env, round, n) || !has(env, value, n) || !opt(env, replyKind, n) ||
+      !opt(env, replyValue, n))
+    return FPX_EINVAL;
+  jint *k = in_ints(env, kind, n), *g = in_ints(env, groupIndex, n), *a = in_ints(env, acceptorIndex, n);
+  jint *s = in_ints(env, slot, n), *e = in_ints(env, slotEnd, n), *r = in_ints(env, round, n), *v = in_ints(env, value, n);
+  jint *rk = out_buf(replyKind, n, sizeof(jint)), *rv = out_buf(replyValue, n, sizeof(jint));
+  int32_t st = FPX_ENOMEM;
+  if (k && a && s && e && r && v && (g || !groupIndex) && (rk || !replyKind) && (rv || !replyValue))
+    st = fpx_mencius_acceptor_inbox(CTX(h), n, k, g, a, s, e, r, v, rk, rv);
+  if (st == FPX_OK) put_ints(env, replyKind, n, rk), put_ints(env, replyValue, n, rv);
+  free(k); free(g); free(a); free(s); free(e); free(r); free(v); free(rk); free(rv);
+  return st;
+}
+
 /* mencius.ProxyLeader.handlePhase2aNoopRange bookkeeping for n ranges (mencius/ProxyLeader.scala:255-303):
  * fpx_proxy_open_noop_ranges */
 JNIEXPORT jint JNICALL Java_frankenpaxos_gpu_Native_proxyOpenNoopRanges(JNIEnv* env, jclass cls, jlong h, jint n,

@@ -1009,7 +1009,8 @@ int32_t fpx_replica_inbox(fpx_ctx* ctx, int32_t n, const int32_t* kind, const in
  * votes as of that message (:167-180), so a caller that needs it ends its burst at that Phase1a and calls
  * fpx_acceptor_phase1b_info_all[_dev] for the promisers (jni/Native.scala's GpuAcceptor does).  A Phase1a in the middle
  * of a burst is still handled correctly for every later message.
- * FPX_BALLOT_ACCEPTOR contexts with num_leader_groups == 1 only; with grid_cols > 0, num_groups == 1: anything else, a
+ * FPX_BALLOT_ACCEPTOR contexts with num_leader_groups == 1 only (Mencius acceptors: fpx_mencius_acceptor_inbox below);
+ * with grid_cols > 0, num_groups == 1: anything else, a
  * NULL context, n < 0 or n >= 2^30, grid_cols < 0, or a NULL kind / acceptor_index / slot / round / value_id with n > 0
  * is FPX_EINVAL at once, nothing enqueued.  n == 0 is FPX_OK.
  * _dev: device pointers (arrays of n), enqueued on the context's stream behind the fold of an earlier fused step
@@ -1030,6 +1031,63 @@ int32_t fpx_acceptor_inbox_dev(fpx_ctx* ctx, int32_t n, const int32_t* d_kind, c
 int32_t fpx_acceptor_inbox(fpx_ctx* ctx, int32_t n, const int32_t* kind, const int32_t* group_index,
                            const int32_t* acceptor_index, const int32_t* slot, const int32_t* round,
                            const int32_t* value_id, int32_t grid_cols, int32_t* reply_kind, int32_t* reply_value);
+/* mencius.Acceptor's inbox (mencius/Acceptor.scala:142-291): handlePhase1a (:166-200), handlePhase2a (:202-235) and
+ * handlePhase2aNoopRange (:237-291) for a BURST of n AcceptorInbound messages in delivery order, the kinds interleaved and
+ * addressed to any of the context's acceptors -- what reference mencius.ProxyLeaders send: one Phase2a per acceptor
+ * address to quorumSize acceptors of the slot's group, one Phase2aNoopRange per acceptor address to quorumSize acceptors
+ * of every acceptor group of the leader group (mencius/ProxyLeader.scala:216-303).  The Mencius form of
+ * fpx_acceptor_inbox: NO run contract applies.  The arrays are what fpx_wire_mencius_decode_acceptor_inbound produces,
+ * plus who received each message:
+ *   kind[i] (fpx_wire.h): FPX_WIRE_PHASE2A (slot, round, value_id) / FPX_WIRE_PHASE2A_NOOP_RANGE (slot = start inclusive,
+ *     slot_end = end exclusive, round) / FPX_WIRE_PHASE1A (round); FPX_WIRE_OTHER is skipped (none of its fields is
+ *     read).  mencius.Acceptor has no read path: the two MaxSlotRequest kinds are a bad kind here.
+ *   group_index[i] (NULL = 0): leader_group * num_groups + acceptor_group, the row numbering of fpx_read_scalars;
+ *   acceptor_index[i]: the acceptor inside that group (0 .. num_replicas - 1), LOCAL to the context.
+ * The result is EXACTLY that of every acceptor handling its messages one by one in index order.  For acceptor e:
+ *   a message of any of the three kinds with round[i] < e.round: Nack(e.round) (:173, :210, :245 -- `<`: an equal round is
+ *     accepted again).
+ *   otherwise e.round := round[i]; a Phase2a stores (round, value_id) in cell (slot, e); a range stores (round, Noop = -1)
+ *     in cell (s, e) of every s in [start, end) with s = start (mod L) and (s / L) % A == e's acceptor group (:261-277).
+ *     The start need not be a slot of e's acceptor group, a range may own no slot at all, and an empty range still moves
+ *     the round and is still answered.
+ *   every cell ends as its LAST accepted covering message left it, a point or a range, whatever their rounds (equal
+ *     rounds with different values come out in index order).
+ *   max_voted (the scalar the library keeps in every mode) is raised by a Phase2a's slot and by a range's largest owned
+ *     slot, as fpx_acceptor_phase2a / fpx_acceptor_phase2a_noop_range raise it.
+ * reply_kind[i]: 0 = no reply (skipped), FPX_WIRE_PHASE2B, FPX_WIRE_PHASE2B_NOOP_RANGE, FPX_WIRE_PHASE1B = promised,
+ * FPX_WIRE_NACK.  reply_value[i]: a Nack's round (the acceptor's, at that moment); a vote's or a promise's round (the
+ * message's); -1 with no reply.  A Nack goes to leader fpx_round_leader(num_leaders, round[i]) of leader group
+ * slot % L / start % L (:215-218, :250-253), which stays with the caller.  Either output may be NULL.
+ * Afterwards the acceptors' rounds, max_voted and vote cells (fpx_read_scalars, fpx_read_state, fpx_state_digest) are what
+ * the message-at-a-time route (fpx_acceptor_phase2a / fpx_acceptor_phase2a_noop_range / fpx_acceptor_phase1a with
+ * single-bit masks) leaves, and so is what the vote kernels keep about fresh rows.
+ * Phase1b.info is NOT produced, as in fpx_acceptor_inbox: a caller that needs it ends its burst at that Phase1a and calls
+ * fpx_acceptor_phase1b_info_all[_dev] for the promisers (jni/MenciusNative.scala's GpuMenciusEngine does).
+ * FPX_BALLOT_ACCEPTOR contexts without a grid quorum (num_leader_groups == 1 is allowed): anything else, a NULL context,
+ * n < 0 or n >= 2^30, or a NULL kind / acceptor_index / slot / slot_end / round / value_id with n > 0 is FPX_EINVAL at
+ * once, nothing enqueued.  n == 0 is FPX_OK.
+ * _dev: device pointers (arrays of n), enqueued on the context's stream behind the fold of an earlier fused step
+ * (fpx_deferred_folds); nothing is read by the host between its passes (csrc/fpx_mencius_acceptor_inbox.hpp: the sort and
+ * the running maxima of fpx_acceptor_inbox, the accepted ranges compacted into a list, every cell written by exactly one
+ * thread; integer atomics only, results are reproducible).  Another kind, an index that names no acceptor of the
+ * context, a round outside 0 .. 2^30 - 2, a Phase2a slot outside [0, num_slots) or of another group than the message's,
+ * a range with start < 0, end < start or end > num_slots, and a range whose start % L is not the receiving acceptor's
+ * leader group (its cells lie in rows that acceptor has no column in) are found on the device before anything is
+ * applied: FPX_EINVAL at fpx_sync, the LOWEST offending index in fpx_error_detail, state untouched, no output written,
+ * and (the _dev convention) the context applies nothing up to that fpx_sync.  The scratch (about 64 B per message and
+ * fpx_acceptor_inbox's claim table) lives in the context, is allocated on first use, grows with n and is counted by
+ * fpx_device_bytes.  Settling the cells costs (owned cells of a range) x (later accepted ranges of the same acceptor in
+ * the burst) interval tests: meant for the handful of ranges per acceptor a tick carries.
+ * The host form takes host arrays, goes through the staging driver as a single run and is synchronous; on an error the
+ * output arrays are left untouched. */
+int32_t fpx_mencius_acceptor_inbox_dev(fpx_ctx* ctx, int32_t n, const int32_t* d_kind, const int32_t* d_group_index,
+                                       const int32_t* d_acceptor_index, const int32_t* d_slot,
+                                       const int32_t* d_slot_end, const int32_t* d_round, const int32_t* d_value_id,
+                                       int32_t* d_reply_kind, int32_t* d_reply_value);
+int32_t fpx_mencius_acceptor_inbox(fpx_ctx* ctx, int32_t n, const int32_t* kind, const int32_t* group_index,
+                                   const int32_t* acceptor_index, const int32_t* slot, const int32_t* slot_end,
+                                   const int32_t* round, const int32_t* value_id, int32_t* reply_kind,
+                                   int32_t* reply_value);
 /* log entries [first, first + count): value (-1 where absent) and present flag */
 int32_t fpx_replica_read_log(fpx_ctx* ctx, int32_t first, int32_t count, int32_t* values,
                              uint8_t* present);
