@@ -1398,6 +1398,7 @@ __global__ void __launch_bounds__(256) k_hp_commit(const EpxState st, const HpBa
 }
 
 #include "fpx_epaxos_mk.hpp"
+#include "fpx_epx_leader.hpp"
 
 struct Buf {
   void* p = nullptr;
@@ -1425,6 +1426,8 @@ struct fpx_epx {
   uint32_t kp_seq = 0;
   bool kp_lds_allowed = false, kp_off = false;
   uint32_t cl_run = 0;
+  EpxLeader ls = {nullptr, nullptr};      // FPX_EPX_F_LEADER_STATE: Replica.leaderStates (fpx_epx_leader.hpp), else not allocated
+  Buf lr_misc;                            // fpx_epx_leader_replies: the decided flags and the compaction's block counts
   bool lds_allowed = false, sort_lds_allowed = false;
   int num_cus = 256;
 };
@@ -1948,6 +1951,10 @@ int32_t fpx_epx_create(const fpx_epx_config* cfg, fpx_epx** out) {
   if (!(n == 3 || n == 5 || n == 7) || cfg->num_keys < 1 || cfg->num_keys > (1 << 24) || cfg->num_instances < 0 ||
       (int64_t)cfg->num_instances * n > (int64_t)1 << 30)
     return FPX_EINVAL;
+  // leader state lives beside the command log; its cells are a sort key of fpx_epx_leader_replies (31 bits)
+  if ((cfg->flags & FPX_EPX_F_LEADER_STATE) &&
+      (cfg->num_instances <= 0 || (int64_t)cfg->num_instances * n * n > (int64_t)1 << 31))
+    return FPX_EINVAL;
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || cfg->device < 0 || cfg->device >= ndev)
     return FPX_ENODEVICE;
@@ -2003,6 +2010,12 @@ int32_t fpx_epx_create(const fpx_epx_config* cfg, fpx_epx** out) {
     if (hipMemsetAsync(e->st.cl_vote, 0xFF, ce * 4, e->stream) != hipSuccess) return fail(FPX_EHIP);
     if (hipMemsetAsync(e->st.cl_triple, 0xFF, ce * 4, e->stream) != hipSuccess) return fail(FPX_EHIP);
     if (hipMemsetAsync(e->st.cl_stamp, 0, (size_t)n * cfg->num_instances * 4, e->stream) != hipSuccess) return fail(FPX_EHIP);
+    if (cfg->flags & FPX_EPX_F_LEADER_STATE) {
+      // every head starts as "not led" (phase 0); a response row is read only once its bit of the head is set
+      if (hipMalloc((void**)&e->ls.head, ce * sizeof(int4)) != hipSuccess) return fail(FPX_ENOMEM);
+      if (hipMalloc((void**)&e->ls.resp, ce * n * (n + 2) * 4) != hipSuccess) return fail(FPX_ENOMEM);
+      if (hipMemsetAsync(e->ls.head, 0, ce * sizeof(int4), e->stream) != hipSuccess) return fail(FPX_EHIP);
+    }
   }
   // the word k_kp_scatter tells the host through (did a key of the tick outgrow the on-chip tables?)
   if (hipHostMalloc((void**)&e->kp_flag, 64, hipHostMallocDefault) == hipSuccess) {
@@ -2023,11 +2036,11 @@ int32_t fpx_epx_destroy(fpx_epx* e) {
   EpxDeviceGuard _dg(e->cfg.device);
   if (e->stream) (void)hipStreamSynchronize(e->stream);
   void* ps[] = {e->st.gets, e->st.sets, e->st.status, e->st.cl_status, e->st.cl_ballot, e->st.cl_vote, e->st.cl_triple,
-                e->st.largest, e->st.cl_stamp, e->st.cl_deps, e->st.cl_dend};
+                e->st.largest, e->st.cl_stamp, e->st.cl_deps, e->st.cl_dend, e->ls.head, e->ls.resp};
   for (void* p : ps)
     if (p) (void)hipFree(p);
   Buf* bs[] = {&e->kv, &e->kv2, &e->seg, &e->conf, &e->tmp, &e->tick, &e->fusedb, &e->metab, &e->stage, &e->mk_misc, &e->mk_rec,
-               &e->mk_pair, &e->mk_pconf};
+               &e->mk_pair, &e->mk_pconf, &e->lr_misc};
   for (Buf* b : bs)
     if (b->p) (void)hipFree(b->p);
   if (e->mk_host) (void)hipHostFree(e->mk_host);
@@ -2729,6 +2742,203 @@ int32_t fpx_epx_handle_preaccept_mk(fpx_epx* e, int32_t m, const int32_t* leader
   return handle_preaccept_impl(e, m, leader, number, ballot_ordering, ballot_replica, nullptr, key_offsets, keys, is_set, triple_id,
                                deps_in, deps_in_values_end, target_mask, ok_bits, resend_bits, nack_bits, commit_bits, nack_ballot,
                                reply_deps, reply_values_end, reply_triple);
+}
+
+// ---- the leader half (FPX_EPX_F_LEADER_STATE): csrc/fpx_epx_leader.hpp ---------------------------------------------------
+static bool leader_state_on(const fpx_epx* e) { return e && (e->cfg.flags & FPX_EPX_F_LEADER_STATE) && e->ls.head; }
+
+int32_t fpx_epx_lead(fpx_epx* e, int32_t m, const int32_t* leader, const int32_t* number, const int32_t* at,
+                     const int32_t* ballot_ordering, const int32_t* key, const uint8_t* is_set, const int32_t* triple_id,
+                     const uint8_t* avoid_fast_path, int32_t* deps, int32_t* deps_values_end) {
+  if (!e || m < 0 || !leader_state_on(e)) return FPX_EINVAL;
+  EpxDeviceGuard _dg(e->cfg.device);
+  if (m == 0) return FPX_OK;
+  if (!leader || !number || !at || !ballot_ordering || !key || !is_set || !triple_id || !avoid_fast_path) return FPX_EINVAL;
+  const int n = e->st.n;
+  const size_t mn = (size_t)m * n;
+  const int NP = n <= 4 ? 4 : 8;
+  int rc;
+  if ((rc = grow(e, &e->kv, mn * 8))) return rc;
+  if ((rc = grow(e, &e->kv2, mn * 8))) return rc;
+  if ((rc = grow(e, &e->tick, (size_t)n * e->st.num_keys * 2 * n * 4))) return rc;
+  if ((rc = grow(e, &e->seg, (size_t)n * e->st.num_keys * 8))) return rc;
+  if ((rc = grow(e, &e->conf, mn * NP * 4))) return rc;
+  const int32_t *d_leader, *d_number, *d_at, *d_bo, *d_key, *d_tr, *d_zero;
+  const uint8_t *d_set, *d_avoid;
+  uint8_t *d_skip, *d_act;
+  int32_t *d_deps, *d_dend, *d_rd, *d_re;
+  auto launch = [&]() -> int {
+    LdBatch lb;
+    memset(&lb, 0, sizeof(lb));
+    lb.m = m, lb.leader = d_leader, lb.number = d_number, lb.b_ord = d_bo, lb.at = d_at, lb.key = d_key, lb.is_set = d_set;
+    lb.triple = d_tr, lb.avoid = d_avoid, lb.deps = d_deps, lb.dend = d_dend, lb.skip = d_skip, lb.act = d_act;
+    lb.kv = (uint2*)e->kv.p, lb.reply_deps = d_rd, lb.reply_end = d_re;
+    int rc2;
+    if ((rc2 = next_run_id(e, &lb.run_id))) return rc2;
+    // K7's "processed" branch at replica at[i] alone, with an empty deps_in: its gate table, its scan, its reply kernel
+    HpBatch hb;
+    memset(&hb, 0, sizeof(hb));
+    hb.m = m, hb.leader = d_leader, hb.number = d_number, hb.b_ord = d_bo, hb.b_rep = d_at, hb.key = d_key, hb.is_set = d_set;
+    hb.triple = d_tr, hb.deps_in = d_zero, hb.reply_deps = d_rd, hb.reply_end = d_re, hb.act = d_act, hb.kv = lb.kv;
+    hb.conf = (int32_t*)e->conf.p, hb.tick = (int32_t*)e->tick.p;
+    const dim3 gm((m + 255) / 256), gmn((unsigned)(((long long)m * n + 255) / 256)), blk(256);
+    hipLaunchKernelGGL(k_ld_validate, gm, blk, 0, e->stream, e->st, lb);
+    hipLaunchKernelGGL(k_ld_gate, gmn, blk, 0, e->stream, e->st, lb);
+    EpxBatch sb;
+    memset(&sb, 0, sizeof(sb));
+    sb.m = m, sb.number = d_number, sb.kv = hb.kv;
+    const uint32_t* key_totals = nullptr;
+    int key_buckets = 0;
+    sb.kv_sorted = sort_by_key(e, m, hb.kv, (uint2*)e->kv2.p, nullptr, &rc2, &key_totals, &key_buckets);
+    if (rc2) return rc2;
+    sb.tick = (int32_t*)e->tick.p, sb.seg = (int32_t*)e->seg.p, sb.conf = (int32_t*)e->conf.p;
+    launch_segments(e, sb, key_totals, key_buckets);
+    by_n(n, [&](auto N) {
+      launch_hp<N>(e, sb, hb);
+      hipLaunchKernelGGL((k_ld_install<N>), gm, blk, 0, e->stream, e->st, e->ls, lb);
+    });
+    const long long tot = (long long)e->st.num_keys * n * n;
+    hipLaunchKernelGGL(k_hp_commit, dim3((unsigned)((tot + 255) / 256)), blk, 0, e->stream, e->st, hb);
+    return FPX_OK;
+  };
+  // the outputs reach the caller only on FPX_OK / FPX_EFATAL_PROTOCOL: FPX_EINVAL leaves the caller's arrays as they were
+  std::vector<int32_t> tmp;
+  try {
+    tmp.resize(mn + (size_t)m);
+  } catch (const std::bad_alloc&) {  // (no exception crosses the C ABI)
+    return FPX_ENOMEM;
+  }
+  rc = host_call(e, {in(d_leader, leader, m), in(d_number, number, m), in(d_at, at, m), in(d_bo, ballot_ordering, m),
+                     in(d_key, key, m), in(d_tr, triple_id, m), in(d_set, is_set, m), in(d_avoid, avoid_fast_path, m),
+                     scratch(d_zero, mn, 0), scratch(d_skip, m, 0), out(d_deps, tmp.data(), mn), out(d_dend, tmp.data() + mn, m),
+                     scratch(d_act, mn), scratch(d_rd, mn * n), scratch(d_re, mn)},
+                 launch);
+  if (rc != FPX_OK && rc != FPX_EFATAL_PROTOCOL) return rc;
+  if (deps) memcpy(deps, tmp.data(), mn * 4);
+  if (deps_values_end) memcpy(deps_values_end, tmp.data() + mn, (size_t)m * 4);
+  return rc;
+}
+
+static int32_t leader_replies_launch(fpx_epx* e, int32_t m, const int32_t* d_kind, const int32_t* d_to, const int32_t* d_leader,
+                                     const int32_t* d_number, const int32_t* d_bo, const int32_t* d_br, const int32_t* d_ridx,
+                                     const int32_t* d_seq, const int32_t* d_deps, const int32_t* d_dend, int32_t* d_outcome,
+                                     int32_t* d_out_seq, int32_t* d_out_deps, int32_t* d_out_end, int32_t* d_out_triple,
+                                     int32_t* d_decided, int32_t* d_num_decided) {
+  const int n = e->st.n;
+  LrBatch b;
+  memset(&b, 0, sizeof(b));
+  b.m = m, b.kind = d_kind, b.to = d_to, b.leader = d_leader, b.number = d_number, b.b_ord = d_bo, b.b_rep = d_br, b.ridx = d_ridx;
+  b.seq = d_seq, b.deps = d_deps, b.dend = d_dend, b.outcome = d_outcome, b.out_seq = d_out_seq, b.out_deps = d_out_deps;
+  b.out_end = d_out_end, b.out_triple = d_out_triple, b.decided = d_decided, b.num_decided = d_num_decided;
+  b.blocks = (m + LR_BLOCK - 1) / LR_BLOCK;
+  int rc;
+  if ((rc = grow(e, &e->kv, (size_t)m * 8))) return rc;
+  if ((rc = grow(e, &e->kv2, (size_t)m * 8))) return rc;
+  const size_t flag_bytes = ((size_t)m + 255) & ~(size_t)255;
+  if ((rc = grow(e, &e->lr_misc, flag_bytes + (size_t)b.blocks * 4))) return rc;
+  b.kv = (uint2*)e->kv.p, b.flag = (uint8_t*)e->lr_misc.p, b.bsum = (uint32_t*)((char*)e->lr_misc.p + flag_bytes);
+  const dim3 gm((m + 255) / 256), blk(256);
+  hipLaunchKernelGGL(k_lr_validate, gm, blk, 0, e->stream, e->st, b);
+  unsigned bits = 1;  // the cells of the context: (to, leader, number)
+  while (((uint64_t)1 << bits) < (uint64_t)n * n * e->st.num_instances) ++bits;
+  b.sorted = radix_sort_pairs(e, 1, m, bits, b.kv, (uint2*)e->kv2.p, nullptr, &rc, nullptr, nullptr);
+  if (rc) return rc;
+  by_n(n, [&](auto N) { hipLaunchKernelGGL((k_lr_walk<N>), gm, blk, 0, e->stream, e->st, e->ls, b); });
+  if (d_decided || d_num_decided) {
+    hipLaunchKernelGGL(k_lr_count, dim3(b.blocks), blk, 0, e->stream, e->st, b);
+    hipLaunchKernelGGL(k_lr_bscan, dim3(1), blk, 0, e->stream, e->st, b);
+    if (d_decided) hipLaunchKernelGGL(k_lr_compact, dim3(b.blocks), blk, 0, e->stream, e->st, b);
+  }
+  return FPX_OK;
+}
+
+int32_t fpx_epx_leader_replies_dev(fpx_epx* e, int32_t m, const int32_t* d_kind, const int32_t* d_to, const int32_t* d_leader,
+                                   const int32_t* d_number, const int32_t* d_ballot_ordering, const int32_t* d_ballot_replica,
+                                   const int32_t* d_replica_index, const int32_t* d_sequence_number, const int32_t* d_deps,
+                                   const int32_t* d_deps_values_end, int32_t* d_outcome, int32_t* d_out_seq, int32_t* d_out_deps,
+                                   int32_t* d_out_values_end, int32_t* d_out_triple, int32_t* d_decided_index,
+                                   int32_t* d_num_decided) {
+  if (!e || m < 0 || m >= (1 << 30) || !leader_state_on(e)) return FPX_EINVAL;
+  EpxDeviceGuard _dg(e->cfg.device);
+  if (m == 0) {
+    if (d_num_decided) EHIP(e, hipMemsetAsync(d_num_decided, 0, 4, e->stream));
+    return FPX_OK;
+  }
+  if (!d_kind || !d_to || !d_leader || !d_number || !d_ballot_ordering || !d_ballot_replica || !d_replica_index || !d_deps)
+    return FPX_EINVAL;
+  int rc = leader_replies_launch(e, m, d_kind, d_to, d_leader, d_number, d_ballot_ordering, d_ballot_replica, d_replica_index,
+                                 d_sequence_number, d_deps, d_deps_values_end, d_outcome, d_out_seq, d_out_deps, d_out_values_end,
+                                 d_out_triple, d_decided_index, d_num_decided);
+  return rc ? rc : launch_check(e);
+}
+
+int32_t fpx_epx_leader_replies(fpx_epx* e, int32_t m, const int32_t* kind, const int32_t* to, const int32_t* leader,
+                               const int32_t* number, const int32_t* ballot_ordering, const int32_t* ballot_replica,
+                               const int32_t* replica_index, const int32_t* sequence_number, const int32_t* deps,
+                               const int32_t* deps_values_end, int32_t* outcome, int32_t* out_seq, int32_t* out_deps,
+                               int32_t* out_values_end, int32_t* out_triple, int32_t* decided_index, int32_t* num_decided) {
+  if (!e || m < 0 || m >= (1 << 30) || !leader_state_on(e)) return FPX_EINVAL;
+  EpxDeviceGuard _dg(e->cfg.device);
+  if (m == 0) {
+    if (num_decided) *num_decided = 0;
+    return FPX_OK;
+  }
+  if (!kind || !to || !leader || !number || !ballot_ordering || !ballot_replica || !replica_index || !deps) return FPX_EINVAL;
+  const size_t mn = (size_t)m * e->st.n;
+  const int32_t *d_kind, *d_to, *d_leader, *d_number, *d_bo, *d_br, *d_ridx, *d_seq, *d_deps, *d_dend;
+  int32_t *d_outcome, *d_oseq, *d_odeps, *d_oend, *d_otr, *d_dec, *d_nd;
+  auto launch = [&]() -> int {
+    return leader_replies_launch(e, m, d_kind, d_to, d_leader, d_number, d_bo, d_br, d_ridx, sequence_number ? d_seq : nullptr,
+                                 d_deps, deps_values_end ? d_dend : nullptr, d_outcome, d_oseq, d_odeps, d_oend, d_otr, d_dec, d_nd);
+  };
+  // an output is downloaded only on FPX_OK / FPX_EFATAL_PROTOCOL: FPX_EINVAL leaves the caller's arrays as they were
+  int32_t *h_outcome = nullptr, *h_oseq = nullptr, *h_odeps = nullptr, *h_oend = nullptr, *h_otr = nullptr, *h_dec = nullptr;
+  std::vector<int32_t> tmp;
+  try {
+    tmp.resize(5 * (size_t)m + mn + 1);
+  } catch (const std::bad_alloc&) {  // (no exception crosses the C ABI)
+    return FPX_ENOMEM;
+  }
+  h_outcome = tmp.data(), h_oseq = h_outcome + m, h_oend = h_oseq + m, h_otr = h_oend + m, h_dec = h_otr + m, h_odeps = h_dec + m;
+  int32_t* h_nd = h_odeps + mn;
+  const int rc = host_call(e, {in(d_kind, kind, m), in(d_to, to, m), in(d_leader, leader, m), in(d_number, number, m),
+                               in(d_bo, ballot_ordering, m), in(d_br, ballot_replica, m), in(d_ridx, replica_index, m),
+                               in(d_seq, sequence_number, m), in(d_dend, deps_values_end, m), in(d_deps, deps, mn),
+                               out(d_outcome, h_outcome, m), out(d_oseq, h_oseq, m), out(d_oend, h_oend, m), out(d_otr, h_otr, m),
+                               out(d_dec, h_dec, m), out(d_odeps, h_odeps, mn), out(d_nd, h_nd, 1)},
+                           launch);
+  if (rc != FPX_OK && rc != FPX_EFATAL_PROTOCOL) return rc;
+  if (outcome) memcpy(outcome, h_outcome, (size_t)m * 4);
+  if (out_seq) memcpy(out_seq, h_oseq, (size_t)m * 4);
+  if (out_values_end) memcpy(out_values_end, h_oend, (size_t)m * 4);
+  if (out_triple) memcpy(out_triple, h_otr, (size_t)m * 4);
+  if (out_deps) memcpy(out_deps, h_odeps, mn * 4);
+  if (decided_index) memcpy(decided_index, h_dec, (size_t)*h_nd * 4);
+  if (num_decided) *num_decided = *h_nd;
+  return rc;
+}
+
+int32_t fpx_epx_read_leader_state(fpx_epx* e, int32_t replica, int32_t leader, int32_t number, int32_t out[8],
+                                  int32_t* responses) {
+  if (!leader_state_on(e) || !out || replica < 0 || replica >= e->st.n || leader < 0 || leader >= e->st.n || number < 0 ||
+      number >= e->st.num_instances)
+    return FPX_EINVAL;
+  EpxDeviceGuard _dg(e->cfg.device);
+  const int n = e->st.n;
+  const size_t c = ((size_t)replica * n + leader) * e->st.num_instances + number;
+  int32_t h[4], ballot = 0, vote = 0;
+  uint8_t kind = 0;
+  EHIP(e, hipStreamSynchronize(e->stream));
+  EHIP(e, hipMemcpy(h, e->ls.head + c, 16, hipMemcpyDeviceToHost));
+  EHIP(e, hipMemcpy(&kind, e->st.cl_status + c, 1, hipMemcpyDeviceToHost));
+  EHIP(e, hipMemcpy(&ballot, e->st.cl_ballot + c, 4, hipMemcpyDeviceToHost));
+  EHIP(e, hipMemcpy(&vote, e->st.cl_vote + c, 4, hipMemcpyDeviceToHost));
+  const int phase = h[0] & 3;
+  const bool live = phase != 0 && kind != CL_COMMITTED && ballot == h[1] && vote == h[1];
+  out[0] = live ? phase : 0, out[1] = h[1], out[2] = (h[0] >> 2) & 1, out[3] = h[2], out[4] = h[3], out[5] = (h[0] >> 3) & 1;
+  out[6] = ((uint32_t)h[0] >> 8) & 0xff, out[7] = phase;
+  if (responses) EHIP(e, hipMemcpy(responses, e->ls.resp + c * n * (n + 2), (size_t)n * (n + 2) * 4, hipMemcpyDeviceToHost));
+  return FPX_OK;
 }
 
 }  // extern "C"

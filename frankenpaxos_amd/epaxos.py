@@ -9,6 +9,13 @@ from . import _lib
 from ._lib import FpxError
 
 
+FPX_EPX_F_LEADER_STATE = 1
+# fpx_epx_leader_replies: message kinds and per-message outcomes (include/fpx.h)
+PRE_ACCEPT_OK, ACCEPT_OK, NACK, SLOW_PATH_TIMER = 0, 1, 2, 3
+(IGNORED, WAITING, START_SLOW_PATH_TIMER, FAST_COMMIT, ACCEPT, SLOW_COMMIT, NACK_RECOVER, NACK_IGNORED,
+ FATAL) = range(9)
+
+
 class FpxEpxConfig(C.Structure):
     _fields_ = [("num_replicas", C.c_int32), ("num_keys", C.c_int32), ("device", C.c_int32),
                 ("flags", C.c_uint32), ("num_instances", C.c_int32)]
@@ -28,13 +35,15 @@ def _bind(L):
 
 
 class EPaxos:
-    def __init__(self, num_replicas, num_keys, device=0, num_instances=0):
+    def __init__(self, num_replicas, num_keys, device=0, num_instances=0, leader_state=False):
         """num_instances > 0: every replica keeps its command log for instances (leader, number < num_instances):
-        pre-accept records it, prepare() / accept() run the per-instance Paxos on it"""
+        pre-accept records it, prepare() / accept() run the per-instance Paxos on it.
+        leader_state (needs num_instances > 0): the context also keeps Replica.leaderStates, for lead() and
+        leader_replies() -- hosted replicas that lead instances among peers in other processes"""
         self.L = _lib.lib()
         _bind(self.L)
         self.n, self.num_keys = num_replicas, num_keys
-        cfg = FpxEpxConfig(num_replicas, num_keys, device, 0, num_instances)
+        cfg = FpxEpxConfig(num_replicas, num_keys, device, FPX_EPX_F_LEADER_STATE if leader_state else 0, num_instances)
         h = C.c_void_p()
         st = self.L.fpx_epx_create(C.byref(cfg), C.byref(h))
         if st:
@@ -254,6 +263,62 @@ class EPaxos:
         p = lambda a: None if a is None else a.ctypes.data
         return self.L.fpx_epx_handle_commit_mk(self._h, m, p(leader), p(number), p(tr), p(off), p(keys), p(is_set), p(d), p(de),
                                                p(tgt))
+
+    # ---- the leader half (leader_state=True) ----
+    def lead(self, leader, number, at, ballot_ordering, key, is_set, triple_id, avoid_fast_path=None):
+        """transitionToPreAcceptPhase of instance (leader, number) at replica `at` in ballot (ballot_ordering, at), key -1 =
+        Noop: (status, deps[m, n], deps_values_end[m]) -- the dependencies of the PreAccept to send"""
+        a32 = lambda x: np.ascontiguousarray(x, dtype=np.int32)
+        leader, number, at, bo, key, tr = a32(leader), a32(number), a32(at), a32(ballot_ordering), a32(key), a32(triple_id)
+        m = len(leader)
+        is_set = np.ascontiguousarray(is_set, dtype=np.uint8)
+        avoid = np.zeros(m, np.uint8) if avoid_fast_path is None else np.ascontiguousarray(avoid_fast_path, dtype=np.uint8)
+        deps, dend = np.zeros((m, self.n), np.int32), np.zeros(m, np.int32)
+        p = lambda a: a.ctypes.data
+        st = self.L.fpx_epx_lead(self._h, m, p(leader), p(number), p(at), p(bo), p(key), p(is_set), p(tr), p(avoid), p(deps),
+                                 p(dend))
+        return st, deps, dend
+
+    def leader_replies(self, kind, to, leader, number, ballot_ordering, ballot_replica, replica_index, sequence_number=None,
+                       deps=None, deps_values_end=None):
+        """one burst of PreAcceptOk (0) / AcceptOk (1) / Nack (2) / defaultToSlowPath-timer (3) events in delivery order:
+        (status, outcome[m], out_seq[m], out_deps[m, n], out_values_end[m], out_triple[m], decided_index[num_decided])"""
+        a32 = lambda x: np.ascontiguousarray(x, dtype=np.int32)
+        kind, to, leader, number = a32(kind), a32(to), a32(leader), a32(number)
+        bo, br, ridx = a32(ballot_ordering), a32(ballot_replica), a32(replica_index)
+        m = len(kind)
+        seq = None if sequence_number is None else a32(sequence_number)
+        deps = np.zeros((m, self.n), np.int32) if deps is None else a32(deps)
+        dend = None if deps_values_end is None else a32(deps_values_end)
+        outcome, oseq, oend, otr, dec = (np.full(m, -9, np.int32) for _ in range(5))
+        odeps = np.full((m, self.n), -9, np.int32)
+        nd = np.full(1, -9, np.int32)
+        p = lambda a: None if a is None else a.ctypes.data
+        st = self.L.fpx_epx_leader_replies(self._h, m, p(kind), p(to), p(leader), p(number), p(bo), p(br), p(ridx), p(seq),
+                                           p(deps), p(dend), p(outcome), p(oseq), p(odeps), p(oend), p(otr), p(dec), p(nd))
+        return st, outcome, oseq, odeps, oend, otr, dec[:max(int(nd[0]), 0)]
+
+    def leader_replies_dev(self, kind, to, leader, number, ballot_ordering, ballot_replica, replica_index, sequence_number,
+                           deps, deps_values_end, outcome=None, out_seq=None, out_deps=None, out_values_end=None,
+                           out_triple=None, decided_index=None, num_decided=None):
+        """the same on device tensors (int32), enqueued on the context's stream; the status comes with sync()"""
+        d = lambda t: None if t is None else t.data_ptr()
+        st = self.L.fpx_epx_leader_replies_dev(self._h, kind.numel(), d(kind), d(to), d(leader), d(number), d(ballot_ordering),
+                                               d(ballot_replica), d(replica_index), d(sequence_number), d(deps),
+                                               d(deps_values_end), d(outcome), d(out_seq), d(out_deps), d(out_values_end),
+                                               d(out_triple), d(decided_index), d(num_decided))
+        if st:
+            raise FpxError(st, "fpx_epx_leader_replies_dev")
+
+    def read_leader_state(self, replica, leader, number):
+        """(phase [0 when not live], ballot, avoid_fast_path, triple id, key, is_set, response mask, stored phase),
+        responses[n, n + 2] (row q: sequence number, n watermarks, values_end)"""
+        out = np.zeros(8, np.int32)
+        resp = np.zeros((self.n, self.n + 2), np.int32)
+        st = self.L.fpx_epx_read_leader_state(self._h, replica, leader, number, out.ctypes.data, resp.ctypes.data)
+        if st:
+            raise FpxError(st, "fpx_epx_read_leader_state")
+        return tuple(int(x) for x in out), resp
 
     def read_cmdlog_deps(self, replica, leader, number):
         """the dependencies kept with a command-log entry: (watermarks[n], values_end)"""

@@ -940,16 +940,57 @@ struct RecoveryDecision {
   int32_t tripleId = -1;
 };
 
+// transitionToPreAcceptPhase of one instance at one hosted replica (Replica.scala:633-729)
+struct LeadRequest {
+  Instance instance;
+  int at = 0;                  // the replica that leads it, in ballot (ballotOrdering, at)
+  int32_t ballotOrdering = 0;
+  Command command{-1, false};  // key -1 = Noop
+  int32_t tripleId = -1;
+  bool avoidFastPath = false;
+};
+// the PreAccept to send: its dependencies; fatal = the reference would have died (:662-682), nothing was done
+struct LeadResult {
+  bool fatal = false;
+  std::vector<int32_t> dependencies;
+  int32_t ownValuesEnd = 0;
+};
+// what arrives at a hosted leader, in delivery order
+struct LeaderInbound {
+  enum Kind { PreAcceptOk = 0, AcceptOk = 1, Nack = 2, DefaultToSlowPathTimer = 3 } kind = PreAcceptOk;
+  int to = 0;                            // the receiving replica
+  Instance instance;
+  Ballot ballot;                         // a Nack's largestBallot
+  int replicaIndex = 0;                  // the sender
+  int32_t sequenceNumber = 0;            // PreAcceptOk
+  std::vector<int32_t> dependencies;     // PreAcceptOk: n watermarks (empty = none)
+  int32_t ownValuesEnd = 0;
+};
+// what the reference does with it (handlePreAcceptOk :1291-1419, handleAcceptOk :1514-1565, handleNack :1577-1630, the
+// defaultToSlowPath timer :1015-1036)
+struct LeaderOutcome {
+  enum What {
+    Ignored = 0, Waiting = 1, StartDefaultToSlowPathTimer = 2, CommitFastPath = 3, TransitionToAcceptPhase = 4,
+    CommitSlowPath = 5, StartRecoverInstanceTimer = 6, NackIgnored = 7, Fatal = 8
+  } what = Ignored;
+  // CommitFastPath / TransitionToAcceptPhase / CommitSlowPath: the triple of the Commit / Accept to send
+  int32_t sequenceNumber = 0, ownValuesEnd = 0, tripleId = -1;
+  std::vector<int32_t> dependencies;
+};
+
 // The conflict indices (and, with numInstances > 0, the command logs) of the n replicas, resident in HBM.
 class PreAcceptEngine {
  public:
-  PreAcceptEngine(int f, int numKeys, int device = 0, int numInstances = 0) : n_(2 * f + 1) {
+  // leaderState (needs numInstances > 0): the engine also keeps Replica.leaderStates (Replica.scala:499), for lead() and
+  // handleReplies() -- hosted replicas leading instances among peers in other processes
+  PreAcceptEngine(int f, int numKeys, int device = 0, int numInstances = 0, bool leaderState = false) : n_(2 * f + 1) {
     if (f < 1) throw std::invalid_argument("f must be >= 1.");
     fpx_epx_config c{};
     c.num_replicas = n_;
     c.num_keys = numKeys;
     c.device = device;
     c.num_instances = numInstances;
+    c.flags = leaderState ? FPX_EPX_F_LEADER_STATE : 0u;
     check(fpx_epx_create(&c, &epx_), "fpx_epx_create");
   }
   ~PreAcceptEngine() {
@@ -1050,6 +1091,65 @@ class PreAcceptEngine {
           "Replica.handlePrepareOk");
     std::vector<RecoveryDecision> out(m);
     for (int i = 0; i < m; ++i) out[i].action = (RecoveryDecision::Action)act[i], out[i].source = src[i], out[i].tripleId = tr[i];
+    return out;
+  }
+
+  // transitionToPreAcceptPhase (Replica.scala:633-729) at requests[i].at, in vector order; instances pairwise distinct
+  std::vector<LeadResult> lead(const std::vector<LeadRequest>& requests) {
+    const int m = (int)requests.size();
+    std::vector<int32_t> leader(m), number(m), at(m), bo(m), key(m), tr(m), deps((size_t)m * n_), dend(m);
+    std::vector<uint8_t> isSet(m), avoid(m);
+    for (int i = 0; i < m; ++i) {
+      const LeadRequest& q = requests[i];
+      leader[i] = q.instance.replicaIndex, number[i] = q.instance.instanceNumber, at[i] = q.at, bo[i] = q.ballotOrdering;
+      key[i] = q.command.key, isSet[i] = q.command.isSet ? 1 : 0, tr[i] = q.tripleId, avoid[i] = q.avoidFastPath ? 1 : 0;
+    }
+    const int32_t st = fpx_epx_lead(epx_, m, leader.data(), number.data(), at.data(), bo.data(), key.data(), isSet.data(),
+                                    tr.data(), avoid.data(), deps.data(), dend.data());
+    if (st != FPX_EFATAL_PROTOCOL) check(st, "Replica.transitionToPreAcceptPhase");
+    std::vector<LeadResult> out(m);
+    for (int i = 0; i < m; ++i) {
+      out[i].dependencies.assign(deps.begin() + (size_t)i * n_, deps.begin() + (size_t)(i + 1) * n_);
+      out[i].ownValuesEnd = dend[i];
+      // a skipped message is the one whose entry still is not the PreAcceptedEntry of this ballot
+      if (st == FPX_EFATAL_PROTOCOL) {
+        const CmdLogEntry e = cmdLog(requests[i].at, requests[i].instance);
+        out[i].fatal = !(e.kind == EntryKind::PreAccepted && e.ballot == Ballot{requests[i].ballotOrdering, requests[i].at} &&
+                         e.tripleId == requests[i].tripleId);
+      }
+    }
+    return out;
+  }
+
+  // one burst of PreAcceptOk / AcceptOk / Nack messages and fired defaultToSlowPath timers, in delivery order, through
+  // ONE device call; outcome i is what handling message i alone, after the messages before it, gives.  decided (may be
+  // null): the indices whose outcome carries a triple to send, in order
+  std::vector<LeaderOutcome> handleReplies(const std::vector<LeaderInbound>& msgs, std::vector<int>* decided = nullptr) {
+    const int m = (int)msgs.size();
+    std::vector<int32_t> kind(m), to(m), leader(m), number(m), bo(m), br(m), q(m), seq(m), dend(m), deps((size_t)m * n_, 0);
+    for (int i = 0; i < m; ++i) {
+      const LeaderInbound& a = msgs[i];
+      kind[i] = (int32_t)a.kind, to[i] = a.to, leader[i] = a.instance.replicaIndex, number[i] = a.instance.instanceNumber;
+      bo[i] = a.ballot.ordering, br[i] = a.ballot.replicaIndex, q[i] = a.replicaIndex, seq[i] = a.sequenceNumber;
+      dend[i] = a.ownValuesEnd;
+      if (!a.dependencies.empty()) {
+        if ((int)a.dependencies.size() != n_) throw std::invalid_argument("one dependency watermark per replica");
+        std::copy(a.dependencies.begin(), a.dependencies.end(), deps.begin() + (size_t)i * n_);
+      }
+    }
+    std::vector<int32_t> outcome(m), oseq(m), oend(m), otr(m), dec(m), odeps((size_t)m * n_);
+    int32_t nd = 0;
+    const int32_t st = fpx_epx_leader_replies(epx_, m, kind.data(), to.data(), leader.data(), number.data(), bo.data(), br.data(),
+                                              q.data(), seq.data(), deps.data(), dend.data(), outcome.data(), oseq.data(),
+                                              odeps.data(), oend.data(), otr.data(), dec.data(), &nd);
+    if (st != FPX_EFATAL_PROTOCOL) check(st, "Replica.handlePreAcceptOk / handleAcceptOk / handleNack");
+    std::vector<LeaderOutcome> out(m);
+    for (int i = 0; i < m; ++i) {
+      out[i].what = (LeaderOutcome::What)outcome[i];
+      out[i].sequenceNumber = oseq[i], out[i].ownValuesEnd = oend[i], out[i].tripleId = otr[i];
+      out[i].dependencies.assign(odeps.begin() + (size_t)i * n_, odeps.begin() + (size_t)(i + 1) * n_);
+    }
+    if (decided) decided->assign(dec.begin(), dec.begin() + nd);
     return out;
   }
 

@@ -14,6 +14,16 @@
 //                      and `send`s what the Scala handlers would have sent.  Between hosted replicas nothing crosses the
 //                      transport: the PreAccept / PreAcceptOk / Accept / AcceptOk of a tick are the kernels' own traffic.
 //
+//                      remotePeers = true (off by default; the engine created with leaderState = true): the actor LEADS
+//                      its instances among replicas in OTHER processes, reference Replicas included.  A ClientRequest goes
+//                      through Native.epxLead (transitionToPreAcceptPhase at this replica alone) and the PreAccept out to
+//                      thriftyOtherReplicas(fastQuorumSize - 1); PreAcceptOk / AcceptOk / Nack are enqueued, and a tick
+//                      flushes them through ONE Native.epxLeaderReplies call, after which Commit goes to the other
+//                      replicas or Accept to slowQuorumSize - 1 of them.  The actor keeps the defaultToSlowPath and resend
+//                      timers (a fired defaultToSlowPath timer becomes a kind-3 event of the next burst).  Limits: single-key
+//                      commands and Noops (no multi-key lead), no Preparing phase, recovery is answered but not originated
+//                      (a Nack that asks for it, outcome 6, is logged).
+//
 // The same natives driven on wire bytes -- two conflicting commands met in different orders, differing PreAcceptOks, the
 // slow path, Accept, AcceptOk, Commit -- against the oracle: tests/test_jni_shim.py::test_an_epaxos_slow_path_commit_...
 //
@@ -50,10 +60,13 @@ class GpuEPaxosEngine[Transport <: frankenpaxos.Transport[Transport]](
     logger: Logger,
     config: Config[Transport],
     numKeys: Int = 1 << 10,
-    numInstances: Int = 1 << 20          // instances (leader, number < numInstances) the command logs hold
+    numInstances: Int = 1 << 20,         // instances (leader, number < numInstances) the command logs hold
+    leaderState: Boolean = false         // also keep Replica.leaderStates on the device (GpuEPaxosReplica's remotePeers)
 ) {
   val n: Int = config.n
-  val handle: Long = Native.epxCreateWithLog(n, numKeys, 0, numInstances)
+  val hasLeaderState: Boolean = leaderState
+  val handle: Long = if (leaderState) Native.epxCreateWithLeaderState(n, numKeys, 0, numInstances)
+                     else Native.epxCreateWithLog(n, numKeys, 0, numInstances)
   if (handle < 0) Native.check((-handle).toInt, logger)
 
   // a command's triple id is its index here (the GPU carries the int32; Accept and Commit name a triple by it)
@@ -103,7 +116,13 @@ class GpuEPaxosReplica[Transport <: frankenpaxos.Transport[Transport]](
     // true: committed instances are ordered by libfpx's device dependency graph (Native.epxExecute, 2.2 - 2.6e9 commands/s
     // at 2^20 instances per call, profiles/r06_depgraph_dev.md) instead of `dependencyGraph` (the reference's, 2 - 3e7/s);
     // the state machine, the client table and the replies stay where they are.  Default off: the reference's own graph.
-    deviceExecution: Boolean = false
+    deviceExecution: Boolean = false,
+    // true: the other replicas live in other processes; this actor leads its instances through Native.epxLead /
+    // Native.epxLeaderReplies (the engine needs leaderState = true).  Default off: all n replicas in this process.
+    remotePeers: Boolean = false,
+    thrifty: Boolean = true,             // PreAccept / Accept to a thrifty quorum (else to every other replica)
+    resendPeriod: java.time.Duration = java.time.Duration.ofSeconds(1),              // resendPreAccepts / resendAccepts
+    defaultToSlowPathPeriod: java.time.Duration = java.time.Duration.ofSeconds(1)
 ) extends Actor(address, transport, logger) {
   override type InboundMessage = ReplicaInbound
   override val serializer = ReplicaInboundSerializer
@@ -251,6 +270,10 @@ class GpuEPaxosReplica[Transport <: frankenpaxos.Transport[Transport]](
       case Request.Accept(r)        => enqueue(accepts, (src, r))
       case Request.Prepare(r)       => enqueue(prepares, (src, r))
       case Request.Commit(r)        => enqueue(commits, r)   // from a replica outside this process (Replica.handleCommit :1567)
+      case Request.PreAcceptOk(r) if remotePeers =>
+        enqueue(leaderInbox, LeaderEvent(0, r.instance, r.ballot, r.replicaIndex, r.sequenceNumber, Some(r.dependencies)))
+      case Request.AcceptOk(r) if remotePeers => enqueue(leaderInbox, LeaderEvent(1, r.instance, r.ballot, r.replicaIndex, 0, None))
+      case Request.Nack(r) if remotePeers     => enqueue(leaderInbox, LeaderEvent(2, r.instance, r.largestBallot, index, 0, None))
       case Request.PreAcceptOk(_) | Request.AcceptOk(_) | Request.PrepareOk(_) | Request.Nack(_) =>
         // replies to a leader role: between hosted replicas they never leave the device; from a replica outside, they
         // belong to a reference Replica that originated the round (see the scope note above)
@@ -266,7 +289,121 @@ class GpuEPaxosReplica[Transport <: frankenpaxos.Transport[Transport]](
       // the own-leader column carries the explicit ids number + 1 .. valuesEnd - 1 (dependencies.subtractOne, :582)
       frankenpaxos.compact.IntPrefixSetProto(watermark = w(l), value = if (l == own && valuesEnd > 0) (number + 1 until valuesEnd) else Seq())))
 
+  // ---- remotePeers: the leader half.  What the device keeps is Replica.leaderStates; what stays here is what only an actor
+  // can hold -- the timers of an instance being led and the messages they re-send.
+  private case class LeaderEvent(kind: Int, instance: Instance, ballot: Ballot, replicaIndex: Int, sequenceNumber: Int,
+                                 dependencies: Option[InstancePrefixSetProto])
+  private class Leading(val ballot: Ballot, val triple: Int, var resend: Transport#Timer, var slowPath: Option[Transport#Timer])
+  private val leaderInbox = mutable.Buffer[LeaderEvent]()
+  private val leading = mutable.Map[Instance, Leading]()
+  private def otherReplicas: Seq[Int] = (1 until n).map(d => (index + d) % n)
+  private def thriftyOtherReplicas(k: Int): Seq[Int] = if (thrifty) otherReplicas.take(k) else otherReplicas   // :556-563
+  private def resendTimer(name: String, msg: ReplicaInbound): Transport#Timer = {                               // :996-1013, 1038-1051
+    lazy val t: Transport#Timer = timer(name, resendPeriod, () => { otherReplicas.foreach(replicas(_).send(msg)); t.start() })
+    t.start()
+    t
+  }
+  private def stopLeading(instance: Instance): Unit =                                                            // stopTimers :618-630
+    leading.remove(instance).foreach { l => l.resend.stop(); l.slowPath.foreach(_.stop()) }
+  // a PreAccept / Accept / Prepare of a higher ballot takes the instance away (:1239-1242, 1480-1483, 1645-1648); the device
+  // sees it in the command-log entry the message moved, the timers are stopped here
+  private def ballotLt(a: Ballot, b: Ballot): Boolean =
+    a.ordering < b.ordering || (a.ordering == b.ordering && a.replicaIndex < b.replicaIndex)
+  private def yieldTo(instance: Instance, ballot: Ballot): Unit =
+    if (leading.get(instance).exists(l => ballotLt(l.ballot, ballot))) stopLeading(instance)
+
+  // ClientRequests, led at THIS replica alone: transitionToPreAcceptPhase (:633-729) through Native.epxLead
+  private def leadRequests(): Unit = {
+    val m = requests.size
+    logger.check(engine.hasLeaderState)
+    val leader = Array.fill(m)(index); val number = new Array[Int](m); val key = new Array[Int](m); val isSet = new Array[Byte](m)
+    val first = engine.triples.size
+    for (((_, r), i) <- requests.zipWithIndex) {
+      number(i) = engine.nextNumber(index); engine.nextNumber(index) += 1
+      val (k, set) = engine.classify(r.command)
+      if (k.length != 1) logger.fatal("GpuEPaxosReplica(remotePeers): single-key commands only; a multi-key lead is not built.")
+      key(i) = k(0); isSet(i) = if (set) 1 else 0
+      engine.triples += CommandOrNoop().withCommand(r.command)
+    }
+    val deps = new Array[Int](m * n); val ends = new Array[Int](m)
+    val st = Native.epxLead(engine.handle, m, n, leader, number, Array.fill(m)(index), Array.fill(m)(0), key, isSet,
+                            Array.tabulate(m)(first + _), new Array[Byte](m), deps, ends)
+    if (st == 9) logger.fatal("transitionToPreAcceptPhase: the instance is committed or known in a larger ballot (:662-682).")
+    Native.check(st, logger)
+    val ballot = Ballot(0, index)                                                                               // defaultBallot :453
+    for (i <- 0 until m) {
+      val instance = Instance(index, number(i))
+      val preAccept = ReplicaInbound().withPreAccept(PreAccept(instance = instance, ballot = ballot,
+        commandOrNoop = engine.triples(first + i), sequenceNumber = 0,
+        dependencies = prefixSet(deps.slice(i * n, (i + 1) * n), index, ends(i), number(i))))
+      thriftyOtherReplicas(config.fastQuorumSize - 1).foreach(replicas(_).send(preAccept))                      // :705-706
+      leading(instance) = new Leading(ballot, first + i, resendTimer(s"resendPreAccepts $instance $ballot", preAccept), None)
+    }
+    requests.clear()
+  }
+
+  // the burst's PreAcceptOks, AcceptOks, Nacks and fired defaultToSlowPath timers: ONE device call, then what the handlers
+  // would have sent
+  private def flushLeaderReplies(): Unit = {
+    val k = leaderInbox.size
+    val ev = leaderInbox.toArray
+    val zeros = Array.fill(n)(0)
+    val deps = ev.flatMap(e => e.dependencies.map(watermarks).getOrElse(zeros))
+    val ends = ev.map(e => e.dependencies.map(d => ownEnd(e.instance, d)).getOrElse(0))
+    val outcome = new Array[Int](k); val triple = new Array[Int](3 * k); val outDeps = new Array[Int](k * n)
+    val decided = new Array[Int](k + 1)
+    val st = Native.epxLeaderReplies(engine.handle, k, n, ev.map(_.kind), Array.fill(k)(index), ev.map(_.instance.replicaIndex),
+                                     ev.map(_.instance.instanceNumber), ev.map(_.ballot.ordering), ev.map(_.ballot.replicaIndex),
+                                     ev.map(_.replicaIndex), ev.map(_.sequenceNumber), deps, ends, outcome, triple, outDeps, decided)
+    leaderInbox.clear()
+    if (st == 9) logger.fatal("a reply in a ballot above the one led in (logger.checkLt :1333, :1550), or a defaultToSlowPath " +
+                              "timer outside the pre-accept phase (:1024-1028).")
+    Native.check(st, logger)
+    for (i <- 0 until k) outcome(i) match {
+      case 2 =>                                                                                                 // :1353-1364
+        val instance = ev(i).instance
+        leading.get(instance).foreach { l =>
+          val t = timer(s"defaultToSlowPath $instance", defaultToSlowPathPeriod,
+                        () => enqueue(leaderInbox, LeaderEvent(3, instance, l.ballot, index, 0, None)))
+          t.start(); l.slowPath = Some(t)
+        }
+      case 6 => logger.debug(s"GpuEPaxosReplica: Nack for ${ev(i).instance} in a larger ballot; recovery is not originated here.")
+      case _ => ()
+    }
+    for (j <- 1 to decided(0)) {
+      val i = decided(j)
+      val instance = ev(i).instance
+      val (l, x) = (instance.replicaIndex, instance.instanceNumber)
+      val w = outDeps.slice(i * n, (i + 1) * n); val end = triple(k + i); val id = triple(2 * k + i)
+      val dependencies = prefixSet(w, l, end, x)
+      if (outcome(i) == 4) {                                                                                    // transitionToAcceptPhase :765-792
+        leading.get(instance).foreach { led =>
+          led.resend.stop(); led.slowPath.foreach(_.stop()); led.slowPath = None
+          val accept = ReplicaInbound().withAccept(Accept(instance = instance, ballot = led.ballot, commandOrNoop = engine.triples(id),
+                                                          sequenceNumber = triple(i), dependencies = dependencies))
+          thriftyOtherReplicas(config.slowQuorumSize - 1).foreach(replicas(_).send(accept))
+          led.resend = resendTimer(s"resendAccepts $instance ${led.ballot}", accept)
+        }
+        engine.tripleDeps(id) = (w, end)
+      } else {                                                                                                  // commit :815-860
+        stopLeading(instance)
+        engine.depsOf((l, x)) = (w, end)
+        val commit = Commit(instance = instance, commandOrNoop = engine.triples(id), sequenceNumber = triple(i), dependencies = dependencies)
+        otherReplicas.foreach(replicas(_).send(ReplicaInbound().withCommit(commit)))
+        learnCommit(instance, commit.commandOrNoop, commit.dependencies)
+      }
+    }
+    if (decided(0) > 0) executeGraph()
+  }
+
   private def flushTick(): Unit = {
+    if (remotePeers) {
+      if (requests.nonEmpty) leadRequests()
+      for (c <- commits) stopLeading(c.instance)                                                                // commit :822, :831
+      for ((_, p) <- preAccepts) yieldTo(p.instance, p.ballot)
+      for ((_, a) <- accepts) yieldTo(a.instance, a.ballot)
+      for ((_, p) <- prepares) yieldTo(p.instance, p.ballot)
+    }
     // ---- the burst's client requests, led by THIS replica: one pre-accept tick (epaxos/Replica.scala:1121-1157,
     // 633-729, 1159-1419).  The tick's delivery order at every replica is the arrival order here; the PreAccept goes to
     // all other replicas (ThriftySystem.NotThrifty, :83), the first n - 2 answers are counted (:1376)
@@ -464,6 +601,9 @@ class GpuEPaxosReplica[Transport <: frankenpaxos.Transport[Transport]](
       }
       prepares.clear()
     }
+    // ---- replies to the instances this replica leads (remotePeers), after the burst's PreAccepts / Accepts / Prepares /
+    // Commits have moved the command log: a reply for an instance that was taken away finds its leader state gone
+    if (leaderInbox.nonEmpty) flushLeaderReplies()
     queued = 0
   }
 

@@ -194,6 +194,26 @@ object Native {
                                  tripleId: Array[Int], depsIn: Array[Int], depsInValuesEnd: Array[Int],
                                  targetMask: Array[Byte], replies: Array[Byte], nackBallot: Array[Int],
                                  replyDeps: Array[Int], replyEndTriple: Array[Int]): Int
+  // ---- the leader half of an instance (include/fpx.h, FPX_EPX_F_LEADER_STATE): a context that also keeps
+  // Replica.leaderStates, for replicas that lead among peers in other processes
+  @native def epxCreateWithLeaderState(numReplicas: Int, numKeys: Int, device: Int, numInstances: Int): Long
+  // transitionToPreAcceptPhase at replica at(i) in ballot (ballotOrdering(i), at(i)) (epaxos/Replica.scala:633-729), key -1 =
+  // Noop; deps (m x n) / depsValuesEnd (m): the dependencies of the PreAccept to send.  9 (FPX_EFATAL_PROTOCOL): a message
+  // the reference would have died on was skipped
+  @native def epxLead(handle: Long, m: Int, numReplicas: Int, leader: Array[Int], number: Array[Int], at: Array[Int],
+                      ballotOrdering: Array[Int], key: Array[Int], isSet: Array[Byte], tripleId: Array[Int],
+                      avoidFastPath: Array[Byte], deps: Array[Int], depsValuesEnd: Array[Int]): Int
+  // one burst of PreAcceptOk (kind 0) / AcceptOk (1) / Nack (2) messages and fired defaultToSlowPath timers (3) at hosted
+  // leaders, in delivery order (handlePreAcceptOk :1291-1419, handleAcceptOk :1514-1565, handleNack :1577-1630).  outcome (m):
+  // 0 ignored, 1 waiting, 2 start the defaultToSlowPath timer, 3 fast commit, 4 Accept phase, 5 slow commit, 6 Nack: start
+  // the recover-instance timer, 7 Nack ignored, 8 skipped (fatal in the reference); triple = sequence number | values end |
+  // triple id (3 x m) and outDeps (m x n): the triple of the Commit / Accept to send for 3 / 4 / 5; decided (m + 1): how
+  // many messages have such an outcome, then their indices
+  @native def epxLeaderReplies(handle: Long, m: Int, numReplicas: Int, kind: Array[Int], to: Array[Int], leader: Array[Int],
+                               number: Array[Int], ballotOrdering: Array[Int], ballotReplica: Array[Int],
+                               replicaIndex: Array[Int], sequenceNumber: Array[Int], deps: Array[Int],
+                               depsValuesEnd: Array[Int], outcome: Array[Int], triple: Array[Int], outDeps: Array[Int],
+                               decided: Array[Int]): Int
   // the multi-key forms of epxPreaccept / epxAccept / epxHandleCommit / epxHandlePreaccept: command i's keys are
   // keys(keyOffsets(i) until keyOffsets(i + 1)) (keyOffsets: m + 1 entries from 0), everything else as above
   @native def epxPreacceptMk(handle: Long, m: Int, numReplicas: Int, leader: Array[Int],

@@ -739,6 +739,84 @@ JNIEXPORT jint JNICALL Java_frankenpaxos_gpu_Native_epxHandlePreaccept(
   return st;
 }
 
+/* ---- the leader half of an instance (FPX_EPX_F_LEADER_STATE, include/fpx.h): hosted replicas among reference peers ------- */
+JNIEXPORT jlong JNICALL Java_frankenpaxos_gpu_Native_epxCreateWithLeaderState(JNIEnv* env, jclass cls, jint numReplicas,
+                                                                              jint numKeys, jint device, jint numInstances) {
+  fpx_epx_config cfg = {numReplicas, numKeys, device, FPX_EPX_F_LEADER_STATE, numInstances};
+  fpx_epx* e = NULL;
+  int32_t st = fpx_epx_create(&cfg, &e);
+  return st == FPX_OK ? (jlong)(intptr_t)e : -(jlong)st;
+}
+
+/* transitionToPreAcceptPhase at replica at[i] (epaxos/Replica.scala:633-729): key -1 = Noop; deps m x n and depsValuesEnd m
+ * (out, may be null) = the dependencies of the PreAccept to send */
+JNIEXPORT jint JNICALL Java_frankenpaxos_gpu_Native_epxLead(JNIEnv* env, jclass cls, jlong h, jint m, jint numReplicas,
+                                                            jintArray leader, jintArray number, jintArray at,
+                                                            jintArray ballotOrdering, jintArray key, jbyteArray isSet,
+                                                            jintArray tripleId, jbyteArray avoidFastPath, jintArray deps,
+                                                            jintArray depsValuesEnd) {
+  if (m < 0 || numReplicas < 3 || !epx_n_is(h, numReplicas)) return FPX_EINVAL;
+  if (m == 0) return FPX_OK;
+  const jlong mn = (jlong)m * numReplicas;
+  if (!has(env, leader, m) || !has(env, number, m) || !has(env, at, m) || !has(env, ballotOrdering, m) || !has(env, key, m) ||
+      !has(env, isSet, m) || !has(env, tripleId, m) || !has(env, avoidFastPath, m) || !opt(env, deps, mn) ||
+      !opt(env, depsValuesEnd, m))
+    return FPX_EINVAL;
+  jint *l = in_ints(env, leader, m), *nu = in_ints(env, number, m), *a = in_ints(env, at, m),
+       *bo = in_ints(env, ballotOrdering, m), *k = in_ints(env, key, m), *tr = in_ints(env, tripleId, m);
+  jbyte *is = in_bytes(env, isSet, m), *av = in_bytes(env, avoidFastPath, m);
+  jint *d = out_buf(deps, mn, 4), *de = out_buf(depsValuesEnd, m, 4);
+  int32_t st = (!l || !nu || !a || !bo || !k || !tr || !is || !av || (deps && !d) || (depsValuesEnd && !de))
+                   ? FPX_ENOMEM
+                   : fpx_epx_lead((fpx_epx*)(intptr_t)h, m, l, nu, a, bo, k, (const uint8_t*)is, tr, (const uint8_t*)av, d, de);
+  if (st == FPX_OK || st == FPX_EFATAL_PROTOCOL) {
+    put_ints(env, deps, mn, d);
+    put_ints(env, depsValuesEnd, m, de);
+  }
+  free(l); free(nu); free(a); free(bo); free(k); free(tr); free(is); free(av); free(d); free(de);
+  return st;
+}
+
+/* one burst of PreAcceptOk (0) / AcceptOk (1) / Nack (2) messages and fired defaultToSlowPath timers (3), in delivery order
+ * (fpx_epx_leader_replies).  deps m x n.  Out (each may be null): outcome m; triple = outSeq | outValuesEnd | outTriple (3 x m);
+ * outDeps m x n; decided m + 1 = the number of decided messages, then their indices */
+JNIEXPORT jint JNICALL Java_frankenpaxos_gpu_Native_epxLeaderReplies(
+    JNIEnv* env, jclass cls, jlong h, jint m, jint numReplicas, jintArray kind, jintArray to, jintArray leader, jintArray number,
+    jintArray ballotOrdering, jintArray ballotReplica, jintArray replicaIndex, jintArray sequenceNumber, jintArray deps,
+    jintArray depsValuesEnd, jintArray outcome, jintArray triple, jintArray outDeps, jintArray decided) {
+  if (m < 0 || numReplicas < 3 || !epx_n_is(h, numReplicas)) return FPX_EINVAL;
+  const jlong mn = (jlong)m * numReplicas;
+  if (!opt(env, decided, (jlong)m + 1)) return FPX_EINVAL;
+  if (m == 0) {
+    const jint zero = 0;
+    if (decided) (*env)->SetIntArrayRegion(env, decided, 0, 1, &zero);
+    return FPX_OK;
+  }
+  if (!has(env, kind, m) || !has(env, to, m) || !has(env, leader, m) || !has(env, number, m) || !has(env, ballotOrdering, m) ||
+      !has(env, ballotReplica, m) || !has(env, replicaIndex, m) || !opt(env, sequenceNumber, m) || !has(env, deps, mn) ||
+      !opt(env, depsValuesEnd, m) || !opt(env, outcome, m) || !opt(env, triple, 3 * (jlong)m) || !opt(env, outDeps, mn))
+    return FPX_EINVAL;
+  jint *kd = in_ints(env, kind, m), *t = in_ints(env, to, m), *l = in_ints(env, leader, m), *nu = in_ints(env, number, m),
+       *bo = in_ints(env, ballotOrdering, m), *br = in_ints(env, ballotReplica, m), *q = in_ints(env, replicaIndex, m),
+       *d = in_ints(env, deps, mn);
+  jint* sq = sequenceNumber ? in_ints(env, sequenceNumber, m) : NULL;
+  jint* de = depsValuesEnd ? in_ints(env, depsValuesEnd, m) : NULL;
+  jint *oc = out_buf(outcome, m, 4), *tp = out_buf(triple, 3 * (jlong)m, 4), *od = out_buf(outDeps, mn, 4),
+       *dc = out_buf(decided, (jlong)m + 1, 4);
+  int32_t st = (!kd || !t || !l || !nu || !bo || !br || !q || !d || (sequenceNumber && !sq) || (depsValuesEnd && !de) ||
+                (outcome && !oc) || (triple && !tp) || (outDeps && !od) || (decided && !dc))
+                   ? FPX_ENOMEM
+                   : fpx_epx_leader_replies((fpx_epx*)(intptr_t)h, m, kd, t, l, nu, bo, br, q, sq, d, de, oc, tp,
+                                            od, tp ? tp + m : NULL, tp ? tp + 2 * (size_t)m : NULL, dc ? dc + 1 : NULL, dc);
+  if (st == FPX_OK || st == FPX_EFATAL_PROTOCOL) {
+    put_ints(env, outcome, m, oc); put_ints(env, triple, 3 * (jlong)m, tp); put_ints(env, outDeps, mn, od);
+    if (dc) put_ints(env, decided, (jlong)dc[0] + 1, dc);
+  }
+  free(kd); free(t); free(l); free(nu); free(bo); free(br); free(q); free(d); free(sq); free(de); free(oc); free(tp); free(od);
+  free(dc);
+  return st;
+}
+
 /* ---- multi-key get / set commands (the _mk entry points): keyOffsets m + 1, keys keyOffsets[m] (fpx.h) -------------- */
 /* copies the key lists: 0 = a list the library may look at (it checks the rest), else FPX_EINVAL / FPX_ENOMEM */
 static int32_t in_key_lists(JNIEnv* env, jint m, jintArray keyOffsets, jintArray keys, jint** off, jint** k) {

@@ -876,6 +876,120 @@ int32_t fpx_epx_handle_commit_mk(fpx_epx* epx, int32_t m, const int32_t* leader,
                                  const int32_t* triple_id, const int32_t* key_offsets, const int32_t* keys,
                                  const uint8_t* is_set, const int32_t* deps, const int32_t* deps_values_end,
                                  const uint8_t* target_mask);
+/* ---- the leader half of an instance: hosted replicas that lead among peers in other processes ---------------------
+ * FPX_EPX_F_LEADER_STATE in fpx_epx_config.flags (valid only with num_instances > 0, and n * n * num_instances <= 2^31;
+ * FPX_EINVAL at fpx_epx_create otherwise): the context keeps Replica.leaderStates (epaxos/Replica.scala:499) per replica and
+ * instance beside the command log -- the phase (none / PreAccepting / Accepting; Preparing stays with fpx_epx_prepare and
+ * fpx_epx_handle_prepare_oks), the ballot, avoidFastPath, the triple id and the command's key / is_set, who has answered,
+ * for PreAccepting every response's sequence number and dependencies, for Accepting the triple's.  16 + 4 n (n + 2) bytes
+ * per (replica, leader, number): 76 / 156 / 268 B at n = 3 / 5 / 7, n * n * num_instances of them.  Without the flag nothing
+ * of it is allocated, the three calls below are FPX_EINVAL and every other call behaves as it always did.
+ *
+ * The reference drops leaderStates(instance) when a PreAccept, Accept or Prepare of a higher ballot arrives (:1239-1242,
+ * 1480-1483, 1645-1648) or the instance is committed (:831).  The kernels of those messages do not know about leader
+ * state; in each of these cases the replica's own command-log entry ends committed or with a ballot above the one led in,
+ * so a leader state is LIVE exactly while the entry at that replica is not committed and still carries the state's ballot
+ * both as ballot and as vote ballot.  fpx_epx_leader_replies tests that (one gather per instance) before it looks at a
+ * state; a state that is not live counts as none.  (fpx_epx_accept PROPOSED by the hosted replica itself in a higher ballot
+ * -- a recovery it originates -- moves the entry the same way and so ends the state too, where the reference would replace
+ * it by Accepting in the new ballot: originating recovery is outside the leader state.)
+ *
+ * fpx_epx_lead: transitionToPreAcceptPhase (:633-729) at ONE replica.  Message i: instance (leader[i], number[i]) led by
+ *   replica at[i] in ballot (ballot_ordering[i], at[i]), command key[i] / is_set[i] (key -1 = Noop), CommandTriple id
+ *   triple_id[i], avoidFastPath avoid_fast_path[i]; messages are handled in array order, instances pairwise distinct per
+ *   call (FPX_EINVAL otherwise).  At replica at[i]: dependencies = the command's conflicts in THAT replica's index, in array
+ *   order, minus the instance itself (:640-641, 569-600); PreAcceptedEntry(ballot, ballot, triple) (:684-693);
+ *   updateConflictIndex (:694); leaderStates(instance) = PreAccepting with the replica's own PreAcceptOk, sequence number 0,
+ *   as its first response (:712-728).  largestBallot is not touched (the reference does not touch it here).  It is K7's
+ *   "processed" branch with an empty deps_in, on K7's scan.
+ *   deps (m x n watermarks) / deps_values_end (m): the dependencies of the PreAccept to send, shaped like
+ *   fpx_epx_handle_preaccept's deps_in (may be NULL).  A CommittedEntry at at[i], or an entry there with a larger ballot or
+ *   vote ballot, is where the reference dies (:662-682): FPX_EFATAL_PROTOCOL, that message is skipped (its deps are zeros),
+ *   the others are applied.  FPX_EINVAL with nothing applied and no output written: the flag missing, an instance outside the
+ *   command log, a key outside the index (< -1 or >= num_keys), at[i] outside 0..n-1, ballot_ordering outside 0 .. 2^27 - 1.
+ *   Single-key commands and Noops only. */
+#define FPX_EPX_F_LEADER_STATE 1u
+int32_t fpx_epx_lead(fpx_epx* epx, int32_t m, const int32_t* leader, const int32_t* number, const int32_t* at,
+                     const int32_t* ballot_ordering, const int32_t* key, const uint8_t* is_set, const int32_t* triple_id,
+                     const uint8_t* avoid_fast_path, int32_t* deps, int32_t* deps_values_end);
+/* fpx_epx_leader_replies: ONE burst of what arrives at hosted leaders, in delivery order, the kinds interleaved, addressed
+ * to any replica of the context, answered exactly as if handled one message at a time.  Message i: kind[i], to[i] the
+ * receiving replica, the instance (leader[i], number[i]), the message's ballot (ballot_ordering[i], ballot_replica[i]) -- a
+ * Nack's largest_ballot --, replica_index[i] the sender, and for a PreAcceptOk sequence_number[i] (NULL = zeros), deps[i * n ..]
+ * (n watermarks) and deps_values_end[i] (NULL = zeros; the explicit ids number + 1 .. end - 1 of the own-leader column folded
+ * into their end, 0 = none): the arrays of fpx_wire_epaxos_decode_replica_inbound plus who received each message.
+ *   kind 0 PreAcceptOk (:1291-1419)  ignored unless the state is PreAccepting and the message's ballot is not below the
+ *          state's; a ballot ABOVE it is logger.checkLt (:1333): FPX_EFATAL_PROTOCOL, the message is skipped.  Else
+ *          responses(replicaIndex) = the message -- a later message of one sender replaces the earlier one, contents and
+ *          all; replica_index == to replaces the leader's own response -- and with old / new the response counts:
+ *            new < slowQuorumSize                                   FPX_EPX_WAITING (:1345)
+ *            !avoidFastPath, old < slow <= new, slow < fast         FPX_EPX_START_SLOW_PATH_TIMER (:1353-1364)
+ *            avoidFastPath (new >= slow)                            the slow path (:1369-1372)
+ *            new >= fastQuorumSize                                  Util.popularItems over the (sequence number,
+ *                     dependencies) of the senders other than `to`, threshold fastQuorumSize - 1 (:1382-1396): a
+ *                     candidate -> FPX_EPX_FAST_COMMIT with it (:1401-1410), none -> the slow path (:1411-1415)
+ *            anything else                                          FPX_EPX_WAITING
+ *          the slow path (preAcceptingSlowPath :796-813, transitionToAcceptPhase :732-793): FPX_EPX_ACCEPT; the triple takes
+ *          the max of the sequence numbers and the union of ALL responses' dependencies, the own one included;
+ *          AcceptedEntry(ballot, ballot, triple) WITH its dependencies at `to`; the state becomes Accepting with the
+ *          replica's own AcceptOk.
+ *   kind 1 AcceptOk (:1514-1565)     ignored unless the state is Accepting and the ballot not below the state's; above it is
+ *          logger.checkLt (:1550): FPX_EFATAL_PROTOCOL, skipped.  responses(replicaIndex) is set; slowQuorumSize of them ->
+ *          FPX_EPX_SLOW_COMMIT with the Accept's triple, else FPX_EPX_WAITING.
+ *   kind 2 Nack (:1577-1630)         largestBallot of `to` is raised in every case (:1578; fpx_epx_read_cmdlog's out[4]);
+ *          FPX_EPX_NACK_RECOVER when an instance being led has a ballot < the Nack's (the caller starts or resets its
+ *          recover-instance timer, :1623-1629), else FPX_EPX_NACK_IGNORED.
+ *   kind 3 the defaultToSlowPath timer fired (:1015-1036), a caller event placed in the burst where it fired: state
+ *          PreAccepting with at least slowQuorumSize responses -> the slow path, FPX_EPX_ACCEPT; any other state is the
+ *          reference's logger.fatal (:1024-1028), fewer responses its logger.check (:801): FPX_EFATAL_PROTOCOL, skipped.
+ *          The ballot, sender and dependency fields of a kind-3 message are not read.
+ * Any commit writes CommittedEntry(triple) with its dependencies at `to` and clears the state (:815-831); the conflict index
+ * already holds the instance (fpx_epx_lead put it, and TopOne.put is a maximum).  Dependencies are compared and united as
+ * SETS: on the own-leader column of instance (L, x) a cover of x and a cover of x + 1 are the same set (the instance itself
+ * is never a dependency, :582), so every response is brought to the form own_column gives before it is stored -- a
+ * watermark above x with no explicit ids is read as a cover.
+ * quorums (epaxos/Config.scala): slowQuorumSize = f + 1, fastQuorumSize = n - 1.
+ * Outputs per message (any may be NULL): outcome; for FPX_EPX_FAST_COMMIT / _ACCEPT / _SLOW_COMMIT the triple of the Commit
+ * or Accept the caller now sends -- out_seq, out_deps (m x n), out_values_end, out_triple (elsewhere 0 / zeros / 0 / -1);
+ * decided_index[0 .. *num_decided) = the indices of those messages in message order, compacted on the device.  A message
+ * that was skipped has outcome FPX_EPX_FATAL; the status is FPX_EFATAL_PROTOCOL and the rest of the burst is applied.
+ * FPX_EINVAL, nothing applied, no output written: the flag missing, an unknown kind, `to` outside 0..n-1, an instance outside
+ * the command log; for kinds 0 - 2 replica_index or ballot_replica outside 0..n-1 or ballot_ordering outside 0 .. 2^27 - 1;
+ * for kind 0 a negative watermark or explicit ids not above the instance (deps_values_end != 0 needs
+ * deps_values_end >= number + 2 and the own-leader watermark == number).  m < 2^30.
+ * Cost: one stable radix sort of the burst on (to, leader, number) (K5's k_rs_*, up to three passes), then ONE thread per
+ * instance walks that instance's messages in delivery order -- n - 1 of them in normal operation; k re-sent replies of one
+ * instance are k sequential steps of one thread while the other instances proceed.
+ * fpx_epx_leader_replies_dev: device pointers on the context's stream (d_num_decided too); status through fpx_epx_sync. */
+enum {
+  FPX_EPX_IGNORED = 0,               /* not leading / another phase / a stale ballot */
+  FPX_EPX_WAITING = 1,               /* recorded; no quorum yet */
+  FPX_EPX_START_SLOW_PATH_TIMER = 2, /* a slow quorum for the first time: start the defaultToSlowPath timer */
+  FPX_EPX_FAST_COMMIT = 3,           /* commit(.., informOthers = true) on the fast path: send Commit */
+  FPX_EPX_ACCEPT = 4,                /* transitionToAcceptPhase: send Accept to slowQuorumSize - 1 replicas */
+  FPX_EPX_SLOW_COMMIT = 5,           /* commit of the Accept's triple: send Commit */
+  FPX_EPX_NACK_RECOVER = 6,          /* start / reset the recover-instance timer */
+  FPX_EPX_NACK_IGNORED = 7,
+  FPX_EPX_FATAL = 8                  /* the reference would have died on this message; it was skipped */
+};
+int32_t fpx_epx_leader_replies(fpx_epx* epx, int32_t m, const int32_t* kind, const int32_t* to, const int32_t* leader,
+                               const int32_t* number, const int32_t* ballot_ordering, const int32_t* ballot_replica,
+                               const int32_t* replica_index, const int32_t* sequence_number, const int32_t* deps,
+                               const int32_t* deps_values_end, int32_t* outcome, int32_t* out_seq, int32_t* out_deps,
+                               int32_t* out_values_end, int32_t* out_triple, int32_t* decided_index, int32_t* num_decided);
+int32_t fpx_epx_leader_replies_dev(fpx_epx* epx, int32_t m, const int32_t* d_kind, const int32_t* d_to,
+                                   const int32_t* d_leader, const int32_t* d_number, const int32_t* d_ballot_ordering,
+                                   const int32_t* d_ballot_replica, const int32_t* d_replica_index,
+                                   const int32_t* d_sequence_number, const int32_t* d_deps, const int32_t* d_deps_values_end,
+                                   int32_t* d_outcome, int32_t* d_out_seq, int32_t* d_out_deps, int32_t* d_out_values_end,
+                                   int32_t* d_out_triple, int32_t* d_decided_index, int32_t* d_num_decided);
+/* readback (parity) of one leader state: out[0] = phase (0 none, 1 PreAccepting, 2 Accepting; 0 when the state is not live),
+ * out[1] = ballot, out[2] = avoidFastPath, out[3] = triple id, out[4] = key, out[5] = is_set, out[6] = who has answered (bit
+ * q), out[7] = the phase as stored (live or not); responses (may be NULL) n rows of n + 2 ints: row q = sequence number,
+ * n watermarks, values_end of what replica q answered (meaningful for the bits of out[6]; Accepting: row `replica` holds
+ * the triple's). */
+int32_t fpx_epx_read_leader_state(fpx_epx* epx, int32_t replica, int32_t leader, int32_t number, int32_t out[8],
+                                  int32_t* responses);
 /* one command-log entry: out[0..4] = kind, ballot, voteBallot, triple id, the replica's largestBallot */
 int32_t fpx_epx_read_cmdlog(fpx_epx* epx, int32_t replica, int32_t leader, int32_t number, int32_t out[5]);
 /* the dependencies kept with that entry: deps[n] watermarks (deps[0] = -1: known by triple id only), *values_end */
