@@ -22,12 +22,11 @@
 //
 //   k_ai_keys     thread / message: checks the message (kind, index, slot, round, the slot's group) and writes the sort
 //                 key: its entry, or E for a message that is skipped
-//   k_ri_hist, k_ai_hscan, k_ri_scatter   a stable LSD radix sort by that key, RI_RADIX_BITS bits per pass over the bits
-//                 of E: rank by position, never an atomic cursor.  The count and scatter passes are fpx_replica_inbox.hpp's
-//                 as they are; the scan of the counts takes several counts per thread (all n messages are sorted here)
+//   k_sort_count, k_sort_scan, k_sort_scatter   (fpx_burst_sort.hpp) a stable LSD radix sort by that key over the bits of
+//                 E: rank by position, never an atomic cursor
 //   k_ai_tilemax<0>, k_ai_tilescan   workgroup / tile of AI_TILE positions: the tile's largest round word; then one
 //                 workgroup, AI_SCAN_THREADS tiles per step with a carry: the exclusive running maximum over the tiles
-//                 (the shape of k_ri_tilemax / k_ri_tilescan, on 64-bit words)
+//                 (the shape of k_ri_tilemax / k_ri_tilescan of fpx_replica_inbox.hpp, on 64-bit words)
 //   k_ai_accept   workgroup / tile: the round every message meets, accept or Nack, the replies of Phase1a / Phase2a; an
 //                 accepted Phase2a bids for its cell in the claim table with atomicMax of its index; the last message of
 //                 a segment leaves the acceptor's new round in fin_round
@@ -45,16 +44,17 @@
 #include <limits.h>
 
 #include "../../include/fpx_wire.h"
-#include "fpx_replica_inbox.hpp"
+#include "fpx_burst_sort.hpp"
+#include "fpx_tally_msgs.hpp"
 
 namespace fpx {
 
-constexpr int AI_TILE = 256;           // sorted positions per tile (one per thread)
+constexpr int AI_TILE = BURST_TILE;    // sorted positions per tile (one per thread)
 constexpr int AI_SCAN_THREADS = 1024;  // tiles per step of k_ai_tilescan
 constexpr unsigned long long AI_EMPTY = ~0ull;
 
-// words of AcceptorInbox::hdr (AI_M is the sort's length word: RiSort reads hdr[RI_M])
-enum { AI_OK = 0, AI_M = RI_M, AI_HDR_WORDS = 8 };
+// words of AcceptorInbox::hdr (AI_M is the sort's length word)
+enum { AI_OK = 0, AI_M = 2, AI_HDR_WORDS = BURST_HDR_WORDS };
 
 struct AcceptorInbox {
   int32_t n, E;  // E = ngroups * R: the number of entries, and the sort key of a skipped message
@@ -116,45 +116,6 @@ __global__ void __launch_bounds__(256) k_ai_keys(const Geom g, const State st, c
   key0[i] = key, val0[i] = i;
 }
 
-// k_ri_hscan for a sort over EVERY message of a burst: the digit-major counts are RI_RADIX per 256 messages (131 072 words at
-// 2^21 messages), and one workgroup that takes a count per thread and step spends longer on them than any other pass
-// of the call (profiles/acceptor_inbox.md).  Here a thread takes AI_HSCAN_PER consecutive counts a step.
-constexpr int AI_HSCAN_PER = 8;
-__global__ void __launch_bounds__(1024) k_ai_hscan(const RiSort a) {
-  __shared__ int wtot[16];
-  __shared__ int carry;
-  const int m = a.hdr[RI_M], tiles = (m + RI_SORT_TILE - 1) / RI_SORT_TILE;
-  const long long len = (long long)tiles * RI_RADIX;
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-  if (t == 0) carry = 0;
-  __syncthreads();
-  for (long long base = 0; base < len; base += 1024 * AI_HSCAN_PER) {
-    const long long b0 = base + (long long)t * AI_HSCAN_PER;
-    int v[AI_HSCAN_PER], sum = 0;
-#pragma unroll
-    for (int j = 0; j < AI_HSCAN_PER; ++j) v[j] = b0 + j < len ? a.hist[b0 + j] : 0, sum += v[j];
-    int inc = sum;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const int o = __shfl_up(inc, d);
-      if (lane >= d) inc += o;
-    }
-    if (lane == 63) wtot[wave] = inc;
-    __syncthreads();
-    int before = carry;
-    for (int w = 0; w < wave; ++w) before += wtot[w];
-    int at = before + inc - sum;
-#pragma unroll
-    for (int j = 0; j < AI_HSCAN_PER; ++j) {
-      if (b0 + j < len) a.hist[b0 + j] = at;
-      at += v[j];
-    }
-    __syncthreads();
-    if (t == 1023) carry = before + inc;
-    __syncthreads();
-  }
-}
-
 // what position p contributes to the running maximum: MODE 0 the round of a Phase1a / Phase2a, MODE 1 the slot of an
 // accepted Phase2a, each + 1 under the position's key (0 = nothing); MODE 2 is MODE 0 for a Mencius acceptor, whose
 // Phase2aNoopRanges move the round too (fpx_mencius_acceptor_inbox.hpp)
@@ -176,74 +137,20 @@ __global__ void __launch_bounds__(256) k_ai_tilemax(const AcceptorInbox b) {
   __shared__ long long w[4];
   const int ntiles = (b.n + AI_TILE - 1) / AI_TILE;
   for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-    long long v = ai_word<MODE>(b, tile * AI_TILE + (int)threadIdx.x);
-#pragma unroll
-    for (int k = 1; k < 64; k <<= 1) {
-      const long long o = __shfl_xor(v, k);
-      v = o > v ? o : v;
-    }
-    if ((threadIdx.x & 63) == 0) w[threadIdx.x >> 6] = v;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      long long r = w[0];
-      for (int j = 1; j < 4; ++j) r = w[j] > r ? w[j] : r;
-      b.tile[tile] = r;
-    }
-    __syncthreads();
+    const long long m = block_reduce<ScanMax, 256>(ai_word<MODE>(b, tile * AI_TILE + (int)threadIdx.x), w);
+    if (threadIdx.x == 0) b.tile[tile] = m;
   }
 }
 
 // the exclusive running maximum over the tiles, one workgroup; also freezes "the burst is applied" for the kernels behind
 __global__ void __launch_bounds__(AI_SCAN_THREADS) k_ai_tilescan(const State st, const AcceptorInbox b) {
-  __shared__ long long wtot[AI_SCAN_THREADS / 64];
-  __shared__ long long carry;
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-  if (t == 0) {
-    carry = -1;
-    b.hdr[AI_OK] = st.status[ST_ABORT] == 0 && st.status[ST_MSG_BAD] == 0 ? 1 : 0;
-  }
-  __syncthreads();
-  const int ntiles = (b.n + AI_TILE - 1) / AI_TILE;
-  for (int base = 0; base < ntiles; base += AI_SCAN_THREADS) {
-    const int ti = base + t;
-    long long inc = ti < ntiles ? b.tile[ti] : -1;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const long long o = __shfl_up(inc, d);
-      if (lane >= d && o > inc) inc = o;
-    }
-    long long excl = __shfl_up(inc, 1);  // the wavefront's earlier lanes
-    if (lane == 0) excl = -1;
-    if (lane == 63) wtot[wave] = inc;
-    __syncthreads();
-    long long before = carry;
-    for (int w = 0; w < wave; ++w) before = wtot[w] > before ? wtot[w] : before;
-    if (ti < ntiles) b.tile[ti] = excl > before ? excl : before;
-    __syncthreads();
-    if (t == AI_SCAN_THREADS - 1) carry = inc > before ? inc : before;
-    __syncthreads();
-  }
+  __shared__ long long lds[SCAN_ARRAY_LDS(AI_SCAN_THREADS)];
+  if (threadIdx.x == 0) b.hdr[AI_OK] = st.status[ST_ABORT] == 0 && st.status[ST_MSG_BAD] == 0 ? 1 : 0;
+  (void)scan_array_excl<ScanMax, AI_SCAN_THREADS, 1>(b.tile, (b.n + AI_TILE - 1) / AI_TILE, lds);
 }
 
-// the largest word before this thread's position: the tile's carry and the threads before it (256 threads, all call it)
-__device__ __forceinline__ long long ai_block_excl(long long w, long long carry, long long* wtot) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  long long inc = w;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const long long o = __shfl_up(inc, d);
-    if (lane >= d && o > inc) inc = o;
-  }
-  long long excl = __shfl_up(inc, 1);
-  if (lane == 0) excl = -1;
-  if (lane == 63) wtot[wave] = inc;
-  __syncthreads();
-  long long before = carry;
-  for (int j = 0; j < wave; ++j) before = wtot[j] > before ? wtot[j] : before;
-  return excl > before ? excl : before;
-}
-
-// the running maximum of the segment of `key` before this position, started at `start` (x = ai_block_excl's result)
+// the running maximum of the segment of `key` before this position, started at `start` (x = the largest word before the
+// position: block_excl_scan over the tile, from the tile's carry)
 __device__ __forceinline__ int ai_running(long long x, int key, int start) {
   if (x < 0 || (int)(x >> 32) != key) return start;
   const int v = (int)(x & 0xffffffffll) - 1;
@@ -273,7 +180,7 @@ __device__ __forceinline__ size_t ai_cell(const Geom& g, int slot, int key) {
 __global__ void __launch_bounds__(256) k_ai_accept(const Geom g, const State st, const AcceptorInbox b) {
   __shared__ long long wtot[4];
   const int p = blockIdx.x * AI_TILE + threadIdx.x;
-  const long long x = ai_block_excl(ai_word<0>(b, p), b.tile[blockIdx.x], wtot);
+  const long long x = block_excl_scan<ScanMax, 256>(ai_word<0>(b, p), b.tile[blockIdx.x], wtot);
   if (p >= b.n) return;
   const int key = b.key[p];
   int acc = 0, tp = -1;
@@ -309,7 +216,7 @@ __global__ void __launch_bounds__(256) k_ai_accept(const Geom g, const State st,
 __global__ void __launch_bounds__(256) k_ai_reads(const Geom g, const State st, const AcceptorInbox b) {
   __shared__ long long wtot[4];
   const int p = blockIdx.x * AI_TILE + threadIdx.x;
-  const long long x = ai_block_excl(ai_word<1>(b, p), b.tile[blockIdx.x], wtot);
+  const long long x = block_excl_scan<ScanMax, 256>(ai_word<1>(b, p), b.tile[blockIdx.x], wtot);
   if (p >= b.n || b.hdr[AI_OK] == 0) return;
   const int key = b.key[p];
   if (key >= b.E) return;

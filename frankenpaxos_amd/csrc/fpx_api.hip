@@ -26,6 +26,7 @@
 #include "fpx_tally_msgs.hpp"
 #include "fpx_mencius_msgs.hpp"
 #include "fpx_replica_msgs.hpp"
+#include "fpx_burst_sort.hpp"
 #include "fpx_replica_inbox.hpp"
 #include "fpx_acceptor_inbox.hpp"
 #include "fpx_mencius_acceptor_inbox.hpp"
@@ -315,6 +316,27 @@ int grow(fpx_ctx* ctx, DevBuf* b, size_t bytes) {
   return FPX_OK;
 }
 
+// grow() for a buffer that fpx_device_bytes counts
+int grow_counted(fpx_ctx* ctx, DevBuf* b, size_t bytes) {
+  const size_t had = b->cap;
+  const int rc = grow(ctx, b, bytes);
+  ctx->bytes += (int64_t)b->cap - (int64_t)had;
+  return rc;
+}
+
+// A call's scratch, cut into arrays by `lay` (fpx_scratch.hpp): the layout runs over a null base for the size the buffer
+// must have, and again over the buffer
+template <typename S, typename Lay>
+int carve(fpx_ctx* ctx, DevBuf* buf, bool counted, S* out, Lay lay) {
+  Carver size(nullptr);
+  (void)lay(size);
+  const int rc = counted ? grow_counted(ctx, buf, size.size()) : grow(ctx, buf, size.size());
+  if (rc) return rc;
+  Carver c(buf->p);
+  *out = lay(c);
+  return FPX_OK;
+}
+
 template <typename T>
 int dalloc(fpx_ctx* ctx, T** p, size_t count) {
   HIPCHK(ctx, hipMalloc(reinterpret_cast<void**>(p), count * sizeof(T)));
@@ -472,6 +494,16 @@ void fill32(fpx_ctx* ctx, void* p, int32_t v, size_t n) {
   if (n == 0) return;
   const int grid = (int)std::max<size_t>(1, std::min<size_t>((n + 255) / 256, (size_t)ctx->num_cus * 8));
   hipLaunchKernelGGL(k_fill32, dim3(grid), dim3(256), 0, ctx->stream, (int32_t*)p, v, n);
+}
+
+// a claim array of `words` int32 that lives as long as the context: the first call allocates it, counts it and sets
+// every word to INT_MAX, its value between calls
+int claim_array(fpx_ctx* ctx, DevBuf* b, size_t words) {
+  if (b->p) return FPX_OK;
+  const int rc = grow_counted(ctx, b, words * 4);
+  if (rc) return rc;
+  fill32(ctx, b->p, INT_MAX, b->cap / 4);
+  return FPX_OK;
 }
 
 int launch_check(fpx_ctx* ctx) {
@@ -643,12 +675,7 @@ int enqueue_tally(fpx_ctx* ctx, Batch& b) {
 // the owner table, the messages' entries and the gathered rows (zeroed) of a claim / gather / tally call
 int prepare_tally_msgs(fpx_ctx* ctx, MsgBatch& b) {
   int rc;
-  if (!ctx->m_owner.p) {
-    const size_t words = (size_t)ctx->g.S * ctx->g.wp;
-    if ((rc = grow(ctx, &ctx->m_owner, words * 4))) return rc;
-    ctx->bytes += (int64_t)ctx->m_owner.cap;
-    fill32(ctx, ctx->m_owner.p, INT_MAX, ctx->m_owner.cap / 4);
-  }
+  if ((rc = claim_array(ctx, &ctx->m_owner, (size_t)ctx->g.S * ctx->g.wp))) return rc;
   if ((rc = grow(ctx, &ctx->m_entry, (size_t)b.n * 4))) return rc;
   if ((rc = grow(ctx, &ctx->m_rows, (size_t)b.n * 32))) return rc;
   b.owner = (int32_t*)ctx->m_owner.p, b.entry = (int32_t*)ctx->m_entry.p, b.row_bits = (unsigned long long*)ctx->m_rows.p;
@@ -2761,11 +2788,7 @@ int32_t fpx_mencius_proxy_phase2b_msgs_dev(fpx_ctx* ctx, int32_t n, const int32_
   if (n == 0) return FPX_OK;
   if (!d_acceptor_index || !d_slot || !d_round) return FPX_EINVAL;
   const RangeTable& rt = ctx->rt[ctx->rt_cur];
-  if (!ctx->mm_claim.p) {
-    if ((rc = grow(ctx, &ctx->mm_claim, (size_t)rt.cap * 4))) return rc;
-    ctx->bytes += (int64_t)ctx->mm_claim.cap;
-    fill32(ctx, ctx->mm_claim.p, INT_MAX, ctx->mm_claim.cap / 4);
-  }
+  if ((rc = claim_array(ctx, &ctx->mm_claim, (size_t)rt.cap))) return rc;
   MenciusMsgs b;
   memset(&b, 0, sizeof(b));
   b.m.n = n, b.m.kind = d_kind, b.m.acceptor = d_acceptor_index, b.m.slot = d_slot, b.m.round = d_round;
@@ -2989,6 +3012,22 @@ int32_t fpx_replica_chosen_noop_range(fpx_ctx* ctx, int32_t slot_start, int32_t 
   return fetch_status(ctx);
 }
 
+// the ReplicaMsgs of a burst over its carved scratch; the claim array is the context's, made by the first call
+static int replica_msgs(fpx_ctx* ctx, int32_t n, int nblk, const int32_t* d_kind, const int32_t* d_slot,
+                        const int32_t* d_slot_end, const int32_t* d_value_id, const uint8_t* d_mask,
+                        const ReplicaMsgsScratch& s, ReplicaMsgs* b) {
+  const int rc = claim_array(ctx, &ctx->rm_claim, (size_t)ctx->g.S);
+  if (rc) return rc;
+  memset(b, 0, sizeof(*b));
+  b->n = n, b->nblk = nblk;
+  b->nparts = std::max(1, std::min({nblk, ctx->num_cus * 8, LG_MAX_PARTS}));
+  b->chosen_kind = FPX_WIRE_CHOSEN, b->range_kind = FPX_WIRE_CHOSEN_NOOP_RANGE;
+  b->kind = d_kind, b->slot = d_slot, b->slot_end = d_slot_end, b->value = d_value_id, b->mask = d_mask;
+  b->claim = (int32_t*)ctx->rm_claim.p;
+  b->hdr = s.hdr, b->parts = s.parts, b->blk = s.blk, b->list = s.list, b->res = s.res;
+  return FPX_OK;
+}
+
 // mencius.Replica.handleChosen + handleChosenNoopRange for a burst in delivery order (fpx_replica_msgs.hpp): eight launches,
 // nothing read by the host in between
 int32_t fpx_replica_chosen_msgs_dev(fpx_ctx* ctx, int32_t n, const int32_t* d_kind, const int32_t* d_slot,
@@ -2998,22 +3037,12 @@ int32_t fpx_replica_chosen_msgs_dev(fpx_ctx* ctx, int32_t n, const int32_t* d_ki
   if (n == 0) return FPX_OK;
   if (!d_kind || !d_slot || !d_slot_end || !d_value_id) return FPX_EINVAL;
   int rc;
-  if (!ctx->rm_claim.p) {
-    if ((rc = grow(ctx, &ctx->rm_claim, (size_t)ctx->g.S * 4))) return rc;
-    ctx->bytes += (int64_t)ctx->rm_claim.cap;
-    fill32(ctx, ctx->rm_claim.p, INT_MAX, ctx->rm_claim.cap / 4);
-  }
+  const int nblk = (n + 255) / 256;
+  ReplicaMsgsScratch s;  // (rm_buf is not counted in fpx_device_bytes)
+  if ((rc = carve(ctx, &ctx->rm_buf, false, &s, [&](Carver& c) { return lay_replica_msgs(c, nblk, n, LG_MAX_PARTS); })))
+    return rc;
   ReplicaMsgs b;
-  memset(&b, 0, sizeof(b));
-  b.n = n, b.nblk = (n + 255) / 256;
-  b.nparts = std::max(1, std::min({b.nblk, ctx->num_cus * 8, LG_MAX_PARTS}));
-  const size_t words = (size_t)RM_HDR_WORDS + 3 * (size_t)LG_MAX_PARTS + (size_t)b.nblk + 2 * (size_t)n;
-  if ((rc = grow(ctx, &ctx->rm_buf, words * 4))) return rc;
-  b.chosen_kind = FPX_WIRE_CHOSEN, b.range_kind = FPX_WIRE_CHOSEN_NOOP_RANGE;
-  b.kind = d_kind, b.slot = d_slot, b.slot_end = d_slot_end, b.value = d_value_id, b.mask = d_mask;
-  b.claim = (int32_t*)ctx->rm_claim.p;
-  b.hdr = (int32_t*)ctx->rm_buf.p;
-  b.parts = b.hdr + RM_HDR_WORDS, b.blk = b.parts + 3 * LG_MAX_PARTS, b.list = b.blk + b.nblk, b.res = b.list + n;
+  if ((rc = replica_msgs(ctx, n, nblk, d_kind, d_slot, d_slot_end, d_value_id, d_mask, s, &b))) return rc;
   const dim3 per_msg(b.nblk), blk(256);
   const int sweep = std::min(std::max(b.nblk, ctx->num_cus), ctx->num_cus * 8);
   hipLaunchKernelGGL(k_rm_claim, per_msg, blk, 0, ctx->stream, ctx->g, ctx->st, b);
@@ -3061,43 +3090,24 @@ int32_t fpx_replica_inbox_dev(fpx_ctx* ctx, int32_t n, const int32_t* d_kind, co
   if (n == 0 && nout == 0) return FPX_OK;
   if (n > 0 && (!d_kind || !d_slot || !d_value_id)) return FPX_EINVAL;
   int rc;
-  if (!ctx->rm_claim.p) {
-    if ((rc = grow(ctx, &ctx->rm_claim, (size_t)ctx->g.S * 4))) return rc;
-    ctx->bytes += (int64_t)ctx->rm_claim.cap;
-    fill32(ctx, ctx->rm_claim.p, INT_MAX, ctx->rm_claim.cap / 4);
-  }
   const int nblk = std::max(1, (n + 255) / 256);
-  const size_t cap_n = (size_t)nblk * 256;  // >= n and >= 1
   const size_t ntiles_max = ((size_t)ctx->g.S + RI_TILE - 1) / RI_TILE;
-  const size_t words = 3 * (size_t)RM_HDR_WORDS + 3 * (size_t)LG_MAX_PARTS + (size_t)nblk + ntiles_max +
-                       (nout ? (size_t)RI_RADIX * nblk + 4 * cap_n : 0);
-  const size_t had = ctx->ri_buf.cap;
-  if ((rc = grow(ctx, &ctx->ri_buf, words * 4))) return rc;
-  ctx->bytes += (int64_t)ctx->ri_buf.cap - (int64_t)had;
+  ReplicaInboxScratch s;
+  if ((rc = carve(ctx, &ctx->ri_buf, true, &s,
+                  [&](Carver& c) { return lay_replica_inbox(c, nblk, ntiles_max, LG_MAX_PARTS, nout != 0); })))
+    return rc;
   // the Chosens: fpx_replica_msgs.hpp's kernels on a burst without ranges
   ReplicaMsgs m;
-  memset(&m, 0, sizeof(m));
-  m.n = n, m.nblk = nblk;
-  m.nparts = std::max(1, std::min({nblk, ctx->num_cus * 8, LG_MAX_PARTS}));
-  m.chosen_kind = FPX_WIRE_CHOSEN, m.range_kind = FPX_WIRE_CHOSEN_NOOP_RANGE;
-  m.kind = d_kind, m.slot = d_slot, m.slot_end = d_slot, m.value = d_value_id, m.mask = d_mask;
-  m.claim = (int32_t*)ctx->rm_claim.p;
-  m.hdr = (int32_t*)ctx->ri_buf.p;
+  if ((rc = replica_msgs(ctx, n, nblk, d_kind, d_slot, d_slot, d_value_id, d_mask, s.m, &m))) return rc;
   ReplicaInbox b;
   memset(&b, 0, sizeof(b));
   b.n = n, b.S = ctx->g.S;
   b.kind = d_kind, b.slot = d_slot, b.mask = d_mask;
-  b.claim = m.claim, b.mhdr = m.hdr, b.rhdr = b.mhdr + RM_HDR_WORDS, b.hdr = b.rhdr + RM_HDR_WORDS;
-  m.parts = b.hdr + RM_HDR_WORDS;
-  b.blk = m.parts + 3 * LG_MAX_PARTS, b.tmax = b.blk + nblk;
-  if (nout) {
-    b.hist = b.tmax + ntiles_max;
-    b.key[0] = b.hist + (size_t)RI_RADIX * nblk, b.key[1] = b.key[0] + cap_n;
-    b.val[0] = b.key[1] + cap_n, b.val[1] = b.val[0] + cap_n;
-  }
+  b.claim = m.claim, b.mhdr = m.hdr, b.rhdr = s.rhdr, b.hdr = s.hdr, b.blk = m.blk, b.tmax = s.tmax;
+  b.key0 = s.sort.key[0], b.val0 = s.sort.val[0];
   b.exec_count = d_exec_count, b.reply_slot = d_reply_slot, b.order = d_order, b.counts = d_counts;
   ReplicaMsgs r = m;  // the reads' counts through k_rm_offsets: its "number of ranges" is the number of reads
-  r.hdr = b.rhdr, r.blk = b.blk;
+  r.hdr = b.rhdr;
   const dim3 per_msg(nblk), blk(256);
   const int sweep = std::min(std::max(nblk, ctx->num_cus), ctx->num_cus * 8);
   hipLaunchKernelGGL(k_ri_claim, per_msg, blk, 0, ctx->stream, ctx->g, ctx->st, b);
@@ -3115,18 +3125,7 @@ int32_t fpx_replica_inbox_dev(fpx_ctx* ctx, int32_t n, const int32_t* d_kind, co
   hipLaunchKernelGGL(k_ri_execby, dim3(tiles_grid), blk, 0, ctx->stream, b);
   hipLaunchKernelGGL(k_ri_reads, per_msg, blk, 0, ctx->stream, b);
   // keys are 0 .. num_slots + 1: the pass count is fixed per context
-  int bits = 0;
-  while (((int64_t)ctx->g.S + 1) >> bits) ++bits;
-  const int passes = (bits + RI_RADIX_BITS - 1) / RI_RADIX_BITS;
-  for (int p = 0; p < passes; ++p) {
-    RiSort a;
-    a.hdr = b.hdr, a.hist = b.hist, a.shift = p * RI_RADIX_BITS;
-    a.key_in = b.key[p & 1], a.val_in = b.val[p & 1];
-    a.key_out = b.key[(p + 1) & 1], a.val_out = p + 1 == passes ? d_order : b.val[(p + 1) & 1];
-    hipLaunchKernelGGL(k_ri_hist, per_msg, blk, 0, ctx->stream, a);
-    hipLaunchKernelGGL(k_ri_hscan, dim3(1), dim3(1024), 0, ctx->stream, a);
-    hipLaunchKernelGGL(k_ri_scatter, per_msg, blk, 0, ctx->stream, a);
-  }
+  (void)burst_sort(ctx->stream, b.hdr + RI_M, s.sort, (int64_t)ctx->g.S + 1, nblk, d_order);
   hipLaunchKernelGGL(k_ri_finish, dim3(sweep), blk, 0, ctx->stream, ctx->g, ctx->st, b);
   return launch_check(ctx);
 }
@@ -3179,10 +3178,8 @@ static int32_t ai_claim_table(fpx_ctx* ctx, int32_t n, size_t* tsize_out) {
   size_t tsize = 1024;
   while (tsize < 2 * (size_t)n) tsize <<= 1;
   if (tsize * 8 > ctx->ai_tkey.cap) {  // a new table: every word at its between-calls value
-    const size_t had = ctx->ai_tkey.cap + ctx->ai_tval.cap;
-    if ((rc = grow(ctx, &ctx->ai_tkey, tsize * 8))) return rc;
-    if ((rc = grow(ctx, &ctx->ai_tval, tsize * 4))) return rc;
-    ctx->bytes += (int64_t)(ctx->ai_tkey.cap + ctx->ai_tval.cap) - (int64_t)had;
+    if ((rc = grow_counted(ctx, &ctx->ai_tkey, tsize * 8))) return rc;
+    if ((rc = grow_counted(ctx, &ctx->ai_tval, tsize * 4))) return rc;
     fill32(ctx, ctx->ai_tkey.p, -1, ctx->ai_tkey.cap / 4);
     fill32(ctx, ctx->ai_tval.p, -1, ctx->ai_tval.cap / 4);
   }
@@ -3190,24 +3187,16 @@ static int32_t ai_claim_table(fpx_ctx* ctx, int32_t n, size_t* tsize_out) {
   return FPX_OK;
 }
 
-// the stable radix sort of (key[0], val[0]) by entry; the result is in key[passes & 1], val[passes & 1]
-static int ai_sort_by_entry(fpx_ctx* ctx, int32_t* hdr, int32_t* hist, int32_t* const key[2], int32_t* const val[2], int E,
-                            int nblk) {
-  // keys are 0 .. E: the pass count is fixed per context
-  int bits = 0;
-  while (E >> bits) ++bits;
-  const int passes = (bits + RI_RADIX_BITS - 1) / RI_RADIX_BITS;
-  const dim3 per_tile(nblk), blk(256);
-  for (int p = 0; p < passes; ++p) {
-    RiSort a;
-    a.hdr = hdr, a.hist = hist, a.shift = p * RI_RADIX_BITS;
-    a.key_in = key[p & 1], a.val_in = val[p & 1];
-    a.key_out = key[(p + 1) & 1], a.val_out = val[(p + 1) & 1];
-    hipLaunchKernelGGL(k_ri_hist, per_tile, blk, 0, ctx->stream, a);
-    hipLaunchKernelGGL(k_ai_hscan, dim3(1), dim3(1024), 0, ctx->stream, a);
-    hipLaunchKernelGGL(k_ri_scatter, per_tile, blk, 0, ctx->stream, a);
-  }
-  return passes;
+// the part of an AcceptorInbox that both acceptor calls fill alike: the sizes, the carved scratch, the claim table
+static int acceptor_inbox_args(fpx_ctx* ctx, int32_t n, const AcceptorInboxScratch& s, AcceptorInbox* b) {
+  size_t tsize;
+  const int rc = ai_claim_table(ctx, n, &tsize);
+  if (rc) return rc;
+  b->n = n, b->E = ctx->g.ngroups * ctx->g.R;
+  b->hdr = s.hdr, b->tile = s.tile, b->accslot = s.accslot, b->tpos = s.tpos;
+  b->fin_round = s.fin_round, b->fin_slot = s.fin_slot;
+  b->tkey = (unsigned long long*)ctx->ai_tkey.p, b->tval = (int32_t*)ctx->ai_tval.p, b->tmask = (uint32_t)(tsize - 1);
+  return FPX_OK;
 }
 
 int32_t fpx_acceptor_inbox_dev(fpx_ctx* ctx, int32_t n, const int32_t* d_kind, const int32_t* d_group_index,
@@ -3223,34 +3212,20 @@ int32_t fpx_acceptor_inbox_dev(fpx_ctx* ctx, int32_t n, const int32_t* d_kind, c
   const Geom& g = ctx->g;
   const int E = g.ngroups * g.R;
   const int nblk = (n + AI_TILE - 1) / AI_TILE;
-  const size_t cap_n = (size_t)nblk * AI_TILE;
-  // [hdr | tile (64-bit) | key x 2 | val x 2 | accslot | tpos | hist | fin_round | fin_slot]
-  const size_t words = (size_t)AI_HDR_WORDS + 2 * (size_t)nblk + 6 * cap_n + (size_t)RI_RADIX * nblk + 2 * (size_t)E;
-  size_t had = ctx->ai_buf.cap;
-  if ((rc = grow(ctx, &ctx->ai_buf, words * 4))) return rc;
-  ctx->bytes += (int64_t)ctx->ai_buf.cap - (int64_t)had;
-  size_t tsize;
-  if ((rc = ai_claim_table(ctx, n, &tsize))) return rc;
+  AcceptorInboxScratch s;
+  if ((rc = carve(ctx, &ctx->ai_buf, true, &s, [&](Carver& c) { return lay_acceptor_inbox(c, n, E); }))) return rc;
   AcceptorInbox b;
   memset(&b, 0, sizeof(b));
-  b.n = n, b.E = E, b.grid_cols = grid_cols;
+  if ((rc = acceptor_inbox_args(ctx, n, s, &b))) return rc;
+  b.grid_cols = grid_cols;
   b.kind = d_kind, b.group = d_group_index, b.acceptor = d_acceptor_index, b.slot = d_slot, b.round = d_round;
   b.value = d_value_id;
-  b.hdr = (int32_t*)ctx->ai_buf.p;
-  b.tile = (long long*)(b.hdr + AI_HDR_WORDS);
-  int32_t* key[2];
-  int32_t* val[2];
-  key[0] = (int32_t*)(b.tile + nblk), key[1] = key[0] + cap_n, val[0] = key[1] + cap_n, val[1] = val[0] + cap_n;
-  b.accslot = val[1] + cap_n, b.tpos = b.accslot + cap_n;
-  int32_t* hist = b.tpos + cap_n;
-  b.fin_round = hist + (size_t)RI_RADIX * nblk, b.fin_slot = b.fin_round + E;
-  b.tkey = (unsigned long long*)ctx->ai_tkey.p, b.tval = (int32_t*)ctx->ai_tval.p, b.tmask = (uint32_t)(tsize - 1);
   b.reply_kind = d_reply_kind, b.reply_value = d_reply_value;
   const dim3 per_tile(nblk), blk(256);
   const int sweep = std::max(1, std::min(nblk, ctx->num_cus * 8));
-  hipLaunchKernelGGL(k_ai_keys, per_tile, blk, 0, ctx->stream, g, ctx->st, b, key[0], val[0]);
-  const int passes = ai_sort_by_entry(ctx, b.hdr, hist, key, val, E, nblk);
-  b.key = key[passes & 1], b.perm = val[passes & 1];
+  hipLaunchKernelGGL(k_ai_keys, per_tile, blk, 0, ctx->stream, g, ctx->st, b, s.sort.key[0], s.sort.val[0]);
+  const int at = burst_sort(ctx->stream, b.hdr + AI_M, s.sort, E, nblk);  // keys are 0 .. E
+  b.key = s.sort.key[at], b.perm = s.sort.val[at];
   hipLaunchKernelGGL(k_ai_tilemax<0>, dim3(sweep), blk, 0, ctx->stream, b);
   hipLaunchKernelGGL(k_ai_tilescan, dim3(1), dim3(AI_SCAN_THREADS), 0, ctx->stream, ctx->st, b);
   hipLaunchKernelGGL(k_ai_accept, per_tile, blk, 0, ctx->stream, g, ctx->st, b);
@@ -3312,38 +3287,22 @@ int32_t fpx_mencius_acceptor_inbox_dev(fpx_ctx* ctx, int32_t n, const int32_t* d
   const Geom& g = ctx->g;
   const int E = g.ngroups * g.R;
   const int nblk = (n + AI_TILE - 1) / AI_TILE;
-  const size_t cap_n = (size_t)nblk * AI_TILE;
-  // [hdr | tile (64-bit) | key x 2 | val x 2 | accslot | tpos | rflag | list x 5 | hist | rcnt | fin_round | fin_slot]
-  const size_t words =
-      (size_t)AI_HDR_WORDS + 2 * (size_t)nblk + 12 * cap_n + (size_t)RI_RADIX * nblk + (size_t)nblk + 2 * (size_t)E;
-  size_t had = ctx->mai_buf.cap;
-  if ((rc = grow(ctx, &ctx->mai_buf, words * 4))) return rc;
-  ctx->bytes += (int64_t)ctx->mai_buf.cap - (int64_t)had;
-  size_t tsize;
-  if ((rc = ai_claim_table(ctx, n, &tsize))) return rc;
+  MenciusAcceptorInboxScratch s;
+  if ((rc = carve(ctx, &ctx->mai_buf, true, &s, [&](Carver& c) { return lay_mencius_acceptor_inbox(c, n, E); })))
+    return rc;
   MenciusAcceptorInbox b;
   memset(&b, 0, sizeof(b));
-  b.a.n = n, b.a.E = E, b.a.grid_cols = 0;
+  if ((rc = acceptor_inbox_args(ctx, n, s.a, &b.a))) return rc;
   b.a.kind = d_kind, b.a.group = d_group_index, b.a.acceptor = d_acceptor_index, b.a.slot = d_slot, b.a.round = d_round;
   b.a.value = d_value_id, b.slot_end = d_slot_end;
-  b.a.hdr = (int32_t*)ctx->mai_buf.p;
-  b.a.tile = (long long*)(b.a.hdr + AI_HDR_WORDS);
-  int32_t* key[2];
-  int32_t* val[2];
-  key[0] = (int32_t*)(b.a.tile + nblk), key[1] = key[0] + cap_n, val[0] = key[1] + cap_n, val[1] = val[0] + cap_n;
-  b.a.accslot = val[1] + cap_n, b.a.tpos = b.a.accslot + cap_n, b.rflag = b.a.tpos + cap_n;
-  b.lent = b.rflag + cap_n, b.lq0 = b.lent + cap_n, b.lq1 = b.lq0 + cap_n, b.lround = b.lq1 + cap_n;
-  b.lidx = b.lround + cap_n;
-  int32_t* hist = b.lidx + cap_n;
-  b.rcnt = hist + (size_t)RI_RADIX * nblk;
-  b.a.fin_round = b.rcnt + nblk, b.a.fin_slot = b.a.fin_round + E;
-  b.a.tkey = (unsigned long long*)ctx->ai_tkey.p, b.a.tval = (int32_t*)ctx->ai_tval.p, b.a.tmask = (uint32_t)(tsize - 1);
+  b.rflag = s.rflag, b.rcnt = s.rcnt;
+  b.lent = s.list[0], b.lq0 = s.list[1], b.lq1 = s.list[2], b.lround = s.list[3], b.lidx = s.list[4];
   b.a.reply_kind = d_reply_kind, b.a.reply_value = d_reply_value;
   const dim3 per_tile(nblk), blk(256);
   const int sweep = std::max(1, std::min(nblk, ctx->num_cus * 8));
-  hipLaunchKernelGGL(k_mai_keys, per_tile, blk, 0, ctx->stream, g, ctx->st, b, key[0], val[0]);
-  const int passes = ai_sort_by_entry(ctx, b.a.hdr, hist, key, val, E, nblk);
-  b.a.key = key[passes & 1], b.a.perm = val[passes & 1];
+  hipLaunchKernelGGL(k_mai_keys, per_tile, blk, 0, ctx->stream, g, ctx->st, b, s.a.sort.key[0], s.a.sort.val[0]);
+  const int at = burst_sort(ctx->stream, b.a.hdr + AI_M, s.a.sort, E, nblk);  // keys are 0 .. E
+  b.a.key = s.a.sort.key[at], b.a.perm = s.a.sort.val[at];
   hipLaunchKernelGGL(k_ai_tilemax<2>, dim3(sweep), blk, 0, ctx->stream, b.a);
   hipLaunchKernelGGL(k_ai_tilescan, dim3(1), dim3(AI_SCAN_THREADS), 0, ctx->stream, ctx->st, b.a);
   hipLaunchKernelGGL(k_mai_accept, per_tile, blk, 0, ctx->stream, g, ctx->st, b);

@@ -23,7 +23,7 @@
 // cursor); the sort is stable, so one acceptor's ranges are ONE run of the list in index order, found by binary search.
 //
 //   k_mai_keys    thread / message: checks the message and writes the sort key (its entry, or E = skipped)
-//   k_ri_hist, k_ai_hscan, k_ri_scatter    the stable radix sort by entry, as in fpx_acceptor_inbox.hpp
+//   k_sort_count, k_sort_scan, k_sort_scatter   the stable radix sort by entry, as in fpx_acceptor_inbox.hpp
 //   k_ai_tilemax<2>, k_ai_tilescan         the running maximum of the rounds
 //   k_mai_accept  workgroup / tile: accept or Nack, the replies of all three kinds; an accepted Phase2a bids for its cell;
 //                 an accepted range leaves its largest owned slot + 1 (0: it owns none) for the second scan and is flagged;
@@ -55,7 +55,7 @@ struct MenciusAcceptorInbox {
   int32_t* rcnt;            // [ceil(n / AI_TILE)]  flags per tile, then their exclusive sums
   // the accepted ranges in sorted position order: entry (ascending), owned rows q0 .. q1 in steps of A, round, message
   // index (ascending within an entry)
-  int32_t *lent, *lq0, *lq1, *lround, *lidx;  // [n]
+  int32_t *lent, *lq0, *lq1, *lround, *lidx;  // [n]  (MenciusAcceptorInboxScratch::list, in this order)
 };
 
 // the first and last row q = s / L of range [start, end) that acceptor group ag owns (q % A == ag); *q0 > *q1: none
@@ -101,7 +101,7 @@ __global__ void __launch_bounds__(256) k_mai_accept(const Geom g, const State st
   __shared__ long long wtot[4];
   __shared__ int wcnt[4];
   const int p = blockIdx.x * AI_TILE + threadIdx.x;
-  const long long x = ai_block_excl(ai_word<2>(b.a, p), b.a.tile[blockIdx.x], wtot);
+  const long long x = block_excl_scan<ScanMax, 256>(ai_word<2>(b.a, p), b.a.tile[blockIdx.x], wtot);
   int acc = 0, tp = -1, flag = 0;
   if (p < b.a.n && b.a.hdr[AI_OK] != 0) {
     const int key = b.a.key[p], i = b.a.perm[p];
@@ -139,31 +139,9 @@ __global__ void __launch_bounds__(256) k_mai_accept(const Geom g, const State st
 
 // the exclusive sum of the tiles' counts, one workgroup; the total is the list's length
 __global__ void __launch_bounds__(AI_SCAN_THREADS) k_mai_offsets(const MenciusAcceptorInbox b) {
-  __shared__ int wtot[AI_SCAN_THREADS / 64];
-  __shared__ int carry;
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-  if (t == 0) carry = 0;
-  __syncthreads();
-  const int ntiles = (b.a.n + AI_TILE - 1) / AI_TILE;
-  for (int base = 0; base < ntiles; base += AI_SCAN_THREADS) {
-    const int ti = base + t;
-    const int v = ti < ntiles ? b.rcnt[ti] : 0;
-    int inc = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const int o = __shfl_up(inc, d);
-      if (lane >= d) inc += o;
-    }
-    if (lane == 63) wtot[wave] = inc;
-    __syncthreads();
-    int before = carry;
-    for (int w = 0; w < wave; ++w) before += wtot[w];
-    if (ti < ntiles) b.rcnt[ti] = before + inc - v;
-    __syncthreads();
-    if (t == AI_SCAN_THREADS - 1) carry = before + inc;
-    __syncthreads();
-  }
-  if (t == 0) b.a.hdr[MAI_NLIST] = carry;
+  __shared__ int lds[SCAN_ARRAY_LDS(AI_SCAN_THREADS)];
+  const int total = scan_array_excl<ScanSum, AI_SCAN_THREADS, 1>(b.rcnt, (b.a.n + AI_TILE - 1) / AI_TILE, lds);
+  if (threadIdx.x == 0) b.a.hdr[MAI_NLIST] = total;
 }
 
 __global__ void __launch_bounds__(256) k_mai_list(const Geom g, const MenciusAcceptorInbox b) {
@@ -210,7 +188,7 @@ __device__ __forceinline__ int mai_find(const AcceptorInbox& b, unsigned long lo
 __global__ void __launch_bounds__(256) k_mai_points(const Geom g, const State st, const MenciusAcceptorInbox b) {
   __shared__ long long wtot[4];
   const int p = blockIdx.x * AI_TILE + threadIdx.x;
-  const long long x = ai_block_excl(ai_word<1>(b.a, p), b.a.tile[blockIdx.x], wtot);
+  const long long x = block_excl_scan<ScanMax, 256>(ai_word<1>(b.a, p), b.a.tile[blockIdx.x], wtot);
   if (p >= b.a.n || b.a.hdr[AI_OK] == 0) return;
   const int key = b.a.key[p];
   if (key >= b.a.E) return;

@@ -150,8 +150,9 @@ __global__ void __launch_bounds__(256) k_mm_emit(const State st, const MenciusEm
   const MsgCompact& c = m.c;
   const int i = blockIdx.x * 256 + threadIdx.x;
   const bool f = st.status[ST_ABORT] == 0 && i < c.n && c.chosen[i] != 0;
+  __shared__ int wsum[4];
   int total;
-  const int at = c.blk[blockIdx.x] + block_rank(f, &total);
+  const int at = c.blk[blockIdx.x] + block_rank(f, &total, wsum);
   if (f && at < c.cap) {
     const int kind = m.kind ? m.kind[i] : m.phase2b;
     m.out_kind[at] = kind;

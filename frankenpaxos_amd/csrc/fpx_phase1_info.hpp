@@ -29,6 +29,7 @@
 // not bounded by max_voted, so a deferred fold (k_finalize) of the vote launch before it may stay pending.
 #pragma once
 #include "fpx_kernels.hpp"
+#include "fpx_scan.hpp"
 
 namespace fpx {
 
@@ -168,7 +169,7 @@ __global__ void __launch_bounds__(P1I_COLS * P1I_SEGS) k_p1i_colscan(const State
 // ONE workgroup of 1024: thread i takes `per` consecutive entries
 __global__ void __launch_bounds__(1024) k_p1i_offsets(const Geom g, const State st, const P1iArgs a) {
   __shared__ int64_t wtot[16];
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  const int t = threadIdx.x;
   if (st.status[ST_ABORT] != 0) {
     // the run was refused (a bad tick, a contract violation): nothing is answered
     if (t == 0) a.totals[0] = 0, a.totals[1] = 0, a.offsets[0] = 0, *a.go = 0;
@@ -179,19 +180,8 @@ __global__ void __launch_bounds__(1024) k_p1i_offsets(const Geom g, const State 
   const int e0 = t * per, e1 = (e0 + per) < E ? (e0 + per) : E;
   int64_t mine = 0;
   for (int e = e0; e < e1; ++e) mine += a.ctot[(e / g.R) * g.RS + e % g.R];
-  int64_t inc = mine;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const int64_t o = (int64_t)__shfl_up((long long)inc, d);
-    if (lane >= d) inc += o;
-  }
-  if (lane == 63) wtot[wave] = inc;
-  __syncthreads();
-  int64_t before = inc - mine, total = 0;
-  for (int w = 0; w < 16; ++w) {
-    if (w < wave) before += wtot[w];
-    total += wtot[w];
-  }
+  int64_t total;
+  int64_t before = block_excl_scan<ScanSum, 1024>(mine, (int64_t)0, wtot, &total);
   for (int e = e0; e < e1; ++e) {
     a.offsets[e] = before;
     before += a.ctot[(e / g.R) * g.RS + e % g.R];

@@ -28,6 +28,7 @@
 #include <limits.h>
 
 #include "fpx_kernels.hpp"
+#include "fpx_scan.hpp"
 #include "fpx_phase1b_plan.hpp"
 
 namespace fpx {
@@ -189,14 +190,8 @@ __global__ void __launch_bounds__(1024) k_p1m_plan(const Geom g, const P1mArgs a
       }
     }
     // the winners before this one, and their units
-    int wi = win ? 1 : 0;
-    int64_t ui = units;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const int ow = __shfl_up(wi, d);
-      const int64_t ou = (int64_t)__shfl_up((long long)ui, d);
-      if (lane >= d) wi += ow, ui += ou;
-    }
+    const int wi = wave_incl_scan<ScanSum>(win ? 1 : 0);
+    const int64_t ui = wave_incl_scan<ScanSum>(units);
     if (lane == 63) w_win[wave] = wi, w_units[wave] = ui;
     __syncthreads();
     int bw = c_win;
@@ -207,15 +202,8 @@ __global__ void __launch_bounds__(1024) k_p1m_plan(const Geom g, const P1mArgs a
     if (t == 1023) c_win = bw + wi, c_units = bu + ui;
     __syncthreads();
   }
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const int o = __shfl_xor(ms, d);
-    ms = o > ms ? o : ms;
-  }
-  if (lane == 0) w_max[wave] = ms;
-  __syncthreads();
+  ms = block_reduce<ScanMax, 1024>(ms, w_max);
   if (t != 0) return;
-  for (int w = 0; w < 16; ++w) ms = w_max[w] > ms ? w_max[w] : ms;
   a.unit0[c_win] = c_units;
   const int64_t max_slot = ms > a.recover_slot ? ms : a.recover_slot;  // (recover_slot is -1 for MultiPaxos)
   // logger.check(maxSlot == -1 || slotSystem.leader(maxSlot) == groupIndex)

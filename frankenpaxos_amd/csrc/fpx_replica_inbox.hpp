@@ -22,10 +22,7 @@
 //   k_ri_execby   workgroup / tile: M, written over the claim words of [W0, W1)
 //   k_ri_reads    thread / message: exec_count and reply_slot, the sort key of a read (exec_count; num_slots + 1 for a read
 //                 that stays deferred) at the read's rank, and the count of reads that ran
-//   k_ri_hist, k_ri_hscan, k_ri_scatter   a stable LSD radix sort of the reads by that key, RI_RADIX_BITS bits per pass,
-//                 in the shape of k_rs_hist / k_rs_scan / k_rs_scatter of fpx_epaxos.hip: per-tile digit counts,
-//                 digit-major exclusive sums by one workgroup, and a scatter in which a key's place among the equal digits
-//                 of its tile is its rank by position (ballots), never a cursor handed out by an atomic
+//   k_sort_count, k_sort_scan, k_sort_scatter   (fpx_burst_sort.hpp) a stable LSD radix sort of the reads by that key
 //   k_ri_finish   hands the claim words back (INT_MAX: the Chosens' slots and all of [W0, W1)), commits the watermark,
 //                 writes counts, and turns a bad index into the context's status
 //
@@ -34,18 +31,16 @@
 #include <limits.h>
 
 #include "../../include/fpx_wire.h"
+#include "fpx_burst_sort.hpp"
 #include "fpx_replica_msgs.hpp"
 
 namespace fpx {
 
-constexpr int RI_TILE = 256;           // slots per tile of the executed-by scan (one per thread)
+constexpr int RI_TILE = BURST_TILE;    // slots per tile of the executed-by scan (one per thread)
 constexpr int RI_SCAN_THREADS = 1024;  // tiles per step of k_ri_tilescan: the span's second level is RI_TILE * RI_SCAN_THREADS slots
-constexpr int RI_RADIX_BITS = 4;
-constexpr int RI_RADIX = 1 << RI_RADIX_BITS;
-constexpr int RI_SORT_TILE = 256;  // reads per tile of the sort (one per thread)
 
-// words of ReplicaInbox::hdr
-enum { RI_W0 = 0, RI_W1 = 1, RI_M = 2, RI_RAN = 3, RI_OK = 4, RI_HDR_WORDS = 8 };
+// words of ReplicaInbox::hdr (RI_M is the sort's length word)
+enum { RI_W0 = 0, RI_W1 = 1, RI_M = 2, RI_RAN = 3, RI_OK = 4, RI_HDR_WORDS = BURST_HDR_WORDS };
 
 struct ReplicaInbox {
   int32_t n, S;
@@ -58,9 +53,7 @@ struct ReplicaInbox {
   int32_t* hdr;         // [RI_HDR_WORDS]
   int32_t* blk;         // [nblk]  reads per workgroup of k_ri_claim, then their exclusive sums
   int32_t* tmax;        // [ceil(S / RI_TILE)]  the tiles' maxima, then their exclusive running maxima
-  int32_t* hist;        // [RI_RADIX][tiles of the sort]
-  int32_t* key[2];      // [n] each
-  int32_t* val[2];      // [n] each
+  int32_t *key0, *val0;  // [n]  the sort's input: the reads' keys and message indices, by rank
   int32_t *exec_count, *reply_slot, *order, *counts;
 };
 
@@ -104,25 +97,11 @@ __global__ void __launch_bounds__(256) k_ri_claim(const Geom g, const State st, 
         atomicMin(&b.claim[s], i);
     }
   }
+  __shared__ int wsum[4];
   int total;
-  (void)block_rank(read, &total);
+  (void)block_rank(read, &total, wsum);
   if (threadIdx.x == 0) b.blk[blockIdx.x] = total;
   if (i == 0) b.mhdr[RM_NRANGES] = 0, b.mhdr[RM_JSTAR] = -1, b.hdr[RI_RAN] = 0;
-}
-
-// the largest of 256 threads' values, in every thread (one use per barrier pair: `w` is reused by the next call)
-__device__ __forceinline__ int ri_block_max(int v, int* w) {
-#pragma unroll
-  for (int k = 1; k < 64; k <<= 1) {
-    const int o = __shfl_xor(v, k);
-    v = o > v ? o : v;
-  }
-  if ((threadIdx.x & 63) == 0) w[threadIdx.x >> 6] = v;
-  __syncthreads();
-  int r = w[0];
-  for (int j = 1; j < 4; ++j) r = w[j] > r ? w[j] : r;
-  __syncthreads();
-  return r;
 }
 
 __device__ __forceinline__ int ri_c(const ReplicaInbox& b, int s, int w1) {
@@ -137,63 +116,31 @@ __global__ void __launch_bounds__(256) k_ri_tilemax(const State st, const Replic
   (void)ri_span(st, b, &w0, &w1);
   const int ntiles = (w1 - w0 + RI_TILE - 1) / RI_TILE;
   for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-    const int m = ri_block_max(ri_c(b, w0 + tile * RI_TILE + (int)threadIdx.x, w1), w);
+    const int m = block_reduce<ScanMax, 256>(ri_c(b, w0 + tile * RI_TILE + (int)threadIdx.x, w1), w);
     if (threadIdx.x == 0) b.tmax[tile] = m;
   }
 }
 
 __global__ void __launch_bounds__(RI_SCAN_THREADS) k_ri_tilescan(const State st, const ReplicaInbox b) {
-  __shared__ int wtot[RI_SCAN_THREADS / 64];
-  __shared__ int carry;
+  __shared__ int lds[SCAN_ARRAY_LDS(RI_SCAN_THREADS)];
   int w0, w1;
   const bool ok = ri_span(st, b, &w0, &w1);
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-  if (t == 0) {
-    carry = -1;
+  if (threadIdx.x == 0) {
     b.hdr[RI_W0] = w0, b.hdr[RI_W1] = w1, b.hdr[RI_OK] = ok ? 1 : 0;
     b.hdr[RI_M] = ok && b.order ? b.rhdr[RM_NRANGES] : 0;
   }
-  __syncthreads();
-  const int ntiles = (w1 - w0 + RI_TILE - 1) / RI_TILE;
-  for (int base = 0; base < ntiles; base += RI_SCAN_THREADS) {
-    const int ti = base + t;
-    int inc = ti < ntiles ? b.tmax[ti] : -1;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const int o = __shfl_up(inc, d);
-      if (lane >= d && o > inc) inc = o;
-    }
-    int excl = __shfl_up(inc, 1);  // the wavefront's earlier lanes
-    if (lane == 0) excl = -1;
-    if (lane == 63) wtot[wave] = inc;
-    __syncthreads();
-    int before = carry;
-    for (int w = 0; w < wave; ++w) before = wtot[w] > before ? wtot[w] : before;
-    if (ti < ntiles) b.tmax[ti] = excl > before ? excl : before;
-    __syncthreads();
-    if (t == RI_SCAN_THREADS - 1) carry = inc > before ? inc : before;
-    __syncthreads();
-  }
+  (void)scan_array_excl<ScanMax, RI_SCAN_THREADS, 1>(b.tmax, (w1 - w0 + RI_TILE - 1) / RI_TILE, lds);
 }
 
 __global__ void __launch_bounds__(256) k_ri_execby(const ReplicaInbox b) {
   __shared__ int wtot[4];
   const int w0 = b.hdr[RI_W0], w1 = b.hdr[RI_W1];
   const int ntiles = (w1 - w0 + RI_TILE - 1) / RI_TILE;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
     const int s = w0 + tile * RI_TILE + (int)threadIdx.x;
-    int inc = ri_c(b, s, w1);
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const int o = __shfl_up(inc, d);
-      if (lane >= d && o > inc) inc = o;
-    }
-    if (lane == 63) wtot[wave] = inc;
-    __syncthreads();
-    int before = b.tmax[tile];
-    for (int w = 0; w < wave; ++w) before = wtot[w] > before ? wtot[w] : before;
-    if (s < w1) b.claim[s] = inc > before ? inc : before;
+    const int c = ri_c(b, s, w1);
+    const int before = block_excl_scan<ScanMax, 256>(c, b.tmax[tile], wtot);
+    if (s < w1) b.claim[s] = c > before ? c : before;
     __syncthreads();
   }
 }
@@ -222,101 +169,16 @@ __global__ void __launch_bounds__(256) k_ri_reads(const ReplicaInbox b) {
       exec = -1, reply = -1;  // still deferred
     }
   }
+  __shared__ int wsum[4];
   int total;
-  const int q = b.blk[blockIdx.x] + block_rank(cls != 0, &total);
-  __syncthreads();
-  (void)block_rank(cls != 0 && exec >= 0, &total);
+  const int q = b.blk[blockIdx.x] + block_rank(cls != 0, &total, wsum);
+  __syncthreads();  // (wsum is used again)
+  (void)block_rank(cls != 0 && exec >= 0, &total, wsum);
   if (!ok) return;  // a bad burst writes no output
   if (threadIdx.x == 0 && total != 0) atomicAdd(&b.hdr[RI_RAN], total);
   if (i >= b.n) return;
   b.exec_count[i] = exec, b.reply_slot[i] = reply;
-  if (cls != 0) b.key[0][q] = exec >= 0 ? exec : b.S + 1, b.val[0][q] = i;
-}
-
-// ---- the reads by (exec_count, index): a stable LSD radix sort over the RI_M reads, tile <-> workgroup ----------------
-
-struct RiSort {
-  const int32_t* hdr;
-  int32_t* hist;
-  const int32_t *key_in, *val_in;
-  int32_t *key_out, *val_out;
-  int shift;
-};
-
-__global__ void __launch_bounds__(256) k_ri_hist(const RiSort a) {
-  __shared__ int wc[4][RI_RADIX];
-  const int m = a.hdr[RI_M], tiles = (m + RI_SORT_TILE - 1) / RI_SORT_TILE, tile = blockIdx.x;
-  if (tile >= tiles) return;
-  const int j = tile * RI_SORT_TILE + threadIdx.x;
-  const int d = j < m ? (a.key_in[j] >> a.shift) & (RI_RADIX - 1) : -1;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int v = 0; v < RI_RADIX; ++v) {
-    const int c = __popcll(__ballot(d == v));
-    if (lane == 0) wc[wave][v] = c;
-  }
-  __syncthreads();
-  if (threadIdx.x < RI_RADIX) {
-    const int v = threadIdx.x;
-    a.hist[(size_t)v * tiles + tile] = wc[0][v] + wc[1][v] + wc[2][v] + wc[3][v];
-  }
-}
-
-// exclusive sums over the digit-major counts, one workgroup (k_rm_offsets with a length known on the device)
-__global__ void __launch_bounds__(1024) k_ri_hscan(const RiSort a) {
-  __shared__ int wtot[16];
-  __shared__ int carry;
-  const int m = a.hdr[RI_M], tiles = (m + RI_SORT_TILE - 1) / RI_SORT_TILE;
-  const long long len = (long long)tiles * RI_RADIX;
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-  if (t == 0) carry = 0;
-  __syncthreads();
-  for (long long base = 0; base < len; base += 1024) {
-    const long long bi = base + t;
-    const int v = bi < len ? a.hist[bi] : 0;
-    int inc = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const int o = __shfl_up(inc, d);
-      if (lane >= d) inc += o;
-    }
-    if (lane == 63) wtot[wave] = inc;
-    __syncthreads();
-    int before = carry;
-    for (int w = 0; w < wave; ++w) before += wtot[w];
-    if (bi < len) a.hist[bi] = before + inc - v;
-    __syncthreads();
-    if (t == 1023) carry = before + inc;
-    __syncthreads();
-  }
-}
-
-__global__ void __launch_bounds__(256) k_ri_scatter(const RiSort a) {
-  __shared__ int wc[4][RI_RADIX];
-  const int m = a.hdr[RI_M], tiles = (m + RI_SORT_TILE - 1) / RI_SORT_TILE, tile = blockIdx.x;
-  if (tile >= tiles) return;
-  const int j = tile * RI_SORT_TILE + threadIdx.x;
-  const bool valid = j < m;
-  const int key = valid ? a.key_in[j] : 0, val = valid ? a.val_in[j] : 0;
-  const int d = (key >> a.shift) & (RI_RADIX - 1);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (threadIdx.x < 4 * RI_RADIX) (&wc[0][0])[threadIdx.x] = 0;
-  __syncthreads();
-  // the lanes of this wavefront with the same digit
-  unsigned long long peers = __ballot(valid);
-#pragma unroll
-  for (int bit = 0; bit < RI_RADIX_BITS; ++bit) {
-    const bool one = (d >> bit) & 1;
-    const unsigned long long mk = __ballot(valid && one);
-    peers &= one ? mk : ~mk;
-  }
-  const int rank = __popcll(peers & ((1ull << lane) - 1ull));
-  if (valid && rank == 0) wc[wave][d] = __popcll(peers);
-  __syncthreads();
-  if (!valid) return;
-  int at = a.hist[(size_t)d * tiles + tile] + rank;
-  for (int w = 0; w < wave; ++w) at += wc[w][d];
-  a.key_out[at] = key, a.val_out[at] = val;
+  if (cls != 0) b.key0[q] = exec >= 0 ? exec : b.S + 1, b.val0[q] = i;
 }
 
 __global__ void __launch_bounds__(256) k_ri_finish(const Geom g, const State st, const ReplicaInbox b) {

@@ -38,12 +38,14 @@
 #include <limits.h>
 
 #include "fpx_kernels.hpp"
+#include "fpx_scan.hpp"
+#include "fpx_scratch.hpp"
 #include "fpx_tally_msgs.hpp"
 
 namespace fpx {
 
 // words of ReplicaMsgs::hdr
-enum { RM_NRANGES = 0, RM_JSTAR = 1, RM_HDR_WORDS = 8 };
+enum { RM_NRANGES = 0, RM_JSTAR = 1, RM_HDR_WORDS = BURST_HDR_WORDS };
 constexpr int RM_WALK_THREADS = 1024;
 
 struct ReplicaMsgs {
@@ -84,43 +86,24 @@ __global__ void __launch_bounds__(256) k_rm_claim(const Geom g, const State st, 
       }
     }
   }
+  __shared__ int wsum[4];
   int total;
-  (void)block_rank(range, &total);
+  (void)block_rank(range, &total, wsum);
   if (threadIdx.x == 0) b.blk[blockIdx.x] = total;
 }
 
 __global__ void __launch_bounds__(1024) k_rm_offsets(const ReplicaMsgs b) {
-  __shared__ int wtot[16];
-  __shared__ int carry;
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-  if (t == 0) carry = 0;
-  __syncthreads();
-  for (int base = 0; base < b.nblk; base += 1024) {
-    const int bi = base + t;
-    const int v = bi < b.nblk ? b.blk[bi] : 0;
-    int inc = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const int o = __shfl_up(inc, d);
-      if (lane >= d) inc += o;
-    }
-    if (lane == 63) wtot[wave] = inc;
-    __syncthreads();
-    int before = carry;
-    for (int w = 0; w < wave; ++w) before += wtot[w];
-    if (bi < b.nblk) b.blk[bi] = before + inc - v;
-    __syncthreads();
-    if (t == 1023) carry = before + inc;
-    __syncthreads();
-  }
-  if (t == 0) b.hdr[RM_NRANGES] = carry, b.hdr[RM_JSTAR] = -1;
+  __shared__ int lds[SCAN_ARRAY_LDS(1024)];
+  const int total = scan_array_excl<ScanSum, 1024, 1>(b.blk, b.nblk, lds);
+  if (threadIdx.x == 0) b.hdr[RM_NRANGES] = total, b.hdr[RM_JSTAR] = -1;
 }
 
 __global__ void __launch_bounds__(256) k_rm_list(const ReplicaMsgs b) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   const bool range = i < b.n && rm_kind(b, i) == b.range_kind;
+  __shared__ int wsum[4];
   int total;
-  const int at = b.blk[blockIdx.x] + block_rank(range, &total);
+  const int at = b.blk[blockIdx.x] + block_rank(range, &total, wsum);
   if (range) b.list[at] = i, b.res[at] = -1;  // "stopped after 0 puts" until k_rm_walk says otherwise
 }
 

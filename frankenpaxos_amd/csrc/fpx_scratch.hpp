@@ -1,0 +1,115 @@
+// fpx_scratch.hpp -- how the burst entry points of fpx_api.hip cut their per-call scratch buffer into arrays.  Host code,
+// no HIP: tests/burst_scratch_main.cpp runs the layouts under the sanitizers.
+//
+// A layout is ONE function over a Carver.  It runs twice per call: over a null base to learn the size the buffer must
+// have, then over the buffer.  The size and the pointers come from the same take() calls and cannot disagree.
+#pragma once
+#include <cstddef>
+#include <cstdint>
+
+namespace fpx {
+
+constexpr int BURST_HDR_WORDS = 8;  // every burst call's header of device-side scalars
+constexpr int BURST_TILE = 256;     // messages (slots, sorted positions) per tile: one per thread of a workgroup
+constexpr int SORT_RADIX_BITS = 4;  // fpx_burst_sort.hpp
+constexpr int SORT_RADIX = 1 << SORT_RADIX_BITS;
+
+// bump allocation: every array starts on a multiple of ALIGN bytes, the alignment of the device allocation itself
+struct Carver {
+  static constexpr size_t ALIGN = 256;
+  char* base;
+  size_t at = 0;
+  explicit Carver(void* b) : base(static_cast<char*>(b)) {}
+  template <typename T>
+  T* take(size_t count) {
+    static_assert(ALIGN % alignof(T) == 0, "ALIGN covers every element type");
+    at = (at + ALIGN - 1) / ALIGN * ALIGN;
+    T* p = base ? reinterpret_cast<T*>(base + at) : nullptr;
+    at += count * sizeof(T);
+    return p;
+  }
+  size_t size() const { return at; }
+};
+
+inline size_t burst_tiles(size_t n) { return (n + BURST_TILE - 1) / BURST_TILE; }
+
+// fpx_burst_sort.hpp: the digit counts of `tiles` tiles, and the two key and value buffers of tiles * BURST_TILE pairs
+struct SortScratch {
+  int32_t* hist;
+  int32_t *key[2], *val[2];
+};
+inline SortScratch lay_sort(Carver& c, size_t tiles) {
+  SortScratch s;
+  s.hist = c.take<int32_t>(SORT_RADIX * tiles);
+  for (int j = 0; j < 2; ++j) s.key[j] = c.take<int32_t>(tiles * BURST_TILE);
+  for (int j = 0; j < 2; ++j) s.val[j] = c.take<int32_t>(tiles * BURST_TILE);
+  return s;
+}
+
+// fpx_replica_msgs.hpp (ReplicaMsgs): nblk workgroups of messages, `ranges` list places (n, or 0 for a burst without)
+struct ReplicaMsgsScratch {
+  int32_t *hdr, *parts, *blk, *list, *res;
+};
+inline ReplicaMsgsScratch lay_replica_msgs(Carver& c, size_t nblk, size_t ranges, size_t max_parts) {
+  ReplicaMsgsScratch s;
+  s.hdr = c.take<int32_t>(BURST_HDR_WORDS);
+  s.parts = c.take<int32_t>(3 * max_parts);
+  s.blk = c.take<int32_t>(nblk);
+  s.list = c.take<int32_t>(ranges);
+  s.res = c.take<int32_t>(ranges);
+  return s;
+}
+
+// fpx_replica_inbox.hpp (ReplicaInbox): the Chosens' ReplicaMsgs, and for a call with outputs the reads' sort
+struct ReplicaInboxScratch {
+  ReplicaMsgsScratch m;
+  int32_t *rhdr, *hdr, *tmax;
+  SortScratch sort;
+};
+inline ReplicaInboxScratch lay_replica_inbox(Carver& c, size_t nblk, size_t slot_tiles, size_t max_parts, bool outputs) {
+  ReplicaInboxScratch s;
+  s.m = lay_replica_msgs(c, nblk, 0, max_parts);
+  s.rhdr = c.take<int32_t>(BURST_HDR_WORDS);
+  s.hdr = c.take<int32_t>(BURST_HDR_WORDS);
+  s.tmax = c.take<int32_t>(slot_tiles);
+  s.sort = lay_sort(c, outputs ? nblk : 0);
+  return s;
+}
+
+// fpx_acceptor_inbox.hpp (AcceptorInbox): n messages to E entries
+struct AcceptorInboxScratch {
+  int32_t* hdr;
+  long long* tile;
+  SortScratch sort;
+  int32_t *accslot, *tpos, *fin_round, *fin_slot;
+};
+inline AcceptorInboxScratch lay_acceptor_inbox(Carver& c, size_t n, size_t E) {
+  const size_t tiles = burst_tiles(n);
+  AcceptorInboxScratch s;
+  s.hdr = c.take<int32_t>(BURST_HDR_WORDS);
+  s.tile = c.take<long long>(tiles);
+  s.sort = lay_sort(c, tiles);
+  s.accslot = c.take<int32_t>(tiles * BURST_TILE);
+  s.tpos = c.take<int32_t>(tiles * BURST_TILE);
+  s.fin_round = c.take<int32_t>(E);
+  s.fin_slot = c.take<int32_t>(E);
+  return s;
+}
+
+// fpx_mencius_acceptor_inbox.hpp (MenciusAcceptorInbox): the above, the range flags, their tile counts and the list
+struct MenciusAcceptorInboxScratch {
+  AcceptorInboxScratch a;
+  int32_t *rflag, *rcnt;
+  int32_t* list[5];  // lent, lq0, lq1, lround, lidx
+};
+inline MenciusAcceptorInboxScratch lay_mencius_acceptor_inbox(Carver& c, size_t n, size_t E) {
+  const size_t tiles = burst_tiles(n);
+  MenciusAcceptorInboxScratch s;
+  s.a = lay_acceptor_inbox(c, n, E);
+  s.rflag = c.take<int32_t>(tiles * BURST_TILE);
+  s.rcnt = c.take<int32_t>(tiles);
+  for (int j = 0; j < 5; ++j) s.list[j] = c.take<int32_t>(tiles * BURST_TILE);
+  return s;
+}
+
+}  // namespace fpx

@@ -28,6 +28,7 @@
 #include <limits.h>
 
 #include "fpx_kernels.hpp"
+#include "fpx_scan.hpp"
 
 namespace fpx {
 
@@ -178,65 +179,30 @@ struct MsgCompact {
   int64_t* totals;
 };
 
-// this thread's rank among the workgroup's flagged threads, and the workgroup's count (256 threads)
-__device__ __forceinline__ int block_rank(bool flag, int* total) {
-  __shared__ int wsum[4];
-  const unsigned long long m = __ballot(flag);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (lane == 0) wsum[wave] = __popcll(m);
-  __syncthreads();
-  int before = 0, all = 0;
-  for (int w = 0; w < 4; ++w) {
-    before += w < wave ? wsum[w] : 0;
-    all += wsum[w];
-  }
-  *total = all;
-  return before + __popcll(m & ((1ull << lane) - 1ull));
-}
-
 __global__ void __launch_bounds__(256) k_msgs_count(const State st, const MsgCompact c) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   const bool f = st.status[ST_ABORT] == 0 && i < c.n && c.chosen[i] != 0;
+  __shared__ int wsum[4];
   int total;
-  (void)block_rank(f, &total);
+  (void)block_rank(f, &total, wsum);
   if (threadIdx.x == 0) c.blk[blockIdx.x] = total;
 }
 
 __global__ void __launch_bounds__(1024) k_msgs_scan(const State st, const MsgCompact c) {
-  __shared__ int wtot[16];
-  __shared__ int carry;
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-  if (t == 0) carry = 0;
-  __syncthreads();
-  for (int base = 0; base < c.nblk; base += 1024) {
-    const int bi = base + t;
-    const int v = bi < c.nblk ? c.blk[bi] : 0;
-    int inc = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const int o = __shfl_up(inc, d);
-      if (lane >= d) inc += o;
-    }
-    if (lane == 63) wtot[wave] = inc;
-    __syncthreads();
-    int before = carry;
-    for (int w = 0; w < wave; ++w) before += wtot[w];
-    if (bi < c.nblk) c.blk[bi] = before + inc - v;
-    __syncthreads();
-    if (t == 1023) carry = before + inc;
-    __syncthreads();
-  }
-  if (t == 0) {
-    c.totals[0] = carry;
-    if (carry > c.cap) report(st, 5 /*FPX_ECAPACITY*/, -1, -1, -1);
+  __shared__ int lds[SCAN_ARRAY_LDS(1024)];
+  const int total = scan_array_excl<ScanSum, 1024, 1>(c.blk, c.nblk, lds);
+  if (threadIdx.x == 0) {
+    c.totals[0] = total;
+    if (total > c.cap) report(st, 5 /*FPX_ECAPACITY*/, -1, -1, -1);
   }
 }
 
 __global__ void __launch_bounds__(256) k_msgs_emit(const State st, const MsgCompact c) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   const bool f = st.status[ST_ABORT] == 0 && i < c.n && c.chosen[i] != 0;
+  __shared__ int wsum[4];
   int total;
-  const int at = c.blk[blockIdx.x] + block_rank(f, &total);
+  const int at = c.blk[blockIdx.x] + block_rank(f, &total, wsum);
   if (f && at < c.cap) {
     c.out_slot[at] = c.slot[i];
     c.out_round[at] = c.chosen_round[i];

@@ -133,6 +133,27 @@ def test_streams_equal_the_model_and_the_message_at_a_time_route(fa, name, dev):
     gpu.close(), twin.close()
 
 
+def test_a_burst_that_takes_the_one_workgroup_scans_past_their_first_step(fa):
+    """n = 1024 * 256 + 3 * 256 + 57 messages are 1028 tiles: the sort's count scan (fpx_burst_sort.hpp, 8192 counts a
+    step) has 16 * 1028 = 16 448 counts, three steps, and the 64-bit tile scan (1024 tiles a step) two -- the carry of
+    scan_array_excl (fpx_scan.hpp) in both instantiations.  Against the model only: the message-at-a-time twin would
+    take minutes here"""
+    n = 1024 * 256 + 3 * 256 + 57
+    b = AS.make(21, n=n, R=3, S=4096)
+    gpu, model = context(fa, b), M.Sequential(b.R, b.groups, b.S)
+    st, bad, want_kind, want_value = model.run(b)
+    assert st == 0
+    for k in (M.PHASE2B, M.PHASE1B, M.NACK, MSR):                      # every reply kind, and both kinds of read
+        assert (want_kind == k).sum() >= 1000, k
+    assert (b.kind == MSR).sum() >= 1000 and (b.kind == BMSR).sum() >= 1000
+    st, rk, rv = call(gpu, b, True)
+    assert st == 0, gpu.error_detail()
+    np.testing.assert_array_equal(rk, want_kind)
+    np.testing.assert_array_equal(rv, want_value)
+    assert_equals_model(gpu, model, "n = %d" % n)
+    gpu.close()
+
+
 @pytest.mark.parametrize("dev", [False, True])
 def test_a_fused_step_left_pending_before_the_burst(fa, dev):
     """the burst reads promised and max_voted: it must come behind the fold of the fused step enqueued before it"""

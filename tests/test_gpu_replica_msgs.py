@@ -178,6 +178,35 @@ def test_loops_that_iterate_every_class_and_many_chosens(fa, oracle):
     gpu.close()
 
 
+def test_ranges_listed_from_offsets_that_went_through_the_carry(fa, oracle):
+    """n = 1024 * 256 + 3 * 256 + 57 messages are 1028 workgroups of k_rm_claim: k_rm_offsets (scan_array_excl of
+    fpx_scan.hpp, 1024 counts a step) takes two steps, and the ranges behind message 1024 * 256 get their list places from
+    offsets that carry the first step's total.  Those are the ranges of classes 0 .. 15; the Chosens of their classes keep
+    to rows 200 and up, so every one of them still finds its first slot free and puts a run of Noops"""
+    S, L, tail = 1 << 16, 256, 16
+    n, first_step = 1024 * 256 + 3 * 256 + 57, 1024 * 256
+    gpu, ref = pair(fa, oracle, S, L)
+    rng = np.random.default_rng(6)
+    slots = rng.integers(0, S, n - L)
+    low = (slots % L < tail) & (slots // L < 200)                    # rows 0 .. 199 of those classes -> 200 .. 255
+    slots[low] = slots[low] % L + L * (200 + (slots[low] // L) % 56)
+    msgs = [Ch(int(s), int(v)) for s, v in zip(slots, rng.integers(0, 1 << 30, n - L))]
+    ranges = {c: Rg(c + L * (c % 7), S - L * (c % 5)) for c in range(L)}
+    for c in range(tail, L):
+        msgs.insert(int(rng.integers(0, len(msgs) + 1)), ranges[c])
+    for c in range(tail):
+        msgs.insert(int(rng.integers(first_step + 8, len(msgs) + 1)), ranges[c])
+    assert len(msgs) == n
+    behind = [m for m in msgs[first_step:] if m[0] == RS.CHOSEN_NOOP_RANGE and m[1] % L < tail]
+    assert len(behind) == tail
+    got, stats = run(gpu, ref, msgs, dev=True)
+    assert stats["truncated"] + stats["full"] == L and stats["redundant"] > 1000
+    vals, pres = gpu.replica_read_log(0, S)
+    for m in behind:                                                # (run() has compared the whole log with the oracle's)
+        assert pres[m[1]] and vals[m[1]] == RS.NOOP and pres[m[1] + L] and vals[m[1] + L] == RS.NOOP
+    gpu.close()
+
+
 def test_refusal(fa, oracle):
     import torch
 
