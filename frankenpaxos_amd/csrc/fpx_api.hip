@@ -19,6 +19,7 @@
 #include <type_traits>
 #include <vector>
 
+#include "fpx_host.hpp"
 #include "fpx_kernels.hpp"
 #include "fpx_phase1_info.hpp"
 #include "fpx_phase1b_msgs.hpp"
@@ -35,15 +36,6 @@
 #include "../../include/fpx_wire.h"
 
 using namespace fpx;
-
-namespace {
-
-struct DevBuf {
-  void* p = nullptr;
-  size_t cap = 0;
-};
-
-}  // namespace
 
 // RCCL is bound at run time (dlopen), never at link time: a process that already carries an RCCL (PyTorch
 // bundles its own librccl.so) must keep using THAT copy -- two RCCLs in one address space do not share their
@@ -198,23 +190,10 @@ struct fpx_ctx {
 
 namespace {
 
-#define HIPCHK(ctx, expr)                       \
-  do {                                          \
-    hipError_t _e = (expr);                     \
-    if (_e != hipSuccess) {                     \
-      if (ctx) (ctx)->last_hip = (int)_e;       \
-      return _e == hipErrorOutOfMemory ? FPX_ENOMEM : FPX_EHIP; \
-    }                                           \
-  } while (0)
-
-// Every entry point runs with the context's device current and restores the caller's on return: allocations
-// (staging buffers, events) and launches otherwise land on whatever device the calling thread last selected --
-// two contexts on two GPUs in one process (or a torch.cuda.set_device elsewhere) would fault.
+// Every entry point runs inside a DeviceScope (fpx_host.hpp) of the context's device.
 void flush_pending_fin(fpx_ctx* ctx);
-struct DeviceGuard {
-  int prev = -1;
-  bool switched = false;
-  explicit DeviceGuard(int device) { enter(device); }
+struct DeviceGuard : DeviceScope {
+  explicit DeviceGuard(int device) : DeviceScope(device) {}
   // Every entry point that takes the context starts here; all but fpx_phase2_fused_dev (which enters by device number
   // and deals with a pending fold itself) first launch the fold of the last K3 launch if it is still pending -- so
   // nothing that reads or moves the acceptors' scalars ever sees them short of a launch (see k_phase2_fin).
@@ -223,15 +202,6 @@ struct DeviceGuard {
     enter(ctx->cfg.device);
     if (ctx->pending_fin.nblk) flush_pending_fin(const_cast<fpx_ctx*>(ctx));
   }
-  void enter(int device) {
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    if (prev != device) switched = hipSetDevice(device) == hipSuccess;
-  }
-  ~DeviceGuard() {
-    if (switched && prev >= 0) (void)hipSetDevice(prev);
-  }
-  DeviceGuard(const DeviceGuard&) = delete;
-  DeviceGuard& operator=(const DeviceGuard&) = delete;
 };
 
 int check_config(const fpx_config* c) {
@@ -305,17 +275,6 @@ void make_geom(const fpx_config& c, Geom* g) {
   }
 }
 
-int grow(fpx_ctx* ctx, DevBuf* b, size_t bytes) {
-  if (bytes <= b->cap) return FPX_OK;
-  if (b->p) HIPCHK(ctx, hipFree(b->p));
-  b->p = nullptr;
-  b->cap = 0;
-  size_t cap = std::max<size_t>(bytes, 4096);
-  HIPCHK(ctx, hipMalloc(&b->p, cap));
-  b->cap = cap;
-  return FPX_OK;
-}
-
 // grow() for a buffer that fpx_device_bytes counts
 int grow_counted(fpx_ctx* ctx, DevBuf* b, size_t bytes) {
   const size_t had = b->cap;
@@ -324,17 +283,13 @@ int grow_counted(fpx_ctx* ctx, DevBuf* b, size_t bytes) {
   return rc;
 }
 
-// A call's scratch, cut into arrays by `lay` (fpx_scratch.hpp): the layout runs over a null base for the size the buffer
-// must have, and again over the buffer
+// carve() for a buffer that fpx_device_bytes counts
 template <typename S, typename Lay>
-int carve(fpx_ctx* ctx, DevBuf* buf, bool counted, S* out, Lay lay) {
-  Carver size(nullptr);
-  (void)lay(size);
-  const int rc = counted ? grow_counted(ctx, buf, size.size()) : grow(ctx, buf, size.size());
-  if (rc) return rc;
-  Carver c(buf->p);
-  *out = lay(c);
-  return FPX_OK;
+int carve_counted(fpx_ctx* ctx, DevBuf* buf, S* out, Lay lay) {
+  const size_t had = buf->cap;
+  const int rc = carve(ctx, buf, out, lay);
+  ctx->bytes += (int64_t)buf->cap - (int64_t)had;
+  return rc;
 }
 
 template <typename T>
@@ -503,15 +458,6 @@ int claim_array(fpx_ctx* ctx, DevBuf* b, size_t words) {
   const int rc = grow_counted(ctx, b, words * 4);
   if (rc) return rc;
   fill32(ctx, b->p, INT_MAX, b->cap / 4);
-  return FPX_OK;
-}
-
-int launch_check(fpx_ctx* ctx) {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    ctx->last_hip = (int)e;
-    return FPX_EHIP;
-  }
   return FPX_OK;
 }
 
@@ -3039,7 +2985,7 @@ int32_t fpx_replica_chosen_msgs_dev(fpx_ctx* ctx, int32_t n, const int32_t* d_ki
   int rc;
   const int nblk = (n + 255) / 256;
   ReplicaMsgsScratch s;  // (rm_buf is not counted in fpx_device_bytes)
-  if ((rc = carve(ctx, &ctx->rm_buf, false, &s, [&](Carver& c) { return lay_replica_msgs(c, nblk, n, LG_MAX_PARTS); })))
+  if ((rc = carve(ctx, &ctx->rm_buf, &s, [&](Carver& c) { return lay_replica_msgs(c, nblk, n, LG_MAX_PARTS); })))
     return rc;
   ReplicaMsgs b;
   if ((rc = replica_msgs(ctx, n, nblk, d_kind, d_slot, d_slot_end, d_value_id, d_mask, s, &b))) return rc;
@@ -3093,7 +3039,7 @@ int32_t fpx_replica_inbox_dev(fpx_ctx* ctx, int32_t n, const int32_t* d_kind, co
   const int nblk = std::max(1, (n + 255) / 256);
   const size_t ntiles_max = ((size_t)ctx->g.S + RI_TILE - 1) / RI_TILE;
   ReplicaInboxScratch s;
-  if ((rc = carve(ctx, &ctx->ri_buf, true, &s,
+  if ((rc = carve_counted(ctx, &ctx->ri_buf, &s,
                   [&](Carver& c) { return lay_replica_inbox(c, nblk, ntiles_max, LG_MAX_PARTS, nout != 0); })))
     return rc;
   // the Chosens: fpx_replica_msgs.hpp's kernels on a burst without ranges
@@ -3213,7 +3159,7 @@ int32_t fpx_acceptor_inbox_dev(fpx_ctx* ctx, int32_t n, const int32_t* d_kind, c
   const int E = g.ngroups * g.R;
   const int nblk = (n + AI_TILE - 1) / AI_TILE;
   AcceptorInboxScratch s;
-  if ((rc = carve(ctx, &ctx->ai_buf, true, &s, [&](Carver& c) { return lay_acceptor_inbox(c, n, E); }))) return rc;
+  if ((rc = carve_counted(ctx, &ctx->ai_buf, &s, [&](Carver& c) { return lay_acceptor_inbox(c, n, E); }))) return rc;
   AcceptorInbox b;
   memset(&b, 0, sizeof(b));
   if ((rc = acceptor_inbox_args(ctx, n, s, &b))) return rc;
@@ -3288,7 +3234,7 @@ int32_t fpx_mencius_acceptor_inbox_dev(fpx_ctx* ctx, int32_t n, const int32_t* d
   const int E = g.ngroups * g.R;
   const int nblk = (n + AI_TILE - 1) / AI_TILE;
   MenciusAcceptorInboxScratch s;
-  if ((rc = carve(ctx, &ctx->mai_buf, true, &s, [&](Carver& c) { return lay_mencius_acceptor_inbox(c, n, E); })))
+  if ((rc = carve_counted(ctx, &ctx->mai_buf, &s, [&](Carver& c) { return lay_mencius_acceptor_inbox(c, n, E); })))
     return rc;
   MenciusAcceptorInbox b;
   memset(&b, 0, sizeof(b));

@@ -319,15 +319,15 @@ __device__ __forceinline__ uint32_t dg_hash(const int* c, int bits) {
   return h >> (32 - bits);
 }
 __global__ void __launch_bounds__(256) k_dg_rekey(const DgCommon a) {  // after the sort on the hash: the main key, by vertex
-  __shared__ uint32_t sh[8];
+  __shared__ uint32_t sh[4];
   const int p = blockIdx.x * blockDim.x + threadIdx.x;
   if (p < a.m) a.pairs[p].x = a.key32[a.pairs[p].y];
   if (blockIdx.x == 0) {  // the number of executables (ctl[3]) from the workgroups' counts of the keys kernel
     const int vblocks = (a.m + 255) >> 8;
     uint32_t s = 0;
     for (int b = (int)threadIdx.x; b < vblocks; b += 256) s += (uint32_t)a.belig[b];
-    const uint32_t ex = block_excl_sum(s, sh);
-    if (threadIdx.x == 255) a.ctl[3] = (int32_t)(ex + s);
+    s = block_reduce<ScanSum, 256>(s, sh);
+    if (threadIdx.x == 0) a.ctl[3] = (int32_t)s;
   }
 }
 
@@ -426,47 +426,39 @@ __device__ __forceinline__ uint32_t dg_starts(const DgCommon& a, const Clo& c, i
 // message indices in execution order
 template <class Clo>
 __global__ void __launch_bounds__(256) k_dg_count_starts(const DgCommon a, const Clo c) {
-  __shared__ uint32_t sh[8];
+  __shared__ uint32_t sh[4];
   const int executables = a.ctl[3];
   const int t0 = blockIdx.x * DG_TILE;
   uint32_t total = 0;
   for (int j = 0; j < DG_TILE / 256; ++j) total += dg_starts(a, c, t0 + j * 256 + threadIdx.x, executables);
-  const uint32_t ex = block_excl_sum(total, sh);
-  if (threadIdx.x == 255) a.tstarts[blockIdx.x] = (int32_t)(ex + total);
+  total = block_reduce<ScanSum, 256>(total, sh);
+  if (threadIdx.x == 0) a.tstarts[blockIdx.x] = (int32_t)total;
 }
 
 template <class Clo>
 __global__ void __launch_bounds__(256) k_dg_emit(const DgCommon a, const Clo c) {
-  __shared__ uint32_t sh[8];
-  __shared__ uint32_t before_tile;
+  __shared__ uint32_t sh[4];
   const int executables = a.ctl[3];
   const int t0 = blockIdx.x * DG_TILE;
   uint32_t mine[DG_TILE / 256];
 #pragma unroll
   for (int j = 0; j < DG_TILE / 256; ++j) mine[j] = dg_starts(a, c, t0 + j * 256 + threadIdx.x, executables);
-  {
-    // the components that start in the tiles before this one: 256 threads add up the tiles' counts (one thread walking up to
-    // 512 of them was ~10 us of the kernel)
-    uint32_t s = 0;
-    for (int t = (int)threadIdx.x; t < (int)blockIdx.x; t += 256) s += (uint32_t)a.tstarts[t];
-    const uint32_t ex = block_excl_sum(s, sh);
-    if (threadIdx.x == 255) before_tile = ex + s;
-    __syncthreads();
-  }
-  uint32_t run = before_tile;
+  // the components that start in the tiles before this one: 256 threads add up the tiles' counts (one thread walking up to
+  // 512 of them was ~10 us of the kernel)
+  uint32_t s = 0;
+  for (int t = (int)threadIdx.x; t < (int)blockIdx.x; t += 256) s += (uint32_t)a.tstarts[t];
+  uint32_t run = block_reduce<ScanSum, 256>(s, sh);  // (ends with a barrier: sh is free for the first step)
 #pragma unroll
   for (int j = 0; j < DG_TILE / 256; ++j) {
-    const uint32_t ex = block_excl_sum(mine[j], sh);
+    uint32_t step;
+    const uint32_t ex = block_excl_scan<ScanSum, 256>(mine[j], run, sh, &step);
     const int p = t0 + j * 256 + threadIdx.x;
     if (p < executables) {
-      a.comp[p] = (int32_t)(run + ex + mine[j]) - 1;
+      a.comp[p] = (int32_t)(ex + mine[j]) - 1;
       a.order[p] = a.msg_of[a.pairs[p].y];
     }
-    __syncthreads();
-    if (threadIdx.x == 255) sh[7] = ex + mine[j];
-    __syncthreads();
-    run += sh[7];
-    __syncthreads();
+    run += step;
+    __syncthreads();  // every thread has read sh before the next step writes it
   }
   if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) a.ctl[4] = (int32_t)run;
 }

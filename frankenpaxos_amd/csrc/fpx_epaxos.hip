@@ -37,6 +37,10 @@
 #include <vector>
 
 #include "../../include/fpx.h"
+#include "fpx_host.hpp"
+#include "fpx_scan.hpp"
+
+using namespace fpx;
 
 namespace {
 
@@ -272,24 +276,6 @@ __global__ void __launch_bounds__(256) k_rs_scan(const RsArgs a) {
   }
 }
 
-// exclusive prefix of one value per thread over the threads of the workgroup (up to 512; sh: 8 words of LDS)
-__device__ __forceinline__ uint32_t block_excl_sum(uint32_t v, uint32_t* sh) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, nw = blockDim.x >> 6;
-  uint32_t inc = v;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const uint32_t o = __shfl_up(inc, d);
-    if (lane >= d) inc += o;
-  }
-  __syncthreads();
-  if (lane == 63) sh[w] = inc;
-  __syncthreads();
-  uint32_t before = 0;
-  for (int j = 0; j < nw; ++j) before += j < w ? sh[j] : 0u;
-  return before + inc - v;
-}
-__device__ __forceinline__ uint32_t block_excl_sum_256(uint32_t v, uint32_t* sh) { return block_excl_sum(v, sh); }
-
 // 8 wavefronts per tile, each ranks an eighth of it (8 steps of 64): twice the wavefronts per CU of a 4-wavefront
 // version at the same LDS, and half the serial chain per wavefront.  The per-wavefront digit counters / cursors are
 // 16 bits wide (a tile has 4096 elements), two digits per LDS word, updated with 32-bit LDS atomics on the half.
@@ -341,8 +327,8 @@ __global__ void __launch_bounds__(64 * RS_SW) k_rs_scatter(const RsArgs a) {
         all += a.tot[r * B + 2 * p] + (2 * p + 1 < B ? a.tot[r * B + 2 * p + 1] : 0u);
       }
     }
-    uint32_t tstart = block_excl_sum(mine, sh);
-    uint32_t gstart = block_excl_sum(all, sh);
+    uint32_t tstart = block_excl_scan<ScanSum, 64 * RS_SW>(mine, 0u, sh);
+    uint32_t gstart = block_excl_scan<ScanSum, 64 * RS_SW>(all, 0u, sh + RS_SW);  // (other words: no barrier in between)
     for (int j = 0; j < pp; ++j) {
       const int p = p0 + j;
       if (p < npairs) {
@@ -423,7 +409,7 @@ __global__ void __launch_bounds__(256) k_epx_segments_from_totals(const EpxState
   uint32_t mine = 0;
   for (int j = 0; j < per; ++j)
     if (d0 + j < B) mine += tot[r * B + d0 + j];
-  uint32_t start = block_excl_sum_256(mine, sh);
+  uint32_t start = block_excl_scan<ScanSum, 256>(mine, 0u, sh);
   for (int j = 0; j < per; ++j) {
     const int k = d0 + j;
     if (k < B) {
@@ -1038,16 +1024,6 @@ __global__ void __launch_bounds__(256) k_cl_handle(const EpxState st, const ClBa
   }
 }
 
-__device__ __forceinline__ int block_max_256(int v, int* sh) {
-#pragma unroll
-  for (int k = 1; k < 64; k <<= 1) v = imax(v, __shfl_xor(v, k));
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  const int out = imax(imax(sh[0], sh[1]), imax(sh[2], sh[3]));
-  __syncthreads();
-  return out;
-}
-
 __global__ void __launch_bounds__(256) k_cl_tilemax(const ClBatch b, int tiles) {
   __shared__ int sh[4];
   const int r = blockIdx.y, t = blockIdx.x;
@@ -1056,22 +1032,18 @@ __global__ void __launch_bounds__(256) k_cl_tilemax(const ClBatch b, int tiles) 
     const int i = t * CL_TILE + k;
     if (i < b.m) v = imax(v, b.contrib[(size_t)r * b.m + i]);
   }
-  v = block_max_256(v, sh);
+  v = block_reduce<ScanMax, 256>(v, sh);
   if (threadIdx.x == 0) b.tilemax[(size_t)r * tiles + t] = v;
 }
 
-// one block per replica: tilemax -> what the replica had seen BEFORE each tile; the replica's new largestBallot
+// one block per replica: tilemax -> what the replica had seen BEFORE each tile; the replica's new largestBallot.  (ScanMax:
+// ballots are >= 0 and k_cl_tilemax starts from -1, so nothing scanned is below -1.)
 __global__ void __launch_bounds__(256) k_cl_tilescan(const EpxState st, const ClBatch b, int tiles) {
+  __shared__ int lds[SCAN_ARRAY_LDS(256)];
   if (st.status[0] == FPX_EINVAL) return;
   const int r = blockIdx.x;
-  if (threadIdx.x != 0) return;  // tiles <= a few thousand: a serial walk of one thread is microseconds
-  int run = st.largest[r];
-  for (int t = 0; t < tiles; ++t) {
-    const int v = b.tilemax[(size_t)r * tiles + t];
-    b.tilemax[(size_t)r * tiles + t] = run;
-    run = imax(run, v);
-  }
-  st.largest[r] = run;
+  const int run = scan_array_excl<ScanMax, 256, 1>(b.tilemax + (size_t)r * tiles, tiles, lds, st.largest[r]);
+  if (threadIdx.x == 0) st.largest[r] = run;
 }
 
 // the largestBallot a Nack of (i, r) carries = max(before the tile, inclusive prefix inside the tile)
@@ -1400,11 +1372,6 @@ __global__ void __launch_bounds__(256) k_hp_commit(const EpxState st, const HpBa
 #include "fpx_epaxos_mk.hpp"
 #include "fpx_epx_leader.hpp"
 
-struct Buf {
-  void* p = nullptr;
-  size_t cap = 0;
-};
-
 }  // namespace
 
 struct fpx_epx {
@@ -1412,13 +1379,13 @@ struct fpx_epx {
   EpxState st;
   hipStream_t stream = nullptr, own_stream = nullptr;
   int last_hip = 0;
-  Buf kv, kv2, seg, conf, tmp, tick, fusedb, metab;
-  Buf stage;                                               // the arrays of a host-pointer call (host_call)
-  Buf mk_misc, mk_rec, mk_pair, mk_pconf;                  // multi-key commands (fpx_epaxos_mk.hpp)
+  DevBuf kv, kv2, seg, conf, tmp, tick, fusedb, metab;
+  DevBuf stage;                                            // the arrays of a host-pointer call (host_call)
+  DevBuf mk_misc, mk_rec, mk_pair, mk_pconf;               // multi-key commands (fpx_epaxos_mk.hpp)
   int32_t* mk_host = nullptr;                              // page-locked: k_mk_total's line
-  Buf p_fast, p_deps, p_ldeps, p_own;      // the four output arrays when a packed tick goes the first form's way
-  Buf kp_hist, kp_recs, kp_misc;          // K5 second form (fpx_epaxos_kp.hpp)
-  Buf dg_msg, dg_direct, dg_clo, dg_pre, dg_tmax, dg_pairs, dg_pairs2, dg_ctl, dg_key;  // device dependency-graph execution
+  DevBuf p_fast, p_deps, p_ldeps, p_own;   // the four output arrays when a packed tick goes the first form's way
+  DevBuf kp_hist, kp_recs, kp_misc;       // K5 second form (fpx_epaxos_kp.hpp)
+  DevBuf dg_msg, dg_direct, dg_clo, dg_pre, dg_tmax, dg_pairs, dg_pairs2, dg_ctl, dg_key;  // device dependency-graph execution
   int32_t dg_seq = 0;
   int dg_rounds_hint = 8;                 // closure rounds the first chunk of the next fpx_epx_execute_dev enqueues (DG_ROUNDS at first)
   uint32_t* kp_flag = nullptr;            // page-locked: [0] sequence number of the tick whose count [1] is valid
@@ -1427,52 +1394,12 @@ struct fpx_epx {
   bool kp_lds_allowed = false, kp_off = false;
   uint32_t cl_run = 0;
   EpxLeader ls = {nullptr, nullptr};      // FPX_EPX_F_LEADER_STATE: Replica.leaderStates (fpx_epx_leader.hpp), else not allocated
-  Buf lr_misc;                            // fpx_epx_leader_replies: the decided flags and the compaction's block counts
+  DevBuf lr_misc;                         // fpx_epx_leader_replies: the decided flags and the compaction's block counts
   bool lds_allowed = false, sort_lds_allowed = false;
   int num_cus = 256;
 };
 
 namespace {
-
-// the context's device is current inside every entry point, the caller's is restored on return (see fpx_api.hip)
-struct EpxDeviceGuard {
-  int prev = -1;
-  bool switched = false;
-  explicit EpxDeviceGuard(int device) {
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    if (prev != device) switched = hipSetDevice(device) == hipSuccess;
-  }
-  ~EpxDeviceGuard() {
-    if (switched && prev >= 0) (void)hipSetDevice(prev);
-  }
-};
-
-#define EHIP(e, expr)                                            \
-  do {                                                           \
-    hipError_t _x = (expr);                                      \
-    if (_x != hipSuccess) {                                      \
-      (e)->last_hip = (int)_x;                                   \
-      return _x == hipErrorOutOfMemory ? FPX_ENOMEM : FPX_EHIP;  \
-    }                                                            \
-  } while (0)
-
-int grow(fpx_epx* e, Buf* b, size_t bytes) {
-  if (bytes <= b->cap) return FPX_OK;
-  if (b->p) EHIP(e, hipFree(b->p));
-  b->p = nullptr, b->cap = 0;
-  EHIP(e, hipMalloc(&b->p, std::max<size_t>(bytes, 256)));
-  b->cap = std::max<size_t>(bytes, 256);
-  return FPX_OK;
-}
-
-int launch_check(fpx_epx* e) {
-  hipError_t le = hipGetLastError();
-  if (le != hipSuccess) {
-    e->last_hip = (int)le;
-    return FPX_EHIP;
-  }
-  return FPX_OK;
-}
 
 // f(std::integral_constant<int, n>) for the replica counts a context can have (3, 5, 7)
 template <typename F>
@@ -1488,7 +1415,7 @@ auto by_n(int n, F&& f) {
 // instances of one batch must be distinct
 int next_run_id(fpx_epx* e, uint32_t* id) {
   if (++e->cl_run == 0) {  // stamp space exhausted: start over
-    EHIP(e, hipMemsetAsync(e->st.cl_stamp, 0, (size_t)e->st.n * e->st.num_instances * 4, e->stream));
+    HIPCHK(e, hipMemsetAsync(e->st.cl_stamp, 0, (size_t)e->st.n * e->st.num_instances * 4, e->stream));
     e->cl_run = 1;
   }
   *id = e->cl_run;
@@ -1554,7 +1481,7 @@ int host_call(fpx_epx* e, std::initializer_list<Staged> arrays, Launch launch) {
   char* p = base;
   for (const Staged& a : arrays) {
     a.place(a.slot, p);
-    if (a.src && a.bytes) EHIP(e, hipMemcpyAsync(p, a.src, a.bytes, hipMemcpyHostToDevice, e->stream));
+    if (a.src && a.bytes) HIPCHK(e, hipMemcpyAsync(p, a.src, a.bytes, hipMemcpyHostToDevice, e->stream));
     p += a.span();
   }
   char* run = nullptr;  // [run, p) is filled with the byte `value`
@@ -1562,16 +1489,16 @@ int host_call(fpx_epx* e, std::initializer_list<Staged> arrays, Launch launch) {
   p = base;
   for (const Staged& a : arrays) {
     if (a.fill != value) {
-      if (value != NO_FILL) EHIP(e, hipMemsetAsync(run, value, p - run, e->stream));
+      if (value != NO_FILL) HIPCHK(e, hipMemsetAsync(run, value, p - run, e->stream));
       run = p, value = a.fill;
     }
     p += a.span();
   }
-  if (value != NO_FILL) EHIP(e, hipMemsetAsync(run, value, p - run, e->stream));
+  if (value != NO_FILL) HIPCHK(e, hipMemsetAsync(run, value, p - run, e->stream));
   if ((rc = launch()) || (rc = launch_check(e))) return rc;
   p = base;
   for (const Staged& a : arrays) {
-    if (a.dst && a.bytes) EHIP(e, hipMemcpyAsync(a.dst, p, a.bytes, hipMemcpyDeviceToHost, e->stream));
+    if (a.dst && a.bytes) HIPCHK(e, hipMemcpyAsync(a.dst, p, a.bytes, hipMemcpyDeviceToHost, e->stream));
     p += a.span();
   }
   return fpx_epx_sync(e);
@@ -1675,7 +1602,7 @@ int launch_kp(fpx_epx* e, const EpxBatch& b, int32_t* d_packed, bool* done) {
     const size_t need = 1024 + (size_t)a.B * KP_TOT_STRIDE * 4;
     if (need > e->kp_misc.cap) {
       if ((rc = grow(e, &e->kp_misc, need))) return rc;
-      EHIP(e, hipMemsetAsync(e->kp_misc.p, 0, e->kp_misc.cap, e->stream));
+      HIPCHK(e, hipMemsetAsync(e->kp_misc.p, 0, e->kp_misc.cap, e->stream));
     }
   }
   char* misc = (char*)e->kp_misc.p;
@@ -1725,7 +1652,7 @@ int launch_kp(fpx_epx* e, const EpxBatch& b, int32_t* d_packed, bool* done) {
     if ((spin & 0xffff) == 0xffff && hipStreamQuery(ps) != hipErrorNotReady) break;  // finished, or failed
   }
   if (!seen) {
-    EHIP(e, hipStreamSynchronize(ps));
+    HIPCHK(e, hipStreamSynchronize(ps));
     if (flag[0] != a.seq) return FPX_EHIP;
   }
   if (flag[1] != 0) return FPX_OK;  // a hot key: the first form takes the whole tick
@@ -1858,18 +1785,18 @@ int dg_run(fpx_epx* e, Form& form, int m, const int32_t* d_leader, const int32_t
         if (q != hipErrorNotReady) break;
       }
     }
-    EHIP(e, hipStreamSynchronize(e->stream));
+    HIPCHK(e, hipStreamSynchronize(e->stream));
     return host[7] == want ? FPX_OK : FPX_EHIP;
   };
-  EHIP(e, hipMemsetAsync(a.msg_of, 0xFF, (size_t)m * 4, e->stream));
-  EHIP(e, hipMemsetAsync(a.ctl, 0, 256, e->stream));
+  HIPCHK(e, hipMemsetAsync(a.msg_of, 0xFF, (size_t)m * 4, e->stream));
+  HIPCHK(e, hipMemsetAsync(a.ctl, 0, 256, e->stream));
   form.before_rounds(e->stream, grid);
   const Clo clo = form.closures();
   int enqueued = 0, executables = 0;
   for (int chunk = 0;; ++chunk) {
     // A chunk of closure rounds at once: a round returns at its first instruction when the one before it moved nothing,
     // and everything behind them is enqueued right away -- one host read per chunk, and a full chunk covers 2^8 hops
-    if (chunk > 0) EHIP(e, hipMemsetAsync(a.ctl + 8, 0, (DG_ROUNDS + 1) * 4, e->stream));
+    if (chunk > 0) HIPCHK(e, hipMemsetAsync(a.ctl + 8, 0, (DG_ROUNDS + 1) * 4, e->stream));
     // How many rounds to enqueue: a round that finds "the one before moved nothing" leaves at its first instruction, but it
     // is still a launch (and its second kernel another): ~8 us per skipped round, four of them per FIFO tick.  The first
     // chunk enqueues one round more than moved something in the context's previous call (ticks of one deployment need the
@@ -1900,7 +1827,7 @@ int dg_run(fpx_epx* e, Form& form, int m, const int32_t* d_leader, const int32_t
     e->dg_rounds_hint = host[5] != 0 ? DG_ROUNDS : host[6] + 1;
     if (a.count_moved) {
       int32_t dbg[64];
-      EHIP(e, hipMemcpy(dbg, a.ctl, sizeof(dbg), hipMemcpyDeviceToHost));
+      HIPCHK(e, hipMemcpy(dbg, a.ctl, sizeof(dbg), hipMemcpyDeviceToHost));
       fprintf(stderr, "libfpx: depgraph (%s) chunk %d, vertices moved per round:", Form::name, chunk);
       for (int k = 1; k <= DG_ROUNDS; ++k) fprintf(stderr, " %d", dbg[24 + k]);
       fprintf(stderr, " (%d rounds enqueued)\n", rounds);
@@ -1971,7 +1898,7 @@ int32_t fpx_epx_create(const fpx_epx_config* cfg, fpx_epx** out) {
     fpx_epx_destroy(e);
     return code;
   };
-  EpxDeviceGuard _dg(cfg->device);
+  DeviceScope _dg(cfg->device);
   if (hipSetDevice(cfg->device) != hipSuccess) return fail(FPX_ENODEVICE);
   if (hipStreamCreateWithFlags(&e->own_stream, hipStreamNonBlocking) != hipSuccess) return fail(FPX_EHIP);
   e->stream = e->own_stream;
@@ -2033,19 +1960,19 @@ int32_t fpx_epx_create(const fpx_epx_config* cfg, fpx_epx** out) {
 
 int32_t fpx_epx_destroy(fpx_epx* e) {
   if (!e) return FPX_EINVAL;
-  EpxDeviceGuard _dg(e->cfg.device);
+  DeviceScope _dg(e->cfg.device);
   if (e->stream) (void)hipStreamSynchronize(e->stream);
   void* ps[] = {e->st.gets, e->st.sets, e->st.status, e->st.cl_status, e->st.cl_ballot, e->st.cl_vote, e->st.cl_triple,
                 e->st.largest, e->st.cl_stamp, e->st.cl_deps, e->st.cl_dend, e->ls.head, e->ls.resp};
   for (void* p : ps)
     if (p) (void)hipFree(p);
-  Buf* bs[] = {&e->kv, &e->kv2, &e->seg, &e->conf, &e->tmp, &e->tick, &e->fusedb, &e->metab, &e->stage, &e->mk_misc, &e->mk_rec,
-               &e->mk_pair, &e->mk_pconf, &e->lr_misc};
-  for (Buf* b : bs)
+  DevBuf* bs[] = {&e->kv, &e->kv2, &e->seg, &e->conf, &e->tmp, &e->tick, &e->fusedb, &e->metab, &e->stage, &e->mk_misc, &e->mk_rec,
+                  &e->mk_pair, &e->mk_pconf, &e->lr_misc};
+  for (DevBuf* b : bs)
     if (b->p) (void)hipFree(b->p);
   if (e->mk_host) (void)hipHostFree(e->mk_host);
-  for (Buf* b : {&e->kp_hist, &e->kp_recs, &e->kp_misc, &e->p_fast, &e->p_deps, &e->p_ldeps, &e->p_own, &e->dg_msg, &e->dg_direct,
-                 &e->dg_clo, &e->dg_pre, &e->dg_tmax, &e->dg_pairs, &e->dg_pairs2, &e->dg_ctl, &e->dg_key})
+  for (DevBuf* b : {&e->kp_hist, &e->kp_recs, &e->kp_misc, &e->p_fast, &e->p_deps, &e->p_ldeps, &e->p_own, &e->dg_msg, &e->dg_direct,
+                    &e->dg_clo, &e->dg_pre, &e->dg_tmax, &e->dg_pairs, &e->dg_pairs2, &e->dg_ctl, &e->dg_key})
     if (b->p) (void)hipFree(b->p);
   if (e->kp_flag) (void)hipHostFree(e->kp_flag);
   if (e->own_stream) (void)hipStreamDestroy(e->own_stream);
@@ -2055,21 +1982,21 @@ int32_t fpx_epx_destroy(fpx_epx* e) {
 
 int32_t fpx_epx_set_stream(fpx_epx* e, void* hip_stream) {
   if (!e) return FPX_EINVAL;
-  EpxDeviceGuard _dg(e->cfg.device);
-  EHIP(e, hipStreamSynchronize(e->stream));
+  DeviceScope _dg(e->cfg.device);
+  HIPCHK(e, hipStreamSynchronize(e->stream));
   e->stream = hip_stream == FPX_STREAM_OWN ? e->own_stream : (hipStream_t)hip_stream;
   return FPX_OK;
 }
 
 int32_t fpx_epx_sync(fpx_epx* e) {
   if (!e) return FPX_EINVAL;
-  EpxDeviceGuard _dg(e->cfg.device);
+  DeviceScope _dg(e->cfg.device);
   int32_t h[2] = {0, 0};
-  EHIP(e, hipMemcpyAsync(h, e->st.status, sizeof(h), hipMemcpyDeviceToHost, e->stream));
-  EHIP(e, hipStreamSynchronize(e->stream));
+  HIPCHK(e, hipMemcpyAsync(h, e->st.status, sizeof(h), hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(e, hipStreamSynchronize(e->stream));
   if (h[0] != 0) {
-    EHIP(e, hipMemsetAsync(e->st.status, 0, 32, e->stream));
-    EHIP(e, hipStreamSynchronize(e->stream));
+    HIPCHK(e, hipMemsetAsync(e->st.status, 0, 32, e->stream));
+    HIPCHK(e, hipStreamSynchronize(e->stream));
   }
   return h[0];
 }
@@ -2092,7 +2019,7 @@ static int32_t preaccept_dev_impl(fpx_epx* e, int32_t m, const int32_t* d_leader
                                   uint8_t* d_fast, int32_t* d_deps, int32_t* d_leader_deps, int32_t* d_own_values_end,
                                   int32_t* d_packed) {
   if (!e || m < 0) return FPX_EINVAL;
-  EpxDeviceGuard _dg(e->cfg.device);
+  DeviceScope _dg(e->cfg.device);
   if (m == 0) return FPX_OK;
   const int n = e->st.n;
   int rc;
@@ -2159,7 +2086,7 @@ int32_t fpx_epx_execute_dev(fpx_epx* e, int32_t m, const int32_t* d_leader, cons
                             const uint8_t* d_committed, const int32_t* first, const int32_t* count, int32_t* d_order,
                             int32_t* d_component, int64_t* num_executed, int64_t* num_components, int32_t* needs_host_path) {
   if (!e || m < 0 || !first || !count || (m > 0 && (!d_leader || !d_number || !d_packed || !d_order || !d_component))) return FPX_EINVAL;
-  EpxDeviceGuard _dg(e->cfg.device);
+  DeviceScope _dg(e->cfg.device);
   if (num_executed) *num_executed = 0;
   if (num_components) *num_components = 0;
   if (needs_host_path) *needs_host_path = 0;
@@ -2176,7 +2103,7 @@ int32_t fpx_epx_execute(fpx_epx* e, int32_t m, const int32_t* leader, const int3
                         int32_t* order, int32_t* component, int64_t* num_executed, int64_t* num_components,
                         int32_t* needs_host_path) {
   if (!e || m < 0 || !first || !count || (m > 0 && (!leader || !number || !deps || !order || !component))) return FPX_EINVAL;
-  EpxDeviceGuard _dg(e->cfg.device);
+  DeviceScope _dg(e->cfg.device);
   if (num_executed) *num_executed = 0;
   if (num_components) *num_components = 0;
   if (needs_host_path) *needs_host_path = 0;
@@ -2199,16 +2126,16 @@ int32_t fpx_epx_execute(fpx_epx* e, int32_t m, const int32_t* leader, const int3
   const uint8_t* d_mask;
   int32_t *d_order, *d_comp;
   auto launch = [&]() -> int {
-    EHIP(e, hipStreamSynchronize(e->stream));  // (the host arrays and `lines` may be pageable)
+    HIPCHK(e, hipStreamSynchronize(e->stream));  // (the host arrays and `lines` may be pageable)
     int64_t ne = 0, nc = 0;
     int32_t nh = 0;
     const int rc = fpx_epx_execute_dev(e, m, d_leader, d_number, d_packed, committed ? d_mask : nullptr, first, count, d_order,
                                        d_comp, &ne, &nc, &nh);
     if (rc) return rc;
     if (ne > 0 && !nh) {  // (the executed entries only)
-      EHIP(e, hipMemcpyAsync(order, d_order, (size_t)ne * 4, hipMemcpyDeviceToHost, e->stream));
-      EHIP(e, hipMemcpyAsync(component, d_comp, (size_t)ne * 4, hipMemcpyDeviceToHost, e->stream));
-      EHIP(e, hipStreamSynchronize(e->stream));
+      HIPCHK(e, hipMemcpyAsync(order, d_order, (size_t)ne * 4, hipMemcpyDeviceToHost, e->stream));
+      HIPCHK(e, hipMemcpyAsync(component, d_comp, (size_t)ne * 4, hipMemcpyDeviceToHost, e->stream));
+      HIPCHK(e, hipStreamSynchronize(e->stream));
     }
     if (num_executed) *num_executed = ne;
     if (num_components) *num_components = nc;
@@ -2245,14 +2172,15 @@ static int32_t preaccept_mk_impl(fpx_epx* e, int32_t m, const int32_t* d_leader,
                                  const uint8_t* d_seen_mask, const int32_t* d_rank, const int32_t* d_triple_id, uint8_t* d_fast,
                                  int32_t* d_deps, int32_t* d_leader_deps, int32_t* d_own_values_end, int32_t* d_packed) {
   if (!e || m < 0) return FPX_EINVAL;
-  EpxDeviceGuard _dg(e->cfg.device);
+  DeviceScope _dg(e->cfg.device);
   if (m == 0) return FPX_OK;
   if (!d_off) return FPX_EINVAL;
   const int n = e->st.n;
   const int tiles = (m + MK_TILE - 1) / MK_TILE;
   int rc;
   const int blocks = (m + 255) / 256;
-  if ((rc = grow(e, &e->mk_misc, 64 + (size_t)m * 4 + (size_t)n * tiles * 4 + (size_t)blocks * 8 + 16))) return rc;
+  MkPrologueScratch ps;
+  if ((rc = carve(e, &e->mk_misc, &ps, [&](Carver& c) { return lay_mk_prologue(c, m, n, tiles, blocks); }))) return rc;
   if (!e->mk_host && hipHostMalloc((void**)&e->mk_host, 64, hipHostMallocDefault) != hipSuccess) {
     e->mk_host = nullptr;
     return FPX_ENOMEM;
@@ -2261,14 +2189,13 @@ static int32_t preaccept_mk_impl(fpx_epx* e, int32_t m, const int32_t* d_leader,
   memset(&mb, 0, sizeof(mb));
   mb.m = m, mb.tiles = tiles, mb.off = d_off, mb.keys = d_keys, mb.leader = d_leader, mb.number = d_number;
   mb.is_set = d_is_set, mb.resp_mask = d_resp_mask, mb.seen_mask = d_seen_mask, mb.rank = d_rank;
-  mb.info = (int32_t*)e->mk_misc.p, mb.ucnt = mb.info + 16, mb.tsum = (uint32_t*)(mb.ucnt + m);
-  mb.part = (int2*)(((uintptr_t)(mb.tsum + (size_t)n * tiles) + 15) & ~(uintptr_t)15);
+  mb.info = ps.info, mb.ucnt = ps.ucnt, mb.tsum = ps.tsum, mb.part = (int2*)ps.part;
   const dim3 gm(blocks), blk(256);
   hipLaunchKernelGGL(k_mk_prep, gm, blk, 0, e->stream, e->st, mb);
   hipLaunchKernelGGL(k_mk_total, dim3(1), blk, 0, e->stream, e->st, mb, blocks);
   int32_t* h = e->mk_host;  // page-locked
-  EHIP(e, hipMemcpyAsync(h, mb.info, 16, hipMemcpyDeviceToHost, e->stream));
-  EHIP(e, hipStreamSynchronize(e->stream));
+  HIPCHK(e, hipMemcpyAsync(h, mb.info, 16, hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(e, hipStreamSynchronize(e->stream));
   if (h[3] != 0) return fpx_epx_sync(e);  // (returns the status and clears it)
   const int U = h[0], P = h[2];
   if (P > FPX_EPX_MK_MAX_PAIRS) return FPX_EINVAL;
@@ -2278,7 +2205,8 @@ static int32_t preaccept_mk_impl(fpx_epx* e, int32_t m, const int32_t* d_leader,
   if (d_packed && (rc = packed_fallback(e, m, &d_fast, &d_deps, &d_leader_deps, &d_own_values_end))) return rc;
   const int NP = n <= 4 ? 4 : 8, Ux = std::max(U, 1);
   if ((rc = grow(e, &e->mk_rec, (size_t)n * m * 16))) return rc;
-  if ((rc = grow(e, &e->mk_pair, (size_t)std::max(P, 1) * 5 + 64))) return rc;
+  MkPairScratch pairs;
+  if ((rc = carve(e, &e->mk_pair, &pairs, [&](Carver& c) { return lay_mk_pairs(c, P); }))) return rc;
   if ((rc = grow(e, &e->mk_pconf, (size_t)std::max(P, 1) * n * NP * 4))) return rc;
   if ((rc = grow(e, &e->kv, (size_t)n * Ux * 8))) return rc;
   if ((rc = grow(e, &e->kv2, (size_t)n * Ux * 8))) return rc;
@@ -2286,7 +2214,7 @@ static int32_t preaccept_mk_impl(fpx_epx* e, int32_t m, const int32_t* d_leader,
   if ((rc = grow(e, &e->seg, (size_t)n * e->st.num_keys * 8))) return rc;
   if ((rc = grow(e, &e->conf, (size_t)m * n * NP * 4))) return rc;
   mb.P = P, mb.U = U, mb.rec = (int4*)e->mk_rec.p, mb.kv = (uint2*)e->kv.p;
-  mb.pnum = (int32_t*)e->mk_pair.p, mb.uniq = (uint8_t*)e->mk_pair.p + (size_t)std::max(P, 1) * 4;
+  mb.pnum = pairs.pnum, mb.uniq = pairs.uniq;
   hipLaunchKernelGGL(k_mk_pairs, gm, blk, 0, e->stream, mb);
   hipLaunchKernelGGL(k_mk_place, gm, blk, 0, e->stream, e->st, mb);
   hipLaunchKernelGGL(k_mk_tilesum, dim3(tiles, n), blk, 0, e->stream, mb);
@@ -2351,7 +2279,7 @@ static int32_t preaccept_host(fpx_epx* e, int32_t m, const int32_t* leader, cons
                               const uint8_t* seen_mask, const int32_t* rank, const int32_t* triple_id, uint8_t* fast,
                               int32_t* deps, int32_t* leader_deps, int32_t* own_values_end) {
   if (!e || m < 0 || (m > 0 && (!leader || !number || !(key || key_off) || !is_set || !resp_mask || !rank))) return FPX_EINVAL;
-  EpxDeviceGuard _dg(e->cfg.device);
+  DeviceScope _dg(e->cfg.device);
   if (m == 0) return FPX_OK;
   const int n = e->st.n;
   int64_t P = 0;
@@ -2401,7 +2329,7 @@ static int32_t cl_run(fpx_epx* e, int accept, int32_t m, const int32_t* leader, 
                       int32_t* reply_vote, int32_t* reply_triple, const int32_t* key_off = nullptr,
                       const int32_t* keys = nullptr) {
   if (!e || m < 0) return FPX_EINVAL;
-  EpxDeviceGuard _dg(e->cfg.device);
+  DeviceScope _dg(e->cfg.device);
   if (e->st.num_instances <= 0) return FPX_EINVAL;
   if (m == 0) return FPX_OK;
   if (!leader || !number || !b_ord || !b_rep || !target || (accept && (!triple || !(key || key_off) || !is_set))) return FPX_EINVAL;
@@ -2458,7 +2386,7 @@ static int32_t handle_commit_impl(fpx_epx* e, int32_t m, const int32_t* leader, 
                                   const int32_t* key, const int32_t* key_off, const int32_t* keys, const uint8_t* is_set,
                                   const int32_t* deps, const int32_t* deps_values_end, const uint8_t* target_mask) {
   if (!e || m < 0) return FPX_EINVAL;
-  EpxDeviceGuard _dg(e->cfg.device);
+  DeviceScope _dg(e->cfg.device);
   if (e->st.num_instances <= 0) return FPX_EINVAL;
   if (m == 0) return FPX_OK;
   if (!leader || !number || !triple_id || !(key || key_off) || !is_set || !target_mask) return FPX_EINVAL;
@@ -2522,7 +2450,7 @@ int32_t fpx_epx_handle_prepare_oks(fpx_epx* e, int32_t m, const int32_t* leader,
                                    const int32_t* reply_status, const int32_t* reply_vote_ballot, const int32_t* reply_triple,
                                    int32_t as_intended, int32_t* action, int32_t* source, int32_t* triple) {
   if (!e || m < 0) return FPX_EINVAL;
-  EpxDeviceGuard _dg(e->cfg.device);
+  DeviceScope _dg(e->cfg.device);
   if (e->st.num_instances <= 0) return FPX_EINVAL;
   if (m == 0) return FPX_OK;
   if (!leader || !number || !ballot_ordering || !ballot_replica || !resp_mask || !reply_status || !reply_vote_ballot || !reply_triple)
@@ -2562,7 +2490,7 @@ static int32_t handle_preaccept_impl(fpx_epx* e, int32_t m, const int32_t* leade
                                      uint8_t* resend_bits, uint8_t* nack_bits, uint8_t* commit_bits, int32_t* nack_ballot,
                                      int32_t* reply_deps, int32_t* reply_values_end, int32_t* reply_triple) {
   if (!e || m < 0) return FPX_EINVAL;
-  EpxDeviceGuard _dg(e->cfg.device);
+  DeviceScope _dg(e->cfg.device);
   if (e->st.num_instances <= 0) return FPX_EINVAL;
   if (m == 0) return FPX_OK;
   if (!leader || !number || !ballot_ordering || !ballot_replica || !(key || key_off) || !is_set || !deps_in || !target_mask)
@@ -2581,8 +2509,9 @@ static int32_t handle_preaccept_impl(fpx_epx* e, int32_t m, const int32_t* leade
   if ((rc = grow(e, &e->tick, (size_t)n * e->st.num_keys * 2 * n * 4))) return rc;
   if ((rc = grow(e, &e->seg, (size_t)n * e->st.num_keys * 8))) return rc;
   if ((rc = grow(e, &e->conf, (size_t)m * n * NP * 4))) return rc;
+  MkPairScratch pairs = {nullptr, nullptr};
   if (key_off) {
-    if ((rc = grow(e, &e->mk_pair, (size_t)std::max(P, 1) * 5 + 64))) return rc;
+    if ((rc = carve(e, &e->mk_pair, &pairs, [&](Carver& c) { return lay_mk_pairs(c, P); }))) return rc;
     if ((rc = grow(e, &e->mk_pconf, (size_t)std::max(P, 1) * n * NP * 4))) return rc;
   }
   const int32_t *d_leader, *d_number, *d_bo, *d_br, *d_key, *d_tr, *d_dend, *d_din, *d_off, *d_keys;
@@ -2596,7 +2525,7 @@ static int32_t handle_preaccept_impl(fpx_epx* e, int32_t m, const int32_t* leade
     if (key_off) {
       d_pconf = (int32_t*)e->mk_pconf.p;
       mb.m = m, mb.P = P, mb.off = d_off, mb.keys = d_keys, mb.number = d_number;
-      mb.pnum = (int32_t*)e->mk_pair.p, mb.uniq = (uint8_t*)e->mk_pair.p + (size_t)std::max(P, 1) * 4;
+      mb.pnum = pairs.pnum, mb.uniq = pairs.uniq;
     }
     HpBatch hb;
     memset(&hb, 0, sizeof(hb));
@@ -2656,11 +2585,11 @@ int32_t fpx_epx_read_cmdlog_deps(fpx_epx* e, int32_t replica, int32_t leader, in
   if (!e || !deps || !values_end || e->st.num_instances <= 0 || replica < 0 || replica >= e->st.n || leader < 0 ||
       leader >= e->st.n || number < 0 || number >= e->st.num_instances)
     return FPX_EINVAL;
-  EpxDeviceGuard _dg(e->cfg.device);
+  DeviceScope _dg(e->cfg.device);
   const size_t c = ((size_t)replica * e->st.n + leader) * e->st.num_instances + number;
-  EHIP(e, hipStreamSynchronize(e->stream));
-  EHIP(e, hipMemcpy(deps, e->st.cl_deps + c * e->st.n, (size_t)e->st.n * 4, hipMemcpyDeviceToHost));
-  EHIP(e, hipMemcpy(values_end, e->st.cl_dend + c, 4, hipMemcpyDeviceToHost));
+  HIPCHK(e, hipStreamSynchronize(e->stream));
+  HIPCHK(e, hipMemcpy(deps, e->st.cl_deps + c * e->st.n, (size_t)e->st.n * 4, hipMemcpyDeviceToHost));
+  HIPCHK(e, hipMemcpy(values_end, e->st.cl_dend + c, 4, hipMemcpyDeviceToHost));
   return FPX_OK;
 }
 
@@ -2668,16 +2597,16 @@ int32_t fpx_epx_read_cmdlog(fpx_epx* e, int32_t replica, int32_t leader, int32_t
   if (!e || !out || e->st.num_instances <= 0 || replica < 0 || replica >= e->st.n || leader < 0 || leader >= e->st.n ||
       number < 0 || number >= e->st.num_instances)
     return FPX_EINVAL;
-  EpxDeviceGuard _dg(e->cfg.device);
+  DeviceScope _dg(e->cfg.device);
   const size_t c = ((size_t)replica * e->st.n + leader) * e->st.num_instances + number;
   uint8_t kind = 0;
-  EHIP(e, hipStreamSynchronize(e->stream));
-  EHIP(e, hipMemcpy(&kind, e->st.cl_status + c, 1, hipMemcpyDeviceToHost));
+  HIPCHK(e, hipStreamSynchronize(e->stream));
+  HIPCHK(e, hipMemcpy(&kind, e->st.cl_status + c, 1, hipMemcpyDeviceToHost));
   out[0] = kind;
-  EHIP(e, hipMemcpy(&out[1], e->st.cl_ballot + c, 4, hipMemcpyDeviceToHost));
-  EHIP(e, hipMemcpy(&out[2], e->st.cl_vote + c, 4, hipMemcpyDeviceToHost));
-  EHIP(e, hipMemcpy(&out[3], e->st.cl_triple + c, 4, hipMemcpyDeviceToHost));
-  EHIP(e, hipMemcpy(&out[4], e->st.largest + replica, 4, hipMemcpyDeviceToHost));
+  HIPCHK(e, hipMemcpy(&out[1], e->st.cl_ballot + c, 4, hipMemcpyDeviceToHost));
+  HIPCHK(e, hipMemcpy(&out[2], e->st.cl_vote + c, 4, hipMemcpyDeviceToHost));
+  HIPCHK(e, hipMemcpy(&out[3], e->st.cl_triple + c, 4, hipMemcpyDeviceToHost));
+  HIPCHK(e, hipMemcpy(&out[4], e->st.largest + replica, 4, hipMemcpyDeviceToHost));
   return FPX_OK;
 }
 
@@ -2691,11 +2620,11 @@ int32_t fpx_epx_info(fpx_epx* e, int32_t* num_replicas, int32_t* num_keys, int32
 
 int32_t fpx_epx_read_index(fpx_epx* e, int32_t replica, int32_t key, int32_t* gets, int32_t* sets) {
   if (!e || replica < 0 || replica >= e->st.n || key < 0 || key >= e->st.num_keys) return FPX_EINVAL;
-  EpxDeviceGuard _dg(e->cfg.device);
+  DeviceScope _dg(e->cfg.device);
   const size_t off = ((size_t)replica * e->st.num_keys + key) * e->st.n;
-  EHIP(e, hipStreamSynchronize(e->stream));
-  if (gets) EHIP(e, hipMemcpy(gets, e->st.gets + off, (size_t)e->st.n * 4, hipMemcpyDeviceToHost));
-  if (sets) EHIP(e, hipMemcpy(sets, e->st.sets + off, (size_t)e->st.n * 4, hipMemcpyDeviceToHost));
+  HIPCHK(e, hipStreamSynchronize(e->stream));
+  if (gets) HIPCHK(e, hipMemcpy(gets, e->st.gets + off, (size_t)e->st.n * 4, hipMemcpyDeviceToHost));
+  if (sets) HIPCHK(e, hipMemcpy(sets, e->st.sets + off, (size_t)e->st.n * 4, hipMemcpyDeviceToHost));
   return FPX_OK;
 }
 
@@ -2751,7 +2680,7 @@ int32_t fpx_epx_lead(fpx_epx* e, int32_t m, const int32_t* leader, const int32_t
                      const int32_t* ballot_ordering, const int32_t* key, const uint8_t* is_set, const int32_t* triple_id,
                      const uint8_t* avoid_fast_path, int32_t* deps, int32_t* deps_values_end) {
   if (!e || m < 0 || !leader_state_on(e)) return FPX_EINVAL;
-  EpxDeviceGuard _dg(e->cfg.device);
+  DeviceScope _dg(e->cfg.device);
   if (m == 0) return FPX_OK;
   if (!leader || !number || !at || !ballot_ordering || !key || !is_set || !triple_id || !avoid_fast_path) return FPX_EINVAL;
   const int n = e->st.n;
@@ -2834,9 +2763,9 @@ static int32_t leader_replies_launch(fpx_epx* e, int32_t m, const int32_t* d_kin
   int rc;
   if ((rc = grow(e, &e->kv, (size_t)m * 8))) return rc;
   if ((rc = grow(e, &e->kv2, (size_t)m * 8))) return rc;
-  const size_t flag_bytes = ((size_t)m + 255) & ~(size_t)255;
-  if ((rc = grow(e, &e->lr_misc, flag_bytes + (size_t)b.blocks * 4))) return rc;
-  b.kv = (uint2*)e->kv.p, b.flag = (uint8_t*)e->lr_misc.p, b.bsum = (uint32_t*)((char*)e->lr_misc.p + flag_bytes);
+  LrScratch ls;
+  if ((rc = carve(e, &e->lr_misc, &ls, [&](Carver& c) { return lay_leader_replies(c, m, b.blocks); }))) return rc;
+  b.kv = (uint2*)e->kv.p, b.flag = ls.flag, b.bsum = ls.bsum;
   const dim3 gm((m + 255) / 256), blk(256);
   hipLaunchKernelGGL(k_lr_validate, gm, blk, 0, e->stream, e->st, b);
   unsigned bits = 1;  // the cells of the context: (to, leader, number)
@@ -2859,9 +2788,9 @@ int32_t fpx_epx_leader_replies_dev(fpx_epx* e, int32_t m, const int32_t* d_kind,
                                    int32_t* d_out_values_end, int32_t* d_out_triple, int32_t* d_decided_index,
                                    int32_t* d_num_decided) {
   if (!e || m < 0 || m >= (1 << 30) || !leader_state_on(e)) return FPX_EINVAL;
-  EpxDeviceGuard _dg(e->cfg.device);
+  DeviceScope _dg(e->cfg.device);
   if (m == 0) {
-    if (d_num_decided) EHIP(e, hipMemsetAsync(d_num_decided, 0, 4, e->stream));
+    if (d_num_decided) HIPCHK(e, hipMemsetAsync(d_num_decided, 0, 4, e->stream));
     return FPX_OK;
   }
   if (!d_kind || !d_to || !d_leader || !d_number || !d_ballot_ordering || !d_ballot_replica || !d_replica_index || !d_deps)
@@ -2878,7 +2807,7 @@ int32_t fpx_epx_leader_replies(fpx_epx* e, int32_t m, const int32_t* kind, const
                                const int32_t* deps_values_end, int32_t* outcome, int32_t* out_seq, int32_t* out_deps,
                                int32_t* out_values_end, int32_t* out_triple, int32_t* decided_index, int32_t* num_decided) {
   if (!e || m < 0 || m >= (1 << 30) || !leader_state_on(e)) return FPX_EINVAL;
-  EpxDeviceGuard _dg(e->cfg.device);
+  DeviceScope _dg(e->cfg.device);
   if (m == 0) {
     if (num_decided) *num_decided = 0;
     return FPX_OK;
@@ -2923,21 +2852,21 @@ int32_t fpx_epx_read_leader_state(fpx_epx* e, int32_t replica, int32_t leader, i
   if (!leader_state_on(e) || !out || replica < 0 || replica >= e->st.n || leader < 0 || leader >= e->st.n || number < 0 ||
       number >= e->st.num_instances)
     return FPX_EINVAL;
-  EpxDeviceGuard _dg(e->cfg.device);
+  DeviceScope _dg(e->cfg.device);
   const int n = e->st.n;
   const size_t c = ((size_t)replica * n + leader) * e->st.num_instances + number;
   int32_t h[4], ballot = 0, vote = 0;
   uint8_t kind = 0;
-  EHIP(e, hipStreamSynchronize(e->stream));
-  EHIP(e, hipMemcpy(h, e->ls.head + c, 16, hipMemcpyDeviceToHost));
-  EHIP(e, hipMemcpy(&kind, e->st.cl_status + c, 1, hipMemcpyDeviceToHost));
-  EHIP(e, hipMemcpy(&ballot, e->st.cl_ballot + c, 4, hipMemcpyDeviceToHost));
-  EHIP(e, hipMemcpy(&vote, e->st.cl_vote + c, 4, hipMemcpyDeviceToHost));
+  HIPCHK(e, hipStreamSynchronize(e->stream));
+  HIPCHK(e, hipMemcpy(h, e->ls.head + c, 16, hipMemcpyDeviceToHost));
+  HIPCHK(e, hipMemcpy(&kind, e->st.cl_status + c, 1, hipMemcpyDeviceToHost));
+  HIPCHK(e, hipMemcpy(&ballot, e->st.cl_ballot + c, 4, hipMemcpyDeviceToHost));
+  HIPCHK(e, hipMemcpy(&vote, e->st.cl_vote + c, 4, hipMemcpyDeviceToHost));
   const int phase = h[0] & 3;
   const bool live = phase != 0 && kind != CL_COMMITTED && ballot == h[1] && vote == h[1];
   out[0] = live ? phase : 0, out[1] = h[1], out[2] = (h[0] >> 2) & 1, out[3] = h[2], out[4] = h[3], out[5] = (h[0] >> 3) & 1;
   out[6] = ((uint32_t)h[0] >> 8) & 0xff, out[7] = phase;
-  if (responses) EHIP(e, hipMemcpy(responses, e->ls.resp + c * n * (n + 2), (size_t)n * (n + 2) * 4, hipMemcpyDeviceToHost));
+  if (responses) HIPCHK(e, hipMemcpy(responses, e->ls.resp + c * n * (n + 2), (size_t)n * (n + 2) * 4, hipMemcpyDeviceToHost));
   return FPX_OK;
 }
 

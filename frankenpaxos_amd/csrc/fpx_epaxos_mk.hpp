@@ -39,12 +39,6 @@ struct MkBatch {
   uint2* kv;            // [n][U] the pair sequences, (key | is_set << 27 | leader << 28, pair index)
 };
 
-__device__ __forceinline__ int wave_sum(int v) {
-#pragma unroll
-  for (int k = 1; k < 64; k <<= 1) v += __shfl_xor(v, k);
-  return v;
-}
-
 __global__ void __launch_bounds__(256) k_mk_prep(const EpxState st, const MkBatch b) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   int u = 0, not_one = 0;
@@ -68,8 +62,10 @@ __global__ void __launch_bounds__(256) k_mk_prep(const EpxState st, const MkBatc
     not_one = hi - lo != 1;
   }
   // per-workgroup partial sums (one address hit by every wavefront's atomics cost ~0.4 ms at 2^20 commands)
+  // (both sums behind ONE barrier and no barrier after it; two block_reduce calls were measurably slower in this kernel,
+  // which has little else to do: profiles/epaxos_primitives.md, "Speed")
   __shared__ int sh[8];
-  u = wave_sum(u), not_one = wave_sum(not_one);
+  u = wave_reduce<ScanSum>(u), not_one = wave_reduce<ScanSum>(not_one);
   if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = u, sh[4 + (threadIdx.x >> 6)] = not_one;
   __syncthreads();
   if (threadIdx.x == 0)
@@ -78,16 +74,11 @@ __global__ void __launch_bounds__(256) k_mk_prep(const EpxState st, const MkBatc
 
 // one workgroup: the partial sums -> info[0..1]; info[3] = the status word, so the host reads one line
 __global__ void __launch_bounds__(256) k_mk_total(const EpxState st, const MkBatch b, int blocks) {
-  __shared__ int sh[8];
+  __shared__ int sh[4];
   int u = 0, not_one = 0;
   for (int j = threadIdx.x; j < blocks; j += 256) u += b.part[j].x, not_one += b.part[j].y;
-  u = wave_sum(u), not_one = wave_sum(not_one);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = u, sh[4 + (threadIdx.x >> 6)] = not_one;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    b.info[0] = sh[0] + sh[1] + sh[2] + sh[3], b.info[1] = sh[4] + sh[5] + sh[6] + sh[7];
-    b.info[3] = st.status[0];
-  }
+  u = block_reduce<ScanSum, 256>(u, sh), not_one = block_reduce<ScanSum, 256>(not_one, sh);
+  if (threadIdx.x == 0) b.info[0] = u, b.info[1] = not_one, b.info[3] = st.status[0];
 }
 
 __global__ void __launch_bounds__(256) k_mk_pairs(const MkBatch b) {
@@ -140,27 +131,14 @@ __global__ void __launch_bounds__(256) k_mk_tilesum(const MkBatch b) {
     const int p = t * MK_TILE + k * 256 + threadIdx.x;
     if (p < b.m) s += (int)((uint32_t)b.rec[(size_t)r * b.m + p].y & MK_U_MASK);
   }
-  s = wave_sum(s);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) b.tsum[(size_t)r * b.tiles + t] = (uint32_t)(sh[0] + sh[1] + sh[2] + sh[3]);
+  s = block_reduce<ScanSum, 256>(s, sh);
+  if (threadIdx.x == 0) b.tsum[(size_t)r * b.tiles + t] = (uint32_t)s;
 }
 
 // one workgroup per replica: the tile sums -> exclusive tile offsets, in place
 __global__ void __launch_bounds__(256) k_mk_tilescan(const MkBatch b) {
-  __shared__ uint32_t sh[8];
-  const int r = blockIdx.x, per = (b.tiles + 255) / 256, t0 = threadIdx.x * per;
-  uint32_t* ts = b.tsum + (size_t)r * b.tiles;
-  uint32_t mine = 0;
-  for (int j = 0; j < per; ++j)
-    if (t0 + j < b.tiles) mine += ts[t0 + j];
-  uint32_t start = block_excl_sum_256(mine, sh);
-  for (int j = 0; j < per; ++j)
-    if (t0 + j < b.tiles) {
-      const uint32_t c = ts[t0 + j];
-      ts[t0 + j] = start;
-      start += c;
-    }
+  __shared__ uint32_t lds[SCAN_ARRAY_LDS(256)];
+  scan_array_excl<ScanSum, 256, 1>(b.tsum + (size_t)blockIdx.x * b.tiles, b.tiles, lds);
 }
 
 // thread = 4 consecutive positions of one replica's order: the exclusive offsets inside the tile, then the command's
@@ -168,7 +146,7 @@ __global__ void __launch_bounds__(256) k_mk_tilescan(const MkBatch b) {
 // rank is that position: a record left from an earlier tick fails it, see RsArgs::rank), so the writes below are bounded
 // by U whatever the ranks were.
 __global__ void __launch_bounds__(256) k_mk_scatter(const EpxState st, const MkBatch b) {
-  __shared__ uint32_t sh[8];
+  __shared__ uint32_t sh[4];
   const int r = blockIdx.y, t = blockIdx.x, p0 = t * MK_TILE + threadIdx.x * 4;
   int4 rc[4];
   uint32_t s = 0;
@@ -178,7 +156,7 @@ __global__ void __launch_bounds__(256) k_mk_scatter(const EpxState st, const MkB
     rc[k] = p < b.m ? b.rec[(size_t)r * b.m + p] : make_int4(-1, 0, 0, 0);
     s += (uint32_t)rc[k].y & MK_U_MASK;
   }
-  uint32_t base = b.tsum[(size_t)r * b.tiles + t] + block_excl_sum_256(s, sh);
+  uint32_t base = block_excl_scan<ScanSum, 256>(s, b.tsum[(size_t)r * b.tiles + t], sh);
   uint2* out = b.kv + (size_t)r * b.U;
   bool bad = false;
 #pragma unroll

@@ -374,35 +374,27 @@ __device__ __forceinline__ uint32_t lr_flags4(const LrBatch& b, int first, uint3
 }
 
 __global__ void __launch_bounds__(256) k_lr_count(const EpxState st, const LrBatch b) {
-  __shared__ uint32_t sh[8];
+  __shared__ uint32_t sh[4];
   if (st.status[0] == FPX_EINVAL) return;
   uint32_t f[4];
-  const uint32_t v = lr_flags4(b, blockIdx.x * LR_BLOCK + threadIdx.x * 4, f);
-  const uint32_t before = block_excl_sum(v, sh);
-  if (threadIdx.x == 255) b.bsum[blockIdx.x] = before + v;
+  const uint32_t all = block_reduce<ScanSum, 256>(lr_flags4(b, blockIdx.x * LR_BLOCK + threadIdx.x * 4, f), sh);
+  if (threadIdx.x == 0) b.bsum[blockIdx.x] = all;
 }
 
 __global__ void __launch_bounds__(256) k_lr_bscan(const EpxState st, const LrBatch b) {
-  __shared__ uint32_t sh[8];
+  __shared__ uint32_t lds[SCAN_ARRAY_LDS(256)];
   if (st.status[0] == FPX_EINVAL) return;
-  const int per = (b.blocks + 255) / 256, t0 = threadIdx.x * per, t1 = min(b.blocks, t0 + per);
-  uint32_t sum = 0;
-  for (int t = t0; t < t1; ++t) sum += b.bsum[t];
-  uint32_t run = block_excl_sum(sum, sh);
-  if (threadIdx.x == 255 && b.num_decided) *b.num_decided = (int32_t)(run + sum);
-  for (int t = t0; t < t1; ++t) {
-    const uint32_t v = b.bsum[t];
-    b.bsum[t] = run, run += v;
-  }
+  const uint32_t all = scan_array_excl<ScanSum, 256, 1>(b.bsum, b.blocks, lds);
+  if (threadIdx.x == 0 && b.num_decided) *b.num_decided = (int32_t)all;
 }
 
 __global__ void __launch_bounds__(256) k_lr_compact(const EpxState st, const LrBatch b) {
-  __shared__ uint32_t sh[8];
+  __shared__ uint32_t sh[4];
   if (st.status[0] == FPX_EINVAL) return;
   uint32_t f[4];
   const int first = blockIdx.x * LR_BLOCK + threadIdx.x * 4;
   const uint32_t v = lr_flags4(b, first, f);
-  uint32_t at = b.bsum[blockIdx.x] + block_excl_sum(v, sh);
+  uint32_t at = block_excl_scan<ScanSum, 256>(v, b.bsum[blockIdx.x], sh);
 #pragma unroll
   for (int k = 0; k < 4; ++k)
     if (f[k]) b.decided[at++] = first + k;

@@ -1,6 +1,7 @@
-// fpx_scan.hpp -- the workgroup building blocks of the burst kernels (fpx_*_msgs.hpp, fpx_*_inbox.hpp, fpx_burst_sort.hpp):
-// a wavefront scan, a workgroup scan and reduction, the one-workgroup scan of an array in global memory, and a flagged
-// thread's rank.  Templates over the operation (ScanSum, ScanMax) and the value type (int, long long, int64_t).
+// fpx_scan.hpp -- the workgroup building blocks of the burst kernels (fpx_*_msgs.hpp, fpx_*_inbox.hpp, fpx_burst_sort.hpp)
+// and of the EPaxos kernels (fpx_epaxos.hip and its headers): a wavefront scan, a workgroup scan and reduction, the
+// one-workgroup scan of an array in global memory, and a flagged thread's rank.  Templates over the operation (ScanSum,
+// ScanMax) and the value type (any 4- or 8-byte integer).
 //
 // LDS: the CALLER declares the scratch and passes it in; nothing here declares a __shared__ of its own (one declared in
 // an inlined helper would be ONE variable for all the helper's call sites of a kernel).  Every function that takes a
@@ -74,13 +75,20 @@ __device__ __forceinline__ T block_excl_scan(T v, T carry, T* wtot, T* total = n
   return Op::op(before, excl);
 }
 
-// op over every thread's value, in every thread.  w: THREADS / 64 words; ends with a barrier, so `w` is free again
-template <typename Op, int THREADS, typename T>
-__device__ __forceinline__ T block_reduce(T v, T* w) {
+// op over the values of the wavefront's 64 lanes, in every lane
+template <typename Op, typename T>
+__device__ __forceinline__ T wave_reduce(T v) {
 #pragma unroll
   for (int k = 1; k < 64; k <<= 1) {
     v = Op::op(v, scan_shfl_xor(v, k));
   }
+  return v;
+}
+
+// op over every thread's value, in every thread.  w: THREADS / 64 words; ends with a barrier, so `w` is free again
+template <typename Op, int THREADS, typename T>
+__device__ __forceinline__ T block_reduce(T v, T* w) {
+  v = wave_reduce<Op>(v);
   if ((threadIdx.x & 63) == 0) w[threadIdx.x >> 6] = v;
   __syncthreads();
   T r = w[0];
@@ -91,14 +99,15 @@ __device__ __forceinline__ T block_reduce(T v, T* w) {
 }
 
 // ONE workgroup rewrites a[0 .. len) in place to its exclusive scan, THREADS * PER elements a step (a thread takes PER
-// consecutive ones) with a carry from step to step, and returns op over all of a -- the identity when len is 0 -- to every
-// thread.  len may come from device memory; every thread passes the same.  lds: SCAN_ARRAY_LDS(THREADS) words
+// consecutive ones) with a carry from step to step that begins as `start`, and returns op over `start` and all of a --
+// `start` when len is 0 -- to every thread.  len and start may come from device memory; every thread passes the same.
+// lds: SCAN_ARRAY_LDS(THREADS) words
 #define SCAN_ARRAY_LDS(THREADS) ((THREADS) / 64 + 1)
 template <typename Op, int THREADS, int PER, typename T, typename Len>
-__device__ __forceinline__ T scan_array_excl(T* a, Len len, T* lds) {
+__device__ __forceinline__ T scan_array_excl(T* a, Len len, T* lds, T start = Op::template identity<T>()) {
   T* carry = lds + THREADS / 64;
   const int t = threadIdx.x;
-  if (t == 0) *carry = Op::template identity<T>();
+  if (t == 0) *carry = start;
   __syncthreads();
   for (Len base = 0; base < len; base += THREADS * PER) {
     const Len b0 = base + (Len)t * PER;

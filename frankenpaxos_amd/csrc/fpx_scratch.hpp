@@ -1,5 +1,6 @@
-// fpx_scratch.hpp -- how the burst entry points of fpx_api.hip cut their per-call scratch buffer into arrays.  Host code,
-// no HIP: tests/burst_scratch_main.cpp runs the layouts under the sanitizers.
+// fpx_scratch.hpp -- how the burst entry points of fpx_api.hip and the EPaxos entry points of fpx_epaxos.hip cut their
+// per-call scratch buffers into arrays.  Host code, no HIP: tests/burst_scratch_main.cpp runs the layouts under the
+// sanitizers.
 //
 // A layout is ONE function over a Carver.  It runs twice per call: over a null base to learn the size the buffer must
 // have, then over the buffer.  The size and the pointers come from the same take() calls and cannot disagree.
@@ -109,6 +110,47 @@ inline MenciusAcceptorInboxScratch lay_mencius_acceptor_inbox(Carver& c, size_t 
   s.rflag = c.take<int32_t>(tiles * BURST_TILE);
   s.rcnt = c.take<int32_t>(tiles);
   for (int j = 0; j < 5; ++j) s.list[j] = c.take<int32_t>(tiles * BURST_TILE);
+  return s;
+}
+
+// fpx_epaxos_mk.hpp, the prologue of a multi-key tick of m commands at n replicas (k_mk_prep, k_mk_total, k_mk_tilesum,
+// k_mk_tilescan): `tiles` scan tiles per replica, `blocks` workgroups of k_mk_prep
+struct MkPrologueScratch {
+  int32_t *info, *ucnt;
+  uint32_t* tsum;
+  int32_t* part;  // [blocks][2]: the kernels' int2
+};
+inline MkPrologueScratch lay_mk_prologue(Carver& c, size_t m, size_t n, size_t tiles, size_t blocks) {
+  MkPrologueScratch s;
+  s.info = c.take<int32_t>(16);
+  s.ucnt = c.take<int32_t>(m);
+  s.tsum = c.take<uint32_t>(n * tiles);
+  s.part = c.take<int32_t>(2 * blocks);
+  return s;
+}
+
+// fpx_epaxos_mk.hpp, per key of the commands' key lists (k_mk_pairs): P of them, one array element for P = 0
+struct MkPairScratch {
+  int32_t* pnum;
+  uint8_t* uniq;
+};
+inline MkPairScratch lay_mk_pairs(Carver& c, size_t P) {
+  const size_t len = P ? P : 1;
+  MkPairScratch s;
+  s.pnum = c.take<int32_t>(len);
+  s.uniq = c.take<uint8_t>(len);
+  return s;
+}
+
+// fpx_epx_leader.hpp, the compaction of a burst of m replies (k_lr_walk's flags; k_lr_count, k_lr_bscan, k_lr_compact)
+struct LrScratch {
+  uint8_t* flag;
+  uint32_t* bsum;
+};
+inline LrScratch lay_leader_replies(Carver& c, size_t m, size_t blocks) {
+  LrScratch s;
+  s.flag = c.take<uint8_t>(m);
+  s.bsum = c.take<uint32_t>(blocks);
   return s;
 }
 

@@ -1,5 +1,6 @@
-// burst_scratch_main.cpp -- TEST INFRASTRUCTURE ONLY: lays out the scratch of the four burst entry points with
-// frankenpaxos_amd/csrc/fpx_scratch.hpp (host code, no HIP) exactly as fpx_api.hip's carve() does -- over a null base for
+// burst_scratch_main.cpp -- TEST INFRASTRUCTURE ONLY: lays out the scratch of the four burst entry points and of the
+// EPaxos multi-key tick and leader-replies compaction with frankenpaxos_amd/csrc/fpx_scratch.hpp (host code, no HIP)
+// exactly as carve() (fpx_host.hpp) does for fpx_api.hip and fpx_epaxos.hip -- over a null base for
 // the size, then over a buffer of that size -- and checks that every array is aligned for its type, lies inside the size
 // of the sizing pass, and overlaps no other.  Every array is then written from end to end, so that built with
 // -fsanitize=address,undefined (tests/test_burst_scratch_cpu.py) a layout that leaves its buffer is an error of its own.
@@ -112,6 +113,25 @@ int main() {
       add_acceptor(v, s.a, n, E);
       add(v, "rflag", s.rflag, tiles * BURST_TILE), add(v, "rcnt", s.rcnt, tiles);
       for (int j = 0; j < 5; ++j) add(v, "list", s.list[j], tiles * BURST_TILE);
+    });
+    // EPaxos, n commands / key-list entries / replies: the lengths are what the kernels index (MK_TILE = LR_BLOCK = 1024
+    // positions per scan tile, 256 commands per workgroup of k_mk_prep)
+    const size_t tiles1k = (n + 1023) / 1024;
+    for (size_t replicas : {(size_t)3, (size_t)5, (size_t)7})
+      check(replicas == 3 ? "mk_prologue n=3" : replicas == 5 ? "mk_prologue n=5" : "mk_prologue n=7", n,
+            [&](Carver& c, std::vector<Span>* v) {
+              const MkPrologueScratch s = lay_mk_prologue(c, n, replicas, tiles1k, nblk);
+              add(v, "info", s.info, 16), add(v, "ucnt", s.ucnt, n), add(v, "tsum", s.tsum, replicas * tiles1k);
+              add(v, "part", s.part, 2 * nblk);
+              if (reinterpret_cast<uintptr_t>(s.part) % 8 != 0) std::printf("FAIL mk_prologue: part is no int2 array\n"), ++failures;
+            });
+    check("mk_pairs", n, [&](Carver& c, std::vector<Span>* v) {  // (no array per replica in this one)
+      const MkPairScratch s = lay_mk_pairs(c, n);
+      add(v, "pnum", s.pnum, n ? n : 1), add(v, "uniq", s.uniq, n ? n : 1);
+    });
+    check("leader_replies", n, [&](Carver& c, std::vector<Span>* v) {
+      const LrScratch s = lay_leader_replies(c, n, tiles1k);
+      add(v, "flag", s.flag, n), add(v, "bsum", s.bsum, tiles1k);
     });
   }
   if (failures) return std::printf("%d failures\n", failures), 1;

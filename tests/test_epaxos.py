@@ -651,6 +651,66 @@ def test_epaxos_prepare_accept_match_oracle(oracle, n, NI, m):
     assert EPaxos(n, 8).accept([1], [1], [0], [1], [0], [0b001])[0] == fa.FPX_EINVAL
 
 
+@pytest.mark.gpu
+def test_epaxos_nack_ballots_cross_the_second_step_of_the_tile_scan(oracle):
+    """k_cl_tilemax -> k_cl_tilescan -> k_cl_nacks with more tiles than the one workgroup of k_cl_tilescan scans in a step
+    (256 tiles of CL_TILE = 1024 messages): one batch of 256 * 1024 + 1024 + 1 distinct instances, three times on one context
+    (Prepare, Prepare, Accept), so that the second and third start from a largestBallot that is not the initial one.  In the
+    second batch the ballots rise and fall, the largest ballot of all arrives in the last tile of the first step, and the
+    messages of the first tile of the second step and the one message of the final, partial tile are Nacked: their Nacks
+    must carry it.  Every reply, every Nack ballot and every replica's largestBallot after each call, GPU == oracle"""
+    from frankenpaxos_amd.epaxos import EPaxos
+
+    n, TILE, STEP = 3, 1024, 256 * 1024
+    m = STEP + TILE + 1
+    NI = m // n
+    assert n * NI == m                                            # the batch is every instance of the context, once
+    gpu, ref = EPaxos(n, 4, num_instances=NI), oracle.EPaxos(n, 4, num_instances=NI)
+    rng = np.random.default_rng(4)
+    i = np.arange(m)
+    leader, number = (i // NI).astype(np.int32), (i % NI).astype(np.int32)
+    late = np.concatenate([np.arange(STEP, STEP + 8), [m - 1]])   # first tile of the second step; the final partial tile
+    spike = STEP - 6                                              # last tile of the first step
+
+    def same(a, b):
+        assert a[0] == b[0]
+        for x, y in zip(a[1:], b[1:]):
+            np.testing.assert_array_equal(x, y)
+        for r in range(n):
+            assert gpu.read_cmdlog(r, r, 0)[4] == ref.read_cmdlog(r, r, 0)[4]
+
+    # 1. every instance is prepared at every replica in a small ballot (>= (1, .) at the instances that are Nacked later)
+    ord1, rep1 = rng.integers(0, 6, m).astype(np.int32), rng.integers(0, n, m).astype(np.int32)
+    ord1[late] = 1 + ord1[late] % 5
+    all_r = np.full(m, (1 << n) - 1, np.uint8)
+    a, b = gpu.prepare(leader, number, ord1, rep1, all_r), ref.prepare(leader, number, ord1, rep1, all_r)
+    assert a[0] == 0
+    same(a, b)
+    # 2. half the ballots fall below what the instances hold (Nacks), the others rise tile by tile
+    ord2 = np.where(rng.random(m) < 0.5, rng.integers(0, 3, m), 6 + i // 4096 + rng.integers(0, 3, m)).astype(np.int32)
+    rep2 = rng.integers(0, n, m).astype(np.int32)
+    tgt2 = rng.integers(1, 1 << n, m).astype(np.uint8)
+    ord2[spike], rep2[spike], tgt2[spike] = 5000, 1, (1 << n) - 1
+    ord2[late], rep2[late], tgt2[late] = 0, 0, (1 << n) - 1
+    a, b = gpu.prepare(leader, number, ord2, rep2, tgt2), ref.prepare(leader, number, ord2, rep2, tgt2)
+    assert a[0] == 0
+    same(a, b)
+    assert (a[2][late] == (1 << n) - 1).all() and (a[4][late] == enc(5000, 1)).all()
+    assert 0 < int((a[2] != 0).sum()) < m
+    assert [gpu.read_cmdlog(r, r, 0)[4] for r in range(n)] == [enc(5000, 1)] * n
+    # 3. Accepts in ballots on both sides of that, never to their proposer
+    ord3 = np.where(rng.random(m) < 0.5, rng.integers(0, 100, m), rng.integers(0, 10000, m)).astype(np.int32)
+    rep3 = rng.integers(0, n, m).astype(np.int32)
+    tgt3 = (rng.integers(0, 1 << n, m) & ~(1 << rep3)).astype(np.uint8)
+    tr = rng.integers(0, 1 << 20, m).astype(np.int32)
+    a, b = gpu.accept(leader, number, ord3, rep3, tr, tgt3), ref.accept(leader, number, ord3, rep3, tr, tgt3)
+    same(a, b)
+    assert int((a[2][STEP:] != 0).sum()) > 0 and int(a[5].sum()) > 0
+    for r in range(n):
+        for inst in rng.choice(m, size=200, replace=False):
+            assert gpu.read_cmdlog(r, int(inst) // NI, int(inst) % NI) == ref.read_cmdlog(r, int(inst) // NI, int(inst) % NI)
+
+
 def test_oracle_handle_commit_by_hand(oracle):
     """Replica.handleCommit (epaxos/Replica.scala:1567-1575 -> commit :815-830), n = 5, by hand: replica 2 holds an
     AcceptedEntry for (0, 5) in Ballot(3, 1) (one AcceptOk + the proposer's own = 2 < f + 1 = 3: not committed); a Commit

@@ -77,6 +77,59 @@ def test_burst_sizes(size):
     assert len(res[1][1]) == size
 
 
+def test_a_burst_that_takes_the_block_count_scan_past_its_first_step():
+    # k_lr_count -> k_lr_bscan -> k_lr_compact with more blocks than the one workgroup of k_lr_bscan scans in a step (256
+    # blocks of LR_BLOCK = 1024 messages): 256 * 1024 + 1024 + 1 messages.  The burst is one burst of 64 messages again and
+    # again, each copy on instances of its own (Noops, so a copy's answers do not depend on its instance numbers): the model
+    # answers the 64 once, and its answer repeats.  Messages 0 and 63 of the 64 decide, so the first block, the last message
+    # of the first step (262 143), the first of the second (262 144) and the one message of the final block all do
+    n, B, STEP = 3, 64, 256 * 1024
+    m = STEP + 1024 + 1
+    leads, burst = [], []
+    for k in range(B):
+        if k % 4 == 1:                                            # a second answer for the instance before: ignored
+            burst.append(burst[-1])
+            continue
+        j = len(leads)
+        L, x = j % n, j // n
+        leads.append((L, x, L, 0, -1, 1, j, int(j % 5 == 0)))
+        w = [0] * n
+        if j % 7 == 0:
+            w[(L + 1) % n] = 1 + j % 3                            # one more dependency than the leader named: the slow path
+        burst.append(_ok((L + 1 + j % 2) % n, w, to=L, L=L, x=x, seq=int(j % 13 == 0)))
+    per = (len(leads) + n - 1) // n                               # instance numbers a copy takes of every leader
+    copies = (m + B - 1) // B
+    model = M.LeaderModel(n, 4, per)
+    want = S.run_model(model, [("lead", leads), ("replies", burst)])
+    assert want[0][0] == 0 and want[1][0] == 0
+    rows = want[1][1]
+    assert rows[0][0] in (3, 4, 5) and rows[63][0] in (3, 4, 5) and sorted(set(r[0] for r in rows))[0] < 3
+    assert (m - 1) % B == 0 and (STEP - 1) % B == 63
+
+    def tiled(col, shift=0, upto=None):
+        a = np.tile(np.asarray(col, np.int32), (copies,) + (1,) * (np.ndim(col) - 1))
+        if shift:
+            a = a + np.repeat(np.arange(copies, dtype=np.int32) * shift, len(col))
+        return a[:upto]
+
+    e = ctx(n, num_instances=per * copies)
+    lc = list(zip(*leads))
+    st, deps, dend = e.lead(tiled(lc[0]), tiled(lc[1], per), tiled(lc[2]), tiled(lc[3]), tiled(lc[4]),
+                            tiled(lc[5]).astype(np.uint8), tiled(lc[6]), tiled(lc[7]).astype(np.uint8))
+    assert st == 0
+    np.testing.assert_array_equal(deps, tiled([d[0] for d in want[0][1]]))
+    np.testing.assert_array_equal(dend, tiled([d[1] for d in want[0][1]]))
+    a = S.burst_arrays(n, burst)
+    st, outcome, oseq, odeps, oend, otr, dec = e.leader_replies(*[tiled(c, per if k == 3 else 0, m) for k, c in enumerate(a)])
+    assert st == 0
+    for got, k in [(outcome, 0), (oseq, 1), (odeps, 2), (oend, 3), (otr, 4)]:
+        np.testing.assert_array_equal(got, tiled([r[k] for r in rows], 0, m))
+    expect = np.flatnonzero(np.isin(outcome, [3, 4, 5]))
+    np.testing.assert_array_equal(dec, expect)                    # (its length is num_decided)
+    assert {0, STEP - 1, STEP, m - 1} <= set(expect.tolist()) and len(expect) < m
+    e.close()
+
+
 def test_a_run_of_200_resent_answers():
     n, z = 5, [0] * 5
     burst = [_ok(1 + (j % 2), [0, j % 3, 0, 0, 0]) for j in range(199)] + [_ok(3, z), _ok(4, z)]
