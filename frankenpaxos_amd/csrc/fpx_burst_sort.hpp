@@ -81,12 +81,13 @@ __global__ void __launch_bounds__(256) k_sort_scatter(const BurstSort a) {
 }
 
 // Sorts the *d_len pairs (s.key[0], s.val[0]) by keys 0 .. max_key; `tiles` is the grid: the tiles *d_len can come to.
-// The sorted keys end up in s.key[r] and the values in s.val[r] for the r returned -- or in val_last, where given
+// The sorted keys end up in s.key[r] and the values in s.val[r] for the r returned -- or in val_last, where given.  There
+// is always at least one pass, so that holds for max_key == 0 (every key 0) too: r is then 1
 inline int burst_sort(hipStream_t stream, const int32_t* d_len, const SortScratch& s, int64_t max_key, int tiles,
                       int32_t* val_last = nullptr) {
   int bits = 0;
   while (max_key >> bits) ++bits;
-  const int passes = (bits + SORT_RADIX_BITS - 1) / SORT_RADIX_BITS;
+  const int passes = bits ? (bits + SORT_RADIX_BITS - 1) / SORT_RADIX_BITS : 1;
   const dim3 per_tile(tiles), blk(256);
   for (int p = 0; p < passes; ++p) {
     BurstSort a;

@@ -1,7 +1,7 @@
 // fpx_scan.hpp -- the workgroup building blocks of the burst kernels (fpx_*_msgs.hpp, fpx_*_inbox.hpp, fpx_burst_sort.hpp)
 // and of the EPaxos kernels (fpx_epaxos.hip and its headers): a wavefront scan, a workgroup scan and reduction, the
 // one-workgroup scan of an array in global memory, and a flagged thread's rank.  Templates over the operation (ScanSum,
-// ScanMax) and the value type (any 4- or 8-byte integer).
+// ScanMax) and the value type: any 4- or 8-byte integer for ScanSum (an unsigned sum wraps), a signed one for ScanMax.
 //
 // LDS: the CALLER declares the scratch and passes it in; nothing here declares a __shared__ of its own (one declared in
 // an inlined helper would be ONE variable for all the helper's call sites of a kernel).  Every function that takes a
@@ -14,6 +14,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 namespace fpx {
 
 struct ScanSum {
@@ -22,12 +24,19 @@ struct ScanSum {
   template <typename T>
   static __device__ __forceinline__ T op(T a, T b) { return a + b; }
 };
-// the maximum of claim words, rounds + 1 and slots + 1: nothing scanned is below -1, which so serves as "nothing yet"
+// the maximum of claim words, rounds + 1 and slots + 1: nothing scanned is below -1, which so serves as "nothing yet".
+// Signed types only: (T)-1 is the LARGEST value of an unsigned T
 struct ScanMax {
   template <typename T>
-  static __device__ __forceinline__ T identity() { return (T)-1; }
+  static __device__ __forceinline__ T identity() {
+    static_assert(std::is_signed<T>::value, "ScanMax scans signed integers: -1 is its 'nothing yet'");
+    return (T)-1;
+  }
   template <typename T>
-  static __device__ __forceinline__ T op(T a, T b) { return b > a ? b : a; }
+  static __device__ __forceinline__ T op(T a, T b) {
+    static_assert(std::is_signed<T>::value, "ScanMax scans signed integers: -1 is its 'nothing yet'");
+    return b > a ? b : a;
+  }
 };
 
 // __shfl_up / __shfl_xor of a 4- or 8-byte integer of any name
