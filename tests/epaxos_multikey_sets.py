@@ -10,6 +10,17 @@ from oracle.epaxos_sets import ACCEPTED, COMMITTED, PRE_ACCEPTED, Entry
 from oracle import epaxos_sets as base
 
 
+_PREFIXES = {}
+
+
+def prefix_set(leader, top):
+    """{(leader, x) : x < top}, built once: the sets below are unions of these (explicit sets still, only faster)"""
+    s = _PREFIXES.get((leader, top))
+    if s is None:
+        s = _PREFIXES[(leader, top)] = frozenset((leader, x) for x in range(top))
+    return s
+
+
 class Replica(base.Replica):
     def top_one_conflicts(self, keys, is_set):
         merged = [0] * self.n
@@ -29,7 +40,7 @@ class Replica(base.Replica):
         if keys is None:                                    # Noop (:592-593)
             return set()
         top = self.top_one_conflicts(keys, is_set)
-        deps = {(l, x) for l in range(self.n) for x in range(top[l])}
+        deps = set().union(*(prefix_set(l, top[l]) for l in range(self.n)))
         deps.discard(instance)                              # subtractOne (:582)
         return deps
 
