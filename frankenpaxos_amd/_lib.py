@@ -197,6 +197,7 @@ SIGNATURES = {
     "fpx_read_tally": (C.c_int32, [VP, C.c_int32, I32P, VP, VP, VP, VP]),
     "fpx_state_digest": (C.c_int32, [VP, VP]),
     "fpx_ballot_summary_audit": (C.c_int32, [VP, VP]),
+    "fpx_vote_summary_audit": (C.c_int32, [VP, VP]),
     "fpx_comm_unique_id": (C.c_int32, [VP]),
     "fpx_comm_create": (C.c_int32, [VP, VP, C.c_int32, C.c_int32]),
     "fpx_comm_destroy": (C.c_int32, [VP]),

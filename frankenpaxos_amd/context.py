@@ -894,6 +894,15 @@ class Context:
             raise FpxError(st, "fpx_ballot_summary_audit")
         return int(out[0]), int(out[1]), int(out[2])
 
+    def vote_summary_audit(self):
+        """(fresh rows, rows kept as cells, compact rows) of the vote rows (fpx_vote_summary_audit).  Call it before
+        read_state(), which turns every compact row back into cells"""
+        out = np.zeros(3, np.int64)
+        st = self.L.fpx_vote_summary_audit(self._h, _hp(out))
+        if st:
+            raise FpxError(st, "fpx_vote_summary_audit")
+        return int(out[0]), int(out[1]), int(out[2])
+
     def read_tally(self, slot):
         n = C.c_int32()
         rounds = np.zeros(8, np.int32)

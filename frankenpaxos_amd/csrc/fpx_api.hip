@@ -131,6 +131,7 @@ struct fpx_ctx {
   int hnext = 0;
   int32_t index_base = 0;  // message index of the run being launched in its host batch (error reports are batch-relative)
   bool lazy_active = false;  // PER_SLOT: lazy Phase1a promises may be outstanding (k_phase2 runs its lazy-aware form)
+  bool may_compact = false;  // some vote row may be ROW_COMPACT: a steady walk may have run since all rows were last fresh or cells
   bool packed_pass = false;  // the launch being enqueued is the packed walk over runs of acceptors (k_phase2 MODE 3)
   DevBuf d_run_done;         // one byte per chunk: taken by the packed walk
   // K4: the proxy leader's noop-range tallies (two buffers: fpx_proxy_forget rehashes into the other one)
@@ -305,7 +306,7 @@ size_t lds_bytes(const fpx_ctx* ctx, bool fused, bool targets) {
   return tab + 4 * (fused ? sizeof(WaveOut<true>) : sizeof(WaveOut<false>)) + (targets ? 4 * (256 + 16) * sizeof(uint64_t) : 0);
 }
 
-// messages per wavefront at G = 64: CHUNK for batches that fill the chip anyway, fewer (down to 4) for small
+// messages per wavefront at G = 64: CHUNK (CHUNK_RECORDS) for batches that fill the chip anyway, fewer (down to 4) for small
 // ones -- a wave walks its chunk one row at a time, so a 20 k-message epoch in 32-message chunks is 670 waves
 // walking 32 dependent steps each on a machine with room for 6000
 int chunk_for(const fpx_ctx* ctx, int n) {
@@ -313,7 +314,8 @@ int chunk_for(const fpx_ctx* ctx, int n) {
   // (the floor: the sweep of profiles/r06_raw/adversarial_chunk_sweep.txt -- 8 / 4 / 2 / 1 messages per wavefront at ~21 500
   // messages per launch: 6.12 / 6.50 / 6.55 / 6.53e8 proposals/s; 4 stays)
   const long long want_waves = (long long)ctx->num_cus * 16;
-  int ch = CHUNK;
+  // (records are kept AND written: the steady walk needs one acceptor group; with several every row still stores its cells)
+  int ch = ctx->st.vote_sum && ctx->g.ngroups == 1 ? CHUNK_RECORDS : CHUNK;
   while (ch > 4 && (long long)(n + ch - 1) / ch < want_waves) ch >>= 1;
   return ch;
 }
@@ -552,6 +554,18 @@ int enqueue_phase2(fpx_ctx* ctx, Batch& b, bool fused) {
     if (rc) return rc;
     b.run_done = (uint8_t*)ctx->d_run_done.p;
   }
+  // Vote-row records.  Only a dense launch (its steady walk) writes them, and only the dense kernels read them: in front of a launch that carries target masks the compact rows among its slots become
+  // cells (k_expand_batch; an undelivered message's row too, which changes no cell's value) -- while there may be any.
+  // A stream of such launches alone (the adversarial one) never pays the launch
+  if (ctx->st.vote_sum) {
+    if (!b.target) {
+      if (g.ngroups == 1) ctx->may_compact = true;
+    } else if (ctx->may_compact) {
+      const int ge = (int)std::min<long long>(((long long)b.n + 3) / 4, (long long)ctx->num_cus * 8);
+      hipLaunchKernelGGL(k_expand_batch, dim3(ge), dim3(256), 0, ctx->stream, ctx->g, ctx->st, b.slot, b.n);
+      if ((rc = launch_check(ctx))) return rc;
+    }
+  }
   const bool prof = ctx->profiling && ctx->ev_used + 2 <= ctx->ev.size();
   for (int pass = two ? 0 : 1; pass < 2; ++pass) {
     // start of the first vote kernel to end of the last (two with the packed walk ahead)
@@ -686,12 +700,13 @@ int init_state(fpx_ctx* ctx) {
   HIPCHK(ctx, hipMemsetAsync(st.pl_value, 0xFF, (size_t)g.S * g.wp * 4, ctx->stream));
   HIPCHK(ctx, hipMemsetAsync(st.pl_bits, 0, (size_t)g.S * g.wp * 32, ctx->stream));
   HIPCHK(ctx, hipMemsetAsync(st.stamp, 0, (size_t)g.S * 4, ctx->stream));
-  HIPCHK(ctx, hipMemsetAsync(st.row_voted, 0, (size_t)g.S, ctx->stream));
+  HIPCHK(ctx, hipMemsetAsync(st.row_voted, 0, (size_t)g.S, ctx->stream));  // ROW_FRESH (the records of fresh rows are never read)
   HIPCHK(ctx, hipMemsetAsync(st.lz_round, 0xFF, (nsc + 4) * 4, ctx->stream));
   HIPCHK(ctx, hipMemsetAsync(st.lz_from, 0, (nsc + 4) * 4, ctx->stream));
   HIPCHK(ctx, hipMemsetAsync(st.max_ballot, 0xFF, (nsc + 4) * 4, ctx->stream));
   HIPCHK(ctx, hipMemsetAsync(st.p1, 0, ((size_t)4 * g.R + 64) * 4, ctx->stream));
   ctx->lazy_active = false, ctx->lz_min_from = 0x7fffffff;
+  ctx->may_compact = false;
   HIPCHK(ctx, hipMemsetAsync(st.run_round, 0xFF, (size_t)g.ngroups * 4, ctx->stream));
   HIPCHK(ctx, hipMemsetAsync(st.status, 0, 8 * 4, ctx->stream));
   HIPCHK(ctx, hipMemsetAsync(st.part_stamp, 0, (size_t)2 * ctx->max_grid * 4, ctx->stream));
@@ -1008,7 +1023,7 @@ void free_state(fpx_ctx* ctx) {
   void* ps[] = {st.promised, st.max_voted, ctx->slab, st.pl_key, st.pl_value,
                 st.pl_bits,  st.stamp,     st.run_round,  st.status,     st.part,
                 st.log_value, st.log_present, st.log_scalars, st.part_stamp, st.part_all,
-                st.row_voted, st.ballot_sum, st.lz_round, st.lz_from, st.max_ballot, st.p1,
+                st.row_voted, st.ballot_sum, st.vote_sum, st.lz_round, st.lz_from, st.max_ballot, st.p1,
                 ctx->rt[0].key, ctx->rt[0].bits, ctx->rt[0].owner, ctx->rt[0].count,
                 ctx->rt[1].key, ctx->rt[1].bits, ctx->rt[1].owner, ctx->rt[1].count, ctx->d_rng.p, ctx->d_run_done.p};
   for (void* p : ps)
@@ -1531,7 +1546,8 @@ int32_t fpx_create(const fpx_config* cfg, fpx_ctx** out) {
   if (hipGetDeviceProperties(&prop, cfg->device) == hipSuccess) ctx->num_cus = prop.multiProcessorCount;
   // 32 workgroups per CU: at 2^20 messages every wavefront gets exactly one CHUNK-message chunk and
   // the hardware dispatcher load-balances them (measured r01: +10 % over a 2048-workgroup persistent
-  // grid, a further +8 % going from 64- to 32-message chunks)
+  // grid, a further +8 % going from 64- to 32-message chunks).  Where vote-row records are written (chunk_for:
+  // CHUNK_RECORDS = 64 messages) the same 2^20 messages are half as many workgroups, 16 per CU, still one chunk each
   int G = 1;
   while (G * 4 < ctx->g.R) G <<= 1;
   ctx->lanes_per_slot = G;
@@ -1666,6 +1682,9 @@ int32_t fpx_create(const fpx_config* cfg, fpx_ctx** out) {
       if ((rc = dalloc(ctx, &t.count, (size_t)1))) return fail(rc);
     }
   }
+  // the vote-row records live where the summaries do.  Allocated LAST: every other array of the context then lands
+  // where it did before there were records
+  if (g.per_slot && sums_kept(g) && (rc = dalloc(ctx, &st.vote_sum, (size_t)g.S))) return fail(rc);
   if ((rc = init_state(ctx))) return fail(rc);
   if (hipStreamSynchronize(ctx->stream) != hipSuccess) return fail(FPX_EHIP);
   *out = ctx;
@@ -3457,6 +3476,12 @@ int32_t fpx_read_state(fpx_ctx* ctx, int32_t* vote_round, int32_t* vote_value, i
     int rcf = flush_promises(ctx);
     if (rcf) return rcf;
   }
+  if (ctx->st.vote_sum && (vote_round || vote_value)) {  // whole arrays are copied: compact rows become cells first
+    hipLaunchKernelGGL(k_expand_rows, dim3(ctx->num_cus * 8), dim3(256), 0, ctx->stream, ctx->g, ctx->st);
+    int rce = launch_check(ctx);
+    if (rce) return rce;
+    ctx->may_compact = false;
+  }
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
   // device rows are RS cells long, the caller's are R
   // leader-group-major rows: leader group lg's rows are contiguous on the device and every L-th row of the caller's array
@@ -3833,9 +3858,9 @@ int32_t fpx_state_digest(fpx_ctx* ctx, uint64_t out[8]) {
   const int big = ctx->num_cus * 16;
   const size_t n4 = (size_t)g.S * (size_t)(g.RS / 4);
   const int gc = (int)std::max<size_t>(1, std::min<size_t>((n4 + 255) / 256, (size_t)big));
-  hipLaunchKernelGGL(k_digest_cells, dim3(gc), dim3(256), 0, ctx->stream, g, ctx->st.vote_round, g.VS, d + 0);
-  hipLaunchKernelGGL(k_digest_cells, dim3(gc), dim3(256), 0, ctx->stream, g, ctx->st.vote_value, g.VS, d + 1);
-  if (ctx->st.ballot) hipLaunchKernelGGL(k_digest_cells, dim3(gc), dim3(256), 0, ctx->stream, g, ctx->st.ballot, g.RS, d + 2);
+  hipLaunchKernelGGL(k_digest_cells, dim3(gc), dim3(256), 0, ctx->stream, g, ctx->st, ctx->st.vote_round, g.VS, 0, d + 0);
+  hipLaunchKernelGGL(k_digest_cells, dim3(gc), dim3(256), 0, ctx->stream, g, ctx->st, ctx->st.vote_value, g.VS, 1, d + 1);
+  if (ctx->st.ballot) hipLaunchKernelGGL(k_digest_cells, dim3(gc), dim3(256), 0, ctx->stream, g, ctx->st, ctx->st.ballot, g.RS, -1, d + 2);
   const int nsc = g.ngroups * g.R;
   const int gs = std::max(1, std::min((nsc + 255) / 256, big));
   hipLaunchKernelGGL(k_digest_1d, dim3(gs), dim3(256), 0, ctx->stream, ctx->st.promised, nsc, d + 3);
@@ -3870,6 +3895,20 @@ int32_t fpx_ballot_summary_audit(fpx_ctx* ctx, int64_t out[3]) {
   if (g.R > 32) hipLaunchKernelGGL(k_ballot_audit<64>, grid, dim3(256), 0, ctx->stream, g, ctx->st, d);
   else if (g.R > 4) hipLaunchKernelGGL(k_ballot_audit<8>, grid, dim3(256), 0, ctx->stream, g, ctx->st, d);
   else hipLaunchKernelGGL(k_ballot_audit<1>, grid, dim3(256), 0, ctx->stream, g, ctx->st, d);
+  if ((rc = launch_check(ctx))) return rc;
+  HIPCHK(ctx, hipMemcpyAsync(out, d, 3 * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  return FPX_OK;
+}
+
+int32_t fpx_vote_summary_audit(fpx_ctx* ctx, int64_t out[3]) {
+  DeviceGuard _dg(ctx);
+  if (!ctx || !out) return FPX_EINVAL;
+  int rc;
+  if ((rc = grow(ctx, &ctx->d_scratch, 128))) return rc;
+  unsigned long long* d = (unsigned long long*)ctx->d_scratch.p;
+  HIPCHK(ctx, hipMemsetAsync(d, 0, 3 * sizeof(unsigned long long), ctx->stream));
+  hipLaunchKernelGGL(k_vote_audit, dim3(ctx->num_cus * 8), dim3(256), 0, ctx->stream, ctx->g, ctx->st, d);
   if ((rc = launch_check(ctx))) return rc;
   HIPCHK(ctx, hipMemcpyAsync(out, d, 3 * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));

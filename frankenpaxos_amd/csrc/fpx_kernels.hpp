@@ -41,6 +41,15 @@ typedef unsigned int uint4v __attribute__((ext_vector_type(4)));
 enum : uint32_t { KEY_DONE = 0x80000000u, KEY_RANGE = 0x40000000u, KEY_ROUND_MASK = 0x3fffffffu };
 constexpr int MAX_ROUND = 0x3ffffffe;
 constexpr int SUM_MIXED = INT32_MIN;  // State::ballot_sum: the row's cells differ (never a legal round)
+// State::row_voted, the state of a slot's vote rows
+enum : uint8_t {
+  ROW_FRESH = 0,    // nobody has voted: every cell of both vote rows is -1
+  ROW_CELLS = 1,    // the cells are authoritative
+  ROW_COMPACT = 2   // every acceptor r < R of the row's group holds State::vote_sum[row]; the stored cells are unspecified
+};
+struct __attribute__((aligned(8))) VoteRec {  // State::vote_sum: what every acceptor of a compact row voted
+  int32_t round, value;
+};
 constexpr int PART_ALL_STRIDE = 32;  // ints: one 128-byte line per shard of the whole-group maxima
 
 // One slot row in flight per wavefront: batching 2 / 4 rows per wave cost occupancy and measured
@@ -49,6 +58,12 @@ constexpr int PART_ALL_STRIDE = 32;  // ints: one 128-byte line per shard of the
 // already cover the latency.
 constexpr int CHUNK = 32;  // messages per wavefront chunk at R in (128, 256]: 64 / 32 / 16 / 8 measured,
                            // 32 and 16 are best (profiles/r01_tuning_sweep4.txt): finer units balance the XCDs
+// ... and in the contexts that keep vote-row records (State::vote_sum): a steady chunk is per-lane work only there, so at
+// 32 half the lanes idled and a launch was twice the workgroups.  32 against 64 in such contexts, three runs each:
+// headline 2.08e10 against 3.24e10 slots/s, thrifty 3.69e9 against 4.15e9, thrifty_random 2.31e9 against 2.34e9,
+// adversarial 7.31e8 against 7.33e8 (profiles/r09_vote_records.md).  The acceptor model's rows still cost their 2 KiB
+// of stores each and keep 32
+constexpr int CHUNK_RECORDS = 64;
 
 // status word layout in HBM (int32[8])
 // ST_ABORT: set by k_validate only (FPX_EINVAL / FPX_EORDER on a _dev batch): every later kernel up to the next
@@ -109,8 +124,9 @@ struct State {
   int32_t* lz_from;     // [ngroups][R]   first slot the lazy promise covers (the Phase1a's chosenWatermark)
   int32_t* max_ballot;  // [ngroups][R]   an upper bound of the acceptor's effective ballots
   int32_t* p1;          // [4][R] + 8     scratch of one Phase1a: mode / a / b / c per acceptor, then its control words (P1_SWEEP ..)
-  uint8_t* row_voted;   // [S]            0 = no acceptor of the slot's group has ever voted in it (its cells
-                        //                are all -1): partially voted cells can then be written whole without a read
+  uint8_t* row_voted;   // [S]            ROW_FRESH = no acceptor of the slot's group has ever voted in it (its cells
+                        //                are all -1): partially voted cells can then be written whole without a read;
+                        //                ROW_CELLS; ROW_COMPACT (only where vote_sum is kept)
   uint32_t* stamp;      // [S]            run id of the last run that touched the slot
   int32_t* run_round;   // [ngroups]      the single round of the current run per group (-1 = none)
   int32_t* status;      // [8]
@@ -126,7 +142,20 @@ struct State {
   // vote kernel that finds a row uniform takes its cells from this word instead of reading the row.  Kept only where the
   // vote kernel reads it, rows of more than 128 cells (sums_kept): elsewhere null, as if every row were SUM_MIXED
   int32_t* ballot_sum;  // [S] or null
+  // The same idea for the WRITES of the vote rows, kept where ballot_sum is kept: a chunk in which the whole group votes
+  // (the steady walk of the vote kernel) stores one (round, value) record per row and the row state ROW_COMPACT instead
+  // of 2 x R cells that all hold the same two words.  Whoever reads a cell of such a row takes the record (row_record);
+  // a vote that does not come from the whole group first writes the record into every cell (ROW_CELLS again).  Null:
+  // no row is ever ROW_COMPACT
+  VoteRec* vote_sum;    // [S] or null
 };
+
+// the record of row `prow` if the row is compact: the value of both vote arrays' cells r < R
+__device__ __forceinline__ bool row_record(const State& st, size_t prow, VoteRec* rec) {
+  if (!st.vote_sum || st.row_voted[prow] != ROW_COMPACT) return false;
+  *rec = st.vote_sum[prow];
+  return true;
+}
 
 // the ballot-row summaries are kept (and read by the vote kernel) for rows of more than 128 cells: 1 KiB rows, G = 64
 __host__ __device__ __forceinline__ bool sums_kept(const Geom& g) { return g.R > 128; }
@@ -149,7 +178,7 @@ struct Batch {
   int32_t parity;          // K1 / K3 launch counter mod 3: which third of part_all this launch uses
   uint32_t launch_seq;     // K1 / K3 launch counter (never 0): stamps the rows of `part` this launch writes
   int32_t check_round;     // validate: enforce one round per group (ACCEPTOR ballot mode)
-  int32_t chunk;           // K1 / K3 at G = 64: messages per wavefront (4 .. CHUNK)
+  int32_t chunk;           // K1 / K3 at G = 64: messages per wavefront (4 .. CHUNK, or CHUNK_RECORDS)
   int32_t index_base;      // added to the message index an error reports (host batches launched in pieces)
   int32_t solo;            // K1 / K3: the launch is ONE workgroup, which applies its maxima itself (no k_finalize follows)
   int32_t sc_lds;          // K1 / K3 on leader-group-major rows: byte offset of 4 x 3 KiB of LDS for the column quads (0 = none)
@@ -962,6 +991,52 @@ __global__ void __launch_bounds__(256) k_ballot_audit(const Geom g, const State 
   if (threadIdx.x < 3 && cnt[threadIdx.x]) atomicAdd(&out[threadIdx.x], cnt[threadIdx.x]);
 }
 
+// A wavefront writes a compact row out: its record into every cell of both vote rows (16 bytes per lane and array, RS is
+// a multiple of 4; cells past R are padding), then ROW_CELLS.  Any other row is left alone
+__device__ __forceinline__ void expand_row(const Geom& g, const State& st, int row, int lane) {
+  VoteRec rec;
+  if (!row_record(st, (size_t)row, &rec)) return;  // (the same answer in every lane: the state is written below, behind the loads)
+  for (int r0 = 4 * lane; r0 < g.RS; r0 += 256) {
+    const size_t c = (size_t)row * g.VS + r0;
+    *reinterpret_cast<int4v*>(st.vote_round + c) = int4v{rec.round, rec.round, rec.round, rec.round};
+    *reinterpret_cast<int4v*>(st.vote_value + c) = int4v{rec.value, rec.value, rec.value, rec.value};
+  }
+  if (lane == 0) st.row_voted[row] = ROW_CELLS;
+}
+
+// fpx_read_state copies whole arrays: every compact row becomes cells first.  One wavefront per row at a time
+__global__ void __launch_bounds__(256) k_expand_rows(const Geom g, const State st) {
+  const int lane = threadIdx.x & 63;
+  const int wave = (int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6), nwaves = (int)((gridDim.x * blockDim.x) >> 6);
+  for (int row = wave; row < g.S; row += nwaves) expand_row(g, st, row, lane);
+}
+
+// In front of a vote launch that carries target masks (whose kernels know nothing of records: their code is what it was
+// before there were any, see fpx_phase2_body.inc): the compact rows among the batch's slots become cells.  Launched only
+// while the context may hold compact rows at all.  Rows of more than 128 cells only (vote_sum): a slot is its row
+__global__ void __launch_bounds__(256) k_expand_batch(const Geom g, const State st, const int32_t* slot, int n) {
+  if (st.status[ST_ABORT] != 0) return;  // a failed validation applies nothing
+  const int lane = threadIdx.x & 63;
+  const int wave = (int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6), nwaves = (int)((gridDim.x * blockDim.x) >> 6);
+  for (int m = wave; m < n; m += nwaves) {
+    const int s = slot[m];
+    if (s >= 0 && s < g.S) expand_row(g, st, s, lane);
+  }
+}
+
+// fpx_vote_summary_audit: rows per state (ROW_FRESH, ROW_CELLS, ROW_COMPACT) into out[0..2]
+__global__ void __launch_bounds__(256) k_vote_audit(const Geom g, const State st, unsigned long long* out) {
+  __shared__ unsigned long long cnt[3];
+  if (threadIdx.x < 3) cnt[threadIdx.x] = 0ull;
+  __syncthreads();
+  for (int row = blockIdx.x * blockDim.x + threadIdx.x; row < g.S; row += gridDim.x * blockDim.x) {
+    const int v = st.row_voted[row];
+    atomicAdd(&cnt[v < 2 ? v : 2], 1ull);
+  }
+  __syncthreads();
+  if (threadIdx.x < 3 && cnt[threadIdx.x]) atomicAdd(&out[threadIdx.x], cnt[threadIdx.x]);
+}
+
 __global__ void k_lazy_clear(const Geom g, const State st) {
   const int e = blockIdx.x * blockDim.x + threadIdx.x;
   if (e < g.ngroups * g.R) st.lz_round[e] = -1, st.lz_from[e] = 0;
@@ -999,8 +1074,13 @@ __global__ void __launch_bounds__(256) k_gather_acceptor(const Geom g, const Sta
   if (s >= g.S) return;
   const bool mine = group_of_slot(g, s) == group;
   const size_t ps = (size_t)phys_slot(g, s), c = ps * g.RS + replica, vc = ps * g.VS + replica;
-  vr[s] = mine ? st.vote_round[vc] : -1;
-  vv[s] = mine ? st.vote_value[vc] : -1;
+  VoteRec rec;
+  if (mine && row_record(st, ps, &rec)) {
+    vr[s] = rec.round, vv[s] = rec.value;
+  } else {
+    vr[s] = mine ? st.vote_round[vc] : -1;
+    vv[s] = mine ? st.vote_value[vc] : -1;
+  }
   bl[s] = (mine && st.ballot) ? st.ballot[c] : -1;
 }
 
@@ -1014,7 +1094,9 @@ __global__ void __launch_bounds__(256) k_max_voted_in(const Geom g, const State 
   int best = -1;
   if (i < count) {
     const int s = first + i;
-    if (group_of_slot(g, s) == group && st.vote_round[(size_t)phys_slot(g, s) * g.VS + replica] != -1) best = s;
+    const size_t ps = (size_t)phys_slot(g, s);
+    VoteRec rec;
+    if (group_of_slot(g, s) == group && (row_record(st, ps, &rec) ? rec.round : st.vote_round[ps * g.VS + replica]) != -1) best = s;
   }
 #pragma unroll
   for (int k = 1; k < 64; k <<= 1) {
@@ -1202,9 +1284,13 @@ __global__ void __launch_bounds__(256)
     int best_round = -1, best_val = -1, best_idx = 1 << 30;
     if (live && r0 < g.R) {
       const int grp = group_of_slot(g, s);
-      const size_t row = (size_t)phys_slot(g, s) * g.VS + r0;
+      const size_t ps = (size_t)phys_slot(g, s), row = ps * g.VS + r0;
       int vr[4] = {-1, -1, -1, -1}, vv[4] = {-1, -1, -1, -1};
-      if (vec) {
+      VoteRec rec;
+      if (row_record(st, ps, &rec)) {  // (cells past R are masked below, as for the 16-byte loads)
+#pragma unroll
+        for (int k = 0; k < 4; ++k) vr[k] = rec.round, vv[k] = rec.value;
+      } else if (vec) {
         const int4v a = *reinterpret_cast<const int4v*>(st.vote_round + row);
         const int4v c = *reinterpret_cast<const int4v*>(st.vote_value + row);
 #pragma unroll
@@ -1285,15 +1371,24 @@ __device__ __forceinline__ void block_add_u64(uint64_t v, uint64_t* out) {
   }
 }
 
-// a cell array [S][RS]: element (s, r), r < R, contributes digest_term(s * R + r, a[s][r])
-__global__ void __launch_bounds__(256) k_digest_cells(const Geom g, const int32_t* a, int stride, uint64_t* out) {
+// a cell array [S][RS]: element (s, r), r < R, contributes digest_term(s * R + r, a[s][r]).  which = 0 / 1: the array is
+// vote_round / vote_value, whose compact rows (row_record) count as the cells they stand for; -1: no such rows
+__global__ void __launch_bounds__(256) k_digest_cells(const Geom g, const State st, const int32_t* a, int stride, int which,
+                                                      uint64_t* out) {
   const size_t q = (size_t)(g.RS >> 2);  // int4's per row; row s starts at a + s * stride
   const size_t n4 = (size_t)g.S * q;
   uint64_t acc = 0;
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (size_t)gridDim.x * blockDim.x) {
     const size_t prow = i / q, s = (size_t)slot_of_row(g, (int)prow);
     const int r0 = (int)(i - prow * q) * 4;
-    const int4v v = *reinterpret_cast<const int4v*>(a + prow * (size_t)stride + (size_t)r0);
+    int4v v;
+    VoteRec rec;
+    if (which >= 0 && row_record(st, prow, &rec)) {
+      const int c = which == 0 ? rec.round : rec.value;
+      v = int4v{c, c, c, c};
+    } else {
+      v = *reinterpret_cast<const int4v*>(a + prow * (size_t)stride + (size_t)r0);
+    }
 #pragma unroll
     for (int k = 0; k < 4; ++k)
       if (r0 + k < g.R) acc += digest_term(s * (size_t)g.R + (size_t)(r0 + k), v[k]);

@@ -87,6 +87,19 @@ __device__ __forceinline__ int4v p1i_load(const int32_t* a, size_t row, int r0, 
   return v;
 }
 
+// the lane's four cells of both vote rows of row `ps` (vv null: the rounds only); a compact row's are its record
+__device__ __forceinline__ void p1i_load_votes(const Geom& g, const State& st, size_t ps, int r0, int vec, int4v* vr, int4v* vv) {
+  VoteRec rec;
+  if (row_record(st, ps, &rec)) {  // (cells past R: masked by the callers' `sel`)
+    *vr = int4v{rec.round, rec.round, rec.round, rec.round};
+    if (vv) *vv = int4v{rec.value, rec.value, rec.value, rec.value};
+    return;
+  }
+  const size_t row = ps * g.VS + r0;
+  *vr = p1i_load(st.vote_round, row, r0, g.R, vec);
+  if (vv) *vv = p1i_load(st.vote_value, row, r0, g.R, vec);
+}
+
 template <int G>
 __global__ void __launch_bounds__(256) k_p1i_count(const Geom g, const State st, const P1iArgs a) {
   if (st.status[ST_ABORT] != 0) return;
@@ -115,7 +128,8 @@ __global__ void __launch_bounds__(256) k_p1i_count(const Geom g, const State st,
           const int j = i * Q + q;
           const int64_t s = first + (int64_t)j * NG;
           if (s < a.lo || s >= g.S) continue;
-          const int4v vr = p1i_load(st.vote_round, (size_t)phys_slot(g, (int)s) * g.VS + r0, r0, g.R, a.vec);
+          int4v vr;
+          p1i_load_votes(g, st, (size_t)phys_slot(g, (int)s), r0, a.vec, &vr, nullptr);
 #pragma unroll
           for (int k = 0; k < 4; ++k)
             if (vr[k] != -1) w[k] |= 1ull << j;
@@ -244,9 +258,7 @@ __global__ void __launch_bounds__(64) k_p1i_scatter(const Geom g, const State st
         const bool live = sel && s >= a.lo && s < g.S;
         int4v vr = {-1, -1, -1, -1}, vv = {-1, -1, -1, -1};
         if (live) {
-          const size_t row = (size_t)phys_slot(g, (int)s) * g.VS + r0;
-          vr = p1i_load(st.vote_round, row, r0, g.R, a.vec);
-          vv = p1i_load(st.vote_value, row, r0, g.R, a.vec);
+          p1i_load_votes(g, st, (size_t)phys_slot(g, (int)s), r0, a.vec, &vr, &vv);
         }
 #pragma unroll
         for (int k = 0; k < 4; ++k) {

@@ -27,6 +27,14 @@ __global__ void __launch_bounds__(256)
   // the 4-byte gather of its summary, and at G = 8 .. 32 the bookkeeping cost these kernels a wave per SIMD
   // (kernel-resource-usage) for a gain nothing measures.  Below G = 64 there are no summaries (State::ballot_sum null)
   constexpr bool SUMREAD = PERSLOT && G == 64;
+  // the vote-row records (State::vote_sum, ROW_COMPACT) live where the summaries do, and only the dense kernels know of
+  // them.  The steady walk writes them; a dense chunk that takes the general walk first turns the compact rows it
+  // delivers to back into cells.  The kernels that carry target masks (MODE 1, 2, 3) never meet a compact row: the host
+  // launches k_expand_batch in front of them while the context may hold any, and their code is what it was before there
+  // were records -- with the gather of the row state as an int and the test for a compact row in them, per step or per
+  // chunk, the adversarial stream (4 messages per wavefront, no row ever compact) ran 2.4 % below the parent's rate,
+  // without them at it (profiles/r09_vote_records.md)
+  constexpr bool RECS = SUMREAD && MODE == 0;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   FPX_P2_PROLOGUE
 
@@ -187,7 +195,14 @@ __global__ void __launch_bounds__(256)
       if (g.lg_rows || !one_group) place_of_slot(g, myslot, &myphys, &mygrp);
     }
     bool myfresh = false;
-    if constexpr (TGT) myfresh = mv && st.row_voted[myphys] == 0;
+    bool mycompact = false;     // my message's row is a record (its state is gathered with the chunk, like its summary)
+    bool compacted = false;     // the chunk took the steady walk: its rows leave as records
+    if constexpr (RECS) {
+      const int rs = mv ? (int)st.row_voted[myphys] : (int)ROW_CELLS;
+      mycompact = rs == ROW_COMPACT;
+    } else if constexpr (TGT) {
+      myfresh = mv && st.row_voted[myphys] == 0;
+    }
     int mysum = SUM_MIXED;  // the summary of my message's row (SUM_MIXED: read the row)
     if constexpr (SUMREAD) mysum = mv ? st.ballot_sum[myphys] : SUM_MIXED;  // (G = 64: R > 128, allocated: sums_kept)
     // ---- walk the chunk, Q slots per step; the ballot row of the next step is already in flight ----
@@ -441,34 +456,34 @@ __global__ void __launch_bounds__(256)
     __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0), expcnt and lgkmcnt untouched
     // The steady walk.  A chunk every valid message of which is delivered (a new (slot, round) with a free way) to a
     // uniform row whose round it is not below makes the same choice in every row: the whole group votes (a quorum, checked
-    // once above), nobody Nacks, the slot is chosen.  Its rows then cost only their stores, taken from the lanes as
-    // scalars -- the general walk's decision, bitmap and reductions (~650 instructions per row) are what paced the
-    // headline once the uniform rows were no longer read (profiles/r08_steady_walk.md).  What it writes is what the
-    // general walk writes for such a chunk, store for store: both rows, the ballot row and its summary where the round
-    // moves, the whole-group maxima, and (below the walk) the chosen records.  A slot met twice in the chunk sees the
-    // summary gathered with the chunk on both paths.
+    // once above), nobody Nacks, the slot is chosen.  The general walk's decision, bitmap and reductions (~650
+    // instructions per row) are what paced the headline once the uniform rows were no longer read
+    // (profiles/r08_steady_walk.md); the 2 KiB of vote cells per row, 512 copies of two words, were 98 % of its bytes
+    // after that (profiles/r09_vote_records.md).  Such a chunk writes per-lane data only: its rows' records, and (below
+    // the walk) their state, key words and chosen records; the ballot row and its summary where the round moves, and
+    // the whole-group maxima, are what the general walk writes.  The decision does not depend on what the rows held:
+    // the whole group overwrites it.  The per-lane record stores rely on the run contract (include/fpx.h): the slots of a
+    // batch are pairwise distinct, so no two lanes store one record.
     bool steady = false;
     if constexpr (STEADY)
       steady = steady_ok && __all(!mv || (mydeliver && myslot >= 0 && mysum != SUM_MIXED && myround >= mysum));
     if (STEADY && steady) {
-      const int nv = b.n - v0 < CH ? b.n - v0 : CH;  // the valid messages are the first nv lanes
-      for (int t = 0; t < nv; ++t) {
+      // no vote cells: the whole group votes in every row, so a row is its message's (round, value) -- one record per
+      // lane, and (below the walk) the row state ROW_COMPACT
+      compacted = true;
+      if (mv) st.vote_sum[myphys] = VoteRec{myround, myvalue};
+      // the rows whose ballot moves still get their 1 KiB ballot row and its summary (none in a stream that stays in its round)
+      for (uint64_t mov = __ballot(mv && myround != mysum); mov; mov &= mov - 1) {
+        const int t = (int)__ffsll((unsigned long long)mov) - 1;
         const int s = __builtin_amdgcn_readlane(myslot, t);
         const int rnd = __builtin_amdgcn_readlane(myround, t);
-        const int val = __builtin_amdgcn_readlane(myvalue, t);
-        const int bs = __builtin_amdgcn_readlane(mysum, t);
-        if (own) {
-          const int4v rr = {rnd, rnd, rnd, rnd};
-          const int4v vv = {val, val, val, val};
-          const size_t vrow = (size_t)s * (size_t)g.VS + (size_t)r0;
-          row_store(rr, reinterpret_cast<int4v*>(st.vote_round + vrow));
-          row_store(vv, reinterpret_cast<int4v*>(st.vote_value + vrow));
-          if (rnd != bs) row_store(rr, reinterpret_cast<int4v*>(st.ballot + (size_t)s * (size_t)g.RS + (size_t)r0));
-        }
-        if (rnd != bs && lane == 0) st.ballot_sum[s] = rnd;
-        w_slot = s > w_slot ? s : w_slot;
-        w_round = rnd > w_round ? rnd : w_round;
+        if (own) row_store(int4v{rnd, rnd, rnd, rnd}, reinterpret_cast<int4v*>(st.ballot + (size_t)s * (size_t)g.RS + (size_t)r0));
+        if (lane == 0) st.ballot_sum[s] = rnd;
       }
+      const int ms = __builtin_amdgcn_readlane(wave_max_to_lane63(mv ? myslot + 1 : 0), 63) - 1;
+      const int mr = __builtin_amdgcn_readlane(wave_max_to_lane63(mv ? myround + 1 : 0), 63) - 1;
+      w_slot = ms > w_slot ? ms : w_slot;
+      w_round = mr > w_round ? mr : w_round;
       if constexpr (FUSED) {
         if (mv) wo->chosen[lane] = 1, wo->nack_round[lane] = -1;
       } else {
@@ -482,6 +497,27 @@ __global__ void __launch_bounds__(256)
       }
     }
     if (!STEADY || !steady) {  // (without the steady walk: no branch at all, the code of the kernels before it)
+    // Compact rows a message of this chunk is delivered to become cells BEFORE the walk: every lane stores the record
+    // into all its cells of both rows (even if nobody will vote), the row is ROW_CELLS from here on, and the walk below
+    // is the code it was before there were records.  One scalar test per chunk; the cells a step then votes in are
+    // stored twice, on a path only a change of regime takes.  An undelivered message (a known (slot, round)) leaves
+    // its row a record.
+    if constexpr (RECS) {
+      const bool mine = mycompact && mydeliver;
+      if (const uint64_t exp = __ballot(mine)) {
+        for (uint64_t e = exp; e; e &= e - 1) {
+          const int ps = __builtin_amdgcn_readlane(myphys, (int)__ffsll((unsigned long long)e) - 1);
+          const VoteRec rec = st.vote_sum[ps];  // (one address for the wavefront)
+          if (own) {
+            const size_t vrow = (size_t)ps * (size_t)g.VS + (size_t)r0;
+            row_store(int4v{rec.round, rec.round, rec.round, rec.round}, reinterpret_cast<int4v*>(st.vote_round + vrow));
+            row_store(int4v{rec.value, rec.value, rec.value, rec.value}, reinterpret_cast<int4v*>(st.vote_value + vrow));
+          }
+        }
+        if (mine) st.row_voted[myphys] = ROW_CELLS;
+        __builtin_amdgcn_s_waitcnt(0x0F70);  // the walk overwrites these cells: behind the stores
+      }
+    }
     if constexpr (!EARLY) thr_cur = load_thr(0, s_cur, grp_cur, phys_cur);
     for (int t = 0; t < G * CH / 64; ++t) {
       const int src = t * Q + q;
@@ -706,7 +742,12 @@ __global__ void __launch_bounds__(256)
     // ---- outputs of the 64 messages leave as coalesced lines ------------------------------------
     wave_lds_sync();
     // the slot's row is no longer known to be all -1 (marked even if every acceptor Nacked: that only costs the shortcut)
-    if (TGT ? (myfresh && mydeliver) : (mv && mydeliver)) st.row_voted[myphys] = 1;
+    // (a steady chunk delivers every valid message and leaves records; the compact rows of any other were marked above)
+    if (STEADY && compacted) {
+      if (mv) st.row_voted[myphys] = ROW_COMPACT;
+    } else if (TGT ? (myfresh && mydeliver) : (mv && mydeliver)) {
+      st.row_voted[myphys] = ROW_CELLS;
+    }
     if (mv) {
       if constexpr (!FUSED) {
         if (b.vote_bits) {

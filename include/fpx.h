@@ -112,7 +112,7 @@ typedef enum {
  * voted 16-byte cells by read-modify-write instead of 4-byte stores.  Results are identical either way. */
 #define FPX_F_SCATTERED_TARGETS 2u
 /* Without that hint, on 256-cell rows of one acceptor group (R = 253 .. 256, threshold / majority / unanimous quorums),
- * launches that carry target masks run as TWO kernels: chunks of 32 messages that all go to a RUN of neighbouring
+ * launches that carry target masks run as TWO kernels: chunks of up to 64 messages that all go to a RUN of neighbouring
  * acceptors -- positions [start, start + len) of the row, cyclically, start a multiple of 16, len <= 128: what a proxy
  * leader sends that rotates a window of f + 1 acceptors over the group instead of shuffling (any f + 1 will do,
  * ProxyLeader.scala:190-191; jni/Native.scala's GpuProxyLeader does) -- of rows nobody voted in yet are walked two
@@ -1347,7 +1347,11 @@ int32_t fpx_acceptor_phase1(fpx_ctx* ctx, int32_t round, int32_t chosen_watermar
 int32_t fpx_read_acceptor(fpx_ctx* ctx, int32_t group, int32_t replica, int32_t* promised,
                           int32_t* max_voted_slot, int32_t* vote_round, int32_t* vote_value,
                           int32_t* ballot);
-/* whole-array readback, slot-major [S][R] int32 (may be NULL each) */
+/* whole-array readback, slot-major [S][R] int32 (may be NULL each).  FPX_BALLOT_PER_SLOT with more than 128 acceptors
+ * per group keeps the votes of a row in which the whole group voted as one (round, value) record instead of 2 x R cells
+ * (fpx_vote_summary_audit); a readback of either vote array first writes every such record into its row's cells, so a
+ * read-only caller still costs those rows their 2 KiB each and their compact form -- fpx_read_acceptor,
+ * fpx_state_digest and the Phase1b entry points answer from the records and leave them. */
 int32_t fpx_read_state(fpx_ctx* ctx, int32_t* vote_round, int32_t* vote_value, int32_t* ballot);
 /* per-acceptor scalars, [num_leader_groups * num_groups][R] */
 int32_t fpx_read_scalars(fpx_ctx* ctx, int32_t* promised, int32_t* max_voted_slot);
@@ -1419,6 +1423,15 @@ int32_t fpx_state_digest(fpx_ctx* ctx, uint64_t out[8]);
  * acceptors keep no summaries: every row counts as mixed.  FPX_EINVAL in FPX_BALLOT_ACCEPTOR mode.  Waits for the
  * stream. */
 int32_t fpx_ballot_summary_audit(fpx_ctx* ctx, int64_t out[3]);
+
+/* The states of the vote rows, a test hook.  out[0] = fresh rows (no vote, every cell -1), out[1] = rows whose cells are
+ * authoritative, out[2] = compact rows: every acceptor of the row's group holds the row's (round, value) record and the
+ * stored cells are unspecified.  Records are kept where the ballot summaries are (FPX_BALLOT_PER_SLOT, more than 128
+ * acceptors per group); elsewhere out[2] is 0.  out[0] + out[1] + out[2] = num_slots.  A row goes compact when a batch
+ * without target masks has the whole group vote in it; it becomes cells again when a dense batch delivers a message to
+ * it that not the whole group accepts, and when a batch WITH target masks names its slot (delivered or not).  Waits for
+ * the stream. */
+int32_t fpx_vote_summary_audit(fpx_ctx* ctx, int64_t out[3]);
 
 #ifdef __cplusplus
 }
