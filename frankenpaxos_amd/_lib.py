@@ -49,6 +49,11 @@ CENSUS_WORDS = CENSUS_CELLS * len(CENSUS_FORMS) + 3
 # fpx_range_launch_census (include/fpx.h): its words in order
 RANGE_CENSUS_FORMS = ("chain", "steps", "band", "fill_lg", "fill_sweep", "fill_range", "tally_only", "open_only",
                       "acceptors_only", "rehash")
+# fpx_epx_tick_census and fpx_epx_limits (include/fpx.h): their words in order
+EPX_CENSUS_WORDS = ("kp", "kp_handed_over", "v1_switched_off", "v1_keys", "v1_full", "v1_log_n3", "v1_index_bits",
+                    "no_key_kernel", "scalar_loads", "sort_bucket1", "sort_bucket2", "sort_radix1", "sort_radix2",
+                    "sort_radix3", "long_way")
+EPX_LIMIT_WORDS = ("kp_tc", "key_tc", "nbk", "kp_max_occ", "kp_maxb", "kp_waves")
 
 
 class FpxConfig(C.Structure):
@@ -145,6 +150,8 @@ SIGNATURES = {
     "fpx_epx_create": (C.c_int32, [VP, C.POINTER(VP)]),
     "fpx_epx_destroy": (C.c_int32, [VP]),
     "fpx_epx_info": (C.c_int32, [VP, I32P, I32P, I32P]),
+    "fpx_epx_limits": (C.c_int32, [VP, C.c_int32, I32P, I32P]),
+    "fpx_epx_tick_census": (C.c_int32, [VP, C.c_int32, C.POINTER(C.c_int64), I32P]),
     "fpx_epx_set_stream": (C.c_int32, [VP, VP]),
     "fpx_epx_sync": (C.c_int32, [VP]),
     "fpx_epx_preaccept": (C.c_int32, [VP, C.c_int32] + [VP] * 12),

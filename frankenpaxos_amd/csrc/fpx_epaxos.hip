@@ -90,7 +90,14 @@ struct EpxBatch {
   int2* meta;               // [m] or null: (number, resp_mask | seen_mask << 8) of message i, ONE gather for k_epx_key
   uint8_t* fused;           // [num_keys] or null: 1 = k_epx_key did the key's scan and decisions on chip
   int32_t* unfused;         // number of keys left to k_epx_scan / k_epx_decide (null: all of them)
+  unsigned long long* census;  // [EPX_CD_WORDS] the first form's device words of fpx_epx_tick_census, or null
 };
+
+// the device's words of fpx_epx_tick_census (include/fpx.h: FPX_EPX_CENSUS_SORT_BUCKET1 ... in this order).  The first
+// EPX_CD_SORTS are the sort routes of k_epx_key2 (fpx_epaxos_kp.hpp), tallied in LDS per workgroup and kept in the second
+// form's own control buffer (launch_kp); EPX_CD_LONG_WAY is the first form's, in the context's census buffer
+constexpr int EPX_CD_BUCKET1 = 0, EPX_CD_RADIX1 = 2, EPX_CD_SORTS = 5;  // (bucket attempts 1, 2; radix sorts of 1, 2, 3 passes)
+constexpr int EPX_CD_LONG_WAY = 5, EPX_CD_WORDS = 8;
 
 constexpr uint32_t EPX_KEY_MASK = (1u << 27) - 1u;
 constexpr int EPX_SET_SHIFT = 27, EPX_LEADER_SHIFT = 28;
@@ -852,6 +859,8 @@ __global__ void __launch_bounds__(256) k_epx_commit(const EpxState st, const Epx
   if (st.status[0] != 0) return;
   const long long per = (long long)st.num_keys * st.n;            // entries of one replica's gets (or sets)
   const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  // fpx_epx_tick_census: the keys k_epx_key left to the long way this tick (kernels of one stream: no atomic needed)
+  if (t == 0 && b.census && b.unfused) b.census[EPX_CD_LONG_WAY] += (unsigned long long)*b.unfused;
   if (t >= per * st.n) return;
   const int r = (int)(t / per);
   const long long e = t % per;                                    // key * n + leader
@@ -1392,6 +1401,8 @@ struct fpx_epx {
   uint32_t* kp_flag_dev = nullptr;
   uint32_t kp_seq = 0;
   bool kp_lds_allowed = false, kp_off = false;
+  int64_t census[FPX_EPX_CENSUS_WORDS] = {};       // fpx_epx_tick_census: the host's words (the device's are added when it is read)
+  unsigned long long* census_dev = nullptr;        // [EPX_CD_WORDS]
   uint32_t cl_run = 0;
   EpxLeader ls = {nullptr, nullptr};      // FPX_EPX_F_LEADER_STATE: Replica.leaderStates (fpx_epx_leader.hpp), else not allocated
   DevBuf lr_misc;                         // fpx_epx_leader_replies: the decided flags and the compaction's block counts
@@ -1596,9 +1607,9 @@ int launch_kp(fpx_epx* e, const EpxBatch& b, int32_t* d_packed, bool* done) {
   if ((rc = grow(e, &e->kp_hist, (size_t)a.tiles * a.B * 2))) return rc;
   if ((rc = grow(e, &e->kp_recs, (size_t)a.B * T::TC * T::NI * 4))) return rc;
   {
-    // fingerprints, control and verdict words, one word per group of tiles (m < 2^21: at most 128 groups), then the claim
-    // counters (one 64-byte sector per key): they must read zero before the first tick, later the key kernel leaves
-    // them at zero
+    // fingerprints, control and verdict words, the census of the sort routes, one word per group of tiles (m < 2^21: at
+    // most 128 groups), then the claim counters (one 64-byte sector per key): they must read zero before the first tick,
+    // later the key kernel leaves them at zero.  (num_keys is the context's: the buffer grows once, the census is never lost)
     const size_t need = 1024 + (size_t)a.B * KP_TOT_STRIDE * 4;
     if (need > e->kp_misc.cap) {
       if ((rc = grow(e, &e->kp_misc, need))) return rc;
@@ -1610,6 +1621,9 @@ int launch_kp(fpx_epx* e, const EpxBatch& b, int32_t* d_packed, bool* done) {
   a.fp = (unsigned long long*)misc;              // 16 words of 8 bytes
   a.ctl = (uint32_t*)(misc + 128);               // 1 word
   a.bad = (uint32_t*)(misc + 192);               // 2 words
+  // misc + 256: EPX_CD_SORTS words of 8 bytes, the census of k_epx_key2's sort routes.  The kernel reaches them from a.tot
+  // (tot - KP_CENSUS_BACK), a pointer it holds anyway: a pointer of their own was two more registers at n = 5
+  static_assert(1024 - KP_CENSUS_BACK * 4 == 256 && 256 + EPX_CD_SORTS * 8 <= 512, "the census words lie between bad and big");
   a.big = (uint32_t*)(misc + 512);               // [groups <= 128]
   a.tot = (uint32_t*)(misc + 1024);
   a.host_flag = e->kp_flag_dev, a.tc = T::TC;
@@ -1619,6 +1633,7 @@ int launch_kp(fpx_epx* e, const EpxBatch& b, int32_t* d_packed, bool* done) {
                      (uintptr_t)b.is_set | (uintptr_t)b.seen_mask;
     a.vec = (bits & 15u) == 0 && (b.m & 3) == 0;
   }
+  if (!a.vec) ++e->census[FPX_EPX_CENSUS_SCALAR_LOADS];
   if (!e->kp_lds_allowed) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_epx_key2<N, false>), hipFuncAttributeMaxDynamicSharedMemorySize,
                               (int)T::BYTES);
@@ -1655,7 +1670,11 @@ int launch_kp(fpx_epx* e, const EpxBatch& b, int32_t* d_packed, bool* done) {
     HIPCHK(e, hipStreamSynchronize(ps));
     if (flag[0] != a.seq) return FPX_EHIP;
   }
-  if (flag[1] != 0) return FPX_OK;  // a hot key: the first form takes the whole tick
+  if (flag[1] != 0) {  // a hot key: the first form takes the whole tick
+    ++e->census[FPX_EPX_CENSUS_KP_HANDED_OVER];
+    return FPX_OK;
+  }
+  ++e->census[FPX_EPX_CENSUS_KP];
   *done = true;
   return FPX_OK;
 }
@@ -1953,6 +1972,8 @@ int32_t fpx_epx_create(const fpx_epx_config* cfg, fpx_epx** out) {
     (void)hipGetLastError();
   }
   e->kp_off = getenv("FPX_EPX_V1") != nullptr;
+  if (hipMalloc((void**)&e->census_dev, EPX_CD_WORDS * 8) != hipSuccess) return fail(FPX_ENOMEM);
+  if (hipMemsetAsync(e->census_dev, 0, EPX_CD_WORDS * 8, e->stream) != hipSuccess) return fail(FPX_EHIP);
   if (hipStreamSynchronize(e->stream) != hipSuccess) return fail(FPX_EHIP);
   *out = e;
   return FPX_OK;
@@ -1963,7 +1984,7 @@ int32_t fpx_epx_destroy(fpx_epx* e) {
   DeviceScope _dg(e->cfg.device);
   if (e->stream) (void)hipStreamSynchronize(e->stream);
   void* ps[] = {e->st.gets, e->st.sets, e->st.status, e->st.cl_status, e->st.cl_ballot, e->st.cl_vote, e->st.cl_triple,
-                e->st.largest, e->st.cl_stamp, e->st.cl_deps, e->st.cl_dend, e->ls.head, e->ls.resp};
+                e->st.largest, e->st.cl_stamp, e->st.cl_deps, e->st.cl_dend, e->ls.head, e->ls.resp, e->census_dev};
   for (void* p : ps)
     if (p) (void)hipFree(p);
   DevBuf* bs[] = {&e->kv, &e->kv2, &e->seg, &e->conf, &e->tmp, &e->tick, &e->fusedb, &e->metab, &e->stage, &e->mk_misc, &e->mk_rec,
@@ -2037,6 +2058,14 @@ static int32_t preaccept_dev_impl(fpx_epx* e, int32_t m, const int32_t* d_leader
     bool done = false;
     if ((rc = by_n(n, [&](auto N) { return launch_kp<N>(e, kb, d_packed, &done); }))) return rc;
     if (done) return launch_check(e);
+  } else {
+    // fpx_epx_tick_census: why the second form was not tried -- the first reason that holds, in the header's order
+    const int why = e->kp_off || !e->kp_flag_dev                            ? FPX_EPX_CENSUS_V1_SWITCHED_OFF
+                    : e->st.num_keys > KP_MAXB                              ? FPX_EPX_CENSUS_V1_KEYS
+                    : (long long)m > (long long)e->st.num_keys * kp_tc      ? FPX_EPX_CENSUS_V1_FULL
+                    : !((e->st.num_instances == 0 && !d_triple_id) || n >= 5) ? FPX_EPX_CENSUS_V1_LOG_N3
+                                                                            : FPX_EPX_CENSUS_V1_INDEX_BITS;
+    ++e->census[why];
   }
   if (d_packed && (rc = packed_fallback(e, m, &d_fast, &d_deps, &d_leader_deps, &d_own_values_end))) return rc;
   if ((rc = grow(e, &e->kv, (size_t)n * m * 8))) return rc;
@@ -2054,8 +2083,11 @@ static int32_t preaccept_dev_impl(fpx_epx* e, int32_t m, const int32_t* d_leader
   b.tick = (int32_t*)e->tick.p;
   b.seg = (int32_t*)e->seg.p, b.conf = (int32_t*)e->conf.p;
   b.fast = d_fast, b.deps = d_deps, b.leader_deps = d_leader_deps, b.own_values_end = d_own_values_end;
+  b.census = e->census_dev;
   // the per-key on-chip path (k_epx_key): message indices must fit its 21-bit hash words, one workgroup per key
-  if (m < (1 << 21) - 1 && e->st.num_keys <= (1 << 16) && !getenv("FPX_EPX_NO_KEY_TILES")) {
+  const bool key_kernel = m < (1 << 21) - 1 && e->st.num_keys <= (1 << 16) && !getenv("FPX_EPX_NO_KEY_TILES");
+  if (!key_kernel) ++e->census[FPX_EPX_CENSUS_NO_KEY_KERNEL];
+  if (key_kernel) {
     if ((rc = grow(e, &e->fusedb, (size_t)e->st.num_keys + 64))) return rc;
     b.unfused = (int32_t*)e->fusedb.p;
     b.fused = (uint8_t*)e->fusedb.p + 64;
@@ -2615,6 +2647,37 @@ int32_t fpx_epx_info(fpx_epx* e, int32_t* num_replicas, int32_t* num_keys, int32
   if (num_replicas) *num_replicas = e->st.n;
   if (num_keys) *num_keys = e->st.num_keys;
   if (num_instances) *num_instances = e->st.num_instances;
+  return FPX_OK;
+}
+
+int32_t fpx_epx_limits(fpx_epx* e, int32_t cap, int32_t* out, int32_t* n) {
+  if (!e || cap < 0 || (cap > 0 && !out)) return FPX_EINVAL;
+  int32_t v[FPX_EPX_LIMIT_WORDS];
+  by_n(e->st.n, [&](auto N) {
+    v[FPX_EPX_LIMIT_KP_TC] = KpTile<N>::TC, v[FPX_EPX_LIMIT_KEY_TC] = KeyTile<N>::TC, v[FPX_EPX_LIMIT_NBK] = KpTile<N>::NBK;
+    v[FPX_EPX_LIMIT_KP_WAVES] = KpTile<N>::W;
+    return 0;
+  });
+  v[FPX_EPX_LIMIT_KP_MAX_OCC] = KP_MAX_OCC, v[FPX_EPX_LIMIT_KP_MAXB] = KP_MAXB;
+  for (int j = 0; j < std::min<int>(cap, FPX_EPX_LIMIT_WORDS); ++j) out[j] = v[j];
+  if (n) *n = FPX_EPX_LIMIT_WORDS;
+  return FPX_OK;
+}
+
+int32_t fpx_epx_tick_census(fpx_epx* e, int32_t cap, int64_t* out, int32_t* n) {
+  if (!e || cap < 0 || (cap > 0 && !out)) return FPX_EINVAL;
+  DeviceScope _dg(e->cfg.device);
+  unsigned long long dev[EPX_CD_WORDS] = {};
+  HIPCHK(e, hipMemcpyAsync(dev, e->census_dev, sizeof(dev), hipMemcpyDeviceToHost, e->stream));
+  if (e->kp_misc.p)  // the sort routes: counted beside the second form's control words (launch_kp)
+    HIPCHK(e, hipMemcpyAsync(dev, (char*)e->kp_misc.p + 256, EPX_CD_SORTS * 8, hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(e, hipStreamSynchronize(e->stream));
+  int64_t v[FPX_EPX_CENSUS_WORDS];
+  for (int j = 0; j < FPX_EPX_CENSUS_WORDS; ++j) v[j] = e->census[j];
+  static_assert(FPX_EPX_CENSUS_WORDS - FPX_EPX_CENSUS_SORT_BUCKET1 == EPX_CD_LONG_WAY + 1, "the device's words, in the header's order");
+  for (int j = 0; j <= EPX_CD_LONG_WAY; ++j) v[FPX_EPX_CENSUS_SORT_BUCKET1 + j] = (int64_t)dev[j];
+  for (int j = 0; j < std::min<int>(cap, FPX_EPX_CENSUS_WORDS); ++j) out[j] = v[j];
+  if (n) *n = FPX_EPX_CENSUS_WORDS;
   return FPX_OK;
 }
 

@@ -35,8 +35,7 @@ constexpr int KP_RADIX_BITS = 7, KP_RADIX = 1 << KP_RADIX_BITS;
 constexpr int KP_MAX_OCC = 24;           // fullest rank bucket the bucket sort accepts before the key is radix-sorted instead
 constexpr int KP_TOT_STRIDE = 16;        // words between two keys' claim counters: a 64-byte sector each (the claims of
                                          // 1024 keys are returning atomics on 1024 different sectors, not on 32 lines)
-constexpr int KP_IDX_BITS = 21;          // message indices and ranks: m < 2^21
-constexpr uint32_t KP_IDX_MASK = (1u << KP_IDX_BITS) - 1u;
+constexpr int KP_CENSUS_BACK = 192;       // words from the census of the sort routes to the claim counters behind it (launch_kp)
 constexpr uint32_t KP_INVALID = 0xffffffffu;  // sort word of a command the replica takes no part in (sorts last)
 
 template <int N> struct KpTile {
@@ -66,58 +65,7 @@ template <int N> struct KpTile {
   static_assert(TC <= (1 << KP_SLOT_BITS), "slots share the sort word with the rank");
 };
 
-// flags of a command as the key kernel keeps them: leader | is_set << 3 | resp_mask << 8 | seen_mask << 16
-__device__ __forceinline__ int kp_flags(int L, int is_set, unsigned resp, unsigned seen) {
-  return L | (is_set ? 8 : 0) | (int)(resp << 8) | (int)(seen << 16);
-}
-
-// The record.  resp_mask is n - 2 of the n - 1 replicas that are not the leader: the header names the ONE that is left
-// out (its index among the non-leaders), which with leader, is_set and seen_mask fits beside a 21-bit message index for
-// n <= 5.  Ranks are < m < 2^21: two ranks' words carry a third rank's halves in their upper 11 bits.
-template <int N>
-__device__ __forceinline__ void kp_pack(uint32_t* w, int i, int x, int L, int is_set, unsigned resp, unsigned seen, const int* rk) {
-  const unsigned full = (1u << N) - 1u;
-  const int q = __ffs((int)(full & ~resp & ~(1u << L))) - 1;  // the non-leader whose answer is not waited for
-  const unsigned e = (unsigned)(q - (q > L ? 1 : 0));
-  const unsigned hdr = (unsigned)L | (is_set ? 8u : 0u) | (seen << 4) | (e << (4 + N));
-  auto pair_lo = [](int a, int c) { return (uint32_t)a | (((uint32_t)c & 0x7ffu) << KP_IDX_BITS); };
-  auto pair_hi = [](int a, int c) { return (uint32_t)a | (((uint32_t)c >> 11) << KP_IDX_BITS); };
-  if constexpr (N <= 3) {
-    w[0] = (uint32_t)i | (hdr << KP_IDX_BITS), w[1] = (uint32_t)x;
-    w[2] = pair_lo(rk[0], rk[2]), w[3] = pair_hi(rk[1], rk[2]);
-  } else if constexpr (N <= 5) {
-    w[0] = (uint32_t)i | (hdr << KP_IDX_BITS), w[1] = (uint32_t)x;
-    w[2] = pair_lo(rk[0], rk[4]), w[3] = pair_hi(rk[1], rk[4]), w[4] = (uint32_t)rk[2], w[5] = (uint32_t)rk[3];
-  } else {
-    w[0] = (uint32_t)i, w[1] = (uint32_t)x, w[2] = (uint32_t)kp_flags(L, is_set, resp, seen);
-    w[3] = pair_lo(rk[0], rk[4]), w[4] = pair_hi(rk[1], rk[4]);
-    w[5] = pair_lo(rk[2], rk[5]), w[6] = pair_hi(rk[3], rk[5]), w[7] = (uint32_t)rk[6];
-  }
-}
-
-template <int N>
-__device__ __forceinline__ void kp_unpack(const uint32_t* w, int* i, int* x, int* flags, int* rk) {
-  auto third = [](uint32_t a, uint32_t c) { return (int)((a >> KP_IDX_BITS) | ((c >> KP_IDX_BITS) << 11)); };
-  if constexpr (N <= 5) {
-    *i = (int)(w[0] & KP_IDX_MASK), *x = (int)w[1];
-    const unsigned hdr = w[0] >> KP_IDX_BITS, full = (1u << N) - 1u;
-    const int L = (int)(hdr & 7u);
-    const unsigned seen = (hdr >> 4) & full, e = hdr >> (4 + N);
-    const unsigned q = e + (e >= (unsigned)L ? 1u : 0u);
-    *flags = kp_flags(L, (int)((hdr >> 3) & 1u), full & ~(1u << L) & ~(1u << q), seen);
-    rk[0] = (int)(w[2] & KP_IDX_MASK), rk[1] = (int)(w[3] & KP_IDX_MASK);
-    if constexpr (N <= 3) {
-      rk[2] = third(w[2], w[3]);
-    } else {
-      rk[2] = (int)w[4], rk[3] = (int)w[5], rk[4] = third(w[2], w[3]);
-    }
-  } else {
-    *i = (int)w[0], *x = (int)w[1], *flags = (int)w[2];
-    rk[0] = (int)(w[3] & KP_IDX_MASK), rk[1] = (int)(w[4] & KP_IDX_MASK), rk[4] = third(w[3], w[4]);
-    rk[2] = (int)(w[5] & KP_IDX_MASK), rk[3] = (int)(w[6] & KP_IDX_MASK), rk[5] = third(w[5], w[6]);
-    rk[6] = (int)w[7];
-  }
-}
+#include "fpx_epaxos_rec.hpp"  // KP_IDX_BITS, kp_flags, kp_pack, kp_unpack: the record
 
 struct KpArgs {
   int m, tiles, B;                  // B = num_keys
@@ -448,6 +396,9 @@ __global__ void __launch_bounds__(KpTile<N>::THREADS) k_epx_key2(const EpxState 
   int* rmax = rmin + N;
   int* degenerate = rmax + N;                                                   // a rank bucket is too full: radix sort
   int* base = degenerate + 1;                                                   // [N][2N] the replicas' TopOne vectors of the key
+  uint32_t* tally = reinterpret_cast<uint32_t*>(base + N * 2 * N);              // [EPX_CD_SORTS] this workgroup's keys by sort route, [1] a flag
+                                                                                // (fpx_epx_tick_census; the misc words have room)
+  static_assert((3 * N + 1 + EPX_CD_SORTS + 1) * 4 <= 256, "the tally lies in the 256 bytes of misc words");
   // a tick that is not applied (an error, a key beyond the tables, ranks that are no permutation) still has to leave
   // the claim counters at zero for the next one
   auto give_up = [&]() {
@@ -507,6 +458,7 @@ __global__ void __launch_bounds__(KpTile<N>::THREADS) k_epx_key2(const EpxState 
   Next cur, nxt;
   int k = blockIdx.x;
   if (k >= st.num_keys) return;
+  if (threadIdx.x < EPX_CD_SORTS) tally[threadIdx.x] = 0;  // (only thread 0 adds to it, below)
   fetch(k, cur);
   __syncthreads();
   for (; k < st.num_keys; k += gridDim.x) {
@@ -536,7 +488,7 @@ __global__ void __launch_bounds__(KpTile<N>::THREADS) k_epx_key2(const EpxState 
       }
       for (int j = threadIdx.x; j < N * T::W * 2 * N; j += T::THREADS) tot[j] = 0;
       for (int j = threadIdx.x; j < N * T::NBK; j += T::THREADS) bk[j] = 0;
-      if (threadIdx.x == 0) *degenerate = 0;
+      if (threadIdx.x == 0) *degenerate = 0, tally[EPX_CD_SORTS] = 0;
       if (threadIdx.x < N) rmin[threadIdx.x] = 0x7fffffff, rmax[threadIdx.x] = 0;  // (only a second sorting attempt uses them)
       // the replicas' TopOne vectors of the key (KeyValueStore.scala:229-230), the carries of the scans: requested
       // here, parked in LDS before the scans need them (held in registers across the key they spilled)
@@ -584,7 +536,7 @@ __global__ void __launch_bounds__(KpTile<N>::THREADS) k_epx_key2(const EpxState 
         if (lane == 0 && mn <= mx) atomicMin(&rmin[r], mn), atomicMax(&rmax[r], mx);
         for (int j = threadIdx.x; j < N * T::NBK; j += T::THREADS) bk[j] = 0;
         __syncthreads();
-        if (threadIdx.x == 0) *degenerate = 0;
+        if (threadIdx.x == 0) *degenerate = 0, tally[EPX_CD_SORTS] = 1;
         lo = rmin[r];
         span1 = rmax[r] >= lo ? (unsigned)(rmax[r] - lo) : 0u;
       }
@@ -663,6 +615,8 @@ __global__ void __launch_bounds__(KpTile<N>::THREADS) k_epx_key2(const EpxState 
     }
     // ---- LSD radix sort of the replica's words on the rank bits, in LDS (the words the replica has no part in are
     // all ones: they stay behind the others)
+    // the census: which route sorted this key (tally[EPX_CD_SORTS]: did the second attempt run?)
+    if (threadIdx.x == 0 && c > 0) tally[sort_passes > 0 ? EPX_CD_RADIX1 - 1 + sort_passes : EPX_CD_BUCKET1 + (int)tally[EPX_CD_SORTS]] += 1;
     for (int pass = 0; pass < sort_passes; ++pass) {
       const int shift = KP_SLOT_BITS + pass * KP_RADIX_BITS;
       mycnt[lane] = 0, mycnt[lane + 64] = 0;
@@ -912,6 +866,22 @@ __global__ void __launch_bounds__(KpTile<N>::THREADS) k_epx_key2(const EpxState 
     }
     __syncthreads();  // the tables are reused by the next key
     cur = nxt;
+  }
+  // the census of the sort routes: one atomic per word and workgroup, none per key.  The words lie KP_CENSUS_BACK words in
+  // front of the claim counters, in the same buffer (launch_kp lays it out and holds the static_assert that ties
+  // KP_CENSUS_BACK to that layout; the tally's place in LDS is asserted where `tally` is declared).  Which five threads add,
+  // and that they reach the words through a.tot, has no meaning beyond the register allocator's: the plain tick's
+  // instantiations keep the parent commit's VGPRs and scratch with the LAST five threads, the command-log ones do not
+  // exceed them with the FIRST five (profiles/epaxos_tick_path_tests.md).  tally is final here: only thread 0 wrote it, in
+  // front of the loop's last barrier
+  // (the two branches are written out: one expression for both gave the plain instantiations other instructions)
+  if constexpr (LOG) {
+    if (threadIdx.x < EPX_CD_SORTS && tally[threadIdx.x] != 0)
+      atomicAdd(reinterpret_cast<unsigned long long*>(a.tot - KP_CENSUS_BACK) + threadIdx.x, (unsigned long long)tally[threadIdx.x]);
+  } else {
+    if (threadIdx.x >= T::THREADS - EPX_CD_SORTS && tally[T::THREADS - 1 - threadIdx.x] != 0)
+      atomicAdd(reinterpret_cast<unsigned long long*>(a.tot - KP_CENSUS_BACK) + (T::THREADS - 1 - threadIdx.x),
+                (unsigned long long)tally[T::THREADS - 1 - threadIdx.x]);
   }
 }
 #undef RF

@@ -392,6 +392,28 @@ class EPaxos:
         n = self.n
         return packed[:, 2 * n + 2], packed[:, :n], packed[:, n:2 * n], packed[:, 2 * n:2 * n + 2]
 
+    def limits(self):
+        """the exact-fit limits of the pre-accept tick for this n (include/fpx.h, fpx_epx_limits): {"kp_tc": commands of
+        one key the second form holds on chip, "key_tc": the first form's, "nbk", "kp_max_occ", "kp_maxb", "kp_waves"}"""
+        nw = len(_lib.EPX_LIMIT_WORDS)
+        out = (C.c_int32 * nw)()
+        n = C.c_int32(0)
+        st = self.L.fpx_epx_limits(self._h, nw, out, C.byref(n))
+        if st or n.value != nw:
+            raise FpxError(st, "fpx_epx_limits")
+        return dict(zip(_lib.EPX_LIMIT_WORDS, (int(x) for x in out)))
+
+    def tick_census(self):
+        """diagnostic: the paths the single-key pre-accept ticks took since the context was created (include/fpx.h,
+        fpx_epx_tick_census), as {word name: count}; waits for the context's stream"""
+        nw = len(_lib.EPX_CENSUS_WORDS)
+        out = (C.c_int64 * nw)()
+        n = C.c_int32(0)
+        st = self.L.fpx_epx_tick_census(self._h, nw, out, C.byref(n))
+        if st or n.value != nw:
+            raise FpxError(st, "fpx_epx_tick_census")
+        return dict(zip(_lib.EPX_CENSUS_WORDS, (int(x) for x in out)))
+
     def read_index(self, replica, key):
         g = np.zeros(self.n, np.int32)
         s = np.zeros(self.n, np.int32)

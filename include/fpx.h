@@ -642,6 +642,74 @@ int32_t fpx_epx_create(const fpx_epx_config* cfg, fpx_epx** out);
 int32_t fpx_epx_destroy(fpx_epx* epx);
 /* n, num_keys, num_instances of the context (any pointer may be NULL) */
 int32_t fpx_epx_info(fpx_epx* epx, int32_t* num_replicas, int32_t* num_keys, int32_t* num_instances);
+/* the exact-fit limits of the pre-accept tick for the context's n, so that tests and tools read them and do not restate
+ * them.  Writes min(cap, FPX_EPX_LIMIT_WORDS) int32 words to out and FPX_EPX_LIMIT_WORDS to *n (either may be NULL):
+ *   FPX_EPX_LIMIT_KP_TC       commands of one key the second form (partition by key, k_epx_key2) holds on chip
+ *   FPX_EPX_LIMIT_KEY_TC      commands of one key the first form's per-key kernel (k_epx_key) holds on chip
+ *   FPX_EPX_LIMIT_NBK         rank buckets of the second form's bucket sort
+ *   FPX_EPX_LIMIT_KP_MAX_OCC  words of one replica in the fullest bucket that sort accepts
+ *   FPX_EPX_LIMIT_KP_MAXB     keys the second form takes
+ *   FPX_EPX_LIMIT_KP_WAVES    wavefronts per replica in k_epx_key2 (a key's slots are split among them in runs of 64) */
+enum {
+  FPX_EPX_LIMIT_KP_TC = 0,
+  FPX_EPX_LIMIT_KEY_TC = 1,
+  FPX_EPX_LIMIT_NBK = 2,
+  FPX_EPX_LIMIT_KP_MAX_OCC = 3,
+  FPX_EPX_LIMIT_KP_MAXB = 4,
+  FPX_EPX_LIMIT_KP_WAVES = 5,
+  FPX_EPX_LIMIT_WORDS = 6
+};
+int32_t fpx_epx_limits(fpx_epx* epx, int32_t cap, int32_t* out, int32_t* n);
+/* diagnostic: a census of the paths the single-key pre-accept ticks (fpx_epx_preaccept, _dev, _packed_dev; not the _mk
+ * entry points) took since fpx_epx_create -- the counters cover the life of the context, like those of
+ * fpx_vote_launch_census.  Writes min(cap, FPX_EPX_CENSUS_WORDS) int64 words to out and FPX_EPX_CENSUS_WORDS to *n (either
+ * may be NULL); reading waits for the context's stream and copies two small blocks of device words (64 and 40 bytes), it
+ * launches nothing.
+ * Host words, bumped where the host decides; a tick counts under exactly one of the first seven:
+ *   FPX_EPX_CENSUS_KP               taken by the second form (k_kp_hist, k_kp_scatter, k_epx_key2) and not handed over.  It is
+ *                                   counted when the partition reports that every key fits: a tick k_epx_key2 then refuses
+ *                                   (a bad message, rank rows that are no permutations: FPX_EINVAL, nothing applied)
+ *                                   counts here as well, its keys under no sort route
+ *   FPX_EPX_CENSUS_KP_HANDED_OVER   partitioned by the second form, which found a key with more commands than its
+ *                                   on-chip tables hold: nothing was applied, the first form took the whole tick
+ *   sent to the first form by dispatch, without a partition launch -- the first reason that holds, in this order:
+ *   FPX_EPX_CENSUS_V1_SWITCHED_OFF  FPX_EPX_V1 in the environment at fpx_epx_create (or no page-locked word to be had)
+ *   FPX_EPX_CENSUS_V1_KEYS          num_keys > FPX_EPX_LIMIT_KP_MAXB
+ *   FPX_EPX_CENSUS_V1_FULL          m > num_keys * FPX_EPX_LIMIT_KP_TC: some key must overflow
+ *   FPX_EPX_CENSUS_V1_LOG_N3        n = 3 with a command log (or a triple_id array)
+ *   FPX_EPX_CENSUS_V1_INDEX_BITS    m >= 2^21
+ * and beside them
+ *   FPX_EPX_CENSUS_NO_KEY_KERNEL    first-form ticks that ran k_epx_scan / k_epx_decide without the per-key kernel k_epx_key
+ *   FPX_EPX_CENSUS_SCALAR_LOADS     partition launches (applied or handed over) that read the tick element by element:
+ *                                   an input array off a 16-byte boundary, or m % 4 != 0
+ * Device words, read when the census is read.  Non-empty keys of the second-form ticks that were applied, by the route that put their
+ * sort words in rank order.  k_epx_key2 sorts a key's n replicas side by side and ONE replica's overfull bucket sends all
+ * of them to the next route, so a key counts once, under the route of its worst replica:
+ *   FPX_EPX_CENSUS_SORT_BUCKET1     bucket sort over the tick's ranks [0, m)
+ *   FPX_EPX_CENSUS_SORT_BUCKET2     bucket sort over the key's own rank range, after the first attempt met a bucket of
+ *                                   more than FPX_EPX_LIMIT_KP_MAX_OCC words
+ *   FPX_EPX_CENSUS_SORT_RADIX1 .. 3 LSD radix sort of 1, 2, 3 passes of 7 bits (ceil(bits(m) / 7)), after both attempts did
+ *   FPX_EPX_CENSUS_LONG_WAY         keys the first form's k_epx_key left to k_epx_scan / k_epx_decide (more commands than
+ *                                   FPX_EPX_LIMIT_KEY_TC), summed over the ticks */
+enum {
+  FPX_EPX_CENSUS_KP = 0,
+  FPX_EPX_CENSUS_KP_HANDED_OVER = 1,
+  FPX_EPX_CENSUS_V1_SWITCHED_OFF = 2,
+  FPX_EPX_CENSUS_V1_KEYS = 3,
+  FPX_EPX_CENSUS_V1_FULL = 4,
+  FPX_EPX_CENSUS_V1_LOG_N3 = 5,
+  FPX_EPX_CENSUS_V1_INDEX_BITS = 6,
+  FPX_EPX_CENSUS_NO_KEY_KERNEL = 7,
+  FPX_EPX_CENSUS_SCALAR_LOADS = 8,
+  FPX_EPX_CENSUS_SORT_BUCKET1 = 9,
+  FPX_EPX_CENSUS_SORT_BUCKET2 = 10,
+  FPX_EPX_CENSUS_SORT_RADIX1 = 11,
+  FPX_EPX_CENSUS_SORT_RADIX2 = 12,
+  FPX_EPX_CENSUS_SORT_RADIX3 = 13,
+  FPX_EPX_CENSUS_LONG_WAY = 14,
+  FPX_EPX_CENSUS_WORDS = 15
+};
+int32_t fpx_epx_tick_census(fpx_epx* epx, int32_t cap, int64_t* out, int32_t* n);
 int32_t fpx_epx_set_stream(fpx_epx* epx, void* hip_stream);
 int32_t fpx_epx_preaccept(fpx_epx* epx, int32_t m, const int32_t* leader, const int32_t* number,
                           const int32_t* key, const uint8_t* is_set, const uint8_t* resp_mask,

@@ -90,6 +90,22 @@ def test_range_launch_census_layout_matches_the_binding(fa, tmp_path):
                                                                          C.POINTER(C.c_int32)])
 
 
+def test_epx_tick_census_and_limits_layout_matches_the_binding(fa, tmp_path):
+    """the words of fpx_epx_tick_census and fpx_epx_limits (include/fpx.h) in the order EPaxos.tick_census / limits name them"""
+    census = [x.upper() for x in fa._lib.EPX_CENSUS_WORDS] + ["WORDS"]
+    limits = [x.upper() for x in fa._lib.EPX_LIMIT_WORDS] + ["WORDS"]
+    names = ["FPX_EPX_CENSUS_" + x for x in census] + ["FPX_EPX_LIMIT_" + x for x in limits]
+    src = tmp_path / "e.c"
+    src.write_text('#include <stdio.h>\n#include "fpx.h"\nint main(void){printf("%s\\n", %s); return 0;}\n'
+                   % (" ".join(["%d"] * len(names)), ", ".join(names)))
+    exe = tmp_path / "e"
+    assert os.system("gcc -std=c99 -Wall -Werror -I%s %s -o %s" % (os.path.join(ROOT, "include"), src, exe)) == 0
+    got = list(map(int, os.popen(str(exe)).read().split()))
+    assert got == list(range(len(census))) + list(range(len(limits)))
+    assert fa._lib.SIGNATURES["fpx_epx_tick_census"] == (C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(C.c_int64),
+                                                                     C.POINTER(C.c_int32)])
+
+
 def test_config_struct_layout_matches_the_oracle(fa, oracle):
     a, b = fa.FpxConfig, oracle.Config
     assert [(n, t) for n, t in a._fields_] == [(n, t) for n, t in b._fields_]

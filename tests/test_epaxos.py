@@ -1263,8 +1263,8 @@ def test_epaxos_a_hot_key_goes_the_first_forms_way(oracle, n):
     from frankenpaxos_amd.epaxos import EPaxos
 
     num_keys = 16
-    tc = {3: 1536, 5: 1152, 7: 832}[n]
     gpu, ref = EPaxos(n, num_keys), oracle.EPaxos(n, num_keys)
+    tc = gpu.limits()["kp_tc"]                              # (read, not restated: 832 stood here for n = 7 when it was 640)
     rng = np.random.default_rng(n)
     nxt = [0] * n
     dev = torch.device("cuda:0")
@@ -1290,6 +1290,11 @@ def test_epaxos_a_hot_key_goes_the_first_forms_way(oracle, n):
             np.testing.assert_array_equal(deps, want[2])
             np.testing.assert_array_equal(ldeps, want[3])
             np.testing.assert_array_equal(own, want[4])
+        # the census (include/fpx.h, fpx_epx_tick_census): tick 0 stayed in the second form, ticks 1 and 2 were partitioned
+        # and handed over, tick 3 returned to the second form
+        census = gpu.tick_census()
+        assert (census["kp"], census["kp_handed_over"]) == [(1, 0), (1, 1), (1, 2), (2, 2)][tick], census
+        assert sum(census[w] for w in ("v1_switched_off", "v1_keys", "v1_full", "v1_log_n3", "v1_index_bits")) == 0
     for r in range(n):
         for k in range(num_keys):
             ga, sa = gpu.read_index(r, k)
