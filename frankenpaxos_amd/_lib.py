@@ -177,6 +177,8 @@ SIGNATURES = {
     "fpx_epx_lead": (C.c_int32, [VP, C.c_int32] + [VP] * 10),
     "fpx_epx_leader_replies": (C.c_int32, [VP, C.c_int32] + [VP] * 17),
     "fpx_epx_leader_replies_dev": (C.c_int32, [VP, C.c_int32] + [VP] * 17),
+    "fpx_epx_replica_inbox": (C.c_int32, [VP, C.c_int32] + [VP] * 17),
+    "fpx_epx_replica_inbox_dev": (C.c_int32, [VP, C.c_int32] + [VP] * 17),
     "fpx_epx_read_leader_state": (C.c_int32, [VP, C.c_int32, C.c_int32, C.c_int32, VP, VP]),
     "fpx_replica_chosen": (C.c_int32, [VP, C.c_int32, VP, VP, VP, I32P, I32P]),
     "fpx_replica_chosen_dev": (C.c_int32, [VP, C.c_int32, VP, VP, VP]),

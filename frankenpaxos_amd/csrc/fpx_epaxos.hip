@@ -1380,6 +1380,7 @@ __global__ void __launch_bounds__(256) k_hp_commit(const EpxState st, const HpBa
 
 #include "fpx_epaxos_mk.hpp"
 #include "fpx_epx_leader.hpp"
+#include "fpx_epx_inbox.hpp"
 
 }  // namespace
 
@@ -1406,6 +1407,7 @@ struct fpx_epx {
   uint32_t cl_run = 0;
   EpxLeader ls = {nullptr, nullptr};      // FPX_EPX_F_LEADER_STATE: Replica.leaderStates (fpx_epx_leader.hpp), else not allocated
   DevBuf lr_misc;                         // fpx_epx_leader_replies: the decided flags and the compaction's block counts
+  DevBuf ri_misc;                         // fpx_epx_replica_inbox: lay_epx_inbox
   bool lds_allowed = false, sort_lds_allowed = false;
   int num_cus = 256;
 };
@@ -1988,7 +1990,7 @@ int32_t fpx_epx_destroy(fpx_epx* e) {
   for (void* p : ps)
     if (p) (void)hipFree(p);
   DevBuf* bs[] = {&e->kv, &e->kv2, &e->seg, &e->conf, &e->tmp, &e->tick, &e->fusedb, &e->metab, &e->stage, &e->mk_misc, &e->mk_rec,
-                  &e->mk_pair, &e->mk_pconf, &e->lr_misc};
+                  &e->mk_pair, &e->mk_pconf, &e->lr_misc, &e->ri_misc};
   for (DevBuf* b : bs)
     if (b->p) (void)hipFree(b->p);
   if (e->mk_host) (void)hipHostFree(e->mk_host);
@@ -2907,6 +2909,144 @@ int32_t fpx_epx_leader_replies(fpx_epx* e, int32_t m, const int32_t* kind, const
   if (out_deps) memcpy(out_deps, h_odeps, mn * 4);
   if (decided_index) memcpy(decided_index, h_dec, (size_t)*h_nd * 4);
   if (num_decided) *num_decided = *h_nd;
+  return rc;
+}
+
+// ---- the replica half, a burst at a time: csrc/fpx_epx_inbox.hpp -------------------------------------------------------------
+static int32_t replica_inbox_launch(fpx_epx* e, int32_t m, const int32_t* d_kind, const int32_t* d_to, const int32_t* d_leader,
+                                    const int32_t* d_number, const int32_t* d_bo, const int32_t* d_br, const int32_t* d_key,
+                                    const uint8_t* d_set, const int32_t* d_tr, const int32_t* d_deps, const int32_t* d_dend,
+                                    int32_t* d_outcome, int32_t* d_oballot, int32_t* d_ostatus, int32_t* d_odeps, int32_t* d_oend,
+                                    int32_t* d_otriple) {
+  const int n = e->st.n, NP = n <= 4 ? 4 : 8;
+  const int tiles = (m + CL_TILE - 1) / CL_TILE;
+  const size_t mn = (size_t)m * n;
+  int rc;
+  if ((rc = grow(e, &e->kv, mn * 8))) return rc;
+  if ((rc = grow(e, &e->kv2, mn * 8))) return rc;
+  if ((rc = grow(e, &e->tick, (size_t)n * e->st.num_keys * 2 * n * 4))) return rc;
+  if ((rc = grow(e, &e->seg, (size_t)n * e->st.num_keys * 8))) return rc;
+  if ((rc = grow(e, &e->conf, mn * NP * 4))) return rc;
+  EpxInboxScratch s;
+  if ((rc = carve(e, &e->ri_misc, &s, [&](Carver& c) { return lay_epx_inbox(c, m, n, tiles); }))) return rc;
+  RiBatch b;
+  memset(&b, 0, sizeof(b));
+  b.m = m, b.kind = d_kind, b.to = d_to, b.leader = d_leader, b.number = d_number, b.b_ord = d_bo, b.b_rep = d_br, b.key = d_key;
+  b.is_set = d_set, b.triple = d_tr, b.deps = d_deps, b.dend = d_dend, b.outcome = d_outcome, b.out_ballot = d_oballot;
+  b.out_status = d_ostatus, b.out_deps = d_odeps, b.out_end = d_oend, b.out_triple = d_otriple;
+  b.ckv = (uint2*)s.cell[0], b.kv = (uint2*)e->kv.p, b.contrib = s.contrib, b.nackflag = s.nackflag, b.src = s.src, b.last = s.last;
+  b.conf = (int32_t*)e->conf.p;
+  const dim3 gm((m + 255) / 256), blk(256);
+  hipLaunchKernelGGL(k_ri_validate, gm, blk, 0, e->stream, e->st, b);
+  unsigned bits = 1;  // the cells of the context: (to, leader, number)
+  while (((uint64_t)1 << bits) < (uint64_t)n * n * e->st.num_instances) ++bits;
+  {
+    // both sorts of the call count their digits in e->tmp: it has its final size before the first one is enqueued
+    unsigned kbits = 1;
+    while ((1u << kbits) <= (unsigned)e->st.num_keys) ++kbits;
+    auto hist_bytes = [&](size_t nseq, unsigned sort_bits) {
+      const unsigned passes = (sort_bits + RS_MAXW - 1) / RS_MAXW, width = (sort_bits + passes - 1) / passes;
+      return (nseq * ((m + RS_TILE - 1) / RS_TILE) + nseq) * ((size_t)4 << width);
+    };
+    if ((rc = grow(e, &e->tmp, std::max(hist_bytes(1, bits), hist_bytes(n, kbits))))) return rc;
+  }
+  b.sorted = radix_sort_pairs(e, 1, m, bits, b.ckv, (uint2*)s.cell[1], nullptr, &rc, nullptr, nullptr);
+  if (rc) return rc;
+  by_n(n, [&](auto N) { hipLaunchKernelGGL((k_ri_walk<N>), gm, blk, 0, e->stream, e->st, b); });
+  // the conflict scan of what each replica looks up and puts, in array order: K7's sort / segments / scan
+  EpxBatch sb;
+  memset(&sb, 0, sizeof(sb));
+  sb.m = m, sb.number = d_number, sb.kv = b.kv;
+  const uint32_t* key_totals = nullptr;
+  int key_buckets = 0;
+  sb.kv_sorted = sort_by_key(e, m, b.kv, (uint2*)e->kv2.p, nullptr, &rc, &key_totals, &key_buckets);
+  if (rc) return rc;
+  sb.tick = (int32_t*)e->tick.p, sb.seg = (int32_t*)e->seg.p, sb.conf = (int32_t*)e->conf.p;
+  launch_segments(e, sb, key_totals, key_buckets);
+  // the largestBallot every Nack carries: prefix max per replica over the ballots it took in (as for Prepare / Accept)
+  ClBatch cb;
+  memset(&cb, 0, sizeof(cb));
+  cb.m = m, cb.contrib = s.contrib, cb.nackflag = s.nackflag, cb.tilemax = s.tilemax, cb.nack_ballot = d_oballot;
+  hipLaunchKernelGGL(k_cl_tilemax, dim3(tiles, n), blk, 0, e->stream, cb, tiles);
+  hipLaunchKernelGGL(k_cl_tilescan, dim3(n), blk, 0, e->stream, e->st, cb, tiles);
+  hipLaunchKernelGGL(k_cl_nacks, dim3(tiles, n), blk, 0, e->stream, cb, tiles);
+  HpBatch hb;
+  memset(&hb, 0, sizeof(hb));
+  hb.tick = sb.tick;
+  const long long tot = (long long)e->st.num_keys * n * n;
+  by_n(n, [&](auto N) {
+    hipLaunchKernelGGL((k_epx_scan<N>), dim3((N * e->st.num_keys + 3) / 4), blk, 0, e->stream, e->st, sb);
+    // the replies read the dependencies the entries held before the burst; only then are the entries' overwritten
+    hipLaunchKernelGGL((k_ri_reply<N>), gm, blk, 0, e->stream, e->st, b);
+    hipLaunchKernelGGL((k_ri_store<N>), gm, blk, 0, e->stream, e->st, b);
+  });
+  hipLaunchKernelGGL(k_hp_commit, dim3((unsigned)((tot + 255) / 256)), blk, 0, e->stream, e->st, hb);
+  return FPX_OK;
+}
+
+static int32_t replica_inbox_check(const fpx_epx* e, int32_t m) {
+  if (!e || m < 0 || m > FPX_EPX_INBOX_MAX || e->st.num_instances <= 0) return FPX_EINVAL;
+  if ((uint64_t)e->st.n * e->st.n * e->st.num_instances >= ((uint64_t)1 << 32)) return FPX_EINVAL;  // a cell is 32 bits of the sort
+  return FPX_OK;
+}
+
+int32_t fpx_epx_replica_inbox_dev(fpx_epx* e, int32_t m, const int32_t* d_kind, const int32_t* d_to, const int32_t* d_leader,
+                                  const int32_t* d_number, const int32_t* d_ballot_ordering, const int32_t* d_ballot_replica,
+                                  const int32_t* d_key, const uint8_t* d_is_set, const int32_t* d_triple_id,
+                                  const int32_t* d_deps, const int32_t* d_deps_values_end, int32_t* d_outcome,
+                                  int32_t* d_out_ballot, int32_t* d_out_status, int32_t* d_out_deps, int32_t* d_out_values_end,
+                                  int32_t* d_out_triple) {
+  if (replica_inbox_check(e, m)) return FPX_EINVAL;
+  DeviceScope _dg(e->cfg.device);
+  if (m == 0) return FPX_OK;
+  if (!d_kind || !d_to || !d_leader || !d_number || !d_ballot_ordering || !d_ballot_replica || !d_key || !d_is_set || !d_triple_id ||
+      !d_deps)
+    return FPX_EINVAL;
+  int rc = replica_inbox_launch(e, m, d_kind, d_to, d_leader, d_number, d_ballot_ordering, d_ballot_replica, d_key, d_is_set,
+                                d_triple_id, d_deps, d_deps_values_end, d_outcome, d_out_ballot, d_out_status, d_out_deps,
+                                d_out_values_end, d_out_triple);
+  return rc ? rc : launch_check(e);
+}
+
+int32_t fpx_epx_replica_inbox(fpx_epx* e, int32_t m, const int32_t* kind, const int32_t* to, const int32_t* leader,
+                              const int32_t* number, const int32_t* ballot_ordering, const int32_t* ballot_replica,
+                              const int32_t* key, const uint8_t* is_set, const int32_t* triple_id, const int32_t* deps,
+                              const int32_t* deps_values_end, int32_t* outcome, int32_t* out_ballot, int32_t* out_status,
+                              int32_t* out_deps, int32_t* out_values_end, int32_t* out_triple) {
+  if (replica_inbox_check(e, m)) return FPX_EINVAL;
+  DeviceScope _dg(e->cfg.device);
+  if (m == 0) return FPX_OK;
+  if (!kind || !to || !leader || !number || !ballot_ordering || !ballot_replica || !key || !is_set || !triple_id || !deps)
+    return FPX_EINVAL;
+  const size_t mn = (size_t)m * e->st.n;
+  const int32_t *d_kind, *d_to, *d_leader, *d_number, *d_bo, *d_br, *d_key, *d_tr, *d_deps, *d_dend;
+  const uint8_t* d_set;
+  int32_t *d_outcome, *d_ob, *d_os, *d_odeps, *d_oend, *d_otr;
+  auto launch = [&]() -> int {
+    return replica_inbox_launch(e, m, d_kind, d_to, d_leader, d_number, d_bo, d_br, d_key, d_set, d_tr, d_deps,
+                                deps_values_end ? d_dend : nullptr, d_outcome, d_ob, d_os, d_odeps, d_oend, d_otr);
+  };
+  // an output is downloaded only on FPX_OK: FPX_EINVAL leaves the caller's arrays as they were
+  std::vector<int32_t> tmp;
+  try {
+    tmp.resize(5 * (size_t)m + mn);
+  } catch (const std::bad_alloc&) {  // (no exception crosses the C ABI)
+    return FPX_ENOMEM;
+  }
+  int32_t *h_outcome = tmp.data(), *h_ob = h_outcome + m, *h_os = h_ob + m, *h_oend = h_os + m, *h_otr = h_oend + m, *h_odeps = h_otr + m;
+  const int rc = host_call(e, {in(d_kind, kind, m), in(d_to, to, m), in(d_leader, leader, m), in(d_number, number, m),
+                               in(d_bo, ballot_ordering, m), in(d_br, ballot_replica, m), in(d_key, key, m), in(d_tr, triple_id, m),
+                               in(d_dend, deps_values_end, m), in(d_deps, deps, mn), in(d_set, is_set, m),
+                               out(d_outcome, h_outcome, m), out(d_ob, h_ob, m), out(d_os, h_os, m), out(d_oend, h_oend, m),
+                               out(d_otr, h_otr, m), out(d_odeps, h_odeps, mn)},
+                           launch);
+  if (rc != FPX_OK) return rc;
+  if (outcome) memcpy(outcome, h_outcome, (size_t)m * 4);
+  if (out_ballot) memcpy(out_ballot, h_ob, (size_t)m * 4);
+  if (out_status) memcpy(out_status, h_os, (size_t)m * 4);
+  if (out_values_end) memcpy(out_values_end, h_oend, (size_t)m * 4);
+  if (out_triple) memcpy(out_triple, h_otr, (size_t)m * 4);
+  if (out_deps) memcpy(out_deps, h_odeps, mn * 4);
   return rc;
 }
 

@@ -154,4 +154,24 @@ inline LrScratch lay_leader_replies(Carver& c, size_t m, size_t blocks) {
   return s;
 }
 
+// fpx_epx_inbox.hpp, a burst of m peer messages at n replicas: the (cell, message index) pairs of the cell sort and its
+// other buffer (2 words a pair), per message where a reply's dependencies come from, per sorted position the run's last
+// writer of the dependencies, and the n x m tables of the largestBallot scan (k_cl_tilemax / k_cl_tilescan / k_cl_nacks)
+// with their `tiles` tile maxima per replica.  (Under the sanitizers: tests/epx_inbox_scratch_main.cpp.)
+struct EpxInboxScratch {
+  uint32_t* cell[2];
+  int32_t *src, *last, *contrib, *tilemax;
+  uint8_t* nackflag;
+};
+inline EpxInboxScratch lay_epx_inbox(Carver& c, size_t m, size_t n, size_t tiles) {
+  EpxInboxScratch s;
+  for (int j = 0; j < 2; ++j) s.cell[j] = c.take<uint32_t>(2 * m);
+  s.src = c.take<int32_t>(m);
+  s.last = c.take<int32_t>(m);
+  s.contrib = c.take<int32_t>(n * m);
+  s.tilemax = c.take<int32_t>(n * tiles);
+  s.nackflag = c.take<uint8_t>(n * m);
+  return s;
+}
+
 }  // namespace fpx

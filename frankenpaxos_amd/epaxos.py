@@ -14,6 +14,11 @@ FPX_EPX_F_LEADER_STATE = 1
 PRE_ACCEPT_OK, ACCEPT_OK, NACK, SLOW_PATH_TIMER = 0, 1, 2, 3
 (IGNORED, WAITING, START_SLOW_PATH_TIMER, FAST_COMMIT, ACCEPT, SLOW_COMMIT, NACK_RECOVER, NACK_IGNORED,
  FATAL) = range(9)
+# fpx_epx_replica_inbox: message kinds and per-message outcomes (include/fpx.h)
+IN_PRE_ACCEPT, IN_ACCEPT, IN_COMMIT, IN_PREPARE = 0, 1, 2, 3
+(RI_IGNORED, RI_PRE_ACCEPT_OK, RI_PRE_ACCEPT_OK_AGAIN, RI_ACCEPT_OK, RI_ACCEPT_OK_AGAIN, RI_LEARNT, RI_PREPARE_OK, RI_NACK,
+ RI_COMMIT_BACK) = range(9)
+INBOX_MAX = 1 << 24
 
 
 class FpxEpxConfig(C.Structure):
@@ -309,6 +314,38 @@ class EPaxos:
                                                d(out_triple), d(decided_index), d(num_decided))
         if st:
             raise FpxError(st, "fpx_epx_leader_replies_dev")
+
+    # ---- the replica half, a burst at a time ----
+    def replica_inbox(self, kind, to, leader, number, ballot_ordering, ballot_replica, key, is_set, triple_id, deps,
+                      deps_values_end=None):
+        """one burst of PreAccept (0) / Accept (1) / Commit (2) / Prepare (3) messages from peer replicas in delivery order,
+        message i to replica to[i]: (status, outcome[m], out_ballot[m], out_status[m], out_deps[m, n], out_values_end[m],
+        out_triple[m]); on a status other than 0 the outputs keep their fill of -9"""
+        a32 = lambda x: np.ascontiguousarray(x, dtype=np.int32)
+        kind, to, leader, number = a32(kind), a32(to), a32(leader), a32(number)
+        bo, br, key, tr = a32(ballot_ordering), a32(ballot_replica), a32(key), a32(triple_id)
+        is_set = np.ascontiguousarray(is_set, dtype=np.uint8)
+        m = len(kind)
+        deps = a32(deps).reshape(m, self.n)
+        dend = None if deps_values_end is None else a32(deps_values_end)
+        outcome, ob, os_, oend, otr = (np.full(m, -9, np.int32) for _ in range(5))
+        odeps = np.full((m, self.n), -9, np.int32)
+        p = lambda a: None if a is None else a.ctypes.data
+        st = self.L.fpx_epx_replica_inbox(self._h, m, p(kind), p(to), p(leader), p(number), p(bo), p(br), p(key), p(is_set),
+                                          p(tr), p(deps), p(dend), p(outcome), p(ob), p(os_), p(odeps), p(oend), p(otr))
+        return st, outcome, ob, os_, odeps, oend, otr
+
+    def replica_inbox_dev(self, kind, to, leader, number, ballot_ordering, ballot_replica, key, is_set, triple_id, deps,
+                          deps_values_end=None, outcome=None, out_ballot=None, out_status=None, out_deps=None,
+                          out_values_end=None, out_triple=None):
+        """the same on device tensors (int32; is_set uint8), enqueued on the context's stream; the status comes with sync()"""
+        d = lambda t: None if t is None else t.data_ptr()
+        st = self.L.fpx_epx_replica_inbox_dev(self._h, kind.numel(), d(kind), d(to), d(leader), d(number), d(ballot_ordering),
+                                              d(ballot_replica), d(key), d(is_set), d(triple_id), d(deps), d(deps_values_end),
+                                              d(outcome), d(out_ballot), d(out_status), d(out_deps), d(out_values_end),
+                                              d(out_triple))
+        if st:
+            raise FpxError(st, "fpx_epx_replica_inbox_dev")
 
     def read_leader_state(self, replica, leader, number):
         """(phase [0 when not live], ballot, avoid_fast_path, triple id, key, is_set, response mask, stored phase),

@@ -24,6 +24,12 @@
 //                      commands and Noops (no multi-key lead), no Preparing phase, recovery is answered but not originated
 //                      (a Nack that asks for it, outcome 6, is logged).
 //
+//                      inboxBurst = true (off by default): what replicas OUTSIDE send this one -- PreAccept, Accept, Prepare,
+//                      Commit -- is enqueued as it arrives and a tick flushes it through ONE Native.epxReplicaInbox call, in
+//                      arrival order: a leader's PreAccept that lands twice in one burst is answered twice, and an Accept is
+//                      handleAccept at this replica alone (no proposer step on the hosted context, no commit on one AcceptOk).
+//                      Limits: single-key commands and Noops.
+//
 // The same natives driven on wire bytes -- two conflicting commands met in different orders, differing PreAcceptOks, the
 // slow path, Accept, AcceptOk, Commit -- against the oracle: tests/test_jni_shim.py::test_an_epaxos_slow_path_commit_...
 //
@@ -120,6 +126,10 @@ class GpuEPaxosReplica[Transport <: frankenpaxos.Transport[Transport]](
     // true: the other replicas live in other processes; this actor leads its instances through Native.epxLead /
     // Native.epxLeaderReplies (the engine needs leaderState = true).  Default off: all n replicas in this process.
     remotePeers: Boolean = false,
+    // true: what replicas outside send this one -- PreAccept, Accept, Prepare, Commit -- goes through ONE
+    // Native.epxReplicaInbox call per flush, in arrival order, instances repeated freely (single-key commands and Noops).
+    // Default off: one native call per kind of message, as below.
+    inboxBurst: Boolean = false,
     thrifty: Boolean = true,             // PreAccept / Accept to a thrifty quorum (else to every other replica)
     resendPeriod: java.time.Duration = java.time.Duration.ofSeconds(1),              // resendPreAccepts / resendAccepts
     defaultToSlowPathPeriod: java.time.Duration = java.time.Duration.ofSeconds(1)
@@ -249,7 +259,7 @@ class GpuEPaxosReplica[Transport <: frankenpaxos.Transport[Transport]](
   private val prepares = mutable.Buffer[(Transport#Address, Prepare)]()
   private val commits = mutable.Buffer[Commit]()
   private var queued = 0
-  private val tick = timer("gpuEPaxosTick", java.time.Duration.ZERO, () => flushTick())
+  private val tick = timer("gpuEPaxosTick", java.time.Duration.ZERO, () => { if (inboxBurst) flushPeerInbox(); flushTick() })
   private def enqueue[T](q: mutable.Buffer[T], x: T): Unit = { if (queued == 0) tick.start(); q += x; queued += 1 }
 
   override def receive(src: Transport#Address, inbound: ReplicaInbound): Unit = {
@@ -266,6 +276,10 @@ class GpuEPaxosReplica[Transport <: frankenpaxos.Transport[Transport]](
               ClientInbound().withClientReply(ClientReply(clientPseudonym = r.command.clientPseudonym,
                                                           clientId = r.command.clientId, result = ByteString.copyFrom(output))))
         }
+      case Request.PreAccept(r) if inboxBurst => enqueue(peerInbox, PeerEvent(0, src, r.instance, r.ballot, Some(r.commandOrNoop), Some(r.dependencies)))
+      case Request.Accept(r) if inboxBurst => enqueue(peerInbox, PeerEvent(1, src, r.instance, r.ballot, Some(r.commandOrNoop), Some(r.dependencies)))
+      case Request.Commit(r) if inboxBurst => enqueue(peerInbox, PeerEvent(2, src, r.instance, Ballot(0, 0), Some(r.commandOrNoop), Some(r.dependencies)))
+      case Request.Prepare(r) if inboxBurst => enqueue(peerInbox, PeerEvent(3, src, r.instance, r.ballot, None, None))
       case Request.PreAccept(r)     => enqueue(preAccepts, (src, r))
       case Request.Accept(r)        => enqueue(accepts, (src, r))
       case Request.Prepare(r)       => enqueue(prepares, (src, r))
@@ -394,6 +408,75 @@ class GpuEPaxosReplica[Transport <: frankenpaxos.Transport[Transport]](
       }
     }
     if (decided(0) > 0) executeGraph()
+  }
+
+  // ---- inboxBurst: the replica half.  What replicas outside sent since the last flush -- PreAccepts, Accepts, Commits,
+  // Prepares, in arrival order -- goes through ONE device call (fpx_epx_replica_inbox), which answers every message as
+  // handlePreAccept / handleAccept / handleCommit / handlePrepare would one at a time; then what the handlers would have sent.
+  private case class PeerEvent(kind: Int, src: Transport#Address, instance: Instance, ballot: Ballot,
+                               commandOrNoop: Option[CommandOrNoop], dependencies: Option[InstancePrefixSetProto])
+  private val peerInbox = mutable.Buffer[PeerEvent]()
+  // the own-leader column as the device's command log holds it: (watermark <= number, explicit ids number + 1 .. end - 1)
+  private def deviceShape(instance: Instance, deps: InstancePrefixSetProto): Boolean = {
+    val own = deps.intPrefixSet(instance.replicaIndex)
+    val x = instance.instanceNumber
+    own.value.isEmpty || (own.watermark <= x && own.value.sorted == (x + 1 to own.value.max))
+  }
+  private def flushPeerInbox(): Unit = {
+    if (peerInbox.isEmpty) return
+    val k = peerInbox.size
+    val ev = peerInbox.toArray
+    peerInbox.clear()
+    if (remotePeers) for (e <- ev) if (e.kind == 2) stopLeading(e.instance) else yieldTo(e.instance, e.ballot)
+    val key = new Array[Int](k); val isSet = new Array[Byte](k); val tripleId = Array.fill(k)(-1)
+    val deps = new Array[Int](k * n); val ends = new Array[Int](k)
+    for ((e, i) <- ev.zipWithIndex; c <- e.commandOrNoop; d <- e.dependencies) {
+      val (ks, set) = engine.classify(c)
+      if (ks.exists(_.length != 1)) logger.fatal("GpuEPaxosReplica(inboxBurst): single-key commands and Noops only.")
+      key(i) = ks.map(_(0)).getOrElse(-1); isSet(i) = if (set) 1 else 0
+      tripleId(i) = engine.triples.size; engine.triples += c
+      val (w, end) = (watermarks(d), ownEnd(e.instance, d))
+      // an Accept's or a Commit's dependencies that the command log does not represent stay here; the device names the
+      // triple by its id alone (a row starting with -1).  A PreAccept's are checked by the device (FPX_EINVAL).
+      if (e.kind == 0 || deviceShape(e.instance, d)) { Array.copy(w, 0, deps, i * n, n); ends(i) = end } else deps(i * n) = -1
+      if (e.kind == 1) engine.tripleDeps(tripleId(i)) = (w, end)
+    }
+    val outcome = new Array[Int](k); val reply = new Array[Int](4 * k); val outDeps = new Array[Int](k * n)
+    Native.check(Native.epxReplicaInbox(engine.handle, k, n, ev.map(_.kind), Array.fill(k)(index), ev.map(_.instance.replicaIndex),
+                                        ev.map(_.instance.instanceNumber), ev.map(_.ballot.ordering), ev.map(_.ballot.replicaIndex),
+                                        key, isSet, tripleId, deps, ends, outcome, reply, outDeps), logger)
+    var learnt = false
+    for ((e, i) <- ev.zipWithIndex) {
+      val back = chan[Replica[Transport]](e.src, Replica.serializer)
+      val (l, x) = (e.instance.replicaIndex, e.instance.instanceNumber)
+      val ballot = reply(i); val triple = reply(3 * k + i)
+      // the reply's dependencies: from the command log, or -- a triple the device knows by its id -- from the engine
+      def sent: Option[InstancePrefixSetProto] =
+        (if (outDeps(i * n) >= 0) Some((outDeps.slice(i * n, (i + 1) * n), reply(2 * k + i)))
+         else engine.tripleDeps.get(triple).orElse(engine.depsOf.get((l, x)))).map { case (w, end) => prefixSet(w, l, end, x) }
+      outcome(i) match {
+        case 1 | 2 => back.send(ReplicaInbound().withPreAcceptOk(PreAcceptOk(e.instance, e.ballot, index, 0, sent.get)))   // :1196-1210, 1281-1288
+        case 3 | 4 => back.send(ReplicaInbound().withAcceptOk(AcceptOk(e.instance, e.ballot, index)))                    // :1451-1461, 1505-1511
+        case 5 =>                                                                                                       // :1567-1575
+          val d = e.dependencies.get
+          engine.depsOf((l, x)) = (watermarks(d), ownEnd(e.instance, d))
+          learnCommit(e.instance, e.commandOrNoop.get, d); learnt = true
+        case 6 =>                                                                                                       // :1654-1743
+          val status = reply(k + i)
+          val seen = status != 0 && triple >= 0
+          back.send(ReplicaInbound().withPrepareOk(PrepareOk(
+            ballot = e.ballot, instance = e.instance, replicaIndex = index,
+            voteBallot = if (ballot < 0) Replica.nullBallot else Ballot(ballot >> 3, ballot & 7),
+            status = status match { case 0 | 1 => CommandStatus.NotSeen; case 2 => CommandStatus.PreAccepted; case _ => CommandStatus.Accepted },
+            commandOrNoop = if (seen) Some(engine.triples(triple)) else None,
+            sequenceNumber = if (seen) Some(0) else None,
+            dependencies = if (seen) sent else None)))
+        case 7 => back.send(ReplicaInbound().withNack(Nack(e.instance, Ballot(ballot >> 3, ballot & 7))))
+        case 8 => sent.foreach(d => back.send(ReplicaInbound().withCommit(Commit(e.instance, engine.triples(triple), 0, d))))
+        case _ => ()                                                                                                    // :1222-1224
+      }
+    }
+    if (learnt) executeGraph()
   }
 
   private def flushTick(): Unit = {

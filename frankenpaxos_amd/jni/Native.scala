@@ -214,6 +214,16 @@ object Native {
                                replicaIndex: Array[Int], sequenceNumber: Array[Int], deps: Array[Int],
                                depsValuesEnd: Array[Int], outcome: Array[Int], triple: Array[Int], outDeps: Array[Int],
                                decided: Array[Int]): Int
+  // one burst of PreAccept (kind 0) / Accept (1) / Commit (2) / Prepare (3) messages from peer replicas, message i to replica
+  // to(i), in delivery order, instances repeated freely (handlePreAccept :1159-1289, handleAccept :1421-1511, handleCommit
+  // :1567-1575, handlePrepare :1632-1757).  deps (m x n): a row starting with -1 on an Accept / a Commit = the triple is known
+  // by its id alone.  outcome (m): 0 ignored, 1 PreAcceptOk, 2 PreAcceptOk again, 3 AcceptOk, 4 AcceptOk again, 5 learnt, 6
+  // PrepareOk, 7 Nack, 8 the Commit goes back; reply = ballot (a Nack's largestBallot, a PrepareOk's voteBallot) | PrepareOk
+  // status | values end | triple id (4 x m) and outDeps (m x n): the triple of the PreAcceptOk / Commit / PrepareOk to send
+  @native def epxReplicaInbox(handle: Long, m: Int, numReplicas: Int, kind: Array[Int], to: Array[Int], leader: Array[Int],
+                              number: Array[Int], ballotOrdering: Array[Int], ballotReplica: Array[Int], key: Array[Int],
+                              isSet: Array[Byte], tripleId: Array[Int], deps: Array[Int], depsValuesEnd: Array[Int],
+                              outcome: Array[Int], reply: Array[Int], outDeps: Array[Int]): Int
   // the multi-key forms of epxPreaccept / epxAccept / epxHandleCommit / epxHandlePreaccept: command i's keys are
   // keys(keyOffsets(i) until keyOffsets(i + 1)) (keyOffsets: m + 1 entries from 0), everything else as above
   @native def epxPreacceptMk(handle: Long, m: Int, numReplicas: Int, leader: Array[Int],

@@ -817,6 +817,40 @@ JNIEXPORT jint JNICALL Java_frankenpaxos_gpu_Native_epxLeaderReplies(
   return st;
 }
 
+/* one burst of PreAccept (0) / Accept (1) / Commit (2) / Prepare (3) messages from peer replicas, message i to replica to[i],
+ * in delivery order (fpx_epx_replica_inbox).  deps m x n (row starting with -1 on an Accept / a Commit: the triple is known by
+ * its id alone), depsValuesEnd m or null.  Out (each may be null): outcome m; reply = outBallot | outStatus | outValuesEnd |
+ * outTriple (4 x m); outDeps m x n */
+JNIEXPORT jint JNICALL Java_frankenpaxos_gpu_Native_epxReplicaInbox(
+    JNIEnv* env, jclass cls, jlong h, jint m, jint numReplicas, jintArray kind, jintArray to, jintArray leader, jintArray number,
+    jintArray ballotOrdering, jintArray ballotReplica, jintArray key, jbyteArray isSet, jintArray tripleId, jintArray deps,
+    jintArray depsValuesEnd, jintArray outcome, jintArray reply, jintArray outDeps) {
+  if (m < 0 || numReplicas < 3 || !epx_n_is(h, numReplicas)) return FPX_EINVAL;
+  if (m == 0) return FPX_OK;
+  const jlong mn = (jlong)m * numReplicas;
+  if (!has(env, kind, m) || !has(env, to, m) || !has(env, leader, m) || !has(env, number, m) || !has(env, ballotOrdering, m) ||
+      !has(env, ballotReplica, m) || !has(env, key, m) || !has(env, isSet, m) || !has(env, tripleId, m) || !has(env, deps, mn) ||
+      !opt(env, depsValuesEnd, m) || !opt(env, outcome, m) || !opt(env, reply, 4 * (jlong)m) || !opt(env, outDeps, mn))
+    return FPX_EINVAL;
+  jint *kd = in_ints(env, kind, m), *t = in_ints(env, to, m), *l = in_ints(env, leader, m), *nu = in_ints(env, number, m),
+       *bo = in_ints(env, ballotOrdering, m), *br = in_ints(env, ballotReplica, m), *k = in_ints(env, key, m),
+       *tr = in_ints(env, tripleId, m), *d = in_ints(env, deps, mn);
+  jbyte* is = in_bytes(env, isSet, m);
+  jint* de = depsValuesEnd ? in_ints(env, depsValuesEnd, m) : NULL;
+  jint *oc = out_buf(outcome, m, 4), *rp = out_buf(reply, 4 * (jlong)m, 4), *od = out_buf(outDeps, mn, 4);
+  int32_t st = (!kd || !t || !l || !nu || !bo || !br || !k || !tr || !d || !is || (depsValuesEnd && !de) || (outcome && !oc) ||
+                (reply && !rp) || (outDeps && !od))
+                   ? FPX_ENOMEM
+                   : fpx_epx_replica_inbox((fpx_epx*)(intptr_t)h, m, kd, t, l, nu, bo, br, k, (const uint8_t*)is, tr, d, de, oc, rp,
+                                           rp ? rp + m : NULL, od, rp ? rp + 2 * (size_t)m : NULL, rp ? rp + 3 * (size_t)m : NULL);
+  if (st == FPX_OK) {
+    put_ints(env, outcome, m, oc); put_ints(env, reply, 4 * (jlong)m, rp); put_ints(env, outDeps, mn, od);
+  }
+  free(kd); free(t); free(l); free(nu); free(bo); free(br); free(k); free(tr); free(d); free(is); free(de); free(oc); free(rp);
+  free(od);
+  return st;
+}
+
 /* ---- multi-key get / set commands (the _mk entry points): keyOffsets m + 1, keys keyOffsets[m] (fpx.h) -------------- */
 /* copies the key lists: 0 = a list the library may look at (it checks the rest), else FPX_EINVAL / FPX_ENOMEM */
 static int32_t in_key_lists(JNIEnv* env, jint m, jintArray keyOffsets, jintArray keys, jint** off, jint** k) {

@@ -1051,6 +1051,82 @@ int32_t fpx_epx_leader_replies_dev(fpx_epx* epx, int32_t m, const int32_t* d_kin
                                    const int32_t* d_sequence_number, const int32_t* d_deps, const int32_t* d_deps_values_end,
                                    int32_t* d_outcome, int32_t* d_out_seq, int32_t* d_out_deps, int32_t* d_out_values_end,
                                    int32_t* d_out_triple, int32_t* d_decided_index, int32_t* d_num_decided);
+/* ---- the replica half of an instance, a burst at a time --------------------------------------------------------------
+ * fpx_epx_replica_inbox: ONE burst of what peer replicas send hosted replicas -- PreAccept, Accept, Commit, Prepare -- in
+ * delivery order, the kinds interleaved, instances and keys repeated freely, answered exactly as Replica.handlePreAccept /
+ * handleAccept / handleCommit / handlePrepare would answer them one message at a time.  Needs num_instances > 0; does NOT
+ * need FPX_EPX_F_LEADER_STATE.  Message i goes to the ONE replica to[i]: kind[i], the instance (leader[i], number[i]), the
+ * message's ballot (ballot_ordering[i], ballot_replica[i]), the command key[i] / is_set[i] (key -1 = Noop; single-key
+ * commands and Noops only), the CommandTriple's id triple_id[i], its dependencies deps[i * n ..] (n watermarks) and
+ * deps_values_end[i] (the array may be NULL = zeros), shaped as fpx_epx_handle_preaccept's deps_in and
+ * fpx_epx_handle_commit's deps.  For an Accept or a Commit deps[i * n] = -1 says "the triple is known by its id alone"
+ * (what fpx_epx_read_cmdlog_deps reports for such an entry); the rest of that row is not read.
+ *   kind FPX_EPX_IN_PRE_ACCEPT (:1159-1289), as fpx_epx_handle_preaccept at one replica:
+ *          a CommittedEntry                                  FPX_EPX_RI_COMMIT_BACK, the Commit goes back (:1227-1238)
+ *          an entry with ballot > the message's             FPX_EPX_RI_NACK (:1180-1184, 1189-1192, 1215-1218)
+ *          PreAcceptedEntry voted in the message's ballot    FPX_EPX_RI_PRE_ACCEPT_OK_AGAIN, from the stored triple (:1196-1210)
+ *          AcceptedEntry voted in the message's ballot       FPX_EPX_RI_IGNORED (:1222-1224)
+ *          else                                              FPX_EPX_RI_PRE_ACCEPT_OK: largestBallot is raised (:1251), the
+ *                 dependencies are the command's conflicts in to[i]'s index, minus the instance, united with the message's
+ *                 (:1255-1262), PreAcceptedEntry(ballot, ballot, triple) (:1265-1276), updateConflictIndex (:1279)
+ *   kind FPX_EPX_IN_ACCEPT (:1421-1511) -- handleAccept alone: no proposer step, no commit (fpx_epx_accept is the whole phase):
+ *          a CommittedEntry                                  FPX_EPX_RI_COMMIT_BACK (:1463-1474)
+ *          an entry with ballot > the message's             FPX_EPX_RI_NACK (:1432-1449)
+ *          AcceptedEntry voted in the message's ballot       FPX_EPX_RI_ACCEPT_OK_AGAIN, nothing changes (:1451-1461)
+ *          else                                              FPX_EPX_RI_ACCEPT_OK: largestBallot is raised (:1487),
+ *                 AcceptedEntry(ballot, ballot, triple) with the message's dependencies, or by id (:1493-1502),
+ *                 updateConflictIndex (:1503)
+ *   kind FPX_EPX_IN_COMMIT (:1567-1575, 815-830): the entry is replaced whole by CommittedEntry(triple) with the message's
+ *          dependencies (or by id), the index learns the command (:828): FPX_EPX_RI_LEARNT.  The ballot fields are not read.
+ *   kind FPX_EPX_IN_PREPARE (:1632-1757): largestBallot is raised first, in every case (:1637).  The key fields are not read.
+ *          a CommittedEntry                                  FPX_EPX_RI_COMMIT_BACK (:1744-1755)
+ *          an entry with ballot > the message's             FPX_EPX_RI_NACK
+ *          no entry / NoCommandEntry                         FPX_EPX_RI_PREPARE_OK, out_status 0, NoCommandEntry(ballot)
+ *                                                            (:1654-1669, 1686-1701)
+ *          else                                              FPX_EPX_RI_PREPARE_OK, out_status 2 (PreAccepted) / 3
+ *                 (Accepted), out_ballot = the entry's voteBallot, the entry's triple; only `ballot` moves (:1711-1743)
+ * A leader state of to[i] (FPX_EPX_F_LEADER_STATE) ends as the reference ends it (:1239-1242, 1480-1483, 1645-1648, 831):
+ * every write of this call moves the entry as the per-kind calls do, and the liveness rule above fpx_epx_lead reads the entry.
+ * Outputs per message (any may be NULL): outcome; out_ballot -- a Nack's largestBallot of to[i] AT THAT MOMENT of the burst
+ * (encoded ordering * 8 + replica), a PrepareOk's voteBallot, else -1; out_status -- -1 unless FPX_EPX_RI_PREPARE_OK;
+ * out_deps (m x n) / out_values_end / out_triple -- the dependencies and triple id of the reply that was sent: the
+ * PreAcceptOk (first or again), the Commit sent back, the PrepareOk of status 2 / 3 (a triple stored by id: -1 in every
+ * column); elsewhere zeros / 0 / -1.
+ * FPX_EINVAL, nothing applied, no output written: num_instances = 0, an unknown kind, `to` outside 0..n-1, an instance
+ * outside the command log; kinds 0, 1, 3: ballot_replica outside 0..n-1 or ballot_ordering outside 0 .. 2^27 - 1; kinds 0, 1,
+ * 2: a key outside [-1, num_keys); kind 0: a negative watermark, an own-leader watermark above the instance, or explicit
+ * ids not above it (deps_values_end != 0 needs the own-leader watermark == number and deps_values_end >= number + 2); kinds
+ * 1, 2 with dependencies given: a negative watermark, or deps_values_end != 0 with deps_values_end <= number + 1 or the
+ * own-leader watermark > number; m > FPX_EPX_INBOX_MAX; n * n * num_instances >= 2^32.  There is no FPX_EFATAL_PROTOCOL
+ * on this side; m = 0 is FPX_OK.
+ * Cost: one stable radix sort of the burst on (to, leader, number), ONE thread per (replica, instance) walking that cell's
+ * messages in delivery order, then K7's conflict scan (a sort of n x m pairs on the key, one wavefront per (replica, key)) and
+ * the largestBallot scan of fpx_epx_prepare.
+ * fpx_epx_replica_inbox_dev: device pointers on the context's stream; status through fpx_epx_sync. */
+#define FPX_EPX_INBOX_MAX (1 << 24)
+enum { FPX_EPX_IN_PRE_ACCEPT = 0, FPX_EPX_IN_ACCEPT = 1, FPX_EPX_IN_COMMIT = 2, FPX_EPX_IN_PREPARE = 3 };
+enum {
+  FPX_EPX_RI_IGNORED = 0,
+  FPX_EPX_RI_PRE_ACCEPT_OK = 1,       /* processed: send PreAcceptOk */
+  FPX_EPX_RI_PRE_ACCEPT_OK_AGAIN = 2, /* send the PreAcceptOk of the stored triple again */
+  FPX_EPX_RI_ACCEPT_OK = 3,           /* taken in: send AcceptOk */
+  FPX_EPX_RI_ACCEPT_OK_AGAIN = 4,     /* send AcceptOk again */
+  FPX_EPX_RI_LEARNT = 5,              /* a Commit: nothing to send */
+  FPX_EPX_RI_PREPARE_OK = 6,          /* send PrepareOk(out_status, out_ballot, the triple) */
+  FPX_EPX_RI_NACK = 7,                /* send Nack(instance, out_ballot) */
+  FPX_EPX_RI_COMMIT_BACK = 8          /* the instance is committed here: send Commit with the stored triple */
+};
+int32_t fpx_epx_replica_inbox(fpx_epx* epx, int32_t m, const int32_t* kind, const int32_t* to, const int32_t* leader,
+                              const int32_t* number, const int32_t* ballot_ordering, const int32_t* ballot_replica,
+                              const int32_t* key, const uint8_t* is_set, const int32_t* triple_id, const int32_t* deps,
+                              const int32_t* deps_values_end, int32_t* outcome, int32_t* out_ballot, int32_t* out_status,
+                              int32_t* out_deps, int32_t* out_values_end, int32_t* out_triple);
+int32_t fpx_epx_replica_inbox_dev(fpx_epx* epx, int32_t m, const int32_t* d_kind, const int32_t* d_to, const int32_t* d_leader,
+                                  const int32_t* d_number, const int32_t* d_ballot_ordering, const int32_t* d_ballot_replica,
+                                  const int32_t* d_key, const uint8_t* d_is_set, const int32_t* d_triple_id,
+                                  const int32_t* d_deps, const int32_t* d_deps_values_end, int32_t* d_outcome,
+                                  int32_t* d_out_ballot, int32_t* d_out_status, int32_t* d_out_deps, int32_t* d_out_values_end,
+                                  int32_t* d_out_triple);
 /* readback (parity) of one leader state: out[0] = phase (0 none, 1 PreAccepting, 2 Accepting; 0 when the state is not live),
  * out[1] = ballot, out[2] = avoidFastPath, out[3] = triple id, out[4] = key, out[5] = is_set, out[6] = who has answered (bit
  * q), out[7] = the phase as stored (live or not); responses (may be NULL) n rows of n + 2 ints: row q = sequence number,
