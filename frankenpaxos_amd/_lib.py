@@ -49,6 +49,12 @@ CENSUS_WORDS = CENSUS_CELLS * len(CENSUS_FORMS) + 3
 # fpx_range_launch_census (include/fpx.h): its words in order
 RANGE_CENSUS_FORMS = ("chain", "steps", "band", "fill_lg", "fill_sweep", "fill_range", "tally_only", "open_only",
                       "acceptors_only", "rehash")
+# the EPaxos context flags, and the outcomes of fpx_epx_recover / fpx_epx_recovery_replies (include/fpx.h)
+FPX_EPX_F_LEADER_STATE = 1
+FPX_EPX_F_RECOVERY = 2
+FPX_EPX_RV_PREPARING, FPX_EPX_RV_COMMITTED, FPX_EPX_RV_FATAL = range(3)
+(FPX_EPX_RC_IGNORED, FPX_EPX_RC_WAITING, FPX_EPX_RC_ACCEPT, FPX_EPX_RC_PRE_ACCEPT, FPX_EPX_RC_PRE_ACCEPT_NOOP,
+ FPX_EPX_RC_FATAL) = range(6)
 # fpx_epx_tick_census and fpx_epx_limits (include/fpx.h): their words in order
 EPX_CENSUS_WORDS = ("kp", "kp_handed_over", "v1_switched_off", "v1_keys", "v1_full", "v1_log_n3", "v1_index_bits",
                     "no_key_kernel", "scalar_loads", "sort_bucket1", "sort_bucket2", "sort_radix1", "sort_radix2",
@@ -180,6 +186,11 @@ SIGNATURES = {
     "fpx_epx_replica_inbox": (C.c_int32, [VP, C.c_int32] + [VP] * 17),
     "fpx_epx_replica_inbox_dev": (C.c_int32, [VP, C.c_int32] + [VP] * 17),
     "fpx_epx_read_leader_state": (C.c_int32, [VP, C.c_int32, C.c_int32, C.c_int32, VP, VP]),
+    "fpx_epx_recover": (C.c_int32, [VP, C.c_int32] + [VP] * 8),
+    "fpx_epx_recovery_replies": (C.c_int32, [VP, C.c_int32] + [VP] * 13 + [C.c_int32] + [VP] * 9),
+    "fpx_epx_recovery_replies_dev": (C.c_int32, [VP, C.c_int32] + [VP] * 13 + [C.c_int32] + [VP] * 9),
+    "fpx_epx_lead_accept": (C.c_int32, [VP, C.c_int32] + [VP] * 10),
+    "fpx_epx_read_recovery_state": (C.c_int32, [VP, C.c_int32, C.c_int32, C.c_int32, VP]),
     "fpx_replica_chosen": (C.c_int32, [VP, C.c_int32, VP, VP, VP, I32P, I32P]),
     "fpx_replica_chosen_dev": (C.c_int32, [VP, C.c_int32, VP, VP, VP]),
     "fpx_replica_chosen_msgs": (C.c_int32, [VP, C.c_int32, VP, VP, VP, VP, VP, I32P, I32P]),

@@ -1380,6 +1380,7 @@ __global__ void __launch_bounds__(256) k_hp_commit(const EpxState st, const HpBa
 
 #include "fpx_epaxos_mk.hpp"
 #include "fpx_epx_leader.hpp"
+#include "fpx_epx_recovery.hpp"
 #include "fpx_epx_inbox.hpp"
 
 }  // namespace
@@ -1405,7 +1406,8 @@ struct fpx_epx {
   int64_t census[FPX_EPX_CENSUS_WORDS] = {};       // fpx_epx_tick_census: the host's words (the device's are added when it is read)
   unsigned long long* census_dev = nullptr;        // [EPX_CD_WORDS]
   uint32_t cl_run = 0;
-  EpxLeader ls = {nullptr, nullptr};      // FPX_EPX_F_LEADER_STATE: Replica.leaderStates (fpx_epx_leader.hpp), else not allocated
+  EpxLeader ls = {nullptr, nullptr, nullptr};  // FPX_EPX_F_LEADER_STATE: Replica.leaderStates (fpx_epx_leader.hpp), else not
+                                          // allocated; prep with FPX_EPX_F_RECOVERY (fpx_epx_recovery.hpp)
   DevBuf lr_misc;                         // fpx_epx_leader_replies: the decided flags and the compaction's block counts
   DevBuf ri_misc;                         // fpx_epx_replica_inbox: lay_epx_inbox
   bool lds_allowed = false, sort_lds_allowed = false;
@@ -1903,6 +1905,8 @@ int32_t fpx_epx_create(const fpx_epx_config* cfg, fpx_epx** out) {
   if ((cfg->flags & FPX_EPX_F_LEADER_STATE) &&
       (cfg->num_instances <= 0 || (int64_t)cfg->num_instances * n * n > (int64_t)1 << 31))
     return FPX_EINVAL;
+  // the Preparing phase is one more phase of the leader state
+  if ((cfg->flags & FPX_EPX_F_RECOVERY) && !(cfg->flags & FPX_EPX_F_LEADER_STATE)) return FPX_EINVAL;
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || cfg->device < 0 || cfg->device >= ndev)
     return FPX_ENODEVICE;
@@ -1963,6 +1967,9 @@ int32_t fpx_epx_create(const fpx_epx_config* cfg, fpx_epx** out) {
       if (hipMalloc((void**)&e->ls.head, ce * sizeof(int4)) != hipSuccess) return fail(FPX_ENOMEM);
       if (hipMalloc((void**)&e->ls.resp, ce * n * (n + 2) * 4) != hipSuccess) return fail(FPX_ENOMEM);
       if (hipMemsetAsync(e->ls.head, 0, ce * sizeof(int4), e->stream) != hipSuccess) return fail(FPX_EHIP);
+      // (a PrepareOk's row of prep, like a response row, is read only once its bit of the head is set)
+      if ((cfg->flags & FPX_EPX_F_RECOVERY) && hipMalloc((void**)&e->ls.prep, ce * n * sizeof(int2)) != hipSuccess)
+        return fail(FPX_ENOMEM);
     }
   }
   // the word k_kp_scatter tells the host through (did a key of the tick outgrow the on-chip tables?)
@@ -1986,7 +1993,7 @@ int32_t fpx_epx_destroy(fpx_epx* e) {
   DeviceScope _dg(e->cfg.device);
   if (e->stream) (void)hipStreamSynchronize(e->stream);
   void* ps[] = {e->st.gets, e->st.sets, e->st.status, e->st.cl_status, e->st.cl_ballot, e->st.cl_vote, e->st.cl_triple,
-                e->st.largest, e->st.cl_stamp, e->st.cl_deps, e->st.cl_dend, e->ls.head, e->ls.resp, e->census_dev};
+                e->st.largest, e->st.cl_stamp, e->st.cl_deps, e->st.cl_dend, e->ls.head, e->ls.resp, e->ls.prep, e->census_dev};
   for (void* p : ps)
     if (p) (void)hipFree(p);
   DevBuf* bs[] = {&e->kv, &e->kv2, &e->seg, &e->conf, &e->tmp, &e->tick, &e->fusedb, &e->metab, &e->stage, &e->mk_misc, &e->mk_rec,
@@ -3066,10 +3073,228 @@ int32_t fpx_epx_read_leader_state(fpx_epx* e, int32_t replica, int32_t leader, i
   HIPCHK(e, hipMemcpy(&ballot, e->st.cl_ballot + c, 4, hipMemcpyDeviceToHost));
   HIPCHK(e, hipMemcpy(&vote, e->st.cl_vote + c, 4, hipMemcpyDeviceToHost));
   const int phase = h[0] & 3;
-  const bool live = phase != 0 && kind != CL_COMMITTED && ballot == h[1] && vote == h[1];
+  const bool live = phase != 0 && kind != CL_COMMITTED && ballot == h[1] && (phase == LS_PREPARING || vote == h[1]);
   out[0] = live ? phase : 0, out[1] = h[1], out[2] = (h[0] >> 2) & 1, out[3] = h[2], out[4] = h[3], out[5] = (h[0] >> 3) & 1;
   out[6] = ((uint32_t)h[0] >> 8) & 0xff, out[7] = phase;
   if (responses) HIPCHK(e, hipMemcpy(responses, e->ls.resp + c * n * (n + 2), (size_t)n * (n + 2) * 4, hipMemcpyDeviceToHost));
+  return FPX_OK;
+}
+
+// ---- originating recovery (FPX_EPX_F_RECOVERY): csrc/fpx_epx_recovery.hpp ------------------------------------------------
+static bool recovery_on(const fpx_epx* e) { return leader_state_on(e) && (e->cfg.flags & FPX_EPX_F_RECOVERY) && e->ls.prep; }
+
+int32_t fpx_epx_recover(fpx_epx* e, int32_t m, const int32_t* leader, const int32_t* number, const int32_t* at, int32_t* outcome,
+                        int32_t* out_ballot_ordering, int32_t* out_status, int32_t* out_vote_ballot, int32_t* out_triple) {
+  if (!e || m < 0 || !recovery_on(e)) return FPX_EINVAL;
+  DeviceScope _dg(e->cfg.device);
+  if (m == 0) return FPX_OK;
+  if (!leader || !number || !at) return FPX_EINVAL;
+  const int n = e->st.n;
+  const int32_t *d_leader, *d_number, *d_at;
+  uint32_t* d_rank;
+  int32_t *d_base, *d_count, *d_outcome, *d_ord, *d_os, *d_ov, *d_ot;
+  auto launch = [&]() -> int {
+    RvBatch b;
+    memset(&b, 0, sizeof(b));
+    b.m = m, b.leader = d_leader, b.number = d_number, b.at = d_at, b.rank = d_rank, b.base = d_base, b.count = d_count;
+    b.outcome = d_outcome, b.out_ord = d_ord, b.out_status = d_os, b.out_vote = d_ov, b.out_triple = d_ot;
+    int rc2;
+    if ((rc2 = next_run_id(e, &b.run_id))) return rc2;
+    const dim3 gm((m + 255) / 256), blk(256);
+    hipLaunchKernelGGL(k_rv_validate, gm, blk, 0, e->stream, e->st, b);
+    for (int r = 0; r < n; ++r) {  // row r of `rank` to its exclusive scan, its total to count[r]
+      LrBatch sb;
+      memset(&sb, 0, sizeof(sb));
+      sb.bsum = d_rank + (size_t)r * m, sb.blocks = m, sb.num_decided = d_count + r;
+      hipLaunchKernelGGL(k_lr_bscan, dim3(1), blk, 0, e->stream, e->st, sb);
+    }
+    hipLaunchKernelGGL(k_rv_base, dim3(1), dim3(64), 0, e->stream, e->st, b);
+    by_n(n, [&](auto N) { hipLaunchKernelGGL((k_rv_install<N>), gm, blk, 0, e->stream, e->st, e->ls, b); });
+    return FPX_OK;
+  };
+  // the outputs reach the caller only on FPX_OK / FPX_EFATAL_PROTOCOL: FPX_EINVAL leaves the caller's arrays as they were
+  std::vector<int32_t> tmp;
+  try {
+    tmp.resize(5 * (size_t)m);
+  } catch (const std::bad_alloc&) {  // (no exception crosses the C ABI)
+    return FPX_ENOMEM;
+  }
+  int32_t *h_outcome = tmp.data(), *h_ord = h_outcome + m, *h_os = h_ord + m, *h_ov = h_os + m, *h_ot = h_ov + m;
+  const int rc = host_call(e, {in(d_leader, leader, m), in(d_number, number, m), in(d_at, at, m), scratch(d_rank, (size_t)m * n),
+                               scratch(d_base, 8), scratch(d_count, 8, 0), out(d_outcome, h_outcome, m), out(d_ord, h_ord, m), out(d_os, h_os, m),
+                               out(d_ov, h_ov, m), out(d_ot, h_ot, m)},
+                           launch);
+  if (rc != FPX_OK && rc != FPX_EFATAL_PROTOCOL) return rc;
+  if (outcome) memcpy(outcome, h_outcome, (size_t)m * 4);
+  if (out_ballot_ordering) memcpy(out_ballot_ordering, h_ord, (size_t)m * 4);
+  if (out_status) memcpy(out_status, h_os, (size_t)m * 4);
+  if (out_vote_ballot) memcpy(out_vote_ballot, h_ov, (size_t)m * 4);
+  if (out_triple) memcpy(out_triple, h_ot, (size_t)m * 4);
+  return rc;
+}
+
+static int32_t recovery_replies_launch(fpx_epx* e, int32_t m, const int32_t* d_to, const int32_t* d_leader, const int32_t* d_number,
+                                       const int32_t* d_bo, const int32_t* d_br, const int32_t* d_ridx, const int32_t* d_status,
+                                       const int32_t* d_vo, const int32_t* d_vr, const int32_t* d_tr, const int32_t* d_seq,
+                                       const int32_t* d_deps, const int32_t* d_dend, int32_t as_intended, int32_t* d_outcome,
+                                       int32_t* d_source, int32_t* d_otr, int32_t* d_oballot, int32_t* d_oseq, int32_t* d_odeps,
+                                       int32_t* d_oend, int32_t* d_decided, int32_t* d_num_decided) {
+  const int n = e->st.n;
+  RrBatch b;
+  memset(&b, 0, sizeof(b));
+  b.m = m, b.as_intended = as_intended ? 1 : 0, b.to = d_to, b.leader = d_leader, b.number = d_number, b.b_ord = d_bo, b.b_rep = d_br;
+  b.ridx = d_ridx, b.status = d_status, b.v_ord = d_vo, b.v_rep = d_vr, b.triple = d_tr, b.seq = d_seq, b.deps = d_deps, b.dend = d_dend;
+  b.outcome = d_outcome, b.out_source = d_source, b.out_triple = d_otr, b.out_ballot = d_oballot, b.out_seq = d_oseq;
+  b.out_deps = d_odeps, b.out_end = d_oend;
+  LrBatch cb;  // the compaction of fpx_epx_leader_replies, on this burst's flags
+  memset(&cb, 0, sizeof(cb));
+  cb.m = m, cb.decided = d_decided, cb.num_decided = d_num_decided, cb.blocks = (m + LR_BLOCK - 1) / LR_BLOCK;
+  int rc;
+  if ((rc = grow(e, &e->kv, (size_t)m * 8))) return rc;
+  if ((rc = grow(e, &e->kv2, (size_t)m * 8))) return rc;
+  LrScratch ls;
+  if ((rc = carve(e, &e->lr_misc, &ls, [&](Carver& c) { return lay_leader_replies(c, m, cb.blocks); }))) return rc;
+  b.kv = (uint2*)e->kv.p, b.flag = ls.flag, cb.flag = ls.flag, cb.bsum = ls.bsum;
+  const dim3 gm((m + 255) / 256), blk(256);
+  hipLaunchKernelGGL(k_rr_validate, gm, blk, 0, e->stream, e->st, b);
+  unsigned bits = 1;  // the cells of the context: (to, leader, number)
+  while (((uint64_t)1 << bits) < (uint64_t)n * n * e->st.num_instances) ++bits;
+  b.sorted = radix_sort_pairs(e, 1, m, bits, b.kv, (uint2*)e->kv2.p, nullptr, &rc, nullptr, nullptr);
+  if (rc) return rc;
+  by_n(n, [&](auto N) { hipLaunchKernelGGL((k_rr_walk<N>), gm, blk, 0, e->stream, e->st, e->ls, b); });
+  if (d_decided || d_num_decided) {
+    hipLaunchKernelGGL(k_lr_count, dim3(cb.blocks), blk, 0, e->stream, e->st, cb);
+    hipLaunchKernelGGL(k_lr_bscan, dim3(1), blk, 0, e->stream, e->st, cb);
+    if (d_decided) hipLaunchKernelGGL(k_lr_compact, dim3(cb.blocks), blk, 0, e->stream, e->st, cb);
+  }
+  return FPX_OK;
+}
+
+int32_t fpx_epx_recovery_replies_dev(fpx_epx* e, int32_t m, const int32_t* d_to, const int32_t* d_leader, const int32_t* d_number,
+                                     const int32_t* d_ballot_ordering, const int32_t* d_ballot_replica,
+                                     const int32_t* d_replica_index, const int32_t* d_status, const int32_t* d_vote_ballot_ordering,
+                                     const int32_t* d_vote_ballot_replica, const int32_t* d_triple_id,
+                                     const int32_t* d_sequence_number, const int32_t* d_deps, const int32_t* d_deps_values_end,
+                                     int32_t as_intended, int32_t* d_outcome, int32_t* d_out_source, int32_t* d_out_triple,
+                                     int32_t* d_out_ballot, int32_t* d_out_seq, int32_t* d_out_deps, int32_t* d_out_values_end,
+                                     int32_t* d_decided_index, int32_t* d_num_decided) {
+  if (!e || m < 0 || m >= (1 << 30) || !recovery_on(e)) return FPX_EINVAL;
+  DeviceScope _dg(e->cfg.device);
+  if (m == 0) {
+    if (d_num_decided) HIPCHK(e, hipMemsetAsync(d_num_decided, 0, 4, e->stream));
+    return FPX_OK;
+  }
+  if (!d_to || !d_leader || !d_number || !d_ballot_ordering || !d_ballot_replica || !d_replica_index || !d_status ||
+      !d_vote_ballot_ordering || !d_vote_ballot_replica || !d_triple_id || !d_deps)
+    return FPX_EINVAL;
+  int rc = recovery_replies_launch(e, m, d_to, d_leader, d_number, d_ballot_ordering, d_ballot_replica, d_replica_index, d_status,
+                                   d_vote_ballot_ordering, d_vote_ballot_replica, d_triple_id, d_sequence_number, d_deps,
+                                   d_deps_values_end, as_intended, d_outcome, d_out_source, d_out_triple, d_out_ballot, d_out_seq,
+                                   d_out_deps, d_out_values_end, d_decided_index, d_num_decided);
+  return rc ? rc : launch_check(e);
+}
+
+int32_t fpx_epx_recovery_replies(fpx_epx* e, int32_t m, const int32_t* to, const int32_t* leader, const int32_t* number,
+                                 const int32_t* ballot_ordering, const int32_t* ballot_replica, const int32_t* replica_index,
+                                 const int32_t* status, const int32_t* vote_ballot_ordering, const int32_t* vote_ballot_replica,
+                                 const int32_t* triple_id, const int32_t* sequence_number, const int32_t* deps,
+                                 const int32_t* deps_values_end, int32_t as_intended, int32_t* outcome, int32_t* out_source,
+                                 int32_t* out_triple, int32_t* out_ballot, int32_t* out_seq, int32_t* out_deps,
+                                 int32_t* out_values_end, int32_t* decided_index, int32_t* num_decided) {
+  if (!e || m < 0 || m >= (1 << 30) || !recovery_on(e)) return FPX_EINVAL;
+  DeviceScope _dg(e->cfg.device);
+  if (m == 0) {
+    if (num_decided) *num_decided = 0;
+    return FPX_OK;
+  }
+  if (!to || !leader || !number || !ballot_ordering || !ballot_replica || !replica_index || !status || !vote_ballot_ordering ||
+      !vote_ballot_replica || !triple_id || !deps)
+    return FPX_EINVAL;
+  const size_t mn = (size_t)m * e->st.n;
+  const int32_t *d_to, *d_leader, *d_number, *d_bo, *d_br, *d_ridx, *d_status, *d_vo, *d_vr, *d_tr, *d_seq, *d_deps, *d_dend;
+  int32_t *d_outcome, *d_src, *d_otr, *d_ob, *d_oseq, *d_odeps, *d_oend, *d_dec, *d_nd;
+  auto launch = [&]() -> int {
+    return recovery_replies_launch(e, m, d_to, d_leader, d_number, d_bo, d_br, d_ridx, d_status, d_vo, d_vr, d_tr,
+                                   sequence_number ? d_seq : nullptr, d_deps, deps_values_end ? d_dend : nullptr, as_intended,
+                                   d_outcome, d_src, d_otr, d_ob, d_oseq, d_odeps, d_oend, d_dec, d_nd);
+  };
+  // an output is downloaded only on FPX_OK / FPX_EFATAL_PROTOCOL: FPX_EINVAL leaves the caller's arrays as they were
+  std::vector<int32_t> tmp;
+  try {
+    tmp.resize(7 * (size_t)m + mn + 1);
+  } catch (const std::bad_alloc&) {  // (no exception crosses the C ABI)
+    return FPX_ENOMEM;
+  }
+  int32_t *h_outcome = tmp.data(), *h_src = h_outcome + m, *h_otr = h_src + m, *h_ob = h_otr + m, *h_oseq = h_ob + m;
+  int32_t *h_oend = h_oseq + m, *h_dec = h_oend + m, *h_odeps = h_dec + m, *h_nd = h_odeps + mn;
+  const int rc = host_call(e, {in(d_to, to, m), in(d_leader, leader, m), in(d_number, number, m), in(d_bo, ballot_ordering, m),
+                               in(d_br, ballot_replica, m), in(d_ridx, replica_index, m), in(d_status, status, m),
+                               in(d_vo, vote_ballot_ordering, m), in(d_vr, vote_ballot_replica, m), in(d_tr, triple_id, m),
+                               in(d_seq, sequence_number, m), in(d_dend, deps_values_end, m), in(d_deps, deps, mn),
+                               out(d_outcome, h_outcome, m), out(d_src, h_src, m), out(d_otr, h_otr, m), out(d_ob, h_ob, m),
+                               out(d_oseq, h_oseq, m), out(d_oend, h_oend, m), out(d_dec, h_dec, m), out(d_odeps, h_odeps, mn),
+                               out(d_nd, h_nd, 1)},
+                           launch);
+  if (rc != FPX_OK && rc != FPX_EFATAL_PROTOCOL) return rc;
+  if (outcome) memcpy(outcome, h_outcome, (size_t)m * 4);
+  if (out_source) memcpy(out_source, h_src, (size_t)m * 4);
+  if (out_triple) memcpy(out_triple, h_otr, (size_t)m * 4);
+  if (out_ballot) memcpy(out_ballot, h_ob, (size_t)m * 4);
+  if (out_seq) memcpy(out_seq, h_oseq, (size_t)m * 4);
+  if (out_values_end) memcpy(out_values_end, h_oend, (size_t)m * 4);
+  if (out_deps) memcpy(out_deps, h_odeps, mn * 4);
+  if (decided_index) memcpy(decided_index, h_dec, (size_t)*h_nd * 4);
+  if (num_decided) *num_decided = *h_nd;
+  return rc;
+}
+
+int32_t fpx_epx_lead_accept(fpx_epx* e, int32_t m, const int32_t* leader, const int32_t* number, const int32_t* at,
+                            const int32_t* ballot_ordering, const int32_t* key, const uint8_t* is_set, const int32_t* triple_id,
+                            const int32_t* sequence_number, const int32_t* deps, const int32_t* deps_values_end) {
+  if (!e || m < 0 || !recovery_on(e)) return FPX_EINVAL;
+  DeviceScope _dg(e->cfg.device);
+  if (m == 0) return FPX_OK;
+  if (!leader || !number || !at || !ballot_ordering || !key || !is_set || !triple_id || !deps) return FPX_EINVAL;
+  const int n = e->st.n;
+  const size_t mn = (size_t)m * n;
+  const int32_t *d_leader, *d_number, *d_at, *d_bo, *d_key, *d_tr, *d_seq, *d_deps, *d_dend;
+  const uint8_t* d_set;
+  auto launch = [&]() -> int {
+    LaBatch b;
+    memset(&b, 0, sizeof(b));
+    b.m = m, b.leader = d_leader, b.number = d_number, b.at = d_at, b.b_ord = d_bo, b.key = d_key, b.is_set = d_set, b.triple = d_tr;
+    b.seq = sequence_number ? d_seq : nullptr, b.deps = d_deps, b.dend = deps_values_end ? d_dend : nullptr;
+    int rc2;
+    if ((rc2 = next_run_id(e, &b.run_id))) return rc2;
+    const dim3 gm((m + 255) / 256), blk(256);
+    hipLaunchKernelGGL(k_la_validate, gm, blk, 0, e->stream, e->st, b);
+    by_n(n, [&](auto N) { hipLaunchKernelGGL((k_la_install<N>), gm, blk, 0, e->stream, e->st, e->ls, b); });
+    return FPX_OK;
+  };
+  return host_call(e, {in(d_leader, leader, m), in(d_number, number, m), in(d_at, at, m), in(d_bo, ballot_ordering, m),
+                       in(d_key, key, m), in(d_tr, triple_id, m), in(d_seq, sequence_number, m), in(d_dend, deps_values_end, m),
+                       in(d_deps, deps, mn), in(d_set, is_set, m)},
+                   launch);
+}
+
+int32_t fpx_epx_read_recovery_state(fpx_epx* e, int32_t replica, int32_t leader, int32_t number, int32_t* out) {
+  if (!recovery_on(e) || !out || replica < 0 || replica >= e->st.n || leader < 0 || leader >= e->st.n || number < 0 ||
+      number >= e->st.num_instances)
+    return FPX_EINVAL;
+  DeviceScope _dg(e->cfg.device);
+  const int n = e->st.n;
+  const size_t c = ((size_t)replica * n + leader) * e->st.num_instances + number;
+  int32_t h[4], p[16];
+  HIPCHK(e, hipStreamSynchronize(e->stream));
+  HIPCHK(e, hipMemcpy(h, e->ls.head + c, 16, hipMemcpyDeviceToHost));
+  HIPCHK(e, hipMemcpy(p, e->ls.prep + c * n, (size_t)n * 8, hipMemcpyDeviceToHost));
+  const bool preparing = (h[0] & 3) == LS_PREPARING;
+  for (int q = 0; q < n; ++q) {
+    const bool has = preparing && (((uint32_t)h[0] >> (8 + q)) & 1u);
+    out[q * 3] = has ? (int32_t)(((uint32_t)h[0] >> (16 + 2 * q)) & 3u) : -1;
+    out[q * 3 + 1] = has ? p[2 * q] : -1;
+    out[q * 3 + 2] = has ? p[2 * q + 1] : -1;
+  }
   return FPX_OK;
 }
 

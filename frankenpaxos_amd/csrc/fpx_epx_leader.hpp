@@ -22,11 +22,12 @@
 // Integer compares, max and atomics only; plain vector stores.
 #pragma once
 
-enum { LS_NONE = 0, LS_PRE_ACCEPTING = 1, LS_ACCEPTING = 2 };
+enum { LS_NONE = 0, LS_PRE_ACCEPTING = 1, LS_ACCEPTING = 2, LS_PREPARING = 3 };  // (Preparing: fpx_epx_recovery.hpp)
 
 struct EpxLeader {
   int4* head;     // [n * n * num_instances]
   int32_t* resp;  // [n * n * num_instances][n][n + 2]
+  int2* prep;     // [n * n * num_instances][n] FPX_EPX_F_RECOVERY (else null): a PrepareOk's (voteBallot, triple id)
 };
 
 __device__ __forceinline__ int ls_pack(int phase, int avoid, int is_set, unsigned mask) {
@@ -226,7 +227,10 @@ __global__ void __launch_bounds__(256) k_lr_walk(const EpxState st, const EpxLea
   // The reference drops leaderStates(instance) when a PreAccept / Accept / Prepare of a higher ballot arrives (:1239-1242,
   // 1480-1483, 1645-1648) or the instance commits (:831).  Each of them leaves the replica's own entry committed or with
   // another ballot / vote ballot than the one led in, so the state is live exactly while the entry still shows it.
-  if (phase != LS_NONE && (st.cl_status[c] == CL_COMMITTED || st.cl_ballot[c] != ballot || st.cl_vote[c] != ballot)) phase = LS_NONE;
+  // (A Preparing state -- fpx_epx_recovery.hpp -- moved `ballot` only: the vote ballot is not compared.)
+  if (phase != LS_NONE && (st.cl_status[c] == CL_COMMITTED || st.cl_ballot[c] != ballot ||
+                           (phase != LS_PREPARING && st.cl_vote[c] != ballot)))
+    phase = LS_NONE;
   bool dirty = phase != (h0.x & 3);
   LrCell<N> cell{ls.resp + c * N * (N + 2)};
 
@@ -315,7 +319,7 @@ __global__ void __launch_bounds__(256) k_lr_walk(const EpxState st, const EpxLea
       atomicMax(&st.largest[to], mb);  // :1578, whatever follows
       outcome = (phase != LS_NONE && ballot < mb) ? FPX_EPX_NACK_RECOVER : FPX_EPX_NACK_IGNORED;  // :1580-1629
     } else {
-      // the defaultToSlowPath timer (:1023-1031); preAcceptingSlowPath checks responses.size >= slowQuorumSize (:801)
+      // the defaultToSlowPath timer (:1023-1031; any other state, Preparing too, is its logger.fatal); preAcceptingSlowPath checks responses.size >= slowQuorumSize (:801)
       if (phase == LS_PRE_ACCEPTING && __popc(mask) >= SLOW) slow_path = true;
       else fatal = true;
     }

@@ -10,6 +10,10 @@ from ._lib import FpxError
 
 
 FPX_EPX_F_LEADER_STATE = 1
+FPX_EPX_F_RECOVERY = 2
+# fpx_epx_recover / fpx_epx_recovery_replies: per-message outcomes (include/fpx.h)
+RV_PREPARING, RV_COMMITTED, RV_FATAL = range(3)
+RC_IGNORED, RC_WAITING, RC_ACCEPT, RC_PRE_ACCEPT, RC_PRE_ACCEPT_NOOP, RC_FATAL = range(6)
 # fpx_epx_leader_replies: message kinds and per-message outcomes (include/fpx.h)
 PRE_ACCEPT_OK, ACCEPT_OK, NACK, SLOW_PATH_TIMER = 0, 1, 2, 3
 (IGNORED, WAITING, START_SLOW_PATH_TIMER, FAST_COMMIT, ACCEPT, SLOW_COMMIT, NACK_RECOVER, NACK_IGNORED,
@@ -40,15 +44,18 @@ def _bind(L):
 
 
 class EPaxos:
-    def __init__(self, num_replicas, num_keys, device=0, num_instances=0, leader_state=False):
+    def __init__(self, num_replicas, num_keys, device=0, num_instances=0, leader_state=False, recovery=False):
         """num_instances > 0: every replica keeps its command log for instances (leader, number < num_instances):
         pre-accept records it, prepare() / accept() run the per-instance Paxos on it.
         leader_state (needs num_instances > 0): the context also keeps Replica.leaderStates, for lead() and
-        leader_replies() -- hosted replicas that lead instances among peers in other processes"""
+        leader_replies() -- hosted replicas that lead instances among peers in other processes.
+        recovery (needs leader_state): the leader state has the Preparing phase, for recover(), recovery_replies() and
+        lead_accept() -- hosted replicas that originate an instance's recovery"""
         self.L = _lib.lib()
         _bind(self.L)
         self.n, self.num_keys = num_replicas, num_keys
-        cfg = FpxEpxConfig(num_replicas, num_keys, device, FPX_EPX_F_LEADER_STATE if leader_state else 0, num_instances)
+        flags = (FPX_EPX_F_LEADER_STATE if leader_state else 0) | (FPX_EPX_F_RECOVERY if recovery else 0)
+        cfg = FpxEpxConfig(num_replicas, num_keys, device, flags, num_instances)
         h = C.c_void_p()
         st = self.L.fpx_epx_create(C.byref(cfg), C.byref(h))
         if st:
@@ -314,6 +321,78 @@ class EPaxos:
                                                d(out_triple), d(decided_index), d(num_decided))
         if st:
             raise FpxError(st, "fpx_epx_leader_replies_dev")
+
+    # ---- originating recovery (recovery=True) ----
+    def recover(self, leader, number, at):
+        """transitionToPreparePhase of instance (leader, number) at replica `at`, its own Prepare delivered at once:
+        (status, outcome[m], ballot_ordering[m] of the Prepare to send, and the own PrepareOk: status[m], vote_ballot[m]
+        encoded, triple[m]); on FPX_EINVAL the outputs keep their fill of -9"""
+        a32 = lambda x: np.ascontiguousarray(x, dtype=np.int32)
+        leader, number, at = a32(leader), a32(number), a32(at)
+        m = len(leader)
+        outcome, ord_, os_, ov, ot = (np.full(m, -9, np.int32) for _ in range(5))
+        p = lambda a: a.ctypes.data
+        st = self.L.fpx_epx_recover(self._h, m, p(leader), p(number), p(at), p(outcome), p(ord_), p(os_), p(ov), p(ot))
+        return st, outcome, ord_, os_, ov, ot
+
+    def recovery_replies(self, to, leader, number, ballot_ordering, ballot_replica, replica_index, status,
+                         vote_ballot_ordering, vote_ballot_replica, triple_id, sequence_number=None, deps=None,
+                         deps_values_end=None, as_intended=False):
+        """one burst of PrepareOks in delivery order: (status, outcome[m], source[m], triple[m], ballot[m], out_seq[m],
+        out_deps[m, n], out_values_end[m], decided_index[num_decided])"""
+        a32 = lambda x: np.ascontiguousarray(x, dtype=np.int32)
+        to, leader, number = a32(to), a32(leader), a32(number)
+        bo, br, ridx, stt = a32(ballot_ordering), a32(ballot_replica), a32(replica_index), a32(status)
+        vo, vr, tr = a32(vote_ballot_ordering), a32(vote_ballot_replica), a32(triple_id)
+        m = len(to)
+        seq = None if sequence_number is None else a32(sequence_number)
+        deps = np.zeros((m, self.n), np.int32) if deps is None else a32(deps)
+        dend = None if deps_values_end is None else a32(deps_values_end)
+        outcome, src, otr, ob, oseq, oend, dec = (np.full(m, -9, np.int32) for _ in range(7))
+        odeps = np.full((m, self.n), -9, np.int32)
+        nd = np.full(1, -9, np.int32)
+        p = lambda a: None if a is None else a.ctypes.data
+        st = self.L.fpx_epx_recovery_replies(self._h, m, p(to), p(leader), p(number), p(bo), p(br), p(ridx), p(stt), p(vo), p(vr),
+                                             p(tr), p(seq), p(deps), p(dend), 1 if as_intended else 0, p(outcome), p(src),
+                                             p(otr), p(ob), p(oseq), p(odeps), p(oend), p(dec), p(nd))
+        return st, outcome, src, otr, ob, oseq, odeps, oend, dec[:max(int(nd[0]), 0)]
+
+    def recovery_replies_dev(self, to, leader, number, ballot_ordering, ballot_replica, replica_index, status,
+                             vote_ballot_ordering, vote_ballot_replica, triple_id, sequence_number, deps, deps_values_end,
+                             as_intended=False, outcome=None, out_source=None, out_triple=None, out_ballot=None, out_seq=None,
+                             out_deps=None, out_values_end=None, decided_index=None, num_decided=None):
+        """the same on device tensors (int32), enqueued on the context's stream; the status comes with sync()"""
+        d = lambda t: None if t is None else t.data_ptr()
+        st = self.L.fpx_epx_recovery_replies_dev(self._h, to.numel(), d(to), d(leader), d(number), d(ballot_ordering),
+                                                 d(ballot_replica), d(replica_index), d(status), d(vote_ballot_ordering),
+                                                 d(vote_ballot_replica), d(triple_id), d(sequence_number), d(deps),
+                                                 d(deps_values_end), 1 if as_intended else 0, d(outcome), d(out_source),
+                                                 d(out_triple), d(out_ballot), d(out_seq), d(out_deps), d(out_values_end),
+                                                 d(decided_index), d(num_decided))
+        if st:
+            raise FpxError(st, "fpx_epx_recovery_replies_dev")
+
+    def lead_accept(self, leader, number, at, ballot_ordering, key, is_set, triple_id, sequence_number, deps,
+                    deps_values_end=None):
+        """transitionToAcceptPhase of instance (leader, number) at replica `at` in ballot (ballot_ordering, at) with the triple
+        (triple_id, sequence_number, deps[m, n], deps_values_end) -> status"""
+        a32 = lambda x: None if x is None else np.ascontiguousarray(x, dtype=np.int32)
+        leader, number, at, bo, key, tr = a32(leader), a32(number), a32(at), a32(ballot_ordering), a32(key), a32(triple_id)
+        m = len(leader)
+        is_set = np.ascontiguousarray(is_set, dtype=np.uint8)
+        seq, dend = a32(sequence_number), a32(deps_values_end)
+        deps = a32(deps).reshape(m, self.n)
+        p = lambda a: None if a is None else a.ctypes.data
+        return self.L.fpx_epx_lead_accept(self._h, m, p(leader), p(number), p(at), p(bo), p(key), p(is_set), p(tr), p(seq),
+                                          p(deps), p(dend))
+
+    def read_recovery_state(self, replica, leader, number):
+        """[n, 3]: per responder the PrepareOk's status, voteBallot (encoded) and triple id; -1s where there is none"""
+        out = np.zeros((self.n, 3), np.int32)
+        st = self.L.fpx_epx_read_recovery_state(self._h, replica, leader, number, out.ctypes.data)
+        if st:
+            raise FpxError(st, "fpx_epx_read_recovery_state")
+        return out
 
     # ---- the replica half, a burst at a time ----
     def replica_inbox(self, kind, to, leader, number, ballot_ordering, ballot_replica, key, is_set, triple_id, deps,

@@ -978,19 +978,75 @@ struct LeaderOutcome {
   std::vector<int32_t> dependencies;
 };
 
+// transitionToPreparePhase of one instance at one hosted replica (Replica.scala:969-996), its own Prepare delivered at once
+struct RecoverRequest {
+  Instance instance;
+  int at = 0;
+};
+enum class RecoverOutcome { Preparing = FPX_EPX_RV_PREPARING, Committed = FPX_EPX_RV_COMMITTED, Fatal = FPX_EPX_RV_FATAL };
+// the Prepare to send in ballot (ballotOrdering, at), and the replica's own PrepareOk
+struct RecoverResult {
+  RecoverOutcome outcome = RecoverOutcome::Preparing;
+  int32_t ballotOrdering = 0;
+  int32_t status = -1;         // 0 NotSeen, 2 PreAccepted, 3 Accepted; -1: no PrepareOk
+  Ballot voteBallot;
+  int32_t tripleId = -1;
+};
+// a PrepareOk at a hosted replica
+struct PrepareOkInbound {
+  int to = 0;
+  Instance instance;
+  Ballot ballot;
+  int replicaIndex = 0;
+  int32_t status = 0;                    // 0 NotSeen, 2 PreAccepted, 3 Accepted
+  Ballot voteBallot;
+  int32_t tripleId = -1;                 // equal commands carry equal ids
+  int32_t sequenceNumber = 0;
+  std::vector<int32_t> dependencies;     // n watermarks (empty = none); not read for status 0
+  int32_t ownValuesEnd = 0;
+};
+enum class RecoveryOutcome {
+  Ignored = FPX_EPX_RC_IGNORED, Waiting = FPX_EPX_RC_WAITING, AcceptPhase = FPX_EPX_RC_ACCEPT,
+  PreAcceptCommand = FPX_EPX_RC_PRE_ACCEPT, PreAcceptNoop = FPX_EPX_RC_PRE_ACCEPT_NOOP, Fatal = FPX_EPX_RC_FATAL
+};
+// what handlePrepareOk does with it (Replica.scala:1759-1869).  A decision clears the state: apply it with lead()
+// (avoidFastPath) or leadAccept() BEFORE the engine sees another burst for that instance
+struct RecoveryReply {
+  RecoveryOutcome outcome = RecoveryOutcome::Ignored;
+  int source = -1;
+  int32_t tripleId = -1;
+  Ballot ballot;                         // the recovery's ballot, on a decision
+  int32_t sequenceNumber = 0, ownValuesEnd = 0;   // AcceptPhase: the triple
+  std::vector<int32_t> dependencies;
+};
+// transitionToAcceptPhase of one instance at one hosted replica with a given triple (Replica.scala:732-793)
+struct LeadAcceptRequest {
+  Instance instance;
+  int at = 0;
+  int32_t ballotOrdering = 0;
+  Command command{-1, false};
+  int32_t tripleId = -1;
+  int32_t sequenceNumber = 0;
+  std::vector<int32_t> dependencies;     // n watermarks; {-1, ...}: known by tripleId only
+  int32_t ownValuesEnd = 0;
+};
+
 // The conflict indices (and, with numInstances > 0, the command logs) of the n replicas, resident in HBM.
 class PreAcceptEngine {
  public:
   // leaderState (needs numInstances > 0): the engine also keeps Replica.leaderStates (Replica.scala:499), for lead() and
   // handleReplies() -- hosted replicas leading instances among peers in other processes
-  PreAcceptEngine(int f, int numKeys, int device = 0, int numInstances = 0, bool leaderState = false) : n_(2 * f + 1) {
+  // recovery (needs leaderState): the leader state has the Preparing phase, for recover(), handlePrepareOks(burst) and
+  // leadAccept() -- hosted replicas that originate an instance's recovery
+  PreAcceptEngine(int f, int numKeys, int device = 0, int numInstances = 0, bool leaderState = false, bool recovery = false)
+      : n_(2 * f + 1) {
     if (f < 1) throw std::invalid_argument("f must be >= 1.");
     fpx_epx_config c{};
     c.num_replicas = n_;
     c.num_keys = numKeys;
     c.device = device;
     c.num_instances = numInstances;
-    c.flags = leaderState ? FPX_EPX_F_LEADER_STATE : 0u;
+    c.flags = (leaderState ? FPX_EPX_F_LEADER_STATE : 0u) | (recovery ? FPX_EPX_F_RECOVERY : 0u);
     check(fpx_epx_create(&c, &epx_), "fpx_epx_create");
   }
   ~PreAcceptEngine() {
@@ -1151,6 +1207,87 @@ class PreAcceptEngine {
     }
     if (decided) decided->assign(dec.begin(), dec.begin() + nd);
     return out;
+  }
+
+  // transitionToPreparePhase (Replica.scala:969-996) at requests[i].at, in vector order; instances pairwise distinct
+  std::vector<RecoverResult> recover(const std::vector<RecoverRequest>& requests) {
+    const int m = (int)requests.size();
+    std::vector<int32_t> leader(m), number(m), at(m), outcome(m), ord(m), os(m), ov(m), ot(m);
+    for (int i = 0; i < m; ++i)
+      leader[i] = requests[i].instance.replicaIndex, number[i] = requests[i].instance.instanceNumber, at[i] = requests[i].at;
+    const int32_t st = fpx_epx_recover(epx_, m, leader.data(), number.data(), at.data(), outcome.data(), ord.data(), os.data(),
+                                       ov.data(), ot.data());
+    if (st != FPX_EFATAL_PROTOCOL) check(st, "Replica.transitionToPreparePhase");
+    std::vector<RecoverResult> out(m);
+    for (int i = 0; i < m; ++i) {
+      out[i].outcome = (RecoverOutcome)outcome[i], out[i].ballotOrdering = ord[i], out[i].status = os[i];
+      out[i].voteBallot = Ballot::decode(ov[i]), out[i].tripleId = ot[i];
+    }
+    return out;
+  }
+
+  // one burst of PrepareOks in delivery order through ONE device call; decided (may be null): the indices of the decisions
+  std::vector<RecoveryReply> handlePrepareOks(const std::vector<PrepareOkInbound>& msgs, bool asIntended = false,
+                                              std::vector<int>* decided = nullptr) {
+    const int m = (int)msgs.size();
+    std::vector<int32_t> to(m), leader(m), number(m), bo(m), br(m), q(m), status(m), vo(m), vr(m), tr(m), seq(m), dend(m);
+    std::vector<int32_t> deps((size_t)m * n_, 0);
+    for (int i = 0; i < m; ++i) {
+      const PrepareOkInbound& a = msgs[i];
+      to[i] = a.to, leader[i] = a.instance.replicaIndex, number[i] = a.instance.instanceNumber;
+      bo[i] = a.ballot.ordering, br[i] = a.ballot.replicaIndex, q[i] = a.replicaIndex, status[i] = a.status;
+      vo[i] = a.voteBallot.ordering, vr[i] = a.voteBallot.replicaIndex, tr[i] = a.tripleId, seq[i] = a.sequenceNumber;
+      dend[i] = a.ownValuesEnd;
+      if (!a.dependencies.empty()) {
+        if ((int)a.dependencies.size() != n_) throw std::invalid_argument("one dependency watermark per replica");
+        std::copy(a.dependencies.begin(), a.dependencies.end(), deps.begin() + (size_t)i * n_);
+      }
+    }
+    std::vector<int32_t> outcome(m), src(m), otr(m), ob(m), oseq(m), oend(m), dec(m), odeps((size_t)m * n_);
+    int32_t nd = 0;
+    const int32_t st = fpx_epx_recovery_replies(epx_, m, to.data(), leader.data(), number.data(), bo.data(), br.data(), q.data(),
+                                                status.data(), vo.data(), vr.data(), tr.data(), seq.data(), deps.data(),
+                                                dend.data(), asIntended ? 1 : 0, outcome.data(), src.data(), otr.data(),
+                                                ob.data(), oseq.data(), odeps.data(), oend.data(), dec.data(), &nd);
+    if (st != FPX_EFATAL_PROTOCOL) check(st, "Replica.handlePrepareOk");
+    std::vector<RecoveryReply> out(m);
+    for (int i = 0; i < m; ++i) {
+      out[i].outcome = (RecoveryOutcome)outcome[i], out[i].source = src[i], out[i].tripleId = otr[i];
+      out[i].ballot = Ballot::decode(ob[i]), out[i].sequenceNumber = oseq[i], out[i].ownValuesEnd = oend[i];
+      out[i].dependencies.assign(odeps.begin() + (size_t)i * n_, odeps.begin() + (size_t)(i + 1) * n_);
+    }
+    if (decided) decided->assign(dec.begin(), dec.begin() + nd);
+    return out;
+  }
+
+  // transitionToAcceptPhase (Replica.scala:732-793) at requests[i].at with the given triple; false where the reference
+  // would have died (a CommittedEntry, or an entry with a larger ballot or vote ballot) and nothing was done
+  std::vector<bool> leadAccept(const std::vector<LeadAcceptRequest>& requests) {
+    const int m = (int)requests.size();
+    std::vector<int32_t> leader(m), number(m), at(m), bo(m), key(m), tr(m), seq(m), dend(m), deps((size_t)m * n_, 0);
+    std::vector<uint8_t> isSet(m);
+    for (int i = 0; i < m; ++i) {
+      const LeadAcceptRequest& q = requests[i];
+      leader[i] = q.instance.replicaIndex, number[i] = q.instance.instanceNumber, at[i] = q.at, bo[i] = q.ballotOrdering;
+      key[i] = q.command.key, isSet[i] = q.command.isSet ? 1 : 0, tr[i] = q.tripleId, seq[i] = q.sequenceNumber;
+      dend[i] = q.ownValuesEnd;
+      if (!q.dependencies.empty()) {
+        if ((int)q.dependencies.size() != n_) throw std::invalid_argument("one dependency watermark per replica");
+        std::copy(q.dependencies.begin(), q.dependencies.end(), deps.begin() + (size_t)i * n_);
+      }
+    }
+    const int32_t st = fpx_epx_lead_accept(epx_, m, leader.data(), number.data(), at.data(), bo.data(), key.data(), isSet.data(),
+                                           tr.data(), seq.data(), deps.data(), dend.data());
+    if (st != FPX_EFATAL_PROTOCOL) check(st, "Replica.transitionToAcceptPhase");
+    std::vector<bool> ok(m, true);
+    if (st == FPX_EFATAL_PROTOCOL) {
+      for (int i = 0; i < m; ++i) {  // a skipped message is the one whose entry still is not the AcceptedEntry of this ballot
+        const CmdLogEntry e = cmdLog(requests[i].at, requests[i].instance);
+        ok[i] = e.kind == EntryKind::Accepted && e.voteBallot == Ballot{requests[i].ballotOrdering, requests[i].at} &&
+                e.tripleId == requests[i].tripleId;
+      }
+    }
+    return ok;
   }
 
   CmdLogEntry cmdLog(int replica, Instance instance) {

@@ -21,8 +21,17 @@
 //                      flushes them through ONE Native.epxLeaderReplies call, after which Commit goes to the other
 //                      replicas or Accept to slowQuorumSize - 1 of them.  The actor keeps the defaultToSlowPath and resend
 //                      timers (a fired defaultToSlowPath timer becomes a kind-3 event of the next burst).  Limits: single-key
-//                      commands and Noops (no multi-key lead), no Preparing phase, recovery is answered but not originated
-//                      (a Nack that asks for it, outcome 6, is logged).
+//                      commands and Noops (no multi-key lead); without originateRecovery there is no Preparing phase:
+//                      recovery is answered but not originated (a Nack that asks for it, outcome 6, is logged).
+//
+//                      originateRecovery = true (off by default; with remotePeers, the engine created with recovery = true):
+//                      the actor ORIGINATES an instance's recovery.  A Nack that asks for it (outcome 6) and an instance that
+//                      blocks execution start the reference's recover-instance timer (:1066, 1623-1629, 891-895); when it
+//                      fires, Native.epxRecover is transitionToPreparePhase at this replica with its own Prepare, and the
+//                      Prepare goes to slowQuorumSize - 1 others.  PrepareOks are enqueued and a tick flushes them through
+//                      ONE Native.epxRecoveryReplies call; its decisions are applied in the same flush with Native.epxLead
+//                      (avoidFastPath) or Native.epxLeadAccept, and the PreAccept or Accept is sent.  The actor keeps the
+//                      resend-Prepares timer.  Limits: single-key commands and Noops.
 //
 //                      inboxBurst = true (off by default): what replicas OUTSIDE send this one -- PreAccept, Accept, Prepare,
 //                      Commit -- is enqueued as it arrives and a tick flushes it through ONE Native.epxReplicaInbox call, in
@@ -67,16 +76,22 @@ class GpuEPaxosEngine[Transport <: frankenpaxos.Transport[Transport]](
     config: Config[Transport],
     numKeys: Int = 1 << 10,
     numInstances: Int = 1 << 20,         // instances (leader, number < numInstances) the command logs hold
-    leaderState: Boolean = false         // also keep Replica.leaderStates on the device (GpuEPaxosReplica's remotePeers)
+    leaderState: Boolean = false,        // also keep Replica.leaderStates on the device (GpuEPaxosReplica's remotePeers)
+    recovery: Boolean = false            // ... with the Preparing phase (GpuEPaxosReplica's originateRecovery); needs leaderState
 ) {
   val n: Int = config.n
   val hasLeaderState: Boolean = leaderState
-  val handle: Long = if (leaderState) Native.epxCreateWithLeaderState(n, numKeys, 0, numInstances)
+  val hasRecovery: Boolean = leaderState && recovery
+  val handle: Long = if (hasRecovery) Native.epxCreateWithRecovery(n, numKeys, 0, numInstances)
+                     else if (leaderState) Native.epxCreateWithLeaderState(n, numKeys, 0, numInstances)
                      else Native.epxCreateWithLog(n, numKeys, 0, numInstances)
   if (handle < 0) Native.check((-handle).toInt, logger)
 
   // a command's triple id is its index here (the GPU carries the int32; Accept and Commit name a triple by it)
   val triples = mutable.ArrayBuffer[CommandOrNoop]()
+  // originateRecovery: equal commands get equal triple ids (handlePrepareOk compares the commands of PrepareOks, :1845)
+  private val internedTriples = mutable.Map[CommandOrNoop, Int]()
+  def intern(c: CommandOrNoop): Int = internedTriples.getOrElseUpdate(c, { triples += c; triples.size - 1 })
   // instance -> the dependencies it committed with: n watermarks + the end of the own column's explicit ids (0 = none)
   val depsOf = mutable.Map[(Int, Int), (Array[Int], Int)]()
   // triple id -> the dependencies an Accept carried (the device names an accepted triple by its id alone)
@@ -130,6 +145,12 @@ class GpuEPaxosReplica[Transport <: frankenpaxos.Transport[Transport]](
     // Native.epxReplicaInbox call per flush, in arrival order, instances repeated freely (single-key commands and Noops).
     // Default off: one native call per kind of message, as below.
     inboxBurst: Boolean = false,
+    // true (needs remotePeers and an engine with recovery = true): this actor originates an instance's recovery through
+    // Native.epxRecover / Native.epxRecoveryReplies / Native.epxLeadAccept.  Default off: recovery is answered only.
+    originateRecovery: Boolean = false,
+    prepareOksAsIntended: Boolean = false,   // handlePrepareOk's two tests as the reference's comments describe them (include/fpx.h)
+    recoverInstanceTimerMinPeriod: java.time.Duration = java.time.Duration.ofMillis(500),
+    recoverInstanceTimerMaxPeriod: java.time.Duration = java.time.Duration.ofMillis(1500),
     thrifty: Boolean = true,             // PreAccept / Accept to a thrifty quorum (else to every other replica)
     resendPeriod: java.time.Duration = java.time.Duration.ofSeconds(1),              // resendPreAccepts / resendAccepts
     defaultToSlowPathPeriod: java.time.Duration = java.time.Duration.ofSeconds(1)
@@ -219,6 +240,7 @@ class GpuEPaxosReplica[Transport <: frankenpaxos.Transport[Transport]](
       }
       executedAbove(inst) = pendingDeps.remove(inst).get
     }
+    if (originateRecovery) for (i <- blockers if !recoverTimers.contains(i)) recoverTimers(i) = makeRecoverInstanceTimer(i)   // :891-895
     executables.clear(); blockers.clear()
     for (l <- 0 until n) {                                               // the executed prefixes move up; what lies below them is forgotten
       while (executedAbove.remove(Instance(l, executedPrefix(l))).isDefined) executedPrefix(l) += 1
@@ -227,6 +249,7 @@ class GpuEPaxosReplica[Transport <: frankenpaxos.Transport[Transport]](
   def executeGraph(): Unit = {                                           // :883-917
     if (deviceExecution) { executeGraphOnDevice(); return }
     dependencyGraph.appendExecute(None, executables, blockers)
+    if (originateRecovery) for (i <- blockers if !recoverTimers.contains(i)) recoverTimers(i) = makeRecoverInstanceTimer(i)   // :891-895
     for (i <- executables) {
       committed.remove(i) match {
         case None                => logger.fatal(s"Instance $i is ready for execution but was never committed here.")
@@ -259,7 +282,12 @@ class GpuEPaxosReplica[Transport <: frankenpaxos.Transport[Transport]](
   private val prepares = mutable.Buffer[(Transport#Address, Prepare)]()
   private val commits = mutable.Buffer[Commit]()
   private var queued = 0
-  private val tick = timer("gpuEPaxosTick", java.time.Duration.ZERO, () => { if (inboxBurst) flushPeerInbox(); flushTick() })
+  private val tick = timer("gpuEPaxosTick", java.time.Duration.ZERO, () => {
+    // (PrepareOks first, and their decisions applied, before another burst of any kind reaches the context: include/fpx.h)
+    if (originateRecovery) { flushPrepareOks(); flushRecoveries() }
+    if (inboxBurst) flushPeerInbox()
+    flushTick()
+  })
   private def enqueue[T](q: mutable.Buffer[T], x: T): Unit = { if (queued == 0) tick.start(); q += x; queued += 1 }
 
   override def receive(src: Transport#Address, inbound: ReplicaInbound): Unit = {
@@ -288,6 +316,7 @@ class GpuEPaxosReplica[Transport <: frankenpaxos.Transport[Transport]](
         enqueue(leaderInbox, LeaderEvent(0, r.instance, r.ballot, r.replicaIndex, r.sequenceNumber, Some(r.dependencies)))
       case Request.AcceptOk(r) if remotePeers => enqueue(leaderInbox, LeaderEvent(1, r.instance, r.ballot, r.replicaIndex, 0, None))
       case Request.Nack(r) if remotePeers     => enqueue(leaderInbox, LeaderEvent(2, r.instance, r.largestBallot, index, 0, None))
+      case Request.PrepareOk(r) if originateRecovery => enqueue(prepareOkInbox, r)
       case Request.PreAcceptOk(_) | Request.AcceptOk(_) | Request.PrepareOk(_) | Request.Nack(_) =>
         // replies to a leader role: between hosted replicas they never leave the device; from a replica outside, they
         // belong to a reference Replica that originated the round (see the scope note above)
@@ -323,8 +352,24 @@ class GpuEPaxosReplica[Transport <: frankenpaxos.Transport[Transport]](
   // sees it in the command-log entry the message moved, the timers are stopped here
   private def ballotLt(a: Ballot, b: Ballot): Boolean =
     a.ordering < b.ordering || (a.ordering == b.ordering && a.replicaIndex < b.replicaIndex)
-  private def yieldTo(instance: Instance, ballot: Ballot): Unit =
+  private def yieldTo(instance: Instance, ballot: Ballot): Unit = {
     if (leading.get(instance).exists(l => ballotLt(l.ballot, ballot))) stopLeading(instance)
+    if (originateRecovery && recovering.get(instance).exists(r => ballotLt(r.ballot, ballot))) stopRecovering(instance)
+  }
+
+  // transitionToPreAcceptPhase (:633-729) of a batch of pairwise distinct instances at THIS replica: the one place that
+  // calls Native.epxLead -- for ClientRequests, and for the recoveries that start over (originateRecovery).  Returns the
+  // dependencies of the PreAccepts to send: (m x n watermarks, m values ends)
+  private def leadHere(leader: Array[Int], number: Array[Int], ballotOrdering: Array[Int], key: Array[Int], isSet: Array[Byte],
+                       tripleId: Array[Int], avoidFastPath: Array[Byte]): (Array[Int], Array[Int]) = {
+    val m = leader.length
+    val deps = new Array[Int](m * n); val ends = new Array[Int](m)
+    val st = Native.epxLead(engine.handle, m, n, leader, number, Array.fill(m)(index), ballotOrdering, key, isSet, tripleId,
+                            avoidFastPath, deps, ends)
+    if (st == 9) logger.fatal("transitionToPreAcceptPhase: the instance is committed or known in a larger ballot (:662-682).")
+    Native.check(st, logger)
+    (deps, ends)
+  }
 
   // ClientRequests, led at THIS replica alone: transitionToPreAcceptPhase (:633-729) through Native.epxLead
   private def leadRequests(): Unit = {
@@ -339,11 +384,7 @@ class GpuEPaxosReplica[Transport <: frankenpaxos.Transport[Transport]](
       key(i) = k(0); isSet(i) = if (set) 1 else 0
       engine.triples += CommandOrNoop().withCommand(r.command)
     }
-    val deps = new Array[Int](m * n); val ends = new Array[Int](m)
-    val st = Native.epxLead(engine.handle, m, n, leader, number, Array.fill(m)(index), Array.fill(m)(0), key, isSet,
-                            Array.tabulate(m)(first + _), new Array[Byte](m), deps, ends)
-    if (st == 9) logger.fatal("transitionToPreAcceptPhase: the instance is committed or known in a larger ballot (:662-682).")
-    Native.check(st, logger)
+    val (deps, ends) = leadHere(leader, number, Array.fill(m)(0), key, isSet, Array.tabulate(m)(first + _), new Array[Byte](m))
     val ballot = Ballot(0, index)                                                                               // defaultBallot :453
     for (i <- 0 until m) {
       val instance = Instance(index, number(i))
@@ -381,6 +422,7 @@ class GpuEPaxosReplica[Transport <: frankenpaxos.Transport[Transport]](
                         () => enqueue(leaderInbox, LeaderEvent(3, instance, l.ballot, index, 0, None)))
           t.start(); l.slowPath = Some(t)
         }
+      case 6 if originateRecovery => startOrResetRecoverTimer(ev(i).instance)                                   // :1623-1629
       case 6 => logger.debug(s"GpuEPaxosReplica: Nack for ${ev(i).instance} in a larger ballot; recovery is not originated here.")
       case _ => ()
     }
@@ -410,6 +452,125 @@ class GpuEPaxosReplica[Transport <: frankenpaxos.Transport[Transport]](
     if (decided(0) > 0) executeGraph()
   }
 
+  // ---- originateRecovery: the Preparing phase.  The device keeps the Preparing state and its PrepareOks; what stays here
+  // is the recover-instance timers (:513, 1066-1078), the resend-Prepares timer of an instance being recovered (:1053-1064)
+  // and the interned commands the PrepareOks named.
+  private val prepareOkInbox = mutable.Buffer[PrepareOk]()
+  private val recoverTimers = mutable.Map[Instance, Transport#Timer]()
+  private class Recovering(val ballot: Ballot, val resend: Transport#Timer)
+  private val recovering = mutable.Map[Instance, Recovering]()
+  private val toRecover = mutable.Buffer[Instance]()
+  private val noopTriple: Int = if (originateRecovery) engine.intern(CommandOrNoop().withNoop(Noop())) else -1
+  logger.check(!originateRecovery || (remotePeers && engine.hasRecovery))
+  private def makeRecoverInstanceTimer(instance: Instance): Transport#Timer = {                                  // :1066-1078
+    lazy val t: Transport#Timer = timer(s"recoverInstance $instance",
+      frankenpaxos.Util.randomDuration(recoverInstanceTimerMinPeriod, recoverInstanceTimerMaxPeriod),
+      () => { enqueue(toRecover, instance); t.start() })
+    t.start()
+    t
+  }
+  private def startOrResetRecoverTimer(instance: Instance): Unit = recoverTimers.get(instance) match {
+    case Some(t) => t.reset()
+    case None    => recoverTimers(instance) = makeRecoverInstanceTimer(instance)
+  }
+  // handlePreAccept / handleAccept / handlePrepare reset it (:1249, 1490, 1640); commit stops it (:849-856)
+  private def resetRecoverTimer(instance: Instance): Unit = recoverTimers.get(instance).foreach(_.reset())
+  private def stopRecoverTimer(instance: Instance): Unit = recoverTimers.remove(instance).foreach(_.stop())
+  private def stopRecovering(instance: Instance): Unit = recovering.remove(instance).foreach(_.resend.stop())
+
+  // the recover-instance timers that fired since the last flush: transitionToPreparePhase (:969-996) at this replica, with
+  // its own Prepare, in ONE device call; then the Prepare to slowQuorumSize - 1 others
+  private def flushRecoveries(): Unit = {
+    val inst = toRecover.distinct.toArray                              // (the instances of one call are pairwise distinct)
+    toRecover.clear()
+    val m = inst.length
+    if (m == 0) return
+    val result = new Array[Int](5 * m)
+    val st = Native.epxRecover(engine.handle, m, n, inst.map(_.replicaIndex), inst.map(_.instanceNumber), Array.fill(m)(index), result)
+    if (st == 9) logger.fatal("transitionToPreparePhase: an entry in a ballot not below largestBallot + 1.")
+    Native.check(st, logger)
+    for (i <- 0 until m if result(i) == 0) {                           // (1: committed here -- the Commit went round already)
+      val instance = inst(i)
+      stopLeading(instance); stopRecovering(instance)                  // :970 stopTimers(instance)
+      val ballot = Ballot(result(m + i), index)
+      val prepare = ReplicaInbound().withPrepare(Prepare(instance = instance, ballot = ballot))
+      thriftyOtherReplicas(config.slowQuorumSize - 1).foreach(replicas(_).send(prepare))                          // :978-983
+      recovering(instance) = new Recovering(ballot, resendTimer(s"resendPrepares $instance $ballot", prepare))
+    }
+  }
+
+  // the burst's PrepareOks: ONE device call (handlePrepareOk :1759-1869), and its decisions applied before anything else
+  // reaches the context -- between the two calls the device holds no state for the instance
+  private def flushPrepareOks(): Unit = {
+    val k = prepareOkInbox.size
+    if (k == 0) return
+    val ev = prepareOkInbox.toArray
+    prepareOkInbox.clear()
+    val zeros = Array.fill(n)(0)
+    val status = ev.map(_.status match { case CommandStatus.NotSeen => 0; case CommandStatus.PreAccepted => 2; case _ => 3 })
+    val nul = (b: Ballot) => b.ordering < 0
+    val tripleId = ev.map(e => e.commandOrNoop.map(engine.intern).getOrElse(-1))
+    val deps = ev.zip(status).flatMap { case (e, s) => if (s == 0) zeros else e.dependencies.map(watermarks).getOrElse(zeros) }
+    val ends = ev.zip(status).map { case (e, s) => if (s == 0) 0 else e.dependencies.map(d => ownEnd(e.instance, d)).getOrElse(0) }
+    val outcome = new Array[Int](k); val decision = new Array[Int](5 * k); val outDeps = new Array[Int](k * n)
+    val decided = new Array[Int](k + 1)
+    val st = Native.epxRecoveryReplies(engine.handle, k, n, Array.fill(k)(index), ev.map(_.instance.replicaIndex),
+                                       ev.map(_.instance.instanceNumber), ev.map(_.ballot.ordering), ev.map(_.ballot.replicaIndex),
+                                       ev.map(_.replicaIndex), status, ev.map(e => if (nul(e.voteBallot)) -1 else e.voteBallot.ordering),
+                                       ev.map(e => if (nul(e.voteBallot)) -1 else e.voteBallot.replicaIndex), tripleId,
+                                       ev.map(_.sequenceNumber.getOrElse(0)), deps, ends, if (prepareOksAsIntended) 1 else 0,
+                                       outcome, decision, outDeps, decided)
+    if (st == 9) logger.fatal("a PrepareOk in a ballot above the one recovered in (logger.checkLt :1792).")
+    Native.check(st, logger)
+    val d = (1 to decided(0)).map(decided(_))
+    val (toAccept, toLead) = d.partition(outcome(_) == 2)
+    val ballotOf = (i: Int) => Ballot(decision(2 * k + i) >> 3, decision(2 * k + i) & 7)
+    d.foreach(i => stopRecovering(ev(i).instance))
+    if (toLead.nonEmpty) {                                             // :1856-1867 transitionToPreAcceptPhase, avoidFastPath
+      val m = toLead.size
+      val id = toLead.map(i => if (outcome(i) == 4) noopTriple else decision(k + i)).toArray
+      val cls = id.map(t => engine.classify(engine.triples(t)))
+      if (cls.exists(_._1.exists(_.length != 1))) logger.fatal("GpuEPaxosReplica(originateRecovery): single-key commands and Noops only.")
+      val (lDeps, lEnds) = leadHere(toLead.map(ev(_).instance.replicaIndex).toArray, toLead.map(ev(_).instance.instanceNumber).toArray,
+                                    toLead.map(ballotOf(_).ordering).toArray, cls.map(_._1.map(_(0)).getOrElse(-1)),
+                                    cls.map(c => (if (c._2) 1 else 0).toByte), id, Array.fill(m)(1.toByte))
+      for ((i, j) <- toLead.zipWithIndex) {
+        val instance = ev(i).instance
+        val preAccept = ReplicaInbound().withPreAccept(PreAccept(instance = instance, ballot = ballotOf(i),
+          commandOrNoop = engine.triples(id(j)), sequenceNumber = 0,
+          dependencies = prefixSet(lDeps.slice(j * n, (j + 1) * n), instance.replicaIndex, lEnds(j), instance.instanceNumber)))
+        thriftyOtherReplicas(config.fastQuorumSize - 1).foreach(replicas(_).send(preAccept))
+        leading(instance) = new Leading(ballotOf(i), id(j), resendTimer(s"resendPreAccepts $instance ${ballotOf(i)}", preAccept), None)
+      }
+    }
+    if (toAccept.nonEmpty) {                                           // :1813-1851 transitionToAcceptPhase with the triple
+      val m = toAccept.size
+      val id = toAccept.map(i => decision(k + i)).toArray
+      val cls = id.map(t => engine.classify(engine.triples(t)))
+      if (cls.exists(_._1.exists(_.length != 1))) logger.fatal("GpuEPaxosReplica(originateRecovery): single-key commands and Noops only.")
+      val aDeps = toAccept.flatMap(i => outDeps.slice(i * n, (i + 1) * n)).toArray
+      val aEnds = toAccept.map(i => decision(4 * k + i)).toArray; val aSeq = toAccept.map(i => decision(3 * k + i)).toArray
+      val st2 = Native.epxLeadAccept(engine.handle, m, n, toAccept.map(ev(_).instance.replicaIndex).toArray,
+                                     toAccept.map(ev(_).instance.instanceNumber).toArray, Array.fill(m)(index),
+                                     toAccept.map(ballotOf(_).ordering).toArray, cls.map(_._1.map(_(0)).getOrElse(-1)),
+                                     cls.map(c => (if (c._2) 1 else 0).toByte), id, aSeq, aDeps, aEnds)
+      if (st2 == 9) logger.fatal("transitionToAcceptPhase: the instance is committed or known in a larger ballot (:740-757).")
+      Native.check(st2, logger)
+      for ((i, j) <- toAccept.zipWithIndex) {
+        val instance = ev(i).instance
+        val (l, x) = (instance.replicaIndex, instance.instanceNumber)
+        // the triple's dependencies: the PrepareOk's, or -- the own entry knew its triple by id alone -- the engine's
+        val (w, end) = if (aDeps(j * n) >= 0) (aDeps.slice(j * n, (j + 1) * n), aEnds(j))
+                       else engine.tripleDeps.getOrElse(id(j), (Array.fill(n)(0), 0))
+        engine.tripleDeps(id(j)) = (w, end)
+        val accept = ReplicaInbound().withAccept(Accept(instance = instance, ballot = ballotOf(i), commandOrNoop = engine.triples(id(j)),
+                                                        sequenceNumber = aSeq(j), dependencies = prefixSet(w, l, end, x)))
+        thriftyOtherReplicas(config.slowQuorumSize - 1).foreach(replicas(_).send(accept))
+        leading(instance) = new Leading(ballotOf(i), id(j), resendTimer(s"resendAccepts $instance ${ballotOf(i)}", accept), None)
+      }
+    }
+  }
+
   // ---- inboxBurst: the replica half.  What replicas outside sent since the last flush -- PreAccepts, Accepts, Commits,
   // Prepares, in arrival order -- goes through ONE device call (fpx_epx_replica_inbox), which answers every message as
   // handlePreAccept / handleAccept / handleCommit / handlePrepare would one at a time; then what the handlers would have sent.
@@ -428,13 +589,15 @@ class GpuEPaxosReplica[Transport <: frankenpaxos.Transport[Transport]](
     val ev = peerInbox.toArray
     peerInbox.clear()
     if (remotePeers) for (e <- ev) if (e.kind == 2) stopLeading(e.instance) else yieldTo(e.instance, e.ballot)
+    if (originateRecovery) for (e <- ev) if (e.kind == 2) { stopRecoverTimer(e.instance); stopRecovering(e.instance) } else resetRecoverTimer(e.instance)
     val key = new Array[Int](k); val isSet = new Array[Byte](k); val tripleId = Array.fill(k)(-1)
     val deps = new Array[Int](k * n); val ends = new Array[Int](k)
     for ((e, i) <- ev.zipWithIndex; c <- e.commandOrNoop; d <- e.dependencies) {
       val (ks, set) = engine.classify(c)
       if (ks.exists(_.length != 1)) logger.fatal("GpuEPaxosReplica(inboxBurst): single-key commands and Noops only.")
       key(i) = ks.map(_(0)).getOrElse(-1); isSet(i) = if (set) 1 else 0
-      tripleId(i) = engine.triples.size; engine.triples += c
+      // (originateRecovery: equal commands get equal ids -- the own PrepareOk's triple id meets the peers' in handlePrepareOk)
+      if (originateRecovery) tripleId(i) = engine.intern(c) else { tripleId(i) = engine.triples.size; engine.triples += c }
       val (w, end) = (watermarks(d), ownEnd(e.instance, d))
       // an Accept's or a Commit's dependencies that the command log does not represent stay here; the device names the
       // triple by its id alone (a row starting with -1).  A PreAccept's are checked by the device (FPX_EINVAL).
@@ -486,6 +649,12 @@ class GpuEPaxosReplica[Transport <: frankenpaxos.Transport[Transport]](
       for ((_, p) <- preAccepts) yieldTo(p.instance, p.ballot)
       for ((_, a) <- accepts) yieldTo(a.instance, a.ballot)
       for ((_, p) <- prepares) yieldTo(p.instance, p.ballot)
+    }
+    if (originateRecovery) {
+      for (c <- commits) { stopRecoverTimer(c.instance); stopRecovering(c.instance) }                           // :849-856
+      for ((_, p) <- preAccepts) resetRecoverTimer(p.instance)                                                  // :1249
+      for ((_, a) <- accepts) resetRecoverTimer(a.instance)                                                     // :1490
+      for ((_, p) <- prepares) resetRecoverTimer(p.instance)                                                    // :1640
     }
     // ---- the burst's client requests, led by THIS replica: one pre-accept tick (epaxos/Replica.scala:1121-1157,
     // 633-729, 1159-1419).  The tick's delivery order at every replica is the arrival order here; the PreAccept goes to

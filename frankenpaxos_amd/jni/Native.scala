@@ -224,6 +224,29 @@ object Native {
                               number: Array[Int], ballotOrdering: Array[Int], ballotReplica: Array[Int], key: Array[Int],
                               isSet: Array[Byte], tripleId: Array[Int], deps: Array[Int], depsValuesEnd: Array[Int],
                               outcome: Array[Int], reply: Array[Int], outDeps: Array[Int]): Int
+  // ---- originating an instance's recovery (include/fpx.h, FPX_EPX_F_RECOVERY): a context with leader state AND the
+  // Preparing phase
+  @native def epxCreateWithRecovery(numReplicas: Int, numKeys: Int, device: Int, numInstances: Int): Long
+  // transitionToPreparePhase at replica at(i) with its own Prepare delivered at once (epaxos/Replica.scala:969-996,
+  // 1632-1757).  result (5 x m) = outcome (0 Preparing, 1 the instance is committed here, 2 skipped: fatal in the reference) |
+  // the ballot ordering of the Prepare to send | the own PrepareOk's status | voteBallot (encoded) | triple id
+  @native def epxRecover(handle: Long, m: Int, numReplicas: Int, leader: Array[Int], number: Array[Int], at: Array[Int],
+                         result: Array[Int]): Int
+  // one burst of PrepareOks at hosted replicas, in delivery order (handlePrepareOk :1759-1869).  status 0 NotSeen / 2
+  // PreAccepted / 3 Accepted, vote ballot (-1, -1) = null.  outcome (m): 0 ignored, 1 waiting, 2 Accept phase (epxLeadAccept
+  // with the triple), 3 pre-accept the command of the triple id again, 4 pre-accept a Noop (both: epxLead, avoidFastPath), 5
+  // skipped (fatal in the reference); decision = source | triple id | ballot | sequence number | values end (5 x m) and
+  // outDeps (m x n); decided (m + 1): how many decisions, then their indices.  Apply them BEFORE the next burst of any kind
+  @native def epxRecoveryReplies(handle: Long, m: Int, numReplicas: Int, to: Array[Int], leader: Array[Int], number: Array[Int],
+                                 ballotOrdering: Array[Int], ballotReplica: Array[Int], replicaIndex: Array[Int],
+                                 status: Array[Int], voteBallotOrdering: Array[Int], voteBallotReplica: Array[Int],
+                                 tripleId: Array[Int], sequenceNumber: Array[Int], deps: Array[Int], depsValuesEnd: Array[Int],
+                                 asIntended: Int, outcome: Array[Int], decision: Array[Int], outDeps: Array[Int],
+                                 decided: Array[Int]): Int
+  // transitionToAcceptPhase at replica at(i) in ballot (ballotOrdering(i), at(i)) with the triple given (:732-793)
+  @native def epxLeadAccept(handle: Long, m: Int, numReplicas: Int, leader: Array[Int], number: Array[Int], at: Array[Int],
+                            ballotOrdering: Array[Int], key: Array[Int], isSet: Array[Byte], tripleId: Array[Int],
+                            sequenceNumber: Array[Int], deps: Array[Int], depsValuesEnd: Array[Int]): Int
   // the multi-key forms of epxPreaccept / epxAccept / epxHandleCommit / epxHandlePreaccept: command i's keys are
   // keys(keyOffsets(i) until keyOffsets(i + 1)) (keyOffsets: m + 1 entries from 0), everything else as above
   @native def epxPreacceptMk(handle: Long, m: Int, numReplicas: Int, leader: Array[Int],

@@ -851,6 +851,107 @@ JNIEXPORT jint JNICALL Java_frankenpaxos_gpu_Native_epxReplicaInbox(
   return st;
 }
 
+/* ---- originating an instance's recovery (FPX_EPX_F_RECOVERY, include/fpx.h): the Preparing phase of a hosted replica ------- */
+JNIEXPORT jlong JNICALL Java_frankenpaxos_gpu_Native_epxCreateWithRecovery(JNIEnv* env, jclass cls, jint numReplicas,
+                                                                           jint numKeys, jint device, jint numInstances) {
+  fpx_epx_config cfg = {numReplicas, numKeys, device, FPX_EPX_F_LEADER_STATE | FPX_EPX_F_RECOVERY, numInstances};
+  fpx_epx* e = NULL;
+  int32_t st = fpx_epx_create(&cfg, &e);
+  return st == FPX_OK ? (jlong)(intptr_t)e : -(jlong)st;
+}
+
+/* transitionToPreparePhase at replica at[i] with its own Prepare (epaxos/Replica.scala:969-996, 1632-1757).  Out (may be null):
+ * result = outcome | ballotOrdering | status | voteBallot | tripleId (5 x m) */
+JNIEXPORT jint JNICALL Java_frankenpaxos_gpu_Native_epxRecover(JNIEnv* env, jclass cls, jlong h, jint m, jint numReplicas,
+                                                               jintArray leader, jintArray number, jintArray at,
+                                                               jintArray result) {
+  if (m < 0 || numReplicas < 3 || !epx_n_is(h, numReplicas)) return FPX_EINVAL;
+  if (m == 0) return FPX_OK;
+  if (!has(env, leader, m) || !has(env, number, m) || !has(env, at, m) || !opt(env, result, 5 * (jlong)m)) return FPX_EINVAL;
+  jint *l = in_ints(env, leader, m), *nu = in_ints(env, number, m), *a = in_ints(env, at, m);
+  jint* r = out_buf(result, 5 * (jlong)m, 4);
+  const size_t k = (size_t)m;
+  int32_t st = (!l || !nu || !a || (result && !r))
+                   ? FPX_ENOMEM
+                   : fpx_epx_recover((fpx_epx*)(intptr_t)h, m, l, nu, a, r, r ? r + k : NULL, r ? r + 2 * k : NULL,
+                                     r ? r + 3 * k : NULL, r ? r + 4 * k : NULL);
+  if (st == FPX_OK || st == FPX_EFATAL_PROTOCOL) put_ints(env, result, 5 * (jlong)m, r);
+  free(l); free(nu); free(a); free(r);
+  return st;
+}
+
+/* one burst of PrepareOks at hosted replicas, in delivery order (fpx_epx_recovery_replies).  status 0 / 2 / 3, vote ballot
+ * (-1, -1) = null, deps m x n.  Out (each may be null): outcome m; decision = source | tripleId | ballot | sequenceNumber |
+ * valuesEnd (5 x m); outDeps m x n; decided m + 1 = the number of decisions, then their indices */
+JNIEXPORT jint JNICALL Java_frankenpaxos_gpu_Native_epxRecoveryReplies(
+    JNIEnv* env, jclass cls, jlong h, jint m, jint numReplicas, jintArray to, jintArray leader, jintArray number,
+    jintArray ballotOrdering, jintArray ballotReplica, jintArray replicaIndex, jintArray status, jintArray voteBallotOrdering,
+    jintArray voteBallotReplica, jintArray tripleId, jintArray sequenceNumber, jintArray deps, jintArray depsValuesEnd,
+    jint asIntended, jintArray outcome, jintArray decision, jintArray outDeps, jintArray decided) {
+  if (m < 0 || numReplicas < 3 || !epx_n_is(h, numReplicas)) return FPX_EINVAL;
+  const jlong mn = (jlong)m * numReplicas;
+  if (!opt(env, decided, (jlong)m + 1)) return FPX_EINVAL;
+  if (m == 0) {
+    const jint zero = 0;
+    if (decided) (*env)->SetIntArrayRegion(env, decided, 0, 1, &zero);
+    return FPX_OK;
+  }
+  if (!has(env, to, m) || !has(env, leader, m) || !has(env, number, m) || !has(env, ballotOrdering, m) ||
+      !has(env, ballotReplica, m) || !has(env, replicaIndex, m) || !has(env, status, m) || !has(env, voteBallotOrdering, m) ||
+      !has(env, voteBallotReplica, m) || !has(env, tripleId, m) || !opt(env, sequenceNumber, m) || !has(env, deps, mn) ||
+      !opt(env, depsValuesEnd, m) || !opt(env, outcome, m) || !opt(env, decision, 5 * (jlong)m) || !opt(env, outDeps, mn))
+    return FPX_EINVAL;
+  jint *t = in_ints(env, to, m), *l = in_ints(env, leader, m), *nu = in_ints(env, number, m),
+       *bo = in_ints(env, ballotOrdering, m), *br = in_ints(env, ballotReplica, m), *q = in_ints(env, replicaIndex, m),
+       *s = in_ints(env, status, m), *vo = in_ints(env, voteBallotOrdering, m), *vr = in_ints(env, voteBallotReplica, m),
+       *tr = in_ints(env, tripleId, m), *d = in_ints(env, deps, mn);
+  jint* sq = sequenceNumber ? in_ints(env, sequenceNumber, m) : NULL;
+  jint* de = depsValuesEnd ? in_ints(env, depsValuesEnd, m) : NULL;
+  jint *oc = out_buf(outcome, m, 4), *dn = out_buf(decision, 5 * (jlong)m, 4), *od = out_buf(outDeps, mn, 4),
+       *dc = out_buf(decided, (jlong)m + 1, 4);
+  const size_t k = (size_t)m;
+  int32_t st = (!t || !l || !nu || !bo || !br || !q || !s || !vo || !vr || !tr || !d || (sequenceNumber && !sq) ||
+                (depsValuesEnd && !de) || (outcome && !oc) || (decision && !dn) || (outDeps && !od) || (decided && !dc))
+                   ? FPX_ENOMEM
+                   : fpx_epx_recovery_replies((fpx_epx*)(intptr_t)h, m, t, l, nu, bo, br, q, s, vo, vr, tr, sq, d, de, asIntended,
+                                              oc, dn, dn ? dn + k : NULL, dn ? dn + 2 * k : NULL, dn ? dn + 3 * k : NULL, od,
+                                              dn ? dn + 4 * k : NULL, dc ? dc + 1 : NULL, dc);
+  if (st == FPX_OK || st == FPX_EFATAL_PROTOCOL) {
+    put_ints(env, outcome, m, oc); put_ints(env, decision, 5 * (jlong)m, dn); put_ints(env, outDeps, mn, od);
+    if (dc) put_ints(env, decided, (jlong)dc[0] + 1, dc);
+  }
+  free(t); free(l); free(nu); free(bo); free(br); free(q); free(s); free(vo); free(vr); free(tr); free(d); free(sq); free(de);
+  free(oc); free(dn); free(od); free(dc);
+  return st;
+}
+
+/* transitionToAcceptPhase at replica at[i] with a given triple (epaxos/Replica.scala:732-793): key -1 = Noop; deps m x n (a row
+ * starting with -1: the triple is known by its id alone), sequenceNumber / depsValuesEnd m or null */
+JNIEXPORT jint JNICALL Java_frankenpaxos_gpu_Native_epxLeadAccept(JNIEnv* env, jclass cls, jlong h, jint m, jint numReplicas,
+                                                                  jintArray leader, jintArray number, jintArray at,
+                                                                  jintArray ballotOrdering, jintArray key, jbyteArray isSet,
+                                                                  jintArray tripleId, jintArray sequenceNumber, jintArray deps,
+                                                                  jintArray depsValuesEnd) {
+  if (m < 0 || numReplicas < 3 || !epx_n_is(h, numReplicas)) return FPX_EINVAL;
+  if (m == 0) return FPX_OK;
+  const jlong mn = (jlong)m * numReplicas;
+  if (!has(env, leader, m) || !has(env, number, m) || !has(env, at, m) || !has(env, ballotOrdering, m) || !has(env, key, m) ||
+      !has(env, isSet, m) || !has(env, tripleId, m) || !opt(env, sequenceNumber, m) || !has(env, deps, mn) ||
+      !opt(env, depsValuesEnd, m))
+    return FPX_EINVAL;
+  jint *l = in_ints(env, leader, m), *nu = in_ints(env, number, m), *a = in_ints(env, at, m),
+       *bo = in_ints(env, ballotOrdering, m), *k = in_ints(env, key, m), *tr = in_ints(env, tripleId, m),
+       *d = in_ints(env, deps, mn);
+  jbyte* is = in_bytes(env, isSet, m);
+  jint* sq = sequenceNumber ? in_ints(env, sequenceNumber, m) : NULL;
+  jint* de = depsValuesEnd ? in_ints(env, depsValuesEnd, m) : NULL;
+  int32_t st = (!l || !nu || !a || !bo || !k || !tr || !d || !is || (sequenceNumber && !sq) || (depsValuesEnd && !de))
+                   ? FPX_ENOMEM
+                   : fpx_epx_lead_accept((fpx_epx*)(intptr_t)h, m, l, nu, a, bo, k, (const uint8_t*)is, tr, sq, d, de);
+  free(l); free(nu); free(a); free(bo); free(k); free(tr); free(d); free(is); free(sq); free(de);
+  return st;
+}
+
 /* ---- multi-key get / set commands (the _mk entry points): keyOffsets m + 1, keys keyOffsets[m] (fpx.h) -------------- */
 /* copies the key lists: 0 = a list the library may look at (it checks the rest), else FPX_EINVAL / FPX_ENOMEM */
 static int32_t in_key_lists(JNIEnv* env, jint m, jintArray keyOffsets, jintArray keys, jint** off, jint** k) {

@@ -947,8 +947,8 @@ int32_t fpx_epx_handle_commit_mk(fpx_epx* epx, int32_t m, const int32_t* leader,
 /* ---- the leader half of an instance: hosted replicas that lead among peers in other processes ---------------------
  * FPX_EPX_F_LEADER_STATE in fpx_epx_config.flags (valid only with num_instances > 0, and n * n * num_instances <= 2^31;
  * FPX_EINVAL at fpx_epx_create otherwise): the context keeps Replica.leaderStates (epaxos/Replica.scala:499) per replica and
- * instance beside the command log -- the phase (none / PreAccepting / Accepting; Preparing stays with fpx_epx_prepare and
- * fpx_epx_handle_prepare_oks), the ballot, avoidFastPath, the triple id and the command's key / is_set, who has answered,
+ * instance beside the command log -- the phase (none / PreAccepting / Accepting; Preparing with FPX_EPX_F_RECOVERY, below;
+ * fpx_epx_prepare and fpx_epx_handle_prepare_oks stay the all-replicas-in-one-context form), the ballot, avoidFastPath, the triple id and the command's key / is_set, who has answered,
  * for PreAccepting every response's sequence number and dependencies, for Accepting the triple's.  16 + 4 n (n + 2) bytes
  * per (replica, leader, number): 76 / 156 / 268 B at n = 3 / 5 / 7, n * n * num_instances of them.  Without the flag nothing
  * of it is allocated, the three calls below are FPX_EINVAL and every other call behaves as it always did.
@@ -960,7 +960,7 @@ int32_t fpx_epx_handle_commit_mk(fpx_epx* epx, int32_t m, const int32_t* leader,
  * both as ballot and as vote ballot.  fpx_epx_leader_replies tests that (one gather per instance) before it looks at a
  * state; a state that is not live counts as none.  (fpx_epx_accept PROPOSED by the hosted replica itself in a higher ballot
  * -- a recovery it originates -- moves the entry the same way and so ends the state too, where the reference would replace
- * it by Accepting in the new ballot: originating recovery is outside the leader state.)
+ * it by Accepting in the new ballot: a hosted replica among remote peers originates recovery with fpx_epx_recover instead.)
  *
  * fpx_epx_lead: transitionToPreAcceptPhase (:633-729) at ONE replica.  Message i: instance (leader[i], number[i]) led by
  *   replica at[i] in ballot (ballot_ordering[i], at[i]), command key[i] / is_set[i] (key -1 = Noop), CommandTriple id
@@ -1127,13 +1127,121 @@ int32_t fpx_epx_replica_inbox_dev(fpx_epx* epx, int32_t m, const int32_t* d_kind
                                   const int32_t* d_deps, const int32_t* d_deps_values_end, int32_t* d_outcome,
                                   int32_t* d_out_ballot, int32_t* d_out_status, int32_t* d_out_deps, int32_t* d_out_values_end,
                                   int32_t* d_out_triple);
-/* readback (parity) of one leader state: out[0] = phase (0 none, 1 PreAccepting, 2 Accepting; 0 when the state is not live),
+/* readback (parity) of one leader state: out[0] = phase (0 none, 1 PreAccepting, 2 Accepting, 3 Preparing; 0 when not live),
  * out[1] = ballot, out[2] = avoidFastPath, out[3] = triple id, out[4] = key, out[5] = is_set, out[6] = who has answered (bit
  * q), out[7] = the phase as stored (live or not); responses (may be NULL) n rows of n + 2 ints: row q = sequence number,
  * n watermarks, values_end of what replica q answered (meaningful for the bits of out[6]; Accepting: row `replica` holds
  * the triple's). */
 int32_t fpx_epx_read_leader_state(fpx_epx* epx, int32_t replica, int32_t leader, int32_t number, int32_t out[8],
                                   int32_t* responses);
+/* ---- originating an instance's recovery: the Preparing phase of a hosted replica among remote peers ------------------
+ * FPX_EPX_F_RECOVERY in fpx_epx_config.flags, valid only together with FPX_EPX_F_LEADER_STATE (FPX_EINVAL at
+ * fpx_epx_create otherwise).  The leader state gets a third phase, Preparing (3): per responder q the PrepareOk's status
+ * (0 NotSeen, 2 PreAccepted, 3 Accepted -- fpx_epx_prepare's codes; 2 bits each in the state's head), its voteBallot and
+ * triple id (a side array of 8 n bytes per cell: 24 / 40 / 56 B at n = 3 / 5 / 7) and its sequence number and
+ * dependencies (the response row q that exists already, in canonical form).  Without the flag nothing of it is allocated
+ * and the calls below are FPX_EINVAL.
+ * LIVENESS extends the rule above fpx_epx_lead: a Preparing state is live exactly while the entry at that replica is not
+ * committed and its `ballot` equals the state's.  The vote ballot is not compared: a Prepare moves `ballot` only.  Every
+ * event on which the reference drops a Preparing state -- a higher-ballot PreAccept, Accept or Prepare (:1239-1242,
+ * 1480-1483, 1645-1648), a commit (:831) -- raises the entry's ballot or commits it.
+ *
+ * fpx_epx_recover: transitionToPreparePhase (:969-996) at ONE hosted replica, with that replica's own Prepare.  Message i:
+ *   the instance (leader[i], number[i]) at replica at[i]; array order; the instances of one call pairwise distinct.
+ *   The ballot is Ballot(largestBallot(at).ordering + 1, at), which becomes largestBallot(at); the k-th recovery at one
+ *   replica within a call takes ordering + k.  The reference sends the Prepare "to all replicas, including ourselves";
+ *   the self-addressed one is delivered inside the call (one of its legal schedules), as handlePrepare (:1632-1757):
+ *     a CommittedEntry                FPX_EPX_RV_COMMITTED, no state installed (the net effect of Prepare, the Commit
+ *                                     back, and commit clearing the state); largestBallot stays raised
+ *     no entry / NoCommandEntry       NoCommandEntry(ballot); the own PrepareOk has status 0
+ *     else                            the entry's `ballot` moves; the own PrepareOk carries the entry's status,
+ *                                     voteBallot, triple id and stored dependencies
+ *   and in both of the latter FPX_EPX_RV_PREPARING: the state is Preparing in the new ballot with the own PrepareOk as
+ *   its first response.  An entry whose ballot is not below the new one cannot occur (largestBallot bounds it); if it
+ *   does: FPX_EPX_RV_FATAL, FPX_EFATAL_PROTOCOL, the message is skipped.
+ *   Outputs (any may be NULL): outcome; out_ballot_ordering, the Prepare to send (ballot replica = at[i]); out_status /
+ *   out_vote_ballot (encoded, -1 = null) / out_triple, the own PrepareOk (-1 where there is none).
+ *   FPX_EINVAL, nothing applied: the flag missing, an instance outside the command log, at[i] outside 0..n-1, an instance
+ *   repeated within the call, an ordering that would reach 2^27.
+ *
+ * fpx_epx_recovery_replies: ONE burst of PrepareOks in delivery order, addressed to any hosted replica, answered as
+ *   handlePrepareOk (:1759-1869) would answer them one at a time.  Message i: to[i], the instance, the message's ballot,
+ *   replica_index[i] the sender, status[i] (0 / 2 / 3), the voteBallot (vote_ballot_ordering[i], vote_ballot_replica[i];
+ *   -1, -1 = null), triple_id[i] (equal commands carry equal ids, as everywhere a triple id is taken), and
+ *   sequence_number[i] (NULL = zeros), deps[i * n ..], deps_values_end[i] (NULL = zeros) with the shape and validation of a
+ *   PreAcceptOk of fpx_epx_leader_replies -- not read for status 0.  as_intended has fpx_epx_handle_prepare_oks' meaning:
+ *   0 evaluates the two tests as the reference's code does (the Some(..) compare at :1813 never matches; :1836 reads the
+ *   Prepare's ballot), 1 as its comments describe.
+ *     the state not live or not Preparing, or a ballot below the state's      FPX_EPX_RC_IGNORED
+ *     a ballot above the state's (checkLt :1792)      FPX_EPX_RC_FATAL, FPX_EFATAL_PROTOCOL, skipped, the rest applied
+ *     else responses(replicaIndex) = the message (a later one of a sender replaces the earlier); fewer than f + 1
+ *     responses                                       FPX_EPX_RC_WAITING
+ *     at f + 1 the decision (:1804-1867), over the responses of the maximum voteBallot alone:
+ *       as_intended only: an Accepted one                                   FPX_EPX_RC_ACCEPT with its triple
+ *       as_intended only: Util.popularItems, threshold f, over the PreAccepted ones voted in Ballot(0, leader) from
+ *         senders other than `to`, compared on (triple id, sequence number, dependencies AS SETS, by the own-column rule
+ *         of fpx_epx_leader_replies): a candidate                           FPX_EPX_RC_ACCEPT with it
+ *       a PreAccepted one                      FPX_EPX_RC_PRE_ACCEPT with its triple id
+ *       else                                   FPX_EPX_RC_PRE_ACCEPT_NOOP
+ *     out_source is the lowest replica index that qualifies (fpx_epx_handle_prepare_oks' choice), -1 for the Noop.
+ *   A decision CLEARS the state; the transition itself is the caller's next call: fpx_epx_lead with the recovery's ballot
+ *   ordering and avoid_fast_path = 1 for RC_PRE_ACCEPT (the command filed under the triple id) and RC_PRE_ACCEPT_NOOP (key
+ *   -1), fpx_epx_lead_accept for RC_ACCEPT.
+ *   ORDERING CONTRACT: the caller applies a burst's decisions before it hands the context another burst of any kind for
+ *   those instances.  Between the two calls the state is none, where the reference moved atomically.
+ *   Outputs per message (any may be NULL): outcome, out_source, out_triple (-1 without one), out_ballot (the recovery's
+ *   ballot, encoded, on a decision; else -1), for RC_ACCEPT the triple's out_seq / out_deps (m x n) / out_values_end
+ *   (elsewhere zeros; an own PrepareOk whose entry knew its triple by id alone gives -1 in every column);
+ *   decided_index[0 .. *num_decided) = the indices of the decisions in message order, compacted on the device.
+ *   FPX_EINVAL, nothing applied, no output written: the flag missing, an index or ballot out of range, a status outside
+ *   {0, 2, 3}, malformed dependencies of a status-2/3 message, m >= 2^30.  m = 0 is FPX_OK.
+ * fpx_epx_recovery_replies_dev: device pointers on the context's stream (d_num_decided too); status through fpx_epx_sync.
+ *
+ * fpx_epx_lead_accept: transitionToAcceptPhase (:732-793) at ONE hosted replica with a triple the caller names; host
+ *   pointers, array order, instances pairwise distinct.  A CommittedEntry at at[i], or an entry there with a larger ballot
+ *   or vote ballot, is the reference's fatal / checkLe: FPX_EFATAL_PROTOCOL, the message is skipped.  Else
+ *   AcceptedEntry(ballot, ballot, triple) with the given dependencies (deps[i * n] = -1: by id alone, as an Accept of
+ *   fpx_epx_replica_inbox), updateConflictIndex (the replica may never have seen the instance), and the state becomes
+ *   Accepting with the replica's own AcceptOk and the triple in row at[i].  largestBallot is not touched.  The AcceptOks
+ *   then go through fpx_epx_leader_replies unchanged.  FPX_EINVAL as fpx_epx_lead, and for dependencies an Accept of the
+ *   inbox would refuse.
+ * fpx_epx_read_leader_state reports out[0] = 3 for a live Preparing state; its responses rows are the PrepareOks'
+ * (sequence number, dependencies).  fpx_epx_read_recovery_state: out n x 3 = per responder status, voteBallot (encoded),
+ * triple id; -1, -1, -1 for a replica that has not answered or when the stored phase is not Preparing. */
+#define FPX_EPX_F_RECOVERY 2u
+enum { FPX_EPX_RV_PREPARING = 0, FPX_EPX_RV_COMMITTED = 1, FPX_EPX_RV_FATAL = 2 };
+enum {
+  FPX_EPX_RC_IGNORED = 0,
+  FPX_EPX_RC_WAITING = 1,
+  FPX_EPX_RC_ACCEPT = 2,          /* fpx_epx_lead_accept with the triple given */
+  FPX_EPX_RC_PRE_ACCEPT = 3,      /* fpx_epx_lead, avoid_fast_path = 1, the command of out_triple */
+  FPX_EPX_RC_PRE_ACCEPT_NOOP = 4, /* fpx_epx_lead, avoid_fast_path = 1, a Noop */
+  FPX_EPX_RC_FATAL = 5            /* the reference would have died on this message; it was skipped */
+};
+int32_t fpx_epx_recover(fpx_epx* epx, int32_t m, const int32_t* leader, const int32_t* number, const int32_t* at,
+                        int32_t* outcome, int32_t* out_ballot_ordering, int32_t* out_status, int32_t* out_vote_ballot,
+                        int32_t* out_triple);
+int32_t fpx_epx_recovery_replies(fpx_epx* epx, int32_t m, const int32_t* to, const int32_t* leader, const int32_t* number,
+                                 const int32_t* ballot_ordering, const int32_t* ballot_replica, const int32_t* replica_index,
+                                 const int32_t* status, const int32_t* vote_ballot_ordering,
+                                 const int32_t* vote_ballot_replica, const int32_t* triple_id, const int32_t* sequence_number,
+                                 const int32_t* deps, const int32_t* deps_values_end, int32_t as_intended, int32_t* outcome,
+                                 int32_t* out_source, int32_t* out_triple, int32_t* out_ballot, int32_t* out_seq,
+                                 int32_t* out_deps, int32_t* out_values_end, int32_t* decided_index, int32_t* num_decided);
+int32_t fpx_epx_recovery_replies_dev(fpx_epx* epx, int32_t m, const int32_t* d_to, const int32_t* d_leader,
+                                     const int32_t* d_number, const int32_t* d_ballot_ordering,
+                                     const int32_t* d_ballot_replica, const int32_t* d_replica_index, const int32_t* d_status,
+                                     const int32_t* d_vote_ballot_ordering, const int32_t* d_vote_ballot_replica,
+                                     const int32_t* d_triple_id, const int32_t* d_sequence_number, const int32_t* d_deps,
+                                     const int32_t* d_deps_values_end, int32_t as_intended, int32_t* d_outcome,
+                                     int32_t* d_out_source, int32_t* d_out_triple, int32_t* d_out_ballot, int32_t* d_out_seq,
+                                     int32_t* d_out_deps, int32_t* d_out_values_end, int32_t* d_decided_index,
+                                     int32_t* d_num_decided);
+int32_t fpx_epx_lead_accept(fpx_epx* epx, int32_t m, const int32_t* leader, const int32_t* number, const int32_t* at,
+                            const int32_t* ballot_ordering, const int32_t* key, const uint8_t* is_set,
+                            const int32_t* triple_id, const int32_t* sequence_number, const int32_t* deps,
+                            const int32_t* deps_values_end);
+int32_t fpx_epx_read_recovery_state(fpx_epx* epx, int32_t replica, int32_t leader, int32_t number, int32_t* out);
 /* one command-log entry: out[0..4] = kind, ballot, voteBallot, triple id, the replica's largestBallot */
 int32_t fpx_epx_read_cmdlog(fpx_epx* epx, int32_t replica, int32_t leader, int32_t number, int32_t out[5]);
 /* the dependencies kept with that entry: deps[n] watermarks (deps[0] = -1: known by triple id only), *values_end */
