@@ -1392,6 +1392,8 @@ struct fpx_epx {
   int last_hip = 0;
   DevBuf kv, kv2, seg, conf, tmp, tick, fusedb, metab;
   DevBuf stage;                                            // the arrays of a host-pointer call (host_call)
+  char* held = nullptr;                                    // its held outputs on the host: pageable, grows, never shrinks
+  size_t held_cap = 0;
   DevBuf mk_misc, mk_rec, mk_pair, mk_pconf;               // multi-key commands (fpx_epaxos_mk.hpp)
   int32_t* mk_host = nullptr;                              // page-locked: k_mk_total's line
   DevBuf p_fast, p_deps, p_ldeps, p_own;   // the four output arrays when a packed tick goes the first form's way
@@ -1453,7 +1455,7 @@ int packed_fallback(fpx_epx* e, int m, uint8_t** fast, int32_t** deps, int32_t**
 // ---- host-pointer calls: stage, launch, copy back ------------------------------------------------------------------
 // An array of a host call, carved out of the context's staging buffer: uploaded from `src` when that is not NULL,
 // downloaded to `dst` when that is not NULL, and starting as `fill` bytes (0 or 0xFF; NO_FILL: whatever the buffer held).
-// It is staged either way: an input or output the caller leaves out is device scratch.
+// It is staged either way: an input or output the caller leaves out is device scratch.  (But opt_in.)
 constexpr int NO_FILL = -1;
 constexpr size_t STAGE_ALIGN = 256;  // (what hipMalloc guarantees)
 struct Staged {
@@ -1463,7 +1465,10 @@ struct Staged {
   void* dst;
   size_t bytes;
   int fill;
+  bool hold = false;                // held(): dst gets the array only once the call's status is known
+  const void* length = nullptr;     // held_first(): the slot of the held word that counts the elements dst gets
   size_t span() const { return (bytes + STAGE_ALIGN - 1) & ~(STAGE_ALIGN - 1); }
+  size_t host_span() const { return hold ? (bytes + 7) & ~(size_t)7 : 0; }
 };
 template <typename T>
 Staged arr(T*& d, const void* src, void* dst, size_t count, int fill) {
@@ -1473,25 +1478,53 @@ template <typename T>
 Staged in(T*& d, const void* src, size_t count) {
   return arr(d, src, nullptr, count, NO_FILL);
 }
+// an input the caller may leave out: then it takes no staging space and the kernels see a null pointer
+template <typename T>
+Staged opt_in(T*& d, const void* src, size_t count) {
+  if (src) return in(d, src, count);
+  return {&d, [](void* s, char*) { *static_cast<T**>(s) = nullptr; }, nullptr, nullptr, 0, NO_FILL};
+}
+// an output that is downloaded whatever the call's status
 template <typename T>
 Staged out(T*& d, void* dst, size_t count, int fill = NO_FILL) {
   return arr(d, nullptr, dst, count, fill);
+}
+// an output that reaches `dst` only when the call ends in FPX_OK or FPX_EFATAL_PROTOCOL: a call that ends in FPX_EINVAL
+// leaves the caller's array as it was.  It is downloaded into the context's own host buffer and copied from there.
+template <typename T>
+Staged held(T*& d, T* dst, size_t count) {
+  Staged a = arr(d, nullptr, dst, count, NO_FILL);
+  a.hold = true;
+  return a;
+}
+// a held output of which dst gets the first *n elements only, n being another held word of the call (decided_index)
+inline Staged held_first(int32_t*& d, int32_t* dst, size_t count, int32_t*& n) {
+  Staged a = held(d, dst, count);
+  a.length = &n;
+  return a;
 }
 template <typename T>
 Staged scratch(T*& d, size_t count, int fill = NO_FILL) {
   return arr(d, nullptr, nullptr, count, fill);
 }
 
-// The driver of the host-pointer entry points: grows the staging buffer once to hold every array, carves them in order,
-// uploads the inputs, fills (neighbours with one fill value are one memset), runs launch(), checks the launches, downloads
-// the outputs and returns the device's status.  The host checks of the call come before it: nothing is staged on a bad
-// batch.
+// The driver of the host-pointer entry points: grows the staging buffer once to hold every array (and the host buffer of
+// the held outputs: FPX_ENOMEM with nothing launched), carves them in order, uploads the inputs, fills (neighbours with one
+// fill value are one memset), runs launch(), checks the launches, downloads the outputs, synchronises once and returns the
+// device's status; then the held outputs go to the caller, if the status lets them.  The host checks of the call come
+// before it: nothing is staged on a bad batch.
 template <typename Launch>
 int host_call(fpx_epx* e, std::initializer_list<Staged> arrays, Launch launch) {
-  size_t total = 0;
-  for (const Staged& a : arrays) total += a.span();
+  size_t total = 0, held_total = 0;
+  for (const Staged& a : arrays) total += a.span(), held_total += a.host_span();
   int rc;
   if ((rc = grow(e, &e->stage, total))) return rc;
+  if (held_total > e->held_cap) {
+    char* h = static_cast<char*>(malloc(held_total));
+    if (!h) return FPX_ENOMEM;
+    free(e->held);
+    e->held = h, e->held_cap = held_total;
+  }
   char* const base = (char*)e->stage.p;
   char* p = base;
   for (const Staged& a : arrays) {
@@ -1512,11 +1545,28 @@ int host_call(fpx_epx* e, std::initializer_list<Staged> arrays, Launch launch) {
   if (value != NO_FILL) HIPCHK(e, hipMemsetAsync(run, value, p - run, e->stream));
   if ((rc = launch()) || (rc = launch_check(e))) return rc;
   p = base;
+  char* h = e->held;
   for (const Staged& a : arrays) {
-    if (a.dst && a.bytes) HIPCHK(e, hipMemcpyAsync(a.dst, p, a.bytes, hipMemcpyDeviceToHost, e->stream));
-    p += a.span();
+    void* const to = a.hold ? h : a.dst;  // (a held output is downloaded whether the caller wants it or not: a count may be read)
+    if (to && a.bytes) HIPCHK(e, hipMemcpyAsync(to, p, a.bytes, hipMemcpyDeviceToHost, e->stream));
+    p += a.span(), h += a.host_span();
   }
-  return fpx_epx_sync(e);
+  rc = fpx_epx_sync(e);
+  if (rc != FPX_OK && rc != FPX_EFATAL_PROTOCOL) return rc;
+  auto held_at = [&](const void* slot) {  // where the held array of `slot` lies in e->held
+    const char* at = e->held;
+    for (const Staged& a : arrays) {
+      if (a.hold && a.slot == slot) break;
+      at += a.host_span();
+    }
+    return at;
+  };
+  for (const Staged& a : arrays) {
+    if (!a.hold || !a.dst) continue;
+    const size_t bytes = a.length ? (size_t)*reinterpret_cast<const int32_t*>(held_at(a.length)) * 4 : a.bytes;
+    memcpy(a.dst, held_at(a.slot), bytes);
+  }
+  return rc;
 }
 
 template <int N>
@@ -1552,6 +1602,12 @@ void launch_segments(fpx_epx* e, const EpxBatch& b, const uint32_t* key_totals, 
     hipLaunchKernelGGL(k_epx_segments, dim3((e->st.n * e->st.num_keys + 255) / 256), dim3(256), 0, e->stream, e->st, b);
 }
 
+// the bytes of e->tmp a sort of nseq sequences of m pairs on `bits` bits counts its digits in (radix_sort_pairs)
+size_t radix_sort_bytes(size_t nseq, int m, unsigned bits) {
+  const unsigned passes = (bits + RS_MAXW - 1) / RS_MAXW, width = (bits + passes - 1) / passes;
+  return (nseq * ((m + RS_TILE - 1) / RS_TILE) + nseq) * ((size_t)4 << width);
+}
+
 // stable LSD radix sort of nseq sequences of m pairs on the low `bits` bits of the key word; returns the buffer that
 // holds the result
 uint2* radix_sort_pairs(fpx_epx* e, int nseq, int m, unsigned bits, uint2* a_buf, uint2* b_buf, const int32_t* check_rank, int* rc_out,
@@ -1561,7 +1617,7 @@ uint2* radix_sort_pairs(fpx_epx* e, int nseq, int m, unsigned bits, uint2* a_buf
   const unsigned B = 1u << width;
   RsArgs a;
   a.m = m, a.tiles = (m + RS_TILE - 1) / RS_TILE;
-  *rc_out = grow(e, &e->tmp, ((size_t)n * a.tiles * B + (size_t)n * B) * 4);
+  *rc_out = grow(e, &e->tmp, radix_sort_bytes(n, m, bits));
   if (*rc_out) return nullptr;
   a.hist = (uint32_t*)e->tmp.p, a.tot = a.hist + (size_t)n * a.tiles * B;
   if (!e->sort_lds_allowed) {
@@ -1588,12 +1644,66 @@ uint2* radix_sort_pairs(fpx_epx* e, int nseq, int m, unsigned bits, uint2* a_buf
   return buf[cur];  // where the last pass left the sequence
 }
 
+unsigned key_bits(const fpx_epx* e) {
+  unsigned bits = 1;
+  while ((1u << bits) <= (unsigned)e->st.num_keys) ++bits;
+  return bits;
+}
+
 // the n replicas' sequences of a tick on the key bits
 uint2* sort_by_key(fpx_epx* e, int m, uint2* a_buf, uint2* b_buf, const int32_t* check_rank, int* rc_out,
                    const uint32_t** key_totals, int* key_buckets) {
+  return radix_sort_pairs(e, e->st.n, m, key_bits(e), a_buf, b_buf, check_rank, rc_out, key_totals, key_buckets);
+}
+
+unsigned cell_bits(const fpx_epx* e) {  // the cells of the context: (to, leader, number)
   unsigned bits = 1;
-  while ((1u << bits) <= (unsigned)e->st.num_keys) ++bits;
-  return radix_sort_pairs(e, e->st.n, m, bits, a_buf, b_buf, check_rank, rc_out, key_totals, key_buckets);
+  while (((uint64_t)1 << bits) < (uint64_t)e->st.n * e->st.n * e->st.num_instances) ++bits;
+  return bits;
+}
+
+// a burst's (cell, message index) pairs on the cell bits: a cell's messages become one run, in delivery order
+const uint2* sort_by_cell(fpx_epx* e, int m, uint2* a_buf, uint2* b_buf, int* rc_out) {
+  return radix_sort_pairs(e, 1, m, cell_bits(e), a_buf, b_buf, nullptr, rc_out, nullptr, nullptr);
+}
+
+// the buffers of a conflict scan of m messages at the n replicas (K7's): the sort pairs twice, the rows a tick sees, the
+// key segments, the conflicts
+int grow_conflict_scan(fpx_epx* e, int m) {
+  const int n = e->st.n, NP = n <= 4 ? 4 : 8;
+  const size_t mn = (size_t)m * n;
+  int rc;
+  if ((rc = grow(e, &e->kv, mn * 8))) return rc;
+  if ((rc = grow(e, &e->kv2, mn * 8))) return rc;
+  if ((rc = grow(e, &e->tick, (size_t)n * e->st.num_keys * 2 * n * 4))) return rc;
+  if ((rc = grow(e, &e->seg, (size_t)n * e->st.num_keys * 8))) return rc;
+  return grow(e, &e->conf, mn * NP * 4);
+}
+
+// K7's sort and segments over the pairs the caller's kernels left in e->kv, in array order: *sb is what k_epx_scan takes
+int sort_conflict_scan(fpx_epx* e, int m, const int32_t* number, EpxBatch* sb) {
+  memset(sb, 0, sizeof(*sb));
+  sb->m = m, sb->number = number, sb->kv = (uint2*)e->kv.p;
+  const uint32_t* key_totals = nullptr;
+  int key_buckets = 0, rc;
+  sb->kv_sorted = sort_by_key(e, m, sb->kv, (uint2*)e->kv2.p, nullptr, &rc, &key_totals, &key_buckets);
+  if (rc) return rc;
+  sb->tick = (int32_t*)e->tick.p, sb->seg = (int32_t*)e->seg.p, sb->conf = (int32_t*)e->conf.p;
+  launch_segments(e, *sb, key_totals, key_buckets);
+  return FPX_OK;
+}
+
+// decided_index = the indices of the flagged messages of a burst, in message order, and their number (fpx_epx_leader.hpp);
+// a caller that wants the number alone gets it without the placing
+void launch_compaction(fpx_epx* e, int m, const LrScratch& s, int32_t* d_decided, int32_t* d_num_decided) {
+  if (!d_decided && !d_num_decided) return;
+  LrBatch b;
+  memset(&b, 0, sizeof(b));
+  b.m = m, b.flag = s.flag, b.bsum = s.bsum, b.decided = d_decided, b.blocks = (m + LR_BLOCK - 1) / LR_BLOCK;
+  const dim3 blk(256);
+  hipLaunchKernelGGL(k_lr_count, dim3(b.blocks), blk, 0, e->stream, e->st, b);
+  hipLaunchKernelGGL(k_lr_bscan, dim3(1), blk, 0, e->stream, e->st, b.bsum, b.blocks, (size_t)0, d_num_decided);
+  if (d_decided) hipLaunchKernelGGL(k_lr_compact, dim3(b.blocks), blk, 0, e->stream, e->st, b);
 }
 
 // K5, second form: returns FPX_OK with *done = true when the tick went through it, *done = false when the first
@@ -2000,6 +2110,7 @@ int32_t fpx_epx_destroy(fpx_epx* e) {
                   &e->mk_pair, &e->mk_pconf, &e->lr_misc, &e->ri_misc};
   for (DevBuf* b : bs)
     if (b->p) (void)hipFree(b->p);
+  free(e->held);
   if (e->mk_host) (void)hipHostFree(e->mk_host);
   for (DevBuf* b : {&e->kp_hist, &e->kp_recs, &e->kp_misc, &e->p_fast, &e->p_deps, &e->p_ldeps, &e->p_own, &e->dg_msg, &e->dg_direct,
                     &e->dg_clo, &e->dg_pre, &e->dg_tmax, &e->dg_pairs, &e->dg_pairs2, &e->dg_ctl, &e->dg_key})
@@ -2757,43 +2868,26 @@ int32_t fpx_epx_lead(fpx_epx* e, int32_t m, const int32_t* leader, const int32_t
   if (!leader || !number || !at || !ballot_ordering || !key || !is_set || !triple_id || !avoid_fast_path) return FPX_EINVAL;
   const int n = e->st.n;
   const size_t mn = (size_t)m * n;
-  const int NP = n <= 4 ? 4 : 8;
   int rc;
-  if ((rc = grow(e, &e->kv, mn * 8))) return rc;
-  if ((rc = grow(e, &e->kv2, mn * 8))) return rc;
-  if ((rc = grow(e, &e->tick, (size_t)n * e->st.num_keys * 2 * n * 4))) return rc;
-  if ((rc = grow(e, &e->seg, (size_t)n * e->st.num_keys * 8))) return rc;
-  if ((rc = grow(e, &e->conf, mn * NP * 4))) return rc;
-  const int32_t *d_leader, *d_number, *d_at, *d_bo, *d_key, *d_tr, *d_zero;
-  const uint8_t *d_set, *d_avoid;
-  uint8_t *d_skip, *d_act;
-  int32_t *d_deps, *d_dend, *d_rd, *d_re;
+  if ((rc = grow_conflict_scan(e, m))) return rc;
+  LdBatch lb;
+  memset(&lb, 0, sizeof(lb));
+  lb.m = m, lb.kv = (uint2*)e->kv.p;
+  // K7's "processed" branch at replica at[i] alone, with an empty deps_in: its gate table, its scan, its reply kernel
+  HpBatch hb;
+  memset(&hb, 0, sizeof(hb));
+  hb.m = m, hb.kv = lb.kv;
   auto launch = [&]() -> int {
-    LdBatch lb;
-    memset(&lb, 0, sizeof(lb));
-    lb.m = m, lb.leader = d_leader, lb.number = d_number, lb.b_ord = d_bo, lb.at = d_at, lb.key = d_key, lb.is_set = d_set;
-    lb.triple = d_tr, lb.avoid = d_avoid, lb.deps = d_deps, lb.dend = d_dend, lb.skip = d_skip, lb.act = d_act;
-    lb.kv = (uint2*)e->kv.p, lb.reply_deps = d_rd, lb.reply_end = d_re;
     int rc2;
     if ((rc2 = next_run_id(e, &lb.run_id))) return rc2;
-    // K7's "processed" branch at replica at[i] alone, with an empty deps_in: its gate table, its scan, its reply kernel
-    HpBatch hb;
-    memset(&hb, 0, sizeof(hb));
-    hb.m = m, hb.leader = d_leader, hb.number = d_number, hb.b_ord = d_bo, hb.b_rep = d_at, hb.key = d_key, hb.is_set = d_set;
-    hb.triple = d_tr, hb.deps_in = d_zero, hb.reply_deps = d_rd, hb.reply_end = d_re, hb.act = d_act, hb.kv = lb.kv;
-    hb.conf = (int32_t*)e->conf.p, hb.tick = (int32_t*)e->tick.p;
+    hb.leader = lb.leader, hb.number = lb.number, hb.b_ord = lb.b_ord, hb.b_rep = lb.at, hb.key = lb.key, hb.is_set = lb.is_set;
+    hb.triple = lb.triple, hb.act = lb.act, lb.reply_deps = hb.reply_deps, lb.reply_end = hb.reply_end;
     const dim3 gm((m + 255) / 256), gmn((unsigned)(((long long)m * n + 255) / 256)), blk(256);
     hipLaunchKernelGGL(k_ld_validate, gm, blk, 0, e->stream, e->st, lb);
     hipLaunchKernelGGL(k_ld_gate, gmn, blk, 0, e->stream, e->st, lb);
     EpxBatch sb;
-    memset(&sb, 0, sizeof(sb));
-    sb.m = m, sb.number = d_number, sb.kv = hb.kv;
-    const uint32_t* key_totals = nullptr;
-    int key_buckets = 0;
-    sb.kv_sorted = sort_by_key(e, m, hb.kv, (uint2*)e->kv2.p, nullptr, &rc2, &key_totals, &key_buckets);
-    if (rc2) return rc2;
-    sb.tick = (int32_t*)e->tick.p, sb.seg = (int32_t*)e->seg.p, sb.conf = (int32_t*)e->conf.p;
-    launch_segments(e, sb, key_totals, key_buckets);
+    if ((rc2 = sort_conflict_scan(e, m, lb.number, &sb))) return rc2;
+    hb.conf = sb.conf, hb.tick = sb.tick;
     by_n(n, [&](auto N) {
       launch_hp<N>(e, sb, hb);
       hipLaunchKernelGGL((k_ld_install<N>), gm, blk, 0, e->stream, e->st, e->ls, lb);
@@ -2802,35 +2896,16 @@ int32_t fpx_epx_lead(fpx_epx* e, int32_t m, const int32_t* leader, const int32_t
     hipLaunchKernelGGL(k_hp_commit, dim3((unsigned)((tot + 255) / 256)), blk, 0, e->stream, e->st, hb);
     return FPX_OK;
   };
-  // the outputs reach the caller only on FPX_OK / FPX_EFATAL_PROTOCOL: FPX_EINVAL leaves the caller's arrays as they were
-  std::vector<int32_t> tmp;
-  try {
-    tmp.resize(mn + (size_t)m);
-  } catch (const std::bad_alloc&) {  // (no exception crosses the C ABI)
-    return FPX_ENOMEM;
-  }
-  rc = host_call(e, {in(d_leader, leader, m), in(d_number, number, m), in(d_at, at, m), in(d_bo, ballot_ordering, m),
-                     in(d_key, key, m), in(d_tr, triple_id, m), in(d_set, is_set, m), in(d_avoid, avoid_fast_path, m),
-                     scratch(d_zero, mn, 0), scratch(d_skip, m, 0), out(d_deps, tmp.data(), mn), out(d_dend, tmp.data() + mn, m),
-                     scratch(d_act, mn), scratch(d_rd, mn * n), scratch(d_re, mn)},
-                 launch);
-  if (rc != FPX_OK && rc != FPX_EFATAL_PROTOCOL) return rc;
-  if (deps) memcpy(deps, tmp.data(), mn * 4);
-  if (deps_values_end) memcpy(deps_values_end, tmp.data() + mn, (size_t)m * 4);
-  return rc;
+  return host_call(e, {in(lb.leader, leader, m), in(lb.number, number, m), in(lb.at, at, m), in(lb.b_ord, ballot_ordering, m),
+                       in(lb.key, key, m), in(lb.triple, triple_id, m), in(lb.is_set, is_set, m), in(lb.avoid, avoid_fast_path, m),
+                       scratch(hb.deps_in, mn, 0), scratch(lb.skip, m, 0), held(lb.deps, deps, mn), held(lb.dend, deps_values_end, m),
+                       scratch(lb.act, mn), scratch(hb.reply_deps, mn * n), scratch(hb.reply_end, mn)},
+                   launch);
 }
 
-static int32_t leader_replies_launch(fpx_epx* e, int32_t m, const int32_t* d_kind, const int32_t* d_to, const int32_t* d_leader,
-                                     const int32_t* d_number, const int32_t* d_bo, const int32_t* d_br, const int32_t* d_ridx,
-                                     const int32_t* d_seq, const int32_t* d_deps, const int32_t* d_dend, int32_t* d_outcome,
-                                     int32_t* d_out_seq, int32_t* d_out_deps, int32_t* d_out_end, int32_t* d_out_triple,
-                                     int32_t* d_decided, int32_t* d_num_decided) {
-  const int n = e->st.n;
-  LrBatch b;
-  memset(&b, 0, sizeof(b));
-  b.m = m, b.kind = d_kind, b.to = d_to, b.leader = d_leader, b.number = d_number, b.b_ord = d_bo, b.b_rep = d_br, b.ridx = d_ridx;
-  b.seq = d_seq, b.deps = d_deps, b.dend = d_dend, b.outcome = d_outcome, b.out_seq = d_out_seq, b.out_deps = d_out_deps;
-  b.out_end = d_out_end, b.out_triple = d_out_triple, b.decided = d_decided, b.num_decided = d_num_decided;
+// b: the messages and the outputs (any of which may be null); the scratch fields are filled here
+static int32_t leader_replies_launch(fpx_epx* e, LrBatch b) {
+  const int m = b.m;
   b.blocks = (m + LR_BLOCK - 1) / LR_BLOCK;
   int rc;
   if ((rc = grow(e, &e->kv, (size_t)m * 8))) return rc;
@@ -2840,16 +2915,10 @@ static int32_t leader_replies_launch(fpx_epx* e, int32_t m, const int32_t* d_kin
   b.kv = (uint2*)e->kv.p, b.flag = ls.flag, b.bsum = ls.bsum;
   const dim3 gm((m + 255) / 256), blk(256);
   hipLaunchKernelGGL(k_lr_validate, gm, blk, 0, e->stream, e->st, b);
-  unsigned bits = 1;  // the cells of the context: (to, leader, number)
-  while (((uint64_t)1 << bits) < (uint64_t)n * n * e->st.num_instances) ++bits;
-  b.sorted = radix_sort_pairs(e, 1, m, bits, b.kv, (uint2*)e->kv2.p, nullptr, &rc, nullptr, nullptr);
+  b.sorted = sort_by_cell(e, m, b.kv, (uint2*)e->kv2.p, &rc);
   if (rc) return rc;
-  by_n(n, [&](auto N) { hipLaunchKernelGGL((k_lr_walk<N>), gm, blk, 0, e->stream, e->st, e->ls, b); });
-  if (d_decided || d_num_decided) {
-    hipLaunchKernelGGL(k_lr_count, dim3(b.blocks), blk, 0, e->stream, e->st, b);
-    hipLaunchKernelGGL(k_lr_bscan, dim3(1), blk, 0, e->stream, e->st, b);
-    if (d_decided) hipLaunchKernelGGL(k_lr_compact, dim3(b.blocks), blk, 0, e->stream, e->st, b);
-  }
+  by_n(e->st.n, [&](auto N) { hipLaunchKernelGGL((k_lr_walk<N>), gm, blk, 0, e->stream, e->st, e->ls, b); });
+  launch_compaction(e, m, ls, b.decided, b.num_decided);
   return FPX_OK;
 }
 
@@ -2867,9 +2936,13 @@ int32_t fpx_epx_leader_replies_dev(fpx_epx* e, int32_t m, const int32_t* d_kind,
   }
   if (!d_kind || !d_to || !d_leader || !d_number || !d_ballot_ordering || !d_ballot_replica || !d_replica_index || !d_deps)
     return FPX_EINVAL;
-  int rc = leader_replies_launch(e, m, d_kind, d_to, d_leader, d_number, d_ballot_ordering, d_ballot_replica, d_replica_index,
-                                 d_sequence_number, d_deps, d_deps_values_end, d_outcome, d_out_seq, d_out_deps, d_out_values_end,
-                                 d_out_triple, d_decided_index, d_num_decided);
+  LrBatch b;
+  memset(&b, 0, sizeof(b));
+  b.m = m, b.kind = d_kind, b.to = d_to, b.leader = d_leader, b.number = d_number, b.b_ord = d_ballot_ordering;
+  b.b_rep = d_ballot_replica, b.ridx = d_replica_index, b.seq = d_sequence_number, b.deps = d_deps, b.dend = d_deps_values_end;
+  b.outcome = d_outcome, b.out_seq = d_out_seq, b.out_deps = d_out_deps, b.out_end = d_out_values_end, b.out_triple = d_out_triple;
+  b.decided = d_decided_index, b.num_decided = d_num_decided;
+  int rc = leader_replies_launch(e, b);
   return rc ? rc : launch_check(e);
 }
 
@@ -2886,94 +2959,43 @@ int32_t fpx_epx_leader_replies(fpx_epx* e, int32_t m, const int32_t* kind, const
   }
   if (!kind || !to || !leader || !number || !ballot_ordering || !ballot_replica || !replica_index || !deps) return FPX_EINVAL;
   const size_t mn = (size_t)m * e->st.n;
-  const int32_t *d_kind, *d_to, *d_leader, *d_number, *d_bo, *d_br, *d_ridx, *d_seq, *d_deps, *d_dend;
-  int32_t *d_outcome, *d_oseq, *d_odeps, *d_oend, *d_otr, *d_dec, *d_nd;
-  auto launch = [&]() -> int {
-    return leader_replies_launch(e, m, d_kind, d_to, d_leader, d_number, d_bo, d_br, d_ridx, sequence_number ? d_seq : nullptr,
-                                 d_deps, deps_values_end ? d_dend : nullptr, d_outcome, d_oseq, d_odeps, d_oend, d_otr, d_dec, d_nd);
-  };
-  // an output is downloaded only on FPX_OK / FPX_EFATAL_PROTOCOL: FPX_EINVAL leaves the caller's arrays as they were
-  int32_t *h_outcome = nullptr, *h_oseq = nullptr, *h_odeps = nullptr, *h_oend = nullptr, *h_otr = nullptr, *h_dec = nullptr;
-  std::vector<int32_t> tmp;
-  try {
-    tmp.resize(5 * (size_t)m + mn + 1);
-  } catch (const std::bad_alloc&) {  // (no exception crosses the C ABI)
-    return FPX_ENOMEM;
-  }
-  h_outcome = tmp.data(), h_oseq = h_outcome + m, h_oend = h_oseq + m, h_otr = h_oend + m, h_dec = h_otr + m, h_odeps = h_dec + m;
-  int32_t* h_nd = h_odeps + mn;
-  const int rc = host_call(e, {in(d_kind, kind, m), in(d_to, to, m), in(d_leader, leader, m), in(d_number, number, m),
-                               in(d_bo, ballot_ordering, m), in(d_br, ballot_replica, m), in(d_ridx, replica_index, m),
-                               in(d_seq, sequence_number, m), in(d_dend, deps_values_end, m), in(d_deps, deps, mn),
-                               out(d_outcome, h_outcome, m), out(d_oseq, h_oseq, m), out(d_oend, h_oend, m), out(d_otr, h_otr, m),
-                               out(d_dec, h_dec, m), out(d_odeps, h_odeps, mn), out(d_nd, h_nd, 1)},
-                           launch);
-  if (rc != FPX_OK && rc != FPX_EFATAL_PROTOCOL) return rc;
-  if (outcome) memcpy(outcome, h_outcome, (size_t)m * 4);
-  if (out_seq) memcpy(out_seq, h_oseq, (size_t)m * 4);
-  if (out_values_end) memcpy(out_values_end, h_oend, (size_t)m * 4);
-  if (out_triple) memcpy(out_triple, h_otr, (size_t)m * 4);
-  if (out_deps) memcpy(out_deps, h_odeps, mn * 4);
-  if (decided_index) memcpy(decided_index, h_dec, (size_t)*h_nd * 4);
-  if (num_decided) *num_decided = *h_nd;
-  return rc;
+  LrBatch b;
+  memset(&b, 0, sizeof(b));
+  b.m = m;
+  return host_call(e, {in(b.kind, kind, m), in(b.to, to, m), in(b.leader, leader, m), in(b.number, number, m),
+                       in(b.b_ord, ballot_ordering, m), in(b.b_rep, ballot_replica, m), in(b.ridx, replica_index, m),
+                       opt_in(b.seq, sequence_number, m), opt_in(b.dend, deps_values_end, m), in(b.deps, deps, mn),
+                       held(b.outcome, outcome, m), held(b.out_seq, out_seq, m), held(b.out_end, out_values_end, m),
+                       held(b.out_triple, out_triple, m), held_first(b.decided, decided_index, m, b.num_decided),
+                       held(b.out_deps, out_deps, mn), held(b.num_decided, num_decided, 1)},
+                   [&]() -> int { return leader_replies_launch(e, b); });
 }
 
 // ---- the replica half, a burst at a time: csrc/fpx_epx_inbox.hpp -------------------------------------------------------------
-static int32_t replica_inbox_launch(fpx_epx* e, int32_t m, const int32_t* d_kind, const int32_t* d_to, const int32_t* d_leader,
-                                    const int32_t* d_number, const int32_t* d_bo, const int32_t* d_br, const int32_t* d_key,
-                                    const uint8_t* d_set, const int32_t* d_tr, const int32_t* d_deps, const int32_t* d_dend,
-                                    int32_t* d_outcome, int32_t* d_oballot, int32_t* d_ostatus, int32_t* d_odeps, int32_t* d_oend,
-                                    int32_t* d_otriple) {
-  const int n = e->st.n, NP = n <= 4 ? 4 : 8;
+// b: the messages and the outputs (any of which may be null); the scratch fields are filled here
+static int32_t replica_inbox_launch(fpx_epx* e, RiBatch b) {
+  const int m = b.m, n = e->st.n;
   const int tiles = (m + CL_TILE - 1) / CL_TILE;
-  const size_t mn = (size_t)m * n;
   int rc;
-  if ((rc = grow(e, &e->kv, mn * 8))) return rc;
-  if ((rc = grow(e, &e->kv2, mn * 8))) return rc;
-  if ((rc = grow(e, &e->tick, (size_t)n * e->st.num_keys * 2 * n * 4))) return rc;
-  if ((rc = grow(e, &e->seg, (size_t)n * e->st.num_keys * 8))) return rc;
-  if ((rc = grow(e, &e->conf, mn * NP * 4))) return rc;
+  if ((rc = grow_conflict_scan(e, m))) return rc;
   EpxInboxScratch s;
   if ((rc = carve(e, &e->ri_misc, &s, [&](Carver& c) { return lay_epx_inbox(c, m, n, tiles); }))) return rc;
-  RiBatch b;
-  memset(&b, 0, sizeof(b));
-  b.m = m, b.kind = d_kind, b.to = d_to, b.leader = d_leader, b.number = d_number, b.b_ord = d_bo, b.b_rep = d_br, b.key = d_key;
-  b.is_set = d_set, b.triple = d_tr, b.deps = d_deps, b.dend = d_dend, b.outcome = d_outcome, b.out_ballot = d_oballot;
-  b.out_status = d_ostatus, b.out_deps = d_odeps, b.out_end = d_oend, b.out_triple = d_otriple;
   b.ckv = (uint2*)s.cell[0], b.kv = (uint2*)e->kv.p, b.contrib = s.contrib, b.nackflag = s.nackflag, b.src = s.src, b.last = s.last;
   b.conf = (int32_t*)e->conf.p;
   const dim3 gm((m + 255) / 256), blk(256);
   hipLaunchKernelGGL(k_ri_validate, gm, blk, 0, e->stream, e->st, b);
-  unsigned bits = 1;  // the cells of the context: (to, leader, number)
-  while (((uint64_t)1 << bits) < (uint64_t)n * n * e->st.num_instances) ++bits;
-  {
-    // both sorts of the call count their digits in e->tmp: it has its final size before the first one is enqueued
-    unsigned kbits = 1;
-    while ((1u << kbits) <= (unsigned)e->st.num_keys) ++kbits;
-    auto hist_bytes = [&](size_t nseq, unsigned sort_bits) {
-      const unsigned passes = (sort_bits + RS_MAXW - 1) / RS_MAXW, width = (sort_bits + passes - 1) / passes;
-      return (nseq * ((m + RS_TILE - 1) / RS_TILE) + nseq) * ((size_t)4 << width);
-    };
-    if ((rc = grow(e, &e->tmp, std::max(hist_bytes(1, bits), hist_bytes(n, kbits))))) return rc;
-  }
-  b.sorted = radix_sort_pairs(e, 1, m, bits, b.ckv, (uint2*)s.cell[1], nullptr, &rc, nullptr, nullptr);
+  // both sorts of the call count their digits in e->tmp: it has its final size before the first one is enqueued
+  if ((rc = grow(e, &e->tmp, std::max(radix_sort_bytes(1, m, cell_bits(e)), radix_sort_bytes(n, m, key_bits(e)))))) return rc;
+  b.sorted = sort_by_cell(e, m, b.ckv, (uint2*)s.cell[1], &rc);
   if (rc) return rc;
   by_n(n, [&](auto N) { hipLaunchKernelGGL((k_ri_walk<N>), gm, blk, 0, e->stream, e->st, b); });
   // the conflict scan of what each replica looks up and puts, in array order: K7's sort / segments / scan
   EpxBatch sb;
-  memset(&sb, 0, sizeof(sb));
-  sb.m = m, sb.number = d_number, sb.kv = b.kv;
-  const uint32_t* key_totals = nullptr;
-  int key_buckets = 0;
-  sb.kv_sorted = sort_by_key(e, m, b.kv, (uint2*)e->kv2.p, nullptr, &rc, &key_totals, &key_buckets);
-  if (rc) return rc;
-  sb.tick = (int32_t*)e->tick.p, sb.seg = (int32_t*)e->seg.p, sb.conf = (int32_t*)e->conf.p;
-  launch_segments(e, sb, key_totals, key_buckets);
+  if ((rc = sort_conflict_scan(e, m, b.number, &sb))) return rc;
   // the largestBallot every Nack carries: prefix max per replica over the ballots it took in (as for Prepare / Accept)
   ClBatch cb;
   memset(&cb, 0, sizeof(cb));
-  cb.m = m, cb.contrib = s.contrib, cb.nackflag = s.nackflag, cb.tilemax = s.tilemax, cb.nack_ballot = d_oballot;
+  cb.m = m, cb.contrib = s.contrib, cb.nackflag = s.nackflag, cb.tilemax = s.tilemax, cb.nack_ballot = b.out_ballot;
   hipLaunchKernelGGL(k_cl_tilemax, dim3(tiles, n), blk, 0, e->stream, cb, tiles);
   hipLaunchKernelGGL(k_cl_tilescan, dim3(n), blk, 0, e->stream, e->st, cb, tiles);
   hipLaunchKernelGGL(k_cl_nacks, dim3(tiles, n), blk, 0, e->stream, cb, tiles);
@@ -3009,9 +3031,13 @@ int32_t fpx_epx_replica_inbox_dev(fpx_epx* e, int32_t m, const int32_t* d_kind, 
   if (!d_kind || !d_to || !d_leader || !d_number || !d_ballot_ordering || !d_ballot_replica || !d_key || !d_is_set || !d_triple_id ||
       !d_deps)
     return FPX_EINVAL;
-  int rc = replica_inbox_launch(e, m, d_kind, d_to, d_leader, d_number, d_ballot_ordering, d_ballot_replica, d_key, d_is_set,
-                                d_triple_id, d_deps, d_deps_values_end, d_outcome, d_out_ballot, d_out_status, d_out_deps,
-                                d_out_values_end, d_out_triple);
+  RiBatch b;
+  memset(&b, 0, sizeof(b));
+  b.m = m, b.kind = d_kind, b.to = d_to, b.leader = d_leader, b.number = d_number, b.b_ord = d_ballot_ordering;
+  b.b_rep = d_ballot_replica, b.key = d_key, b.is_set = d_is_set, b.triple = d_triple_id, b.deps = d_deps, b.dend = d_deps_values_end;
+  b.outcome = d_outcome, b.out_ballot = d_out_ballot, b.out_status = d_out_status, b.out_deps = d_out_deps;
+  b.out_end = d_out_values_end, b.out_triple = d_out_triple;
+  int rc = replica_inbox_launch(e, b);
   return rc ? rc : launch_check(e);
 }
 
@@ -3026,35 +3052,17 @@ int32_t fpx_epx_replica_inbox(fpx_epx* e, int32_t m, const int32_t* kind, const 
   if (!kind || !to || !leader || !number || !ballot_ordering || !ballot_replica || !key || !is_set || !triple_id || !deps)
     return FPX_EINVAL;
   const size_t mn = (size_t)m * e->st.n;
-  const int32_t *d_kind, *d_to, *d_leader, *d_number, *d_bo, *d_br, *d_key, *d_tr, *d_deps, *d_dend;
-  const uint8_t* d_set;
-  int32_t *d_outcome, *d_ob, *d_os, *d_odeps, *d_oend, *d_otr;
-  auto launch = [&]() -> int {
-    return replica_inbox_launch(e, m, d_kind, d_to, d_leader, d_number, d_bo, d_br, d_key, d_set, d_tr, d_deps,
-                                deps_values_end ? d_dend : nullptr, d_outcome, d_ob, d_os, d_odeps, d_oend, d_otr);
-  };
-  // an output is downloaded only on FPX_OK: FPX_EINVAL leaves the caller's arrays as they were
-  std::vector<int32_t> tmp;
-  try {
-    tmp.resize(5 * (size_t)m + mn);
-  } catch (const std::bad_alloc&) {  // (no exception crosses the C ABI)
-    return FPX_ENOMEM;
-  }
-  int32_t *h_outcome = tmp.data(), *h_ob = h_outcome + m, *h_os = h_ob + m, *h_oend = h_os + m, *h_otr = h_oend + m, *h_odeps = h_otr + m;
-  const int rc = host_call(e, {in(d_kind, kind, m), in(d_to, to, m), in(d_leader, leader, m), in(d_number, number, m),
-                               in(d_bo, ballot_ordering, m), in(d_br, ballot_replica, m), in(d_key, key, m), in(d_tr, triple_id, m),
-                               in(d_dend, deps_values_end, m), in(d_deps, deps, mn), in(d_set, is_set, m),
-                               out(d_outcome, h_outcome, m), out(d_ob, h_ob, m), out(d_os, h_os, m), out(d_oend, h_oend, m),
-                               out(d_otr, h_otr, m), out(d_odeps, h_odeps, mn)},
-                           launch);
-  if (rc != FPX_OK) return rc;
-  if (outcome) memcpy(outcome, h_outcome, (size_t)m * 4);
-  if (out_ballot) memcpy(out_ballot, h_ob, (size_t)m * 4);
-  if (out_status) memcpy(out_status, h_os, (size_t)m * 4);
-  if (out_values_end) memcpy(out_values_end, h_oend, (size_t)m * 4);
-  if (out_triple) memcpy(out_triple, h_otr, (size_t)m * 4);
-  if (out_deps) memcpy(out_deps, h_odeps, mn * 4);
-  return rc;
+  RiBatch b;
+  memset(&b, 0, sizeof(b));
+  b.m = m;
+  // (the held outputs reach the caller on FPX_OK and FPX_EFATAL_PROTOCOL; these kernels raise nothing but FPX_EINVAL, so
+  // here that is: on FPX_OK alone)
+  return host_call(e, {in(b.kind, kind, m), in(b.to, to, m), in(b.leader, leader, m), in(b.number, number, m),
+                       in(b.b_ord, ballot_ordering, m), in(b.b_rep, ballot_replica, m), in(b.key, key, m), in(b.triple, triple_id, m),
+                       opt_in(b.dend, deps_values_end, m), in(b.deps, deps, mn), in(b.is_set, is_set, m),
+                       held(b.outcome, outcome, m), held(b.out_ballot, out_ballot, m), held(b.out_status, out_status, m),
+                       held(b.out_end, out_values_end, m), held(b.out_triple, out_triple, m), held(b.out_deps, out_deps, mn)},
+                   [&]() -> int { return replica_inbox_launch(e, b); });
 }
 
 int32_t fpx_epx_read_leader_state(fpx_epx* e, int32_t replica, int32_t leader, int32_t number, int32_t out[8],
@@ -3090,83 +3098,43 @@ int32_t fpx_epx_recover(fpx_epx* e, int32_t m, const int32_t* leader, const int3
   if (m == 0) return FPX_OK;
   if (!leader || !number || !at) return FPX_EINVAL;
   const int n = e->st.n;
-  const int32_t *d_leader, *d_number, *d_at;
-  uint32_t* d_rank;
-  int32_t *d_base, *d_count, *d_outcome, *d_ord, *d_os, *d_ov, *d_ot;
+  RvBatch b;
+  memset(&b, 0, sizeof(b));
+  b.m = m;
   auto launch = [&]() -> int {
-    RvBatch b;
-    memset(&b, 0, sizeof(b));
-    b.m = m, b.leader = d_leader, b.number = d_number, b.at = d_at, b.rank = d_rank, b.base = d_base, b.count = d_count;
-    b.outcome = d_outcome, b.out_ord = d_ord, b.out_status = d_os, b.out_vote = d_ov, b.out_triple = d_ot;
-    int rc2;
-    if ((rc2 = next_run_id(e, &b.run_id))) return rc2;
+    int rc;
+    if ((rc = next_run_id(e, &b.run_id))) return rc;
     const dim3 gm((m + 255) / 256), blk(256);
     hipLaunchKernelGGL(k_rv_validate, gm, blk, 0, e->stream, e->st, b);
-    for (int r = 0; r < n; ++r) {  // row r of `rank` to its exclusive scan, its total to count[r]
-      LrBatch sb;
-      memset(&sb, 0, sizeof(sb));
-      sb.bsum = d_rank + (size_t)r * m, sb.blocks = m, sb.num_decided = d_count + r;
-      hipLaunchKernelGGL(k_lr_bscan, dim3(1), blk, 0, e->stream, e->st, sb);
-    }
+    // every row of `rank` to its exclusive scan, row r's total to count[r]
+    hipLaunchKernelGGL(k_lr_bscan, dim3(n), blk, 0, e->stream, e->st, b.rank, m, (size_t)m, b.count);
     hipLaunchKernelGGL(k_rv_base, dim3(1), dim3(64), 0, e->stream, e->st, b);
     by_n(n, [&](auto N) { hipLaunchKernelGGL((k_rv_install<N>), gm, blk, 0, e->stream, e->st, e->ls, b); });
     return FPX_OK;
   };
-  // the outputs reach the caller only on FPX_OK / FPX_EFATAL_PROTOCOL: FPX_EINVAL leaves the caller's arrays as they were
-  std::vector<int32_t> tmp;
-  try {
-    tmp.resize(5 * (size_t)m);
-  } catch (const std::bad_alloc&) {  // (no exception crosses the C ABI)
-    return FPX_ENOMEM;
-  }
-  int32_t *h_outcome = tmp.data(), *h_ord = h_outcome + m, *h_os = h_ord + m, *h_ov = h_os + m, *h_ot = h_ov + m;
-  const int rc = host_call(e, {in(d_leader, leader, m), in(d_number, number, m), in(d_at, at, m), scratch(d_rank, (size_t)m * n),
-                               scratch(d_base, 8), scratch(d_count, 8, 0), out(d_outcome, h_outcome, m), out(d_ord, h_ord, m), out(d_os, h_os, m),
-                               out(d_ov, h_ov, m), out(d_ot, h_ot, m)},
-                           launch);
-  if (rc != FPX_OK && rc != FPX_EFATAL_PROTOCOL) return rc;
-  if (outcome) memcpy(outcome, h_outcome, (size_t)m * 4);
-  if (out_ballot_ordering) memcpy(out_ballot_ordering, h_ord, (size_t)m * 4);
-  if (out_status) memcpy(out_status, h_os, (size_t)m * 4);
-  if (out_vote_ballot) memcpy(out_vote_ballot, h_ov, (size_t)m * 4);
-  if (out_triple) memcpy(out_triple, h_ot, (size_t)m * 4);
-  return rc;
+  return host_call(e, {in(b.leader, leader, m), in(b.number, number, m), in(b.at, at, m), scratch(b.rank, (size_t)m * n),
+                       scratch(b.base, 8), scratch(b.count, 8, 0), held(b.outcome, outcome, m),
+                       held(b.out_ord, out_ballot_ordering, m), held(b.out_status, out_status, m),
+                       held(b.out_vote, out_vote_ballot, m), held(b.out_triple, out_triple, m)},
+                   launch);
 }
 
-static int32_t recovery_replies_launch(fpx_epx* e, int32_t m, const int32_t* d_to, const int32_t* d_leader, const int32_t* d_number,
-                                       const int32_t* d_bo, const int32_t* d_br, const int32_t* d_ridx, const int32_t* d_status,
-                                       const int32_t* d_vo, const int32_t* d_vr, const int32_t* d_tr, const int32_t* d_seq,
-                                       const int32_t* d_deps, const int32_t* d_dend, int32_t as_intended, int32_t* d_outcome,
-                                       int32_t* d_source, int32_t* d_otr, int32_t* d_oballot, int32_t* d_oseq, int32_t* d_odeps,
-                                       int32_t* d_oend, int32_t* d_decided, int32_t* d_num_decided) {
-  const int n = e->st.n;
-  RrBatch b;
-  memset(&b, 0, sizeof(b));
-  b.m = m, b.as_intended = as_intended ? 1 : 0, b.to = d_to, b.leader = d_leader, b.number = d_number, b.b_ord = d_bo, b.b_rep = d_br;
-  b.ridx = d_ridx, b.status = d_status, b.v_ord = d_vo, b.v_rep = d_vr, b.triple = d_tr, b.seq = d_seq, b.deps = d_deps, b.dend = d_dend;
-  b.outcome = d_outcome, b.out_source = d_source, b.out_triple = d_otr, b.out_ballot = d_oballot, b.out_seq = d_oseq;
-  b.out_deps = d_odeps, b.out_end = d_oend;
-  LrBatch cb;  // the compaction of fpx_epx_leader_replies, on this burst's flags
-  memset(&cb, 0, sizeof(cb));
-  cb.m = m, cb.decided = d_decided, cb.num_decided = d_num_decided, cb.blocks = (m + LR_BLOCK - 1) / LR_BLOCK;
+// b: the messages and the outputs (any of which may be null); the scratch fields are filled here
+static int32_t recovery_replies_launch(fpx_epx* e, RrBatch b) {
+  const int m = b.m;
   int rc;
   if ((rc = grow(e, &e->kv, (size_t)m * 8))) return rc;
   if ((rc = grow(e, &e->kv2, (size_t)m * 8))) return rc;
-  LrScratch ls;
-  if ((rc = carve(e, &e->lr_misc, &ls, [&](Carver& c) { return lay_leader_replies(c, m, cb.blocks); }))) return rc;
-  b.kv = (uint2*)e->kv.p, b.flag = ls.flag, cb.flag = ls.flag, cb.bsum = ls.bsum;
+  LrScratch ls;  // the compaction of fpx_epx_leader_replies, on this burst's flags
+  if ((rc = carve(e, &e->lr_misc, &ls, [&](Carver& c) { return lay_leader_replies(c, m, (m + LR_BLOCK - 1) / LR_BLOCK); })))
+    return rc;
+  b.kv = (uint2*)e->kv.p, b.flag = ls.flag;
   const dim3 gm((m + 255) / 256), blk(256);
   hipLaunchKernelGGL(k_rr_validate, gm, blk, 0, e->stream, e->st, b);
-  unsigned bits = 1;  // the cells of the context: (to, leader, number)
-  while (((uint64_t)1 << bits) < (uint64_t)n * n * e->st.num_instances) ++bits;
-  b.sorted = radix_sort_pairs(e, 1, m, bits, b.kv, (uint2*)e->kv2.p, nullptr, &rc, nullptr, nullptr);
+  b.sorted = sort_by_cell(e, m, b.kv, (uint2*)e->kv2.p, &rc);
   if (rc) return rc;
-  by_n(n, [&](auto N) { hipLaunchKernelGGL((k_rr_walk<N>), gm, blk, 0, e->stream, e->st, e->ls, b); });
-  if (d_decided || d_num_decided) {
-    hipLaunchKernelGGL(k_lr_count, dim3(cb.blocks), blk, 0, e->stream, e->st, cb);
-    hipLaunchKernelGGL(k_lr_bscan, dim3(1), blk, 0, e->stream, e->st, cb);
-    if (d_decided) hipLaunchKernelGGL(k_lr_compact, dim3(cb.blocks), blk, 0, e->stream, e->st, cb);
-  }
+  by_n(e->st.n, [&](auto N) { hipLaunchKernelGGL((k_rr_walk<N>), gm, blk, 0, e->stream, e->st, e->ls, b); });
+  launch_compaction(e, m, ls, b.decided, b.num_decided);
   return FPX_OK;
 }
 
@@ -3187,10 +3155,14 @@ int32_t fpx_epx_recovery_replies_dev(fpx_epx* e, int32_t m, const int32_t* d_to,
   if (!d_to || !d_leader || !d_number || !d_ballot_ordering || !d_ballot_replica || !d_replica_index || !d_status ||
       !d_vote_ballot_ordering || !d_vote_ballot_replica || !d_triple_id || !d_deps)
     return FPX_EINVAL;
-  int rc = recovery_replies_launch(e, m, d_to, d_leader, d_number, d_ballot_ordering, d_ballot_replica, d_replica_index, d_status,
-                                   d_vote_ballot_ordering, d_vote_ballot_replica, d_triple_id, d_sequence_number, d_deps,
-                                   d_deps_values_end, as_intended, d_outcome, d_out_source, d_out_triple, d_out_ballot, d_out_seq,
-                                   d_out_deps, d_out_values_end, d_decided_index, d_num_decided);
+  RrBatch b;
+  memset(&b, 0, sizeof(b));
+  b.m = m, b.as_intended = as_intended ? 1 : 0, b.to = d_to, b.leader = d_leader, b.number = d_number, b.b_ord = d_ballot_ordering;
+  b.b_rep = d_ballot_replica, b.ridx = d_replica_index, b.status = d_status, b.v_ord = d_vote_ballot_ordering;
+  b.v_rep = d_vote_ballot_replica, b.triple = d_triple_id, b.seq = d_sequence_number, b.deps = d_deps, b.dend = d_deps_values_end;
+  b.outcome = d_outcome, b.out_source = d_out_source, b.out_triple = d_out_triple, b.out_ballot = d_out_ballot, b.out_seq = d_out_seq;
+  b.out_deps = d_out_deps, b.out_end = d_out_values_end, b.decided = d_decided_index, b.num_decided = d_num_decided;
+  int rc = recovery_replies_launch(e, b);
   return rc ? rc : launch_check(e);
 }
 
@@ -3211,41 +3183,18 @@ int32_t fpx_epx_recovery_replies(fpx_epx* e, int32_t m, const int32_t* to, const
       !vote_ballot_replica || !triple_id || !deps)
     return FPX_EINVAL;
   const size_t mn = (size_t)m * e->st.n;
-  const int32_t *d_to, *d_leader, *d_number, *d_bo, *d_br, *d_ridx, *d_status, *d_vo, *d_vr, *d_tr, *d_seq, *d_deps, *d_dend;
-  int32_t *d_outcome, *d_src, *d_otr, *d_ob, *d_oseq, *d_odeps, *d_oend, *d_dec, *d_nd;
-  auto launch = [&]() -> int {
-    return recovery_replies_launch(e, m, d_to, d_leader, d_number, d_bo, d_br, d_ridx, d_status, d_vo, d_vr, d_tr,
-                                   sequence_number ? d_seq : nullptr, d_deps, deps_values_end ? d_dend : nullptr, as_intended,
-                                   d_outcome, d_src, d_otr, d_ob, d_oseq, d_odeps, d_oend, d_dec, d_nd);
-  };
-  // an output is downloaded only on FPX_OK / FPX_EFATAL_PROTOCOL: FPX_EINVAL leaves the caller's arrays as they were
-  std::vector<int32_t> tmp;
-  try {
-    tmp.resize(7 * (size_t)m + mn + 1);
-  } catch (const std::bad_alloc&) {  // (no exception crosses the C ABI)
-    return FPX_ENOMEM;
-  }
-  int32_t *h_outcome = tmp.data(), *h_src = h_outcome + m, *h_otr = h_src + m, *h_ob = h_otr + m, *h_oseq = h_ob + m;
-  int32_t *h_oend = h_oseq + m, *h_dec = h_oend + m, *h_odeps = h_dec + m, *h_nd = h_odeps + mn;
-  const int rc = host_call(e, {in(d_to, to, m), in(d_leader, leader, m), in(d_number, number, m), in(d_bo, ballot_ordering, m),
-                               in(d_br, ballot_replica, m), in(d_ridx, replica_index, m), in(d_status, status, m),
-                               in(d_vo, vote_ballot_ordering, m), in(d_vr, vote_ballot_replica, m), in(d_tr, triple_id, m),
-                               in(d_seq, sequence_number, m), in(d_dend, deps_values_end, m), in(d_deps, deps, mn),
-                               out(d_outcome, h_outcome, m), out(d_src, h_src, m), out(d_otr, h_otr, m), out(d_ob, h_ob, m),
-                               out(d_oseq, h_oseq, m), out(d_oend, h_oend, m), out(d_dec, h_dec, m), out(d_odeps, h_odeps, mn),
-                               out(d_nd, h_nd, 1)},
-                           launch);
-  if (rc != FPX_OK && rc != FPX_EFATAL_PROTOCOL) return rc;
-  if (outcome) memcpy(outcome, h_outcome, (size_t)m * 4);
-  if (out_source) memcpy(out_source, h_src, (size_t)m * 4);
-  if (out_triple) memcpy(out_triple, h_otr, (size_t)m * 4);
-  if (out_ballot) memcpy(out_ballot, h_ob, (size_t)m * 4);
-  if (out_seq) memcpy(out_seq, h_oseq, (size_t)m * 4);
-  if (out_values_end) memcpy(out_values_end, h_oend, (size_t)m * 4);
-  if (out_deps) memcpy(out_deps, h_odeps, mn * 4);
-  if (decided_index) memcpy(decided_index, h_dec, (size_t)*h_nd * 4);
-  if (num_decided) *num_decided = *h_nd;
-  return rc;
+  RrBatch b;
+  memset(&b, 0, sizeof(b));
+  b.m = m, b.as_intended = as_intended ? 1 : 0;
+  return host_call(e, {in(b.to, to, m), in(b.leader, leader, m), in(b.number, number, m), in(b.b_ord, ballot_ordering, m),
+                       in(b.b_rep, ballot_replica, m), in(b.ridx, replica_index, m), in(b.status, status, m),
+                       in(b.v_ord, vote_ballot_ordering, m), in(b.v_rep, vote_ballot_replica, m), in(b.triple, triple_id, m),
+                       opt_in(b.seq, sequence_number, m), opt_in(b.dend, deps_values_end, m), in(b.deps, deps, mn),
+                       held(b.outcome, outcome, m), held(b.out_source, out_source, m), held(b.out_triple, out_triple, m),
+                       held(b.out_ballot, out_ballot, m), held(b.out_seq, out_seq, m), held(b.out_end, out_values_end, m),
+                       held_first(b.decided, decided_index, m, b.num_decided), held(b.out_deps, out_deps, mn),
+                       held(b.num_decided, num_decided, 1)},
+                   [&]() -> int { return recovery_replies_launch(e, b); });
 }
 
 int32_t fpx_epx_lead_accept(fpx_epx* e, int32_t m, const int32_t* leader, const int32_t* number, const int32_t* at,
@@ -3256,24 +3205,20 @@ int32_t fpx_epx_lead_accept(fpx_epx* e, int32_t m, const int32_t* leader, const 
   if (m == 0) return FPX_OK;
   if (!leader || !number || !at || !ballot_ordering || !key || !is_set || !triple_id || !deps) return FPX_EINVAL;
   const int n = e->st.n;
-  const size_t mn = (size_t)m * n;
-  const int32_t *d_leader, *d_number, *d_at, *d_bo, *d_key, *d_tr, *d_seq, *d_deps, *d_dend;
-  const uint8_t* d_set;
+  LaBatch b;
+  memset(&b, 0, sizeof(b));
+  b.m = m;
   auto launch = [&]() -> int {
-    LaBatch b;
-    memset(&b, 0, sizeof(b));
-    b.m = m, b.leader = d_leader, b.number = d_number, b.at = d_at, b.b_ord = d_bo, b.key = d_key, b.is_set = d_set, b.triple = d_tr;
-    b.seq = sequence_number ? d_seq : nullptr, b.deps = d_deps, b.dend = deps_values_end ? d_dend : nullptr;
-    int rc2;
-    if ((rc2 = next_run_id(e, &b.run_id))) return rc2;
+    int rc;
+    if ((rc = next_run_id(e, &b.run_id))) return rc;
     const dim3 gm((m + 255) / 256), blk(256);
     hipLaunchKernelGGL(k_la_validate, gm, blk, 0, e->stream, e->st, b);
     by_n(n, [&](auto N) { hipLaunchKernelGGL((k_la_install<N>), gm, blk, 0, e->stream, e->st, e->ls, b); });
     return FPX_OK;
   };
-  return host_call(e, {in(d_leader, leader, m), in(d_number, number, m), in(d_at, at, m), in(d_bo, ballot_ordering, m),
-                       in(d_key, key, m), in(d_tr, triple_id, m), in(d_seq, sequence_number, m), in(d_dend, deps_values_end, m),
-                       in(d_deps, deps, mn), in(d_set, is_set, m)},
+  return host_call(e, {in(b.leader, leader, m), in(b.number, number, m), in(b.at, at, m), in(b.b_ord, ballot_ordering, m),
+                       in(b.key, key, m), in(b.triple, triple_id, m), opt_in(b.seq, sequence_number, m),
+                       opt_in(b.dend, deps_values_end, m), in(b.deps, deps, (size_t)m * n), in(b.is_set, is_set, m)},
                    launch);
 }
 

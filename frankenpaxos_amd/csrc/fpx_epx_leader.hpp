@@ -385,11 +385,14 @@ __global__ void __launch_bounds__(256) k_lr_count(const EpxState st, const LrBat
   if (threadIdx.x == 0) b.bsum[blockIdx.x] = all;
 }
 
-__global__ void __launch_bounds__(256) k_lr_bscan(const EpxState st, const LrBatch b) {
+// an array scan: workgroup r rewrites the `len` words of row r (rows `stride` words apart) to their exclusive scan and
+// leaves the row's sum in total[r] (total may be null).  The compaction's block counts are one row, fpx_epx_recover's
+// ranks n.
+__global__ void __launch_bounds__(256) k_lr_bscan(const EpxState st, uint32_t* a, int len, size_t stride, int32_t* total) {
   __shared__ uint32_t lds[SCAN_ARRAY_LDS(256)];
   if (st.status[0] == FPX_EINVAL) return;
-  const uint32_t all = scan_array_excl<ScanSum, 256, 1>(b.bsum, b.blocks, lds);
-  if (threadIdx.x == 0 && b.num_decided) *b.num_decided = (int32_t)all;
+  const uint32_t all = scan_array_excl<ScanSum, 256, 1>(a + blockIdx.x * stride, len, lds);
+  if (threadIdx.x == 0 && total) total[blockIdx.x] = (int32_t)all;
 }
 
 __global__ void __launch_bounds__(256) k_lr_compact(const EpxState st, const LrBatch b) {

@@ -51,8 +51,8 @@ __global__ void __launch_bounds__(256) k_rv_validate(const EpxState st, const Rv
 }
 
 // The k-th recovery of the call at replica r takes ordering(largestBallot(r)) + 1 + k: k is the exclusive scan of row r of
-// `rank`, which k_lr_bscan -- the one-workgroup array scan of the compaction -- takes in place, one launch per replica,
-// leaving the row's total in count[r].  This kernel reads every replica's ordering before any message raises it.
+// `rank`, which k_lr_bscan -- the array scan of the compaction -- takes in place, the n rows in one launch of n workgroups,
+// leaving row r's total in count[r].  This kernel reads every replica's ordering before any message raises it.
 __global__ void __launch_bounds__(64) k_rv_base(const EpxState st, const RvBatch b) {
   const int r = threadIdx.x;
   if (r >= st.n) return;
@@ -139,6 +139,8 @@ struct RrBatch {
   uint2* kv;            // (cell, message index)
   const uint2* sorted;
   uint8_t* flag;        // [m] 1 = a decision
+  int32_t* decided;     // the compaction's (k_lr_*, through an LrBatch of its own)
+  int32_t* num_decided;
 };
 
 __global__ void __launch_bounds__(256) k_rr_validate(const EpxState st, const RrBatch b) {

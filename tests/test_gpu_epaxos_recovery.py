@@ -91,6 +91,46 @@ def test_burst_lengths(m):
         both(n, [rec, ("prepare_oks", burst, as_intended)])
 
 
+@pytest.mark.parametrize("n", [3, 5, 7])
+def test_a_call_of_600_recoveries_ranks_every_replica_in_one_launch(n):
+    # k_lr_bscan scans the n rows of `rank` in one launch, a workgroup per row, 256 flags a step: a call of 600 is three steps
+    # per row with a ragged last one.  at[] is uneven -- replica 0 takes most of the call (more than two steps of ones),
+    # replica 1 nothing at all (a row of zeros, total 0), the others a few each -- so every row has another total and long
+    # stretches of zeros.  Some instances are committed, pre-accepted or were already recovered by an earlier call when the
+    # call meets them (a second recovery of an instance takes a ballot above the first; the SAME instance twice in one call
+    # is FPX_EINVAL by contract, which the call before the last holds against the model on rows of this length).
+    import random
+
+    m, ni = 600, 256
+    rng = random.Random(100 + n)
+    insts = rng.sample([(L, x) for L in range(n) for x in range(ni)], m)
+    ats = rng.choices(range(n), [20, 0] + list(range(1, n - 1)), k=m)
+    per_row = [ats.count(r) for r in range(n)]
+    assert per_row[0] > 512 - 256 and per_row[1] == 0 and len(set(per_row)) == n and all(c > 0 for c in per_row[2:])
+    z, ops = [0] * n, []
+    for k, (inst, at) in enumerate(zip(insts, ats)):
+        if k % 7 == 0:
+            ops.append(("commit", inst, 3000 + k, z, 0, at, k % NK, k & 1))
+        elif k % 11 == 0:
+            ops.append(("preaccept", inst, (0, inst[0]), k % NK, k & 1, 3000 + k, z, 0, at))
+    call = [(i[0], i[1], at) for i, at in zip(insts, ats)]
+    ops.append(("recover", call[1::5]))                                # (some of them committed: k = 21, 56, ..)
+    ops.append(("recover", call + [call[300]]))                        # FPX_EINVAL: nothing moves
+    ops.append(("recover", call))
+    e, model = ctx(n, num_instances=ni), R.RecoveryModel(n, NK, ni)
+    res = [(S.run_gpu_op(e, op), S.run_op(model, op)) for op in ops]
+    for k, (got, want) in enumerate(res):
+        assert got == want, (k, ops[k][0])
+    assert res[-2][0] == (R.EINVAL, None) and res[-1][0][0] == 0
+    rows = res[-1][0][1]                                               # (outcome, ballot ordering, status, vote, triple)
+    assert {r[0] for r in rows} == {R.RV_PREPARING, R.RV_COMMITTED} and {r[2] for r in rows} >= {-1, 0, 2}
+    for r in range(n):                                                 # the ranks of a row are 0 .. its total - 1, in order
+        mine = [row[1] for row, at in zip(rows, ats) if at == r]
+        assert mine == list(range(mine[0], mine[0] + per_row[r])) if mine else per_row[r] == 0
+    same_state(S.gpu_state(e, ops), S.model_state(model, ops))
+    e.close()
+
+
 def test_the_device_form_on_the_contexts_stream():
     import torch
 
