@@ -181,15 +181,19 @@ SIGNATURES = {
     "fpx_epx_accept_mk": (C.c_int32, [VP, C.c_int32] + [VP] * 14),
     "fpx_epx_handle_commit_mk": (C.c_int32, [VP, C.c_int32] + [VP] * 9),
     "fpx_epx_lead": (C.c_int32, [VP, C.c_int32] + [VP] * 10),
+    "fpx_epx_lead_mk": (C.c_int32, [VP, C.c_int32] + [VP] * 11),
     "fpx_epx_leader_replies": (C.c_int32, [VP, C.c_int32] + [VP] * 17),
     "fpx_epx_leader_replies_dev": (C.c_int32, [VP, C.c_int32] + [VP] * 17),
     "fpx_epx_replica_inbox": (C.c_int32, [VP, C.c_int32] + [VP] * 17),
     "fpx_epx_replica_inbox_dev": (C.c_int32, [VP, C.c_int32] + [VP] * 17),
+    "fpx_epx_replica_inbox_mk": (C.c_int32, [VP, C.c_int32] + [VP] * 18),
+    "fpx_epx_replica_inbox_mk_dev": (C.c_int32, [VP, C.c_int32] + [VP] * 8 + [C.c_int32] + [VP] * 10),
     "fpx_epx_read_leader_state": (C.c_int32, [VP, C.c_int32, C.c_int32, C.c_int32, VP, VP]),
     "fpx_epx_recover": (C.c_int32, [VP, C.c_int32] + [VP] * 8),
     "fpx_epx_recovery_replies": (C.c_int32, [VP, C.c_int32] + [VP] * 13 + [C.c_int32] + [VP] * 9),
     "fpx_epx_recovery_replies_dev": (C.c_int32, [VP, C.c_int32] + [VP] * 13 + [C.c_int32] + [VP] * 9),
     "fpx_epx_lead_accept": (C.c_int32, [VP, C.c_int32] + [VP] * 10),
+    "fpx_epx_lead_accept_mk": (C.c_int32, [VP, C.c_int32] + [VP] * 11),
     "fpx_epx_read_recovery_state": (C.c_int32, [VP, C.c_int32, C.c_int32, C.c_int32, VP]),
     "fpx_replica_chosen": (C.c_int32, [VP, C.c_int32, VP, VP, VP, I32P, I32P]),
     "fpx_replica_chosen_dev": (C.c_int32, [VP, C.c_int32, VP, VP, VP]),

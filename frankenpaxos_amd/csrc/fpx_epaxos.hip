@@ -1668,13 +1668,14 @@ const uint2* sort_by_cell(fpx_epx* e, int m, uint2* a_buf, uint2* b_buf, int* rc
 }
 
 // the buffers of a conflict scan of m messages at the n replicas (K7's): the sort pairs twice, the rows a tick sees, the
-// key segments, the conflicts
-int grow_conflict_scan(fpx_epx* e, int m) {
+// key segments, the conflicts.  Key lists (pairs >= 0): the sort pairs are per (message, key) pair, at least one
+int grow_conflict_scan(fpx_epx* e, int m, int pairs = -1) {
   const int n = e->st.n, NP = n <= 4 ? 4 : 8;
-  const size_t mn = (size_t)m * n;
+  const size_t mn = (size_t)m * n, pn = pairs < 0 ? mn : (size_t)std::max(pairs, 1) * n;
   int rc;
-  if ((rc = grow(e, &e->kv, mn * 8))) return rc;
-  if ((rc = grow(e, &e->kv2, mn * 8))) return rc;
+  if ((rc = grow(e, &e->kv, pn * 8))) return rc;
+  if ((rc = grow(e, &e->kv2, pn * 8))) return rc;
+  if (pairs >= 0 && (rc = grow(e, &e->mk_pconf, pn * NP * 4))) return rc;
   if ((rc = grow(e, &e->tick, (size_t)n * e->st.num_keys * 2 * n * 4))) return rc;
   if ((rc = grow(e, &e->seg, (size_t)n * e->st.num_keys * 8))) return rc;
   return grow(e, &e->conf, mn * NP * 4);
@@ -2859,20 +2860,29 @@ int32_t fpx_epx_handle_preaccept_mk(fpx_epx* e, int32_t m, const int32_t* leader
 // ---- the leader half (FPX_EPX_F_LEADER_STATE): csrc/fpx_epx_leader.hpp ---------------------------------------------------
 static bool leader_state_on(const fpx_epx* e) { return e && (e->cfg.flags & FPX_EPX_F_LEADER_STATE) && e->ls.head; }
 
-int32_t fpx_epx_lead(fpx_epx* e, int32_t m, const int32_t* leader, const int32_t* number, const int32_t* at,
-                     const int32_t* ballot_ordering, const int32_t* key, const uint8_t* is_set, const int32_t* triple_id,
-                     const uint8_t* avoid_fast_path, int32_t* deps, int32_t* deps_values_end) {
+// key or (key_off, keys): the single-key form or the key lists
+static int32_t lead_impl(fpx_epx* e, int32_t m, const int32_t* leader, const int32_t* number, const int32_t* at,
+                         const int32_t* ballot_ordering, const int32_t* key, const int32_t* key_off, const int32_t* keys,
+                         const uint8_t* is_set, const int32_t* triple_id, const uint8_t* avoid_fast_path, int32_t* deps,
+                         int32_t* deps_values_end) {
   if (!e || m < 0 || !leader_state_on(e)) return FPX_EINVAL;
   DeviceScope _dg(e->cfg.device);
   if (m == 0) return FPX_OK;
-  if (!leader || !number || !at || !ballot_ordering || !key || !is_set || !triple_id || !avoid_fast_path) return FPX_EINVAL;
+  if (!leader || !number || !at || !ballot_ordering || !(key || key_off) || !is_set || !triple_id || !avoid_fast_path)
+    return FPX_EINVAL;
   const int n = e->st.n;
   const size_t mn = (size_t)m * n;
+  // key lists: P pairs in array order instead of m messages in the scan, as fpx_epx_handle_preaccept_mk
+  int64_t P64 = 0;
+  if (key_off && check_key_lists(m, key_off, keys, e->st.num_keys, &P64)) return FPX_EINVAL;
+  const int P = key_off ? (int)P64 : m;
   int rc;
-  if ((rc = grow_conflict_scan(e, m))) return rc;
+  if ((rc = grow_conflict_scan(e, m, key_off ? P : -1))) return rc;
+  MkPairScratch pairs = {nullptr, nullptr};
+  if (key_off && (rc = carve(e, &e->mk_pair, &pairs, [&](Carver& c) { return lay_mk_pairs(c, P); }))) return rc;
   LdBatch lb;
   memset(&lb, 0, sizeof(lb));
-  lb.m = m, lb.kv = (uint2*)e->kv.p;
+  lb.m = m, lb.kv = (uint2*)e->kv.p, lb.uniq = pairs.uniq, lb.P = P;
   // K7's "processed" branch at replica at[i] alone, with an empty deps_in: its gate table, its scan, its reply kernel
   HpBatch hb;
   memset(&hb, 0, sizeof(hb));
@@ -2880,27 +2890,60 @@ int32_t fpx_epx_lead(fpx_epx* e, int32_t m, const int32_t* leader, const int32_t
   auto launch = [&]() -> int {
     int rc2;
     if ((rc2 = next_run_id(e, &lb.run_id))) return rc2;
+    if (!key_off) lb.key_off = lb.keys = nullptr;
+    else lb.key = nullptr;
     hb.leader = lb.leader, hb.number = lb.number, hb.b_ord = lb.b_ord, hb.b_rep = lb.at, hb.key = lb.key, hb.is_set = lb.is_set;
+    hb.key_off = lb.key_off, hb.keys = lb.keys, hb.uniq = lb.uniq, hb.P = P;
     hb.triple = lb.triple, hb.act = lb.act, lb.reply_deps = hb.reply_deps, lb.reply_end = hb.reply_end;
     const dim3 gm((m + 255) / 256), gmn((unsigned)(((long long)m * n + 255) / 256)), blk(256);
     hipLaunchKernelGGL(k_ld_validate, gm, blk, 0, e->stream, e->st, lb);
+    if (key_off) {
+      MkBatch mb;
+      memset(&mb, 0, sizeof(mb));
+      mb.m = m, mb.P = P, mb.off = lb.key_off, mb.keys = lb.keys, mb.number = lb.number, mb.pnum = pairs.pnum, mb.uniq = pairs.uniq;
+      hipLaunchKernelGGL(k_mk_pairs, gm, blk, 0, e->stream, mb);
+    }
     hipLaunchKernelGGL(k_ld_gate, gmn, blk, 0, e->stream, e->st, lb);
     EpxBatch sb;
-    if ((rc2 = sort_conflict_scan(e, m, lb.number, &sb))) return rc2;
-    hb.conf = sb.conf, hb.tick = sb.tick;
+    memset(&sb, 0, sizeof(sb));
+    // (key lists that are all empty: nothing to scan, nothing for the index to learn)
+    if (P > 0 && (rc2 = sort_conflict_scan(e, P, key_off ? pairs.pnum : lb.number, &sb))) return rc2;
+    if (key_off) sb.conf = (int32_t*)e->mk_pconf.p;
+    hb.conf = (int32_t*)e->conf.p, hb.tick = (int32_t*)e->tick.p;
+    MkMerge mm;
+    memset(&mm, 0, sizeof(mm));
+    mm.m = m, mm.off = lb.key_off, mm.uniq = pairs.uniq, mm.pconf = sb.conf, mm.conf = (int32_t*)e->conf.p, mm.act = lb.act;
     by_n(n, [&](auto N) {
-      launch_hp<N>(e, sb, hb);
+      launch_hp<N>(e, sb, hb, key_off ? &mm : nullptr, P > 0);
       hipLaunchKernelGGL((k_ld_install<N>), gm, blk, 0, e->stream, e->st, e->ls, lb);
     });
     const long long tot = (long long)e->st.num_keys * n * n;
-    hipLaunchKernelGGL(k_hp_commit, dim3((unsigned)((tot + 255) / 256)), blk, 0, e->stream, e->st, hb);
+    if (P > 0) hipLaunchKernelGGL(k_hp_commit, dim3((unsigned)((tot + 255) / 256)), blk, 0, e->stream, e->st, hb);
     return FPX_OK;
   };
   return host_call(e, {in(lb.leader, leader, m), in(lb.number, number, m), in(lb.at, at, m), in(lb.b_ord, ballot_ordering, m),
-                       in(lb.key, key, m), in(lb.triple, triple_id, m), in(lb.is_set, is_set, m), in(lb.avoid, avoid_fast_path, m),
-                       scratch(hb.deps_in, mn, 0), scratch(lb.skip, m, 0), held(lb.deps, deps, mn), held(lb.dend, deps_values_end, m),
-                       scratch(lb.act, mn), scratch(hb.reply_deps, mn * n), scratch(hb.reply_end, mn)},
+                       in(lb.key, key, key ? m : 0), in(lb.triple, triple_id, m), in(lb.is_set, is_set, m),
+                       in(lb.avoid, avoid_fast_path, m), in(lb.key_off, key_off, key_off ? m + 1 : 0),
+                       in(lb.keys, keys, key_off ? P : 0), scratch(hb.deps_in, mn, 0), scratch(lb.skip, m, 0),
+                       held(lb.deps, deps, mn), held(lb.dend, deps_values_end, m), scratch(lb.act, mn),
+                       scratch(hb.reply_deps, mn * n), scratch(hb.reply_end, mn)},
                    launch);
+}
+
+int32_t fpx_epx_lead(fpx_epx* e, int32_t m, const int32_t* leader, const int32_t* number, const int32_t* at,
+                     const int32_t* ballot_ordering, const int32_t* key, const uint8_t* is_set, const int32_t* triple_id,
+                     const uint8_t* avoid_fast_path, int32_t* deps, int32_t* deps_values_end) {
+  if (m > 0 && !key) return FPX_EINVAL;
+  return lead_impl(e, m, leader, number, at, ballot_ordering, key, nullptr, nullptr, is_set, triple_id, avoid_fast_path, deps,
+                   deps_values_end);
+}
+
+int32_t fpx_epx_lead_mk(fpx_epx* e, int32_t m, const int32_t* leader, const int32_t* number, const int32_t* at,
+                        const int32_t* ballot_ordering, const int32_t* key_offsets, const int32_t* keys, const uint8_t* is_set,
+                        const int32_t* triple_id, const uint8_t* avoid_fast_path, int32_t* deps, int32_t* deps_values_end) {
+  if (m > 0 && !key_offsets) return FPX_EINVAL;
+  return lead_impl(e, m, leader, number, at, ballot_ordering, nullptr, key_offsets, keys, is_set, triple_id, avoid_fast_path,
+                   deps, deps_values_end);
 }
 
 // b: the messages and the outputs (any of which may be null); the scratch fields are filled here
@@ -2972,26 +3015,40 @@ int32_t fpx_epx_leader_replies(fpx_epx* e, int32_t m, const int32_t* kind, const
 }
 
 // ---- the replica half, a burst at a time: csrc/fpx_epx_inbox.hpp -------------------------------------------------------------
-// b: the messages and the outputs (any of which may be null); the scratch fields are filled here
-static int32_t replica_inbox_launch(fpx_epx* e, RiBatch b) {
+// b: the messages and the outputs (any of which may be null); the scratch fields are filled here.  MK: b.key_off / b.keys
+// / b.P in place of b.key
+extern "C++" template <bool MK>
+int32_t replica_inbox_launch(fpx_epx* e, RiBatch b) {
   const int m = b.m, n = e->st.n;
+  const int P = MK ? b.P : m;  // what one replica's conflict scan runs over
   const int tiles = (m + CL_TILE - 1) / CL_TILE;
   int rc;
-  if ((rc = grow_conflict_scan(e, m))) return rc;
+  if ((rc = grow_conflict_scan(e, m, MK ? P : -1))) return rc;
   EpxInboxScratch s;
-  if ((rc = carve(e, &e->ri_misc, &s, [&](Carver& c) { return lay_epx_inbox(c, m, n, tiles); }))) return rc;
+  if constexpr (MK) {
+    EpxInboxMkScratch ms;
+    if ((rc = carve(e, &e->ri_misc, &ms, [&](Carver& c) { return lay_epx_inbox_mk(c, m, P, n, tiles); }))) return rc;
+    s = ms.msg, b.uniq = ms.pair.uniq, b.pnum = ms.pair.pnum;
+    b.pconf = (int32_t*)e->mk_pconf.p, b.merged = (int32_t*)e->conf.p;
+  } else {
+    if ((rc = carve(e, &e->ri_misc, &s, [&](Carver& c) { return lay_epx_inbox(c, m, n, tiles); }))) return rc;
+  }
   b.ckv = (uint2*)s.cell[0], b.kv = (uint2*)e->kv.p, b.contrib = s.contrib, b.nackflag = s.nackflag, b.src = s.src, b.last = s.last;
   b.conf = (int32_t*)e->conf.p;
   const dim3 gm((m + 255) / 256), blk(256);
-  hipLaunchKernelGGL(k_ri_validate, gm, blk, 0, e->stream, e->st, b);
+  hipLaunchKernelGGL(k_ri_validate<MK>, gm, blk, 0, e->stream, e->st, b);
+  if constexpr (MK) hipLaunchKernelGGL(k_ri_lists, gm, blk, 0, e->stream, e->st, b);
   // both sorts of the call count their digits in e->tmp: it has its final size before the first one is enqueued
-  if ((rc = grow(e, &e->tmp, std::max(radix_sort_bytes(1, m, cell_bits(e)), radix_sort_bytes(n, m, key_bits(e)))))) return rc;
+  if ((rc = grow(e, &e->tmp, std::max(radix_sort_bytes(1, m, cell_bits(e)), radix_sort_bytes(n, P, key_bits(e)))))) return rc;
   b.sorted = sort_by_cell(e, m, b.ckv, (uint2*)s.cell[1], &rc);
   if (rc) return rc;
-  by_n(n, [&](auto N) { hipLaunchKernelGGL((k_ri_walk<N>), gm, blk, 0, e->stream, e->st, b); });
+  by_n(n, [&](auto N) { hipLaunchKernelGGL((k_ri_walk<N, MK>), gm, blk, 0, e->stream, e->st, b); });
   // the conflict scan of what each replica looks up and puts, in array order: K7's sort / segments / scan
+  // (key lists that are all empty: nothing to scan, nothing for the index to learn)
   EpxBatch sb;
-  if ((rc = sort_conflict_scan(e, m, b.number, &sb))) return rc;
+  memset(&sb, 0, sizeof(sb));
+  if (P > 0 && (rc = sort_conflict_scan(e, P, MK ? b.pnum : b.number, &sb))) return rc;
+  if constexpr (MK) sb.conf = (int32_t*)e->mk_pconf.p;
   // the largestBallot every Nack carries: prefix max per replica over the ballots it took in (as for Prepare / Accept)
   ClBatch cb;
   memset(&cb, 0, sizeof(cb));
@@ -3004,12 +3061,13 @@ static int32_t replica_inbox_launch(fpx_epx* e, RiBatch b) {
   hb.tick = sb.tick;
   const long long tot = (long long)e->st.num_keys * n * n;
   by_n(n, [&](auto N) {
-    hipLaunchKernelGGL((k_epx_scan<N>), dim3((N * e->st.num_keys + 3) / 4), blk, 0, e->stream, e->st, sb);
+    if (P > 0) hipLaunchKernelGGL((k_epx_scan<N>), dim3((N * e->st.num_keys + 3) / 4), blk, 0, e->stream, e->st, sb);
+    if constexpr (MK) hipLaunchKernelGGL((k_ri_merge<N>), gm, blk, 0, e->stream, e->st, b);
     // the replies read the dependencies the entries held before the burst; only then are the entries' overwritten
-    hipLaunchKernelGGL((k_ri_reply<N>), gm, blk, 0, e->stream, e->st, b);
-    hipLaunchKernelGGL((k_ri_store<N>), gm, blk, 0, e->stream, e->st, b);
+    hipLaunchKernelGGL((k_ri_reply<N, MK>), gm, blk, 0, e->stream, e->st, b);
+    hipLaunchKernelGGL((k_ri_store<N, MK>), gm, blk, 0, e->stream, e->st, b);
   });
-  hipLaunchKernelGGL(k_hp_commit, dim3((unsigned)((tot + 255) / 256)), blk, 0, e->stream, e->st, hb);
+  if (P > 0) hipLaunchKernelGGL(k_hp_commit, dim3((unsigned)((tot + 255) / 256)), blk, 0, e->stream, e->st, hb);
   return FPX_OK;
 }
 
@@ -3037,7 +3095,7 @@ int32_t fpx_epx_replica_inbox_dev(fpx_epx* e, int32_t m, const int32_t* d_kind, 
   b.b_rep = d_ballot_replica, b.key = d_key, b.is_set = d_is_set, b.triple = d_triple_id, b.deps = d_deps, b.dend = d_deps_values_end;
   b.outcome = d_outcome, b.out_ballot = d_out_ballot, b.out_status = d_out_status, b.out_deps = d_out_deps;
   b.out_end = d_out_values_end, b.out_triple = d_out_triple;
-  int rc = replica_inbox_launch(e, b);
+  int rc = replica_inbox_launch<false>(e, b);
   return rc ? rc : launch_check(e);
 }
 
@@ -3062,7 +3120,55 @@ int32_t fpx_epx_replica_inbox(fpx_epx* e, int32_t m, const int32_t* kind, const 
                        opt_in(b.dend, deps_values_end, m), in(b.deps, deps, mn), in(b.is_set, is_set, m),
                        held(b.outcome, outcome, m), held(b.out_ballot, out_ballot, m), held(b.out_status, out_status, m),
                        held(b.out_end, out_values_end, m), held(b.out_triple, out_triple, m), held(b.out_deps, out_deps, mn)},
-                   [&]() -> int { return replica_inbox_launch(e, b); });
+                   [&]() -> int { return replica_inbox_launch<false>(e, b); });
+}
+
+int32_t fpx_epx_replica_inbox_mk_dev(fpx_epx* e, int32_t m, const int32_t* d_kind, const int32_t* d_to, const int32_t* d_leader,
+                                     const int32_t* d_number, const int32_t* d_ballot_ordering, const int32_t* d_ballot_replica,
+                                     const int32_t* d_key_offsets, const int32_t* d_keys, int32_t num_pairs,
+                                     const uint8_t* d_is_set, const int32_t* d_triple_id, const int32_t* d_deps,
+                                     const int32_t* d_deps_values_end, int32_t* d_outcome, int32_t* d_out_ballot,
+                                     int32_t* d_out_status, int32_t* d_out_deps, int32_t* d_out_values_end, int32_t* d_out_triple) {
+  if (replica_inbox_check(e, m) || num_pairs < 0 || num_pairs > FPX_EPX_MK_MAX_PAIRS) return FPX_EINVAL;
+  DeviceScope _dg(e->cfg.device);
+  if (m == 0) return FPX_OK;
+  if (!d_kind || !d_to || !d_leader || !d_number || !d_ballot_ordering || !d_ballot_replica || !d_key_offsets ||
+      (num_pairs > 0 && !d_keys) || !d_is_set || !d_triple_id || !d_deps)
+    return FPX_EINVAL;
+  RiBatch b;
+  memset(&b, 0, sizeof(b));
+  b.m = m, b.kind = d_kind, b.to = d_to, b.leader = d_leader, b.number = d_number, b.b_ord = d_ballot_ordering;
+  b.b_rep = d_ballot_replica, b.key_off = d_key_offsets, b.keys = d_keys, b.P = num_pairs, b.is_set = d_is_set;
+  b.triple = d_triple_id, b.deps = d_deps, b.dend = d_deps_values_end;
+  b.outcome = d_outcome, b.out_ballot = d_out_ballot, b.out_status = d_out_status, b.out_deps = d_out_deps;
+  b.out_end = d_out_values_end, b.out_triple = d_out_triple;
+  int rc = replica_inbox_launch<true>(e, b);
+  return rc ? rc : launch_check(e);
+}
+
+int32_t fpx_epx_replica_inbox_mk(fpx_epx* e, int32_t m, const int32_t* kind, const int32_t* to, const int32_t* leader,
+                                 const int32_t* number, const int32_t* ballot_ordering, const int32_t* ballot_replica,
+                                 const int32_t* key_offsets, const int32_t* keys, const uint8_t* is_set, const int32_t* triple_id,
+                                 const int32_t* deps, const int32_t* deps_values_end, int32_t* outcome, int32_t* out_ballot,
+                                 int32_t* out_status, int32_t* out_deps, int32_t* out_values_end, int32_t* out_triple) {
+  if (replica_inbox_check(e, m)) return FPX_EINVAL;
+  DeviceScope _dg(e->cfg.device);
+  if (m == 0) return FPX_OK;
+  if (!kind || !to || !leader || !number || !ballot_ordering || !ballot_replica || !key_offsets || !is_set || !triple_id || !deps)
+    return FPX_EINVAL;
+  int64_t P = 0;  // (the device checks the lists again, as it does for the device form)
+  if (check_key_lists(m, key_offsets, keys, e->st.num_keys, &P)) return FPX_EINVAL;
+  const size_t mn = (size_t)m * e->st.n;
+  RiBatch b;
+  memset(&b, 0, sizeof(b));
+  b.m = m, b.P = (int)P;
+  return host_call(e, {in(b.kind, kind, m), in(b.to, to, m), in(b.leader, leader, m), in(b.number, number, m),
+                       in(b.b_ord, ballot_ordering, m), in(b.b_rep, ballot_replica, m), in(b.key_off, key_offsets, (size_t)m + 1),
+                       in(b.keys, keys, P), in(b.triple, triple_id, m), opt_in(b.dend, deps_values_end, m), in(b.deps, deps, mn),
+                       in(b.is_set, is_set, m), held(b.outcome, outcome, m), held(b.out_ballot, out_ballot, m),
+                       held(b.out_status, out_status, m), held(b.out_end, out_values_end, m), held(b.out_triple, out_triple, m),
+                       held(b.out_deps, out_deps, mn)},
+                   [&]() -> int { return replica_inbox_launch<true>(e, b); });
 }
 
 int32_t fpx_epx_read_leader_state(fpx_epx* e, int32_t replica, int32_t leader, int32_t number, int32_t out[8],
@@ -3197,29 +3303,53 @@ int32_t fpx_epx_recovery_replies(fpx_epx* e, int32_t m, const int32_t* to, const
                    [&]() -> int { return recovery_replies_launch(e, b); });
 }
 
-int32_t fpx_epx_lead_accept(fpx_epx* e, int32_t m, const int32_t* leader, const int32_t* number, const int32_t* at,
-                            const int32_t* ballot_ordering, const int32_t* key, const uint8_t* is_set, const int32_t* triple_id,
-                            const int32_t* sequence_number, const int32_t* deps, const int32_t* deps_values_end) {
+// key or (key_off, keys): the single-key form or the key lists
+static int32_t lead_accept_impl(fpx_epx* e, int32_t m, const int32_t* leader, const int32_t* number, const int32_t* at,
+                                const int32_t* ballot_ordering, const int32_t* key, const int32_t* key_off, const int32_t* keys,
+                                const uint8_t* is_set, const int32_t* triple_id, const int32_t* sequence_number,
+                                const int32_t* deps, const int32_t* deps_values_end) {
   if (!e || m < 0 || !recovery_on(e)) return FPX_EINVAL;
   DeviceScope _dg(e->cfg.device);
   if (m == 0) return FPX_OK;
-  if (!leader || !number || !at || !ballot_ordering || !key || !is_set || !triple_id || !deps) return FPX_EINVAL;
+  if (!leader || !number || !at || !ballot_ordering || !(key || key_off) || !is_set || !triple_id || !deps) return FPX_EINVAL;
   const int n = e->st.n;
+  int64_t P = 0;
+  if (key_off && check_key_lists(m, key_off, keys, e->st.num_keys, &P)) return FPX_EINVAL;
   LaBatch b;
   memset(&b, 0, sizeof(b));
   b.m = m;
   auto launch = [&]() -> int {
     int rc;
     if ((rc = next_run_id(e, &b.run_id))) return rc;
+    if (!key_off) b.key_off = b.keys = nullptr;
+    else b.key = nullptr;
     const dim3 gm((m + 255) / 256), blk(256);
     hipLaunchKernelGGL(k_la_validate, gm, blk, 0, e->stream, e->st, b);
     by_n(n, [&](auto N) { hipLaunchKernelGGL((k_la_install<N>), gm, blk, 0, e->stream, e->st, e->ls, b); });
     return FPX_OK;
   };
   return host_call(e, {in(b.leader, leader, m), in(b.number, number, m), in(b.at, at, m), in(b.b_ord, ballot_ordering, m),
-                       in(b.key, key, m), in(b.triple, triple_id, m), opt_in(b.seq, sequence_number, m),
-                       opt_in(b.dend, deps_values_end, m), in(b.deps, deps, (size_t)m * n), in(b.is_set, is_set, m)},
+                       in(b.key, key, key ? m : 0), in(b.triple, triple_id, m), opt_in(b.seq, sequence_number, m),
+                       opt_in(b.dend, deps_values_end, m), in(b.deps, deps, (size_t)m * n), in(b.is_set, is_set, m),
+                       in(b.key_off, key_off, key_off ? m + 1 : 0), in(b.keys, keys, P)},
                    launch);
+}
+
+int32_t fpx_epx_lead_accept(fpx_epx* e, int32_t m, const int32_t* leader, const int32_t* number, const int32_t* at,
+                            const int32_t* ballot_ordering, const int32_t* key, const uint8_t* is_set, const int32_t* triple_id,
+                            const int32_t* sequence_number, const int32_t* deps, const int32_t* deps_values_end) {
+  if (m > 0 && !key) return FPX_EINVAL;
+  return lead_accept_impl(e, m, leader, number, at, ballot_ordering, key, nullptr, nullptr, is_set, triple_id, sequence_number,
+                          deps, deps_values_end);
+}
+
+int32_t fpx_epx_lead_accept_mk(fpx_epx* e, int32_t m, const int32_t* leader, const int32_t* number, const int32_t* at,
+                               const int32_t* ballot_ordering, const int32_t* key_offsets, const int32_t* keys,
+                               const uint8_t* is_set, const int32_t* triple_id, const int32_t* sequence_number,
+                               const int32_t* deps, const int32_t* deps_values_end) {
+  if (m > 0 && !key_offsets) return FPX_EINVAL;
+  return lead_accept_impl(e, m, leader, number, at, ballot_ordering, nullptr, key_offsets, keys, is_set, triple_id,
+                          sequence_number, deps, deps_values_end);
 }
 
 int32_t fpx_epx_read_recovery_state(fpx_epx* e, int32_t replica, int32_t leader, int32_t number, int32_t* out) {

@@ -81,17 +81,21 @@ __global__ void __launch_bounds__(256) k_mk_total(const EpxState st, const MkBat
   if (threadIdx.x == 0) b.info[0] = u, b.info[1] = not_one, b.info[3] = st.status[0];
 }
 
+// the pairs keys[lo .. hi) of one command with instance number x
+__device__ __forceinline__ void mk_command_pairs(const int32_t* keys, int lo, int hi, int x, uint8_t* uniq, int32_t* pnum) {
+  for (int j = lo; j < hi; ++j) {
+    const int k = keys[j];
+    bool first = true;
+    for (int q = lo; first && q < j; ++q) first = keys[q] != k;
+    uniq[j] = first ? 1 : 0;
+    pnum[j] = x;
+  }
+}
+
 __global__ void __launch_bounds__(256) k_mk_pairs(const MkBatch b) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= b.m) return;
-  const int lo = b.off[i], hi = b.off[i + 1], x = b.number[i];
-  for (int j = lo; j < hi; ++j) {
-    const int k = b.keys[j];
-    bool first = true;
-    for (int q = lo; first && q < j; ++q) first = b.keys[q] != k;
-    b.uniq[j] = first ? 1 : 0;
-    b.pnum[j] = x;
-  }
+  mk_command_pairs(b.keys, b.off[i], b.off[i + 1], b.number[i], b.uniq, b.pnum);
 }
 
 // k_epx_keys' checks, and the command's record at its position in every replica's order

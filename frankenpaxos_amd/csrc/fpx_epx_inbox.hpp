@@ -26,6 +26,17 @@
 //                   for a PreAccept, the message's own for an Accept or a Commit), or the pre-burst cl_deps
 //   k_ri_store<N>   cl_deps / cl_dend of every touched cell from its last writer -- a launch of its own, AFTER k_ri_reply:
 //                   every reply that needs the pre-burst dependencies has read them before any is overwritten
+//
+// Key lists (fpx_epx_replica_inbox_mk, the MK = true instantiations; fpx_epaxos_mk.hpp has the conflict model): the entry
+// walk never looks at keys, so only the conflict scan changes -- from m messages per replica to P = key_off[m] (message,
+// key) pairs per replica, in array order, as K7's pair form.
+//   k_ri_lists      the lists checked ON THE DEVICE (the device form has no host wait): key_off[0] = 0, non-decreasing,
+//                   key_off[m] = the caller's num_pairs, keys in range; uniq / pnum of every pair (mk_command_pairs) and the
+//                   n x P sort pairs filled with "takes no part".  A thread touches pairs only inside [0, num_pairs)
+//   k_ri_walk       a put writes one sort word per distinct key of the message, at its pair positions
+//   K7's scan       over P pairs, number = pnum, rows pconf[P][n][NP]
+//   k_ri_merge<N>   for every processed PreAccept the max over its distinct keys' pair rows at replica to[i] -> conf, which
+//                   k_ri_reply / k_ri_store read as before
 // Integer compares, max and atomics only; plain vector stores.
 #pragma once
 
@@ -41,7 +52,10 @@ struct RiBatch {
   const int32_t* number;
   const int32_t* b_ord;
   const int32_t* b_rep;
-  const int32_t* key;
+  const int32_t* key;      // null in the key-list form
+  const int32_t* key_off;  // key-list form (else null): message i's keys are keys[key_off[i] .. key_off[i + 1]), P pairs in all
+  const int32_t* keys;
+  int P;
   const uint8_t* is_set;
   const int32_t* triple;
   const int32_t* deps;  // [m][n]
@@ -54,14 +68,19 @@ struct RiBatch {
   int32_t* out_triple;
   uint2* ckv;           // (cell, message index)
   const uint2* sorted;
-  uint2* kv;            // [n][m] K7's sort pairs
+  uint2* kv;            // [n][m] K7's sort pairs; key lists: [n][P], pair j at position j
   int32_t* contrib;     // [n][m] k_cl_tilemax / k_cl_nacks
   uint8_t* nackflag;    // [n][m]
   int32_t* src;         // [m]
   int32_t* last;        // [m] by the sorted position of the run head
-  const int32_t* conf;  // [m][n][NP] from k_epx_scan
+  const int32_t* conf;  // [m][n][NP] from k_epx_scan; key lists: from k_ri_merge
+  uint8_t* uniq;        // key lists: [P] the pair's key occurs for the first time in its command
+  int32_t* pnum;        // [P] the instance number of the pair's message
+  const int32_t* pconf; // [P][n][NP] from k_epx_scan
+  int32_t* merged;      // = conf, for k_ri_merge to write
 };
 
+template <bool MK>
 __global__ void __launch_bounds__(256) k_ri_validate(const EpxState st, const RiBatch b) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= b.m) return;
@@ -71,7 +90,9 @@ __global__ void __launch_bounds__(256) k_ri_validate(const EpxState st, const Ri
     const int bo = b.b_ord[i], br = b.b_rep[i];
     ok = bo >= 0 && bo < (1 << 27) && br >= 0 && br < n;
   }
-  if (ok && kind != RI_PREPARE) ok = b.key[i] >= -1 && b.key[i] < st.num_keys;  // a Prepare carries no command
+  if constexpr (!MK) {  // (key lists: k_ri_lists)
+    if (ok && kind != RI_PREPARE) ok = b.key[i] >= -1 && b.key[i] < st.num_keys;  // a Prepare carries no command
+  }
   const int end = b.dend ? b.dend[i] : 0;
   if (ok && kind == RI_PRE_ACCEPT) {  // k_hp_validate's rules
     for (int l = 0; l < n; ++l) ok = ok && b.deps[(size_t)i * n + l] >= 0;
@@ -87,13 +108,41 @@ __global__ void __launch_bounds__(256) k_ri_validate(const EpxState st, const Ri
   // no (replica, message) pair takes part in the conflict scan or in the largestBallot scan until the walk says so
   for (int r = 0; r < n; ++r) {
     const size_t o = (size_t)r * b.m + i;
-    b.kv[o] = make_uint2((uint32_t)st.num_keys, (uint32_t)i);
+    if constexpr (!MK) b.kv[o] = make_uint2((uint32_t)st.num_keys, (uint32_t)i);
     b.contrib[o] = -1;
     b.nackflag[o] = 0;
   }
 }
 
-template <int N>
+// Key lists: the CSR checked before anything is applied, then what k_mk_pairs gives.  The offsets are the caller's device
+// memory, so a thread believes only its own two: with 0 <= lo <= hi <= P it stays inside keys[P], uniq[P], pnum[P] and
+// kv[n][P] whatever the rest of the array says.  (A Prepare's list is checked with the rest of the CSR -- the offsets are
+// one array -- but never looked up.)
+__global__ void __launch_bounds__(256) k_ri_lists(const EpxState st, const RiBatch b) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= b.m) return;
+  const int P = b.P, lo = b.key_off[i], hi = b.key_off[i + 1];
+  bool ok = lo >= 0 && lo <= hi && hi <= P && (i > 0 || lo == 0) && (i < b.m - 1 || hi == P);
+  for (int j = lo; ok && j < hi; ++j) ok = b.keys[j] >= 0 && b.keys[j] < st.num_keys;
+  if (!ok) {
+    epx_report(st.status, FPX_EINVAL, i);
+    return;
+  }
+  mk_command_pairs(b.keys, lo, hi, b.number[i], b.uniq, b.pnum);
+  for (int r = 0; r < st.n; ++r)
+    for (int j = lo; j < hi; ++j) b.kv[(size_t)r * P + j] = make_uint2((uint32_t)st.num_keys, (uint32_t)j);
+}
+
+// message i's pairs [lo, hi), empty unless they lie inside [0, P).  k_ri_lists reports a bad list as FPX_EINVAL and the
+// kernels below stand back from that status -- but the status word may already hold an earlier call's other error, which
+// they do not stand back from: so they, too, believe no offset they have not bounded themselves
+__device__ __forceinline__ void ri_pairs(const RiBatch& b, int i, int* lo, int* hi) {
+  const int l = b.key_off[i], h = b.key_off[i + 1];
+  const bool ok = l >= 0 && l <= h && h <= b.P;
+  *lo = ok ? l : 0, *hi = ok ? h : 0;
+}
+
+template <int N, bool MK>
 __global__ void __launch_bounds__(256) k_ri_walk(const EpxState st, const RiBatch b) {
   if (st.status[0] == FPX_EINVAL) return;
   const int j0 = blockIdx.x * blockDim.x + threadIdx.x;
@@ -161,7 +210,15 @@ __global__ void __launch_bounds__(256) k_ri_walk(const EpxState st, const RiBatc
     const size_t o = (size_t)to * b.m + i;
     if (contrib >= 0) b.contrib[o] = contrib;
     if (outcome == FPX_EPX_RI_NACK) b.nackflag[o] = 1;
-    if (put && b.key[i] >= 0) {  // (a Noop has no conflicts and leaves the index alone, :592-593, 602-614)
+    if constexpr (MK) {
+      if (put) {  // under every distinct key of the list (KeyValueStore.scala:236-254); no keys = nothing, as a Noop
+        const uint32_t flags = ((uint32_t)(b.is_set[i] ? 1 : 0) << EPX_SET_SHIFT) | ((uint32_t)L << EPX_LEADER_SHIFT);
+        int lo, hi;
+        ri_pairs(b, i, &lo, &hi);
+        for (int q = lo; q < hi; ++q)
+          if (b.uniq[q]) b.kv[(size_t)to * b.P + q] = make_uint2((uint32_t)b.keys[q] | flags, (uint32_t)q);
+      }
+    } else if (put && b.key[i] >= 0) {  // (a Noop has no conflicts and leaves the index alone, :592-593, 602-614)
       const uint32_t flags = ((uint32_t)(b.is_set[i] ? 1 : 0) << EPX_SET_SHIFT) | ((uint32_t)L << EPX_LEADER_SHIFT);
       b.kv[o] = make_uint2((uint32_t)b.key[i] | flags, (uint32_t)i);
     }
@@ -175,8 +232,36 @@ __global__ void __launch_bounds__(256) k_ri_walk(const EpxState st, const RiBatc
   b.last[j0] = src;
 }
 
-// the dependencies the entry holds once message s has written it: (watermarks, values_end) as the per-kind kernels store them
+// Key lists: the conflict row of every PROCESSED PreAccept (src[i] == i with kind PreAccept is exactly that set) at the
+// replica it went to = the element-wise max over its distinct keys of the pair rows; a command without keys: zeros
 template <int N>
+__global__ void __launch_bounds__(256) k_ri_merge(const EpxState st, const RiBatch b) {
+  if (st.status[0] == FPX_EINVAL) return;
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= b.m || b.kind[i] != RI_PRE_ACCEPT || b.src[i] != i) return;
+  constexpr int NP = ConfRow<N>::NP;
+  const int r = b.to[i];
+  if (r < 0 || r >= N) return;  // (reported by k_ri_validate; see ri_pairs)
+  int4 a0 = make_int4(0, 0, 0, 0), a1 = make_int4(0, 0, 0, 0);  // (rows are 16 / 32 bytes, aligned: whole-row loads, as k_mk_merge)
+  int lo, hi;
+  ri_pairs(b, i, &lo, &hi);
+  for (int j = lo; j < hi; ++j) {
+    if (!b.uniq[j]) continue;
+    const int4* row = reinterpret_cast<const int4*>(b.pconf + ((size_t)j * N + r) * NP);
+    const int4 x = row[0];
+    a0 = make_int4(imax(a0.x, x.x), imax(a0.y, x.y), imax(a0.z, x.z), imax(a0.w, x.w));
+    if constexpr (NP == 8) {
+      const int4 y = row[1];
+      a1 = make_int4(imax(a1.x, y.x), imax(a1.y, y.y), imax(a1.z, y.z), imax(a1.w, y.w));
+    }
+  }
+  int4* dst = reinterpret_cast<int4*>(b.merged + ((size_t)i * N + r) * NP);
+  dst[0] = a0;
+  if constexpr (NP == 8) dst[1] = a1;
+}
+
+// the dependencies the entry holds once message s has written it: (watermarks, values_end) as the per-kind kernels store them
+template <int N, bool MK>
 __device__ __forceinline__ void ri_stored(const RiBatch& b, int s, int* w, int* end) {
   constexpr int NP = ConfRow<N>::NP;
   const int L = b.leader[s], x = b.number[s];
@@ -191,7 +276,10 @@ __device__ __forceinline__ void ri_stored(const RiBatch& b, int s, int* w, int* 
   int row[N], e = 0;
 #pragma unroll
   for (int l = 0; l < N; ++l) row[l] = 0;
-  if (b.key[s] >= 0) {  // computeSequenceNumberAndDependencies :569-600: the conflicts the scan found at replica to[s]
+  bool has_keys;  // a command with keys (not a Noop, not an empty list)
+  if constexpr (MK) has_keys = b.key_off[s + 1] > b.key_off[s];
+  else has_keys = b.key[s] >= 0;
+  if (has_keys) {  // computeSequenceNumberAndDependencies :569-600: the conflicts the scan found at replica to[s]
     const int32_t* cr = b.conf + ((size_t)s * N + b.to[s]) * NP;
 #pragma unroll
     for (int l = 0; l < N; ++l) row[l] = cr[l];
@@ -206,7 +294,7 @@ __device__ __forceinline__ void ri_stored(const RiBatch& b, int s, int* w, int* 
   *end = e;
 }
 
-template <int N>
+template <int N, bool MK>
 __global__ void __launch_bounds__(256) k_ri_reply(const EpxState st, const RiBatch b) {
   if (st.status[0] == FPX_EINVAL) return;
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -216,7 +304,7 @@ __global__ void __launch_bounds__(256) k_ri_reply(const EpxState st, const RiBat
 #pragma unroll
   for (int l = 0; l < N; ++l) w[l] = 0;
   if (s >= 0) {
-    ri_stored<N>(b, s, w, &end);
+    ri_stored<N, MK>(b, s, w, &end);
   } else if (s == RI_OLD) {
     const size_t c = ((size_t)b.to[i] * N + b.leader[i]) * st.num_instances + b.number[i];
 #pragma unroll
@@ -230,7 +318,7 @@ __global__ void __launch_bounds__(256) k_ri_reply(const EpxState st, const RiBat
   if (b.out_end) b.out_end[i] = end;
 }
 
-template <int N>
+template <int N, bool MK>
 __global__ void __launch_bounds__(256) k_ri_store(const EpxState st, const RiBatch b) {
   if (st.status[0] == FPX_EINVAL) return;
   const int j = blockIdx.x * blockDim.x + threadIdx.x;
@@ -240,7 +328,7 @@ __global__ void __launch_bounds__(256) k_ri_store(const EpxState st, const RiBat
   const int s = b.last[j];
   if (s < 0) return;  // no message of the run wrote the dependencies
   int w[N], end = 0;
-  ri_stored<N>(b, s, w, &end);
+  ri_stored<N, MK>(b, s, w, &end);
   const size_t c = e.x;
 #pragma unroll
   for (int l = 0; l < N; ++l) st.cl_deps[c * N + l] = w[l];

@@ -6,7 +6,8 @@
 //
 // The state of cell c = (replica r, leader L, number x), the command log's cell index:
 //   head[c]   int4: x = phase | avoidFastPath << 2 | is_set << 3 | responses << 8 (bit q: replica q has answered)
-//                   y = ballot (encoded as the command log's), z = triple id, w = key (-1 = Noop)
+//                   y = ballot (encoded as the command log's), z = triple id, w = key (-1 = Noop or a command without keys,
+//                   FPX_EPX_KEY_LIST = two or more distinct keys: the caller holds the list by triple id; ls_key_word)
 //   resp[c]   n rows of n + 2 ints, row q = what replica q answered: sequence number, n watermarks, values_end -- always
 //             in the canonical form own_column gives.  Accepting keeps the triple's (sequence number, dependencies) in
 //             row r, the replica's own.
@@ -34,6 +35,17 @@ __device__ __forceinline__ int ls_pack(int phase, int avoid, int is_set, unsigne
   return phase | (avoid << 2) | (is_set << 3) | (int)(mask << 8);
 }
 
+// head.w of message i's command: its key (key_off null), or for a key list the one distinct key / -1 for none /
+// FPX_EPX_KEY_LIST for more
+__device__ __forceinline__ int ls_key_word(const int32_t* key, const int32_t* key_off, const int32_t* keys, int i) {
+  if (!key_off) return key[i];
+  const int lo = key_off[i], hi = key_off[i + 1];
+  if (lo == hi) return -1;
+  for (int j = lo + 1; j < hi; ++j)
+    if (keys[j] != keys[lo]) return FPX_EPX_KEY_LIST;
+  return keys[lo];
+}
+
 // ---- fpx_epx_lead ------------------------------------------------------------------------------------------------------
 struct LdBatch {
   int m;
@@ -41,7 +53,11 @@ struct LdBatch {
   const int32_t* number;
   const int32_t* b_ord;
   const int32_t* at;
-  const int32_t* key;
+  const int32_t* key;      // -1 = Noop; null in the key-list form
+  const int32_t* key_off;  // key-list form (else null), as HpBatch's: checked on the host, P pairs, uniq from k_mk_pairs
+  const int32_t* keys;
+  const uint8_t* uniq;
+  int P;
   const uint8_t* is_set;
   const int32_t* triple;
   const uint8_t* avoid;
@@ -49,7 +65,7 @@ struct LdBatch {
   int32_t* dend;      // [m] out
   uint8_t* skip;      // [m] scratch: the reference would have died (:662-682)
   uint8_t* act;       // [n][m] K7's gate table
-  uint2* kv;          // [n][m] K7's sort pairs
+  uint2* kv;          // [n][m] K7's sort pairs; key lists: [n][P]
   const int32_t* reply_deps;  // [m][n][n] from k_hp_reply
   const int32_t* reply_end;   // [m][n]
   uint32_t run_id;
@@ -58,7 +74,8 @@ struct LdBatch {
 __global__ void __launch_bounds__(256) k_ld_validate(const EpxState st, const LdBatch b) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= b.m) return;
-  const int n = st.n, L = b.leader[i], x = b.number[i], bo = b.b_ord[i], at = b.at[i], k = b.key[i];
+  const int n = st.n, L = b.leader[i], x = b.number[i], bo = b.b_ord[i], at = b.at[i];
+  const int k = b.key_off ? 0 : b.key[i];  // (key lists: checked on the host)
   bool ok = L >= 0 && L < n && x >= 0 && x < st.num_instances && bo >= 0 && bo < (1 << 27) && at >= 0 && at < n && k >= -1 &&
             k < st.num_keys;
   if (ok) ok = atomicExch(&st.cl_stamp[(size_t)L * st.num_instances + x], b.run_id) != b.run_id;
@@ -72,7 +89,7 @@ __global__ void __launch_bounds__(256) k_ld_gate(const EpxState st, const LdBatc
   const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= (long long)b.m * n) return;
   const int r = (int)(t / b.m), i = (int)(t % b.m);
-  const int L = b.leader[i], x = b.number[i], k = b.key[i];
+  const int L = b.leader[i], x = b.number[i], k = b.key_off ? 0 : b.key[i];
   int act = HP_NONE;
   // (a malformed message is reported by k_ld_validate; here it only must not index out of bounds)
   if (r == b.at[i] && L >= 0 && L < n && x >= 0 && x < st.num_instances) {
@@ -90,6 +107,11 @@ __global__ void __launch_bounds__(256) k_ld_gate(const EpxState st, const LdBatc
   b.act[o] = (uint8_t)act;
   const bool scanned = act == HP_PROCESS && k >= 0 && k < st.num_keys;
   const uint32_t flags = ((uint32_t)(b.is_set[i] ? 1 : 0) << EPX_SET_SHIFT) | ((uint32_t)(L & 7) << EPX_LEADER_SHIFT);
+  if (b.key_off) {  // one pair per (message, distinct key), in array order; the payload is the pair index (as k_hp_gate)
+    for (int j = b.key_off[i]; j < b.key_off[i + 1]; ++j)
+      b.kv[(size_t)r * b.P + j] = make_uint2((scanned && b.uniq[j] ? (uint32_t)b.keys[j] : (uint32_t)st.num_keys) | flags, (uint32_t)j);
+    return;
+  }
   b.kv[o] = make_uint2((scanned ? (uint32_t)k : (uint32_t)st.num_keys) | flags, (uint32_t)i);
 }
 
@@ -112,7 +134,7 @@ __global__ void __launch_bounds__(256) k_ld_install(const EpxState st, const Epx
     end = b.reply_end[(size_t)i * N + r];
     const size_t c = ((size_t)r * N + b.leader[i]) * st.num_instances + b.number[i];
     ls.head[c] = make_int4(ls_pack(LS_PRE_ACCEPTING, b.avoid[i] ? 1 : 0, b.is_set[i] ? 1 : 0, 1u << r), b.b_ord[i] * 8 + r,
-                           b.triple[i], b.key[i]);
+                           b.triple[i], ls_key_word(b.key, b.key_off, b.keys, i));
     int32_t* row = ls.resp + (c * N + r) * (N + 2);
     row[0] = 0;  // sequence numbers are 0 with top-k dependencies (:575-578, 599)
 #pragma unroll

@@ -271,7 +271,9 @@ struct LaBatch {
   const int32_t* number;
   const int32_t* at;
   const int32_t* b_ord;
-  const int32_t* key;
+  const int32_t* key;      // -1 = Noop; null in the key-list form
+  const int32_t* key_off;  // key-list form (else null): checked on the host
+  const int32_t* keys;
   const uint8_t* is_set;
   const int32_t* triple;
   const int32_t* seq;   // may be null: 0
@@ -283,7 +285,7 @@ struct LaBatch {
 __global__ void __launch_bounds__(256) k_la_validate(const EpxState st, const LaBatch b) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= b.m) return;
-  const int n = st.n, L = b.leader[i], x = b.number[i], bo = b.b_ord[i], at = b.at[i], k = b.key[i];
+  const int n = st.n, L = b.leader[i], x = b.number[i], bo = b.b_ord[i], at = b.at[i], k = b.key_off ? 0 : b.key[i];
   bool ok = L >= 0 && L < n && x >= 0 && x < st.num_instances && bo >= 0 && bo < (1 << 27) && at >= 0 && at < n && k >= -1 &&
             k < st.num_keys;
   if (ok && b.deps[(size_t)i * n] != -1) {  // fpx_epx_handle_commit's rules, as an Accept of the inbox
@@ -323,7 +325,8 @@ __global__ void __launch_bounds__(256) k_la_install(const EpxState st, const Epx
   st.cl_dend[c] = end, row[1 + N] = end;
   // updateConflictIndex (:763): the replica may never have seen the instance.  TopOne.put is a maximum, instances are
   // pairwise distinct and nothing of this call reads the index, so the order of the puts does not show
-  if (b.key[i] >= 0) index_put(st, r, b.key[i], b.is_set[i], L, x);
+  index_put_cmd(st, r, b.key, b.key_off, b.keys, i, b.is_set[i], L, x);  // (every key of a list; a Noop, no keys: nothing)
   // Accepting with the replica's own AcceptOk, the triple in its row (:765-790)
-  ls.head[c] = make_int4(ls_pack(LS_ACCEPTING, 0, b.is_set[i] ? 1 : 0, 1u << r), ballot, b.triple[i], b.key[i]);
+  ls.head[c] = make_int4(ls_pack(LS_ACCEPTING, 0, b.is_set[i] ? 1 : 0, 1u << r), ballot, b.triple[i],
+                         ls_key_word(b.key, b.key_off, b.keys, i));
 }

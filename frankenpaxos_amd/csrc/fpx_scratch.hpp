@@ -174,4 +174,17 @@ inline EpxInboxScratch lay_epx_inbox(Carver& c, size_t m, size_t n, size_t tiles
   return s;
 }
 
+// the key-list form (fpx_epx_replica_inbox_mk): the above, sized by the m messages, and the pieces sized by the P (message,
+// key) pairs.  (Under the sanitizers: tests/epx_inbox_mk_scratch_main.cpp.)
+struct EpxInboxMkScratch {
+  EpxInboxScratch msg;
+  MkPairScratch pair;
+};
+inline EpxInboxMkScratch lay_epx_inbox_mk(Carver& c, size_t m, size_t P, size_t n, size_t tiles) {
+  EpxInboxMkScratch s;
+  s.msg = lay_epx_inbox(c, m, n, tiles);
+  s.pair = lay_mk_pairs(c, P);
+  return s;
+}
+
 }  // namespace fpx

@@ -23,6 +23,7 @@ IN_PRE_ACCEPT, IN_ACCEPT, IN_COMMIT, IN_PREPARE = 0, 1, 2, 3
 (RI_IGNORED, RI_PRE_ACCEPT_OK, RI_PRE_ACCEPT_OK_AGAIN, RI_ACCEPT_OK, RI_ACCEPT_OK_AGAIN, RI_LEARNT, RI_PREPARE_OK, RI_NACK,
  RI_COMMIT_BACK) = range(9)
 INBOX_MAX = 1 << 24
+KEY_LIST = -2         # FPX_EPX_KEY_LIST: a leader state's key word for a list of two or more distinct keys
 
 
 class FpxEpxConfig(C.Structure):
@@ -291,6 +292,21 @@ class EPaxos:
                                  p(dend))
         return st, deps, dend
 
+    def lead_mk(self, leader, number, at, ballot_ordering, key_lists, is_set, triple_id, avoid_fast_path=None):
+        """lead() with a key list per command (an empty list: no conflicts, no put); the leader state keeps the key, -1 or
+        KEY_LIST for one / no / several distinct keys"""
+        a32 = lambda x: np.ascontiguousarray(x, dtype=np.int32)
+        off, keys = self.key_lists(key_lists)
+        leader, number, at, bo, tr = a32(leader), a32(number), a32(at), a32(ballot_ordering), a32(triple_id)
+        m = len(leader)
+        is_set = np.ascontiguousarray(is_set, dtype=np.uint8)
+        avoid = np.zeros(m, np.uint8) if avoid_fast_path is None else np.ascontiguousarray(avoid_fast_path, dtype=np.uint8)
+        deps, dend = np.zeros((m, self.n), np.int32), np.zeros(m, np.int32)
+        p = lambda a: a.ctypes.data
+        st = self.L.fpx_epx_lead_mk(self._h, m, p(leader), p(number), p(at), p(bo), p(off), p(keys), p(is_set), p(tr), p(avoid),
+                                    p(deps), p(dend))
+        return st, deps, dend
+
     def leader_replies(self, kind, to, leader, number, ballot_ordering, ballot_replica, replica_index, sequence_number=None,
                        deps=None, deps_values_end=None):
         """one burst of PreAcceptOk (0) / AcceptOk (1) / Nack (2) / defaultToSlowPath-timer (3) events in delivery order:
@@ -386,6 +402,20 @@ class EPaxos:
         return self.L.fpx_epx_lead_accept(self._h, m, p(leader), p(number), p(at), p(bo), p(key), p(is_set), p(tr), p(seq),
                                           p(deps), p(dend))
 
+    def lead_accept_mk(self, leader, number, at, ballot_ordering, key_lists, is_set, triple_id, sequence_number, deps,
+                       deps_values_end=None):
+        """lead_accept() with a key list per triple -> status"""
+        a32 = lambda x: None if x is None else np.ascontiguousarray(x, dtype=np.int32)
+        off, keys = self.key_lists(key_lists)
+        leader, number, at, bo, tr = a32(leader), a32(number), a32(at), a32(ballot_ordering), a32(triple_id)
+        m = len(leader)
+        is_set = np.ascontiguousarray(is_set, dtype=np.uint8)
+        seq, dend = a32(sequence_number), a32(deps_values_end)
+        deps = a32(deps).reshape(m, self.n)
+        p = lambda a: None if a is None else a.ctypes.data
+        return self.L.fpx_epx_lead_accept_mk(self._h, m, p(leader), p(number), p(at), p(bo), p(off), p(keys), p(is_set), p(tr),
+                                             p(seq), p(deps), p(dend))
+
     def read_recovery_state(self, replica, leader, number):
         """[n, 3]: per responder the PrepareOk's status, voteBallot (encoded) and triple id; -1s where there is none"""
         out = np.zeros((self.n, 3), np.int32)
@@ -426,8 +456,42 @@ class EPaxos:
         if st:
             raise FpxError(st, "fpx_epx_replica_inbox_dev")
 
+    def replica_inbox_mk(self, kind, to, leader, number, ballot_ordering, ballot_replica, key_lists, is_set, triple_id, deps,
+                         deps_values_end=None):
+        """replica_inbox() with a key list per message (a Prepare's is not read; an empty list behaves as a Noop)"""
+        a32 = lambda x: np.ascontiguousarray(x, dtype=np.int32)
+        off, keys = self.key_lists(key_lists)
+        kind, to, leader, number = a32(kind), a32(to), a32(leader), a32(number)
+        bo, br, tr = a32(ballot_ordering), a32(ballot_replica), a32(triple_id)
+        is_set = np.ascontiguousarray(is_set, dtype=np.uint8)
+        m = len(kind)
+        deps = a32(deps).reshape(m, self.n)
+        dend = None if deps_values_end is None else a32(deps_values_end)
+        outcome, ob, os_, oend, otr = (np.full(m, -9, np.int32) for _ in range(5))
+        odeps = np.full((m, self.n), -9, np.int32)
+        p = lambda a: None if a is None else a.ctypes.data
+        st = self.L.fpx_epx_replica_inbox_mk(self._h, m, p(kind), p(to), p(leader), p(number), p(bo), p(br), p(off), p(keys),
+                                             p(is_set), p(tr), p(deps), p(dend), p(outcome), p(ob), p(os_), p(odeps), p(oend),
+                                             p(otr))
+        return st, outcome, ob, os_, odeps, oend, otr
+
+    def replica_inbox_mk_dev(self, kind, to, leader, number, ballot_ordering, ballot_replica, key_offsets, keys, is_set,
+                             triple_id, deps, deps_values_end=None, outcome=None, out_ballot=None, out_status=None,
+                             out_deps=None, out_values_end=None, out_triple=None, num_pairs=None):
+        """the same on device tensors (int32; is_set uint8): key_offsets[m + 1] and keys; num_pairs (default: keys.numel())
+        is checked against key_offsets[m] on the device.  Enqueued on the context's stream; the status comes with sync()"""
+        d = lambda t: None if t is None else t.data_ptr()
+        num_pairs = keys.numel() if num_pairs is None else int(num_pairs)
+        st = self.L.fpx_epx_replica_inbox_mk_dev(self._h, kind.numel(), d(kind), d(to), d(leader), d(number), d(ballot_ordering),
+                                                 d(ballot_replica), d(key_offsets), d(keys), num_pairs, d(is_set), d(triple_id),
+                                                 d(deps), d(deps_values_end), d(outcome), d(out_ballot), d(out_status),
+                                                 d(out_deps), d(out_values_end), d(out_triple))
+        if st:
+            raise FpxError(st, "fpx_epx_replica_inbox_mk_dev")
+
     def read_leader_state(self, replica, leader, number):
-        """(phase [0 when not live], ballot, avoid_fast_path, triple id, key, is_set, response mask, stored phase),
+        """(phase [0 when not live], ballot, avoid_fast_path, triple id, key [-1: none, KEY_LIST: two or more distinct keys,
+        the caller holds the list], is_set, response mask, stored phase),
         responses[n, n + 2] (row q: sequence number, n watermarks, values_end)"""
         out = np.zeros(8, np.int32)
         resp = np.zeros((self.n, self.n + 2), np.int32)

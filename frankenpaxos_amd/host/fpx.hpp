@@ -946,6 +946,7 @@ struct LeadRequest {
   int at = 0;                  // the replica that leads it, in ballot (ballotOrdering, at)
   int32_t ballotOrdering = 0;
   Command command{-1, false};  // key -1 = Noop
+  std::vector<int32_t> keys;   // a multi-key get / set (command.isSet says which): its key list, in place of command.key
   int32_t tripleId = -1;
   bool avoidFastPath = false;
 };
@@ -1025,6 +1026,7 @@ struct LeadAcceptRequest {
   int at = 0;
   int32_t ballotOrdering = 0;
   Command command{-1, false};
+  std::vector<int32_t> keys;             // a multi-key get / set: its key list, in place of command.key
   int32_t tripleId = -1;
   int32_t sequenceNumber = 0;
   std::vector<int32_t> dependencies;     // n watermarks; {-1, ...}: known by tripleId only
@@ -1160,8 +1162,13 @@ class PreAcceptEngine {
       leader[i] = q.instance.replicaIndex, number[i] = q.instance.instanceNumber, at[i] = q.at, bo[i] = q.ballotOrdering;
       key[i] = q.command.key, isSet[i] = q.command.isSet ? 1 : 0, tr[i] = q.tripleId, avoid[i] = q.avoidFastPath ? 1 : 0;
     }
-    const int32_t st = fpx_epx_lead(epx_, m, leader.data(), number.data(), at.data(), bo.data(), key.data(), isSet.data(),
-                                    tr.data(), avoid.data(), deps.data(), dend.data());
+    // requests that all have one key (or none: a Noop) take the single-key call, any other batch its key-list form
+    std::vector<int32_t> off, keys;
+    const bool lists = keyLists(requests, &key, &off, &keys);
+    const int32_t st = lists ? fpx_epx_lead_mk(epx_, m, leader.data(), number.data(), at.data(), bo.data(), off.data(), keys.data(),
+                                               isSet.data(), tr.data(), avoid.data(), deps.data(), dend.data())
+                             : fpx_epx_lead(epx_, m, leader.data(), number.data(), at.data(), bo.data(), key.data(), isSet.data(),
+                                            tr.data(), avoid.data(), deps.data(), dend.data());
     if (st != FPX_EFATAL_PROTOCOL) check(st, "Replica.transitionToPreAcceptPhase");
     std::vector<LeadResult> out(m);
     for (int i = 0; i < m; ++i) {
@@ -1276,8 +1283,12 @@ class PreAcceptEngine {
         std::copy(q.dependencies.begin(), q.dependencies.end(), deps.begin() + (size_t)i * n_);
       }
     }
-    const int32_t st = fpx_epx_lead_accept(epx_, m, leader.data(), number.data(), at.data(), bo.data(), key.data(), isSet.data(),
-                                           tr.data(), seq.data(), deps.data(), dend.data());
+    std::vector<int32_t> off, keys;
+    const bool lists = keyLists(requests, &key, &off, &keys);
+    const int32_t st = lists ? fpx_epx_lead_accept_mk(epx_, m, leader.data(), number.data(), at.data(), bo.data(), off.data(),
+                                                      keys.data(), isSet.data(), tr.data(), seq.data(), deps.data(), dend.data())
+                             : fpx_epx_lead_accept(epx_, m, leader.data(), number.data(), at.data(), bo.data(), key.data(),
+                                                   isSet.data(), tr.data(), seq.data(), deps.data(), dend.data());
     if (st != FPX_EFATAL_PROTOCOL) check(st, "Replica.transitionToAcceptPhase");
     std::vector<bool> ok(m, true);
     if (st == FPX_EFATAL_PROTOCOL) {
@@ -1288,6 +1299,25 @@ class PreAcceptEngine {
       }
     }
     return ok;
+  }
+
+  // the key lists of a batch of requests with `command` and `keys`: false when every request has at most one key -- then
+  // *key holds them (-1 = none) for the single-key call -- else the CSR pair (a request without `keys`: its command.key)
+  template <typename Request>
+  static bool keyLists(const std::vector<Request>& requests, std::vector<int32_t>* key, std::vector<int32_t>* off,
+                       std::vector<int32_t>* keys) {
+    bool lists = false;
+    off->assign(1, 0);
+    for (size_t i = 0; i < requests.size(); ++i) {
+      const Request& q = requests[i];
+      lists = lists || q.keys.size() > 1;
+      if (q.keys.empty() && q.command.key >= 0) keys->push_back(q.command.key);
+      keys->insert(keys->end(), q.keys.begin(), q.keys.end());
+      off->push_back((int32_t)keys->size());
+      (*key)[i] = q.keys.empty() ? q.command.key : q.keys[0];
+    }
+    if (keys->empty()) keys->push_back(0);  // (data() of an empty vector may be null)
+    return lists;
   }
 
   CmdLogEntry cmdLog(int replica, Instance instance) {

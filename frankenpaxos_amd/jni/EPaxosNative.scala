@@ -20,8 +20,8 @@
 //                      thriftyOtherReplicas(fastQuorumSize - 1); PreAcceptOk / AcceptOk / Nack are enqueued, and a tick
 //                      flushes them through ONE Native.epxLeaderReplies call, after which Commit goes to the other
 //                      replicas or Accept to slowQuorumSize - 1 of them.  The actor keeps the defaultToSlowPath and resend
-//                      timers (a fired defaultToSlowPath timer becomes a kind-3 event of the next burst).  Limits: single-key
-//                      commands and Noops (no multi-key lead); without originateRecovery there is no Preparing phase:
+//                      timers (a fired defaultToSlowPath timer becomes a kind-3 event of the next burst).  Without
+//                      originateRecovery there is no Preparing phase:
 //                      recovery is answered but not originated (a Nack that asks for it, outcome 6, is logged).
 //
 //                      originateRecovery = true (off by default; with remotePeers, the engine created with recovery = true):
@@ -31,13 +31,12 @@
 //                      Prepare goes to slowQuorumSize - 1 others.  PrepareOks are enqueued and a tick flushes them through
 //                      ONE Native.epxRecoveryReplies call; its decisions are applied in the same flush with Native.epxLead
 //                      (avoidFastPath) or Native.epxLeadAccept, and the PreAccept or Accept is sent.  The actor keeps the
-//                      resend-Prepares timer.  Limits: single-key commands and Noops.
+//                      resend-Prepares timer.
 //
 //                      inboxBurst = true (off by default): what replicas OUTSIDE send this one -- PreAccept, Accept, Prepare,
 //                      Commit -- is enqueued as it arrives and a tick flushes it through ONE Native.epxReplicaInbox call, in
 //                      arrival order: a leader's PreAccept that lands twice in one burst is answered twice, and an Accept is
 //                      handleAccept at this replica alone (no proposer step on the hosted context, no commit on one AcceptOk).
-//                      Limits: single-key commands and Noops.
 //
 // The same natives driven on wire bytes -- two conflicting commands met in different orders, differing PreAcceptOks, the
 // slow path, Accept, AcceptOk, Commit -- against the oracle: tests/test_jni_shim.py::test_an_epaxos_slow_path_commit_...
@@ -142,7 +141,7 @@ class GpuEPaxosReplica[Transport <: frankenpaxos.Transport[Transport]](
     // Native.epxLeaderReplies (the engine needs leaderState = true).  Default off: all n replicas in this process.
     remotePeers: Boolean = false,
     // true: what replicas outside send this one -- PreAccept, Accept, Prepare, Commit -- goes through ONE
-    // Native.epxReplicaInbox call per flush, in arrival order, instances repeated freely (single-key commands and Noops).
+    // Native.epxReplicaInbox call per flush, in arrival order, instances repeated freely.
     // Default off: one native call per kind of message, as below.
     inboxBurst: Boolean = false,
     // true (needs remotePeers and an engine with recovery = true): this actor originates an instance's recovery through
@@ -360,12 +359,17 @@ class GpuEPaxosReplica[Transport <: frankenpaxos.Transport[Transport]](
   // transitionToPreAcceptPhase (:633-729) of a batch of pairwise distinct instances at THIS replica: the one place that
   // calls Native.epxLead -- for ClientRequests, and for the recoveries that start over (originateRecovery).  Returns the
   // dependencies of the PreAccepts to send: (m x n watermarks, m values ends)
-  private def leadHere(leader: Array[Int], number: Array[Int], ballotOrdering: Array[Int], key: Array[Int], isSet: Array[Byte],
-                       tripleId: Array[Int], avoidFastPath: Array[Byte]): (Array[Int], Array[Int]) = {
+  private def leadHere(leader: Array[Int], number: Array[Int], ballotOrdering: Array[Int], keys: Seq[Option[Array[Int]]],
+                       isSet: Array[Byte], tripleId: Array[Int], avoidFastPath: Array[Byte]): (Array[Int], Array[Int]) = {
     val m = leader.length
     val deps = new Array[Int](m * n); val ends = new Array[Int](m)
-    val st = Native.epxLead(engine.handle, m, n, leader, number, Array.fill(m)(index), ballotOrdering, key, isSet, tripleId,
-                            avoidFastPath, deps, ends)
+    // (engine.singleKeys: the natives this has always gone to when every command has one key, else their Mk forms)
+    val st = if (engine.singleKeys(keys))
+               Native.epxLead(engine.handle, m, n, leader, number, Array.fill(m)(index), ballotOrdering, engine.singleKey(keys), isSet,
+                              tripleId, avoidFastPath, deps, ends)
+             else
+               Native.epxLeadMk(engine.handle, m, n, leader, number, Array.fill(m)(index), ballotOrdering, engine.keyOffsets(keys),
+                                engine.keyList(keys), isSet, tripleId, avoidFastPath, deps, ends)
     if (st == 9) logger.fatal("transitionToPreAcceptPhase: the instance is committed or known in a larger ballot (:662-682).")
     Native.check(st, logger)
     (deps, ends)
@@ -375,16 +379,16 @@ class GpuEPaxosReplica[Transport <: frankenpaxos.Transport[Transport]](
   private def leadRequests(): Unit = {
     val m = requests.size
     logger.check(engine.hasLeaderState)
-    val leader = Array.fill(m)(index); val number = new Array[Int](m); val key = new Array[Int](m); val isSet = new Array[Byte](m)
+    val leader = Array.fill(m)(index); val number = new Array[Int](m); val isSet = new Array[Byte](m)
+    val keys = new Array[Option[Array[Int]]](m)
     val first = engine.triples.size
     for (((_, r), i) <- requests.zipWithIndex) {
       number(i) = engine.nextNumber(index); engine.nextNumber(index) += 1
       val (k, set) = engine.classify(r.command)
-      if (k.length != 1) logger.fatal("GpuEPaxosReplica(remotePeers): single-key commands only; a multi-key lead is not built.")
-      key(i) = k(0); isSet(i) = if (set) 1 else 0
+      keys(i) = Some(k); isSet(i) = if (set) 1 else 0
       engine.triples += CommandOrNoop().withCommand(r.command)
     }
-    val (deps, ends) = leadHere(leader, number, Array.fill(m)(0), key, isSet, Array.tabulate(m)(first + _), new Array[Byte](m))
+    val (deps, ends) = leadHere(leader, number, Array.fill(m)(0), keys, isSet, Array.tabulate(m)(first + _), new Array[Byte](m))
     val ballot = Ballot(0, index)                                                                               // defaultBallot :453
     for (i <- 0 until m) {
       val instance = Instance(index, number(i))
@@ -530,9 +534,8 @@ class GpuEPaxosReplica[Transport <: frankenpaxos.Transport[Transport]](
       val m = toLead.size
       val id = toLead.map(i => if (outcome(i) == 4) noopTriple else decision(k + i)).toArray
       val cls = id.map(t => engine.classify(engine.triples(t)))
-      if (cls.exists(_._1.exists(_.length != 1))) logger.fatal("GpuEPaxosReplica(originateRecovery): single-key commands and Noops only.")
       val (lDeps, lEnds) = leadHere(toLead.map(ev(_).instance.replicaIndex).toArray, toLead.map(ev(_).instance.instanceNumber).toArray,
-                                    toLead.map(ballotOf(_).ordering).toArray, cls.map(_._1.map(_(0)).getOrElse(-1)),
+                                    toLead.map(ballotOf(_).ordering).toArray, cls.map(_._1),
                                     cls.map(c => (if (c._2) 1 else 0).toByte), id, Array.fill(m)(1.toByte))
       for ((i, j) <- toLead.zipWithIndex) {
         val instance = ev(i).instance
@@ -547,13 +550,17 @@ class GpuEPaxosReplica[Transport <: frankenpaxos.Transport[Transport]](
       val m = toAccept.size
       val id = toAccept.map(i => decision(k + i)).toArray
       val cls = id.map(t => engine.classify(engine.triples(t)))
-      if (cls.exists(_._1.exists(_.length != 1))) logger.fatal("GpuEPaxosReplica(originateRecovery): single-key commands and Noops only.")
+      val aKeys = cls.map(_._1).toSeq; val aSet = cls.map(c => (if (c._2) 1 else 0).toByte)
+      val (aLeader, aNumber) = (toAccept.map(ev(_).instance.replicaIndex).toArray, toAccept.map(ev(_).instance.instanceNumber).toArray)
       val aDeps = toAccept.flatMap(i => outDeps.slice(i * n, (i + 1) * n)).toArray
       val aEnds = toAccept.map(i => decision(4 * k + i)).toArray; val aSeq = toAccept.map(i => decision(3 * k + i)).toArray
-      val st2 = Native.epxLeadAccept(engine.handle, m, n, toAccept.map(ev(_).instance.replicaIndex).toArray,
-                                     toAccept.map(ev(_).instance.instanceNumber).toArray, Array.fill(m)(index),
-                                     toAccept.map(ballotOf(_).ordering).toArray, cls.map(_._1.map(_(0)).getOrElse(-1)),
-                                     cls.map(c => (if (c._2) 1 else 0).toByte), id, aSeq, aDeps, aEnds)
+      val aOrd = toAccept.map(ballotOf(_).ordering).toArray
+      val st2 = if (engine.singleKeys(aKeys))
+                  Native.epxLeadAccept(engine.handle, m, n, aLeader, aNumber, Array.fill(m)(index), aOrd, engine.singleKey(aKeys), aSet,
+                                       id, aSeq, aDeps, aEnds)
+                else
+                  Native.epxLeadAcceptMk(engine.handle, m, n, aLeader, aNumber, Array.fill(m)(index), aOrd, engine.keyOffsets(aKeys),
+                                         engine.keyList(aKeys), aSet, id, aSeq, aDeps, aEnds)
       if (st2 == 9) logger.fatal("transitionToAcceptPhase: the instance is committed or known in a larger ballot (:740-757).")
       Native.check(st2, logger)
       for ((i, j) <- toAccept.zipWithIndex) {
@@ -590,12 +597,11 @@ class GpuEPaxosReplica[Transport <: frankenpaxos.Transport[Transport]](
     peerInbox.clear()
     if (remotePeers) for (e <- ev) if (e.kind == 2) stopLeading(e.instance) else yieldTo(e.instance, e.ballot)
     if (originateRecovery) for (e <- ev) if (e.kind == 2) { stopRecoverTimer(e.instance); stopRecovering(e.instance) } else resetRecoverTimer(e.instance)
-    val key = new Array[Int](k); val isSet = new Array[Byte](k); val tripleId = Array.fill(k)(-1)
+    val keys = Array.fill[Option[Array[Int]]](k)(None); val isSet = new Array[Byte](k); val tripleId = Array.fill(k)(-1)
     val deps = new Array[Int](k * n); val ends = new Array[Int](k)
     for ((e, i) <- ev.zipWithIndex; c <- e.commandOrNoop; d <- e.dependencies) {
       val (ks, set) = engine.classify(c)
-      if (ks.exists(_.length != 1)) logger.fatal("GpuEPaxosReplica(inboxBurst): single-key commands and Noops only.")
-      key(i) = ks.map(_(0)).getOrElse(-1); isSet(i) = if (set) 1 else 0
+      keys(i) = ks; isSet(i) = if (set) 1 else 0
       // (originateRecovery: equal commands get equal ids -- the own PrepareOk's triple id meets the peers' in handlePrepareOk)
       if (originateRecovery) tripleId(i) = engine.intern(c) else { tripleId(i) = engine.triples.size; engine.triples += c }
       val (w, end) = (watermarks(d), ownEnd(e.instance, d))
@@ -605,9 +611,16 @@ class GpuEPaxosReplica[Transport <: frankenpaxos.Transport[Transport]](
       if (e.kind == 1) engine.tripleDeps(tripleId(i)) = (w, end)
     }
     val outcome = new Array[Int](k); val reply = new Array[Int](4 * k); val outDeps = new Array[Int](k * n)
-    Native.check(Native.epxReplicaInbox(engine.handle, k, n, ev.map(_.kind), Array.fill(k)(index), ev.map(_.instance.replicaIndex),
-                                        ev.map(_.instance.instanceNumber), ev.map(_.ballot.ordering), ev.map(_.ballot.replicaIndex),
-                                        key, isSet, tripleId, deps, ends, outcome, reply, outDeps), logger)
+    // (a Prepare has no command: None, which is key -1 in the one form and an empty list in the other; neither is read)
+    Native.check(if (engine.singleKeys(keys))
+                   Native.epxReplicaInbox(engine.handle, k, n, ev.map(_.kind), Array.fill(k)(index), ev.map(_.instance.replicaIndex),
+                                          ev.map(_.instance.instanceNumber), ev.map(_.ballot.ordering), ev.map(_.ballot.replicaIndex),
+                                          engine.singleKey(keys), isSet, tripleId, deps, ends, outcome, reply, outDeps)
+                 else
+                   Native.epxReplicaInboxMk(engine.handle, k, n, ev.map(_.kind), Array.fill(k)(index),
+                                            ev.map(_.instance.replicaIndex), ev.map(_.instance.instanceNumber),
+                                            ev.map(_.ballot.ordering), ev.map(_.ballot.replicaIndex), engine.keyOffsets(keys),
+                                            engine.keyList(keys), isSet, tripleId, deps, ends, outcome, reply, outDeps), logger)
     var learnt = false
     for ((e, i) <- ev.zipWithIndex) {
       val back = chan[Replica[Transport]](e.src, Replica.serializer)

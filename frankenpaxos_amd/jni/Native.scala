@@ -267,6 +267,21 @@ object Native {
                                    isSet: Array[Byte], tripleId: Array[Int], depsIn: Array[Int],
                                    depsInValuesEnd: Array[Int], targetMask: Array[Byte], replies: Array[Byte],
                                    nackBallot: Array[Int], replyDeps: Array[Int], replyEndTriple: Array[Int]): Int
+  // ... and of the calls a hosted replica makes among REMOTE peers: epxReplicaInbox, epxLead, epxLeadAccept.  The leader
+  // state keeps one key word per instance (the key, -1 for no key, -2 for a list of two or more distinct keys): the
+  // caller holds the list by triple id
+  @native def epxReplicaInboxMk(handle: Long, m: Int, numReplicas: Int, kind: Array[Int], to: Array[Int], leader: Array[Int],
+                                number: Array[Int], ballotOrdering: Array[Int], ballotReplica: Array[Int],
+                                keyOffsets: Array[Int], keys: Array[Int], isSet: Array[Byte], tripleId: Array[Int],
+                                deps: Array[Int], depsValuesEnd: Array[Int], outcome: Array[Int], reply: Array[Int],
+                                outDeps: Array[Int]): Int
+  @native def epxLeadMk(handle: Long, m: Int, numReplicas: Int, leader: Array[Int], number: Array[Int], at: Array[Int],
+                        ballotOrdering: Array[Int], keyOffsets: Array[Int], keys: Array[Int], isSet: Array[Byte],
+                        tripleId: Array[Int], avoidFastPath: Array[Byte], deps: Array[Int], depsValuesEnd: Array[Int]): Int
+  @native def epxLeadAcceptMk(handle: Long, m: Int, numReplicas: Int, leader: Array[Int], number: Array[Int], at: Array[Int],
+                              ballotOrdering: Array[Int], keyOffsets: Array[Int], keys: Array[Int], isSet: Array[Byte],
+                              tripleId: Array[Int], sequenceNumber: Array[Int], deps: Array[Int],
+                              depsValuesEnd: Array[Int]): Int
   @native def epxReadCmdlog(handle: Long, numReplicas: Int, replica: Int, leader: Int, number: Int,
                             entry: Array[Int]): Int
   // multi-GPU: one context per GPU, one RCCL communicator over them (fpx_comm_*); the 128-byte id of

@@ -1084,6 +1084,99 @@ JNIEXPORT jint JNICALL Java_frankenpaxos_gpu_Native_epxHandlePreacceptMk(
   return st;
 }
 
+/* epxReplicaInbox with key lists (fpx_epx_replica_inbox_mk); the other arrays and the outputs are epxReplicaInbox's */
+JNIEXPORT jint JNICALL Java_frankenpaxos_gpu_Native_epxReplicaInboxMk(
+    JNIEnv* env, jclass cls, jlong h, jint m, jint numReplicas, jintArray kind, jintArray to, jintArray leader, jintArray number,
+    jintArray ballotOrdering, jintArray ballotReplica, jintArray keyOffsets, jintArray keys, jbyteArray isSet, jintArray tripleId,
+    jintArray deps, jintArray depsValuesEnd, jintArray outcome, jintArray reply, jintArray outDeps) {
+  if (m < 0 || numReplicas < 3 || !epx_n_is(h, numReplicas)) return FPX_EINVAL;
+  if (m == 0) return FPX_OK;
+  const jlong mn = (jlong)m * numReplicas;
+  if (!has(env, kind, m) || !has(env, to, m) || !has(env, leader, m) || !has(env, number, m) || !has(env, ballotOrdering, m) ||
+      !has(env, ballotReplica, m) || !has(env, isSet, m) || !has(env, tripleId, m) || !has(env, deps, mn) ||
+      !opt(env, depsValuesEnd, m) || !opt(env, outcome, m) || !opt(env, reply, 4 * (jlong)m) || !opt(env, outDeps, mn))
+    return FPX_EINVAL;
+  jint *off, *k;
+  int32_t st = in_key_lists(env, m, keyOffsets, keys, &off, &k);
+  jint *kd = in_ints(env, kind, m), *t = in_ints(env, to, m), *l = in_ints(env, leader, m), *nu = in_ints(env, number, m),
+       *bo = in_ints(env, ballotOrdering, m), *br = in_ints(env, ballotReplica, m), *tr = in_ints(env, tripleId, m),
+       *d = in_ints(env, deps, mn);
+  jbyte* is = in_bytes(env, isSet, m);
+  jint* de = depsValuesEnd ? in_ints(env, depsValuesEnd, m) : NULL;
+  jint *oc = out_buf(outcome, m, 4), *rp = out_buf(reply, 4 * (jlong)m, 4), *od = out_buf(outDeps, mn, 4);
+  if (st == FPX_OK)
+    st = (!kd || !t || !l || !nu || !bo || !br || !tr || !d || !is || (depsValuesEnd && !de) || (outcome && !oc) ||
+          (reply && !rp) || (outDeps && !od))
+             ? FPX_ENOMEM
+             : fpx_epx_replica_inbox_mk((fpx_epx*)(intptr_t)h, m, kd, t, l, nu, bo, br, off, k, (const uint8_t*)is, tr, d, de, oc,
+                                        rp, rp ? rp + m : NULL, od, rp ? rp + 2 * (size_t)m : NULL,
+                                        rp ? rp + 3 * (size_t)m : NULL);
+  if (st == FPX_OK) {
+    put_ints(env, outcome, m, oc); put_ints(env, reply, 4 * (jlong)m, rp); put_ints(env, outDeps, mn, od);
+  }
+  free(off); free(k); free(kd); free(t); free(l); free(nu); free(bo); free(br); free(tr); free(d); free(is); free(de); free(oc);
+  free(rp); free(od);
+  return st;
+}
+
+/* epxLead with key lists (fpx_epx_lead_mk) */
+JNIEXPORT jint JNICALL Java_frankenpaxos_gpu_Native_epxLeadMk(JNIEnv* env, jclass cls, jlong h, jint m, jint numReplicas,
+                                                              jintArray leader, jintArray number, jintArray at,
+                                                              jintArray ballotOrdering, jintArray keyOffsets, jintArray keys,
+                                                              jbyteArray isSet, jintArray tripleId, jbyteArray avoidFastPath,
+                                                              jintArray deps, jintArray depsValuesEnd) {
+  if (m < 0 || numReplicas < 3 || !epx_n_is(h, numReplicas)) return FPX_EINVAL;
+  if (m == 0) return FPX_OK;
+  const jlong mn = (jlong)m * numReplicas;
+  if (!has(env, leader, m) || !has(env, number, m) || !has(env, at, m) || !has(env, ballotOrdering, m) || !has(env, isSet, m) ||
+      !has(env, tripleId, m) || !has(env, avoidFastPath, m) || !opt(env, deps, mn) || !opt(env, depsValuesEnd, m))
+    return FPX_EINVAL;
+  jint *off, *k;
+  int32_t st = in_key_lists(env, m, keyOffsets, keys, &off, &k);
+  jint *l = in_ints(env, leader, m), *nu = in_ints(env, number, m), *a = in_ints(env, at, m),
+       *bo = in_ints(env, ballotOrdering, m), *tr = in_ints(env, tripleId, m);
+  jbyte *is = in_bytes(env, isSet, m), *av = in_bytes(env, avoidFastPath, m);
+  jint *d = out_buf(deps, mn, 4), *de = out_buf(depsValuesEnd, m, 4);
+  if (st == FPX_OK)
+    st = (!l || !nu || !a || !bo || !tr || !is || !av || (deps && !d) || (depsValuesEnd && !de))
+             ? FPX_ENOMEM
+             : fpx_epx_lead_mk((fpx_epx*)(intptr_t)h, m, l, nu, a, bo, off, k, (const uint8_t*)is, tr, (const uint8_t*)av, d, de);
+  if (st == FPX_OK || st == FPX_EFATAL_PROTOCOL) {
+    put_ints(env, deps, mn, d);
+    put_ints(env, depsValuesEnd, m, de);
+  }
+  free(off); free(k); free(l); free(nu); free(a); free(bo); free(tr); free(is); free(av); free(d); free(de);
+  return st;
+}
+
+/* epxLeadAccept with key lists (fpx_epx_lead_accept_mk) */
+JNIEXPORT jint JNICALL Java_frankenpaxos_gpu_Native_epxLeadAcceptMk(JNIEnv* env, jclass cls, jlong h, jint m, jint numReplicas,
+                                                                    jintArray leader, jintArray number, jintArray at,
+                                                                    jintArray ballotOrdering, jintArray keyOffsets,
+                                                                    jintArray keys, jbyteArray isSet, jintArray tripleId,
+                                                                    jintArray sequenceNumber, jintArray deps,
+                                                                    jintArray depsValuesEnd) {
+  if (m < 0 || numReplicas < 3 || !epx_n_is(h, numReplicas)) return FPX_EINVAL;
+  if (m == 0) return FPX_OK;
+  const jlong mn = (jlong)m * numReplicas;
+  if (!has(env, leader, m) || !has(env, number, m) || !has(env, at, m) || !has(env, ballotOrdering, m) || !has(env, isSet, m) ||
+      !has(env, tripleId, m) || !opt(env, sequenceNumber, m) || !has(env, deps, mn) || !opt(env, depsValuesEnd, m))
+    return FPX_EINVAL;
+  jint *off, *k;
+  int32_t st = in_key_lists(env, m, keyOffsets, keys, &off, &k);
+  jint *l = in_ints(env, leader, m), *nu = in_ints(env, number, m), *a = in_ints(env, at, m),
+       *bo = in_ints(env, ballotOrdering, m), *tr = in_ints(env, tripleId, m), *d = in_ints(env, deps, mn);
+  jbyte* is = in_bytes(env, isSet, m);
+  jint* sq = sequenceNumber ? in_ints(env, sequenceNumber, m) : NULL;
+  jint* de = depsValuesEnd ? in_ints(env, depsValuesEnd, m) : NULL;
+  if (st == FPX_OK)
+    st = (!l || !nu || !a || !bo || !tr || !d || !is || (sequenceNumber && !sq) || (depsValuesEnd && !de))
+             ? FPX_ENOMEM
+             : fpx_epx_lead_accept_mk((fpx_epx*)(intptr_t)h, m, l, nu, a, bo, off, k, (const uint8_t*)is, tr, sq, d, de);
+  free(off); free(k); free(l); free(nu); free(a); free(bo); free(tr); free(d); free(is); free(sq); free(de);
+  return st;
+}
+
 /* entry = kind, ballot, voteBallot, triple id, the replica's largestBallot, then the n stored dependency watermarks
  * and the own column's values end (5 + n + 1 ints) */
 JNIEXPORT jint JNICALL Java_frankenpaxos_gpu_Native_epxReadCmdlog(JNIEnv* env, jclass cls, jlong h, jint numReplicas,

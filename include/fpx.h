@@ -975,11 +975,21 @@ int32_t fpx_epx_handle_commit_mk(fpx_epx* epx, int32_t m, const int32_t* leader,
  *   vote ballot, is where the reference dies (:662-682): FPX_EFATAL_PROTOCOL, that message is skipped (its deps are zeros),
  *   the others are applied.  FPX_EINVAL with nothing applied and no output written: the flag missing, an instance outside the
  *   command log, a key outside the index (< -1 or >= num_keys), at[i] outside 0..n-1, ballot_ordering outside 0 .. 2^27 - 1.
- *   Single-key commands and Noops only. */
+ *   Single-key commands and Noops; key lists: fpx_epx_lead_mk.
+ * fpx_epx_lead_mk: as fpx_epx_lead, with key lists (the CSR arrays and rules above FPX_EPX_MK_MAX_PAIRS; checked on the
+ *   host).  The dependencies are the element-wise max over the command's distinct keys of each key's conflicts at replica
+ *   at[i], and the put goes under every key (K7's pair form at one replica).  The leader state stores ONE key word: the key
+ *   when the list has exactly one distinct key, -1 when it has none, FPX_EPX_KEY_LIST otherwise -- the caller holds the
+ *   list by triple id.  One-key lists leave the outputs and the device state of fpx_epx_lead with key = keys. */
 #define FPX_EPX_F_LEADER_STATE 1u
+#define FPX_EPX_KEY_LIST (-2)
 int32_t fpx_epx_lead(fpx_epx* epx, int32_t m, const int32_t* leader, const int32_t* number, const int32_t* at,
                      const int32_t* ballot_ordering, const int32_t* key, const uint8_t* is_set, const int32_t* triple_id,
                      const uint8_t* avoid_fast_path, int32_t* deps, int32_t* deps_values_end);
+int32_t fpx_epx_lead_mk(fpx_epx* epx, int32_t m, const int32_t* leader, const int32_t* number, const int32_t* at,
+                        const int32_t* ballot_ordering, const int32_t* key_offsets, const int32_t* keys,
+                        const uint8_t* is_set, const int32_t* triple_id, const uint8_t* avoid_fast_path, int32_t* deps,
+                        int32_t* deps_values_end);
 /* fpx_epx_leader_replies: ONE burst of what arrives at hosted leaders, in delivery order, the kinds interleaved, addressed
  * to any replica of the context, answered exactly as if handled one message at a time.  Message i: kind[i], to[i] the
  * receiving replica, the instance (leader[i], number[i]), the message's ballot (ballot_ordering[i], ballot_replica[i]) -- a
@@ -1056,8 +1066,8 @@ int32_t fpx_epx_leader_replies_dev(fpx_epx* epx, int32_t m, const int32_t* d_kin
  * delivery order, the kinds interleaved, instances and keys repeated freely, answered exactly as Replica.handlePreAccept /
  * handleAccept / handleCommit / handlePrepare would answer them one message at a time.  Needs num_instances > 0; does NOT
  * need FPX_EPX_F_LEADER_STATE.  Message i goes to the ONE replica to[i]: kind[i], the instance (leader[i], number[i]), the
- * message's ballot (ballot_ordering[i], ballot_replica[i]), the command key[i] / is_set[i] (key -1 = Noop; single-key
- * commands and Noops only), the CommandTriple's id triple_id[i], its dependencies deps[i * n ..] (n watermarks) and
+ * message's ballot (ballot_ordering[i], ballot_replica[i]), the command key[i] / is_set[i] (key -1 = Noop; key lists:
+ * fpx_epx_replica_inbox_mk), the CommandTriple's id triple_id[i], its dependencies deps[i * n ..] (n watermarks) and
  * deps_values_end[i] (the array may be NULL = zeros), shaped as fpx_epx_handle_preaccept's deps_in and
  * fpx_epx_handle_commit's deps.  For an Accept or a Commit deps[i * n] = -1 says "the triple is known by its id alone"
  * (what fpx_epx_read_cmdlog_deps reports for such an entry); the rest of that row is not read.
@@ -1102,7 +1112,18 @@ int32_t fpx_epx_leader_replies_dev(fpx_epx* epx, int32_t m, const int32_t* d_kin
  * Cost: one stable radix sort of the burst on (to, leader, number), ONE thread per (replica, instance) walking that cell's
  * messages in delivery order, then K7's conflict scan (a sort of n x m pairs on the key, one wavefront per (replica, key)) and
  * the largestBallot scan of fpx_epx_prepare.
- * fpx_epx_replica_inbox_dev: device pointers on the context's stream; status through fpx_epx_sync. */
+ * fpx_epx_replica_inbox_dev: device pointers on the context's stream; status through fpx_epx_sync.
+ *
+ * fpx_epx_replica_inbox_mk / _mk_dev: as fpx_epx_replica_inbox / _dev, with key lists (the CSR arrays and rules above
+ * FPX_EPX_MK_MAX_PAIRS) in place of key.  A Prepare's list is not looked up (the lists are one CSR: its offsets and keys are checked with the
+ * rest).  An Accept taken in or a Commit puts the instance
+ * under EVERY distinct key of its list (:602-614).  A processed PreAccept's conflicts are the element-wise max over its
+ * distinct keys of each key's top-one row in to[i]'s index -- the puts to[i] made earlier in the burst and those from
+ * before it -- and it then puts under every key.  One-key lists leave the outputs and the device state of
+ * fpx_epx_replica_inbox with key = keys.  The device form also takes num_pairs, the length of d_keys: the lists are checked
+ * on the device (d_key_offsets[0] = 0, non-decreasing, d_key_offsets[m] = num_pairs, keys in range), there is no host wait
+ * for the pair count, and the status comes through fpx_epx_sync.  m <= FPX_EPX_INBOX_MAX, num_pairs <= FPX_EPX_MK_MAX_PAIRS.
+ * Cost: the scan's sort is over n x num_pairs pairs, plus one max per processed PreAccept over its pairs' rows. */
 #define FPX_EPX_INBOX_MAX (1 << 24)
 enum { FPX_EPX_IN_PRE_ACCEPT = 0, FPX_EPX_IN_ACCEPT = 1, FPX_EPX_IN_COMMIT = 2, FPX_EPX_IN_PREPARE = 3 };
 enum {
@@ -1127,8 +1148,22 @@ int32_t fpx_epx_replica_inbox_dev(fpx_epx* epx, int32_t m, const int32_t* d_kind
                                   const int32_t* d_deps, const int32_t* d_deps_values_end, int32_t* d_outcome,
                                   int32_t* d_out_ballot, int32_t* d_out_status, int32_t* d_out_deps, int32_t* d_out_values_end,
                                   int32_t* d_out_triple);
+int32_t fpx_epx_replica_inbox_mk(fpx_epx* epx, int32_t m, const int32_t* kind, const int32_t* to, const int32_t* leader,
+                                 const int32_t* number, const int32_t* ballot_ordering, const int32_t* ballot_replica,
+                                 const int32_t* key_offsets, const int32_t* keys, const uint8_t* is_set,
+                                 const int32_t* triple_id, const int32_t* deps, const int32_t* deps_values_end,
+                                 int32_t* outcome, int32_t* out_ballot, int32_t* out_status, int32_t* out_deps,
+                                 int32_t* out_values_end, int32_t* out_triple);
+int32_t fpx_epx_replica_inbox_mk_dev(fpx_epx* epx, int32_t m, const int32_t* d_kind, const int32_t* d_to,
+                                     const int32_t* d_leader, const int32_t* d_number, const int32_t* d_ballot_ordering,
+                                     const int32_t* d_ballot_replica, const int32_t* d_key_offsets, const int32_t* d_keys,
+                                     int32_t num_pairs, const uint8_t* d_is_set, const int32_t* d_triple_id,
+                                     const int32_t* d_deps, const int32_t* d_deps_values_end, int32_t* d_outcome,
+                                     int32_t* d_out_ballot, int32_t* d_out_status, int32_t* d_out_deps,
+                                     int32_t* d_out_values_end, int32_t* d_out_triple);
 /* readback (parity) of one leader state: out[0] = phase (0 none, 1 PreAccepting, 2 Accepting, 3 Preparing; 0 when not live),
- * out[1] = ballot, out[2] = avoidFastPath, out[3] = triple id, out[4] = key, out[5] = is_set, out[6] = who has answered (bit
+ * out[1] = ballot, out[2] = avoidFastPath, out[3] = triple id, out[4] = the key word as stored (the key; -1 for a Noop
+ * or a command without keys; FPX_EPX_KEY_LIST for a list of two or more distinct keys), out[5] = is_set, out[6] = who has answered (bit
  * q), out[7] = the phase as stored (live or not); responses (may be NULL) n rows of n + 2 ints: row q = sequence number,
  * n watermarks, values_end of what replica q answered (meaningful for the bits of out[6]; Accepting: row `replica` holds
  * the triple's). */
@@ -1205,6 +1240,8 @@ int32_t fpx_epx_read_leader_state(fpx_epx* epx, int32_t replica, int32_t leader,
  *   Accepting with the replica's own AcceptOk and the triple in row at[i].  largestBallot is not touched.  The AcceptOks
  *   then go through fpx_epx_leader_replies unchanged.  FPX_EINVAL as fpx_epx_lead, and for dependencies an Accept of the
  *   inbox would refuse.
+ * fpx_epx_lead_accept_mk: as fpx_epx_lead_accept, with key lists (checked on the host): updateConflictIndex puts the
+ *   instance under every key, and the state's key word follows fpx_epx_lead_mk's rule.
  * fpx_epx_read_leader_state reports out[0] = 3 for a live Preparing state; its responses rows are the PrepareOks'
  * (sequence number, dependencies).  fpx_epx_read_recovery_state: out n x 3 = per responder status, voteBallot (encoded),
  * triple id; -1, -1, -1 for a replica that has not answered or when the stored phase is not Preparing. */
@@ -1241,6 +1278,10 @@ int32_t fpx_epx_lead_accept(fpx_epx* epx, int32_t m, const int32_t* leader, cons
                             const int32_t* ballot_ordering, const int32_t* key, const uint8_t* is_set,
                             const int32_t* triple_id, const int32_t* sequence_number, const int32_t* deps,
                             const int32_t* deps_values_end);
+int32_t fpx_epx_lead_accept_mk(fpx_epx* epx, int32_t m, const int32_t* leader, const int32_t* number, const int32_t* at,
+                               const int32_t* ballot_ordering, const int32_t* key_offsets, const int32_t* keys,
+                               const uint8_t* is_set, const int32_t* triple_id, const int32_t* sequence_number,
+                               const int32_t* deps, const int32_t* deps_values_end);
 int32_t fpx_epx_read_recovery_state(fpx_epx* epx, int32_t replica, int32_t leader, int32_t number, int32_t* out);
 /* one command-log entry: out[0..4] = kind, ballot, voteBallot, triple id, the replica's largestBallot */
 int32_t fpx_epx_read_cmdlog(fpx_epx* epx, int32_t replica, int32_t leader, int32_t number, int32_t out[5]);
