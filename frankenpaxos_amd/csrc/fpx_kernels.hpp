@@ -64,6 +64,10 @@ constexpr int CHUNK = 32;  // messages per wavefront chunk at R in (128, 256]: 6
 // adversarial 7.31e8 against 7.33e8 (profiles/r09_vote_records.md).  The acceptor model's rows still cost their 2 KiB
 // of stores each and keep 32
 constexpr int CHUNK_RECORDS = 64;
+// A wavefront still takes ONE such chunk per pass of the steady front pass (fpx_phase2_body.inc).  Units of 2, 3 and 4
+// chunks per wavefront were built and measured: faster on the headline, slower than one chunk on a stream that rewrites
+// every ballot row (supposedly the store pattern of 128 KiB or more of consecutive rows per wavefront; not measured
+// further).  The tables are in profiles/r10_steady_units.md
 
 // status word layout in HBM (int32[8])
 // ST_ABORT: set by k_validate only (FPX_EINVAL / FPX_EORDER on a _dev batch): every later kernel up to the next

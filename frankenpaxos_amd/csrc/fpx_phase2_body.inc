@@ -38,10 +38,26 @@ __global__ void __launch_bounds__(256)
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   FPX_P2_PROLOGUE
 
-  if (st.status[ST_ABORT] != 0) return;  // a failed validation applies nothing
+  // the dense G = 64 kernels without lazy promises: the steady front pass (below) takes the chunks of a steady stream.
+  // They ask for the abort flag and their first messages together and look at the flag behind the table clear's barrier
+  constexpr bool STEADY = G == 64 && MODE == 0 && PS == 1;
+  if constexpr (!STEADY) {
+    if (st.status[ST_ABORT] != 0) return;  // a failed validation applies nothing
+  }
 
   const int lane = threadIdx.x & 63;
   const int wib = threadIdx.x >> 6;
+  // the front pass's chunk: its messages in registers (-1 in the lanes without one)
+  int f_slot = -1, f_round = 0, f_value = 0, f_abort = 0;
+  auto front_load = [&](int chunk) {  // one coalesced load per array, nothing waited for
+    const int m = chunk * b.chunk + lane;
+    const bool v = lane < b.chunk && m < b.n;
+    f_slot = v ? b.slot[m] : -1, f_round = v ? b.round[m] : 0, f_value = v ? b.value[m] : 0;
+  };
+  if constexpr (STEADY) {
+    front_load(FPX_P2_BID * 4 + wib);
+    f_abort = st.status[ST_ABORT];
+  }
   if constexpr (G == 64 && (MODE == 1 || MODE == 2)) {
     // behind a packed walk: a workgroup all of whose chunks that walk took leaves before it sets anything up (8192
     // workgroups that only found out in their unit loop were 24 us of a 260 us step)
@@ -75,6 +91,9 @@ __global__ void __launch_bounds__(256)
   if (!PERSLOT && g.ngroups != 1)
     for (int i = threadIdx.x; i < ntab; i += blockDim.x) tab_th[i] = st.promised[i];
   __syncthreads();
+  if constexpr (STEADY) {
+    if (f_abort != 0) return;  // a failed validation applies nothing: nothing has been stored, no row asked for
+  }
   int w_slot = -1, w_round = -1;  // maxima over the steps in which the whole group voted (wave-uniform)
   bool table_used = false;
 
@@ -103,9 +122,8 @@ __global__ void __launch_bounds__(256)
   int pk_pr[8] = {-1, -1, -1, -1, -1, -1, -1, -1}, pk_mv[8] = {-1, -1, -1, -1, -1, -1, -1, -1};
   bool pk_used = false;
 
-  // the steady walk (below) of the dense G = 64 kernels without lazy promises: may a chunk take it at all?  One acceptor
-  // group, and (fused) the whole group's votes -- what every row of a steady chunk collects -- make a write quorum
-  constexpr bool STEADY = G == 64 && MODE == 0 && PS == 1;
+  // the steady front pass (below) of the dense G = 64 kernels without lazy promises: may a chunk take it at all?  One
+  // acceptor group, and (fused) the whole group's votes -- what every row of a steady chunk collects -- make a write quorum
   bool steady_ok = false;
   if constexpr (STEADY) {
     if (one_group) {
@@ -114,6 +132,105 @@ __global__ void __launch_bounds__(256)
 #pragma unroll
       for (int w = 0; w < 4; ++w) x[w] &= g.member[w];
       steady_ok = !FUSED || is_write_quorum(g, x);
+    }
+  }
+
+  // ---- the steady front pass ---------------------------------------------------------------------------------------
+  // A chunk every valid message of which is delivered (a new (slot, round) with a free way) to a uniform row whose round
+  // it is not below makes the same choice in every row: the whole group votes (a quorum, checked once above), nobody
+  // Nacks, the slot is chosen.  The general walk's decision, bitmap and reductions (~650 instructions per row) are what
+  // paced the headline once the uniform rows were no longer read (profiles/r08_steady_walk.md); the 2 KiB of vote cells
+  // per row, 512 copies of two words, were 98 % of its bytes after that (profiles/r09_vote_records.md).  Such a chunk is
+  // per-lane work only, and this pass takes it in front of the unit loop: the chunk's messages are asked for in one go
+  // (the first chunk's above, in front of the table clear), then its rows' summaries and tally-key rows in a second, and
+  // the chunk is decided.  A steady chunk stores its rows' records, their state ROW_COMPACT, the key words
+  // and its outputs straight from registers (chosen, in its round, with its value; nobody Nacked), the ballot row and
+  // its summary where the round moves, and raises the whole-group maxima.  Its decision does not depend on what the rows
+  // held (the whole group overwrites it), so the row states are not even read.  The per-lane stores rely on the run
+  // contract (include/fpx.h): the slots of a batch are pairwise distinct, so no two lanes store one record.  A chunk that
+  // is not steady is left untouched: the unit loop below loads it again and walks it row by row (a change of regime; a
+  // steady stream never gets there).  What this pass hands on is wave-uniform: the chunks it took, one bit each in the
+  // order the unit loop meets them, and the two maxima -- none of its registers lives in the general walk (the headline
+  // kernel is one register from losing a wave per SIMD, profiles/r09_vote_records.md section 4).  Bits past the 64th
+  // (a wavefront with more than 64 chunks: 2^27 messages in a launch of this width) are not taken, which costs those
+  // chunks the records, not the result.
+  uint64_t f_took = 0;
+  if constexpr (STEADY) {
+    const int nchunks = (b.n + b.chunk - 1) / b.chunk;
+    uint64_t vb[4] = {0, 0, 0, 0};  // (unfused: every acceptor's bit, what each row of a steady chunk reports)
+    if constexpr (!FUSED) assemble_bits<G>(own, lane, g.base, vb);
+    int bit = 0;  // the chunk's place among this wavefront's
+    for (int chunk = FPX_P2_BID * 4 + wib; chunk < nchunks; chunk += FPX_P2_NBLK * 4, ++bit) {
+      if (bit) front_load(chunk);
+      __builtin_amdgcn_s_waitcnt(0x0F70);  // the chunk's messages
+      int sum = SUM_MIXED;
+      uint4v f_k0 = uint4v{0, 0, 0, 0}, f_k1 = uint4v{0, 0, 0, 0};
+      if (f_slot >= 0) {
+        sum = st.ballot_sum[f_slot];
+        if constexpr (FUSED) {
+          const uint32_t* kr = st.pl_key + (size_t)f_slot * g.wp;
+          f_k0 = *reinterpret_cast<const uint4v*>(kr);
+          if (g.wp == 8) f_k1 = *reinterpret_cast<const uint4v*>(kr + 4);
+        }
+      }
+      __builtin_amdgcn_s_waitcnt(0x0F70);  // the chunk's summaries and key rows
+      if (bit >= 64 || !steady_ok) continue;
+      const int m = chunk * b.chunk + lane;
+      const bool mv = lane < b.chunk && m < b.n;
+      const int s = f_slot, rnd = f_round, val = f_value;
+      // ProxyLeader.handlePhase2a (ProxyLeader.scala:176-184): a known (slot, round) is not delivered; else the free way
+      int way = -1;
+      bool deliver = mv;
+      if constexpr (FUSED) {
+        const uint32_t want = (uint32_t)rnd + 1u;
+        const uint32_t keys[8] = {f_k0[0], f_k0[1], f_k0[2], f_k0[3], f_k1[0], f_k1[1], f_k1[2], f_k1[3]};
+        bool dup = false;
+#pragma unroll
+        for (int w = 7; w >= 0; --w) {
+          if (w < g.ways) {
+            dup = dup || ((keys[w] & KEY_ROUND_MASK) == want);
+            if (keys[w] == 0) way = w;
+          }
+        }
+        deliver = mv && !dup && way >= 0;
+      }
+      if (!__all(!mv || (deliver && s >= 0 && sum != SUM_MIXED && rnd >= sum))) continue;
+      f_took |= 1ull << bit;
+      if (mv) {
+        st.vote_sum[s] = VoteRec{rnd, val};
+        st.row_voted[s] = ROW_COMPACT;
+        if constexpr (FUSED) {
+          // states(slotround) = Done (ProxyLeader.scala:256)
+          st.pl_key[(size_t)s * g.wp + way] = ((uint32_t)rnd + 1u) | KEY_DONE;
+          if (b.chosen) b.chosen[m] = 1;
+          if (b.chosen_round) b.chosen_round[m] = rnd;
+          if (b.chosen_value) b.chosen_value[m] = val;
+        } else {
+          if (b.vote_bits) {
+            uint64_t* o = b.vote_bits + (size_t)m * 4;
+#pragma unroll
+            for (int w = 0; w < 4; ++w) o[w] = vb[w];
+          }
+          if (b.nack_bits) {
+            uint64_t* o = b.nack_bits + (size_t)m * 4;
+#pragma unroll
+            for (int w = 0; w < 4; ++w) o[w] = 0ull;
+          }
+        }
+        if (b.nack_round) b.nack_round[m] = -1;
+      }
+      // the rows whose ballot moves still get their 1 KiB ballot row and its summary (none in a stream that stays in its round)
+      for (uint64_t mov = __ballot(mv && rnd != sum); mov; mov &= mov - 1) {
+        const int t = (int)__ffsll((unsigned long long)mov) - 1;
+        const int ts = __builtin_amdgcn_readlane(s, t);
+        const int tr = __builtin_amdgcn_readlane(rnd, t);
+        if (own) row_store(int4v{tr, tr, tr, tr}, reinterpret_cast<int4v*>(st.ballot + (size_t)ts * (size_t)g.RS + (size_t)r0));
+        if (lane == 0) st.ballot_sum[ts] = tr;
+      }
+      const int ms = __builtin_amdgcn_readlane(wave_max_to_lane63(mv ? s + 1 : 0), 63) - 1;
+      const int mr = __builtin_amdgcn_readlane(wave_max_to_lane63(mv ? rnd + 1 : 0), 63) - 1;
+      w_slot = ms > w_slot ? ms : w_slot;
+      w_round = mr > w_round ? mr : w_round;
     }
   }
 
@@ -163,7 +280,12 @@ __global__ void __launch_bounds__(256)
   const int u1 = tiled / (64 * kc), per_tile = period / kc;  // units of kc columns x 64 rows; units per tile
   const int units = u1 + (b.n - tiled + CH - 1) / CH;        // + the plain chunks behind the tiles
   int32_t* sc = reinterpret_cast<int32_t*>(smem + b.sc_lds) + wib * (3 * 4 * 64);  // [3][4][64] per wavefront
+  // (the STEADY kernels walk the chunks the front pass did not take: f_k counts this wavefront's chunks, the bits of f_took)
+  int f_k = -1;
   for (int unit = bx * 4 + wib; unit < units; unit += FPX_P2_NBLK * 4) {
+    if constexpr (STEADY) {
+      if (++f_k < 64 && (f_took >> f_k & 1)) continue;
+    }
     if constexpr (G == 64 && (MODE == 1 || MODE == 2)) {
       if (b.run_done && b.run_done[unit]) continue;  // the packed walk of the launch before this one took the chunk
     }
@@ -196,7 +318,6 @@ __global__ void __launch_bounds__(256)
     }
     bool myfresh = false;
     bool mycompact = false;     // my message's row is a record (its state is gathered with the chunk, like its summary)
-    bool compacted = false;     // the chunk took the steady walk: its rows leave as records
     if constexpr (RECS) {
       const int rs = mv ? (int)st.row_voted[myphys] : (int)ROW_CELLS;
       mycompact = rs == ROW_COMPACT;
@@ -454,49 +575,7 @@ __global__ void __launch_bounds__(256)
     // body, where -- vmcnt counts stores on gfx9 -- it makes every step wait for the rows the step before it wrote.
     // In the FPX_BALLOT_ACCEPTOR model the walk then has no vector-memory wait at all: rows stream out back to back.
     __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0), expcnt and lgkmcnt untouched
-    // The steady walk.  A chunk every valid message of which is delivered (a new (slot, round) with a free way) to a
-    // uniform row whose round it is not below makes the same choice in every row: the whole group votes (a quorum, checked
-    // once above), nobody Nacks, the slot is chosen.  The general walk's decision, bitmap and reductions (~650
-    // instructions per row) are what paced the headline once the uniform rows were no longer read
-    // (profiles/r08_steady_walk.md); the 2 KiB of vote cells per row, 512 copies of two words, were 98 % of its bytes
-    // after that (profiles/r09_vote_records.md).  Such a chunk writes per-lane data only: its rows' records, and (below
-    // the walk) their state, key words and chosen records; the ballot row and its summary where the round moves, and
-    // the whole-group maxima, are what the general walk writes.  The decision does not depend on what the rows held:
-    // the whole group overwrites it.  The per-lane record stores rely on the run contract (include/fpx.h): the slots of a
-    // batch are pairwise distinct, so no two lanes store one record.
-    bool steady = false;
-    if constexpr (STEADY)
-      steady = steady_ok && __all(!mv || (mydeliver && myslot >= 0 && mysum != SUM_MIXED && myround >= mysum));
-    if (STEADY && steady) {
-      // no vote cells: the whole group votes in every row, so a row is its message's (round, value) -- one record per
-      // lane, and (below the walk) the row state ROW_COMPACT
-      compacted = true;
-      if (mv) st.vote_sum[myphys] = VoteRec{myround, myvalue};
-      // the rows whose ballot moves still get their 1 KiB ballot row and its summary (none in a stream that stays in its round)
-      for (uint64_t mov = __ballot(mv && myround != mysum); mov; mov &= mov - 1) {
-        const int t = (int)__ffsll((unsigned long long)mov) - 1;
-        const int s = __builtin_amdgcn_readlane(myslot, t);
-        const int rnd = __builtin_amdgcn_readlane(myround, t);
-        if (own) row_store(int4v{rnd, rnd, rnd, rnd}, reinterpret_cast<int4v*>(st.ballot + (size_t)s * (size_t)g.RS + (size_t)r0));
-        if (lane == 0) st.ballot_sum[s] = rnd;
-      }
-      const int ms = __builtin_amdgcn_readlane(wave_max_to_lane63(mv ? myslot + 1 : 0), 63) - 1;
-      const int mr = __builtin_amdgcn_readlane(wave_max_to_lane63(mv ? myround + 1 : 0), 63) - 1;
-      w_slot = ms > w_slot ? ms : w_slot;
-      w_round = mr > w_round ? mr : w_round;
-      if constexpr (FUSED) {
-        if (mv) wo->chosen[lane] = 1, wo->nack_round[lane] = -1;
-      } else {
-        uint64_t vb[4];
-        assemble_bits<G>(own, lane, g.base, vb);
-        if (mv) {
-#pragma unroll
-          for (int w = 0; w < 4; ++w) wo->votes[lane][w] = vb[w], wo->nacks[lane][w] = 0ull;
-          wo->nack_round[lane] = -1;
-        }
-      }
-    }
-    if (!STEADY || !steady) {  // (without the steady walk: no branch at all, the code of the kernels before it)
+    {  // the general walk (in the STEADY kernels: of a chunk the front pass left)
     // Compact rows a message of this chunk is delivered to become cells BEFORE the walk: every lane stores the record
     // into all its cells of both rows (even if nobody will vote), the row is ROW_CELLS from here on, and the walk below
     // is the code it was before there were records.  One scalar test per chunk; the cells a step then votes in are
@@ -742,10 +821,8 @@ __global__ void __launch_bounds__(256)
     // ---- outputs of the 64 messages leave as coalesced lines ------------------------------------
     wave_lds_sync();
     // the slot's row is no longer known to be all -1 (marked even if every acceptor Nacked: that only costs the shortcut)
-    // (a steady chunk delivers every valid message and leaves records; the compact rows of any other were marked above)
-    if (STEADY && compacted) {
-      if (mv) st.row_voted[myphys] = ROW_COMPACT;
-    } else if (TGT ? (myfresh && mydeliver) : (mv && mydeliver)) {
+    // (the compact rows the chunk delivers to were marked above; a steady chunk's rows are the front pass's)
+    if (TGT ? (myfresh && mydeliver) : (mv && mydeliver)) {
       st.row_voted[myphys] = ROW_CELLS;
     }
     if (mv) {
