@@ -112,27 +112,17 @@ struct fpx_ctx {
   // the fold (k_finalize's work) of the last K3 launch, when it has not been launched: it rides in the next eligible vote
   // kernel (k_phase2_fin) or is launched by whatever touches the context next (DeviceGuard -> flush_pending_fin)
   FinJob pending_fin = {};       // nblk != 0: pending
-  FinJob carry_fin = {};         // what the launch being enqueued may take into its grid (consumed by launch_phase2_3)
-  State launch_st = {};          // the State of the launch being enqueued: st with ITS half of part / part_stamp
   long long fins_carried = 0;    // diagnostic
   uint32_t launch_seq = 0;  // stamps the partial-maxima rows of a K1 / K3 launch (never 0 in a row that counts)
-  bool batch_increasing = false, batch_one_round = false;  // check_inputs' findings about the current host batch
-  bool force_validate = false;  // host-pointer K3's optimistic whole-batch run is validated even under FPX_F_TRUSTED
-  bool host_validated = false;  // set while a host entry point drives runs it cut itself (split_runs)
   bool profiling = false;
   std::vector<hipEvent_t> ev;  // start/stop pairs
   size_t ev_used = 0;
-  // the events of the K1 / K3 launch being enqueued: they ride on the kernel's own dispatch packet (hipExtLaunchKernelGGL),
-  // so a timed launch puts no marker packets on the stream (two hipEventRecords per launch cost 5 - 15 us of a step)
-  hipEvent_t ev_start = nullptr, ev_stop = nullptr;
   // host-pointer K3 on page-locked arrays: the inputs go up on a stream of their own (host_submit)
   hipStream_t up_stream = nullptr;
   HostSlot* hslots = nullptr;  // calls in flight on page-locked arrays (host_submit / host_wait)
   int hnext = 0;
-  int32_t index_base = 0;  // message index of the run being launched in its host batch (error reports are batch-relative)
   bool lazy_active = false;  // PER_SLOT: lazy Phase1a promises may be outstanding (k_phase2 runs its lazy-aware form)
   bool may_compact = false;  // some vote row may be ROW_COMPACT: a steady walk may have run since all rows were last fresh or cells
-  bool packed_pass = false;  // the launch being enqueued is the packed walk over runs of acceptors (k_phase2 MODE 3)
   DevBuf d_run_done;         // one byte per chunk: taken by the packed walk
   // K4: the proxy leader's noop-range tallies (two buffers: fpx_proxy_forget rehashes into the other one)
   RangeTable rt[2];
@@ -145,8 +135,7 @@ struct fpx_ctx {
   hipEvent_t band_fork = nullptr, band_join = nullptr;
   // fpx_vote_launch_census (include/fpx.h): host counters of the vote launches and of their folds
   int64_t census[FPX_CENSUS_WORDS] = {};
-  int census_cell = 0;                       // the cell of the vote launch just enqueued
-  int census_pending = 0, census_carry = 0;  // the cells of the launches whose folds are pending_fin / carry_fin
+  int census_pending = 0;  // the cell of the launch whose fold is pending_fin
   int64_t range_census[FPX_RANGE_CENSUS_WORDS] = {};  // fpx_range_launch_census: host counters of the K4 launches
   DevBuf d_enc;   // the device encoders' workgroup sums (fpx_wire_encode_*_dev)
   // fpx_wire_phase2_tick: the tick's bytes and offsets, its decoded records (kind, slot, round, is_noop, value_len, value_id,
@@ -359,12 +348,24 @@ int census_launch(fpx_ctx* ctx, int G, int mode, int ps, bool fused, int form, c
   ++ctx->census[cell * FPX_CENSUS_FORMS + form];
   if (b.sc_lds) ++ctx->census[FPX_CENSUS_SC_LDS];
   if (b.th_lds) ++ctx->census[FPX_CENSUS_TH_LDS];
-  return ctx->census_cell = cell;
+  return cell;
 }
 void census_fold(fpx_ctx* ctx, int cell, int fate) { ++ctx->census[cell * FPX_CENSUS_FORMS + fate]; }
 
+// One K1 / K3 kernel launch, as enqueue_phase2 / enqueue_band_merged hand it down the launch chain.
+struct VoteLaunch {
+  State st;             // the State the launch runs on: ctx->st with ITS half of part / part_stamp (begin_phase2_launch)
+  FinJob fin = {};      // the fold of the launch before, offered to this one (nblk != 0): taken into its grid when the
+  int fin_cell = 0;     // kernel has that form (k_phase2_fin); fin_cell: the census cell of the launch it folds
+  // the events ride on the kernel's own dispatch packet (hipExtLaunchKernelGGL), so a timed launch puts no marker packets
+  // on the stream (two hipEventRecords per launch cost 5 - 15 us of a step)
+  hipEvent_t ev_start = nullptr, ev_stop = nullptr;
+  bool packed = false;  // the packed walk over runs of acceptors (k_phase2 MODE 3)
+};
+struct Launched { int cell; bool took_fin; };  // what a launch did: its census cell, whether it took VoteLaunch::fin along
+
 template <int G, int MODE, int PS>
-void launch_phase2_3(fpx_ctx* ctx, const Batch& b0, bool fused, int grid) {
+Launched launch_phase2_3(fpx_ctx* ctx, const VoteLaunch& vl, const Batch& b0, bool fused, int grid) {
   Batch b = b0;
   const size_t lds = phase2_lds(ctx, b, fused, MODE != 0, PS == 0);
   if (fused) allow_lds(k_phase2<G, MODE, PS, true>, lds);
@@ -372,86 +373,84 @@ void launch_phase2_3(fpx_ctx* ctx, const Batch& b0, bool fused, int grid) {
   if constexpr ((G == 64 || G == 1) && (MODE == 0 || MODE == 2) && PS != 0) {
     // the fold of the launch before rides in this one (k_phase2_fin: the shapes of the steady streams -- the headline,
     // configs 2 and 3, the adversarial stream; other shapes leave it to the caller, who launches it by itself)
-    if (fused && ctx->carry_fin.nblk) {
+    if (fused && vl.fin.nblk) {
       allow_lds(k_phase2_fin<G, MODE, PS, true>, lds);
-      hipExtLaunchKernelGGL((k_phase2_fin<G, MODE, PS, true>), dim3(grid + ctx->carry_fin.nblk), dim3(256), (uint32_t)lds, ctx->stream,
-                            ctx->ev_start, ctx->ev_stop, 0, ctx->g, ctx->launch_st, b, ctx->carry_fin);
-      ctx->carry_fin.nblk = 0;
+      hipExtLaunchKernelGGL((k_phase2_fin<G, MODE, PS, true>), dim3(grid + vl.fin.nblk), dim3(256), (uint32_t)lds, ctx->stream,
+                            vl.ev_start, vl.ev_stop, 0, ctx->g, vl.st, b, vl.fin);
       ++ctx->fins_carried;
-      census_launch(ctx, G, MODE, PS, fused, FPX_CENSUS_FIN, b);
-      census_fold(ctx, ctx->census_carry, FPX_CENSUS_FOLD_CARRIED);
-      return;
+      census_fold(ctx, vl.fin_cell, FPX_CENSUS_FOLD_CARRIED);
+      return {census_launch(ctx, G, MODE, PS, fused, FPX_CENSUS_FIN, b), true};
     }
   }
-  census_launch(ctx, G, MODE, PS, fused, b.solo ? FPX_CENSUS_SOLO : FPX_CENSUS_GRID, b);
   if (fused)
-    hipExtLaunchKernelGGL((k_phase2<G, MODE, PS, true>), dim3(grid), dim3(256), (uint32_t)lds, ctx->stream, ctx->ev_start,
-                          ctx->ev_stop, 0, ctx->g, ctx->launch_st, b);
+    hipExtLaunchKernelGGL((k_phase2<G, MODE, PS, true>), dim3(grid), dim3(256), (uint32_t)lds, ctx->stream, vl.ev_start,
+                          vl.ev_stop, 0, ctx->g, vl.st, b);
   else
-    hipExtLaunchKernelGGL((k_phase2<G, MODE, PS, false>), dim3(grid), dim3(256), (uint32_t)lds, ctx->stream, ctx->ev_start,
-                          ctx->ev_stop, 0, ctx->g, ctx->launch_st, b);
+    hipExtLaunchKernelGGL((k_phase2<G, MODE, PS, false>), dim3(grid), dim3(256), (uint32_t)lds, ctx->stream, vl.ev_start,
+                          vl.ev_stop, 0, ctx->g, vl.st, b);
+  return {census_launch(ctx, G, MODE, PS, fused, b.solo ? FPX_CENSUS_SOLO : FPX_CENSUS_GRID, b), false};
 }
 
 template <int G, int MODE>
-void launch_phase2_2b(fpx_ctx* ctx, const Batch& b, bool fused, int grid) {
+Launched launch_phase2_2b(fpx_ctx* ctx, const VoteLaunch& vl, const Batch& b, bool fused, int grid) {
   // ballot model: 0 = per-acceptor scalar, 1 = per cell, 2 = per cell with lazy Phase1a promises outstanding
-  if (!ctx->g.per_slot) launch_phase2_3<G, MODE, 0>(ctx, b, fused, grid);
-  else if (!ctx->lazy_active) launch_phase2_3<G, MODE, 1>(ctx, b, fused, grid);
-  else launch_phase2_3<G, MODE, 2>(ctx, b, fused, grid);
+  if (!ctx->g.per_slot) return launch_phase2_3<G, MODE, 0>(ctx, vl, b, fused, grid);
+  if (!ctx->lazy_active) return launch_phase2_3<G, MODE, 1>(ctx, vl, b, fused, grid);
+  return launch_phase2_3<G, MODE, 2>(ctx, vl, b, fused, grid);
 }
 
 template <int G>
-void launch_phase2_2(fpx_ctx* ctx, const Batch& b, bool fused, int grid) {
+Launched launch_phase2_2(fpx_ctx* ctx, const VoteLaunch& vl, const Batch& b, bool fused, int grid) {
   // rows are padded to a multiple of 4 cells (Geom::RS), so int4 accesses serve every R.
   // mode 0: dense delivery (no target masks); 1: target masks; 2: target masks + FPX_F_SCATTERED_TARGETS
   const int mode = !b.target ? 0 : ((ctx->cfg.flags & FPX_F_SCATTERED_TARGETS) ? 2 : 1);
   if constexpr (G == 64) {
-    if (ctx->packed_pass) {  // the packed walk (enqueue_phase2 runs it ahead of the row-at-a-time walk)
-      if (!ctx->g.per_slot) launch_phase2_3<64, 3, 0>(ctx, b, fused, grid);
-      else launch_phase2_3<64, 3, 1>(ctx, b, fused, grid);
-      return;
+    if (vl.packed) {  // the packed walk (enqueue_phase2 runs it ahead of the row-at-a-time walk)
+      if (!ctx->g.per_slot) return launch_phase2_3<64, 3, 0>(ctx, vl, b, fused, grid);
+      return launch_phase2_3<64, 3, 1>(ctx, vl, b, fused, grid);
     }
   }
-  if (mode == 0) launch_phase2_2b<G, 0>(ctx, b, fused, grid);
-  else if (mode == 1) launch_phase2_2b<G, 1>(ctx, b, fused, grid);
-  else launch_phase2_2b<G, 2>(ctx, b, fused, grid);
+  if (mode == 0) return launch_phase2_2b<G, 0>(ctx, vl, b, fused, grid);
+  if (mode == 1) return launch_phase2_2b<G, 1>(ctx, vl, b, fused, grid);
+  return launch_phase2_2b<G, 2>(ctx, vl, b, fused, grid);
 }
 
-void launch_phase2(fpx_ctx* ctx, const Batch& b, bool fused, int grid) {
+Launched launch_phase2(fpx_ctx* ctx, const VoteLaunch& vl, const Batch& b, bool fused, int grid) {
   switch (ctx->lanes_per_slot) {
-    case 1: launch_phase2_2<1>(ctx, b, fused, grid); break;
-    case 2: launch_phase2_2<2>(ctx, b, fused, grid); break;
-    case 4: launch_phase2_2<4>(ctx, b, fused, grid); break;
-    case 8: launch_phase2_2<8>(ctx, b, fused, grid); break;
-    case 16: launch_phase2_2<16>(ctx, b, fused, grid); break;
-    case 32: launch_phase2_2<32>(ctx, b, fused, grid); break;
-    default: launch_phase2_2<64>(ctx, b, fused, grid); break;
+    case 1: return launch_phase2_2<1>(ctx, vl, b, fused, grid);
+    case 2: return launch_phase2_2<2>(ctx, vl, b, fused, grid);
+    case 4: return launch_phase2_2<4>(ctx, vl, b, fused, grid);
+    case 8: return launch_phase2_2<8>(ctx, vl, b, fused, grid);
+    case 16: return launch_phase2_2<16>(ctx, vl, b, fused, grid);
+    case 32: return launch_phase2_2<32>(ctx, vl, b, fused, grid);
+    default: return launch_phase2_2<64>(ctx, vl, b, fused, grid);
   }
 }
 
 // the vote kernel of a Mencius band with the band's range chain as its first workgroup (enqueue_band_merged)
 template <int G>
-void launch_band_g(fpx_ctx* ctx, const Batch& b, size_t lds, int grid, const RangeTable& rt, const RangeBatch& rb) {
+void launch_band_g(fpx_ctx* ctx, const VoteLaunch& vl, const Batch& b, size_t lds, int grid, const RangeBatch& rb) {
   allow_lds(k_phase2_band<G, 0, 0, true>, lds);
   census_launch(ctx, G, 0, 0, true, FPX_CENSUS_BAND, b);
-  hipExtLaunchKernelGGL((k_phase2_band<G, 0, 0, true>), dim3(grid + 1), dim3(256), (uint32_t)lds, ctx->stream, ctx->ev_start,
-                        ctx->ev_stop, 0, ctx->g, ctx->launch_st, b, rt, rb);
+  hipExtLaunchKernelGGL((k_phase2_band<G, 0, 0, true>), dim3(grid + 1), dim3(256), (uint32_t)lds, ctx->stream, vl.ev_start,
+                        vl.ev_stop, 0, ctx->g, vl.st, b, ctx->rt[ctx->rt_cur], rb);
 }
-void launch_band(fpx_ctx* ctx, const Batch& b, size_t lds, int grid, const RangeTable& rt, const RangeBatch& rb) {
+void launch_band(fpx_ctx* ctx, const VoteLaunch& vl, const Batch& b, size_t lds, int grid, const RangeBatch& rb) {
   switch (ctx->lanes_per_slot) {
-    case 1: launch_band_g<1>(ctx, b, lds, grid, rt, rb); break;
-    case 2: launch_band_g<2>(ctx, b, lds, grid, rt, rb); break;
-    case 4: launch_band_g<4>(ctx, b, lds, grid, rt, rb); break;
-    default: launch_band_g<8>(ctx, b, lds, grid, rt, rb); break;
+    case 1: launch_band_g<1>(ctx, vl, b, lds, grid, rb); break;
+    case 2: launch_band_g<2>(ctx, vl, b, lds, grid, rb); break;
+    case 4: launch_band_g<4>(ctx, vl, b, lds, grid, rb); break;
+    default: launch_band_g<8>(ctx, vl, b, lds, grid, rb); break;
   }
 }
 
-// fill n int32 words on the stream with a kernel (see k_fill32)
-void fill32(fpx_ctx* ctx, void* p, int32_t v, size_t n) {
+// fill n int32 words on a stream (the context's, when none is named) with a kernel (see k_fill32)
+void fill32(fpx_ctx* ctx, void* p, int32_t v, size_t n, hipStream_t stream) {
   if (n == 0) return;
   const int grid = (int)std::max<size_t>(1, std::min<size_t>((n + 255) / 256, (size_t)ctx->num_cus * 8));
-  hipLaunchKernelGGL(k_fill32, dim3(grid), dim3(256), 0, ctx->stream, (int32_t*)p, v, n);
+  hipLaunchKernelGGL(k_fill32, dim3(grid), dim3(256), 0, stream, (int32_t*)p, v, n);
 }
+void fill32(fpx_ctx* ctx, void* p, int32_t v, size_t n) { fill32(ctx, p, v, n, ctx->stream); }
 
 // a claim array of `words` int32 that lives as long as the context: the first call allocates it, counts it and sets
 // every word to INT_MAX, its value between calls
@@ -463,28 +462,28 @@ int claim_array(fpx_ctx* ctx, DevBuf* b, size_t words) {
   return FPX_OK;
 }
 
-// The per-context flags that steer the launches of a host batch, set for the batch and cleared on every way out: a flag
-// left set would change every later call on the context.  cut_on_host: the host cut the batch into runs (split_runs), so
-// the run contract holds by construction and the device-side validation pass is skipped; otherwise the batch is validated
-// on the device even under FPX_F_TRUSTED (that flag is a promise about _dev batches only).  index_base is the message
-// index of the run being launched.
-struct HostFlags {
-  fpx_ctx* ctx;
-  HostFlags(fpx_ctx* c, bool cut_on_host) : ctx(c) { (cut_on_host ? ctx->host_validated : ctx->force_validate) = true; }
-  ~HostFlags() { ctx->host_validated = ctx->force_validate = false, ctx->index_base = 0; }
-  HostFlags(const HostFlags&) = delete;
-  HostFlags& operator=(const HostFlags&) = delete;
+// What the caller of one device run says about it.  A _dev entry point runs AS_CONFIGURED: validated on the device unless
+// the context is FPX_F_TRUSTED.  A host batch run whole is validated even then (FORCE_VALIDATE: that flag is a promise
+// about _dev batches only); one that the host cut into runs itself (split_runs) holds the run contract by construction
+// and skips the device pass (CUT_ON_HOST).  index_base is the message index of the run in its host batch: error reports
+// are batch-relative.
+struct RunOpts {
+  enum Validate { AS_CONFIGURED, FORCE_VALIDATE, CUT_ON_HOST } validate = AS_CONFIGURED;
+  int32_t index_base = 0;
+  bool validates(const fpx_ctx* ctx) const {
+    return validate == FORCE_VALIDATE || (validate == AS_CONFIGURED && !(ctx->cfg.flags & FPX_F_TRUSTED));
+  }
 };
 
-// validation pass of one device run (skipped with FPX_F_TRUSTED)
-int enqueue_validate(fpx_ctx* ctx, Batch& b, bool check_round) {
-  b.run_id = ++ctx->run_id;
+// the run's stamp and index base into the batch, then the validation pass of one device run (RunOpts says whether it runs)
+int enqueue_validate(fpx_ctx* ctx, Batch& b, bool check_round, const RunOpts& opts) {
+  b.run_id = ++ctx->run_id, b.index_base = opts.index_base;
   if (ctx->run_id == 0xFFFFFFFFu) {  // stamp space exhausted: start over
     HIPCHK(ctx, hipMemsetAsync(ctx->st.stamp, 0, sizeof(uint32_t) * (size_t)ctx->g.S, ctx->stream));
     ctx->run_id = 0;
     b.run_id = ++ctx->run_id;
   }
-  if (((ctx->cfg.flags & FPX_F_TRUSTED) && !ctx->force_validate) || ctx->host_validated) return FPX_OK;
+  if (!opts.validates(ctx)) return FPX_OK;
   b.check_round = check_round && !ctx->g.per_slot;
   if (b.check_round) fill32(ctx, ctx->st.run_round, -1, (size_t)ctx->g.ngroups);
   hipLaunchKernelGGL(k_validate, dim3((b.n + 255) / 256), dim3(256), 0, ctx->stream, ctx->g, ctx->st, b);
@@ -493,23 +492,25 @@ int enqueue_validate(fpx_ctx* ctx, Batch& b, bool check_round) {
 
 // The launch counter of a K1 / K3 launch decides which third of part_all (Batch::parity) and which half of part /
 // part_stamp (the State handed to the launch and to its fold) it uses: see finalize_body / k_phase2_fin.
-void begin_phase2_launch(fpx_ctx* ctx, Batch& b) {
+State begin_phase2_launch(fpx_ctx* ctx, Batch& b) {
   const uint32_t li = ctx->phase2_launches++;
   b.parity = (int32_t)(li % 3u);
   const size_t half = (size_t)(li & 1u), ntab = (size_t)ctx->g.ngroups * ctx->g.R;
-  ctx->launch_st = ctx->st;
-  ctx->launch_st.part = ctx->st.part + half * (size_t)ctx->max_grid * 2 * ntab;
-  ctx->launch_st.part_stamp = ctx->st.part_stamp + half * (size_t)ctx->max_grid;
+  State st = ctx->st;
+  st.part = ctx->st.part + half * (size_t)ctx->max_grid * 2 * ntab;
+  st.part_stamp = ctx->st.part_stamp + half * (size_t)ctx->max_grid;
+  return st;
 }
 
-FinJob fin_job_of(const fpx_ctx* ctx, const Batch& b, int grid) {
+// the fold of the launch of b on `st` (begin_phase2_launch's) over `grid` workgroups
+FinJob fin_job_of(const fpx_ctx* ctx, const State& st, const Batch& b, int grid) {
   FinJob fj;
   const int ntab = ctx->g.ngroups * ctx->g.R;
   fj.fgx = (ntab + 63) / 64;
   fj.slices = std::max(FINALIZE_SLICES, std::min(256, grid / 32));  // ~8 partial rows per wavefront
   fj.nblk = fj.fgx * fj.slices;
   fj.par = (int)b.parity, fj.grid = grid, fj.seq = b.launch_seq;
-  fj.part = ctx->launch_st.part, fj.part_stamp = ctx->launch_st.part_stamp;
+  fj.part = st.part, fj.part_stamp = st.part_stamp;
   return fj;
 }
 
@@ -528,14 +529,12 @@ void flush_pending_fin(fpx_ctx* ctx) {
 }
 
 // K1 / K3 on one device run
-int enqueue_phase2(fpx_ctx* ctx, Batch& b, bool fused) {
+int enqueue_phase2(fpx_ctx* ctx, Batch& b, bool fused, const RunOpts& opts) {
   if (b.n == 0) return FPX_OK;
-  b.index_base = ctx->index_base;
-  int rc = enqueue_validate(ctx, b, true);
+  int rc = enqueue_validate(ctx, b, true, opts);
   if (rc) return rc;
   int grid = grid_for(ctx, b.n);
   b.chunk = chunk_for(ctx, b.n);
-  b.index_base = ctx->index_base;
   // at most two chunks per wavefront of one workgroup: that workgroup finalises itself (k_phase2, `solo`); the parity
   // of the partial-maxima buffers is not consumed
   b.solo = (b.n + b.chunk - 1) / b.chunk <= 8 ? 1 : 0;
@@ -569,31 +568,28 @@ int enqueue_phase2(fpx_ctx* ctx, Batch& b, bool fused) {
   const bool prof = ctx->profiling && ctx->ev_used + 2 <= ctx->ev.size();
   for (int pass = two ? 0 : 1; pass < 2; ++pass) {
     // start of the first vote kernel to end of the last (two with the packed walk ahead)
-    ctx->ev_start = prof && pass == (two ? 0 : 1) ? ctx->ev[ctx->ev_used] : nullptr;
-    ctx->ev_stop = prof && pass == 1 ? ctx->ev[ctx->ev_used + 1] : nullptr;
+    VoteLaunch vl;
+    vl.ev_start = prof && pass == (two ? 0 : 1) ? ctx->ev[ctx->ev_used] : nullptr;
+    vl.ev_stop = prof && pass == 1 ? ctx->ev[ctx->ev_used + 1] : nullptr;
     if (b.solo) {
       // (the one workgroup of a solo launch raises the acceptors' scalars with plain loads and stores: nothing may fold
       // beside it -- a pending fold goes first, by itself)
       flush_pending_fin(ctx);
-      b.parity = 0, ctx->launch_st = ctx->st;
+      b.parity = 0, vl.st = ctx->st;
     } else {
-      begin_phase2_launch(ctx, b);
+      vl.st = begin_phase2_launch(ctx, b);
     }
     if (++ctx->launch_seq == 0) ctx->launch_seq = 1;
     b.launch_seq = ctx->launch_seq;
-    ctx->packed_pass = pass == 0;
+    vl.packed = pass == 0;
     // the fold of the launch before, if it is still pending: offered to this launch (launch_phase2_3 takes it into its
     // grid when the kernel has that form), else launched by itself behind it -- before the launch after this one either way
-    ctx->carry_fin = ctx->pending_fin;
-    ctx->census_carry = ctx->census_pending;
+    vl.fin = ctx->pending_fin, vl.fin_cell = ctx->census_pending;
     ctx->pending_fin.nblk = 0;
-    launch_phase2(ctx, b, fused, grid);
-    ctx->packed_pass = false;
-    ctx->ev_start = ctx->ev_stop = nullptr;
-    if (ctx->carry_fin.nblk) {
-      launch_fin_alone(ctx, ctx->carry_fin);
-      ctx->carry_fin.nblk = 0;
-      census_fold(ctx, ctx->census_carry, FPX_CENSUS_FOLD_BEHIND);
+    const Launched did = launch_phase2(ctx, vl, b, fused, grid);
+    if (vl.fin.nblk && !did.took_fin) {
+      launch_fin_alone(ctx, vl.fin);
+      census_fold(ctx, vl.fin_cell, FPX_CENSUS_FOLD_BEHIND);
     }
     rc = launch_check(ctx);
     if (rc) return rc;
@@ -601,13 +597,13 @@ int enqueue_phase2(fpx_ctx* ctx, Batch& b, bool fused) {
     if (b.solo) continue;
     // this launch's own fold: with a ballot per cell no vote kernel reads what it writes -- it waits for the next launch
     // (or for whatever touches the context next); with a round per acceptor the next vote kernel starts from it: at once
-    const FinJob fj = fin_job_of(ctx, b, grid);
+    const FinJob fj = fin_job_of(ctx, vl.st, b, grid);
     const bool no_defer = getenv("FPX_NO_DEFER_FINALIZE") != nullptr;  // (read per launch: a test switches it between contexts)
     if (fused && ctx->g.per_slot && !no_defer) {
       ctx->pending_fin = fj;
-      ctx->census_pending = ctx->census_cell;
+      ctx->census_pending = did.cell;
     } else {
-      census_fold(ctx, ctx->census_cell, FPX_CENSUS_FOLD_NOW);
+      census_fold(ctx, did.cell, FPX_CENSUS_FOLD_NOW);
       launch_fin_alone(ctx, fj);
       rc = launch_check(ctx);
       if (rc) return rc;
@@ -616,19 +612,54 @@ int enqueue_phase2(fpx_ctx* ctx, Batch& b, bool fused) {
   return FPX_OK;
 }
 
-int enqueue_open(fpx_ctx* ctx, Batch& b) {
+int enqueue_open(fpx_ctx* ctx, Batch& b, const RunOpts& opts) {
   if (b.n == 0) return FPX_OK;
-  int rc = enqueue_validate(ctx, b, false);
+  int rc = enqueue_validate(ctx, b, false, opts);
   if (rc) return rc;
   hipLaunchKernelGGL(k_open, dim3((b.n + 255) / 256), dim3(256), 0, ctx->stream, ctx->g, ctx->st, b);
   return launch_check(ctx);
 }
 
-int enqueue_tally(fpx_ctx* ctx, Batch& b) {
+int enqueue_tally(fpx_ctx* ctx, Batch& b, const RunOpts& opts) {
   if (b.n == 0) return FPX_OK;
-  int rc = enqueue_validate(ctx, b, false);
+  int rc = enqueue_validate(ctx, b, false, opts);
   if (rc) return rc;
   hipLaunchKernelGGL(k_tally, dim3((b.n + 255) / 256), dim3(256), 0, ctx->stream, ctx->g, ctx->st, b);
+  return launch_check(ctx);
+}
+
+// ---- one device run, as the _dev entry points and the host-pointer paths launch it -----------------------------------
+// An exported _dev function is the device guard, the argument check and an enqueue_* / run_* with RunOpts{}; a host-pointer
+// path calls the same with the RunOpts of its run.  None of them touches a pending fold on its way in: enqueue_phase2 offers
+// it to its launch, the callers of the others launch it first (DeviceGuard, or flush_pending_fin by hand).
+Batch batch_of(int32_t n, const int32_t* d_slot, const int32_t* d_round, const int32_t* d_value_id,
+               const uint64_t* d_target_mask = nullptr) {
+  Batch b;
+  memset(&b, 0, sizeof(b));
+  b.n = n, b.slot = d_slot, b.round = d_round, b.value = d_value_id, b.target = d_target_mask;
+  return b;
+}
+
+int run_phase2_fused(fpx_ctx* ctx, int32_t n, const int32_t* d_slot, const int32_t* d_round, const int32_t* d_value_id,
+                     const uint64_t* d_target_mask, uint8_t* d_chosen, int32_t* d_chosen_round, int32_t* d_chosen_value,
+                     int32_t* d_nack_round, const RunOpts& opts) {
+  Batch b = batch_of(n, d_slot, d_round, d_value_id, d_target_mask);
+  b.chosen = d_chosen, b.chosen_round = d_chosen_round, b.chosen_value = d_chosen_value, b.nack_round = d_nack_round;
+  return enqueue_phase2(ctx, b, true, opts);
+}
+
+int run_replica_chosen(fpx_ctx* ctx, int32_t n, const int32_t* d_slot, const int32_t* d_value_id, const uint8_t* d_mask,
+                       const RunOpts& opts) {
+  if (n == 0) return FPX_OK;
+  Batch b = batch_of(n, d_slot, nullptr, d_value_id);
+  b.mask = d_mask;
+  int rc = enqueue_validate(ctx, b, false, opts);
+  if (rc) return rc;
+  const int ingest_grid = std::max(1, std::min({(n + 255) / 256, ctx->num_cus * 8, LG_MAX_PARTS}));
+  hipLaunchKernelGGL(k_log_ingest, dim3(ingest_grid), dim3(256), 0, ctx->stream, ctx->g, ctx->st, b);
+  hipLaunchKernelGGL(k_log_prep, dim3(1), dim3(256), 0, ctx->stream, ctx->g, ctx->st, ingest_grid);
+  hipLaunchKernelGGL(k_log_scan, dim3(ctx->num_cus * 4), dim3(256), 0, ctx->stream, ctx->g, ctx->st);
+  hipLaunchKernelGGL(k_log_commit, dim3(1), dim3(1), 0, ctx->stream, ctx->st);
   return launch_check(ctx);
 }
 
@@ -711,7 +742,7 @@ int init_state(fpx_ctx* ctx) {
   HIPCHK(ctx, hipMemsetAsync(st.status, 0, 8 * 4, ctx->stream));
   HIPCHK(ctx, hipMemsetAsync(st.part_stamp, 0, (size_t)2 * ctx->max_grid * 4, ctx->stream));
   HIPCHK(ctx, hipMemsetAsync(st.part_all, 0xFF, (size_t)3 * 64 * PART_ALL_STRIDE * 4, ctx->stream));
-  ctx->pending_fin.nblk = 0, ctx->carry_fin.nblk = 0;
+  ctx->pending_fin.nblk = 0;
   HIPCHK(ctx, hipMemsetAsync(st.log_value, 0xFF, (size_t)g.S * 4, ctx->stream));
   HIPCHK(ctx, hipMemsetAsync(st.log_present, 0, (size_t)g.S, ctx->stream));
   for (int k = 0; k < 2; ++k) {
@@ -1083,14 +1114,15 @@ int host_group(const fpx_config& c, int slot) {
   return lg * c.num_groups + ag;
 }
 
-void split_runs(fpx_ctx* ctx, int n, const int32_t* slot, const int32_t* round, bool check_round,
-                std::vector<int>* cuts) {
+// what check_inputs found about a batch on its way: strictly increasing slots (hence distinct), one round
+struct BatchShape { bool increasing = false, one_round = false; };
+
+void split_runs(fpx_ctx* ctx, int n, const int32_t* slot, const int32_t* round, bool check_round, std::vector<int>* cuts,
+                BatchShape shape = {}) {
   cuts->clear();
   cuts->push_back(0);
-  // check_inputs saw strictly increasing slots (hence distinct) in one round: one run
-  const bool one_run = ctx->batch_increasing && (ctx->batch_one_round || !check_round || ctx->g.per_slot);
-  ctx->batch_increasing = ctx->batch_one_round = false;  // findings are about one batch only
-  if (one_run) {
+  // check_inputs saw strictly increasing slots in one round: one run
+  if (shape.increasing && (shape.one_round || !check_round || ctx->g.per_slot)) {
     cuts->push_back(n);
     return;
   }
@@ -1136,7 +1168,7 @@ int check_args(fpx_ctx* ctx, int n, const int32_t* slot, const int32_t* round) {
 // range check of a host batch; the host entry points run it (and split_runs) AFTER enqueueing the uploads,
 // so with page-locked buffers (fpx_host_alloc) the CPU passes overlap the DMA.  Nothing is launched on
 // a bad batch: the staging copies alone change no protocol state.
-int check_inputs(fpx_ctx* ctx, int n, const int32_t* slot, const int32_t* round) {
+int check_inputs(fpx_ctx* ctx, int n, const int32_t* slot, const int32_t* round, BatchShape* shape = nullptr) {
   // one branch-free pass (vectorises): range of slots and rounds, and whether the batch is the common
   // shape -- strictly increasing slots in one round -- that split_runs can accept as a single run
   int32_t smin = INT32_MAX, smax = INT32_MIN, rmin = INT32_MAX, rmax = INT32_MIN;
@@ -1146,8 +1178,7 @@ int check_inputs(fpx_ctx* ctx, int n, const int32_t* slot, const int32_t* round)
     rmin = std::min(rmin, round[i]), rmax = std::max(rmax, round[i]);
   }
   for (int i = 1; i < n; ++i) unordered |= (int32_t)(slot[i] <= slot[i - 1]);
-  ctx->batch_increasing = unordered == 0;
-  ctx->batch_one_round = rmin == rmax;
+  if (shape) shape->increasing = unordered == 0, shape->one_round = rmin == rmax;  // (of use to a batch in range only)
   if (smin >= 0 && smax < ctx->g.S && rmin >= 0 && rmax <= MAX_ROUND) return FPX_OK;
   for (int i = 0; i < n; ++i) {
     if (slot[i] < 0 || slot[i] >= ctx->g.S || round[i] < 0 || round[i] > MAX_ROUND) {
@@ -1157,7 +1188,6 @@ int check_inputs(fpx_ctx* ctx, int n, const int32_t* slot, const int32_t* round)
       break;
     }
   }
-  ctx->batch_increasing = ctx->batch_one_round = false;
   (void)hipStreamSynchronize(ctx->stream);  // the caller's buffers are free again when we return
   return FPX_EINVAL;
 }
@@ -1210,9 +1240,10 @@ T* staged(const DevBuf& b, size_t i) {
 
 // The driver of the host-pointer entry points.  Uploads the inputs and grows the outputs; then cut(&cuts) checks the
 // batch on the host -- behind the uploads, so with page-locked arrays the CPU pass overlaps the DMA; nothing is launched
-// on a bad batch -- and cuts it into runs that satisfy the run contract; run(lo, len) launches messages [lo, lo + len)
-// with ctx->index_base = lo, the runs back to back (= message-at-a-time delivery in array order); then the outputs come
-// down and the device's status is returned.  cut == nullptr: the whole batch is ONE run, validated on the device.
+// on a bad batch -- and cuts it into runs that satisfy the run contract; run(lo, len, opts) launches messages
+// [lo, lo + len) with opts.index_base = lo, the runs back to back (= message-at-a-time delivery in array order); then the
+// outputs come down and the device's status is returned.  cut == nullptr: the whole batch is ONE run, validated on the
+// device (RunOpts::FORCE_VALIDATE; the runs of a cut batch are RunOpts::CUT_ON_HOST).
 template <typename Cut, typename Run>
 int host_batch(fpx_ctx* ctx, int n, std::initializer_list<HostIn> in, std::initializer_list<HostOut> out, Cut cut,
                Run run) {
@@ -1226,14 +1257,13 @@ int host_batch(fpx_ctx* ctx, int n, std::initializer_list<HostIn> in, std::initi
   if constexpr (cut_on_host) {
     if ((rc = cut(&cuts))) return rc;
   }
-  {
-    HostFlags flags(ctx, cut_on_host);
-    for (size_t k = 0; k + 1 < cuts.size(); ++k) {
-      ctx->index_base = cuts[k];
-      if ((rc = run(cuts[k], cuts[k + 1] - cuts[k]))) {
-        (void)hipStreamSynchronize(ctx->stream);
-        return rc;
-      }
+  RunOpts opts;
+  opts.validate = cut_on_host ? RunOpts::CUT_ON_HOST : RunOpts::FORCE_VALIDATE;
+  for (size_t k = 0; k + 1 < cuts.size(); ++k) {
+    opts.index_base = cuts[k];
+    if ((rc = run(cuts[k], cuts[k + 1] - cuts[k], opts))) {
+      (void)hipStreamSynchronize(ctx->stream);
+      return rc;
     }
   }
   for (const HostOut& a : out)
@@ -1244,8 +1274,9 @@ int host_batch(fpx_ctx* ctx, int n, std::initializer_list<HostIn> in, std::initi
 // the cuts of a host batch of messages: the range check (the first offender for fpx_error_detail), then split_runs
 auto message_runs(fpx_ctx* ctx, int n, const int32_t* slot, const int32_t* round, bool check_round) {
   return [=](std::vector<int>* cuts) {
-    const int rc = check_inputs(ctx, n, slot, round);
-    if (rc == FPX_OK) split_runs(ctx, n, slot, round, check_round, cuts);
+    BatchShape shape;
+    const int rc = check_inputs(ctx, n, slot, round, &shape);
+    if (rc == FPX_OK) split_runs(ctx, n, slot, round, check_round, cuts, shape);
     return rc;
   };
 }
@@ -1318,12 +1349,10 @@ int host_submit(fpx_ctx* ctx, int n, const int32_t* slot, const int32_t* round, 
     if (in[a]) HIPCHK(ctx, hipMemcpyAsync(h.in[a].p, in[a], (size_t)n * in_elem[a], hipMemcpyHostToDevice, ctx->up_stream));
   HIPCHK(ctx, hipEventRecord(h.up, ctx->up_stream));
   HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, h.up, 0));
-  {
-    HostFlags flags(ctx, false);  // one run, validated on the device
-    rc = fpx_phase2_fused_dev(ctx, n, (int32_t*)h.in[0].p, (int32_t*)h.in[1].p, (int32_t*)h.in[2].p,
-                              target_mask ? (uint64_t*)h.in[3].p : nullptr, (uint8_t*)dout[0], (int32_t*)dout[1],
-                              (int32_t*)dout[2], (int32_t*)dout[3]);
-  }
+  // one run, validated on the device; a fold that the caller's guard left pending rides in its launch
+  rc = run_phase2_fused(ctx, n, (int32_t*)h.in[0].p, (int32_t*)h.in[1].p, (int32_t*)h.in[2].p,
+                        target_mask ? (uint64_t*)h.in[3].p : nullptr, (uint8_t*)dout[0], (int32_t*)dout[1], (int32_t*)dout[2],
+                        (int32_t*)dout[3], RunOpts{RunOpts::FORCE_VALIDATE});
   if (rc) {
     (void)hipStreamSynchronize(ctx->stream);
     return rc;
@@ -1437,7 +1466,7 @@ int host_p1i(fpx_ctx* ctx, int32_t chosen_watermark, const uint64_t* masks, bool
       ctx, 1, {{&ctx->d_bits_a, up ? masks : nullptr, 0, mbytes}},
       {{&ctx->p1i_off, offsets, 0, (E + 1) * 8}, {&ctx->d_i32_a, slot, 0, rec}, {&ctx->d_i32_b, vote_round, 0, rec},
        {&ctx->d_i32_c, vote_value, 0, rec}, {&ctx->p1i_tot, totals, 0, 16}},
-      nullptr, [&](int, int) {
+      nullptr, [&](int, int, const RunOpts&) {
         return enqueue_p1i(ctx, chosen_watermark, masks ? (const uint64_t*)ctx->d_bits_a.p : nullptr, cap,
                            (int64_t*)ctx->p1i_off.p, (int32_t*)ctx->d_i32_a.p, (int32_t*)ctx->d_i32_b.p, (int32_t*)ctx->d_i32_c.p,
                            (int64_t*)ctx->p1i_tot.p);
@@ -1876,11 +1905,9 @@ int32_t fpx_acceptor_phase2a_dev(fpx_ctx* ctx, int32_t n, const int32_t* d_slot,
                                  uint64_t* d_nack_bits, int32_t* d_nack_round) {
   DeviceGuard _dg(ctx);
   if (!ctx || n < 0) return FPX_EINVAL;
-  Batch b;
-  memset(&b, 0, sizeof(b));
-  b.n = n, b.slot = d_slot, b.round = d_round, b.value = d_value_id, b.target = d_target_mask;
+  Batch b = batch_of(n, d_slot, d_round, d_value_id, d_target_mask);
   b.vote_bits = d_vote_bits, b.nack_bits = d_nack_bits, b.nack_round = d_nack_round;
-  return enqueue_phase2(ctx, b, false);
+  return enqueue_phase2(ctx, b, false, RunOpts{});
 }
 
 int32_t fpx_wire_decode_proxy_leader_inbound_dev(fpx_ctx* ctx, const uint8_t* d_buf, int64_t buf_len,
@@ -1902,10 +1929,6 @@ int32_t fpx_wire_decode_acceptor_inbound_dev(fpx_ctx* ctx, const uint8_t* d_buf,
             value_id_base};
   return wire_decode_dev<1>(ctx, d_buf, buf_len, d_offsets, n, o);
 }
-
-int32_t fpx_phase2_fused_dev(fpx_ctx* ctx, int32_t n, const int32_t* d_slot, const int32_t* d_round,
-                             const int32_t* d_value_id, const uint64_t* d_target_mask, uint8_t* d_chosen,
-                             int32_t* d_chosen_round, int32_t* d_chosen_value, int32_t* d_nack_round);
 
 int32_t fpx_wire_encode_replica_chosen_dev(fpx_ctx* ctx, int32_t n, const uint8_t* d_emit, const int32_t* d_slot,
                                            const int32_t* d_is_noop, const uint8_t* d_values, int64_t values_len,
@@ -1975,7 +1998,7 @@ int32_t fpx_wire_phase2_tick(fpx_ctx* ctx, const uint8_t* in, int64_t in_len, co
       ctx, n, {{&ctx->w_buf, in, 0, (size_t)in_len}, {&ctx->w_off, in_offsets, 8, 8}},
       {{&ctx->w_out, out, 0, (size_t)out_cap}, {&ctx->w_ooff, out_offsets, 8, 8}, {&ctx->d_i32_c, nack_round, 4},
        {&ctx->w_tot, totals, 0, 16}},
-      nullptr, [&](int, int) {
+      nullptr, [&](int, int, const RunOpts& opts) {
         int32_t* rec[6];
         for (int k = 0; k < 6; ++k) rec[k] = (int32_t*)ctx->w_rec[k].p;
         int64_t* value_off = (int64_t*)ctx->w_rec[6].p;
@@ -1988,8 +2011,8 @@ int32_t fpx_wire_phase2_tick(fpx_ctx* ctx, const uint8_t* in, int64_t in_len, co
         hipLaunchKernelGGL(k_wire_tail, dim3(1), dim3(1), 0, ctx->stream, ctx->st);
         if ((r = launch_check(ctx))) return r;
         uint8_t* chosen = (uint8_t*)ctx->d_u8.p;
-        r = fpx_phase2_fused_dev(ctx, n, rec[1], rec[2], rec[5], nullptr, chosen, (int32_t*)ctx->d_i32_a.p,
-                                 (int32_t*)ctx->d_i32_b.p, (int32_t*)ctx->d_i32_c.p);
+        r = run_phase2_fused(ctx, n, rec[1], rec[2], rec[5], nullptr, chosen, (int32_t*)ctx->d_i32_a.p,
+                             (int32_t*)ctx->d_i32_b.p, (int32_t*)ctx->d_i32_c.p, opts);
         if (r) return r;
         return fpx_wire_encode_replica_chosen_dev(ctx, n, chosen, rec[1], rec[3], buf, in_len, value_off, rec[4],
                                                   (uint8_t*)ctx->w_out.p, out_cap, (int64_t*)ctx->w_ooff.p,
@@ -2008,21 +2031,17 @@ int32_t fpx_phase2_fused_dev(fpx_ctx* ctx, int32_t n, const int32_t* d_slot, con
                              int32_t* d_chosen_round, int32_t* d_chosen_value, int32_t* d_nack_round) {
   if (!ctx || n < 0) return FPX_EINVAL;
   DeviceGuard _dg(ctx->cfg.device);  // (by device number: a pending fold of the launch before is this call's to carry)
-  Batch b;
-  memset(&b, 0, sizeof(b));
-  b.n = n, b.slot = d_slot, b.round = d_round, b.value = d_value_id, b.target = d_target_mask;
-  b.chosen = d_chosen, b.chosen_round = d_chosen_round, b.chosen_value = d_chosen_value, b.nack_round = d_nack_round;
-  return enqueue_phase2(ctx, b, true);
+  return run_phase2_fused(ctx, n, d_slot, d_round, d_value_id, d_target_mask, d_chosen, d_chosen_round, d_chosen_value,
+                          d_nack_round, RunOpts{});
 }
 
 int32_t fpx_proxy_open_dev(fpx_ctx* ctx, int32_t n, const int32_t* d_slot, const int32_t* d_round,
                            const int32_t* d_value_id, uint8_t* d_is_new) {
   DeviceGuard _dg(ctx);
   if (!ctx || n < 0) return FPX_EINVAL;
-  Batch b;
-  memset(&b, 0, sizeof(b));
-  b.n = n, b.slot = d_slot, b.round = d_round, b.value = d_value_id, b.is_new = d_is_new;
-  return enqueue_open(ctx, b);
+  Batch b = batch_of(n, d_slot, d_round, d_value_id);
+  b.is_new = d_is_new;
+  return enqueue_open(ctx, b, RunOpts{});
 }
 
 int32_t fpx_proxy_phase2b_dev(fpx_ctx* ctx, int32_t n, const int32_t* d_slot, const int32_t* d_round,
@@ -2030,11 +2049,9 @@ int32_t fpx_proxy_phase2b_dev(fpx_ctx* ctx, int32_t n, const int32_t* d_slot, co
                               int32_t* d_chosen_value) {
   DeviceGuard _dg(ctx);
   if (!ctx || n < 0) return FPX_EINVAL;
-  Batch b;
-  memset(&b, 0, sizeof(b));
-  b.n = n, b.slot = d_slot, b.round = d_round, b.vote_bits = const_cast<uint64_t*>(d_vote_bits);
-  b.chosen = d_newly_chosen, b.chosen_round = d_chosen_round, b.chosen_value = d_chosen_value;
-  return enqueue_tally(ctx, b);
+  Batch b = batch_of(n, d_slot, d_round, nullptr);
+  b.vote_bits = const_cast<uint64_t*>(d_vote_bits), b.chosen = d_newly_chosen, b.chosen_round = d_chosen_round, b.chosen_value = d_chosen_value;
+  return enqueue_tally(ctx, b, RunOpts{});
 }
 
 int32_t fpx_proxy_phase2b_msgs_dev(fpx_ctx* ctx, int32_t n, const int32_t* d_kind, const int32_t* d_group_index,
@@ -2065,7 +2082,7 @@ int32_t fpx_proxy_phase2b_msgs(fpx_ctx* ctx, int32_t n, const int32_t* kind, con
                     {{&ctx->d_value, kind, 4}, {&ctx->d_target, group_index, 4}, {&ctx->d_i32_c, acceptor_index, 4},
                      {&ctx->d_slot, slot, 4}, {&ctx->d_round, round, 4}},
                     {{&ctx->d_u8, newly_chosen, 1}, {&ctx->d_i32_a, chosen_round, 4}, {&ctx->d_i32_b, chosen_value, 4}},
-                    nullptr, [&](int, int) {
+                    nullptr, [&](int, int, const RunOpts&) {
                       return fpx_proxy_phase2b_msgs_dev(
                           ctx, n, kind ? (const int32_t*)ctx->d_value.p : nullptr,
                           group_index ? (const int32_t*)ctx->d_target.p : nullptr, (const int32_t*)ctx->d_i32_c.p,
@@ -2105,7 +2122,7 @@ int32_t fpx_wire_phase2b_tick(fpx_ctx* ctx, const uint8_t* in, int64_t in_len, c
       ctx, n, {{&ctx->w_buf, in, 0, (size_t)in_len}, {&ctx->w_off, in_offsets, 8, 8}},
       {{&ctx->w_out, out_slot, 0, rec}, {&ctx->w_ooff, out_round, 0, rec}, {&ctx->d_i32_c, out_value_id, 0, rec},
        {&ctx->w_tot, totals, 0, 16}},
-      nullptr, [&](int, int) {
+      nullptr, [&](int, int, const RunOpts&) {
         int32_t* r5[5];
         for (int k = 0; k < 5; ++k) r5[k] = (int32_t*)ctx->w_rec[k].p;  // kind, slot, round, group_index, acceptor_index
         int r = fpx_wire_decode_proxy_leader_inbound_dev(ctx, (const uint8_t*)ctx->w_buf.p, in_len,
@@ -2142,14 +2159,13 @@ int32_t fpx_acceptor_phase2a(fpx_ctx* ctx, int32_t n, const int32_t* slot, const
                     {{&ctx->d_slot, slot, 4}, {&ctx->d_round, round, 4}, {&ctx->d_value, value_id, 4},
                      {&ctx->d_target, target_mask, 32}},
                     {{&ctx->d_bits_a, vote_bits, 32}, {&ctx->d_bits_b, nack_bits, 32}, {&ctx->d_i32_a, nack_round, 4}},
-                    message_runs(ctx, n, slot, round, true), [&](int lo, int len) {
-                      return fpx_acceptor_phase2a_dev(
-                          ctx, len, staged<int32_t>(ctx->d_slot, lo), staged<int32_t>(ctx->d_round, lo),
-                          staged<int32_t>(ctx->d_value, lo),
-                          target_mask ? staged<uint64_t>(ctx->d_target, (size_t)lo * 4) : nullptr,
-                          staged<uint64_t>(ctx->d_bits_a, (size_t)lo * 4),
-                          nack_bits ? staged<uint64_t>(ctx->d_bits_b, (size_t)lo * 4) : nullptr,
-                          staged<int32_t>(ctx->d_i32_a, lo));
+                    message_runs(ctx, n, slot, round, true), [&](int lo, int len, const RunOpts& opts) {
+                      Batch b = batch_of(len, staged<int32_t>(ctx->d_slot, lo), staged<int32_t>(ctx->d_round, lo),
+                                         staged<int32_t>(ctx->d_value, lo),
+                                         target_mask ? staged<uint64_t>(ctx->d_target, (size_t)lo * 4) : nullptr);
+                      b.vote_bits = staged<uint64_t>(ctx->d_bits_a, (size_t)lo * 4), b.nack_round = staged<int32_t>(ctx->d_i32_a, lo);
+                      b.nack_bits = nack_bits ? staged<uint64_t>(ctx->d_bits_b, (size_t)lo * 4) : nullptr;
+                      return enqueue_phase2(ctx, b, false, opts);
                     });
 }
 
@@ -2172,12 +2188,10 @@ int32_t fpx_phase2_fused(fpx_ctx* ctx, int32_t n, const int32_t* slot, const int
   }
   const std::initializer_list<HostOut> out = {
       {&ctx->d_u8, chosen, 1}, {&ctx->d_i32_a, chosen_round, 4}, {&ctx->d_i32_b, chosen_value, 4}, {&ctx->d_i32_c, nack_round, 4}};
-  auto run = [&](int lo, int len) {
-    return fpx_phase2_fused_dev(ctx, len, staged<int32_t>(ctx->d_slot, lo), staged<int32_t>(ctx->d_round, lo),
-                                staged<int32_t>(ctx->d_value, lo),
-                                target_mask ? staged<uint64_t>(ctx->d_target, (size_t)lo * 4) : nullptr,
-                                staged<uint8_t>(ctx->d_u8, lo), staged<int32_t>(ctx->d_i32_a, lo),
-                                staged<int32_t>(ctx->d_i32_b, lo), staged<int32_t>(ctx->d_i32_c, lo));
+  auto run = [&](int lo, int len, const RunOpts& opts) {  // (the fold of one run rides in the next run's launch)
+    return run_phase2_fused(ctx, len, staged<int32_t>(ctx->d_slot, lo), staged<int32_t>(ctx->d_round, lo), staged<int32_t>(ctx->d_value, lo),
+                            target_mask ? staged<uint64_t>(ctx->d_target, (size_t)lo * 4) : nullptr, staged<uint8_t>(ctx->d_u8, lo),
+                            staged<int32_t>(ctx->d_i32_a, lo), staged<int32_t>(ctx->d_i32_b, lo), staged<int32_t>(ctx->d_i32_c, lo), opts);
   };
   rc = host_batch(ctx, n,
                   {{&ctx->d_slot, slot, 4}, {&ctx->d_round, round, 4}, {&ctx->d_value, value_id, 4},
@@ -2217,9 +2231,11 @@ int32_t fpx_proxy_open(fpx_ctx* ctx, int32_t n, const int32_t* slot, const int32
   if (n == 0) return FPX_OK;
   if (!value_id) return FPX_EINVAL;
   return host_batch(ctx, n, {{&ctx->d_slot, slot, 4}, {&ctx->d_round, round, 4}, {&ctx->d_value, value_id, 4}},
-                    {{&ctx->d_u8, is_new, 1}}, message_runs(ctx, n, slot, round, false), [&](int lo, int len) {
-                      return fpx_proxy_open_dev(ctx, len, staged<int32_t>(ctx->d_slot, lo), staged<int32_t>(ctx->d_round, lo),
-                                                staged<int32_t>(ctx->d_value, lo), staged<uint8_t>(ctx->d_u8, lo));
+                    {{&ctx->d_u8, is_new, 1}}, message_runs(ctx, n, slot, round, false), [&](int lo, int len, const RunOpts& opts) {
+                      Batch b = batch_of(len, staged<int32_t>(ctx->d_slot, lo), staged<int32_t>(ctx->d_round, lo),
+                                         staged<int32_t>(ctx->d_value, lo));
+                      b.is_new = staged<uint8_t>(ctx->d_u8, lo);
+                      return enqueue_open(ctx, b, opts);
                     });
 }
 
@@ -2232,10 +2248,11 @@ int32_t fpx_proxy_phase2b(fpx_ctx* ctx, int32_t n, const int32_t* slot, const in
   if (!vote_bits) return FPX_EINVAL;
   return host_batch(ctx, n, {{&ctx->d_slot, slot, 4}, {&ctx->d_round, round, 4}, {&ctx->d_bits_a, vote_bits, 32}},
                     {{&ctx->d_u8, newly_chosen, 1}, {&ctx->d_i32_a, chosen_round, 4}, {&ctx->d_i32_b, chosen_value, 4}},
-                    message_runs(ctx, n, slot, round, false), [&](int lo, int len) {
-                      return fpx_proxy_phase2b_dev(ctx, len, staged<int32_t>(ctx->d_slot, lo), staged<int32_t>(ctx->d_round, lo),
-                                                   staged<uint64_t>(ctx->d_bits_a, (size_t)lo * 4), staged<uint8_t>(ctx->d_u8, lo),
-                                                   staged<int32_t>(ctx->d_i32_a, lo), staged<int32_t>(ctx->d_i32_b, lo));
+                    message_runs(ctx, n, slot, round, false), [&](int lo, int len, const RunOpts& opts) {
+                      Batch b = batch_of(len, staged<int32_t>(ctx->d_slot, lo), staged<int32_t>(ctx->d_round, lo), nullptr);
+                      b.vote_bits = staged<uint64_t>(ctx->d_bits_a, (size_t)lo * 4), b.chosen = staged<uint8_t>(ctx->d_u8, lo);
+                      b.chosen_round = staged<int32_t>(ctx->d_i32_a, lo), b.chosen_value = staged<int32_t>(ctx->d_i32_b, lo);
+                      return enqueue_tally(ctx, b, opts);
                     });
 }
 
@@ -2381,8 +2398,8 @@ static int32_t ranges_ctx_ok(fpx_ctx* ctx, int32_t n) {
 
 enum { RANGES_FUSED = 0, RANGES_ACCEPTORS = 1, RANGES_OPEN = 2, RANGES_TALLY = 3 };
 
-// one device run of n ranges; vote_bits must be present for every mode but RANGES_OPEN
-static int enqueue_ranges(fpx_ctx* ctx, RangeBatch& b, int mode) {
+// one device run of n ranges, launched on `stream`; vote_bits must be present for every mode but RANGES_OPEN
+static int enqueue_ranges(fpx_ctx* ctx, RangeBatch& b, int mode, const RunOpts& opts, hipStream_t stream) {
   if (b.n == 0) return FPX_OK;
   const Geom& g = ctx->g;
   const size_t words = (size_t)b.n * g.num_groups * 4;
@@ -2391,10 +2408,9 @@ static int enqueue_ranges(fpx_ctx* ctx, RangeBatch& b, int mode) {
   b.quorum = ctx->cfg.f + 1;
   const int gn = (b.n + 255) / 256;
   const bool acceptors = mode == RANGES_FUSED || mode == RANGES_ACCEPTORS;
-  const bool validate = !(((ctx->cfg.flags & FPX_F_TRUSTED) && !ctx->force_validate) || ctx->host_validated);
-  if (validate) {
-    if (acceptors) fill32(ctx, ctx->st.run_round, -1, (size_t)g.ngroups);
-    hipLaunchKernelGGL(k_ranges_validate, dim3(gn), dim3(256), 0, ctx->stream, g, ctx->st, b, acceptors ? 1 : 0);
+  if (opts.validates(ctx)) {
+    if (acceptors) fill32(ctx, ctx->st.run_round, -1, (size_t)g.ngroups, stream);
+    hipLaunchKernelGGL(k_ranges_validate, dim3(gn), dim3(256), 0, stream, g, ctx->st, b, acceptors ? 1 : 0);
   }
   const RangeTable& rt = ctx->rt[ctx->rt_cur];
   // a few ranges: one workgroup walks clear -> open -> resolve -> acceptors -> tally (fpx_ranges.hpp: k_ranges_chain)
@@ -2405,25 +2421,25 @@ static int enqueue_ranges(fpx_ctx* ctx, RangeBatch& b, int mode) {
   ++ctx->range_census[mode != RANGES_FUSED ? only[mode] : chain ? FPX_RANGE_CENSUS_CHAIN : FPX_RANGE_CENSUS_STEPS];
   if (chain) {
     allow_lds(k_ranges_chain, (size_t)chain_words * 4 + 64);
-    hipLaunchKernelGGL(k_ranges_chain, dim3(1), dim3(1024), (size_t)chain_words * 4, ctx->stream, g, ctx->st, rt, b);
+    hipLaunchKernelGGL(k_ranges_chain, dim3(1), dim3(1024), (size_t)chain_words * 4, stream, g, ctx->st, rt, b);
   }
   if (acceptors && !chain) {
-    fill32(ctx, b.vote_bits, 0, words * 2);
-    if (b.nack_bits) fill32(ctx, b.nack_bits, 0, words * 2);
-    if (b.nack_round) fill32(ctx, b.nack_round, -1, (size_t)b.n);
+    fill32(ctx, b.vote_bits, 0, words * 2, stream);
+    if (b.nack_bits) fill32(ctx, b.nack_bits, 0, words * 2, stream);
+    if (b.nack_round) fill32(ctx, b.nack_round, -1, (size_t)b.n, stream);
   }
   if (!chain && (mode == RANGES_FUSED || mode == RANGES_OPEN)) {
-    hipLaunchKernelGGL(k_ranges_open, dim3(gn), dim3(256), 0, ctx->stream, g, ctx->st, rt, b, 0);
-    hipLaunchKernelGGL(k_ranges_resolve, dim3(gn), dim3(256), 0, ctx->stream, g, ctx->st, rt, b);
+    hipLaunchKernelGGL(k_ranges_open, dim3(gn), dim3(256), 0, stream, g, ctx->st, rt, b, 0);
+    hipLaunchKernelGGL(k_ranges_resolve, dim3(gn), dim3(256), 0, stream, g, ctx->st, rt, b);
   }
   if (acceptors) {
     const long long threads = (long long)b.n * g.num_groups * g.R;
     if (!chain)
-      hipLaunchKernelGGL(k_ranges_acceptors, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, ctx->stream, g, ctx->st, b);
+      hipLaunchKernelGGL(k_ranges_acceptors, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, stream, g, ctx->st, b);
     if (g.lg_rows) {  // leader-group-major rows: a range is one run of rows
       const int gy = std::min(b.n, 4096);
       const int gx = std::max(1, std::min(ctx->num_cus * 16 / gy, 64));
-      hipLaunchKernelGGL(k_ranges_fill_lg, dim3(gx, gy), dim3(256), 0, ctx->stream, g, ctx->st, b);
+      hipLaunchKernelGGL(k_ranges_fill_lg, dim3(gx, gy), dim3(256), 0, stream, g, ctx->st, b);
       ++ctx->range_census[FPX_RANGE_CENSUS_FILL_LG];
     } else if (b.n <= RF_MAXN && g.num_leader_groups <= RF_MAXL) {
       // (RF_JB rows of L ownership words + the kernel's own 12 static bytes: beyond the default 64 KiB of dynamic LDS
@@ -2431,38 +2447,47 @@ static int enqueue_ranges(fpx_ctx* ctx, RangeBatch& b, int mode) {
       allow_lds(k_ranges_fill_rows, (size_t)RF_JB * g.num_leader_groups * 4 + 64);
       // sweep the log rows the ranges touch in memory order (fpx_ranges.hpp)
       hipLaunchKernelGGL(k_ranges_fill_rows, dim3(ctx->num_cus * 8), dim3(256), (size_t)RF_JB * g.num_leader_groups * 4,
-                         ctx->stream, g, ctx->st, b);
+                         stream, g, ctx->st, b);
       ++ctx->range_census[FPX_RANGE_CENSUS_FILL_SWEEP];
     } else {
       const int gy = std::min(b.n, 4096);
       const int gx = std::max(1, std::min(ctx->num_cus * 16 / gy, 64));
-      hipLaunchKernelGGL(k_ranges_fill, dim3(gx, gy), dim3(256), 0, ctx->stream, g, ctx->st, b);
+      hipLaunchKernelGGL(k_ranges_fill, dim3(gx, gy), dim3(256), 0, stream, g, ctx->st, b);
       ++ctx->range_census[FPX_RANGE_CENSUS_FILL_RANGE];
     }
   }
-  if (mode == RANGES_TALLY) hipLaunchKernelGGL(k_ranges_open, dim3(gn), dim3(256), 0, ctx->stream, g, ctx->st, rt, b, 1);
+  if (mode == RANGES_TALLY) hipLaunchKernelGGL(k_ranges_open, dim3(gn), dim3(256), 0, stream, g, ctx->st, rt, b, 1);
   if (!chain && (mode == RANGES_FUSED || mode == RANGES_TALLY))
-    hipLaunchKernelGGL(k_ranges_tally, dim3(gn), dim3(256), 0, ctx->stream, g, ctx->st, rt, b);
+    hipLaunchKernelGGL(k_ranges_tally, dim3(gn), dim3(256), 0, stream, g, ctx->st, rt, b);
   return launch_check(ctx);
+}
+
+// the batch of one fused device run of n ranges, its scratch in d_rng (grow may reallocate it: a caller with a side stream
+// builds the batch while nothing of that stream is in flight)
+static int ranges_fused_batch(fpx_ctx* ctx, int32_t n, const int32_t* d_slot_start, const int32_t* d_slot_end,
+                              const int32_t* d_round, const uint64_t* d_target_masks, uint64_t* d_vote_bits, uint64_t* d_nack_bits,
+                              int32_t* d_nack_round, uint8_t* d_is_new, uint8_t* d_chosen, RangeBatch* b) {
+  memset(b, 0, sizeof(*b));
+  int rc = ranges_ctx_ok(ctx, n);
+  if (rc || n == 0) return rc;
+  const size_t words = (size_t)n * ctx->g.num_groups * 4;
+  // scratch: entry[n], and the vote bitmaps when the caller does not want them
+  if ((rc = grow(ctx, &ctx->d_rng, (size_t)n * 4 + 64 + (d_vote_bits ? 0 : words * 8)))) return rc;
+  b->n = n, b->start = d_slot_start, b->end = d_slot_end, b->round = d_round, b->target = d_target_masks;
+  b->entry = (int32_t*)ctx->d_rng.p;
+  b->vote_bits = d_vote_bits ? d_vote_bits : (uint64_t*)((char*)ctx->d_rng.p + (((size_t)n * 4 + 63) & ~(size_t)63));
+  b->nack_bits = d_nack_bits, b->nack_round = d_nack_round, b->is_new = d_is_new, b->chosen = d_chosen;
+  return FPX_OK;
 }
 
 int32_t fpx_noop_ranges_fused_dev(fpx_ctx* ctx, int32_t n, const int32_t* d_slot_start, const int32_t* d_slot_end,
                                   const int32_t* d_round, const uint64_t* d_target_masks, uint64_t* d_vote_bits,
                                   uint64_t* d_nack_bits, int32_t* d_nack_round, uint8_t* d_is_new, uint8_t* d_chosen) {
   DeviceGuard _dg(ctx);
-  int rc = ranges_ctx_ok(ctx, n);
-  if (rc) return rc;
-  if (n == 0) return FPX_OK;
-  const size_t words = (size_t)n * ctx->g.num_groups * 4;
-  // scratch: entry[n], and the vote bitmaps when the caller does not want them
-  if ((rc = grow(ctx, &ctx->d_rng, (size_t)n * 4 + 64 + (d_vote_bits ? 0 : words * 8)))) return rc;
   RangeBatch b;
-  memset(&b, 0, sizeof(b));
-  b.n = n, b.start = d_slot_start, b.end = d_slot_end, b.round = d_round, b.target = d_target_masks;
-  b.entry = (int32_t*)ctx->d_rng.p;
-  b.vote_bits = d_vote_bits ? d_vote_bits : (uint64_t*)((char*)ctx->d_rng.p + (((size_t)n * 4 + 63) & ~(size_t)63));
-  b.nack_bits = d_nack_bits, b.nack_round = d_nack_round, b.is_new = d_is_new, b.chosen = d_chosen;
-  return enqueue_ranges(ctx, b, RANGES_FUSED);
+  const int rc = ranges_fused_batch(ctx, n, d_slot_start, d_slot_end, d_round, d_target_masks, d_vote_bits, d_nack_bits, d_nack_round,
+                                    d_is_new, d_chosen, &b);
+  return rc ? rc : enqueue_ranges(ctx, b, RANGES_FUSED, RunOpts{}, ctx->stream);
 }
 
 // A band whose halves are independent, in TWO launches instead of four (profiles/r05_cfg5.md): the vote kernel with the
@@ -2470,7 +2495,7 @@ int32_t fpx_noop_ranges_fused_dev(fpx_ctx* ctx, int32_t n, const int32_t* d_slot
 // its grid (k_ranges_fill_lg_fin).  Only for the everyday shape -- groups of at most 32 acceptors on leader-group-major
 // rows, dense delivery, a chain that fits the vote kernel's own LDS, more than one workgroup of commands; *done = false
 // with nothing enqueued otherwise (the caller takes the serial order).
-static int enqueue_band_merged(fpx_ctx* ctx, Batch& b, RangeBatch& rb, bool* done) {
+static int enqueue_band_merged(fpx_ctx* ctx, Batch& b, RangeBatch& rb, const RunOpts& opts, bool* done) {
   *done = false;
   const Geom& g = ctx->g;
   const int G = ctx->lanes_per_slot;
@@ -2484,33 +2509,30 @@ static int enqueue_band_merged(fpx_ctx* ctx, Batch& b, RangeBatch& rb, bool* don
   const size_t lds = std::max(phase2_lds(ctx, b, true, false, true), (size_t)chain_words * 4);
   if (lds > 26000) return FPX_OK;
   // -- from here on as enqueue_phase2 and enqueue_ranges (FPX_F_TRUSTED: no validation passes) --
-  b.index_base = ctx->index_base;
-  int rc = enqueue_validate(ctx, b, true);
+  int rc = enqueue_validate(ctx, b, true, opts);
   if (rc) return rc;
   const int grid = grid_for(ctx, b.n);
   if ((b.n + 4 * b.chunk - 1) / (4 * b.chunk) > grid) ++ctx->census[FPX_CENSUS_CAPPED];
   b.solo = 0;
-  begin_phase2_launch(ctx, b);
+  VoteLaunch vl;
+  vl.st = begin_phase2_launch(ctx, b);
   if (++ctx->launch_seq == 0) ctx->launch_seq = 1;
   b.launch_seq = ctx->launch_seq;
   rb.run_id = ++ctx->run_id;
   rb.fused = 1;
   rb.quorum = ctx->cfg.f + 1;
   const bool prof = ctx->profiling && ctx->ev_used + 2 <= ctx->ev.size();
-  ctx->ev_start = prof ? ctx->ev[ctx->ev_used] : nullptr;
-  ctx->ev_stop = prof ? ctx->ev[ctx->ev_used + 1] : nullptr;
-  const RangeTable& rt = ctx->rt[ctx->rt_cur];
-  launch_band(ctx, b, lds, grid, rt, rb);
-  ctx->ev_start = ctx->ev_stop = nullptr;
+  vl.ev_start = prof ? ctx->ev[ctx->ev_used] : nullptr;
+  vl.ev_stop = prof ? ctx->ev[ctx->ev_used + 1] : nullptr;
+  launch_band(ctx, vl, b, lds, grid, rb);
   if (prof) ctx->ev_used += 2;
   if ((rc = launch_check(ctx))) return rc;
-  const int ntab = g.ngroups * g.R;
-  const int slices = std::max(FINALIZE_SLICES, std::min(256, grid / 32)), fgx = (ntab + 63) / 64;
+  const FinJob fj = fin_job_of(ctx, vl.st, b, grid);  // the vote launch's fold: further rows of the fill's grid
   const int gy = std::min(rb.n, 4096);
   const int gx = std::max(1, std::min(ctx->num_cus * 16 / gy, 64));
-  const int fin_rows = (fgx * slices + gx - 1) / gx;
-  hipLaunchKernelGGL(k_ranges_fill_lg_fin, dim3(gx, gy + fin_rows), dim3(256), 0, ctx->stream, g, ctx->launch_st, rb, gy, fin_rows,
-                     (int)b.parity, grid, b.launch_seq, fgx, slices);
+  const int fin_rows = (fj.nblk + gx - 1) / gx;
+  hipLaunchKernelGGL(k_ranges_fill_lg_fin, dim3(gx, gy + fin_rows), dim3(256), 0, ctx->stream, g, vl.st, rb, gy, fin_rows,
+                     fj.par, fj.grid, fj.seq, fj.fgx, fj.slices);
   *done = true;
   ++ctx->band_merged_steps;
   ++ctx->range_census[FPX_RANGE_CENSUS_BAND];
@@ -2530,12 +2552,23 @@ int32_t fpx_mencius_band_fused_dev(fpx_ctx* ctx, int32_t n, const int32_t* d_slo
   DeviceGuard _dg(ctx);
   if (!ctx || n < 0 || n_ranges < 0) return FPX_EINVAL;
   int rc;
-  if (!independent || n == 0 || n_ranges == 0 || ctx->g.per_slot) {  // the serial order (what the two calls would do)
-    if ((rc = fpx_phase2_fused_dev(ctx, n, d_slot, d_round, d_value_id, d_target_mask, d_chosen, d_chosen_round, d_chosen_value, d_nack_round)))
-      return rc;
-    return fpx_noop_ranges_fused_dev(ctx, n_ranges, d_slot_start, d_slot_end, d_range_round, d_range_target_masks, d_range_vote_bits,
-                                     d_range_nack_bits, d_range_nack_round, d_range_is_new, d_range_chosen);
-  }
+  const RunOpts opts{};
+  auto commands = [&] {
+    return run_phase2_fused(ctx, n, d_slot, d_round, d_value_id, d_target_mask, d_chosen, d_chosen_round, d_chosen_value, d_nack_round, opts);
+  };
+  RangeBatch rb;
+  auto range_batch = [&] {
+    return ranges_fused_batch(ctx, n_ranges, d_slot_start, d_slot_end, d_range_round, d_range_target_masks, d_range_vote_bits,
+                              d_range_nack_bits, d_range_nack_round, d_range_is_new, d_range_chosen, &rb);
+  };
+  // the serial order (what the two calls would do: the second one's guard launches the fold the first one left pending)
+  auto serial = [&] {
+    int r = commands();
+    if (r) return r;
+    flush_pending_fin(ctx);
+    return (r = range_batch()) ? r : enqueue_ranges(ctx, rb, RANGES_FUSED, opts, ctx->stream);
+  };
+  if (!independent || n == 0 || n_ranges == 0 || ctx->g.per_slot) return serial();
   if (!ctx->band_stream) {
     if (hipStreamCreateWithFlags(&ctx->band_stream, hipStreamNonBlocking) != hipSuccess) return FPX_EHIP;
     if (hipEventCreateWithFlags(&ctx->band_fork, hipEventDisableTiming) != hipSuccess ||
@@ -2546,8 +2579,7 @@ int32_t fpx_mencius_band_fused_dev(fpx_ctx* ctx, int32_t n, const int32_t* d_slo
   // the range chain's plain store of an acceptor's round race with k_finalize's atomicMax: silently wrong state, ADVICE
   // r05).  (Not FPX_DEBUG, which only logs: the check sends the step down the validating path, 0.076 -> 0.087 ms per band.)
   const bool debug_env = getenv("FPX_DEBUG_CHECKS") != nullptr;
-  const bool validate = !((ctx->cfg.flags & FPX_F_TRUSTED) && !ctx->force_validate) || debug_env;
-  if (validate) {
+  if (opts.validates(ctx) || debug_env) {
     // is the caller's word good?  Checked before anything is applied (FPX_EORDER, nothing applied); the halves themselves
     // then run one after the other: their run-contract checks share one scratch table (State::run_round)
     const int L = ctx->g.num_leader_groups;
@@ -2555,42 +2587,24 @@ int32_t fpx_mencius_band_fused_dev(fpx_ctx* ctx, int32_t n, const int32_t* d_slo
     fill32(ctx, (int32_t*)ctx->d_band.p, 0, (size_t)L);
     hipLaunchKernelGGL(k_band_mark, dim3((n_ranges + 255) / 256), dim3(256), 0, ctx->stream, ctx->g, n_ranges, d_slot_start, (int32_t*)ctx->d_band.p);
     hipLaunchKernelGGL(k_band_check, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, ctx->g, ctx->st, n, d_slot, d_round,
-                       (const int32_t*)ctx->d_band.p, ctx->index_base);
+                       (const int32_t*)ctx->d_band.p, opts.index_base);
     // a launch that failed here would skip the one check this path exists for, silently
     if ((rc = launch_check(ctx))) return rc;
-    if ((rc = fpx_phase2_fused_dev(ctx, n, d_slot, d_round, d_value_id, d_target_mask, d_chosen, d_chosen_round, d_chosen_value, d_nack_round)))
-      return rc;
-    return fpx_noop_ranges_fused_dev(ctx, n_ranges, d_slot_start, d_slot_end, d_range_round, d_range_target_masks, d_range_vote_bits,
-                                     d_range_nack_bits, d_range_nack_round, d_range_is_new, d_range_chosen);
+    return serial();
   }
-  // the ranges' scratch is sized on the main stream (grow may reallocate: nothing of the side stream is in flight here,
-  // the previous step joined)
-  const size_t words = (size_t)n_ranges * ctx->g.num_groups * 4;
-  if ((rc = ranges_ctx_ok(ctx, n_ranges))) return rc;
-  if ((rc = grow(ctx, &ctx->d_rng, (size_t)n_ranges * 4 + 64 + (d_range_vote_bits ? 0 : words * 8)))) return rc;
+  // the ranges' scratch is sized here, on the main stream: nothing of the side stream is in flight, the previous step joined
+  if ((rc = range_batch())) return rc;
   {
-    Batch b;
-    memset(&b, 0, sizeof(b));
-    b.n = n, b.slot = d_slot, b.round = d_round, b.value = d_value_id, b.target = d_target_mask;
+    Batch b = batch_of(n, d_slot, d_round, d_value_id, d_target_mask);
     b.chosen = d_chosen, b.chosen_round = d_chosen_round, b.chosen_value = d_chosen_value, b.nack_round = d_nack_round;
-    RangeBatch rb;
-    memset(&rb, 0, sizeof(rb));
-    rb.n = n_ranges, rb.start = d_slot_start, rb.end = d_slot_end, rb.round = d_range_round, rb.target = d_range_target_masks;
-    rb.entry = (int32_t*)ctx->d_rng.p;
-    rb.vote_bits = d_range_vote_bits ? d_range_vote_bits : (uint64_t*)((char*)ctx->d_rng.p + (((size_t)n_ranges * 4 + 63) & ~(size_t)63));
-    rb.nack_bits = d_range_nack_bits, rb.nack_round = d_range_nack_round, rb.is_new = d_range_is_new, rb.chosen = d_range_chosen;
     bool done = false;
-    if ((rc = enqueue_band_merged(ctx, b, rb, &done)) || done) return rc;
+    if ((rc = enqueue_band_merged(ctx, b, rb, opts, &done)) || done) return rc;  // (not done: rb is as range_batch left it)
   }
   HIPCHK(ctx, hipEventRecord(ctx->band_fork, ctx->stream));
   HIPCHK(ctx, hipStreamWaitEvent(ctx->band_stream, ctx->band_fork, 0));
-  hipStream_t main_stream = ctx->stream;
-  ctx->stream = ctx->band_stream;
-  rc = fpx_noop_ranges_fused_dev(ctx, n_ranges, d_slot_start, d_slot_end, d_range_round, d_range_target_masks, d_range_vote_bits,
-                                 d_range_nack_bits, d_range_nack_round, d_range_is_new, d_range_chosen);
+  rc = enqueue_ranges(ctx, rb, RANGES_FUSED, opts, ctx->band_stream);
   const hipError_t je = hipEventRecord(ctx->band_join, ctx->band_stream);
-  ctx->stream = main_stream;
-  int rc2 = fpx_phase2_fused_dev(ctx, n, d_slot, d_round, d_value_id, d_target_mask, d_chosen, d_chosen_round, d_chosen_value, d_nack_round);
+  const int rc2 = commands();
   if (je == hipSuccess) HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, ctx->band_join, 0));
   if (je != hipSuccess) return FPX_EHIP;
   return rc ? rc : rc2;
@@ -2680,7 +2694,7 @@ static int32_t host_ranges(fpx_ctx* ctx, int mode, int32_t n, const int32_t* sta
         split_range_runs(ctx, n, start, end, round, true, tally, cuts);
         return FPX_OK;
       },
-      [&](int lo, int len) {
+      [&](int lo, int len, const RunOpts& opts) {
         RangeBatch b;
         memset(&b, 0, sizeof(b));
         b.n = len, b.start = staged<int32_t>(rs.start, lo), b.end = staged<int32_t>(rs.end, lo);
@@ -2690,7 +2704,7 @@ static int32_t host_ranges(fpx_ctx* ctx, int mode, int32_t n, const int32_t* sta
         b.vote_bits = staged<uint64_t>(rs.votes, lo * per), b.nack_bits = staged<uint64_t>(rs.nacks, lo * per);
         b.is_new = staged<uint8_t>(rs.is_new, lo), b.chosen = staged<uint8_t>(rs.chosen, lo);
         if (tally) b.votes_in = b.vote_bits;
-        return enqueue_ranges(ctx, b, mode);
+        return enqueue_ranges(ctx, b, mode, opts, ctx->stream);
       });
 }
 
@@ -2784,7 +2798,7 @@ int32_t fpx_mencius_proxy_phase2b_msgs(fpx_ctx* ctx, int32_t n, const int32_t* k
                     {{&ctx->d_value, kind, 4}, {&ctx->d_target, group_index, 4}, {&ctx->d_i32_c, acceptor_index, 4},
                      {&ctx->d_slot, slot, 4}, {&ctx->mm_end, slot_end, 4}, {&ctx->d_round, round, 4}},
                     {{&ctx->d_u8, newly_chosen, 1}, {&ctx->d_i32_a, chosen_round, 4}, {&ctx->d_i32_b, chosen_value, 4}},
-                    nullptr, [&](int, int) {
+                    nullptr, [&](int, int, const RunOpts&) {
                       return fpx_mencius_proxy_phase2b_msgs_dev(
                           ctx, n, kind ? (const int32_t*)ctx->d_value.p : nullptr,
                           group_index ? (const int32_t*)ctx->d_target.p : nullptr, (const int32_t*)ctx->d_i32_c.p,
@@ -2824,7 +2838,7 @@ int32_t fpx_mencius_phase2b_tick(fpx_ctx* ctx, int32_t n, const int32_t* kind, c
        {&ctx->d_slot, slot, 4}, {&ctx->mm_end, slot_end, 4}, {&ctx->d_round, round, 4}},
       {{&ctx->mm_rec[0], out_kind, 0, rec}, {&ctx->mm_rec[1], out_slot, 0, rec}, {&ctx->mm_rec[2], out_slot_end, 0, rec},
        {&ctx->mm_rec[3], out_round, 0, rec}, {&ctx->mm_rec[4], out_value_id, 0, rec}, {&ctx->w_tot, totals, 0, 16}},
-      nullptr, [&](int, int) {
+      nullptr, [&](int, int, const RunOpts&) {
         const int32_t* d_kind = kind ? (const int32_t*)ctx->d_value.p : nullptr;
         const int32_t* d_end = slot_end ? (const int32_t*)ctx->mm_end.p : nullptr;
         int r = fpx_mencius_proxy_phase2b_msgs_dev(ctx, n, d_kind, group_index ? (const int32_t*)ctx->d_target.p : nullptr,
@@ -2893,18 +2907,7 @@ int32_t fpx_replica_chosen_dev(fpx_ctx* ctx, int32_t n, const int32_t* d_slot, c
                                const uint8_t* d_mask) {
   DeviceGuard _dg(ctx);
   if (!ctx || n < 0) return FPX_EINVAL;
-  if (n == 0) return FPX_OK;
-  Batch b;
-  memset(&b, 0, sizeof(b));
-  b.n = n, b.slot = d_slot, b.value = d_value_id, b.mask = d_mask;
-  int rc = enqueue_validate(ctx, b, false);
-  if (rc) return rc;
-  const int ingest_grid = std::max(1, std::min({(n + 255) / 256, ctx->num_cus * 8, LG_MAX_PARTS}));
-  hipLaunchKernelGGL(k_log_ingest, dim3(ingest_grid), dim3(256), 0, ctx->stream, ctx->g, ctx->st, b);
-  hipLaunchKernelGGL(k_log_prep, dim3(1), dim3(256), 0, ctx->stream, ctx->g, ctx->st, ingest_grid);
-  hipLaunchKernelGGL(k_log_scan, dim3(ctx->num_cus * 4), dim3(256), 0, ctx->stream, ctx->g, ctx->st);
-  hipLaunchKernelGGL(k_log_commit, dim3(1), dim3(1), 0, ctx->stream, ctx->st);
-  return launch_check(ctx);
+  return run_replica_chosen(ctx, n, d_slot, d_value_id, d_mask, RunOpts{});
 }
 
 int32_t fpx_replica_state(fpx_ctx* ctx, int32_t* executed_watermark, int32_t* num_chosen) {
@@ -2940,8 +2943,8 @@ int32_t fpx_replica_chosen(fpx_ctx* ctx, int32_t n, const int32_t* slot, const i
         split_runs(ctx, m, s.data(), nullptr, false, cuts);
         return FPX_OK;
       },
-      [&](int lo, int len) {
-        return fpx_replica_chosen_dev(ctx, len, staged<int32_t>(ctx->d_slot, lo), staged<int32_t>(ctx->d_value, lo), nullptr);
+      [&](int lo, int len, const RunOpts& opts) {
+        return run_replica_chosen(ctx, len, staged<int32_t>(ctx->d_slot, lo), staged<int32_t>(ctx->d_value, lo), nullptr, opts);
       });
   if (rc == FPX_EHIP || rc == FPX_ENOMEM) return rc;  // (a HIP failure: no scalars to report)
   const int st = fpx_replica_state(ctx, executed_watermark, num_chosen);
@@ -3032,7 +3035,7 @@ int32_t fpx_replica_chosen_msgs(fpx_ctx* ctx, int32_t n, const int32_t* kind, co
     rc = host_batch(ctx, n,
                     {{&ctx->d_i32_a, kind, 4}, {&ctx->d_slot, slot, 4}, {&ctx->d_i32_b, slot_end, 4},
                      {&ctx->d_value, value_id, 4}, {&ctx->d_u8, mask, 1}},
-                    {}, nullptr, [&](int, int) {
+                    {}, nullptr, [&](int, int, const RunOpts&) {
                       return fpx_replica_chosen_msgs_dev(ctx, n, (const int32_t*)ctx->d_i32_a.p, (const int32_t*)ctx->d_slot.p,
                                                          (const int32_t*)ctx->d_i32_b.p, (const int32_t*)ctx->d_value.p,
                                                          mask ? (const uint8_t*)ctx->d_u8.p : nullptr);
@@ -3110,7 +3113,7 @@ int32_t fpx_replica_inbox(fpx_ctx* ctx, int32_t n, const int32_t* kind, const in
     if ((rc = grow(ctx, &ctx->ri_out[a], cap))) return rc;
   if ((rc = grow(ctx, &ctx->ri_out[3], 16))) return rc;
   rc = host_batch(ctx, n, {{&ctx->d_i32_a, kind, 4}, {&ctx->d_slot, slot, 4}, {&ctx->d_value, value_id, 4}, {&ctx->d_u8, mask, 1}},
-                  {}, nullptr, [&](int, int) {
+                  {}, nullptr, [&](int, int, const RunOpts&) {
                     return fpx_replica_inbox_dev(ctx, n, (const int32_t*)ctx->d_i32_a.p, (const int32_t*)ctx->d_slot.p,
                                                  (const int32_t*)ctx->d_value.p, mask ? (const uint8_t*)ctx->d_u8.p : nullptr,
                                                  (int32_t*)ctx->ri_out[0].p, (int32_t*)ctx->ri_out[1].p,
@@ -3216,7 +3219,7 @@ int32_t fpx_acceptor_inbox(fpx_ctx* ctx, int32_t n, const int32_t* kind, const i
   rc = host_batch(ctx, n,
                   {{&ctx->d_i32_a, kind, 4}, {&ctx->d_target, group_index, 4}, {&ctx->d_i32_c, acceptor_index, 4},
                    {&ctx->d_slot, slot, 4}, {&ctx->d_round, round, 4}, {&ctx->d_value, value_id, 4}},
-                  {}, nullptr, [&](int, int) {
+                  {}, nullptr, [&](int, int, const RunOpts&) {
                     return fpx_acceptor_inbox_dev(
                         ctx, n, (const int32_t*)ctx->d_i32_a.p, group_index ? (const int32_t*)ctx->d_target.p : nullptr,
                         (const int32_t*)ctx->d_i32_c.p, (const int32_t*)ctx->d_slot.p, (const int32_t*)ctx->d_round.p,
@@ -3298,7 +3301,7 @@ int32_t fpx_mencius_acceptor_inbox(fpx_ctx* ctx, int32_t n, const int32_t* kind,
                   {{&ctx->d_i32_a, kind, 4}, {&ctx->d_target, group_index, 4}, {&ctx->d_i32_c, acceptor_index, 4},
                    {&ctx->d_slot, slot, 4}, {&ctx->d_i32_b, slot_end, 4}, {&ctx->d_round, round, 4},
                    {&ctx->d_value, value_id, 4}},
-                  {}, nullptr, [&](int, int) {
+                  {}, nullptr, [&](int, int, const RunOpts&) {
                     return fpx_mencius_acceptor_inbox_dev(
                         ctx, n, (const int32_t*)ctx->d_i32_a.p, group_index ? (const int32_t*)ctx->d_target.p : nullptr,
                         (const int32_t*)ctx->d_i32_c.p, (const int32_t*)ctx->d_slot.p, (const int32_t*)ctx->d_i32_b.p,
@@ -3440,7 +3443,7 @@ int32_t fpx_leader_phase1b_msgs(fpx_ctx* ctx, int32_t round, int32_t chosen_wate
        {&s[7], info_value_id, 0, rec}},
       {{&s[8], nullptr, 0, outb}, {&s[9], nullptr, 0, outb}, {&s[10], nullptr, 0, outb}, {&s[11], res, 0, sizeof(res)},
        {&s[12], nullptr, 0, heldb}},
-      nullptr, [&](int, int) -> int {
+      nullptr, [&](int, int, const RunOpts&) -> int {
         // -1 in every result word: "not written" (a refused call writes none, an incomplete one two)
         HIPCHK(ctx, hipMemsetAsync(s[11].p, 0xFF, sizeof(res), ctx->stream));
         return fpx_leader_phase1b_msgs_dev(ctx, round, chosen_watermark, leader_group, recover_slot, flags, n,
@@ -3772,11 +3775,9 @@ int32_t fpx_phase2_replica_sharded_dev(fpx_ctx* ctx, int32_t n, const int32_t* d
   if (ctx->comm && (rc = grow(ctx, &ctx->d_mine, (size_t)per * 32))) return rc;
   uint64_t* part = (uint64_t*)ctx->d_part.p;
   // K1: my acceptor columns vote on every slot of the batch; partial bitmaps (bits in my range only) to HBM
-  Batch b;
-  memset(&b, 0, sizeof(b));
-  b.n = n, b.slot = d_slot, b.round = d_round, b.value = d_value_id, b.target = d_target_mask;
+  Batch b = batch_of(n, d_slot, d_round, d_value_id, d_target_mask);
   b.vote_bits = part, b.nack_round = d_nack_round;
-  if ((rc = enqueue_phase2(ctx, b, false))) return rc;
+  if ((rc = enqueue_phase2(ctx, b, false, RunOpts{}))) return rc;
   const uint64_t* mine = part + (size_t)lo * 4;
   if (ctx->comm) {  // also on a communicator of one rank: the same call path, RCCL copies
     // the exchange step: sum (== OR) of the partial bitmaps, scattered so that I receive my slots' rows
@@ -3799,16 +3800,13 @@ int32_t fpx_phase2_replica_sharded_dev(fpx_ctx* ctx, int32_t n, const int32_t* d
   }
   // ProxyLeader.handlePhase2a bookkeeping + handlePhase2b for my slice of the slots; K1's validation pass
   // covered the whole batch (slots distinct), so the slice needs none
-  HostFlags trusted(ctx, true);
-  Batch o;
-  memset(&o, 0, sizeof(o));
-  o.n = per, o.slot = d_slot + lo, o.round = d_round + lo, o.value = d_value_id + lo;
-  if ((rc = enqueue_open(ctx, o))) return rc;
-  Batch t;
-  memset(&t, 0, sizeof(t));
-  t.n = per, t.slot = d_slot + lo, t.round = d_round + lo, t.vote_bits = const_cast<uint64_t*>(mine);
+  const RunOpts covered{RunOpts::CUT_ON_HOST};
+  Batch o = batch_of(per, d_slot + lo, d_round + lo, d_value_id + lo);
+  if ((rc = enqueue_open(ctx, o, covered))) return rc;
+  Batch t = batch_of(per, d_slot + lo, d_round + lo, nullptr);
+  t.vote_bits = const_cast<uint64_t*>(mine);
   t.chosen = d_chosen, t.chosen_round = d_chosen_round, t.chosen_value = d_chosen_value;
-  return enqueue_tally(ctx, t);
+  return enqueue_tally(ctx, t, covered);
 }
 
 int32_t fpx_comm_allgather_chosen_dev(fpx_ctx* ctx, int32_t n_local, const uint8_t* d_chosen,

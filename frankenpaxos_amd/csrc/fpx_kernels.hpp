@@ -183,7 +183,7 @@ struct Batch {
   uint32_t launch_seq;     // K1 / K3 launch counter (never 0): stamps the rows of `part` this launch writes
   int32_t check_round;     // validate: enforce one round per group (ACCEPTOR ballot mode)
   int32_t chunk;           // K1 / K3 at G = 64: messages per wavefront (4 .. CHUNK, or CHUNK_RECORDS)
-  int32_t index_base;      // added to the message index an error reports (host batches launched in pieces)
+  int32_t index_base;      // added to the message index an error reports (the run's RunOpts: host batches launched in pieces)
   int32_t solo;            // K1 / K3: the launch is ONE workgroup, which applies its maxima itself (no k_finalize follows)
   int32_t sc_lds;          // K1 / K3 on leader-group-major rows: byte offset of 4 x 3 KiB of LDS for the column quads (0 = none)
   int32_t th_lds;          // K1 / K3, FPX_BALLOT_ACCEPTOR with several acceptor groups: byte offset of the staged rounds [ngroups * R]

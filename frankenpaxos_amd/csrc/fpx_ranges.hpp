@@ -98,7 +98,8 @@ __global__ void __launch_bounds__(256) k_band_check(const Geom g, const State st
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const int s = slot[i];
-  // (the reported index counts from the caller's first message, as k_validate's does: ADVICE r05)
+  // (the reported index counts from the caller's first message, as k_validate's does -- index_base is the run's
+  // RunOpts::index_base: ADVICE r05)
   if (s >= 0 && lg_mark[s % g.num_leader_groups] != 0) report_abort(st, 6 /*FPX_EORDER*/, i + index_base, s, round ? round[i] : 0);
 }
 

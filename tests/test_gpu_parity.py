@@ -599,6 +599,36 @@ def test_capacity_error_applies_everything_else(fa, oracle):
     assert st == 0 and not chg.any() and (nrg == 2).all()
 
 
+@pytest.mark.parametrize("ballot_mode", [0, 1])
+def test_error_index_is_batch_relative_then_call_relative(fa, ballot_mode):
+    """The message index of an error is counted from the start of the caller's batch: from a later run of a host batch
+    that the host cut into runs it is batch-relative, and a _dev call behind it reports its own, call-relative one.  The
+    oracle has no capacity limit, so the expected triples come from the construction: slot 9's only tally way is
+    Pending in round 0, and every call holds exactly one message for slot 9 in another round."""
+    import torch
+
+    gpu = fa.Context(fa.make_config(num_slots=64, num_replicas=3, f=1, tally_ways=1, ballot_mode=ballot_mode))
+    i32 = lambda a: np.array(a, np.int32)
+    # A: delivered to nobody, the tally of (9, 0) stays Pending
+    assert gpu.phase2_fused(i32([9]), i32([0]), i32([9]), np.zeros((1, 4), np.uint64))[0] == 0
+    # B: the repeated slot 1 fails the whole-batch run; the host cuts at index 2 and replays [0, 2) and [2, 6)
+    slot = i32([1, 2, 1, 3, 9, 4])
+    st, ch = gpu.phase2_fused(slot, np.full(6, 1, np.int32), slot)[:2]
+    print("host batch:", st, gpu.error_detail(), ch)
+    assert st == fa.FPX_ECAPACITY and gpu.error_detail() == (4, 9, 1)
+    # (`chosen` says NEWLY chosen: the second message for slot 1 meets the tally the first one finished, like a duplicate
+    # Phase2a at the reference's proxy leader, and the message over capacity chooses nothing)
+    assert ch.astype(bool).tolist() == [True, True, False, True, False, True]
+    # C: a device batch on the same context counts from its own first message
+    dev = torch.device("cuda:0")
+    t = lambda a: torch.tensor(a, dtype=torch.int32, device=dev)
+    gpu.phase2_fused_dev(t([6, 7, 9]), t([2, 2, 2]), t([6, 7, 9]))
+    st = gpu.sync()
+    print("device batch:", st, gpu.error_detail())
+    assert st == fa.FPX_ECAPACITY and gpu.error_detail() == (2, 9, 2)
+    gpu.close()
+
+
 @pytest.mark.parametrize("fused", [True, False])
 def test_eight_thousand_acceptors_in_one_context(fa, oracle, fused):
     """num_groups * num_leader_groups * R up to 8192 puts 64+ KiB of maxima tables in LDS, above
