@@ -37,6 +37,7 @@
 #include <vector>
 
 #include "../../include/fpx.h"
+#include "../../include/fpx_wire.h"
 #include "fpx_host.hpp"
 #include "fpx_scan.hpp"
 
@@ -1382,6 +1383,7 @@ __global__ void __launch_bounds__(256) k_hp_commit(const EpxState st, const HpBa
 #include "fpx_epx_leader.hpp"
 #include "fpx_epx_recovery.hpp"
 #include "fpx_epx_inbox.hpp"
+#include "fpx_wire_epx_dev.hpp"
 
 }  // namespace
 
@@ -1412,6 +1414,7 @@ struct fpx_epx {
                                           // allocated; prep with FPX_EPX_F_RECOVERY (fpx_epx_recovery.hpp)
   DevBuf lr_misc;                         // fpx_epx_leader_replies: the decided flags and the compaction's block counts
   DevBuf ri_misc;                         // fpx_epx_replica_inbox: lay_epx_inbox
+  DevBuf wire_misc;                       // fpx_wire_epx_leader_tick_dev: the decoded arrays of the tick
   bool lds_allowed = false, sort_lds_allowed = false;
   int num_cus = 256;
 };
@@ -2108,7 +2111,7 @@ int32_t fpx_epx_destroy(fpx_epx* e) {
   for (void* p : ps)
     if (p) (void)hipFree(p);
   DevBuf* bs[] = {&e->kv, &e->kv2, &e->seg, &e->conf, &e->tmp, &e->tick, &e->fusedb, &e->metab, &e->stage, &e->mk_misc, &e->mk_rec,
-                  &e->mk_pair, &e->mk_pconf, &e->lr_misc, &e->ri_misc};
+                  &e->mk_pair, &e->mk_pconf, &e->lr_misc, &e->ri_misc, &e->wire_misc};
   for (DevBuf* b : bs)
     if (b->p) (void)hipFree(b->p);
   free(e->held);
@@ -3012,6 +3015,117 @@ int32_t fpx_epx_leader_replies(fpx_epx* e, int32_t m, const int32_t* kind, const
                        held(b.out_triple, out_triple, m), held_first(b.decided, decided_index, m, b.num_decided),
                        held(b.out_deps, out_deps, mn), held(b.num_decided, num_decided, 1)},
                    [&]() -> int { return leader_replies_launch(e, b); });
+}
+
+// ---- a leader's reply burst from wire bytes: csrc/fpx_wire_epx_dev.hpp (include/fpx_wire.h) ---------------------------------
+static void launch_wire_decode(fpx_epx* e, const uint8_t* d_buf, int64_t buf_len, const int64_t* d_offsets, int32_t n,
+                               const fpxw::EpxFoldOut& o) {
+  hipLaunchKernelGGL(k_epx_wire_decode, dim3((n + 255) / 256), dim3(256), 0, e->stream, e->st, d_buf, buf_len, d_offsets, n,
+                     e->st.n, o);
+}
+
+int32_t fpx_wire_epaxos_decode_replica_inbound_dev(
+    fpx_epx* e, const uint8_t* d_buf, int64_t buf_len, const int64_t* d_offsets, int32_t n, int32_t* d_kind,
+    int32_t* d_instance_leader, int32_t* d_instance_number, int32_t* d_ballot_ordering, int32_t* d_ballot_replica,
+    int32_t* d_replica_index, int32_t* d_sequence_number, int32_t* d_vote_ballot_ordering, int32_t* d_vote_ballot_replica,
+    int32_t* d_status, int32_t* d_is_noop, int64_t* d_cmd_off, int32_t* d_cmd_len, int32_t* d_deps_num_replicas,
+    int32_t* d_deps_watermark, int32_t* d_deps_values_end, int32_t* d_deps_shape, int32_t* d_bad_index) {
+  if (!e || n < 0 || n >= (1 << 30) || buf_len < 0 || !d_bad_index) return FPX_EINVAL;
+  if (n > 0 && (!d_buf || !d_offsets || !d_kind)) return FPX_EINVAL;
+  DeviceScope _dg(e->cfg.device);
+  if (n > 0)
+    launch_wire_decode(e, d_buf, buf_len, d_offsets, n,
+                       fpxw::EpxFoldOut{d_kind, d_instance_leader, d_instance_number, d_ballot_ordering, d_ballot_replica,
+                                        d_replica_index, d_sequence_number, d_vote_ballot_ordering, d_vote_ballot_replica,
+                                        d_status, d_is_noop, d_cmd_off, d_cmd_len, d_deps_num_replicas, d_deps_watermark,
+                                        d_deps_values_end, d_deps_shape});
+  hipLaunchKernelGGL(k_epx_wire_tail, dim3(1), dim3(1), 0, e->stream, e->st, d_bad_index);
+  return launch_check(e);
+}
+
+// the decoded arrays of a tick: device scratch of the call, whichever form it takes
+struct WireTick {
+  int32_t *kind, *nr, *shape, *lr_kind, *leader, *number, *b_ord, *b_rep, *ridx, *seq, *deps, *dend;
+};
+static WireTick lay_wire_tick(Carver& c, size_t m, size_t n) {
+  WireTick w;
+  for (int32_t** a : {&w.kind, &w.nr, &w.shape, &w.lr_kind, &w.leader, &w.number, &w.b_ord, &w.b_rep, &w.ridx, &w.seq, &w.dend})
+    *a = c.take<int32_t>(m);
+  w.deps = c.take<int32_t>(m * n);
+  return w;
+}
+
+// decode -> check -> fpx_epx_leader_replies on the decoded arrays; b: `to` and the outputs
+static int32_t wire_tick_launch(fpx_epx* e, const uint8_t* d_in, int64_t in_len, const int64_t* d_in_offsets, const WireTick& w,
+                                int32_t* d_bad_index, LrBatch b) {
+  fpxw::EpxFoldOut o;
+  memset(&o, 0, sizeof(o));
+  o.kind = w.kind, o.il = w.leader, o.in = w.number, o.bo = w.b_ord, o.br = w.b_rep, o.ri = w.ridx, o.seq = w.seq;
+  o.nr = w.nr, o.wm = w.deps, o.dend = w.dend, o.shape = w.shape;
+  launch_wire_decode(e, d_in, in_len, d_in_offsets, b.m, o);
+  hipLaunchKernelGGL(k_epx_wire_tick_check, dim3((b.m + 255) / 256), dim3(256), 0, e->stream, e->st, b.m, w.kind, w.nr, w.shape,
+                     w.lr_kind, w.ridx);
+  hipLaunchKernelGGL(k_epx_wire_tail, dim3(1), dim3(1), 0, e->stream, e->st, d_bad_index);
+  b.kind = w.lr_kind, b.leader = w.leader, b.number = w.number, b.b_ord = w.b_ord, b.b_rep = w.b_rep, b.ridx = w.ridx;
+  b.seq = w.seq, b.deps = w.deps, b.dend = w.dend;
+  return leader_replies_launch(e, b);
+}
+
+int32_t fpx_wire_epx_leader_tick_dev(fpx_epx* e, const uint8_t* d_in, int64_t in_len, const int64_t* d_in_offsets, int32_t m,
+                                     const int32_t* d_to, int32_t* d_outcome, int32_t* d_out_seq, int32_t* d_out_deps,
+                                     int32_t* d_out_values_end, int32_t* d_out_triple, int32_t* d_decided_index,
+                                     int32_t* d_num_decided, int32_t* d_bad_index) {
+  if (!e || m < 0 || m >= (1 << 30) || in_len < 0 || !d_bad_index || !leader_state_on(e)) return FPX_EINVAL;
+  DeviceScope _dg(e->cfg.device);
+  if (m == 0) {
+    if (d_num_decided) HIPCHK(e, hipMemsetAsync(d_num_decided, 0, 4, e->stream));
+    HIPCHK(e, hipMemsetAsync(d_bad_index, 0xFF, 4, e->stream));
+    return FPX_OK;
+  }
+  if (!d_in || !d_in_offsets || !d_to) return FPX_EINVAL;
+  WireTick w;
+  int rc;
+  if ((rc = carve(e, &e->wire_misc, &w, [&](Carver& c) { return lay_wire_tick(c, (size_t)m, (size_t)e->st.n); }))) return rc;
+  LrBatch b;
+  memset(&b, 0, sizeof(b));
+  b.m = m, b.to = d_to, b.outcome = d_outcome, b.out_seq = d_out_seq, b.out_deps = d_out_deps, b.out_end = d_out_values_end;
+  b.out_triple = d_out_triple, b.decided = d_decided_index, b.num_decided = d_num_decided;
+  rc = wire_tick_launch(e, d_in, in_len, d_in_offsets, w, d_bad_index, b);
+  return rc ? rc : launch_check(e);
+}
+
+int32_t fpx_wire_epx_leader_tick(fpx_epx* e, const uint8_t* in_bytes, int64_t in_len, const int64_t* in_offsets, int32_t m,
+                                 const int32_t* to, int32_t* outcome, int32_t* out_seq, int32_t* out_deps,
+                                 int32_t* out_values_end, int32_t* out_triple, int32_t* decided_index, int32_t* num_decided,
+                                 int32_t* bad_index) {
+  if (!e || m < 0 || m >= (1 << 30) || in_len < 0 || !leader_state_on(e)) return FPX_EINVAL;
+  DeviceScope _dg(e->cfg.device);
+  if (bad_index) *bad_index = -1;
+  if (m == 0) {
+    if (num_decided) *num_decided = 0;
+    return FPX_OK;
+  }
+  if ((in_len > 0 && !in_bytes) || !in_offsets || !to) return FPX_EINVAL;
+  const size_t mn = (size_t)m * e->st.n;
+  const uint8_t* d_in = nullptr;
+  const int64_t* d_off = nullptr;
+  int32_t* d_bad = nullptr;
+  int32_t bad = -1;
+  WireTick w;
+  LrBatch b;
+  memset(&b, 0, sizeof(b));
+  b.m = m;
+  const int32_t rc = host_call(
+      e, {in(d_in, in_bytes, (size_t)in_len), in(d_off, in_offsets, (size_t)m + 1), in(b.to, to, m), scratch(w.kind, m),
+          scratch(w.nr, m), scratch(w.shape, m), scratch(w.lr_kind, m), scratch(w.leader, m), scratch(w.number, m),
+          scratch(w.b_ord, m), scratch(w.b_rep, m), scratch(w.ridx, m), scratch(w.seq, m), scratch(w.dend, m),
+          scratch(w.deps, mn), held(b.outcome, outcome, m), held(b.out_seq, out_seq, m), held(b.out_end, out_values_end, m),
+          held(b.out_triple, out_triple, m), held_first(b.decided, decided_index, m, b.num_decided),
+          held(b.out_deps, out_deps, mn), held(b.num_decided, num_decided, 1), out(d_bad, &bad, 1)},
+      [&]() -> int { return wire_tick_launch(e, d_in, in_len, d_off, w, d_bad, b); });
+  // (the bad index comes down whatever the status; it means something on FPX_EINVAL)
+  if (bad_index && rc == FPX_EINVAL) *bad_index = bad;
+  return rc;
 }
 
 // ---- the replica half, a burst at a time: csrc/fpx_epx_inbox.hpp -------------------------------------------------------------

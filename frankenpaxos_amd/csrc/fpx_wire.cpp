@@ -9,6 +9,7 @@
 
 #include "../../include/fpx.h"
 #include "fpx_wire_emit.hpp"
+#include "fpx_wire_epx_parse.hpp"
 #include "fpx_wire_parse.hpp"
 
 namespace {
@@ -597,141 +598,26 @@ void put_deps(Writer& w, uint32_t field, const fpx_wire_epx_msg& m, int64_t body
   }
 }
 
-bool parse_pair(Reader r, int32_t* a, int32_t* b) {
-  Fields f;
-  if (!parse_flat(r, 0, &f) || (f.seen & 0x6) != 0x6) return false;
-  *a = f.i[1], *b = f.i[2];
-  return true;
-}
-
-struct EpxOne {  // one decoded message
-  int32_t kind = FPX_WIRE_OTHER, il = -1, in = -1, bo = -1, br = -1, ri = -1, seq = -1, vbo = -1, vbr = -1, status = -1;
-  Value cmd;
-  bool has_cmd = false, has_deps = false, has_seq = false;
-  int32_t num_replicas = -1;
+// the host decoder's sink of fpx_wire_epx_parse.hpp: every watermark and every explicit id, as they come
+struct EpxVectors {
   std::vector<int32_t> wm;
   std::vector<std::pair<int32_t, int32_t>> values;
+  void reset() { wm.clear(), values.clear(); }
+  void deps_begin(const Reader&) { reset(); }
+  void value(int leader, int32_t id) { values.push_back({leader, id}); }
+  bool set(int, int32_t w) {
+    wm.push_back(w);
+    return true;
+  }
 };
-
-// IntPrefixSetProto { watermark = 1; repeated int32 value = 2 (unpacked by ScalaPB; packed accepted too) }
-bool parse_int_prefix_set(Reader r, int leader, EpxOne* o) {
-  bool seen_wm = false;
-  int32_t wm = 0;
-  while (r.more()) {
-    const uint64_t tag = r.varint();
-    const uint32_t field = (uint32_t)(tag >> 3), wt = (uint32_t)(tag & 7);
-    if (field == 1 && wt == 0) {
-      wm = as_i32(r.varint());
-      seen_wm = true;
-    } else if (field == 2 && wt == 0) {
-      o->values.push_back({leader, as_i32(r.varint())});
-    } else if (field == 2 && wt == 2) {
-      Reader p = r.sub();
-      while (p.more()) o->values.push_back({leader, as_i32(p.varint())});
-      if (!p.ok) return false;
-    } else {
-      r.skip(wt);
-    }
-  }
-  if (!r.ok || !seen_wm) return false;
-  o->wm.push_back(wm);
-  return true;
-}
-
-bool parse_deps(Reader r, EpxOne* o) {
-  bool seen_n = false;
-  o->wm.clear();
-  o->values.clear();
-  int leader = 0;
-  while (r.more()) {
-    const uint64_t tag = r.varint();
-    const uint32_t field = (uint32_t)(tag >> 3), wt = (uint32_t)(tag & 7);
-    if (field == 1 && wt == 0) {
-      o->num_replicas = as_i32(r.varint());
-      seen_n = true;
-    } else if (field == 2 && wt == 2) {
-      Reader sub = r.sub();
-      if (!r.ok || !parse_int_prefix_set(sub, leader++, o)) return false;
-    } else {
-      r.skip(wt);
-    }
-  }
-  // InstancePrefixSet.fromProto (epaxos/InstancePrefixSet.scala:48-53) takes numReplicas and the sets as they come;
-  // every producer writes exactly numReplicas of them -- anything else is refused here
-  if (!r.ok || !seen_n || o->num_replicas < 0 || (int)o->wm.size() != o->num_replicas) return false;
-  o->has_deps = true;
-  return true;
-}
-
-// the body of one ReplicaInbound member.  layout: which field numbers carry what, per kind
-struct EpxLayout {
-  int instance, ballot, command, seq, deps, replica, vote_ballot, status;
-  unsigned required;  // bits of the field numbers that must be present
-};
-const EpxLayout* epx_layout(int32_t kind) {
-  static const EpxLayout pre_accept{1, 2, 3, 4, 5, 0, 0, 0, 0x3e}, pre_accept_ok{1, 2, 0, 4, 5, 3, 0, 0, 0x3e},
-      accept_ok{2, 3, 0, 0, 0, 7, 0, 0, 0x8c}, commit{1, 0, 2, 3, 4, 0, 0, 0, 0x1e}, prepare{1, 2, 0, 0, 0, 0, 0, 0, 0x6},
-      prepare_ok{2, 1, 6, 7, 8, 3, 4, 5, 0x3e}, nack{1, 2, 0, 0, 0, 0, 0, 0, 0x6};
-  switch (kind) {
-    case FPX_WIRE_EPX_PRE_ACCEPT: case FPX_WIRE_EPX_ACCEPT: return &pre_accept;
-    case FPX_WIRE_EPX_PRE_ACCEPT_OK: return &pre_accept_ok;
-    case FPX_WIRE_EPX_ACCEPT_OK: return &accept_ok;
-    case FPX_WIRE_EPX_COMMIT: return &commit;
-    case FPX_WIRE_EPX_PREPARE: return &prepare;
-    case FPX_WIRE_EPX_PREPARE_OK: return &prepare_ok;
-    case FPX_WIRE_EPX_NACK: return &nack;
-  }
-  return nullptr;
-}
-
-bool parse_epx_member(Reader r, int32_t kind, EpxOne* o) {
-  const EpxLayout& L = *epx_layout(kind);
-  unsigned seen = 0;
-  o->kind = kind;
-  while (r.more()) {
-    const uint64_t tag = r.varint();
-    const int field = (int)(tag >> 3);
-    const uint32_t wt = (uint32_t)(tag & 7);
-    bool known = true;
-    if (field == 0) return false;  // no such field (a layout entry of 0 means "this kind has none": never a match)
-    if (field == L.instance && wt == 2) {
-      if (!parse_pair(r.sub(), &o->il, &o->in)) return false;
-    } else if (field == L.ballot && wt == 2) {
-      if (!parse_pair(r.sub(), &o->bo, &o->br)) return false;
-    } else if (field == L.vote_ballot && wt == 2) {
-      if (!parse_pair(r.sub(), &o->vbo, &o->vbr)) return false;
-    } else if (field == L.command && wt == 2) {
-      Reader sub = r.sub();
-      if (!r.ok || !parse_value(sub, &o->cmd)) return false;
-      o->has_cmd = true;
-    } else if (field == L.deps && wt == 2) {
-      Reader sub = r.sub();
-      if (!r.ok || !parse_deps(sub, o)) return false;
-    } else if (field == L.seq && wt == 0) {
-      o->seq = as_i32(r.varint());
-      o->has_seq = true;
-    } else if (field == L.replica && wt == 0) {
-      o->ri = as_i32(r.varint());
-    } else if (field == L.status && wt == 0) {
-      o->status = as_i32(r.varint());
-    } else {
-      known = false;
-      r.skip(wt);
-    }
-    if (known && field < 32) seen |= 1u << field;
-    if (!r.ok) return false;
-  }
-  return r.ok && (seen & L.required) == L.required;
-}
 
 }  // namespace
 
 int64_t fpx_wire_epaxos_encode_replica_inbound(uint8_t* out, int64_t cap, const fpx_wire_epx_msg* mp) {
   if (!mp) return CANNOT_ENCODE;
   const fpx_wire_epx_msg& m = *mp;
-  const EpxLayout* Lp = epx_layout(m.kind);
-  if (!Lp) return CANNOT_ENCODE;
-  const EpxLayout& L = *Lp;
+  EpxLayout L;
+  if (!epx_layout(m.kind, &L)) return CANNOT_ENCODE;
   const bool is_prepare_ok = m.kind == FPX_WIRE_EPX_PREPARE_OK;
   const bool want_cmd = L.command && (!is_prepare_ok || m.is_noop >= 0);
   const bool want_seq = L.seq && (!is_prepare_ok || m.has_sequence_number);
@@ -802,21 +688,10 @@ int32_t fpx_wire_epaxos_decode_replica_inbound(const uint8_t* buf, int64_t buf_l
   if (max_replicas < 0 || values_cap < 0 || (deps_watermark && max_replicas < 1)) return FPX_EINVAL;
   int64_t nvalues = 0;
   if (values_off && n >= 0) values_off[0] = 0;
-  EpxOne o;
+  EpxScalars o;
+  EpxVectors v;
   const int32_t st = decode_loop(buf, buf_len, offsets, n, bad_index, [&](int32_t i, Reader r) {
-    o = EpxOne();
-    while (r.more()) {  // the last member of the oneof that is present wins
-      const uint64_t tag = r.varint();
-      const uint32_t field = (uint32_t)(tag >> 3), wt = (uint32_t)(tag & 7);
-      if (field >= 2 && field <= 9 && wt == 2) {
-        Reader sub = r.sub();
-        o = EpxOne();
-        if (!r.ok || !parse_epx_member(sub, (int32_t)field + 14, &o)) return false;
-      } else {
-        r.skip(wt);  // ClientRequest = 1 goes to the JVM actor
-      }
-    }
-    if (!r.ok) return false;
+    if (!parse_epx_replica_inbound(r, &o, v)) return false;
     kind[i] = o.kind;
     if (instance_leader) instance_leader[i] = o.il;
     if (instance_number) instance_number[i] = o.in;
@@ -836,14 +711,14 @@ int32_t fpx_wire_epaxos_decode_replica_inbound(const uint8_t* buf, int64_t buf_l
       for (int l = 0; l < max_replicas; ++l) row[l] = 0;
       if (o.has_deps) {
         if (o.num_replicas > max_replicas) return false;
-        for (int l = 0; l < o.num_replicas; ++l) row[l] = o.wm[(size_t)l];
+        for (int l = 0; l < o.num_replicas; ++l) row[l] = v.wm[(size_t)l];
       }
     }
     if (o.has_deps)
-      for (const auto& v : o.values) {
+      for (const auto& x : v.values) {
         if (nvalues < values_cap) {
-          if (values_leader) values_leader[nvalues] = v.first;
-          if (values_id) values_id[nvalues] = v.second;
+          if (values_leader) values_leader[nvalues] = x.first;
+          if (values_id) values_id[nvalues] = x.second;
         }
         ++nvalues;
       }
@@ -853,6 +728,23 @@ int32_t fpx_wire_epaxos_decode_replica_inbound(const uint8_t* buf, int64_t buf_l
   if (st != FPX_OK) return st;
   if (nvalues > values_cap && (values_leader || values_id)) return FPX_ECAPACITY;
   return FPX_OK;
+}
+
+int32_t fpx_wire_epaxos_decode_replica_inbound_folded(
+    const uint8_t* buf, int64_t buf_len, const int64_t* offsets, int32_t n, int32_t num_replicas, int32_t* kind,
+    int32_t* instance_leader, int32_t* instance_number, int32_t* ballot_ordering, int32_t* ballot_replica,
+    int32_t* replica_index, int32_t* sequence_number, int32_t* vote_ballot_ordering, int32_t* vote_ballot_replica,
+    int32_t* status, int32_t* is_noop, int64_t* cmd_off, int32_t* cmd_len, int32_t* deps_num_replicas,
+    int32_t* deps_watermark, int32_t* deps_values_end, int32_t* deps_shape, int32_t* bad_index) {
+  if (n > 0 && !kind) return FPX_EINVAL;
+  if (num_replicas < 0 || (deps_watermark && num_replicas < 1)) return FPX_EINVAL;
+  if (bad_index) *bad_index = -1;
+  const EpxFoldOut o{kind, instance_leader, instance_number, ballot_ordering, ballot_replica, replica_index,
+                     sequence_number, vote_ballot_ordering, vote_ballot_replica, status, is_noop, cmd_off, cmd_len,
+                     deps_num_replicas, deps_watermark, deps_values_end, deps_shape};
+  // the message's whole decode is the header's, the one the device kernel runs
+  return decode_loop(buf, buf_len, offsets, n, bad_index,
+                     [&](int32_t i, Reader r) { return epx_decode_folded(buf, r, i, num_replicas, o); });
 }
 
 }  // extern "C"

@@ -338,6 +338,70 @@ class EPaxos:
         if st:
             raise FpxError(st, "fpx_epx_leader_replies_dev")
 
+    # ---- a leader's reply burst from wire bytes (include/fpx_wire.h) ----
+    def wire_decode_dev_tensors(self, buf, buf_len, offsets, n, only_kind=False):
+        """fpx_wire_epaxos_decode_replica_inbound_dev on device tensors (buf uint8, offsets int64), enqueued on the
+        context's stream: a dict of device tensors (wire.EPX_FOLDED_NAMES, and bad_index[1]); the status comes with sync()"""
+        import torch
+
+        from . import wire
+        L = wire._L()
+        out = {}
+        for k in wire.EPX_FOLDED_NAMES:
+            if only_kind and k != "kind":
+                continue
+            shape = (n, self.n) if k == "deps_watermark" else (n,)
+            out[k] = torch.zeros(shape, dtype=torch.int64 if k == "cmd_off" else torch.int32, device=buf.device)
+        out["bad_index"] = torch.full((1,), -9, dtype=torch.int32, device=buf.device)
+        st = L.fpx_wire_epaxos_decode_replica_inbound_dev(
+            self._h, buf.data_ptr(), buf_len, offsets.data_ptr(), n,
+            *[out[k].data_ptr() if k in out else None for k in wire.EPX_FOLDED_NAMES], out["bad_index"].data_ptr())
+        if st:
+            raise FpxError(st, "fpx_wire_epaxos_decode_replica_inbound_dev")
+        return out
+
+    def wire_decode_dev(self, messages, offsets=None, only_kind=False):
+        """the device decoder on a tick of serialised ReplicaInbound messages: the bytes and offsets are uploaded, the
+        arrays come back as numpy arrays, with status_code (what sync() gave) and bad_index"""
+        import torch
+
+        from . import wire
+        buf, off = wire.pack(messages)
+        n = len(messages)
+        if offsets is not None:
+            off = np.ascontiguousarray(offsets, np.int64)
+            n = len(off) - 1
+        dev = torch.device("cuda", torch.cuda.current_device())
+        d_buf, d_off = torch.from_numpy(buf).to(dev), torch.from_numpy(off).to(dev)
+        torch.cuda.synchronize()
+        t = self.wire_decode_dev_tensors(d_buf, sum(len(m) for m in messages), d_off, n, only_kind)
+        st = self.sync()
+        out = {k: v.cpu().numpy() for k, v in t.items()}
+        out["status_code"], out["bad_index"] = st, int(out["bad_index"][0])
+        return out
+
+    def wire_leader_tick(self, messages, to, offsets=None):
+        """fpx_wire_epx_leader_tick: a burst of serialised PreAcceptOk / AcceptOk / Nack messages, to[i] the replica that
+        received message i -> what leader_replies returns for the decoded burst, plus bad_index:
+        (status, outcome[m], out_seq[m], out_deps[m, n], out_values_end[m], out_triple[m], decided_index[num_decided],
+        bad_index); on FPX_EINVAL the outputs keep their fill of -9"""
+        from . import wire
+        L = wire._L()
+        buf, off = wire.pack(messages)
+        m = len(messages)
+        if offsets is not None:
+            off = np.ascontiguousarray(offsets, np.int64)
+            m = len(off) - 1
+        to = np.ascontiguousarray(to, dtype=np.int32)
+        outcome, oseq, oend, otr, dec = (np.full(m, -9, np.int32) for _ in range(5))
+        odeps = np.full((m, self.n), -9, np.int32)
+        nd = np.full(1, -9, np.int32)
+        bad = C.c_int32(-9)
+        p = lambda a: a.ctypes.data
+        st = L.fpx_wire_epx_leader_tick(self._h, p(buf), sum(len(x) for x in messages), p(off), m, p(to), p(outcome), p(oseq),
+                                        p(odeps), p(oend), p(otr), p(dec), p(nd), C.byref(bad))
+        return st, outcome, oseq, odeps, oend, otr, dec[:max(int(nd[0]), 0)], bad.value
+
     # ---- originating recovery (recovery=True) ----
     def recover(self, leader, number, at):
         """transitionToPreparePhase of instance (leader, number) at replica `at`, its own Prepare delivered at once:

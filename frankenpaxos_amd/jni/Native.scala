@@ -214,6 +214,16 @@ object Native {
                                replicaIndex: Array[Int], sequenceNumber: Array[Int], deps: Array[Int],
                                depsValuesEnd: Array[Int], outcome: Array[Int], triple: Array[Int], outDeps: Array[Int],
                                decided: Array[Int]): Int
+  // the same burst as serialised ReplicaInbound messages, bytes -> decisions without the host parsing a byte
+  // (include/fpx_wire.h, fpx_wire_epx_leader_tick): in (inLen bytes), inOffsets (m + 1 longs) and to (m ints: the replica that
+  // received message i) are direct buffers in native byte order, as wirePhase2Tick's; the outputs are epxLeaderReplies'.
+  // PreAcceptOk, AcceptOk and Nack only -- a fired defaultToSlowPath timer has no bytes: cut the tick there and pass the
+  // event through epxLeaderReplies.  1 (FPX_EINVAL) with badIndex(0) = the first bad offset, malformed message, message of
+  // another kind or PreAcceptOk whose dependencies are not n sets in the burst calls' form (parse that one on the JVM);
+  // nothing was applied.  badIndex(0) = -1 with status 1: epxLeaderReplies' own refusal
+  @native def epxWireLeaderTick(handle: Long, m: Int, numReplicas: Int, in: java.nio.ByteBuffer, inLen: Long,
+                                inOffsets: java.nio.ByteBuffer, to: java.nio.ByteBuffer, outcome: Array[Int],
+                                triple: Array[Int], outDeps: Array[Int], decided: Array[Int], badIndex: Array[Int]): Int
   // one burst of PreAccept (kind 0) / Accept (1) / Commit (2) / Prepare (3) messages from peer replicas, message i to replica
   // to(i), in delivery order, instances repeated freely (handlePreAccept :1159-1289, handleAccept :1421-1511, handleCommit
   // :1567-1575, handlePrepare :1632-1757).  deps (m x n): a row starting with -1 on an Accept / a Commit = the triple is known

@@ -1481,6 +1481,40 @@ JNIEXPORT jint JNICALL Java_frankenpaxos_gpu_Native_wirePhase2Tick(JNIEnv* env, 
   return st;
 }
 
+/* One tick of hosted EPaxos leaders from wire bytes (fpx_wire_epx_leader_tick): in (inLen bytes), inOffsets (m + 1 longs) and
+ * to (m ints) are direct ByteBuffers in native byte order, as wirePhase2Tick's; the outputs are epxLeaderReplies' (each may be
+ * null): outcome m; triple = outSeq | outValuesEnd | outTriple (3 x m); outDeps m x n; decided m + 1 = the number of decided
+ * messages, then their indices.  badIndex[1] (may be null): -1, or on FPX_EINVAL the message the tick was refused for */
+JNIEXPORT jint JNICALL Java_frankenpaxos_gpu_Native_epxWireLeaderTick(JNIEnv* env, jclass cls, jlong h, jint m, jint numReplicas,
+                                                                      jobject in, jlong inLen, jobject inOffsets, jobject to,
+                                                                      jintArray outcome, jintArray triple, jintArray outDeps,
+                                                                      jintArray decided, jintArray badIndex) {
+  if (m < 0 || inLen < 0 || numReplicas < 3 || !epx_n_is(h, numReplicas)) return FPX_EINVAL;
+  const jlong mn = (jlong)m * numReplicas;
+  if (!opt(env, decided, (jlong)m + 1) || !opt(env, badIndex, 1) || !opt(env, outcome, m) || !opt(env, triple, 3 * (jlong)m) ||
+      !opt(env, outDeps, mn))
+    return FPX_EINVAL;
+  int bad = 0;
+  const uint8_t* i = direct(env, in, inLen, &bad);
+  const int64_t* io = direct(env, inOffsets, 8 * ((jlong)m + 1), &bad);
+  const int32_t* t = direct(env, to, 4 * (jlong)m, &bad);
+  if (bad || (m > 0 && (!io || !t || (inLen > 0 && !i)))) return FPX_EINVAL;
+  jint *oc = out_buf(outcome, m, 4), *tp = out_buf(triple, 3 * (jlong)m, 4), *od = out_buf(outDeps, mn, 4),
+       *dc = out_buf(decided, (jlong)m + 1, 4);
+  jint bad_index = -1;
+  int32_t st = (m > 0 && ((outcome && !oc) || (triple && !tp) || (outDeps && !od))) || (decided && !dc)
+                   ? FPX_ENOMEM
+                   : fpx_wire_epx_leader_tick((fpx_epx*)(intptr_t)h, i, inLen, io, m, t, oc, tp, od, tp ? tp + m : NULL,
+                                              tp ? tp + 2 * (size_t)m : NULL, dc ? dc + 1 : NULL, dc, &bad_index);
+  if (st == FPX_OK || st == FPX_EFATAL_PROTOCOL) {
+    put_ints(env, outcome, m, oc); put_ints(env, triple, 3 * (jlong)m, tp); put_ints(env, outDeps, mn, od);
+    if (dc) put_ints(env, decided, (jlong)dc[0] + 1, dc);
+  }
+  put_ints(env, badIndex, 1, &bad_index);
+  free(oc); free(tp); free(od); free(dc);
+  return st;
+}
+
 /* K8 Replica.handlePrepareOk (epaxos/Replica.scala:1759-1884): prepareOk = epxPrepare's output (status | voteBallot |
  * triple, 3 x m x numReplicas), respMask = its okBits; decision = action | source | triple (3 x m ints) */
 JNIEXPORT jint JNICALL Java_frankenpaxos_gpu_Native_epxHandlePrepareOks(JNIEnv* env, jclass cls, jlong h, jint m,

@@ -74,6 +74,14 @@ def _L():
         L.fpx_wire_epaxos_encode_replica_inbound.restype = C.c_int64
         L.fpx_wire_epaxos_decode_replica_inbound.argtypes = [VP, C.c_int64, VP, C.c_int32, C.c_int32] + [VP] * 16 + \
             [C.c_int64, VP, VP, I32P]
+        # the folded EPaxos decoders and the leader tick (epaxos_decode_replica_inbound_folded, EPaxos.wire_*)
+        L.fpx_wire_epaxos_decode_replica_inbound_folded.argtypes = [VP, C.c_int64, VP, C.c_int32, C.c_int32] + [VP] * 17 + [I32P]
+        L.fpx_wire_epaxos_decode_replica_inbound_dev.argtypes = [VP, VP, C.c_int64, VP, C.c_int32] + [VP] * 18
+        L.fpx_wire_epx_leader_tick_dev.argtypes = [VP, VP, C.c_int64, VP, C.c_int32] + [VP] * 9
+        L.fpx_wire_epx_leader_tick.argtypes = [VP, VP, C.c_int64, VP, C.c_int32] + [VP] * 8 + [I32P]
+        for name in ("fpx_wire_epaxos_decode_replica_inbound_folded", "fpx_wire_epaxos_decode_replica_inbound_dev",
+                     "fpx_wire_epx_leader_tick_dev", "fpx_wire_epx_leader_tick"):
+            getattr(L, name).restype = C.c_int32
         L.fpx_wire_phase2b_rows.argtypes = [C.c_int32, VP, VP, VP, VP, VP, C.c_int32, I32P, VP, VP, VP]
         L.fpx_wire_encode_proxy_leader_phase2a.argtypes = [VP, C.c_int64, C.c_int32, C.c_int32, VP, C.c_int32, C.c_int32]
         L.fpx_wire_encode_acceptor_phase2a.argtypes = [VP, C.c_int64, C.c_int32, C.c_int32, VP, C.c_int32, C.c_int32]
@@ -359,5 +367,34 @@ def epaxos_decode_replica_inbound(messages, max_replicas=7, values_cap=None, off
             continue
         break
     out["values_leader"], out["values_id"] = vl[:min(cap, int(out["values_off"][n]))], vi[:min(cap, int(out["values_off"][n]))]
+    out["status_code"], out["bad_index"], out["buf"] = st, bad.value, buf
+    return out
+
+
+EPX_FOLD_MAX = 64     # FPX_WIRE_EPX_FOLD_MAX
+# the arrays of the folded decoders, in argument order; deps_watermark is (n, num_replicas), cmd_off int64
+EPX_FOLDED_NAMES = ("kind", "instance_leader", "instance_number", "ballot_ordering", "ballot_replica", "replica_index",
+                    "sequence_number", "vote_ballot_ordering", "vote_ballot_replica", "status", "is_noop", "cmd_off", "cmd_len",
+                    "deps_num_replicas", "deps_watermark", "deps_values_end", "deps_shape")
+
+
+def epaxos_decode_replica_inbound_folded(messages, num_replicas=7, offsets=None, only_kind=False):
+    """the folded host decoder (fpx_wire_epaxos_decode_replica_inbound_folded): the scalars of
+    epaxos_decode_replica_inbound, deps_watermark, and deps_values_end / deps_shape in place of the explicit ids.
+    only_kind: every optional array is left out (NULL)"""
+    buf, off = pack(messages)
+    n = len(messages)
+    if offsets is not None:
+        off = np.ascontiguousarray(offsets, np.int64)
+        n = len(off) - 1
+    out = {}
+    for k in EPX_FOLDED_NAMES:
+        if only_kind and k != "kind":
+            continue
+        out[k] = np.zeros((n, num_replicas) if k == "deps_watermark" else n, np.int64 if k == "cmd_off" else np.int32)
+    bad = C.c_int32(-1)
+    st = _L().fpx_wire_epaxos_decode_replica_inbound_folded(
+        buf.ctypes.data, sum(len(m) for m in messages), off.ctypes.data, n, num_replicas,
+        *[out[k].ctypes.data if k in out else None for k in EPX_FOLDED_NAMES], C.byref(bad))
     out["status_code"], out["bad_index"], out["buf"] = st, bad.value, buf
     return out

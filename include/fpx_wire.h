@@ -406,6 +406,80 @@ int32_t fpx_wire_epaxos_decode_replica_inbound(const uint8_t* buf, int64_t buf_l
                                                int32_t* deps_watermark, int64_t* values_off, int64_t values_cap,
                                                int32_t* values_leader, int32_t* values_id, int32_t* bad_index);
 
+/* ---- EPaxos, the FOLDED form: what a message's dependencies are to the burst calls of include/fpx.h ---------------
+ * The decoder above hands out every explicit id (a CSR over the tick, which takes a scan to build); the burst calls
+ * (fpx_epx_leader_replies, fpx_epx_replica_inbox, ...) take a watermark row and ONE word, deps_values_end.  The folded
+ * decoders give exactly that, from fixed-size state per message, and so run on the device too -- one parser source for
+ * both sides (csrc/fpx_wire_epx_parse.hpp), which the decoder above runs as well.
+ * The scalars are the decoder's above, field for field (kind, instance_*, ballot_*, replica_index, sequence_number,
+ * vote_ballot_*, status, is_noop, cmd_off / cmd_len, deps_num_replicas), and deps_watermark is n x num_replicas, a
+ * row padded with zeros; a message with more sets than num_replicas is malformed (whether deps_watermark is given or
+ * not).  In place of the explicit ids:
+ *   deps_values_end[i]  0 when message i has no dependencies or its own-leader column (instance_leader) has no
+ *                       explicit ids, else the largest explicit id of that column + 1 (EPaxosNative.scala, ownEnd).
+ *   deps_shape[i]       -1  no dependencies present.
+ *                        1  the set is in the form every EPaxos burst call takes: no explicit id in any other column,
+ *                           and the own column is either empty, or has watermark <= instance_number and the SET of
+ *                           its ids is exactly instance_number + 1 .. deps_values_end - 1 (in any order, an id may
+ *                           repeat: ScalaPB writes a hash set and every runtime reads duplicates into one).
+ *                        0  anything else: an explicit id in a foreign column (top-k dependencies, k > 1), a gap, an
+ *                           id at or below the instance number, an instance_leader outside the columns present, or
+ *                           more than FPX_WIRE_EPX_FOLD_MAX explicit-id entries in the message (the cap makes the set
+ *                           test an exact 64-bit mask and bounds one thread's work; explicit ids come from reordered
+ *                           delivery on one channel and are few).  Such a message is the host decoder's.
+ * The fold is made after the whole member is parsed: `dependencies` may precede `instance` in byte order.
+ * kind is required, every other array may be NULL.  Errors as the decoder above (*bad_index is -1 when there is none). */
+#define FPX_WIRE_EPX_FOLD_MAX 64
+/* host, g++-compiled: runs on a machine without a GPU */
+int32_t fpx_wire_epaxos_decode_replica_inbound_folded(
+    const uint8_t* buf, int64_t buf_len, const int64_t* offsets, int32_t n, int32_t num_replicas, int32_t* kind,
+    int32_t* instance_leader, int32_t* instance_number, int32_t* ballot_ordering, int32_t* ballot_replica,
+    int32_t* replica_index, int32_t* sequence_number, int32_t* vote_ballot_ordering, int32_t* vote_ballot_replica,
+    int32_t* status, int32_t* is_noop, int64_t* cmd_off, int32_t* cmd_len, int32_t* deps_num_replicas,
+    int32_t* deps_watermark, int32_t* deps_values_end, int32_t* deps_shape, int32_t* bad_index);
+
+/* The same ON THE DEVICE, the arrays as device pointers (the bytes and offsets may be page-locked host memory), enqueued
+ * on the EPaxos context's stream; num_replicas = the context's n.  One thread per message.  d_kind is required, every
+ * other output may be NULL -- but d_bad_index, which is ALWAYS written: -1 = none, otherwise the first bad offset, or,
+ * all offsets being good, the first malformed message (a bad offset outranks a malformed message, as in the host
+ * decoders).  A bad tick raises the context's status to FPX_EINVAL the way the EPaxos validation kernels do:
+ * fpx_epx_sync reports it and the calls enqueued behind it apply nothing.  No host wait inside.  n < 2^30.  The outputs of
+ * a failed decode are unspecified. */
+struct fpx_epx;
+int32_t fpx_wire_epaxos_decode_replica_inbound_dev(
+    struct fpx_epx* epx, const uint8_t* d_buf, int64_t buf_len, const int64_t* d_offsets, int32_t n, int32_t* d_kind,
+    int32_t* d_instance_leader, int32_t* d_instance_number, int32_t* d_ballot_ordering, int32_t* d_ballot_replica,
+    int32_t* d_replica_index, int32_t* d_sequence_number, int32_t* d_vote_ballot_ordering,
+    int32_t* d_vote_ballot_replica, int32_t* d_status, int32_t* d_is_noop, int64_t* d_cmd_off, int32_t* d_cmd_len,
+    int32_t* d_deps_num_replicas, int32_t* d_deps_watermark, int32_t* d_deps_values_end, int32_t* d_deps_shape,
+    int32_t* d_bad_index);
+
+/* One tick of hosted leaders (FPX_EPX_F_LEADER_STATE), bytes -> decisions: m serialised ReplicaInbound messages (in,
+ * in_len, in_offsets[m + 1]; to[i] = the replica that received message i) -> copy up (host form) -> the decoder above
+ * -> check -> fpx_epx_leader_replies_dev on the decoded arrays -> copy down.  The outputs are those of
+ * fpx_epx_leader_replies[_dev] (include/fpx.h), unchanged, any of which may be NULL; the host form stages and holds them
+ * exactly as fpx_epx_leader_replies does, the _dev form keeps the decoded arrays in scratch the context owns.
+ * The tick holds PreAcceptOk, AcceptOk and Nack only (kinds 0, 1, 2 of fpx_epx_leader_replies); the caller routes by the
+ * outer oneof tag, one byte.  A Nack carries no replica_index: the tick passes 0, which fpx_epx_leader_replies range-checks
+ * and does not read for a Nack.  A defaultToSlowPath timer event (kind 3) has no bytes: the caller cuts its tick there and
+ * passes the event through fpx_epx_leader_replies.
+ * FPX_EINVAL with *bad_index (d_bad_index: always written; bad_index may be NULL) and NOTHING applied: a bad offset; a
+ * malformed message; a message of any other kind, ClientRequest / OTHER included; a PreAcceptOk whose
+ * deps_num_replicas is not the context's n or whose deps_shape is not 1 (the caller parses that one on the host).
+ * Offsets are judged first, then the lowest offending index is reported.  A burst that decodes cleanly but that
+ * fpx_epx_leader_replies itself refuses stays FPX_EINVAL with *bad_index = -1.  Otherwise every output and every piece
+ * of device state is what fpx_epx_leader_replies leaves for the decoded burst, FPX_EFATAL_PROTOCOL (which skips a message
+ * and applies the rest) included.  m = 0: FPX_OK, *num_decided = 0.  m < 2^30. */
+int32_t fpx_wire_epx_leader_tick_dev(struct fpx_epx* epx, const uint8_t* d_in, int64_t in_len,
+                                     const int64_t* d_in_offsets, int32_t m, const int32_t* d_to, int32_t* d_outcome,
+                                     int32_t* d_out_seq, int32_t* d_out_deps, int32_t* d_out_values_end,
+                                     int32_t* d_out_triple, int32_t* d_decided_index, int32_t* d_num_decided,
+                                     int32_t* d_bad_index);
+int32_t fpx_wire_epx_leader_tick(struct fpx_epx* epx, const uint8_t* in, int64_t in_len, const int64_t* in_offsets,
+                                 int32_t m, const int32_t* to, int32_t* outcome, int32_t* out_seq, int32_t* out_deps,
+                                 int32_t* out_values_end, int32_t* out_triple, int32_t* decided_index,
+                                 int32_t* num_decided, int32_t* bad_index);
+
 #ifdef __cplusplus
 }
 #endif
