@@ -34,6 +34,16 @@ def row_range(L, lg, ja, jb, extra=0):
     return ja * L + lg, jb * L + lg + 1 + extra
 
 
+def band_halves(L, rows, n_ranges):
+    """commands of the lower half of the leader groups (rows 0 ... 31), ranges of the upper half"""
+    h = L // 2
+    slot = (np.arange(32)[:, None] * L + np.arange(h)[None, :]).reshape(-1).astype(np.int32)
+    ranges = [row_range(L, h + k % h, 4 * (k // h), 4 * (k // h) + k % 2, extra=k % 3) for k in range(n_ranges)]
+    assert 4 * (n_ranges // h) + 2 <= rows
+    start, end = (np.array(x, np.int32) for x in zip(*ranges))
+    return slot, start, end
+
+
 def overlaps(start, end, L):
     """bool [n]: range i shares a row with another non-empty range of its leader group (exact duplicates included)"""
     ja, jb = rows_of(start, end, L)

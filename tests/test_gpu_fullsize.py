@@ -192,25 +192,7 @@ def test_config5_mencius_256_leader_groups_4m_slots(fa, oracle, row_layout):
             np.testing.assert_array_equal(x, y)
 
 
-def _band_on_device(fa, gpu, fused_op, ranges_op, independent):
-    """one proxy-leader step through fpx_mencius_band_fused_dev on device-resident arrays; returns the two halves' outputs
-    in the order of phase2_fused / noop_ranges_fused"""
-    import torch
-    dev = torch.device("cuda:0")
-    d = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-    _, slot, rr, val, tgt = fused_op
-    _, st_, en_, rn_, tm = ranges_op
-    n, k, A = len(slot), len(st_), gpu.cfg.num_groups
-    ch, cr, cv, nr = (torch.zeros(n, dtype=torch.uint8, device=dev), torch.full((n,), -1, dtype=torch.int32, device=dev),
-                      torch.full((n,), -1, dtype=torch.int32, device=dev), torch.full((n,), -1, dtype=torch.int32, device=dev))
-    vb, nb = (torch.zeros((k, A, 4), dtype=torch.int64, device=dev) for _ in range(2))
-    rnr, new, rch = (torch.full((k,), -1, dtype=torch.int32, device=dev), torch.zeros(k, dtype=torch.uint8, device=dev),
-                     torch.zeros(k, dtype=torch.uint8, device=dev))
-    gpu.mencius_band_fused_dev(d(slot), d(rr), d(val), None if tgt is None else d(tgt.view(np.int64)), ch, cr, cv, nr, d(st_), d(en_),
-                               d(rn_), d(np.ascontiguousarray(tm).view(np.int64)), vb, nb, rnr, new, rch, independent=independent)
-    st = gpu.sync()
-    h = lambda t: t.cpu().numpy()
-    return st, (h(ch), h(cr), h(cv), h(nr)), (h(vb).view(np.uint64), h(nb).view(np.uint64), h(rnr), h(new), h(rch))
+_band_on_device = W.band_on_device   # (shared with tests/test_gpu_round_range.py)
 
 
 @pytest.mark.parametrize("dense", [False, True])

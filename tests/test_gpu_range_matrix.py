@@ -222,14 +222,7 @@ def test_chain_passes_and_admission_limits(fa, oracle, row_layout, n, A, R, form
 # ---------------------------------------------------------------------------------------------------------------------
 # the band: the chain as the first workgroup of k_phase2_band (256 threads)
 # ---------------------------------------------------------------------------------------------------------------------
-def band_halves(L, rows, n_ranges):
-    """commands of the lower half of the leader groups (rows 0 ... 31), ranges of the upper half"""
-    h = L // 2
-    slot = (np.arange(32)[:, None] * L + np.arange(h)[None, :]).reshape(-1).astype(np.int32)
-    ranges = [RB.row_range(L, h + k % h, 4 * (k // h), 4 * (k // h) + k % 2, extra=k % 3) for k in range(n_ranges)]
-    assert 4 * (n_ranges // h) + 2 <= rows
-    start, end = (np.array(x, np.int32) for x in zip(*ranges))
-    return slot, start, end
+band_halves = RB.band_halves
 
 
 @pytest.mark.parametrize("n_ranges,form", BAND_CASES)

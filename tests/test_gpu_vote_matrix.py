@@ -47,23 +47,7 @@ def cells(ctx, **want):
             if all(k[keys.index(name)] == val for name, val in want.items())}
 
 
-def shaped(script, delivery, solo_every=2, solo_n=400):
-    """the adversarial script with its vote batches delivered as the case asks: no target masks when dense; every
-    `solo_every`-th batch cut into pieces of at most `solo_n` messages (each a solo launch), the others whole"""
-    out, k = [], 0
-    for op in script:
-        if op[0] not in ("fused", "k1k2"):
-            out.append(op)
-            continue
-        op = list(op)
-        if delivery == "dense":
-            op[4] = None
-        n = len(op[1])
-        size = solo_n if solo_every and k % solo_every == 1 else max(n, 1)
-        for lo in range(0, n, size):
-            out.append(tuple([op[0]] + [None if a is None else a[lo:lo + size] for a in op[1:]]))
-        k += 1
-    return out
+shaped = W.shaped   # (shared with tests/round_range_cases.py)
 
 
 def steady_ops(kind, lo, n, R, rng, delivery):
