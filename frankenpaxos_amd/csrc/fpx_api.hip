@@ -17,6 +17,7 @@
 #include <new>
 #include <set>
 #include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "fpx_host.hpp"
@@ -72,12 +73,6 @@ struct HostSlot {
   int n = 0;
 };
 
-// host staging of a range batch (host_ranges): int32 start / end / round / entry / nack_round, u8 is_new / chosen, and
-// num_groups x 4 words of target / vote / nack bits per range
-struct RangeStage {
-  DevBuf start, end, round, entry, nack_round, is_new, chosen, target, votes, nacks;
-};
-
 struct fpx_ctx {
   fpx_config cfg;
   Geom g;
@@ -92,8 +87,11 @@ struct fpx_ctx {
   int64_t bytes = 0;
   int last_hip = 0;
   int32_t err_index = -1, err_slot = -1, err_round = -1;
-  // host-API staging (device)
-  DevBuf d_slot, d_round, d_value, d_target, d_bits_a, d_bits_b, d_i32_a, d_i32_b, d_i32_c, d_u8, d_scratch;
+  // Host-pointer entry points: every array of a call -- inputs, outputs, device-only temporaries -- is carved out of ONE
+  // staging buffer by the driver the EPaxos context shares (host_call, fpx_host.hpp); an entry point lists its arrays and
+  // the list points its typed slots at them.  No array of a host form has a buffer of its own in this struct.
+  HostStage stage;
+  DevBuf d_scratch;  // the few words (or the one dump) that a read-back entry point, Phase 1 included, copies out itself
   // host-side run splitting
   std::vector<uint32_t> hstamp;
   uint32_t hrun = 0;
@@ -128,7 +126,6 @@ struct fpx_ctx {
   RangeTable rt[2];
   int rt_cur = 0;
   DevBuf d_rng;     // scratch of device range batches (fpx_noop_ranges_fused_dev)
-  RangeStage rng;  // staging of host range batches
   // fpx_mencius_band_fused_dev: the ranges' half of an independent step runs here, between a fork and a join event
   hipStream_t band_stream = nullptr;
   int64_t band_merged_steps = 0;
@@ -138,36 +135,30 @@ struct fpx_ctx {
   int census_pending = 0;  // the cell of the launch whose fold is pending_fin
   int64_t range_census[FPX_RANGE_CENSUS_WORDS] = {};  // fpx_range_launch_census: host counters of the K4 launches
   DevBuf d_enc;   // the device encoders' workgroup sums (fpx_wire_encode_*_dev)
-  // fpx_wire_phase2_tick: the tick's bytes and offsets, its decoded records (kind, slot, round, is_noop, value_len, value_id,
-  // value_off), the reply's bytes, offsets and totals
-  DevBuf w_buf, w_off, w_rec[7], w_out, w_ooff, w_tot;
   // fpx_proxy_phase2b_msgs_dev (fpx_tally_msgs.hpp): the owner word of every tally entry ([S][wp], INT_MAX between calls;
-  // allocated by the first call), and per call the messages' entries, the gathered rows and the compaction's workgroup sums
-  DevBuf m_owner, m_entry, m_rows, m_blk;
+  // allocated by the first call), and per call the messages' entries and the gathered rows
+  DevBuf m_owner, m_entry, m_rows;
   // fpx_mencius_proxy_phase2b_msgs_dev (fpx_mencius_msgs.hpp): the claim word of every range-table entry ([cap], INT_MAX
-  // between calls; allocated by the first call; one array for both table buffers), and the tick's staged slot_end / records
-  DevBuf mm_claim, mm_end, mm_rec[5];
+  // between calls; allocated by the first call; one array for both table buffers)
+  DevBuf mm_claim;
   // fpx_replica_chosen_msgs_dev (fpx_replica_msgs.hpp): the claim word of every slot ([S], INT_MAX between calls; allocated
   // by the first call), and per call the header words, the workgroups' folds, and the list of the burst's ranges
   DevBuf rm_claim, rm_buf;
   // fpx_replica_inbox[_dev] (fpx_replica_inbox.hpp): the per-call scratch (header words, the workgroups' folds, the tiles'
-  // maxima, the sort's counts and its two key / value buffers), and the host form's staged outputs (exec_count, reply_slot,
-  // order, counts).  The claim words are rm_claim's.
-  DevBuf ri_buf, ri_out[4];
+  // maxima, the sort's counts and its two key / value buffers).  The claim words are rm_claim's.
+  DevBuf ri_buf;
   // fpx_acceptor_inbox[_dev] (fpx_acceptor_inbox.hpp): the per-call scratch (header words, the tiles' maxima, the sort's
-  // counts and its two key / value buffers, the accepted slots and claim positions, the entries' new scalars), the claim
-  // table sized by the largest burst so far (cell numbers, all ones between calls; bids, -1 between calls), and the host
-  // form's staged replies
-  DevBuf ai_buf, ai_tkey, ai_tval, ai_out[2];
+  // counts and its two key / value buffers, the accepted slots and claim positions, the entries' new scalars), and the claim
+  // table sized by the largest burst so far (cell numbers, all ones between calls; bids, -1 between calls)
+  DevBuf ai_buf, ai_tkey, ai_tval;
   // fpx_mencius_acceptor_inbox[_dev] (fpx_mencius_acceptor_inbox.hpp): the per-call scratch (ai_buf's parts, the range
-  // flags, the tiles' range counts and the list of accepted ranges).  The claim table and the staged replies are ai_*'s.
+  // flags, the tiles' range counts and the list of accepted ranges).  The claim table is ai_*'s.
   DevBuf mai_buf;
-  // fpx_acceptor_phase1b_info_all[_dev] (fpx_phase1_info.hpp): the chunk counts, column totals and the go word; the host
-  // form's offsets and totals
-  DevBuf p1i, p1i_off, p1i_tot;
+  // fpx_acceptor_phase1b_info_all[_dev] (fpx_phase1_info.hpp): the chunk counts, column totals and the go word
+  DevBuf p1i;
   // fpx_leader_phase1b_msgs[_dev] (fpx_phase1b_msgs.hpp): the per-call scratch (control block, first / last tables, the
-  // winners' work list), the bid table (cap x 8 bytes), and the host form's staging (8 inputs, 5 outputs)
-  DevBuf p1m_buf, p1m_tab, p1m_stage[13];
+  // winners' work list), and the bid table (cap x 8 bytes)
+  DevBuf p1m_buf, p1m_tab;
   DevBuf d_band;  // [num_leader_groups] marks: the leader groups with a range in the step being checked
   // multi-GPU (fpx_comm_*): one communicator per context, rank = this context's GPU
   RcclComm comm = nullptr;
@@ -640,6 +631,17 @@ Batch batch_of(int32_t n, const int32_t* d_slot, const int32_t* d_round, const i
   return b;
 }
 
+// messages [lo, lo + len) of a batch whose arrays are staged whole (a run of a host batch)
+Batch run_of(const Batch& w, int lo, int len) {
+  const auto at = [lo](auto* p, size_t per) { return p ? p + (size_t)lo * per : p; };
+  Batch b = w;
+  b.n = len, b.slot = at(w.slot, 1), b.round = at(w.round, 1), b.value = at(w.value, 1), b.target = at(w.target, 4);
+  b.vote_bits = at(w.vote_bits, 4), b.nack_bits = at(w.nack_bits, 4), b.nack_round = at(w.nack_round, 1);
+  b.chosen = at(w.chosen, 1), b.chosen_round = at(w.chosen_round, 1), b.chosen_value = at(w.chosen_value, 1);
+  b.is_new = at(w.is_new, 1);
+  return b;
+}
+
 int run_phase2_fused(fpx_ctx* ctx, int32_t n, const int32_t* d_slot, const int32_t* d_round, const int32_t* d_value_id,
                      const uint64_t* d_target_mask, uint8_t* d_chosen, int32_t* d_chosen_round, int32_t* d_chosen_value,
                      int32_t* d_nack_round, const RunOpts& opts) {
@@ -1059,24 +1061,12 @@ void free_state(fpx_ctx* ctx) {
                 ctx->rt[1].key, ctx->rt[1].bits, ctx->rt[1].owner, ctx->rt[1].count, ctx->d_rng.p, ctx->d_run_done.p};
   for (void* p : ps)
     if (p) (void)hipFree(p);
-  RangeStage& rs = ctx->rng;
-  DevBuf* bs[] = {&ctx->d_slot,   &ctx->d_round, &ctx->d_value, &ctx->d_target, &ctx->d_bits_a, &ctx->d_bits_b,
-                  &ctx->d_i32_a,  &ctx->d_i32_b, &ctx->d_i32_c, &ctx->d_u8,     &ctx->d_scratch,
-                  &rs.start,      &rs.end,       &rs.round,     &rs.entry,      &rs.nack_round, &rs.is_new,
-                  &rs.chosen,     &rs.target,    &rs.votes,     &rs.nacks,
-                  &ctx->d_enc,    &ctx->w_buf,   &ctx->w_off,   &ctx->w_out,    &ctx->w_ooff,   &ctx->w_tot,
-                  &ctx->w_rec[0], &ctx->w_rec[1], &ctx->w_rec[2], &ctx->w_rec[3], &ctx->w_rec[4], &ctx->w_rec[5],
-                  &ctx->w_rec[6], &ctx->m_owner, &ctx->m_entry,  &ctx->m_rows,   &ctx->m_blk,
-                  &ctx->rm_claim, &ctx->rm_buf,   &ctx->mm_claim, &ctx->mm_end,   &ctx->mm_rec[0], &ctx->mm_rec[1],
-                  &ctx->mm_rec[2], &ctx->mm_rec[3], &ctx->mm_rec[4],
-                  &ctx->p1i,      &ctx->p1i_off, &ctx->p1i_tot, &ctx->p1m_buf, &ctx->p1m_tab,
-                  &ctx->ri_buf,   &ctx->ri_out[0], &ctx->ri_out[1], &ctx->ri_out[2], &ctx->ri_out[3],
-                  &ctx->ai_buf,   &ctx->ai_tkey,  &ctx->ai_tval, &ctx->ai_out[0], &ctx->ai_out[1],
-                  &ctx->mai_buf};
+  free_stage(&ctx->stage);
+  DevBuf* bs[] = {&ctx->d_scratch, &ctx->d_enc,   &ctx->m_owner, &ctx->m_entry, &ctx->m_rows,  &ctx->rm_claim,
+                  &ctx->rm_buf,    &ctx->mm_claim, &ctx->p1i,     &ctx->p1m_buf, &ctx->p1m_tab, &ctx->ri_buf,
+                  &ctx->ai_buf,    &ctx->ai_tkey,  &ctx->ai_tval, &ctx->mai_buf};
   for (DevBuf* b : bs)
     if (b->p) (void)hipFree(b->p);
-  for (DevBuf& b : ctx->p1m_stage)
-    if (b.p) (void)hipFree(b.p);
   for (hipEvent_t e : ctx->ev) (void)hipEventDestroy(e);
   ctx->ev.clear();
   for (hipEvent_t e : ctx->cev) (void)hipEventDestroy(e);
@@ -1192,14 +1182,6 @@ int check_inputs(fpx_ctx* ctx, int n, const int32_t* slot, const int32_t* round,
   return FPX_EINVAL;
 }
 
-template <typename T>
-int h2d(fpx_ctx* ctx, DevBuf* b, const T* src, size_t count) {
-  int rc = grow(ctx, b, count * sizeof(T));
-  if (rc) return rc;
-  if (src && count) HIPCHK(ctx, hipMemcpyAsync(b->p, src, count * sizeof(T), hipMemcpyHostToDevice, ctx->stream));
-  return FPX_OK;
-}
-
 template <int G>
 void launch_p1b(fpx_ctx* ctx, const uint64_t* d_q, int wm, int count, int32_t* d_sr, int32_t* d_sv) {
   const int per_block = 4 * (64 / G);
@@ -1208,51 +1190,25 @@ void launch_p1b(fpx_ctx* ctx, const uint64_t* d_q, int wm, int count, int32_t* d
                      ctx->vec ? 1 : 0, d_sr, d_sv);
 }
 
-template <typename T>
-int d2h(fpx_ctx* ctx, T* dst, const DevBuf& b, size_t count) {
-  if (dst && count) HIPCHK(ctx, hipMemcpyAsync(dst, b.p, count * sizeof(T), hipMemcpyDeviceToHost, ctx->stream));
-  return FPX_OK;
-}
-
-
 // ---- host batches: stage, cut into runs, run, copy back ----------------------------------------------------------
-// The arrays of a host batch: `bytes` per message in the caller's array and in its staging buffer.  An input whose
-// array is NULL is neither uploaded nor staged; every output is staged, and downloaded when its array is not NULL.
-// `extra`: bytes on top of n * bytes (a tick's byte buffer is not per message; its offsets are n + 1).
-struct HostIn {
-  DevBuf* buf;
-  const void* src;
-  size_t bytes;
-  size_t extra = 0;
-};
-struct HostOut {
-  DevBuf* buf;
-  void* dst;
-  size_t bytes;
-  size_t extra = 0;
+// how a host-pointer call on an fpx_ctx ends: with the device's status (fetch_status synchronises); a held output reaches
+// the caller when that is FPX_OK -- the burst was applied
+struct CtxEnd {
+  fpx_ctx* ctx;
+  int operator()() const { return fetch_status(ctx); }
+  static bool applied(int rc) { return rc == FPX_OK; }
 };
 
-// message i of a staging buffer of T
-template <typename T>
-T* staged(const DevBuf& b, size_t i) {
-  return (T*)b.p + i;
-}
-
-// The driver of the host-pointer entry points.  Uploads the inputs and grows the outputs; then cut(&cuts) checks the
-// batch on the host -- behind the uploads, so with page-locked arrays the CPU pass overlaps the DMA; nothing is launched
-// on a bad batch -- and cuts it into runs that satisfy the run contract; run(lo, len, opts) launches messages
-// [lo, lo + len) with opts.index_base = lo, the runs back to back (= message-at-a-time delivery in array order); then the
-// outputs come down and the device's status is returned.  cut == nullptr: the whole batch is ONE run, validated on the
-// device (RunOpts::FORCE_VALIDATE; the runs of a cut batch are RunOpts::CUT_ON_HOST).
+// The launches of a host batch whose arrays are staged.  cut(&cuts) checks the batch on the host -- behind the uploads, so
+// with page-locked arrays the CPU pass overlaps the DMA; nothing is launched on a bad batch -- and cuts it into runs that
+// satisfy the run contract; run(lo, len, opts) launches messages [lo, lo + len) with opts.index_base = lo (a run addresses
+// its slice of a staged array as slot + lo), the runs back to back (= message-at-a-time delivery in array order).
+// cut == nullptr: the whole batch is ONE run, validated on the device (RunOpts::FORCE_VALIDATE; the runs of a cut batch
+// are RunOpts::CUT_ON_HOST).  A run that fails ends the call: the stream is synchronised, nothing is downloaded.
 template <typename Cut, typename Run>
-int host_batch(fpx_ctx* ctx, int n, std::initializer_list<HostIn> in, std::initializer_list<HostOut> out, Cut cut,
-               Run run) {
+int launch_runs(fpx_ctx* ctx, int n, Cut cut, Run run) {
   constexpr bool cut_on_host = !std::is_null_pointer<Cut>::value;
   int rc;
-  for (const HostIn& a : in)
-    if (a.src && (rc = h2d(ctx, a.buf, (const char*)a.src, (size_t)n * a.bytes + a.extra))) return rc;
-  for (const HostOut& a : out)
-    if ((rc = grow(ctx, a.buf, (size_t)n * a.bytes + a.extra))) return rc;
   std::vector<int> cuts{0, n};
   if constexpr (cut_on_host) {
     if ((rc = cut(&cuts))) return rc;
@@ -1266,9 +1222,14 @@ int host_batch(fpx_ctx* ctx, int n, std::initializer_list<HostIn> in, std::initi
       return rc;
     }
   }
-  for (const HostOut& a : out)
-    if ((rc = d2h(ctx, (char*)a.dst, *a.buf, (size_t)n * a.bytes + a.extra))) return rc;
-  return fetch_status(ctx);
+  return FPX_OK;
+}
+
+// The driver of the host-pointer entry points: host_call (fpx_host.hpp) stages the arrays, the runs are launched, the
+// outputs come down -- whatever the device's status says afterwards -- and the device's status is returned.
+template <typename Cut, typename Run>
+int host_runs(fpx_ctx* ctx, int n, std::initializer_list<Staged> arrays, Cut cut, Run run) {
+  return host_call(ctx, arrays, [&] { return launch_runs(ctx, n, cut, run); }, CtxEnd{ctx});
 }
 
 // the cuts of a host batch of messages: the range check (the first offender for fpx_error_detail), then split_runs
@@ -1456,21 +1417,21 @@ int enqueue_p1i(fpx_ctx* ctx, int32_t chosen_watermark, const uint64_t* d_masks,
   return launch_check(ctx);
 }
 
-// the host form's staging: the masks up (d_bits_a), offsets / records / totals down -- ONE run of the staging driver
-int host_p1i(fpx_ctx* ctx, int32_t chosen_watermark, const uint64_t* masks, bool masks_staged, int64_t cap, int64_t* offsets,
-                    int32_t* slot, int32_t* vote_round, int32_t* vote_value, int64_t* count) {
-  const size_t E = (size_t)ctx->g.ngroups * ctx->g.R, mbytes = (size_t)ctx->g.ngroups * 32, rec = (size_t)cap * 4;
+// the host form's staging: the masks up (`masks`; or they are on the device already, `d_masks`; neither: every acceptor),
+// offsets / records / totals down -- ONE run of the staging driver
+int host_p1i(fpx_ctx* ctx, int32_t chosen_watermark, const uint64_t* masks, const uint64_t* d_masks, int64_t cap,
+             int64_t* offsets, int32_t* slot, int32_t* vote_round, int32_t* vote_value, int64_t* count) {
+  const size_t E = (size_t)ctx->g.ngroups * ctx->g.R;
   int64_t totals[2] = {0, 0};
-  const bool up = masks && !masks_staged;
-  const int rc = host_batch(
-      ctx, 1, {{&ctx->d_bits_a, up ? masks : nullptr, 0, mbytes}},
-      {{&ctx->p1i_off, offsets, 0, (E + 1) * 8}, {&ctx->d_i32_a, slot, 0, rec}, {&ctx->d_i32_b, vote_round, 0, rec},
-       {&ctx->d_i32_c, vote_value, 0, rec}, {&ctx->p1i_tot, totals, 0, 16}},
-      nullptr, [&](int, int, const RunOpts&) {
-        return enqueue_p1i(ctx, chosen_watermark, masks ? (const uint64_t*)ctx->d_bits_a.p : nullptr, cap,
-                           (int64_t*)ctx->p1i_off.p, (int32_t*)ctx->d_i32_a.p, (int32_t*)ctx->d_i32_b.p, (int32_t*)ctx->d_i32_c.p,
-                           (int64_t*)ctx->p1i_tot.p);
-      });
+  uint64_t* d_up;
+  int64_t *d_off, *d_tot;
+  int32_t *d_slot, *d_vr, *d_vv;
+  const int rc = host_runs(ctx, 1,
+                           {opt_in(d_up, masks, (size_t)ctx->g.ngroups * 4), out(d_off, offsets, E + 1), out(d_slot, slot, cap),
+                            out(d_vr, vote_round, cap), out(d_vv, vote_value, cap), out(d_tot, totals, 2)},
+                           nullptr, [&](int, int, const RunOpts&) {
+                             return enqueue_p1i(ctx, chosen_watermark, masks ? d_up : d_masks, cap, d_off, d_slot, d_vr, d_vv, d_tot);
+                           });
   if (count) *count = totals[0];
   return rc;
 }
@@ -1971,7 +1932,7 @@ int32_t fpx_wire_encode_leader_nack_dev(fpx_ctx* ctx, int32_t dialect, int32_t n
   return wire_encode_dev<ENC_NACK>(ctx, a);
 }
 
-// One proxy-leader tick, bytes to bytes, through the staging driver of the host-pointer entry points (host_batch): the
+// One proxy-leader tick, bytes to bytes, through the staging driver of the host-pointer entry points (host_runs): the
 // tick's bytes and offsets go up, ONE device run decodes, requires Phase2a's, votes and tallies, and encodes the Chosen
 // messages, and the reply's bytes, offsets, totals and Nack rounds come down.
 int32_t fpx_wire_phase2_tick(fpx_ctx* ctx, const uint8_t* in, int64_t in_len, const int64_t* in_offsets, int32_t n,
@@ -1987,36 +1948,29 @@ int32_t fpx_wire_phase2_tick(fpx_ctx* ctx, const uint8_t* in, int64_t in_len, co
   if (!mapped_host(in) || !mapped_host(in_offsets) || (out && !mapped_host(out)) || !mapped_host(out_offsets) ||
       (nack_round && !mapped_host(nack_round)))
     return FPX_EINVAL;
-  int rc;
-  const size_t rec_bytes[7] = {4, 4, 4, 4, 4, 4, 8};
-  for (int k = 0; k < 7; ++k)
-    if ((rc = grow(ctx, &ctx->w_rec[k], (size_t)n * rec_bytes[k]))) return rc;
-  for (DevBuf* b : {&ctx->d_u8, &ctx->d_i32_a, &ctx->d_i32_b})
-    if ((rc = grow(ctx, b, (size_t)n * 4))) return rc;
   int64_t totals[2] = {0, 0};
-  rc = host_batch(
-      ctx, n, {{&ctx->w_buf, in, 0, (size_t)in_len}, {&ctx->w_off, in_offsets, 8, 8}},
-      {{&ctx->w_out, out, 0, (size_t)out_cap}, {&ctx->w_ooff, out_offsets, 8, 8}, {&ctx->d_i32_c, nack_round, 4},
-       {&ctx->w_tot, totals, 0, 16}},
+  uint8_t *d_buf, *d_out, *d_chosen;
+  int64_t *d_off, *d_ooff, *d_tot, *value_off;
+  int32_t *d_nack, *d_cround, *d_cvalue, *rec[6];  // the decoded records: kind, slot, round, is_noop, value_len, value_id
+  const size_t m = (size_t)n;
+  const int rc = host_runs(
+      ctx, n,
+      {fpx::in(d_buf, in, (size_t)in_len), fpx::in(d_off, in_offsets, m + 1), fpx::out(d_out, out, (size_t)out_cap),
+       fpx::out(d_ooff, out_offsets, m + 1), fpx::out(d_nack, nack_round, m), fpx::out(d_tot, totals, 2), scratch(rec[0], m),
+       scratch(rec[1], m), scratch(rec[2], m), scratch(rec[3], m), scratch(rec[4], m), scratch(rec[5], m), scratch(value_off, m),
+       scratch(d_chosen, m), scratch(d_cround, m), scratch(d_cvalue, m)},
       nullptr, [&](int, int, const RunOpts& opts) {
-        int32_t* rec[6];
-        for (int k = 0; k < 6; ++k) rec[k] = (int32_t*)ctx->w_rec[k].p;
-        int64_t* value_off = (int64_t*)ctx->w_rec[6].p;
-        const uint8_t* buf = (const uint8_t*)ctx->w_buf.p;
-        int r = fpx_wire_decode_proxy_leader_inbound_dev(ctx, buf, in_len, (const int64_t*)ctx->w_off.p, n, rec[0], rec[1],
-                                                         rec[2], rec[3], value_off, rec[4], nullptr, nullptr, 0, rec[5]);
+        int r = fpx_wire_decode_proxy_leader_inbound_dev(ctx, d_buf, in_len, d_off, n, rec[0], rec[1], rec[2], rec[3], value_off,
+                                                         rec[4], nullptr, nullptr, 0, rec[5]);
         if (r) return r;
         hipLaunchKernelGGL(k_wire_require_kind, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, ctx->st, rec[0], n,
                            (int32_t)FPX_WIRE_PHASE2A);
         hipLaunchKernelGGL(k_wire_tail, dim3(1), dim3(1), 0, ctx->stream, ctx->st);
         if ((r = launch_check(ctx))) return r;
-        uint8_t* chosen = (uint8_t*)ctx->d_u8.p;
-        r = run_phase2_fused(ctx, n, rec[1], rec[2], rec[5], nullptr, chosen, (int32_t*)ctx->d_i32_a.p,
-                             (int32_t*)ctx->d_i32_b.p, (int32_t*)ctx->d_i32_c.p, opts);
+        r = run_phase2_fused(ctx, n, rec[1], rec[2], rec[5], nullptr, d_chosen, d_cround, d_cvalue, d_nack, opts);
         if (r) return r;
-        return fpx_wire_encode_replica_chosen_dev(ctx, n, chosen, rec[1], rec[3], buf, in_len, value_off, rec[4],
-                                                  (uint8_t*)ctx->w_out.p, out_cap, (int64_t*)ctx->w_ooff.p,
-                                                  (int64_t*)ctx->w_tot.p);
+        return fpx_wire_encode_replica_chosen_dev(ctx, n, d_chosen, rec[1], rec[3], d_buf, in_len, value_off, rec[4], d_out,
+                                                  out_cap, d_ooff, d_tot);
       });
   if (bad_index && (rc == FPX_EINVAL || rc == FPX_EORDER)) *bad_index = ctx->err_index;
   if (rc != FPX_OK && rc != FPX_ECAPACITY) return rc;
@@ -2078,17 +2032,16 @@ int32_t fpx_proxy_phase2b_msgs(fpx_ctx* ctx, int32_t n, const int32_t* kind, con
   if (!ctx || n < 0 || n >= (1 << 30) || grid_cols < 0) return FPX_EINVAL;
   if (n == 0) return FPX_OK;
   if (!acceptor_index || !slot || !round) return FPX_EINVAL;
-  return host_batch(ctx, n,
-                    {{&ctx->d_value, kind, 4}, {&ctx->d_target, group_index, 4}, {&ctx->d_i32_c, acceptor_index, 4},
-                     {&ctx->d_slot, slot, 4}, {&ctx->d_round, round, 4}},
-                    {{&ctx->d_u8, newly_chosen, 1}, {&ctx->d_i32_a, chosen_round, 4}, {&ctx->d_i32_b, chosen_value, 4}},
-                    nullptr, [&](int, int, const RunOpts&) {
-                      return fpx_proxy_phase2b_msgs_dev(
-                          ctx, n, kind ? (const int32_t*)ctx->d_value.p : nullptr,
-                          group_index ? (const int32_t*)ctx->d_target.p : nullptr, (const int32_t*)ctx->d_i32_c.p,
-                          (const int32_t*)ctx->d_slot.p, (const int32_t*)ctx->d_round.p, grid_cols, (uint8_t*)ctx->d_u8.p,
-                          (int32_t*)ctx->d_i32_a.p, (int32_t*)ctx->d_i32_b.p);
-                    });
+  int32_t *d_kind, *d_group, *d_acceptor, *d_slot, *d_round, *d_cround, *d_cvalue;
+  uint8_t* d_chosen;
+  return host_runs(ctx, n,
+                   {opt_in(d_kind, kind, n), opt_in(d_group, group_index, n), in(d_acceptor, acceptor_index, n), in(d_slot, slot, n),
+                    in(d_round, round, n), out(d_chosen, newly_chosen, n), out(d_cround, chosen_round, n),
+                    out(d_cvalue, chosen_value, n)},
+                   nullptr, [&](int, int, const RunOpts&) {
+                     return fpx_proxy_phase2b_msgs_dev(ctx, n, d_kind, d_group, d_acceptor, d_slot, d_round, grid_cols, d_chosen,
+                                                       d_cround, d_cvalue);
+                   });
 }
 
 // One tick of a proxy leader among remote acceptors, bytes to records, through the staging driver as ONE run: the tick's
@@ -2107,35 +2060,27 @@ int32_t fpx_wire_phase2b_tick(fpx_ctx* ctx, const uint8_t* in, int64_t in_len, c
   if (!mapped_host(in) || !mapped_host(in_offsets) ||
       (out_cap > 0 && (!mapped_host(out_slot) || !mapped_host(out_round) || !mapped_host(out_value_id))))
     return FPX_EINVAL;
-  int rc;
-  for (int k = 0; k < 5; ++k)
-    if ((rc = grow(ctx, &ctx->w_rec[k], (size_t)n * 4))) return rc;
-  for (DevBuf* b : {&ctx->d_u8, &ctx->d_i32_a, &ctx->d_i32_b})
-    if ((rc = grow(ctx, b, (size_t)n * 4))) return rc;
   MsgCompact c;
   memset(&c, 0, sizeof(c));
   c.n = n, c.nblk = (n + 255) / 256, c.cap = out_cap;
-  if ((rc = grow(ctx, &ctx->m_blk, (size_t)c.nblk * 4))) return rc;
   int64_t totals[2] = {0, 0};
-  const size_t rec = (size_t)out_cap * 4;
-  rc = host_batch(
-      ctx, n, {{&ctx->w_buf, in, 0, (size_t)in_len}, {&ctx->w_off, in_offsets, 8, 8}},
-      {{&ctx->w_out, out_slot, 0, rec}, {&ctx->w_ooff, out_round, 0, rec}, {&ctx->d_i32_c, out_value_id, 0, rec},
-       {&ctx->w_tot, totals, 0, 16}},
+  uint8_t *d_buf, *d_chosen;
+  int64_t* d_off;
+  int32_t *d_cround, *d_cvalue, *r5[5];  // the decoded records: kind, slot, round, group_index, acceptor_index
+  const size_t m = (size_t)n, cap = (size_t)out_cap;
+  const int rc = host_runs(
+      ctx, n,
+      {fpx::in(d_buf, in, (size_t)in_len), fpx::in(d_off, in_offsets, m + 1), out(c.out_slot, out_slot, cap),
+       out(c.out_round, out_round, cap), out(c.out_value, out_value_id, cap), out(c.totals, totals, 2), scratch(r5[0], m),
+       scratch(r5[1], m), scratch(r5[2], m), scratch(r5[3], m), scratch(r5[4], m), scratch(d_chosen, m), scratch(d_cround, m),
+       scratch(d_cvalue, m), scratch(c.blk, (size_t)c.nblk)},
       nullptr, [&](int, int, const RunOpts&) {
-        int32_t* r5[5];
-        for (int k = 0; k < 5; ++k) r5[k] = (int32_t*)ctx->w_rec[k].p;  // kind, slot, round, group_index, acceptor_index
-        int r = fpx_wire_decode_proxy_leader_inbound_dev(ctx, (const uint8_t*)ctx->w_buf.p, in_len,
-                                                         (const int64_t*)ctx->w_off.p, n, r5[0], r5[1], r5[2], nullptr,
-                                                         nullptr, nullptr, r5[3], r5[4], 0, nullptr);
+        int r = fpx_wire_decode_proxy_leader_inbound_dev(ctx, d_buf, in_len, d_off, n, r5[0], r5[1], r5[2], nullptr, nullptr,
+                                                         nullptr, r5[3], r5[4], 0, nullptr);
         if (r) return r;
-        r = fpx_proxy_phase2b_msgs_dev(ctx, n, r5[0], r5[3], r5[4], r5[1], r5[2], grid_cols, (uint8_t*)ctx->d_u8.p,
-                                       (int32_t*)ctx->d_i32_a.p, (int32_t*)ctx->d_i32_b.p);
+        r = fpx_proxy_phase2b_msgs_dev(ctx, n, r5[0], r5[3], r5[4], r5[1], r5[2], grid_cols, d_chosen, d_cround, d_cvalue);
         if (r) return r;
-        c.chosen = (const uint8_t*)ctx->d_u8.p, c.slot = r5[1], c.chosen_round = (const int32_t*)ctx->d_i32_a.p;
-        c.chosen_value = (const int32_t*)ctx->d_i32_b.p, c.blk = (int32_t*)ctx->m_blk.p;
-        c.out_slot = (int32_t*)ctx->w_out.p, c.out_round = (int32_t*)ctx->w_ooff.p, c.out_value = (int32_t*)ctx->d_i32_c.p;
-        c.totals = (int64_t*)ctx->w_tot.p;
+        c.chosen = d_chosen, c.slot = r5[1], c.chosen_round = d_cround, c.chosen_value = d_cvalue;
         hipLaunchKernelGGL(k_msgs_count, dim3(c.nblk), dim3(256), 0, ctx->stream, ctx->st, c);
         hipLaunchKernelGGL(k_msgs_scan, dim3(1), dim3(1024), 0, ctx->stream, ctx->st, c);
         hipLaunchKernelGGL(k_msgs_emit, dim3(c.nblk), dim3(256), 0, ctx->stream, ctx->st, c);
@@ -2155,18 +2100,16 @@ int32_t fpx_acceptor_phase2a(fpx_ctx* ctx, int32_t n, const int32_t* slot, const
   if (rc) return rc;
   if (n == 0) return FPX_OK;
   if (!value_id) return FPX_EINVAL;
-  return host_batch(ctx, n,
-                    {{&ctx->d_slot, slot, 4}, {&ctx->d_round, round, 4}, {&ctx->d_value, value_id, 4},
-                     {&ctx->d_target, target_mask, 32}},
-                    {{&ctx->d_bits_a, vote_bits, 32}, {&ctx->d_bits_b, nack_bits, 32}, {&ctx->d_i32_a, nack_round, 4}},
-                    message_runs(ctx, n, slot, round, true), [&](int lo, int len, const RunOpts& opts) {
-                      Batch b = batch_of(len, staged<int32_t>(ctx->d_slot, lo), staged<int32_t>(ctx->d_round, lo),
-                                         staged<int32_t>(ctx->d_value, lo),
-                                         target_mask ? staged<uint64_t>(ctx->d_target, (size_t)lo * 4) : nullptr);
-                      b.vote_bits = staged<uint64_t>(ctx->d_bits_a, (size_t)lo * 4), b.nack_round = staged<int32_t>(ctx->d_i32_a, lo);
-                      b.nack_bits = nack_bits ? staged<uint64_t>(ctx->d_bits_b, (size_t)lo * 4) : nullptr;
-                      return enqueue_phase2(ctx, b, false, opts);
-                    });
+  Batch w = batch_of(n, nullptr, nullptr, nullptr);
+  const size_t m = (size_t)n;
+  return host_runs(ctx, n,
+                   {in(w.slot, slot, m), in(w.round, round, m), in(w.value, value_id, m), opt_in(w.target, target_mask, m * 4),
+                    out(w.vote_bits, vote_bits, m * 4), nack_bits ? out(w.nack_bits, nack_bits, m * 4) : absent(w.nack_bits),
+                    out(w.nack_round, nack_round, m)},
+                   message_runs(ctx, n, slot, round, true), [&](int lo, int len, const RunOpts& opts) {
+                     Batch b = run_of(w, lo, len);
+                     return enqueue_phase2(ctx, b, false, opts);
+                   });
 }
 
 // Host-pointer K3.  Optimistic: the uploads are followed at once by the whole batch as ONE validated
@@ -2186,21 +2129,27 @@ int32_t fpx_phase2_fused(fpx_ctx* ctx, int32_t n, const int32_t* slot, const int
     rc = host_fused_staged(ctx, n, slot, round, value_id, target_mask, chosen, chosen_round, chosen_value, nack_round, &used);
     if (used) return rc;
   }
-  const std::initializer_list<HostOut> out = {
-      {&ctx->d_u8, chosen, 1}, {&ctx->d_i32_a, chosen_round, 4}, {&ctx->d_i32_b, chosen_value, 4}, {&ctx->d_i32_c, nack_round, 4}};
-  auto run = [&](int lo, int len, const RunOpts& opts) {  // (the fold of one run rides in the next run's launch)
-    return run_phase2_fused(ctx, len, staged<int32_t>(ctx->d_slot, lo), staged<int32_t>(ctx->d_round, lo), staged<int32_t>(ctx->d_value, lo),
-                            target_mask ? staged<uint64_t>(ctx->d_target, (size_t)lo * 4) : nullptr, staged<uint8_t>(ctx->d_u8, lo),
-                            staged<int32_t>(ctx->d_i32_a, lo), staged<int32_t>(ctx->d_i32_b, lo), staged<int32_t>(ctx->d_i32_c, lo), opts);
+  // the arrays are staged ONCE: both passes launch from, and download, the same layout of the staging buffer
+  Batch w = batch_of(n, nullptr, nullptr, nullptr);
+  const size_t m = (size_t)n;
+  const std::initializer_list<Staged> arrays = {
+      in(w.slot, slot, m), in(w.round, round, m), in(w.value, value_id, m), opt_in(w.target, target_mask, m * 4),
+      out(w.chosen, chosen, m), out(w.chosen_round, chosen_round, m), out(w.chosen_value, chosen_value, m),
+      out(w.nack_round, nack_round, m)};
+  const StageLayout l = lay_stage(arrays);
+  if ((rc = stage_arrays(ctx, arrays, l))) return rc;
+  auto pass = [&](auto cut) -> int {
+    int r = launch_runs(ctx, n, cut, [&](int lo, int len, const RunOpts& opts) {  // (the fold of one run rides in the next run's launch)
+      Batch b = run_of(w, lo, len);
+      return enqueue_phase2(ctx, b, true, opts);
+    });
+    if (r || (r = fetch_arrays(ctx, arrays, l))) return r;
+    return fetch_status(ctx);
   };
-  rc = host_batch(ctx, n,
-                  {{&ctx->d_slot, slot, 4}, {&ctx->d_round, round, 4}, {&ctx->d_value, value_id, 4},
-                   {&ctx->d_target, target_mask, 32}},
-                  out, nullptr, run);
+  rc = pass(nullptr);
   if (rc == FPX_EINVAL) return check_inputs(ctx, n, slot, round);  // the FIRST offender, for fpx_error_detail
   if (rc != FPX_EORDER) return rc;
-  // the host-split replay: the inputs are still in the staging buffers
-  return host_batch(ctx, n, {}, out, message_runs(ctx, n, slot, round, true), run);
+  return pass(message_runs(ctx, n, slot, round, true));  // the host-split replay: the inputs are still staged
 }
 
 int32_t fpx_phase2_fused_submit(fpx_ctx* ctx, int32_t n, const int32_t* slot, const int32_t* round, const int32_t* value_id,
@@ -2230,13 +2179,12 @@ int32_t fpx_proxy_open(fpx_ctx* ctx, int32_t n, const int32_t* slot, const int32
   if (rc) return rc;
   if (n == 0) return FPX_OK;
   if (!value_id) return FPX_EINVAL;
-  return host_batch(ctx, n, {{&ctx->d_slot, slot, 4}, {&ctx->d_round, round, 4}, {&ctx->d_value, value_id, 4}},
-                    {{&ctx->d_u8, is_new, 1}}, message_runs(ctx, n, slot, round, false), [&](int lo, int len, const RunOpts& opts) {
-                      Batch b = batch_of(len, staged<int32_t>(ctx->d_slot, lo), staged<int32_t>(ctx->d_round, lo),
-                                         staged<int32_t>(ctx->d_value, lo));
-                      b.is_new = staged<uint8_t>(ctx->d_u8, lo);
-                      return enqueue_open(ctx, b, opts);
-                    });
+  Batch w = batch_of(n, nullptr, nullptr, nullptr);
+  return host_runs(ctx, n, {in(w.slot, slot, n), in(w.round, round, n), in(w.value, value_id, n), out(w.is_new, is_new, n)},
+                   message_runs(ctx, n, slot, round, false), [&](int lo, int len, const RunOpts& opts) {
+                     Batch b = run_of(w, lo, len);
+                     return enqueue_open(ctx, b, opts);
+                   });
 }
 
 int32_t fpx_proxy_phase2b(fpx_ctx* ctx, int32_t n, const int32_t* slot, const int32_t* round, const uint64_t* vote_bits,
@@ -2246,14 +2194,15 @@ int32_t fpx_proxy_phase2b(fpx_ctx* ctx, int32_t n, const int32_t* slot, const in
   if (rc) return rc;
   if (n == 0) return FPX_OK;
   if (!vote_bits) return FPX_EINVAL;
-  return host_batch(ctx, n, {{&ctx->d_slot, slot, 4}, {&ctx->d_round, round, 4}, {&ctx->d_bits_a, vote_bits, 32}},
-                    {{&ctx->d_u8, newly_chosen, 1}, {&ctx->d_i32_a, chosen_round, 4}, {&ctx->d_i32_b, chosen_value, 4}},
-                    message_runs(ctx, n, slot, round, false), [&](int lo, int len, const RunOpts& opts) {
-                      Batch b = batch_of(len, staged<int32_t>(ctx->d_slot, lo), staged<int32_t>(ctx->d_round, lo), nullptr);
-                      b.vote_bits = staged<uint64_t>(ctx->d_bits_a, (size_t)lo * 4), b.chosen = staged<uint8_t>(ctx->d_u8, lo);
-                      b.chosen_round = staged<int32_t>(ctx->d_i32_a, lo), b.chosen_value = staged<int32_t>(ctx->d_i32_b, lo);
-                      return enqueue_tally(ctx, b, opts);
-                    });
+  Batch w = batch_of(n, nullptr, nullptr, nullptr);
+  const size_t m = (size_t)n;
+  return host_runs(ctx, n,
+                   {in(w.slot, slot, m), in(w.round, round, m), in(w.vote_bits, vote_bits, m * 4), out(w.chosen, newly_chosen, m),
+                    out(w.chosen_round, chosen_round, m), out(w.chosen_value, chosen_value, m)},
+                   message_runs(ctx, n, slot, round, false), [&](int lo, int len, const RunOpts& opts) {
+                     Batch b = run_of(w, lo, len);
+                     return enqueue_tally(ctx, b, opts);
+                   });
 }
 
 // Phase1a on device-resident arguments, asynchronous: d_target_mask 4 words or NULL, d_outp / d_outn 4 words each = promised
@@ -2680,14 +2629,16 @@ static int32_t host_ranges(fpx_ctx* ctx, int mode, int32_t n, const int32_t* sta
   const bool tally = mode == RANGES_TALLY;
   if (!start || !end || !round || (tally && !votes_in)) return FPX_EINVAL;
   if ((rc = check_ranges(ctx, n, start, end, round))) return rc;
-  const size_t per = (size_t)ctx->g.num_groups * 4;
-  RangeStage& rs = ctx->rng;
-  return host_batch(
+  // per range: int32 start / end / round / entry / nack_round, u8 is_new / chosen, and num_groups x 4 words of target /
+  // vote / nack bits; the votes are ONE array that goes up (the tally's input) and comes down
+  const size_t per = (size_t)ctx->g.num_groups * 4, m = (size_t)n;
+  RangeBatch w;
+  memset(&w, 0, sizeof(w));
+  return host_runs(
       ctx, n,
-      {{&rs.start, start, 4}, {&rs.end, end, 4}, {&rs.round, round, 4}, {&rs.target, target_masks, per * 8},
-       {&rs.votes, votes_in, per * 8}},
-      {{&rs.votes, vote_bits, per * 8}, {&rs.nacks, nack_bits, per * 8}, {&rs.nack_round, nack_round, 4},
-       {&rs.is_new, is_new, 1}, {&rs.chosen, chosen, 1}, {&rs.entry, nullptr, 4}},
+      {in(w.start, start, m), in(w.end, end, m), in(w.round, round, m), opt_in(w.target, target_masks, m * per),
+       inout(w.vote_bits, votes_in, vote_bits, m * per), out(w.nack_bits, nack_bits, m * per), out(w.nack_round, nack_round, m),
+       out(w.is_new, is_new, m), out(w.chosen, chosen, m), scratch(w.entry, m)},
       [&](std::vector<int>* cuts) {
         // one round per leader group in every run: the acceptors' scalar needs it, and the table insert relies on
         // "same (start, end) in one launch => same key"
@@ -2695,14 +2646,10 @@ static int32_t host_ranges(fpx_ctx* ctx, int mode, int32_t n, const int32_t* sta
         return FPX_OK;
       },
       [&](int lo, int len, const RunOpts& opts) {
-        RangeBatch b;
-        memset(&b, 0, sizeof(b));
-        b.n = len, b.start = staged<int32_t>(rs.start, lo), b.end = staged<int32_t>(rs.end, lo);
-        b.round = staged<int32_t>(rs.round, lo);
-        b.target = target_masks ? staged<uint64_t>(rs.target, lo * per) : nullptr;
-        b.entry = staged<int32_t>(rs.entry, lo), b.nack_round = staged<int32_t>(rs.nack_round, lo);
-        b.vote_bits = staged<uint64_t>(rs.votes, lo * per), b.nack_bits = staged<uint64_t>(rs.nacks, lo * per);
-        b.is_new = staged<uint8_t>(rs.is_new, lo), b.chosen = staged<uint8_t>(rs.chosen, lo);
+        RangeBatch b = w;
+        b.n = len, b.start += lo, b.end += lo, b.round += lo, b.entry += lo, b.nack_round += lo, b.is_new += lo, b.chosen += lo;
+        if (b.target) b.target += lo * per;
+        b.vote_bits += lo * per, b.nack_bits += lo * per;
         if (tally) b.votes_in = b.vote_bits;
         return enqueue_ranges(ctx, b, mode, opts, ctx->stream);
       });
@@ -2794,18 +2741,16 @@ int32_t fpx_mencius_proxy_phase2b_msgs(fpx_ctx* ctx, int32_t n, const int32_t* k
   if (n >= (1 << 30)) return FPX_EINVAL;
   if (n == 0) return FPX_OK;
   if (!acceptor_index || !slot || !round) return FPX_EINVAL;
-  return host_batch(ctx, n,
-                    {{&ctx->d_value, kind, 4}, {&ctx->d_target, group_index, 4}, {&ctx->d_i32_c, acceptor_index, 4},
-                     {&ctx->d_slot, slot, 4}, {&ctx->mm_end, slot_end, 4}, {&ctx->d_round, round, 4}},
-                    {{&ctx->d_u8, newly_chosen, 1}, {&ctx->d_i32_a, chosen_round, 4}, {&ctx->d_i32_b, chosen_value, 4}},
-                    nullptr, [&](int, int, const RunOpts&) {
-                      return fpx_mencius_proxy_phase2b_msgs_dev(
-                          ctx, n, kind ? (const int32_t*)ctx->d_value.p : nullptr,
-                          group_index ? (const int32_t*)ctx->d_target.p : nullptr, (const int32_t*)ctx->d_i32_c.p,
-                          (const int32_t*)ctx->d_slot.p, slot_end ? (const int32_t*)ctx->mm_end.p : nullptr,
-                          (const int32_t*)ctx->d_round.p, (uint8_t*)ctx->d_u8.p, (int32_t*)ctx->d_i32_a.p,
-                          (int32_t*)ctx->d_i32_b.p);
-                    });
+  int32_t *d_kind, *d_group, *d_acceptor, *d_slot, *d_end, *d_round, *d_cround, *d_cvalue;
+  uint8_t* d_chosen;
+  return host_runs(ctx, n,
+                   {opt_in(d_kind, kind, n), opt_in(d_group, group_index, n), in(d_acceptor, acceptor_index, n), in(d_slot, slot, n),
+                    opt_in(d_end, slot_end, n), in(d_round, round, n), out(d_chosen, newly_chosen, n),
+                    out(d_cround, chosen_round, n), out(d_cvalue, chosen_value, n)},
+                   nullptr, [&](int, int, const RunOpts&) {
+                     return fpx_mencius_proxy_phase2b_msgs_dev(ctx, n, d_kind, d_group, d_acceptor, d_slot, d_end, d_round, d_chosen,
+                                                               d_cround, d_cvalue);
+                   });
 }
 
 // One tick of a Mencius proxy leader among remote acceptors, decoded arrays to records, through the staging driver as ONE
@@ -2823,35 +2768,27 @@ int32_t fpx_mencius_phase2b_tick(fpx_ctx* ctx, int32_t n, const int32_t* kind, c
   *out_count = 0;
   if (n == 0) return FPX_OK;
   if (!acceptor_index || !slot || !round) return FPX_EINVAL;
-  for (DevBuf* b : {&ctx->d_u8, &ctx->d_i32_a, &ctx->d_i32_b})
-    if ((rc = grow(ctx, b, (size_t)n * 4))) return rc;
   MenciusEmit m;
   memset(&m, 0, sizeof(m));
   MsgCompact& c = m.c;
   c.n = n, c.nblk = (n + 255) / 256, c.cap = out_cap;
-  if ((rc = grow(ctx, &ctx->m_blk, (size_t)c.nblk * 4))) return rc;
   int64_t totals[2] = {0, 0};
-  const size_t rec = (size_t)out_cap * 4;
-  rc = host_batch(
+  int32_t *d_kind, *d_group, *d_acceptor, *d_slot, *d_end, *d_round, *d_cround, *d_cvalue;
+  uint8_t* d_chosen;
+  const size_t msgs = (size_t)n, cap = (size_t)out_cap;
+  rc = host_runs(
       ctx, n,
-      {{&ctx->d_value, kind, 4}, {&ctx->d_target, group_index, 4}, {&ctx->d_i32_c, acceptor_index, 4},
-       {&ctx->d_slot, slot, 4}, {&ctx->mm_end, slot_end, 4}, {&ctx->d_round, round, 4}},
-      {{&ctx->mm_rec[0], out_kind, 0, rec}, {&ctx->mm_rec[1], out_slot, 0, rec}, {&ctx->mm_rec[2], out_slot_end, 0, rec},
-       {&ctx->mm_rec[3], out_round, 0, rec}, {&ctx->mm_rec[4], out_value_id, 0, rec}, {&ctx->w_tot, totals, 0, 16}},
+      {opt_in(d_kind, kind, msgs), opt_in(d_group, group_index, msgs), in(d_acceptor, acceptor_index, msgs), in(d_slot, slot, msgs),
+       opt_in(d_end, slot_end, msgs), in(d_round, round, msgs), out(m.out_kind, out_kind, cap), out(c.out_slot, out_slot, cap),
+       out(m.out_slot_end, out_slot_end, cap), out(c.out_round, out_round, cap), out(c.out_value, out_value_id, cap),
+       out(c.totals, totals, 2), scratch(d_chosen, msgs), scratch(d_cround, msgs), scratch(d_cvalue, msgs),
+       scratch(c.blk, (size_t)c.nblk)},
       nullptr, [&](int, int, const RunOpts&) {
-        const int32_t* d_kind = kind ? (const int32_t*)ctx->d_value.p : nullptr;
-        const int32_t* d_end = slot_end ? (const int32_t*)ctx->mm_end.p : nullptr;
-        int r = fpx_mencius_proxy_phase2b_msgs_dev(ctx, n, d_kind, group_index ? (const int32_t*)ctx->d_target.p : nullptr,
-                                                   (const int32_t*)ctx->d_i32_c.p, (const int32_t*)ctx->d_slot.p, d_end,
-                                                   (const int32_t*)ctx->d_round.p, (uint8_t*)ctx->d_u8.p,
-                                                   (int32_t*)ctx->d_i32_a.p, (int32_t*)ctx->d_i32_b.p);
+        int r = fpx_mencius_proxy_phase2b_msgs_dev(ctx, n, d_kind, d_group, d_acceptor, d_slot, d_end, d_round, d_chosen, d_cround,
+                                                   d_cvalue);
         if (r) return r;
-        c.chosen = (const uint8_t*)ctx->d_u8.p, c.slot = (const int32_t*)ctx->d_slot.p;
-        c.chosen_round = (const int32_t*)ctx->d_i32_a.p, c.chosen_value = (const int32_t*)ctx->d_i32_b.p;
-        c.blk = (int32_t*)ctx->m_blk.p, c.totals = (int64_t*)ctx->w_tot.p;
-        c.out_slot = (int32_t*)ctx->mm_rec[1].p, c.out_round = (int32_t*)ctx->mm_rec[3].p, c.out_value = (int32_t*)ctx->mm_rec[4].p;
+        c.chosen = d_chosen, c.slot = d_slot, c.chosen_round = d_cround, c.chosen_value = d_cvalue;
         m.kind = d_kind, m.slot_end = d_end, m.phase2b = FPX_WIRE_PHASE2B, m.range_kind = FPX_WIRE_PHASE2B_NOOP_RANGE;
-        m.out_kind = (int32_t*)ctx->mm_rec[0].p, m.out_slot_end = (int32_t*)ctx->mm_rec[2].p;
         hipLaunchKernelGGL(k_msgs_count, dim3(c.nblk), dim3(256), 0, ctx->stream, ctx->st, c);
         hipLaunchKernelGGL(k_msgs_scan, dim3(1), dim3(1024), 0, ctx->stream, ctx->st, c);
         hipLaunchKernelGGL(k_mm_emit, dim3(c.nblk), dim3(256), 0, ctx->stream, ctx->st, m);
@@ -2937,15 +2874,14 @@ int32_t fpx_replica_chosen(fpx_ctx* ctx, int32_t n, const int32_t* slot, const i
   for (int i = 0; i < n; ++i)
     if (!mask || mask[i]) s.push_back(slot[i]), v.push_back(value_id[i]);
   const int m = (int)s.size();
-  const int rc = host_batch(
-      ctx, m, {{&ctx->d_slot, s.data(), 4}, {&ctx->d_value, v.data(), 4}}, {},
+  int32_t *d_slot, *d_value;
+  const int rc = host_runs(
+      ctx, m, {in(d_slot, s.data(), (size_t)m), in(d_value, v.data(), (size_t)m)},
       [&](std::vector<int>* cuts) {
         split_runs(ctx, m, s.data(), nullptr, false, cuts);
         return FPX_OK;
       },
-      [&](int lo, int len, const RunOpts& opts) {
-        return run_replica_chosen(ctx, len, staged<int32_t>(ctx->d_slot, lo), staged<int32_t>(ctx->d_value, lo), nullptr, opts);
-      });
+      [&](int lo, int len, const RunOpts& opts) { return run_replica_chosen(ctx, len, d_slot + lo, d_value + lo, nullptr, opts); });
   if (rc == FPX_EHIP || rc == FPX_ENOMEM) return rc;  // (a HIP failure: no scalars to report)
   const int st = fpx_replica_state(ctx, executed_watermark, num_chosen);
   return st ? st : rc;
@@ -3031,15 +2967,13 @@ int32_t fpx_replica_chosen_msgs(fpx_ctx* ctx, int32_t n, const int32_t* kind, co
   DeviceGuard _dg(ctx);
   if (!ctx || n < 0 || n >= (1 << 30) || (n > 0 && (!kind || !slot || !slot_end || !value_id))) return FPX_EINVAL;
   int rc = FPX_OK;
+  int32_t *d_kind, *d_slot, *d_end, *d_value;
+  uint8_t* d_mask;
   if (n > 0)
-    rc = host_batch(ctx, n,
-                    {{&ctx->d_i32_a, kind, 4}, {&ctx->d_slot, slot, 4}, {&ctx->d_i32_b, slot_end, 4},
-                     {&ctx->d_value, value_id, 4}, {&ctx->d_u8, mask, 1}},
-                    {}, nullptr, [&](int, int, const RunOpts&) {
-                      return fpx_replica_chosen_msgs_dev(ctx, n, (const int32_t*)ctx->d_i32_a.p, (const int32_t*)ctx->d_slot.p,
-                                                         (const int32_t*)ctx->d_i32_b.p, (const int32_t*)ctx->d_value.p,
-                                                         mask ? (const uint8_t*)ctx->d_u8.p : nullptr);
-                    });
+    rc = host_runs(ctx, n, {in(d_kind, kind, n), in(d_slot, slot, n), in(d_end, slot_end, n), in(d_value, value_id, n), opt_in(d_mask, mask, n)},
+                   nullptr, [&](int, int, const RunOpts&) {
+                     return fpx_replica_chosen_msgs_dev(ctx, n, d_kind, d_slot, d_end, d_value, d_mask);
+                   });
   if (rc == FPX_EHIP || rc == FPX_ENOMEM) return rc;  // (a HIP failure: no scalars to report)
   const int st = fpx_replica_state(ctx, executed_watermark, num_chosen);
   return st ? st : rc;
@@ -3107,25 +3041,15 @@ int32_t fpx_replica_inbox(fpx_ctx* ctx, int32_t n, const int32_t* kind, const in
   if (ctx->g.num_leader_groups > 1) return FPX_EINVAL;
   if (n > 0 && (!exec_count || !reply_slot || !order)) return FPX_EINVAL;
   if (!counts) return FPX_EINVAL;
-  int rc;
-  const size_t cap = (size_t)std::max(n, 1) * 4;
-  for (int a = 0; a < 3; ++a)
-    if ((rc = grow(ctx, &ctx->ri_out[a], cap))) return rc;
-  if ((rc = grow(ctx, &ctx->ri_out[3], 16))) return rc;
-  rc = host_batch(ctx, n, {{&ctx->d_i32_a, kind, 4}, {&ctx->d_slot, slot, 4}, {&ctx->d_value, value_id, 4}, {&ctx->d_u8, mask, 1}},
-                  {}, nullptr, [&](int, int, const RunOpts&) {
-                    return fpx_replica_inbox_dev(ctx, n, (const int32_t*)ctx->d_i32_a.p, (const int32_t*)ctx->d_slot.p,
-                                                 (const int32_t*)ctx->d_value.p, mask ? (const uint8_t*)ctx->d_u8.p : nullptr,
-                                                 (int32_t*)ctx->ri_out[0].p, (int32_t*)ctx->ri_out[1].p,
-                                                 (int32_t*)ctx->ri_out[2].p, (int32_t*)ctx->ri_out[3].p);
-                  });
+  int32_t *d_kind, *d_slot, *d_value, *d_exec, *d_reply, *d_order, *d_counts;
+  uint8_t* d_mask;
+  const int rc = host_runs(ctx, n,
+                           {in(d_kind, kind, n), in(d_slot, slot, n), in(d_value, value_id, n), opt_in(d_mask, mask, n),
+                            held(d_exec, exec_count, n), held(d_reply, reply_slot, n), held(d_order, order, n), held(d_counts, counts, 4)},
+                           nullptr, [&](int, int, const RunOpts&) {
+                             return fpx_replica_inbox_dev(ctx, n, d_kind, d_slot, d_value, d_mask, d_exec, d_reply, d_order, d_counts);
+                           });
   if (rc == FPX_EHIP || rc == FPX_ENOMEM) return rc;  // (a HIP failure: no scalars to report)
-  if (rc == FPX_OK) {
-    int32_t* outs[3] = {exec_count, reply_slot, order};
-    for (int a = 0; a < 3; ++a)
-      if (n > 0) HIPCHK(ctx, hipMemcpyAsync(outs[a], ctx->ri_out[a].p, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(counts, ctx->ri_out[3].p, 16, hipMemcpyDeviceToHost, ctx->stream));
-  }
   const int st = fpx_replica_state(ctx, executed_watermark, num_chosen);  // (synchronises the stream)
   return st ? st : rc;
 }
@@ -3214,23 +3138,15 @@ int32_t fpx_acceptor_inbox(fpx_ctx* ctx, int32_t n, const int32_t* kind, const i
   if ((rc = acceptor_inbox_ctx_ok(ctx, n, grid_cols))) return rc;
   if (n == 0) return FPX_OK;
   if (!kind || !acceptor_index || !slot || !round || !value_id) return FPX_EINVAL;
-  for (int a = 0; a < 2; ++a)
-    if ((rc = grow(ctx, &ctx->ai_out[a], (size_t)n * 4))) return rc;
-  rc = host_batch(ctx, n,
-                  {{&ctx->d_i32_a, kind, 4}, {&ctx->d_target, group_index, 4}, {&ctx->d_i32_c, acceptor_index, 4},
-                   {&ctx->d_slot, slot, 4}, {&ctx->d_round, round, 4}, {&ctx->d_value, value_id, 4}},
-                  {}, nullptr, [&](int, int, const RunOpts&) {
-                    return fpx_acceptor_inbox_dev(
-                        ctx, n, (const int32_t*)ctx->d_i32_a.p, group_index ? (const int32_t*)ctx->d_target.p : nullptr,
-                        (const int32_t*)ctx->d_i32_c.p, (const int32_t*)ctx->d_slot.p, (const int32_t*)ctx->d_round.p,
-                        (const int32_t*)ctx->d_value.p, grid_cols, reply_kind ? (int32_t*)ctx->ai_out[0].p : nullptr,
-                        reply_value ? (int32_t*)ctx->ai_out[1].p : nullptr);
-                  });
-  if (rc != FPX_OK) return rc;
-  if (reply_kind) HIPCHK(ctx, hipMemcpyAsync(reply_kind, ctx->ai_out[0].p, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
-  if (reply_value) HIPCHK(ctx, hipMemcpyAsync(reply_value, ctx->ai_out[1].p, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-  return FPX_OK;
+  int32_t *d_kind, *d_group, *d_acceptor, *d_slot, *d_round, *d_value, *d_rkind, *d_rvalue;
+  return host_runs(ctx, n,
+                   {in(d_kind, kind, n), opt_in(d_group, group_index, n), in(d_acceptor, acceptor_index, n), in(d_slot, slot, n),
+                    in(d_round, round, n), in(d_value, value_id, n), reply_kind ? held(d_rkind, reply_kind, n) : absent(d_rkind),
+                    reply_value ? held(d_rvalue, reply_value, n) : absent(d_rvalue)},
+                   nullptr, [&](int, int, const RunOpts&) {
+                     return fpx_acceptor_inbox_dev(ctx, n, d_kind, d_group, d_acceptor, d_slot, d_round, d_value, grid_cols, d_rkind,
+                                                   d_rvalue);
+                   });
 }
 
 // mencius.Acceptor's inbox for a burst of per-acceptor messages in delivery order, Phase2aNoopRanges among them
@@ -3295,24 +3211,16 @@ int32_t fpx_mencius_acceptor_inbox(fpx_ctx* ctx, int32_t n, const int32_t* kind,
   if ((rc = mencius_acceptor_inbox_ctx_ok(ctx, n))) return rc;
   if (n == 0) return FPX_OK;
   if (!kind || !acceptor_index || !slot || !slot_end || !round || !value_id) return FPX_EINVAL;
-  for (int a = 0; a < 2; ++a)
-    if ((rc = grow(ctx, &ctx->ai_out[a], (size_t)n * 4))) return rc;
-  rc = host_batch(ctx, n,
-                  {{&ctx->d_i32_a, kind, 4}, {&ctx->d_target, group_index, 4}, {&ctx->d_i32_c, acceptor_index, 4},
-                   {&ctx->d_slot, slot, 4}, {&ctx->d_i32_b, slot_end, 4}, {&ctx->d_round, round, 4},
-                   {&ctx->d_value, value_id, 4}},
-                  {}, nullptr, [&](int, int, const RunOpts&) {
-                    return fpx_mencius_acceptor_inbox_dev(
-                        ctx, n, (const int32_t*)ctx->d_i32_a.p, group_index ? (const int32_t*)ctx->d_target.p : nullptr,
-                        (const int32_t*)ctx->d_i32_c.p, (const int32_t*)ctx->d_slot.p, (const int32_t*)ctx->d_i32_b.p,
-                        (const int32_t*)ctx->d_round.p, (const int32_t*)ctx->d_value.p,
-                        reply_kind ? (int32_t*)ctx->ai_out[0].p : nullptr, reply_value ? (int32_t*)ctx->ai_out[1].p : nullptr);
-                  });
-  if (rc != FPX_OK) return rc;
-  if (reply_kind) HIPCHK(ctx, hipMemcpyAsync(reply_kind, ctx->ai_out[0].p, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
-  if (reply_value) HIPCHK(ctx, hipMemcpyAsync(reply_value, ctx->ai_out[1].p, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-  return FPX_OK;
+  int32_t *d_kind, *d_group, *d_acceptor, *d_slot, *d_end, *d_round, *d_value, *d_rkind, *d_rvalue;
+  return host_runs(ctx, n,
+                   {in(d_kind, kind, n), opt_in(d_group, group_index, n), in(d_acceptor, acceptor_index, n), in(d_slot, slot, n),
+                    in(d_end, slot_end, n), in(d_round, round, n), in(d_value, value_id, n),
+                    reply_kind ? held(d_rkind, reply_kind, n) : absent(d_rkind),
+                    reply_value ? held(d_rvalue, reply_value, n) : absent(d_rvalue)},
+                   nullptr, [&](int, int, const RunOpts&) {
+                     return fpx_mencius_acceptor_inbox_dev(ctx, n, d_kind, d_group, d_acceptor, d_slot, d_end, d_round, d_value,
+                                                           d_rkind, d_rvalue);
+                   });
 }
 
 int32_t fpx_replica_read_log(fpx_ctx* ctx, int32_t first, int32_t count, int32_t* values, uint8_t* present) {
@@ -3331,9 +3239,9 @@ int32_t fpx_leader_phase1b_scan(fpx_ctx* ctx, int32_t chosen_watermark, const ui
   if (!ctx || !quorum_masks || chosen_watermark < 0 || cap < 0) return FPX_EINVAL;
   const int ng = ctx->g.ngroups;
   int rc;
-  if ((rc = grow(ctx, &ctx->d_target, (size_t)ng * 32 + 64))) return rc;
-  uint64_t* d_q = (uint64_t*)ctx->d_target.p;
-  int32_t* d_max = (int32_t*)(d_q + (size_t)ng * 4);
+  if ((rc = grow(ctx, &ctx->d_scratch, (size_t)ng * 32 + 64 + (size_t)cap * 8))) return rc;
+  uint64_t* d_q = (uint64_t*)ctx->d_scratch.p;
+  int32_t *d_max = (int32_t*)(d_q + (size_t)ng * 4), *d_sr = d_max + 16, *d_sv = d_sr + cap;
   HIPCHK(ctx, hipMemcpyAsync(d_q, quorum_masks, (size_t)ng * 32, hipMemcpyHostToDevice, ctx->stream));
   HIPCHK(ctx, hipMemsetAsync(d_max, 0xFF, 4, ctx->stream));
   const int ntab = ng * ctx->g.R;
@@ -3348,9 +3256,6 @@ int32_t fpx_leader_phase1b_scan(fpx_ctx* ctx, int32_t chosen_watermark, const ui
   const int64_t want = (int64_t)hmax - chosen_watermark + 1;
   const int count = (int)std::max<int64_t>(0, std::min<int64_t>(want, cap));
   if (count == 0) return FPX_OK;
-  if ((rc = grow(ctx, &ctx->d_i32_a, (size_t)count * 4))) return rc;
-  if ((rc = grow(ctx, &ctx->d_i32_b, (size_t)count * 4))) return rc;
-  int32_t *d_sr = (int32_t*)ctx->d_i32_a.p, *d_sv = (int32_t*)ctx->d_i32_b.p;
   switch (ctx->lanes_per_slot) {
     case 1: launch_p1b<1>(ctx, d_q, chosen_watermark, count, d_sr, d_sv); break;
     case 2: launch_p1b<2>(ctx, d_q, chosen_watermark, count, d_sr, d_sv); break;
@@ -3361,8 +3266,8 @@ int32_t fpx_leader_phase1b_scan(fpx_ctx* ctx, int32_t chosen_watermark, const ui
     default: launch_p1b<64>(ctx, d_q, chosen_watermark, count, d_sr, d_sv); break;
   }
   if ((rc = launch_check(ctx))) return rc;
-  if ((rc = d2h(ctx, safe_round, ctx->d_i32_a, (size_t)count))) return rc;
-  if ((rc = d2h(ctx, safe_value, ctx->d_i32_b, (size_t)count))) return rc;
+  if (safe_round) HIPCHK(ctx, hipMemcpyAsync(safe_round, d_sr, (size_t)count * 4, hipMemcpyDeviceToHost, ctx->stream));
+  if (safe_value) HIPCHK(ctx, hipMemcpyAsync(safe_value, d_sv, (size_t)count * 4, hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
   return FPX_OK;
 }
@@ -3432,26 +3337,24 @@ int32_t fpx_leader_phase1b_msgs(fpx_ctx* ctx, int32_t round, int32_t chosen_wate
   }
   if (total > 0 && (!info_slot || !info_vote_round || !info_value_id)) return FPX_EINVAL;
   DeviceGuard _dg(ctx->cfg.device);
-  DevBuf* s = ctx->p1m_stage;
-  const size_t rec = (size_t)total * 4, outb = (size_t)cap * 4, heldb = (size_t)ctx->g.ngroups * 32;
+  const size_t m = (size_t)n, rec = (size_t)total, outs = (size_t)cap, heldw = (size_t)ctx->g.ngroups * 4;
   const int64_t zero = 0;
   int64_t res[8];
-  const int rc = host_batch(
+  int32_t *d_kind, *d_msg_round, *d_group, *d_acceptor, *d_is, *d_ir, *d_iv, *d_out_slot, *d_sr, *d_sv;
+  int64_t *d_off, *d_res;
+  uint64_t* d_held;
+  // (n == 0: one zero offset goes up; -1 in every result word: "not written" -- a refused call writes none, an incomplete
+  // one two)
+  const int rc = host_runs(
       ctx, n,
-      {{&s[0], kind, 4}, {&s[1], msg_round, 4}, {&s[2], group_index, 4}, {&s[3], acceptor_index, 4},
-       {&s[4], n > 0 ? offsets : &zero, 8, 8}, {&s[5], info_slot, 0, rec}, {&s[6], info_vote_round, 0, rec},
-       {&s[7], info_value_id, 0, rec}},
-      {{&s[8], nullptr, 0, outb}, {&s[9], nullptr, 0, outb}, {&s[10], nullptr, 0, outb}, {&s[11], res, 0, sizeof(res)},
-       {&s[12], nullptr, 0, heldb}},
-      nullptr, [&](int, int, const RunOpts&) -> int {
-        // -1 in every result word: "not written" (a refused call writes none, an incomplete one two)
-        HIPCHK(ctx, hipMemsetAsync(s[11].p, 0xFF, sizeof(res), ctx->stream));
-        return fpx_leader_phase1b_msgs_dev(ctx, round, chosen_watermark, leader_group, recover_slot, flags, n,
-                                           kind ? (const int32_t*)s[0].p : nullptr, (const int32_t*)s[1].p,
-                                           group_index ? (const int32_t*)s[2].p : nullptr, (const int32_t*)s[3].p,
-                                           (const int64_t*)s[4].p, (const int32_t*)s[5].p, (const int32_t*)s[6].p,
-                                           (const int32_t*)s[7].p, grid_cols, cap, (int32_t*)s[8].p, (int32_t*)s[9].p,
-                                           (int32_t*)s[10].p, (int64_t*)s[11].p, (uint64_t*)s[12].p);
+      {opt_in(d_kind, kind, m), in(d_msg_round, msg_round, m), opt_in(d_group, group_index, m), in(d_acceptor, acceptor_index, m),
+       in(d_off, n > 0 ? offsets : &zero, m + 1), in(d_is, info_slot, rec), in(d_ir, info_vote_round, rec),
+       in(d_iv, info_value_id, rec), scratch(d_out_slot, outs), scratch(d_sr, outs), scratch(d_sv, outs), out(d_res, res, 8, 0xFF),
+       scratch(d_held, heldw)},
+      nullptr, [&](int, int, const RunOpts&) {
+        return fpx_leader_phase1b_msgs_dev(ctx, round, chosen_watermark, leader_group, recover_slot, flags, n, d_kind, d_msg_round,
+                                           d_group, d_acceptor, d_off, d_is, d_ir, d_iv, grid_cols, cap, d_out_slot, d_sr, d_sv,
+                                           d_res, d_held);
       });
   if (rc == FPX_EHIP || rc == FPX_ENOMEM || rc == FPX_EINVAL) return rc;
   // what the device wrote, and no more, reaches the caller's arrays
@@ -3460,11 +3363,12 @@ int32_t fpx_leader_phase1b_msgs(fpx_ctx* ctx, int32_t round, int32_t chosen_wate
     if (res[1] == -1) result[1] = -1;
   } else if (res[0] == 1) {
     for (int w = 0; w < 6; ++w) result[w] = res[w];
-    const size_t wr = (size_t)res[5];
-    int rc2;
-    if ((rc2 = d2h(ctx, out_slot, s[8], wr)) || (rc2 = d2h(ctx, safe_round, s[9], wr)) || (rc2 = d2h(ctx, safe_value, s[10], wr)))
-      return rc2;
-    if ((rc2 = d2h(ctx, held_bits, s[12], (size_t)ctx->g.ngroups * 4))) return rc2;
+    // the first res[5] records and the held bits, from the staging buffer, which keeps them until the next call
+    const size_t wr = (size_t)res[5] * 4;
+    const std::pair<void*, const void*> down[3] = {{out_slot, d_out_slot}, {safe_round, d_sr}, {safe_value, d_sv}};
+    for (const auto& a : down)
+      if (a.first && wr) HIPCHK(ctx, hipMemcpyAsync(a.first, a.second, wr, hipMemcpyDeviceToHost, ctx->stream));
+    if (held_bits) HIPCHK(ctx, hipMemcpyAsync(held_bits, d_held, heldw * 8, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
   }
   return rc;
@@ -3615,9 +3519,7 @@ int32_t fpx_acceptor_phase1b_info_all(fpx_ctx* ctx, int32_t chosen_watermark, co
                                       int64_t* offsets, int32_t* slot, int32_t* vote_round, int32_t* vote_value, int64_t* count) {
   if (!p1i_args_ok(ctx, cap, offsets, slot, vote_round, vote_value, count)) return FPX_EINVAL;
   DeviceGuard _dg(ctx->cfg.device);
-  int rc;
-  if ((rc = grow(ctx, &ctx->d_bits_a, (size_t)ctx->g.ngroups * 32))) return rc;  // (host_batch stages only what it uploads)
-  return host_p1i(ctx, chosen_watermark, acceptor_masks, false, cap, offsets, slot, vote_round, vote_value, count);
+  return host_p1i(ctx, chosen_watermark, acceptor_masks, nullptr, cap, offsets, slot, vote_round, vote_value, count);
 }
 
 int32_t fpx_acceptor_phase1(fpx_ctx* ctx, int32_t round, int32_t chosen_watermark, const uint64_t* target_masks,
@@ -3628,10 +3530,9 @@ int32_t fpx_acceptor_phase1(fpx_ctx* ctx, int32_t round, int32_t chosen_watermar
   const int ng = ctx->g.ngroups;
   const size_t words = (size_t)ng * 4;
   int rc;
-  // d_bits_a: the promised bits (the info pass's masks); d_bits_b: the nack bits, then the targets
-  if ((rc = grow(ctx, &ctx->d_bits_a, words * 8))) return rc;
-  if ((rc = grow(ctx, &ctx->d_bits_b, 2 * words * 8))) return rc;
-  uint64_t *d_prom = (uint64_t*)ctx->d_bits_a.p, *d_nack = (uint64_t*)ctx->d_bits_b.p, *d_tgt = d_nack + words;
+  // the promised bits (the info pass's masks), the nack bits, the targets: outside the staging buffer, which is host_p1i's
+  if ((rc = grow(ctx, &ctx->d_scratch, 3 * words * 8))) return rc;
+  uint64_t *d_prom = (uint64_t*)ctx->d_scratch.p, *d_nack = d_prom + words, *d_tgt = d_nack + words;
   if (target_masks) HIPCHK(ctx, hipMemcpyAsync(d_tgt, target_masks, words * 8, hipMemcpyHostToDevice, ctx->stream));
   // the reply bits of the groups nobody addressed (the Phase1a kernels write an addressed group's in full)
   HIPCHK(ctx, hipMemsetAsync(d_prom, 0, words * 8, ctx->stream));
@@ -3647,8 +3548,8 @@ int32_t fpx_acceptor_phase1(fpx_ctx* ctx, int32_t round, int32_t chosen_watermar
                               d_prom + (size_t)grp * 4, d_nack + (size_t)grp * 4)))
       return rc;
   }
-  rc = host_p1i(ctx, chosen_watermark, d_prom, true, cap, offsets, slot, vote_round, vote_value, count);  // (synchronises)
-  // the reply bits last, straight into the caller's arrays (host_p1i leaves d_bits_a / d_bits_b alone)
+  rc = host_p1i(ctx, chosen_watermark, nullptr, d_prom, cap, offsets, slot, vote_round, vote_value, count);  // (synchronises)
+  // the reply bits last, straight into the caller's arrays
   if (promised_bits) HIPCHK(ctx, hipMemcpyAsync(promised_bits, d_prom, words * 8, hipMemcpyDeviceToHost, ctx->stream));
   if (nack_bits) HIPCHK(ctx, hipMemcpyAsync(nack_bits, d_nack, words * 8, hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));

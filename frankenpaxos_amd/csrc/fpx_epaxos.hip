@@ -1393,9 +1393,7 @@ struct fpx_epx {
   hipStream_t stream = nullptr, own_stream = nullptr;
   int last_hip = 0;
   DevBuf kv, kv2, seg, conf, tmp, tick, fusedb, metab;
-  DevBuf stage;                                            // the arrays of a host-pointer call (host_call)
-  char* held = nullptr;                                    // its held outputs on the host: pageable, grows, never shrinks
-  size_t held_cap = 0;
+  HostStage stage;                                         // the arrays of a host-pointer call and its held outputs (host_call)
   DevBuf mk_misc, mk_rec, mk_pair, mk_pconf;               // multi-key commands (fpx_epaxos_mk.hpp)
   int32_t* mk_host = nullptr;                              // page-locked: k_mk_total's line
   DevBuf p_fast, p_deps, p_ldeps, p_own;   // the four output arrays when a packed tick goes the first form's way
@@ -1455,121 +1453,17 @@ int packed_fallback(fpx_epx* e, int m, uint8_t** fast, int32_t** deps, int32_t**
   return FPX_OK;
 }
 
-// ---- host-pointer calls: stage, launch, copy back ------------------------------------------------------------------
-// An array of a host call, carved out of the context's staging buffer: uploaded from `src` when that is not NULL,
-// downloaded to `dst` when that is not NULL, and starting as `fill` bytes (0 or 0xFF; NO_FILL: whatever the buffer held).
-// It is staged either way: an input or output the caller leaves out is device scratch.  (But opt_in.)
-constexpr int NO_FILL = -1;
-constexpr size_t STAGE_ALIGN = 256;  // (what hipMalloc guarantees)
-struct Staged {
-  void* slot;                   // the caller's T*, pointed at the array
-  void (*place)(void*, char*);
-  const void* src;
-  void* dst;
-  size_t bytes;
-  int fill;
-  bool hold = false;                // held(): dst gets the array only once the call's status is known
-  const void* length = nullptr;     // held_first(): the slot of the held word that counts the elements dst gets
-  size_t span() const { return (bytes + STAGE_ALIGN - 1) & ~(STAGE_ALIGN - 1); }
-  size_t host_span() const { return hold ? (bytes + 7) & ~(size_t)7 : 0; }
+// ---- host-pointer calls: the shared driver (fpx_host.hpp), ended the way of this context -------------------------------
+// fpx_epx_sync synchronises once and returns the device's status; the held outputs go to the caller when the call ends in
+// FPX_OK or FPX_EFATAL_PROTOCOL
+struct EpxEnd {
+  fpx_epx* e;
+  int operator()() const { return fpx_epx_sync(e); }
+  static bool applied(int rc) { return rc == FPX_OK || rc == FPX_EFATAL_PROTOCOL; }
 };
-template <typename T>
-Staged arr(T*& d, const void* src, void* dst, size_t count, int fill) {
-  return {&d, [](void* s, char* p) { *static_cast<T**>(s) = reinterpret_cast<T*>(p); }, src, dst, count * sizeof(T), fill};
-}
-template <typename T>
-Staged in(T*& d, const void* src, size_t count) {
-  return arr(d, src, nullptr, count, NO_FILL);
-}
-// an input the caller may leave out: then it takes no staging space and the kernels see a null pointer
-template <typename T>
-Staged opt_in(T*& d, const void* src, size_t count) {
-  if (src) return in(d, src, count);
-  return {&d, [](void* s, char*) { *static_cast<T**>(s) = nullptr; }, nullptr, nullptr, 0, NO_FILL};
-}
-// an output that is downloaded whatever the call's status
-template <typename T>
-Staged out(T*& d, void* dst, size_t count, int fill = NO_FILL) {
-  return arr(d, nullptr, dst, count, fill);
-}
-// an output that reaches `dst` only when the call ends in FPX_OK or FPX_EFATAL_PROTOCOL: a call that ends in FPX_EINVAL
-// leaves the caller's array as it was.  It is downloaded into the context's own host buffer and copied from there.
-template <typename T>
-Staged held(T*& d, T* dst, size_t count) {
-  Staged a = arr(d, nullptr, dst, count, NO_FILL);
-  a.hold = true;
-  return a;
-}
-// a held output of which dst gets the first *n elements only, n being another held word of the call (decided_index)
-inline Staged held_first(int32_t*& d, int32_t* dst, size_t count, int32_t*& n) {
-  Staged a = held(d, dst, count);
-  a.length = &n;
-  return a;
-}
-template <typename T>
-Staged scratch(T*& d, size_t count, int fill = NO_FILL) {
-  return arr(d, nullptr, nullptr, count, fill);
-}
-
-// The driver of the host-pointer entry points: grows the staging buffer once to hold every array (and the host buffer of
-// the held outputs: FPX_ENOMEM with nothing launched), carves them in order, uploads the inputs, fills (neighbours with one
-// fill value are one memset), runs launch(), checks the launches, downloads the outputs, synchronises once and returns the
-// device's status; then the held outputs go to the caller, if the status lets them.  The host checks of the call come
-// before it: nothing is staged on a bad batch.
 template <typename Launch>
 int host_call(fpx_epx* e, std::initializer_list<Staged> arrays, Launch launch) {
-  size_t total = 0, held_total = 0;
-  for (const Staged& a : arrays) total += a.span(), held_total += a.host_span();
-  int rc;
-  if ((rc = grow(e, &e->stage, total))) return rc;
-  if (held_total > e->held_cap) {
-    char* h = static_cast<char*>(malloc(held_total));
-    if (!h) return FPX_ENOMEM;
-    free(e->held);
-    e->held = h, e->held_cap = held_total;
-  }
-  char* const base = (char*)e->stage.p;
-  char* p = base;
-  for (const Staged& a : arrays) {
-    a.place(a.slot, p);
-    if (a.src && a.bytes) HIPCHK(e, hipMemcpyAsync(p, a.src, a.bytes, hipMemcpyHostToDevice, e->stream));
-    p += a.span();
-  }
-  char* run = nullptr;  // [run, p) is filled with the byte `value`
-  int value = NO_FILL;
-  p = base;
-  for (const Staged& a : arrays) {
-    if (a.fill != value) {
-      if (value != NO_FILL) HIPCHK(e, hipMemsetAsync(run, value, p - run, e->stream));
-      run = p, value = a.fill;
-    }
-    p += a.span();
-  }
-  if (value != NO_FILL) HIPCHK(e, hipMemsetAsync(run, value, p - run, e->stream));
-  if ((rc = launch()) || (rc = launch_check(e))) return rc;
-  p = base;
-  char* h = e->held;
-  for (const Staged& a : arrays) {
-    void* const to = a.hold ? h : a.dst;  // (a held output is downloaded whether the caller wants it or not: a count may be read)
-    if (to && a.bytes) HIPCHK(e, hipMemcpyAsync(to, p, a.bytes, hipMemcpyDeviceToHost, e->stream));
-    p += a.span(), h += a.host_span();
-  }
-  rc = fpx_epx_sync(e);
-  if (rc != FPX_OK && rc != FPX_EFATAL_PROTOCOL) return rc;
-  auto held_at = [&](const void* slot) {  // where the held array of `slot` lies in e->held
-    const char* at = e->held;
-    for (const Staged& a : arrays) {
-      if (a.hold && a.slot == slot) break;
-      at += a.host_span();
-    }
-    return at;
-  };
-  for (const Staged& a : arrays) {
-    if (!a.hold || !a.dst) continue;
-    const size_t bytes = a.length ? (size_t)*reinterpret_cast<const int32_t*>(held_at(a.length)) * 4 : a.bytes;
-    memcpy(a.dst, held_at(a.slot), bytes);
-  }
-  return rc;
+  return fpx::host_call(e, arrays, launch, EpxEnd{e});
 }
 
 template <int N>
@@ -2110,11 +2004,11 @@ int32_t fpx_epx_destroy(fpx_epx* e) {
                 e->st.largest, e->st.cl_stamp, e->st.cl_deps, e->st.cl_dend, e->ls.head, e->ls.resp, e->ls.prep, e->census_dev};
   for (void* p : ps)
     if (p) (void)hipFree(p);
-  DevBuf* bs[] = {&e->kv, &e->kv2, &e->seg, &e->conf, &e->tmp, &e->tick, &e->fusedb, &e->metab, &e->stage, &e->mk_misc, &e->mk_rec,
+  DevBuf* bs[] = {&e->kv, &e->kv2, &e->seg, &e->conf, &e->tmp, &e->tick, &e->fusedb, &e->metab, &e->mk_misc, &e->mk_rec,
                   &e->mk_pair, &e->mk_pconf, &e->lr_misc, &e->ri_misc, &e->wire_misc};
   for (DevBuf* b : bs)
     if (b->p) (void)hipFree(b->p);
-  free(e->held);
+  free_stage(&e->stage);
   if (e->mk_host) (void)hipHostFree(e->mk_host);
   for (DevBuf* b : {&e->kp_hist, &e->kp_recs, &e->kp_misc, &e->p_fast, &e->p_deps, &e->p_ldeps, &e->p_own, &e->dg_msg, &e->dg_direct,
                     &e->dg_clo, &e->dg_pre, &e->dg_tmax, &e->dg_pairs, &e->dg_pairs2, &e->dg_ctl, &e->dg_key})
