@@ -188,6 +188,11 @@ SIGNATURES = {
     "fpx_epx_replica_inbox_dev": (C.c_int32, [VP, C.c_int32] + [VP] * 17),
     "fpx_epx_replica_inbox_mk": (C.c_int32, [VP, C.c_int32] + [VP] * 18),
     "fpx_epx_replica_inbox_mk_dev": (C.c_int32, [VP, C.c_int32] + [VP] * 8 + [C.c_int32] + [VP] * 10),
+    "fpx_epx_keys_enable": (C.c_int32, [VP, C.c_int64]),
+    "fpx_epx_keys_count": (C.c_int32, [VP, I32P, C.POINTER(C.c_int64)]),
+    "fpx_epx_keys_intern_dev": (C.c_int32, [VP, VP, C.c_int64, VP, VP, C.c_int32, VP]),
+    "fpx_epx_keys_intern": (C.c_int32, [VP, VP, C.c_int64, VP, VP, C.c_int32, VP]),
+    "fpx_epx_keys_read": (C.c_int32, [VP, C.c_int32, C.c_int32, VP, VP, C.c_int64]),
     "fpx_epx_read_leader_state": (C.c_int32, [VP, C.c_int32, C.c_int32, C.c_int32, VP, VP]),
     "fpx_epx_recover": (C.c_int32, [VP, C.c_int32] + [VP] * 8),
     "fpx_epx_recovery_replies": (C.c_int32, [VP, C.c_int32] + [VP] * 13 + [C.c_int32] + [VP] * 9),

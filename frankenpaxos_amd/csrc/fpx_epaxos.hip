@@ -1383,6 +1383,7 @@ __global__ void __launch_bounds__(256) k_hp_commit(const EpxState st, const HpBa
 #include "fpx_epx_leader.hpp"
 #include "fpx_epx_recovery.hpp"
 #include "fpx_epx_inbox.hpp"
+#include "fpx_intern.hpp"
 #include "fpx_wire_epx_dev.hpp"
 
 }  // namespace
@@ -1413,6 +1414,8 @@ struct fpx_epx {
   DevBuf lr_misc;                         // fpx_epx_leader_replies: the decided flags and the compaction's block counts
   DevBuf ri_misc;                         // fpx_epx_replica_inbox: lay_epx_inbox
   DevBuf wire_misc;                       // fpx_wire_epx_leader_tick_dev: the decoded arrays of the tick
+  InternTable keys = {};                  // fpx_epx_keys_enable: the key table (fpx_intern.hpp), else not allocated
+  DevBuf keys_misc, rt_misc;              // fpx_epx_keys_intern_dev: lay_intern; the classify and the replica tick: their layouts
   bool lds_allowed = false, sort_lds_allowed = false;
   int num_cus = 256;
 };
@@ -2001,11 +2004,12 @@ int32_t fpx_epx_destroy(fpx_epx* e) {
   DeviceScope _dg(e->cfg.device);
   if (e->stream) (void)hipStreamSynchronize(e->stream);
   void* ps[] = {e->st.gets, e->st.sets, e->st.status, e->st.cl_status, e->st.cl_ballot, e->st.cl_vote, e->st.cl_triple,
-                e->st.largest, e->st.cl_stamp, e->st.cl_deps, e->st.cl_dend, e->ls.head, e->ls.resp, e->ls.prep, e->census_dev};
+                e->st.largest, e->st.cl_stamp, e->st.cl_deps, e->st.cl_dend, e->ls.head, e->ls.resp, e->ls.prep, e->census_dev,
+                e->keys.slot, e->keys.first, e->keys.key_off, e->keys.arena, e->keys.meta};
   for (void* p : ps)
     if (p) (void)hipFree(p);
   DevBuf* bs[] = {&e->kv, &e->kv2, &e->seg, &e->conf, &e->tmp, &e->tick, &e->fusedb, &e->metab, &e->mk_misc, &e->mk_rec,
-                  &e->mk_pair, &e->mk_pconf, &e->lr_misc, &e->ri_misc, &e->wire_misc};
+                  &e->mk_pair, &e->mk_pconf, &e->lr_misc, &e->ri_misc, &e->wire_misc, &e->keys_misc, &e->rt_misc};
   for (DevBuf* b : bs)
     if (b->p) (void)hipFree(b->p);
   free_stage(&e->stage);
@@ -3177,6 +3181,288 @@ int32_t fpx_epx_replica_inbox_mk(fpx_epx* e, int32_t m, const int32_t* kind, con
                        held(b.out_status, out_status, m), held(b.out_end, out_values_end, m), held(b.out_triple, out_triple, m),
                        held(b.out_deps, out_deps, mn)},
                    [&]() -> int { return replica_inbox_launch<true>(e, b); });
+}
+
+// ---- the key table: csrc/fpx_intern.hpp ----------------------------------------------------------------------------------
+static bool keys_on(const fpx_epx* e) { return e && e->keys.slot; }
+
+int32_t fpx_epx_keys_enable(fpx_epx* e, int64_t arena_bytes) {
+  if (!e || arena_bytes < 0 || arena_bytes > 0x7fffffff || keys_on(e)) return FPX_EINVAL;
+  DeviceScope _dg(e->cfg.device);
+  InternTable t = {};
+  t.num_keys = e->st.num_keys, t.slots = fpxi::slots_for(t.num_keys), t.arena_bytes = arena_bytes;
+  const size_t slots = (size_t)t.slots;
+  hipError_t err = hipMalloc((void**)&t.slot, slots * 8);
+  if (err == hipSuccess) err = hipMalloc((void**)&t.first, slots * 4);
+  if (err == hipSuccess) err = hipMalloc((void**)&t.key_off, ((size_t)t.num_keys + 1) * 4);
+  if (err == hipSuccess) err = hipMalloc((void**)&t.arena, (size_t)std::max<int64_t>(arena_bytes, 1));
+  if (err == hipSuccess) err = hipMalloc((void**)&t.meta, 8);
+  if (err == hipSuccess) err = hipMemsetAsync(t.slot, 0, slots * 8, e->stream);
+  if (err == hipSuccess) err = hipMemsetAsync(t.first, INTERN_IDLE & 0xff, slots * 4, e->stream);
+  if (err == hipSuccess) err = hipMemsetAsync(t.key_off, 0, ((size_t)t.num_keys + 1) * 4, e->stream);
+  if (err == hipSuccess) err = hipMemsetAsync(t.meta, 0, 8, e->stream);
+  if (err == hipSuccess) err = hipStreamSynchronize(e->stream);
+  if (err != hipSuccess) {
+    for (void* p : {(void*)t.slot, (void*)t.first, (void*)t.key_off, (void*)t.arena, (void*)t.meta})
+      if (p) (void)hipFree(p);
+    e->last_hip = (int)err;
+    return err == hipErrorOutOfMemory ? FPX_ENOMEM : FPX_EHIP;
+  }
+  e->keys = t;
+  return FPX_OK;
+}
+
+int32_t fpx_epx_keys_count(fpx_epx* e, int32_t* count, int64_t* arena_used) {
+  if (!keys_on(e)) return FPX_EINVAL;
+  DeviceScope _dg(e->cfg.device);
+  int32_t h[2] = {0, 0};
+  HIPCHK(e, hipMemcpyAsync(h, e->keys.meta, sizeof(h), hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(e, hipStreamSynchronize(e->stream));
+  if (count) *count = h[0];
+  if (arena_used) *arena_used = h[1];
+  return FPX_OK;
+}
+
+// an exclusive scan of a[0 .. rows * INTERN_ROW) in two levels of k_lr_bscan: inside every row (a row's sum to tot), then
+// over tot (the total to *total).  Element i's scan is a[i] + tot[i / INTERN_ROW]
+static void scan_rows_launch(fpx_epx* e, uint32_t* a, size_t rows, int32_t* tot, int32_t* total) {
+  hipLaunchKernelGGL(k_lr_bscan, dim3((unsigned)rows), dim3(256), 0, e->stream, e->st, a, (int)INTERN_ROW, (size_t)INTERN_ROW, tot);
+  hipLaunchKernelGGL(k_lr_bscan, dim3(1), dim3(256), 0, e->stream, e->st, (uint32_t*)tot, (int)rows, (size_t)0, total);
+}
+
+// one batch: b's strings, count and ids; the scratch fields are filled here
+static int32_t intern_launch(fpx_epx* e, InternBatch b, const InternScratch& s) {
+  b.slot_of = s.slot_of, b.rank = s.rank, b.gt = s.gt, b.ctl = s.ctl;
+  for (int j = 0; j < 3; ++j) b.sc[j] = s.sc[j], b.tot[j] = s.tot[j];
+  static_assert(IC_WORDS == INTERN_CTL_WORDS && INTERN_ROW == INTERN_SCAN_ROW, "a batch's scratch as lay_intern sizes it");
+  HIPCHK(e, hipMemsetAsync(b.ctl, 0, IC_WORDS * 8, e->stream));
+  const size_t rows = scan_rows((size_t)b.P);
+  const dim3 gp((b.P + 255) / 256), blk(256);
+  if (b.P > 0) {
+    hipLaunchKernelGGL(k_int_probe, gp, blk, 0, e->stream, e->keys, b);
+    hipLaunchKernelGGL(k_int_flags, dim3((unsigned)(rows * INTERN_ROW / 256)), blk, 0, e->stream, e->keys, b);
+    for (int j = 0; j < 3; ++j) scan_rows_launch(e, b.sc[j], rows, b.tot[j], b.gt + j);
+  }
+  hipLaunchKernelGGL(k_int_decide, dim3(1), dim3(1), 0, e->stream, e->keys, b, e->st.status);
+  if (b.P > 0) {
+    hipLaunchKernelGGL(k_int_rollback, gp, blk, 0, e->stream, e->keys, b);
+    hipLaunchKernelGGL(k_int_commit, gp, blk, 0, e->stream, e->keys, b);
+    hipLaunchKernelGGL(k_int_ids, gp, blk, 0, e->stream, e->keys, b);
+  }
+  return FPX_OK;
+}
+
+static int32_t keys_intern_check(const fpx_epx* e, int64_t bytes_len, int32_t P) {
+  return !keys_on(e) || bytes_len < 0 || P < 0 || P > FPX_EPX_MK_MAX_PAIRS ? FPX_EINVAL : FPX_OK;
+}
+
+static int32_t keys_intern_impl(fpx_epx* e, const uint8_t* d_bytes, int64_t bytes_len, const int64_t* d_off, const int32_t* d_len,
+                                int32_t P, int32_t* d_ids) {
+  InternScratch s;
+  int rc;
+  if ((rc = carve(e, &e->keys_misc, &s, [&](Carver& c) { return lay_intern(c, (size_t)P); }))) return rc;
+  InternBatch b;
+  memset(&b, 0, sizeof(b));
+  b.bytes = d_bytes, b.bytes_len = bytes_len, b.off = d_off, b.len = d_len, b.P = P, b.ids = d_ids;
+  return intern_launch(e, b, s);
+}
+
+int32_t fpx_epx_keys_intern_dev(fpx_epx* e, const uint8_t* d_bytes, int64_t bytes_len, const int64_t* d_off, const int32_t* d_len,
+                                int32_t P, int32_t* d_ids) {
+  if (keys_intern_check(e, bytes_len, P)) return FPX_EINVAL;
+  if (P == 0) return FPX_OK;
+  if ((bytes_len > 0 && !d_bytes) || !d_off || !d_len || !d_ids) return FPX_EINVAL;
+  DeviceScope _dg(e->cfg.device);
+  const int rc = keys_intern_impl(e, d_bytes, bytes_len, d_off, d_len, P, d_ids);
+  return rc ? rc : launch_check(e);
+}
+
+int32_t fpx_epx_keys_intern(fpx_epx* e, const uint8_t* bytes, int64_t bytes_len, const int64_t* off, const int32_t* len, int32_t P,
+                            int32_t* ids) {
+  if (keys_intern_check(e, bytes_len, P)) return FPX_EINVAL;
+  if (P == 0) return FPX_OK;
+  if ((bytes_len > 0 && !bytes) || !off || !len || !ids) return FPX_EINVAL;
+  DeviceScope _dg(e->cfg.device);
+  const uint8_t* d_bytes = nullptr;
+  const int64_t* d_off = nullptr;
+  const int32_t* d_len = nullptr;
+  int32_t* d_ids = nullptr;
+  return host_call(e, {in(d_bytes, bytes, (size_t)bytes_len), in(d_off, off, P), in(d_len, len, P), held(d_ids, ids, P)},
+                   [&]() -> int { return keys_intern_impl(e, d_bytes, bytes_len, d_off, d_len, P, d_ids); });
+}
+
+int32_t fpx_epx_keys_read(fpx_epx* e, int32_t first_id, int32_t n, int32_t* key_off_out, uint8_t* bytes_out, int64_t cap) {
+  if (!keys_on(e) || first_id < 0 || n < 0 || cap < 0 || !key_off_out) return FPX_EINVAL;
+  DeviceScope _dg(e->cfg.device);
+  int32_t count = 0;
+  HIPCHK(e, hipMemcpyAsync(&count, e->keys.meta, 4, hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(e, hipStreamSynchronize(e->stream));
+  if ((int64_t)first_id + n > count) return FPX_EINVAL;
+  HIPCHK(e, hipMemcpy(key_off_out, e->keys.key_off + first_id, ((size_t)n + 1) * 4, hipMemcpyDeviceToHost));
+  const int32_t base = key_off_out[0];
+  for (int32_t j = 0; j <= n; ++j) key_off_out[j] -= base;
+  if (key_off_out[n] > cap) return FPX_ECAPACITY;
+  if (key_off_out[n] > 0) {
+    if (!bytes_out) return FPX_EINVAL;
+    HIPCHK(e, hipMemcpy(bytes_out, e->keys.arena + base, (size_t)key_off_out[n], hipMemcpyDeviceToHost));
+  }
+  return FPX_OK;
+}
+
+// ---- a replica's inbox from wire bytes: csrc/fpx_wire_epx_dev.hpp (include/fpx_wire.h) ---------------------------------------
+// the tick's check between the count and the scan (a classify on its own has none)
+struct ClsTick {
+  const int32_t *kind, *nr, *shape;
+  int32_t triple_base;
+  const int32_t* triple_in;
+  int32_t *ri_kind, *triple;
+};
+
+// b: the commands and the outputs; the scratch fields are filled here.  d_keys: the ids of the pairs
+static int32_t classify_launch(fpx_epx* e, ClsBatch b, const EpxClassifyScratch& s, int32_t* d_keys, const ClsTick* tk) {
+  b.cnt = s.cnt, b.cscan = s.cscan, b.ctot = s.ctot, b.cgt = s.cgt, b.np = s.np, b.pair_off = s.pair_off, b.pair_len = s.pair_len;
+  const size_t rows = scan_rows((size_t)b.m);
+  const dim3 gm((b.m + 255) / 256), blk(256);
+  hipLaunchKernelGGL(k_cls_count, dim3((unsigned)(rows * INTERN_ROW / 256)), blk, 0, e->stream, e->st, b);
+  if (tk)
+    hipLaunchKernelGGL(k_epx_wire_replica_check, gm, blk, 0, e->stream, e->st, b.m, tk->kind, tk->nr, tk->shape, b.shape,
+                       tk->triple_base, tk->triple_in, tk->ri_kind, tk->triple);
+  // (the tail first: a bad tick is FPX_EINVAL by the time the scans look at the status)
+  hipLaunchKernelGGL(k_epx_wire_tail, dim3(1), dim3(1), 0, e->stream, e->st, b.result);
+  scan_rows_launch(e, b.cscan, rows, b.ctot, b.cgt);
+  hipLaunchKernelGGL(k_cls_decide, dim3(1), dim3(1), 0, e->stream, e->st, b);
+  hipLaunchKernelGGL(k_cls_emit, gm, blk, 0, e->stream, b);
+  InternBatch ib;
+  memset(&ib, 0, sizeof(ib));
+  ib.bytes = b.buf, ib.bytes_len = b.buf_len, ib.off = s.pair_off, ib.len = s.pair_len, ib.P = b.max_pairs, ib.count = s.np;
+  ib.ids = d_keys;
+  const int rc = intern_launch(e, ib, s.in);
+  if (rc) return rc;
+  hipLaunchKernelGGL(k_cls_result, dim3(1), dim3(1), 0, e->stream, b, (const long long*)s.in.ctl);
+  return FPX_OK;
+}
+
+static int32_t classify_check(const fpx_epx* e, int64_t buf_len, int32_t m, int32_t max_pairs) {
+  return !keys_on(e) || buf_len < 0 || buf_len > 0x7fffffff || m < 0 || m > FPX_EPX_INBOX_MAX || max_pairs < 0 ||
+                 max_pairs > FPX_EPX_MK_MAX_PAIRS
+             ? FPX_EINVAL
+             : FPX_OK;
+}
+
+int32_t fpx_wire_epx_classify_dev(fpx_epx* e, const uint8_t* d_buf, int64_t buf_len, const int64_t* d_cmd_off,
+                                  const int32_t* d_cmd_len, int32_t m, int32_t max_pairs, int32_t* d_key_offsets, int32_t* d_keys,
+                                  uint8_t* d_is_set, int32_t* d_is_noop, int32_t* d_cmd_shape, int32_t* d_result) {
+  if (classify_check(e, buf_len, m, max_pairs) || !d_result) return FPX_EINVAL;
+  DeviceScope _dg(e->cfg.device);
+  if (m == 0) {
+    HIPCHK(e, hipMemsetAsync(d_result, 0, 16, e->stream));
+    HIPCHK(e, hipMemsetAsync(d_result, 0xFF, 4, e->stream));
+    if (d_key_offsets) HIPCHK(e, hipMemsetAsync(d_key_offsets, 0, 4, e->stream));
+    return FPX_OK;
+  }
+  if ((buf_len > 0 && !d_buf) || !d_cmd_off || !d_cmd_len || !d_key_offsets || (max_pairs > 0 && !d_keys) || !d_is_set ||
+      !d_is_noop || !d_cmd_shape)
+    return FPX_EINVAL;
+  EpxClassifyScratch s;
+  int rc;
+  if ((rc = carve(e, &e->rt_misc, &s, [&](Carver& c) { return lay_epx_classify(c, (size_t)m, (size_t)max_pairs); }))) return rc;
+  ClsBatch b;
+  memset(&b, 0, sizeof(b));
+  b.buf = d_buf, b.buf_len = buf_len, b.cmd_off = d_cmd_off, b.cmd_len = d_cmd_len, b.m = m, b.max_pairs = max_pairs;
+  b.key_offsets = d_key_offsets, b.is_set = d_is_set, b.is_noop = d_is_noop, b.shape = d_cmd_shape, b.result = d_result;
+  rc = classify_launch(e, b, s, d_keys, nullptr);
+  return rc ? rc : launch_check(e);
+}
+
+// stage 1 (decode, check, classify, intern), ONE host wait for the pair count and the status, stage 2
+// (fpx_epx_replica_inbox_mk_dev's launches on the decoded arrays); o: `to` and the outputs
+static int32_t replica_tick_impl(fpx_epx* e, const uint8_t* d_in, int64_t in_len, const int64_t* d_in_offsets, int32_t triple_base,
+                                 const int32_t* d_triple_id, int32_t max_pairs, RiBatch o, int32_t* d_bad_index,
+                                 int32_t* d_num_pairs) {
+  const int32_t m = o.m;
+  EpxReplicaTickScratch w;
+  int rc;
+  if ((rc = carve(e, &e->rt_misc, &w,
+                  [&](Carver& c) { return lay_epx_replica_tick(c, (size_t)m, (size_t)e->st.n, (size_t)max_pairs); })))
+    return rc;
+  fpxw::EpxFoldOut fo;
+  memset(&fo, 0, sizeof(fo));
+  fo.kind = w.kind, fo.il = w.leader, fo.in = w.number, fo.bo = w.b_ord, fo.br = w.b_rep, fo.cmd_off = w.cmd_off;
+  fo.cmd_len = w.cmd_len, fo.nr = w.nr, fo.wm = w.deps, fo.dend = w.dend, fo.shape = w.shape;
+  launch_wire_decode(e, d_in, in_len, d_in_offsets, m, fo);
+  ClsBatch b;
+  memset(&b, 0, sizeof(b));
+  b.buf = d_in, b.buf_len = in_len, b.cmd_off = w.cmd_off, b.cmd_len = w.cmd_len, b.m = m, b.max_pairs = max_pairs;
+  b.key_offsets = w.key_offsets, b.is_set = w.is_set, b.is_noop = w.is_noop, b.shape = w.cmd_shape, b.result = w.result;
+  const ClsTick tk{w.kind, w.nr, w.shape, triple_base, d_triple_id, w.ri_kind, w.triple};
+  if ((rc = classify_launch(e, b, w.cls, w.keys, &tk))) return rc;
+  if (d_bad_index) HIPCHK(e, hipMemcpyAsync(d_bad_index, w.result, 4, hipMemcpyDeviceToDevice, e->stream));
+  if (d_num_pairs) HIPCHK(e, hipMemcpyAsync(d_num_pairs, w.result + 1, 4, hipMemcpyDeviceToDevice, e->stream));
+  int32_t h[6] = {0, 0, 0, 0, 0, 0};
+  HIPCHK(e, hipMemcpyAsync(h, w.result, 16, hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(e, hipMemcpyAsync(h + 4, e->st.status, 8, hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(e, hipStreamSynchronize(e->stream));
+  if (h[4] != 0) return FPX_OK;  // refused: the status stays on the context for fpx_epx_sync
+  if (h[1] < 0 || h[1] > max_pairs) return FPX_EHIP;
+  o.kind = w.ri_kind, o.leader = w.leader, o.number = w.number, o.b_ord = w.b_ord, o.b_rep = w.b_rep;
+  o.key_off = w.key_offsets, o.keys = w.keys, o.P = h[1], o.is_set = w.is_set, o.triple = w.triple, o.deps = w.deps, o.dend = w.dend;
+  return replica_inbox_launch<true>(e, o);
+}
+
+static int32_t replica_tick_check(const fpx_epx* e, int64_t in_len, int32_t m, int32_t max_pairs) {
+  return replica_inbox_check(e, m) || classify_check(e, in_len, m, max_pairs) ? FPX_EINVAL : FPX_OK;
+}
+
+int32_t fpx_wire_epx_replica_tick_dev(fpx_epx* e, const uint8_t* d_in, int64_t in_len, const int64_t* d_in_offsets, int32_t m,
+                                      const int32_t* d_to, int32_t triple_base, const int32_t* d_triple_id, int32_t max_pairs,
+                                      int32_t* d_outcome, int32_t* d_out_ballot, int32_t* d_out_status, int32_t* d_out_deps,
+                                      int32_t* d_out_values_end, int32_t* d_out_triple, int32_t* d_bad_index,
+                                      int32_t* d_num_pairs) {
+  if (replica_tick_check(e, in_len, m, max_pairs) || !d_bad_index) return FPX_EINVAL;
+  DeviceScope _dg(e->cfg.device);
+  if (m == 0) {
+    HIPCHK(e, hipMemsetAsync(d_bad_index, 0xFF, 4, e->stream));
+    if (d_num_pairs) HIPCHK(e, hipMemsetAsync(d_num_pairs, 0, 4, e->stream));
+    return FPX_OK;
+  }
+  if ((in_len > 0 && !d_in) || !d_in_offsets || !d_to) return FPX_EINVAL;
+  RiBatch o;
+  memset(&o, 0, sizeof(o));
+  o.m = m, o.to = d_to, o.outcome = d_outcome, o.out_ballot = d_out_ballot, o.out_status = d_out_status, o.out_deps = d_out_deps;
+  o.out_end = d_out_values_end, o.out_triple = d_out_triple;
+  const int rc = replica_tick_impl(e, d_in, in_len, d_in_offsets, triple_base, d_triple_id, max_pairs, o, d_bad_index, d_num_pairs);
+  return rc ? rc : launch_check(e);
+}
+
+int32_t fpx_wire_epx_replica_tick(fpx_epx* e, const uint8_t* in_bytes, int64_t in_len, const int64_t* in_offsets, int32_t m,
+                                  const int32_t* to, int32_t triple_base, const int32_t* triple_id, int32_t max_pairs,
+                                  int32_t* outcome, int32_t* out_ballot, int32_t* out_status, int32_t* out_deps,
+                                  int32_t* out_values_end, int32_t* out_triple, int32_t* bad_index, int32_t* num_pairs) {
+  if (replica_tick_check(e, in_len, m, max_pairs)) return FPX_EINVAL;
+  DeviceScope _dg(e->cfg.device);
+  if (bad_index) *bad_index = -1;
+  if (num_pairs) *num_pairs = 0;
+  if (m == 0) return FPX_OK;
+  if ((in_len > 0 && !in_bytes) || !in_offsets || !to) return FPX_EINVAL;
+  const size_t mn = (size_t)m * e->st.n;
+  const uint8_t* d_in = nullptr;
+  const int64_t* d_off = nullptr;
+  const int32_t* d_triple = nullptr;
+  int32_t *d_bad = nullptr, *d_np = nullptr;
+  int32_t res[2] = {-1, 0};
+  RiBatch o;
+  memset(&o, 0, sizeof(o));
+  o.m = m;
+  const int32_t rc = host_call(
+      e, {in(d_in, in_bytes, (size_t)in_len), in(d_off, in_offsets, (size_t)m + 1), in(o.to, to, m), opt_in(d_triple, triple_id, m),
+          held(o.outcome, outcome, m), held(o.out_ballot, out_ballot, m), held(o.out_status, out_status, m),
+          held(o.out_end, out_values_end, m), held(o.out_triple, out_triple, m), held(o.out_deps, out_deps, mn),
+          out(d_bad, &res[0], 1), out(d_np, &res[1], 1)},
+      [&]() -> int { return replica_tick_impl(e, d_in, in_len, d_off, triple_base, d_triple, max_pairs, o, d_bad, d_np); });
+  // (the two words come down whatever the status; the bad index means something on FPX_EINVAL)
+  if (bad_index && rc == FPX_EINVAL) *bad_index = res[0];
+  if (num_pairs) *num_pairs = res[1];
+  return rc;
 }
 
 int32_t fpx_epx_read_leader_state(fpx_epx* e, int32_t replica, int32_t leader, int32_t number, int32_t out[8],

@@ -187,4 +187,77 @@ inline EpxInboxMkScratch lay_epx_inbox_mk(Carver& c, size_t m, size_t P, size_t 
   return s;
 }
 
+// fpx_intern.hpp, one batch of P strings: per pair its slot and its first-occurrence flag; the three arrays the batch scans
+// (flag, low and high half of the flagged length), padded to whole rows of INTERN_SCAN_ROW pairs, with the rows' sums and
+// the three totals; and the batch's 8 control words.  (Under the sanitizers: tests/epx_cmd_parse_fuzz_main.cpp, as the
+// two layouts below.)
+constexpr int INTERN_CTL_WORDS = 8;
+constexpr size_t INTERN_SCAN_ROW = 1024;
+inline size_t scan_rows(size_t n) { return (n + INTERN_SCAN_ROW - 1) / INTERN_SCAN_ROW; }
+struct InternScratch {
+  int32_t *slot_of, *rank;
+  uint32_t* sc[3];
+  int32_t* tot[3];
+  int32_t* gt;
+  long long* ctl;
+};
+inline InternScratch lay_intern(Carver& c, size_t P) {
+  const size_t rows = scan_rows(P);
+  InternScratch s;
+  s.slot_of = c.take<int32_t>(P);
+  s.rank = c.take<int32_t>(P);
+  for (int j = 0; j < 3; ++j) s.sc[j] = c.take<uint32_t>(rows * INTERN_SCAN_ROW);
+  for (int j = 0; j < 3; ++j) s.tot[j] = c.take<int32_t>(rows);
+  s.gt = c.take<int32_t>(4);
+  s.ctl = c.take<long long>(INTERN_CTL_WORDS);
+  return s;
+}
+
+// fpx_wire_epx_dev.hpp, the classify of m commands into at most max_pairs (message, key) pairs: the key count per message,
+// its scan in rows as above with the rows' sums and the total, the word that tells the intern batch how many pairs there
+// are, where each pair's key lies, and that batch
+struct EpxClassifyScratch {
+  int32_t *cnt, *np, *ctot, *cgt;
+  uint32_t* cscan;
+  int64_t* pair_off;
+  int32_t* pair_len;
+  InternScratch in;
+};
+inline EpxClassifyScratch lay_epx_classify(Carver& c, size_t m, size_t max_pairs) {
+  EpxClassifyScratch s;
+  s.cnt = c.take<int32_t>(m);
+  s.cscan = c.take<uint32_t>(scan_rows(m) * INTERN_SCAN_ROW);
+  s.ctot = c.take<int32_t>(scan_rows(m));
+  s.cgt = c.take<int32_t>(1);
+  s.np = c.take<int32_t>(1);
+  s.pair_off = c.take<int64_t>(max_pairs);
+  s.pair_len = c.take<int32_t>(max_pairs);
+  s.in = lay_intern(c, max_pairs);
+  return s;
+}
+
+// fpx_wire_epx_replica_tick: the decoded arrays of m messages at n replicas, the classify's outputs (what
+// fpx_epx_replica_inbox_mk takes) and its scratch
+struct EpxReplicaTickScratch {
+  int32_t *kind, *nr, *shape, *ri_kind, *leader, *number, *b_ord, *b_rep, *dend, *cmd_len, *is_noop, *cmd_shape, *triple;
+  int32_t *deps, *key_offsets, *keys, *result;
+  int64_t* cmd_off;
+  uint8_t* is_set;
+  EpxClassifyScratch cls;
+};
+inline EpxReplicaTickScratch lay_epx_replica_tick(Carver& c, size_t m, size_t n, size_t max_pairs) {
+  EpxReplicaTickScratch s;
+  for (int32_t** a : {&s.kind, &s.nr, &s.shape, &s.ri_kind, &s.leader, &s.number, &s.b_ord, &s.b_rep, &s.dend, &s.cmd_len,
+                      &s.is_noop, &s.cmd_shape, &s.triple})
+    *a = c.take<int32_t>(m);
+  s.deps = c.take<int32_t>(m * n);
+  s.key_offsets = c.take<int32_t>(m + 1);
+  s.keys = c.take<int32_t>(max_pairs);
+  s.result = c.take<int32_t>(4);
+  s.cmd_off = c.take<int64_t>(m);
+  s.is_set = c.take<uint8_t>(m);
+  s.cls = lay_epx_classify(c, m, max_pairs);
+  return s;
+}
+
 }  // namespace fpx

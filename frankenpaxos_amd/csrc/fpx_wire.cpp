@@ -8,6 +8,8 @@
 #include <vector>
 
 #include "../../include/fpx.h"
+#include "fpx_epx_cmd_parse.hpp"
+#include "fpx_intern.hpp"
 #include "fpx_wire_emit.hpp"
 #include "fpx_wire_epx_parse.hpp"
 #include "fpx_wire_parse.hpp"
@@ -746,5 +748,62 @@ int32_t fpx_wire_epaxos_decode_replica_inbound_folded(
   return decode_loop(buf, buf_len, offsets, n, bad_index,
                      [&](int32_t i, Reader r) { return epx_decode_folded(buf, r, i, num_replicas, o); });
 }
+
+// ---- the key lists of EPaxos commands: csrc/fpx_epx_cmd_parse.hpp, the parser k_cls_count / k_cls_emit run on the device ----
+namespace {
+struct HostPairSink {
+  const uint8_t* base;
+  int64_t* off;
+  int32_t* len;
+  int64_t first, cap;
+  void key(int32_t j, const uint8_t* at, int32_t n) {
+    if (first + j >= cap) return;
+    if (off) off[first + j] = at - base;
+    if (len) len[first + j] = n;
+  }
+};
+}  // namespace
+
+int32_t fpx_wire_epx_classify(const uint8_t* buf, int64_t buf_len, const int64_t* cmd_off, const int32_t* cmd_len, int32_t m,
+                              int32_t max_pairs, int32_t* key_offsets, int64_t* pair_off, int32_t* pair_len, uint8_t* is_set,
+                              int32_t* is_noop, int32_t* cmd_shape, int32_t* bad_index) {
+  if (m < 0 || buf_len < 0 || buf_len > 0x7fffffff || max_pairs < 0 || !key_offsets || (m > 0 && (!cmd_off || !cmd_len)))
+    return FPX_EINVAL;
+  if (bad_index) *bad_index = -1;
+  int64_t total = 0;
+  int32_t bad = -1;
+  for (int32_t i = 0; i < m; ++i) {
+    key_offsets[i] = (int32_t)total;
+    EpxCmd c;
+    int32_t noop = -1, shape = -1;
+    if (cmd_len[i] >= 0) {
+      bool ok = cmd_off[i] >= 0 && cmd_off[i] <= buf_len - cmd_len[i];
+      const Reader r{buf + (ok ? cmd_off[i] : 0), buf + (ok ? cmd_off[i] + cmd_len[i] : 0)};
+      if (ok) {
+        EpxNoKeys none;
+        ok = epx_parse_command(r, &c, none);
+      }
+      if (!ok && bad < 0) bad = i;
+      if (ok && c.shape == 1 && c.num_keys > 0) {  // (the second walk: only a canonical frame's keys are reported)
+        HostPairSink s{buf, pair_off, pair_len, total, max_pairs};
+        EpxCmd again;
+        (void)epx_parse_command(r, &again, s);
+      }
+      noop = c.is_noop, shape = c.shape;
+    }
+    if (is_set) is_set[i] = (uint8_t)c.is_set;
+    if (is_noop) is_noop[i] = noop;
+    if (cmd_shape) cmd_shape[i] = shape;
+    total += c.num_keys;
+  }
+  key_offsets[m] = (int32_t)total;
+  if (bad >= 0) {
+    if (bad_index) *bad_index = bad;
+    return FPX_EINVAL;
+  }
+  return total > max_pairs ? FPX_ECAPACITY : FPX_OK;
+}
+
+uint64_t fpx_wire_epx_key_hash(const uint8_t* bytes, int64_t len) { return fpxi::fnv1a64(bytes, len < 0 ? 0 : len); }
 
 }  // extern "C"

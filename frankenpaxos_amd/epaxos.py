@@ -402,6 +402,129 @@ class EPaxos:
                                         p(odeps), p(oend), p(otr), p(dec), p(nd), C.byref(bad))
         return st, outcome, oseq, odeps, oend, otr, dec[:max(int(nd[0]), 0)], bad.value
 
+    # ---- the key table and a replica's inbox from wire bytes (include/fpx.h fpx_epx_keys_*, include/fpx_wire.h) ----
+    KEY_MAX_LEN = 4096    # FPX_EPX_KEY_MAX_LEN
+
+    def keys_enable(self, arena_bytes):
+        """fpx_epx_keys_enable: the context keeps the key strings -> key ids map on the device, arena_bytes for the strings"""
+        st = self.L.fpx_epx_keys_enable(self._h, int(arena_bytes))
+        if st:
+            raise FpxError(st, "fpx_epx_keys_enable")
+
+    def keys_count(self):
+        """(ids handed out, arena bytes used)"""
+        n, used = C.c_int32(0), C.c_int64(0)
+        st = self.L.fpx_epx_keys_count(self._h, C.byref(n), C.byref(used))
+        if st:
+            raise FpxError(st, "fpx_epx_keys_count")
+        return n.value, used.value
+
+    @staticmethod
+    def pack_keys(keys):
+        """a list of bytes -> (bytes uint8, off int64, len int32), back to back"""
+        ln = np.array([len(k) for k in keys], np.int32)
+        off = np.zeros(len(keys), np.int64)
+        if len(keys):
+            off[1:] = np.cumsum(ln[:-1], dtype=np.int64)
+        return np.frombuffer(b"".join(bytes(k) for k in keys), np.uint8).copy(), off, ln
+
+    def keys_intern(self, keys=None, packed=None):
+        """fpx_epx_keys_intern on a list of bytes (or packed = (bytes, off, len) arrays): (status, ids[P]); the ids of a
+        refused batch keep their fill of -9"""
+        buf, off, ln = self.pack_keys(keys) if packed is None else packed
+        buf = np.ascontiguousarray(buf, np.uint8)
+        off, ln = np.ascontiguousarray(off, np.int64), np.ascontiguousarray(ln, np.int32)
+        ids = np.full(len(off), -9, np.int32)
+        st = self.L.fpx_epx_keys_intern(self._h, buf.ctypes.data if len(buf) else None, len(buf), off.ctypes.data, ln.ctypes.data,
+                                        len(off), ids.ctypes.data)
+        return st, ids
+
+    def keys_intern_dev(self, buf, off, ln, ids, buf_len=None):
+        """fpx_epx_keys_intern_dev on device tensors (uint8, int64, int32 -> int32), enqueued; the status comes with sync()"""
+        st = self.L.fpx_epx_keys_intern_dev(self._h, buf.data_ptr(), buf.numel() if buf_len is None else buf_len, off.data_ptr(),
+                                            ln.data_ptr(), off.numel(), ids.data_ptr())
+        if st:
+            raise FpxError(st, "fpx_epx_keys_intern_dev")
+
+    def keys_read(self, first_id=0, n=None):
+        """fpx_epx_keys_read: the keys of ids first_id .. first_id + n - 1 (default: all) as a list of bytes"""
+        if n is None:
+            n = self.keys_count()[0] - first_id
+        off = np.zeros(n + 1, np.int32)
+        out = np.zeros(1, np.uint8)
+        st = self.L.fpx_epx_keys_read(self._h, first_id, n, off.ctypes.data, out.ctypes.data, 0)
+        if st == _lib.FPX_ECAPACITY:
+            out = np.zeros(int(off[n]), np.uint8)
+            st = self.L.fpx_epx_keys_read(self._h, first_id, n, off.ctypes.data, out.ctypes.data, len(out))
+        if st:
+            raise FpxError(st, "fpx_epx_keys_read")
+        return [out[off[j]:off[j + 1]].tobytes() for j in range(n)]
+
+    def wire_classify_dev(self, buf, cmd_off, cmd_len, max_pairs):
+        """fpx_wire_epx_classify_dev on the serialised CommandOrNoops cmd_off / cmd_len locate in buf (uint8 array; all
+        uploaded): a dict of numpy arrays key_offsets[m + 1], keys[num_pairs] (ids), is_set, is_noop, cmd_shape, result[4]
+        (bad index, num_pairs, new keys, new bytes) and status_code (what sync() gave)"""
+        import torch
+
+        from . import wire
+        L = wire._L()
+        dev = torch.device("cuda", torch.cuda.current_device())
+        up = lambda a, t: torch.from_numpy(np.array(a, dtype=t)).to(dev)
+        m = len(cmd_off)
+        d_buf = up(buf if len(buf) else np.zeros(1, np.uint8), np.uint8)
+        d_off, d_len = up(cmd_off, np.int64), up(cmd_len, np.int32)
+        z = lambda k, t: torch.full((max(k, 1),), -9, dtype=t, device=dev)
+        koff, keys, iset = z(m + 1, torch.int32), z(max_pairs, torch.int32), z(m, torch.uint8)
+        noop, shape, res = z(m, torch.int32), z(m, torch.int32), z(4, torch.int32)
+        torch.cuda.synchronize()
+        st = L.fpx_wire_epx_classify_dev(self._h, d_buf.data_ptr(), len(buf), d_off.data_ptr(), d_len.data_ptr(), m, max_pairs,
+                                         koff.data_ptr(), keys.data_ptr(), iset.data_ptr(), noop.data_ptr(), shape.data_ptr(),
+                                         res.data_ptr())
+        if st:
+            raise FpxError(st, "fpx_wire_epx_classify_dev")
+        st = self.sync()
+        res = res.cpu().numpy()
+        P = int(res[1]) if st == 0 else 0
+        return {"key_offsets": koff.cpu().numpy()[:m + 1], "keys": keys.cpu().numpy()[:P], "is_set": iset.cpu().numpy()[:m],
+                "is_noop": noop.cpu().numpy()[:m], "cmd_shape": shape.cpu().numpy()[:m], "result": res, "status_code": st}
+
+    def wire_replica_tick(self, messages, to, max_pairs, triple_base=0, triple_id=None, offsets=None):
+        """fpx_wire_epx_replica_tick: a burst of serialised PreAccept / Accept / Commit / Prepare messages, to[i] the replica
+        that received message i -> what replica_inbox_mk returns for the decoded burst, plus bad_index and num_pairs:
+        (status, outcome[m], out_ballot[m], out_status[m], out_deps[m, n], out_values_end[m], out_triple[m], bad_index,
+        num_pairs); on a refusal the outputs keep their fill of -9"""
+        from . import wire
+        L = wire._L()
+        buf, off = wire.pack(messages)
+        m = len(messages)
+        if offsets is not None:
+            off = np.ascontiguousarray(offsets, np.int64)
+            m = len(off) - 1
+        to = np.ascontiguousarray(to, dtype=np.int32)
+        tr = None if triple_id is None else np.ascontiguousarray(triple_id, dtype=np.int32)
+        outcome, ob, os_, oend, otr = (np.full(m, -9, np.int32) for _ in range(5))
+        odeps = np.full((m, self.n), -9, np.int32)
+        bad, npairs = C.c_int32(-9), C.c_int32(-9)
+        p = lambda a: None if a is None else a.ctypes.data
+        st = L.fpx_wire_epx_replica_tick(self._h, p(buf), sum(len(x) for x in messages), p(off), m, p(to), triple_base, p(tr),
+                                         max_pairs, p(outcome), p(ob), p(os_), p(odeps), p(oend), p(otr), C.byref(bad),
+                                         C.byref(npairs))
+        return st, outcome, ob, os_, odeps, oend, otr, bad.value, npairs.value
+
+    def wire_replica_tick_dev(self, buf, buf_len, offsets, to, max_pairs, triple_base=0, triple_id=None, outcome=None,
+                              out_ballot=None, out_status=None, out_deps=None, out_values_end=None, out_triple=None,
+                              bad_index=None, num_pairs=None):
+        """the same on device tensors (buf uint8, offsets int64[m + 1], the rest int32); bad_index[1] is required.  ONE host
+        wait inside (the pair count); the status comes with sync()"""
+        from . import wire
+        L = wire._L()
+        d = lambda t: None if t is None else t.data_ptr()
+        st = L.fpx_wire_epx_replica_tick_dev(self._h, d(buf), buf_len, d(offsets), offsets.numel() - 1, d(to), triple_base,
+                                             d(triple_id), max_pairs, d(outcome), d(out_ballot), d(out_status), d(out_deps),
+                                             d(out_values_end), d(out_triple), d(bad_index), d(num_pairs))
+        if st:
+            raise FpxError(st, "fpx_wire_epx_replica_tick_dev")
+
     # ---- originating recovery (recovery=True) ----
     def recover(self, leader, number, at):
         """transitionToPreparePhase of instance (leader, number) at replica `at`, its own Prepare delivered at once:

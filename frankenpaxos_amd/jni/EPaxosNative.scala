@@ -76,7 +76,9 @@ class GpuEPaxosEngine[Transport <: frankenpaxos.Transport[Transport]](
     numKeys: Int = 1 << 10,
     numInstances: Int = 1 << 20,         // instances (leader, number < numInstances) the command logs hold
     leaderState: Boolean = false,        // also keep Replica.leaderStates on the device (GpuEPaxosReplica's remotePeers)
-    recovery: Boolean = false            // ... with the Preparing phase (GpuEPaxosReplica's originateRecovery); needs leaderState
+    recovery: Boolean = false,           // ... with the Preparing phase (GpuEPaxosReplica's originateRecovery); needs leaderState
+    deviceKeys: Boolean = false,         // key strings -> key ids in the DEVICE's table (Native.epxKeysEnable); keyOf caches it
+    keyArenaBytes: Long = 1L << 24       // ... with this many bytes for the key strings
 ) {
   val n: Int = config.n
   val hasLeaderState: Boolean = leaderState
@@ -99,7 +101,23 @@ class GpuEPaxosEngine[Transport <: frankenpaxos.Transport[Transport]](
   val actors = mutable.Buffer[GpuEPaxosReplica[Transport]]()
   val nextNumber: Array[Int] = Array.fill(n)(0)             // Replica.nextAvailableInstance, per hosted leader
   private val keyIds = mutable.Map[String, Int]()
-  def keyOf(k: String): Int = keyIds.getOrElseUpdate(k, { logger.check(keyIds.size < numKeys); keyIds.size })
+  if (deviceKeys) Native.check(Native.epxKeysEnable(handle, keyArenaBytes), logger)
+  // deviceKeys: the device hands out the ids (fpx_epx_keys_intern), also to the frames that go to Native.epxWireReplicaTick
+  // as bytes; a miss here asks it and caches the answer, so the JVM and the device never hand out ids side by side
+  private def deviceKeyOf(k: String): Int = {
+    val bytes = k.getBytes(java.nio.charset.StandardCharsets.UTF_8)
+    val id = new Array[Int](1)
+    Native.check(Native.epxKeysIntern(handle, 1, bytes, bytes.length.toLong, Array(0L), Array(bytes.length), id), logger)
+    id(0)
+  }
+  def keyOf(k: String): Int =
+    if (deviceKeys) keyIds.getOrElseUpdate(k, deviceKeyOf(k))
+    else keyIds.getOrElseUpdate(k, { logger.check(keyIds.size < numKeys); keyIds.size })
+
+  // A caller that holds raw ReplicaInbound frames routes them by the outer oneof tag, one byte: 0x12 (PreAccept), 0x22
+  // (Accept), 0x32 (Commit) and 0x3a (Prepare) go to the replica tick native (Native.scala; needs deviceKeys) as 0x1a /
+  // 0x2a / 0x4a go to the leader tick native (INTEGRATION.md); every other frame, and a frame either tick refuses, is the JVM's
+  def isReplicaTickFrame(first: Byte): Boolean = first == 0x12 || first == 0x22 || first == 0x32 || first == 0x3a
 
   // (key ids, is set) of a key-value-store command, any number of keys (KeyValueStore.scala:221-302 merges and puts over
   // all of them); only a request that is neither a get nor a set is outside the device's conflict model

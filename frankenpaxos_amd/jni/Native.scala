@@ -224,6 +224,25 @@ object Native {
   @native def epxWireLeaderTick(handle: Long, m: Int, numReplicas: Int, in: java.nio.ByteBuffer, inLen: Long,
                                 inOffsets: java.nio.ByteBuffer, to: java.nio.ByteBuffer, outcome: Array[Int],
                                 triple: Array[Int], outDeps: Array[Int], decided: Array[Int], badIndex: Array[Int]): Int
+  // the context's key table (include/fpx.h, fpx_epx_keys_enable): key strings -> key ids on the device (what
+  // GpuEPaxosEngine.keyOf is on the JVM), arenaBytes for the strings.  Once per context
+  @native def epxKeysEnable(handle: Long, arenaBytes: Long): Int
+  // one batch of key strings (fpx_epx_keys_intern): string p = bytes(off(p) until off(p) + len(p)), UTF-8 as on the wire
+  // -> ids(p); equal strings get equal ids, new ones the next ids in order of first occurrence.  5 (FPX_ECAPACITY): more
+  // keys than numKeys or more bytes than the arena; 1: a key longer than 4096 bytes; nothing applied either way
+  @native def epxKeysIntern(handle: Long, count: Int, bytes: Array[Byte], bytesLen: Long, off: Array[Long], len: Array[Int],
+                            ids: Array[Int]): Int
+  // one tick of hosted replicas from wire bytes (include/fpx_wire.h, fpx_wire_epx_replica_tick; needs epxKeysEnable): in /
+  // inOffsets / to as epxWireLeaderTick's; PreAccept, Accept, Commit and Prepare frames only.  The triple id of message i is
+  // tripleId(i), or with tripleId null tripleBase + i (-1 for a Prepare).  The outputs are epxReplicaInboxMk's.  result(0):
+  // -1, or with status 1 the first bad offset, malformed frame, frame of another kind or frame whose dependencies or command
+  // are not in the canonical shape (parse that one on the JVM) -- nothing applied, nothing interned; -1 with status 1:
+  // epxReplicaInboxMk's own refusal (the burst's keys stay interned).  result(1): the (message, key) pairs; status 5 with
+  // more than maxPairs of them (call again), or when the key table is full
+  @native def epxWireReplicaTick(handle: Long, m: Int, numReplicas: Int, in: java.nio.ByteBuffer, inLen: Long,
+                                 inOffsets: java.nio.ByteBuffer, to: java.nio.ByteBuffer, tripleBase: Int, tripleId: Array[Int],
+                                 maxPairs: Int, outcome: Array[Int], reply: Array[Int], outDeps: Array[Int],
+                                 result: Array[Int]): Int
   // one burst of PreAccept (kind 0) / Accept (1) / Commit (2) / Prepare (3) messages from peer replicas, message i to replica
   // to(i), in delivery order, instances repeated freely (handlePreAccept :1159-1289, handleAccept :1421-1511, handleCommit
   // :1567-1575, handlePrepare :1632-1757).  deps (m x n): a row starting with -1 on an Accept / a Commit = the triple is known

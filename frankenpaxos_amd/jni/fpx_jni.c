@@ -1515,6 +1515,67 @@ JNIEXPORT jint JNICALL Java_frankenpaxos_gpu_Native_epxWireLeaderTick(JNIEnv* en
   return st;
 }
 
+/* The context's key table (fpx_epx_keys_enable): key strings -> key ids on the device, arenaBytes for the strings */
+JNIEXPORT jint JNICALL Java_frankenpaxos_gpu_Native_epxKeysEnable(JNIEnv* env, jclass cls, jlong h, jlong arenaBytes) {
+  return fpx_epx_keys_enable((fpx_epx*)(intptr_t)h, arenaBytes);
+}
+
+/* One batch of key strings (fpx_epx_keys_intern): string p = bytes[off[p] .. off[p] + len[p]) (UTF-8, as the wire has it)
+ * -> ids[p]; new strings get the next ids in order of first occurrence.  Nothing is applied on a status other than 0 */
+JNIEXPORT jint JNICALL Java_frankenpaxos_gpu_Native_epxKeysIntern(JNIEnv* env, jclass cls, jlong h, jint count, jbyteArray bytes,
+                                                                  jlong bytesLen, jlongArray off, jintArray len, jintArray ids) {
+  if (count < 0 || bytesLen < 0 || !h) return FPX_EINVAL;
+  if (count == 0) return FPX_OK;
+  if (!has(env, off, count) || !has(env, len, count) || !has(env, ids, count) || (bytesLen > 0 && !has(env, bytes, bytesLen)))
+    return FPX_EINVAL;
+  jbyte* b = bytesLen > 0 ? in_bytes(env, bytes, bytesLen) : NULL;
+  jlong* o = in_longs(env, off, count);
+  jint *l = in_ints(env, len, count), *out = out_buf(ids, count, 4);
+  int32_t st = ((bytesLen > 0 && !b) || !o || !l || !out)
+                   ? FPX_ENOMEM
+                   : fpx_epx_keys_intern((fpx_epx*)(intptr_t)h, (const uint8_t*)b, bytesLen, (const int64_t*)o, l, count, out);
+  if (st == FPX_OK) put_ints(env, ids, count, out);
+  free(b); free(o); free(l); free(out);
+  return st;
+}
+
+/* One tick of hosted EPaxos replicas from wire bytes (fpx_wire_epx_replica_tick): in (inLen bytes), inOffsets (m + 1 longs) and
+ * to (m ints) are direct ByteBuffers in native byte order, as epxWireLeaderTick's; tripleId (m ints, may be null: tripleBase +
+ * i, -1 for a Prepare); the outputs are epxReplicaInboxMk's (each may be null): outcome m; reply = ballot | PrepareOk status |
+ * values end | triple id (4 x m); outDeps m x n.  result[2] (may be null): the bad index (-1, or on FPX_EINVAL the message the
+ * tick was refused for) and the number of (message, key) pairs */
+JNIEXPORT jint JNICALL Java_frankenpaxos_gpu_Native_epxWireReplicaTick(JNIEnv* env, jclass cls, jlong h, jint m, jint numReplicas,
+                                                                       jobject in, jlong inLen, jobject inOffsets, jobject to,
+                                                                       jint tripleBase, jintArray tripleId, jint maxPairs,
+                                                                       jintArray outcome, jintArray reply, jintArray outDeps,
+                                                                       jintArray result) {
+  if (m < 0 || inLen < 0 || maxPairs < 0 || numReplicas < 3 || !epx_n_is(h, numReplicas)) return FPX_EINVAL;
+  const jlong mn = (jlong)m * numReplicas;
+  if (!opt(env, result, 2) || !opt(env, outcome, m) || !opt(env, reply, 4 * (jlong)m) || !opt(env, outDeps, mn) ||
+      !opt(env, tripleId, m))
+    return FPX_EINVAL;
+  int bad = 0;
+  const uint8_t* i = direct(env, in, inLen, &bad);
+  const int64_t* io = direct(env, inOffsets, 8 * ((jlong)m + 1), &bad);
+  const int32_t* t = direct(env, to, 4 * (jlong)m, &bad);
+  if (bad || (m > 0 && (!io || !t || (inLen > 0 && !i)))) return FPX_EINVAL;
+  jint* tr = (tripleId && m > 0) ? in_ints(env, tripleId, m) : NULL;
+  jint *oc = out_buf(outcome, m, 4), *rp = out_buf(reply, 4 * (jlong)m, 4), *od = out_buf(outDeps, mn, 4);
+  jint res[2] = {-1, 0};
+  const size_t sm = (size_t)m;
+  int32_t st = m > 0 && ((tripleId && !tr) || (outcome && !oc) || (reply && !rp) || (outDeps && !od))
+                   ? FPX_ENOMEM
+                   : fpx_wire_epx_replica_tick((fpx_epx*)(intptr_t)h, i, inLen, io, m, t, tripleBase, tr, maxPairs, oc, rp,
+                                               rp ? rp + sm : NULL, od, rp ? rp + 2 * sm : NULL, rp ? rp + 3 * sm : NULL,
+                                               &res[0], &res[1]);
+  if (st == FPX_OK) {
+    put_ints(env, outcome, m, oc); put_ints(env, reply, 4 * (jlong)m, rp); put_ints(env, outDeps, mn, od);
+  }
+  put_ints(env, result, 2, res);
+  free(tr); free(oc); free(rp); free(od);
+  return st;
+}
+
 /* K8 Replica.handlePrepareOk (epaxos/Replica.scala:1759-1884): prepareOk = epxPrepare's output (status | voteBallot |
  * triple, 3 x m x numReplicas), respMask = its okBits; decision = action | source | triple (3 x m ints) */
 JNIEXPORT jint JNICALL Java_frankenpaxos_gpu_Native_epxHandlePrepareOks(JNIEnv* env, jclass cls, jlong h, jint m,

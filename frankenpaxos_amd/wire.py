@@ -82,6 +82,17 @@ def _L():
         for name in ("fpx_wire_epaxos_decode_replica_inbound_folded", "fpx_wire_epaxos_decode_replica_inbound_dev",
                      "fpx_wire_epx_leader_tick_dev", "fpx_wire_epx_leader_tick"):
             getattr(L, name).restype = C.c_int32
+        # the replica's inbox from wire bytes: the host classify, the table's hash, and the device calls (EPaxos.wire_*)
+        L.fpx_wire_epx_classify.argtypes = [VP, C.c_int64, VP, VP, C.c_int32, C.c_int32] + [VP] * 6 + [I32P]
+        L.fpx_wire_epx_classify.restype = C.c_int32
+        L.fpx_wire_epx_key_hash.argtypes = [VP, C.c_int64]
+        L.fpx_wire_epx_key_hash.restype = C.c_uint64
+        L.fpx_wire_epx_classify_dev.argtypes = [VP, VP, C.c_int64, VP, VP, C.c_int32, C.c_int32] + [VP] * 6
+        L.fpx_wire_epx_replica_tick_dev.argtypes = [VP, VP, C.c_int64, VP, C.c_int32, VP, C.c_int32, VP, C.c_int32] + [VP] * 8
+        L.fpx_wire_epx_replica_tick.argtypes = [VP, VP, C.c_int64, VP, C.c_int32, VP, C.c_int32, VP, C.c_int32] + [VP] * 6 + \
+            [I32P, I32P]
+        for name in ("fpx_wire_epx_classify_dev", "fpx_wire_epx_replica_tick_dev", "fpx_wire_epx_replica_tick"):
+            getattr(L, name).restype = C.c_int32
         L.fpx_wire_phase2b_rows.argtypes = [C.c_int32, VP, VP, VP, VP, VP, C.c_int32, I32P, VP, VP, VP]
         L.fpx_wire_encode_proxy_leader_phase2a.argtypes = [VP, C.c_int64, C.c_int32, C.c_int32, VP, C.c_int32, C.c_int32]
         L.fpx_wire_encode_acceptor_phase2a.argtypes = [VP, C.c_int64, C.c_int32, C.c_int32, VP, C.c_int32, C.c_int32]
@@ -397,4 +408,37 @@ def epaxos_decode_replica_inbound_folded(messages, num_replicas=7, offsets=None,
         buf.ctypes.data, sum(len(m) for m in messages), off.ctypes.data, n, num_replicas,
         *[out[k].ctypes.data if k in out else None for k in EPX_FOLDED_NAMES], C.byref(bad))
     out["status_code"], out["bad_index"], out["buf"] = st, bad.value, buf
+    return out
+
+
+def epx_key_hash(key):
+    """fpx_wire_epx_key_hash: FNV-1a 64 of a key's bytes, the hash of the device key table (csrc/fpx_intern.hpp)"""
+    b = np.frombuffer(bytes(key), np.uint8)
+    return int(_L().fpx_wire_epx_key_hash(b.ctypes.data if len(b) else None, len(b)))
+
+
+def epx_classify(buf, cmd_off, cmd_len, max_pairs=None):
+    """fpx_wire_epx_classify, the host classify of serialised CommandOrNoops in buf (uint8 array): a dict of key_offsets
+    [m + 1], pair_off / pair_len (where pair j's key lies in buf), keys (the pairs' key strings as bytes), is_set (uint8),
+    is_noop, cmd_shape, status_code and bad_index.  max_pairs None: sized by a first call"""
+    buf = np.ascontiguousarray(buf, np.uint8)
+    cmd_off, cmd_len = np.ascontiguousarray(cmd_off, np.int64), np.ascontiguousarray(cmd_len, np.int32)
+    m = len(cmd_off)
+    out = {"key_offsets": np.zeros(m + 1, np.int32), "is_set": np.zeros(m, np.uint8), "is_noop": np.zeros(m, np.int32),
+           "cmd_shape": np.zeros(m, np.int32)}
+    bad = C.c_int32(-1)
+    cap = 0 if max_pairs is None else max_pairs
+    while True:
+        po, pl = np.zeros(max(cap, 1), np.int64), np.zeros(max(cap, 1), np.int32)
+        st = _L().fpx_wire_epx_classify(buf.ctypes.data, len(buf), cmd_off.ctypes.data, cmd_len.ctypes.data, m, cap,
+                                        out["key_offsets"].ctypes.data, po.ctypes.data, pl.ctypes.data, out["is_set"].ctypes.data,
+                                        out["is_noop"].ctypes.data, out["cmd_shape"].ctypes.data, C.byref(bad))
+        if st == _lib.FPX_ECAPACITY and max_pairs is None:
+            cap = int(out["key_offsets"][m])
+            continue
+        break
+    P = min(cap, int(out["key_offsets"][m])) if st in (0, _lib.FPX_ECAPACITY) else 0
+    out["pair_off"], out["pair_len"] = po[:P], pl[:P]
+    out["keys"] = [buf[int(o):int(o) + int(n)].tobytes() for o, n in zip(po[:P], pl[:P])] if st == 0 else []
+    out["status_code"], out["bad_index"] = st, bad.value
     return out

@@ -1161,6 +1161,37 @@ int32_t fpx_epx_replica_inbox_mk_dev(fpx_epx* epx, int32_t m, const int32_t* d_k
                                      const int32_t* d_deps, const int32_t* d_deps_values_end, int32_t* d_outcome,
                                      int32_t* d_out_ballot, int32_t* d_out_status, int32_t* d_out_deps,
                                      int32_t* d_out_values_end, int32_t* d_out_triple);
+/* ---- the key table: equal key strings, equal key ids, on the device ------------------------------------------------------
+ * Every entry point above takes key ids in [0, num_keys) and leaves the mapping from key strings to the caller; on the JVM
+ * that is GpuEPaxosEngine.keyOf (jni/EPaxosNative.scala), a mutable.Map[String, Int].  A context that calls
+ * fpx_epx_keys_enable keeps that map on the device (csrc/fpx_intern.hpp): an open-addressing table of
+ * max(16, the power of two >= 2 x num_keys) slots under FNV-1a 64 with linear probing, the keys' bytes in an arena of
+ * arena_bytes (< 2^31).  Opt-in: a context that never enables it is what it was.  A second call: FPX_EINVAL.
+ *
+ * fpx_epx_keys_intern: ONE batch of P strings, string p = bytes[off[p] .. off[p] + len[p]) -> ids[p].  Equal strings get
+ * equal ids (keys are bytes, compared as bytes: no Unicode normalisation; the empty string is a key like any other); a
+ * string the table does not hold gets the next id -- count, count + 1, ... in order of FIRST OCCURRENCE in the batch, so the
+ * ids are a function of the input alone.  Ids are never reused and the table only grows.  Identity is always the byte
+ * compare; the hash picks the home slot and nothing else.
+ * FPX_EINVAL with nothing applied: a string outside the buffer or longer than FPX_EPX_KEY_MAX_LEN; P > FPX_EPX_MK_MAX_PAIRS;
+ * a context without the table.  FPX_ECAPACITY with nothing applied (the same batch without its offender then succeeds):
+ * more than num_keys distinct keys, or more than arena_bytes of them.  An error already raised on the context in front of
+ * a _dev batch refuses it as well.  P = 0 is FPX_OK.
+ * fpx_epx_keys_intern_dev: device pointers on the context's stream, no host wait; status through fpx_epx_sync; the ids
+ * of a refused batch are -1.
+ * fpx_epx_keys_count: the ids handed out and the arena bytes used (either may be NULL); waits for the stream.
+ * fpx_epx_keys_read: ids first_id .. first_id + n - 1 back as bytes, for tests and for a JVM that warms its cache:
+ * key_off_out[n + 1] (key j = bytes_out[key_off_out[j] .. key_off_out[j + 1])) and the bytes.  cap too small:
+ * FPX_ECAPACITY with key_off_out filled, key_off_out[n] = the capacity needed (the convention of
+ * fpx_wire_epaxos_decode_replica_inbound) -- call again.  Ids the table has not handed out: FPX_EINVAL. */
+#define FPX_EPX_KEY_MAX_LEN 4096
+int32_t fpx_epx_keys_enable(fpx_epx* epx, int64_t arena_bytes);
+int32_t fpx_epx_keys_count(fpx_epx* epx, int32_t* count, int64_t* arena_used);
+int32_t fpx_epx_keys_intern_dev(fpx_epx* epx, const uint8_t* d_bytes, int64_t bytes_len, const int64_t* d_off,
+                                const int32_t* d_len, int32_t P, int32_t* d_ids);
+int32_t fpx_epx_keys_intern(fpx_epx* epx, const uint8_t* bytes, int64_t bytes_len, const int64_t* off, const int32_t* len,
+                            int32_t P, int32_t* ids);
+int32_t fpx_epx_keys_read(fpx_epx* epx, int32_t first_id, int32_t n, int32_t* key_off_out, uint8_t* bytes_out, int64_t cap);
 /* readback (parity) of one leader state: out[0] = phase (0 none, 1 PreAccepting, 2 Accepting, 3 Preparing; 0 when not live),
  * out[1] = ballot, out[2] = avoidFastPath, out[3] = triple id, out[4] = the key word as stored (the key; -1 for a Noop
  * or a command without keys; FPX_EPX_KEY_LIST for a list of two or more distinct keys), out[5] = is_set, out[6] = who has answered (bit

@@ -480,6 +480,75 @@ int32_t fpx_wire_epx_leader_tick(struct fpx_epx* epx, const uint8_t* in, int64_t
                                  int32_t* out_values_end, int32_t* out_triple, int32_t* decided_index,
                                  int32_t* num_decided, int32_t* bad_index);
 
+/* ---- a replica's inbox from wire bytes ------------------------------------------------------------------------------
+ * The counterpart of fpx_wire_epx_leader_tick for what peer replicas SEND hosted replicas: PreAccept, Accept, Commit and
+ * Prepare.  Three of them carry a command, whose keys EPaxosNative.scala's classify reads with
+ * KeyValueStoreInput.parseFrom and keyOf turns into ids on the JVM; here both happen on the device, against the context's
+ * key table (include/fpx.h, fpx_epx_keys_enable -- without it every call below is FPX_EINVAL).
+ *
+ * The command's key list (csrc/fpx_epx_cmd_parse.hpp, one source for host and device), from the serialised CommandOrNoop
+ * the decoders locate (cmd_off / cmd_len): CommandOrNoop { command = 1 | noop = 2 } -> Command.command (field 4) ->
+ * KeyValueStoreInput { get_request = 1 { repeated key = 1 } | set_request = 2 { repeated { key = 1; value = 2 } } }.
+ *   cmd_shape 1   canonical: exactly one member in CommandOrNoop; a Command with its four fields, `command` exactly once;
+ *                 exactly one request member; every pair exactly one key (and a value); no unknown field and no other
+ *                 wire type on the way down; no key longer than FPX_EPX_KEY_MAX_LEN.  is_noop / is_set say which, the keys
+ *                 are reported in wire order.  A request without keys is shape 1 with an empty list, which the _mk calls
+ *                 treat like a Noop.
+ *   cmd_shape 0   anything else that is well-formed protobuf (ScalaPB would merge repeated members or take the last one;
+ *                 Request.Empty; a required field missing): that frame is the JVM's, as deps_shape 0 frames are.  is_noop
+ *                 = is_set = 0, no keys.
+ *   malformed     truncated, a length running past its parent, a bad wire type: an error, as in the decoders.
+ *   cmd_len[i] < 0: the message has no command (a Prepare): an empty list, is_noop = cmd_shape = -1.
+ *
+ * fpx_wire_epx_classify: the host classify (g++-compiled, no GPU): key_offsets[m + 1] and, for pair j of the burst, where
+ * its key lies in buf (pair_off[j], pair_len[j]; either may be NULL) -- the caller maps strings to ids.  FPX_EINVAL with
+ * *bad_index: the first malformed command (or one outside buf).  FPX_ECAPACITY: more than max_pairs pairs;
+ * key_offsets[m] says how many.
+ * fpx_wire_epx_key_hash: the table's hash (FNV-1a 64), for tests that choose colliding keys.
+ *
+ * fpx_wire_epx_classify_dev: the same on the device, and the ids: count -> scan -> parse again -> intern -> d_key_offsets
+ * [m + 1] / d_keys[max_pairs], the CSR the _mk calls take; d_is_set as they take it.  d_result, 4 words: the bad index (-1
+ * = none), num_pairs, the new keys and the new bytes this call interned.  No host wait; status through fpx_epx_sync:
+ * FPX_EINVAL (a malformed command, d_result[0]) or FPX_ECAPACITY (more than max_pairs pairs -- d_result[1] says how many
+ * -- or the key table's limits), NOTHING interned either way.  Shape-0 commands are reported, not refused.  buf_len <
+ * 2^31, m <= FPX_EPX_INBOX_MAX, max_pairs <= FPX_EPX_MK_MAX_PAIRS.
+ *
+ * fpx_wire_epx_replica_tick[_dev]: one tick of hosted replicas, bytes -> outputs (Replica.scala:1159-1289, 1421-1511,
+ * 1567-1575, 1632-1757 through fpx_epx_replica_inbox_mk).  m serialised ReplicaInbound messages, to[i] the replica that
+ * received message i; the CommandTriple id of message i is triple_id[i], or with triple_id NULL triple_base + i (-1 for a
+ * Prepare).  Stage 1, enqueued without a wait: the decoder, a check (PreAccept, Accept, Commit -- deps_num_replicas == n,
+ * deps_shape == 1, cmd_shape == 1 -- and Prepare; the ballot's fields and the instance go in as decoded), the classify
+ * above.  Then ONE host wait for the pair count and the status -- as fpx_epx_preaccept_mk_dev waits for its pair count,
+ * so the tick CANNOT be captured into a HIP graph -- and stage 2: fpx_epx_replica_inbox_mk_dev's launches on the decoded
+ * arrays.  An Accept or a Commit always passes its decoded dependencies (the by-id form is never produced).
+ * The outputs are those of fpx_epx_replica_inbox_mk (any may be NULL; the host form holds them as that call does), then
+ * the bad index and num_pairs.  Refusals, in this order, each with nothing applied to the command logs or the index:
+ *   FPX_EINVAL, the lowest offending index, nothing interned: a bad offset (judged first); a malformed message or
+ *                 command; a message of another kind; deps_shape or cmd_shape 0
+ *   FPX_ECAPACITY, nothing interned: more than max_pairs pairs (num_pairs says how many), the key table's limits
+ *   FPX_EINVAL, bad index -1: a burst that stage 1 accepts and fpx_epx_replica_inbox_mk_dev refuses (an instance outside
+ *                 the log, a watermark rule, ...).  The keys of THAT burst stay interned: ids are never reused and the
+ *                 table only grows.
+ * m = 0 is FPX_OK.  The _dev form returns what enqueueing returns; its status comes through fpx_epx_sync. */
+int32_t fpx_wire_epx_classify(const uint8_t* buf, int64_t buf_len, const int64_t* cmd_off, const int32_t* cmd_len, int32_t m,
+                              int32_t max_pairs, int32_t* key_offsets, int64_t* pair_off, int32_t* pair_len,
+                              uint8_t* is_set, int32_t* is_noop, int32_t* cmd_shape, int32_t* bad_index);
+uint64_t fpx_wire_epx_key_hash(const uint8_t* bytes, int64_t len);
+int32_t fpx_wire_epx_classify_dev(struct fpx_epx* epx, const uint8_t* d_buf, int64_t buf_len, const int64_t* d_cmd_off,
+                                  const int32_t* d_cmd_len, int32_t m, int32_t max_pairs, int32_t* d_key_offsets,
+                                  int32_t* d_keys, uint8_t* d_is_set, int32_t* d_is_noop, int32_t* d_cmd_shape,
+                                  int32_t* d_result);
+int32_t fpx_wire_epx_replica_tick_dev(struct fpx_epx* epx, const uint8_t* d_in, int64_t in_len, const int64_t* d_in_offsets,
+                                      int32_t m, const int32_t* d_to, int32_t triple_base, const int32_t* d_triple_id,
+                                      int32_t max_pairs, int32_t* d_outcome, int32_t* d_out_ballot, int32_t* d_out_status,
+                                      int32_t* d_out_deps, int32_t* d_out_values_end, int32_t* d_out_triple,
+                                      int32_t* d_bad_index, int32_t* d_num_pairs);
+int32_t fpx_wire_epx_replica_tick(struct fpx_epx* epx, const uint8_t* in, int64_t in_len, const int64_t* in_offsets,
+                                  int32_t m, const int32_t* to, int32_t triple_base, const int32_t* triple_id,
+                                  int32_t max_pairs, int32_t* outcome, int32_t* out_ballot, int32_t* out_status,
+                                  int32_t* out_deps, int32_t* out_values_end, int32_t* out_triple, int32_t* bad_index,
+                                  int32_t* num_pairs);
+
 #ifdef __cplusplus
 }
 #endif
