@@ -1385,6 +1385,7 @@ __global__ void __launch_bounds__(256) k_hp_commit(const EpxState st, const HpBa
 #include "fpx_epx_inbox.hpp"
 #include "fpx_intern.hpp"
 #include "fpx_wire_epx_dev.hpp"
+#include "fpx_wire_epx_enc_dev.hpp"
 
 }  // namespace
 
@@ -1416,6 +1417,8 @@ struct fpx_epx {
   DevBuf wire_misc;                       // fpx_wire_epx_leader_tick_dev: the decoded arrays of the tick
   InternTable keys = {};                  // fpx_epx_keys_enable: the key table (fpx_intern.hpp), else not allocated
   DevBuf keys_misc, rt_misc;              // fpx_epx_keys_intern_dev: lay_intern; the classify and the replica tick: their layouts
+  DevBuf enc_misc;                        // fpx_wire_epx_encode_replica_replies_dev and the bytes tick: their layouts
+  bool enc_direct = false;                // FPX_EPX_ENC_DIRECT: the reply encoder's direct form for every wavefront
   bool lds_allowed = false, sort_lds_allowed = false;
   int num_cus = 256;
 };
@@ -1992,6 +1995,7 @@ int32_t fpx_epx_create(const fpx_epx_config* cfg, fpx_epx** out) {
     (void)hipGetLastError();
   }
   e->kp_off = getenv("FPX_EPX_V1") != nullptr;
+  e->enc_direct = getenv("FPX_EPX_ENC_DIRECT") != nullptr;
   if (hipMalloc((void**)&e->census_dev, EPX_CD_WORDS * 8) != hipSuccess) return fail(FPX_ENOMEM);
   if (hipMemsetAsync(e->census_dev, 0, EPX_CD_WORDS * 8, e->stream) != hipSuccess) return fail(FPX_EHIP);
   if (hipStreamSynchronize(e->stream) != hipSuccess) return fail(FPX_EHIP);
@@ -2009,7 +2013,7 @@ int32_t fpx_epx_destroy(fpx_epx* e) {
   for (void* p : ps)
     if (p) (void)hipFree(p);
   DevBuf* bs[] = {&e->kv, &e->kv2, &e->seg, &e->conf, &e->tmp, &e->tick, &e->fusedb, &e->metab, &e->mk_misc, &e->mk_rec,
-                  &e->mk_pair, &e->mk_pconf, &e->lr_misc, &e->ri_misc, &e->wire_misc, &e->keys_misc, &e->rt_misc};
+                  &e->mk_pair, &e->mk_pconf, &e->lr_misc, &e->ri_misc, &e->wire_misc, &e->keys_misc, &e->rt_misc, &e->enc_misc};
   for (DevBuf* b : bs)
     if (b->p) (void)hipFree(b->p);
   free_stage(&e->stage);
@@ -2034,14 +2038,15 @@ int32_t fpx_epx_set_stream(fpx_epx* e, void* hip_stream) {
 int32_t fpx_epx_sync(fpx_epx* e) {
   if (!e) return FPX_EINVAL;
   DeviceScope _dg(e->cfg.device);
-  int32_t h[2] = {0, 0};
+  int32_t h[EPX_ST_ENC + 1] = {};
   HIPCHK(e, hipMemcpyAsync(h, e->st.status, sizeof(h), hipMemcpyDeviceToHost, e->stream));
   HIPCHK(e, hipStreamSynchronize(e->stream));
-  if (h[0] != 0) {
+  if (h[0] != 0 || h[EPX_ST_ENC] != 0) {
     HIPCHK(e, hipMemsetAsync(e->st.status, 0, 32, e->stream));
     HIPCHK(e, hipStreamSynchronize(e->stream));
   }
-  return h[0];
+  // (the reply encoder's per-call code, fpx_wire_epx_enc_dev.hpp: reported when nothing else is)
+  return h[0] != 0 ? h[0] : h[EPX_ST_ENC];
 }
 
 // key lists (the _mk entry points): key_off[0] = 0, non-decreasing, at most FPX_EPX_MK_MAX_PAIRS keys, each in [0, num_keys)
@@ -3378,10 +3383,12 @@ int32_t fpx_wire_epx_classify_dev(fpx_epx* e, const uint8_t* d_buf, int64_t buf_
 // (fpx_epx_replica_inbox_mk_dev's launches on the decoded arrays); o: `to` and the outputs
 static int32_t replica_tick_impl(fpx_epx* e, const uint8_t* d_in, int64_t in_len, const int64_t* d_in_offsets, int32_t triple_base,
                                  const int32_t* d_triple_id, int32_t max_pairs, RiBatch o, int32_t* d_bad_index,
-                                 int32_t* d_num_pairs) {
+                                 int32_t* d_num_pairs, EpxReplicaTickScratch* decoded = nullptr, bool* stage2 = nullptr) {
+  // (the bytes tick: *decoded = the tick's decoded arrays, *stage2 = whether stage 1 let the burst through)
   const int32_t m = o.m;
   EpxReplicaTickScratch w;
   int rc;
+  if (stage2) *stage2 = false;
   if ((rc = carve(e, &e->rt_misc, &w,
                   [&](Carver& c) { return lay_epx_replica_tick(c, (size_t)m, (size_t)e->st.n, (size_t)max_pairs); })))
     return rc;
@@ -3404,6 +3411,8 @@ static int32_t replica_tick_impl(fpx_epx* e, const uint8_t* d_in, int64_t in_len
   HIPCHK(e, hipStreamSynchronize(e->stream));
   if (h[4] != 0) return FPX_OK;  // refused: the status stays on the context for fpx_epx_sync
   if (h[1] < 0 || h[1] > max_pairs) return FPX_EHIP;
+  if (decoded) *decoded = w;
+  if (stage2) *stage2 = true;
   o.kind = w.ri_kind, o.leader = w.leader, o.number = w.number, o.b_ord = w.b_ord, o.b_rep = w.b_rep;
   o.key_off = w.key_offsets, o.keys = w.keys, o.P = h[1], o.is_set = w.is_set, o.triple = w.triple, o.deps = w.deps, o.dend = w.dend;
   return replica_inbox_launch<true>(e, o);
@@ -3462,6 +3471,184 @@ int32_t fpx_wire_epx_replica_tick(fpx_epx* e, const uint8_t* in_bytes, int64_t i
   // (the two words come down whatever the status; the bad index means something on FPX_EINVAL)
   if (bad_index && rc == FPX_EINVAL) *bad_index = res[0];
   if (num_pairs) *num_pairs = res[1];
+  return rc;
+}
+
+// ---- the replies of a replica tick as wire bytes: csrc/fpx_wire_epx_enc_dev.hpp (include/fpx_wire.h) ---------------------------
+// a: the records and the outputs; the scratch fields are filled here
+static int32_t reply_encode_launch(fpx_epx* e, EreArgs a, const EpxReplyEncScratch& s) {
+  static_assert(ERE_C_WORDS == EPX_REPLY_ENC_CTL_WORDS, "a call's control words as lay_epx_reply_enc sizes them");
+  const size_t rows = scan_rows((size_t)a.m);
+  a.in.n = e->st.n, a.rows = (int32_t)rows, a.direct = e->enc_direct ? 1 : 0;
+  a.lscan = s.lscan, a.ltot = s.ltot, a.lgt = s.lgt, a.ctl = s.ctl;
+  HIPCHK(e, hipMemsetAsync(a.ctl, 0, ERE_C_WORDS * 4, e->stream));
+  HIPCHK(e, hipMemsetAsync(a.ctl + ERE_C_BAD, ERE_NO_BAD & 0xff, 4, e->stream));
+  const dim3 blk(ERE_BLOCK);
+  if (rows) {
+    hipLaunchKernelGGL(k_ere_len, dim3((unsigned)(rows * INTERN_ROW / ERE_BLOCK)), blk, 0, e->stream, a);
+    scan_rows_launch(e, a.lscan, rows, a.ltot, a.lgt);
+  }
+  hipLaunchKernelGGL(k_ere_decide, dim3(1), dim3(256), 0, e->stream, e->st, a);
+  if (rows) hipLaunchKernelGGL(k_ere_emit, dim3((unsigned)((a.m + ERE_BLOCK - 1) / ERE_BLOCK)), blk, 0, e->stream, a);
+  return FPX_OK;
+}
+
+static int32_t reply_encode_check(const fpx_epx* e, int32_t m, const uint8_t* d_out, int64_t cap, const int64_t* d_out_offsets,
+                                  const uint8_t* d_reply_kind, const int64_t* d_totals) {
+  return !e || m < 0 || m > FPX_EPX_INBOX_MAX || cap < 0 || (cap > 0 && !d_out) || !d_out_offsets || !d_totals ||
+                 (m > 0 && !d_reply_kind)
+             ? FPX_EINVAL
+             : FPX_OK;
+}
+
+int32_t fpx_wire_epx_encode_replica_replies_dev(fpx_epx* e, int32_t m, const int32_t* d_to, const int32_t* d_leader,
+                                                const int32_t* d_number, const int32_t* d_ballot_ordering,
+                                                const int32_t* d_ballot_replica, const int32_t* d_outcome,
+                                                const int32_t* d_out_ballot, const int32_t* d_out_status,
+                                                const int32_t* d_out_deps, const int32_t* d_out_values_end, uint8_t* d_out,
+                                                int64_t cap, int64_t* d_out_offsets, uint8_t* d_reply_kind, int64_t* d_totals) {
+  if (reply_encode_check(e, m, d_out, cap, d_out_offsets, d_reply_kind, d_totals)) return FPX_EINVAL;
+  if (m > 0 && (!d_to || !d_leader || !d_number || !d_ballot_ordering || !d_ballot_replica || !d_outcome || !d_out_ballot ||
+                !d_out_status || !d_out_deps || !d_out_values_end))
+    return FPX_EINVAL;
+  DeviceScope _dg(e->cfg.device);
+  EpxReplyEncScratch s;
+  EreArgs a;
+  memset(&a, 0, sizeof(a));
+  a.m = m;
+  int rc;
+  if ((rc = carve(e, &e->enc_misc, &s, [&](Carver& c) { return lay_epx_reply_enc(c, (size_t)m); })))
+    return rc;
+  a.in = fpxw::EpxReplyIn{e->st.n,   d_to,         d_leader,     d_number,   d_ballot_ordering, d_ballot_replica,
+                          d_outcome, d_out_ballot, d_out_status, d_out_deps, d_out_values_end};
+  a.out = d_out, a.cap = cap, a.out_offsets = d_out_offsets, a.reply_kind = d_reply_kind, a.totals = d_totals;
+  rc = reply_encode_launch(e, a, s);
+  return rc ? rc : launch_check(e);
+}
+
+// replica_tick_impl, then the encoder on the decoded arrays the tick holds in scratch and on the inbox outputs -- the
+// caller's where it asks for them, the tick's own otherwise.  o: `to` and the optional outputs; a: the encoder's outputs
+static int32_t replica_tick_bytes_impl(fpx_epx* e, const uint8_t* d_in, int64_t in_len, const int64_t* d_in_offsets,
+                                       int32_t triple_base, const int32_t* d_triple_id, int32_t max_pairs, RiBatch o, EreArgs a,
+                                       int32_t* d_bad_index, int32_t* d_num_pairs, bool* stage2) {
+  const int32_t m = o.m;
+  EpxTickBytesScratch t;
+  int rc;
+  if ((rc = carve(e, &e->enc_misc, &t, [&](Carver& c) { return lay_epx_tick_bytes(c, (size_t)m, (size_t)e->st.n); }))) return rc;
+  if (!o.outcome) o.outcome = t.outcome;
+  if (!o.out_ballot) o.out_ballot = t.out_ballot;
+  if (!o.out_status) o.out_status = t.out_status;
+  if (!o.out_end) o.out_end = t.out_end;
+  if (!o.out_deps) o.out_deps = t.out_deps;
+  // a refused tick encodes nothing: the totals and the first offset say so unless the encoder runs
+  HIPCHK(e, hipMemsetAsync(a.totals, 0, 24, e->stream));
+  HIPCHK(e, hipMemsetAsync(a.totals + 3, 0xFF, 8, e->stream));
+  HIPCHK(e, hipMemsetAsync(a.out_offsets, 0, 8, e->stream));
+  EpxReplicaTickScratch w;
+  if ((rc = replica_tick_impl(e, d_in, in_len, d_in_offsets, triple_base, d_triple_id, max_pairs, o, d_bad_index, d_num_pairs, &w,
+                              stage2)) ||
+      !*stage2)
+    return rc;
+  a.m = m;
+  a.in = fpxw::EpxReplyIn{e->st.n,   o.to,         w.leader,     w.number,   w.b_ord,  w.b_rep,
+                          o.outcome, o.out_ballot, o.out_status, o.out_deps, o.out_end};
+  return reply_encode_launch(e, a, t.enc);
+}
+
+int32_t fpx_wire_epx_replica_tick_bytes_dev(fpx_epx* e, const uint8_t* d_in, int64_t in_len, const int64_t* d_in_offsets,
+                                            int32_t m, const int32_t* d_to, int32_t triple_base, const int32_t* d_triple_id,
+                                            int32_t max_pairs, uint8_t* d_out, int64_t out_cap, int64_t* d_out_offsets,
+                                            uint8_t* d_reply_kind, int64_t* d_totals, int32_t* d_outcome, int32_t* d_out_ballot,
+                                            int32_t* d_out_status, int32_t* d_out_deps, int32_t* d_out_values_end,
+                                            int32_t* d_out_triple, int32_t* d_bad_index, int32_t* d_num_pairs) {
+  if (replica_tick_check(e, in_len, m, max_pairs) || !d_bad_index ||
+      reply_encode_check(e, m, d_out, out_cap, d_out_offsets, d_reply_kind, d_totals))
+    return FPX_EINVAL;
+  DeviceScope _dg(e->cfg.device);
+  if (m == 0) {
+    HIPCHK(e, hipMemsetAsync(d_bad_index, 0xFF, 4, e->stream));
+    if (d_num_pairs) HIPCHK(e, hipMemsetAsync(d_num_pairs, 0, 4, e->stream));
+    HIPCHK(e, hipMemsetAsync(d_totals, 0, 24, e->stream));
+    HIPCHK(e, hipMemsetAsync(d_totals + 3, 0xFF, 8, e->stream));
+    HIPCHK(e, hipMemsetAsync(d_out_offsets, 0, 8, e->stream));
+    return FPX_OK;
+  }
+  if ((in_len > 0 && !d_in) || !d_in_offsets || !d_to) return FPX_EINVAL;
+  RiBatch o;
+  memset(&o, 0, sizeof(o));
+  o.m = m, o.to = d_to, o.outcome = d_outcome, o.out_ballot = d_out_ballot, o.out_status = d_out_status, o.out_deps = d_out_deps;
+  o.out_end = d_out_values_end, o.out_triple = d_out_triple;
+  EreArgs a;
+  memset(&a, 0, sizeof(a));
+  a.out = d_out, a.cap = out_cap, a.out_offsets = d_out_offsets, a.reply_kind = d_reply_kind, a.totals = d_totals;
+  bool stage2 = false;
+  const int rc = replica_tick_bytes_impl(e, d_in, in_len, d_in_offsets, triple_base, d_triple_id, max_pairs, o, a, d_bad_index,
+                                         d_num_pairs, &stage2);
+  return rc ? rc : launch_check(e);
+}
+
+// the host form's end: the encoder's FPX_ECAPACITY means the tick WAS applied, so the held outputs reach the caller then too
+// (stage 1's FPX_ECAPACITY -- too many pairs, the key table's limits -- applied nothing: *stage2 tells the two apart)
+struct EpxBytesEnd {
+  fpx_epx* e;
+  const bool* stage2;
+  int operator()() const { return fpx_epx_sync(e); }
+  bool applied(int rc) const { return EpxEnd::applied(rc) || (rc == FPX_ECAPACITY && *stage2); }
+};
+
+int32_t fpx_wire_epx_replica_tick_bytes(fpx_epx* e, const uint8_t* in_bytes, int64_t in_len, const int64_t* in_offsets, int32_t m,
+                                        const int32_t* to, int32_t triple_base, const int32_t* triple_id, int32_t max_pairs,
+                                        uint8_t* out_bytes, int64_t out_cap, int64_t* out_offsets, uint8_t* reply_kind,
+                                        int64_t* totals, int32_t* outcome, int32_t* out_ballot, int32_t* out_status,
+                                        int32_t* out_deps, int32_t* out_values_end, int32_t* out_triple, int32_t* bad_index,
+                                        int32_t* num_pairs) {
+  if (replica_tick_check(e, in_len, m, max_pairs) || reply_encode_check(e, m, out_bytes, out_cap, out_offsets, reply_kind, totals))
+    return FPX_EINVAL;
+  DeviceScope _dg(e->cfg.device);
+  if (bad_index) *bad_index = -1;
+  if (num_pairs) *num_pairs = 0;
+  totals[0] = totals[1] = totals[2] = 0, totals[3] = -1;
+  out_offsets[0] = 0;
+  if (m == 0) return FPX_OK;
+  if ((in_len > 0 && !in_bytes) || !in_offsets || !to) return FPX_EINVAL;
+  const size_t mn = (size_t)m * e->st.n;
+  const uint8_t* d_in = nullptr;
+  const int64_t* d_off = nullptr;
+  const int32_t* d_triple = nullptr;
+  int32_t *d_bad = nullptr, *d_np = nullptr;
+  int32_t res[2] = {-1, 0};
+  RiBatch o;
+  memset(&o, 0, sizeof(o));
+  o.m = m;
+  EreArgs a;
+  memset(&a, 0, sizeof(a));
+  a.cap = out_cap;
+  bool stage2 = false;
+  // an inbox output the caller leaves out is not staged: the tick keeps it in its own scratch
+  auto opt_held = [](int32_t*& d, int32_t* dst, size_t count) { return dst ? held(d, dst, count) : absent(d); };
+  // the reply bytes, offsets and kinds are scratch of the call: they come down behind it (below), the bytes the encoder wrote
+  // and no more, and only when it wrote them -- a refusal leaves the caller's arrays as they were
+  const int32_t rc = fpx::host_call(
+      e,
+      {in(d_in, in_bytes, (size_t)in_len), in(d_off, in_offsets, (size_t)m + 1), in(o.to, to, m), opt_in(d_triple, triple_id, m),
+       opt_held(o.outcome, outcome, m), opt_held(o.out_ballot, out_ballot, m), opt_held(o.out_status, out_status, m),
+       opt_held(o.out_end, out_values_end, m), opt_held(o.out_triple, out_triple, m), opt_held(o.out_deps, out_deps, mn),
+       scratch(a.out, (size_t)out_cap), scratch(a.out_offsets, (size_t)m + 1), scratch(a.reply_kind, m), out(a.totals, totals, 4),
+       out(d_bad, &res[0], 1), out(d_np, &res[1], 1)},
+      [&]() -> int {
+        return replica_tick_bytes_impl(e, d_in, in_len, d_off, triple_base, d_triple, max_pairs, o, a, d_bad, d_np, &stage2);
+      },
+      EpxBytesEnd{e, &stage2});
+  if (bad_index && rc == FPX_EINVAL) *bad_index = res[0];
+  if (num_pairs) *num_pairs = res[1];
+  if (rc == FPX_OK || rc == FPX_EFATAL_PROTOCOL) {
+    HIPCHK(e, hipMemcpyAsync(out_offsets, a.out_offsets, ((size_t)m + 1) * 8, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(e, hipMemcpyAsync(reply_kind, a.reply_kind, (size_t)m, hipMemcpyDeviceToHost, e->stream));
+    if (totals[1] > 0) HIPCHK(e, hipMemcpyAsync(out_bytes, a.out, (size_t)totals[1], hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+  } else if (!(rc == FPX_ECAPACITY && stage2)) {
+    totals[0] = totals[1] = totals[2] = 0, totals[3] = -1;
+  }
   return rc;
 }
 

@@ -260,4 +260,35 @@ inline EpxReplicaTickScratch lay_epx_replica_tick(Carver& c, size_t m, size_t n,
   return s;
 }
 
+// fpx_wire_epx_enc_dev.hpp, the replies of m records: the replies' lengths and their scan in rows as above, with the rows'
+// sums and the total, and the call's control words.  (Under the sanitizers: tests/epx_reply_emit_main.cpp, as the layout
+// below.)
+constexpr int EPX_REPLY_ENC_CTL_WORDS = 4;
+struct EpxReplyEncScratch {
+  uint32_t* lscan;
+  int32_t *ltot, *lgt, *ctl;
+};
+inline EpxReplyEncScratch lay_epx_reply_enc(Carver& c, size_t m) {
+  EpxReplyEncScratch s;
+  s.lscan = c.take<uint32_t>(scan_rows(m) * INTERN_SCAN_ROW);
+  s.ltot = c.take<int32_t>(scan_rows(m));
+  s.lgt = c.take<int32_t>(1);
+  s.ctl = c.take<int32_t>(EPX_REPLY_ENC_CTL_WORDS);
+  return s;
+}
+
+// fpx_wire_epx_replica_tick_bytes_dev: the encoder's scratch, and the inbox outputs the encoder reads, which the tick keeps
+// here when the caller does not ask for them
+struct EpxTickBytesScratch {
+  EpxReplyEncScratch enc;
+  int32_t *outcome, *out_ballot, *out_status, *out_end, *out_deps;
+};
+inline EpxTickBytesScratch lay_epx_tick_bytes(Carver& c, size_t m, size_t n) {
+  EpxTickBytesScratch s;
+  s.enc = lay_epx_reply_enc(c, m);
+  for (int32_t** a : {&s.outcome, &s.out_ballot, &s.out_status, &s.out_end}) *a = c.take<int32_t>(m);
+  s.out_deps = c.take<int32_t>(m * n);
+  return s;
+}
+
 }  // namespace fpx

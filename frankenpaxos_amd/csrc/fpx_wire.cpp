@@ -11,6 +11,7 @@
 #include "fpx_epx_cmd_parse.hpp"
 #include "fpx_intern.hpp"
 #include "fpx_wire_emit.hpp"
+#include "fpx_wire_epx_emit.hpp"
 #include "fpx_wire_epx_parse.hpp"
 #include "fpx_wire_parse.hpp"
 
@@ -675,6 +676,42 @@ int64_t fpx_wire_epaxos_encode_replica_inbound(uint8_t* out, int64_t cap, const 
       }
     }
   });
+}
+
+// the replies of a replica tick, a burst at a time: the emitter and the decision table of fpx_wire_epx_emit.hpp, which the
+// device encoder (fpx_wire_epx_enc_dev.hpp) compiles too
+int32_t fpx_wire_epx_encode_replica_replies(int32_t n, int32_t m, const int32_t* to, const int32_t* leader, const int32_t* number,
+                                            const int32_t* ballot_ordering, const int32_t* ballot_replica, const int32_t* outcome,
+                                            const int32_t* out_ballot, const int32_t* out_status, const int32_t* out_deps,
+                                            const int32_t* out_values_end, uint8_t* out, int64_t cap, int64_t* out_offsets,
+                                            uint8_t* reply_kind, int64_t* totals) {
+  if (!totals) return FPX_EINVAL;
+  totals[0] = totals[1] = totals[2] = 0, totals[3] = -1;
+  if (n < 1 || m < 0 || m > FPX_EPX_INBOX_MAX || cap < 0 || !out_offsets || (cap > 0 && !out)) return FPX_EINVAL;
+  if (m > 0 && (!to || !leader || !number || !ballot_ordering || !ballot_replica || !outcome || !out_ballot || !out_status ||
+                !out_deps || !out_values_end || !reply_kind))
+    return FPX_EINVAL;
+  const EpxReplyIn a{n, to, leader, number, ballot_ordering, ballot_replica, outcome, out_ballot, out_status, out_deps, out_values_end};
+  int64_t encoded = 0, bytes = 0, deferred = 0;
+  out_offsets[0] = 0;
+  for (int32_t i = 0; i < m; ++i) {
+    const EpxReplyPlan p = epx_reply_plan(a, i);
+    if (p.kind == EPX_REPLY_UNKNOWN) {
+      totals[3] = i;
+      return FPX_EINVAL;
+    }
+    encoded += p.kind == EPX_REPLY_ENCODED, deferred += p.kind == EPX_REPLY_DEFERRED, bytes += p.len;
+  }
+  totals[0] = encoded, totals[1] = bytes, totals[2] = deferred;
+  if (bytes > cap) return FPX_ECAPACITY;
+  int64_t at = 0;
+  for (int32_t i = 0; i < m; ++i) {
+    const EpxReplyPlan p = epx_reply_plan(a, i);
+    reply_kind[i] = (uint8_t)p.kind;
+    if (p.kind == EPX_REPLY_ENCODED) at += epx_reply_emit(out + at, a, i, p.outcome);
+    out_offsets[i + 1] = at;
+  }
+  return FPX_OK;
 }
 
 int32_t fpx_wire_epaxos_decode_replica_inbound(const uint8_t* buf, int64_t buf_len, const int64_t* offsets, int32_t n,

@@ -525,6 +525,103 @@ class EPaxos:
         if st:
             raise FpxError(st, "fpx_wire_epx_replica_tick_dev")
 
+    # ---- a replica tick's replies as wire bytes ----
+    def encode_replica_replies_dev(self, to, leader, number, ballot_ordering, ballot_replica, outcome, out_ballot, out_status,
+                                   out_deps, out_values_end, out, cap, out_offsets, reply_kind, totals, m=None):
+        """fpx_wire_epx_encode_replica_replies_dev on device tensors (the ten record arrays int32, out uint8 or None for the
+        sizing call, out_offsets int64[m + 1], reply_kind uint8[m], totals int64[4]), enqueued: no host wait, the status comes
+        with sync().  m: the number of records (default: to.numel())"""
+        from . import wire
+        L = wire._L()
+        d = lambda t: None if t is None else t.data_ptr()
+        st = L.fpx_wire_epx_encode_replica_replies_dev(
+            self._h, to.numel() if m is None else m, d(to), d(leader), d(number), d(ballot_ordering), d(ballot_replica), d(outcome),
+            d(out_ballot), d(out_status), d(out_deps), d(out_values_end), d(out), cap, d(out_offsets), d(reply_kind), d(totals))
+        if st:
+            raise FpxError(st, "fpx_wire_epx_encode_replica_replies_dev")
+
+    def encode_replica_replies(self, cap=None, base_offset=0, **arrays):
+        """the device encoder on host arrays (the ten of wire.EPX_REPLY_RECORDS): upload, encode, sync, download.  The result
+        is wire.epx_encode_replica_replies's dict, with the same fills where the call writes nothing.  cap None: sized by a
+        first call; base_offset: the output starts that many bytes behind a 256-byte boundary"""
+        import torch
+
+        from . import wire
+        rec = wire.epx_reply_records(self.n, **arrays)
+        m = len(rec[0])
+        dev = torch.device("cuda", torch.cuda.current_device())
+        up = [torch.from_numpy(a.reshape(-1) if a.size else np.zeros(1, np.int32)).to(dev) for a in rec]
+        off = torch.full((m + 1,), -9, dtype=torch.int64, device=dev)
+        kind = torch.full((max(m, 1),), 9, dtype=torch.uint8, device=dev)
+        totals = torch.full((4,), -9, dtype=torch.int64, device=dev)
+        torch.cuda.synchronize()
+        if cap is None:
+            self.encode_replica_replies_dev(*up, None, 0, off, kind, totals, m=m)
+            st = self.sync()
+            if st not in (0, _lib.FPX_ECAPACITY):
+                return {"status_code": st, "out": np.zeros(0, np.uint8), "out_offsets": off.cpu().numpy(),
+                        "reply_kind": kind.cpu().numpy()[:m], "totals": totals.cpu().numpy(), "replies": []}
+            cap = int(totals.cpu()[1])
+            off.fill_(-9), kind.fill_(9)
+        buf = torch.full((base_offset + cap + 16,), 0xEE, dtype=torch.uint8, device=dev)
+        out = buf[base_offset:]
+        torch.cuda.synchronize()
+        self.encode_replica_replies_dev(*up, out if cap > 0 else None, cap, off, kind, totals, m=m)
+        st = self.sync()
+        whole = buf.cpu().numpy()
+        o, off = whole[base_offset:base_offset + cap], off.cpu().numpy()
+        replies = [o[int(off[i]):int(off[i + 1])].tobytes() for i in range(m)] if st == 0 else []
+        return {"status_code": st, "out": o, "out_offsets": off, "reply_kind": kind.cpu().numpy()[:m],
+                "totals": totals.cpu().numpy(), "replies": replies, "around": (whole[:base_offset], whole[base_offset + cap:])}
+
+    def wire_replica_tick_bytes(self, messages, to, max_pairs, out_cap=None, triple_base=0, triple_id=None, offsets=None,
+                                soa=True):
+        """fpx_wire_epx_replica_tick_bytes: wire_replica_tick, and the replies as wire bytes.  A dict: status_code, out
+        (uint8[out_cap]), out_offsets, reply_kind, totals, replies (per-message bytes, on FPX_OK), bad_index, num_pairs, and
+        with soa the six struct-of-arrays outputs of wire_replica_tick (outcome, out_ballot, out_status, out_deps,
+        out_values_end, out_triple); what the call leaves alone keeps its fill (-9; kinds 9; bytes 0xEE).  out_cap None:
+        len(messages) x wire.EPX_REPLY_MAX"""
+        from . import wire
+        L = wire._L()
+        buf, off = wire.pack(messages)
+        m = len(messages)
+        if offsets is not None:
+            off = np.ascontiguousarray(offsets, np.int64)
+            m = len(off) - 1
+        to = np.ascontiguousarray(to, dtype=np.int32)
+        tr = None if triple_id is None else np.ascontiguousarray(triple_id, dtype=np.int32)
+        cap = m * wire.EPX_REPLY_MAX if out_cap is None else out_cap
+        out, ooff, kind = np.full(max(cap, 1), 0xEE, np.uint8), np.full(m + 1, -9, np.int64), np.full(max(m, 1), 9, np.uint8)
+        totals = np.full(4, -9, np.int64)
+        names = ("outcome", "out_ballot", "out_status", "out_deps", "out_values_end", "out_triple")
+        arr = {k: (np.full((m, self.n) if k == "out_deps" else m, -9, np.int32) if soa else None) for k in names}
+        bad, npairs = C.c_int32(-9), C.c_int32(-9)
+        p = lambda a: None if a is None else a.ctypes.data
+        st = L.fpx_wire_epx_replica_tick_bytes(self._h, p(buf), sum(len(x) for x in messages), p(off), m, p(to), triple_base, p(tr),
+                                               max_pairs, p(out) if cap > 0 else None, cap, p(ooff), p(kind), p(totals),
+                                               *[p(arr[k]) for k in names], C.byref(bad), C.byref(npairs))
+        replies = [out[int(ooff[i]):int(ooff[i + 1])].tobytes() for i in range(m)] if st == 0 else []
+        res = {"status_code": st, "out": out[:cap], "out_offsets": ooff, "reply_kind": kind[:m], "totals": totals,
+               "replies": replies, "bad_index": bad.value, "num_pairs": npairs.value}
+        res.update(arr)
+        return res
+
+    def wire_replica_tick_bytes_dev(self, buf, buf_len, offsets, to, max_pairs, out, out_cap, out_offsets, reply_kind, totals,
+                                    triple_base=0, triple_id=None, outcome=None, out_ballot=None, out_status=None,
+                                    out_deps=None, out_values_end=None, out_triple=None, bad_index=None, num_pairs=None):
+        """the same on device tensors (buf, out, reply_kind uint8; offsets, out_offsets, totals int64; the rest int32);
+        bad_index[1] is required, the six struct-of-arrays outputs are optional.  ONE host wait inside (the pair count);
+        the status comes with sync()"""
+        from . import wire
+        L = wire._L()
+        d = lambda t: None if t is None else t.data_ptr()
+        st = L.fpx_wire_epx_replica_tick_bytes_dev(self._h, d(buf), buf_len, d(offsets), offsets.numel() - 1, d(to), triple_base,
+                                                   d(triple_id), max_pairs, d(out), out_cap, d(out_offsets), d(reply_kind),
+                                                   d(totals), d(outcome), d(out_ballot), d(out_status), d(out_deps),
+                                                   d(out_values_end), d(out_triple), d(bad_index), d(num_pairs))
+        if st:
+            raise FpxError(st, "fpx_wire_epx_replica_tick_bytes_dev")
+
     # ---- originating recovery (recovery=True) ----
     def recover(self, leader, number, at):
         """transitionToPreparePhase of instance (leader, number) at replica `at`, its own Prepare delivered at once:

@@ -83,6 +83,7 @@ class GpuEPaxosEngine[Transport <: frankenpaxos.Transport[Transport]](
   val n: Int = config.n
   val hasLeaderState: Boolean = leaderState
   val hasRecovery: Boolean = leaderState && recovery
+  val hasDeviceKeys: Boolean = deviceKeys
   val handle: Long = if (hasRecovery) Native.epxCreateWithRecovery(n, numKeys, 0, numInstances)
                      else if (leaderState) Native.epxCreateWithLeaderState(n, numKeys, 0, numInstances)
                      else Native.epxCreateWithLog(n, numKeys, 0, numInstances)
@@ -608,6 +609,45 @@ class GpuEPaxosReplica[Transport <: frankenpaxos.Transport[Transport]](
     val x = instance.instanceNumber
     own.value.isEmpty || (own.watermark <= x && own.value.sorted == (x + 1 to own.value.max))
   }
+  // The burst through Native.epxWireReplicaTickBytes (include/fpx_wire.h, fpx_wire_epx_replica_tick_bytes): the device decodes
+  // the frames, interns the keys, answers the burst and serialises the replies.  The result: per message the bytes to send
+  // back, null where there is nothing to send or the reply is deferred to the loop in flushPeerInbox (which reads outcome /
+  // reply / outDeps, filled here as epxReplicaInboxMk fills them).  null altogether: the tick refused a frame, nothing was
+  // applied.  (The actor framework hands this actor parsed messages, so the frames are serialised again here; a transport
+  // that hands over the raw frames passes them straight through, INTEGRATION.md.)
+  private def wireTickBytes(ev: Array[PeerEvent], tripleId: Array[Int], outcome: Array[Int], reply: Array[Int],
+                            outDeps: Array[Int]): Array[Array[Byte]] = {
+    val k = ev.length
+    val frames: Array[Array[Byte]] = ev.map(e => (e.kind match {
+      case 0 => ReplicaInbound().withPreAccept(PreAccept(e.instance, e.ballot, e.commandOrNoop.get, 0, e.dependencies.get))
+      case 1 => ReplicaInbound().withAccept(Accept(e.instance, e.ballot, e.commandOrNoop.get, 0, e.dependencies.get))
+      case 2 => ReplicaInbound().withCommit(Commit(e.instance, e.commandOrNoop.get, 0, e.dependencies.get))
+      case _ => ReplicaInbound().withPrepare(Prepare(e.instance, e.ballot))
+    }).toByteArray)
+    def direct(bytes: Int) = java.nio.ByteBuffer.allocateDirect(math.max(bytes, 8)).order(java.nio.ByteOrder.nativeOrder)
+    val inLen = frames.map(_.length.toLong).sum
+    val in = direct(inLen.toInt); val inOffsets = direct(8 * (k + 1)); val to = direct(4 * k)
+    var at = 0L
+    for ((f, i) <- frames.zipWithIndex) { inOffsets.putLong(8 * i, at); in.put(f); at += f.length; to.putInt(4 * i, index) }
+    inOffsets.putLong(8 * k, at)
+    val outCap = 472L * k                                    // FPX_WIRE_EPX_REPLY_MAX: FPX_ECAPACITY cannot happen
+    val out = direct(outCap.toInt); val outOffsets = direct(8 * (k + 1)); val replyKind = direct(k)
+    val result = new Array[Long](6)
+    val maxPairs = math.min(frames.map(_.length).sum, 1 << 24)   // (a key is at least two bytes of its frame)
+    val st = Native.epxWireReplicaTickBytes(engine.handle, k, n, in, inLen, inOffsets, to, 0, tripleId, maxPairs, out, outCap,
+                                            outOffsets, replyKind, outcome, reply, outDeps, result)
+    if (st == 1 && result(0) >= 0) return null               // a frame the device does not take: nothing applied, nothing interned
+    Native.check(st, logger)
+    Array.tabulate(k) { i =>
+      if (replyKind.get(i) != 1) null
+      else {
+        val (lo, hi) = (outOffsets.getLong(8 * i).toInt, outOffsets.getLong(8 * (i + 1)).toInt)
+        val bytes = new Array[Byte](hi - lo)
+        out.position(lo); out.get(bytes); bytes
+      }
+    }
+  }
+
   private def flushPeerInbox(): Unit = {
     if (peerInbox.isEmpty) return
     val k = peerInbox.size
@@ -618,8 +658,6 @@ class GpuEPaxosReplica[Transport <: frankenpaxos.Transport[Transport]](
     val keys = Array.fill[Option[Array[Int]]](k)(None); val isSet = new Array[Byte](k); val tripleId = Array.fill(k)(-1)
     val deps = new Array[Int](k * n); val ends = new Array[Int](k)
     for ((e, i) <- ev.zipWithIndex; c <- e.commandOrNoop; d <- e.dependencies) {
-      val (ks, set) = engine.classify(c)
-      keys(i) = ks; isSet(i) = if (set) 1 else 0
       // (originateRecovery: equal commands get equal ids -- the own PrepareOk's triple id meets the peers' in handlePrepareOk)
       if (originateRecovery) tripleId(i) = engine.intern(c) else { tripleId(i) = engine.triples.size; engine.triples += c }
       val (w, end) = (watermarks(d), ownEnd(e.instance, d))
@@ -629,7 +667,16 @@ class GpuEPaxosReplica[Transport <: frankenpaxos.Transport[Transport]](
       if (e.kind == 1) engine.tripleDeps(tripleId(i)) = (w, end)
     }
     val outcome = new Array[Int](k); val reply = new Array[Int](4 * k); val outDeps = new Array[Int](k * n)
+    // deviceKeys: the burst goes down as frames and the replies come back serialised (Native.epxWireReplicaTickBytes);
+    // encoded(i) is then reply i's bytes and the loop below builds only the deferred ones.  null: the tick refused a frame
+    // with nothing applied (dependencies or a command outside the canonical shape), and the burst goes the parsed way
+    val encoded: Array[Array[Byte]] = if (engine.hasDeviceKeys) wireTickBytes(ev, tripleId, outcome, reply, outDeps) else null
+    if (encoded == null) for ((e, i) <- ev.zipWithIndex; c <- e.commandOrNoop) {
+      val (ks, set) = engine.classify(c)
+      keys(i) = ks; isSet(i) = if (set) 1 else 0
+    }
     // (a Prepare has no command: None, which is key -1 in the one form and an empty list in the other; neither is read)
+    if (encoded == null)
     Native.check(if (engine.singleKeys(keys))
                    Native.epxReplicaInbox(engine.handle, k, n, ev.map(_.kind), Array.fill(k)(index), ev.map(_.instance.replicaIndex),
                                           ev.map(_.instance.instanceNumber), ev.map(_.ballot.ordering), ev.map(_.ballot.replicaIndex),
@@ -648,7 +695,8 @@ class GpuEPaxosReplica[Transport <: frankenpaxos.Transport[Transport]](
       def sent: Option[InstancePrefixSetProto] =
         (if (outDeps(i * n) >= 0) Some((outDeps.slice(i * n, (i + 1) * n), reply(2 * k + i)))
          else engine.tripleDeps.get(triple).orElse(engine.depsOf.get((l, x)))).map { case (w, end) => prefixSet(w, l, end, x) }
-      outcome(i) match {
+      if (encoded != null && encoded(i) != null) transport.send(this, e.src, encoded(i))   // the device wrote this reply
+      else outcome(i) match {
         case 1 | 2 => back.send(ReplicaInbound().withPreAcceptOk(PreAcceptOk(e.instance, e.ballot, index, 0, sent.get)))   // :1196-1210, 1281-1288
         case 3 | 4 => back.send(ReplicaInbound().withAcceptOk(AcceptOk(e.instance, e.ballot, index)))                    // :1451-1461, 1505-1511
         case 5 =>                                                                                                       // :1567-1575

@@ -243,6 +243,18 @@ object Native {
                                  inOffsets: java.nio.ByteBuffer, to: java.nio.ByteBuffer, tripleBase: Int, tripleId: Array[Int],
                                  maxPairs: Int, outcome: Array[Int], reply: Array[Int], outDeps: Array[Int],
                                  result: Array[Int]): Int
+  // the same tick, bytes to bytes (fpx_wire_epx_replica_tick_bytes): the replies the replicas send back come out serialised --
+  // reply i is out[outOffsets(i) until outOffsets(i + 1)) (direct buffers, native order: outCap bytes, m + 1 longs), empty when
+  // replyKind(i) (m bytes) is 0 (nothing to send) or 2 (deferred: a Commit sent back, a PrepareOk that carries a command, a
+  // PreAcceptOk of a triple stored by id or with more than 64 explicit ids -- build that one from outcome / reply / outDeps as
+  // before).  outcome, reply and outDeps may be null.  result (6 longs): the bad index and the pairs as above, then the replies
+  // encoded, the bytes needed, the records deferred and -1.  outCap >= 472 * m (FPX_WIRE_EPX_REPLY_MAX) always suffices;
+  // status 5 with result(3) > outCap: the tick WAS applied and the arrays are valid -- encode from them
+  @native def epxWireReplicaTickBytes(handle: Long, m: Int, numReplicas: Int, in: java.nio.ByteBuffer, inLen: Long,
+                                      inOffsets: java.nio.ByteBuffer, to: java.nio.ByteBuffer, tripleBase: Int,
+                                      tripleId: Array[Int], maxPairs: Int, out: java.nio.ByteBuffer, outCap: Long,
+                                      outOffsets: java.nio.ByteBuffer, replyKind: java.nio.ByteBuffer, outcome: Array[Int],
+                                      reply: Array[Int], outDeps: Array[Int], result: Array[Long]): Int
   // one burst of PreAccept (kind 0) / Accept (1) / Commit (2) / Prepare (3) messages from peer replicas, message i to replica
   // to(i), in delivery order, instances repeated freely (handlePreAccept :1159-1289, handleAccept :1421-1511, handleCommit
   // :1567-1575, handlePrepare :1632-1757).  deps (m x n): a row starting with -1 on an Accept / a Commit = the triple is known

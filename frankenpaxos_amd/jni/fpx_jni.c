@@ -1576,6 +1576,51 @@ JNIEXPORT jint JNICALL Java_frankenpaxos_gpu_Native_epxWireReplicaTick(JNIEnv* e
   return st;
 }
 
+/* The same tick, bytes to bytes (fpx_wire_epx_replica_tick_bytes): the inputs as above; the replies come back in direct
+ * ByteBuffers the caller slices by index -- out (outCap bytes), outOffsets (m + 1 longs: reply i = out[outOffsets[i] ..
+ * outOffsets[i + 1])) and replyKind (m bytes: 0 none, 1 encoded, 2 deferred to the caller), native byte order.  outcome, reply
+ * and outDeps (each may be null) are epxWireReplicaTick's: a caller needs them for its deferred records.  result[6] (may be
+ * null): the bad index, the (message, key) pairs, then the encoder's totals -- replies encoded, bytes needed, records deferred,
+ * the first unknown outcome (-1).  Status 5 with result[3] > outCap: the tick WAS applied, the arrays are valid, the caller
+ * encodes from them (or calls fpx_wire_epx_encode_replica_replies); any other status but 0 leaves every output as it was */
+JNIEXPORT jint JNICALL Java_frankenpaxos_gpu_Native_epxWireReplicaTickBytes(JNIEnv* env, jclass cls, jlong h, jint m, jint numReplicas,
+                                                                            jobject in, jlong inLen, jobject inOffsets, jobject to,
+                                                                            jint tripleBase, jintArray tripleId, jint maxPairs,
+                                                                            jobject out, jlong outCap, jobject outOffsets,
+                                                                            jobject replyKind, jintArray outcome, jintArray reply,
+                                                                            jintArray outDeps, jlongArray result) {
+  if (m < 0 || inLen < 0 || maxPairs < 0 || outCap < 0 || numReplicas < 3 || !epx_n_is(h, numReplicas)) return FPX_EINVAL;
+  const jlong mn = (jlong)m * numReplicas;
+  if (!opt(env, result, 6) || !opt(env, outcome, m) || !opt(env, reply, 4 * (jlong)m) || !opt(env, outDeps, mn) ||
+      !opt(env, tripleId, m))
+    return FPX_EINVAL;
+  int bad = 0;
+  const uint8_t* i = direct(env, in, inLen, &bad);
+  const int64_t* io = direct(env, inOffsets, 8 * ((jlong)m + 1), &bad);
+  const int32_t* t = direct(env, to, 4 * (jlong)m, &bad);
+  uint8_t* o = direct(env, out, outCap, &bad);
+  int64_t* oo = direct(env, outOffsets, 8 * ((jlong)m + 1), &bad);
+  uint8_t* rk = direct(env, replyKind, m, &bad);
+  if (bad || !oo || (m > 0 && (!io || !t || !rk || (inLen > 0 && !i))) || (outCap > 0 && !o)) return FPX_EINVAL;
+  jint* tr = (tripleId && m > 0) ? in_ints(env, tripleId, m) : NULL;
+  jint *oc = out_buf(outcome, m, 4), *rp = out_buf(reply, 4 * (jlong)m, 4), *od = out_buf(outDeps, mn, 4);
+  int32_t res[2] = {-1, 0};
+  int64_t totals[4] = {0, 0, 0, -1};
+  const size_t sm = (size_t)m;
+  int32_t st = m > 0 && ((tripleId && !tr) || (outcome && !oc) || (reply && !rp) || (outDeps && !od))
+                   ? FPX_ENOMEM
+                   : fpx_wire_epx_replica_tick_bytes((fpx_epx*)(intptr_t)h, i, inLen, io, m, t, tripleBase, tr, maxPairs, o, outCap,
+                                                     oo, rk, totals, oc, rp, rp ? rp + sm : NULL, od, rp ? rp + 2 * sm : NULL,
+                                                     rp ? rp + 3 * sm : NULL, &res[0], &res[1]);
+  if (st == FPX_OK || (st == FPX_ECAPACITY && totals[1] > outCap)) {
+    put_ints(env, outcome, m, oc); put_ints(env, reply, 4 * (jlong)m, rp); put_ints(env, outDeps, mn, od);
+  }
+  const jlong r[6] = {res[0], res[1], totals[0], totals[1], totals[2], totals[3]};
+  put_longs(env, result, 6, r);
+  free(tr); free(oc); free(rp); free(od);
+  return st;
+}
+
 /* K8 Replica.handlePrepareOk (epaxos/Replica.scala:1759-1884): prepareOk = epxPrepare's output (status | voteBallot |
  * triple, 3 x m x numReplicas), respMask = its okBits; decision = action | source | triple (3 x m ints) */
 JNIEXPORT jint JNICALL Java_frankenpaxos_gpu_Native_epxHandlePrepareOks(JNIEnv* env, jclass cls, jlong h, jint m,

@@ -93,6 +93,15 @@ def _L():
             [I32P, I32P]
         for name in ("fpx_wire_epx_classify_dev", "fpx_wire_epx_replica_tick_dev", "fpx_wire_epx_replica_tick"):
             getattr(L, name).restype = C.c_int32
+        # a replica tick's replies as wire bytes: the host batch encoder, the device encoder and the bytes tick
+        L.fpx_wire_epx_encode_replica_replies.argtypes = [C.c_int32, C.c_int32] + [VP] * 11 + [C.c_int64, VP, VP, VP]
+        L.fpx_wire_epx_encode_replica_replies_dev.argtypes = [VP, C.c_int32] + [VP] * 11 + [C.c_int64, VP, VP, VP]
+        tick_bytes = [VP, VP, C.c_int64, VP, C.c_int32, VP, C.c_int32, VP, C.c_int32, VP, C.c_int64, VP, VP, VP] + [VP] * 6
+        L.fpx_wire_epx_replica_tick_bytes_dev.argtypes = tick_bytes + [VP, VP]
+        L.fpx_wire_epx_replica_tick_bytes.argtypes = tick_bytes + [I32P, I32P]
+        for name in ("fpx_wire_epx_encode_replica_replies", "fpx_wire_epx_encode_replica_replies_dev",
+                     "fpx_wire_epx_replica_tick_bytes_dev", "fpx_wire_epx_replica_tick_bytes"):
+            getattr(L, name).restype = C.c_int32
         L.fpx_wire_phase2b_rows.argtypes = [C.c_int32, VP, VP, VP, VP, VP, C.c_int32, I32P, VP, VP, VP]
         L.fpx_wire_encode_proxy_leader_phase2a.argtypes = [VP, C.c_int64, C.c_int32, C.c_int32, VP, C.c_int32, C.c_int32]
         L.fpx_wire_encode_acceptor_phase2a.argtypes = [VP, C.c_int64, C.c_int32, C.c_int32, VP, C.c_int32, C.c_int32]
@@ -442,3 +451,44 @@ def epx_classify(buf, cmd_off, cmd_len, max_pairs=None):
     out["keys"] = [buf[int(o):int(o) + int(n)].tobytes() for o, n in zip(po[:P], pl[:P])] if st == 0 else []
     out["status_code"], out["bad_index"] = st, bad.value
     return out
+
+
+EPX_REPLY_MAX = 472   # FPX_WIRE_EPX_REPLY_MAX
+EPX_REPLY_NONE, EPX_REPLY_ENCODED, EPX_REPLY_DEFERRED = 0, 1, 2
+# the records of a replica tick, in the encoders' argument order: the decoded messages, then replica_inbox's outputs
+EPX_REPLY_RECORDS = ("to", "leader", "number", "ballot_ordering", "ballot_replica", "outcome", "out_ballot", "out_status",
+                     "out_deps", "out_values_end")
+
+
+def epx_reply_records(n, **arrays):
+    """the ten record arrays of EPX_REPLY_RECORDS as contiguous int32 (out_deps (m, n)), in argument order"""
+    rec = [np.ascontiguousarray(arrays[k], np.int32) for k in EPX_REPLY_RECORDS]
+    m = len(rec[0])
+    rec[8] = rec[8].reshape(m, n) if m else np.zeros((0, n), np.int32)
+    assert all(len(a) == m for a in rec)
+    return rec
+
+
+def epx_encode_replica_replies(n, cap=None, out=None, **arrays):
+    """fpx_wire_epx_encode_replica_replies, the host batch encoder of a replica tick's replies.  arrays: the ten of
+    EPX_REPLY_RECORDS.  cap None: sized by a first call (cap 0, no buffer).  A dict: status_code, out (uint8[cap], or the
+    array passed in), out_offsets (int64[m + 1]), reply_kind (uint8[m]), totals (int64[4]: encoded, bytes needed, deferred,
+    the first unknown outcome) and replies, the list of per-message bytes on FPX_OK; what the call leaves alone keeps
+    its fill (offsets -9, kinds 9, bytes 0xEE)"""
+    rec = epx_reply_records(n, **arrays)
+    m = len(rec[0])
+    fn = _L().fpx_wire_epx_encode_replica_replies
+    off, kind, totals = np.full(m + 1, -9, np.int64), np.full(m, 9, np.uint8), np.full(4, -9, np.int64)
+    p = lambda a: a.ctypes.data if a is not None and a.size else None
+    if cap is None:
+        st = fn(n, m, *[p(a) for a in rec], None, 0, off.ctypes.data, p(kind), totals.ctypes.data)
+        if st not in (0, _lib.FPX_ECAPACITY):
+            return {"status_code": st, "out": np.zeros(0, np.uint8), "out_offsets": off, "reply_kind": kind, "totals": totals,
+                    "replies": []}
+        cap = int(totals[1])
+        off[:], kind[:] = -9, 9
+    if out is None:
+        out = np.full(cap, 0xEE, np.uint8)
+    st = fn(n, m, *[p(a) for a in rec], p(out), cap, off.ctypes.data, p(kind), totals.ctypes.data)
+    replies = [out[int(off[i]):int(off[i + 1])].tobytes() for i in range(m)] if st == 0 else []
+    return {"status_code": st, "out": out, "out_offsets": off, "reply_kind": kind, "totals": totals, "replies": replies}

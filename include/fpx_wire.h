@@ -549,6 +549,92 @@ int32_t fpx_wire_epx_replica_tick(struct fpx_epx* epx, const uint8_t* in, int64_
                                   int32_t* out_deps, int32_t* out_values_end, int32_t* out_triple, int32_t* bad_index,
                                   int32_t* num_pairs);
 
+/* ---- a replica tick's replies as wire bytes ---------------------------------------------------------------------------
+ * The outbound half of the tick above: what fpx_epx_replica_inbox[_mk] answers (outcome, out_ballot, out_status, out_deps
+ * [m x n], out_values_end; include/fpx.h, FPX_EPX_RI_*) becomes the serialised ReplicaInbound messages the hosted replicas send
+ * back, without the caller building one message at a time (EPaxosNative.scala, flushPeerInbox).  One emitter source for both
+ * sides, csrc/fpx_wire_epx_emit.hpp: an encoded reply is, byte for byte, what fpx_wire_epaxos_encode_replica_inbound returns
+ * for the same message.  Message i -- received by replica to[i], instance (leader[i], number[i]), the MESSAGE's ballot
+ * (ballot_ordering[i], ballot_replica[i]) -- by outcome[i]:
+ *   IGNORED, LEARNT                    no reply                                                          reply_kind 0
+ *   PRE_ACCEPT_OK, PRE_ACCEPT_OK_AGAIN PreAcceptOk(instance, the message's ballot, to[i], 0, deps): deps = the n watermarks of
+ *                                      row i, and in the own-leader column (l == leader[i]) the explicit ids number + 1 ..
+ *                                      out_values_end - 1, ascending, when out_values_end > 0.      reply_kind 1 -- but 2
+ *                                      (deferred) when out_deps[i * n] < 0 (a triple stored by id: the caller has its
+ *                                      dependencies) or the own column would carry more than FPX_WIRE_EPX_FOLD_MAX ids
+ *   ACCEPT_OK, ACCEPT_OK_AGAIN         AcceptOk(instance, the message's ballot, to[i])                   reply_kind 1
+ *   NACK                               Nack(instance, Ballot(out_ballot >> 3, out_ballot & 7))           reply_kind 1
+ *   PREPARE_OK                         out_status 0: PrepareOk(the message's ballot, instance, to[i], voteBallot, NotSeen)
+ *                                      without the three optional fields; voteBallot = (-1, -1), the reference's nullBallot,
+ *                                      when out_ballot < 0.  reply_kind 1.  Any other out_status: reply_kind 2, the reply
+ *                                      carries the stored triple's CommandOrNoop, whose bytes live with the caller
+ *   COMMIT_BACK                        reply_kind 2, for the same reason
+ * A deferred record is no error: it contributes no bytes and the caller builds that one reply from the struct-of-arrays
+ * outputs, as it does today.  (The steady traffic of a replica is outcomes 1, 3 and 7; the deferred ones are recovery and
+ * commit-back.)  The records are not validated beyond outcome being in 0 .. 8.
+ *   bytes    the reply of message i is out[out_offsets[i] .. out_offsets[i + 1]), empty for kinds 0 and 2: offsets are per
+ *            MESSAGE, m + 1 of them, nothing is compacted (reply i goes to the sender of message i).
+ *   totals   4 words, ALWAYS written: the replies encoded, the bytes needed, the records deferred, and the first record with
+ *            an unknown outcome (-1 = none; this context has no error-detail call, so the index travels here).
+ *   FPX_ECAPACITY  the bytes needed exceed cap (or, on the device, reach 4 GiB in one call: its scan is 32 bits wide -- cut the
+ *            burst): no byte of out and no out_offsets entry beyond [0] (= 0) is written, reply_kind
+ *            is not written; totals say what to allocate.  cap == 0 with out == NULL is the sizing call.
+ *   FPX_EINVAL     an outcome outside 0 .. 8: totals[3] names the first, nothing else is written but out_offsets[0] = 0.
+ *   m == 0   FPX_OK, totals 0, out_offsets[0] = 0.
+ * A NULL required array, n < 1, negative sizes or m > FPX_EPX_INBOX_MAX: FPX_EINVAL at once.
+ * FPX_WIRE_EPX_REPLY_MAX: no encoded reply is longer, given what fpx_epx_replica_inbox puts out -- n <= 7, at most 64 explicit
+ * ids, a ballot ordering below 2^27, every other number a non-negative int32.  It is a PreAcceptOk: 3 bytes of wrapper, the
+ * instance 10, the ballot 9, replica_index and sequence_number 2 each, and 3 + 443 of dependencies (numReplicas 2, six columns
+ * of 8, the own column 3 + 6 + 64 x 6).  cap >= m x FPX_WIRE_EPX_REPLY_MAX makes FPX_ECAPACITY unreachable.
+ *
+ * fpx_wire_epx_encode_replica_replies: the host batch encoder, g++-compiled, no GPU.
+ * fpx_wire_epx_encode_replica_replies_dev: the same arrays as device pointers (n is the context's), enqueued on the context's
+ * stream, no host wait inside -- so, once the context's scratch is sized (the first call with a larger m than any before
+ * allocates 4 bytes per record: run one call with the largest m outside the capture), it can be captured into a HIP
+ * graph.  Both errors above are PER-CALL codes: they come through fpx_epx_sync, which returns and clears them like any status
+ * (a status raised by another call outranks them), but no later call on the context stands back behind them.  A context that
+ * is in its "apply nothing" state when the encoder runs (a refused burst in front of it): totals 0, out_offsets[0] = 0,
+ * nothing else.
+ *
+ * fpx_wire_epx_replica_tick_bytes[_dev]: fpx_wire_epx_replica_tick's stages, unchanged, then the encoder on the decoded
+ * arrays the tick holds in scratch and on the inbox outputs: frames in, the frames to send back out.  The six struct-of-
+ * arrays outputs are ALL optional here -- a caller needs them for its deferred records (reply_kind 2); what it leaves NULL
+ * the tick keeps in scratch of its own and never copies down.  Refusals are exactly fpx_wire_epx_replica_tick's, in its order,
+ * each with nothing applied and nothing encoded (totals 0, out_offsets[0] = 0; the host form leaves every other output array
+ * as it was).  FPX_ECAPACITY from the ENCODER means the tick WAS applied: the struct-of-arrays outputs, where requested, are
+ * valid and the caller encodes from them (fpx_wire_epx_encode_replica_replies); totals[1] > out_cap tells this
+ * FPX_ECAPACITY from stage 1's, whose totals are 0.  Like its sibling the tick waits once on the host for the pair count and
+ * cannot be captured into a graph.  m = 0 is FPX_OK.
+ * The host form goes through the staging driver like its sibling.  Its copy down moves 32 bytes of totals, 8 bytes of bad
+ * index and pair count, then -- on FPX_OK -- 8 (m + 1) bytes of offsets, m bytes of kinds and the totals[1] bytes of the
+ * replies, NOT out_cap bytes; plus 4 bytes per message for each requested struct-of-arrays output (4 n for out_deps), against
+ * the (5 + n) x 4 bytes per message fpx_wire_epx_replica_tick moves for all six.  out_cap bytes are staged on the device.
+ * Deviations from the issue's proposal: totals has a fourth word; reply_kind is bytes. */
+#define FPX_WIRE_EPX_REPLY_MAX 472
+int32_t fpx_wire_epx_encode_replica_replies(int32_t n, int32_t m, const int32_t* to, const int32_t* leader, const int32_t* number,
+                                            const int32_t* ballot_ordering, const int32_t* ballot_replica, const int32_t* outcome,
+                                            const int32_t* out_ballot, const int32_t* out_status, const int32_t* out_deps,
+                                            const int32_t* out_values_end, uint8_t* out, int64_t cap, int64_t* out_offsets,
+                                            uint8_t* reply_kind, int64_t* totals);
+int32_t fpx_wire_epx_encode_replica_replies_dev(struct fpx_epx* epx, int32_t m, const int32_t* d_to, const int32_t* d_leader,
+                                                const int32_t* d_number, const int32_t* d_ballot_ordering,
+                                                const int32_t* d_ballot_replica, const int32_t* d_outcome,
+                                                const int32_t* d_out_ballot, const int32_t* d_out_status,
+                                                const int32_t* d_out_deps, const int32_t* d_out_values_end, uint8_t* d_out,
+                                                int64_t cap, int64_t* d_out_offsets, uint8_t* d_reply_kind, int64_t* d_totals);
+int32_t fpx_wire_epx_replica_tick_bytes_dev(struct fpx_epx* epx, const uint8_t* d_in, int64_t in_len, const int64_t* d_in_offsets,
+                                            int32_t m, const int32_t* d_to, int32_t triple_base, const int32_t* d_triple_id,
+                                            int32_t max_pairs, uint8_t* d_out, int64_t out_cap, int64_t* d_out_offsets,
+                                            uint8_t* d_reply_kind, int64_t* d_totals, int32_t* d_outcome, int32_t* d_out_ballot,
+                                            int32_t* d_out_status, int32_t* d_out_deps, int32_t* d_out_values_end,
+                                            int32_t* d_out_triple, int32_t* d_bad_index, int32_t* d_num_pairs);
+int32_t fpx_wire_epx_replica_tick_bytes(struct fpx_epx* epx, const uint8_t* in, int64_t in_len, const int64_t* in_offsets,
+                                        int32_t m, const int32_t* to, int32_t triple_base, const int32_t* triple_id,
+                                        int32_t max_pairs, uint8_t* out, int64_t out_cap, int64_t* out_offsets,
+                                        uint8_t* reply_kind, int64_t* totals, int32_t* outcome, int32_t* out_ballot,
+                                        int32_t* out_status, int32_t* out_deps, int32_t* out_values_end, int32_t* out_triple,
+                                        int32_t* bad_index, int32_t* num_pairs);
+
 #ifdef __cplusplus
 }
 #endif
