@@ -193,6 +193,11 @@ SIGNATURES = {
     "fpx_epx_keys_intern_dev": (C.c_int32, [VP, VP, C.c_int64, VP, VP, C.c_int32, VP]),
     "fpx_epx_keys_intern": (C.c_int32, [VP, VP, C.c_int64, VP, VP, C.c_int32, VP]),
     "fpx_epx_keys_read": (C.c_int32, [VP, C.c_int32, C.c_int32, VP, VP, C.c_int64]),
+    "fpx_epx_cmds_enable": (C.c_int32, [VP, C.c_int32, C.c_int64]),
+    "fpx_epx_cmds_put_dev": (C.c_int32, [VP, VP, C.c_int64, VP, VP, VP, C.c_int32, VP]),
+    "fpx_epx_cmds_put": (C.c_int32, [VP, VP, C.c_int64, VP, VP, VP, C.c_int32, VP]),
+    "fpx_epx_cmds_read": (C.c_int32, [VP, C.c_int32, VP, C.c_int64, I32P]),
+    "fpx_epx_cmds_stats": (C.c_int32, [VP, VP]),
     "fpx_epx_read_leader_state": (C.c_int32, [VP, C.c_int32, C.c_int32, C.c_int32, VP, VP]),
     "fpx_epx_recover": (C.c_int32, [VP, C.c_int32] + [VP] * 8),
     "fpx_epx_recovery_replies": (C.c_int32, [VP, C.c_int32] + [VP] * 13 + [C.c_int32] + [VP] * 9),

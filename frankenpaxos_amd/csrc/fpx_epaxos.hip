@@ -1385,6 +1385,7 @@ __global__ void __launch_bounds__(256) k_hp_commit(const EpxState st, const HpBa
 #include "fpx_epx_inbox.hpp"
 #include "fpx_intern.hpp"
 #include "fpx_wire_epx_dev.hpp"
+#include "fpx_epx_cmds.hpp"
 #include "fpx_wire_epx_enc_dev.hpp"
 
 }  // namespace
@@ -1419,6 +1420,9 @@ struct fpx_epx {
   DevBuf keys_misc, rt_misc;              // fpx_epx_keys_intern_dev: lay_intern; the classify and the replica tick: their layouts
   DevBuf enc_misc;                        // fpx_wire_epx_encode_replica_replies_dev and the bytes tick: their layouts
   bool enc_direct = false;                // FPX_EPX_ENC_DIRECT: the reply encoder's direct form for every wavefront
+  CmdStore cmds = {};                     // fpx_epx_cmds_enable: the command store (fpx_epx_cmds.hpp), else not allocated
+  DevBuf cmds_misc;                       // a put: lay_epx_cmds_put
+  bool cmds_bytewise = true;              // the command copy's single-byte form, the default; FPX_EPX_CMDS_WORDS: the 16-byte-word form
   bool lds_allowed = false, sort_lds_allowed = false;
   int num_cus = 256;
 };
@@ -1996,6 +2000,7 @@ int32_t fpx_epx_create(const fpx_epx_config* cfg, fpx_epx** out) {
   }
   e->kp_off = getenv("FPX_EPX_V1") != nullptr;
   e->enc_direct = getenv("FPX_EPX_ENC_DIRECT") != nullptr;
+  e->cmds_bytewise = getenv("FPX_EPX_CMDS_WORDS") == nullptr;
   if (hipMalloc((void**)&e->census_dev, EPX_CD_WORDS * 8) != hipSuccess) return fail(FPX_ENOMEM);
   if (hipMemsetAsync(e->census_dev, 0, EPX_CD_WORDS * 8, e->stream) != hipSuccess) return fail(FPX_EHIP);
   if (hipStreamSynchronize(e->stream) != hipSuccess) return fail(FPX_EHIP);
@@ -2009,11 +2014,13 @@ int32_t fpx_epx_destroy(fpx_epx* e) {
   if (e->stream) (void)hipStreamSynchronize(e->stream);
   void* ps[] = {e->st.gets, e->st.sets, e->st.status, e->st.cl_status, e->st.cl_ballot, e->st.cl_vote, e->st.cl_triple,
                 e->st.largest, e->st.cl_stamp, e->st.cl_deps, e->st.cl_dend, e->ls.head, e->ls.resp, e->ls.prep, e->census_dev,
-                e->keys.slot, e->keys.first, e->keys.key_off, e->keys.arena, e->keys.meta};
+                e->keys.slot, e->keys.first, e->keys.key_off, e->keys.arena, e->keys.meta,
+                e->cmds.off, e->cmds.len, e->cmds.claim, e->cmds.arena, e->cmds.meta};
   for (void* p : ps)
     if (p) (void)hipFree(p);
   DevBuf* bs[] = {&e->kv, &e->kv2, &e->seg, &e->conf, &e->tmp, &e->tick, &e->fusedb, &e->metab, &e->mk_misc, &e->mk_rec,
-                  &e->mk_pair, &e->mk_pconf, &e->lr_misc, &e->ri_misc, &e->wire_misc, &e->keys_misc, &e->rt_misc, &e->enc_misc};
+                  &e->mk_pair, &e->mk_pconf, &e->lr_misc, &e->ri_misc, &e->wire_misc, &e->keys_misc, &e->rt_misc, &e->enc_misc,
+                  &e->cmds_misc};
   for (DevBuf* b : bs)
     if (b->p) (void)hipFree(b->p);
   free_stage(&e->stage);
@@ -3314,6 +3321,118 @@ int32_t fpx_epx_keys_read(fpx_epx* e, int32_t first_id, int32_t n, int32_t* key_
   return FPX_OK;
 }
 
+// ---- the command store: csrc/fpx_epx_cmds.hpp ---------------------------------------------------------------------------
+static bool cmds_on(const fpx_epx* e) { return e && e->cmds.off; }
+
+int32_t fpx_epx_cmds_enable(fpx_epx* e, int32_t max_triples, int64_t arena_bytes) {
+  if (!e || max_triples < 1 || arena_bytes < 0 || cmds_on(e)) return FPX_EINVAL;
+  DeviceScope _dg(e->cfg.device);
+  CmdStore t = {};
+  t.max_triples = max_triples, t.arena_bytes = arena_bytes;
+  const size_t ids = (size_t)max_triples;
+  hipError_t err = hipMalloc((void**)&t.off, ids * 8);
+  if (err == hipSuccess) err = hipMalloc((void**)&t.len, ids * 4);
+  if (err == hipSuccess) err = hipMalloc((void**)&t.claim, ids * 4);
+  if (err == hipSuccess) err = hipMalloc((void**)&t.arena, (size_t)std::max<int64_t>(arena_bytes, 1));
+  if (err == hipSuccess) err = hipMalloc((void**)&t.meta, 32);
+  if (err == hipSuccess) err = hipMemsetAsync(t.off, 0xFF, ids * 8, e->stream);
+  if (err == hipSuccess) err = hipMemsetAsync(t.len, 0, ids * 4, e->stream);
+  if (err == hipSuccess) err = hipMemsetAsync(t.claim, CMDS_IDLE & 0xff, ids * 4, e->stream);
+  if (err == hipSuccess) err = hipMemsetAsync(t.meta, 0, 32, e->stream);
+  if (err == hipSuccess) err = hipStreamSynchronize(e->stream);
+  if (err != hipSuccess) {
+    for (void* p : {(void*)t.off, (void*)t.len, (void*)t.claim, (void*)t.arena, (void*)t.meta})
+      if (p) (void)hipFree(p);
+    e->last_hip = (int)err;
+    return err == hipErrorOutOfMemory ? FPX_ENOMEM : FPX_EHIP;
+  }
+  e->cmds = t;
+  return FPX_OK;
+}
+
+// one burst; d_result may be null (the ticks': the store's counts say what a put did)
+static int32_t cmds_put_launch(fpx_epx* e, const uint8_t* d_buf, int64_t buf_len, const int64_t* d_cmd_off, const int32_t* d_cmd_len,
+                               const int32_t* d_triple, int32_t m, bool check_spans, long long* d_result) {
+  static_assert(CMC_WORDS == EPX_CMDS_CTL_WORDS && CMD_MAX_LEN == FPX_EPX_CMD_MAX_LEN, "a put's scratch as lay_epx_cmds_put sizes it");
+  EpxCmdsPutScratch s;
+  int rc;
+  if ((rc = carve(e, &e->cmds_misc, &s, [&](Carver& c) { return lay_epx_cmds_put(c, (size_t)m); }))) return rc;
+  const size_t rows = scan_rows((size_t)m);
+  CmdPut b;
+  memset(&b, 0, sizeof(b));
+  b.buf = d_buf, b.buf_len = buf_len, b.cmd_off = d_cmd_off, b.cmd_len = d_cmd_len, b.triple = d_triple, b.m = m;
+  b.rows = (int32_t)rows, b.check_spans = check_spans ? 1 : 0, b.bytewise = e->cmds_bytewise ? 1 : 0;
+  b.result = d_result ? d_result : s.result;
+  b.lscan = s.lscan, b.ltot = s.ltot, b.lgt = s.lgt, b.ctl = s.ctl;
+  HIPCHK(e, hipMemsetAsync(b.ctl, 0, CMC_WORDS * 4, e->stream));
+  HIPCHK(e, hipMemsetAsync(b.ctl + CMC_BAD, CMDS_IDLE & 0xff, 4, e->stream));
+  const dim3 gm((unsigned)((m + CMD_BLOCK - 1) / CMD_BLOCK)), blk(CMD_BLOCK);
+  hipLaunchKernelGGL(k_cmd_claim, gm, blk, 0, e->stream, e->st, e->cmds, b);
+  hipLaunchKernelGGL(k_cmd_len, dim3((unsigned)(rows * INTERN_ROW / CMD_BLOCK)), blk, 0, e->stream, e->st, e->cmds, b);
+  scan_rows_launch(e, b.lscan, rows, b.ltot, b.lgt);
+  hipLaunchKernelGGL(k_cmd_decide, dim3(1), dim3(256), 0, e->stream, e->st, e->cmds, b);
+  hipLaunchKernelGGL(k_cmd_copy, gm, blk, 0, e->stream, e->cmds, b);
+  hipLaunchKernelGGL(k_cmd_release, gm, blk, 0, e->stream, e->cmds, b);
+  return FPX_OK;
+}
+
+static int32_t cmds_put_check(const fpx_epx* e, int64_t buf_len, int32_t m) {
+  return !cmds_on(e) || buf_len < 0 || m < 0 || m > FPX_EPX_INBOX_MAX ? FPX_EINVAL : FPX_OK;
+}
+
+int32_t fpx_epx_cmds_put_dev(fpx_epx* e, const uint8_t* d_buf, int64_t buf_len, const int64_t* d_cmd_off, const int32_t* d_cmd_len,
+                             const int32_t* d_triple_id, int32_t m, int64_t* d_result) {
+  if (cmds_put_check(e, buf_len, m) || !d_result) return FPX_EINVAL;
+  DeviceScope _dg(e->cfg.device);
+  if (m == 0) {
+    HIPCHK(e, hipMemsetAsync(d_result, 0, 32, e->stream));
+    return FPX_OK;
+  }
+  if ((buf_len > 0 && !d_buf) || !d_cmd_off || !d_cmd_len || !d_triple_id) return FPX_EINVAL;
+  const int rc = cmds_put_launch(e, d_buf, buf_len, d_cmd_off, d_cmd_len, d_triple_id, m, true, (long long*)d_result);
+  return rc ? rc : launch_check(e);
+}
+
+int32_t fpx_epx_cmds_put(fpx_epx* e, const uint8_t* buf, int64_t buf_len, const int64_t* cmd_off, const int32_t* cmd_len,
+                         const int32_t* triple_id, int32_t m, int64_t* result) {
+  if (cmds_put_check(e, buf_len, m) || !result) return FPX_EINVAL;
+  result[0] = result[1] = result[2] = result[3] = 0;
+  if (m == 0) return FPX_OK;
+  if ((buf_len > 0 && !buf) || !cmd_off || !cmd_len || !triple_id) return FPX_EINVAL;
+  DeviceScope _dg(e->cfg.device);
+  const uint8_t* d_buf = nullptr;
+  const int64_t* d_off = nullptr;
+  const int32_t *d_len = nullptr, *d_triple = nullptr;
+  long long* d_res = nullptr;
+  return host_call(e, {in(d_buf, buf, (size_t)buf_len), in(d_off, cmd_off, m), in(d_len, cmd_len, m), in(d_triple, triple_id, m),
+                       out(d_res, result, 4)},
+                   [&]() -> int { return cmds_put_launch(e, d_buf, buf_len, d_off, d_len, d_triple, m, true, d_res); });
+}
+
+int32_t fpx_epx_cmds_read(fpx_epx* e, int32_t triple_id, uint8_t* out, int64_t cap, int32_t* len) {
+  if (!cmds_on(e) || triple_id < 0 || triple_id >= e->cmds.max_triples || cap < 0 || !len) return FPX_EINVAL;
+  DeviceScope _dg(e->cfg.device);
+  long long off = -1;
+  int32_t n = 0;
+  HIPCHK(e, hipMemcpyAsync(&off, e->cmds.off + triple_id, 8, hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(e, hipMemcpyAsync(&n, e->cmds.len + triple_id, 4, hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(e, hipStreamSynchronize(e->stream));
+  *len = off < 0 ? -1 : n;
+  if (off < 0 || n == 0) return FPX_OK;
+  if (n > cap) return FPX_ECAPACITY;
+  if (!out) return FPX_EINVAL;
+  HIPCHK(e, hipMemcpy(out, e->cmds.arena + off, (size_t)n, hipMemcpyDeviceToHost));
+  return FPX_OK;
+}
+
+int32_t fpx_epx_cmds_stats(fpx_epx* e, int64_t* out) {
+  if (!cmds_on(e) || !out) return FPX_EINVAL;
+  DeviceScope _dg(e->cfg.device);
+  HIPCHK(e, hipMemcpyAsync(out, e->cmds.meta, 32, hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(e, hipStreamSynchronize(e->stream));
+  return FPX_OK;
+}
+
 // ---- a replica's inbox from wire bytes: csrc/fpx_wire_epx_dev.hpp (include/fpx_wire.h) ---------------------------------------
 // the tick's check between the count and the scan (a classify on its own has none)
 struct ClsTick {
@@ -3415,7 +3534,9 @@ static int32_t replica_tick_impl(fpx_epx* e, const uint8_t* d_in, int64_t in_len
   if (stage2) *stage2 = true;
   o.kind = w.ri_kind, o.leader = w.leader, o.number = w.number, o.b_ord = w.b_ord, o.b_rep = w.b_rep;
   o.key_off = w.key_offsets, o.keys = w.keys, o.P = h[1], o.is_set = w.is_set, o.triple = w.triple, o.deps = w.deps, o.dend = w.dend;
-  return replica_inbox_launch<true>(e, o);
+  if ((rc = replica_inbox_launch<true>(e, o))) return rc;
+  // the burst's commands into the store, behind stage 2 and standing back behind its status: the spans are the decoder's
+  return cmds_on(e) ? cmds_put_launch(e, d_in, in_len, w.cmd_off, w.cmd_len, w.triple, m, false, nullptr) : FPX_OK;
 }
 
 static int32_t replica_tick_check(const fpx_epx* e, int64_t in_len, int32_t m, int32_t max_pairs) {
@@ -3479,7 +3600,7 @@ int32_t fpx_wire_epx_replica_tick(fpx_epx* e, const uint8_t* in_bytes, int64_t i
 static int32_t reply_encode_launch(fpx_epx* e, EreArgs a, const EpxReplyEncScratch& s) {
   static_assert(ERE_C_WORDS == EPX_REPLY_ENC_CTL_WORDS, "a call's control words as lay_epx_reply_enc sizes them");
   const size_t rows = scan_rows((size_t)a.m);
-  a.in.n = e->st.n, a.rows = (int32_t)rows, a.direct = e->enc_direct ? 1 : 0;
+  a.in.n = e->st.n, a.rows = (int32_t)rows, a.direct = e->enc_direct ? 1 : 0, a.bytewise = e->cmds_bytewise ? 1 : 0;
   a.lscan = s.lscan, a.ltot = s.ltot, a.lgt = s.lgt, a.ctl = s.ctl;
   HIPCHK(e, hipMemsetAsync(a.ctl, 0, ERE_C_WORDS * 4, e->stream));
   HIPCHK(e, hipMemsetAsync(a.ctl + ERE_C_BAD, ERE_NO_BAD & 0xff, 4, e->stream));
@@ -3501,12 +3622,19 @@ static int32_t reply_encode_check(const fpx_epx* e, int32_t m, const uint8_t* d_
              : FPX_OK;
 }
 
-int32_t fpx_wire_epx_encode_replica_replies_dev(fpx_epx* e, int32_t m, const int32_t* d_to, const int32_t* d_leader,
-                                                const int32_t* d_number, const int32_t* d_ballot_ordering,
-                                                const int32_t* d_ballot_replica, const int32_t* d_outcome,
-                                                const int32_t* d_out_ballot, const int32_t* d_out_status,
-                                                const int32_t* d_out_deps, const int32_t* d_out_values_end, uint8_t* d_out,
-                                                int64_t cap, int64_t* d_out_offsets, uint8_t* d_reply_kind, int64_t* d_totals) {
+// the context's command store as the encoder's source (none when the store is not enabled)
+static fpxw::EpxCmdSource cmds_source(const fpx_epx* e) {
+  fpxw::EpxCmdSource c;
+  if (cmds_on(e)) c.off = (const int64_t*)e->cmds.off, c.len = e->cmds.len, c.arena = e->cmds.arena, c.max_triples = e->cmds.max_triples;
+  return c;
+}
+
+// d_out_triple null: the encoder without a command source
+static int32_t reply_encode_dev(fpx_epx* e, int32_t m, const int32_t* d_to, const int32_t* d_leader, const int32_t* d_number,
+                                const int32_t* d_ballot_ordering, const int32_t* d_ballot_replica, const int32_t* d_outcome,
+                                const int32_t* d_out_ballot, const int32_t* d_out_status, const int32_t* d_out_deps,
+                                const int32_t* d_out_values_end, const int32_t* d_out_triple, uint8_t* d_out, int64_t cap,
+                                int64_t* d_out_offsets, uint8_t* d_reply_kind, int64_t* d_totals) {
   if (reply_encode_check(e, m, d_out, cap, d_out_offsets, d_reply_kind, d_totals)) return FPX_EINVAL;
   if (m > 0 && (!d_to || !d_leader || !d_number || !d_ballot_ordering || !d_ballot_replica || !d_outcome || !d_out_ballot ||
                 !d_out_status || !d_out_deps || !d_out_values_end))
@@ -3521,9 +3649,33 @@ int32_t fpx_wire_epx_encode_replica_replies_dev(fpx_epx* e, int32_t m, const int
     return rc;
   a.in = fpxw::EpxReplyIn{e->st.n,   d_to,         d_leader,     d_number,   d_ballot_ordering, d_ballot_replica,
                           d_outcome, d_out_ballot, d_out_status, d_out_deps, d_out_values_end};
+  if (d_out_triple) a.in.out_triple = d_out_triple, a.in.cmds = cmds_source(e);
   a.out = d_out, a.cap = cap, a.out_offsets = d_out_offsets, a.reply_kind = d_reply_kind, a.totals = d_totals;
   rc = reply_encode_launch(e, a, s);
   return rc ? rc : launch_check(e);
+}
+
+int32_t fpx_wire_epx_encode_replica_replies_dev(fpx_epx* e, int32_t m, const int32_t* d_to, const int32_t* d_leader,
+                                                const int32_t* d_number, const int32_t* d_ballot_ordering,
+                                                const int32_t* d_ballot_replica, const int32_t* d_outcome,
+                                                const int32_t* d_out_ballot, const int32_t* d_out_status,
+                                                const int32_t* d_out_deps, const int32_t* d_out_values_end, uint8_t* d_out,
+                                                int64_t cap, int64_t* d_out_offsets, uint8_t* d_reply_kind, int64_t* d_totals) {
+  return reply_encode_dev(e, m, d_to, d_leader, d_number, d_ballot_ordering, d_ballot_replica, d_outcome, d_out_ballot,
+                          d_out_status, d_out_deps, d_out_values_end, nullptr, d_out, cap, d_out_offsets, d_reply_kind, d_totals);
+}
+
+int32_t fpx_wire_epx_encode_replica_replies_cmds_dev(fpx_epx* e, int32_t m, const int32_t* d_to, const int32_t* d_leader,
+                                                     const int32_t* d_number, const int32_t* d_ballot_ordering,
+                                                     const int32_t* d_ballot_replica, const int32_t* d_outcome,
+                                                     const int32_t* d_out_ballot, const int32_t* d_out_status,
+                                                     const int32_t* d_out_deps, const int32_t* d_out_values_end,
+                                                     const int32_t* d_out_triple, uint8_t* d_out, int64_t cap,
+                                                     int64_t* d_out_offsets, uint8_t* d_reply_kind, int64_t* d_totals) {
+  if (m > 0 && !d_out_triple) return FPX_EINVAL;
+  return reply_encode_dev(e, m, d_to, d_leader, d_number, d_ballot_ordering, d_ballot_replica, d_outcome, d_out_ballot,
+                          d_out_status, d_out_deps, d_out_values_end, d_out_triple, d_out, cap, d_out_offsets, d_reply_kind,
+                          d_totals);
 }
 
 // replica_tick_impl, then the encoder on the decoded arrays the tick holds in scratch and on the inbox outputs -- the
@@ -3534,7 +3686,9 @@ static int32_t replica_tick_bytes_impl(fpx_epx* e, const uint8_t* d_in, int64_t 
   const int32_t m = o.m;
   EpxTickBytesScratch t;
   int rc;
-  if ((rc = carve(e, &e->enc_misc, &t, [&](Carver& c) { return lay_epx_tick_bytes(c, (size_t)m, (size_t)e->st.n); }))) return rc;
+  if ((rc = carve(e, &e->enc_misc, &t, [&](Carver& c) { return lay_epx_tick_bytes(c, (size_t)m, (size_t)e->st.n, cmds_on(e)); })))
+    return rc;
+  if (!o.out_triple) o.out_triple = t.out_triple;  // (null without the store: nobody reads it then)
   if (!o.outcome) o.outcome = t.outcome;
   if (!o.out_ballot) o.out_ballot = t.out_ballot;
   if (!o.out_status) o.out_status = t.out_status;
@@ -3552,6 +3706,8 @@ static int32_t replica_tick_bytes_impl(fpx_epx* e, const uint8_t* d_in, int64_t 
   a.m = m;
   a.in = fpxw::EpxReplyIn{e->st.n,   o.to,         w.leader,     w.number,   w.b_ord,  w.b_rep,
                           o.outcome, o.out_ballot, o.out_status, o.out_deps, o.out_end};
+  // (the burst's own commands are in the store by now: the put ran behind stage 2)
+  if (cmds_on(e)) a.in.out_triple = o.out_triple, a.in.cmds = cmds_source(e);
   return reply_encode_launch(e, a, t.enc);
 }
 

@@ -279,15 +279,35 @@ inline EpxReplyEncScratch lay_epx_reply_enc(Carver& c, size_t m) {
 
 // fpx_wire_epx_replica_tick_bytes_dev: the encoder's scratch, and the inbox outputs the encoder reads, which the tick keeps
 // here when the caller does not ask for them
+// (out_triple: on a context with the command store, which looks the replies' commands up by it)
 struct EpxTickBytesScratch {
   EpxReplyEncScratch enc;
-  int32_t *outcome, *out_ballot, *out_status, *out_end, *out_deps;
+  int32_t *outcome, *out_ballot, *out_status, *out_end, *out_deps, *out_triple;
 };
-inline EpxTickBytesScratch lay_epx_tick_bytes(Carver& c, size_t m, size_t n) {
+inline EpxTickBytesScratch lay_epx_tick_bytes(Carver& c, size_t m, size_t n, bool triple = false) {
   EpxTickBytesScratch s;
   s.enc = lay_epx_reply_enc(c, m);
   for (int32_t** a : {&s.outcome, &s.out_ballot, &s.out_status, &s.out_end}) *a = c.take<int32_t>(m);
   s.out_deps = c.take<int32_t>(m * n);
+  s.out_triple = triple ? c.take<int32_t>(m) : nullptr;
+  return s;
+}
+
+// fpx_epx_cmds.hpp, a put of m records: the writers' lengths and their scan in rows as above, with the rows' sums and the
+// total, the call's control words and its result when the caller wants none
+constexpr int EPX_CMDS_CTL_WORDS = 8;
+struct EpxCmdsPutScratch {
+  uint32_t* lscan;
+  int32_t *ltot, *lgt, *ctl;
+  long long* result;
+};
+inline EpxCmdsPutScratch lay_epx_cmds_put(Carver& c, size_t m) {
+  EpxCmdsPutScratch s;
+  s.lscan = c.take<uint32_t>(scan_rows(m) * INTERN_SCAN_ROW);
+  s.ltot = c.take<int32_t>(scan_rows(m));
+  s.lgt = c.take<int32_t>(1);
+  s.ctl = c.take<int32_t>(EPX_CMDS_CTL_WORDS);
+  s.result = c.take<long long>(4);
   return s;
 }
 

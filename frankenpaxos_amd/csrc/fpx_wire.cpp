@@ -680,18 +680,15 @@ int64_t fpx_wire_epaxos_encode_replica_inbound(uint8_t* out, int64_t cap, const 
 
 // the replies of a replica tick, a burst at a time: the emitter and the decision table of fpx_wire_epx_emit.hpp, which the
 // device encoder (fpx_wire_epx_enc_dev.hpp) compiles too
-int32_t fpx_wire_epx_encode_replica_replies(int32_t n, int32_t m, const int32_t* to, const int32_t* leader, const int32_t* number,
-                                            const int32_t* ballot_ordering, const int32_t* ballot_replica, const int32_t* outcome,
-                                            const int32_t* out_ballot, const int32_t* out_status, const int32_t* out_deps,
-                                            const int32_t* out_values_end, uint8_t* out, int64_t cap, int64_t* out_offsets,
-                                            uint8_t* reply_kind, int64_t* totals) {
+// (a.cmds: the command source of the _cmds form, or none)
+static int32_t encode_replica_replies(const EpxReplyIn& a, int32_t m, uint8_t* out, int64_t cap, int64_t* out_offsets,
+                                      uint8_t* reply_kind, int64_t* totals) {
   if (!totals) return FPX_EINVAL;
   totals[0] = totals[1] = totals[2] = 0, totals[3] = -1;
-  if (n < 1 || m < 0 || m > FPX_EPX_INBOX_MAX || cap < 0 || !out_offsets || (cap > 0 && !out)) return FPX_EINVAL;
-  if (m > 0 && (!to || !leader || !number || !ballot_ordering || !ballot_replica || !outcome || !out_ballot || !out_status ||
-                !out_deps || !out_values_end || !reply_kind))
+  if (a.n < 1 || m < 0 || m > FPX_EPX_INBOX_MAX || cap < 0 || !out_offsets || (cap > 0 && !out)) return FPX_EINVAL;
+  if (m > 0 && (!a.to || !a.leader || !a.number || !a.b_ord || !a.b_rep || !a.outcome || !a.out_ballot || !a.out_status ||
+                !a.out_deps || !a.out_end || !reply_kind))
     return FPX_EINVAL;
-  const EpxReplyIn a{n, to, leader, number, ballot_ordering, ballot_replica, outcome, out_ballot, out_status, out_deps, out_values_end};
   int64_t encoded = 0, bytes = 0, deferred = 0;
   out_offsets[0] = 0;
   for (int32_t i = 0; i < m; ++i) {
@@ -708,10 +705,46 @@ int32_t fpx_wire_epx_encode_replica_replies(int32_t n, int32_t m, const int32_t*
   for (int32_t i = 0; i < m; ++i) {
     const EpxReplyPlan p = epx_reply_plan(a, i);
     reply_kind[i] = (uint8_t)p.kind;
-    if (p.kind == EPX_REPLY_ENCODED) at += epx_reply_emit(out + at, a, i, p.outcome);
+    if (p.kind == EPX_REPLY_ENCODED && p.cmd_len >= 0) {
+      int64_t cmd_at = 0;
+      const int64_t len = epx_reply_emit_around(out + at, a, i, p, &cmd_at);
+      if (p.cmd_len > 0) memcpy(out + at + cmd_at, a.cmds.arena + p.cmd_off, (size_t)p.cmd_len);
+      at += len;
+    } else if (p.kind == EPX_REPLY_ENCODED) {
+      at += epx_reply_emit(out + at, a, i, p.outcome);
+    }
     out_offsets[i + 1] = at;
   }
   return FPX_OK;
+}
+
+int32_t fpx_wire_epx_encode_replica_replies(int32_t n, int32_t m, const int32_t* to, const int32_t* leader, const int32_t* number,
+                                            const int32_t* ballot_ordering, const int32_t* ballot_replica, const int32_t* outcome,
+                                            const int32_t* out_ballot, const int32_t* out_status, const int32_t* out_deps,
+                                            const int32_t* out_values_end, uint8_t* out, int64_t cap, int64_t* out_offsets,
+                                            uint8_t* reply_kind, int64_t* totals) {
+  const EpxReplyIn a{n, to, leader, number, ballot_ordering, ballot_replica, outcome, out_ballot, out_status, out_deps, out_values_end};
+  return encode_replica_replies(a, m, out, cap, out_offsets, reply_kind, totals);
+}
+
+int32_t fpx_wire_epx_encode_replica_replies_cmds(int32_t n, int32_t m, const int32_t* to, const int32_t* leader,
+                                                 const int32_t* number, const int32_t* ballot_ordering,
+                                                 const int32_t* ballot_replica, const int32_t* outcome, const int32_t* out_ballot,
+                                                 const int32_t* out_status, const int32_t* out_deps, const int32_t* out_values_end,
+                                                 const int32_t* out_triple, const int64_t* cmd_off, const int32_t* cmd_len,
+                                                 const uint8_t* arena, int32_t max_triples, uint8_t* out, int64_t cap,
+                                                 int64_t* out_offsets, uint8_t* reply_kind, int64_t* totals) {
+  EpxReplyIn a{n, to, leader, number, ballot_ordering, ballot_replica, outcome, out_ballot, out_status, out_deps, out_values_end};
+  // a store is all of its parts (and the triples to look up) or none: none is the function above
+  if (cmd_off || cmd_len || max_triples != 0) {
+    if (!cmd_off || !cmd_len || max_triples < 0 || (m > 0 && !out_triple)) {
+      if (totals) totals[0] = totals[1] = totals[2] = 0, totals[3] = -1;
+      return FPX_EINVAL;
+    }
+    a.out_triple = out_triple;
+    a.cmds.off = cmd_off, a.cmds.len = cmd_len, a.cmds.arena = arena, a.cmds.max_triples = max_triples;
+  }
+  return encode_replica_replies(a, m, out, cap, out_offsets, reply_kind, totals);
 }
 
 int32_t fpx_wire_epaxos_decode_replica_inbound(const uint8_t* buf, int64_t buf_len, const int64_t* offsets, int32_t n,

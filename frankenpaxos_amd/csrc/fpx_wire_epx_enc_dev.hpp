@@ -20,13 +20,17 @@
 //     direct  every lane runs the Writer at its own offset of the output: byte stores to HBM.  A wavefront that holds a
 //             reply longer than ERE_SLOT (a PreAcceptOk with explicit ids, or one with wide watermarks at n = 7) goes this
 //             way whole; FPX_EPX_ENC_DIRECT in the environment of fpx_epx_create sends every wavefront this way (the A/B of
-//             profiles/epx_wire_replica_replies.md).
+//             profiles/epx_wire_replica_replies.md).  So does a wavefront that holds a reply with a stored command (a Commit
+//             back, a PrepareOk of a seen instance: fpx_wire_epx_encode_replica_replies_cmds_dev): the lane writes the
+//             fields in front of and behind the command, and the command's bytes are copied from the store's arena by the
+//             whole wavefront, one command after the other (cmds_wave_copy of fpx_epx_cmds.hpp, the store's own copy).
 // wave64; plain C++ stores only.
 //
 // Errors are PER-CALL codes, kept in status words of their own (EPX_ST_ENC): a reply buffer that is too small
 // (FPX_ECAPACITY) or an outcome outside 0 .. 8 (FPX_EINVAL) stops THIS encode; no later kernel of the context stands back
 // behind it, and fpx_epx_sync returns and clears it like any status.
 #pragma once
+#include "fpx_epx_cmds.hpp"
 #include "fpx_wire_epx_emit.hpp"
 
 enum { EPX_ST_ENC = 3, EPX_ST_ENC_INDEX = 4 };  // status words: the encoder's per-call code and its index
@@ -37,7 +41,7 @@ enum { ERE_C_BAD = 0, ERE_C_GO = 1, ERE_C_ENCODED = 2, ERE_C_DEFERRED = 3, ERE_C
 
 struct EreArgs {
   fpxw::EpxReplyIn in;
-  int32_t m, rows, direct;
+  int32_t m, rows, direct, bytewise;  // bytewise: the command copy's form (fpx_epx_cmds.hpp)
   uint8_t* out;
   int64_t cap;
   int64_t* out_offsets;  // [m + 1]
@@ -78,7 +82,7 @@ __device__ __forceinline__ bool ere_refused(const EpxState& st) {
 }
 
 // behind the two levels of the scan.  ltot[j] is the rows' exclusive scan modulo 2^32 and a row's sum is far below 2^32 (1024
-// replies of at most a few hundred bytes), so neighbours' differences are the rows' sums exactly and their 64-bit sum is the
+// replies of at most 2^16 bytes of command and a few hundred more), so neighbours' differences are the rows' sums exactly and their 64-bit sum is the
 // bytes needed, however large
 __global__ void __launch_bounds__(256) k_ere_decide(const EpxState st, const EreArgs a) {
   __shared__ unsigned long long bytes_all;
@@ -139,8 +143,18 @@ __global__ void __launch_bounds__(ERE_BLOCK) k_ere_emit(const EreArgs a) {
     if (i == a.m - 1) a.out_offsets[a.m] = (int64_t)(off + len);
   }
   const bool enc = p.kind == fpxw::EPX_REPLY_ENCODED;
-  const bool direct = a.direct != 0 || __any(len > (uint64_t)ERE_SLOT) != 0;  // the same in every lane of the wavefront
-  if (enc) (void)fpxw::epx_reply_emit(direct ? a.out + off : slot[wave][lane], a.in, i, p.outcome);
+  const bool cmd = enc && p.cmd_len >= 0;
+  const bool direct = a.direct != 0 || __any(len > (uint64_t)ERE_SLOT || cmd) != 0;  // the same in every lane of the wavefront
+  int64_t cmd_at = 0;
+  if (cmd) (void)fpxw::epx_reply_emit_around(a.out + off, a.in, i, p, &cmd_at);
+  else if (enc) (void)fpxw::epx_reply_emit(direct ? a.out + off : slot[wave][lane], a.in, i, p.outcome);
+  // the commands of the wavefront, one after the other, all 64 lanes on each
+  for (unsigned long long has = __ballot(cmd && p.cmd_len > 0); has; has &= has - 1) {
+    const int l = __ffsll((long long)has) - 1;
+    uint8_t* const dst = a.out + __shfl((long long)(off + (uint64_t)cmd_at), l);
+    const uint8_t* const src = a.in.cmds.arena + __shfl((long long)p.cmd_off, l);
+    cmds_wave_copy(dst, CmdOneRun{src, __shfl(p.cmd_len, l)}, lane, a.bytewise != 0);
+  }
   const int64_t s = __shfl((long long)off, 0), e = __shfl((long long)(off + len), 63);
   rel[wave][lane] = (int32_t)((int64_t)off - s);
   if (lane == 63) rel[wave][64] = (int32_t)(e - s);

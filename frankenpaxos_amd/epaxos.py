@@ -460,6 +460,57 @@ class EPaxos:
             raise FpxError(st, "fpx_epx_keys_read")
         return [out[off[j]:off[j + 1]].tobytes() for j in range(n)]
 
+    # ---- the command store (include/fpx.h fpx_epx_cmds_*) ----
+    CMD_MAX_LEN = 1 << 16    # FPX_EPX_CMD_MAX_LEN
+
+    def cmds_enable(self, max_triples, arena_bytes):
+        """fpx_epx_cmds_enable: the context keeps the triples' serialised commands on the device, by triple id"""
+        st = self.L.fpx_epx_cmds_enable(self._h, int(max_triples), int(arena_bytes))
+        if st:
+            raise FpxError(st, "fpx_epx_cmds_enable")
+
+    def cmds_put(self, commands=None, triple_id=None, packed=None):
+        """fpx_epx_cmds_put on a list of bytes (or packed = (bytes, off, len) arrays) and their triple ids:
+        (status, result[4] = new commands, new bytes, skipped, refused; on FPX_EINVAL -1 and the bad index)"""
+        buf, off, ln = self.pack_keys(commands) if packed is None else packed
+        buf = np.ascontiguousarray(buf, np.uint8)
+        off, ln = np.ascontiguousarray(off, np.int64), np.ascontiguousarray(ln, np.int32)
+        tr = np.ascontiguousarray(triple_id, np.int32)
+        assert len(tr) == len(off) == len(ln)
+        res = np.full(4, -9, np.int64)
+        st = self.L.fpx_epx_cmds_put(self._h, buf.ctypes.data if len(buf) else None, len(buf), off.ctypes.data, ln.ctypes.data,
+                                     tr.ctypes.data, len(off), res.ctypes.data)
+        return st, res
+
+    def cmds_put_dev(self, buf, off, ln, triple_id, result, buf_len=None):
+        """fpx_epx_cmds_put_dev on device tensors (uint8, int64, int32, int32 -> int64[4]), enqueued; the status comes with
+        sync()"""
+        st = self.L.fpx_epx_cmds_put_dev(self._h, buf.data_ptr(), buf.numel() if buf_len is None else buf_len, off.data_ptr(),
+                                         ln.data_ptr(), triple_id.data_ptr(), off.numel(), result.data_ptr())
+        if st:
+            raise FpxError(st, "fpx_epx_cmds_put_dev")
+
+    def cmds_read(self, triple_id):
+        """fpx_epx_cmds_read: the stored bytes of one triple id, None when it has none"""
+        n = C.c_int32(0)
+        st = self.L.fpx_epx_cmds_read(self._h, int(triple_id), None, 0, C.byref(n))
+        if st == _lib.FPX_ECAPACITY:
+            out = np.zeros(n.value, np.uint8)
+            st = self.L.fpx_epx_cmds_read(self._h, int(triple_id), out.ctypes.data, len(out), C.byref(n))
+            if st == 0:
+                return out.tobytes()
+        if st:
+            raise FpxError(st, "fpx_epx_cmds_read")
+        return None if n.value < 0 else b""
+
+    def cmds_stats(self):
+        """fpx_epx_cmds_stats: (commands stored, arena bytes used, records skipped so far, bursts refused so far)"""
+        out = np.zeros(4, np.int64)
+        st = self.L.fpx_epx_cmds_stats(self._h, out.ctypes.data)
+        if st:
+            raise FpxError(st, "fpx_epx_cmds_stats")
+        return tuple(int(x) for x in out)
+
     def wire_classify_dev(self, buf, cmd_off, cmd_len, max_pairs):
         """fpx_wire_epx_classify_dev on the serialised CommandOrNoops cmd_off / cmd_len locate in buf (uint8 array; all
         uploaded): a dict of numpy arrays key_offsets[m + 1], keys[num_pairs] (ids), is_set, is_noop, cmd_shape, result[4]
@@ -540,10 +591,26 @@ class EPaxos:
         if st:
             raise FpxError(st, "fpx_wire_epx_encode_replica_replies_dev")
 
-    def encode_replica_replies(self, cap=None, base_offset=0, **arrays):
+    def encode_replica_replies_cmds_dev(self, to, leader, number, ballot_ordering, ballot_replica, outcome, out_ballot,
+                                        out_status, out_deps, out_values_end, out_triple, out, cap, out_offsets, reply_kind,
+                                        totals, m=None):
+        """fpx_wire_epx_encode_replica_replies_cmds_dev: encode_replica_replies_dev with out_triple (int32[m]); the replies
+        that carry a stored command are encoded from the context's command store"""
+        from . import wire
+        L = wire._L()
+        d = lambda t: None if t is None else t.data_ptr()
+        st = L.fpx_wire_epx_encode_replica_replies_cmds_dev(
+            self._h, to.numel() if m is None else m, d(to), d(leader), d(number), d(ballot_ordering), d(ballot_replica), d(outcome),
+            d(out_ballot), d(out_status), d(out_deps), d(out_values_end), d(out_triple), d(out), cap, d(out_offsets), d(reply_kind),
+            d(totals))
+        if st:
+            raise FpxError(st, "fpx_wire_epx_encode_replica_replies_cmds_dev")
+
+    def encode_replica_replies(self, cap=None, base_offset=0, out_triple=None, **arrays):
         """the device encoder on host arrays (the ten of wire.EPX_REPLY_RECORDS): upload, encode, sync, download.  The result
         is wire.epx_encode_replica_replies's dict, with the same fills where the call writes nothing.  cap None: sized by a
-        first call; base_offset: the output starts that many bytes behind a 256-byte boundary"""
+        first call; base_offset: the output starts that many bytes behind a 256-byte boundary; out_triple: the _cmds_dev
+        call with these triple ids"""
         import torch
 
         from . import wire
@@ -551,12 +618,18 @@ class EPaxos:
         m = len(rec[0])
         dev = torch.device("cuda", torch.cuda.current_device())
         up = [torch.from_numpy(a.reshape(-1) if a.size else np.zeros(1, np.int32)).to(dev) for a in rec]
+        if out_triple is not None:
+            tr = np.ascontiguousarray(out_triple, np.int32)
+            up.append(torch.from_numpy(tr if tr.size else np.zeros(1, np.int32)).to(dev))
+            encode = self.encode_replica_replies_cmds_dev
+        else:
+            encode = self.encode_replica_replies_dev
         off = torch.full((m + 1,), -9, dtype=torch.int64, device=dev)
         kind = torch.full((max(m, 1),), 9, dtype=torch.uint8, device=dev)
         totals = torch.full((4,), -9, dtype=torch.int64, device=dev)
         torch.cuda.synchronize()
         if cap is None:
-            self.encode_replica_replies_dev(*up, None, 0, off, kind, totals, m=m)
+            encode(*up, None, 0, off, kind, totals, m=m)
             st = self.sync()
             if st not in (0, _lib.FPX_ECAPACITY):
                 return {"status_code": st, "out": np.zeros(0, np.uint8), "out_offsets": off.cpu().numpy(),
@@ -566,7 +639,7 @@ class EPaxos:
         buf = torch.full((base_offset + cap + 16,), 0xEE, dtype=torch.uint8, device=dev)
         out = buf[base_offset:]
         torch.cuda.synchronize()
-        self.encode_replica_replies_dev(*up, out if cap > 0 else None, cap, off, kind, totals, m=m)
+        encode(*up, out if cap > 0 else None, cap, off, kind, totals, m=m)
         st = self.sync()
         whole = buf.cpu().numpy()
         o, off = whole[base_offset:base_offset + cap], off.cpu().numpy()

@@ -23,6 +23,7 @@
 // through libfpx; there is no host implementation of the predicates or handlers in this file.
 #pragma once
 
+#include <array>
 #include <cstdint>
 #include <map>
 #include <optional>
@@ -1330,6 +1331,43 @@ class PreAcceptEngine {
     out.kind = (EntryKind)e[0], out.ballot = Ballot::decode(e[1]), out.voteBallot = Ballot::decode(e[2]);
     out.tripleId = e[3], out.largestBallot = Ballot::decode(e[4]);
     return out;
+  }
+
+  // ---- the command store (include/fpx.h, fpx_epx_cmds_*): triple id -> the serialised CommandOrNoop on the device, what
+  // `triples` is to a Replica that keeps them on the host.  commandsEnable once; commandsPut: one burst, command i belongs to
+  // tripleIds[i] (first stored wins) -> {new commands, new bytes, skipped records, refused}
+  void commandsEnable(int32_t maxTriples, int64_t arenaBytes) {
+    check(fpx_epx_cmds_enable(epx_, maxTriples, arenaBytes), "commandsEnable");
+  }
+  std::array<int64_t, 4> commandsPut(const std::vector<std::string>& commands, const std::vector<int32_t>& tripleIds) {
+    if (commands.size() != tripleIds.size()) throw std::invalid_argument("commandsPut: one triple id per command");
+    std::string bytes;
+    std::vector<int64_t> off;
+    std::vector<int32_t> len;
+    for (const std::string& c : commands) off.push_back((int64_t)bytes.size()), len.push_back((int32_t)c.size()), bytes += c;
+    std::array<int64_t, 4> result{};
+    check(fpx_epx_cmds_put(epx_, (const uint8_t*)bytes.data(), (int64_t)bytes.size(), off.data(), len.data(), tripleIds.data(),
+                           (int32_t)commands.size(), result.data()), "commandsPut");
+    return result;
+  }
+  // the stored bytes of a triple id; false: it has none
+  bool commandOf(int32_t tripleId, std::string* out) {
+    int32_t len = 0;
+    int32_t st = fpx_epx_cmds_read(epx_, tripleId, nullptr, 0, &len);
+    if (st == FPX_ECAPACITY) {
+      out->assign((size_t)len, '\0');
+      st = fpx_epx_cmds_read(epx_, tripleId, (uint8_t*)&(*out)[0], len, &len);
+    } else if (st == FPX_OK) {
+      out->clear();
+    }
+    check(st, "commandOf");
+    return len >= 0;
+  }
+  // {commands stored, arena bytes used, records skipped so far, bursts refused so far}
+  std::array<int64_t, 4> commandsStats() {
+    std::array<int64_t, 4> s{};
+    check(fpx_epx_cmds_stats(epx_, s.data()), "commandsStats");
+    return s;
   }
 
   // replica's conflict-index entry of a key: the TopOne watermarks of gets and of sets (util/TopOne.scala)

@@ -78,7 +78,10 @@ class GpuEPaxosEngine[Transport <: frankenpaxos.Transport[Transport]](
     leaderState: Boolean = false,        // also keep Replica.leaderStates on the device (GpuEPaxosReplica's remotePeers)
     recovery: Boolean = false,           // ... with the Preparing phase (GpuEPaxosReplica's originateRecovery); needs leaderState
     deviceKeys: Boolean = false,         // key strings -> key ids in the DEVICE's table (Native.epxKeysEnable); keyOf caches it
-    keyArenaBytes: Long = 1L << 24       // ... with this many bytes for the key strings
+    keyArenaBytes: Long = 1L << 24,      // ... with this many bytes for the key strings
+    deviceCommands: Boolean = false,     // triple id -> command bytes in the DEVICE's store too (Native.epxCmdsEnable); needs deviceKeys
+    maxDeviceTriples: Int = 1 << 22,     // ... for the triple ids below this
+    commandArenaBytes: Long = 1L << 28   // ... with this many bytes for the commands
 ) {
   val n: Int = config.n
   val hasLeaderState: Boolean = leaderState
@@ -103,6 +106,33 @@ class GpuEPaxosEngine[Transport <: frankenpaxos.Transport[Transport]](
   val nextNumber: Array[Int] = Array.fill(n)(0)             // Replica.nextAvailableInstance, per hosted leader
   private val keyIds = mutable.Map[String, Int]()
   if (deviceKeys) Native.check(Native.epxKeysEnable(handle, keyArenaBytes), logger)
+  // deviceCommands: the device keeps the triples' bytes as well, so the bytes tick encodes the Commit sent back and the
+  // PrepareOk of a seen instance itself.  The ticks put the commands of the frames they decode; every other triple id -- the
+  // ones leadRequests, intern and the recovery path hand to Native.epxLead* -- is put from `triples` here, before the next
+  // bytes tick could be asked for it.  The ids a bytes tick carries itself (`inTick`) are left to the tick's own put, so no
+  // command goes down twice; if that tick is refused the caller puts them after all (putTriples).
+  logger.check(!deviceCommands || deviceKeys)
+  val hasDeviceCommands: Boolean = deviceCommands
+  if (deviceCommands) Native.check(Native.epxCmdsEnable(handle, maxDeviceTriples, commandArenaBytes), logger)
+  private var triplesPut = 0
+  var maxCommandBytes = 0                                    // the longest command put so far: sizes the bytes tick's output
+  def putTriples(ids: Array[Int]): Unit = if (deviceCommands && ids.nonEmpty) {
+    val cmds = ids.map(t => triples(t).toByteArray)
+    val off = cmds.scanLeft(0L)(_ + _.length)
+    val bytes = new Array[Byte](off.last.toInt)
+    for ((c, i) <- cmds.zipWithIndex) Array.copy(c, 0, bytes, off(i).toInt, c.length)
+    val result = new Array[Long](4)
+    Native.check(Native.epxCmdsPut(handle, ids.length, bytes, off.last, off.init, cmds.map(_.length), ids, result), logger)
+    // neither is an error of the call, but the replies of these triples stay deferred (built here) from now on: say so
+    if (result(2) > 0) logger.warn(s"GpuEPaxosEngine: ${result(2)} commands skipped by the device store (id >= $maxDeviceTriples or longer than 65536 bytes)")
+    if (result(3) != 0) logger.warn(s"GpuEPaxosEngine: the device command store is full ($commandArenaBytes bytes): ${ids.length} commands not stored")
+    maxCommandBytes = math.max(maxCommandBytes, cmds.map(_.length).max)
+  }
+  def putNewTriples(inTick: Set[Int] = Set.empty): Unit = if (deviceCommands && triplesPut < triples.size) {
+    putTriples((triplesPut until triples.size).filterNot(inTick).toArray)
+    triplesPut = triples.size
+  }
+  def noteTickCommands(longest: Int): Unit = maxCommandBytes = math.max(maxCommandBytes, longest)
   // deviceKeys: the device hands out the ids (fpx_epx_keys_intern), also to the frames that go to Native.epxWireReplicaTick
   // as bytes; a miss here asks it and caches the answer, so the JVM and the device never hand out ids side by side
   private def deviceKeyOf(k: String): Int = {
@@ -630,13 +660,28 @@ class GpuEPaxosReplica[Transport <: frankenpaxos.Transport[Transport]](
     var at = 0L
     for ((f, i) <- frames.zipWithIndex) { inOffsets.putLong(8 * i, at); in.put(f); at += f.length; to.putInt(4 * i, index) }
     inOffsets.putLong(8 * k, at)
-    val outCap = 472L * k                                    // FPX_WIRE_EPX_REPLY_MAX: FPX_ECAPACITY cannot happen
+    // 472 * m is FPX_WIRE_EPX_REPLY_MAX: without the command store FPX_ECAPACITY cannot happen.  With it a reply may carry
+    // any stored command, 503 + its bytes (FPX_WIRE_EPX_CMD_REPLY_MAX, none above 65536): the worst case where that is small,
+    // else a budget of four times the burst's own bytes -- and a burst that outgrows it is answered the parsed way (below)
+    val carried = (for ((e, i) <- ev.zipWithIndex if e.commandOrNoop.nonEmpty && tripleId(i) >= 0) yield tripleId(i)).toSet
+    engine.putNewTriples(inTick = carried)                   // (the frames' own commands: the tick puts them)
+    if (engine.hasDeviceCommands)
+      engine.noteTickCommands(ev.flatMap(_.commandOrNoop).map(_.serializedSize).foldLeft(0)(math.max))
+    val worst = (503L + math.min(engine.maxCommandBytes, 65536)) * k
+    val outCap = if (!engine.hasDeviceCommands) 472L * k
+                 else math.min(math.min(worst, 503L * k + math.max(4 * inLen, 1L << 20)), Int.MaxValue - 8L)
     val out = direct(outCap.toInt); val outOffsets = direct(8 * (k + 1)); val replyKind = direct(k)
     val result = new Array[Long](6)
     val maxPairs = math.min(frames.map(_.length).sum, 1 << 24)   // (a key is at least two bytes of its frame)
     val st = Native.epxWireReplicaTickBytes(engine.handle, k, n, in, inLen, inOffsets, to, 0, tripleId, maxPairs, out, outCap,
                                             outOffsets, replyKind, outcome, reply, outDeps, result)
-    if (st == 1 && result(0) >= 0) return null               // a frame the device does not take: nothing applied, nothing interned
+    if (st == 1 && result(0) >= 0) {                         // a frame the device does not take: nothing applied, nothing interned
+      engine.putTriples(carried.toArray.sorted)              // (... nor stored: the parsed way's natives put no commands)
+      return null
+    }
+    // the encoder's FPX_ECAPACITY (result(3) > outCap): the tick WAS applied and outcome / reply / outDeps are valid, so every
+    // reply of this burst is built from them as a deferred one is
+    if (st == 5 && result(3) > outCap) return Array.fill[Array[Byte]](k)(null)
     Native.check(st, logger)
     Array.tabulate(k) { i =>
       if (replyKind.get(i) != 1) null

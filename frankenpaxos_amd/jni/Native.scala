@@ -232,6 +232,19 @@ object Native {
   // keys than numKeys or more bytes than the arena; 1: a key longer than 4096 bytes; nothing applied either way
   @native def epxKeysIntern(handle: Long, count: Int, bytes: Array[Byte], bytesLen: Long, off: Array[Long], len: Array[Int],
                             ids: Array[Int]): Int
+  // the context's command store (include/fpx.h, fpx_epx_cmds_enable): triple id -> the serialised CommandOrNoop on the device
+  // (what GpuEPaxosEngine.triples is on the JVM), ids below maxTriples, arenaBytes for the bytes.  Once per context.  With it
+  // the two ticks below keep the command of every frame under its triple id, and epxWireReplicaTickBytes encodes the Commit sent
+  // back and the PrepareOk of a PreAccepted / Accepted instance itself
+  @native def epxCmdsEnable(handle: Long, maxTriples: Int, arenaBytes: Long): Int
+  // one burst of commands (fpx_epx_cmds_put) for the triple ids that never pass through a tick (the ones handed to epxLead*):
+  // command p = bytes(off(p) until off(p) + len(p)) belongs to tripleId(p).  An id that has bytes keeps them; an id >=
+  // maxTriples or a command above 65536 bytes is skipped (its replies stay deferred); a burst that does not fit the arena stores
+  // nothing.  None of these is an error.  result (4 longs, may be null): new commands, new bytes, skipped, refused (0 / 1)
+  @native def epxCmdsPut(handle: Long, count: Int, bytes: Array[Byte], bytesLen: Long, off: Array[Long], len: Array[Int],
+                         tripleId: Array[Int], result: Array[Long]): Int
+  // out (4 longs): commands stored, arena bytes used, records skipped so far, bursts refused so far
+  @native def epxCmdsStats(handle: Long, out: Array[Long]): Int
   // one tick of hosted replicas from wire bytes (include/fpx_wire.h, fpx_wire_epx_replica_tick; needs epxKeysEnable): in /
   // inOffsets / to as epxWireLeaderTick's; PreAccept, Accept, Commit and Prepare frames only.  The triple id of message i is
   // tripleId(i), or with tripleId null tripleBase + i (-1 for a Prepare).  The outputs are epxReplicaInboxMk's.  result(0):
@@ -248,7 +261,9 @@ object Native {
   // replyKind(i) (m bytes) is 0 (nothing to send) or 2 (deferred: a Commit sent back, a PrepareOk that carries a command, a
   // PreAcceptOk of a triple stored by id or with more than 64 explicit ids -- build that one from outcome / reply / outDeps as
   // before).  outcome, reply and outDeps may be null.  result (6 longs): the bad index and the pairs as above, then the replies
-  // encoded, the bytes needed, the records deferred and -1.  outCap >= 472 * m (FPX_WIRE_EPX_REPLY_MAX) always suffices;
+  // encoded, the bytes needed, the records deferred and -1.  outCap >= 472 * m (FPX_WIRE_EPX_REPLY_MAX) always suffices
+  // without the command store; with it a reply that carries a command of c bytes takes up to 503 + c
+  // (FPX_WIRE_EPX_CMD_REPLY_MAX) and only records with by-id dependencies or more than 64 explicit ids stay deferred;
   // status 5 with result(3) > outCap: the tick WAS applied and the arrays are valid -- encode from them
   @native def epxWireReplicaTickBytes(handle: Long, m: Int, numReplicas: Int, in: java.nio.ByteBuffer, inLen: Long,
                                       inOffsets: java.nio.ByteBuffer, to: java.nio.ByteBuffer, tripleBase: Int,

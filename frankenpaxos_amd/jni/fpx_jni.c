@@ -1539,6 +1539,47 @@ JNIEXPORT jint JNICALL Java_frankenpaxos_gpu_Native_epxKeysIntern(JNIEnv* env, j
   return st;
 }
 
+/* The context's command store (fpx_epx_cmds_enable): triple id -> the serialised CommandOrNoop on the device, ids in
+ * [0, maxTriples), arenaBytes for the bytes.  With it the ticks below keep every frame's command and epxWireReplicaTickBytes
+ * encodes the Commit sent back and the PrepareOk of a seen instance itself */
+JNIEXPORT jint JNICALL Java_frankenpaxos_gpu_Native_epxCmdsEnable(JNIEnv* env, jclass cls, jlong h, jint maxTriples,
+                                                                  jlong arenaBytes) {
+  return fpx_epx_cmds_enable((fpx_epx*)(intptr_t)h, maxTriples, arenaBytes);
+}
+
+/* One burst of commands (fpx_epx_cmds_put): command p = bytes[off[p] .. off[p] + len[p]) belongs to triple tripleId[p]; an
+ * id that has bytes keeps them.  result[4] (may be null): new commands, new bytes, skipped records, refused (0 / 1); on
+ * FPX_EINVAL for a span outside bytes: -1 and the lowest such index */
+JNIEXPORT jint JNICALL Java_frankenpaxos_gpu_Native_epxCmdsPut(JNIEnv* env, jclass cls, jlong h, jint count, jbyteArray bytes,
+                                                               jlong bytesLen, jlongArray off, jintArray len, jintArray tripleId,
+                                                               jlongArray result) {
+  if (count < 0 || bytesLen < 0 || !h || !opt(env, result, 4)) return FPX_EINVAL;
+  if (count > 0 && (!has(env, off, count) || !has(env, len, count) || !has(env, tripleId, count) ||
+                    (bytesLen > 0 && !has(env, bytes, bytesLen))))
+    return FPX_EINVAL;
+  jbyte* b = (count > 0 && bytesLen > 0) ? in_bytes(env, bytes, bytesLen) : NULL;
+  jlong* o = count > 0 ? in_longs(env, off, count) : NULL;
+  jint *l = count > 0 ? in_ints(env, len, count) : NULL, *t = count > 0 ? in_ints(env, tripleId, count) : NULL;
+  int64_t res[4] = {0, 0, 0, 0};
+  int32_t st = count > 0 && ((bytesLen > 0 && !b) || !o || !l || !t)
+                   ? FPX_ENOMEM
+                   : fpx_epx_cmds_put((fpx_epx*)(intptr_t)h, (const uint8_t*)b, bytesLen, (const int64_t*)o, l, t, count, res);
+  const jlong r[4] = {res[0], res[1], res[2], res[3]};
+  put_longs(env, result, 4, r);
+  free(b); free(o); free(l); free(t);
+  return st;
+}
+
+/* fpx_epx_cmds_stats: out[4] = commands stored, arena bytes used, records skipped so far, bursts refused so far */
+JNIEXPORT jint JNICALL Java_frankenpaxos_gpu_Native_epxCmdsStats(JNIEnv* env, jclass cls, jlong h, jlongArray out) {
+  if (!h || !has(env, out, 4)) return FPX_EINVAL;
+  int64_t s[4] = {0, 0, 0, 0};
+  const int32_t st = fpx_epx_cmds_stats((fpx_epx*)(intptr_t)h, s);
+  const jlong r[4] = {s[0], s[1], s[2], s[3]};
+  if (st == FPX_OK) put_longs(env, out, 4, r);
+  return st;
+}
+
 /* One tick of hosted EPaxos replicas from wire bytes (fpx_wire_epx_replica_tick): in (inLen bytes), inOffsets (m + 1 longs) and
  * to (m ints) are direct ByteBuffers in native byte order, as epxWireLeaderTick's; tripleId (m ints, may be null: tripleBase +
  * i, -1 for a Prepare); the outputs are epxReplicaInboxMk's (each may be null): outcome m; reply = ballot | PrepareOk status |

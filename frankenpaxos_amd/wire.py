@@ -96,10 +96,13 @@ def _L():
         # a replica tick's replies as wire bytes: the host batch encoder, the device encoder and the bytes tick
         L.fpx_wire_epx_encode_replica_replies.argtypes = [C.c_int32, C.c_int32] + [VP] * 11 + [C.c_int64, VP, VP, VP]
         L.fpx_wire_epx_encode_replica_replies_dev.argtypes = [VP, C.c_int32] + [VP] * 11 + [C.c_int64, VP, VP, VP]
+        L.fpx_wire_epx_encode_replica_replies_cmds.argtypes = [C.c_int32, C.c_int32] + [VP] * 14 + [C.c_int32, VP, C.c_int64, VP, VP, VP]
+        L.fpx_wire_epx_encode_replica_replies_cmds_dev.argtypes = [VP, C.c_int32] + [VP] * 12 + [C.c_int64, VP, VP, VP]
         tick_bytes = [VP, VP, C.c_int64, VP, C.c_int32, VP, C.c_int32, VP, C.c_int32, VP, C.c_int64, VP, VP, VP] + [VP] * 6
         L.fpx_wire_epx_replica_tick_bytes_dev.argtypes = tick_bytes + [VP, VP]
         L.fpx_wire_epx_replica_tick_bytes.argtypes = tick_bytes + [I32P, I32P]
         for name in ("fpx_wire_epx_encode_replica_replies", "fpx_wire_epx_encode_replica_replies_dev",
+                     "fpx_wire_epx_encode_replica_replies_cmds", "fpx_wire_epx_encode_replica_replies_cmds_dev",
                      "fpx_wire_epx_replica_tick_bytes_dev", "fpx_wire_epx_replica_tick_bytes"):
             getattr(L, name).restype = C.c_int32
         L.fpx_wire_phase2b_rows.argtypes = [C.c_int32, VP, VP, VP, VP, VP, C.c_int32, I32P, VP, VP, VP]
@@ -454,6 +457,15 @@ def epx_classify(buf, cmd_off, cmd_len, max_pairs=None):
 
 
 EPX_REPLY_MAX = 472   # FPX_WIRE_EPX_REPLY_MAX
+EPX_CMD_MAX_LEN = 1 << 16   # FPX_EPX_CMD_MAX_LEN
+
+
+def epx_cmd_reply_max(cmd_len):
+    """FPX_WIRE_EPX_CMD_REPLY_MAX(cmd_len): no reply that carries a command of cmd_len bytes is longer"""
+    vl = lambda v: 1 if v < 128 else 2 if v < 16384 else 3
+    inner = 496 + vl(cmd_len) + cmd_len
+    return 1 + vl(inner) + inner
+
 EPX_REPLY_NONE, EPX_REPLY_ENCODED, EPX_REPLY_DEFERRED = 0, 1, 2
 # the records of a replica tick, in the encoders' argument order: the decoded messages, then replica_inbox's outputs
 EPX_REPLY_RECORDS = ("to", "leader", "number", "ballot_ordering", "ballot_replica", "outcome", "out_ballot", "out_status",
@@ -469,15 +481,34 @@ def epx_reply_records(n, **arrays):
     return rec
 
 
-def epx_encode_replica_replies(n, cap=None, out=None, **arrays):
+def epx_encode_replica_replies_cmds(n, out_triple, store, cap=None, out=None, **arrays):
+    """fpx_wire_epx_encode_replica_replies_cmds: epx_encode_replica_replies with out_triple (int32[m]) and a command store
+    given as plain arrays, store = (cmd_off int64[max_triples], cmd_len int32[max_triples], arena uint8) or None for no
+    store; the same dict"""
+    tr = np.ascontiguousarray(out_triple, np.int32)
+    if store is None:
+        extra = [tr.ctypes.data if tr.size else None, None, None, None, 0]
+    else:
+        coff, clen = np.ascontiguousarray(store[0], np.int64), np.ascontiguousarray(store[1], np.int32)
+        arena = np.ascontiguousarray(store[2], np.uint8)
+        assert len(coff) == len(clen)
+        extra = [tr.ctypes.data if tr.size else None, coff.ctypes.data, clen.ctypes.data,
+                 arena.ctypes.data if arena.size else None, len(coff)]
+    return epx_encode_replica_replies(n, cap=cap, out=out, _fn=(_L().fpx_wire_epx_encode_replica_replies_cmds, extra), **arrays)
+
+
+def epx_encode_replica_replies(n, cap=None, out=None, _fn=None, **arrays):
     """fpx_wire_epx_encode_replica_replies, the host batch encoder of a replica tick's replies.  arrays: the ten of
     EPX_REPLY_RECORDS.  cap None: sized by a first call (cap 0, no buffer).  A dict: status_code, out (uint8[cap], or the
     array passed in), out_offsets (int64[m + 1]), reply_kind (uint8[m]), totals (int64[4]: encoded, bytes needed, deferred,
     the first unknown outcome) and replies, the list of per-message bytes on FPX_OK; what the call leaves alone keeps
-    its fill (offsets -9, kinds 9, bytes 0xEE)"""
+    its fill (offsets -9, kinds 9, bytes 0xEE).  (_fn: the _cmds form's function and its extra arguments.)"""
     rec = epx_reply_records(n, **arrays)
     m = len(rec[0])
-    fn = _L().fpx_wire_epx_encode_replica_replies
+    if _fn is None:
+        fn = _L().fpx_wire_epx_encode_replica_replies
+    else:
+        fn = lambda n_, m_, *a: _fn[0](n_, m_, *a[:10], *_fn[1], *a[10:])
     off, kind, totals = np.full(m + 1, -9, np.int64), np.full(m, 9, np.uint8), np.full(4, -9, np.int64)
     p = lambda a: a.ctypes.data if a is not None and a.size else None
     if cap is None:

@@ -1192,6 +1192,46 @@ int32_t fpx_epx_keys_intern_dev(fpx_epx* epx, const uint8_t* d_bytes, int64_t by
 int32_t fpx_epx_keys_intern(fpx_epx* epx, const uint8_t* bytes, int64_t bytes_len, const int64_t* off, const int32_t* len,
                             int32_t P, int32_t* ids);
 int32_t fpx_epx_keys_read(fpx_epx* epx, int32_t first_id, int32_t n, int32_t* key_off_out, uint8_t* bytes_out, int64_t cap);
+/* ---- the command store: a triple's serialised CommandOrNoop, by triple id, on the device ---------------------------------
+ * The entry points above know a triple by its id alone; its bytes live with the caller (on the JVM, engine.triples of
+ * jni/EPaxosNative.scala).  A context that calls fpx_epx_cmds_enable keeps them on the device as well (csrc/fpx_epx_cmds.hpp):
+ * per triple id in [0, max_triples) a 64-bit arena offset (-1 = no bytes) and a length, and a byte arena of arena_bytes that
+ * only grows -- the command log never forgets, and neither does the store.  With it the replies that carry a stored command
+ * (the Commit sent back, the PrepareOk of a PreAccepted / Accepted instance) are encoded on the device
+ * (include/fpx_wire.h).  Opt-in: a context that never enables it is what it was.  A second call, max_triples < 1 or a negative
+ * size: FPX_EINVAL.
+ *
+ * fpx_epx_cmds_put: ONE burst of m records; record i's command is buf[cmd_off[i] .. cmd_off[i] + cmd_len[i]) and belongs to
+ * triple triple_id[i].  Record i is considered only if triple_id[i] >= 0 and cmd_len[i] >= 0 (a Prepare has -1 in both).
+ * The arena is a function of the input alone, whatever the schedule:
+ *   - an id >= max_triples, or a length above FPX_EPX_CMD_MAX_LEN, is SKIPPED: counted, no error; the replies of such a
+ *     triple stay deferred;
+ *   - an id that has bytes already is left alone: first stored wins and nothing is compared (equal ids mean equal triples:
+ *     that contract is the caller's, above);
+ *   - among the records of the burst with a new id the lowest index is the writer;
+ *   - the writers' commands are packed into the arena in index order, without padding;
+ *   - new bytes that do not fit the free arena, or reach 4 GiB in one burst (the scan is 32 bits wide): nothing of the burst
+ *     is stored, the burst counts as one REFUSED burst.  This is no context status: the call is FPX_OK.
+ *   result[4]: new commands, new bytes, skipped records, refused (0 / 1).
+ * FPX_EINVAL with nothing stored and nothing counted: a considered record whose (cmd_off, cmd_len) lies outside buf --
+ * result is then {-1, the lowest such index, 0, 0}; a context without the store; m > FPX_EPX_INBOX_MAX; NULL arrays.
+ * m = 0 is FPX_OK, result 0.
+ * fpx_epx_cmds_put_dev: device pointers on the context's stream, no host wait; status through fpx_epx_sync.  A status
+ * already raised on the context in front of it: it stands back, nothing stored, nothing counted, result 0.
+ * fpx_epx_cmds_read: the bytes of one id into out[0 .. cap): *len = their number, -1 = the id has no bytes (FPX_OK);
+ * *len > cap: FPX_ECAPACITY, call again.  An id outside [0, max_triples): FPX_EINVAL.  Waits for the stream.
+ * fpx_epx_cmds_stats: out[4] = commands stored, arena bytes used, records skipped so far, bursts refused so far.
+ * The copy has two forms (csrc/fpx_epx_cmds.hpp), the same bytes either way: lane l of a wavefront takes byte l, l + 64, ... of
+ * its span (the default: the faster one on commands of tens of bytes, the A/B of profiles/epx_wire_replica_cmds.md), or, with
+ * FPX_EPX_CMDS_WORDS in the environment of fpx_epx_create, aligned 16-byte words assembled from the unaligned source. */
+#define FPX_EPX_CMD_MAX_LEN (1 << 16)
+int32_t fpx_epx_cmds_enable(fpx_epx* epx, int32_t max_triples, int64_t arena_bytes);
+int32_t fpx_epx_cmds_put_dev(fpx_epx* epx, const uint8_t* d_buf, int64_t buf_len, const int64_t* d_cmd_off,
+                             const int32_t* d_cmd_len, const int32_t* d_triple_id, int32_t m, int64_t* d_result);
+int32_t fpx_epx_cmds_put(fpx_epx* epx, const uint8_t* buf, int64_t buf_len, const int64_t* cmd_off, const int32_t* cmd_len,
+                         const int32_t* triple_id, int32_t m, int64_t* result);
+int32_t fpx_epx_cmds_read(fpx_epx* epx, int32_t triple_id, uint8_t* out, int64_t cap, int32_t* len);
+int32_t fpx_epx_cmds_stats(fpx_epx* epx, int64_t* out);
 /* readback (parity) of one leader state: out[0] = phase (0 none, 1 PreAccepting, 2 Accepting, 3 Preparing; 0 when not live),
  * out[1] = ballot, out[2] = avoidFastPath, out[3] = triple id, out[4] = the key word as stored (the key; -1 for a Noop
  * or a command without keys; FPX_EPX_KEY_LIST for a list of two or more distinct keys), out[5] = is_set, out[6] = who has answered (bit

@@ -567,7 +567,8 @@ int32_t fpx_wire_epx_replica_tick(struct fpx_epx* epx, const uint8_t* in, int64_
  *   PREPARE_OK                         out_status 0: PrepareOk(the message's ballot, instance, to[i], voteBallot, NotSeen)
  *                                      without the three optional fields; voteBallot = (-1, -1), the reference's nullBallot,
  *                                      when out_ballot < 0.  reply_kind 1.  Any other out_status: reply_kind 2, the reply
- *                                      carries the stored triple's CommandOrNoop, whose bytes live with the caller
+ *                                      carries the stored triple's CommandOrNoop, whose bytes live with the caller (but see
+ *                                      "with the command store" below)
  *   COMMIT_BACK                        reply_kind 2, for the same reason
  * A deferred record is no error: it contributes no bytes and the caller builds that one reply from the struct-of-arrays
  * outputs, as it does today.  (The steady traffic of a replica is outcomes 1, 3 and 7; the deferred ones are recovery and
@@ -609,8 +610,58 @@ int32_t fpx_wire_epx_replica_tick(struct fpx_epx* epx, const uint8_t* in, int64_
  * index and pair count, then -- on FPX_OK -- 8 (m + 1) bytes of offsets, m bytes of kinds and the totals[1] bytes of the
  * replies, NOT out_cap bytes; plus 4 bytes per message for each requested struct-of-arrays output (4 n for out_deps), against
  * the (5 + n) x 4 bytes per message fpx_wire_epx_replica_tick moves for all six.  out_cap bytes are staged on the device.
- * Deviations from the issue's proposal: totals has a fourth word; reply_kind is bytes. */
+ * Deviations from the issue's proposal: totals has a fourth word; reply_kind is bytes.
+ *
+ * ---- with the command store (include/fpx.h, fpx_epx_cmds_*) ----
+ * Everything above holds for a context without the store and for the two encoders above on any context.  The _cmds forms take
+ * out_triple as well and a command source -- triple t's serialised CommandOrNoop is arena[cmd_off[t] .. cmd_off[t] + cmd_len[t]),
+ * cmd_off[t] < 0 = no bytes, t in [0, max_triples) -- and encode the two replies that carry a stored command:
+ *   COMMIT_BACK                        Commit(instance, the stored CommandOrNoop verbatim, 0, deps)       reply_kind 1
+ *   PREPARE_OK, out_status 2 / 3       PrepareOk(the message's ballot, instance, to[i], voteBallot, PreAccepted / Accepted
+ *                                      (wire status out_status - 1), the stored CommandOrNoop, 0, deps)  reply_kind 1
+ * when out_triple[i] is in range and has bytes, out_deps[i * n] >= 0 and the own column has at most FPX_WIRE_EPX_FOLD_MAX
+ * explicit ids (deps as a PreAcceptOk's, above); otherwise the record stays deferred (reply_kind 2), as does a PREPARE_OK
+ * of any other out_status but 0.  What is left deferred with the store: dependencies known by id only, more than 64 explicit
+ * ids, a triple the store skipped or never saw.
+ * FPX_WIRE_EPX_CMD_REPLY_MAX(cmd_len): no reply that carries a command of cmd_len <= FPX_EPX_CMD_MAX_LEN bytes is longer, under
+ * the assumptions of FPX_WIRE_EPX_REPLY_MAX.  It is a PrepareOk whose voteBallot is nullBallot: the ballot 9, the instance 10,
+ * replica_index 2, voteBallot 24 (two ten-byte varints), status 2, the command 1 + varint(cmd_len) + cmd_len,
+ * sequence_number 2 and 3 + 443 of dependencies: 496 + varint(cmd_len) + cmd_len of inner bytes, under 1 + varint(inner) of
+ * wrapper.
+ * fpx_wire_epx_encode_replica_replies_cmds: the host batch encoder with the store as plain arrays; cmd_off == cmd_len == NULL
+ * and max_triples == 0 is no store, exactly fpx_wire_epx_encode_replica_replies.
+ * fpx_wire_epx_encode_replica_replies_cmds_dev: the _dev arguments and d_out_triple (required for m > 0); the source is the
+ * context's store (a context without one: exactly the _dev call).  No host wait, the same capture rules; the store's arrays
+ * are read, so a put enqueued in front of it on the stream is seen.
+ * On a context with the store fpx_wire_epx_replica_tick[_dev] and fpx_wire_epx_replica_tick_bytes[_dev] PUT the burst's commands
+ * (the decoded cmd_off / cmd_len, triple_id or triple_base + i) behind stage 2, standing back behind its status: a burst
+ * that is refused anywhere stores nothing.  The put takes the command of EVERY decoded frame of an applied burst, whatever its
+ * outcome: a frame the inbox answers with a Nack or ignores leaves its bytes in the arena too, under its triple id, although
+ * that triple never enters the command log (the arena is sized by the frames received, not by the instances stored).  The
+ * bytes tick then encodes with the store, so a Commit and a Prepare of one
+ * instance in ONE burst give a reply that carries that burst's bytes.  totals, reply_kind and the refusals keep their meaning;
+ * a reply may now be as long as FPX_WIRE_EPX_CMD_REPLY_MAX(cmd_len), so m x FPX_WIRE_EPX_REPLY_MAX no longer rules FPX_ECAPACITY
+ * out: that code from the encoder still means the tick was applied, totals[1] says what to allocate, and the caller re-encodes
+ * with fpx_wire_epx_encode_replica_replies_cmds_dev from the struct-of-arrays outputs it asked for. */
 #define FPX_WIRE_EPX_REPLY_MAX 472
+#define FPX_WIRE_VARINT_LEN21(v) ((v) < (1 << 7) ? 1 : (v) < (1 << 14) ? 2 : 3) /* v < 2^21 */
+#define FPX_WIRE_EPX_CMD_REPLY_INNER(cmd_len) (496 + FPX_WIRE_VARINT_LEN21(cmd_len) + (cmd_len))
+#define FPX_WIRE_EPX_CMD_REPLY_MAX(cmd_len) \
+  (1 + FPX_WIRE_VARINT_LEN21(FPX_WIRE_EPX_CMD_REPLY_INNER(cmd_len)) + FPX_WIRE_EPX_CMD_REPLY_INNER(cmd_len))
+int32_t fpx_wire_epx_encode_replica_replies_cmds(int32_t n, int32_t m, const int32_t* to, const int32_t* leader,
+                                                 const int32_t* number, const int32_t* ballot_ordering,
+                                                 const int32_t* ballot_replica, const int32_t* outcome, const int32_t* out_ballot,
+                                                 const int32_t* out_status, const int32_t* out_deps, const int32_t* out_values_end,
+                                                 const int32_t* out_triple, const int64_t* cmd_off, const int32_t* cmd_len,
+                                                 const uint8_t* arena, int32_t max_triples, uint8_t* out, int64_t cap,
+                                                 int64_t* out_offsets, uint8_t* reply_kind, int64_t* totals);
+int32_t fpx_wire_epx_encode_replica_replies_cmds_dev(struct fpx_epx* epx, int32_t m, const int32_t* d_to, const int32_t* d_leader,
+                                                     const int32_t* d_number, const int32_t* d_ballot_ordering,
+                                                     const int32_t* d_ballot_replica, const int32_t* d_outcome,
+                                                     const int32_t* d_out_ballot, const int32_t* d_out_status,
+                                                     const int32_t* d_out_deps, const int32_t* d_out_values_end,
+                                                     const int32_t* d_out_triple, uint8_t* d_out, int64_t cap,
+                                                     int64_t* d_out_offsets, uint8_t* d_reply_kind, int64_t* d_totals);
 int32_t fpx_wire_epx_encode_replica_replies(int32_t n, int32_t m, const int32_t* to, const int32_t* leader, const int32_t* number,
                                             const int32_t* ballot_ordering, const int32_t* ballot_replica, const int32_t* outcome,
                                             const int32_t* out_ballot, const int32_t* out_status, const int32_t* out_deps,
