@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 from tests import epaxos_cmd_cases as CC
+from tests.epaxos_cluster import KINDS, command_of, frame  # noqa: F401  (shared with the cluster tests; imported from here too)
 from tests import epaxos_inbox_mk_model as MM
 from tests import epaxos_inbox_mk_streams as MS
 from tests import epaxos_inbox_model as IM
@@ -16,8 +17,6 @@ from tests import epaxos_inbox_streams as S
 pytestmark = pytest.mark.gpu
 NK, NI = 4, 64
 EINVAL, ECAPACITY = 1, 5
-KINDS = {16: IM.IN_PRE_ACCEPT, 18: IM.IN_ACCEPT, 20: IM.IN_COMMIT, 21: IM.IN_PREPARE}
-WIRE_KIND = {v: k for k, v in KINDS.items()}
 
 
 @pytest.fixture(scope="module")
@@ -44,26 +43,6 @@ def wire_burst(seed, n, m, **kw):
             x = x[:9] + ([0] * n, 0)
         out.append(x)
     return out
-
-
-def command_of(x):
-    """the serialised CommandOrNoop of a message: a list without keys travels as a Noop, a get or a set without keys"""
-    keys = [b"k%d" % k for k in x[6]]
-    if not keys and x[8] % 3 == 0:
-        return CC.NOOP
-    return (CC.set_ if x[7] else CC.get)(keys, client_id=x[8])
-
-
-def frame(wire, x, command=None):
-    kind, to, L, inst, bo, br, keys, is_set, tid, w, end = x
-    if kind == IM.IN_PREPARE:
-        return wire.epaxos_encode(21, (L, inst), ballot=(bo, br))
-    values = [(L, v) for v in range(inst + 1, end)] if end else []
-    cmd = command_of(x) if command is None else command
-    kw = dict(command=cmd, sequence_number=tid & 0xff, deps=w, values=values)
-    if kind == IM.IN_COMMIT:
-        return wire.epaxos_encode(20, (L, inst), **kw)
-    return wire.epaxos_encode(WIRE_KIND[kind], (L, inst), ballot=(bo, br), **kw)
 
 
 def parent_way(wire, e, d, frames, to, triple):
